@@ -32,6 +32,7 @@ carries besides the contract fields:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: starts the N ranks itself as a child torch.distributed.run)
+    python bench.py ... --dump-outputs DIR   (also writes the last timed step's HDR image to DIR/hdr.npy)
 """
 import argparse
 import json
@@ -237,6 +238,7 @@ def slim_config(c):
 
 DETAIL_NAME = "bench_detail.json"
 SLIM_LIMIT = 4096
+DUMP_LIMIT = 64 << 20
 
 
 def slim_line(result, detail_path=None):
@@ -287,6 +289,18 @@ def write_detail(result, path=None):
                 f.write("\n")
         except OSError as e:
             print("bench: could not write %s (%s)" % (t, e), file=sys.stderr)
+
+
+def dump_outputs(path, image):
+    """--dump-outputs DIR: the HDR image the timed path left behind in its last step (what a caller of ctx.render receives;
+    rank 0's gathered frame with N > 1) as DIR/hdr.npy, float32, so that two builds can be compared output for output.
+    An image over DUMP_LIMIT bytes (C5: 133 MB) is cut to a fixed, seeded set of whole rows, the same for every run."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(image.cpu().numpy(), np.float32)
+    if img.nbytes > DUMP_LIMIT:
+        rows = np.random.default_rng(0).choice(img.shape[0], DUMP_LIMIT // img[0].nbytes, replace=False)
+        img = img[np.sort(rows)]
+    np.save(os.path.join(path, "hdr.npy"), img)
 
 
 def spawn_ranks(n):
@@ -683,7 +697,11 @@ def main():
                     help="one chain of launches on one stream instead of two overlapping half-batches (A/B)")
     ap.add_argument("--in-order", action="store_true",
                     help="no frames in flight: every step starts after the previous one has finished (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the HDR image of the last timed step to DIR/hdr.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the ranks as a child process.  Nothing above this line has touched the
@@ -907,6 +925,8 @@ def main():
         if world_size > 1:
             torch.cuda.synchronize()
         image = full if world_size > 1 else hdr
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, image)
         paths_per_step = width * height * spp
         ms_per_step = elapsed * 1e3 / args.steps
         alone = None

@@ -74,6 +74,55 @@ def gpu_ctx():
     ctx.close()
 
 
+def flight_helmet_bin(doc, world):
+    """FlightHelmet.bin rebuilt from the packed fixture (tests/golden/flight_helmet.npz): every accessor of the glTF `doc`
+    filled with what the fixture's streams hold (fp16 positions and uvs, snorm10 normals and tangents, u16 indices) as
+    float32 / u16.  The packing is exact on these values, so ingesting the rebuilt buffer gives the fixture's bytes
+    wherever ingesting the shipped one does (tests/golden/make_reference_assets.py checks both on the shipped asset)."""
+    words = np.concatenate(world._buffers[0]).astype(np.uint32)
+    out = bytearray(doc["buffers"][0]["byteLength"])
+
+    def put(accessor, values):
+        a = doc["accessors"][accessor]
+        view = doc["bufferViews"][a["bufferView"]]
+        data = np.ascontiguousarray(values).tobytes()
+        assert view.get("byteStride", len(data) // a["count"]) * a["count"] == len(data) <= view["byteLength"]
+        off = view.get("byteOffset", 0) + a.get("byteOffset", 0)
+        out[off:off + len(data)] = data
+
+    def snorm(w):  # glm::unpackSnorm3x10_1x2: sign-extended 10/10/10/2-bit fields / (511, 511, 511, 1), clamped to -1
+        fields = [(w << np.uint32(22 - s)).view(np.int32) >> 22 for s in (0, 10, 20)] + [w.view(np.int32) >> 30]
+        return np.maximum(np.stack(fields, axis=1).astype(np.float32) / np.array([511, 511, 511, 1], np.float32), np.float32(-1))
+
+    for mesh, md, info in zip(doc["meshes"], world.metadatas, world.mesh_infos):
+        (prim,) = mesh["primitives"]
+        attrs, n = prim["attributes"], info.vertexCount
+        assert md.usesShortIndices == 1 and doc["accessors"][prim["indices"]]["componentType"] == 5123
+        put(prim["indices"], words.view(np.uint16)[md.indicesOffset:md.indicesOffset + info.indexCount])
+        put(attrs["POSITION"], words[md.positionsOffset:md.positionsOffset + 2 * n].view(np.float16).reshape(n, 4)[:, :3].astype(np.float32))
+        put(attrs["NORMAL"], snorm(words[md.normalsOffset:md.normalsOffset + n])[:, :3])
+        put(attrs["TANGENT"], snorm(words[md.tangentsOffset:md.tangentsOffset + n]))
+        put(attrs["TEXCOORD_0"], words[md.texCoord0sOffset:md.texCoord0sOffset + n].view(np.float16).reshape(n, 2).astype(np.float32))
+    return bytes(out)
+
+
+@pytest.fixture(scope="session")
+def flight_helmet_gltf(tmp_path_factory):
+    """The reference's FlightHelmet glTF asset in a temporary directory; the path of its .gltf.  From
+    tests/golden/flight_helmet_gltf.tar.xz: the .gltf as shipped and its images reduced to 64 x 64
+    (tests/golden/make_reference_assets.py); the .bin (3.4 MB) rebuilt from tests/golden/flight_helmet.npz."""
+    import json
+    import lzma
+    import tarfile
+    from prosper_amd import flight_helmet
+    d = tmp_path_factory.mktemp("flight_helmet_gltf")
+    with lzma.open(os.path.join(ROOT, "tests", "golden", "flight_helmet_gltf.tar.xz")) as f, tarfile.open(fileobj=f) as tar:
+        tar.extractall(d, filter="data")
+    doc = json.loads((d / "FlightHelmet.gltf").read_text())
+    (d / doc["buffers"][0]["uri"]).write_bytes(flight_helmet_bin(doc, flight_helmet.load_fixture(sky_size=0)))
+    return str(d / "FlightHelmet.gltf")
+
+
 @pytest.fixture(scope="session")
 def cornell_world():
     from prosper_amd import scenes

@@ -38,10 +38,36 @@ def test_slim_line_of_a_full_result_stays_under_4_kb():
     assert len(text) < 4096 and "roofline" in json.loads(text) and "cpu_baseline" in json.loads(text)
 
 
+def test_dumped_outputs_stay_under_the_limit_and_do_not_vary(tmp_path):
+    """--dump-outputs: an image that fits is written whole; a larger one (C5's 3840 x 2160 frame) as the same seeded rows
+    in every run, under 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "hdr.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.arange(2160, dtype=torch.float32)[:, None, None].expand(2160, 3840, 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    b, c = np.load(tmp_path / "b" / "hdr.npy"), np.load(tmp_path / "c" / "hdr.npy")
+    assert b.nbytes <= 64 << 20 and b.shape[1:] == (3840, 4) and b.shape[0] > 1000 and np.array_equal(b, c)
+    rows = b[:, 0, 0]
+    assert (np.diff(rows) > 0).all() and (b == rows[:, None, None]).all()  # whole rows, in image order
+
+
+def test_steps_below_one_are_refused():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=120, cwd=ROOT)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
 @pytest.mark.gpu
 def test_bench_json_line_has_the_contract_fields(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2",
-                          "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "exactly one line on stdout"
@@ -57,6 +83,11 @@ def test_bench_json_line_has_the_contract_fields(tmp_path):
     assert d["scaling"] == "strong" and d["vs_baseline"] is None and d["dtype"] == "f32" and d["data"] == "synthetic"
     assert "workload" in d["config"] and "model" not in d["config"]
     assert d["value"] > 0 and d["ms_per_step"] > 0
+    # the dumped output is the image of the timed path: c1's 256 x 256 frame, the radiance the line reports
+    import numpy as np
+    hdr = np.load(tmp_path / "out" / "hdr.npy")
+    assert hdr.dtype == np.float32 and hdr.shape == (256, 256, 4)
+    assert float(hdr[..., :3].mean()) == pytest.approx(d["mean_radiance"], rel=1e-4) and (hdr[..., 3] == 1).all()
     # value = paths of one step / time per step
     paths = d["config"]["width"] * d["config"]["height"] * d["config"]["spp"]
     assert abs(d["value"] - paths / d["ms_per_step"] / 1e3) <= 1e-4 * d["value"]  # (the line carries 5 significant digits)

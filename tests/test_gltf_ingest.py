@@ -1,6 +1,6 @@
 """glTF -> World ingest (prosper_amd/gltf.py) against a hand-made fixture whose expected tables
 are derived here from the reference's conventions (file:line in the assertions), plus the reference's own
-FlightHelmet asset when /root/reference is mounted (CPU container only; it cannot travel to the GPU box)."""
+FlightHelmet asset (tests/golden/flight_helmet_gltf.tar.xz)."""
 import math
 import os
 
@@ -11,7 +11,6 @@ from prosper_amd import gltf, structs as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TINY = os.path.join(HERE, "golden", "tiny_scene.gltf")
-FLIGHT_HELMET = "/root/reference/res/glTF/FlightHelmet/glTF/FlightHelmet.gltf"
 
 
 @pytest.fixture(scope="module")
@@ -144,10 +143,9 @@ def test_tiny_scene_renders_on_the_oracle(oracle, tiny):
     assert np.isfinite(rad).all() and rad[..., :3].max() > 0.0
 
 
-@pytest.mark.skipif(not os.path.exists(FLIGHT_HELMET), reason="the reference's sample asset is only mounted in the CPU container")
-def test_flight_helmet_tables(oracle):
+def test_flight_helmet_tables(oracle, flight_helmet_gltf):
     from conftest import default_pc
-    w = gltf.load_gltf(FLIGHT_HELMET)
+    w = gltf.load_gltf(flight_helmet_gltf)
     assert w.triangle_count() == 94722
     assert len(w.materials) == 6 and len(w.textures) == 16 and len(w.samplers) == 1
     assert len(w.missing_images) == 5  # the checkout carries 10 of the 15 images

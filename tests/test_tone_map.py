@@ -1,6 +1,6 @@
 """Tone map, the step after the path: oracle.c ora_tone_map against an independent NumPy float64
-evaluation of res/shader/tone_map.comp, the DDS reader on the reference's LUT (CPU container only), and - with
--m gpu - the HIP kernel against the oracle through the C-ABI, bit for bit."""
+evaluation of res/shader/tone_map.comp, the DDS reader on the reference's LUT (tests/golden/tony_mc_mapface.dds.xz), and
+- with -m gpu - the HIP kernel against the oracle through the C-ABI, bit for bit."""
 import os
 
 import numpy as np
@@ -8,7 +8,15 @@ import pytest
 
 from prosper_amd import dds, scenes, structs as S
 
-LUT_PATH = "/root/reference/res/texture/tony_mc_mapface.dds"
+
+@pytest.fixture(scope="module")
+def reference_lut_path(tmp_path_factory):
+    """res/texture/tony_mc_mapface.dds, byte for byte (tests/golden/make_reference_assets.py)."""
+    import lzma
+    path = tmp_path_factory.mktemp("lut") / "tony_mc_mapface.dds"
+    with lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tony_mc_mapface.dds.xz")) as f:
+        path.write_bytes(f.read())
+    return str(path)
 
 
 def synthetic_lut(dim=48, seed=3):
@@ -92,9 +100,8 @@ def test_oracle_tone_map_matches_float64_evaluation(oracle, exposure, contrast):
     assert diff.max() <= 1.0 and (diff > 0).mean() < 0.02
 
 
-@pytest.mark.skipif(not os.path.exists(LUT_PATH), reason="the reference's LUT is only mounted in the CPU container")
-def test_reads_the_reference_lut(oracle):
-    lut = dds.read_lut(LUT_PATH)
+def test_reads_the_reference_lut(oracle, reference_lut_path):
+    lut = dds.read_lut(reference_lut_path)
     assert lut.shape == (48, 48, 48)
     rgb = dds.decode_r9g9b9e5(lut)
     assert rgb[0, 0, 0].max() < 0.02 and 0.9 < rgb[-1, -1, -1].min() <= 1.01  # black stays black, white ~ white
@@ -159,13 +166,13 @@ def test_gpu_tone_map_edge_values_and_errors(gpu_ctx, oracle, cornell_world):
         ctx.close()
 
 
-def test_dds_lut_write_read_round_trip(tmp_path):
+def test_dds_lut_write_read_round_trip(tmp_path, reference_lut_path):
     lut = synthetic_lut(12)
     p = tmp_path / "lut.dds"
     dds.write_lut(str(p), lut)
     assert np.array_equal(dds.read_lut(str(p)), lut)
-    if os.path.exists(LUT_PATH):  # same header fields as the reference's file
-        assert open(LUT_PATH, "rb").read(148)[76:92] == p.read_bytes()[76:92]
+    # same header fields as the reference's file
+    assert open(reference_lut_path, "rb").read(148)[76:92] == p.read_bytes()[76:92]
 
 
 @pytest.mark.gpu
