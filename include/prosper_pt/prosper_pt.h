@@ -71,9 +71,10 @@ typedef struct prosper_pt_device_desc
 enum
 {
     /* Default pipeline: wavefront stage kernels (generate+extend / shade / shadow / extend /
-     * accumulate) with per-wave ballot compaction.  The two alternatives produce the same pixels
-     * and are kept for A/B timing: MEGAKERNEL = one lane per pixel runs whole paths,
-     * PERSISTENT = resident waves that regenerate finished paths from a global counter. */
+     * accumulate) with per-wave ballot compaction.  MEGAKERNEL = one lane per pixel runs whole
+     * paths: the same pixels, kept for A/B timing.
+     * PERSISTENT is reserved (a removed experiment): prosper_pt_create refuses it with
+     * PROSPER_PT_ERR_UNSUPPORTED. */
     PROSPER_PT_CREATE_MEGAKERNEL = 1u << 0,
     PROSPER_PT_CREATE_PERSISTENT = 1u << 1,
     /* run the wavefront pipeline as ONE chain of launches on the caller's stream instead of two
@@ -249,7 +250,7 @@ enum
     PROSPER_PT_VARIANT_LDS_TABLES = 1u << 1,      /* wf_shade stages instances/transforms/materials/lights in LDS */
     PROSPER_PT_VARIANT_BATCHED_TEXTURES = 1u << 2, /* the twelve texel loads of a hit issued together */
     PROSPER_PT_VARIANT_TEXTURE_PACKS = 1u << 3,  /* some material's base / MR / normal texels are interleaved per texel */
-    PROSPER_PT_VARIANT_RAW_RECORDS = 1u << 4,    /* 64-byte raw shading records decoded per hit (debug option rawRecords: an experiment) */
+    PROSPER_PT_VARIANT_RAW_RECORDS = 1u << 4,    /* reserved: never set */
     PROSPER_PT_VARIANT_STACK_SHIFT = 8,           /* bits 8..15: LDS traversal-stack entries (16/24/32) */
 };
 
@@ -309,20 +310,20 @@ typedef struct prosper_pt_debug_options
     float rebuildCostRatio;    /* 0: 1.3 - growth of the tree's surface-area measure at which an update also rebuilds */
     uint32_t alwaysRebuild;    /* rebuild with every update, synchronously */
     uint32_t failNextUpdate;   /* the next host-side rebuild fails (the recovery test); cleared by that failure */
-    /* ---- measured-slower experiments: only in a library built with -DPPT_EXPERIMENTS (prosper_pt_has_experiments);
-     *      setting any of them in the default build fails with PROSPER_PT_ERR_UNSUPPORTED ---- */
-    uint32_t poolVariant;      /* wf_trace out of an LDS ray pool (1, 2, 3) */
-    uint32_t rawRecords;       /* 64-byte raw shading records decoded per hit (upload) */
-    uint32_t tileOrder;        /* camera-ray batches take the tiles by the cost of a probe ray */
-    uint32_t hipGraph;         /* a pipelined render's chain of launches through a HIP graph */
-    uint32_t pipelinedChains;  /* 2: a frame in flight runs as two chains */
-    uint32_t mergeLimit;       /* a workgroup's four segments traced by one wave below this many rays */
+    /* ---- reserved: the switches of removed experiments.  They must be 0: a nonzero value fails with
+     *      PROSPER_PT_ERR_UNSUPPORTED (prosper_pt_set_debug_options, and prosper_pt_create through
+     *      PROSPER_PT_DEBUG_OPTIONS) ---- */
+    uint32_t poolVariant;
+    uint32_t rawRecords;
+    uint32_t tileOrder;
+    uint32_t hipGraph;
+    uint32_t pipelinedChains;
+    uint32_t mergeLimit;
 } prosper_pt_debug_options;
 
 const char *prosper_pt_last_error(void);
 uint32_t prosper_pt_abi_version(void);
-/* 1 when the library was built with -DPPT_EXPERIMENTS (the measured-slower kernel variants are compiled in), else 0.
- * In the default build PROSPER_PT_CREATE_PERSISTENT is refused by prosper_pt_create as well. */
+/* Always 0: the measured-slower kernel variants this reported on were removed from the library. */
 uint32_t prosper_pt_has_experiments(void);
 void prosper_pt_debug_options_default(prosper_pt_debug_options *out);
 int prosper_pt_set_debug_options(prosper_pt_ctx *ctx, const prosper_pt_debug_options *options);

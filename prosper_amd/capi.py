@@ -13,7 +13,7 @@ from . import structs as S
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROSPER_PT_LIB (read by this BINDING, i.e. by tests and measurement scripts - the library itself never looks): another
-# build of the library, e.g. libprosper_pt_experiments.so (make -C prosper_amd/csrc EXPERIMENTS=1)
+# build of the library, e.g. a tuning variant of scripts/build_variant.sh
 LIB_PATH = os.environ.get("PROSPER_PT_LIB") or os.path.join(_HERE, "libprosper_pt.so")
 
 
@@ -169,7 +169,8 @@ def _tile_ref(tile):
 
 
 def has_experiments():
-    """True when the loaded library was built with -DPPT_EXPERIMENTS (the measured-slower variants are compiled in)."""
+    """prosper_pt_has_experiments: always False (the measured-slower variants were removed from the library); kept for the
+    ABI and for tests/conftest.py."""
     return bool(lib().prosper_pt_has_experiments())
 
 

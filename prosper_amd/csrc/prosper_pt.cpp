@@ -96,8 +96,6 @@ WavefrontOptions wavefront_options(const prosper_pt_ctx *ctx)
     o.ldsStackEntries = d.ldsStackEntries;
     o.noLdsScene = d.noLdsScene != 0;
     o.noLdsTables = d.noLdsTables != 0;
-    o.poolVariant = d.poolVariant;
-    o.hipGraph = d.hipGraph != 0;
     return o;
 }
 
@@ -435,10 +433,8 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     }
 
     if ((rc = finish_geometry(ctx, target, job))) return rc;
-    ctx->rawRecords = target.rawRecords;
     ctx->stats.deviceBytes = ctx->sceneBytes;
     ctx->stats.alphaBoundBytes = ctx->alphaBoundBytes;
-    ctx->sceneStamp++;
     ctx->stats.textureSeconds = textureSeconds;
     ctx->stats.uploadSeconds = seconds_since(tUpload);
     return PROSPER_PT_OK;
@@ -634,16 +630,15 @@ uint32_t compute_local_width(uint32_t width, const prosper_pt_tile_desc *tile)
 
 int check_debug_options(const prosper_pt_debug_options &o)
 {
-#ifndef PPT_EXPERIMENTS
+    // the reserved fields (prosper_pt.h): the removed experiments
     if (o.poolVariant || o.rawRecords || o.tileOrder || o.hipGraph || o.pipelinedChains || o.mergeLimit)
-        return fail(PROSPER_PT_ERR_UNSUPPORTED, "debug options: an experiment was requested, but the library was built without -DPPT_EXPERIMENTS");
-#endif
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "debug options: poolVariant, rawRecords, tileOrder, hipGraph, pipelinedChains and mergeLimit are reserved and must be 0");
     if (o.ldsStackEntries != 0u && o.ldsStackEntries != 16u && o.ldsStackEntries != 24u && o.ldsStackEntries != 32u)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "debug options: ldsStackEntries is 0, 16, 24 or 32");
     if (o.segmentLength != 0u && (o.segmentLength < 64u || o.segmentLength > 8192u || o.segmentLength % 64u != 0u))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "debug options: segmentLength is a multiple of 64 in [64, 8192]");
     if (o.chains > kMaxChains) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "debug options: at most three launch chains");
-    if (o.leafSize > 8u || o.alphaCellShift > 15 || o.nodeOrder > 2 || o.poolVariant > 3u)
+    if (o.leafSize > 8u || o.alphaCellShift > 15 || o.nodeOrder > 2)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "debug options: a value is out of range");
     if (!(o.sahTraversalCost >= 0.0f) || !(o.boxPad >= 0.0f) || !(o.rebuildCostRatio >= 0.0f))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "debug options: a coefficient is negative or NaN");
@@ -715,14 +710,17 @@ bool parse_debug_options(const char *text, prosper_pt_debug_options *out, std::s
     return true;
 }
 
-bool debug_options_from_environment(prosper_pt_debug_options *out, std::string *err)
+// false with the message in *err and the error code in *code (the reserved fields fail as through
+// prosper_pt_set_debug_options, everything else as an invalid argument)
+bool debug_options_from_environment(prosper_pt_debug_options *out, std::string *err, int *code)
 {
     const char *gate = std::getenv("PROSPER_PT_DEBUG");
     if (!gate || std::strcmp(gate, "1") != 0) return true;
     const char *text = std::getenv("PROSPER_PT_DEBUG_OPTIONS");
     if (!text) return true;
+    *code = PROSPER_PT_ERR_INVALID_ARGUMENT;
     if (!parse_debug_options(text, out, err)) return false;
-    if (check_debug_options(*out) != PROSPER_PT_OK)
+    if ((*code = check_debug_options(*out)) != PROSPER_PT_OK)
     {
         *err = ppt::g_lastErrorStorage;
         return false;
@@ -737,14 +735,7 @@ extern "C" {
 const char *prosper_pt_last_error(void) { return ppt::g_lastErrorStorage.c_str(); }
 uint32_t prosper_pt_abi_version(void) { return PROSPER_PT_ABI_VERSION; }
 
-uint32_t prosper_pt_has_experiments(void)
-{
-#ifdef PPT_EXPERIMENTS
-    return 1u;
-#else
-    return 0u;
-#endif
-}
+uint32_t prosper_pt_has_experiments(void) { return 0u; }
 
 void prosper_pt_debug_options_default(prosper_pt_debug_options *out)
 {
@@ -792,10 +783,8 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     PPT_HIP(hipGetDeviceProperties(&prop, desc->device_ordinal));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PROSPER_PT_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library carries gfx950 code only");
-#ifndef PPT_EXPERIMENTS
     if (desc->flags & PROSPER_PT_CREATE_PERSISTENT)
-        return fail(PROSPER_PT_ERR_UNSUPPORTED, "the persistent pipeline is an experiment: build the library with -DPPT_EXPERIMENTS");
-#endif
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "PROSPER_PT_CREATE_PERSISTENT is reserved: the persistent pipeline was removed");
     prosper_pt_ctx *ctx = new (std::nothrow) prosper_pt_ctx();
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     ctx->device = desc->device_ordinal;
@@ -804,10 +793,11 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     {
         // the ONE place the library looks at the environment, and only when asked to (prosper_pt.h, debug options)
         std::string err;
-        if (!debug_options_from_environment(&ctx->debug, &err))
+        int code = PROSPER_PT_OK;
+        if (!debug_options_from_environment(&ctx->debug, &err, &code))
         {
             delete ctx;
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, err);
+            return fail(code, err);
         }
     }
     bool eventsOk = true;
@@ -830,8 +820,7 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     for (auto &ws : ctx->workStreams)
         eventsOk = eventsOk && ws && hipEventRecord(ctx->chainFork, ws) == hipSuccess && hipStreamSynchronize(ws) == hipSuccess;
     if (!eventsOk || hipMalloc((void **)&ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&ctx->dWorkCounter, 64) != hipSuccess)
+        hipMemset(ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess)
     {
         prosper_pt_destroy(ctx);
         return fail(PROSPER_PT_ERR_HIP, "context allocation failed");
@@ -850,12 +839,10 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     free_scene(ctx);
     if (ctx->ownedHdr) (void)hipFree(ctx->ownedHdr);
     if (ctx->dCounters) (void)hipFree(ctx->dCounters);
-    if (ctx->dWorkCounter) (void)hipFree(ctx->dWorkCounter);
     for (RenderSlot &slot : ctx->slots)
     {
         if (slot.wfBlock) (void)hipFree(slot.wfBlock);
         if (slot.stackOverflow) (void)hipFree(slot.stackOverflow);
-        if (slot.tileOrder) (void)hipFree(slot.tileOrder);
     }
     if (ctx->restirScratch) (void)hipFree(ctx->restirScratch);
     if (ctx->toneLut) (void)hipFree(ctx->toneLut);
@@ -873,8 +860,6 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
         if (slot.free) (void)hipEventDestroy(slot.free);
     }
     for (auto &ws : ctx->workStreams)
-        if (ws) (void)hipStreamDestroy(ws);
-    for (auto &ws : ctx->extraStreams)
         if (ws) (void)hipStreamDestroy(ws);
     if (ctx->buildStream) (void)hipStreamDestroy(ctx->buildStream);
     if (ctx->pinnedStaging) (void)hipHostFree(ctx->pinnedStaging);
@@ -1018,7 +1003,6 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
     if (rc != PROSPER_PT_OK) return rc;
     acc->stale = false;
     acc->rebuilds++;
-    ctx->sceneStamp++;
     ctx->stats.nodeCount = bvh.nodes.size();
     ctx->stats.maxDepth = bvh.maxDepth;
     ctx->stats.deviceBytes = ctx->sceneBytes;
@@ -1107,7 +1091,6 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
     ctx->dTransforms = acc->dTransformsV[v];
     ctx->scene = next;
     acc->refits++;
-    ctx->sceneStamp++;
     acc->pending = false;
     acc->stale = false;
     return PROSPER_PT_OK;
@@ -1264,7 +1247,7 @@ int prosper_pt_get_scene_stats(prosper_pt_ctx *ctx, prosper_pt_scene_stats *out)
     out->variantFlags =
         (plan.sceneInLds ? PROSPER_PT_VARIANT_LDS_SCENE : 0u) | (plan.tablesInLds ? PROSPER_PT_VARIANT_LDS_TABLES : 0u) |
         (ctx->scene.batchedTextures ? PROSPER_PT_VARIANT_BATCHED_TEXTURES : 0u) |
-        (ctx->packedMaterials ? PROSPER_PT_VARIANT_TEXTURE_PACKS : 0u) | (ctx->rawRecords ? PROSPER_PT_VARIANT_RAW_RECORDS : 0u) |
+        (ctx->packedMaterials ? PROSPER_PT_VARIANT_TEXTURE_PACKS : 0u) |
         (ldsEntries << PROSPER_PT_VARIANT_STACK_SHIFT);
     return PROSPER_PT_OK;
 }
@@ -1389,9 +1372,6 @@ int prosper_pt_render_frames(
     p.localWidth = localWidth;
     p.frameCount = frame_count;
     p.traceDeadPaths = ctx->debug.traceDeadPaths ? 1u : 0u;
-    // sparse segments (pt_wavefront.hip RayMap), an experiment that lost (profiles/r03_sparse_segments.txt): debug option
-    // mergeLimit = rays up to which a workgroup's four segments are traced by one wave; default never
-    p.mergeLimit = ctx->debug.mergeLimit;
 
     if (localWidth == 0) return PROSPER_PT_OK;
     const bool countWork = (render_flags & PROSPER_PT_RENDER_COUNT_WORK) != 0;
@@ -1402,7 +1382,7 @@ int prosper_pt_render_frames(
     LaunchTimer *tp = ctx->kernelTiming ? &timer : nullptr;
     // a staged prosper_pt_update_transforms runs now, on the stream this render's path stages use: a pipelined render's own
     // chain (beside the frames in flight, which keep reading their scene version), else the caller's stream
-    const bool wavefrontPipelined = !(ctx->flags & (PROSPER_PT_CREATE_MEGAKERNEL | PROSPER_PT_CREATE_PERSISTENT)) &&
+    const bool wavefrontPipelined = !(ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL) &&
                                     (render_flags & PROSPER_PT_RENDER_PIPELINED) != 0 && !countWork;
     {
         const uint32_t nextSlot = wavefrontPipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
@@ -1427,18 +1407,6 @@ int prosper_pt_render_frames(
         launch_render_megakernel(ctx->scene, p, ctx->hdr, ctx->dCounters, ovf, countWork, s);
         release_slot(ctx->slots[0], s);
     }
-#ifdef PPT_EXPERIMENTS
-    else if (ctx->flags & PROSPER_PT_CREATE_PERSISTENT)
-    {
-        int32_t *ovf = nullptr;
-        const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, persistent_grid_blocks(), s, &ovf);
-        if (orc != PROSPER_PT_OK) return orc;
-        wait_for_slot(ctx->slots[0], s);
-        if (tp) tp->mark(kStageGenerate, s);
-        launch_render_persistent(ctx->scene, p, ctx->hdr, ctx->dCounters, ctx->dWorkCounter, ovf, countWork, s);
-        release_slot(ctx->slots[0], s);
-    }
-#endif
     else
     {
         // wavefront: all frames of the batch are in flight together, in chunks that keep the
@@ -1459,29 +1427,15 @@ int prosper_pt_render_frames(
         const uint32_t slotIndex = pipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
         RenderSlot &slot = ctx->slots[slotIndex];
         ctx->lastSlot = slotIndex;
-#ifdef PPT_EXPERIMENT_MESH_STREAMS_AFTER_FIRST_RENDER // (A/B: does the worker's stream cost anything once it shares a queue?)
-        (void)ensure_build_stream(ctx);
-#endif
         WavefrontChains chains;
         LaunchTimer chainTimers[kMaxChains];
         chains.count = (pipelined || (ctx->flags & PROSPER_PT_CREATE_SINGLE_CHAIN)) ? 1u : 2u;
         if (!pipelined && ctx->debug.chains >= 1u && ctx->debug.chains <= kMaxChains) chains.count = ctx->debug.chains; // tuning hook (in-order mode)
-        // experiment (profiles/r03_hip_graph.txt, "two chains per frame in flight"): debug option pipelinedChains = 2 splits a
-        // pipelined frame's segment groups over two chains, the second on a stream of its own
-        bool twoDetached = false;
-#ifdef PPT_EXPERIMENTS
-        if (pipelined && ctx->debug.pipelinedChains == 2u)
-        {
-            if (!ctx->extraStreams[slotIndex]) PPT_HIP(hipStreamCreateWithFlags(&ctx->extraStreams[slotIndex], hipStreamNonBlocking));
-            twoDetached = true;
-            chains.count = 2u;
-        }
-#endif
         chains.detached = pipelined;
         chains.fork = ctx->chainFork;
         for (uint32_t i = 0; i < kMaxChains; ++i)
         {
-            chains.streams[i] = pipelined ? ((twoDetached && i == 1u) ? ctx->extraStreams[slotIndex] : ctx->workStreams[slotIndex]) : ctx->workStreams[i];
+            chains.streams[i] = pipelined ? ctx->workStreams[slotIndex] : ctx->workStreams[i];
             chains.join[i] = slot.chainJoin[i];
             chainTimers[i].events = slot.chainEvents[i];
             chainTimers[i].stage = slot.chainStage[i];
@@ -1511,52 +1465,6 @@ int prosper_pt_render_frames(
             int32_t *ovf = nullptr;
             const int orc = ensure_scratch_dwords(ctx, slot, plan.scratchDwordsPerBlock, wavefront_grid_blocks(w), s, &ovf);
             if (orc != PROSPER_PT_OK) return orc;
-            w.tileOrder = nullptr;
-#ifdef PPT_EXPERIMENTS
-            // EXPERIMENT (debug option tileOrder; measured slower, profiles/r03_tile_order.txt): the camera-ray batches
-            // take the tiles by cost, heaviest first, so that every segment's stride through the sequence gets the same mix;
-            // recomputed when the view or the geometry changed since this slot's last order
-            const bool tileOrderExperiment = ctx->debug.tileOrder != 0;
-            if (frames >= 4u && tileOrderExperiment)
-            {
-                const size_t tiles = (size_t)tilesX * tilesY;
-                RenderSlot::OrderKey key = {};
-                std::memcpy(key.camera, pp.eye, sizeof(float) * 12);
-                key.camera[12] = pp.aspect;
-                key.camera[13] = pp.tanHalfFovY;
-                key.width = pp.width;
-                key.height = pp.height;
-                key.stripeWidth = pp.stripeWidth;
-                key.stripeIndex = pp.stripeIndex;
-                key.stripeCount = pp.stripeCount;
-                key.localWidth = pp.localWidth;
-                key.sceneStamp = ctx->sceneStamp;
-                hipStream_t os = pipelined ? ctx->workStreams[slotIndex] : s;
-                if (slot.tileOrderTiles < tiles)
-                {
-                    PPT_HIP(hipDeviceSynchronize());
-                    if (slot.tileOrder) PPT_HIP(hipFree(slot.tileOrder));
-                    slot.tileOrder = nullptr;
-                    slot.tileOrderTiles = 0;
-                    PPT_HIP(hipMalloc((void **)&slot.tileOrder, (2 * tiles + 512) * sizeof(uint32_t)));
-                    slot.tileOrderTiles = tiles;
-                    slot.orderValid = false;
-                }
-                if (!slot.orderValid || std::memcmp(&key, &slot.orderKey, sizeof(key)) != 0)
-                {
-                    // behind the slot's previous user (it reads the old order) and behind a refit on another stream
-                    if (pipelined && slot.freeRecorded) PPT_HIP(hipStreamWaitEvent(os, slot.free, 0));
-                    if (!pipelined) wait_for_slot(slot, s);
-                    if (pipelined && ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(os, ctx->accel->sceneEvent, 0));
-                    launch_tile_order(
-                        ctx->scene, pp, tilesX, tilesY, plan.ldsStackEntries, ovf, slot.tileOrder, slot.tileOrder + slot.tileOrderTiles, os);
-                    PPT_HIP(hipGetLastError());
-                    slot.orderKey = key;
-                    slot.orderValid = true;
-                }
-                w.tileOrder = slot.tileOrder;
-            }
-#endif
             // the slot's previous user (a render of two calls ago, or the previous chunk of this one) must be done
             // with the workspace: detached chains wait for that on their own stream, the others on the caller's
             chains.after = slot.freeRecorded ? slot.free : nullptr;

@@ -283,8 +283,6 @@ struct prosper_pt_ctx
     ppt::DeviceScene scene = {};
     prosper_pt_scene_stats stats = {};
     uint32_t packedMaterials = 0; // materials whose three textures are interleaved (MaterialPack)
-    bool rawRecords = false;      // the scene keeps 64-byte raw shading records (RawShadeTriangle)
-    uint64_t sceneStamp = 0;      // bumped whenever the geometry the rays see changes (upload, refit, rebuild)
     uint64_t alphaTriangleCount = 0, alphaBoundBytes = 0; // any-hit records and bytes of alpha bounds (AlphaMaterial)
     // light buffers are re-uploaded every frame in prosper; keep their device addresses mutable
     ppt::LightState *lights = nullptr; // the scene's light buffers (device copies in the scene's allocation list)
@@ -310,7 +308,6 @@ struct prosper_pt_ctx
     uint32_t localWidth = 0, height = 0;
 
     unsigned long long *dCounters = nullptr; // kStageCount x 16 u64: one block of work counters per kernel stage
-    uint32_t *dWorkCounter = nullptr;        // work-distribution counter of the persistent kernel
     // wavefront workspace (one allocation, carved into the WavefrontBuffers arrays)
     // global overflow of the traversal stacks (only for trees whose stack bound exceeds the LDS stack)
     uint64_t wfSlots = 0;
@@ -345,16 +342,6 @@ struct prosper_pt_ctx
         uint32_t chainLaunches[ppt::kMaxChains] = {};
         hipEvent_t free = nullptr; // recorded after the accumulate kernel of the slot's last render
         bool freeRecorded = false;
-        // tiles by the cost of a probe ray (pt_wavefront.hip "tile order"), valid for the view in `orderKey`
-        uint32_t *tileOrder = nullptr; // [tiles] + scratch [tiles + 512]
-        size_t tileOrderTiles = 0;
-        struct OrderKey
-        {
-            float camera[14];
-            uint32_t width, height, stripeWidth, stripeIndex, stripeCount, localWidth;
-            uint64_t sceneStamp;
-        } orderKey = {};
-        bool orderValid = false;
     };
     // prosper keeps two frames in flight; a third one fills the machine better at the batch sizes of a multi-GPU
     // rank share (1/4 share 0.71 -> 0.66 ms, C3 19.3 -> 18.9 ms; profiles/r01_pipelined.txt)
@@ -363,8 +350,6 @@ struct prosper_pt_ctx
     // share queues and serialise): a pipelined render's chain runs on workStreams[slot], the two chains of an
     // in-order render on workStreams[0] and [1].  All ordering between them goes through events.
     hipStream_t workStreams[kRenderSlots] = {};
-    // experiment (debug option pipelinedChains = 2): a second chain per frame in flight; created on first use
-    hipStream_t extraStreams[kRenderSlots] = {};
     RenderSlot slots[kRenderSlots];
     uint32_t lastSlot = 0;  // of the last render
     uint32_t timedSlot = 0; // of the last render that ran with kernel timing on (timing readout)

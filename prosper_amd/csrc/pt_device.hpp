@@ -9,13 +9,6 @@ namespace ppt
 {
 
 #define PPT_D __device__ __forceinline__
-// 64-byte raw shading records (pt_scene.hpp RawShadeTriangle): an experiment that lost (profiles/r03_raw_records.txt),
-// compiled in only with -DPPT_EXPERIMENTS
-#ifdef PPT_EXPERIMENTS
-#define PPT_RAW_RECORDS(s) ((s).rawShadeTriangles != nullptr)
-#else
-#define PPT_RAW_RECORDS(s) false
-#endif
 
 constexpr uint32_t kMissIndex = 0xFFFFFFFFu; // rt/reference/main.rgen:47
 
@@ -1177,8 +1170,7 @@ PPT_D uint32_t any_hit_settle(
         cnt.anyHitCalls++;
         const uint32_t di = s.alphaTriangles[alphaIndex].drawInstance, prim = s.alphaTriangles[alphaIndex].primitive;
         const uint32_t record = s.triangleOffsets[di] + prim;
-        const uint32_t recordFlags = PPT_RAW_RECORDS(s) ? s.rawShadeTriangles[record].flags : s.shadeTriangles[record].flags;
-        cnt.shortIndexHits += (recordFlags & kTriFlagShortIndices) ? 1u : 0u;
+        cnt.shortIndexHits += (s.shadeTriangles[record].flags & kTriFlagShortIndices) ? 1u : 0u;
     }
     if (texelBits == 0ull) return alpha_verdict(fp.mode, 1.0f, fp.factorA, fp.cutoff, fp.u) ? kAlphaAccept : kAlphaReject;
 
@@ -1322,7 +1314,6 @@ struct TraversalStack
     // all three - the LDS part nearly always has room for three more - instead of one per push
     PPT_D void push_hit_children(int32_t &sp, const float e[4], const int32_t ref[4]) const
     {
-#ifndef PPT_EXPERIMENT_PUSH_EACH
         if (ldsOnly || (uint32_t)sp + 3u <= cap)
         {
             if (e[3] < kInf) lds[(uint32_t)(sp++) * ldsStride] = ref[3];
@@ -1330,7 +1321,6 @@ struct TraversalStack
             if (e[1] < kInf) lds[(uint32_t)(sp++) * ldsStride] = ref[1];
             return;
         }
-#endif
         if (e[3] < kInf) push(sp, ref[3]);
         if (e[2] < kInf) push(sp, ref[2]);
         if (e[1] < kInf) push(sp, ref[1]);
@@ -1453,27 +1443,7 @@ struct GlobalGeom
     PPT_D NodeData node(int32_t i) const
     {
         const uint4 *np = reinterpret_cast<const uint4 *>(nodes + i);
-#ifdef PPT_EXPERIMENT_SPLIT_NODE_LOADS
-        // measurement only (scripts/build_variant.sh split -DPPT_EXPERIMENT_SPLIT_NODE_LOADS): the same 80 bytes as ten
-        // 8-byte loads - twice the cache accesses, same lines (profiles/r02_gather_microbench.txt)
-        typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-        u32x2v h[10];
-        asm volatile("global_load_dwordx2 %0, %10, off\n\tglobal_load_dwordx2 %1, %10, off offset:8\n\t"
-                     "global_load_dwordx2 %2, %10, off offset:16\n\tglobal_load_dwordx2 %3, %10, off offset:24\n\t"
-                     "global_load_dwordx2 %4, %10, off offset:32\n\tglobal_load_dwordx2 %5, %10, off offset:40\n\t"
-                     "global_load_dwordx2 %6, %10, off offset:48\n\tglobal_load_dwordx2 %7, %10, off offset:56\n\t"
-                     "global_load_dwordx2 %8, %10, off offset:64\n\tglobal_load_dwordx2 %9, %10, off offset:72\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(h[0]), "=&v"(h[1]), "=&v"(h[2]), "=&v"(h[3]), "=&v"(h[4]), "=&v"(h[5]), "=&v"(h[6]),
-                       "=&v"(h[7]), "=&v"(h[8]), "=&v"(h[9])
-                     : "v"(np)
-                     : "memory");
-        return NodeData{uint4{h[0].x, h[0].y, h[1].x, h[1].y}, uint4{h[2].x, h[2].y, h[3].x, h[3].y},
-                        uint4{h[4].x, h[4].y, h[5].x, h[5].y}, uint4{h[6].x, h[6].y, h[7].x, h[7].y},
-                        uint4{h[8].x, h[8].y, h[9].x, h[9].y}};
-#else
         return NodeData{np[0], np[1], np[2], np[3], np[4]};
-#endif
     }
     template <bool SORTED>
     PPT_D void test_node(int32_t i, f3 o, const RaySlabs &rs, float tMin, float tMax, float e[4], int32_t ref[4]) const
@@ -1566,7 +1536,6 @@ constexpr uint32_t kLdsSceneFloat4s = 768; // 12 KB
 PPT_D bool descend_any(const float e[4], const int32_t ref[4], const TraversalStack &stack, int32_t &sp, int32_t &node)
 {
     bool found = false;
-#ifndef PPT_EXPERIMENT_PUSH_EACH
     if (stack.ldsOnly || (uint32_t)sp + 3u <= stack.cap) // one capacity test for the (at most three) pushes of this visit
     {
 #pragma unroll
@@ -1583,7 +1552,6 @@ PPT_D bool descend_any(const float e[4], const int32_t ref[4], const TraversalSt
             }
         return found;
     }
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (e[k] < kInf)
@@ -1710,51 +1678,25 @@ PPT_D f3 mapped_normal(f3 tsn, f3 normal, f3 tangent, float sgn)
 template <bool COUNT, bool BATCHED_TEXTURES = false>
 PPT_D Surface evaluate_surface(const DeviceScene &s, f3 rayDir, const Hit &hit, LaneCounters &cnt)
 {
-    // loadVertexThroughIndexBuffer x 3 (geometry.glsl:220-244) from the triangle's record: decoded at upload (128 B), or
-    // - big scenes - the raw stream values (64 B) decoded here by the same functions
+    // loadVertexThroughIndexBuffer x 3 (geometry.glsl:220-244) from the triangle's record, decoded at upload (128 B)
     const prosper_DrawInstance inst = s.drawInstances[hit.drawInstance];
     const uint32_t record = s.triangleOffsets[hit.drawInstance] + hit.primitive;
     Vertex v0, v1, v2;
-    uint32_t recordFlags;
-    if (PPT_RAW_RECORDS(s))
-    {
-        const uint4 *rec = reinterpret_cast<const uint4 *>(s.rawShadeTriangles + record);
-        const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
-        recordFlags = q3.w;
-        v0.position = unpack_half3(q0.x, q0.y);
-        v1.position = unpack_half3(q0.z, q0.w);
-        v2.position = unpack_half3(q1.x, q1.y);
-        const f3 zero = f3{0.0f, 0.0f, 0.0f};
-        const bool noNormals = (recordFlags & kRawNoNormals) != 0u, noTangents = (recordFlags & kRawNoTangents) != 0u;
-        v0.normal = noNormals ? zero : unpack_snorm_r10g10b10(q1.z);
-        v1.normal = noNormals ? zero : unpack_snorm_r10g10b10(q1.w);
-        v2.normal = noNormals ? zero : unpack_snorm_r10g10b10(q2.x);
-        const f3 t0 = unpack_snorm_r10g10b10(q2.y), t1 = unpack_snorm_r10g10b10(q2.z), t2 = unpack_snorm_r10g10b10(q2.w);
-        v0.tangent = noTangents ? f4{0.0f, 0.0f, 0.0f, 0.0f} : f4{t0.x, t0.y, t0.z, (float)((int32_t)q2.y >> 30)};
-        v1.tangent = noTangents ? f4{0.0f, 0.0f, 0.0f, 0.0f} : f4{t1.x, t1.y, t1.z, (float)((int32_t)q2.z >> 30)};
-        v2.tangent = noTangents ? f4{0.0f, 0.0f, 0.0f, 0.0f} : f4{t2.x, t2.y, t2.z, (float)((int32_t)q2.w >> 30)};
-        v0.uv = unpack_half2(q3.x);
-        v1.uv = unpack_half2(q3.y);
-        v2.uv = unpack_half2(q3.z);
-    }
-    else
-    {
-        const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + record);
-        const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
-        recordFlags = __builtin_bit_cast(uint32_t, q7.z);
-        v0.normal = f3{q0.x, q0.y, q0.z};
-        v1.normal = f3{q1.x, q1.y, q1.z};
-        v2.normal = f3{q2.x, q2.y, q2.z};
-        v0.uv = unpack_half2(__builtin_bit_cast(uint32_t, q0.w));
-        v1.uv = unpack_half2(__builtin_bit_cast(uint32_t, q1.w));
-        v2.uv = unpack_half2(__builtin_bit_cast(uint32_t, q2.w));
-        v0.tangent = f4{q3.x, q3.y, q3.z, q3.w};
-        v1.tangent = f4{q4.x, q4.y, q4.z, q4.w};
-        v2.tangent = f4{q5.x, q5.y, q5.z, q5.w};
-        v0.position = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
-        v1.position = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
-        v2.position = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
-    }
+    const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + record);
+    const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6], q7 = rec[7];
+    const uint32_t recordFlags = __builtin_bit_cast(uint32_t, q7.z);
+    v0.normal = f3{q0.x, q0.y, q0.z};
+    v1.normal = f3{q1.x, q1.y, q1.z};
+    v2.normal = f3{q2.x, q2.y, q2.z};
+    v0.uv = unpack_half2(__builtin_bit_cast(uint32_t, q0.w));
+    v1.uv = unpack_half2(__builtin_bit_cast(uint32_t, q1.w));
+    v2.uv = unpack_half2(__builtin_bit_cast(uint32_t, q2.w));
+    v0.tangent = f4{q3.x, q3.y, q3.z, q3.w};
+    v1.tangent = f4{q4.x, q4.y, q4.z, q4.w};
+    v2.tangent = f4{q5.x, q5.y, q5.z, q5.w};
+    v0.position = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
+    v1.position = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
+    v2.position = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
     const Vertex vi = interpolate(v0, v1, v2, hit.bary);
     const Vertex v = transform(vi, s.modelInstanceTransforms[inst.modelInstanceIndex]);
     if constexpr (COUNT)

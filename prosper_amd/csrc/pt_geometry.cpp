@@ -42,7 +42,6 @@ GeometryTarget context_target(prosper_pt_ctx *ctx)
     t.buildOpt = build_options(ctx);
     t.flatBvh = ctx->debug.flatBvh != 0;
     t.noUploadRefit = ctx->debug.noUploadRefit != 0;
-    t.rawRecords = ctx->debug.rawRecords != 0; // (refused by prosper_pt_set_debug_options unless built with -DPPT_EXPERIMENTS)
     return t;
 }
 
@@ -402,19 +401,10 @@ int finish_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryJob &job)
     *t.alphaTriangleCount = job.alphaTotal;
     if ((rc = device_alloc(ctx, (size_t)(total ? total : 1) * 4, &d))) return rc;
     acc->dPerm = static_cast<uint32_t *>(d);
-    // decoded 128-byte records; debug option rawRecords (an experiment) keeps the raw 64-byte form instead, decoded per hit (same
-    // pixels, tested).  Measured and not made a default for any scene size (profiles/r03_raw_records.txt): even on
-    // S-sponza-class, whose 33.6 MB of records outgrow the L2 and whose wf_shade runs at 6.7 TB/s, the ~150 instructions of
-    // decoding cost more than the 64 bytes save (wf_shade 910 -> 931 us; C4 687 -> 721, C2 220 -> 248, FlightHelmet 97 -> 104)
-    void *dShade = nullptr, *dRaw = nullptr;
-    if (t.rawRecords)
-    {
-        if ((rc = device_alloc(ctx, sizeof(RawShadeTriangle) * (size_t)(total ? total : 1), &dRaw))) return rc;
-    }
-    else if ((rc = device_alloc(ctx, sizeof(ShadeTriangle) * (size_t)(total ? total : 1), &dShade)))
-        return rc;
+    // the decoded 128-byte shading records
+    void *dShade = nullptr;
+    if ((rc = device_alloc(ctx, sizeof(ShadeTriangle) * (size_t)(total ? total : 1), &dShade))) return rc;
     s.shadeTriangles = static_cast<const ShadeTriangle *>(dShade);
-    s.rawShadeTriangles = static_cast<const RawShadeTriangle *>(dRaw);
     const size_t triBytes = sizeof(WorldTriangle) * (size_t)(total ? total : 1);
     void *dTris = nullptr;
     if ((rc = device_alloc(ctx, triBytes, &dTris))) return rc;
@@ -426,8 +416,7 @@ int finish_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryJob &job)
 
     launch_flatten_triangles(
         s, acc->dOffsets, acc->drawInstanceCount, acc->dFlags, acc->dFlat, static_cast<ShadeTriangle *>(dShade),
-        const_cast<AlphaTriangle *>(s.alphaTriangles), (uint32_t)total, t.stream, nullptr, nullptr,
-        static_cast<RawShadeTriangle *>(dRaw));
+        const_cast<AlphaTriangle *>(s.alphaTriangles), (uint32_t)total, t.stream);
     PPT_HIP(hipGetLastError());
     PPT_HIP(hipStreamSynchronize(t.stream));
     t.lap("records");
@@ -679,7 +668,7 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
         // the old generation: frames in flight may still read its arrays, and its events / pinned staging may be in use
         const void *gone[] = {old->dFlat, old->dPerm, old->dLeafPosition, old->dOffsets, old->dFlags, old->dNodeBounds, old->dRefitOrder,
                               old->dCost, ctx->scene.alphaOffsets, ctx->scene.alphaTriangles, ctx->scene.shadeTriangles,
-                              ctx->scene.rawShadeTriangles, b->dAlphaSnapshot};
+                              b->dAlphaSnapshot};
         for (const void *p : gone) retire(ctx, p);
         for (uint32_t v = 0; v < AccelState::kVersions; ++v)
         {
@@ -696,7 +685,6 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
         s.alphaOffsets = b->scene.alphaOffsets;
         s.alphaTriangles = b->scene.alphaTriangles;
         s.shadeTriangles = b->scene.shadeTriangles;
-        s.rawShadeTriangles = b->scene.rawShadeTriangles;
         s.modelInstanceTransforms = b->scene.modelInstanceTransforms;
         ctx->dTransforms = acc->dTransformsV[0];
         ctx->alphaTriangleCount = b->alphaTriangleCount;
@@ -707,7 +695,6 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
         ctx->stats.bvhBuildSeconds = b->stats.bvhBuildSeconds;
         ctx->stats.alphaTriangleCount = b->stats.alphaTriangleCount;
         ctx->stats.deviceBytes = ctx->sceneBytes;
-        ctx->sceneStamp++;
         gs->installs++;
         // a material that changed while the build ran: its any-hit records are rewritten by the next flush of the tables
         if (ms->changes != b->materialChanges && ctx->alphaTriangleCount)

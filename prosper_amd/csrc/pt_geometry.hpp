@@ -35,7 +35,7 @@ struct GeometryTarget
     uint64_t *alphaTriangleCount = nullptr;
     hipStream_t stream = nullptr;
     BvhBuildOptions buildOpt;
-    bool flatBvh = false, noUploadRefit = false, rawRecords = false;
+    bool flatBvh = false, noUploadRefit = false;
     // debug option buildTiming: where a build spends its time (stderr)
     std::chrono::steady_clock::time_point tick = std::chrono::steady_clock::now();
     void lap(const char *what)

@@ -23,7 +23,7 @@ __global__ void flatten_triangles_kernel(
     DeviceScene s, const uint32_t *__restrict__ triOffsets, uint32_t drawInstanceCount,
     const uint32_t *__restrict__ drawInstanceFlags, WorldTriangle *__restrict__ out,
     ShadeTriangle *__restrict__ shadeOut, AlphaTriangle *__restrict__ alphaOut, uint32_t total,
-    const uint32_t *__restrict__ leafPosition, WorldTriangle *__restrict__ leafOrder, RawShadeTriangle *__restrict__ rawOut)
+    const uint32_t *__restrict__ leafPosition, WorldTriangle *__restrict__ leafOrder)
 {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -60,64 +60,37 @@ __global__ void flatten_triangles_kernel(
     t.flags = diFlags | (alphaIndex << kTriAlphaShift); // a non-opaque triangle names its alpha record
     out[g] = t;
     if (leafOrder != nullptr) leafOrder[leafPosition[g]] = t; // moved instances: straight into the traversal's (leaf) order
-    if (shadeOut == nullptr && rawOut == nullptr) return; // re-flatten after moved instances: the shading records are object-space
+    if (shadeOut == nullptr) return; // re-flatten after moved instances: the shading records are object-space
 
-    // the shading record of this triangle: decoded (pt_scene.hpp ShadeTriangle: geometry.glsl:220-244 per corner) or, for
-    // scenes that keep the 64-byte form, the raw stream values (RawShadeTriangle)
+    // the shading record of this triangle (pt_scene.hpp ShadeTriangle: geometry.glsl:220-244 per corner)
     const uint32_t vi[3] = {i0, i1, i2};
     uint32_t uvBits[3];
     for (int c = 0; c < 3; ++c)
         uvBits[c] = m.texCoord0sOffset == PROSPER_PT_ABSENT ? 0u : geo_u32(s, m.bufferIndex)[m.texCoord0sOffset + vi[c]];
-#ifdef PPT_EXPERIMENTS
-    if (rawOut != nullptr)
+    ShadeTriangle sh;
+    for (int c = 0; c < 3; ++c)
     {
-        RawShadeTriangle raw;
-        for (int c = 0; c < 3; ++c)
+        const Vertex vtx = load_vertex_through_index_buffer(s, m, prim * 3 + c);
+        sh.normalUv[c][0] = vtx.normal.x;
+        sh.normalUv[c][1] = vtx.normal.y;
+        sh.normalUv[c][2] = vtx.normal.z;
+        sh.normalUv[c][3] = __builtin_bit_cast(float, uvBits[c]);
+        sh.tangent[c][0] = vtx.tangent.x;
+        sh.tangent[c][1] = vtx.tangent.y;
+        sh.tangent[c][2] = vtx.tangent.z;
+        sh.tangent[c][3] = vtx.tangent.w;
+        if (m.positionsOffset == PROSPER_PT_ABSENT)
+            sh.position[c][0] = sh.position[c][1] = 0u;
+        else
         {
-            if (m.positionsOffset == PROSPER_PT_ABSENT)
-                raw.position[c][0] = raw.position[c][1] = 0u;
-            else
-            {
-                const u32x2 pp = *(global_u32x2_ptr)(geo_u32(s, m.bufferIndex) + m.positionsOffset + vi[c] * 2);
-                raw.position[c][0] = pp.x;
-                raw.position[c][1] = pp.y;
-            }
-            raw.normal[c] = m.normalsOffset == PROSPER_PT_ABSENT ? 0u : geo_u32(s, m.bufferIndex)[m.normalsOffset + vi[c]];
-            raw.tangent[c] = m.tangentsOffset == PROSPER_PT_ABSENT ? 0u : geo_u32(s, m.bufferIndex)[m.tangentsOffset + vi[c]];
-            raw.uv[c] = uvBits[c];
+            const u32x2 pp = *(global_u32x2_ptr)(geo_u32(s, m.bufferIndex) + m.positionsOffset + vi[c] * 2);
+            sh.position[c][0] = pp.x;
+            sh.position[c][1] = pp.y;
         }
-        raw.flags = (diFlags & kTriFlagShortIndices) | (m.normalsOffset == PROSPER_PT_ABSENT ? kRawNoNormals : 0u) |
-                    (m.tangentsOffset == PROSPER_PT_ABSENT ? kRawNoTangents : 0u);
-        rawOut[g] = raw;
     }
-#endif
-    if (shadeOut != nullptr)
-    {
-        ShadeTriangle sh;
-        for (int c = 0; c < 3; ++c)
-        {
-            const Vertex vtx = load_vertex_through_index_buffer(s, m, prim * 3 + c);
-            sh.normalUv[c][0] = vtx.normal.x;
-            sh.normalUv[c][1] = vtx.normal.y;
-            sh.normalUv[c][2] = vtx.normal.z;
-            sh.normalUv[c][3] = __builtin_bit_cast(float, uvBits[c]);
-            sh.tangent[c][0] = vtx.tangent.x;
-            sh.tangent[c][1] = vtx.tangent.y;
-            sh.tangent[c][2] = vtx.tangent.z;
-            sh.tangent[c][3] = vtx.tangent.w;
-            if (m.positionsOffset == PROSPER_PT_ABSENT)
-                sh.position[c][0] = sh.position[c][1] = 0u;
-            else
-            {
-                const u32x2 pp = *(global_u32x2_ptr)(geo_u32(s, m.bufferIndex) + m.positionsOffset + vi[c] * 2);
-                sh.position[c][0] = pp.x;
-                sh.position[c][1] = pp.y;
-            }
-        }
-        sh.flags = diFlags;
-        sh.reserved = 0;
-        shadeOut[g] = sh;
-    }
+    sh.flags = diFlags;
+    sh.reserved = 0;
+    shadeOut[g] = sh;
     if (nonOpaque)
     {
         // what the any-hit shader reads of this triangle (pt_scene.hpp AlphaTriangle): scene.rahit:20-31
@@ -148,12 +121,12 @@ __global__ void permute_triangles_kernel(
 void launch_flatten_triangles(
     const DeviceScene &s, const uint32_t *triOffsets, uint32_t drawInstanceCount, const uint32_t *drawInstanceFlags,
     WorldTriangle *out, ShadeTriangle *shadeOut, AlphaTriangle *alphaOut, uint32_t total, hipStream_t stream,
-    const uint32_t *leafPosition, WorldTriangle *leafOrder, RawShadeTriangle *rawOut)
+    const uint32_t *leafPosition, WorldTriangle *leafOrder)
 {
     if (total == 0) return;
     hipLaunchKernelGGL(
         flatten_triangles_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, s, triOffsets, drawInstanceCount,
-        drawInstanceFlags, out, shadeOut, alphaOut, total, leafPosition, leafOrder, rawOut);
+        drawInstanceFlags, out, shadeOut, alphaOut, total, leafPosition, leafOrder);
 }
 
 void launch_permute_triangles(
@@ -441,212 +414,6 @@ void launch_render_megakernel(
     else
         hipLaunchKernelGGL(render_megakernel<false>, grid, block, 0, stream, s, p, hdr, counters, stackOverflow);
 }
-
-#ifdef PPT_EXPERIMENTS // (A/B pipeline, measured no faster than the megakernel: profiles/r01_*)
-// ------------------------------------------------------------------------------------------
-// Persistent waves with path regeneration.
-//
-// One lane per pixel wastes half the machine on this path: paths end after 1..maxBounces bounces
-// (miss, roulette), so within a wave the set of live lanes shrinks every bounce.  Here a fixed set
-// of resident waves pulls pixels from one global counter; every loop iteration runs ONE bounce for
-// all live lanes (all lanes traverse together, then shade together), and a lane whose path ended
-// starts its pixel's next accumulated frame - or claims the next pixel with a wave-aggregated
-// atomic (ballot + popcount, one atomic per wave) - before the next iteration.  A pixel's frames
-// stay on one lane in order, so the running mean of main.rgen:289-297 is evaluated exactly as by
-// frame-at-a-time rendering (same bits), with the history in registers.
-// Work order: 8x8-pixel tiles in row-major tile order, so a wave's first claim is one coherent tile.
-// ------------------------------------------------------------------------------------------
-
-// One iteration of the while loop of main.rgen:241-283 for one lane; returns true when the path
-// has ended (its radiance is then in st.color).
-template <bool COUNT>
-__device__ __forceinline__ bool path_bounce(
-    const DeviceScene &s, const RenderParams &p, PathState &st, const TraversalStack &stack, LaneCounters &cnt)
-{
-    Hit hit;
-    if constexpr (COUNT) cnt.closestRays++;
-    const bool found = trace<false, COUNT>(s, st.o, st.d, 0.0f, kInf, pcg(st.rng.x ^ st.rng.z), stack, hit, cnt);
-    if (!found)
-    {
-        if (p.pc.flags & PROSPER_PC_FLAG_IBL)
-        {
-            if constexpr (COUNT) cnt.skyLookups++;
-            add_bounce(p.pc.flags, st.color, st.throughput * sample_skybox(s, st.d), st.bounce);
-        }
-        return true;
-    }
-    const Surface sf = evaluate_surface<COUNT>(s, st.d, hit, cnt);
-    if (p.pc.drawType != PROSPER_DRAW_TYPE_DEFAULT && p.pc.drawType != PROSPER_DRAW_TYPE_MESHLET_ID)
-    {
-        st.color = debug_color(s, p.pc.drawType, hit, sf);
-        return true;
-    }
-    {
-        f3 l, irradiance;
-        float d;
-        f3 direct = f3{0.0f, 0.0f, 0.0f};
-        if (prepare_direct_lighting<COUNT>(s, sf, st.throughput, st.rng, l, d, irradiance, cnt))
-        {
-            Hit sh;
-            if constexpr (COUNT) cnt.shadowRays++;
-            const f3 brdf = eval_brdf_times_nol(l, sf);
-            const f3 lit = direct_lighting_value(s, st.throughput, irradiance, brdf, 1.0f);
-            const f3 blocked = direct_lighting_value(s, st.throughput, irradiance, brdf, 0.0f);
-            bool occluded = false;
-            if (shadow_ray_matters(lit, blocked))
-                occluded = trace<true, COUNT>(s, sf.positionWS, l, 0.1f, d, pcg(st.rng.x ^ st.rng.y), stack, sh, cnt);
-            direct = occluded ? blocked : lit;
-        }
-        add_bounce(p.pc.flags, st.color, direct, st.bounce);
-    }
-    f3 rd;
-    importance_sample_bounce(sf, st.rng, st.throughput, rd);
-    if (!p.traceDeadPaths && throughput_is_zero(st.throughput)) return true;
-    if (st.bounce > p.pc.rouletteStartBounce)
-    {
-        if (st.rng.rnd01() < fmax_(0.05f, 1.0f - max3(st.throughput))) return true;
-    }
-    st.o = offset_ray(sf.positionWS, sf.normalWS);
-    st.d = rd;
-    st.bounce++;
-    // the loop conditions of main.rgen:241-244, evaluated now instead of next iteration
-    return st.bounce >= PROSPER_RT_MAX_BOUNCES || st.bounce >= p.pc.maxBounces;
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(256) void render_persistent(
-    DeviceScene s, RenderParams p, float4 *__restrict__ hdr, unsigned long long *__restrict__ counters,
-    uint32_t *__restrict__ workCounter, int32_t *__restrict__ stackOverflow)
-{
-    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t lane = threadIdx.x & 63u;
-    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
-                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
-
-    const uint32_t tilesX = (p.localWidth + 7u) / 8u;
-    const uint32_t tilesY = (p.height + 7u) / 8u;
-    const uint32_t totalWork = tilesX * tilesY * 64u;
-    const bool zeroBounces = p.pc.maxBounces == 0;
-
-    LaneCounters cnt = {};
-    PathState st = {};
-    float4 history = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    uint32_t lx = 0, py = 0, px = 0;
-    uint32_t frame = 0;    // accumulated frames finished for the current pixel
-    bool havePixel = false; // lane owns a pixel
-    bool active = false;    // lane has a path in flight
-    bool done = false;      // work counter exhausted
-
-    while (true)
-    {
-        if (!active && !done)
-        {
-            if (havePixel && frame >= p.frameCount)
-            {
-                hdr[(size_t)py * p.localWidth + lx] = history;
-                havePixel = false;
-            }
-            if (!havePixel)
-            {
-                // wave-aggregated claim of the next work items
-                const unsigned long long need = __ballot(1);
-                const uint32_t leader = (uint32_t)__builtin_ctzll(need);
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(workCounter, (uint32_t)__builtin_popcountll(need));
-                base = __shfl(base, leader, 64);
-                const uint32_t idx = base + (uint32_t)__builtin_popcountll(need & ((1ull << lane) - 1ull));
-                if (idx >= totalWork)
-                    done = true;
-                else
-                {
-                    const uint32_t tile = idx >> 6, inTile = idx & 63u;
-                    lx = (tile % tilesX) * 8u + (inTile & 7u);
-                    py = (tile / tilesX) * 8u + (inTile >> 3);
-                    if (lx < p.localWidth && py < p.height)
-                    {
-                        px = local_to_global_x(p, lx);
-                        havePixel = true;
-                        frame = 0;
-                    }
-                }
-            }
-            if (havePixel)
-            {
-                start_path<COUNT>(p, px, py, (p.pc.frameIndex + frame) % PROSPER_RT_FRAME_PERIOD, st, cnt);
-                active = true;
-            }
-        }
-        if (__ballot(active) == 0ull)
-        {
-            if (__ballot(!done) == 0ull) break;
-            continue;
-        }
-        if (active)
-        {
-            const bool ended = zeroBounces ? true : path_bounce<COUNT>(s, p, st, stack, cnt);
-            if (ended)
-            {
-                // main.rgen:285-298; skipHistory applies to the first frame of a batch only
-                const bool skip = (frame == 0 && (p.pc.flags & PROSPER_PC_FLAG_SKIP_HISTORY)) ||
-                                  !(p.pc.flags & PROSPER_PC_FLAG_ACCUMULATE);
-                if (skip)
-                    history = make_float4(st.color.x, st.color.y, st.color.z, 1.0f);
-                else
-                {
-                    if (frame == 0) history = hdr[(size_t)py * p.localWidth + lx];
-                    if constexpr (COUNT) cnt.historyReads++;
-                    const float hc = history.w + 1.0f;
-                const float invHc = 1.0f / hc;
-                history = make_float4(
-                    __builtin_fmaf(st.color.x - history.x, invHc, history.x), __builtin_fmaf(st.color.y - history.y, invHc, history.y),
-                    __builtin_fmaf(st.color.z - history.z, invHc, history.z), hc);
-                }
-                if constexpr (COUNT) cnt.pixelsWritten++;
-                frame++;
-                active = false;
-            }
-        }
-    }
-    flush_counters<COUNT>(cnt, counters);
-}
-
-uint32_t persistent_grid_blocks()
-{
-    static uint32_t cached = 0;
-    if (cached) return cached;
-    int perCu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, render_persistent<false>, 256, 0) != hipSuccess || perCu < 1)
-    {
-        perCu = 2;
-        prop.multiProcessorCount = 256;
-    }
-    cached = (uint32_t)perCu * (uint32_t)prop.multiProcessorCount;
-    return cached;
-}
-
-void launch_render_persistent(
-    const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, uint32_t *workCounter,
-    int32_t *stackOverflow, bool countWork, hipStream_t stream)
-{
-    const uint32_t tilesX = (p.localWidth + 7u) / 8u;
-    const uint32_t tilesY = (p.height + 7u) / 8u;
-    const uint32_t waves = tilesX * tilesY;
-    if (waves == 0) return;
-    (void)hipMemsetAsync(workCounter, 0, sizeof(uint32_t), stream);
-    uint32_t blocks = persistent_grid_blocks();
-    const uint32_t needed = (waves + 3u) / 4u;
-    if (blocks > needed) blocks = needed;
-    const dim3 grid(blocks), block(256);
-    if (countWork)
-        hipLaunchKernelGGL(render_persistent<true>, grid, block, 0, stream, s, p, hdr, counters, workCounter, stackOverflow);
-    else
-        hipLaunchKernelGGL(render_persistent<false>, grid, block, 0, stream, s, p, hdr, counters, workCounter, stackOverflow);
-}
-
-#endif // PPT_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------------
 // RGBA32F -> RGBA16F

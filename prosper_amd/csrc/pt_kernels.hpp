@@ -11,7 +11,7 @@ namespace ppt
 // Stage index of a render kernel: selects its block of 16 work counters and its timing bucket.
 enum : uint32_t
 {
-    kStageGenerate = 0, // wf_generate_extend, or the single kernel of the megakernel/persistent pipelines
+    kStageGenerate = 0, // wf_generate_extend, or the single kernel of the megakernel pipeline
     kStageShade = 1,
     kStageTrace = 2,
     kStageAccumulate = 3,
@@ -44,7 +44,7 @@ struct LaunchTimer
 void launch_flatten_triangles(
     const DeviceScene &s, const uint32_t *triOffsets, uint32_t drawInstanceCount, const uint32_t *drawInstanceFlags,
     WorldTriangle *out, ShadeTriangle *shadeOut, AlphaTriangle *alphaOut, uint32_t total, hipStream_t stream,
-    const uint32_t *leafPosition = nullptr, WorldTriangle *leafOrder = nullptr, RawShadeTriangle *rawOut = nullptr);
+    const uint32_t *leafPosition = nullptr, WorldTriangle *leafOrder = nullptr);
 // refit of an unchanged tree after moved instances: exact bounds level by level (`order` = nodes by height,
 // levelOffsets[levels + 1] on the HOST), then every node's boxes re-encoded; *cost += the tree's surface-area measure
 void launch_refit(
@@ -64,27 +64,12 @@ void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);
 uint32_t megakernel_grid_blocks(const RenderParams &p);
-#ifdef PPT_EXPERIMENTS
-uint32_t persistent_grid_blocks();
-#endif
 uint32_t wavefront_grid_blocks(const WavefrontBuffers &w);
-// tiles ordered by the cost of a probe ray (heaviest first) into order[tilesX * tilesY]; `scratch` holds
-// tilesX * tilesY + 512 more uint32s; `stackOverflow` as for the render's traversal kernels (the probe's grid is smaller)
-#ifdef PPT_EXPERIMENTS
-void launch_tile_order(
-    const DeviceScene &s, const RenderParams &p, uint32_t tilesX, uint32_t tilesY, uint32_t ldsStackEntries, int32_t *stackOverflow,
-    uint32_t *order, uint32_t *scratch, hipStream_t stream);
-#endif
 // `stackOverflow`: global array of (stack bound - LDS entries) x (grid lanes) ints, or nullptr when the
 // BVH's stack bound fits the kernel's LDS stack
 void launch_render_megakernel(
     const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, int32_t *stackOverflow,
     bool countWork, hipStream_t stream);
-#ifdef PPT_EXPERIMENTS
-void launch_render_persistent(
-    const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, uint32_t *workCounter,
-    int32_t *stackOverflow, bool countWork, hipStream_t stream);
-#endif
 // The wavefront pipeline runs its segment groups as `count` independent chains of launches (generate,
 // shade/trace per bounce), chain i on streams[i] with its own launch timer, forked from and joined back
 // into the caller's stream around them; the accumulate kernel follows on the caller's stream.  With
@@ -112,18 +97,13 @@ struct WavefrontPlan
     uint32_t overflowEntries;       // their stack entries per lane in global memory (stack bound - LDS entries)
     bool sceneInLds;                // a scene of a few KB is traversed out of an LDS copy
     bool tablesInLds;               // wf_shade stages the scene tables in LDS
-    bool hipGraph;                  // experiment: a detached chain's launches through a HIP graph
-    uint32_t poolVariant;           // 0: wf_trace walks its rays lane-owned (trace_stream); else index + 1 of the ray-pool variant
-    uint32_t poolOverflowEntries;   // stack entries per pool slot in global memory
-    uint32_t scratchDwordsPerBlock; // ints of `scratch` per workgroup: the larger of the two kernels' needs
+    uint32_t scratchDwordsPerBlock; // ints of `scratch` per workgroup: overflowEntries x 256 lanes
 };
 // what a context's debug options (prosper_pt_debug_options) say about the kernel variants; all zero = the defaults
 struct WavefrontOptions
 {
     uint32_t ldsStackEntries = 0; // 16 / 24 / 32 forces the LDS stack size
     bool noLdsScene = false, noLdsTables = false;
-    uint32_t poolVariant = 0;     // experiments (-DPPT_EXPERIMENTS): ray-pool wf_trace, HIP graph
-    bool hipGraph = false;
 };
 WavefrontPlan wavefront_plan(
     uint32_t stackBound, uint32_t nodeCount, uint32_t triCount, const DeviceScene &s, const WavefrontOptions &opt);

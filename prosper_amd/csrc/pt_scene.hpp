@@ -109,24 +109,6 @@ struct alignas(16) ShadeTriangle
 };
 static_assert(sizeof(ShadeTriangle) == 128, "shade triangle is 128 B");
 
-// The same three corners as the vertex streams hold them, 64 B, kept INSTEAD of ShadeTriangle under
-// PROSPER_PT_DEBUG_RAW_RECORDS=1 (DeviceScene::rawShadeTriangles) and decoded per hit by the very functions
-// flatten_triangles runs for the decoded record: same bits.  An experiment (round-2 verdict item 6): half the record bytes
-// against ~150 more instructions per hit (six unpackSnorm + normalize) - slower on every configuration, also on
-// S-sponza-class whose 33.6 MB of records outgrow the L2 (profiles/r03_raw_records.txt).
-//   q0: position halfs of corner 0 (xy, z_) and 1;  q1: corner 2, normal 0, normal 1 (snorm10);
-//   q2: normal 2, tangents 0..2 (snorm10, sign in the top two bits);  q3: texCoord0 0..2 (two halfs), flags
-struct alignas(64) RawShadeTriangle
-{
-    uint32_t position[3][2];
-    uint32_t normal[3];
-    uint32_t tangent[3];
-    uint32_t uv[3];
-    uint32_t flags; // bit 1: u16-indexed mesh; bit 2: the mesh has no normals; bit 3: no tangents
-};
-static_assert(sizeof(RawShadeTriangle) == 64, "raw shade triangle is 64 B");
-constexpr uint32_t kRawNoNormals = 4u, kRawNoTangents = 8u;
-
 // RGBA8 texels in 8 x 4 tiles of one 128-byte cache line each (texel (i, j) at tile (i >> 3, j >> 2),
 // row-major inside the tile; the allocation is padded to whole tiles).  The 2 x 2 footprint of a bilinear
 // fetch then falls into one line two times out of three instead of always two (rows are `width * 4` bytes
@@ -171,8 +153,7 @@ struct DeviceScene
 {
     const BvhNode *nodes;
     const WorldTriangle *triangles;
-    const ShadeTriangle *shadeTriangles; // (drawInstance, primitive) order; nullptr when the scene keeps raw records
-    const RawShadeTriangle *rawShadeTriangles; // the 64-byte form (PROSPER_PT_DEBUG_RAW_RECORDS=1), else nullptr
+    const ShadeTriangle *shadeTriangles; // (drawInstance, primitive) order
     const uint32_t *triangleOffsets;     // first record of each draw instance
     const void *const *geometryBuffers;  // device array of device pointers
     const prosper_GeometryMetadata *geometryMetadatas;
@@ -226,9 +207,6 @@ struct RenderParams
     // audit switch (PROSPER_PT_DEBUG_TRACE_DEAD_PATHS=1): keep tracing paths whose throughput is exactly zero, as the
     // GLSL does; the images must not differ (arithmetic contract)
     uint32_t traceDeadPaths;
-    // wf_trace: the four segments of a workgroup are traced by ONE of its waves when together they hold at most this many
-    // shadow rays and at most this many closest-hit rays (pt_wavefront.hip "sparse segments"); 0 = never
-    uint32_t mergeLimit;
 };
 
 // Workspace of the wavefront pipeline (pt_wavefront.hip).  Paths live in fixed-length SEGMENTS of
@@ -258,9 +236,6 @@ struct WavefrontBuffers
     uint32_t pixelsPadded; // tilesX * tilesY * 64
     uint32_t tilesX;
     uint32_t tilesY;
-    // tiles in the order the camera-ray batches take them: heaviest first, by the cost of a probe ray through the tile's
-    // centre (pt_wavefront.hip tile order); nullptr = raster order
-    const uint32_t *tileOrder;
     // Banded batches (pt_wavefront.hip batch dealing): the segments [x * bandSegments, (x + 1) * bandSegments) - the ones XCD x
     // runs when a launch covers all groups - take the camera-ray batches of the tiles [bandTile[x], bandTile[x + 1]) only, so
     // that the paths an XCD traces start in one band of the image and the part of the scene they see stays in its L2.

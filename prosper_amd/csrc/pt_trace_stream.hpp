@@ -153,39 +153,13 @@ PPT_D void trace_stream(
             do
             {
                 if constexpr (COUNT) cnt.nodePhaseSteps += lane == 0 ? 1u : 0u;
-#ifdef PPT_EXPERIMENT_COUNT_DRAIN_STEPS
-                // measurement only (profiles/r04_stream_tails.txt): node steps taken after the stream ran out of rays to hand out
-                if constexpr (COUNT) cnt.historyReads += (lane == 0 && next >= n) ? 1u : 0u;
-#endif
-#ifdef PPT_EXPERIMENT_COUNT_IDLE_LANES
-                // measurement only: lanes WITHOUT A RAY (idle, nothing left to refill from) summed over the node steps of the
-                // shadow stream (historyReads) and of the closest-hit stream (pixelsWritten): what a merged stream could fill
-                if constexpr (COUNT)
-                {
-                    const uint32_t idle = (uint32_t)__builtin_popcountll(__ballot(state == kLaneIdle || state == kLaneFinished));
-                    if (lane == 0 && next >= n) (ANY ? cnt.historyReads : cnt.pixelsWritten) += idle;
-                }
-#endif
-#ifdef PPT_EXPERIMENT_COUNT_NARROW_STEPS
-                if constexpr (COUNT) // measurement only (profiles/r02_exec_mask_microbench.txt): node steps with <= 8 lanes
-                {
-                    const int active = __builtin_popcountll(__ballot(state == kLaneNode));
-                    cnt.historyReads += (lane == 0 && active <= 8) ? 1u : 0u;
-                }
-#endif
                 if (state == kLaneNode)
                 {
                     if constexpr (COUNT) cnt.nodeVisits++;
                     float e[4];
                     int32_t ref[4];
                     bool entered;
-#ifdef PPT_EXPERIMENT_UNSORTED_CLOSEST
-                    // measurement only (profiles/r04_child_order.txt): closest-hit rays take the children in storage order
-                    // like the any-hit rays - what the five-comparator sort buys in node visits against what it costs
-                    if constexpr (true)
-#else
                     if constexpr (ANY)
-#endif
                     {
                         g.template test_node<false>(node, o, rs, tMin, hit.t, e, ref);
                         entered = descend_any(e, ref, stack, sp, node);
@@ -221,16 +195,6 @@ PPT_D void trace_stream(
             do
             {
                 if constexpr (COUNT) cnt.trianglePhaseSteps += lane == 0 ? 1u : 0u;
-#ifdef PPT_EXPERIMENT_COUNT_DRAIN_STEPS
-                if constexpr (COUNT) cnt.pixelsWritten += (lane == 0 && next >= n) ? 1u : 0u; // triangle steps after the stream ran out
-#endif
-#ifdef PPT_EXPERIMENT_COUNT_NARROW_STEPS
-                if constexpr (COUNT) // triangle steps with <= 8 lanes
-                {
-                    const int active = __builtin_popcountll(__ballot(state == kLaneTri));
-                    cnt.pixelsWritten += (lane == 0 && active <= 8) ? 1u : 0u;
-                }
-#endif
                 // One step tests the next TWO triangles of the leaf when some lane has two left (SAH leaves are
                 // mostly pairs: a quad, a box face): both edge-function sets (the cheap rejection), then ONE pass
                 // through distance / guard / acceptance for whichever of them the ray goes through.  A ray through
@@ -283,23 +247,11 @@ PPT_D void trace_stream(
                         else
                         {
                             // rt/scene.rahit:18-39 runs in a phase of its own (kLaneAny)
-#ifdef PPT_EXPERIMENT_SETTLE_IN_TRI_PHASE
-                            // measured slower (profiles/r03_alpha_bounds.txt): the two dependent loads lengthen every
-                            // triangle step of the wave by more than the any-hit phases they save
-                            AlphaFootprint fp;
-                            const uint32_t verdict =
-                                any_hit_settle<COUNT>(s, flags >> kTriAlphaShift, f2{bu, bv}, seed, cnt, fp);
-                            if (verdict == kAlphaAccept)
-                                accept(di, prim, t, bu, bv);
-                            else if (verdict == kAlphaUndecided)
-#endif
-                            {
-                                cAlpha = flags >> kTriAlphaShift;
-                                cT = t;
-                                cBu = bu;
-                                cBv = bv;
-                                state = kLaneAny;
-                            }
+                            cAlpha = flags >> kTriAlphaShift;
+                            cT = t;
+                            cBu = bu;
+                            cBv = bv;
+                            state = kLaneAny;
                         }
                     }
                     if (state == kLaneTri && triCount == 0) pop();
@@ -309,21 +261,10 @@ PPT_D void trace_stream(
         }
         else if (pick == kLaneAny)
         {
-#ifdef PPT_EXPERIMENT_COUNT_ANY_STEPS
-            if constexpr (COUNT) cnt.historyReads += lane == 0 ? 1u : 0u; // measurement only: any-hit phase steps
-#endif
             if (state == kLaneAny)
             {
                 state = kLaneTri;
-#ifdef PPT_EXPERIMENT_SETTLE_IN_TRI_PHASE
-                // the footprint again (a lane keeps only the candidate between phases), then the exact evaluation
-                AlphaFootprint fp;
-                LaneCounters uncounted = {};
-                (void)any_hit_settle<false>(s, cAlpha, f2{cBu, cBv}, seed, uncounted, fp);
-                if (any_hit_exact<COUNT>(fp, cnt))
-#else
                 if (any_hit_record<COUNT>(s, cAlpha, f2{cBu, cBv}, seed, cnt))
-#endif
                 {
                     const AlphaTriangle *rec = s.alphaTriangles + cAlpha;
                     accept(rec->drawInstance, rec->primitive, cT, cBu, cBv);

@@ -23,9 +23,6 @@
 
 #include "pt_device.hpp"
 #include "pt_render_common.hpp"
-#ifdef PPT_EXPERIMENTS
-#include "pt_trace_pool.hpp"
-#endif
 #include "pt_trace_stream.hpp"
 
 // Register budgets (measured on C2/C3, profiles/r01_occupancy_ab.txt): the traversal kernels (generate,
@@ -233,11 +230,7 @@ __device__ __forceinline__ BatchLane batch_lane(
     }
     // 2^shift batches per tile, each a block of 64 >> shift pixels: 8x8, 8x4, 4x4, 4x2, 2x2, 2x1, 1x1
     const uint32_t rank = rem >> shift, part = rem & ((1u << shift) - 1u);
-#ifdef PPT_EXPERIMENTS
-    const uint32_t tile = (w.tileOrder != nullptr && tileBase + rank < (w.pixelsPadded >> 6)) ? w.tileOrder[tileBase + rank] : tileBase + rank; // (wave-uniform: a scalar load)
-#else
     const uint32_t tile = tileBase + rank;
-#endif
     const uint32_t wShift = (7u - shift) >> 1, hShift = (6u - shift) >> 1; // log2 of the block's width and height
     const uint32_t pixel = lane & ((64u >> shift) - 1u);
     const uint32_t bx = part & ((8u >> wShift) - 1u), by = part >> (3u - wShift);
@@ -269,57 +262,6 @@ __device__ __forceinline__ void add_to_slot(float4 *color, uint32_t slot, uint32
     color[slot] = make_float4(acc.x, acc.y, acc.z, 0.0f);
 #endif
 }
-
-// How a wave walks a stream of rays: lane-owned (trace_stream) or out of its LDS ray pool (trace_pool)
-struct StreamTracer
-{
-    TraversalStack stack;
-    template <bool ANY, bool COUNT, class Geom, class Fetch, class Commit>
-    __device__ __forceinline__ void run(
-        const Geom &g, const DeviceScene &s, uint32_t n, float, LaneCounters &cnt, Fetch &&fetch, Commit &&commit) const
-    {
-        trace_stream<ANY, COUNT>(g, s, n, stack, cnt, fetch, commit);
-    }
-};
-// 64 rays at a time in lockstep (trace_in's while-while loop), as the camera rays are traced: no phases, no refill.
-struct LockstepTracer
-{
-    TraversalStack stack;
-    template <bool ANY, bool COUNT, class Geom, class Fetch, class Commit>
-    __device__ __forceinline__ void run(
-        const Geom &g, const DeviceScene &s, uint32_t n, float, LaneCounters &cnt, Fetch &&fetch, Commit &&commit) const
-    {
-        const uint32_t lane = threadIdx.x & 63u;
-        for (uint32_t k0 = 0; k0 < n; k0 += 64u)
-        {
-            const uint32_t k = k0 + lane;
-            const bool valid = k < n;
-            StreamRay r;
-            r.o = f3{0.0f, 0.0f, 0.0f};
-            r.d = f3{0.0f, 0.0f, 1.0f};
-            r.tMin = 0.0f;
-            r.tMax = -1.0f; // a ray that cannot hit anything
-            r.seed = 0u;
-            if (valid) r = fetch(k);
-            Hit hit;
-            const bool found = trace_in<ANY, COUNT>(g, s, r.o, r.d, r.tMin, r.tMax, r.seed, stack, hit, cnt);
-            commit(valid, k, valid && found, hit, r.d);
-        }
-    }
-};
-#ifdef PPT_EXPERIMENTS
-template <uint32_t P, uint32_t S, uint32_t B>
-struct PoolTracer
-{
-    RayPool<P, S> pool;
-    template <bool ANY, bool COUNT, class Geom, class Fetch, class Commit>
-    __device__ __forceinline__ void run(
-        const Geom &g, const DeviceScene &s, uint32_t n, float tMin, LaneCounters &cnt, Fetch &&fetch, Commit &&commit) const
-    {
-        trace_pool<ANY, COUNT, B>(g, s, n, tMin, pool, cnt, fetch, commit);
-    }
-};
-#endif
 
 // Copies the BVH nodes and world triangles into this workgroup's LDS as they are (LdsGeomHalf).
 __device__ __forceinline__ LdsGeomHalf stage_scene_in_lds_half(const DeviceScene &s, float4 *lds, uint32_t nodeCount, uint32_t triCount)
@@ -363,93 +305,6 @@ __device__ __forceinline__ LdsGeom stage_scene_in_lds(const DeviceScene &s, floa
 
 } // namespace
 
-#ifdef PPT_EXPERIMENTS
-// ------------------------------------------------------------------------------------------
-// tile order: which tiles are expensive?
-// ------------------------------------------------------------------------------------------
-//
-// EXPERIMENT (debug option tileOrder, -DPPT_EXPERIMENTS builds only), measured and NOT the default (profiles/r03_tile_order.txt).
-// A segment takes every nSeg-th batch of the render's batch sequence.  In raster order its share of expensive tiles
-// (FlightHelmet: a fifth of the tiles see the mesh and cost 15-20x a sky tile) varies from segment to segment like any
-// systematic sample of a patchy image - the slowest wave sets the launch's tail (cu_busy 0.78).  Sorted by cost, the
-// sequence is monotone and every stride through it gets the same mix.  The cost of a tile = node visits + triangle tests
-// + any-hit calls of ONE probe ray through its centre (32 400 rays for a 1920x1080 frame, a few microseconds), binned to
-// 256 levels; a counting sort (histogram by the probe kernel, a one-workgroup scan, a scatter) orders the tiles heaviest
-// first.  Within a bin the order is whatever the atomics give: it decides which wave traces which tile, never a pixel.
-// Result: the waves' loads do even out, and the kernels get SLOWER (FlightHelmet wf_generate_extend 888 -> 977 us, C4 5667 ->
-// 6047; steps +2 to +4 %): neighbouring workgroups no longer work on neighbouring tiles, and every wave meets its heavy
-// tiles at the same time.  The strided raster order - a stratified sample of the image already - stays.
-
-template <int STACK>
-__global__ __launch_bounds__(256) void probe_tiles_kernel(
-    DeviceScene s, RenderParams p, uint32_t tilesX, uint32_t tiles, int32_t *__restrict__ stackOverflow, uint32_t overflowStride,
-    uint32_t *__restrict__ bins, uint32_t *__restrict__ histogram)
-{
-    __shared__ int32_t ldsStack[STACK * 256];
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const TraversalStack stack{(lds_int32 *)ldsStack + (threadIdx.x >> 6) * (STACK * 64u) + (threadIdx.x & 63u),
-                               stackOverflow + blockIdx.x * 256u + threadIdx.x, (uint32_t)STACK, overflowStride, 64u};
-    if (t >= tiles) return;
-    const uint32_t ty = t / tilesX, tx = t - ty * tilesX;
-    const uint32_t lx = tx * 8u + 4u, py = ty * 8u + 4u;
-    uint32_t cost = 0u;
-    if (lx < p.localWidth + 4u && py < p.height + 4u)
-    {
-        const f2 uv = f2{((float)local_to_global_x(p, lx < p.localWidth ? lx : p.localWidth - 1u)) / (float)p.width,
-                         ((float)(py < p.height ? py : p.height - 1u)) / (float)p.height};
-        const Ray ray = pinhole_camera_ray(p, uv);
-        LaneCounters cnt = {};
-        Hit hit;
-        (void)trace_in<false, true>(GlobalGeom{s.nodes, s.triangles}, s, ray.o, ray.d, 0.0f, kInf, 0x9E3779B9u, stack, hit, cnt);
-        cost = cnt.nodeVisits + cnt.triangleTests + cnt.anyHitCalls;
-    }
-    const uint32_t bin = cost > 255u ? 255u : cost;
-    bins[t] = bin;
-    atomicAdd(&histogram[bin], 1u);
-}
-
-// histogram[256] -> cursor[b] = tiles in heavier bins (one workgroup of 256)
-__global__ __launch_bounds__(256) void tile_order_scan_kernel(const uint32_t *__restrict__ histogram, uint32_t *__restrict__ cursor)
-{
-    __shared__ uint32_t counts[256];
-    counts[threadIdx.x] = histogram[threadIdx.x];
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t b = threadIdx.x + 1u; b < 256u; ++b) before += counts[b];
-    cursor[threadIdx.x] = before;
-}
-
-__global__ __launch_bounds__(256) void tile_order_scatter_kernel(
-    const uint32_t *__restrict__ bins, uint32_t *__restrict__ cursor, uint32_t *__restrict__ order, uint32_t tiles)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= tiles) return;
-    order[atomicAdd(&cursor[bins[t]], 1u)] = t;
-}
-
-// scratch: bins[tiles], histogram[256], cursor[256] (uint32 each) behind order[tiles]
-void launch_tile_order(
-    const DeviceScene &s, const RenderParams &p, uint32_t tilesX, uint32_t tilesY, uint32_t ldsStackEntries, int32_t *stackOverflow,
-    uint32_t *order, uint32_t *scratch, hipStream_t stream)
-{
-    const uint32_t tiles = tilesX * tilesY;
-    if (tiles == 0) return;
-    uint32_t *bins = scratch, *histogram = scratch + tiles, *cursor = histogram + 256;
-    (void)hipMemsetAsync(histogram, 0, 256 * sizeof(uint32_t), stream);
-    const dim3 grid((tiles + 255u) / 256u), block(256);
-    const uint32_t stride = grid.x * 256u;
-    if (ldsStackEntries == 16u)
-        hipLaunchKernelGGL(probe_tiles_kernel<16>, grid, block, 0, stream, s, p, tilesX, tiles, stackOverflow, stride, bins, histogram);
-    else if (ldsStackEntries == 24u)
-        hipLaunchKernelGGL(probe_tiles_kernel<24>, grid, block, 0, stream, s, p, tilesX, tiles, stackOverflow, stride, bins, histogram);
-    else
-        hipLaunchKernelGGL(probe_tiles_kernel<32>, grid, block, 0, stream, s, p, tilesX, tiles, stackOverflow, stride, bins, histogram);
-    hipLaunchKernelGGL(tile_order_scan_kernel, dim3(1), dim3(256), 0, stream, histogram, cursor);
-    hipLaunchKernelGGL(tile_order_scatter_kernel, grid, block, 0, stream, bins, cursor, order, tiles);
-}
-
-#endif // PPT_EXPERIMENTS
-
 // ------------------------------------------------------------------------------------------
 // generate + first extend
 // ------------------------------------------------------------------------------------------
@@ -461,13 +316,8 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
 {
     __shared__ int32_t ldsStack[STACK * 256];
     __shared__ float4 ldsScene[LDS_SCENE ? kLdsSceneFloat4s : 1];
-#ifdef PPT_EXPERIMENT_GEN_LDS_F32
-    LdsGeom lg = {};
-    if constexpr (LDS_SCENE) lg = stage_scene_in_lds(s, ldsScene, nodeCount, triCount);
-#else
     LdsGeomHalf lg = {};
     if constexpr (LDS_SCENE) lg = stage_scene_in_lds_half(s, ldsScene, nodeCount, triCount);
-#endif
     const GlobalGeom gg{s.nodes, s.triangles};
     const SegmentId id = my_segment(w);
     if (!id.valid) return;
@@ -590,40 +440,17 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
 // extend: traceClosest of bounce >= 1
 // ------------------------------------------------------------------------------------------
 
-// Sparse segments - an EXPERIMENT (debug option mergeLimit, -DPPT_EXPERIMENTS builds only; profiles/r03_sparse_segments.txt).  A wave
-// owns a segment, and what survives a stage stays in it: on a sparse image (FlightHelmet: one camera ray in ten hits
-// anything) the later stages run waves whose streams hold a few dozen to a few hundred rays (52 % of wf_trace's node steps
-// ran with <= 8 lanes there).  The idea: when the four segments of a workgroup together hold few enough rays, ONE of its
-// waves traces all of them as one stream - RayMap turns a stream position into the record's offset from the first
-// segment's base (the four segments are contiguous), the hits are compacted into the first segment, and from then on the
-// paths of the group live there.  Which wave traces a ray does not change its hit, and a path's shadow ray and next
-// closest-hit ray are still traced by the same wave in that order (both lists are merged, or neither): same pixels
-// (tested).  Measured: fuller waves, and SLOWER the more is merged (FlightHelmet wf_trace 364 -> 445 / 604 us per launch at
-// a limit of 256 / 1024 rays, the step 1.88 -> 1.98 / 2.14 ms; also the 1/8 rank share of C2, 0.32 -> 0.41 ms): with a few
-// hundred rays per wave the kernel is bound by the latency of each wave's own chain of steps, and a quarter of the waves
-// hide a quarter of it.  A sparse stage wants MORE waves, not fuller ones.
-struct RayMap
-{
-    uint32_t c0, c01, c012; // rays in the first one / two / three segments; identity: c0 = ~0
-    uint32_t segLen;
-    __device__ __forceinline__ uint32_t at(uint32_t i) const
-    {
-        return i < c0 ? i : (i < c01 ? segLen + (i - c0) : (i < c012 ? 2u * segLen + (i - c01) : 3u * segLen + (i - c012)));
-    }
-};
-
-// One wave's extend work: traces `n` live rays (buffer set `cur`) of its segment - or of its workgroup's four, through
-// `map` - and compacts the hits into the segment `id`; returns their number.
-template <bool COUNT, class Geom, class Tracer>
+// One wave's extend work: traces the `n` live rays (buffer set `cur`) of its segment `id` and compacts the hits to the
+// segment's front; returns their number.
+template <bool COUNT, class Geom>
 __device__ __forceinline__ uint32_t extend_segment(
     const Geom &g, const DeviceScene &s, const RenderParams &p, const WavefrontBuffers &w, const SegmentId &id, uint32_t n,
-    const RayMap &map, uint32_t bounce, uint32_t cur, const Tracer &tracer, LaneCounters &cnt)
+    uint32_t bounce, uint32_t cur, const TraversalStack &stack, LaneCounters &cnt)
 {
     const float4 *__restrict__ rayA = w.rayA[cur];
     const float4 *__restrict__ rayB = w.rayB[cur];
     uint32_t nHit = 0;
-    auto fetch = [&](uint32_t i) {
-        const uint32_t k = map.at(i);
+    auto fetch = [&](uint32_t k) {
         const float4 a = sld(&rayA[id.base + k]);
         const float4 b = sld(&rayB[id.base + k]);
         if constexpr (COUNT) cnt.closestRays++;
@@ -635,8 +462,7 @@ __device__ __forceinline__ uint32_t extend_segment(
         r.seed = asu(a.w);
         return r;
     };
-    auto commit = [&](bool pred, uint32_t i, bool found, const Hit &hit, const f3 &dir) {
-        const uint32_t k = map.at(i);
+    auto commit = [&](bool pred, uint32_t k, bool found, const Hit &hit, const f3 &dir) {
         if (pred && !found && (p.pc.flags & PROSPER_PC_FLAG_IBL))
         {
             if constexpr (COUNT) cnt.skyLookups++;
@@ -653,7 +479,7 @@ __device__ __forceinline__ uint32_t extend_segment(
         }
         nHit += total;
     };
-    tracer.template run<false, COUNT>(g, s, n, 0.0f, cnt, fetch, commit);
+    trace_stream<false, COUNT>(g, s, n, stack, cnt, fetch, commit);
     return nHit;
 }
 
@@ -833,15 +659,14 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
 // shadow
 // ------------------------------------------------------------------------------------------
 
-// One wave's shadow work: shadow() for the `n` shadow rays shade queued in its segment (or in its workgroup's four,
-// through `map`); adds the direct term of bounce `bounce` where the light is visible.
-template <bool COUNT, class Geom, class Tracer>
+// One wave's shadow work: shadow() for the `n` shadow rays shade queued in its segment; adds the direct term of bounce
+// `bounce` where the light is visible.
+template <bool COUNT, class Geom>
 __device__ __forceinline__ void shadow_segment(
     const Geom &g, const DeviceScene &s, const RenderParams &p, const WavefrontBuffers &w, const SegmentId &id, uint32_t n,
-    const RayMap &map, uint32_t bounce, const Tracer &tracer, LaneCounters &cnt)
+    uint32_t bounce, const TraversalStack &stack, LaneCounters &cnt)
 {
-    auto fetch = [&](uint32_t i) {
-        const uint32_t k = map.at(i);
+    auto fetch = [&](uint32_t k) {
         const float4 a = sld(&w.shA[id.base + k]);
         const float4 b = sld(&w.shB[id.base + k]);
         StreamRay r;
@@ -852,10 +677,10 @@ __device__ __forceinline__ void shadow_segment(
         r.seed = asu(a.w);
         return r;
     };
-    auto commit = [&](bool pred, uint32_t i, bool occluded, const Hit &, const f3 &) {
+    auto commit = [&](bool pred, uint32_t k, bool occluded, const Hit &, const f3 &) {
         if (pred)
         {
-            const float4 c = sld(&w.shC[id.base + map.at(i)]);
+            const float4 c = sld(&w.shC[id.base + k]);
             const uint32_t packed = asu(c.w);
             const uint32_t nanMask = packed >> 28;
             if (!occluded || nanMask)
@@ -870,75 +695,7 @@ __device__ __forceinline__ void shadow_segment(
             }
         }
     };
-    tracer.template run<true, COUNT>(g, s, n, 0.1f, cnt, fetch, commit);
-}
-
-// What a wave of wf_trace traces: its own segment's lists, or - sparse segments, see RayMap - all four of its workgroup's
-// (the leader) or nothing (the other three).
-struct TraceWork
-{
-    SegmentId id;      // where the records are read from (base) and the hits compacted into
-    uint32_t nShadow, nRays;
-    RayMap shadowMap, rayMap;
-    bool merged, leader;
-};
-__device__ __forceinline__ TraceWork trace_work(const RenderParams &p, const WavefrontBuffers &w, const SegmentId &id, bool doExtend)
-{
-    TraceWork t;
-    t.id = id;
-    t.nShadow = w.segShadow[id.seg];
-    t.nRays = doExtend ? w.segRays[id.seg] : 0u;
-    t.shadowMap = t.rayMap = RayMap{~0u, ~0u, ~0u, w.segLen};
-    t.merged = t.leader = false;
-#ifdef PPT_EXPERIMENTS
-    if (p.mergeLimit == 0u) return t;
-    const uint32_t limit = p.mergeLimit < w.segLen ? p.mergeLimit : w.segLen;
-    const uint32_t seg0 = id.seg & ~3u;
-    uint32_t cs[4], cr[4];
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k)
-    {
-        const bool valid = seg0 + k < w.nSeg;
-        cs[k] = valid ? w.segShadow[seg0 + k] : 0u;
-        cr[k] = (valid && doExtend) ? w.segRays[seg0 + k] : 0u;
-    }
-    const uint32_t totalS = cs[0] + cs[1] + cs[2] + cs[3], totalR = cr[0] + cr[1] + cr[2] + cr[3];
-    if (totalS > limit || totalR > limit) return t;
-    t.merged = true;
-    // the leading wave rotates with the workgroup (the dispatcher deals a workgroup's waves over the SIMDs in order)
-    uint32_t leader = (seg0 >> 2) & 3u;
-    if (seg0 + leader >= w.nSeg) leader = 0u;
-    if ((threadIdx.x >> 6) == leader)
-    {
-        t.leader = true;
-        t.id.seg = seg0;
-        t.id.base = seg0 * w.segLen;
-        t.nShadow = totalS;
-        t.nRays = totalR;
-        t.shadowMap = RayMap{cs[0], cs[0] + cs[1], cs[0] + cs[1] + cs[2], w.segLen};
-        t.rayMap = RayMap{cr[0], cr[0] + cr[1], cr[0] + cr[1] + cr[2], w.segLen};
-    }
-    else
-    {
-        t.nShadow = 0u;
-        t.nRays = 0u;
-    }
-#endif
-    return t;
-}
-// the hit counts of the segments a wave answers for, after its extend work: its own; merged, the leader's hits are the
-// first segment's and every other segment of the group is empty from here on
-__device__ __forceinline__ void store_hit_counts(const WavefrontBuffers &w, const SegmentId &own, const TraceWork &t, uint32_t nHit)
-{
-    if (lane_id() != 0u) return;
-    if (!t.merged)
-    {
-        w.segHits[own.seg] = nHit;
-        return;
-    }
-    const uint32_t seg0 = own.seg & ~3u;
-    if (t.leader) w.segHits[seg0] = nHit;
-    if (own.seg != seg0) w.segHits[own.seg] = 0u;
+    trace_stream<true, COUNT>(g, s, n, stack, cnt, fetch, commit);
 }
 
 // Shadow rays of bounce `bounce` and (unless it was the last bounce) the closest-hit rays of bounce
@@ -954,32 +711,20 @@ __global__ __launch_bounds__(256, PPT_TRACE_WPE(STACK)) void wf_trace(
 {
     __shared__ int32_t ldsStack[STACK * 256];
     __shared__ float4 ldsScene[LDS_SCENE ? kLdsSceneFloat4s : 1];
-#ifdef PPT_EXPERIMENT_TRACE_LDS_HALF
-    LdsGeomHalf lg = {}; // (A/B: the 80-byte node image, as until round 4)
-    if constexpr (LDS_SCENE) lg = stage_scene_in_lds_half(s, ldsScene, nodeCount, triCount);
-#else
     LdsGeom lg = {};
     if constexpr (LDS_SCENE) lg = stage_scene_in_lds(s, ldsScene, nodeCount, triCount);
-#endif
     const GlobalGeom gg{s.nodes, s.triangles};
     const SegmentId id = my_segment(w);
     if (!id.valid) return;
-    const StreamTracer stack{TraversalStack{(lds_int32 *)ldsStack + (threadIdx.x >> 6) * (STACK * 64u) + lane_id(),
-                                            stackOverflow + blockIdx.x * 256u + threadIdx.x, (uint32_t)STACK,
-                                            gridDim.x * 256u, 64u, LDS_SCENE}};
+    const TraversalStack stack{(lds_int32 *)ldsStack + (threadIdx.x >> 6) * (STACK * 64u) + lane_id(),
+                               stackOverflow + blockIdx.x * 256u + threadIdx.x, (uint32_t)STACK, gridDim.x * 256u, 64u, LDS_SCENE};
     LaneCounters cnt = {};
-    const TraceWork t = trace_work(p, w, id, doExtend != 0u);
-#ifdef PPT_EXPERIMENT_LDS_SCENE_LOCKSTEP
-    const LockstepTracer lockstep{stack.stack};
-#endif
+    const uint32_t nShadow = w.segShadow[id.seg];
+    const uint32_t nRays = doExtend ? w.segRays[id.seg] : 0u;
     if constexpr (LDS_SCENE)
-#ifdef PPT_EXPERIMENT_LDS_SCENE_LOCKSTEP
-        shadow_segment<COUNT>(lg, s, p, w, t.id, t.nShadow, t.shadowMap, bounce, lockstep, cnt);
-#else
-        shadow_segment<COUNT>(lg, s, p, w, t.id, t.nShadow, t.shadowMap, bounce, stack, cnt);
-#endif
+        shadow_segment<COUNT>(lg, s, p, w, id, nShadow, bounce, stack, cnt);
     else
-        shadow_segment<COUNT>(gg, s, p, w, t.id, t.nShadow, t.shadowMap, bounce, stack, cnt);
+        shadow_segment<COUNT>(gg, s, p, w, id, nShadow, bounce, stack, cnt);
     if (doExtend)
     {
         // same wave, same CU: a workgroup-scope fence (s_waitcnt vmcnt(0)) orders the shadow phase's
@@ -987,58 +732,13 @@ __global__ __launch_bounds__(256, PPT_TRACE_WPE(STACK)) void wf_trace(
         __threadfence_block();
         uint32_t nHit;
         if constexpr (LDS_SCENE)
-#ifdef PPT_EXPERIMENT_LDS_SCENE_LOCKSTEP
-            nHit = extend_segment<COUNT>(lg, s, p, w, t.id, t.nRays, t.rayMap, bounce + 1u, nextCur, lockstep, cnt);
-#else
-            nHit = extend_segment<COUNT>(lg, s, p, w, t.id, t.nRays, t.rayMap, bounce + 1u, nextCur, stack, cnt);
-#endif
+            nHit = extend_segment<COUNT>(lg, s, p, w, id, nRays, bounce + 1u, nextCur, stack, cnt);
         else
-            nHit = extend_segment<COUNT>(gg, s, p, w, t.id, t.nRays, t.rayMap, bounce + 1u, nextCur, stack, cnt);
-        store_hit_counts(w, id, t, nHit);
+            nHit = extend_segment<COUNT>(gg, s, p, w, id, nRays, bounce + 1u, nextCur, stack, cnt);
+        if (lane_id() == 0u) w.segHits[id.seg] = nHit;
     }
     flush_counters<COUNT>(cnt, counters);
 }
-
-#ifdef PPT_EXPERIMENTS
-// wf_trace with the wave's rays in an LDS pool of P slots (pt_trace_pool.hpp) instead of one per lane.
-template <bool COUNT, uint32_t P, uint32_t S, uint32_t B, bool LDS_SCENE>
-__global__ __launch_bounds__(256, 3) void wf_trace_pool(
-    DeviceScene s, RenderParams p, WavefrontBuffers w, uint32_t bounce, uint32_t nextCur, uint32_t doExtend,
-    uint32_t nodeCount, uint32_t triCount, int32_t *__restrict__ scratch, uint32_t overflowEntries,
-    unsigned long long *__restrict__ counters)
-{
-    __shared__ uint32_t ldsPool[RayPool<P, S>::kLdsDwords * 4u];
-    __shared__ float4 ldsScene[LDS_SCENE ? kLdsSceneFloat4s : 1];
-    LdsGeomHalf lg = {};
-    if constexpr (LDS_SCENE) lg = stage_scene_in_lds_half(s, ldsScene, nodeCount, triCount);
-    const GlobalGeom gg{s.nodes, s.triangles};
-    const SegmentId id = my_segment(w);
-    if (!id.valid) return;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const PoolTracer<P, S, B> tracer{
-        RayPool<P, S>::carve(ldsPool, wave, reinterpret_cast<uint32_t *>(scratch), blockIdx.x * 4u + wave, overflowEntries)};
-    LaneCounters cnt = {};
-    RenderParams own = p;
-    own.mergeLimit = 0u; // (the pool experiment keeps every wave on its own segment)
-    const TraceWork t = trace_work(own, w, id, doExtend != 0u);
-    if constexpr (LDS_SCENE)
-        shadow_segment<COUNT>(lg, s, p, w, t.id, t.nShadow, t.shadowMap, bounce, tracer, cnt);
-    else
-        shadow_segment<COUNT>(gg, s, p, w, t.id, t.nShadow, t.shadowMap, bounce, tracer, cnt);
-    if (doExtend)
-    {
-        __threadfence_block();
-        uint32_t nHit;
-        if constexpr (LDS_SCENE)
-            nHit = extend_segment<COUNT>(lg, s, p, w, t.id, t.nRays, t.rayMap, bounce + 1u, nextCur, tracer, cnt);
-        else
-            nHit = extend_segment<COUNT>(gg, s, p, w, t.id, t.nRays, t.rayMap, bounce + 1u, nextCur, tracer, cnt);
-        store_hit_counts(w, id, t, nHit);
-    }
-    flush_counters<COUNT>(cnt, counters);
-}
-
-#endif // PPT_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------------
 // accumulate: main.rgen:285-298 over the frames of the batch, in order
@@ -1091,34 +791,6 @@ __global__ __launch_bounds__(256) void wf_accumulate(
 // host-side sequencing
 // ------------------------------------------------------------------------------------------
 
-#ifdef PPT_EXPERIMENTS
-// ray-pool variants of wf_trace (debug option poolVariant = index): slots per wave, LDS stack entries per slot, batches per
-// step.  An experiment kept for its measurements (profiles/r02_pool_experiment.txt): fewer, fuller instructions, but slower.
-#define PPT_POOL_VARIANTS(X) X(1, 128, 8, 1) X(2, 96, 10, 1) X(3, 128, 8, 2)
-
-template <bool COUNT, bool LDS_SCENE>
-static void launch_trace_pool(
-    uint32_t variant, dim3 grid, dim3 block, hipStream_t stream, const DeviceScene &s, const RenderParams &p,
-    const WavefrontBuffers &w, uint32_t b, uint32_t nextCur, uint32_t doExtend, uint32_t nodeCount, uint32_t triCount,
-    int32_t *scratch, uint32_t overflowEntries, unsigned long long *counters)
-{
-    switch (variant)
-    {
-#define PPT_POOL_CASE(index, P, S, B)                                                                                  \
-    case index:                                                                                                        \
-        hipLaunchKernelGGL(                                                                                            \
-            (wf_trace_pool<COUNT, P, S, B, LDS_SCENE>), grid, block, 0, stream, s, p, w, b, nextCur, doExtend, nodeCount,  \
-            triCount, scratch, overflowEntries, counters);                                                             \
-        break;
-        PPT_POOL_VARIANTS(PPT_POOL_CASE)
-#undef PPT_POOL_CASE
-    default:
-        break;
-    }
-}
-
-#endif // PPT_EXPERIMENTS
-
 template <bool COUNT, int STACK, bool LDS_SCENE>
 static void enqueue_wavefront(
     const DeviceScene &s, const RenderParams &p, unsigned long long *counters, const WavefrontBuffers &w,
@@ -1154,16 +826,9 @@ static void enqueue_wavefront(
         if (!debugDraw)
         {
             mark(kStageTrace);
-#ifdef PPT_EXPERIMENTS
-            if (plan.poolVariant)
-                launch_trace_pool<COUNT, LDS_SCENE>(
-                    plan.poolVariant, grid, block, stream, s, p, w, b, cur ^ 1u, last ? 0u : 1u, nodeCount, triCount,
-                    stackOverflow, plan.poolOverflowEntries, cTrace);
-            else
-#endif
-                hipLaunchKernelGGL(
-                    (wf_trace<COUNT, STACK, LDS_SCENE>), grid, block, 0, stream, s, p, w, b, cur ^ 1u, last ? 0u : 1u,
-                    nodeCount, triCount, stackOverflow, cTrace);
+            hipLaunchKernelGGL(
+                (wf_trace<COUNT, STACK, LDS_SCENE>), grid, block, 0, stream, s, p, w, b, cur ^ 1u, last ? 0u : 1u,
+                nodeCount, triCount, stackOverflow, cTrace);
         }
     }
 }
@@ -1197,8 +862,7 @@ bool wavefront_scene_in_lds(uint32_t ldsStackEntries, uint32_t stackBound, uint3
     return ldsStackEntries == 16u && stackBound <= 16u && nodeCount * kLdsNodeStride + triCount * 3u <= kLdsSceneFloat4s && !disabled;
 }
 
-// The traversal kernels of a render and the global scratch they index: the lane-owned kernels keep `overflowEntries`
-// stack entries per lane there, a ray-pool wf_trace its slots' hit / candidate records and deeper stack entries.
+// The traversal kernels of a render and the global scratch they index: `overflowEntries` stack entries per lane.
 WavefrontPlan wavefront_plan(
     uint32_t stackBound, uint32_t nodeCount, uint32_t triCount, const DeviceScene &s, const WavefrontOptions &opt)
 {
@@ -1207,25 +871,7 @@ WavefrontPlan wavefront_plan(
     plan.overflowEntries = stackBound > plan.ldsStackEntries ? stackBound - plan.ldsStackEntries : 0u;
     plan.sceneInLds = wavefront_scene_in_lds(plan.ldsStackEntries, stackBound, nodeCount, triCount, opt.noLdsScene);
     plan.tablesInLds = wavefront_shade_tables_in_lds(s, opt.noLdsTables);
-    uint32_t poolDwords = 0;
-#ifdef PPT_EXPERIMENTS
-    plan.hipGraph = opt.hipGraph;
-    switch (opt.poolVariant)
-    {
-#define PPT_POOL_CASE(index, P, S, B)                                                                                  \
-    case index:                                                                                                        \
-        plan.poolVariant = index;                                                                                      \
-        plan.poolOverflowEntries = stackBound > S ? stackBound - S : 0u;                                               \
-        poolDwords = 4u * RayPool<P, S>::scratch_dwords(plan.poolOverflowEntries);                                     \
-        break;
-        PPT_POOL_VARIANTS(PPT_POOL_CASE)
-#undef PPT_POOL_CASE
-    default:
-        break;
-    }
-#endif
-    const uint32_t laneDwords = plan.overflowEntries * 256u;
-    plan.scratchDwordsPerBlock = laneDwords > poolDwords ? laneDwords : poolDwords;
+    plan.scratchDwordsPerBlock = plan.overflowEntries * 256u;
     return plan;
 }
 
@@ -1280,60 +926,6 @@ void launch_render_wavefront(
         int32_t *ovf = stackOverflow ? stackOverflow + (size_t)blocksBefore * plan.scratchDwordsPerBlock : nullptr;
         if (countWork)
             enqueue_for_stack<true>(s, p, counters, part, plan, ovf, nodeCount, triCount, ct, cs);
-#ifdef PPT_EXPERIMENTS
-        else if (plan.hipGraph && !ct)
-        {
-            // EXPERIMENT (debug option hipGraph, profiles/r03_hip_graph.txt): the chain's launches captured into a HIP
-            // graph and submitted as one; captured and instantiated anew every time (the kernel arguments change with
-            // every frame), so only the DEVICE side of the comparison means anything
-            struct Launched
-            {
-                hipGraphExec_t exec = nullptr;
-                hipEvent_t done = nullptr;
-            };
-            static thread_local Launched previous[8];
-            static thread_local uint32_t turn = 0;
-            Launched &mine = previous[turn++ & 7u];
-            // an executable graph goes once ITS launch has finished: the event recorded behind it says so
-            if (mine.exec)
-            {
-                (void)hipEventSynchronize(mine.done);
-                (void)hipGraphExecDestroy(mine.exec);
-                mine.exec = nullptr;
-            }
-            if (!mine.done) (void)hipEventCreateWithFlags(&mine.done, hipEventDisableTiming);
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            bool ok = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed) == hipSuccess;
-            if (ok)
-            {
-                enqueue_for_stack<false>(s, p, counters, part, plan, ovf, nodeCount, triCount, nullptr, cs);
-                // (a failed EndCapture still ends the capture: the stream is usable again either way)
-                ok = hipStreamEndCapture(cs, &graph) == hipSuccess && graph != nullptr;
-            }
-            if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (ok) ok = hipGraphLaunch(exec, cs) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (ok)
-            {
-                mine.exec = exec;
-                (void)hipEventRecord(mine.done, cs);
-            }
-            else
-            {
-                if (exec) (void)hipGraphExecDestroy(exec);
-                (void)hipGetLastError();
-                hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-                if (hipStreamIsCapturing(cs, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
-                {
-                    hipGraph_t dropped = nullptr;
-                    (void)hipStreamEndCapture(cs, &dropped);
-                    if (dropped) (void)hipGraphDestroy(dropped);
-                }
-                enqueue_for_stack<false>(s, p, counters, part, plan, ovf, nodeCount, triCount, ct, cs);
-            }
-        }
-#endif
         else
             enqueue_for_stack<false>(s, p, counters, part, plan, ovf, nodeCount, triCount, ct, cs);
         blocksBefore += ((part.groupCount + 7u) / 8u) * 8u;

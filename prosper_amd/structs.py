@@ -153,7 +153,7 @@ FILTER_NEAREST, FILTER_LINEAR = 0, 1
 WRAP_REPEAT, WRAP_MIRRORED_REPEAT, WRAP_CLAMP_TO_EDGE = 0, 1, 2
 
 CREATE_MEGAKERNEL = 1 << 0
-CREATE_PERSISTENT = 1 << 1
+CREATE_PERSISTENT = 1 << 1  # reserved: prosper_pt_create refuses it
 CREATE_SINGLE_CHAIN = 1 << 2
 RENDER_COUNT_WORK = 1 << 0
 RENDER_PIPELINED = 1 << 1
@@ -288,6 +288,7 @@ class DebugOptions(C.Structure):
                 ("segments", C.c_uint32), ("segmentLength", C.c_uint32), ("chains", C.c_uint32), ("ldsStackEntries", C.c_uint32),
                 ("noLdsScene", C.c_uint32), ("noLdsTables", C.c_uint32), ("traceDeadPaths", C.c_uint32), ("bandedBatches", C.c_int32),
                 ("rebuildCostRatio", C.c_float), ("alwaysRebuild", C.c_uint32), ("failNextUpdate", C.c_uint32),
+                # reserved (removed experiments): must be 0
                 ("poolVariant", C.c_uint32), ("rawRecords", C.c_uint32), ("tileOrder", C.c_uint32), ("hipGraph", C.c_uint32),
                 ("pipelinedChains", C.c_uint32), ("mergeLimit", C.c_uint32)]
 
@@ -310,7 +311,7 @@ VARIANT_LDS_SCENE = 1
 VARIANT_LDS_TABLES = 2
 VARIANT_BATCHED_TEXTURES = 4
 VARIANT_TEXTURE_PACKS = 8
-VARIANT_RAW_RECORDS = 16
+VARIANT_RAW_RECORDS = 16  # reserved: never set
 VARIANT_STACK_SHIFT = 8
 
 

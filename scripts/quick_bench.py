@@ -16,7 +16,6 @@ def main():
     ap.add_argument("--config", default="c2")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--megakernel", action="store_true")
-    ap.add_argument("--persistent", action="store_true")
     ap.add_argument("--single-chain", action="store_true", help="PROSPER_PT_CREATE_SINGLE_CHAIN (A/B)")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--counters", action="store_true", help="one counted render: per-stage work counters")
@@ -46,8 +45,7 @@ def main():
     h = args.height or h
     world = builder()
     cam, focal = Camera.from_world(world, w, h).update_buffer()
-    ctx = capi.Context(0, S.CREATE_MEGAKERNEL if args.megakernel else (
-        S.CREATE_PERSISTENT if args.persistent else (S.CREATE_SINGLE_CHAIN if args.single_chain else 0)))
+    ctx = capi.Context(0, S.CREATE_MEGAKERNEL if args.megakernel else (S.CREATE_SINGLE_CHAIN if args.single_chain else 0))
     ctx.upload_scene(world)
     if args.stats:
         st = ctx.scene_stats()
@@ -77,7 +75,7 @@ def main():
     print("  " + "  ".join("%s %dx%.0fus" % (k.replace("wf_", ""), v[1], v[0] * 1e3 / max(1, v[1])) for k, v in per.items() if v[1]))
     img = ctx.read_hdr()
     print("%s %s: median %.3f ms  min %.3f  => %.1f Mpaths/s  (checksum %.6f)" % (
-        args.config, "megakernel" if args.megakernel else ("persistent" if args.persistent else "wavefront"), med, times[0], w * h * spp / args.ranks / med / 1e3,
+        args.config, "megakernel" if args.megakernel else "wavefront", med, times[0], w * h * spp / args.ranks / med / 1e3,
         float(img[..., :3].astype("float64").mean())))
 
 

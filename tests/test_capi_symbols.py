@@ -133,3 +133,5 @@ print("after upload", ctx.debug_options().ldsStackEntries)
     assert "unknown option 'stack'" in run({"PROSPER_PT_DEBUG": "1", "PROSPER_PT_DEBUG_OPTIONS": "stack=16"})
     assert "is not a value" in run({"PROSPER_PT_DEBUG": "1", "PROSPER_PT_DEBUG_OPTIONS": "ldsStackEntries=sixteen"})
     assert "ldsStackEntries is 0, 16, 24 or 32" in run({"PROSPER_PT_DEBUG": "1", "PROSPER_PT_DEBUG_OPTIONS": "ldsStackEntries=20"})
+    # a reserved option (a removed experiment) fails the create as it fails prosper_pt_set_debug_options
+    assert "error -6: debug options: poolVariant" in run({"PROSPER_PT_DEBUG": "1", "PROSPER_PT_DEBUG_OPTIONS": "tileOrder=1"})

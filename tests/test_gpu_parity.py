@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import default_pc, needs_experiments, same_bits
+from conftest import default_pc, same_bits
 from prosper_amd import capi, scenes, structs as S
 
 pytestmark = pytest.mark.gpu
@@ -729,49 +729,6 @@ def test_gltf_scene_bit_exact(gpu_ctx, oracle, draw_type):
     assert ok.all(), "%s: %d of %d pixels differ" % (draw_type, (~ok).sum(), ok.size)
 
 
-@needs_experiments
-def test_raw_shading_records_equal_decoded_ones(gpu_ctx, oracle, sponza_small):
-    """Big scenes keep a triangle's three corners as the vertex streams hold them (64 B, RawShadeTriangle) and decode them
-    per hit; small ones keep the decoded 128-byte record.  debug option rawRecords forces either: the same bits, on
-    scenes with normal maps and instancing, on meshes without tangents or normals (a hand-made one), through every
-    pipeline and the counting kernels - and the oracle's."""
-    import os
-    from prosper_amd import gltf
-    from prosper_amd.world import World
-    bare = World()                       # a mesh with positions only, one with normals but no tangents, one with everything
-    mat = bare.add_material(base_color=(0.8, 0.7, 0.6, 1.0), metallic=0.2, roughness=0.6)
-    p, n, t, uv, idx = scenes.quad((-1.5, 0.0, -1.0), (1.5, 0.0, -1.0), (1.5, 0.0, 1.0), (-1.5, 0.0, 1.0))
-    for k, kw in enumerate((dict(), dict(normals=n), dict(normals=n, tangents=t, uvs=uv))):
-        mesh = bare.add_mesh(p + np.array([0.0, 0.4 * k, -0.8 * k]), idx, mat, **kw)
-        bare.add_instance(bare.add_model([(mesh, mat)]))
-    bare.add_point_light((1.0, 1.0, 1.0), 60.0, (0.0, 2.5, 1.0))
-    bare.camera = dict(eye=(0.0, 2.2, 3.5), target=(0.0, 0.3, -0.5), up=(0.0, 1.0, 0.0), fov=0.9, zN=0.1, zF=100.0)
-    tiny = gltf.load_gltf(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tiny_scene.gltf"))
-    for world, brute in ((sponza_small, False), (scenes.transform_zoo(), True), (bare, True), (tiny, True)):
-        w, h = 240, 136
-        cam, fl = _camera(oracle, world, w, h)
-        images = {}
-        for raw in ("0", "1"):
-            capi.debug(rawRecords=int(raw))
-            gpu_ctx.upload_scene(world)
-            assert bool(gpu_ctx.scene_stats().variantFlags & S.VARIANT_RAW_RECORDS) == (raw == "1")
-            out = []
-            for name in ("Default", "ShadingNormal", "TexCoord0", "Position"):
-                pc = default_pc(S, fl, draw_type=S.DrawType[name], max_bounces=3, ibl=world.skybox is not None)
-                gpu_ctx.render(pc, cam, w, h, frames=2, flags=S.RENDER_COUNT_WORK if name == "Default" else 0)
-                out.append(gpu_ctx.read_hdr())
-            images[raw] = out
-        capi.debug(rawRecords=None)
-        for a, b in zip(images["0"], images["1"]):
-            assert same_bits(a, b).all()
-        osc = oracle.OracleScene(world, brute_force=brute)
-        want = None
-        for frame in (1, 2):
-            want, _ = osc.render(default_pc(S, fl, frame_index=frame, max_bounces=3, ibl=world.skybox is not None,
-                                            skip_history=(frame == 1)), cam, w, h, history=want)
-        assert same_bits(images["1"][0], want).all()
-
-
 def test_banded_batches_give_the_same_pixels(gpu_ctx, oracle, sponza_small):
     """Debug option bandedBatches (default: by scene size): every XCD's segments take the camera-ray batches of one band of
     the image instead of batches strided over all of it (pt_wavefront.hip, WavefrontBuffers::bandSegments).  Which segment
@@ -804,60 +761,16 @@ def test_banded_batches_give_the_same_pixels(gpu_ctx, oracle, sponza_small):
     assert same_bits(gpu_ctx.read_hdr(), want).all()
 
 
-@needs_experiments
-def test_tiles_dealt_by_cost_give_the_same_pixels(gpu_ctx, oracle):
-    """debug option tileOrder (an experiment, profiles/r03_tile_order.txt): the camera-ray batches take the tiles by
-    the cost of a probe ray instead of in raster order.  Which wave traces which tile never decides a pixel: the same
-    bits on the FlightHelmet fixture (mostly sky) and on a rank's stripes of S-sponza-class, in order and with frames in
-    flight, after the view changed and after an instance moved."""
-    from prosper_amd import flight_helmet, tiling
-    from prosper_amd.world import translate
-    helmet = flight_helmet.load_fixture()
-    sponza = scenes.sponza_class(lights=(4, 4), foliage=True, texture_size=64, sky_size=32, detail=0.25)
-    for world, tile in ((helmet, None), (sponza, tiling.tile_for_rank(1, 2))):
-        w, h = 512, 288
-        cam, fl = _camera(oracle, world, w, h)
-        pc = default_pc(S, fl, max_bounces=3, ibl=True)
-        images = {}
-        for on in (False, True):
-            if on:
-                capi.debug(tileOrder=1)
-            gpu_ctx.upload_scene(world)
-            out = []
-            for flags in (0, S.RENDER_PIPELINED, S.RENDER_PIPELINED):
-                gpu_ctx.render(pc, cam, w, h, tile=tile, frames=8, flags=flags)
-                out.append(gpu_ctx.read_hdr())
-            cam2, fl2 = oracle.camera_uniforms((0.5, 0.3, 0.6) if world is helmet else (-8.0, 3.0, 1.5), world.camera["target"],
-                                               world.camera["up"], world.camera["fov"], world.camera["zN"], world.camera["zF"], w, h)
-            gpu_ctx.render(default_pc(S, fl2, max_bounces=3, ibl=True), cam2, w, h, tile=tile, frames=5, flags=S.RENDER_PIPELINED)
-            out.append(gpu_ctx.read_hdr())
-            if world is sponza:
-                moved = scenes.sponza_class(lights=(4, 4), foliage=True, texture_size=64, sky_size=32, detail=0.25)
-                model, m = moved.model_instances[4]
-                moved.model_instances[4] = (model, translate((0.3, 0.2, -0.2)) @ m)
-                gpu_ctx.update_transforms(moved)
-                gpu_ctx.render(pc, cam, w, h, tile=tile, frames=8, flags=S.RENDER_PIPELINED)
-                out.append(gpu_ctx.read_hdr())
-            images[on] = out
-        capi.debug(tileOrder=None)
-        assert same_bits(images[False][0], images[False][1]).all()
-        for a, b in zip(images[False], images[True]):
-            assert same_bits(a, b).all()
-
-
 def test_all_pipelines_produce_identical_pixels(gpu_ctx, oracle, cornell_world):
-    """Default wavefront pipeline, PROSPER_PT_CREATE_PERSISTENT and PROSPER_PT_CREATE_MEGAKERNEL are
-    the same function of (pixel, frame): identical images, identical counters, all equal to the oracle."""
+    """The default wavefront pipeline and PROSPER_PT_CREATE_MEGAKERNEL are the same function of (pixel, frame):
+    identical images, identical counters, both equal to the oracle.  PROSPER_PT_CREATE_PERSISTENT is reserved."""
     from prosper_amd import capi
     w, h = 200, 120  # not a multiple of the 8x8 / 16x16 tiles: exercises partial tiles
     cam, fl = _camera(oracle, cornell_world, w, h)
+    with pytest.raises(capi.ProsperPtError) as refused:
+        capi.Context(device=0, flags=S.CREATE_PERSISTENT)
+    assert refused.value.code == -6  # PROSPER_PT_ERR_UNSUPPORTED
     others = [capi.Context(device=0, flags=S.CREATE_MEGAKERNEL)]
-    if capi.has_experiments():  # (the persistent pipeline is compiled in only with -DPPT_EXPERIMENTS)
-        others.append(capi.Context(device=0, flags=S.CREATE_PERSISTENT))
-    else:
-        with pytest.raises(capi.ProsperPtError) as refused:
-            capi.Context(device=0, flags=S.CREATE_PERSISTENT)
-        assert refused.value.code == -6  # PROSPER_PT_ERR_UNSUPPORTED
     images, counts = [], []
     for ctx in [gpu_ctx] + others:
         ctx.upload_scene(cornell_world)
@@ -885,6 +798,21 @@ def test_all_pipelines_produce_identical_pixels(gpu_ctx, oracle, cornell_world):
     gpu_ctx.render(default_pc(S, fl, max_bounces=0), cam, w, h)
     z = gpu_ctx.read_hdr()
     assert (z[..., :3] == 0).all() and (z[..., 3] == 1).all()
+
+
+def test_reserved_debug_options_are_refused():
+    """The debug options of the removed experiments are reserved: each one, set alone on a fresh context before any
+    upload or render, fails with PROSPER_PT_ERR_UNSUPPORTED and leaves the context's options as they were."""
+    ctx = capi.Context(device=0)
+    try:
+        for name in ("poolVariant", "rawRecords", "tileOrder", "hipGraph", "pipelinedChains", "mergeLimit"):
+            with pytest.raises(capi.ProsperPtError) as refused:
+                ctx.set_debug(**{name: 1})
+            assert refused.value.code == -6, name  # PROSPER_PT_ERR_UNSUPPORTED
+            assert getattr(ctx.debug_options(), name) == 0, name
+            ctx.set_debug()
+    finally:
+        ctx.close()
 
 
 def test_lds_stack_variants_agree(gpu_ctx, oracle, sponza_small):
@@ -1373,14 +1301,14 @@ def test_zero_throughput_rule_does_not_change_the_image(gpu_ctx, oracle, sponza_
     """Arithmetic contract: a path whose throughput is exactly (0, 0, 0) ends.  With debug option traceDeadPaths
     the kernels keep tracing such paths like the GLSL does: more rays (the counters say how many), the same bits in
     every pixel with clampIndirect on, the reference's default (without it the traced paths' NaN sky terms survive:
-    DESIGN.md section 3) - on the small S-sponza-class scene with lights, foliage and IBL and on S-cornell, all three pipelines."""
+    DESIGN.md section 3) - on the small S-sponza-class scene with lights, foliage and IBL and on S-cornell, both pipelines."""
     from prosper_amd import capi
     for world, kw in ((sponza_small, dict(max_bounces=5, ibl=True, roulette=6)),
                       (scenes.cornell(with_skybox=True), dict(max_bounces=6, ibl=True, roulette=2))):
         w, h = 480, 270
         cam, fl = _camera(oracle, world, w, h)
         pc = default_pc(S, fl, **kw)
-        for create in (0, S.CREATE_MEGAKERNEL) + ((S.CREATE_PERSISTENT,) if capi.has_experiments() else ()):
+        for create in (0, S.CREATE_MEGAKERNEL):
             ctx = capi.Context(device=0, flags=create)
             try:
                 ctx.upload_scene(world)
@@ -1458,26 +1386,6 @@ def test_lds_resident_scene_equals_global_memory_traversal(gpu_ctx, oracle, corn
     gpu_ctx.render(pc, cam, w, h, frames=2)
     assert same_bits(gpu_ctx.read_hdr(), lds).all()
     capi.debug(noLdsScene=None)
-
-
-@needs_experiments
-@pytest.mark.parametrize("variant", ["1", "2", "3"])
-def test_ray_pool_trace_variants_equal_the_lane_owned_traversal(gpu_ctx, oracle, variant):
-    """wf_trace_pool (pt_trace_pool.hpp: the wave's rays in an LDS pool, debug option poolVariant) is an experiment kept
-    for its measurements; it must still produce the oracle's pixels - opaque and alpha-tested geometry, lights, sky."""
-    from prosper_amd import scenes
-    world = scenes.sponza_class(detail=0.25, lights=(24, 24), foliage=True, texture_size=64, sky_size=64)
-    w, h = 200, 120
-    cam, fl = _camera(oracle, world, w, h)
-    pc = default_pc(S, fl, max_bounces=4, ibl=True)
-    gpu_ctx.upload_scene(world)
-    want, _ = oracle.OracleScene(world).render(pc, cam, w, h)
-    capi.debug(poolVariant=int(variant))
-    gpu_ctx.render(pc, cam, w, h)
-    got = gpu_ctx.read_hdr()
-    capi.debug(poolVariant=None)
-    ok = same_bits(got, want).all(axis=2)
-    assert ok.all(), "%d of %d pixels differ" % ((~ok).sum(), ok.size)
 
 
 def test_full_sponza_class_scene_parity(gpu_ctx, oracle):
@@ -1570,34 +1478,3 @@ def test_full_size_flight_helmet_parity(gpu_ctx, oracle):
     from prosper_amd import flight_helmet
     got, _ = _full_size_parity(gpu_ctx, oracle, flight_helmet.load_fixture(), 2, "FlightHelmet")
     assert np.isfinite(got).all() and (got[..., 3] == 2).all()
-
-
-@needs_experiments
-def test_sparse_segments_traced_by_one_wave_give_the_same_pixels(gpu_ctx, oracle):
-    """debug option mergeLimit (pt_wavefront.hip RayMap; an experiment, off by default): where the four segments of a
-    workgroup hold few rays, one wave traces them all and the group's paths live in its first segment from then on.  Which
-    wave traces a ray changes no hit: the image of a sparse scene (a small lit object under a sky, most camera rays miss) is
-    the same at every limit, and the oracle's."""
-    world = scenes.sponza_class(lights=(4, 4), foliage=True, texture_size=32, sky_size=16, detail=0.25)
-    # pull the camera far back: the atrium covers a fraction of the image, the rest is sky
-    cam_def = dict(world.camera)
-    eye, target = np.asarray(cam_def["eye"], np.float64), np.asarray(cam_def["target"], np.float64)
-    cam_def["eye"] = tuple(target + (eye - target) * 6.0 + np.array([0.0, 25.0, 0.0]))
-    cam_def["zF"] = 1000.0
-    world.camera = cam_def
-    w, h = 512, 288
-    cam, fl = _camera(oracle, world, w, h)
-    pc = default_pc(S, fl, max_bounces=4, ibl=True)
-    gpu_ctx.upload_scene(world)
-    images = []
-    for limit in ("0", "64", "100000"):
-        capi.debug(mergeLimit=int(limit))
-        gpu_ctx.render(pc, cam, w, h, frames=4, flags=S.RENDER_PIPELINED)
-        images.append(gpu_ctx.read_hdr())
-    capi.debug(mergeLimit=None)
-    assert same_bits(images[0], images[1]).all() and same_bits(images[0], images[2]).all()
-    osc = oracle.OracleScene(world)
-    want = None
-    for frame in range(1, 5):
-        want, _ = osc.render(default_pc(S, fl, frame_index=frame, max_bounces=4, ibl=True, skip_history=(frame == 1)), cam, w, h, history=want)
-    assert same_bits(images[0], want).all()
