@@ -87,6 +87,21 @@ void prosper_host_tone_map_destroy(prosper_host_tone_map *pass);
 void prosper_host_tone_map_draw_ui(prosper_host_tone_map *pass, float exposure, float contrast);
 int prosper_host_tone_map_record(prosper_host_tone_map *pass, void *stream, void *deviceRgba8, size_t byteSize);
 
+/* render::rtdi::RtDirectIllumination (host/rt_direct_illumination.hpp; reference
+ * src/render/rtdi/RtDirectIllumination.hpp:19-58) on a context the scene was uploaded to (borrowed): drawUi's
+ * "Spatial reuse" toggle (default on), record = Camera::updateBuffer + initial reservoirs + optional spatial reuse +
+ * trace (prosper_pt_restir_di_record) + end of frame; returns the TracePC it pushed. */
+typedef struct prosper_host_rt_direct_illumination prosper_host_rt_direct_illumination;
+int prosper_host_rt_direct_illumination_create(prosper_pt_ctx *ctx, prosper_host_rt_direct_illumination **out);
+void prosper_host_rt_direct_illumination_destroy(prosper_host_rt_direct_illumination *pass);
+void prosper_host_rt_direct_illumination_draw_ui(prosper_host_rt_direct_illumination *pass, int spatialReuse);
+void prosper_host_rt_direct_illumination_recompile_shaders(prosper_host_rt_direct_illumination *pass);
+void prosper_host_rt_direct_illumination_release_preserved(prosper_host_rt_direct_illumination *pass);
+int prosper_host_rt_direct_illumination_record(
+    prosper_host_rt_direct_illumination *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    const prosper_pt_restir_inputs *gbuffer, int resetAccumulation, uint32_t drawType, uint32_t nextFrame, void *stream,
+    prosper_pt_restir_trace_pc *outPushConstants);
+
 #ifdef __cplusplus
 }
 #endif

@@ -521,6 +521,40 @@ int prosper_pt_restir_di_trace(
     prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
     uint32_t height, const prosper_pt_restir_inputs *inputs, void *stream);
 
+/* The two passes that produce the reservoirs the trace reads (src/render/rtdi/RtDirectIllumination.cpp:70-115), same
+ * surface reconstruction, seeded per pixel with (px, py, frameIndex):
+ *   PROSPER_PT_RESTIR_INITIAL  res/shader/restir_di/initial_reservoirs.comp: RIS over 5 uniformly drawn lights,
+ *                              target luminance(irradiance * BRDF * NoL), no visibility.  inputs->reservoirs is ignored.
+ *   PROSPER_PT_RESTIR_SPATIAL  res/shader/restir_di/spatial_reuse.comp: resamples up to 5 neighbour reservoirs of
+ *                              inputs->reservoirs (disc offsets, 10 % depth and 0.9 normal tests).
+ * Writes width*height float2 reservoirs to `device_out_reservoirs` (device memory, 8-byte aligned; it must not be
+ * inputs->reservoirs), or with NULL to a context-owned buffer (prosper_pt_get_restir_reservoirs_device_ptr). */
+enum
+{
+    PROSPER_PT_RESTIR_INITIAL = 0,
+    PROSPER_PT_RESTIR_SPATIAL = 1,
+};
+int prosper_pt_restir_di_resample(
+    prosper_pt_ctx *ctx, uint32_t stage, uint32_t frameIndex, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const prosper_pt_restir_inputs *inputs, void *device_out_reservoirs, void *stream);
+/* RtDirectIllumination::record: initial reservoirs, the spatial pass when recordFlags has
+ * PROSPER_PT_RESTIR_SPATIAL_REUSE, then prosper_pt_restir_di_trace's pass, all with pc->frameIndex, on `stream`.
+ * inputs->reservoirs is ignored: the reservoirs live in two context-owned device buffers (8 bytes per pixel each).
+ * Host G-buffer inputs are copied once per call.  All three kernels read the same scene and light version. */
+enum
+{
+    PROSPER_PT_RESTIR_SPATIAL_REUSE = 1u << 0,
+};
+int prosper_pt_restir_di_record(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, void *stream);
+/* The reservoirs the last prosper_pt_restir_di_record traced with (or the context-owned buffer the last
+ * prosper_pt_restir_di_resample wrote): width*height float2 in device memory, valid until the next record / resample
+ * with a larger extent or destroy.  *out_bytes may be NULL. */
+int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes);
+/* Synchronises `stream` and copies those reservoirs (byte_size = width*height*8 of the call that made them) to host memory. */
+int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, size_t byte_size, void *stream);
+
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of
  * per-tile HDR buffers".)  The reference renders the whole image on one GPU and asserts renderArea.offset == 0

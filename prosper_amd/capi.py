@@ -78,6 +78,12 @@ def lib():
     L.prosper_pt_blit_rgba16f.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_restir_di_trace.argtypes = [
         vp, C.POINTER(S.RestirTracePC), C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
+    L.prosper_pt_restir_di_resample.argtypes = [
+        vp, u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp, vp]
+    L.prosper_pt_restir_di_record.argtypes = [
+        vp, C.POINTER(S.RestirTracePC), u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
+    L.prosper_pt_get_restir_reservoirs_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.prosper_pt_read_restir_reservoirs.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -132,6 +138,17 @@ def lib():
     L.prosper_host_rt_reference_release_preserved.restype = None
     L.prosper_host_rt_reference_record.argtypes = [
         vp, vp, u32, u32, C.POINTER(RecordOptions), u32, C.POINTER(S.TileDesc), u32, vp, C.POINTER(S.ReferencePC)]
+    L.prosper_host_rt_direct_illumination_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_rt_direct_illumination_destroy.argtypes = [vp]
+    L.prosper_host_rt_direct_illumination_destroy.restype = None
+    L.prosper_host_rt_direct_illumination_draw_ui.argtypes = [vp, C.c_int]
+    L.prosper_host_rt_direct_illumination_draw_ui.restype = None
+    L.prosper_host_rt_direct_illumination_recompile_shaders.argtypes = [vp]
+    L.prosper_host_rt_direct_illumination_recompile_shaders.restype = None
+    L.prosper_host_rt_direct_illumination_release_preserved.argtypes = [vp]
+    L.prosper_host_rt_direct_illumination_release_preserved.restype = None
+    L.prosper_host_rt_direct_illumination_record.argtypes = [
+        vp, vp, u32, u32, C.POINTER(S.RestirInputs), C.c_int, u32, u32, vp, C.POINTER(S.RestirTracePC)]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -206,6 +223,7 @@ class Context:
         self._base_debug = None
         self._debug_seen = -1
         self._world = None
+        self._restir_extent = None
         if _borrowed is not None:
             self._h = C.c_void_p(_borrowed)
             return
@@ -394,6 +412,71 @@ class Context:
         inp = S.RestirInputs(ar_ptr, nm_ptr, depth_ptr, res_ptr, 1, 0)
         _check(lib().prosper_pt_restir_di_trace(self._h, C.byref(pc), C.byref(camera), width, height, C.byref(inp),
                                                 C.c_void_p(stream)))
+
+    @staticmethod
+    def _restir_host_inputs(albedo_roughness, normal_metallic, depth, reservoirs=None):
+        ar = np.ascontiguousarray(albedo_roughness, np.float32)
+        nm = np.ascontiguousarray(normal_metallic, np.float32)
+        dp = np.ascontiguousarray(depth, np.float32)
+        h, w = dp.shape
+        assert ar.shape == (h, w, 4) and nm.shape == (h, w, 4)
+        rs = None
+        if reservoirs is not None:
+            rs = np.ascontiguousarray(reservoirs, np.float32)
+            assert rs.shape == (h, w, 2)
+        inp = S.RestirInputs(ar.ctypes.data, nm.ctypes.data, dp.ctypes.data, None if rs is None else rs.ctypes.data, 0, 0)
+        return inp, (ar, nm, dp, rs), w, h
+
+    def restir_di_resample(self, stage, frame_index, camera, albedo_roughness, normal_metallic, depth, reservoirs=None,
+                           stream=None):
+        """One resampling pass (S.RESTIR_INITIAL / S.RESTIR_SPATIAL) over host G-buffer arrays shaped as for
+        restir_di_trace (`reservoirs` [h, w, 2]: the spatial pass's input).  Returns the reservoirs, float32 [h, w, 2]
+        (the light index's bits in [..., 0])."""
+        inp, keep, w, h = self._restir_host_inputs(albedo_roughness, normal_metallic, depth, reservoirs)
+        _check(lib().prosper_pt_restir_di_resample(self._h, stage, frame_index, C.byref(camera), w, h, C.byref(inp), None,
+                                                   C.c_void_p(stream)))
+        del keep
+        self._restir_extent = (w, h)
+        return self.read_restir_reservoirs(stream)
+
+    def restir_di_resample_device(self, stage, frame_index, camera, width, height, ar_ptr, nm_ptr, depth_ptr,
+                                  res_ptr=None, out_ptr=None, stream=None):
+        """Same with device-resident inputs; writes `out_ptr` (device) or, with None, the context's reservoirs."""
+        inp = S.RestirInputs(ar_ptr, nm_ptr, depth_ptr, res_ptr, 1, 0)
+        _check(lib().prosper_pt_restir_di_resample(self._h, stage, frame_index, C.byref(camera), width, height,
+                                                   C.byref(inp), C.c_void_p(out_ptr), C.c_void_p(stream)))
+        if out_ptr is None:
+            self._restir_extent = (width, height)
+
+    def restir_di_record(self, pc, camera, albedo_roughness, normal_metallic, depth, spatial_reuse=True, stream=None):
+        """RtDirectIllumination::record over host G-buffer arrays: initial reservoirs, optional spatial reuse, trace."""
+        inp, keep, w, h = self._restir_host_inputs(albedo_roughness, normal_metallic, depth)
+        flags = S.RESTIR_SPATIAL_REUSE if spatial_reuse else 0
+        _check(lib().prosper_pt_restir_di_record(self._h, C.byref(pc), flags, C.byref(camera), w, h, C.byref(inp),
+                                                 C.c_void_p(stream)))
+        del keep
+        self._restir_extent = (w, h)
+
+    def restir_di_record_device(self, pc, camera, width, height, ar_ptr, nm_ptr, depth_ptr, spatial_reuse=True,
+                                stream=None):
+        inp = S.RestirInputs(ar_ptr, nm_ptr, depth_ptr, None, 1, 0)
+        flags = S.RESTIR_SPATIAL_REUSE if spatial_reuse else 0
+        _check(lib().prosper_pt_restir_di_record(self._h, C.byref(pc), flags, C.byref(camera), width, height,
+                                                 C.byref(inp), C.c_void_p(stream)))
+        self._restir_extent = (width, height)
+
+    def restir_reservoirs_device_ptr(self):
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(lib().prosper_pt_get_restir_reservoirs_device_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def read_restir_reservoirs(self, stream=None, extent=None):
+        """The reservoirs the last record traced with (or the last resample wrote to the context's buffers), float32
+        [h, w, 2]; synchronises `stream`.  `extent` (w, h): of a record made through another handle of the context."""
+        w, h = extent or self._restir_extent
+        out = np.empty((h, w, 2), np.float32)
+        _check(lib().prosper_pt_read_restir_reservoirs(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
 
     def set_tone_map_lut(self, lut_r9g9b9e5):
         """lut: uint32 [dim, dim, dim] (z, y, x) R9G9B9E5 texels, e.g. from prosper_amd.dds.read_lut."""

@@ -845,6 +845,8 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
         if (slot.stackOverflow) (void)hipFree(slot.stackOverflow);
     }
     if (ctx->restirScratch) (void)hipFree(ctx->restirScratch);
+    for (void *r : ctx->restirReservoirs)
+        if (r) (void)hipFree(r);
     if (ctx->toneLut) (void)hipFree(ctx->toneLut);
     if (ctx->toneScratch) (void)hipFree(ctx->toneScratch);
     for (auto &e : ctx->events)
@@ -1551,13 +1553,13 @@ int prosper_pt_blit_rgba16f(prosper_pt_ctx *ctx, uint16_t *host_rgba16f, size_t 
     return PROSPER_PT_OK;
 }
 
-int prosper_pt_restir_di_trace(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height, const prosper_pt_restir_inputs *in, void *stream)
+// ---- ReSTIR-DI (src/render/rtdi/RtDirectIllumination.cpp:70-115) ----
+
+// What every ReSTIR entry checks of the scene before its arguments' extents: a scene, the meshes a worker finished
+// meanwhile, no failed transform update.
+static int restir_check_scene(prosper_pt_ctx *ctx, const char *what)
 {
-    if (!ctx || !pc || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth || !in->reservoirs)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: null argument");
-    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_restir_di_trace called before prosper_pt_upload_scene");
+    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + " called before prosper_pt_upload_scene");
     if (ctx->meshBuild)
     {
         const int prc = poll_mesh_build(ctx, false);
@@ -1565,19 +1567,100 @@ int prosper_pt_restir_di_trace(
     }
     if (ctx->accel && ctx->accel->stale && !ctx->accel->pending)
         return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_update_transforms failed: update the transforms again (or upload the scene) before tracing");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    return PROSPER_PT_OK;
+}
+
+// The pending transform, light and material updates take effect on `s` before the call's first kernel: every kernel
+// the call launches after this reads the same scene and light version (mark_versions_read after the last one).
+static int restir_flush(prosper_pt_ctx *ctx, hipStream_t s)
+{
     PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    int frc = flush_pending_update(ctx, s);
+    if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, s);
+    if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, s);
+    if (frc != PROSPER_PT_OK) return frc;
+    if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
+    if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
+    if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
+    return PROSPER_PT_OK;
+}
+
+static RestirCamera restir_camera(const prosper_CameraUniforms *camera)
+{
+    RestirCamera c;
+    c.eye[0] = camera->eye.x;
+    c.eye[1] = camera->eye.y;
+    c.eye[2] = camera->eye.z;
+    std::memcpy(c.clipToWorld, &camera->clipToWorld, 64);
+    float c2c[16];
+    std::memcpy(c2c, &camera->cameraToClip, 64);
+    c.cameraToClip22 = c2c[2 * 4 + 2]; // column 2, row 2
+    c.cameraToClip32 = c2c[3 * 4 + 2]; // column 3, row 2
+    return c;
+}
+
+// The G-buffer (and, with `withReservoirs`, the reservoirs) on the device: host inputs are copied into one scratch
+// allocation, 16 + 16 + 8 + 4 bytes per pixel.
+struct RestirDeviceInputs
+{
+    const void *ar, *nm, *res;
+    const float *depth;
+};
+static int restir_device_inputs(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_inputs *in, size_t pixels, bool withReservoirs, hipStream_t s,
+    RestirDeviceInputs &out)
+{
+    out.ar = in->albedoRoughness;
+    out.nm = in->normalMetallic;
+    out.res = in->reservoirs;
+    out.depth = in->nonLinearDepth;
+    if (in->onDevice) return PROSPER_PT_OK;
+    const size_t need = pixels * 44u + 64u;
+    if (ctx->restirScratchBytes < need)
     {
-        int frc = flush_pending_update(ctx, s);
-        if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, s);
-        if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, s);
-        if (frc != PROSPER_PT_OK) return frc;
-        if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
-        if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
-        if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
+        PPT_HIP(hipStreamSynchronize(s));
+        if (ctx->restirScratch) PPT_HIP(hipFree(ctx->restirScratch));
+        ctx->restirScratch = nullptr;
+        ctx->restirScratchBytes = 0;
+        PPT_HIP(hipMalloc(&ctx->restirScratch, need));
+        ctx->restirScratchBytes = need;
     }
+    uint8_t *base = static_cast<uint8_t *>(ctx->restirScratch);
+    PPT_HIP(hipMemcpyAsync(base, in->albedoRoughness, pixels * 16u, hipMemcpyHostToDevice, s));
+    PPT_HIP(hipMemcpyAsync(base + pixels * 16u, in->normalMetallic, pixels * 16u, hipMemcpyHostToDevice, s));
+    if (withReservoirs) PPT_HIP(hipMemcpyAsync(base + pixels * 32u, in->reservoirs, pixels * 8u, hipMemcpyHostToDevice, s));
+    PPT_HIP(hipMemcpyAsync(base + pixels * 40u, in->nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
+    out.ar = base;
+    out.nm = base + pixels * 16u;
+    out.res = base + pixels * 32u;
+    out.depth = reinterpret_cast<const float *>(base + pixels * 40u);
+    return PROSPER_PT_OK;
+}
+
+// The two context-owned reservoir buffers, grown like restirScratch (what still reads them on `s` finishes first).
+static int restir_reservoir_buffers(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s)
+{
+    const size_t need = pixels * 8u;
+    if (ctx->restirReservoirBytes >= need && ctx->restirReservoirs[0]) return PROSPER_PT_OK;
+    PPT_HIP(hipStreamSynchronize(s));
+    for (void *&r : ctx->restirReservoirs)
+    {
+        if (r) PPT_HIP(hipFree(r));
+        r = nullptr;
+    }
+    ctx->restirReservoirBytes = 0;
+    ctx->restirLastReservoirs = nullptr;
+    ctx->restirLastReservoirBytes = 0;
+    for (void *&r : ctx->restirReservoirs) PPT_HIP(hipMalloc(&r, need));
+    ctx->restirReservoirBytes = need;
+    return PROSPER_PT_OK;
+}
+
+// The trace pass over device inputs: the HDR image, the traversal stacks, the launch.
+static int restir_trace(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const RestirDeviceInputs &in, hipStream_t s)
+{
     const size_t pixels = (size_t)width * height;
     const size_t bytes = pixels * sizeof(float4);
     if (ctx->externalHdr)
@@ -1606,43 +1689,145 @@ int prosper_pt_restir_di_trace(
     ctx->stripeCount = 1;
     wait_for_gather_before_writing_tile(ctx, s);
 
-    const void *ar = in->albedoRoughness, *nm = in->normalMetallic, *res = in->reservoirs;
-    const float *depth = in->nonLinearDepth;
-    if (!in->onDevice)
-    {
-        // host inputs: one scratch allocation, 16 + 16 + 4 + 8 bytes per pixel
-        const size_t need = pixels * 44u + 64u;
-        if (ctx->restirScratchBytes < need)
-        {
-            PPT_HIP(hipStreamSynchronize(s));
-            if (ctx->restirScratch) PPT_HIP(hipFree(ctx->restirScratch));
-            ctx->restirScratch = nullptr;
-            ctx->restirScratchBytes = 0;
-            PPT_HIP(hipMalloc(&ctx->restirScratch, need));
-            ctx->restirScratchBytes = need;
-        }
-        uint8_t *base = static_cast<uint8_t *>(ctx->restirScratch);
-        PPT_HIP(hipMemcpyAsync(base, in->albedoRoughness, pixels * 16u, hipMemcpyHostToDevice, s));
-        PPT_HIP(hipMemcpyAsync(base + pixels * 16u, in->normalMetallic, pixels * 16u, hipMemcpyHostToDevice, s));
-        PPT_HIP(hipMemcpyAsync(base + pixels * 32u, in->reservoirs, pixels * 8u, hipMemcpyHostToDevice, s));
-        PPT_HIP(hipMemcpyAsync(base + pixels * 40u, in->nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
-        ar = base;
-        nm = base + pixels * 16u;
-        res = base + pixels * 32u;
-        depth = reinterpret_cast<const float *>(base + pixels * 40u);
-    }
     int32_t *ovf = nullptr;
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), s, &ovf);
     if (orc != PROSPER_PT_OK) return orc;
     wait_for_slot(ctx->slots[0], s);
-    const float eye[3] = {camera->eye.x, camera->eye.y, camera->eye.z};
-    float c2w[16];
-    std::memcpy(c2w, &camera->clipToWorld, 64);
     launch_restir_di_trace(
-        ctx->scene, pc->drawType, pc->frameIndex, pc->flags, width, height, eye, c2w, ar, nm, depth, res, ctx->hdr, ovf, s);
+        ctx->scene, pc->drawType, pc->frameIndex, pc->flags, width, height, restir_camera(camera), in.ar, in.nm, in.depth,
+        in.res, ctx->hdr, ovf, s);
     release_slot(ctx->slots[0], s);
     PPT_HIP(hipGetLastError());
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_restir_di_trace(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const prosper_pt_restir_inputs *in, void *stream)
+{
+    if (!ctx || !pc || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth || !in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: null argument");
+    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_trace");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = restir_flush(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    RestirDeviceInputs din;
+    rc = restir_device_inputs(ctx, in, (size_t)width * height, true, s, din);
+    if (rc == PROSPER_PT_OK) rc = restir_trace(ctx, pc, camera, width, height, din, s);
+    if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_restir_di_resample(
+    prosper_pt_ctx *ctx, uint32_t stage, uint32_t frameIndex, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const prosper_pt_restir_inputs *in, void *device_out_reservoirs, void *stream)
+{
+    if (!ctx || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: null argument");
+    if (stage != PROSPER_PT_RESTIR_INITIAL && stage != PROSPER_PT_RESTIR_SPATIAL)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: unknown stage");
+    const bool spatial = stage == PROSPER_PT_RESTIR_SPATIAL;
+    if (spatial && !in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass needs input reservoirs");
+    if (device_out_reservoirs && (reinterpret_cast<uintptr_t>(device_out_reservoirs) & 7u))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: output reservoirs must be 8-byte aligned");
+    if (spatial && in->onDevice && device_out_reservoirs == in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass cannot write its input");
+    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_resample");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: empty extent");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pixels = (size_t)width * height;
+    int rc = restir_flush(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    void *out = device_out_reservoirs;
+    if (!out)
+    {
+        rc = restir_reservoir_buffers(ctx, pixels, s);
+        if (rc != PROSPER_PT_OK) return rc;
+        // the spatial pass writes the buffer it does not read
+        out = spatial && in->onDevice && in->reservoirs == ctx->restirReservoirs[1] ? ctx->restirReservoirs[0]
+                                                                                    : ctx->restirReservoirs[spatial ? 1 : 0];
+    }
+    RestirDeviceInputs din;
+    rc = restir_device_inputs(ctx, in, pixels, spatial, s, din);
+    if (rc != PROSPER_PT_OK) return rc;
+    const RestirCamera cam = restir_camera(camera);
+    if (spatial)
+        launch_restir_di_spatial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, din.res, out, s);
+    else
+        launch_restir_di_initial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, out, s);
+    PPT_HIP(hipGetLastError());
+    if (!device_out_reservoirs)
+    {
+        ctx->restirLastReservoirs = out;
+        ctx->restirLastReservoirBytes = pixels * 8u;
+    }
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_restir_di_record(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, void *stream)
+{
+    if (!ctx || !pc || !camera || !gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: null argument");
+    if (recordFlags & ~(uint32_t)PROSPER_PT_RESTIR_SPATIAL_REUSE)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: unknown record flags");
+    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_record");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pixels = (size_t)width * height;
+    int rc = restir_flush(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = restir_reservoir_buffers(ctx, pixels, s);
+    RestirDeviceInputs din;
+    if (rc == PROSPER_PT_OK) rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
+    if (rc != PROSPER_PT_OK) return rc;
+    const RestirCamera cam = restir_camera(camera);
+    // InitialReservoirs, then SpatialReuse when the toggle is on, then Trace (RtDirectIllumination.cpp:80-109)
+    launch_restir_di_initial(
+        ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, ctx->restirReservoirs[0], s);
+    din.res = ctx->restirReservoirs[0];
+    if (recordFlags & PROSPER_PT_RESTIR_SPATIAL_REUSE)
+    {
+        launch_restir_di_spatial(
+            ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, ctx->restirReservoirs[0],
+            ctx->restirReservoirs[1], s);
+        din.res = ctx->restirReservoirs[1];
+    }
+    PPT_HIP(hipGetLastError());
+    ctx->restirLastReservoirs = din.res;
+    ctx->restirLastReservoirBytes = pixels * 8u;
+    rc = restir_trace(ctx, pc, camera, width, height, din, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes)
+{
+    if (!ctx || !out_ptr) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_restir_reservoirs_device_ptr: null argument");
+    if (!ctx->restirLastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
+    *out_ptr = const_cast<void *>(ctx->restirLastReservoirs);
+    if (out_bytes) *out_bytes = ctx->restirLastReservoirBytes;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, size_t byte_size, void *stream)
+{
+    if (!ctx || !host_float2) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: null argument");
+    if (!ctx->restirLastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
+    if (byte_size != ctx->restirLastReservoirBytes)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: size differs from the reservoirs'");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(host_float2, ctx->restirLastReservoirs, byte_size, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_set_tone_map_lut(prosper_pt_ctx *ctx, const uint32_t *lut, uint32_t dim)

@@ -321,6 +321,10 @@ struct prosper_pt_ctx
 
     void *restirScratch = nullptr; // device copies of host G-buffer inputs (prosper_pt_restir_di_trace)
     size_t restirScratchBytes = 0;
+    void *restirReservoirs[2] = {}; // ping-pong reservoir buffers of the ReSTIR-DI passes (width*height float2 each)
+    size_t restirReservoirBytes = 0; // of each
+    const void *restirLastReservoirs = nullptr; // prosper_pt_get_restir_reservoirs_device_ptr
+    size_t restirLastReservoirBytes = 0;
     uint32_t *toneLut = nullptr; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     void *toneScratch = nullptr; // RGBA8 output when the caller only wants a host copy

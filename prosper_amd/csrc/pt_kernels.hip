@@ -458,9 +458,12 @@ void launch_blit_rgba16f(const float4 *in, void *out, uint32_t count, hipStream_
 }
 
 // ------------------------------------------------------------------------------------------
-// ReSTIR-DI trace (res/shader/rt/direct_illumination/main.rgen:44-165, src/render/rtdi/Trace.cpp:297): a second
-// client of the traversal.  One lane per pixel, a wave per 8x8 tile: surface from the G-buffer, the pixel's
-// reservoir light, one shadow ray (any-hit included), BRDF, running mean into the HDR image.
+// ReSTIR-DI (src/render/rtdi/RtDirectIllumination.cpp:70-115): three passes over the G-buffer, one lane per pixel,
+// 256-lane blocks over 16x16 tiles (a wave per 8x8 quarter) dealt to the XCDs in contiguous bands (restir_tile).
+//   restir_di_initial_kernel   RIS over 5 uniformly drawn lights      (restir_di/initial_reservoirs.comp)
+//   restir_di_spatial_kernel   resamples 5 neighbour reservoirs        (restir_di/spatial_reuse.comp)
+//   restir_di_trace_kernel     the reservoir's light, one shadow ray   (rt/direct_illumination/main.rgen:44-165,
+//                              a second client of the traversal; src/render/rtdi/Trace.cpp:297)
 // ------------------------------------------------------------------------------------------
 
 // scene/material.glsl:20-32
@@ -479,30 +482,37 @@ struct RestirParams
     uint32_t drawType, frameIndex, flags, width, height;
     float eye[3];
     float clipToWorld[16]; // column-major
+    float cameraToClip22, cameraToClip32; // linearizeDepth (scene/camera.glsl:11-22)
 };
 
-__global__ __launch_bounds__(256) void restir_di_trace_kernel(
-    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
-    const float *__restrict__ nonLinearDepth, const float2 *__restrict__ reservoirs, float4 *__restrict__ hdr,
-    int32_t *__restrict__ stackOverflow)
+// Block b and b + 8 run on the same XCD: the tiles [x * perXcd, (x + 1) * perXcd) go to XCD x, so the neighbours the
+// spatial pass reads mostly sit in the L2 of the XCD that reads them.  False past the last tile.
+PPT_D bool restir_pixel(const RestirParams &p, uint32_t &px, uint32_t &py)
 {
-    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
     const uint32_t tilesX = (p.width + 15u) / 16u, tilesY = (p.height + 15u) / 16u;
     const uint32_t numTiles = tilesX * tilesY;
     const uint32_t perXcd = (numTiles + 7u) / 8u;
     const uint32_t tile = (blockIdx.x % 8u) * perXcd + (blockIdx.x / 8u);
-    if (tile >= numTiles) return;
+    if (tile >= numTiles) return false;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t px = (tile % tilesX) * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t py = (tile / tilesX) * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
-                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
-    if (px >= p.width || py >= p.height) return;
-    const size_t i = (size_t)py * p.width + px;
+    px = (tile % tilesX) * 16u + (wave & 1u) * 8u + (lane & 7u);
+    py = (tile / tilesX) * 16u + (wave >> 1) * 8u + (lane >> 3);
+    return true;
+}
 
-    // main.rgen:113-129
+// scene/camera.glsl:11-22
+PPT_D float linearize_depth(const RestirParams &p, float nonLinearDepth)
+{
+    return -p.cameraToClip32 / (nonLinearDepth + p.cameraToClip22);
+}
+
+// The VisibleSurface of a G-buffer texel, as all three passes build it (main.rgen:113-129,
+// initial_reservoirs.comp:70-87, spatial_reuse.comp:145-162): uv = px / size (no half-pixel offset), worldPos through
+// clipToWorld, the signed-octahedral normal, alpha = -1.
+PPT_D Surface restir_surface(
+    const RestirParams &p, uint32_t px, uint32_t py, float depth, const float4 &ar, const float4 &nm)
+{
     const f2 uv = f2{(float)px / (float)p.width, (float)py / (float)p.height};
-    const float depth = nonLinearDepth[i];
     Surface sf;
     {
         // worldPos, scene/camera.glsl:27-33
@@ -515,7 +525,6 @@ __global__ __launch_bounds__(256) void restir_di_trace_kernel(
         sf.positionWS = f3{vx, vy, vz} * (1.0f / vw);
     }
     sf.invViewRayWS = normalize(f3{p.eye[0], p.eye[1], p.eye[2]} - sf.positionWS);
-    const float4 ar = albedoRoughness[i], nm = normalMetallic[i];
     sf.material.albedo = f3{ar.x, ar.y, ar.z};
     sf.material.roughness = ar.w;
     sf.material.normal = signed_oct_decode(f3{nm.x, nm.y, nm.w});
@@ -524,6 +533,144 @@ __global__ __launch_bounds__(256) void restir_di_trace_kernel(
     sf.normalWS = sf.material.normal;
     sf.uv = f2{0.0f, 0.0f};
     sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
+    return sf;
+}
+
+// pHatLight, restir_di/resampling_phat.glsl: luminance (common/math.glsl:15) of the unshadowed contribution
+PPT_D float restir_p_hat(const DeviceScene &s, const Surface &sf, uint32_t lightIndex)
+{
+    f3 l, irradiance;
+    float d;
+    sample_light(s, sf.positionWS, lightIndex, l, d, irradiance);
+    return dot(f3{0.299f, 0.587f, 0.114f}, irradiance * eval_brdf_times_nol(l, sf));
+}
+
+// restir_di/reservoir.glsl packReservoir
+PPT_D float2 pack_reservoir(int32_t lightIndex, float weight)
+{
+    return make_float2(u2f((uint32_t)lightIndex), weight);
+}
+
+// initial_reservoirs.comp:31-60 initialLightCandidate.  The pHat of the pick is kept rather than evaluated again: the
+// same function of the same light, the same bits.
+__global__ __launch_bounds__(256) void restir_di_initial_kernel(
+    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
+    const float *__restrict__ nonLinearDepth, float2 *__restrict__ outReservoirs)
+{
+    uint32_t px, py;
+    if (!restir_pixel(p, px, py) || px >= p.width || py >= p.height) return;
+    const size_t i = (size_t)py * p.width + px;
+    const Surface sf = restir_surface(p, px, py, nonLinearDepth[i], albedoRoughness[i], normalMetallic[i]);
+    Rng rng{px, py, p.frameIndex}; // :72
+
+    const int32_t lightCount = 1 + (int32_t)(s.pointLightCount + s.spotLightCount);
+    int32_t chosen = -1;
+    float chosenPHat = 0.0f;
+    float sumResamplingWeights = 0.0f;
+    for (int k = 0; k < 5; ++k)
+    {
+        int32_t lightIndex = (int32_t)(rng.rnd01() * (float)lightCount);
+        lightIndex = lightIndex < lightCount - 1 ? lightIndex : lightCount - 1;
+        const float pHat = restir_p_hat(s, sf, (uint32_t)lightIndex);
+        // misWeight 1 / 5, unbiasedContributionWeight = lightCount
+        const float resamplingWeight = (0.2f * pHat) * (float)lightCount;
+        sumResamplingWeights += resamplingWeight;
+        if (rng.rnd01() < resamplingWeight / sumResamplingWeights)
+        {
+            chosen = lightIndex;
+            chosenPHat = pHat;
+        }
+    }
+    outReservoirs[i] = pack_reservoir(chosen, chosen >= 0 ? sumResamplingWeights / chosenPHat : 0.0f);
+}
+
+// spatial_reuse.comp:33-134 resampleReservoirSpatially.  The five slots are unrolled so that their reservoirs stay in
+// registers; every random number is drawn in the GLSL's order (all the disc offsets first, then the accept tests).
+__global__ __launch_bounds__(256) void restir_di_spatial_kernel(
+    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
+    const float *__restrict__ nonLinearDepth, const float2 *__restrict__ inReservoirs, float2 *__restrict__ outReservoirs)
+{
+    uint32_t px, py;
+    if (!restir_pixel(p, px, py) || px >= p.width || py >= p.height) return;
+    const size_t i = (size_t)py * p.width + px;
+    const float depth = nonLinearDepth[i];
+    const Surface sf = restir_surface(p, px, py, depth, albedoRoughness[i], normalMetallic[i]);
+    const float linearDepth = linearize_depth(p, depth);
+    Rng rng{px, py, p.frameIndex}; // :147, the same stream the initial pass of this frame started
+
+    int32_t sampleIndex[5];
+    float sampleWeight[5];
+    uint32_t validSampleCount = 0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+    {
+        sampleIndex[k] = -1;
+        sampleWeight[k] = 0.0f;
+        for (int kill = 0; kill < 5; ++kill)
+        {
+            // uniformSampleDisk (common/sampling.glsl:8-13) * spatialRadius * 2 - spatialRadius, truncated
+            const f2 u = rng.rnd2d01();
+            const float r = sqrt_(u.x);
+            float sn, cs;
+            sincos_(kTwoPi * u.y, sn, cs);
+            const int32_t ox = (int32_t)(((r * cs) * 30.0f) * 2.0f - 30.0f);
+            const int32_t oy = (int32_t)(((r * sn) * 30.0f) * 2.0f - 30.0f);
+            const int32_t qx = (int32_t)px + ox, qy = (int32_t)py + oy;
+            if (qx <= 0 || qy <= 0 || qx >= (int32_t)p.width || qy >= (int32_t)p.height) continue;
+            const size_t q = (size_t)qy * p.width + (size_t)qx;
+            // 10 % depth difference (a NaN passes)
+            if (fabs_(1.0f - linearize_depth(p, nonLinearDepth[q]) / linearDepth) > 0.1f) continue;
+            const float4 nm = normalMetallic[q];
+            if (dot(signed_oct_decode(f3{nm.x, nm.y, nm.w}), sf.normalWS) < 0.9f) continue;
+            const float2 packed = inReservoirs[q];
+            sampleIndex[k] = (int32_t)f2u(packed.x);
+            sampleWeight[k] = packed.y;
+            validSampleCount++;
+            break;
+        }
+    }
+
+    int32_t chosen = -1;
+    float chosenPHat = 0.0f;
+    float sumResamplingWeights = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+    {
+        if (sampleIndex[k] < 0) continue;
+        const float pHat = restir_p_hat(s, sf, (uint32_t)sampleIndex[k]);
+        const float resamplingWeight = pHat * sampleWeight[k];
+        sumResamplingWeights += resamplingWeight;
+        if (rng.rnd01() < resamplingWeight / sumResamplingWeights)
+        {
+            chosen = sampleIndex[k];
+            chosenPHat = pHat;
+        }
+    }
+    float weight = 0.0f;
+    if (chosen >= 0)
+    {
+        const float misWeight = 1.0f / (float)validSampleCount;
+        weight = (misWeight * sumResamplingWeights) / chosenPHat;
+    }
+    outReservoirs[i] = pack_reservoir(chosen, weight);
+}
+
+__global__ __launch_bounds__(256) void restir_di_trace_kernel(
+    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
+    const float *__restrict__ nonLinearDepth, const float2 *__restrict__ reservoirs, float4 *__restrict__ hdr,
+    int32_t *__restrict__ stackOverflow)
+{
+    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
+    uint32_t px, py;
+    if (!restir_pixel(p, px, py)) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
+                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
+    if (px >= p.width || py >= p.height) return;
+    const size_t i = (size_t)py * p.width + px;
+
+    // main.rgen:113-129
+    const Surface sf = restir_surface(p, px, py, nonLinearDepth[i], albedoRoughness[i], normalMetallic[i]);
 
     if (p.drawType != PROSPER_DRAW_TYPE_DEFAULT)
     {
@@ -568,24 +715,58 @@ uint32_t restir_grid_blocks(uint32_t width, uint32_t height)
     return ((numTiles + 7u) / 8u) * 8u;
 }
 
-void launch_restir_di_trace(
-    const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
-    const float eye[3], const float clipToWorld[16], const void *albedoRoughness, const void *normalMetallic,
-    const float *nonLinearDepth, const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream)
+static RestirParams restir_params(
+    uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height, const RestirCamera &cam)
 {
-    if (width == 0 || height == 0) return;
     RestirParams p;
     p.drawType = drawType;
     p.frameIndex = frameIndex;
     p.flags = flags;
     p.width = width;
     p.height = height;
-    for (int k = 0; k < 3; ++k) p.eye[k] = eye[k];
-    for (int k = 0; k < 16; ++k) p.clipToWorld[k] = clipToWorld[k];
+    for (int k = 0; k < 3; ++k) p.eye[k] = cam.eye[k];
+    for (int k = 0; k < 16; ++k) p.clipToWorld[k] = cam.clipToWorld[k];
+    p.cameraToClip22 = cam.cameraToClip22;
+    p.cameraToClip32 = cam.cameraToClip32;
+    return p;
+}
+
+void launch_restir_di_initial(
+    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, void *outReservoirs,
+    hipStream_t stream)
+{
+    if (width == 0 || height == 0) return;
     hipLaunchKernelGGL(
-        restir_di_trace_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, p,
-        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
-        static_cast<const float2 *>(reservoirs), hdr, stackOverflow);
+        restir_di_initial_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
+        restir_params(0, frameIndex, 0, width, height, cam), static_cast<const float4 *>(albedoRoughness),
+        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<float2 *>(outReservoirs));
+}
+
+void launch_restir_di_spatial(
+    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, const void *inReservoirs,
+    void *outReservoirs, hipStream_t stream)
+{
+    if (width == 0 || height == 0) return;
+    hipLaunchKernelGGL(
+        restir_di_spatial_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
+        restir_params(0, frameIndex, 0, width, height, cam), static_cast<const float4 *>(albedoRoughness),
+        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<const float2 *>(inReservoirs),
+        static_cast<float2 *>(outReservoirs));
+}
+
+void launch_restir_di_trace(
+    const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
+    const RestirCamera &cam, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream)
+{
+    if (width == 0 || height == 0) return;
+    hipLaunchKernelGGL(
+        restir_di_trace_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
+        restir_params(drawType, frameIndex, flags, width, height, cam), static_cast<const float4 *>(albedoRoughness),
+        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<const float2 *>(reservoirs), hdr,
+        stackOverflow);
 }
 
 // ------------------------------------------------------------------------------------------

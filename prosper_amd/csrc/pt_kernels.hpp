@@ -55,11 +55,28 @@ void launch_build_alpha_bounds(
 void launch_srgb_monotonicity(uint32_t firstBits, uint32_t lastBits, uint32_t *out, hipStream_t stream);
 void launch_permute_triangles(
     const WorldTriangle *in, const uint32_t *permutation, WorldTriangle *out, uint32_t total, hipStream_t stream);
+// ReSTIR-DI: the camera terms the three passes read of CameraUniforms
+struct RestirCamera
+{
+    float eye[3];
+    float clipToWorld[16]; // column-major
+    float cameraToClip22, cameraToClip32;
+};
 uint32_t restir_grid_blocks(uint32_t width, uint32_t height);
+// reservoirs: width*height float2 (bits of the int light index, unbiasedContributionWeight)
+void launch_restir_di_initial(
+    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, void *outReservoirs,
+    hipStream_t stream);
+// `inReservoirs` and `outReservoirs` must not overlap (a pixel reads its neighbours' input)
+void launch_restir_di_spatial(
+    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, const void *inReservoirs,
+    void *outReservoirs, hipStream_t stream);
 void launch_restir_di_trace(
     const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
-    const float eye[3], const float clipToWorld[16], const void *albedoRoughness, const void *normalMetallic,
-    const float *nonLinearDepth, const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream);
+    const RestirCamera &cam, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream);
 void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);

@@ -1,4 +1,4 @@
-"""Python handles onto the C++ host layer (prosper_amd/csrc/host): `Camera` and `RtReference`.
+"""Python handles onto the C++ host layer (prosper_amd/csrc/host): `Camera`, `RtReference` and the passes beside it.
 
 Same names, argument meaning and error behaviour as prosper's `scene::Camera`
 (src/scene/Camera.hpp) and `render::RtReference` (src/render/RtReference.hpp:32-60); every call
@@ -134,6 +134,59 @@ class RtReference:
 
     def release_preserved(self):
         lib().prosper_host_rt_reference_release_preserved(self._h)
+
+
+class RtDirectIllumination:
+    """render::rtdi::RtDirectIllumination (csrc/host/rt_direct_illumination.hpp) on a Context the scene was uploaded
+    to: drawUi's "Spatial reuse" toggle, record over a G-buffer (initial reservoirs, spatial reuse, trace)."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_rt_direct_illumination_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    @property
+    def context(self):
+        return self._ctx
+
+    def draw_ui(self, spatial_reuse=True):
+        lib().prosper_host_rt_direct_illumination_draw_ui(self._h, int(spatial_reuse))
+
+    def recompile_shaders(self):
+        lib().prosper_host_rt_direct_illumination_recompile_shaders(self._h)
+
+    def release_preserved(self):
+        lib().prosper_host_rt_direct_illumination_release_preserved(self._h)
+
+    def record(self, camera, albedo_roughness, normal_metallic, depth, reset_accumulation=False, draw_type="Default",
+               next_frame=0, stream=None):
+        """Camera::updateBuffer + RtDirectIllumination::record over host G-buffer arrays ([h, w, 4], [h, w, 4],
+        [h, w] float32); returns the TracePC that was pushed."""
+        inp, keep, w, h = Context._restir_host_inputs(albedo_roughness, normal_metallic, depth)
+        pc = S.RestirTracePC()
+        rc = lib().prosper_host_rt_direct_illumination_record(
+            self._h, camera._h, w, h, C.byref(inp), int(reset_accumulation),
+            S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type), next_frame, C.c_void_p(stream),
+            C.byref(pc))
+        del keep
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._ctx._restir_extent = (w, h)
+        return pc
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_rt_direct_illumination_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class TiledRtReference:

@@ -328,3 +328,9 @@ class RestirTracePC(C.Structure):
 class RestirInputs(C.Structure):
     _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetallic", C.c_void_p), ("nonLinearDepth", C.c_void_p),
                 ("reservoirs", C.c_void_p), ("onDevice", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# prosper_pt_restir_di_resample stages and prosper_pt_restir_di_record flags
+RESTIR_INITIAL = 0
+RESTIR_SPATIAL = 1
+RESTIR_SPATIAL_REUSE = 1
