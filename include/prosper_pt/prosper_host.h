@@ -102,6 +102,17 @@ int prosper_host_rt_direct_illumination_record(
     const prosper_pt_restir_inputs *gbuffer, int resetAccumulation, uint32_t drawType, uint32_t nextFrame, void *stream,
     prosper_pt_restir_trace_pc *outPushConstants);
 
+/* render::GBufferTracer (host/gbuffer_tracer.hpp): the ray-traced stand-in for GBufferRenderer::record's output on a
+ * context the scene was uploaded to (borrowed).  record = Camera::updateBuffer + prosper_pt_trace_gbuffer into the
+ * context-owned targets; *outGBuffer receives them as device inputs (onDevice = 1) for
+ * prosper_host_rt_direct_illumination_record or the prosper_pt_restir_di_* entries. */
+typedef struct prosper_host_gbuffer_tracer prosper_host_gbuffer_tracer;
+int prosper_host_gbuffer_tracer_create(prosper_pt_ctx *ctx, prosper_host_gbuffer_tracer **out);
+void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *pass);
+int prosper_host_gbuffer_tracer_record(
+    prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
+    uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer);
+
 #ifdef __cplusplus
 }
 #endif

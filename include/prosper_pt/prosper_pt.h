@@ -544,6 +544,12 @@ int prosper_pt_restir_di_resample(
 enum
 {
     PROSPER_PT_RESTIR_SPATIAL_REUSE = 1u << 0,
+    /* trace the G-buffer first (prosper_pt_trace_gbuffer with pc->drawType, pc->frameIndex) into the context-owned
+     * buffers and run the passes over it; `gbuffer` may then be NULL and is ignored.  All four kernels read one scene
+     * and light version. */
+    PROSPER_PT_RESTIR_TRACE_GBUFFER = 1u << 1,
+    /* with PROSPER_PT_RESTIR_TRACE_GBUFFER only: the jittered G-buffer (PROSPER_PT_GBUFFER_JITTER) */
+    PROSPER_PT_RESTIR_JITTER_GBUFFER = 1u << 2,
 };
 int prosper_pt_restir_di_record(
     prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
@@ -554,6 +560,42 @@ int prosper_pt_restir_di_record(
 int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes);
 /* Synchronises `stream` and copies those reservoirs (byte_size = width*height*8 of the call that made them) to host memory. */
 int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, size_t byte_size, void *stream);
+
+/* The G-buffer the ReSTIR-DI passes read, ray traced over the context's scene: the ray-traced stand-in for prosper's
+ * raster GBufferRenderer (src/render/GBufferRenderer.cpp; res/shader/gbuffer.frag).  One lane per pixel traces the
+ * path tracer's primary ray without depth of field (rt/reference/main.rgen:225-231, the same any-hit rules) and writes
+ *   albedoRoughness  float4 (albedo.rgb, roughness); other draw types (debug_color, 1), MeshletID counts as Default
+ *   normalMetallic   float4 (signedOctEncode(shading normal).xy, metallic, .z); 0 for the other draw types
+ *   nonLinearDepth   float: clip.z / clip.w of cameraToClip * worldToCamera * (position, 1)
+ * and zeros where the ray misses (the targets' clear values).  With PROSPER_PT_GBUFFER_JITTER the ray goes through
+ * the pixel's jittered sample (px, py) + rnd2d01() of the path tracer's rng (px, py, frameIndex): each texel is then
+ * that frame's primary hit.  Without, through the pixel centre (px + 0.5, py + 0.5), as a rasteriser samples.
+ * Unlike the raster G-buffer: no velocity target, no TAA jitter (currentJitter), no meshlet IDs, float storage, BLEND
+ * surfaces follow the path tracer's stochastic transparency, and PrimitiveID is the geometry's triangle index.
+ * `targets`: three caller-owned device buffers (16-byte aligned), or NULL for context-owned ones (grown as needed,
+ * separate from the ReSTIR scratch).  Pending transform, light and material updates take effect first. */
+enum
+{
+    PROSPER_PT_GBUFFER_JITTER = 1u << 0,
+};
+typedef struct prosper_pt_gbuffer_targets
+{
+    void *albedoRoughness; /* width*height float4 */
+    void *normalMetallic;  /* width*height float4 */
+    float *nonLinearDepth; /* width*height float */
+} prosper_pt_gbuffer_targets;
+int prosper_pt_trace_gbuffer(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream);
+/* The last traced G-buffer (either kind of target) as inputs of the ReSTIR-DI entries (onDevice = 1, reservoirs =
+ * NULL) and its extent; NO_SCENE before the first trace.  width / height may be NULL. */
+int prosper_pt_get_gbuffer_device_ptrs(
+    prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height);
+/* Synchronises `stream` and copies the last traced G-buffer to host memory: `pixels` = width*height of that trace;
+ * any of the three pointers may be NULL. */
+int prosper_pt_read_gbuffer(
+    prosper_pt_ctx *ctx, float *host_albedo_roughness, float *host_normal_metallic, float *host_depth, size_t pixels,
+    void *stream);
 
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of

@@ -84,6 +84,10 @@ def lib():
         vp, C.POINTER(S.RestirTracePC), u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
     L.prosper_pt_get_restir_reservoirs_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.prosper_pt_read_restir_reservoirs.argtypes = [vp, vp, C.c_size_t, vp]
+    L.prosper_pt_trace_gbuffer.argtypes = [
+        vp, u32, u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.GBufferTargets), vp]
+    L.prosper_pt_get_gbuffer_device_ptrs.argtypes = [vp, C.POINTER(S.RestirInputs), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_read_gbuffer.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -149,6 +153,10 @@ def lib():
     L.prosper_host_rt_direct_illumination_release_preserved.restype = None
     L.prosper_host_rt_direct_illumination_record.argtypes = [
         vp, vp, u32, u32, C.POINTER(S.RestirInputs), C.c_int, u32, u32, vp, C.POINTER(S.RestirTracePC)]
+    L.prosper_host_gbuffer_tracer_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_gbuffer_tracer_destroy.argtypes = [vp]
+    L.prosper_host_gbuffer_tracer_destroy.restype = None
+    L.prosper_host_gbuffer_tracer_record.argtypes = [vp, vp, u32, u32, u32, u32, C.c_int, vp, C.POINTER(S.RestirInputs)]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -477,6 +485,44 @@ class Context:
         out = np.empty((h, w, 2), np.float32)
         _check(lib().prosper_pt_read_restir_reservoirs(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
+
+    def trace_gbuffer(self, camera, width, height, draw_type=0, frame_index=0, jitter=True, targets=None, stream=None):
+        """prosper_pt_trace_gbuffer: the ray-traced G-buffer of the uploaded scene.  With `targets` None it goes to the
+        context's own buffers and is read back: returns (albedoRoughness [h, w, 4], normalMetallic [h, w, 4],
+        nonLinearDepth [h, w]) float32.  `targets`: three device pointers (ar, nm, depth), written; returns None."""
+        self._sync_debug()
+        t = None if targets is None else S.GBufferTargets(*targets)
+        flags = S.GBUFFER_JITTER if jitter else 0
+        _check(lib().prosper_pt_trace_gbuffer(self._h, int(draw_type), frame_index, flags, C.byref(camera), width, height,
+                                              None if t is None else C.byref(t), C.c_void_p(stream)))
+        if targets is not None:
+            return None
+        return self.read_gbuffer(stream)
+
+    def gbuffer_device_ptrs(self):
+        """The last traced G-buffer: (S.RestirInputs with onDevice = 1, width, height)."""
+        inp, w, h = S.RestirInputs(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_get_gbuffer_device_ptrs(self._h, C.byref(inp), C.byref(w), C.byref(h)))
+        return inp, w.value, h.value
+
+    def read_gbuffer(self, stream=None):
+        """The last traced G-buffer as host arrays (ar [h, w, 4], nm [h, w, 4], depth [h, w]); synchronises `stream`."""
+        _, w, h = self.gbuffer_device_ptrs()
+        ar, nm = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+        depth = np.empty((h, w), np.float32)
+        _check(lib().prosper_pt_read_gbuffer(self._h, ar.ctypes.data, nm.ctypes.data, depth.ctypes.data, w * h,
+                                             C.c_void_p(stream)))
+        return ar, nm, depth
+
+    def restir_di_record_traced(self, pc, camera, width, height, spatial_reuse=True, jitter=True, stream=None):
+        """RtDirectIllumination::record over the G-buffer it traces first (PROSPER_PT_RESTIR_TRACE_GBUFFER) with
+        pc.drawType and pc.frameIndex: from the scene alone to the direct-illumination image."""
+        self._sync_debug()
+        flags = S.RESTIR_TRACE_GBUFFER | (S.RESTIR_SPATIAL_REUSE if spatial_reuse else 0) | (
+            S.RESTIR_JITTER_GBUFFER if jitter else 0)
+        _check(lib().prosper_pt_restir_di_record(self._h, C.byref(pc), flags, C.byref(camera), width, height, None,
+                                                 C.c_void_p(stream)))
+        self._restir_extent = (width, height)
 
     def set_tone_map_lut(self, lut_r9g9b9e5):
         """lut: uint32 [dim, dim, dim] (z, y, x) R9G9B9E5 texels, e.g. from prosper_amd.dds.read_lut."""

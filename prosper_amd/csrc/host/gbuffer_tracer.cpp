@@ -1,0 +1,122 @@
+// host/gbuffer_tracer.cpp — see gbuffer_tracer.hpp.
+#include "gbuffer_tracer.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <new>
+#include <stdexcept>
+#include <string>
+
+#include "../../../include/prosper_pt/prosper_host.h"
+
+#define PROSPER_ASSERT(cond)                                                                                           \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        if (!(cond))                                                                                                   \
+        {                                                                                                              \
+            std::fprintf(stderr, "%s:%d: assertion failed: %s\n", __FILE__, __LINE__, #cond);                          \
+            std::abort();                                                                                              \
+        }                                                                                                              \
+    } while (0)
+
+namespace render
+{
+
+void GBufferTracer::init(prosper_pt_ctx *ctx)
+{
+    PROSPER_ASSERT(!m_initialized);
+    PROSPER_ASSERT(ctx != nullptr);
+    m_ctx = ctx;
+    m_initialized = true;
+}
+
+rtdi::GBuffer GBufferTracer::record(
+    const scene::Camera &cam, uint32_t width, uint32_t height, scene::DrawType drawType, uint32_t frameIndex, bool jitter,
+    void *stream)
+{
+    PROSPER_ASSERT(m_initialized);
+    const uint32_t flags = jitter ? PROSPER_PT_GBUFFER_JITTER : 0u;
+    if (prosper_pt_trace_gbuffer(
+            m_ctx, static_cast<uint32_t>(drawType), frameIndex, flags, &cam.uniforms(), width, height, nullptr, stream) !=
+        PROSPER_PT_OK)
+        throw std::runtime_error(std::string("GBufferTracer::record: ") + prosper_pt_last_error());
+    prosper_pt_restir_inputs in = {};
+    if (prosper_pt_get_gbuffer_device_ptrs(m_ctx, &in, nullptr, nullptr) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("GBufferTracer::record: ") + prosper_pt_last_error());
+    rtdi::GBuffer ret;
+    ret.albedoRoughness = in.albedoRoughness;
+    ret.normalMetallic = in.normalMetallic;
+    ret.nonLinearDepth = in.nonLinearDepth;
+    ret.onDevice = true;
+    ret.width = width;
+    ret.height = height;
+    return ret;
+}
+
+} // namespace render
+
+// ---- plain-C shims (include/prosper_pt/prosper_host.h) ----
+
+struct prosper_host_gbuffer_tracer
+{
+    render::GBufferTracer pass;
+};
+
+extern "C" void prosper_host_set_error(const char *message); // rt_reference.cpp
+
+extern "C" {
+
+int prosper_host_gbuffer_tracer_create(prosper_pt_ctx *ctx, prosper_host_gbuffer_tracer **out)
+{
+    if (!out) return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!ctx)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_create: null context");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    prosper_host_gbuffer_tracer *r = new (std::nothrow) prosper_host_gbuffer_tracer();
+    if (!r) return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    r->pass.init(ctx);
+    *out = r;
+    return PROSPER_PT_OK;
+}
+
+void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *r) { delete r; }
+
+int prosper_host_gbuffer_tracer_record(
+    prosper_host_gbuffer_tracer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
+    uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer)
+{
+    if (!r || !camera || !outGBuffer)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_record: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    if (drawType >= (uint32_t)scene::DrawType::Count)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_record: drawType out of range");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    try
+    {
+        scene::Camera &cam = *prosper_host_camera_object(camera);
+        cam.updateResolution(width, height);
+        cam.updateBuffer();
+        const render::rtdi::GBuffer g =
+            r->pass.record(cam, width, height, static_cast<scene::DrawType>(drawType), frameIndex, jitter != 0, stream);
+        *outGBuffer = prosper_pt_restir_inputs{};
+        outGBuffer->albedoRoughness = g.albedoRoughness;
+        outGBuffer->normalMetallic = g.normalMetallic;
+        outGBuffer->nonLinearDepth = g.nonLinearDepth;
+        outGBuffer->onDevice = 1;
+    }
+    catch (const std::exception &e)
+    {
+        prosper_host_set_error(e.what());
+        return PROSPER_PT_ERR_HIP;
+    }
+    return PROSPER_PT_OK;
+}
+
+} // extern "C"

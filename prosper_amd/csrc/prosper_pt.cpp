@@ -845,6 +845,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
         if (slot.stackOverflow) (void)hipFree(slot.stackOverflow);
     }
     if (ctx->restirScratch) (void)hipFree(ctx->restirScratch);
+    if (ctx->gbufferOwned) (void)hipFree(ctx->gbufferOwned);
     for (void *r : ctx->restirReservoirs)
         if (r) (void)hipFree(r);
     if (ctx->toneLut) (void)hipFree(ctx->toneLut);
@@ -1295,6 +1296,25 @@ static int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s)
     return PROSPER_PT_OK;
 }
 
+// rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
+static void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera)
+{
+    p.eye[0] = camera->eye.x;
+    p.eye[1] = camera->eye.y;
+    p.eye[2] = camera->eye.z;
+    const prosper_mat4 &w2c = camera->worldToCamera;
+    p.right[0] = w2c.col[0].x; p.right[1] = w2c.col[1].x; p.right[2] = w2c.col[2].x;
+    p.up[0] = w2c.col[0].y; p.up[1] = w2c.col[1].y; p.up[2] = w2c.col[2].y;
+    p.fwd[0] = -w2c.col[0].z; p.fwd[1] = -w2c.col[1].z; p.fwd[2] = -w2c.col[2].z;
+    {
+        // volatile: keep the compiler from folding the two divisions into anything but IEEE fp32 divides
+        volatile float c00 = camera->cameraToClip.col[0].x, c11 = camera->cameraToClip.col[1].y;
+        p.aspect = c11 / c00;
+        p.tanHalfFovY = 1.0f / c11;
+    }
+    std::memcpy(p.cameraToWorld, &camera->cameraToWorld, 64);
+}
+
 int prosper_pt_render_frames(
     prosper_pt_ctx *ctx, const prosper_ReferencePC *pc, const prosper_CameraUniforms *camera, uint32_t width,
     uint32_t height, const prosper_pt_tile_desc *tile, uint32_t frame_count, uint32_t render_flags, void *stream)
@@ -1351,21 +1371,7 @@ int prosper_pt_render_frames(
 
     RenderParams p = {};
     p.pc = *pc;
-    // rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
-    p.eye[0] = camera->eye.x;
-    p.eye[1] = camera->eye.y;
-    p.eye[2] = camera->eye.z;
-    const prosper_mat4 &w2c = camera->worldToCamera;
-    p.right[0] = w2c.col[0].x; p.right[1] = w2c.col[1].x; p.right[2] = w2c.col[2].x;
-    p.up[0] = w2c.col[0].y; p.up[1] = w2c.col[1].y; p.up[2] = w2c.col[2].y;
-    p.fwd[0] = -w2c.col[0].z; p.fwd[1] = -w2c.col[1].z; p.fwd[2] = -w2c.col[2].z;
-    {
-        // volatile: keep the compiler from folding the two divisions into anything but IEEE fp32 divides
-        volatile float c00 = camera->cameraToClip.col[0].x, c11 = camera->cameraToClip.col[1].y;
-        p.aspect = c11 / c00;
-        p.tanHalfFovY = 1.0f / c11;
-    }
-    std::memcpy(p.cameraToWorld, &camera->cameraToWorld, 64);
+    set_camera_ray_params(p, camera);
     p.width = width;
     p.height = height;
     p.stripeWidth = tiled ? tile->stripeWidth : 0;
@@ -1769,13 +1775,151 @@ int prosper_pt_restir_di_resample(
     return mark_versions_read(ctx, s);
 }
 
+// ---- ray-traced G-buffer (the ReSTIR-DI passes' input; a stand-in for src/render/GBufferRenderer.cpp) ----
+
+// The context-owned targets, one allocation of 16 + 16 + 4 bytes per pixel, grown like restirScratch.
+static int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, prosper_pt_gbuffer_targets &out)
+{
+    const size_t need = pixels * 36u + 64u;
+    if (ctx->gbufferOwnedBytes < need || !ctx->gbufferOwned)
+    {
+        PPT_HIP(hipStreamSynchronize(s));
+        if (ctx->gbufferLast.albedoRoughness == ctx->gbufferOwned)
+        {
+            ctx->gbufferLast = prosper_pt_gbuffer_targets{};
+            ctx->gbufferLastWidth = ctx->gbufferLastHeight = 0;
+        }
+        if (ctx->gbufferOwned) PPT_HIP(hipFree(ctx->gbufferOwned));
+        ctx->gbufferOwned = nullptr;
+        ctx->gbufferOwnedBytes = 0;
+        PPT_HIP(hipMalloc(&ctx->gbufferOwned, need));
+        ctx->gbufferOwnedBytes = need;
+    }
+    uint8_t *base = static_cast<uint8_t *>(ctx->gbufferOwned);
+    out.albedoRoughness = base;
+    out.normalMetallic = base + pixels * 16u;
+    out.nonLinearDepth = reinterpret_cast<float *>(base + pixels * 32u);
+    return PROSPER_PT_OK;
+}
+
+// The G-buffer pass on `s` after restir_flush: camera terms, the traversal stacks, the launch.
+static int gbuffer_trace(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s)
+{
+    GBufferTraceParams g = {};
+    set_camera_ray_params(g.r, camera);
+    g.r.width = width;
+    g.r.height = height;
+    g.r.localWidth = width;
+    g.r.stripeCount = 1;
+    g.r.frameCount = 1;
+    // worldToClip = cameraToClip * worldToCamera (column-major), in double, rounded once
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r)
+        {
+            double v = 0.0;
+            for (int k = 0; k < 4; ++k)
+                v += (double)(&camera->cameraToClip.col[k].x)[r] * (double)(&camera->worldToCamera.col[c].x)[k];
+            g.worldToClip[c * 4 + r] = (float)v;
+        }
+    g.drawType = drawType;
+    g.frameIndex = frameIndex;
+    g.jitter = jitter ? 1u : 0u;
+
+    int32_t *ovf = nullptr;
+    const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), s, &ovf);
+    if (orc != PROSPER_PT_OK) return orc;
+    wait_for_slot(ctx->slots[0], s);
+    launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+    release_slot(ctx->slots[0], s);
+    PPT_HIP(hipGetLastError());
+    ctx->gbufferLast = t;
+    ctx->gbufferLastWidth = width;
+    ctx->gbufferLastHeight = height;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_trace_gbuffer(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_JITTER)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: unknown flags");
+    if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: empty extent");
+    if (!ctx || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null argument");
+    if (targets)
+    {
+        if (!targets->albedoRoughness || !targets->normalMetallic || !targets->nonLinearDepth)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null target");
+        if ((reinterpret_cast<uintptr_t>(targets->albedoRoughness) | reinterpret_cast<uintptr_t>(targets->normalMetallic) |
+             reinterpret_cast<uintptr_t>(targets->nonLinearDepth)) & 15u)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: targets must be 16-byte aligned");
+    }
+    const int crc = restir_check_scene(ctx, "prosper_pt_trace_gbuffer");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = restir_flush(ctx, s);
+    prosper_pt_gbuffer_targets t = {};
+    if (rc == PROSPER_PT_OK)
+    {
+        if (targets)
+            t = *targets;
+        else
+            rc = gbuffer_owned_targets(ctx, (size_t)width * height, s, t);
+    }
+    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gbuffer_device_ptrs: null argument");
+    if (!ctx->gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    *out = prosper_pt_restir_inputs{};
+    out->albedoRoughness = ctx->gbufferLast.albedoRoughness;
+    out->normalMetallic = ctx->gbufferLast.normalMetallic;
+    out->nonLinearDepth = ctx->gbufferLast.nonLinearDepth;
+    out->onDevice = 1;
+    if (width) *width = ctx->gbufferLastWidth;
+    if (height) *height = ctx->gbufferLastHeight;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_gbuffer(
+    prosper_pt_ctx *ctx, float *host_albedo_roughness, float *host_normal_metallic, float *host_depth, size_t pixels,
+    void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: null argument");
+    if (!ctx->gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    if (pixels != (size_t)ctx->gbufferLastWidth * ctx->gbufferLastHeight)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: pixel count differs from the G-buffer's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const prosper_pt_gbuffer_targets &t = ctx->gbufferLast;
+    if (host_albedo_roughness)
+        PPT_HIP(hipMemcpyAsync(host_albedo_roughness, t.albedoRoughness, pixels * 16u, hipMemcpyDeviceToHost, s));
+    if (host_normal_metallic)
+        PPT_HIP(hipMemcpyAsync(host_normal_metallic, t.normalMetallic, pixels * 16u, hipMemcpyDeviceToHost, s));
+    if (host_depth) PPT_HIP(hipMemcpyAsync(host_depth, t.nonLinearDepth, pixels * 4u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
 int prosper_pt_restir_di_record(
     prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
     uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, void *stream)
 {
-    if (!ctx || !pc || !camera || !gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)
+    if ((recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) && !(recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: JITTER_GBUFFER without TRACE_GBUFFER");
+    const bool traced = (recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER) != 0;
+    if (!ctx || !pc || !camera ||
+        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: null argument");
-    if (recordFlags & ~(uint32_t)PROSPER_PT_RESTIR_SPATIAL_REUSE)
+    if (recordFlags & ~(uint32_t)(PROSPER_PT_RESTIR_SPATIAL_REUSE | PROSPER_PT_RESTIR_TRACE_GBUFFER | PROSPER_PT_RESTIR_JITTER_GBUFFER))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: unknown record flags");
     const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_record");
     if (crc != PROSPER_PT_OK) return crc;
@@ -1786,7 +1930,21 @@ int prosper_pt_restir_di_record(
     int rc = restir_flush(ctx, s);
     if (rc == PROSPER_PT_OK) rc = restir_reservoir_buffers(ctx, pixels, s);
     RestirDeviceInputs din;
-    if (rc == PROSPER_PT_OK) rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
+    if (traced)
+    {
+        // the G-buffer pass first, into the context-owned targets (never the restirScratch a host-input call fills)
+        prosper_pt_gbuffer_targets t = {};
+        if (rc == PROSPER_PT_OK) rc = gbuffer_owned_targets(ctx, pixels, s, t);
+        if (rc == PROSPER_PT_OK)
+            rc = gbuffer_trace(ctx, pc->drawType, pc->frameIndex, (recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) != 0,
+                               camera, width, height, t, s);
+        din.ar = t.albedoRoughness;
+        din.nm = t.normalMetallic;
+        din.depth = t.nonLinearDepth;
+        din.res = nullptr;
+    }
+    else if (rc == PROSPER_PT_OK)
+        rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
     if (rc != PROSPER_PT_OK) return rc;
     const RestirCamera cam = restir_camera(camera);
     // InitialReservoirs, then SpatialReuse when the toggle is on, then Trace (RtDirectIllumination.cpp:80-109)

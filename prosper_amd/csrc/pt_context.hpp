@@ -325,6 +325,10 @@ struct prosper_pt_ctx
     size_t restirReservoirBytes = 0; // of each
     const void *restirLastReservoirs = nullptr; // prosper_pt_get_restir_reservoirs_device_ptr
     size_t restirLastReservoirBytes = 0;
+    void *gbufferOwned = nullptr; // context-owned G-buffer targets (prosper_pt_trace_gbuffer): 16 + 16 + 4 bytes per pixel
+    size_t gbufferOwnedBytes = 0;
+    prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
+    uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
     uint32_t *toneLut = nullptr; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     void *toneScratch = nullptr; // RGBA8 output when the caller only wants a host copy

@@ -5,6 +5,8 @@
 //   render_megakernel   one lane per pixel runs whole paths (rt/reference/main.rgen:225-299)
 //   blit_rgba16f        RGBA32F -> RGBA16F (src/render/RtReference.cpp:339-377)
 //   eval_fn             device self-test entry (prosper_pt_eval_device_fn)
+//   restir_di_*         ReSTIR-DI initial reservoirs, spatial reuse and trace over a G-buffer
+//   gbuffer_trace       the ray-traced G-buffer those passes read
 #include "pt_kernels.hpp"
 
 #include "bvh_encode.hpp"
@@ -487,9 +489,9 @@ struct RestirParams
 
 // Block b and b + 8 run on the same XCD: the tiles [x * perXcd, (x + 1) * perXcd) go to XCD x, so the neighbours the
 // spatial pass reads mostly sit in the L2 of the XCD that reads them.  False past the last tile.
-PPT_D bool restir_pixel(const RestirParams &p, uint32_t &px, uint32_t &py)
+PPT_D bool restir_pixel(uint32_t width, uint32_t height, uint32_t &px, uint32_t &py)
 {
-    const uint32_t tilesX = (p.width + 15u) / 16u, tilesY = (p.height + 15u) / 16u;
+    const uint32_t tilesX = (width + 15u) / 16u, tilesY = (height + 15u) / 16u;
     const uint32_t numTiles = tilesX * tilesY;
     const uint32_t perXcd = (numTiles + 7u) / 8u;
     const uint32_t tile = (blockIdx.x % 8u) * perXcd + (blockIdx.x / 8u);
@@ -499,6 +501,7 @@ PPT_D bool restir_pixel(const RestirParams &p, uint32_t &px, uint32_t &py)
     py = (tile / tilesX) * 16u + (wave >> 1) * 8u + (lane >> 3);
     return true;
 }
+PPT_D bool restir_pixel(const RestirParams &p, uint32_t &px, uint32_t &py) { return restir_pixel(p.width, p.height, px, py); }
 
 // scene/camera.glsl:11-22
 PPT_D float linearize_depth(const RestirParams &p, float nonLinearDepth)
@@ -767,6 +770,86 @@ void launch_restir_di_trace(
         restir_params(drawType, frameIndex, flags, width, height, cam), static_cast<const float4 *>(albedoRoughness),
         static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<const float2 *>(reservoirs), hdr,
         stackOverflow);
+}
+
+// ------------------------------------------------------------------------------------------
+// Ray-traced G-buffer: the three targets of gbuffer.frag (albedoRoughness, normalMetallic, depth) from the path tracer's
+// primary hit, one lane per pixel on the ReSTIR passes' tile / XCD mapping.  The ray is trace_path's camera ray without
+// depth of field: the jittered sample of the pixel (main.rgen:229-231) or its centre.  The rng draws the jitter either
+// way, so the any-hit seed pcg(x ^ z) is the path tracer's in both modes.
+// ------------------------------------------------------------------------------------------
+
+// gbuffer.frag:41-58 signedOctEncode
+PPT_D f3 signed_oct_encode(f3 n)
+{
+    const float sum = (fabs_(n.x) + fabs_(n.y)) + fabs_(n.z);
+    const float x = n.x / sum, y = n.y / sum, z = n.z / sum;
+    f3 o;
+    o.y = y * 0.5f + 0.5f;
+    o.x = x * 0.5f + o.y;
+    o.y = x * -0.5f + o.y;
+    o.z = saturate(z * 3.40282e+38f);
+    return o;
+}
+
+__global__ __launch_bounds__(256) void gbuffer_trace_kernel(
+    DeviceScene s, GBufferTraceParams g, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
+    float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow)
+{
+    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
+    uint32_t px, py;
+    if (!restir_pixel(g.r.width, g.r.height, px, py)) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
+                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
+    if (px >= g.r.width || py >= g.r.height) return;
+    const size_t i = (size_t)py * g.r.width + px;
+
+    Rng rng{px, py, g.frameIndex};
+    const f2 j = rng.rnd2d01();
+    const f2 uv = g.jitter ? f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height}
+                           : f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
+    const Ray ray = pinhole_camera_ray(g.r, uv);
+    LaneCounters cnt = {};
+    Hit hit;
+    if (!trace<false, false>(s, ray.o, ray.d, ray.tMin, ray.tMax, pcg(rng.x ^ rng.z), stack, hit, cnt))
+    {
+        // the clear values of GBufferRenderer.cpp:487-516
+        albedoRoughness[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        nonLinearDepth[i] = 0.0f;
+        return;
+    }
+    const Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
+    if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT && g.drawType != PROSPER_DRAW_TYPE_MESHLET_ID)
+    {
+        // gbuffer.frag:83-99
+        const f3 c = debug_color(s, g.drawType, hit, sf);
+        albedoRoughness[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    else
+    {
+        const f3 enc = signed_oct_encode(sf.normalWS);
+        albedoRoughness[i] = make_float4(sf.material.albedo.x, sf.material.albedo.y, sf.material.albedo.z, sf.material.roughness);
+        normalMetallic[i] = make_float4(enc.x, enc.y, sf.material.metallic, enc.z);
+    }
+    // posNDC.z of gbuffer.vert / gbuffer.frag: (worldToClip * (positionWS, 1)).z / .w
+    const float *m = g.worldToClip;
+    const f3 p = sf.positionWS;
+    const float cz = __builtin_fmaf(m[10], p.z, __builtin_fmaf(m[6], p.y, __builtin_fmaf(m[2], p.x, m[14])));
+    const float cw = __builtin_fmaf(m[11], p.z, __builtin_fmaf(m[7], p.y, __builtin_fmaf(m[3], p.x, m[15])));
+    nonLinearDepth[i] = cz / cw;
+}
+
+void launch_gbuffer_trace(
+    const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
+    int32_t *stackOverflow, hipStream_t stream)
+{
+    if (g.r.width == 0 || g.r.height == 0) return;
+    hipLaunchKernelGGL(
+        gbuffer_trace_kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
+        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -77,6 +77,19 @@ void launch_restir_di_trace(
     const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
     const RestirCamera &cam, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
     const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream);
+// Ray-traced G-buffer (gbuffer_trace_kernel): `r` carries the camera terms of pinhole_camera_ray and the extent, built as
+// prosper_pt_render_frames builds them (r.pc is not read); worldToClip = cameraToClip * worldToCamera, column-major.
+struct GBufferTraceParams
+{
+    RenderParams r;
+    float worldToClip[16];
+    uint32_t drawType, frameIndex, jitter;
+};
+// albedoRoughness, normalMetallic: r.width*r.height float4; nonLinearDepth: r.width*r.height float.  Grid of
+// restir_grid_blocks(r.width, r.height) blocks (the stack overflow array is sized for it).
+void launch_gbuffer_trace(
+    const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
+    int32_t *stackOverflow, hipStream_t stream);
 void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);

@@ -177,9 +177,55 @@ class RtDirectIllumination:
         self._ctx._restir_extent = (w, h)
         return pc
 
+    def record_device(self, camera, gbuffer, width, height, reset_accumulation=False, draw_type="Default",
+                      next_frame=0, stream=None):
+        """Same over a device G-buffer (S.RestirInputs with onDevice = 1, e.g. GBufferTracer.record's)."""
+        pc = S.RestirTracePC()
+        rc = lib().prosper_host_rt_direct_illumination_record(
+            self._h, camera._h, width, height, C.byref(gbuffer), int(reset_accumulation),
+            S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type), next_frame, C.c_void_p(stream),
+            C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._ctx._restir_extent = (width, height)
+        return pc
+
     def close(self):
         if self._h:
             lib().prosper_host_rt_direct_illumination_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GBufferTracer:
+    """render::GBufferTracer (csrc/host/gbuffer_tracer.hpp) on a Context the scene was uploaded to: record traces the
+    G-buffer into the context's buffers and returns them as device inputs (S.RestirInputs, onDevice = 1)."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_gbuffer_tracer_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, width, height, draw_type="Default", frame_index=0, jitter=True, stream=None):
+        out = S.RestirInputs()
+        rc = lib().prosper_host_gbuffer_tracer_record(
+            self._h, camera._h, width, height, S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
+            frame_index, int(jitter), C.c_void_p(stream), C.byref(out))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_gbuffer_tracer_destroy(self._h)
             self._h = None
 
     def __del__(self):

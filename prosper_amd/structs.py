@@ -334,3 +334,13 @@ class RestirInputs(C.Structure):
 RESTIR_INITIAL = 0
 RESTIR_SPATIAL = 1
 RESTIR_SPATIAL_REUSE = 1
+
+# prosper_pt_restir_di_record: trace the G-buffer first (optionally jittered)
+RESTIR_TRACE_GBUFFER = 1 << 1
+RESTIR_JITTER_GBUFFER = 1 << 2
+# prosper_pt_trace_gbuffer flags
+GBUFFER_JITTER = 1 << 0
+
+
+class GBufferTargets(C.Structure):
+    _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetallic", C.c_void_p), ("nonLinearDepth", C.c_void_p)]

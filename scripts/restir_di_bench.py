@@ -1,12 +1,18 @@
 """ReSTIR-DI at 1920x1080: the three passes of RtDirectIllumination::record (initial reservoirs, spatial reuse, trace)
-and the whole record, on S-cornell (C2's scene) and the C4 scene (sponza_class with the sun and 1024 punctual lights).
+and the whole record, on S-cornell (C2's scene), the C4 scene (sponza_class with the sun and 1024 punctual lights) and
+the FlightHelmet fixture.
+
+The ray-traced G-buffer (prosper_pt_trace_gbuffer) is timed too: `gbuffer_ms` jittered and at the pixel centres,
+`record_traced_ms` the record that traces it first (spatial reuse on and off), and the yardstick
+`render_1spp_1bounce_ms`, one prosper_pt_render frame with maxBounces = 1 (the same primary trace and surface, plus
+NEE, a shadow ray and the accumulation), launched alternately with the G-buffer in the same process.
 
 The G-buffer comes from the product's own debug views of the primary hits at 1 spp (Position, ShadingNormal, Albedo,
 Roughness, Metallic), depth by projecting the positions with worldToClip, as tests/test_restir_di.py does.  Each stage is
 timed alone with device events around `--repeats` launches after warm-up, the median of the per-launch times; the
 record with spatial reuse on and off.  Prints one JSON object.
 
-    python scripts/restir_di_bench.py [--repeats 60] [--scenes c2,c4]
+    python scripts/restir_di_bench.py [--repeats 60] [--scenes c2,c4,fh]
 """
 import argparse
 import json
@@ -18,13 +24,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from prosper_amd import capi, scenes, structs as S  # noqa: E402
+from prosper_amd import capi, flight_helmet, scenes, structs as S  # noqa: E402
 from prosper_amd.rt_reference import Camera  # noqa: E402
 
 HBM_ROOF_GBS = 8000.0
 SCENES = {
     "c2": ("S-cornell", lambda: scenes.cornell()),
     "c4": ("sponza_class lights+foliage", lambda: scenes.sponza_class(lights=True, foliage=True)),
+    "fh": ("FlightHelmet", lambda: flight_helmet.load_fixture()),
 }
 
 
@@ -60,6 +67,20 @@ def median_ms(torch, fn, repeats):
     return float(np.median([a.elapsed_time(b) for a, b in events]))
 
 
+def alternating_median_ms(torch, fns, repeats):
+    """Every function timed once per round, the rounds back to back: the median per function."""
+    events = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            events[k].append((a, b))
+    torch.cuda.synchronize()
+    return {k: float(np.median([a.elapsed_time(b) for a, b in ev])) for k, ev in events.items()}
+
+
 def bench_scene(torch, key, repeats, width, height):
     name, make = SCENES[key]
     world = make()
@@ -90,6 +111,27 @@ def bench_scene(torch, key, repeats, width, height):
                 fn()
         torch.cuda.synchronize()
         ms = {k: median_ms(torch, fn, repeats) for k, fn in stages.items()}
+        # the ray-traced G-buffer into caller-owned targets, against one 1-bounce frame of the path tracer
+        gb = [torch.empty_like(x) for x in t]
+        targets = tuple(x.data_ptr() for x in gb)
+        render_pc = S.ReferencePC(0, S.PC_FLAG_SKIP_HISTORY | S.PC_FLAG_ACCUMULATE, 1, 1e-5, 1.0, focal, 3, 1)
+        yard = {
+            "gbuffer_jitter": lambda: ctx.trace_gbuffer(cam, width, height, frame_index=1, jitter=True, targets=targets,
+                                                        stream=st),
+            "gbuffer_centre": lambda: ctx.trace_gbuffer(cam, width, height, frame_index=1, jitter=False, targets=targets,
+                                                        stream=st),
+            "render_1spp_1bounce": lambda: ctx.render(render_pc, cam, width, height, stream=st),
+        }
+        traced = {
+            "spatial_on": lambda: ctx.restir_di_record_traced(pc, cam, width, height, spatial_reuse=True, stream=st),
+            "spatial_off": lambda: ctx.restir_di_record_traced(pc, cam, width, height, spatial_reuse=False, stream=st),
+        }
+        for fn in list(yard.values()) + list(traced.values()):
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        yard_ms = alternating_median_ms(torch, yard, repeats)
+        traced_ms = {k: median_ms(torch, fn, repeats) for k, fn in traced.items()}
         px = width * height
         lit = float((ctx.read_restir_reservoirs(st)[..., 0].copy().view(np.int32) >= 0).mean())
         # algorithmic bytes: G-buffer 16 + 16 + 4 B, reservoirs 8 B in / out, HDR 16 B; the spatial pass's neighbour
@@ -97,7 +139,9 @@ def bench_scene(torch, key, repeats, width, height):
         nbytes = {"initial": 44 * px, "spatial": 52 * px, "trace": 60 * px}
         out = {"scene": name, "width": width, "height": height,
                "lights": 1 + world.point_lights.count + world.spot_lights.count, "repeats": repeats,
-               "pixels_with_a_light": lit, "ms": ms, "algorithmic_bytes": nbytes}
+               "pixels_with_a_light": lit, "ms": ms, "algorithmic_bytes": nbytes,
+               "gbuffer_ms": {"jitter": yard_ms["gbuffer_jitter"], "centre": yard_ms["gbuffer_centre"]},
+               "render_1spp_1bounce_ms": yard_ms["render_1spp_1bounce"], "record_traced_ms": traced_ms}
         out["GBps"] = {k: nbytes[k] / (ms[k] * 1e-3) / 1e9 for k in nbytes}
         out["share_of_hbm_roof"] = {k: out["GBps"][k] / HBM_ROOF_GBS for k in nbytes}
         return out
@@ -108,7 +152,7 @@ def bench_scene(torch, key, repeats, width, height):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--repeats", type=int, default=60)
-    ap.add_argument("--scenes", default="c2,c4")
+    ap.add_argument("--scenes", default="c2,c4,fh")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     args = ap.parse_args()
