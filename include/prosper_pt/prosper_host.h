@@ -113,6 +113,27 @@ int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
     uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer);
 
+/* render::LightClustering (host/light_clustering.hpp; reference src/render/LightClustering.hpp:22-64) on a context the
+ * scene was uploaded to (borrowed): record = Camera::updateBuffer + prosper_pt_cluster_lights into the context-owned
+ * buffers (prosper_pt_read_light_clusters). */
+typedef struct prosper_host_light_clustering prosper_host_light_clustering;
+int prosper_host_light_clustering_create(prosper_pt_ctx *ctx, prosper_host_light_clustering **out);
+void prosper_host_light_clustering_destroy(prosper_host_light_clustering *pass);
+int prosper_host_light_clustering_record(
+    prosper_host_light_clustering *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, void *stream);
+
+/* render::DeferredShading (host/deferred_shading.hpp; reference src/render/DeferredShading.hpp:18-66) on a context the
+ * scene was uploaded to (borrowed): record = Camera::updateBuffer + LightClustering::record + DeferredShading::record
+ * (prosper_pt_deferred_shading) over `gbuffer` (host or device) into the context's HDR image; returns the
+ * DeferredShadingPC it pushed.  applyIbl != 0 is refused with PROSPER_PT_ERR_UNSUPPORTED. */
+typedef struct prosper_host_deferred_shading prosper_host_deferred_shading;
+int prosper_host_deferred_shading_create(prosper_pt_ctx *ctx, prosper_host_deferred_shading **out);
+void prosper_host_deferred_shading_destroy(prosper_host_deferred_shading *pass);
+int prosper_host_deferred_shading_record(
+    prosper_host_deferred_shading *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    const prosper_pt_restir_inputs *gbuffer, int applyIbl, uint32_t drawType, void *stream,
+    prosper_pt_deferred_shading_pc *outPushConstants);
+
 #ifdef __cplusplus
 }
 #endif

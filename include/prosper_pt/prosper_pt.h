@@ -597,6 +597,55 @@ int prosper_pt_read_gbuffer(
     prosper_pt_ctx *ctx, float *host_albedo_roughness, float *host_normal_metallic, float *host_depth, size_t pixels,
     void *stream);
 
+/* ---- clustered lighting and deferred shading (src/render/LightClustering.cpp, src/render/DeferredShading.cpp) ----
+ * prosper's default lighting of its G-buffer: LightClustering::record then DeferredShading::record, compute passes
+ * over the lights, the camera and the G-buffer, unshadowed.
+ *
+ * prosper_pt_cluster_lights: light_clustering.comp into context-owned buffers (grown as needed).  The grid is
+ * ceil(width/32) x ceil(height/32) x 17 clusters; the frustum's tile scale comes from camera->resolution, the slices
+ * from camera->near_ / far_.  Per cluster, x fastest: uint32 pair (indexOffset, pointCount << 16 | spotCount); cluster
+ * k's uint16 light indices sit at [k * 256, k * 256 + pointCount + spotCount), points first, each list in ascending
+ * light order.  A point light is listed where its sphere touches the cluster's frustum, every spot light everywhere.
+ * More than 128 of one type: the 128 lowest indices are kept and the rest counted as dropped.  Pending transform,
+ * light and material updates take effect first. */
+int prosper_pt_cluster_lights(
+    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, void *stream);
+/* The grid of the last clustering (x, y, z = 17); NO_SCENE before the first.  Any pointer may be NULL. */
+int prosper_pt_get_light_cluster_dims(prosper_pt_ctx *ctx, uint32_t *x, uint32_t *y, uint32_t *z);
+/* Synchronises `stream` and copies the last clustering to host memory; any pointer may be NULL.  `clusters` =
+ * x * y * z of that clustering.  host_pointers: clusters uint32 pairs; host_indices: clusters * 256 uint16 (entries past
+ * a cluster's counts are unspecified); host_count: entries kept (the GLSL's lightIndicesCount); host_dropped: entries
+ * past the 128 of a type; host_overflowing: clusters that dropped any. */
+int prosper_pt_read_light_clusters(
+    prosper_pt_ctx *ctx, uint32_t *host_pointers, uint16_t *host_indices, uint32_t *host_count, uint32_t *host_dropped,
+    uint32_t *host_overflowing, size_t clusters, void *stream);
+
+/* DeferredShadingPC (res/shader/shared/shader_structs/push_constants/deferred_shading.h) */
+typedef struct prosper_pt_deferred_shading_pc
+{
+    uint32_t drawType; /* prosper_DrawType: Position writes the position, other non-Default types the G-buffer albedo */
+    uint32_t ibl;      /* 1 is refused with PROSPER_PT_ERR_UNSUPPORTED (no irradiance / radiance maps, no BRDF LUT) */
+} prosper_pt_deferred_shading_pc;
+enum
+{
+    /* trace the G-buffer first (prosper_pt_trace_gbuffer with pc->drawType and `frameIndex`) into the context-owned
+     * buffers; `gbuffer` may then be NULL and is ignored */
+    PROSPER_PT_DEFERRED_TRACE_GBUFFER = 1u << 0,
+    /* with PROSPER_PT_DEFERRED_TRACE_GBUFFER only: the jittered G-buffer (PROSPER_PT_GBUFFER_JITTER) */
+    PROSPER_PT_DEFERRED_JITTER_GBUFFER = 1u << 1,
+};
+/* LightClustering::record + DeferredShading::record: clusters the lights (prosper_pt_cluster_lights) and shades every
+ * G-buffer texel into the context's HDR image (width x height RGBA32F, alpha 1; prosper_pt_read_hdr, _blit_rgba16f and
+ * _tone_map read it).  It overwrites whatever a render or a ReSTIR trace accumulated there.  The colour is the sun,
+ * then the cluster's point lights, then its spot lights, unshadowed.  A texel past the far plane (slice > 16) gets no
+ * point or spot lights; one nearer than the near plane uses slice 0.  `gbuffer`: host or device inputs
+ * (reservoirs ignored).  Pending updates are flushed once: both kernels read one scene and light version.
+ * `frameIndex` is read only by PROSPER_PT_DEFERRED_JITTER_GBUFFER. */
+int prosper_pt_deferred_shading(
+    prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
+    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
+    void *stream);
+
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of
  * per-tile HDR buffers".)  The reference renders the whole image on one GPU and asserts renderArea.offset == 0

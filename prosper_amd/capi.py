@@ -88,6 +88,11 @@ def lib():
         vp, u32, u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.GBufferTargets), vp]
     L.prosper_pt_get_gbuffer_device_ptrs.argtypes = [vp, C.POINTER(S.RestirInputs), C.POINTER(u32), C.POINTER(u32)]
     L.prosper_pt_read_gbuffer.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.prosper_pt_cluster_lights.argtypes = [vp, C.POINTER(S.CameraUniforms), u32, u32, vp]
+    L.prosper_pt_get_light_cluster_dims.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_read_light_clusters.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.prosper_pt_deferred_shading.argtypes = [
+        vp, C.POINTER(S.DeferredShadingPC), u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -157,6 +162,15 @@ def lib():
     L.prosper_host_gbuffer_tracer_destroy.argtypes = [vp]
     L.prosper_host_gbuffer_tracer_destroy.restype = None
     L.prosper_host_gbuffer_tracer_record.argtypes = [vp, vp, u32, u32, u32, u32, C.c_int, vp, C.POINTER(S.RestirInputs)]
+    L.prosper_host_light_clustering_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_light_clustering_destroy.argtypes = [vp]
+    L.prosper_host_light_clustering_destroy.restype = None
+    L.prosper_host_light_clustering_record.argtypes = [vp, vp, u32, u32, vp]
+    L.prosper_host_deferred_shading_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_deferred_shading_destroy.argtypes = [vp]
+    L.prosper_host_deferred_shading_destroy.restype = None
+    L.prosper_host_deferred_shading_record.argtypes = [
+        vp, vp, u32, u32, C.POINTER(S.RestirInputs), C.c_int, u32, vp, C.POINTER(S.DeferredShadingPC)]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -523,6 +537,56 @@ class Context:
         _check(lib().prosper_pt_restir_di_record(self._h, C.byref(pc), flags, C.byref(camera), width, height, None,
                                                  C.c_void_p(stream)))
         self._restir_extent = (width, height)
+
+    def cluster_lights(self, camera, width, height, stream=None):
+        """LightClustering::record (prosper_pt_cluster_lights) into the context's buffers; read_light_clusters reads them."""
+        self._sync_debug()
+        _check(lib().prosper_pt_cluster_lights(self._h, C.byref(camera), width, height, C.c_void_p(stream)))
+
+    def light_cluster_dims(self):
+        """(x, y, z) of the last clustering."""
+        x, y, z = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_get_light_cluster_dims(self._h, C.byref(x), C.byref(y), C.byref(z)))
+        return x.value, y.value, z.value
+
+    def read_light_clusters(self, stream=None):
+        """The last clustering: dict with pointers uint32 [z, y, x, 2], indices uint16 [z, y, x, 256], and the counters
+        count (entries kept), dropped (entries past the 128 of a type), overflowing (clusters that dropped any)."""
+        x, y, z = self.light_cluster_dims()
+        n = x * y * z
+        ptrs = np.empty((z, y, x, 2), np.uint32)
+        idx = np.empty((z, y, x, S.CLUSTER_MAX_POINTS + S.CLUSTER_MAX_SPOTS), np.uint16)
+        count, dropped, overflowing = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_read_light_clusters(self._h, ptrs.ctypes.data, idx.ctypes.data, C.byref(count),
+                                                    C.byref(dropped), C.byref(overflowing), n, C.c_void_p(stream)))
+        return {"pointers": ptrs, "indices": idx, "count": count.value, "dropped": dropped.value,
+                "overflowing": overflowing.value}
+
+    def deferred_shading(self, camera, albedo_roughness, normal_metallic, depth, draw_type=0, ibl=0, stream=None):
+        """LightClustering + DeferredShading over host G-buffer arrays ([h, w, 4], [h, w, 4], [h, w] float32) into the
+        HDR image (read_hdr)."""
+        self._sync_debug()
+        inp, keep, w, h = self._restir_host_inputs(albedo_roughness, normal_metallic, depth)
+        pc = S.DeferredShadingPC(int(draw_type), ibl)
+        _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), 0, 0, C.byref(camera), w, h, C.byref(inp),
+                                                 C.c_void_p(stream)))
+        del keep
+
+    def deferred_shading_device(self, camera, width, height, ar_ptr, nm_ptr, depth_ptr, draw_type=0, stream=None):
+        """Same over device G-buffer pointers."""
+        self._sync_debug()
+        inp = S.RestirInputs(ar_ptr, nm_ptr, depth_ptr, None, 1, 0)
+        pc = S.DeferredShadingPC(int(draw_type), 0)
+        _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), 0, 0, C.byref(camera), width, height,
+                                                 C.byref(inp), C.c_void_p(stream)))
+
+    def deferred_shading_traced(self, camera, width, height, draw_type=0, frame_index=0, jitter=False, stream=None):
+        """Same over the G-buffer it traces first (PROSPER_PT_DEFERRED_TRACE_GBUFFER): from the scene alone to the image."""
+        self._sync_debug()
+        flags = S.DEFERRED_TRACE_GBUFFER | (S.DEFERRED_JITTER_GBUFFER if jitter else 0)
+        pc = S.DeferredShadingPC(int(draw_type), 0)
+        _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), flags, frame_index, C.byref(camera), width,
+                                                 height, None, C.c_void_p(stream)))
 
     def set_tone_map_lut(self, lut_r9g9b9e5):
         """lut: uint32 [dim, dim, dim] (z, y, x) R9G9B9E5 texels, e.g. from prosper_amd.dds.read_lut."""

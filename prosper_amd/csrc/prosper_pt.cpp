@@ -846,6 +846,9 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     }
     if (ctx->restirScratch) (void)hipFree(ctx->restirScratch);
     if (ctx->gbufferOwned) (void)hipFree(ctx->gbufferOwned);
+    if (ctx->clusterPointers) (void)hipFree(ctx->clusterPointers);
+    if (ctx->clusterIndices) (void)hipFree(ctx->clusterIndices);
+    if (ctx->clusterDropped) (void)hipFree(ctx->clusterDropped);
     for (void *r : ctx->restirReservoirs)
         if (r) (void)hipFree(r);
     if (ctx->toneLut) (void)hipFree(ctx->toneLut);
@@ -1662,13 +1665,11 @@ static int restir_reservoir_buffers(prosper_pt_ctx *ctx, size_t pixels, hipStrea
     return PROSPER_PT_OK;
 }
 
-// The trace pass over device inputs: the HDR image, the traversal stacks, the launch.
-static int restir_trace(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height, const RestirDeviceInputs &in, hipStream_t s)
+// The context's HDR image as one whole width x height image (no stripes) for a pass that writes it: the caller-owned
+// buffer, or the owned one grown (and cleared) as needed.
+static int prepare_whole_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, hipStream_t s)
 {
-    const size_t pixels = (size_t)width * height;
-    const size_t bytes = pixels * sizeof(float4);
+    const size_t bytes = (size_t)width * height * sizeof(float4);
     if (ctx->externalHdr)
     {
         if (ctx->externalHdrBytes < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "caller-owned output buffer is too small");
@@ -1694,6 +1695,16 @@ static int restir_trace(
     ctx->stripeIndex = 0;
     ctx->stripeCount = 1;
     wait_for_gather_before_writing_tile(ctx, s);
+    return PROSPER_PT_OK;
+}
+
+// The trace pass over device inputs: the HDR image, the traversal stacks, the launch.
+static int restir_trace(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const RestirDeviceInputs &in, hipStream_t s)
+{
+    const int hrc = prepare_whole_hdr(ctx, width, height, s);
+    if (hrc != PROSPER_PT_OK) return hrc;
 
     int32_t *ovf = nullptr;
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), s, &ovf);
@@ -1963,6 +1974,173 @@ int prosper_pt_restir_di_record(
     ctx->restirLastReservoirBytes = pixels * 8u;
     rc = restir_trace(ctx, pc, camera, width, height, din, s);
     if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+// ---- clustered lighting and deferred shading (src/render/LightClustering.cpp, src/render/DeferredShading.cpp) ----
+
+static ClusterParams cluster_params(const prosper_CameraUniforms *camera, uint32_t width, uint32_t height)
+{
+    ClusterParams c;
+    std::memcpy(c.worldToCamera, &camera->worldToCamera, 64);
+    float c2c[16];
+    std::memcpy(c2c, &camera->cameraToClip, 64);
+    c.cameraToClip00 = c2c[0];
+    c.cameraToClip11 = c2c[1 * 4 + 1];
+    c.resolution[0] = (float)camera->resolution[0];
+    c.resolution[1] = (float)camera->resolution[1];
+    c.near_ = camera->near_;
+    c.far_ = camera->far_;
+    c.dimX = (width + kClusterDim - 1u) / kClusterDim;
+    c.dimY = (height + kClusterDim - 1u) / kClusterDim;
+    return c;
+}
+
+// The clustering pass on `s` after restir_flush: buffers grown as needed (the index buffer starts as 0xFFFF), the
+// launch.  Every cluster writes its pointer and dropped count, so nothing is cleared (LightClustering.cpp's fillBuffer
+// of the counter is replaced by summing the pointers' counts in prosper_pt_read_light_clusters).
+static int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
+{
+    const size_t clusters = (size_t)c.dimX * c.dimY * (kClusterZSlices + 1u);
+    if (ctx->clusterCapacity < clusters || !ctx->clusterPointers)
+    {
+        PPT_HIP(hipStreamSynchronize(s));
+        if (ctx->clusterPointers) PPT_HIP(hipFree(ctx->clusterPointers));
+        if (ctx->clusterIndices) PPT_HIP(hipFree(ctx->clusterIndices));
+        if (ctx->clusterDropped) PPT_HIP(hipFree(ctx->clusterDropped));
+        ctx->clusterPointers = nullptr;
+        ctx->clusterIndices = nullptr;
+        ctx->clusterDropped = nullptr;
+        ctx->clusterCapacity = 0;
+        ctx->clusterDims[0] = ctx->clusterDims[1] = ctx->clusterDims[2] = 0;
+        PPT_HIP(hipMalloc(&ctx->clusterPointers, clusters * 8u));
+        PPT_HIP(hipMalloc((void **)&ctx->clusterIndices, clusters * kClusterSlot * 2u));
+        PPT_HIP(hipMemset(ctx->clusterIndices, 0xFF, clusters * kClusterSlot * 2u));
+        PPT_HIP(hipMalloc((void **)&ctx->clusterDropped, clusters * 4u));
+        ctx->clusterCapacity = clusters;
+    }
+    launch_light_clustering(ctx->scene, c, ctx->clusterPointers, ctx->clusterIndices, ctx->clusterDropped, s);
+    PPT_HIP(hipGetLastError());
+    ctx->clusterDims[0] = c.dimX;
+    ctx->clusterDims[1] = c.dimY;
+    ctx->clusterDims[2] = kClusterZSlices + 1u;
+    return PROSPER_PT_OK;
+}
+
+// near_ and far_ feed log(far / near) and pow(far / near, s): both positive and ordered
+static bool cluster_camera_ok(const prosper_CameraUniforms *camera)
+{
+    return camera->near_ > 0.0f && camera->far_ > camera->near_ && camera->resolution[0] > 0 && camera->resolution[1] > 0;
+}
+
+int prosper_pt_cluster_lights(
+    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (!camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: empty extent");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: camera needs 0 < near_ < far_ and a resolution");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
+    const int crc = restir_check_scene(ctx, "prosper_pt_cluster_lights");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = restir_flush(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, cluster_params(camera, width, height), s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_light_cluster_dims(prosper_pt_ctx *ctx, uint32_t *x, uint32_t *y, uint32_t *z)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_light_cluster_dims: null argument");
+    if (!ctx->clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
+    if (x) *x = ctx->clusterDims[0];
+    if (y) *y = ctx->clusterDims[1];
+    if (z) *z = ctx->clusterDims[2];
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_light_clusters(
+    prosper_pt_ctx *ctx, uint32_t *host_pointers, uint16_t *host_indices, uint32_t *host_count, uint32_t *host_dropped,
+    uint32_t *host_overflowing, size_t clusters, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: null argument");
+    if (!ctx->clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
+    if (clusters != (size_t)ctx->clusterDims[0] * ctx->clusterDims[1] * ctx->clusterDims[2])
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: cluster count differs from the last clustering's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<uint32_t> ptrs(clusters * 2u), dropped(clusters);
+    PPT_HIP(hipMemcpyAsync(ptrs.data(), ctx->clusterPointers, clusters * 8u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipMemcpyAsync(dropped.data(), ctx->clusterDropped, clusters * 4u, hipMemcpyDeviceToHost, s));
+    if (host_indices)
+        PPT_HIP(hipMemcpyAsync(host_indices, ctx->clusterIndices, clusters * kClusterSlot * 2u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    if (host_pointers) std::memcpy(host_pointers, ptrs.data(), clusters * 8u);
+    uint32_t count = 0, droppedSum = 0, overflowing = 0;
+    for (size_t k = 0; k < clusters; ++k)
+    {
+        count += (ptrs[2 * k + 1] >> 16) + (ptrs[2 * k + 1] & 0xFFFFu);
+        droppedSum += dropped[k];
+        overflowing += dropped[k] != 0u;
+    }
+    if (host_count) *host_count = count;
+    if (host_dropped) *host_dropped = droppedSum;
+    if (host_overflowing) *host_overflowing = overflowing;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_deferred_shading(
+    prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
+    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
+    void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (flags & ~(uint32_t)(PROSPER_PT_DEFERRED_TRACE_GBUFFER | PROSPER_PT_DEFERRED_JITTER_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: unknown flags");
+    if ((flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) && !(flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: JITTER_GBUFFER without TRACE_GBUFFER");
+    const bool traced = (flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER) != 0;
+    if (!pc || !camera ||
+        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: ibl is 0 or 1");
+    if (pc->ibl == 1u)
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT, which the library does not generate");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: camera needs 0 < near_ < far_ and a resolution");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
+    const int crc = restir_check_scene(ctx, "prosper_pt_deferred_shading");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pixels = (size_t)width * height;
+    int rc = restir_flush(ctx, s);
+    RestirDeviceInputs din = {};
+    if (traced)
+    {
+        prosper_pt_gbuffer_targets t = {};
+        if (rc == PROSPER_PT_OK) rc = gbuffer_owned_targets(ctx, pixels, s, t);
+        if (rc == PROSPER_PT_OK)
+            rc = gbuffer_trace(ctx, pc->drawType, frameIndex, (flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) != 0, camera,
+                               width, height, t, s);
+        din.ar = t.albedoRoughness;
+        din.nm = t.normalMetallic;
+        din.depth = t.nonLinearDepth;
+    }
+    else if (rc == PROSPER_PT_OK)
+        rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
+    const ClusterParams c = cluster_params(camera, width, height);
+    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, c, s);
+    if (rc == PROSPER_PT_OK) rc = prepare_whole_hdr(ctx, width, height, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    launch_deferred_shading(
+        ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth, ctx->clusterPointers,
+        ctx->clusterIndices, ctx->hdr, s);
+    PPT_HIP(hipGetLastError());
     return mark_versions_read(ctx, s);
 }
 

@@ -329,6 +329,11 @@ struct prosper_pt_ctx
     size_t gbufferOwnedBytes = 0;
     prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
     uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
+    void *clusterPointers = nullptr;    // prosper_pt_cluster_lights: uint2 per cluster
+    uint16_t *clusterIndices = nullptr; // kClusterSlot entries per cluster
+    uint32_t *clusterDropped = nullptr;  // entries dropped, per cluster
+    size_t clusterCapacity = 0;          // clusters the buffers hold
+    uint32_t clusterDims[3] = {};        // of the last clustering
     uint32_t *toneLut = nullptr; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     void *toneScratch = nullptr; // RGBA8 output when the caller only wants a host copy

@@ -7,6 +7,8 @@
 //   eval_fn             device self-test entry (prosper_pt_eval_device_fn)
 //   restir_di_*         ReSTIR-DI initial reservoirs, spatial reuse and trace over a G-buffer
 //   gbuffer_trace       the ray-traced G-buffer those passes read
+//   light_clustering    per-cluster point / spot light lists (LightClustering)
+//   deferred_shading    unshadowed shading of the G-buffer over those lists (DeferredShading)
 #include "pt_kernels.hpp"
 
 #include "bvh_encode.hpp"
@@ -850,6 +852,231 @@ void launch_gbuffer_trace(
     hipLaunchKernelGGL(
         gbuffer_trace_kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
         static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow);
+}
+
+// ------------------------------------------------------------------------------------------
+// Clustered lighting (src/render/LightClustering.cpp, src/render/DeferredShading.cpp):
+//   light_clustering_kernel   one 256-lane block per cluster builds its point / spot lists (light_clustering.comp)
+//   deferred_shading_kernel   one lane per pixel shades the G-buffer texel over its cluster's lists
+//                             (deferred_shading.comp, scene/light_clusters.glsl), unshadowed
+// The three rules the GLSL leaves open: ascending light order in a list, the fixed slot
+// clusterLinearIndex * 256 of the index buffer, and the 128 lowest indices of each type kept on overflow.
+// ------------------------------------------------------------------------------------------
+
+static_assert(PROSPER_MAX_POINT_LIGHT_COUNT <= 256u * 32u, "a lane's share of the point lights must fit a 32-bit mask");
+
+// light_clustering.comp clusterFrustum: six planes (xyz, w), signedDistance = dot(xyz, p) - w
+struct ClusterFrustum
+{
+    f4 planes[6];
+};
+
+// scene/light_clusters.glsl sliceStart
+PPT_D float slice_start(const ClusterParams &c, uint32_t slice)
+{
+    const float sliceFrac = (float)slice / (float)kClusterZSlices;
+    return c.near_ * pow_(c.far_ / c.near_, sliceFrac);
+}
+
+PPT_D ClusterFrustum cluster_frustum(const ClusterParams &c, uint32_t cx, uint32_t cy, uint32_t cz)
+{
+    const float tileScaleX = c.resolution[0] / (float)(2u * kClusterDim);
+    const float tileScaleY = c.resolution[1] / (float)(2u * kClusterDim);
+    const float tileBiasX = tileScaleX - (float)cx, tileBiasY = tileScaleY - (float)cy;
+    // c1 = (m00 * sx, 0, -bx, 0), c2 = (0, m11 * sy, -by, 0), c4 = (0, 0, -1, 0); the projection's Y is already flipped
+    const float c1x = c.cameraToClip00 * tileScaleX, c1z = -tileBiasX;
+    const float c2y = c.cameraToClip11 * tileScaleY, c2z = -tileBiasY;
+    ClusterFrustum f;
+    f.planes[0] = f4{-c1x, 0.0f, -1.0f - c1z, 0.0f};
+    f.planes[1] = f4{c1x, 0.0f, -1.0f + c1z, 0.0f};
+    f.planes[2] = f4{0.0f, -c2y, -1.0f - c2z, 0.0f};
+    f.planes[3] = f4{0.0f, c2y, -1.0f + c2z, 0.0f};
+    f.planes[4] = f4{0.0f, 0.0f, -1.0f, cz == 0 ? 0.0f : slice_start(c, cz)};
+    f.planes[5] = f4{0.0f, 0.0f, 1.0f, -slice_start(c, cz + 1u)};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+    {
+        const f4 p = f.planes[i];
+        const float inv = 1.0f / sqrt_(__builtin_fmaf(p.z, p.z, __builtin_fmaf(p.y, p.y, p.x * p.x)));
+        f.planes[i] = f4{p.x * inv, p.y * inv, p.z * inv, p.w * inv};
+    }
+    return f;
+}
+
+// isPointVisible: the light's sphere (worldToCamera * position, radianceAndRadius.w) against the six planes
+PPT_D bool point_light_visible(const ClusterParams &c, const ClusterFrustum &f, const prosper_PointLight &light)
+{
+    const float *m = c.worldToCamera;
+    const prosper_vec4 q = light.position;
+    const float x = __builtin_fmaf(m[12], q.w, __builtin_fmaf(m[8], q.z, __builtin_fmaf(m[4], q.y, m[0] * q.x)));
+    const float y = __builtin_fmaf(m[13], q.w, __builtin_fmaf(m[9], q.z, __builtin_fmaf(m[5], q.y, m[1] * q.x)));
+    const float z = __builtin_fmaf(m[14], q.w, __builtin_fmaf(m[10], q.z, __builtin_fmaf(m[6], q.y, m[2] * q.x)));
+    const float r = light.radianceAndRadius.w;
+    bool visible = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+    {
+        const f4 p = f.planes[i];
+        visible = visible && __builtin_fmaf(p.z, z, __builtin_fmaf(p.y, y, p.x * x)) - p.w >= -r;
+    }
+    return visible;
+}
+
+__global__ __launch_bounds__(256) void light_clustering_kernel(
+    DeviceScene s, ClusterParams c, uint2 *__restrict__ pointers, uint16_t *__restrict__ indices,
+    uint32_t *__restrict__ dropped)
+{
+    __shared__ uint32_t waveTotals[4];
+    const uint32_t cx = blockIdx.x, cy = blockIdx.y, cz = blockIdx.z;
+    const uint32_t cluster = (cz * c.dimY + cy) * c.dimX + cx;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const ClusterFrustum f = cluster_frustum(c, cx, cy, cz);
+
+    // contiguous chunks of roundedUpQuotient(count, 256) lights per lane, as the GLSL splits them
+    const uint32_t totalPoints = s.pointLightCount;
+    const uint32_t perLane = (totalPoints + 255u) / 256u;
+    uint32_t mask = 0, count = 0;
+    for (uint32_t k = 0; k < perLane; ++k)
+    {
+        const uint32_t pi = tid * perLane + k;
+        if (pi >= totalPoints) break;
+        if (point_light_visible(c, f, s.pointLights->lights[pi]))
+        {
+            mask |= 1u << k;
+            ++count;
+        }
+    }
+    // block-wide exclusive prefix of the lanes' counts: lane order is light order, so the list is ascending
+    uint32_t inclusive = count;
+#pragma unroll
+    for (uint32_t off = 1; off < 64u; off <<= 1)
+    {
+        const uint32_t t = __shfl_up(inclusive, off, 64);
+        if (lane >= off) inclusive += t;
+    }
+    if (lane == 63u) waveTotals[wave] = inclusive;
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t w = 0; w < wave; ++w) base += waveTotals[w];
+    const uint32_t visiblePoints = (waveTotals[0] + waveTotals[1]) + (waveTotals[2] + waveTotals[3]);
+    const uint32_t keptPoints = visiblePoints < kClusterMaxPoints ? visiblePoints : kClusterMaxPoints;
+    // isSpotVisible is always true: every spot, the lowest kClusterMaxSpots of them
+    const uint32_t totalSpots = s.spotLightCount;
+    const uint32_t keptSpots = totalSpots < kClusterMaxSpots ? totalSpots : kClusterMaxSpots;
+    uint16_t *slot = indices + (size_t)cluster * kClusterSlot;
+
+    uint32_t pos = base + inclusive - count;
+    for (uint32_t k = 0; mask != 0u; ++k, mask >>= 1)
+    {
+        if (!(mask & 1u)) continue;
+        if (pos < kClusterMaxPoints) slot[pos] = (uint16_t)(tid * perLane + k);
+        ++pos;
+    }
+    for (uint32_t i = tid; i < keptSpots; i += 256u) slot[keptPoints + i] = (uint16_t)i;
+
+    if (tid == 0)
+    {
+        const uint32_t kept = keptPoints + keptSpots;
+        // packClusterPointer; an empty cluster's offset is 0, as the GLSL writes it
+        pointers[cluster] = make_uint2(kept > 0u ? cluster * kClusterSlot : 0u, (keptPoints << 16) | keptSpots);
+        // per cluster, not one global atomic counter: 34 680 clusters at 1920x1080 would serialise on its address
+        dropped[cluster] = (visiblePoints - keptPoints) + (totalSpots - keptSpots);
+    }
+}
+
+void launch_light_clustering(
+    const DeviceScene &s, const ClusterParams &c, void *pointers, uint16_t *indices, uint32_t *dropped, hipStream_t stream)
+{
+    if (c.dimX == 0 || c.dimY == 0) return;
+    hipLaunchKernelGGL(
+        light_clustering_kernel, dim3(c.dimX, c.dimY, kClusterZSlices + 1u), dim3(256), 0, stream, s, c,
+        static_cast<uint2 *>(pointers), indices, dropped);
+}
+
+// deferred_shading.comp: the G-buffer texel's VisibleSurface (restir_surface), the sun, then its cluster's point and
+// spot lists, each summed from zero and added in that order.  Debug draw types write the position or the G-buffer's
+// albedo without lighting (the GLSL's lighting of those texels is overwritten).
+struct DeferredParams
+{
+    RestirParams r;
+    float near_, far_;
+    uint32_t clustersX, clustersY;
+};
+
+__global__ __launch_bounds__(256) void deferred_shading_kernel(
+    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
+    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr)
+{
+    uint32_t px, py;
+    if (!restir_pixel(d.r, px, py) || px >= d.r.width || py >= d.r.height) return;
+    const size_t i = (size_t)py * d.r.width + px;
+    const float depth = nonLinearDepth[i];
+    const Surface sf = restir_surface(d.r, px, py, depth, albedoRoughness[i], normalMetallic[i]);
+    if (d.r.drawType != PROSPER_DRAW_TYPE_DEFAULT)
+    {
+        const f3 c = d.r.drawType == PROSPER_DRAW_TYPE_POSITION ? sf.positionWS : sf.material.albedo;
+        hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        return;
+    }
+    const float linearDepth = linearize_depth(d.r, depth);
+
+    // evalDirectionalLight (scene/lighting.glsl:8-12)
+    const prosper_DirectionalLightParameters sun = *s.directionalLight;
+    const f3 sunL = -normalize(f3{sun.direction.x, sun.direction.y, sun.direction.z});
+    f3 color = f3{0.0f, 0.0f, 0.0f} + f3{sun.irradiance.x, sun.irradiance.y, sun.irradiance.z} * eval_brdf_times_nol(sunL, sf);
+
+    // clusterIndex: slice = uint(16 * log(-z / near) / log(far / near)); nearer than near (or NaN) is slice 0, past
+    // the last slice (16) a cluster without lights
+    const float ratio = -linearDepth / d.near_;
+    float slice = ratio > 0.0f ? ((float)kClusterZSlices * log2_(ratio)) / log2_(d.far_ / d.near_) : 0.0f;
+    if (!(slice >= 0.0f)) slice = 0.0f;
+    uint32_t offset = 0, pointCount = 0, spotCount = 0;
+    if (slice < (float)(kClusterZSlices + 1u))
+    {
+        const uint32_t cluster = ((uint32_t)slice * d.clustersY + py / kClusterDim) * d.clustersX + px / kClusterDim;
+        const uint2 packed = pointers[cluster];
+        offset = packed.x;
+        pointCount = packed.y >> 16;
+        spotCount = packed.y & 0xFFFFu;
+    }
+    f3 points = f3{0.0f, 0.0f, 0.0f};
+    for (uint32_t k = 0; k < pointCount; ++k)
+    {
+        f3 l, irradiance;
+        float dist;
+        eval_point_light(s.pointLights->lights[indices[offset + k]], sf.positionWS, l, dist, irradiance);
+        points = points + irradiance * eval_brdf_times_nol(l, sf);
+    }
+    color = color + points;
+    f3 spots = f3{0.0f, 0.0f, 0.0f};
+    for (uint32_t k = 0; k < spotCount; ++k)
+    {
+        f3 l, irradiance;
+        float dist;
+        eval_spot_light(s.spotLights->lights[indices[offset + pointCount + k]], sf.positionWS, l, dist, irradiance);
+        spots = spots + irradiance * eval_brdf_times_nol(l, sf);
+    }
+    color = color + spots;
+    hdr[i] = make_float4(color.x, color.y, color.z, 1.0f);
+}
+
+void launch_deferred_shading(
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream)
+{
+    if (width == 0 || height == 0) return;
+    DeferredParams d;
+    d.r = restir_params(drawType, 0, 0, width, height, cam);
+    d.near_ = c.near_;
+    d.far_ = c.far_;
+    d.clustersX = c.dimX;
+    d.clustersY = c.dimY;
+    hipLaunchKernelGGL(
+        deferred_shading_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
+        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
+        static_cast<const uint2 *>(pointers), indices, hdr);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -90,6 +90,30 @@ struct GBufferTraceParams
 void launch_gbuffer_trace(
     const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
     int32_t *stackOverflow, hipStream_t stream);
+// Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
+// uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
+// [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the
+// kClusterMaxPoints / kClusterMaxSpots of a type.
+constexpr uint32_t kClusterDim = 32;       // LightClustering::clusterDim
+constexpr uint32_t kClusterZSlices = 16;   // LightClustering::zSlices
+constexpr uint32_t kClusterMaxPoints = 128; // maxPointIndicesPerTile
+constexpr uint32_t kClusterMaxSpots = 128;  // maxSpotIndicesPerTile
+constexpr uint32_t kClusterSlot = kClusterMaxPoints + kClusterMaxSpots;
+struct ClusterParams
+{
+    float worldToCamera[16]; // column-major
+    float cameraToClip00, cameraToClip11;
+    float resolution[2]; // camera.resolution, which the tile scale is built from (not the extent)
+    float near_, far_;
+    uint32_t dimX, dimY; // ceil(extent / kClusterDim)
+};
+void launch_light_clustering(
+    const DeviceScene &s, const ClusterParams &c, void *pointers, uint16_t *indices, uint32_t *dropped, hipStream_t stream);
+// One lane per pixel over restir_grid_blocks(width, height); reads the lists launch_light_clustering wrote with `c`.
+void launch_deferred_shading(
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream);
 void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);

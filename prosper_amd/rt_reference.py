@@ -235,6 +235,79 @@ class GBufferTracer:
             pass
 
 
+class LightClustering:
+    """render::LightClustering (csrc/host/light_clustering.hpp) on a Context the scene was uploaded to: record clusters
+    the lights for the camera into the context's buffers (Context.read_light_clusters reads them)."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_light_clustering_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, width, height, stream=None):
+        rc = lib().prosper_host_light_clustering_record(self._h, camera._h, width, height, C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_light_clustering_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeferredShading:
+    """render::DeferredShading (csrc/host/deferred_shading.hpp) on a Context the scene was uploaded to: record clusters
+    the lights and shades the G-buffer into the context's HDR image (Context.read_hdr); returns the DeferredShadingPC."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_deferred_shading_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, albedo_roughness, normal_metallic, depth, apply_ibl=False, draw_type="Default",
+               stream=None):
+        """Over host G-buffer arrays ([h, w, 4], [h, w, 4], [h, w] float32)."""
+        ar = np.ascontiguousarray(albedo_roughness, np.float32)
+        nm = np.ascontiguousarray(normal_metallic, np.float32)
+        dp = np.ascontiguousarray(depth, np.float32)
+        h, w = dp.shape
+        inp = S.RestirInputs(ar.ctypes.data, nm.ctypes.data, dp.ctypes.data, None, 0, 0)
+        return self.record_device(camera, inp, w, h, apply_ibl, draw_type, stream)
+
+    def record_device(self, camera, gbuffer, width, height, apply_ibl=False, draw_type="Default", stream=None):
+        """Over a G-buffer given as S.RestirInputs (e.g. GBufferTracer.record's)."""
+        pc = S.DeferredShadingPC()
+        rc = lib().prosper_host_deferred_shading_record(
+            self._h, camera._h, width, height, C.byref(gbuffer), int(apply_ibl),
+            S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type), C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_deferred_shading_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class TiledRtReference:
     """render::TiledRtReference (csrc/host/tiled_rt_reference.hpp): one rank of a multi-GPU job.  record() renders the
     rank's stripes and enqueues the RCCL gather + de-interleave to the root; read_gathered() there returns the image."""

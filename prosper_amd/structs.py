@@ -344,3 +344,18 @@ GBUFFER_JITTER = 1 << 0
 
 class GBufferTargets(C.Structure):
     _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetallic", C.c_void_p), ("nonLinearDepth", C.c_void_p)]
+
+
+class DeferredShadingPC(C.Structure):
+    """DeferredShadingPC, res/shader/shared/shader_structs/push_constants/deferred_shading.h"""
+    _fields_ = [("drawType", C.c_uint32), ("ibl", C.c_uint32)]
+
+
+# prosper_pt_deferred_shading flags: trace the G-buffer first (optionally jittered)
+DEFERRED_TRACE_GBUFFER = 1 << 0
+DEFERRED_JITTER_GBUFFER = 1 << 1
+# LightClustering: 32x32-pixel tiles, 16 depth slices (+ 1), 128 point + 128 spot entries per cluster
+CLUSTER_DIM = 32
+CLUSTER_Z_SLICES = 16
+CLUSTER_MAX_POINTS = 128
+CLUSTER_MAX_SPOTS = 128

@@ -9,6 +9,9 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
 
     --restir-di [--no-spatial]   direct illumination instead: --spp accumulated frames of prosper_pt_restir_di_record
                                  over the jittered ray-traced G-buffer it traces first (PROSPER_PT_RESTIR_TRACE_GBUFFER)
+    --deferred                   prosper's default lighting instead: the pixel-centre ray-traced G-buffer, light
+                                 clustering and deferred shading (prosper_pt_deferred_shading with
+                                 PROSPER_PT_DEFERRED_TRACE_GBUFFER), unshadowed, one frame
 """
 import argparse
 import math
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--restir-di", action="store_true", help="ReSTIR-DI direct illumination from a traced G-buffer")
     ap.add_argument("--no-spatial", action="store_true", help="with --restir-di: no spatial reuse")
+    ap.add_argument("--deferred", action="store_true", help="clustered deferred shading of a traced G-buffer")
     args = ap.parse_args()
     from prosper_amd import capi, dds, gltf, ktx, structs as S
     from prosper_amd.rt_reference import Camera
@@ -66,7 +70,14 @@ def main():
     ctx.upload_scene(world)
     st = ctx.scene_stats()
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_SKIP_HISTORY | (S.PC_FLAG_IBL if args.env else 0)
-    if args.restir_di:
+    if args.deferred:
+        import time
+        t0 = time.perf_counter()
+        ctx.deferred_shading_traced(cam, w, h)
+        ctx.read_hdr()  # (synchronises)
+        ms = (time.perf_counter() - t0) * 1e3
+        args.spp = 1
+    elif args.restir_di:
         import time
         t0 = time.perf_counter()
         for frame in range(1, args.spp + 1):
