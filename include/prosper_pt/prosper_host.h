@@ -125,7 +125,8 @@ int prosper_host_light_clustering_record(
 /* render::DeferredShading (host/deferred_shading.hpp; reference src/render/DeferredShading.hpp:18-66) on a context the
  * scene was uploaded to (borrowed): record = Camera::updateBuffer + LightClustering::record + DeferredShading::record
  * (prosper_pt_deferred_shading) over `gbuffer` (host or device) into the context's HDR image; returns the
- * DeferredShadingPC it pushed.  applyIbl != 0 is refused with PROSPER_PT_ERR_UNSUPPORTED. */
+ * DeferredShadingPC it pushed.  applyIbl != 0 adds evalIBL; it is refused with PROSPER_PT_ERR_UNSUPPORTED until
+ * ImageBasedLighting::recordGeneration has run for the current scene. */
 typedef struct prosper_host_deferred_shading prosper_host_deferred_shading;
 int prosper_host_deferred_shading_create(prosper_pt_ctx *ctx, prosper_host_deferred_shading **out);
 void prosper_host_deferred_shading_destroy(prosper_host_deferred_shading *pass);
@@ -133,6 +134,15 @@ int prosper_host_deferred_shading_record(
     prosper_host_deferred_shading *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const prosper_pt_restir_inputs *gbuffer, int applyIbl, uint32_t drawType, void *stream,
     prosper_pt_deferred_shading_pc *outPushConstants);
+
+/* render::ImageBasedLighting (host/image_based_lighting.hpp; reference src/render/ImageBasedLighting.hpp) on a context
+ * the scene was uploaded to (borrowed): record_generation = prosper_pt_generate_ibl; is_generated returns 1 or 0 (or an
+ * error code), 0 again after a scene upload. */
+typedef struct prosper_host_image_based_lighting prosper_host_image_based_lighting;
+int prosper_host_image_based_lighting_create(prosper_pt_ctx *ctx, prosper_host_image_based_lighting **out);
+void prosper_host_image_based_lighting_destroy(prosper_host_image_based_lighting *pass);
+int prosper_host_image_based_lighting_is_generated(prosper_host_image_based_lighting *pass);
+int prosper_host_image_based_lighting_record_generation(prosper_host_image_based_lighting *pass, void *stream);
 
 #ifdef __cplusplus
 }

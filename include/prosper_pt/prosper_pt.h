@@ -624,7 +624,8 @@ int prosper_pt_read_light_clusters(
 typedef struct prosper_pt_deferred_shading_pc
 {
     uint32_t drawType; /* prosper_DrawType: Position writes the position, other non-Default types the G-buffer albedo */
-    uint32_t ibl;      /* 1 is refused with PROSPER_PT_ERR_UNSUPPORTED (no irradiance / radiance maps, no BRDF LUT) */
+    uint32_t ibl;      /* 1 adds evalIBL over the maps of prosper_pt_generate_ibl; refused with PROSPER_PT_ERR_UNSUPPORTED
+                        * until they exist for the current scene */
 } prosper_pt_deferred_shading_pc;
 enum
 {
@@ -637,7 +638,8 @@ enum
 /* LightClustering::record + DeferredShading::record: clusters the lights (prosper_pt_cluster_lights) and shades every
  * G-buffer texel into the context's HDR image (width x height RGBA32F, alpha 1; prosper_pt_read_hdr, _blit_rgba16f and
  * _tone_map read it).  It overwrites whatever a render or a ReSTIR trace accumulated there.  The colour is the sun,
- * then the cluster's point lights, then its spot lights, unshadowed.  A texel past the far plane (slice > 16) gets no
+ * then the cluster's point lights, then its spot lights, unshadowed, then with pc->ibl = 1 evalIBL over the maps of
+ * prosper_pt_generate_ibl (refused with PROSPER_PT_ERR_UNSUPPORTED until they exist).  A texel past the far plane (slice > 16) gets no
  * point or spot lights; one nearer than the near plane uses slice 0.  `gbuffer`: host or device inputs
  * (reservoirs ignored).  Pending updates are flushed once: both kernels read one scene and light version.
  * `frameIndex` is read only by PROSPER_PT_DEFERRED_JITTER_GBUFFER. */
@@ -645,6 +647,37 @@ int prosper_pt_deferred_shading(
     prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
     const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
     void *stream);
+
+/* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
+ * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.
+ *
+ * prosper_pt_generate_ibl runs the three passes on `stream` into context-owned maps (allocated by the first call, kept
+ * for the context's lifetime): the 6 x 64^2 irradiance cube, the 6 x 512^2 prefiltered radiance cube with 10 mips
+ * (roughness = mip / 10) and the 512^2 split-sum BRDF LUT.  Every environment lookup is the path tracer's seamless
+ * bilinear sky lookup, clamped per channel to 10.  A scene without a sky gives all-zero cubes and the same LUT.  Calling
+ * it again regenerates the maps, bit for bit the same.  NO_SCENE before the first prosper_pt_upload_scene, which clears
+ * the maps' `generated` (they describe the old sky); light, transform, texture, material and mesh updates keep them. */
+int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream);
+typedef struct prosper_pt_ibl_info
+{
+    uint32_t generated;      /* 1 once prosper_pt_generate_ibl ran for the current scene */
+    uint32_t irradianceSize; /* 64 */
+    uint32_t radianceSize;   /* 512 (mip 0) */
+    uint32_t radianceMips;   /* 10 */
+    uint32_t lutSize;        /* 512 */
+    /* device time of each pass of the last generation (0 before the first); reading them waits for it */
+    float irradianceMs, radianceMs, lutMs;
+} prosper_pt_ibl_info;
+int prosper_pt_get_ibl_info(prosper_pt_ctx *ctx, prosper_pt_ibl_info *out);
+/* Synchronises `stream` and copies the maps without their borders to host memory; any pointer may be NULL, and each
+ * given one must hold exactly its map.  Faces +X, -X, +Y, -Y, +Z, -Z, each row-major.
+ *   irradiance: 6 x 64 x 64 RGBA16F (alpha 0), irradiance_bytes = 196 608
+ *   radiance:   the mips one after another from mip 0, each 6 x n x n RGBA16F (alpha 0), radiance_bytes = 16 777 200
+ *   lut:        512 x 512 R16G16 UNORM (scale, bias), row = roughness * 512, column = NoV * 512, lut_bytes = 1 048 576
+ * NO_SCENE if nothing has been generated for the current scene. */
+int prosper_pt_read_ibl(
+    prosper_pt_ctx *ctx, uint16_t *irradiance_rgba16f, size_t irradiance_bytes, uint16_t *radiance_rgba16f,
+    size_t radiance_bytes, uint16_t *lut_rg16, size_t lut_bytes, void *stream);
 
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of

@@ -93,6 +93,9 @@ def lib():
     L.prosper_pt_read_light_clusters.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.prosper_pt_deferred_shading.argtypes = [
         vp, C.POINTER(S.DeferredShadingPC), u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
+    L.prosper_pt_generate_ibl.argtypes = [vp, vp]
+    L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
+    L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -171,6 +174,11 @@ def lib():
     L.prosper_host_deferred_shading_destroy.restype = None
     L.prosper_host_deferred_shading_record.argtypes = [
         vp, vp, u32, u32, C.POINTER(S.RestirInputs), C.c_int, u32, vp, C.POINTER(S.DeferredShadingPC)]
+    L.prosper_host_image_based_lighting_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_image_based_lighting_destroy.argtypes = [vp]
+    L.prosper_host_image_based_lighting_destroy.restype = None
+    L.prosper_host_image_based_lighting_is_generated.argtypes = [vp]
+    L.prosper_host_image_based_lighting_record_generation.argtypes = [vp, vp]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -572,21 +580,50 @@ class Context:
                                                  C.c_void_p(stream)))
         del keep
 
-    def deferred_shading_device(self, camera, width, height, ar_ptr, nm_ptr, depth_ptr, draw_type=0, stream=None):
+    def deferred_shading_device(self, camera, width, height, ar_ptr, nm_ptr, depth_ptr, draw_type=0, stream=None, ibl=0):
         """Same over device G-buffer pointers."""
         self._sync_debug()
         inp = S.RestirInputs(ar_ptr, nm_ptr, depth_ptr, None, 1, 0)
-        pc = S.DeferredShadingPC(int(draw_type), 0)
+        pc = S.DeferredShadingPC(int(draw_type), int(ibl))
         _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), 0, 0, C.byref(camera), width, height,
                                                  C.byref(inp), C.c_void_p(stream)))
 
-    def deferred_shading_traced(self, camera, width, height, draw_type=0, frame_index=0, jitter=False, stream=None):
+    def deferred_shading_traced(self, camera, width, height, draw_type=0, frame_index=0, jitter=False, stream=None,
+                                ibl=0):
         """Same over the G-buffer it traces first (PROSPER_PT_DEFERRED_TRACE_GBUFFER): from the scene alone to the image."""
         self._sync_debug()
         flags = S.DEFERRED_TRACE_GBUFFER | (S.DEFERRED_JITTER_GBUFFER if jitter else 0)
-        pc = S.DeferredShadingPC(int(draw_type), 0)
+        pc = S.DeferredShadingPC(int(draw_type), int(ibl))
         _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), flags, frame_index, C.byref(camera), width,
                                                  height, None, C.c_void_p(stream)))
+
+    def generate_ibl(self, stream=None):
+        """ImageBasedLighting::recordGeneration (prosper_pt_generate_ibl): the irradiance and radiance cubes and the BRDF
+        LUT of the current scene's sky, which deferred shading with ibl=1 reads."""
+        self._sync_debug()
+        _check(lib().prosper_pt_generate_ibl(self._h, C.c_void_p(stream)))
+
+    def ibl_info(self):
+        """S.IblInfo: generated (0/1), the maps' sizes and the last generation's per-pass device times."""
+        info = S.IblInfo()
+        _check(lib().prosper_pt_get_ibl_info(self._h, C.byref(info)))
+        return info
+
+    def read_ibl(self, stream=None):
+        """The maps without borders: dict with irradiance float16 [6, 64, 64, 4], radiance a list of float16
+        [6, n, n, 4] for n = 512 ... 1, lut uint16 [512, 512, 2] (UNORM scale, bias; row = roughness, column = NoV)."""
+        n0, mips = S.IBL_RADIANCE_SIZE, S.IBL_RADIANCE_MIPS
+        irr = np.empty((6, S.IBL_IRRADIANCE_SIZE, S.IBL_IRRADIANCE_SIZE, 4), np.float16)
+        rad = np.empty(sum(6 * (n0 >> m) ** 2 * 4 for m in range(mips)), np.float16)
+        lut = np.empty((S.IBL_LUT_SIZE, S.IBL_LUT_SIZE, 2), np.uint16)
+        _check(lib().prosper_pt_read_ibl(self._h, irr.ctypes.data, irr.nbytes, rad.ctypes.data, rad.nbytes,
+                                         lut.ctypes.data, lut.nbytes, C.c_void_p(stream)))
+        levels, at = [], 0
+        for m in range(mips):
+            n = n0 >> m
+            levels.append(rad[at:at + 6 * n * n * 4].reshape(6, n, n, 4))
+            at += 6 * n * n * 4
+        return {"irradiance": irr, "radiance": levels, "lut": lut}
 
     def set_tone_map_lut(self, lut_r9g9b9e5):
         """lut: uint32 [dim, dim, dim] (z, y, x) R9G9B9E5 texels, e.g. from prosper_amd.dds.read_lut."""

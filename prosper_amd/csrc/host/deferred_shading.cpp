@@ -108,9 +108,10 @@ int prosper_host_deferred_shading_record(
         prosper_host_set_error("prosper_host_deferred_shading_record: drawType out of range");
         return PROSPER_PT_ERR_INVALID_ARGUMENT;
     }
-    if (applyIbl)
+    prosper_pt_ibl_info ibl = {};
+    if (applyIbl && (prosper_pt_get_ibl_info(r->pass.context(), &ibl) != PROSPER_PT_OK || !ibl.generated))
     {
-        prosper_host_set_error("prosper_host_deferred_shading_record: IBL needs ImageBasedLighting's maps, which the library does not generate");
+        prosper_host_set_error("prosper_host_deferred_shading_record: IBL needs ImageBasedLighting's maps: run ImageBasedLighting::recordGeneration after the scene upload");
         return PROSPER_PT_ERR_UNSUPPORTED;
     }
     try
@@ -129,8 +130,8 @@ int prosper_host_deferred_shading_record(
         render::LightClustering clustering;
         clustering.init(r->pass.context());
         const render::LightClusteringOutput clusters = clustering.record(cam, width, height, stream);
-        (void)r->pass.record(cam, render::DeferredShading::Input{g, clusters}, false, static_cast<scene::DrawType>(drawType),
-                             stream);
+        (void)r->pass.record(cam, render::DeferredShading::Input{g, clusters}, applyIbl != 0,
+                             static_cast<scene::DrawType>(drawType), stream);
         if (outPushConstants) *outPushConstants = r->pass.lastPushConstants();
     }
     catch (const std::exception &e)

@@ -4,7 +4,8 @@
 // `record` shades the G-buffer over the light clusters into the context's HDR image through prosper_pt_deferred_shading
 // and returns the DeferredShadingPC it pushed.  prosper_pt_deferred_shading clusters the lights itself, with the same
 // camera and extent as LightClustering::record and so the same lists; Input::lightClusters is checked against the
-// G-buffer's extent.  IBL (applyIbl) is refused: the library does not generate ImageBasedLighting's maps.
+// G-buffer's extent.  applyIbl adds evalIBL over ImageBasedLighting's maps, which recordGeneration must have made for
+// the current scene (Renderer.cpp:380-382 runs it before the first frame that applies IBL).
 #pragma once
 
 #include <cstdint>

@@ -849,6 +849,11 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     if (ctx->clusterPointers) (void)hipFree(ctx->clusterPointers);
     if (ctx->clusterIndices) (void)hipFree(ctx->clusterIndices);
     if (ctx->clusterDropped) (void)hipFree(ctx->clusterDropped);
+    if (ctx->iblIrradiance) (void)hipFree(ctx->iblIrradiance);
+    if (ctx->iblRadiance) (void)hipFree(ctx->iblRadiance);
+    if (ctx->iblLut) (void)hipFree(ctx->iblLut);
+    for (hipEvent_t &e : ctx->iblEvents)
+        if (e) (void)hipEventDestroy(e);
     for (void *r : ctx->restirReservoirs)
         if (r) (void)hipFree(r);
     if (ctx->toneLut) (void)hipFree(ctx->toneLut);
@@ -878,6 +883,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     if (!ctx || !scene) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_upload_scene: null argument");
     int rc = validate_scene(scene);
     if (rc != PROSPER_PT_OK) return rc;
+    ctx->iblGenerated = false; // the maps describe the old sky
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());
@@ -2108,9 +2114,9 @@ int prosper_pt_deferred_shading(
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: empty extent");
     if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
     if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: ibl is 0 or 1");
-    if (pc->ibl == 1u)
+    if (pc->ibl == 1u && (!ctx || !ctx->iblGenerated))
         return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT, which the library does not generate");
+                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
     if (!cluster_camera_ok(camera))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: camera needs 0 < near_ < far_ and a resolution");
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
@@ -2137,11 +2143,103 @@ int prosper_pt_deferred_shading(
     if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, c, s);
     if (rc == PROSPER_PT_OK) rc = prepare_whole_hdr(ctx, width, height, s);
     if (rc != PROSPER_PT_OK) return rc;
-    launch_deferred_shading(
-        ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth, ctx->clusterPointers,
-        ctx->clusterIndices, ctx->hdr, s);
+    if (pc->ibl == 1u)
+        launch_deferred_shading_ibl(
+            ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth,
+            ctx->clusterPointers, ctx->clusterIndices, ctx->iblIrradiance, ctx->iblRadiance, ctx->iblLut, ctx->hdr, s);
+    else
+        launch_deferred_shading(
+            ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth,
+            ctx->clusterPointers, ctx->clusterIndices, ctx->hdr, s);
     PPT_HIP(hipGetLastError());
     return mark_versions_read(ctx, s);
+}
+
+// ---- image-based lighting (src/render/ImageBasedLighting.cpp) ----
+
+int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_generate_ibl: null argument");
+    const int crc = restir_check_scene(ctx, "prosper_pt_generate_ibl");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = restir_flush(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    if (!ctx->iblIrradiance) PPT_HIP(hipMalloc((void **)&ctx->iblIrradiance, kIblIrradianceTexels * 8u));
+    if (!ctx->iblRadiance) PPT_HIP(hipMalloc((void **)&ctx->iblRadiance, kIblRadianceTexels * 8u));
+    if (!ctx->iblLut) PPT_HIP(hipMalloc((void **)&ctx->iblLut, (size_t)kIblLutSize * kIblLutSize * 4u));
+    for (hipEvent_t &e : ctx->iblEvents)
+        if (!e) PPT_HIP(hipEventCreate(&e));
+    launch_ibl_generation(ctx->scene, ctx->iblIrradiance, ctx->iblRadiance, ctx->iblLut, ctx->iblEvents, s);
+    PPT_HIP(hipGetLastError());
+    ctx->iblGenerated = true;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_ibl_info(prosper_pt_ctx *ctx, prosper_pt_ibl_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_ibl_info: null argument");
+    prosper_pt_ibl_info info = {};
+    info.generated = ctx->iblGenerated ? 1u : 0u;
+    info.irradianceSize = kIblIrradianceSize;
+    info.radianceSize = kIblRadianceSize;
+    info.radianceMips = kIblRadianceMips;
+    info.lutSize = kIblLutSize;
+    if (ctx->iblEvents[3])
+    {
+        PPT_HIP(hipSetDevice(ctx->device));
+        PPT_HIP(hipEventSynchronize(ctx->iblEvents[3]));
+        PPT_HIP(hipEventElapsedTime(&info.irradianceMs, ctx->iblEvents[0], ctx->iblEvents[1]));
+        PPT_HIP(hipEventElapsedTime(&info.radianceMs, ctx->iblEvents[1], ctx->iblEvents[2]));
+        PPT_HIP(hipEventElapsedTime(&info.lutMs, ctx->iblEvents[2], ctx->iblEvents[3]));
+    }
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+// The interior texels of `levels` bordered cubes (6 faces of (n + 2)^2 RGBA16F each, n halving per level) to host
+static void strip_cube_borders(const std::vector<uint16_t> &bordered, uint32_t n, uint32_t levels, uint16_t *out)
+{
+    size_t src = 0;
+    for (uint32_t m = 0; m < levels; ++m, n >>= 1)
+    {
+        const size_t n2 = n + 2u;
+        for (uint32_t face = 0; face < 6u; ++face)
+            for (uint32_t j = 0; j < n; ++j)
+            {
+                std::memcpy(out, &bordered[4u * (src + ((size_t)face * n2 + j + 1u) * n2 + 1u)], (size_t)n * 8u);
+                out += 4u * (size_t)n;
+            }
+        src += 6u * n2 * n2;
+    }
+}
+
+int prosper_pt_read_ibl(
+    prosper_pt_ctx *ctx, uint16_t *irradiance_rgba16f, size_t irradiance_bytes, uint16_t *radiance_rgba16f,
+    size_t radiance_bytes, uint16_t *lut_rg16, size_t lut_bytes, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (irradiance_rgba16f && irradiance_bytes != 6u * kIblIrradianceSize * kIblIrradianceSize * 8u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: irradiance_bytes is not 6 x 64 x 64 RGBA16F");
+    size_t radianceTexels = 0;
+    for (uint32_t m = 0; m < kIblRadianceMips; ++m) radianceTexels += 6u * (size_t)(kIblRadianceSize >> m) * (kIblRadianceSize >> m);
+    if (radiance_rgba16f && radiance_bytes != radianceTexels * 8u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: radiance_bytes is not the 10 mips of 6 x 512 x 512 RGBA16F");
+    if (lut_rg16 && lut_bytes != (size_t)kIblLutSize * kIblLutSize * 4u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: lut_bytes is not 512 x 512 R16G16");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: null argument");
+    if (!ctx->iblGenerated) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_ibl: no maps were generated for the current scene (prosper_pt_generate_ibl)");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<uint16_t> irr(irradiance_rgba16f ? 4u * kIblIrradianceTexels : 0u);
+    std::vector<uint16_t> rad(radiance_rgba16f ? 4u * kIblRadianceTexels : 0u);
+    if (irradiance_rgba16f) PPT_HIP(hipMemcpyAsync(irr.data(), ctx->iblIrradiance, irr.size() * 2u, hipMemcpyDeviceToHost, s));
+    if (radiance_rgba16f) PPT_HIP(hipMemcpyAsync(rad.data(), ctx->iblRadiance, rad.size() * 2u, hipMemcpyDeviceToHost, s));
+    if (lut_rg16) PPT_HIP(hipMemcpyAsync(lut_rg16, ctx->iblLut, lut_bytes, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    if (irradiance_rgba16f) strip_cube_borders(irr, kIblIrradianceSize, 1u, irradiance_rgba16f);
+    if (radiance_rgba16f) strip_cube_borders(rad, kIblRadianceSize, kIblRadianceMips, radiance_rgba16f);
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes)

@@ -334,6 +334,11 @@ struct prosper_pt_ctx
     uint32_t *clusterDropped = nullptr;  // entries dropped, per cluster
     size_t clusterCapacity = 0;          // clusters the buffers hold
     uint32_t clusterDims[3] = {};        // of the last clustering
+    uint16_t *iblIrradiance = nullptr; // prosper_pt_generate_ibl: kIblIrradianceTexels RGBA16F, bordered cube
+    uint16_t *iblRadiance = nullptr;   // kIblRadianceTexels RGBA16F, 10 bordered mips
+    uint32_t *iblLut = nullptr;        // kIblLutSize^2 R16G16 UNORM
+    hipEvent_t iblEvents[4] = {};      // around the three passes of the last generation
+    bool iblGenerated = false;         // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
     uint32_t *toneLut = nullptr; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     void *toneScratch = nullptr; // RGBA8 output when the caller only wants a host copy

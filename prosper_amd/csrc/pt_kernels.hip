@@ -8,12 +8,14 @@
 //   restir_di_*         ReSTIR-DI initial reservoirs, spatial reuse and trace over a G-buffer
 //   gbuffer_trace       the ray-traced G-buffer those passes read
 //   light_clustering    per-cluster point / spot light lists (LightClustering)
-//   deferred_shading    unshadowed shading of the G-buffer over those lists (DeferredShading)
+//   deferred_shading    unshadowed shading of the G-buffer over those lists (DeferredShading), with evalIBL over the
+//                       maps of pt_ibl.hip in its _ibl variant
 #include "pt_kernels.hpp"
 
 #include "bvh_encode.hpp"
 #include "pt_bc7.hpp"
 #include "pt_device.hpp"
+#include "pt_ibl.hpp"
 #include "pt_render_common.hpp"
 
 namespace ppt
@@ -1003,10 +1005,32 @@ struct DeferredParams
     uint32_t clustersX, clustersY;
 };
 
-__global__ __launch_bounds__(256) void deferred_shading_kernel(
-    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
+// evalIBL (scene/skybox.glsl:48-83), as written: the split-sum specular over the prefiltered radiance and the BRDF LUT
+// plus the diffuse irradiance, without AO.
+PPT_D f3 eval_ibl(const IblMaps &m, const Surface &sf)
+{
+    const f3 f0 = fresnel_zero(sf);
+    const float NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
+    // schlickFresnelWithRoughness (brdf.glsl:28-31)
+    const float p = pow5(1.0f - NoV);
+    const float r1 = 1.0f - sf.material.roughness;
+    const f3 F = f3{__builtin_fmaf(fmax_(r1, f0.x) - f0.x, p, f0.x), __builtin_fmaf(fmax_(r1, f0.y) - f0.y, p, f0.y),
+                    __builtin_fmaf(fmax_(r1, f0.z) - f0.z, p, f0.z)};
+    const f3 kD = (f3{1.0f, 1.0f, 1.0f} - F) * (1.0f - sf.material.metallic);
+    const f3 diffuse = sample_cube_bordered(m.irradiance, kIblIrradianceSize, sf.normalWS) * sf.material.albedo;
+    const f3 R = reflect(-sf.invViewRayWS, sf.normalWS);
+    const f3 prefiltered = sample_radiance_trilinear(m.radiance, R, sf.material.roughness);
+    const f2 envBrdf = sample_brdf_lut(m.lut, NoV, sf.material.roughness);
+    const f3 specular = prefiltered * (F * envBrdf.x + f3{envBrdf.y, envBrdf.y, envBrdf.y});
+    return kD * diffuse + specular;
+}
+
+// The body of both shading kernels; IBL adds evalIBL after the spot lights (deferred_shading.comp:59-60).
+template <bool IBL>
+PPT_D void deferred_shade(
+    const DeviceScene &s, const DeferredParams &d, const float4 *__restrict__ albedoRoughness,
     const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
-    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr)
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, const IblMaps *ibl)
 {
     uint32_t px, py;
     if (!restir_pixel(d.r, px, py) || px >= d.r.width || py >= d.r.height) return;
@@ -1058,7 +1082,24 @@ __global__ __launch_bounds__(256) void deferred_shading_kernel(
         spots = spots + irradiance * eval_brdf_times_nol(l, sf);
     }
     color = color + spots;
+    if constexpr (IBL) color = color + eval_ibl(*ibl, sf);
     hdr[i] = make_float4(color.x, color.y, color.z, 1.0f);
+}
+
+__global__ __launch_bounds__(256) void deferred_shading_kernel(
+    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
+    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr)
+{
+    deferred_shade<false>(s, d, albedoRoughness, normalMetallic, nonLinearDepth, pointers, indices, hdr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void deferred_shading_ibl_kernel(
+    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
+    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, IblMaps ibl)
+{
+    deferred_shade<true>(s, d, albedoRoughness, normalMetallic, nonLinearDepth, pointers, indices, hdr, &ibl);
 }
 
 void launch_deferred_shading(
@@ -1077,6 +1118,26 @@ void launch_deferred_shading(
         deferred_shading_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
         static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
         static_cast<const uint2 *>(pointers), indices, hdr);
+}
+
+void launch_deferred_shading_ibl(
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
+    const uint32_t *lut, float4 *hdr, hipStream_t stream)
+{
+    if (width == 0 || height == 0) return;
+    DeferredParams d;
+    d.r = restir_params(drawType, 0, 0, width, height, cam);
+    d.near_ = c.near_;
+    d.far_ = c.far_;
+    d.clustersX = c.dimX;
+    d.clustersY = c.dimY;
+    const IblMaps maps = {irradiance, radiance, lut};
+    hipLaunchKernelGGL(
+        deferred_shading_ibl_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
+        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
+        static_cast<const uint2 *>(pointers), indices, hdr, maps);
 }
 
 // ------------------------------------------------------------------------------------------

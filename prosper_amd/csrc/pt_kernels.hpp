@@ -114,6 +114,33 @@ void launch_deferred_shading(
     const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
     const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
     const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream);
+// Image-based lighting (ImageBasedLighting / evalIBL).  Every cube is stored with a one-texel seamless border, as the
+// sky is: 6 faces of (n + 2)^2 RGBA16F texels.  Radiance mip m (size kIblRadianceSize >> m) starts
+// ibl_radiance_offset(m) RGBA texels into its buffer; the LUT is kIblLutSize^2 R16G16 UNORM, row = roughness.
+constexpr uint32_t kIblIrradianceSize = 64; // SkyboxResources::sSkyboxIrradianceResolution
+constexpr uint32_t kIblRadianceSize = 512;  // sSkyboxRadianceResolution
+constexpr uint32_t kIblRadianceMips = 10;   // getMipCount(512)
+constexpr uint32_t kIblLutSize = 512;       // sSpecularBrdfLutResolution
+constexpr uint32_t kIblSamples = 1024;      // NumSamples of prefilter_radiance.comp and integrate_specular_brdf.comp
+__host__ __device__ constexpr size_t ibl_radiance_offset(uint32_t mip)
+{
+    size_t offset = 0;
+    for (uint32_t m = 0; m < mip; ++m)
+        offset += 6u * (size_t)((kIblRadianceSize >> m) + 2u) * ((kIblRadianceSize >> m) + 2u);
+    return offset;
+}
+constexpr size_t kIblIrradianceTexels = 6u * (size_t)(kIblIrradianceSize + 2u) * (kIblIrradianceSize + 2u);
+constexpr size_t kIblRadianceTexels = ibl_radiance_offset(kIblRadianceMips);
+// The three generation passes on `stream` from the scene's sky (a scene without one gives zero maps).  `events`
+// (optional, 4): recorded before the irradiance pass, the radiance pass, the LUT pass and after it.
+void launch_ibl_generation(
+    const DeviceScene &s, uint16_t *irradiance, uint16_t *radiance, uint32_t *lut, hipEvent_t *events, hipStream_t stream);
+// deferred shading with evalIBL after the spot lights (ibl = 1), over the maps launch_ibl_generation wrote
+void launch_deferred_shading_ibl(
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
+    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
+    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
+    const uint32_t *lut, float4 *hdr, hipStream_t stream);
 void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);

@@ -308,6 +308,42 @@ class DeferredShading:
             pass
 
 
+class ImageBasedLighting:
+    """render::ImageBasedLighting (csrc/host/image_based_lighting.hpp) on a Context the scene was uploaded to:
+    record_generation makes the irradiance and radiance cubes and the BRDF LUT that DeferredShading reads with
+    apply_ibl=True; is_generated is False again after a scene upload."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_image_based_lighting_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def is_generated(self):
+        rc = lib().prosper_host_image_based_lighting_is_generated(self._h)
+        if rc < 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return rc == 1
+
+    def record_generation(self, stream=None):
+        rc = lib().prosper_host_image_based_lighting_record_generation(self._h, C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_image_based_lighting_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class TiledRtReference:
     """render::TiledRtReference (csrc/host/tiled_rt_reference.hpp): one rank of a multi-GPU job.  record() renders the
     rank's stripes and enqueues the RCCL gather + de-interleave to the root; read_gathered() there returns the image."""

@@ -359,3 +359,17 @@ CLUSTER_DIM = 32
 CLUSTER_Z_SLICES = 16
 CLUSTER_MAX_POINTS = 128
 CLUSTER_MAX_SPOTS = 128
+
+
+class IblInfo(C.Structure):
+    """prosper_pt_ibl_info: whether the maps exist for the current scene, their sizes, the last generation's pass times"""
+    _fields_ = [("generated", C.c_uint32), ("irradianceSize", C.c_uint32), ("radianceSize", C.c_uint32),
+                ("radianceMips", C.c_uint32), ("lutSize", C.c_uint32), ("irradianceMs", C.c_float),
+                ("radianceMs", C.c_float), ("lutMs", C.c_float)]
+
+
+# ImageBasedLighting: the irradiance cube, the prefiltered radiance cube (mips 512 ... 1) and the BRDF LUT
+IBL_IRRADIANCE_SIZE = 64
+IBL_RADIANCE_SIZE = 512
+IBL_RADIANCE_MIPS = 10
+IBL_LUT_SIZE = 512

@@ -12,6 +12,8 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred                   prosper's default lighting instead: the pixel-centre ray-traced G-buffer, light
                                  clustering and deferred shading (prosper_pt_deferred_shading with
                                  PROSPER_PT_DEFERRED_TRACE_GBUFFER), unshadowed, one frame
+    --deferred --ibl             with the image-based lighting term: the irradiance / radiance maps and the BRDF LUT
+                                 are generated once from the sky (prosper_pt_generate_ibl), then the frame is shaded
 """
 import argparse
 import math
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--restir-di", action="store_true", help="ReSTIR-DI direct illumination from a traced G-buffer")
     ap.add_argument("--no-spatial", action="store_true", help="with --restir-di: no spatial reuse")
     ap.add_argument("--deferred", action="store_true", help="clustered deferred shading of a traced G-buffer")
+    ap.add_argument("--ibl", action="store_true", help="with --deferred: add image-based lighting from the sky")
     args = ap.parse_args()
     from prosper_amd import capi, dds, gltf, ktx, structs as S
     from prosper_amd.rt_reference import Camera
@@ -72,8 +75,10 @@ def main():
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_SKIP_HISTORY | (S.PC_FLAG_IBL if args.env else 0)
     if args.deferred:
         import time
+        if args.ibl:
+            ctx.generate_ibl()  # once per sky, before the first frame that applies IBL (Renderer.cpp:380-382)
         t0 = time.perf_counter()
-        ctx.deferred_shading_traced(cam, w, h)
+        ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
         ctx.read_hdr()  # (synchronises)
         ms = (time.perf_counter() - t0) * 1e3
         args.spp = 1
