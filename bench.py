@@ -10,11 +10,16 @@ max-over-ranks of the wall time).  Steps are enqueued back to back with up to th
 (PROSPER_PT_RENDER_PIPELINED, prosper's frames-in-flight idea; --in-order for A/B): every step's kernels, its
 accumulate and its gather complete inside the timed region, which is bracketed by barrier + synchronize.
 
-The LAST stdout line is ONE JSON object of under 4 KB (tests/test_bench_contract.py): the contract fields, a numbers-only
-`roofline`, `cpu_baseline`, and per sub-configuration (`configs`: C1, C3, C4, FlightHelmet, the C5 rank share) ms/step,
-Mpaths/s, the dominant kernel's fractions and the CPU tracer's rate.  Everything else - per-kernel tables, counters, notes,
-the full roofline objects - goes to bench_detail.json (next to this file, and under gpurun_out/).  What the detail file
-carries besides the contract fields:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if given and
+prints the line.  Everything else it can measure runs with --full (about 70 s on C2): the live PMC passes, the work
+counters, per-kernel and roofline figures, the CPU baseline, the single-sample / rank-share / tone-map / ReSTIR-DI legs and
+the sub-configurations.
+
+The LAST stdout line is ONE JSON object of under 4 KB (tests/test_bench_contract.py): the contract fields and, with --full,
+a numbers-only `roofline`, `cpu_baseline`, and per sub-configuration (`configs`: C1, C3, C4, FlightHelmet, the C5 rank
+share) ms/step, Mpaths/s, the dominant kernel's fractions and the CPU tracer's rate.  Everything else - per-kernel tables,
+counters, notes, the full roofline objects - goes to bench_detail.json (with --full, or wherever --detail names; see
+write_detail).  What the detail file of a --full run carries besides the contract fields:
   roofline   the roof that binds the dominant kernel: VALU issue.  achieved = wave-instructions/s of that kernel
              (SQ_INSTS_VALU per launch, measured IN THIS RUN by rocprofv3 child passes over the same launch shape, /
              the kernel's exclusive share of the step time); peak = the guide's 1024 SIMDs x 2.4 GHz / 2 cycles, the
@@ -29,6 +34,7 @@ carries besides the contract fields:
   cpu_baseline  the oracle (a scalar port) on this box's host cores, bounded sample
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: starts the N ranks itself as a child torch.distributed.run)
@@ -241,14 +247,16 @@ SLIM_LIMIT = 4096
 DUMP_LIMIT = 64 << 20
 
 
-def slim_line(result, detail_path=None):
-    """The ONE stdout line (under SLIM_LIMIT bytes): contract fields + numbers; the rest lives in bench_detail.json."""
+def slim_line(result, detail_path=DETAIL_NAME):
+    """The ONE stdout line (under SLIM_LIMIT bytes): contract fields + numbers; the rest lives in the detail file
+    `detail_path` (None: no detail file was written, the line names none)."""
     line = {k: result.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "frames_per_s",
                                        "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     cfg = result["config"]
     line["config"] = {k: cfg.get(k) for k in ("workload", "width", "height", "spp", "max_bounces", "triangles", "bvh_nodes",
                                               "parallelism", "pipeline")}
-    line["roofline"] = slim_roofline(result.get("roofline"))
+    if "roofline" in result:
+        line["roofline"] = slim_roofline(result["roofline"])
     if "cpu_baseline" in result:
         cb = result["cpu_baseline"]
         sample = ("%d of %d spp of the same frame, %.1f s" % (cb["sample_frames"], cfg["spp"], cb["sample_seconds"])
@@ -265,7 +273,8 @@ def slim_line(result, detail_path=None):
             line[k] = {"ms": result[k]["ms_per_step"], "bound_on_scaling_efficiency": result[k].get("bound_on_scaling_efficiency")}
     if result.get("configs"):
         line["configs"] = {name: slim_config(c) for name, c in result["configs"].items()}
-    line["detail"] = detail_path or DETAIL_NAME
+    if detail_path:
+        line["detail"] = detail_path
     line = rounded(line)
     text = json.dumps(line, separators=(",", ":"))
     if len(text) >= SLIM_LIMIT:  # never again a line the driver cannot parse: drop the optional parts, largest first
@@ -682,14 +691,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 child passes (roofline then quotes the "
-                    "committed profile if it matches the kernel sources, else null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: live PMC passes, work counters, per-kernel and roofline "
+                    "figures, CPU baseline, the single-sample / rank-share / tone-map / ReSTIR-DI legs, the sub-configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU tracer")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 child passes (roofline then quotes "
+                    "the committed profile if it matches the kernel sources, else null)")
     ap.add_argument("--pmc-budget", type=float, default=240.0, help="seconds all rocprofv3 child passes together may take")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU tracing for the headline's cpu_baseline")
-    ap.add_argument("--detail", default=None, help="where the full result goes (default: bench_detail.json here and under gpurun_out/)")
-    ap.add_argument("--no-subconfigs", action="store_true", help="skip the C3 / C4 / FlightHelmet sub-objects")
-    ap.add_argument("--no-extras", action="store_true", help="skip the tone-map and ReSTIR-DI legs")
+    ap.add_argument("--detail", default=None, help="where the full result goes (default with --full: bench_detail.json, see "
+                    "write_detail; a plain run writes one only when this is given)")
+    ap.add_argument("--no-subconfigs", action="store_true", help="with --full: skip the C3 / C4 / FlightHelmet sub-objects")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the tone-map and ReSTIR-DI legs")
     ap.add_argument("--subconfigs", default="c1,c3,c4,helmet,helmet2k")
     ap.add_argument("--megakernel", action="store_true", help="use the one-lane-per-pixel kernel (A/B)")
     ap.add_argument("--persistent", action="store_true", help="use the persistent path-regeneration kernel (A/B)")
@@ -717,12 +730,12 @@ def main():
         raise SystemExit("WORLD_SIZE %d != --gpus %d" % (world_size, args.gpus))
     wavefront = not (args.megakernel or args.persistent)
 
-    # ---- PMC passes of the headline configuration, as child processes, BEFORE this process touches the GPU ----
-    sub_names = [c for c in args.subconfigs.split(",") if c] if (args.config == "c2" and not args.no_subconfigs) else []
+    # ---- --full: PMC passes of the headline configuration, as child processes, BEFORE this process touches the GPU ----
+    sub_names = [c for c in args.subconfigs.split(",") if c] if (args.full and args.config == "c2" and not args.no_subconfigs) else []
     pmc_by_config = {}
     pmc_gave_up = False
     pmc_deadline = time.perf_counter() + args.pmc_budget  # all profiler passes together: bounded, whatever a pass does
-    if world_size == 1 and wavefront:
+    if args.full and world_size == 1 and wavefront:
         for name in [args.config] + sub_names:
             if name not in ("c2", "c3", "c4", "c5", "helmet"):  # (helmet2k: timed, not profiled - the kernels are helmet's)
                 continue
@@ -865,14 +878,15 @@ def main():
         if world_size > 1 and not rehearse and fallback_group is None:
             ctx.gather_wait(stream)
 
-    # deterministic work counters of one launch (outside the timed region)
-    ctx.reset_counters(stream)
-    pc = make_pc(focal, 1, max_bounces, ibl, True)
-    ctx.render(pc, cam, width, height, tile=tile, frames=spp, flags=S.RENDER_COUNT_WORK, stream=stream)
-    counters = ctx.counters(stream).as_dict()
-    bytes_per_step = algorithmic_bytes(counters, stats)
-    stage_counters = [ctx.stage_counters(i, stream).as_dict() for i in range(4)]
-    stage_bytes = [algorithmic_bytes(c, stats) for c in stage_counters]
+    if args.full:
+        # deterministic work counters of one launch (outside the timed region): the roofline's byte model
+        ctx.reset_counters(stream)
+        pc = make_pc(focal, 1, max_bounces, ibl, True)
+        ctx.render(pc, cam, width, height, tile=tile, frames=spp, flags=S.RENDER_COUNT_WORK, stream=stream)
+        counters = ctx.counters(stream).as_dict()
+        bytes_per_step = algorithmic_bytes(counters, stats)
+        stage_counters = [ctx.stage_counters(i, stream).as_dict() for i in range(4)]
+        stage_bytes = [algorithmic_bytes(c, stats) for c in stage_counters]
     ctx.set_kernel_timing(True)
 
     # Device wake-up: the clocks of an idle MI355X take ~40 ms of load to ramp (the first ten 2.5 ms steps after idle
@@ -905,7 +919,7 @@ def main():
     elapsed = time.perf_counter() - t0
     if os.environ.get("PROSPER_BENCH_STEP_TIMES") and rank == 0:
         print("step ms: " + " ".join("%.3f" % (starts[i].elapsed_time(starts[i + 1])) for i in range(args.steps - 1)), file=sys.stderr)
-    _, per_kernel = ctx.last_render_timing()
+    per_kernel = ctx.last_render_timing()[1] if args.full else None
     ctx.set_kernel_timing(False)
 
     t = torch.tensor([elapsed], dtype=torch.float64)
@@ -929,19 +943,6 @@ def main():
             dump_outputs(args.dump_outputs, image)
         paths_per_step = width * height * spp
         ms_per_step = elapsed * 1e3 / args.steps
-        alone = None
-        if world_size == 1 and wavefront and render_flags:
-            alone_ctx = capi.Context(device=local_rank, flags=S.CREATE_SINGLE_CHAIN)
-            alone = time_alone(alone_ctx, world, cam, make_pc(focal, 1, max_bounces, ibl, True), width, height, spp, stream, torch)
-        kernels, scale = kernel_table(per_kernel, stage_bytes, ms_per_step, pmc if world_size == 1 else None, alone,
-                                      stage_counters if world_size == 1 else None)
-        if alone:
-            timed_note = ("each launch ALONE on the GPU (one chain, in order, hipEvents, mean of 3 renders) x %.3f = ms_per_step / "
-                          "sum of the alone durations of a step's launches: with three frames in flight the launches overlap, the "
-                          "exclusive shares add up to the step" % scale)
-        else:
-            timed_note = ("hipEvents around every launch of timed step %d of %d, scaled by %.3f = ms_per_step / sum of the raw "
-                          "durations: the exclusive shares add up to the step" % (timed_step + 1, args.steps, scale))
         result = {
             "metric": "Mpaths/s",
             "value": paths_per_step * args.steps / elapsed / 1e6,
@@ -971,16 +972,30 @@ def main():
                         else "wavefront, 2 concurrent launch chains"))),
                 "preheat_steps": preheat_steps,
             },
-            "roofline": roofline_object(kernels, pmc_source, ms_per_step, timed_note, bytes_per_step),
-            "kernels": kernels,
             "scene": {"upload_ms": stats.uploadSeconds * 1e3, "bvh_build_ms": stats.bvhBuildSeconds * 1e3,
                       "texture_upload_ms": stats.textureSeconds * 1e3, "upload_wall_ms": upload_wall * 1e3,
                       "device_MB": stats.deviceBytes / 1e6, "variant_flags": int(stats.variantFlags)},
-            "whole_pass": {"algorithmic_bytes_per_step": bytes_per_step, "bytes_per_path": bytes_per_step / max(1, counters["paths"])},
-            "counters": counters,
             "mean_radiance": float(image[..., :3].mean().item()),
         }
-        if world_size == 1 and wavefront:
+        if args.full:
+            alone = None
+            if world_size == 1 and wavefront and render_flags:
+                alone_ctx = capi.Context(device=local_rank, flags=S.CREATE_SINGLE_CHAIN)
+                alone = time_alone(alone_ctx, world, cam, make_pc(focal, 1, max_bounces, ibl, True), width, height, spp, stream, torch)
+            kernels, scale = kernel_table(per_kernel, stage_bytes, ms_per_step, pmc if world_size == 1 else None, alone,
+                                          stage_counters if world_size == 1 else None)
+            if alone:
+                timed_note = ("each launch ALONE on the GPU (one chain, in order, hipEvents, mean of 3 renders) x %.3f = ms_per_step / "
+                              "sum of the alone durations of a step's launches: with three frames in flight the launches overlap, the "
+                              "exclusive shares add up to the step" % scale)
+            else:
+                timed_note = ("hipEvents around every launch of timed step %d of %d, scaled by %.3f = ms_per_step / sum of the raw "
+                              "durations: the exclusive shares add up to the step" % (timed_step + 1, args.steps, scale))
+            result["roofline"] = roofline_object(kernels, pmc_source, ms_per_step, timed_note, bytes_per_step)
+            result["kernels"] = kernels
+            result["whole_pass"] = {"algorithmic_bytes_per_step": bytes_per_step, "bytes_per_path": bytes_per_step / max(1, counters["paths"])}
+            result["counters"] = counters
+        if args.full and world_size == 1 and wavefront:
             if not args.no_extras:
                 result["single_sample_frames"] = time_single_sample_frames(ctx, torch, cam, focal, width, height, max_bounces, ibl, stream)
                 result["rank_share"] = time_rank_share(ctx, torch, cam, focal, width, height, spp, max_bounces, ibl, stream, 8, 3, 30, ms_per_step)
@@ -1023,8 +1038,11 @@ def main():
             result["ranks_seen"] = ranks_seen
             result["ranks_seen_by"] = ranks_seen_by
             result["gather_ms"] = gather_ms
-        write_detail(result, args.detail)
-        print(slim_line(result, args.detail))
+        detail = None
+        if args.full or args.detail:
+            write_detail(result, args.detail)
+            detail = args.detail or DETAIL_NAME
+        print(slim_line(result, detail))
 
     ctx.set_output_buffer(0, 0)
     ctx.close()

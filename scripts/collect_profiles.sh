@@ -4,7 +4,7 @@
 #   r04_<config>_kernel_stats.csv         rocprofv3 --kernel-trace --stats of scripts/quick_bench.py --single-chain (one chain, in
 #                                         order: launches never overlap, so calls x average adds up to the steps' time)
 #   r04_<config>_quick_bench.txt          the same command's own per-launch hipEvent times and step time
-#   r04_bench.json / .err                 the default bench.py line (under 4 KB), r04_bench_detail.json the full result beside it
+#   r04_bench.json / .err                 the bench.py --full line (under 4 KB), r04_bench_detail.json the full result beside it
 # usage: bash scripts/collect_profiles.sh [configs...]   (default: c2 c3 c4 helmet)
 set -u
 cd "$(dirname "$0")/.."
@@ -24,5 +24,5 @@ for c in $CONFIGS; do
   tail -2 "$OUT/r04_${c}_quick_bench.txt"
 done
 echo "== bench.py"
-python3 bench.py --steps 20 --warmup 5 --detail "$OUT/r04_bench_detail.json" > "$OUT/r04_bench.json" 2> "$OUT/r04_bench.err"
+python3 bench.py --full --steps 20 --warmup 5 --detail "$OUT/r04_bench_detail.json" > "$OUT/r04_bench.json" 2> "$OUT/r04_bench.err"
 echo "bench rc=$?"

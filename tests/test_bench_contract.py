@@ -63,9 +63,43 @@ def test_steps_below_one_are_refused():
     assert out.returncode != 0 and "--steps" in out.stderr
 
 
+def test_slim_line_of_a_plain_result_names_no_missing_parts():
+    """A plain run (no --full) measures no roofline and writes no detail file unless --detail asks: its line says neither."""
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r03_bench.json")))
+    plain = {k: v for k, v in full.items() if k not in ("roofline", "kernels", "counters", "whole_pass", "cpu_baseline",
+                                                       "gpu_over_cpu", "configs", "single_sample_frames", "rank_share")}
+    d = json.loads(bench.slim_line(plain, None))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["metric"] == plain["metric"] and d["value"] == pytest.approx(plain["value"], rel=1e-4)
+    assert not {"roofline", "cpu_baseline", "configs", "detail"} & set(d)
+    assert json.loads(bench.slim_line(plain, "x.json"))["detail"] == "x.json"
+
+
+@pytest.mark.gpu
+def test_plain_run_does_only_the_headline(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the contract fields, the image of the timed path, nothing else."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mpaths/s" and d["unit"] == "Mpaths/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    paths = d["config"]["width"] * d["config"]["height"] * d["config"]["spp"]
+    assert abs(d["value"] - paths / d["ms_per_step"] / 1e3) <= 1e-4 * d["value"]
+    assert not {"roofline", "cpu_baseline", "configs", "single_sample_frames", "rank_share", "detail"} & set(d)
+    import numpy as np
+    hdr = np.load(tmp_path / "out" / "hdr.npy")
+    assert hdr.shape == (256, 256, 4) and float(hdr[..., :3].mean()) == pytest.approx(d["mean_radiance"], rel=1e-4)
+
+
 @pytest.mark.gpu
 def test_bench_json_line_has_the_contract_fields(tmp_path):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2", "--full",
                           "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "out")],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
