@@ -9,16 +9,7 @@
 
 #include "../../../include/prosper_pt/prosper_host.h"
 #include "rt_reference.hpp"
-
-#define PROSPER_ASSERT(cond)                                                                                           \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (!(cond))                                                                                                   \
-        {                                                                                                              \
-            std::fprintf(stderr, "%s:%d: assertion failed: %s\n", __FILE__, __LINE__, #cond);                          \
-            std::abort();                                                                                              \
-        }                                                                                                              \
-    } while (0)
+#include "host_common.hpp"
 
 namespace render
 {
@@ -52,8 +43,6 @@ struct prosper_host_light_clustering
 {
     render::LightClustering pass;
 };
-
-extern "C" void prosper_host_set_error(const char *message); // rt_reference.cpp
 
 extern "C" {
 

@@ -8,16 +8,7 @@
 #include <string>
 
 #include "../../../include/prosper_pt/prosper_host.h"
-
-#define PROSPER_ASSERT(cond)                                                                                           \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (!(cond))                                                                                                   \
-        {                                                                                                              \
-            std::fprintf(stderr, "%s:%d: assertion failed: %s\n", __FILE__, __LINE__, #cond);                          \
-            std::abort();                                                                                              \
-        }                                                                                                              \
-    } while (0)
+#include "host_common.hpp"
 
 namespace render::rtdi
 {
@@ -113,8 +104,6 @@ struct prosper_host_rt_direct_illumination
 {
     render::rtdi::RtDirectIllumination pass;
 };
-
-extern "C" void prosper_host_set_error(const char *message); // rt_reference.cpp
 
 extern "C" {
 

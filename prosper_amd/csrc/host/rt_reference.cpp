@@ -7,17 +7,7 @@
 #include <string>
 
 #include "../../../include/prosper_pt/prosper_host.h"
-
-// prosper keeps its asserts in every build type (readme.md:88-92): programmer errors abort.
-#define PROSPER_ASSERT(cond)                                                                                           \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (!(cond))                                                                                                   \
-        {                                                                                                              \
-            std::fprintf(stderr, "%s:%d: assertion failed: %s\n", __FILE__, __LINE__, #cond);                          \
-            std::abort();                                                                                              \
-        }                                                                                                              \
-    } while (0)
+#include "host_common.hpp"
 
 namespace scene
 {

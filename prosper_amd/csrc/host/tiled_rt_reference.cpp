@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../../include/prosper_pt/prosper_host.h"
+#include "host_common.hpp"
 
 namespace render
 {
@@ -67,8 +68,6 @@ struct prosper_host_tiled_rt_reference
 };
 
 extern "C" {
-
-void prosper_host_set_error(const char *message); // rt_reference.cpp
 
 int prosper_host_tiled_rt_reference_create(
     int32_t deviceOrdinal, uint32_t rank, uint32_t ranks, const uint8_t commId[PROSPER_PT_COMM_ID_BYTES], uint32_t root,

@@ -78,13 +78,12 @@ ToneMap::Output ToneMap::record(void *stream, void *deviceRgba8, size_t byteSize
 
 // ---- plain-C shims (include/prosper_pt/prosper_host.h) ----
 #include "../../../include/prosper_pt/prosper_host.h"
+#include "host_common.hpp"
 
 struct prosper_host_tone_map
 {
     render::ToneMap pass;
 };
-
-extern "C" void prosper_host_set_error(const char *message); // rt_reference.cpp
 
 extern "C" int prosper_host_tone_map_create(prosper_pt_ctx *ctx, const char *lutDdsPath, prosper_host_tone_map **out)
 {

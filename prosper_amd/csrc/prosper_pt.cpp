@@ -26,6 +26,7 @@
 #include "pt_geometry.hpp"
 #include "pt_kernels.hpp"
 #include "pt_materials.hpp"
+#include "pt_pass_support.hpp"
 #include "pt_scene.hpp"
 #include "pt_tiling.hpp"
 
@@ -81,6 +82,30 @@ int upload(prosper_pt_ctx *ctx, const void *src, size_t bytes, void **out)
     const int rc = device_alloc(ctx, bytes, out);
     if (rc != PROSPER_PT_OK) return rc;
     if (bytes) PPT_HIP(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    return PROSPER_PT_OK;
+}
+
+int grow_buffer(DeviceBuffer &buf, GrowWait wait, hipStream_t s, size_t bytes, size_t allocBytes, int fill)
+{
+    hipError_t e = hipSuccess;
+    if (wait == GrowWait::Stream) e = hipStreamSynchronize(s);
+    if (wait == GrowWait::Device) e = hipDeviceSynchronize();
+    if (buf.ptr)
+    {
+        const hipError_t f = hipFree(buf.ptr);
+        if (e == hipSuccess) e = f;
+    }
+    buf.ptr = nullptr;
+    buf.bytes = 0;
+    if (e == hipSuccess) e = hipMalloc(&buf.ptr, allocBytes);
+    if (e == hipSuccess && fill >= 0) e = hipMemset(buf.ptr, fill, allocBytes);
+    if (e != hipSuccess)
+    {
+        if (buf.ptr) (void)hipFree(buf.ptr);
+        buf.ptr = nullptr;
+        return fail(PROSPER_PT_ERR_HIP, std::string("growing a device buffer: ") + hipGetErrorString(e));
+    }
+    buf.bytes = bytes;
     return PROSPER_PT_OK;
 }
 
@@ -440,7 +465,11 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     return PROSPER_PT_OK;
 }
 
-// A slot's workspace may be reused once the kernels of its previous user are done: `free` is recorded behind them.
+} // namespace
+
+namespace ppt
+{
+
 void wait_for_slot(RenderSlot &slot, hipStream_t stream)
 {
     if (slot.freeRecorded) (void)hipStreamWaitEvent(stream, slot.free, 0);
@@ -450,6 +479,27 @@ void release_slot(RenderSlot &slot, hipStream_t stream)
     (void)hipEventRecord(slot.free, stream);
     slot.freeRecorded = true;
 }
+
+int ensure_stack_overflow(prosper_pt_ctx *ctx, RenderSlot &slot, uint32_t ldsEntries, uint32_t gridBlocks, int32_t **out)
+{
+    const uint32_t bound = ctx->stats.maxDepth;
+    *out = nullptr;
+    if (bound <= ldsEntries) return PROSPER_PT_OK;
+    const size_t bytes = (size_t)(bound - ldsEntries) * 256u * gridBlocks * sizeof(int32_t);
+    if (bytes > slot.stackOverflow.bytes)
+    {
+        // the other slots' renders may be in flight on their own streams
+        const int rc = grow_buffer(slot.stackOverflow, GrowWait::Device, nullptr, bytes, bytes);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    *out = slot.stackOverflow.as<int32_t>();
+    return PROSPER_PT_OK;
+}
+
+} // namespace ppt
+
+namespace
+{
 
 // Sizes and carves the wavefront workspace for `frames` x (tilesX*tilesY*64) path slots.
 int ensure_wavefront_workspace(
@@ -524,41 +574,43 @@ int ensure_wavefront_workspace(
         if (bandSegments == 0) return fail(PROSPER_PT_ERR_UNSUPPORTED, "banded batches: no segment layout covers the image");
     }
     const uint64_t padded = nSeg * segLen;
+    // The arrays, each rounded up to 256 B: laid out from 0 to size the block, then over the block.
     // per slot: 2 x (3 x 16 + 8) B ping-pong state, camera slot 4, hit 16 + idx 4, shadow 48, colour 16; + 3 counters per segment
-    const size_t bytes = (size_t)padded * (2u * (3u * 16u + 8u) + 4u + 16u + 4u + 48u + 16u) + (size_t)nSeg * 12u + 4096u;
-    if (bytes > slot.wfBytes)
-    {
-        PPT_HIP(hipDeviceSynchronize()); // the other slot's render may be in flight on its own streams
-        if (slot.wfBlock) PPT_HIP(hipFree(slot.wfBlock));
-        slot.wfBlock = nullptr;
-        slot.wfBytes = 0;
-        PPT_HIP(hipMalloc(&slot.wfBlock, bytes));
-        slot.wfBytes = bytes;
-    }
-    uint8_t *cursor = static_cast<uint8_t *>(slot.wfBlock);
-    auto carve = [&](size_t n) {
-        void *r = cursor;
-        cursor += (n + 255u) & ~(size_t)255u;
-        return r;
-    };
     WavefrontBuffers w = {};
-    for (int k = 0; k < 2; ++k)
+    auto lay_out = [&](uintptr_t base) {
+        uintptr_t cursor = base;
+        auto carve = [&](size_t n) {
+            void *r = reinterpret_cast<void *>(cursor);
+            cursor += (n + 255u) & ~(size_t)255u;
+            return r;
+        };
+        for (int k = 0; k < 2; ++k)
+        {
+            w.rayA[k] = static_cast<float4 *>(carve(padded * 16u));
+            w.rayB[k] = static_cast<float4 *>(carve(padded * 16u));
+            w.pathT[k] = static_cast<float4 *>(carve(padded * 16u));
+            w.pathR[k] = static_cast<uint2 *>(carve(padded * 8u));
+        }
+        w.cameraSlot = static_cast<uint32_t *>(carve(padded * 4u));
+        w.hit = static_cast<uint4 *>(carve(padded * 16u));
+        w.hitIdx = static_cast<uint32_t *>(carve(padded * 4u));
+        w.shA = static_cast<float4 *>(carve(padded * 16u));
+        w.shB = static_cast<float4 *>(carve(padded * 16u));
+        w.shC = static_cast<float4 *>(carve(padded * 16u));
+        w.color = static_cast<float4 *>(carve(padded * 16u));
+        w.segRays = static_cast<uint32_t *>(carve(nSeg * 4u));
+        w.segHits = static_cast<uint32_t *>(carve(nSeg * 4u));
+        w.segShadow = static_cast<uint32_t *>(carve(nSeg * 4u));
+        return (size_t)(cursor - base);
+    };
+    const size_t bytes = lay_out(0);
+    if (bytes > slot.wfBlock.bytes)
     {
-        w.rayA[k] = static_cast<float4 *>(carve(padded * 16u));
-        w.rayB[k] = static_cast<float4 *>(carve(padded * 16u));
-        w.pathT[k] = static_cast<float4 *>(carve(padded * 16u));
-        w.pathR[k] = static_cast<uint2 *>(carve(padded * 8u));
+        // the other slot's render may be in flight on its own streams
+        const int rc = grow_buffer(slot.wfBlock, GrowWait::Device, nullptr, bytes, bytes);
+        if (rc != PROSPER_PT_OK) return rc;
     }
-    w.cameraSlot = static_cast<uint32_t *>(carve(padded * 4u));
-    w.hit = static_cast<uint4 *>(carve(padded * 16u));
-    w.hitIdx = static_cast<uint32_t *>(carve(padded * 4u));
-    w.shA = static_cast<float4 *>(carve(padded * 16u));
-    w.shB = static_cast<float4 *>(carve(padded * 16u));
-    w.shC = static_cast<float4 *>(carve(padded * 16u));
-    w.color = static_cast<float4 *>(carve(padded * 16u));
-    w.segRays = static_cast<uint32_t *>(carve(nSeg * 4u));
-    w.segHits = static_cast<uint32_t *>(carve(nSeg * 4u));
-    w.segShadow = static_cast<uint32_t *>(carve(nSeg * 4u));
+    lay_out(reinterpret_cast<uintptr_t>(slot.wfBlock.ptr));
     w.segLen = (uint32_t)segLen;
     w.nSeg = (uint32_t)nSeg;
     w.pixelsPadded = (uint32_t)pixelsPadded;
@@ -566,51 +618,7 @@ int ensure_wavefront_workspace(
     w.tilesY = tilesY;
     w.bandSegments = bandSegments;
     for (uint32_t x = 0; x < 9u; ++x) w.bandTile[x] = bandTile[x];
-    if ((size_t)(cursor - static_cast<uint8_t *>(slot.wfBlock)) > slot.wfBytes + 0u)
-    {
-        // carve() rounds every array up to 256 B: re-allocate with the exact carved size
-        const size_t need = (size_t)(cursor - static_cast<uint8_t *>(slot.wfBlock));
-        PPT_HIP(hipDeviceSynchronize()); // the other slot's render may be in flight on its own streams
-        PPT_HIP(hipFree(slot.wfBlock));
-        slot.wfBlock = nullptr;
-        slot.wfBytes = 0;
-        PPT_HIP(hipMalloc(&slot.wfBlock, need));
-        slot.wfBytes = need;
-        return ensure_wavefront_workspace(ctx, slot, tilesX, tilesY, frames, pipelined, banded, out);
-    }
     *out = w;
-    return PROSPER_PT_OK;
-}
-
-// Makes sure the global stack-overflow array covers `gridBlocks` workgroups of 256 lanes for a kernel
-// whose LDS stack holds `ldsEntries` entries; returns nullptr when the tree never needs more.
-static int ensure_scratch_dwords(
-    prosper_pt_ctx *ctx, RenderSlot &slot, size_t dwordsPerBlock, uint32_t gridBlocks, hipStream_t stream, int32_t **out);
-int ensure_stack_overflow(
-    prosper_pt_ctx *ctx, RenderSlot &slot, uint32_t ldsEntries, uint32_t gridBlocks, hipStream_t stream, int32_t **out)
-{
-    const uint32_t bound = ctx->stats.maxDepth;
-    return ensure_scratch_dwords(ctx, slot, bound <= ldsEntries ? 0u : (size_t)(bound - ldsEntries) * 256u, gridBlocks, stream, out);
-}
-// `dwordsPerBlock` ints of kernel scratch per workgroup (stack overflow columns, ray-pool records)
-static int ensure_scratch_dwords(
-    prosper_pt_ctx *ctx, RenderSlot &slot, size_t dwordsPerBlock, uint32_t gridBlocks, hipStream_t stream, int32_t **out)
-{
-    (void)ctx;
-    *out = nullptr;
-    if (dwordsPerBlock == 0u) return PROSPER_PT_OK;
-    const size_t bytes = dwordsPerBlock * gridBlocks * sizeof(int32_t);
-    if (bytes > slot.stackOverflowBytes)
-    {
-        (void)stream;
-        PPT_HIP(hipDeviceSynchronize());
-        if (slot.stackOverflow) PPT_HIP(hipFree(slot.stackOverflow));
-        slot.stackOverflow = nullptr;
-        slot.stackOverflowBytes = 0;
-        PPT_HIP(hipMalloc((void **)&slot.stackOverflow, bytes));
-        slot.stackOverflowBytes = bytes;
-    }
-    *out = slot.stackOverflow;
     return PROSPER_PT_OK;
 }
 
@@ -819,7 +827,8 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     // life of the context: 4 % on FlightHelmet, 2 % on S-sponza-class, 60 % on a 256 x 256 frame (profiles/r04_mesh_streams.txt).
     for (auto &ws : ctx->workStreams)
         eventsOk = eventsOk && ws && hipEventRecord(ctx->chainFork, ws) == hipSuccess && hipStreamSynchronize(ws) == hipSuccess;
-    if (!eventsOk || hipMalloc((void **)&ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
+    if (!eventsOk || !create_gbuffer_passes(ctx) ||
+        hipMalloc((void **)&ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess)
     {
         prosper_pt_destroy(ctx);
@@ -837,27 +846,8 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     (void)hipDeviceSynchronize();
     destroy_tiling(ctx);
     free_scene(ctx);
-    if (ctx->ownedHdr) (void)hipFree(ctx->ownedHdr);
+    destroy_gbuffer_passes(ctx);
     if (ctx->dCounters) (void)hipFree(ctx->dCounters);
-    for (RenderSlot &slot : ctx->slots)
-    {
-        if (slot.wfBlock) (void)hipFree(slot.wfBlock);
-        if (slot.stackOverflow) (void)hipFree(slot.stackOverflow);
-    }
-    if (ctx->restirScratch) (void)hipFree(ctx->restirScratch);
-    if (ctx->gbufferOwned) (void)hipFree(ctx->gbufferOwned);
-    if (ctx->clusterPointers) (void)hipFree(ctx->clusterPointers);
-    if (ctx->clusterIndices) (void)hipFree(ctx->clusterIndices);
-    if (ctx->clusterDropped) (void)hipFree(ctx->clusterDropped);
-    if (ctx->iblIrradiance) (void)hipFree(ctx->iblIrradiance);
-    if (ctx->iblRadiance) (void)hipFree(ctx->iblRadiance);
-    if (ctx->iblLut) (void)hipFree(ctx->iblLut);
-    for (hipEvent_t &e : ctx->iblEvents)
-        if (e) (void)hipEventDestroy(e);
-    for (void *r : ctx->restirReservoirs)
-        if (r) (void)hipFree(r);
-    if (ctx->toneLut) (void)hipFree(ctx->toneLut);
-    if (ctx->toneScratch) (void)hipFree(ctx->toneScratch);
     for (auto &e : ctx->events)
         if (e) (void)hipEventDestroy(e);
     for (RenderSlot &slot : ctx->slots)
@@ -875,7 +865,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     if (ctx->buildStream) (void)hipStreamDestroy(ctx->buildStream);
     if (ctx->pinnedStaging) (void)hipHostFree(ctx->pinnedStaging);
     if (ctx->chainFork) (void)hipEventDestroy(ctx->chainFork);
-    delete ctx;
+    delete ctx; // (its DeviceBuffers with it)
 }
 
 int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *scene)
@@ -883,7 +873,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     if (!ctx || !scene) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_upload_scene: null argument");
     int rc = validate_scene(scene);
     if (rc != PROSPER_PT_OK) return rc;
-    ctx->iblGenerated = false; // the maps describe the old sky
+    forget_ibl_maps(ctx);
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());
@@ -1110,6 +1100,119 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
 
 } // extern "C"
 
+namespace ppt
+{
+
+int check_scene(prosper_pt_ctx *ctx, const char *what)
+{
+    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + " called before prosper_pt_upload_scene");
+    if (ctx->meshBuild)
+    {
+        const int prc = poll_mesh_build(ctx, false);
+        if (prc != PROSPER_PT_OK) return prc;
+    }
+    if (ctx->accel && ctx->accel->stale && !ctx->accel->pending)
+        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_update_transforms failed: update the transforms again (or upload the scene) before tracing");
+    return PROSPER_PT_OK;
+}
+
+int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s)
+{
+    PPT_HIP(hipSetDevice(ctx->device));
+    int frc = flush_pending_update(ctx, s);
+    if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, s);
+    if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, s);
+    if (frc != PROSPER_PT_OK) return frc;
+    if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
+    if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
+    if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
+    return PROSPER_PT_OK;
+}
+
+// The scene and light versions a render (or a pass over a G-buffer) read are free again behind its last kernel on `s` (the
+// accumulate kernel follows the path stages on the caller's stream).  One event per version: a reader on ANOTHER stream
+// than the previous reader's first waits for that one, so the newest record always stands for every reader so far.
+int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s)
+{
+    auto mark = [&](hipEvent_t &event, bool &used, hipStream_t &last) -> int {
+        if (!event) PPT_HIP(hipEventCreateWithFlags(&event, hipEventDisableTiming));
+        if (used && last != s) PPT_HIP(hipStreamWaitEvent(s, event, 0));
+        PPT_HIP(hipEventRecord(event, s));
+        used = true;
+        last = s;
+        return PROSPER_PT_OK;
+    };
+    if (AccelState *acc = ctx->accel)
+    {
+        const int rc = mark(acc->versionFree[acc->cur], acc->versionUsed[acc->cur], acc->versionStream[acc->cur]);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    if (LightState *ls = ctx->lights)
+    {
+        const int rc = mark(ls->versionFree[ls->cur], ls->versionUsed[ls->cur], ls->versionStream[ls->cur]);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    if (MaterialState *ms = ctx->materialState)
+    {
+        const int rc = mark(ms->versionFree[ms->cur], ms->versionUsed[ms->cur], ms->versionStream[ms->cur]);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    return PROSPER_PT_OK;
+}
+
+// rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
+void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera)
+{
+    p.eye[0] = camera->eye.x;
+    p.eye[1] = camera->eye.y;
+    p.eye[2] = camera->eye.z;
+    const prosper_mat4 &w2c = camera->worldToCamera;
+    p.right[0] = w2c.col[0].x; p.right[1] = w2c.col[1].x; p.right[2] = w2c.col[2].x;
+    p.up[0] = w2c.col[0].y; p.up[1] = w2c.col[1].y; p.up[2] = w2c.col[2].y;
+    p.fwd[0] = -w2c.col[0].z; p.fwd[1] = -w2c.col[1].z; p.fwd[2] = -w2c.col[2].z;
+    {
+        // volatile: keep the compiler from folding the two divisions into anything but IEEE fp32 divides
+        volatile float c00 = camera->cameraToClip.col[0].x, c11 = camera->cameraToClip.col[1].y;
+        p.aspect = c11 / c00;
+        p.tanHalfFovY = 1.0f / c11;
+    }
+    std::memcpy(p.cameraToWorld, &camera->cameraToWorld, 64);
+}
+
+int prepare_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, const prosper_pt_tile_desc *tile, hipStream_t s)
+{
+    const bool tiled = tile && tile->stripeCount > 1 && tile->stripeWidth > 0;
+    const uint32_t localWidth = compute_local_width(width, tile);
+    const size_t bytes = (size_t)localWidth * height * sizeof(float4);
+    if (ctx->externalHdr)
+    {
+        if (ctx->externalHdrBytes < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "caller-owned output buffer is too small");
+        ctx->hdr = static_cast<float4 *>(ctx->externalHdr);
+    }
+    else
+    {
+        if (ctx->ownedHdr.bytes < bytes || !ctx->ownedHdr.ptr)
+        {
+            const int rc = grow_buffer(ctx->ownedHdr, GrowWait::Stream, s, bytes, bytes ? bytes : 16, 0);
+            if (rc != PROSPER_PT_OK) return rc;
+        }
+        ctx->hdr = ctx->ownedHdr.as<float4>();
+    }
+    ctx->localWidth = localWidth;
+    ctx->height = height;
+    ctx->lastWidth = width;
+    ctx->stripeWidth = tiled ? tile->stripeWidth : 0;
+    ctx->stripeIndex = tiled ? tile->stripeIndex : 0;
+    ctx->stripeCount = tiled ? tile->stripeCount : 1;
+    // a gather of this tile may still be in flight on the communicator's stream (prosper_pt_gather_tiles): the
+    // accumulate kernel, which writes the tile, is enqueued on `s` and must come after it; detached path stages
+    // (PROSPER_PT_RENDER_PIPELINED) do not wait for `s` and overlap the gather
+    wait_for_gather_before_writing_tile(ctx, s);
+    return PROSPER_PT_OK;
+}
+
+} // namespace ppt
+
 int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count)
 {
     AccelState *acc = ctx->accel;
@@ -1274,56 +1377,6 @@ int prosper_pt_set_output_buffer(prosper_pt_ctx *ctx, void *device_rgba32f, size
     return PROSPER_PT_OK;
 }
 
-// The scene and light versions a render (or a ReSTIR trace) read are free again behind its last kernel on `s` (the
-// accumulate kernel follows the path stages on the caller's stream).  One event per version: a reader on ANOTHER stream
-// than the previous reader's first waits for that one, so the newest record always stands for every reader so far.
-static int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s)
-{
-    auto mark = [&](hipEvent_t &event, bool &used, hipStream_t &last) -> int {
-        if (!event) PPT_HIP(hipEventCreateWithFlags(&event, hipEventDisableTiming));
-        if (used && last != s) PPT_HIP(hipStreamWaitEvent(s, event, 0));
-        PPT_HIP(hipEventRecord(event, s));
-        used = true;
-        last = s;
-        return PROSPER_PT_OK;
-    };
-    if (AccelState *acc = ctx->accel)
-    {
-        const int rc = mark(acc->versionFree[acc->cur], acc->versionUsed[acc->cur], acc->versionStream[acc->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    if (LightState *ls = ctx->lights)
-    {
-        const int rc = mark(ls->versionFree[ls->cur], ls->versionUsed[ls->cur], ls->versionStream[ls->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    if (MaterialState *ms = ctx->materialState)
-    {
-        const int rc = mark(ms->versionFree[ms->cur], ms->versionUsed[ms->cur], ms->versionStream[ms->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    return PROSPER_PT_OK;
-}
-
-// rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
-static void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera)
-{
-    p.eye[0] = camera->eye.x;
-    p.eye[1] = camera->eye.y;
-    p.eye[2] = camera->eye.z;
-    const prosper_mat4 &w2c = camera->worldToCamera;
-    p.right[0] = w2c.col[0].x; p.right[1] = w2c.col[1].x; p.right[2] = w2c.col[2].x;
-    p.up[0] = w2c.col[0].y; p.up[1] = w2c.col[1].y; p.up[2] = w2c.col[2].y;
-    p.fwd[0] = -w2c.col[0].z; p.fwd[1] = -w2c.col[1].z; p.fwd[2] = -w2c.col[2].z;
-    {
-        // volatile: keep the compiler from folding the two divisions into anything but IEEE fp32 divides
-        volatile float c00 = camera->cameraToClip.col[0].x, c11 = camera->cameraToClip.col[1].y;
-        p.aspect = c11 / c00;
-        p.tanHalfFovY = 1.0f / c11;
-    }
-    std::memcpy(p.cameraToWorld, &camera->cameraToWorld, 64);
-}
-
 int prosper_pt_render_frames(
     prosper_pt_ctx *ctx, const prosper_ReferencePC *pc, const prosper_CameraUniforms *camera, uint32_t width,
     uint32_t height, const prosper_pt_tile_desc *tile, uint32_t frame_count, uint32_t render_flags, void *stream)
@@ -1347,36 +1400,9 @@ int prosper_pt_render_frames(
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
 
-    const uint32_t localWidth = compute_local_width(width, tile);
-    const size_t bytes = (size_t)localWidth * height * sizeof(float4);
-    if (ctx->externalHdr)
-    {
-        if (ctx->externalHdrBytes < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "caller-owned output buffer is too small");
-        ctx->hdr = static_cast<float4 *>(ctx->externalHdr);
-    }
-    else
-    {
-        if (ctx->ownedHdrBytes < bytes || !ctx->ownedHdr)
-        {
-            PPT_HIP(hipStreamSynchronize(s));
-            if (ctx->ownedHdr) PPT_HIP(hipFree(ctx->ownedHdr));
-            ctx->ownedHdr = nullptr;
-            PPT_HIP(hipMalloc((void **)&ctx->ownedHdr, bytes ? bytes : 16));
-            PPT_HIP(hipMemset(ctx->ownedHdr, 0, bytes ? bytes : 16));
-            ctx->ownedHdrBytes = bytes;
-        }
-        ctx->hdr = ctx->ownedHdr;
-    }
-    ctx->localWidth = localWidth;
-    ctx->height = height;
-    ctx->lastWidth = width;
-    ctx->stripeWidth = tiled ? tile->stripeWidth : 0;
-    ctx->stripeIndex = tiled ? tile->stripeIndex : 0;
-    ctx->stripeCount = tiled ? tile->stripeCount : 1;
-    // a gather of this tile may still be in flight on the communicator's stream (prosper_pt_gather_tiles): the
-    // accumulate kernel, which writes the tile, is enqueued on `s` and must come after it; detached path stages
-    // (PROSPER_PT_RENDER_PIPELINED) do not wait for `s` and overlap the gather
-    wait_for_gather_before_writing_tile(ctx, s);
+    const int hrc = prepare_hdr(ctx, width, height, tile, s);
+    if (hrc != PROSPER_PT_OK) return hrc;
+    const uint32_t localWidth = ctx->localWidth;
 
     RenderParams p = {};
     p.pc = *pc;
@@ -1417,7 +1443,7 @@ int prosper_pt_render_frames(
     if (ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL)
     {
         int32_t *ovf = nullptr;
-        const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, megakernel_grid_blocks(p), s, &ovf);
+        const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, megakernel_grid_blocks(p), &ovf);
         if (orc != PROSPER_PT_OK) return orc;
         wait_for_slot(ctx->slots[0], s);
         if (tp) tp->mark(kStageGenerate, s);
@@ -1480,7 +1506,7 @@ int prosper_pt_render_frames(
             const WavefrontPlan plan = wavefront_plan(
                 ctx->stats.maxDepth, (uint32_t)ctx->stats.nodeCount, (uint32_t)ctx->stats.triangleCount, ctx->scene, wavefront_options(ctx));
             int32_t *ovf = nullptr;
-            const int orc = ensure_scratch_dwords(ctx, slot, plan.scratchDwordsPerBlock, wavefront_grid_blocks(w), s, &ovf);
+            const int orc = ensure_stack_overflow(ctx, slot, plan.ldsStackEntries, wavefront_grid_blocks(w), &ovf);
             if (orc != PROSPER_PT_OK) return orc;
             // the slot's previous user (a render of two calls ago, or the previous chunk of this one) must be done
             // with the workspace: detached chains wait for that on their own stream, the others on the caller's
@@ -1568,713 +1594,15 @@ int prosper_pt_blit_rgba16f(prosper_pt_ctx *ctx, uint16_t *host_rgba16f, size_t 
     return PROSPER_PT_OK;
 }
 
-// ---- ReSTIR-DI (src/render/rtdi/RtDirectIllumination.cpp:70-115) ----
-
-// What every ReSTIR entry checks of the scene before its arguments' extents: a scene, the meshes a worker finished
-// meanwhile, no failed transform update.
-static int restir_check_scene(prosper_pt_ctx *ctx, const char *what)
-{
-    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + " called before prosper_pt_upload_scene");
-    if (ctx->meshBuild)
-    {
-        const int prc = poll_mesh_build(ctx, false);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    if (ctx->accel && ctx->accel->stale && !ctx->accel->pending)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_update_transforms failed: update the transforms again (or upload the scene) before tracing");
-    return PROSPER_PT_OK;
-}
-
-// The pending transform, light and material updates take effect on `s` before the call's first kernel: every kernel
-// the call launches after this reads the same scene and light version (mark_versions_read after the last one).
-static int restir_flush(prosper_pt_ctx *ctx, hipStream_t s)
-{
-    PPT_HIP(hipSetDevice(ctx->device));
-    int frc = flush_pending_update(ctx, s);
-    if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, s);
-    if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, s);
-    if (frc != PROSPER_PT_OK) return frc;
-    if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
-    if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
-    if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
-    return PROSPER_PT_OK;
-}
-
-static RestirCamera restir_camera(const prosper_CameraUniforms *camera)
-{
-    RestirCamera c;
-    c.eye[0] = camera->eye.x;
-    c.eye[1] = camera->eye.y;
-    c.eye[2] = camera->eye.z;
-    std::memcpy(c.clipToWorld, &camera->clipToWorld, 64);
-    float c2c[16];
-    std::memcpy(c2c, &camera->cameraToClip, 64);
-    c.cameraToClip22 = c2c[2 * 4 + 2]; // column 2, row 2
-    c.cameraToClip32 = c2c[3 * 4 + 2]; // column 3, row 2
-    return c;
-}
-
-// The G-buffer (and, with `withReservoirs`, the reservoirs) on the device: host inputs are copied into one scratch
-// allocation, 16 + 16 + 8 + 4 bytes per pixel.
-struct RestirDeviceInputs
-{
-    const void *ar, *nm, *res;
-    const float *depth;
-};
-static int restir_device_inputs(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_inputs *in, size_t pixels, bool withReservoirs, hipStream_t s,
-    RestirDeviceInputs &out)
-{
-    out.ar = in->albedoRoughness;
-    out.nm = in->normalMetallic;
-    out.res = in->reservoirs;
-    out.depth = in->nonLinearDepth;
-    if (in->onDevice) return PROSPER_PT_OK;
-    const size_t need = pixels * 44u + 64u;
-    if (ctx->restirScratchBytes < need)
-    {
-        PPT_HIP(hipStreamSynchronize(s));
-        if (ctx->restirScratch) PPT_HIP(hipFree(ctx->restirScratch));
-        ctx->restirScratch = nullptr;
-        ctx->restirScratchBytes = 0;
-        PPT_HIP(hipMalloc(&ctx->restirScratch, need));
-        ctx->restirScratchBytes = need;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->restirScratch);
-    PPT_HIP(hipMemcpyAsync(base, in->albedoRoughness, pixels * 16u, hipMemcpyHostToDevice, s));
-    PPT_HIP(hipMemcpyAsync(base + pixels * 16u, in->normalMetallic, pixels * 16u, hipMemcpyHostToDevice, s));
-    if (withReservoirs) PPT_HIP(hipMemcpyAsync(base + pixels * 32u, in->reservoirs, pixels * 8u, hipMemcpyHostToDevice, s));
-    PPT_HIP(hipMemcpyAsync(base + pixels * 40u, in->nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
-    out.ar = base;
-    out.nm = base + pixels * 16u;
-    out.res = base + pixels * 32u;
-    out.depth = reinterpret_cast<const float *>(base + pixels * 40u);
-    return PROSPER_PT_OK;
-}
-
-// The two context-owned reservoir buffers, grown like restirScratch (what still reads them on `s` finishes first).
-static int restir_reservoir_buffers(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s)
-{
-    const size_t need = pixels * 8u;
-    if (ctx->restirReservoirBytes >= need && ctx->restirReservoirs[0]) return PROSPER_PT_OK;
-    PPT_HIP(hipStreamSynchronize(s));
-    for (void *&r : ctx->restirReservoirs)
-    {
-        if (r) PPT_HIP(hipFree(r));
-        r = nullptr;
-    }
-    ctx->restirReservoirBytes = 0;
-    ctx->restirLastReservoirs = nullptr;
-    ctx->restirLastReservoirBytes = 0;
-    for (void *&r : ctx->restirReservoirs) PPT_HIP(hipMalloc(&r, need));
-    ctx->restirReservoirBytes = need;
-    return PROSPER_PT_OK;
-}
-
-// The context's HDR image as one whole width x height image (no stripes) for a pass that writes it: the caller-owned
-// buffer, or the owned one grown (and cleared) as needed.
-static int prepare_whole_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, hipStream_t s)
-{
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    if (ctx->externalHdr)
-    {
-        if (ctx->externalHdrBytes < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "caller-owned output buffer is too small");
-        ctx->hdr = static_cast<float4 *>(ctx->externalHdr);
-    }
-    else
-    {
-        if (ctx->ownedHdrBytes < bytes || !ctx->ownedHdr)
-        {
-            PPT_HIP(hipStreamSynchronize(s));
-            if (ctx->ownedHdr) PPT_HIP(hipFree(ctx->ownedHdr));
-            ctx->ownedHdr = nullptr;
-            PPT_HIP(hipMalloc((void **)&ctx->ownedHdr, bytes));
-            PPT_HIP(hipMemset(ctx->ownedHdr, 0, bytes));
-            ctx->ownedHdrBytes = bytes;
-        }
-        ctx->hdr = ctx->ownedHdr;
-    }
-    ctx->localWidth = width;
-    ctx->height = height;
-    ctx->lastWidth = width;
-    ctx->stripeWidth = 0;
-    ctx->stripeIndex = 0;
-    ctx->stripeCount = 1;
-    wait_for_gather_before_writing_tile(ctx, s);
-    return PROSPER_PT_OK;
-}
-
-// The trace pass over device inputs: the HDR image, the traversal stacks, the launch.
-static int restir_trace(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height, const RestirDeviceInputs &in, hipStream_t s)
-{
-    const int hrc = prepare_whole_hdr(ctx, width, height, s);
-    if (hrc != PROSPER_PT_OK) return hrc;
-
-    int32_t *ovf = nullptr;
-    const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), s, &ovf);
-    if (orc != PROSPER_PT_OK) return orc;
-    wait_for_slot(ctx->slots[0], s);
-    launch_restir_di_trace(
-        ctx->scene, pc->drawType, pc->frameIndex, pc->flags, width, height, restir_camera(camera), in.ar, in.nm, in.depth,
-        in.res, ctx->hdr, ovf, s);
-    release_slot(ctx->slots[0], s);
-    PPT_HIP(hipGetLastError());
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_restir_di_trace(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height, const prosper_pt_restir_inputs *in, void *stream)
-{
-    if (!ctx || !pc || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth || !in->reservoirs)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: null argument");
-    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_trace");
-    if (crc != PROSPER_PT_OK) return crc;
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = restir_flush(ctx, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    RestirDeviceInputs din;
-    rc = restir_device_inputs(ctx, in, (size_t)width * height, true, s, din);
-    if (rc == PROSPER_PT_OK) rc = restir_trace(ctx, pc, camera, width, height, din, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_restir_di_resample(
-    prosper_pt_ctx *ctx, uint32_t stage, uint32_t frameIndex, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height, const prosper_pt_restir_inputs *in, void *device_out_reservoirs, void *stream)
-{
-    if (!ctx || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: null argument");
-    if (stage != PROSPER_PT_RESTIR_INITIAL && stage != PROSPER_PT_RESTIR_SPATIAL)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: unknown stage");
-    const bool spatial = stage == PROSPER_PT_RESTIR_SPATIAL;
-    if (spatial && !in->reservoirs)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass needs input reservoirs");
-    if (device_out_reservoirs && (reinterpret_cast<uintptr_t>(device_out_reservoirs) & 7u))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: output reservoirs must be 8-byte aligned");
-    if (spatial && in->onDevice && device_out_reservoirs == in->reservoirs)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass cannot write its input");
-    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_resample");
-    if (crc != PROSPER_PT_OK) return crc;
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: empty extent");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t pixels = (size_t)width * height;
-    int rc = restir_flush(ctx, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    void *out = device_out_reservoirs;
-    if (!out)
-    {
-        rc = restir_reservoir_buffers(ctx, pixels, s);
-        if (rc != PROSPER_PT_OK) return rc;
-        // the spatial pass writes the buffer it does not read
-        out = spatial && in->onDevice && in->reservoirs == ctx->restirReservoirs[1] ? ctx->restirReservoirs[0]
-                                                                                    : ctx->restirReservoirs[spatial ? 1 : 0];
-    }
-    RestirDeviceInputs din;
-    rc = restir_device_inputs(ctx, in, pixels, spatial, s, din);
-    if (rc != PROSPER_PT_OK) return rc;
-    const RestirCamera cam = restir_camera(camera);
-    if (spatial)
-        launch_restir_di_spatial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, din.res, out, s);
-    else
-        launch_restir_di_initial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, out, s);
-    PPT_HIP(hipGetLastError());
-    if (!device_out_reservoirs)
-    {
-        ctx->restirLastReservoirs = out;
-        ctx->restirLastReservoirBytes = pixels * 8u;
-    }
-    return mark_versions_read(ctx, s);
-}
-
-// ---- ray-traced G-buffer (the ReSTIR-DI passes' input; a stand-in for src/render/GBufferRenderer.cpp) ----
-
-// The context-owned targets, one allocation of 16 + 16 + 4 bytes per pixel, grown like restirScratch.
-static int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, prosper_pt_gbuffer_targets &out)
-{
-    const size_t need = pixels * 36u + 64u;
-    if (ctx->gbufferOwnedBytes < need || !ctx->gbufferOwned)
-    {
-        PPT_HIP(hipStreamSynchronize(s));
-        if (ctx->gbufferLast.albedoRoughness == ctx->gbufferOwned)
-        {
-            ctx->gbufferLast = prosper_pt_gbuffer_targets{};
-            ctx->gbufferLastWidth = ctx->gbufferLastHeight = 0;
-        }
-        if (ctx->gbufferOwned) PPT_HIP(hipFree(ctx->gbufferOwned));
-        ctx->gbufferOwned = nullptr;
-        ctx->gbufferOwnedBytes = 0;
-        PPT_HIP(hipMalloc(&ctx->gbufferOwned, need));
-        ctx->gbufferOwnedBytes = need;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->gbufferOwned);
-    out.albedoRoughness = base;
-    out.normalMetallic = base + pixels * 16u;
-    out.nonLinearDepth = reinterpret_cast<float *>(base + pixels * 32u);
-    return PROSPER_PT_OK;
-}
-
-// The G-buffer pass on `s` after restir_flush: camera terms, the traversal stacks, the launch.
-static int gbuffer_trace(
-    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s)
-{
-    GBufferTraceParams g = {};
-    set_camera_ray_params(g.r, camera);
-    g.r.width = width;
-    g.r.height = height;
-    g.r.localWidth = width;
-    g.r.stripeCount = 1;
-    g.r.frameCount = 1;
-    // worldToClip = cameraToClip * worldToCamera (column-major), in double, rounded once
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 4; ++r)
-        {
-            double v = 0.0;
-            for (int k = 0; k < 4; ++k)
-                v += (double)(&camera->cameraToClip.col[k].x)[r] * (double)(&camera->worldToCamera.col[c].x)[k];
-            g.worldToClip[c * 4 + r] = (float)v;
-        }
-    g.drawType = drawType;
-    g.frameIndex = frameIndex;
-    g.jitter = jitter ? 1u : 0u;
-
-    int32_t *ovf = nullptr;
-    const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), s, &ovf);
-    if (orc != PROSPER_PT_OK) return orc;
-    wait_for_slot(ctx->slots[0], s);
-    launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
-    release_slot(ctx->slots[0], s);
-    PPT_HIP(hipGetLastError());
-    ctx->gbufferLast = t;
-    ctx->gbufferLastWidth = width;
-    ctx->gbufferLastHeight = height;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_trace_gbuffer(
-    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_JITTER)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: unknown flags");
-    if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: empty extent");
-    if (!ctx || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null argument");
-    if (targets)
-    {
-        if (!targets->albedoRoughness || !targets->normalMetallic || !targets->nonLinearDepth)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null target");
-        if ((reinterpret_cast<uintptr_t>(targets->albedoRoughness) | reinterpret_cast<uintptr_t>(targets->normalMetallic) |
-             reinterpret_cast<uintptr_t>(targets->nonLinearDepth)) & 15u)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: targets must be 16-byte aligned");
-    }
-    const int crc = restir_check_scene(ctx, "prosper_pt_trace_gbuffer");
-    if (crc != PROSPER_PT_OK) return crc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = restir_flush(ctx, s);
-    prosper_pt_gbuffer_targets t = {};
-    if (rc == PROSPER_PT_OK)
-    {
-        if (targets)
-            t = *targets;
-        else
-            rc = gbuffer_owned_targets(ctx, (size_t)width * height, s, t);
-    }
-    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gbuffer_device_ptrs: null argument");
-    if (!ctx->gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
-    *out = prosper_pt_restir_inputs{};
-    out->albedoRoughness = ctx->gbufferLast.albedoRoughness;
-    out->normalMetallic = ctx->gbufferLast.normalMetallic;
-    out->nonLinearDepth = ctx->gbufferLast.nonLinearDepth;
-    out->onDevice = 1;
-    if (width) *width = ctx->gbufferLastWidth;
-    if (height) *height = ctx->gbufferLastHeight;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_gbuffer(
-    prosper_pt_ctx *ctx, float *host_albedo_roughness, float *host_normal_metallic, float *host_depth, size_t pixels,
-    void *stream)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: null argument");
-    if (!ctx->gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
-    if (pixels != (size_t)ctx->gbufferLastWidth * ctx->gbufferLastHeight)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: pixel count differs from the G-buffer's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const prosper_pt_gbuffer_targets &t = ctx->gbufferLast;
-    if (host_albedo_roughness)
-        PPT_HIP(hipMemcpyAsync(host_albedo_roughness, t.albedoRoughness, pixels * 16u, hipMemcpyDeviceToHost, s));
-    if (host_normal_metallic)
-        PPT_HIP(hipMemcpyAsync(host_normal_metallic, t.normalMetallic, pixels * 16u, hipMemcpyDeviceToHost, s));
-    if (host_depth) PPT_HIP(hipMemcpyAsync(host_depth, t.nonLinearDepth, pixels * 4u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_restir_di_record(
-    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, void *stream)
-{
-    if ((recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) && !(recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: JITTER_GBUFFER without TRACE_GBUFFER");
-    const bool traced = (recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER) != 0;
-    if (!ctx || !pc || !camera ||
-        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: null argument");
-    if (recordFlags & ~(uint32_t)(PROSPER_PT_RESTIR_SPATIAL_REUSE | PROSPER_PT_RESTIR_TRACE_GBUFFER | PROSPER_PT_RESTIR_JITTER_GBUFFER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: unknown record flags");
-    const int crc = restir_check_scene(ctx, "prosper_pt_restir_di_record");
-    if (crc != PROSPER_PT_OK) return crc;
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t pixels = (size_t)width * height;
-    int rc = restir_flush(ctx, s);
-    if (rc == PROSPER_PT_OK) rc = restir_reservoir_buffers(ctx, pixels, s);
-    RestirDeviceInputs din;
-    if (traced)
-    {
-        // the G-buffer pass first, into the context-owned targets (never the restirScratch a host-input call fills)
-        prosper_pt_gbuffer_targets t = {};
-        if (rc == PROSPER_PT_OK) rc = gbuffer_owned_targets(ctx, pixels, s, t);
-        if (rc == PROSPER_PT_OK)
-            rc = gbuffer_trace(ctx, pc->drawType, pc->frameIndex, (recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) != 0,
-                               camera, width, height, t, s);
-        din.ar = t.albedoRoughness;
-        din.nm = t.normalMetallic;
-        din.depth = t.nonLinearDepth;
-        din.res = nullptr;
-    }
-    else if (rc == PROSPER_PT_OK)
-        rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
-    if (rc != PROSPER_PT_OK) return rc;
-    const RestirCamera cam = restir_camera(camera);
-    // InitialReservoirs, then SpatialReuse when the toggle is on, then Trace (RtDirectIllumination.cpp:80-109)
-    launch_restir_di_initial(
-        ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, ctx->restirReservoirs[0], s);
-    din.res = ctx->restirReservoirs[0];
-    if (recordFlags & PROSPER_PT_RESTIR_SPATIAL_REUSE)
-    {
-        launch_restir_di_spatial(
-            ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, ctx->restirReservoirs[0],
-            ctx->restirReservoirs[1], s);
-        din.res = ctx->restirReservoirs[1];
-    }
-    PPT_HIP(hipGetLastError());
-    ctx->restirLastReservoirs = din.res;
-    ctx->restirLastReservoirBytes = pixels * 8u;
-    rc = restir_trace(ctx, pc, camera, width, height, din, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    return mark_versions_read(ctx, s);
-}
-
-// ---- clustered lighting and deferred shading (src/render/LightClustering.cpp, src/render/DeferredShading.cpp) ----
-
-static ClusterParams cluster_params(const prosper_CameraUniforms *camera, uint32_t width, uint32_t height)
-{
-    ClusterParams c;
-    std::memcpy(c.worldToCamera, &camera->worldToCamera, 64);
-    float c2c[16];
-    std::memcpy(c2c, &camera->cameraToClip, 64);
-    c.cameraToClip00 = c2c[0];
-    c.cameraToClip11 = c2c[1 * 4 + 1];
-    c.resolution[0] = (float)camera->resolution[0];
-    c.resolution[1] = (float)camera->resolution[1];
-    c.near_ = camera->near_;
-    c.far_ = camera->far_;
-    c.dimX = (width + kClusterDim - 1u) / kClusterDim;
-    c.dimY = (height + kClusterDim - 1u) / kClusterDim;
-    return c;
-}
-
-// The clustering pass on `s` after restir_flush: buffers grown as needed (the index buffer starts as 0xFFFF), the
-// launch.  Every cluster writes its pointer and dropped count, so nothing is cleared (LightClustering.cpp's fillBuffer
-// of the counter is replaced by summing the pointers' counts in prosper_pt_read_light_clusters).
-static int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
-{
-    const size_t clusters = (size_t)c.dimX * c.dimY * (kClusterZSlices + 1u);
-    if (ctx->clusterCapacity < clusters || !ctx->clusterPointers)
-    {
-        PPT_HIP(hipStreamSynchronize(s));
-        if (ctx->clusterPointers) PPT_HIP(hipFree(ctx->clusterPointers));
-        if (ctx->clusterIndices) PPT_HIP(hipFree(ctx->clusterIndices));
-        if (ctx->clusterDropped) PPT_HIP(hipFree(ctx->clusterDropped));
-        ctx->clusterPointers = nullptr;
-        ctx->clusterIndices = nullptr;
-        ctx->clusterDropped = nullptr;
-        ctx->clusterCapacity = 0;
-        ctx->clusterDims[0] = ctx->clusterDims[1] = ctx->clusterDims[2] = 0;
-        PPT_HIP(hipMalloc(&ctx->clusterPointers, clusters * 8u));
-        PPT_HIP(hipMalloc((void **)&ctx->clusterIndices, clusters * kClusterSlot * 2u));
-        PPT_HIP(hipMemset(ctx->clusterIndices, 0xFF, clusters * kClusterSlot * 2u));
-        PPT_HIP(hipMalloc((void **)&ctx->clusterDropped, clusters * 4u));
-        ctx->clusterCapacity = clusters;
-    }
-    launch_light_clustering(ctx->scene, c, ctx->clusterPointers, ctx->clusterIndices, ctx->clusterDropped, s);
-    PPT_HIP(hipGetLastError());
-    ctx->clusterDims[0] = c.dimX;
-    ctx->clusterDims[1] = c.dimY;
-    ctx->clusterDims[2] = kClusterZSlices + 1u;
-    return PROSPER_PT_OK;
-}
-
-// near_ and far_ feed log(far / near) and pow(far / near, s): both positive and ordered
-static bool cluster_camera_ok(const prosper_CameraUniforms *camera)
-{
-    return camera->near_ > 0.0f && camera->far_ > camera->near_ && camera->resolution[0] > 0 && camera->resolution[1] > 0;
-}
-
-int prosper_pt_cluster_lights(
-    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, void *stream)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (!camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: empty extent");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: camera needs 0 < near_ < far_ and a resolution");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
-    const int crc = restir_check_scene(ctx, "prosper_pt_cluster_lights");
-    if (crc != PROSPER_PT_OK) return crc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = restir_flush(ctx, s);
-    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, cluster_params(camera, width, height), s);
-    if (rc != PROSPER_PT_OK) return rc;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_get_light_cluster_dims(prosper_pt_ctx *ctx, uint32_t *x, uint32_t *y, uint32_t *z)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_light_cluster_dims: null argument");
-    if (!ctx->clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
-    if (x) *x = ctx->clusterDims[0];
-    if (y) *y = ctx->clusterDims[1];
-    if (z) *z = ctx->clusterDims[2];
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_light_clusters(
-    prosper_pt_ctx *ctx, uint32_t *host_pointers, uint16_t *host_indices, uint32_t *host_count, uint32_t *host_dropped,
-    uint32_t *host_overflowing, size_t clusters, void *stream)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: null argument");
-    if (!ctx->clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
-    if (clusters != (size_t)ctx->clusterDims[0] * ctx->clusterDims[1] * ctx->clusterDims[2])
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: cluster count differs from the last clustering's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<uint32_t> ptrs(clusters * 2u), dropped(clusters);
-    PPT_HIP(hipMemcpyAsync(ptrs.data(), ctx->clusterPointers, clusters * 8u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipMemcpyAsync(dropped.data(), ctx->clusterDropped, clusters * 4u, hipMemcpyDeviceToHost, s));
-    if (host_indices)
-        PPT_HIP(hipMemcpyAsync(host_indices, ctx->clusterIndices, clusters * kClusterSlot * 2u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    if (host_pointers) std::memcpy(host_pointers, ptrs.data(), clusters * 8u);
-    uint32_t count = 0, droppedSum = 0, overflowing = 0;
-    for (size_t k = 0; k < clusters; ++k)
-    {
-        count += (ptrs[2 * k + 1] >> 16) + (ptrs[2 * k + 1] & 0xFFFFu);
-        droppedSum += dropped[k];
-        overflowing += dropped[k] != 0u;
-    }
-    if (host_count) *host_count = count;
-    if (host_dropped) *host_dropped = droppedSum;
-    if (host_overflowing) *host_overflowing = overflowing;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_deferred_shading(
-    prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
-    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
-    void *stream)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (flags & ~(uint32_t)(PROSPER_PT_DEFERRED_TRACE_GBUFFER | PROSPER_PT_DEFERRED_JITTER_GBUFFER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: unknown flags");
-    if ((flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) && !(flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: JITTER_GBUFFER without TRACE_GBUFFER");
-    const bool traced = (flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER) != 0;
-    if (!pc || !camera ||
-        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: ibl is 0 or 1");
-    if (pc->ibl == 1u && (!ctx || !ctx->iblGenerated))
-        return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: camera needs 0 < near_ < far_ and a resolution");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
-    const int crc = restir_check_scene(ctx, "prosper_pt_deferred_shading");
-    if (crc != PROSPER_PT_OK) return crc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t pixels = (size_t)width * height;
-    int rc = restir_flush(ctx, s);
-    RestirDeviceInputs din = {};
-    if (traced)
-    {
-        prosper_pt_gbuffer_targets t = {};
-        if (rc == PROSPER_PT_OK) rc = gbuffer_owned_targets(ctx, pixels, s, t);
-        if (rc == PROSPER_PT_OK)
-            rc = gbuffer_trace(ctx, pc->drawType, frameIndex, (flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) != 0, camera,
-                               width, height, t, s);
-        din.ar = t.albedoRoughness;
-        din.nm = t.normalMetallic;
-        din.depth = t.nonLinearDepth;
-    }
-    else if (rc == PROSPER_PT_OK)
-        rc = restir_device_inputs(ctx, gbuffer, pixels, false, s, din);
-    const ClusterParams c = cluster_params(camera, width, height);
-    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, c, s);
-    if (rc == PROSPER_PT_OK) rc = prepare_whole_hdr(ctx, width, height, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    if (pc->ibl == 1u)
-        launch_deferred_shading_ibl(
-            ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth,
-            ctx->clusterPointers, ctx->clusterIndices, ctx->iblIrradiance, ctx->iblRadiance, ctx->iblLut, ctx->hdr, s);
-    else
-        launch_deferred_shading(
-            ctx->scene, pc->drawType, width, height, restir_camera(camera), c, din.ar, din.nm, din.depth,
-            ctx->clusterPointers, ctx->clusterIndices, ctx->hdr, s);
-    PPT_HIP(hipGetLastError());
-    return mark_versions_read(ctx, s);
-}
-
-// ---- image-based lighting (src/render/ImageBasedLighting.cpp) ----
-
-int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_generate_ibl: null argument");
-    const int crc = restir_check_scene(ctx, "prosper_pt_generate_ibl");
-    if (crc != PROSPER_PT_OK) return crc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = restir_flush(ctx, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    if (!ctx->iblIrradiance) PPT_HIP(hipMalloc((void **)&ctx->iblIrradiance, kIblIrradianceTexels * 8u));
-    if (!ctx->iblRadiance) PPT_HIP(hipMalloc((void **)&ctx->iblRadiance, kIblRadianceTexels * 8u));
-    if (!ctx->iblLut) PPT_HIP(hipMalloc((void **)&ctx->iblLut, (size_t)kIblLutSize * kIblLutSize * 4u));
-    for (hipEvent_t &e : ctx->iblEvents)
-        if (!e) PPT_HIP(hipEventCreate(&e));
-    launch_ibl_generation(ctx->scene, ctx->iblIrradiance, ctx->iblRadiance, ctx->iblLut, ctx->iblEvents, s);
-    PPT_HIP(hipGetLastError());
-    ctx->iblGenerated = true;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_get_ibl_info(prosper_pt_ctx *ctx, prosper_pt_ibl_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_ibl_info: null argument");
-    prosper_pt_ibl_info info = {};
-    info.generated = ctx->iblGenerated ? 1u : 0u;
-    info.irradianceSize = kIblIrradianceSize;
-    info.radianceSize = kIblRadianceSize;
-    info.radianceMips = kIblRadianceMips;
-    info.lutSize = kIblLutSize;
-    if (ctx->iblEvents[3])
-    {
-        PPT_HIP(hipSetDevice(ctx->device));
-        PPT_HIP(hipEventSynchronize(ctx->iblEvents[3]));
-        PPT_HIP(hipEventElapsedTime(&info.irradianceMs, ctx->iblEvents[0], ctx->iblEvents[1]));
-        PPT_HIP(hipEventElapsedTime(&info.radianceMs, ctx->iblEvents[1], ctx->iblEvents[2]));
-        PPT_HIP(hipEventElapsedTime(&info.lutMs, ctx->iblEvents[2], ctx->iblEvents[3]));
-    }
-    *out = info;
-    return PROSPER_PT_OK;
-}
-
-// The interior texels of `levels` bordered cubes (6 faces of (n + 2)^2 RGBA16F each, n halving per level) to host
-static void strip_cube_borders(const std::vector<uint16_t> &bordered, uint32_t n, uint32_t levels, uint16_t *out)
-{
-    size_t src = 0;
-    for (uint32_t m = 0; m < levels; ++m, n >>= 1)
-    {
-        const size_t n2 = n + 2u;
-        for (uint32_t face = 0; face < 6u; ++face)
-            for (uint32_t j = 0; j < n; ++j)
-            {
-                std::memcpy(out, &bordered[4u * (src + ((size_t)face * n2 + j + 1u) * n2 + 1u)], (size_t)n * 8u);
-                out += 4u * (size_t)n;
-            }
-        src += 6u * n2 * n2;
-    }
-}
-
-int prosper_pt_read_ibl(
-    prosper_pt_ctx *ctx, uint16_t *irradiance_rgba16f, size_t irradiance_bytes, uint16_t *radiance_rgba16f,
-    size_t radiance_bytes, uint16_t *lut_rg16, size_t lut_bytes, void *stream)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (irradiance_rgba16f && irradiance_bytes != 6u * kIblIrradianceSize * kIblIrradianceSize * 8u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: irradiance_bytes is not 6 x 64 x 64 RGBA16F");
-    size_t radianceTexels = 0;
-    for (uint32_t m = 0; m < kIblRadianceMips; ++m) radianceTexels += 6u * (size_t)(kIblRadianceSize >> m) * (kIblRadianceSize >> m);
-    if (radiance_rgba16f && radiance_bytes != radianceTexels * 8u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: radiance_bytes is not the 10 mips of 6 x 512 x 512 RGBA16F");
-    if (lut_rg16 && lut_bytes != (size_t)kIblLutSize * kIblLutSize * 4u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: lut_bytes is not 512 x 512 R16G16");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: null argument");
-    if (!ctx->iblGenerated) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_ibl: no maps were generated for the current scene (prosper_pt_generate_ibl)");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<uint16_t> irr(irradiance_rgba16f ? 4u * kIblIrradianceTexels : 0u);
-    std::vector<uint16_t> rad(radiance_rgba16f ? 4u * kIblRadianceTexels : 0u);
-    if (irradiance_rgba16f) PPT_HIP(hipMemcpyAsync(irr.data(), ctx->iblIrradiance, irr.size() * 2u, hipMemcpyDeviceToHost, s));
-    if (radiance_rgba16f) PPT_HIP(hipMemcpyAsync(rad.data(), ctx->iblRadiance, rad.size() * 2u, hipMemcpyDeviceToHost, s));
-    if (lut_rg16) PPT_HIP(hipMemcpyAsync(lut_rg16, ctx->iblLut, lut_bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    if (irradiance_rgba16f) strip_cube_borders(irr, kIblIrradianceSize, 1u, irradiance_rgba16f);
-    if (radiance_rgba16f) strip_cube_borders(rad, kIblRadianceSize, kIblRadianceMips, radiance_rgba16f);
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes)
-{
-    if (!ctx || !out_ptr) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_restir_reservoirs_device_ptr: null argument");
-    if (!ctx->restirLastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
-    *out_ptr = const_cast<void *>(ctx->restirLastReservoirs);
-    if (out_bytes) *out_bytes = ctx->restirLastReservoirBytes;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, size_t byte_size, void *stream)
-{
-    if (!ctx || !host_float2) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: null argument");
-    if (!ctx->restirLastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
-    if (byte_size != ctx->restirLastReservoirBytes)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: size differs from the reservoirs'");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host_float2, ctx->restirLastReservoirs, byte_size, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
-}
-
 int prosper_pt_set_tone_map_lut(prosper_pt_ctx *ctx, const uint32_t *lut, uint32_t dim)
 {
     if (!ctx || !lut || dim < 2 || dim > 256) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_tone_map_lut: bad argument");
     PPT_HIP(hipSetDevice(ctx->device));
-    PPT_HIP(hipDeviceSynchronize());
-    if (ctx->toneLut) PPT_HIP(hipFree(ctx->toneLut));
-    ctx->toneLut = nullptr;
     ctx->toneLutDim = 0;
     const size_t bytes = (size_t)dim * dim * dim * sizeof(uint32_t);
-    PPT_HIP(hipMalloc((void **)&ctx->toneLut, bytes));
-    PPT_HIP(hipMemcpy(ctx->toneLut, lut, bytes, hipMemcpyHostToDevice));
+    const int rc = grow_buffer(ctx->toneLut, GrowWait::Device, nullptr, bytes, bytes);
+    if (rc != PROSPER_PT_OK) return rc;
+    PPT_HIP(hipMemcpy(ctx->toneLut.ptr, lut, bytes, hipMemcpyHostToDevice));
     ctx->toneLutDim = dim;
     return PROSPER_PT_OK;
 }
@@ -2285,7 +1613,7 @@ int prosper_pt_tone_map(
 {
     if (!ctx || (!device_rgba8 && !host_rgba8)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_tone_map: null argument");
     if (!ctx->hdr) return fail(PROSPER_PT_ERR_NO_SCENE, "nothing has been rendered yet");
-    if (!ctx->toneLut) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_tone_map: no LUT (prosper_pt_set_tone_map_lut)");
+    if (!ctx->toneLut.ptr) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_tone_map: no LUT (prosper_pt_set_tone_map_lut)");
     const uint32_t count = ctx->localWidth * ctx->height;
     const size_t bytes = (size_t)count * 4u;
     if (byte_size < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_tone_map: destination too small");
@@ -2294,18 +1622,14 @@ int prosper_pt_tone_map(
     void *out = device_rgba8;
     if (!out)
     {
-        if (ctx->toneScratchBytes < bytes)
+        if (ctx->toneScratch.bytes < bytes)
         {
-            PPT_HIP(hipStreamSynchronize(s));
-            if (ctx->toneScratch) PPT_HIP(hipFree(ctx->toneScratch));
-            ctx->toneScratch = nullptr;
-            ctx->toneScratchBytes = 0;
-            PPT_HIP(hipMalloc(&ctx->toneScratch, bytes + 16));
-            ctx->toneScratchBytes = bytes;
+            const int rc = grow_buffer(ctx->toneScratch, GrowWait::Stream, s, bytes, bytes + 16);
+            if (rc != PROSPER_PT_OK) return rc;
         }
-        out = ctx->toneScratch;
+        out = ctx->toneScratch.ptr;
     }
-    launch_tone_map(ctx->hdr, ctx->toneLut, ctx->toneLutDim, exposure, contrast, out, count, s);
+    launch_tone_map(ctx->hdr, ctx->toneLut.as<uint32_t>(), ctx->toneLutDim, exposure, contrast, out, count, s);
     PPT_HIP(hipGetLastError());
     if (host_rgba8)
     {

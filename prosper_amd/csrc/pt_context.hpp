@@ -25,6 +25,47 @@ struct DeviceAllocation
 // records `msg` as the calling thread's last error (prosper_pt_last_error) and returns `code`
 int fail(int code, const std::string &msg);
 
+// A device buffer of the context that only grows (grow_buffer) and is freed with its owner.  `bytes` is what the last
+// grow asked for; the allocation may be padded beyond it.
+struct DeviceBuffer
+{
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer()
+    {
+        if (ptr) (void)hipFree(ptr);
+    }
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+};
+// What a grow waits for before it frees the old allocation: nothing (a buffer allocated once), the stream of the call,
+// or the whole device (work on other streams may still read the buffer)
+enum class GrowWait
+{
+    None,
+    Stream,
+    Device,
+};
+
+#pragma GCC visibility push(hidden) // (not part of the library's exports)
+
+// The one way a DeviceBuffer grows: wait (`wait`, on `s`), free the old allocation, allocate `allocBytes` (`bytes` and any
+// padding), fill the new allocation with the byte `fill` unless it is negative, record `bytes`.  On failure the buffer is
+// left empty (nullptr, 0).
+int grow_buffer(DeviceBuffer &buf, GrowWait wait, hipStream_t s, size_t bytes, size_t allocBytes, int fill = -1);
+
+// State of the passes over a G-buffer (pt_gbuffer_passes.cpp): their buffers and what the last call of each produced.
+// Made by prosper_pt_create (false: out of host memory), freed by prosper_pt_destroy.
+struct GBufferPassState;
+bool create_gbuffer_passes(prosper_pt_ctx *ctx);
+void destroy_gbuffer_passes(prosper_pt_ctx *ctx);
+// a new scene: the image-based lighting maps describe the old sky
+void forget_ibl_maps(prosper_pt_ctx *ctx);
+
+#pragma GCC visibility pop
+
 // Host + device state of the acceleration structure that outlives prosper_pt_upload_scene, so that moved instances can
 // be re-fitted without rebuilding the scene (prosper_pt_update_transforms): the world triangles in (drawInstance,
 // primitive) order on both sides, the per-instance subtrees (bvh_build.hpp InstancedBvh), the instance table.
@@ -301,8 +342,7 @@ struct prosper_pt_ctx
     size_t pinnedStagingBytes = 0;
 
     float4 *hdr = nullptr; // current HDR buffer (internal or caller-owned)
-    float4 *ownedHdr = nullptr;
-    size_t ownedHdrBytes = 0;
+    ppt::DeviceBuffer ownedHdr;
     void *externalHdr = nullptr;
     size_t externalHdrBytes = 0;
     uint32_t localWidth = 0, height = 0;
@@ -319,30 +359,10 @@ struct prosper_pt_ctx
     uint32_t timedLaunches = 0;
     bool timingValid = false;
 
-    void *restirScratch = nullptr; // device copies of host G-buffer inputs (prosper_pt_restir_di_trace)
-    size_t restirScratchBytes = 0;
-    void *restirReservoirs[2] = {}; // ping-pong reservoir buffers of the ReSTIR-DI passes (width*height float2 each)
-    size_t restirReservoirBytes = 0; // of each
-    const void *restirLastReservoirs = nullptr; // prosper_pt_get_restir_reservoirs_device_ptr
-    size_t restirLastReservoirBytes = 0;
-    void *gbufferOwned = nullptr; // context-owned G-buffer targets (prosper_pt_trace_gbuffer): 16 + 16 + 4 bytes per pixel
-    size_t gbufferOwnedBytes = 0;
-    prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
-    uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
-    void *clusterPointers = nullptr;    // prosper_pt_cluster_lights: uint2 per cluster
-    uint16_t *clusterIndices = nullptr; // kClusterSlot entries per cluster
-    uint32_t *clusterDropped = nullptr;  // entries dropped, per cluster
-    size_t clusterCapacity = 0;          // clusters the buffers hold
-    uint32_t clusterDims[3] = {};        // of the last clustering
-    uint16_t *iblIrradiance = nullptr; // prosper_pt_generate_ibl: kIblIrradianceTexels RGBA16F, bordered cube
-    uint16_t *iblRadiance = nullptr;   // kIblRadianceTexels RGBA16F, 10 bordered mips
-    uint32_t *iblLut = nullptr;        // kIblLutSize^2 R16G16 UNORM
-    hipEvent_t iblEvents[4] = {};      // around the three passes of the last generation
-    bool iblGenerated = false;         // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
-    uint32_t *toneLut = nullptr; // dim^3 R9G9B9E5 texels
+    ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
+    ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
-    void *toneScratch = nullptr; // RGBA8 output when the caller only wants a host copy
-    size_t toneScratchBytes = 0;
+    ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
     // workspace, the stack-overflow array and the two launch chains (pt_kernels.hpp WavefrontChains) with their
@@ -350,10 +370,8 @@ struct prosper_pt_ctx
     // the per-frame descriptor sets play in RtReference::record; everything else uses slot 0.
     struct RenderSlot
     {
-        int32_t *stackOverflow = nullptr;
-        size_t stackOverflowBytes = 0;
-        void *wfBlock = nullptr;
-        size_t wfBytes = 0;
+        ppt::DeviceBuffer stackOverflow;
+        ppt::DeviceBuffer wfBlock;
         hipEvent_t chainJoin[ppt::kMaxChains] = {};
         hipEvent_t chainEvents[ppt::kMaxChains][kMaxTimedLaunches + 1] = {};
         uint32_t chainStage[ppt::kMaxChains][kMaxTimedLaunches] = {};

@@ -1,0 +1,714 @@
+// pt_gbuffer_passes.cpp — C-ABI of the passes over a G-buffer (include/prosper_pt/prosper_pt.h): ReSTIR-DI
+// (prosper_pt_restir_di_*), the ray-traced G-buffer (prosper_pt_trace_gbuffer), clustered lighting and deferred shading
+// (prosper_pt_cluster_lights, prosper_pt_deferred_shading) and image-based lighting (prosper_pt_generate_ibl), with the
+// readbacks of what each produced.  Kernels: pt_gbuffer_kernels.hip, pt_ibl.hip.
+#include "../../include/prosper_pt/prosper_pt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "pt_context.hpp"
+#include "pt_gbuffer_kernels.hpp"
+#include "pt_kernels.hpp"
+#include "pt_pass_support.hpp"
+
+using namespace ppt;
+
+namespace ppt
+{
+
+struct GBufferPassState
+{
+    DeviceBuffer hostInputs; // device copies of a call's host G-buffer inputs (and reservoirs): 16 + 16 + 8 + 4 bytes per pixel
+    DeviceBuffer reservoirs[2]; // ping-pong reservoir buffers of the ReSTIR-DI passes (width*height float2 each)
+    const void *lastReservoirs = nullptr; // prosper_pt_get_restir_reservoirs_device_ptr
+    size_t lastReservoirBytes = 0;
+    DeviceBuffer gbuffer; // context-owned G-buffer targets (prosper_pt_trace_gbuffer): 16 + 16 + 4 bytes per pixel
+    prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
+    uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
+    DeviceBuffer clusterPointers; // prosper_pt_cluster_lights: uint2 per cluster
+    DeviceBuffer clusterIndices;  // kClusterSlot uint16 entries per cluster
+    DeviceBuffer clusterDropped;  // entries dropped, per cluster
+    size_t clusterCapacity = 0;   // clusters the buffers hold
+    uint32_t clusterDims[3] = {}; // of the last clustering
+    DeviceBuffer iblIrradiance; // prosper_pt_generate_ibl: kIblIrradianceTexels RGBA16F, bordered cube
+    DeviceBuffer iblRadiance;   // kIblRadianceTexels RGBA16F, 10 bordered mips
+    DeviceBuffer iblLut;        // kIblLutSize^2 R16G16 UNORM
+    hipEvent_t iblEvents[4] = {}; // around the three passes of the last generation
+    bool iblGenerated = false;    // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
+    ~GBufferPassState()
+    {
+        for (hipEvent_t e : iblEvents)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+bool create_gbuffer_passes(prosper_pt_ctx *ctx)
+{
+    ctx->gbufferPasses = new (std::nothrow) GBufferPassState();
+    return ctx->gbufferPasses != nullptr;
+}
+
+void destroy_gbuffer_passes(prosper_pt_ctx *ctx)
+{
+    delete ctx->gbufferPasses;
+    ctx->gbufferPasses = nullptr;
+}
+
+void forget_ibl_maps(prosper_pt_ctx *ctx)
+{
+    ctx->gbufferPasses->iblGenerated = false;
+}
+
+} // namespace ppt
+
+namespace
+{
+
+// The camera terms a pass needs to rebuild a G-buffer texel's surface (RestirCamera)
+RestirCamera gbuffer_camera(const prosper_CameraUniforms *camera)
+{
+    RestirCamera c;
+    c.eye[0] = camera->eye.x;
+    c.eye[1] = camera->eye.y;
+    c.eye[2] = camera->eye.z;
+    std::memcpy(c.clipToWorld, &camera->clipToWorld, 64);
+    float c2c[16];
+    std::memcpy(c2c, &camera->cameraToClip, 64);
+    c.cameraToClip22 = c2c[2 * 4 + 2]; // column 2, row 2
+    c.cameraToClip32 = c2c[3 * 4 + 2]; // column 3, row 2
+    return c;
+}
+
+// The G-buffer (and, with `withReservoirs`, the reservoirs) on the device: host inputs are copied into hostInputs,
+// 16 + 16 + 8 + 4 bytes per pixel.
+struct DeviceGBuffer
+{
+    const void *ar, *nm, *res;
+    const float *depth;
+};
+int device_gbuffer(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_inputs *in, size_t pixels, bool withReservoirs, hipStream_t s,
+    DeviceGBuffer &out)
+{
+    out.ar = in->albedoRoughness;
+    out.nm = in->normalMetallic;
+    out.res = in->reservoirs;
+    out.depth = in->nonLinearDepth;
+    if (in->onDevice) return PROSPER_PT_OK;
+    DeviceBuffer &scratch = ctx->gbufferPasses->hostInputs;
+    const size_t need = pixels * 44u + 64u;
+    if (scratch.bytes < need)
+    {
+        const int rc = grow_buffer(scratch, GrowWait::Stream, s, need, need);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    uint8_t *base = scratch.as<uint8_t>();
+    PPT_HIP(hipMemcpyAsync(base, in->albedoRoughness, pixels * 16u, hipMemcpyHostToDevice, s));
+    PPT_HIP(hipMemcpyAsync(base + pixels * 16u, in->normalMetallic, pixels * 16u, hipMemcpyHostToDevice, s));
+    if (withReservoirs) PPT_HIP(hipMemcpyAsync(base + pixels * 32u, in->reservoirs, pixels * 8u, hipMemcpyHostToDevice, s));
+    PPT_HIP(hipMemcpyAsync(base + pixels * 40u, in->nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
+    out.ar = base;
+    out.nm = base + pixels * 16u;
+    out.res = base + pixels * 32u;
+    out.depth = reinterpret_cast<const float *>(base + pixels * 40u);
+    return PROSPER_PT_OK;
+}
+
+// The two context-owned reservoir buffers, grown like hostInputs (what still reads them on `s` finishes first).
+int restir_reservoir_buffers(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t need = pixels * 8u;
+    if (st.reservoirs[0].bytes >= need && st.reservoirs[1].bytes >= need) return PROSPER_PT_OK;
+    st.lastReservoirs = nullptr;
+    st.lastReservoirBytes = 0;
+    for (DeviceBuffer &r : st.reservoirs)
+    {
+        const int rc = grow_buffer(r, GrowWait::Stream, s, need, need);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    return PROSPER_PT_OK;
+}
+
+// The trace pass over device inputs: the HDR image, the traversal stacks, the launch.
+int restir_trace(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const DeviceGBuffer &in, hipStream_t s)
+{
+    const int hrc = prepare_hdr(ctx, width, height, nullptr, s);
+    if (hrc != PROSPER_PT_OK) return hrc;
+
+    int32_t *ovf = nullptr;
+    const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
+    if (orc != PROSPER_PT_OK) return orc;
+    wait_for_slot(ctx->slots[0], s);
+    launch_restir_di_trace(
+        ctx->scene, pc->drawType, pc->frameIndex, pc->flags, width, height, gbuffer_camera(camera), in.ar, in.nm, in.depth,
+        in.res, ctx->hdr, ovf, s);
+    release_slot(ctx->slots[0], s);
+    PPT_HIP(hipGetLastError());
+    return PROSPER_PT_OK;
+}
+
+// The context-owned targets, one allocation of 16 + 16 + 4 bytes per pixel, grown like hostInputs.
+int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, prosper_pt_gbuffer_targets &out)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t need = pixels * 36u + 64u;
+    if (st.gbuffer.bytes < need || !st.gbuffer.ptr)
+    {
+        if (st.gbufferLast.albedoRoughness == st.gbuffer.ptr)
+        {
+            st.gbufferLast = prosper_pt_gbuffer_targets{};
+            st.gbufferLastWidth = st.gbufferLastHeight = 0;
+        }
+        const int rc = grow_buffer(st.gbuffer, GrowWait::Stream, s, need, need);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    uint8_t *base = st.gbuffer.as<uint8_t>();
+    out.albedoRoughness = base;
+    out.normalMetallic = base + pixels * 16u;
+    out.nonLinearDepth = reinterpret_cast<float *>(base + pixels * 32u);
+    return PROSPER_PT_OK;
+}
+
+// The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.
+int gbuffer_trace(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s)
+{
+    GBufferTraceParams g = {};
+    set_camera_ray_params(g.r, camera);
+    g.r.width = width;
+    g.r.height = height;
+    g.r.localWidth = width;
+    g.r.stripeCount = 1;
+    g.r.frameCount = 1;
+    // worldToClip = cameraToClip * worldToCamera (column-major), in double, rounded once
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r)
+        {
+            double v = 0.0;
+            for (int k = 0; k < 4; ++k)
+                v += (double)(&camera->cameraToClip.col[k].x)[r] * (double)(&camera->worldToCamera.col[c].x)[k];
+            g.worldToClip[c * 4 + r] = (float)v;
+        }
+    g.drawType = drawType;
+    g.frameIndex = frameIndex;
+    g.jitter = jitter ? 1u : 0u;
+
+    int32_t *ovf = nullptr;
+    const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
+    if (orc != PROSPER_PT_OK) return orc;
+    wait_for_slot(ctx->slots[0], s);
+    launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+    release_slot(ctx->slots[0], s);
+    PPT_HIP(hipGetLastError());
+    GBufferPassState &st = *ctx->gbufferPasses;
+    st.gbufferLast = t;
+    st.gbufferLastWidth = width;
+    st.gbufferLastHeight = height;
+    return PROSPER_PT_OK;
+}
+
+// The G-buffer a record or shading call reads on `s`: traced first into the context-owned targets (`traced`; never the
+// hostInputs a host-input call fills), or the caller's, copied to the device when it is on the host.
+int call_gbuffer(
+    prosper_pt_ctx *ctx, bool traced, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, hipStream_t s, DeviceGBuffer &out)
+{
+    const size_t pixels = (size_t)width * height;
+    if (!traced) return device_gbuffer(ctx, gbuffer, pixels, false, s, out);
+    prosper_pt_gbuffer_targets t = {};
+    int rc = gbuffer_owned_targets(ctx, pixels, s, t);
+    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, jitter, camera, width, height, t, s);
+    out.ar = t.albedoRoughness;
+    out.nm = t.normalMetallic;
+    out.depth = t.nonLinearDepth;
+    out.res = nullptr;
+    return rc;
+}
+
+ClusterParams cluster_params(const prosper_CameraUniforms *camera, uint32_t width, uint32_t height)
+{
+    ClusterParams c;
+    std::memcpy(c.worldToCamera, &camera->worldToCamera, 64);
+    float c2c[16];
+    std::memcpy(c2c, &camera->cameraToClip, 64);
+    c.cameraToClip00 = c2c[0];
+    c.cameraToClip11 = c2c[1 * 4 + 1];
+    c.resolution[0] = (float)camera->resolution[0];
+    c.resolution[1] = (float)camera->resolution[1];
+    c.near_ = camera->near_;
+    c.far_ = camera->far_;
+    c.dimX = (width + kClusterDim - 1u) / kClusterDim;
+    c.dimY = (height + kClusterDim - 1u) / kClusterDim;
+    return c;
+}
+
+// The clustering pass on `s` after flush_scene_updates: buffers grown as needed (the index buffer starts as 0xFFFF), the
+// launch.  Every cluster writes its pointer and dropped count, so nothing is cleared (LightClustering.cpp's fillBuffer
+// of the counter is replaced by summing the pointers' counts in prosper_pt_read_light_clusters).
+int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t clusters = (size_t)c.dimX * c.dimY * (kClusterZSlices + 1u);
+    if (st.clusterCapacity < clusters || !st.clusterPointers.ptr)
+    {
+        st.clusterCapacity = 0;
+        st.clusterDims[0] = st.clusterDims[1] = st.clusterDims[2] = 0;
+        int rc = grow_buffer(st.clusterPointers, GrowWait::Stream, s, clusters * 8u, clusters * 8u);
+        if (rc == PROSPER_PT_OK)
+            rc = grow_buffer(st.clusterIndices, GrowWait::Stream, s, clusters * kClusterSlot * 2u, clusters * kClusterSlot * 2u, 0xFF);
+        if (rc == PROSPER_PT_OK) rc = grow_buffer(st.clusterDropped, GrowWait::Stream, s, clusters * 4u, clusters * 4u);
+        if (rc != PROSPER_PT_OK) return rc;
+        st.clusterCapacity = clusters;
+    }
+    launch_light_clustering(
+        ctx->scene, c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), st.clusterDropped.as<uint32_t>(), s);
+    PPT_HIP(hipGetLastError());
+    st.clusterDims[0] = c.dimX;
+    st.clusterDims[1] = c.dimY;
+    st.clusterDims[2] = kClusterZSlices + 1u;
+    return PROSPER_PT_OK;
+}
+
+// near_ and far_ feed log(far / near) and pow(far / near, s): both positive and ordered
+bool cluster_camera_ok(const prosper_CameraUniforms *camera)
+{
+    return camera->near_ > 0.0f && camera->far_ > camera->near_ && camera->resolution[0] > 0 && camera->resolution[1] > 0;
+}
+
+// The interior texels of `levels` bordered cubes (6 faces of (n + 2)^2 RGBA16F each, n halving per level) to host
+void strip_cube_borders(const std::vector<uint16_t> &bordered, uint32_t n, uint32_t levels, uint16_t *out)
+{
+    size_t src = 0;
+    for (uint32_t m = 0; m < levels; ++m, n >>= 1)
+    {
+        const size_t n2 = n + 2u;
+        for (uint32_t face = 0; face < 6u; ++face)
+            for (uint32_t j = 0; j < n; ++j)
+            {
+                std::memcpy(out, &bordered[4u * (src + ((size_t)face * n2 + j + 1u) * n2 + 1u)], (size_t)n * 8u);
+                out += 4u * (size_t)n;
+            }
+        src += 6u * n2 * n2;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- ReSTIR-DI (src/render/rtdi/RtDirectIllumination.cpp:70-115) ----
+
+int prosper_pt_restir_di_trace(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const prosper_pt_restir_inputs *in, void *stream)
+{
+    if (!ctx || !pc || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth || !in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: null argument");
+    const int crc = check_scene(ctx, "prosper_pt_restir_di_trace");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    DeviceGBuffer din;
+    rc = device_gbuffer(ctx, in, (size_t)width * height, true, s, din);
+    if (rc == PROSPER_PT_OK) rc = restir_trace(ctx, pc, camera, width, height, din, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_restir_di_resample(
+    prosper_pt_ctx *ctx, uint32_t stage, uint32_t frameIndex, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, const prosper_pt_restir_inputs *in, void *device_out_reservoirs, void *stream)
+{
+    if (!ctx || !camera || !in || !in->albedoRoughness || !in->normalMetallic || !in->nonLinearDepth)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: null argument");
+    if (stage != PROSPER_PT_RESTIR_INITIAL && stage != PROSPER_PT_RESTIR_SPATIAL)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: unknown stage");
+    const bool spatial = stage == PROSPER_PT_RESTIR_SPATIAL;
+    if (spatial && !in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass needs input reservoirs");
+    if (device_out_reservoirs && (reinterpret_cast<uintptr_t>(device_out_reservoirs) & 7u))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: output reservoirs must be 8-byte aligned");
+    if (spatial && in->onDevice && device_out_reservoirs == in->reservoirs)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: the spatial pass cannot write its input");
+    const int crc = check_scene(ctx, "prosper_pt_restir_di_resample");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: empty extent");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pixels = (size_t)width * height;
+    int rc = flush_scene_updates(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    void *out = device_out_reservoirs;
+    if (!out)
+    {
+        rc = restir_reservoir_buffers(ctx, pixels, s);
+        if (rc != PROSPER_PT_OK) return rc;
+        // the spatial pass writes the buffer it does not read
+        out = spatial && in->onDevice && in->reservoirs == st.reservoirs[1].ptr ? st.reservoirs[0].ptr
+                                                                                : st.reservoirs[spatial ? 1 : 0].ptr;
+    }
+    DeviceGBuffer din;
+    rc = device_gbuffer(ctx, in, pixels, spatial, s, din);
+    if (rc != PROSPER_PT_OK) return rc;
+    const RestirCamera cam = gbuffer_camera(camera);
+    if (spatial)
+        launch_restir_di_spatial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, din.res, out, s);
+    else
+        launch_restir_di_initial(ctx->scene, frameIndex, width, height, cam, din.ar, din.nm, din.depth, out, s);
+    PPT_HIP(hipGetLastError());
+    if (!device_out_reservoirs)
+    {
+        st.lastReservoirs = out;
+        st.lastReservoirBytes = pixels * 8u;
+    }
+    return mark_versions_read(ctx, s);
+}
+
+// ---- ray-traced G-buffer (the ReSTIR-DI passes' input; a stand-in for src/render/GBufferRenderer.cpp) ----
+
+int prosper_pt_trace_gbuffer(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_JITTER)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: unknown flags");
+    if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: empty extent");
+    if (!ctx || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null argument");
+    if (targets)
+    {
+        if (!targets->albedoRoughness || !targets->normalMetallic || !targets->nonLinearDepth)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: null target");
+        if ((reinterpret_cast<uintptr_t>(targets->albedoRoughness) | reinterpret_cast<uintptr_t>(targets->normalMetallic) |
+             reinterpret_cast<uintptr_t>(targets->nonLinearDepth)) & 15u)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: targets must be 16-byte aligned");
+    }
+    const int crc = check_scene(ctx, "prosper_pt_trace_gbuffer");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s);
+    prosper_pt_gbuffer_targets t = {};
+    if (rc == PROSPER_PT_OK)
+    {
+        if (targets)
+            t = *targets;
+        else
+            rc = gbuffer_owned_targets(ctx, (size_t)width * height, s, t);
+    }
+    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gbuffer_device_ptrs: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    *out = prosper_pt_restir_inputs{};
+    out->albedoRoughness = st.gbufferLast.albedoRoughness;
+    out->normalMetallic = st.gbufferLast.normalMetallic;
+    out->nonLinearDepth = st.gbufferLast.nonLinearDepth;
+    out->onDevice = 1;
+    if (width) *width = st.gbufferLastWidth;
+    if (height) *height = st.gbufferLastHeight;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_gbuffer(
+    prosper_pt_ctx *ctx, float *host_albedo_roughness, float *host_normal_metallic, float *host_depth, size_t pixels,
+    void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    if (pixels != (size_t)st.gbufferLastWidth * st.gbufferLastHeight)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: pixel count differs from the G-buffer's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const prosper_pt_gbuffer_targets &t = st.gbufferLast;
+    if (host_albedo_roughness)
+        PPT_HIP(hipMemcpyAsync(host_albedo_roughness, t.albedoRoughness, pixels * 16u, hipMemcpyDeviceToHost, s));
+    if (host_normal_metallic)
+        PPT_HIP(hipMemcpyAsync(host_normal_metallic, t.normalMetallic, pixels * 16u, hipMemcpyDeviceToHost, s));
+    if (host_depth) PPT_HIP(hipMemcpyAsync(host_depth, t.nonLinearDepth, pixels * 4u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_restir_di_record(
+    prosper_pt_ctx *ctx, const prosper_pt_restir_trace_pc *pc, uint32_t recordFlags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer, void *stream)
+{
+    if ((recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) && !(recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: JITTER_GBUFFER without TRACE_GBUFFER");
+    const bool traced = (recordFlags & PROSPER_PT_RESTIR_TRACE_GBUFFER) != 0;
+    if (!ctx || !pc || !camera ||
+        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: null argument");
+    if (recordFlags & ~(uint32_t)(PROSPER_PT_RESTIR_SPATIAL_REUSE | PROSPER_PT_RESTIR_TRACE_GBUFFER | PROSPER_PT_RESTIR_JITTER_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: unknown record flags");
+    const int crc = check_scene(ctx, "prosper_pt_restir_di_record");
+    if (crc != PROSPER_PT_OK) return crc;
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_record: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t pixels = (size_t)width * height;
+    int rc = flush_scene_updates(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = restir_reservoir_buffers(ctx, pixels, s);
+    DeviceGBuffer din;
+    if (rc == PROSPER_PT_OK)
+        rc = call_gbuffer(
+            ctx, traced, pc->drawType, pc->frameIndex, (recordFlags & PROSPER_PT_RESTIR_JITTER_GBUFFER) != 0, camera, width,
+            height, gbuffer, s, din);
+    if (rc != PROSPER_PT_OK) return rc;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const RestirCamera cam = gbuffer_camera(camera);
+    // InitialReservoirs, then SpatialReuse when the toggle is on, then Trace (RtDirectIllumination.cpp:80-109)
+    launch_restir_di_initial(
+        ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, st.reservoirs[0].ptr, s);
+    din.res = st.reservoirs[0].ptr;
+    if (recordFlags & PROSPER_PT_RESTIR_SPATIAL_REUSE)
+    {
+        launch_restir_di_spatial(
+            ctx->scene, pc->frameIndex, width, height, cam, din.ar, din.nm, din.depth, st.reservoirs[0].ptr,
+            st.reservoirs[1].ptr, s);
+        din.res = st.reservoirs[1].ptr;
+    }
+    PPT_HIP(hipGetLastError());
+    st.lastReservoirs = din.res;
+    st.lastReservoirBytes = pixels * 8u;
+    rc = restir_trace(ctx, pc, camera, width, height, din, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_restir_reservoirs_device_ptr(prosper_pt_ctx *ctx, void **out_ptr, size_t *out_bytes)
+{
+    if (!ctx || !out_ptr) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_restir_reservoirs_device_ptr: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.lastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
+    *out_ptr = const_cast<void *>(st.lastReservoirs);
+    if (out_bytes) *out_bytes = st.lastReservoirBytes;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, size_t byte_size, void *stream)
+{
+    if (!ctx || !host_float2) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.lastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
+    if (byte_size != st.lastReservoirBytes)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: size differs from the reservoirs'");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(host_float2, st.lastReservoirs, byte_size, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
+// ---- clustered lighting and deferred shading (src/render/LightClustering.cpp, src/render/DeferredShading.cpp) ----
+
+int prosper_pt_cluster_lights(
+    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (!camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: empty extent");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: camera needs 0 < near_ < far_ and a resolution");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_cluster_lights: null argument");
+    const int crc = check_scene(ctx, "prosper_pt_cluster_lights");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, cluster_params(camera, width, height), s);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_light_cluster_dims(prosper_pt_ctx *ctx, uint32_t *x, uint32_t *y, uint32_t *z)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_light_cluster_dims: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
+    if (x) *x = st.clusterDims[0];
+    if (y) *y = st.clusterDims[1];
+    if (z) *z = st.clusterDims[2];
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_light_clusters(
+    prosper_pt_ctx *ctx, uint32_t *host_pointers, uint16_t *host_indices, uint32_t *host_count, uint32_t *host_dropped,
+    uint32_t *host_overflowing, size_t clusters, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
+    if (clusters != (size_t)st.clusterDims[0] * st.clusterDims[1] * st.clusterDims[2])
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: cluster count differs from the last clustering's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<uint32_t> ptrs(clusters * 2u), dropped(clusters);
+    PPT_HIP(hipMemcpyAsync(ptrs.data(), st.clusterPointers.ptr, clusters * 8u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipMemcpyAsync(dropped.data(), st.clusterDropped.ptr, clusters * 4u, hipMemcpyDeviceToHost, s));
+    if (host_indices)
+        PPT_HIP(hipMemcpyAsync(host_indices, st.clusterIndices.ptr, clusters * kClusterSlot * 2u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    if (host_pointers) std::memcpy(host_pointers, ptrs.data(), clusters * 8u);
+    uint32_t count = 0, droppedSum = 0, overflowing = 0;
+    for (size_t k = 0; k < clusters; ++k)
+    {
+        count += (ptrs[2 * k + 1] >> 16) + (ptrs[2 * k + 1] & 0xFFFFu);
+        droppedSum += dropped[k];
+        overflowing += dropped[k] != 0u;
+    }
+    if (host_count) *host_count = count;
+    if (host_dropped) *host_dropped = droppedSum;
+    if (host_overflowing) *host_overflowing = overflowing;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_deferred_shading(
+    prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
+    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
+    void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (flags & ~(uint32_t)(PROSPER_PT_DEFERRED_TRACE_GBUFFER | PROSPER_PT_DEFERRED_JITTER_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: unknown flags");
+    if ((flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) && !(flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: JITTER_GBUFFER without TRACE_GBUFFER");
+    const bool traced = (flags & PROSPER_PT_DEFERRED_TRACE_GBUFFER) != 0;
+    if (!pc || !camera ||
+        (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: ibl is 0 or 1");
+    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: camera needs 0 < near_ < far_ and a resolution");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
+    const int crc = check_scene(ctx, "prosper_pt_deferred_shading");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s);
+    DeviceGBuffer din = {};
+    if (rc == PROSPER_PT_OK)
+        rc = call_gbuffer(
+            ctx, traced, pc->drawType, frameIndex, (flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) != 0, camera, width, height,
+            gbuffer, s, din);
+    const ClusterParams c = cluster_params(camera, width, height);
+    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, c, s);
+    if (rc == PROSPER_PT_OK) rc = prepare_hdr(ctx, width, height, nullptr, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (pc->ibl == 1u)
+        launch_deferred_shading_ibl(
+            ctx->scene, pc->drawType, width, height, gbuffer_camera(camera), c, din.ar, din.nm, din.depth,
+            st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), st.iblIrradiance.as<uint16_t>(),
+            st.iblRadiance.as<uint16_t>(), st.iblLut.as<uint32_t>(), ctx->hdr, s);
+    else
+        launch_deferred_shading(
+            ctx->scene, pc->drawType, width, height, gbuffer_camera(camera), c, din.ar, din.nm, din.depth,
+            st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ctx->hdr, s);
+    PPT_HIP(hipGetLastError());
+    return mark_versions_read(ctx, s);
+}
+
+// ---- image-based lighting (src/render/ImageBasedLighting.cpp) ----
+
+int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_generate_ibl: null argument");
+    const int crc = check_scene(ctx, "prosper_pt_generate_ibl");
+    if (crc != PROSPER_PT_OK) return crc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    // allocated once: the maps' sizes are fixed
+    auto allocate_once = [&](DeviceBuffer &b, size_t bytes) {
+        return b.ptr ? PROSPER_PT_OK : grow_buffer(b, GrowWait::None, s, bytes, bytes);
+    };
+    rc = allocate_once(st.iblIrradiance, kIblIrradianceTexels * 8u);
+    if (rc == PROSPER_PT_OK) rc = allocate_once(st.iblRadiance, kIblRadianceTexels * 8u);
+    if (rc == PROSPER_PT_OK) rc = allocate_once(st.iblLut, (size_t)kIblLutSize * kIblLutSize * 4u);
+    if (rc != PROSPER_PT_OK) return rc;
+    for (hipEvent_t &e : st.iblEvents)
+        if (!e) PPT_HIP(hipEventCreate(&e));
+    launch_ibl_generation(
+        ctx->scene, st.iblIrradiance.as<uint16_t>(), st.iblRadiance.as<uint16_t>(), st.iblLut.as<uint32_t>(), st.iblEvents, s);
+    PPT_HIP(hipGetLastError());
+    st.iblGenerated = true;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_ibl_info(prosper_pt_ctx *ctx, prosper_pt_ibl_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_ibl_info: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    prosper_pt_ibl_info info = {};
+    info.generated = st.iblGenerated ? 1u : 0u;
+    info.irradianceSize = kIblIrradianceSize;
+    info.radianceSize = kIblRadianceSize;
+    info.radianceMips = kIblRadianceMips;
+    info.lutSize = kIblLutSize;
+    if (st.iblEvents[3])
+    {
+        PPT_HIP(hipSetDevice(ctx->device));
+        PPT_HIP(hipEventSynchronize(st.iblEvents[3]));
+        PPT_HIP(hipEventElapsedTime(&info.irradianceMs, st.iblEvents[0], st.iblEvents[1]));
+        PPT_HIP(hipEventElapsedTime(&info.radianceMs, st.iblEvents[1], st.iblEvents[2]));
+        PPT_HIP(hipEventElapsedTime(&info.lutMs, st.iblEvents[2], st.iblEvents[3]));
+    }
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_ibl(
+    prosper_pt_ctx *ctx, uint16_t *irradiance_rgba16f, size_t irradiance_bytes, uint16_t *radiance_rgba16f,
+    size_t radiance_bytes, uint16_t *lut_rg16, size_t lut_bytes, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (irradiance_rgba16f && irradiance_bytes != 6u * kIblIrradianceSize * kIblIrradianceSize * 8u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: irradiance_bytes is not 6 x 64 x 64 RGBA16F");
+    size_t radianceTexels = 0;
+    for (uint32_t m = 0; m < kIblRadianceMips; ++m) radianceTexels += 6u * (size_t)(kIblRadianceSize >> m) * (kIblRadianceSize >> m);
+    if (radiance_rgba16f && radiance_bytes != radianceTexels * 8u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: radiance_bytes is not the 10 mips of 6 x 512 x 512 RGBA16F");
+    if (lut_rg16 && lut_bytes != (size_t)kIblLutSize * kIblLutSize * 4u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: lut_bytes is not 512 x 512 R16G16");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.iblGenerated) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_ibl: no maps were generated for the current scene (prosper_pt_generate_ibl)");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<uint16_t> irr(irradiance_rgba16f ? 4u * kIblIrradianceTexels : 0u);
+    std::vector<uint16_t> rad(radiance_rgba16f ? 4u * kIblRadianceTexels : 0u);
+    if (irradiance_rgba16f) PPT_HIP(hipMemcpyAsync(irr.data(), st.iblIrradiance.ptr, irr.size() * 2u, hipMemcpyDeviceToHost, s));
+    if (radiance_rgba16f) PPT_HIP(hipMemcpyAsync(rad.data(), st.iblRadiance.ptr, rad.size() * 2u, hipMemcpyDeviceToHost, s));
+    if (lut_rg16) PPT_HIP(hipMemcpyAsync(lut_rg16, st.iblLut.ptr, lut_bytes, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    if (irradiance_rgba16f) strip_cube_borders(irr, kIblIrradianceSize, 1u, irradiance_rgba16f);
+    if (radiance_rgba16f) strip_cube_borders(rad, kIblRadianceSize, kIblRadianceMips, radiance_rgba16f);
+    return PROSPER_PT_OK;
+}
+
+} // extern "C"

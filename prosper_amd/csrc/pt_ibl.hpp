@@ -1,5 +1,5 @@
 // pt_ibl.hpp — device functions shared by the image-based lighting passes (pt_ibl.hip: ImageBasedLighting's generation
-// kernels) and their reader (pt_kernels.hip: deferred_shading_ibl_kernel, scene/skybox.glsl evalIBL).
+// kernels) and their reader (pt_gbuffer_kernels.hip: deferred_shading_ibl_kernel, scene/skybox.glsl evalIBL).
 //
 // Every map is a cube stored as the sky is (DeviceScene::skybox): 6 faces +X, -X, +Y, -Y, +Z, -Z of (n + 2) x (n + 2)
 // RGBA16F texels, the one-texel border holding the texels the seamless-edge rule finds on the neighbouring face, so a
@@ -7,7 +7,7 @@
 #pragma once
 
 #include "pt_device.hpp"
-#include "pt_kernels.hpp"
+#include "pt_gbuffer_kernels.hpp"
 
 namespace ppt
 {

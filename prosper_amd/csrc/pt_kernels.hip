@@ -5,17 +5,14 @@
 //   render_megakernel   one lane per pixel runs whole paths (rt/reference/main.rgen:225-299)
 //   blit_rgba16f        RGBA32F -> RGBA16F (src/render/RtReference.cpp:339-377)
 //   eval_fn             device self-test entry (prosper_pt_eval_device_fn)
-//   restir_di_*         ReSTIR-DI initial reservoirs, spatial reuse and trace over a G-buffer
-//   gbuffer_trace       the ray-traced G-buffer those passes read
-//   light_clustering    per-cluster point / spot light lists (LightClustering)
-//   deferred_shading    unshadowed shading of the G-buffer over those lists (DeferredShading), with evalIBL over the
-//                       maps of pt_ibl.hip in its _ibl variant
+//
+// The kernels of the passes over a G-buffer (ReSTIR-DI, the traced G-buffer, clustering, deferred shading) are in
+// pt_gbuffer_kernels.hip.
 #include "pt_kernels.hpp"
 
 #include "bvh_encode.hpp"
 #include "pt_bc7.hpp"
 #include "pt_device.hpp"
-#include "pt_ibl.hpp"
 #include "pt_render_common.hpp"
 
 namespace ppt
@@ -461,683 +458,6 @@ void launch_blit_rgba16f(const float4 *in, void *out, uint32_t count, hipStream_
     if (count == 0) return;
     hipLaunchKernelGGL(
         blit_rgba16f_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, in, static_cast<uint2 *>(out), count);
-}
-
-// ------------------------------------------------------------------------------------------
-// ReSTIR-DI (src/render/rtdi/RtDirectIllumination.cpp:70-115): three passes over the G-buffer, one lane per pixel,
-// 256-lane blocks over 16x16 tiles (a wave per 8x8 quarter) dealt to the XCDs in contiguous bands (restir_tile).
-//   restir_di_initial_kernel   RIS over 5 uniformly drawn lights      (restir_di/initial_reservoirs.comp)
-//   restir_di_spatial_kernel   resamples 5 neighbour reservoirs        (restir_di/spatial_reuse.comp)
-//   restir_di_trace_kernel     the reservoir's light, one shadow ray   (rt/direct_illumination/main.rgen:44-165,
-//                              a second client of the traversal; src/render/rtdi/Trace.cpp:297)
-// ------------------------------------------------------------------------------------------
-
-// scene/material.glsl:20-32
-PPT_D f3 signed_oct_decode(f3 n)
-{
-    f3 o;
-    o.x = n.x - n.y;
-    o.y = (n.x + n.y) - 1.0f;
-    o.z = n.z * 2.0f - 1.0f;
-    o.z = o.z * ((1.0f - fabs_(o.x)) - fabs_(o.y));
-    return normalize(o);
-}
-
-struct RestirParams
-{
-    uint32_t drawType, frameIndex, flags, width, height;
-    float eye[3];
-    float clipToWorld[16]; // column-major
-    float cameraToClip22, cameraToClip32; // linearizeDepth (scene/camera.glsl:11-22)
-};
-
-// Block b and b + 8 run on the same XCD: the tiles [x * perXcd, (x + 1) * perXcd) go to XCD x, so the neighbours the
-// spatial pass reads mostly sit in the L2 of the XCD that reads them.  False past the last tile.
-PPT_D bool restir_pixel(uint32_t width, uint32_t height, uint32_t &px, uint32_t &py)
-{
-    const uint32_t tilesX = (width + 15u) / 16u, tilesY = (height + 15u) / 16u;
-    const uint32_t numTiles = tilesX * tilesY;
-    const uint32_t perXcd = (numTiles + 7u) / 8u;
-    const uint32_t tile = (blockIdx.x % 8u) * perXcd + (blockIdx.x / 8u);
-    if (tile >= numTiles) return false;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    px = (tile % tilesX) * 16u + (wave & 1u) * 8u + (lane & 7u);
-    py = (tile / tilesX) * 16u + (wave >> 1) * 8u + (lane >> 3);
-    return true;
-}
-PPT_D bool restir_pixel(const RestirParams &p, uint32_t &px, uint32_t &py) { return restir_pixel(p.width, p.height, px, py); }
-
-// scene/camera.glsl:11-22
-PPT_D float linearize_depth(const RestirParams &p, float nonLinearDepth)
-{
-    return -p.cameraToClip32 / (nonLinearDepth + p.cameraToClip22);
-}
-
-// The VisibleSurface of a G-buffer texel, as all three passes build it (main.rgen:113-129,
-// initial_reservoirs.comp:70-87, spatial_reuse.comp:145-162): uv = px / size (no half-pixel offset), worldPos through
-// clipToWorld, the signed-octahedral normal, alpha = -1.
-PPT_D Surface restir_surface(
-    const RestirParams &p, uint32_t px, uint32_t py, float depth, const float4 &ar, const float4 &nm)
-{
-    const f2 uv = f2{(float)px / (float)p.width, (float)py / (float)p.height};
-    Surface sf;
-    {
-        // worldPos, scene/camera.glsl:27-33
-        const float *m = p.clipToWorld;
-        const float x = uv.x * 2.0f - 1.0f, y = uv.y * 2.0f - 1.0f;
-        const float vx = __builtin_fmaf(m[8], depth, __builtin_fmaf(m[4], y, __builtin_fmaf(m[0], x, m[12])));
-        const float vy = __builtin_fmaf(m[9], depth, __builtin_fmaf(m[5], y, __builtin_fmaf(m[1], x, m[13])));
-        const float vz = __builtin_fmaf(m[10], depth, __builtin_fmaf(m[6], y, __builtin_fmaf(m[2], x, m[14])));
-        const float vw = __builtin_fmaf(m[11], depth, __builtin_fmaf(m[7], y, __builtin_fmaf(m[3], x, m[15])));
-        sf.positionWS = f3{vx, vy, vz} * (1.0f / vw);
-    }
-    sf.invViewRayWS = normalize(f3{p.eye[0], p.eye[1], p.eye[2]} - sf.positionWS);
-    sf.material.albedo = f3{ar.x, ar.y, ar.z};
-    sf.material.roughness = ar.w;
-    sf.material.normal = signed_oct_decode(f3{nm.x, nm.y, nm.w});
-    sf.material.metallic = nm.z;
-    sf.material.alpha = -1.0f;
-    sf.normalWS = sf.material.normal;
-    sf.uv = f2{0.0f, 0.0f};
-    sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
-    return sf;
-}
-
-// pHatLight, restir_di/resampling_phat.glsl: luminance (common/math.glsl:15) of the unshadowed contribution
-PPT_D float restir_p_hat(const DeviceScene &s, const Surface &sf, uint32_t lightIndex)
-{
-    f3 l, irradiance;
-    float d;
-    sample_light(s, sf.positionWS, lightIndex, l, d, irradiance);
-    return dot(f3{0.299f, 0.587f, 0.114f}, irradiance * eval_brdf_times_nol(l, sf));
-}
-
-// restir_di/reservoir.glsl packReservoir
-PPT_D float2 pack_reservoir(int32_t lightIndex, float weight)
-{
-    return make_float2(u2f((uint32_t)lightIndex), weight);
-}
-
-// initial_reservoirs.comp:31-60 initialLightCandidate.  The pHat of the pick is kept rather than evaluated again: the
-// same function of the same light, the same bits.
-__global__ __launch_bounds__(256) void restir_di_initial_kernel(
-    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
-    const float *__restrict__ nonLinearDepth, float2 *__restrict__ outReservoirs)
-{
-    uint32_t px, py;
-    if (!restir_pixel(p, px, py) || px >= p.width || py >= p.height) return;
-    const size_t i = (size_t)py * p.width + px;
-    const Surface sf = restir_surface(p, px, py, nonLinearDepth[i], albedoRoughness[i], normalMetallic[i]);
-    Rng rng{px, py, p.frameIndex}; // :72
-
-    const int32_t lightCount = 1 + (int32_t)(s.pointLightCount + s.spotLightCount);
-    int32_t chosen = -1;
-    float chosenPHat = 0.0f;
-    float sumResamplingWeights = 0.0f;
-    for (int k = 0; k < 5; ++k)
-    {
-        int32_t lightIndex = (int32_t)(rng.rnd01() * (float)lightCount);
-        lightIndex = lightIndex < lightCount - 1 ? lightIndex : lightCount - 1;
-        const float pHat = restir_p_hat(s, sf, (uint32_t)lightIndex);
-        // misWeight 1 / 5, unbiasedContributionWeight = lightCount
-        const float resamplingWeight = (0.2f * pHat) * (float)lightCount;
-        sumResamplingWeights += resamplingWeight;
-        if (rng.rnd01() < resamplingWeight / sumResamplingWeights)
-        {
-            chosen = lightIndex;
-            chosenPHat = pHat;
-        }
-    }
-    outReservoirs[i] = pack_reservoir(chosen, chosen >= 0 ? sumResamplingWeights / chosenPHat : 0.0f);
-}
-
-// spatial_reuse.comp:33-134 resampleReservoirSpatially.  The five slots are unrolled so that their reservoirs stay in
-// registers; every random number is drawn in the GLSL's order (all the disc offsets first, then the accept tests).
-__global__ __launch_bounds__(256) void restir_di_spatial_kernel(
-    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
-    const float *__restrict__ nonLinearDepth, const float2 *__restrict__ inReservoirs, float2 *__restrict__ outReservoirs)
-{
-    uint32_t px, py;
-    if (!restir_pixel(p, px, py) || px >= p.width || py >= p.height) return;
-    const size_t i = (size_t)py * p.width + px;
-    const float depth = nonLinearDepth[i];
-    const Surface sf = restir_surface(p, px, py, depth, albedoRoughness[i], normalMetallic[i]);
-    const float linearDepth = linearize_depth(p, depth);
-    Rng rng{px, py, p.frameIndex}; // :147, the same stream the initial pass of this frame started
-
-    int32_t sampleIndex[5];
-    float sampleWeight[5];
-    uint32_t validSampleCount = 0;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-    {
-        sampleIndex[k] = -1;
-        sampleWeight[k] = 0.0f;
-        for (int kill = 0; kill < 5; ++kill)
-        {
-            // uniformSampleDisk (common/sampling.glsl:8-13) * spatialRadius * 2 - spatialRadius, truncated
-            const f2 u = rng.rnd2d01();
-            const float r = sqrt_(u.x);
-            float sn, cs;
-            sincos_(kTwoPi * u.y, sn, cs);
-            const int32_t ox = (int32_t)(((r * cs) * 30.0f) * 2.0f - 30.0f);
-            const int32_t oy = (int32_t)(((r * sn) * 30.0f) * 2.0f - 30.0f);
-            const int32_t qx = (int32_t)px + ox, qy = (int32_t)py + oy;
-            if (qx <= 0 || qy <= 0 || qx >= (int32_t)p.width || qy >= (int32_t)p.height) continue;
-            const size_t q = (size_t)qy * p.width + (size_t)qx;
-            // 10 % depth difference (a NaN passes)
-            if (fabs_(1.0f - linearize_depth(p, nonLinearDepth[q]) / linearDepth) > 0.1f) continue;
-            const float4 nm = normalMetallic[q];
-            if (dot(signed_oct_decode(f3{nm.x, nm.y, nm.w}), sf.normalWS) < 0.9f) continue;
-            const float2 packed = inReservoirs[q];
-            sampleIndex[k] = (int32_t)f2u(packed.x);
-            sampleWeight[k] = packed.y;
-            validSampleCount++;
-            break;
-        }
-    }
-
-    int32_t chosen = -1;
-    float chosenPHat = 0.0f;
-    float sumResamplingWeights = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-    {
-        if (sampleIndex[k] < 0) continue;
-        const float pHat = restir_p_hat(s, sf, (uint32_t)sampleIndex[k]);
-        const float resamplingWeight = pHat * sampleWeight[k];
-        sumResamplingWeights += resamplingWeight;
-        if (rng.rnd01() < resamplingWeight / sumResamplingWeights)
-        {
-            chosen = sampleIndex[k];
-            chosenPHat = pHat;
-        }
-    }
-    float weight = 0.0f;
-    if (chosen >= 0)
-    {
-        const float misWeight = 1.0f / (float)validSampleCount;
-        weight = (misWeight * sumResamplingWeights) / chosenPHat;
-    }
-    outReservoirs[i] = pack_reservoir(chosen, weight);
-}
-
-__global__ __launch_bounds__(256) void restir_di_trace_kernel(
-    DeviceScene s, RestirParams p, const float4 *__restrict__ albedoRoughness, const float4 *__restrict__ normalMetallic,
-    const float *__restrict__ nonLinearDepth, const float2 *__restrict__ reservoirs, float4 *__restrict__ hdr,
-    int32_t *__restrict__ stackOverflow)
-{
-    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
-    uint32_t px, py;
-    if (!restir_pixel(p, px, py)) return;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
-                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
-    if (px >= p.width || py >= p.height) return;
-    const size_t i = (size_t)py * p.width + px;
-
-    // main.rgen:113-129
-    const Surface sf = restir_surface(p, px, py, nonLinearDepth[i], albedoRoughness[i], normalMetallic[i]);
-
-    if (p.drawType != PROSPER_DRAW_TYPE_DEFAULT)
-    {
-        const f3 c = p.drawType == PROSPER_DRAW_TYPE_POSITION ? sf.positionWS : sf.material.albedo;
-        hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
-        return;
-    }
-    // evaluateDirectLightingReSTIR, main.rgen:88-109
-    const float2 packed = reservoirs[i];
-    const int32_t lightIndex = (int32_t)f2u(packed.x);
-    f3 color = f3{0.0f, 0.0f, 0.0f};
-    if (!(sf.material.alpha == 0.0f || lightIndex < 0))
-    {
-        f3 l, irradiance;
-        float d;
-        sample_light(s, sf.positionWS, (uint32_t)lightIndex, l, d, irradiance);
-        if (dot(l, sf.normalWS) > 0.0f)
-        {
-            LaneCounters cnt = {};
-            Hit sh;
-            const bool occluded = trace<true, false>(s, sf.positionWS, l, 0.1f, d, pcg(px ^ py), stack, sh, cnt);
-            irradiance = irradiance * (occluded ? 0.0f : 1.0f);
-            color = (irradiance * eval_brdf_times_nol(l, sf)) * packed.y;
-        }
-    }
-    if ((p.flags & 1u) || !(p.flags & 2u))
-        hdr[i] = make_float4(color.x, color.y, color.z, 1.0f);
-    else
-    {
-        const float4 h = hdr[i];
-        const float count = h.w + 1.0f;
-        const float inv = 1.0f / count;
-        hdr[i] = make_float4(
-            __builtin_fmaf(color.x - h.x, inv, h.x), __builtin_fmaf(color.y - h.y, inv, h.y),
-            __builtin_fmaf(color.z - h.z, inv, h.z), count);
-    }
-}
-
-uint32_t restir_grid_blocks(uint32_t width, uint32_t height)
-{
-    const uint32_t numTiles = ((width + 15u) / 16u) * ((height + 15u) / 16u);
-    return ((numTiles + 7u) / 8u) * 8u;
-}
-
-static RestirParams restir_params(
-    uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height, const RestirCamera &cam)
-{
-    RestirParams p;
-    p.drawType = drawType;
-    p.frameIndex = frameIndex;
-    p.flags = flags;
-    p.width = width;
-    p.height = height;
-    for (int k = 0; k < 3; ++k) p.eye[k] = cam.eye[k];
-    for (int k = 0; k < 16; ++k) p.clipToWorld[k] = cam.clipToWorld[k];
-    p.cameraToClip22 = cam.cameraToClip22;
-    p.cameraToClip32 = cam.cameraToClip32;
-    return p;
-}
-
-void launch_restir_di_initial(
-    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, void *outReservoirs,
-    hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    hipLaunchKernelGGL(
-        restir_di_initial_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
-        restir_params(0, frameIndex, 0, width, height, cam), static_cast<const float4 *>(albedoRoughness),
-        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<float2 *>(outReservoirs));
-}
-
-void launch_restir_di_spatial(
-    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, const void *inReservoirs,
-    void *outReservoirs, hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    hipLaunchKernelGGL(
-        restir_di_spatial_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
-        restir_params(0, frameIndex, 0, width, height, cam), static_cast<const float4 *>(albedoRoughness),
-        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<const float2 *>(inReservoirs),
-        static_cast<float2 *>(outReservoirs));
-}
-
-void launch_restir_di_trace(
-    const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
-    const RestirCamera &cam, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    hipLaunchKernelGGL(
-        restir_di_trace_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s,
-        restir_params(drawType, frameIndex, flags, width, height, cam), static_cast<const float4 *>(albedoRoughness),
-        static_cast<const float4 *>(normalMetallic), nonLinearDepth, static_cast<const float2 *>(reservoirs), hdr,
-        stackOverflow);
-}
-
-// ------------------------------------------------------------------------------------------
-// Ray-traced G-buffer: the three targets of gbuffer.frag (albedoRoughness, normalMetallic, depth) from the path tracer's
-// primary hit, one lane per pixel on the ReSTIR passes' tile / XCD mapping.  The ray is trace_path's camera ray without
-// depth of field: the jittered sample of the pixel (main.rgen:229-231) or its centre.  The rng draws the jitter either
-// way, so the any-hit seed pcg(x ^ z) is the path tracer's in both modes.
-// ------------------------------------------------------------------------------------------
-
-// gbuffer.frag:41-58 signedOctEncode
-PPT_D f3 signed_oct_encode(f3 n)
-{
-    const float sum = (fabs_(n.x) + fabs_(n.y)) + fabs_(n.z);
-    const float x = n.x / sum, y = n.y / sum, z = n.z / sum;
-    f3 o;
-    o.y = y * 0.5f + 0.5f;
-    o.x = x * 0.5f + o.y;
-    o.y = x * -0.5f + o.y;
-    o.z = saturate(z * 3.40282e+38f);
-    return o;
-}
-
-__global__ __launch_bounds__(256) void gbuffer_trace_kernel(
-    DeviceScene s, GBufferTraceParams g, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
-    float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow)
-{
-    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
-    uint32_t px, py;
-    if (!restir_pixel(g.r.width, g.r.height, px, py)) return;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
-                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
-    if (px >= g.r.width || py >= g.r.height) return;
-    const size_t i = (size_t)py * g.r.width + px;
-
-    Rng rng{px, py, g.frameIndex};
-    const f2 j = rng.rnd2d01();
-    const f2 uv = g.jitter ? f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height}
-                           : f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
-    const Ray ray = pinhole_camera_ray(g.r, uv);
-    LaneCounters cnt = {};
-    Hit hit;
-    if (!trace<false, false>(s, ray.o, ray.d, ray.tMin, ray.tMax, pcg(rng.x ^ rng.z), stack, hit, cnt))
-    {
-        // the clear values of GBufferRenderer.cpp:487-516
-        albedoRoughness[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        nonLinearDepth[i] = 0.0f;
-        return;
-    }
-    const Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
-    if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT && g.drawType != PROSPER_DRAW_TYPE_MESHLET_ID)
-    {
-        // gbuffer.frag:83-99
-        const f3 c = debug_color(s, g.drawType, hit, sf);
-        albedoRoughness[i] = make_float4(c.x, c.y, c.z, 1.0f);
-        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    else
-    {
-        const f3 enc = signed_oct_encode(sf.normalWS);
-        albedoRoughness[i] = make_float4(sf.material.albedo.x, sf.material.albedo.y, sf.material.albedo.z, sf.material.roughness);
-        normalMetallic[i] = make_float4(enc.x, enc.y, sf.material.metallic, enc.z);
-    }
-    // posNDC.z of gbuffer.vert / gbuffer.frag: (worldToClip * (positionWS, 1)).z / .w
-    const float *m = g.worldToClip;
-    const f3 p = sf.positionWS;
-    const float cz = __builtin_fmaf(m[10], p.z, __builtin_fmaf(m[6], p.y, __builtin_fmaf(m[2], p.x, m[14])));
-    const float cw = __builtin_fmaf(m[11], p.z, __builtin_fmaf(m[7], p.y, __builtin_fmaf(m[3], p.x, m[15])));
-    nonLinearDepth[i] = cz / cw;
-}
-
-void launch_gbuffer_trace(
-    const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
-    int32_t *stackOverflow, hipStream_t stream)
-{
-    if (g.r.width == 0 || g.r.height == 0) return;
-    hipLaunchKernelGGL(
-        gbuffer_trace_kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
-        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow);
-}
-
-// ------------------------------------------------------------------------------------------
-// Clustered lighting (src/render/LightClustering.cpp, src/render/DeferredShading.cpp):
-//   light_clustering_kernel   one 256-lane block per cluster builds its point / spot lists (light_clustering.comp)
-//   deferred_shading_kernel   one lane per pixel shades the G-buffer texel over its cluster's lists
-//                             (deferred_shading.comp, scene/light_clusters.glsl), unshadowed
-// The three rules the GLSL leaves open: ascending light order in a list, the fixed slot
-// clusterLinearIndex * 256 of the index buffer, and the 128 lowest indices of each type kept on overflow.
-// ------------------------------------------------------------------------------------------
-
-static_assert(PROSPER_MAX_POINT_LIGHT_COUNT <= 256u * 32u, "a lane's share of the point lights must fit a 32-bit mask");
-
-// light_clustering.comp clusterFrustum: six planes (xyz, w), signedDistance = dot(xyz, p) - w
-struct ClusterFrustum
-{
-    f4 planes[6];
-};
-
-// scene/light_clusters.glsl sliceStart
-PPT_D float slice_start(const ClusterParams &c, uint32_t slice)
-{
-    const float sliceFrac = (float)slice / (float)kClusterZSlices;
-    return c.near_ * pow_(c.far_ / c.near_, sliceFrac);
-}
-
-PPT_D ClusterFrustum cluster_frustum(const ClusterParams &c, uint32_t cx, uint32_t cy, uint32_t cz)
-{
-    const float tileScaleX = c.resolution[0] / (float)(2u * kClusterDim);
-    const float tileScaleY = c.resolution[1] / (float)(2u * kClusterDim);
-    const float tileBiasX = tileScaleX - (float)cx, tileBiasY = tileScaleY - (float)cy;
-    // c1 = (m00 * sx, 0, -bx, 0), c2 = (0, m11 * sy, -by, 0), c4 = (0, 0, -1, 0); the projection's Y is already flipped
-    const float c1x = c.cameraToClip00 * tileScaleX, c1z = -tileBiasX;
-    const float c2y = c.cameraToClip11 * tileScaleY, c2z = -tileBiasY;
-    ClusterFrustum f;
-    f.planes[0] = f4{-c1x, 0.0f, -1.0f - c1z, 0.0f};
-    f.planes[1] = f4{c1x, 0.0f, -1.0f + c1z, 0.0f};
-    f.planes[2] = f4{0.0f, -c2y, -1.0f - c2z, 0.0f};
-    f.planes[3] = f4{0.0f, c2y, -1.0f + c2z, 0.0f};
-    f.planes[4] = f4{0.0f, 0.0f, -1.0f, cz == 0 ? 0.0f : slice_start(c, cz)};
-    f.planes[5] = f4{0.0f, 0.0f, 1.0f, -slice_start(c, cz + 1u)};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-        const f4 p = f.planes[i];
-        const float inv = 1.0f / sqrt_(__builtin_fmaf(p.z, p.z, __builtin_fmaf(p.y, p.y, p.x * p.x)));
-        f.planes[i] = f4{p.x * inv, p.y * inv, p.z * inv, p.w * inv};
-    }
-    return f;
-}
-
-// isPointVisible: the light's sphere (worldToCamera * position, radianceAndRadius.w) against the six planes
-PPT_D bool point_light_visible(const ClusterParams &c, const ClusterFrustum &f, const prosper_PointLight &light)
-{
-    const float *m = c.worldToCamera;
-    const prosper_vec4 q = light.position;
-    const float x = __builtin_fmaf(m[12], q.w, __builtin_fmaf(m[8], q.z, __builtin_fmaf(m[4], q.y, m[0] * q.x)));
-    const float y = __builtin_fmaf(m[13], q.w, __builtin_fmaf(m[9], q.z, __builtin_fmaf(m[5], q.y, m[1] * q.x)));
-    const float z = __builtin_fmaf(m[14], q.w, __builtin_fmaf(m[10], q.z, __builtin_fmaf(m[6], q.y, m[2] * q.x)));
-    const float r = light.radianceAndRadius.w;
-    bool visible = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-    {
-        const f4 p = f.planes[i];
-        visible = visible && __builtin_fmaf(p.z, z, __builtin_fmaf(p.y, y, p.x * x)) - p.w >= -r;
-    }
-    return visible;
-}
-
-__global__ __launch_bounds__(256) void light_clustering_kernel(
-    DeviceScene s, ClusterParams c, uint2 *__restrict__ pointers, uint16_t *__restrict__ indices,
-    uint32_t *__restrict__ dropped)
-{
-    __shared__ uint32_t waveTotals[4];
-    const uint32_t cx = blockIdx.x, cy = blockIdx.y, cz = blockIdx.z;
-    const uint32_t cluster = (cz * c.dimY + cy) * c.dimX + cx;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const ClusterFrustum f = cluster_frustum(c, cx, cy, cz);
-
-    // contiguous chunks of roundedUpQuotient(count, 256) lights per lane, as the GLSL splits them
-    const uint32_t totalPoints = s.pointLightCount;
-    const uint32_t perLane = (totalPoints + 255u) / 256u;
-    uint32_t mask = 0, count = 0;
-    for (uint32_t k = 0; k < perLane; ++k)
-    {
-        const uint32_t pi = tid * perLane + k;
-        if (pi >= totalPoints) break;
-        if (point_light_visible(c, f, s.pointLights->lights[pi]))
-        {
-            mask |= 1u << k;
-            ++count;
-        }
-    }
-    // block-wide exclusive prefix of the lanes' counts: lane order is light order, so the list is ascending
-    uint32_t inclusive = count;
-#pragma unroll
-    for (uint32_t off = 1; off < 64u; off <<= 1)
-    {
-        const uint32_t t = __shfl_up(inclusive, off, 64);
-        if (lane >= off) inclusive += t;
-    }
-    if (lane == 63u) waveTotals[wave] = inclusive;
-    __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < wave; ++w) base += waveTotals[w];
-    const uint32_t visiblePoints = (waveTotals[0] + waveTotals[1]) + (waveTotals[2] + waveTotals[3]);
-    const uint32_t keptPoints = visiblePoints < kClusterMaxPoints ? visiblePoints : kClusterMaxPoints;
-    // isSpotVisible is always true: every spot, the lowest kClusterMaxSpots of them
-    const uint32_t totalSpots = s.spotLightCount;
-    const uint32_t keptSpots = totalSpots < kClusterMaxSpots ? totalSpots : kClusterMaxSpots;
-    uint16_t *slot = indices + (size_t)cluster * kClusterSlot;
-
-    uint32_t pos = base + inclusive - count;
-    for (uint32_t k = 0; mask != 0u; ++k, mask >>= 1)
-    {
-        if (!(mask & 1u)) continue;
-        if (pos < kClusterMaxPoints) slot[pos] = (uint16_t)(tid * perLane + k);
-        ++pos;
-    }
-    for (uint32_t i = tid; i < keptSpots; i += 256u) slot[keptPoints + i] = (uint16_t)i;
-
-    if (tid == 0)
-    {
-        const uint32_t kept = keptPoints + keptSpots;
-        // packClusterPointer; an empty cluster's offset is 0, as the GLSL writes it
-        pointers[cluster] = make_uint2(kept > 0u ? cluster * kClusterSlot : 0u, (keptPoints << 16) | keptSpots);
-        // per cluster, not one global atomic counter: 34 680 clusters at 1920x1080 would serialise on its address
-        dropped[cluster] = (visiblePoints - keptPoints) + (totalSpots - keptSpots);
-    }
-}
-
-void launch_light_clustering(
-    const DeviceScene &s, const ClusterParams &c, void *pointers, uint16_t *indices, uint32_t *dropped, hipStream_t stream)
-{
-    if (c.dimX == 0 || c.dimY == 0) return;
-    hipLaunchKernelGGL(
-        light_clustering_kernel, dim3(c.dimX, c.dimY, kClusterZSlices + 1u), dim3(256), 0, stream, s, c,
-        static_cast<uint2 *>(pointers), indices, dropped);
-}
-
-// deferred_shading.comp: the G-buffer texel's VisibleSurface (restir_surface), the sun, then its cluster's point and
-// spot lists, each summed from zero and added in that order.  Debug draw types write the position or the G-buffer's
-// albedo without lighting (the GLSL's lighting of those texels is overwritten).
-struct DeferredParams
-{
-    RestirParams r;
-    float near_, far_;
-    uint32_t clustersX, clustersY;
-};
-
-// evalIBL (scene/skybox.glsl:48-83), as written: the split-sum specular over the prefiltered radiance and the BRDF LUT
-// plus the diffuse irradiance, without AO.
-PPT_D f3 eval_ibl(const IblMaps &m, const Surface &sf)
-{
-    const f3 f0 = fresnel_zero(sf);
-    const float NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
-    // schlickFresnelWithRoughness (brdf.glsl:28-31)
-    const float p = pow5(1.0f - NoV);
-    const float r1 = 1.0f - sf.material.roughness;
-    const f3 F = f3{__builtin_fmaf(fmax_(r1, f0.x) - f0.x, p, f0.x), __builtin_fmaf(fmax_(r1, f0.y) - f0.y, p, f0.y),
-                    __builtin_fmaf(fmax_(r1, f0.z) - f0.z, p, f0.z)};
-    const f3 kD = (f3{1.0f, 1.0f, 1.0f} - F) * (1.0f - sf.material.metallic);
-    const f3 diffuse = sample_cube_bordered(m.irradiance, kIblIrradianceSize, sf.normalWS) * sf.material.albedo;
-    const f3 R = reflect(-sf.invViewRayWS, sf.normalWS);
-    const f3 prefiltered = sample_radiance_trilinear(m.radiance, R, sf.material.roughness);
-    const f2 envBrdf = sample_brdf_lut(m.lut, NoV, sf.material.roughness);
-    const f3 specular = prefiltered * (F * envBrdf.x + f3{envBrdf.y, envBrdf.y, envBrdf.y});
-    return kD * diffuse + specular;
-}
-
-// The body of both shading kernels; IBL adds evalIBL after the spot lights (deferred_shading.comp:59-60).
-template <bool IBL>
-PPT_D void deferred_shade(
-    const DeviceScene &s, const DeferredParams &d, const float4 *__restrict__ albedoRoughness,
-    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
-    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, const IblMaps *ibl)
-{
-    uint32_t px, py;
-    if (!restir_pixel(d.r, px, py) || px >= d.r.width || py >= d.r.height) return;
-    const size_t i = (size_t)py * d.r.width + px;
-    const float depth = nonLinearDepth[i];
-    const Surface sf = restir_surface(d.r, px, py, depth, albedoRoughness[i], normalMetallic[i]);
-    if (d.r.drawType != PROSPER_DRAW_TYPE_DEFAULT)
-    {
-        const f3 c = d.r.drawType == PROSPER_DRAW_TYPE_POSITION ? sf.positionWS : sf.material.albedo;
-        hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
-        return;
-    }
-    const float linearDepth = linearize_depth(d.r, depth);
-
-    // evalDirectionalLight (scene/lighting.glsl:8-12)
-    const prosper_DirectionalLightParameters sun = *s.directionalLight;
-    const f3 sunL = -normalize(f3{sun.direction.x, sun.direction.y, sun.direction.z});
-    f3 color = f3{0.0f, 0.0f, 0.0f} + f3{sun.irradiance.x, sun.irradiance.y, sun.irradiance.z} * eval_brdf_times_nol(sunL, sf);
-
-    // clusterIndex: slice = uint(16 * log(-z / near) / log(far / near)); nearer than near (or NaN) is slice 0, past
-    // the last slice (16) a cluster without lights
-    const float ratio = -linearDepth / d.near_;
-    float slice = ratio > 0.0f ? ((float)kClusterZSlices * log2_(ratio)) / log2_(d.far_ / d.near_) : 0.0f;
-    if (!(slice >= 0.0f)) slice = 0.0f;
-    uint32_t offset = 0, pointCount = 0, spotCount = 0;
-    if (slice < (float)(kClusterZSlices + 1u))
-    {
-        const uint32_t cluster = ((uint32_t)slice * d.clustersY + py / kClusterDim) * d.clustersX + px / kClusterDim;
-        const uint2 packed = pointers[cluster];
-        offset = packed.x;
-        pointCount = packed.y >> 16;
-        spotCount = packed.y & 0xFFFFu;
-    }
-    f3 points = f3{0.0f, 0.0f, 0.0f};
-    for (uint32_t k = 0; k < pointCount; ++k)
-    {
-        f3 l, irradiance;
-        float dist;
-        eval_point_light(s.pointLights->lights[indices[offset + k]], sf.positionWS, l, dist, irradiance);
-        points = points + irradiance * eval_brdf_times_nol(l, sf);
-    }
-    color = color + points;
-    f3 spots = f3{0.0f, 0.0f, 0.0f};
-    for (uint32_t k = 0; k < spotCount; ++k)
-    {
-        f3 l, irradiance;
-        float dist;
-        eval_spot_light(s.spotLights->lights[indices[offset + pointCount + k]], sf.positionWS, l, dist, irradiance);
-        spots = spots + irradiance * eval_brdf_times_nol(l, sf);
-    }
-    color = color + spots;
-    if constexpr (IBL) color = color + eval_ibl(*ibl, sf);
-    hdr[i] = make_float4(color.x, color.y, color.z, 1.0f);
-}
-
-__global__ __launch_bounds__(256) void deferred_shading_kernel(
-    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
-    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
-    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr)
-{
-    deferred_shade<false>(s, d, albedoRoughness, normalMetallic, nonLinearDepth, pointers, indices, hdr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void deferred_shading_ibl_kernel(
-    DeviceScene s, DeferredParams d, const float4 *__restrict__ albedoRoughness,
-    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
-    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, IblMaps ibl)
-{
-    deferred_shade<true>(s, d, albedoRoughness, normalMetallic, nonLinearDepth, pointers, indices, hdr, &ibl);
-}
-
-void launch_deferred_shading(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    DeferredParams d;
-    d.r = restir_params(drawType, 0, 0, width, height, cam);
-    d.near_ = c.near_;
-    d.far_ = c.far_;
-    d.clustersX = c.dimX;
-    d.clustersY = c.dimY;
-    hipLaunchKernelGGL(
-        deferred_shading_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
-        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr);
-}
-
-void launch_deferred_shading_ibl(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
-    const uint32_t *lut, float4 *hdr, hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    DeferredParams d;
-    d.r = restir_params(drawType, 0, 0, width, height, cam);
-    d.near_ = c.near_;
-    d.far_ = c.far_;
-    d.clustersX = c.dimX;
-    d.clustersY = c.dimY;
-    const IblMaps maps = {irradiance, radiance, lut};
-    hipLaunchKernelGGL(
-        deferred_shading_ibl_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
-        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr, maps);
 }
 
 // ------------------------------------------------------------------------------------------

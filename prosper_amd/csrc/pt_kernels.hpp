@@ -55,92 +55,6 @@ void launch_build_alpha_bounds(
 void launch_srgb_monotonicity(uint32_t firstBits, uint32_t lastBits, uint32_t *out, hipStream_t stream);
 void launch_permute_triangles(
     const WorldTriangle *in, const uint32_t *permutation, WorldTriangle *out, uint32_t total, hipStream_t stream);
-// ReSTIR-DI: the camera terms the three passes read of CameraUniforms
-struct RestirCamera
-{
-    float eye[3];
-    float clipToWorld[16]; // column-major
-    float cameraToClip22, cameraToClip32;
-};
-uint32_t restir_grid_blocks(uint32_t width, uint32_t height);
-// reservoirs: width*height float2 (bits of the int light index, unbiasedContributionWeight)
-void launch_restir_di_initial(
-    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, void *outReservoirs,
-    hipStream_t stream);
-// `inReservoirs` and `outReservoirs` must not overlap (a pixel reads its neighbours' input)
-void launch_restir_di_spatial(
-    const DeviceScene &s, uint32_t frameIndex, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, const void *inReservoirs,
-    void *outReservoirs, hipStream_t stream);
-void launch_restir_di_trace(
-    const DeviceScene &s, uint32_t drawType, uint32_t frameIndex, uint32_t flags, uint32_t width, uint32_t height,
-    const RestirCamera &cam, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *reservoirs, float4 *hdr, int32_t *stackOverflow, hipStream_t stream);
-// Ray-traced G-buffer (gbuffer_trace_kernel): `r` carries the camera terms of pinhole_camera_ray and the extent, built as
-// prosper_pt_render_frames builds them (r.pc is not read); worldToClip = cameraToClip * worldToCamera, column-major.
-struct GBufferTraceParams
-{
-    RenderParams r;
-    float worldToClip[16];
-    uint32_t drawType, frameIndex, jitter;
-};
-// albedoRoughness, normalMetallic: r.width*r.height float4; nonLinearDepth: r.width*r.height float.  Grid of
-// restir_grid_blocks(r.width, r.height) blocks (the stack overflow array is sized for it).
-void launch_gbuffer_trace(
-    const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
-    int32_t *stackOverflow, hipStream_t stream);
-// Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
-// uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
-// [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the
-// kClusterMaxPoints / kClusterMaxSpots of a type.
-constexpr uint32_t kClusterDim = 32;       // LightClustering::clusterDim
-constexpr uint32_t kClusterZSlices = 16;   // LightClustering::zSlices
-constexpr uint32_t kClusterMaxPoints = 128; // maxPointIndicesPerTile
-constexpr uint32_t kClusterMaxSpots = 128;  // maxSpotIndicesPerTile
-constexpr uint32_t kClusterSlot = kClusterMaxPoints + kClusterMaxSpots;
-struct ClusterParams
-{
-    float worldToCamera[16]; // column-major
-    float cameraToClip00, cameraToClip11;
-    float resolution[2]; // camera.resolution, which the tile scale is built from (not the extent)
-    float near_, far_;
-    uint32_t dimX, dimY; // ceil(extent / kClusterDim)
-};
-void launch_light_clustering(
-    const DeviceScene &s, const ClusterParams &c, void *pointers, uint16_t *indices, uint32_t *dropped, hipStream_t stream);
-// One lane per pixel over restir_grid_blocks(width, height); reads the lists launch_light_clustering wrote with `c`.
-void launch_deferred_shading(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream);
-// Image-based lighting (ImageBasedLighting / evalIBL).  Every cube is stored with a one-texel seamless border, as the
-// sky is: 6 faces of (n + 2)^2 RGBA16F texels.  Radiance mip m (size kIblRadianceSize >> m) starts
-// ibl_radiance_offset(m) RGBA texels into its buffer; the LUT is kIblLutSize^2 R16G16 UNORM, row = roughness.
-constexpr uint32_t kIblIrradianceSize = 64; // SkyboxResources::sSkyboxIrradianceResolution
-constexpr uint32_t kIblRadianceSize = 512;  // sSkyboxRadianceResolution
-constexpr uint32_t kIblRadianceMips = 10;   // getMipCount(512)
-constexpr uint32_t kIblLutSize = 512;       // sSpecularBrdfLutResolution
-constexpr uint32_t kIblSamples = 1024;      // NumSamples of prefilter_radiance.comp and integrate_specular_brdf.comp
-__host__ __device__ constexpr size_t ibl_radiance_offset(uint32_t mip)
-{
-    size_t offset = 0;
-    for (uint32_t m = 0; m < mip; ++m)
-        offset += 6u * (size_t)((kIblRadianceSize >> m) + 2u) * ((kIblRadianceSize >> m) + 2u);
-    return offset;
-}
-constexpr size_t kIblIrradianceTexels = 6u * (size_t)(kIblIrradianceSize + 2u) * (kIblIrradianceSize + 2u);
-constexpr size_t kIblRadianceTexels = ibl_radiance_offset(kIblRadianceMips);
-// The three generation passes on `stream` from the scene's sky (a scene without one gives zero maps).  `events`
-// (optional, 4): recorded before the irradiance pass, the radiance pass, the LUT pass and after it.
-void launch_ibl_generation(
-    const DeviceScene &s, uint16_t *irradiance, uint16_t *radiance, uint32_t *lut, hipEvent_t *events, hipStream_t stream);
-// deferred shading with evalIBL after the spot lights (ibl = 1), over the maps launch_ibl_generation wrote
-void launch_deferred_shading_ibl(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
-    const uint32_t *lut, float4 *hdr, hipStream_t stream);
 void launch_tone_map(
     const float4 *hdr, const uint32_t *lut, uint32_t dim, float exposure, float contrast, void *outRgba8, uint32_t count,
     hipStream_t stream);

@@ -1,4 +1,4 @@
-// pt_render_common.hpp — helpers shared by the render kernels (pt_kernels.hip, pt_wavefront.hip).
+// pt_render_common.hpp — helpers shared by the render kernels (pt_kernels.hip, pt_wavefront.hip, pt_gbuffer_kernels.hip).
 #pragma once
 
 #include "pt_device.hpp"
