@@ -5,6 +5,7 @@
   prefilter(sky, mip, face, i, j)   res/shader/ibl/prefilter_radiance.comp at texels of mip `mip` (roughness mip / 10)
   brdf_lut(rows)                    res/shader/ibl/integrate_specular_brdf.comp, whole rows of the 512^2 LUT
   eval_ibl(sf, idx, maps)           scene/skybox.glsl evalIBL over read-back maps (Vulkan's trilinear rule)
+  switch_margin(d)                  how far a direction is from the cube's face switch (float32 may pick the other face)
 
 Everything is float64.  Two frame switches can go either way between float32 and float64 (the irradiance frame's
 |n.y| < 0.99 and the sampler's |N.z| < 0.999); for a texel direction within FLIP_EPS of one, the branch is the one
@@ -61,6 +62,14 @@ def face_coords(d):
     tc = np.where(zsel, -y, np.where(ysel, np.where(y < 0, -z, z), -y))
     ma = np.where(zsel, az, np.where(ysel, ay, ax))
     return face, sc, tc, ma
+
+
+def switch_margin(d):
+    """The relative difference of the two largest |components| of directions d [k, 3]: below ~1e-5 float32 and float64
+    may select different faces (the lookup is continuous there only as far as the two faces' texels agree)."""
+    a = np.sort(np.abs(d), axis=-1)
+    with np.errstate(all="ignore"):
+        return (a[..., 2] - a[..., 1]) / a[..., 2]
 
 
 def face_dir(face, sc, tc):
@@ -248,7 +257,8 @@ def sample_lut(lut, NoV, rough):
 
 
 def eval_ibl(sf, idx, maps):
-    """evalIBL for the pixels idx of restir_resampling_reference.Surfaces sf: float64 [k, 3], |terms| summed [k]."""
+    """evalIBL for the pixels idx of restir_resampling_reference.Surfaces sf: float64 [k, 3], |terms| summed [k], and
+    the smaller switch_margin of the two cube directions (the normal and the reflection vector) [k]."""
     n, v, albedo, rough, metal = sf.n[idx], sf.v[idx], sf.albedo[idx], sf.rough[idx], sf.metal[idx]
     m = metal[:, None]
     f0 = 0.04 * (1.0 - m) + albedo * m
@@ -260,4 +270,5 @@ def eval_ibl(sf, idx, maps):
     pref = sample_radiance(maps["radiance"], R, rough)
     env = sample_lut(maps["lut"], NoV, rough)
     spec = pref * (F * env[:, 0:1] + env[:, 1:2])
-    return kD * diffuse + spec, np.abs(kD * diffuse).sum(-1) + np.abs(spec).sum(-1)
+    margin = np.minimum(switch_margin(n), switch_margin(R))
+    return kD * diffuse + spec, np.abs(kD * diffuse).sum(-1) + np.abs(spec).sum(-1), margin

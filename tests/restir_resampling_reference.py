@@ -4,7 +4,8 @@ tests/test_restir_di_resampling.py:
   initial(...)   res/shader/restir_di/initial_reservoirs.comp:31-60  RIS over 5 uniformly drawn lights
   spatial(...)   res/shader/restir_di/spatial_reuse.comp:33-134      resampling of 5 neighbour reservoirs
 
-Both return (light index int32 [h, w], unbiasedContributionWeight float64 [h, w], margin float64 [h, w]).
+Both return (light index int32 [h, w], unbiasedContributionWeight float64 [h, w], margin float64 [h, w]); spatial also
+returns its neighbour lookups (which pixel looked at which, and whether the pair reached the normal test).
 
 Arithmetic.  The random numbers (pcg3d, rngTo01: common/random.glsl) and everything computed from them alone are
 restated bit for bit in uint32 / float32: the candidate index min(int(rnd01 * lightCount), lightCount - 1), the disc
@@ -178,8 +179,9 @@ class Surfaces:
             self.lin_depth = (-c2c[2, 3]) / (depth.ravel() + c2c[2, 2])  # float32, scene/camera.glsl:11-22
 
 
-def brdf_times_nol(sf, l, idx=slice(None)):
-    """evalBRDFTimesNoL (brdf.glsl:67-87) for the pixels `idx` of `sf` and directions l [n, 3]."""
+def brdf_parts(sf, l, idx=slice(None)):
+    """The terms of evalBRDFTimesNoL (brdf.glsl:67-87) for the pixels `idx` of `sf` and directions l [n, 3]: the diffuse
+    and the specular term (each times NoL) [n, 3], n.l [n], and trowbridgeReitz's denominator NoH^2 (a2 - 1) + 1 [n]."""
     n, v, albedo, rough, metal, NoV = sf.n[idx], sf.v[idx], sf.albedo[idx], sf.rough[idx], sf.metal[idx], sf.NoV[idx]
     with np.errstate(all="ignore"):
         hv = v + l
@@ -199,7 +201,14 @@ def brdf_times_nol(sf, l, idx=slice(None)):
         k = np.maximum(alpha * 0.5, 0.0001)
         G = NoL / (NoL * (1.0 - k) + k) * (NoV / (NoV * (1.0 - k) + k))
         spec = F * (D * G / (4.0 * NoL * NoV + 0.0001))[:, None]
-        return (cdiff / np.pi + spec) * NoL[:, None], np.abs(nl)
+        return (cdiff / np.pi) * NoL[:, None], spec * NoL[:, None], nl, den
+
+
+def brdf_times_nol(sf, l, idx=slice(None)):
+    """evalBRDFTimesNoL (brdf.glsl:67-87) for the pixels `idx` of `sf` and directions l [n, 3]."""
+    with np.errstate(all="ignore"):
+        diffuse, spec, nl, _ = brdf_parts(sf, l, idx)
+        return diffuse + spec, np.abs(nl)
 
 
 def light_contribution(sf, lights, index, idx=slice(None)):
@@ -261,8 +270,11 @@ def disc_offset(u0, u1, oracle):
     return np.trunc(ox).astype(np.int64), np.trunc(oy).astype(np.int64)
 
 
-def spatial(world, cam, ar, nm, depth, reservoirs, frame, oracle):
-    """spatial_reuse.comp for every pixel over the input `reservoirs` [h, w, 2] -> (index, W, margin)."""
+def spatial(world, cam, ar, nm, depth, reservoirs, frame, oracle, lookups=False):
+    """spatial_reuse.comp for every pixel over the input `reservoirs` [h, w, 2] -> (index, W, margin, lookups).
+    The fourth value is None unless `lookups` is set; then it is (p, q, tested): for every neighbour lookup inside the
+    image the flat indices of the pixel and of the neighbour, and whether the pair passed the depth test (`tested`: the
+    normal test was evaluated on it)."""
     sf = Surfaces(cam, ar, nm, depth)
     lights = Lights(world)
     rng = Rng(sf.px, sf.py, frame)
@@ -273,6 +285,7 @@ def spatial(world, cam, ar, nm, depth, reservoirs, frame, oracle):
     margin = np.full(npx, np.inf)
     slots_idx, slots_w = [], []
     valid = np.zeros(npx, np.int64)
+    look_p, look_q, look_t = [], [], []
     for _ in range(SAMPLE_COUNT):
         searching = np.ones(npx, bool)
         s_idx = np.full(npx, -1, np.int32)
@@ -287,6 +300,10 @@ def spatial(world, cam, ar, nm, depth, reservoirs, frame, oracle):
                 depth_ok = ~(np.abs(F32(1.0) - sf.lin_depth[q] / sf.lin_depth) > F32(0.1))  # float32; NaN passes
                 ndot = (sf.n[q] * sf.n).sum(-1)
             tested = inside & depth_ok
+            if lookups:
+                look_p.append(np.nonzero(inside)[0])
+                look_q.append(q[inside])
+                look_t.append(tested[inside])
             margin = np.where(tested, np.minimum(margin, np.abs(ndot - 0.9) / 0.9), margin)
             found = tested & ~(ndot < 0.9)
             s_idx = np.where(found, in_idx[q], s_idx)
@@ -314,4 +331,5 @@ def spatial(world, cam, ar, nm, depth, reservoirs, frame, oracle):
     with np.errstate(all="ignore"):
         W = np.where(chosen >= 0, (1.0 / np.maximum(valid, 1)) * total / chosen_ph, 0.0)
     margin = np.where(~(total > 0) & (chosen < 0), np.inf, margin)
-    return chosen.reshape(h, w), W.reshape(h, w), margin.reshape(h, w)
+    looked = (np.concatenate(look_p), np.concatenate(look_q), np.concatenate(look_t)) if lookups else None
+    return chosen.reshape(h, w), W.reshape(h, w), margin.reshape(h, w), looked

@@ -221,7 +221,7 @@ def test_gpu_known_answers_constant_and_missing_sky_and_determinism():
 
 
 def _ibl_check(got, sf, idx, maps, base, base_total, what):
-    ibl, ibl_total = I.eval_ibl(sf, idx, maps)
+    ibl, ibl_total, _ = I.eval_ibl(sf, idx, maps)
     want = base + ibl
     total = base_total + ibl_total
     g = got[..., :3].reshape(-1, 3)[idx].astype(np.float64)

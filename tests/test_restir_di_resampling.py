@@ -142,7 +142,7 @@ def test_gpu_resampling_passes_match_the_reference(gpu_ctx, oracle, scene):
         _check_against_reference(got, ref_i, ref_w, ref_m, lights)
         # the spatial pass is fed the REFERENCE's initial reservoirs: an error of one pass cannot hide in the other
         ref_res = pack(ref_i, ref_w)
-        sp_i, sp_w, sp_m = R.spatial(world, cam, ar, nm, depth, ref_res, frame, oracle)
+        sp_i, sp_w, sp_m, _ = R.spatial(world, cam, ar, nm, depth, ref_res, frame, oracle)
         got_sp = gpu_ctx.restir_di_resample(S.RESTIR_SPATIAL, frame, cam, ar, nm, depth, ref_res)
         _check_against_reference(got_sp, sp_i, sp_w, sp_m, lights)
         # every light the spatial pass picks is one its offsets can reach: the radius-60 disc around (-30, -30),
@@ -244,7 +244,7 @@ def test_gpu_light_count_change_reaches_every_stage(gpu_ctx, oracle):
             if not spatial:
                 _check_against_reference(res, ref_i, ref_w, ref_m, lights)
             else:  # (fed the GPU's initial reservoirs: a neighbour's undecided pick may differ)
-                sp_i, sp_w, sp_m = R.spatial(fewer, cam, ar, nm, depth, pack(ref_i, ref_w), 2, oracle)
+                sp_i, sp_w, sp_m, _ = R.spatial(fewer, cam, ar, nm, depth, pack(ref_i, ref_w), 2, oracle)
                 decided = sp_m >= 1e-4
                 assert decided.mean() >= 0.99 and (idx[decided] == sp_i[decided]).mean() >= 0.99
     finally:

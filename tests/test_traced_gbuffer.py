@@ -257,7 +257,7 @@ def test_gpu_record_from_the_traced_gbuffer(gpu_ctx, oracle, scene):
                     init = gpu_ctx.restir_di_resample(S.RESTIR_INITIAL, frame, cam, ar, nm, depth)
                     check_reservoirs(init, ref_i, ref_w, ref_m, hit)
                     ref_res = np.stack([ref_i.view(np.float32), ref_w.astype(np.float32)], axis=-1)
-                    sp_i, sp_w, sp_m = R.spatial(world, cam, ar, nm, depth, ref_res, frame, oracle)
+                    sp_i, sp_w, sp_m, _ = R.spatial(world, cam, ar, nm, depth, ref_res, frame, oracle)
                     decided = (sp_m >= 1e-4) & hit
                     assert decided.sum() >= 0.99 * hit.sum() and (idx[decided] == sp_i[decided]).mean() >= 0.99
     finally:
