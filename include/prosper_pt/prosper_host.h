@@ -144,6 +144,26 @@ void prosper_host_image_based_lighting_destroy(prosper_host_image_based_lighting
 int prosper_host_image_based_lighting_is_generated(prosper_host_image_based_lighting *pass);
 int prosper_host_image_based_lighting_record_generation(prosper_host_image_based_lighting *pass, void *stream);
 
+/* render::SkyboxRenderer (host/skybox_renderer.hpp; reference src/render/SkyboxRenderer.hpp) on a context the scene was
+ * uploaded to (borrowed): record = Camera::updateBuffer + prosper_pt_skybox_fill over the context's HDR image.
+ * `nonLinearDepth` NULL: the last traced G-buffer's depth. */
+typedef struct prosper_host_skybox_renderer prosper_host_skybox_renderer;
+int prosper_host_skybox_renderer_create(prosper_pt_ctx *ctx, prosper_host_skybox_renderer **out);
+void prosper_host_skybox_renderer_destroy(prosper_host_skybox_renderer *pass);
+int prosper_host_skybox_renderer_record(
+    prosper_host_skybox_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    const float *nonLinearDepth, uint32_t onDevice, void *stream);
+
+/* render::dof::DepthOfField (host/depth_of_field.hpp; reference src/render/dof/DepthOfField.hpp) on a context
+ * (borrowed): record = Camera::updateBuffer + prosper_pt_depth_of_field with the push constants computed from the
+ * camera's aperture, focus distance and focal length as dof/Setup.cpp and dof/Dilate.cpp compute them; returns them. */
+typedef struct prosper_host_depth_of_field prosper_host_depth_of_field;
+int prosper_host_depth_of_field_create(prosper_pt_ctx *ctx, prosper_host_depth_of_field **out);
+void prosper_host_depth_of_field_destroy(prosper_host_depth_of_field *pass);
+int prosper_host_depth_of_field_record(
+    prosper_host_depth_of_field *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    const prosper_pt_dof_inputs *inputs, void *stream, prosper_pt_dof_pc *outPushConstants);
+
 #ifdef __cplusplus
 }
 #endif

@@ -679,6 +679,104 @@ int prosper_pt_read_ibl(
     prosper_pt_ctx *ctx, uint16_t *irradiance_rgba16f, size_t irradiance_bytes, uint16_t *radiance_rgba16f,
     size_t radiance_bytes, uint16_t *lut_rg16, size_t lut_bytes, void *stream);
 
+/* ---- skybox fill and depth of field (src/render/SkyboxRenderer.cpp, src/render/dof/, res/shader/dof/) ----
+ * What prosper runs between the shaded G-buffer and the tone map: plain compute over the context's HDR
+ * image and a non-linear depth.  Additive: the ABI version stays 4.
+ *
+ * prosper_pt_skybox_fill: every texel whose nonLinearDepth is 0 (reverse-Z far plane, the traced G-buffer's miss
+ * value) gets (sky.rgb, 1) in the context's HDR image; every other texel is left bit for bit as it was.  The sky value
+ * is the path tracer's seamless bilinear lookup of mip 0 of the scene's sky, unclamped, in the direction of the
+ * G-buffer tracer's primary ray through the pixel centre (px + 0.5, py + 0.5); a cube lookup does not depend on the
+ * direction's length, so this is the interpolated cube position of skybox.vert.  A scene without a sky fills
+ * (0, 0, 0, 1).  No velocity output.  `nonLinearDepth`: width*height floats, on the device when `onDevice` is not 0;
+ * NULL means the last traced G-buffer's depth (refused when its extent differs).  The HDR image must be what a render,
+ * a ReSTIR trace or deferred shading produced at this extent.  Pending scene updates take effect first. */
+int prosper_pt_skybox_fill(
+    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const float *nonLinearDepth,
+    uint32_t onDevice, void *stream);
+
+/* The push-constant values of the depth-of-field passes as prosper computes them (Setup.cpp:163-177,
+ * Dilate.cpp:105-127); the host layer's DepthOfField derives them from the camera's aperture, focus distance and focal
+ * length.  Given as numbers, so that small images can have large circles. */
+typedef struct prosper_pt_dof_pc
+{
+    float focusDistance;    /* > 0 */
+    float maxBackgroundCoC; /* >= 0, half-resolution pixels: the circle of a surface infinitely far away */
+    float maxCoC;           /* >= 0: the foreground's circles are clamped to -maxCoC (2 x maxBackgroundCoC in prosper) */
+    int32_t gatherRadius;   /* >= 1, tiles: how far the dilation looks */
+} prosper_pt_dof_pc;
+typedef struct prosper_pt_dof_inputs
+{
+    const void *illumination;    /* width*height RGBA32F; NULL: the context's HDR image, processed in place */
+    const float *nonLinearDepth; /* width*height floats; NULL: the last traced G-buffer's depth (same extent) */
+    uint32_t onDevice;           /* 0: the given pointers are host memory */
+    uint32_t reserved;
+} prosper_pt_dof_inputs;
+/* render::dof::DepthOfField::record: seven compute passes over the illumination and the depth; the result is always
+ * the context's HDR image (prosper_pt_read_hdr, _blit_rgba16f and _tone_map read it), with the input's alpha.  With
+ * hw = ceil(width / 2), hh = ceil(height / 2) and tiles of 8 x 8 half-resolution texels, the context-owned
+ * intermediates (grown as needed) are, in prosper's formats, stored with round-to-nearest-even:
+ *   setup    half-resolution illumination RGBA16F (alpha 1) and circle of confusion R16F.  Each texel takes the four
+ *            full-resolution texels min(2c + {(0,1), (1,1), (1,0), (0,0)}, extent - 1) (the textureGather of the GLSL
+ *            is defined as exactly those); coc = max((1 - focusDistance / -viewZ) * maxBackgroundCoC, -maxCoC) with the
+ *            G-buffer passes' linearizeDepth; the stored CoC is the minimum of the four, the colour their mean with
+ *            weights saturate(1 - (cocOut - coc_i))
+ *   reduce   the illumination's mips, 32 - clz(max(hw, hh)) levels in all, level k of max(hw >> k, 1) x
+ *            max(hh >> k, 1) texels.  Levels 1-6: the float32 mean of four texels of the unrounded level below, over
+ *            the source clamped to its edge (what FidelityFX SPD's 64 x 64 tile computes); levels 7 and up: the mean
+ *            of four stored texels of the level below, clamped to that level's extent
+ *   flatten  min and max CoC of every tile, RG16F
+ *   dilate   over tiles (i, j) away, |i|, |j| <= gatherRadius: the min of the minima of the tiles with
+ *            8 * sqrt(i*i + j*j) <= |min| + 4, likewise the max; tiles outside the image read the edge tile
+ *   gather   foreground and background, RGBA16F: 121 octaweb taps (prosper_pt_dof_sample_offsets) at
+ *            (coord + 0.5) + ringRadius * offset in half-resolution texel units; the CoC lookup is the texel
+ *            clamp(floor(p), 0, size - 1), the colour lookup trilinear over the mips (level l bilinear at
+ *            p * size_l / size_0 - 0.5, clamped to the edge, float weights).  Background (colour, 0), foreground
+ *            (colour, weight); a tile the layer skips stores zeros, as does a foreground texel that takes no tap
+ *   filter   a 3 x 3 median by luminance of each gather, neighbours clamped to the edge: the brightest of the nine goes
+ *            to slot 8, then the three compare-swap rounds of the GLSL as written.  Its second round pairs (0, 2),
+ *            (1, 3), (6, 8) and (7, 9); the last reaches past the nine elements (undefined in the GLSL) and is left out
+ *   combine  the filtered layers over the full-resolution illumination.  The half-resolution coordinates
+ *            floor((x + d) / 2) can lie one past the edge on an even extent: they are clamped to the edge (the GLSL
+ *            leaves an out-of-bounds imageLoad to the driver)
+ * All arithmetic is float32 without contraction.  Refused: non-finite pc values, focusDistance <= 0, a negative CoC,
+ * gatherRadius < 1, an empty extent, illumination = NULL when the HDR image has another extent, nonLinearDepth = NULL
+ * when the last traced G-buffer has another extent.  It needs no scene. */
+int prosper_pt_depth_of_field(
+    prosper_pt_ctx *ctx, const prosper_pt_dof_pc *pc, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height,
+    const prosper_pt_dof_inputs *inputs, void *stream);
+/* The 121 unit offsets (cos phi, sin phi) of the six octaweb rings (1 + 8 + 16 + 24 + 32 + 40 taps), ring by ring:
+ * phi = (s + (ring even ? 0.5 : 0)) * 2 pi / count, float32 of double-precision cos / sin with pi itself.  Host only:
+ * it needs neither a context nor a GPU. */
+void prosper_pt_dof_sample_offsets(float out[242]);
+enum
+{
+    PROSPER_PT_DOF_HALF_ILLUMINATION = 0, /* RGBA16F, `level` selects the mip: max(hw >> level, 1) x max(hh >> level, 1) */
+    PROSPER_PT_DOF_HALF_COC = 1,          /* R16F, hw x hh */
+    PROSPER_PT_DOF_TILE_MIN_MAX = 2,      /* RG16F, tiles */
+    PROSPER_PT_DOF_DILATED_TILE_MIN_MAX = 3,
+    PROSPER_PT_DOF_FG_GATHER = 4, /* RGBA16F, hw x hh */
+    PROSPER_PT_DOF_BG_GATHER = 5,
+    PROSPER_PT_DOF_FG_FILTERED = 6,
+    PROSPER_PT_DOF_BG_FILTERED = 7,
+    PROSPER_PT_DOF_STAGE_COUNT = 8,
+};
+/* Synchronises `stream` and copies one intermediate of the last prosper_pt_depth_of_field to host memory as raw fp16,
+ * row-major; byte_size must be exactly its size.  `level` is read only for PROSPER_PT_DOF_HALF_ILLUMINATION.  NO_SCENE
+ * before the first call. */
+int prosper_pt_read_dof_stage(
+    prosper_pt_ctx *ctx, uint32_t stage, uint32_t level, void *host, size_t byte_size, void *stream);
+typedef struct prosper_pt_dof_info
+{
+    uint32_t valid; /* 1 once prosper_pt_depth_of_field ran */
+    uint32_t width, height, halfWidth, halfHeight, tileWidth, tileHeight;
+    uint32_t mips;  /* levels of the half-resolution illumination */
+    /* device time of each stage of the last call (reading them waits for it) */
+    float setupMs, reduceMs, flattenMs, dilateMs, gatherForegroundMs, gatherBackgroundMs, filterForegroundMs,
+        filterBackgroundMs, combineMs;
+} prosper_pt_dof_info;
+int prosper_pt_get_dof_info(prosper_pt_ctx *ctx, prosper_pt_dof_info *out);
+
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of
  * per-tile HDR buffers".)  The reference renders the whole image on one GPU and asserts renderArea.offset == 0

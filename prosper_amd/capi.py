@@ -96,6 +96,13 @@ def lib():
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
     L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
     L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.prosper_pt_skybox_fill.argtypes = [vp, C.POINTER(S.CameraUniforms), u32, u32, vp, u32, vp]
+    L.prosper_pt_depth_of_field.argtypes = [
+        vp, C.POINTER(S.DofPC), C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.DofInputs), vp]
+    L.prosper_pt_dof_sample_offsets.argtypes = [vp]
+    L.prosper_pt_dof_sample_offsets.restype = None
+    L.prosper_pt_read_dof_stage.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
+    L.prosper_pt_get_dof_info.argtypes = [vp, C.POINTER(S.DofInfo)]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -179,6 +186,14 @@ def lib():
     L.prosper_host_image_based_lighting_destroy.restype = None
     L.prosper_host_image_based_lighting_is_generated.argtypes = [vp]
     L.prosper_host_image_based_lighting_record_generation.argtypes = [vp, vp]
+    L.prosper_host_skybox_renderer_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_skybox_renderer_destroy.argtypes = [vp]
+    L.prosper_host_skybox_renderer_destroy.restype = None
+    L.prosper_host_skybox_renderer_record.argtypes = [vp, vp, u32, u32, vp, u32, vp]
+    L.prosper_host_depth_of_field_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_depth_of_field_destroy.argtypes = [vp]
+    L.prosper_host_depth_of_field_destroy.restype = None
+    L.prosper_host_depth_of_field_record.argtypes = [vp, vp, u32, u32, C.POINTER(S.DofInputs), vp, C.POINTER(S.DofPC)]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -213,6 +228,13 @@ def _check(rc):
 
 def _tile_ref(tile):
     return C.byref(tile) if tile is not None else None
+
+
+def dof_sample_offsets():
+    """prosper_pt_dof_sample_offsets: the octaweb's 121 unit offsets, float32 [121, 2] (needs no GPU)."""
+    out = np.empty((S.DOF_TAPS, 2), np.float32)
+    lib().prosper_pt_dof_sample_offsets(out.ctypes.data)
+    return out
 
 
 def has_experiments():
@@ -624,6 +646,57 @@ class Context:
             levels.append(rad[at:at + 6 * n * n * 4].reshape(6, n, n, 4))
             at += 6 * n * n * 4
         return {"irradiance": irr, "radiance": levels, "lut": lut}
+
+    def skybox_fill(self, camera, width, height, depth=None, depth_ptr=None, stream=None):
+        """SkyboxRenderer (prosper_pt_skybox_fill): the sky into every HDR texel whose depth is 0.  `depth`: a host array
+        [h, w]; `depth_ptr`: a device pointer; neither: the last traced G-buffer's depth."""
+        self._sync_debug()
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert dp is None or dp.shape == (height, width)
+        ptr = depth_ptr if dp is None else dp.ctypes.data
+        _check(lib().prosper_pt_skybox_fill(self._h, C.byref(camera), width, height, C.c_void_p(ptr),
+                                            1 if dp is None else 0, C.c_void_p(stream)))
+
+    def depth_of_field(self, pc, camera, width, height, illumination=None, depth=None, illumination_ptr=None,
+                       depth_ptr=None, stream=None):
+        """render::dof::DepthOfField (prosper_pt_depth_of_field) with the push constants `pc` (S.DofPC) into the HDR image.
+        `illumination` [h, w, 4] and `depth` [h, w]: host arrays (both or neither); `illumination_ptr`, `depth_ptr`:
+        device pointers.  No illumination: the HDR image in place; no depth: the last traced G-buffer's."""
+        host = illumination is not None or depth is not None
+        assert not (host and (illumination_ptr or depth_ptr)), "host and device inputs cannot be mixed"
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert il is None or il.shape == (height, width, 4)
+        assert dp is None or dp.shape == (height, width)
+        if host:
+            inp = S.DofInputs(None if il is None else il.ctypes.data, None if dp is None else dp.ctypes.data, 0, 0)
+        else:
+            inp = S.DofInputs(illumination_ptr, depth_ptr, 1, 0)
+        _check(lib().prosper_pt_depth_of_field(self._h, C.byref(pc), C.byref(camera), width, height, C.byref(inp),
+                                               C.c_void_p(stream)))
+
+    def dof_info(self):
+        """S.DofInfo: the last depth-of-field call's extents, mip count and per-stage device times."""
+        info = S.DofInfo()
+        _check(lib().prosper_pt_get_dof_info(self._h, C.byref(info)))
+        return info
+
+    def read_dof_stage(self, stage, level=0, stream=None):
+        """One intermediate of the last depth_of_field as float16: [h, w, 4] for the half-resolution illumination (mip
+        `level`), the gathers and the filtered layers, [h, w] for the CoC, [th, tw, 2] (min, max) for the tiles."""
+        i = self.dof_info()
+        hw, hh = i.halfWidth, i.halfHeight
+        if stage == S.DOF_HALF_ILLUMINATION:
+            shape = (max(hh >> level, 1), max(hw >> level, 1), 4)
+        elif stage == S.DOF_HALF_COC:
+            shape = (hh, hw)
+        elif stage in (S.DOF_TILE_MIN_MAX, S.DOF_DILATED_TILE_MIN_MAX):
+            shape = (i.tileHeight, i.tileWidth, 2)
+        else:
+            shape = (hh, hw, 4)
+        out = np.empty(shape, np.float16)
+        _check(lib().prosper_pt_read_dof_stage(self._h, stage, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
 
     def set_tone_map_lut(self, lut_r9g9b9e5):
         """lut: uint32 [dim, dim, dim] (z, y, x) R9G9B9E5 texels, e.g. from prosper_amd.dds.read_lut."""

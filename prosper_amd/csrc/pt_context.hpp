@@ -63,6 +63,11 @@ bool create_gbuffer_passes(prosper_pt_ctx *ctx);
 void destroy_gbuffer_passes(prosper_pt_ctx *ctx);
 // a new scene: the image-based lighting maps describe the old sky
 void forget_ibl_maps(prosper_pt_ctx *ctx);
+// State of the skybox fill and of depth of field (pt_dof_passes.cpp): the intermediates of the last call.  Made and
+// freed like the G-buffer passes' state.
+struct DofPassState;
+bool create_dof_passes(prosper_pt_ctx *ctx);
+void destroy_dof_passes(prosper_pt_ctx *ctx);
 
 #pragma GCC visibility pop
 
@@ -360,6 +365,7 @@ struct prosper_pt_ctx
     bool timingValid = false;
 
     ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
+    ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

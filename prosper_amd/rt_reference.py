@@ -308,6 +308,81 @@ class DeferredShading:
             pass
 
 
+class SkyboxRenderer:
+    """render::SkyboxRenderer (csrc/host/skybox_renderer.hpp) on a Context the scene was uploaded to: record fills the sky
+    into the context's HDR image wherever the depth is the far plane's (Context.skybox_fill)."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_skybox_renderer_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, width, height, depth=None, depth_ptr=None, stream=None):
+        """`depth`: a host array [h, w]; `depth_ptr`: a device pointer; neither: the last traced G-buffer's depth."""
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        rc = lib().prosper_host_skybox_renderer_record(
+            self._h, camera._h, width, height, C.c_void_p(depth_ptr if dp is None else dp.ctypes.data),
+            1 if dp is None else 0, C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_skybox_renderer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DepthOfField:
+    """render::dof::DepthOfField (csrc/host/depth_of_field.hpp) on a Context: record computes the push constants from the
+    camera's aperture, focus distance and focal length and runs the seven passes into the context's HDR image
+    (Context.read_hdr); returns the S.DofPC it pushed."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_depth_of_field_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, width, height, illumination=None, depth=None, stream=None):
+        """Over host arrays ([h, w, 4], [h, w] float32); None: the HDR image in place / the last traced G-buffer's depth."""
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        host = il is not None or dp is not None
+        inp = S.DofInputs(None if il is None else il.ctypes.data, None if dp is None else dp.ctypes.data, 0 if host else 1, 0)
+        return self.record_inputs(camera, width, height, inp, stream)
+
+    def record_inputs(self, camera, width, height, inputs, stream=None):
+        """Over S.DofInputs (device pointers with onDevice = 1)."""
+        pc = S.DofPC()
+        rc = lib().prosper_host_depth_of_field_record(self._h, camera._h, width, height, C.byref(inputs),
+                                                      C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_depth_of_field_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ImageBasedLighting:
     """render::ImageBasedLighting (csrc/host/image_based_lighting.hpp) on a Context the scene was uploaded to:
     record_generation makes the irradiance and radiance cubes and the BRDF LUT that DeferredShading reads with

@@ -368,6 +368,34 @@ class IblInfo(C.Structure):
                 ("radianceMs", C.c_float), ("lutMs", C.c_float)]
 
 
+class DofPC(C.Structure):
+    """prosper_pt_dof_pc: the push-constant values of the depth-of-field passes (Setup.cpp:163-177, Dilate.cpp:105-127)"""
+    _fields_ = [("focusDistance", C.c_float), ("maxBackgroundCoC", C.c_float), ("maxCoC", C.c_float),
+                ("gatherRadius", C.c_int32)]
+
+
+class DofInputs(C.Structure):
+    """prosper_pt_dof_inputs: illumination (None: the HDR image in place), depth (None: the last traced G-buffer's)"""
+    _fields_ = [("illumination", C.c_void_p), ("nonLinearDepth", C.c_void_p), ("onDevice", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class DofInfo(C.Structure):
+    """prosper_pt_dof_info: the last depth-of-field call's extents, mip count and per-stage device times"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid", "width", "height", "halfWidth", "halfHeight", "tileWidth",
+                                          "tileHeight", "mips")] + [
+        (n, C.c_float) for n in ("setupMs", "reduceMs", "flattenMs", "dilateMs", "gatherForegroundMs",
+                                 "gatherBackgroundMs", "filterForegroundMs", "filterBackgroundMs", "combineMs")]
+
+
+# prosper_pt_read_dof_stage: one value per intermediate of depth of field
+DOF_STAGES = ("half_illumination", "half_coc", "tile_min_max", "dilated_tile_min_max", "fg_gather", "bg_gather",
+              "fg_filtered", "bg_filtered")
+(DOF_HALF_ILLUMINATION, DOF_HALF_COC, DOF_TILE_MIN_MAX, DOF_DILATED_TILE_MIN_MAX, DOF_FG_GATHER, DOF_BG_GATHER,
+ DOF_FG_FILTERED, DOF_BG_FILTERED) = range(8)
+DOF_TAPS = 121  # six octaweb rings: 1 + 8 + 16 + 24 + 32 + 40
+
+
 # ImageBasedLighting: the irradiance cube, the prefiltered radiance cube (mips 512 ... 1) and the BRDF LUT
 IBL_IRRADIANCE_SIZE = 64
 IBL_RADIANCE_SIZE = 512

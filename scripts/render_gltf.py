@@ -14,6 +14,10 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  PROSPER_PT_DEFERRED_TRACE_GBUFFER), unshadowed, one frame
     --deferred --ibl             with the image-based lighting term: the irradiance / radiance maps and the BRDF LUT
                                  are generated once from the sky (prosper_pt_generate_ibl), then the frame is shaded
+    --deferred --sky             prosper_pt_skybox_fill after the shading: the sky wherever the G-buffer's ray missed
+    --deferred --sky --dof --aperture A --focus D
+                                 prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
+                                 aperture diameter A and focus distance D in scene units drive the push constants
 """
 import argparse
 import math
@@ -55,9 +59,15 @@ def main():
     ap.add_argument("--no-spatial", action="store_true", help="with --restir-di: no spatial reuse")
     ap.add_argument("--deferred", action="store_true", help="clustered deferred shading of a traced G-buffer")
     ap.add_argument("--ibl", action="store_true", help="with --deferred: add image-based lighting from the sky")
+    ap.add_argument("--sky", action="store_true", help="with --deferred: fill the sky where the G-buffer's ray missed")
+    ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
+    ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
+    ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
     args = ap.parse_args()
+    if (args.sky or args.dof) and not args.deferred:
+        ap.error("--sky and --dof belong to --deferred")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
-    from prosper_amd.rt_reference import Camera
+    from prosper_amd.rt_reference import Camera, DepthOfField
     w, h = (int(v) for v in args.size.lower().split("x"))
     world = gltf.load_gltf(args.gltf, bc7_on_gpu=True)  # prosper_cache BC7 files are decoded by the library at upload
     if world.missing_images:
@@ -68,7 +78,12 @@ def main():
         world.camera["eye"] = tuple(float(v) for v in args.eye.split(","))
     if args.target:
         world.camera["target"] = tuple(float(v) for v in args.target.split(","))
-    cam, focal = Camera.from_world(world, w, h).update_buffer()
+    hcam = Camera.from_world(world, w, h)
+    if args.dof:
+        c = world.camera
+        focus = args.focus or math.dist(c["eye"], c["target"])
+        hcam.set_parameters(c["fov"], c["zN"], c["zF"], args.aperture, focus)
+    cam, focal = hcam.update_buffer()
     ctx = capi.Context(0)
     ctx.upload_scene(world)
     st = ctx.scene_stats()
@@ -79,6 +94,12 @@ def main():
             ctx.generate_ibl()  # once per sky, before the first frame that applies IBL (Renderer.cpp:380-382)
         t0 = time.perf_counter()
         ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
+        if args.sky:
+            ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
+        if args.dof:
+            dpc = DepthOfField(ctx).record(hcam, w, h)  # in place over the traced G-buffer's depth
+            print("depth of field: focus %.3f, maxBackgroundCoC %.2f half-resolution texels, gatherRadius %d tiles" % (
+                dpc.focusDistance, dpc.maxBackgroundCoC, dpc.gatherRadius), file=sys.stderr)
         ctx.read_hdr()  # (synchronises)
         ms = (time.perf_counter() - t0) * 1e3
         args.spp = 1
