@@ -164,6 +164,20 @@ int prosper_host_depth_of_field_record(
     prosper_host_depth_of_field *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const prosper_pt_dof_inputs *inputs, void *stream, prosper_pt_dof_pc *outPushConstants);
 
+/* render::bloom::Bloom (host/bloom.hpp; reference src/render/bloom/Bloom.hpp) on a context (borrowed), with prosper's
+ * defaults: threshold 1, blend factors .9, .04, .04, biquadratic sampling, half resolution.  draw_ui sets what prosper's
+ * drawUi edits (resolutionScale: 0 Half, 1 Quarter); record = prosper_pt_bloom with those settings over `illumination`
+ * (RGBA32F; NULL: the context's HDR image in place) and returns the push constants it used. */
+typedef struct prosper_host_bloom prosper_host_bloom;
+int prosper_host_bloom_create(prosper_pt_ctx *ctx, prosper_host_bloom **out);
+void prosper_host_bloom_destroy(prosper_host_bloom *pass);
+void prosper_host_bloom_draw_ui(
+    prosper_host_bloom *pass, float threshold, float blendFactor0, float blendFactor1, float blendFactor2,
+    uint32_t biquadratic, uint32_t resolutionScale);
+int prosper_host_bloom_record(
+    prosper_host_bloom *pass, uint32_t width, uint32_t height, const void *illumination, uint32_t onDevice, void *stream,
+    prosper_pt_bloom_pc *outPushConstants);
+
 #ifdef __cplusplus
 }
 #endif

@@ -777,6 +777,85 @@ typedef struct prosper_pt_dof_info
 } prosper_pt_dof_info;
 int prosper_pt_get_dof_info(prosper_pt_ctx *ctx, prosper_pt_dof_info *out);
 
+/* ---- bloom, the multi-resolution blur (src/render/bloom/{Separate,Reduce,Blur,Compose}.cpp, res/shader/bloom/) ----
+ * What prosper runs first between the sky-filled illumination and the tone map (Renderer.cpp:516-573):
+ * its default technique (Bloom.hpp:57-58: MultiResolutionBlur at half resolution), plain compute over the context's HDR
+ * image.  The FFT technique is not part of this library.  Additive: the ABI version stays 4. */
+typedef struct prosper_pt_bloom_pc
+{
+    float threshold;          /* finite, >= 0; Separate.hpp: 1 */
+    float blendFactors[3];    /* finite, >= 0; Compose.hpp: .9, .04, .04 */
+    uint32_t resolutionScale; /* 0 Half, 1 Quarter */
+    uint32_t biquadratic;     /* 0 / 1; Compose.hpp: 1 */
+    uint32_t reserved[2];     /* 0 */
+} prosper_pt_bloom_pc;
+/* render::bloom::Bloom::record: separate, reduce, blur and compose; the result is always the context's HDR image
+ * (prosper_pt_read_hdr, _blit_rgba16f, _tone_map and _depth_of_field read it), with alpha 1 as compose.comp writes it.
+ * `illumination`: width*height RGBA32F (prosper's image is RGBA16F), on the device when `onDevice` is not 0; NULL: the
+ * HDR image, in place (compose reads only the texel it writes).  With s = 2 (Half) or 4 (Quarter), the working extent
+ * ww = width / s, wh = height / s (integer division, Separate.cpp:106-111) and level k of max(ww >> k, 1) x
+ * max(wh >> k, 1) RGBA16F texels, the context owns three grow-only images of four levels, stored with
+ * round-to-nearest-even: `highlights` (separate and reduce write it), `horizontal` and `blurred` (the horizontal and the
+ * vertical blur's outputs; prosper ping-pongs two images and overwrites the blur's input).  Where the GLSL reads a
+ * level of its working image that no blur pass wrote, that level is read from `highlights`.
+ * A bilinear lookup of a level at uv has the texel coordinate c = uv * size - 0.5, i = floor(c), f = c - i, and blends
+ * the texels i, i + 1 of both axes with float weights; texels outside are (0, 0, 0, 0) for separate and blur
+ * (bilinearBorderTransparentBlackSampler, also in Blur.cpp:113-129) and clamped to the edge for compose.  Every uv here
+ * is a ratio of integers, and c is formed from the integers, without the float round trip through uv.
+ *   separate  over ww x wh.  Half: one lookup of the illumination at uv = 2 coord / resolution, i.e. the mean of the
+ *             texels 2 coord - 1 and 2 coord of both axes; Quarter: the mean (sum / 4) of four such lookups at
+ *             (4 coord + (-1 | 1, -1 | 1)) / resolution in the order (-1,-1), (-1,1), (1,-1), (1,1).  No + 0.5 is applied:
+ *             at coord 0 the lookups take in the border.  Stores (max(rgb - threshold, 0), 0) into level 0
+ *   reduce    levels 1-3 of `highlights` (SPD with three mips): level k is the float32 mean (((a + b) + c) + d) * 0.25
+ *             of four unrounded level k - 1 texels over the source clamped to its edge, virtual texels past a level's
+ *             extent included; only texels inside the level's extent are stored; alpha stays 0
+ *   blur      horizontal (`highlights` -> `horizontal`), then vertical (`horizontal` -> `blurred`), of the levels
+ *             first, first + 1, first + 2 with first = 0 (Half) or 1 (Quarter): four lookups of the level at
+ *             (coord + 0.5 + dir * OFFSETS[i]) / resolution weighted by WEIGHTS[i] (blur.comp:20-25), summed in
+ *             order, alpha 1.  The horizontal pass of level 1 adds the streak: with h = levelWidth / 2,
+ *             sum over i in [-h, h) of w(i) * L0(uv + (i, 0) / resolution) divided by (2 levelWidth), L0 the lookup
+ *             of `highlights` level 0 at the level-1 uv and w(i) of prosper_pt_bloom_streak_weights
+ *   compose   over width x height, uv = (coord + 0.5) / resolution: illumination.rgb + sum_l blendFactors[l] * level_l
+ *             for the levels 0, 1, 2, each read from `blurred` if a blur pass wrote it and from `highlights` otherwise
+ *             (level 0 at Quarter).  biquadratic = 1 is sampleBiquadratic as written: the mean of the four lookups at
+ *             uv -/+ c, c = (q (q - 1) + 0.5) / res, q = fract(uv res), in the order (-,-), (-,+), (+,+), (+,-), with
+ *             res = vec2(width, height) / (s * 2^l), a float division and not the level's integer size
+ * All arithmetic is float32 without contraction.  Refused, changing nothing: a NULL pc, non-finite or negative values,
+ * an unknown scale, biquadratic above 1, non-zero reserved words, an empty extent or one above 32768, illumination = NULL
+ * when the HDR image has another extent, and an extent on which a blurred level would be empty (ww or wh below 4 at
+ * Half, below 8 at Quarter; prosper asserts there, Blur.cpp:196).  It needs no scene. */
+int prosper_pt_bloom(
+    prosper_pt_ctx *ctx, const prosper_pt_bloom_pc *pc, uint32_t width, uint32_t height, const void *illumination,
+    uint32_t onDevice, void *stream);
+/* The streak's weights for i = -halfWidth .. halfWidth - 1, 2 * halfWidth floats each (blur.comp:56-66):
+ * b = 4 (|sin(.5 i)| + |cos(.95 i)| + |sin(.75 i)|) * (150 / max(.015 i^2 + |i|, 1)) and rg = c * that with c = .05 for
+ * |i| < 10 and .01 otherwise (the GLSL's abs(i) / 10 is an integer division inside saturate), computed in double
+ * precision from the integer i as ((c * 4) * wave) * fall and rounded once to float32.  This is the definition: GLSL's
+ * float32 sin and cos have no stated precision.  Host only: it needs neither a context nor a GPU. */
+void prosper_pt_bloom_streak_weights(uint32_t halfWidth, float *rg, float *b);
+enum
+{
+    PROSPER_PT_BLOOM_HIGHLIGHTS = 0, /* levels 0-3 */
+    PROSPER_PT_BLOOM_HORIZONTAL = 1, /* levels firstLevel .. firstLevel + 2 */
+    PROSPER_PT_BLOOM_BLURRED = 2,    /* levels firstLevel .. firstLevel + 2 */
+    PROSPER_PT_BLOOM_STAGE_COUNT = 3,
+};
+/* Synchronises `stream` and copies one level of one working image of the last prosper_pt_bloom to host memory as raw
+ * RGBA16F, row-major; byte_size must be exactly its size.  A level the stage did not write is refused.  NO_SCENE before
+ * the first call. */
+int prosper_pt_read_bloom_stage(
+    prosper_pt_ctx *ctx, uint32_t stage, uint32_t level, void *host, size_t byte_size, void *stream);
+typedef struct prosper_pt_bloom_info
+{
+    uint32_t valid; /* 1 once prosper_pt_bloom ran */
+    uint32_t width, height, workingWidth, workingHeight;
+    uint32_t firstLevel;      /* the first blurred level */
+    uint32_t streakHalfWidth; /* max(workingWidth >> 1, 1) / 2 */
+    /* device time of each stage of the last call (reading them waits for it); the blurs by level firstLevel + n */
+    float separateMs, reduceMs, blurHorizontalMs[3], blurVerticalMs[3], composeMs;
+} prosper_pt_bloom_info;
+int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out);
+
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of
  * per-tile HDR buffers".)  The reference renders the whole image on one GPU and asserts renderArea.offset == 0

@@ -103,6 +103,11 @@ def lib():
     L.prosper_pt_dof_sample_offsets.restype = None
     L.prosper_pt_read_dof_stage.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
     L.prosper_pt_get_dof_info.argtypes = [vp, C.POINTER(S.DofInfo)]
+    L.prosper_pt_bloom.argtypes = [vp, C.POINTER(S.BloomPC), u32, u32, vp, u32, vp]
+    L.prosper_pt_bloom_streak_weights.argtypes = [u32, vp, vp]
+    L.prosper_pt_bloom_streak_weights.restype = None
+    L.prosper_pt_read_bloom_stage.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
+    L.prosper_pt_get_bloom_info.argtypes = [vp, C.POINTER(S.BloomInfo)]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -194,6 +199,12 @@ def lib():
     L.prosper_host_depth_of_field_destroy.argtypes = [vp]
     L.prosper_host_depth_of_field_destroy.restype = None
     L.prosper_host_depth_of_field_record.argtypes = [vp, vp, u32, u32, C.POINTER(S.DofInputs), vp, C.POINTER(S.DofPC)]
+    L.prosper_host_bloom_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_bloom_destroy.argtypes = [vp]
+    L.prosper_host_bloom_destroy.restype = None
+    L.prosper_host_bloom_draw_ui.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, u32, u32]
+    L.prosper_host_bloom_draw_ui.restype = None
+    L.prosper_host_bloom_record.argtypes = [vp, u32, u32, vp, u32, vp, C.POINTER(S.BloomPC)]
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -235,6 +246,14 @@ def dof_sample_offsets():
     out = np.empty((S.DOF_TAPS, 2), np.float32)
     lib().prosper_pt_dof_sample_offsets(out.ctypes.data)
     return out
+
+
+def bloom_streak_weights(half_width):
+    """prosper_pt_bloom_streak_weights: (rg, b), float32 [2 * half_width] each, for i = -half_width .. half_width - 1
+    (needs no GPU)."""
+    rg, b = np.empty(2 * half_width, np.float32), np.empty(2 * half_width, np.float32)
+    lib().prosper_pt_bloom_streak_weights(half_width, rg.ctypes.data, b.ctypes.data)
+    return rg, b
 
 
 def has_experiments():
@@ -696,6 +715,30 @@ class Context:
             shape = (hh, hw, 4)
         out = np.empty(shape, np.float16)
         _check(lib().prosper_pt_read_dof_stage(self._h, stage, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def bloom(self, pc, width, height, illumination=None, illumination_ptr=None, stream=None):
+        """render::bloom::Bloom's multi-resolution blur (prosper_pt_bloom) with `pc` (S.BloomPC) into the HDR image.
+        `illumination`: a host array [h, w, 4]; `illumination_ptr`: a device pointer; neither: the HDR image in place."""
+        assert illumination is None or illumination_ptr is None, "host and device inputs cannot be mixed"
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        assert il is None or il.shape == (height, width, 4)
+        ptr = illumination_ptr if il is None else il.ctypes.data
+        _check(lib().prosper_pt_bloom(self._h, C.byref(pc), width, height, C.c_void_p(ptr), 1 if il is None else 0,
+                                      C.c_void_p(stream)))
+
+    def bloom_info(self):
+        """S.BloomInfo: the last bloom call's extents, first blurred level, streak half-width and per-stage device times."""
+        info = S.BloomInfo()
+        _check(lib().prosper_pt_get_bloom_info(self._h, C.byref(info)))
+        return info
+
+    def read_bloom_stage(self, stage, level, stream=None):
+        """Level `level` of one working image of the last bloom (S.BLOOM_HIGHLIGHTS, _HORIZONTAL, _BLURRED) as float16
+        [h, w, 4]."""
+        i = self.bloom_info()
+        out = np.empty((max(i.workingHeight >> level, 1), max(i.workingWidth >> level, 1), 4), np.float16)
+        _check(lib().prosper_pt_read_bloom_stage(self._h, stage, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
 
     def set_tone_map_lut(self, lut_r9g9b9e5):

@@ -827,7 +827,7 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     // life of the context: 4 % on FlightHelmet, 2 % on S-sponza-class, 60 % on a 256 x 256 frame (profiles/r04_mesh_streams.txt).
     for (auto &ws : ctx->workStreams)
         eventsOk = eventsOk && ws && hipEventRecord(ctx->chainFork, ws) == hipSuccess && hipStreamSynchronize(ws) == hipSuccess;
-    if (!eventsOk || !create_gbuffer_passes(ctx) || !create_dof_passes(ctx) ||
+    if (!eventsOk || !create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) ||
         hipMalloc((void **)&ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess)
     {
@@ -848,6 +848,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     free_scene(ctx);
     destroy_gbuffer_passes(ctx);
     destroy_dof_passes(ctx);
+    destroy_bloom_passes(ctx);
     if (ctx->dCounters) (void)hipFree(ctx->dCounters);
     for (auto &e : ctx->events)
         if (e) (void)hipEventDestroy(e);

@@ -68,6 +68,10 @@ void forget_ibl_maps(prosper_pt_ctx *ctx);
 struct DofPassState;
 bool create_dof_passes(prosper_pt_ctx *ctx);
 void destroy_dof_passes(prosper_pt_ctx *ctx);
+// State of bloom (pt_bloom_passes.cpp): the working images of the last call.  Made and freed like the others.
+struct BloomPassState;
+bool create_bloom_passes(prosper_pt_ctx *ctx);
+void destroy_bloom_passes(prosper_pt_ctx *ctx);
 
 #pragma GCC visibility pop
 
@@ -366,6 +370,7 @@ struct prosper_pt_ctx
 
     ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
     ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
+    ppt::BloomPassState *bloomPasses = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

@@ -383,6 +383,45 @@ class DepthOfField:
             pass
 
 
+class Bloom:
+    """render::bloom::Bloom (csrc/host/bloom.hpp) on a Context, with prosper's defaults: draw_ui sets the threshold, the
+    blend factors, the sampling and the resolution scale; record runs the four passes into the context's HDR image
+    (Context.read_hdr) and returns the S.BloomPC it pushed."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_bloom_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def draw_ui(self, threshold=1.0, blend_factors=(0.9, 0.04, 0.04), biquadratic=True, resolution_scale=S.BLOOM_HALF):
+        lib().prosper_host_bloom_draw_ui(self._h, threshold, blend_factors[0], blend_factors[1], blend_factors[2],
+                                         1 if biquadratic else 0, resolution_scale)
+
+    def record(self, width, height, illumination=None, illumination_ptr=None, stream=None):
+        """`illumination`: a host array [h, w, 4]; `illumination_ptr`: a device pointer; neither: the HDR image in place."""
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        pc = S.BloomPC()
+        rc = lib().prosper_host_bloom_record(self._h, width, height, C.c_void_p(illumination_ptr if il is None else il.ctypes.data),
+                                             1 if il is None else 0, C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_bloom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ImageBasedLighting:
     """render::ImageBasedLighting (csrc/host/image_based_lighting.hpp) on a Context the scene was uploaded to:
     record_generation makes the irradiance and radiance cubes and the BRDF LUT that DeferredShading reads with

@@ -396,6 +396,33 @@ DOF_STAGES = ("half_illumination", "half_coc", "tile_min_max", "dilated_tile_min
 DOF_TAPS = 121  # six octaweb rings: 1 + 8 + 16 + 24 + 32 + 40
 
 
+class BloomPC(C.Structure):
+    """prosper_pt_bloom_pc: threshold (Separate.hpp), blend factors and sampling (Compose.hpp), resolution scale
+    (0 Half, 1 Quarter; Bloom.hpp).  BloomPC.default() holds prosper's defaults."""
+    _fields_ = [("threshold", C.c_float), ("blendFactors", C.c_float * 3), ("resolutionScale", C.c_uint32),
+                ("biquadratic", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def default(cls, threshold=1.0, blend_factors=(0.9, 0.04, 0.04), resolution_scale=0, biquadratic=1):
+        return cls(threshold, (C.c_float * 3)(*blend_factors), resolution_scale, biquadratic, (C.c_uint32 * 2)(0, 0))
+
+
+class BloomInfo(C.Structure):
+    """prosper_pt_bloom_info: the last bloom call's extents, first blurred level, streak half-width and per-stage device
+    times"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid", "width", "height", "workingWidth", "workingHeight", "firstLevel",
+                                          "streakHalfWidth")] + [
+        ("separateMs", C.c_float), ("reduceMs", C.c_float), ("blurHorizontalMs", C.c_float * 3),
+        ("blurVerticalMs", C.c_float * 3), ("composeMs", C.c_float)]
+
+
+# prosper_pt_read_bloom_stage: the three working images of bloom, four levels each
+BLOOM_STAGES = ("highlights", "horizontal", "blurred")
+BLOOM_HIGHLIGHTS, BLOOM_HORIZONTAL, BLOOM_BLURRED = range(3)
+BLOOM_LEVELS = 4
+BLOOM_HALF, BLOOM_QUARTER = 0, 1
+
+
 # ImageBasedLighting: the irradiance cube, the prefiltered radiance cube (mips 512 ... 1) and the BRDF LUT
 IBL_IRRADIANCE_SIZE = 64
 IBL_RADIANCE_SIZE = 512

@@ -15,6 +15,9 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred --ibl             with the image-based lighting term: the irradiance / radiance maps and the BRDF LUT
                                  are generated once from the sky (prosper_pt_generate_ibl), then the frame is shaded
     --deferred --sky             prosper_pt_skybox_fill after the shading: the sky wherever the G-buffer's ray missed
+    --deferred --bloom [--bloom-threshold T] [--bloom-quarter]
+                                 prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
+                                 defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573)
     --deferred --sky --dof --aperture A --focus D
                                  prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
                                  aperture diameter A and focus distance D in scene units drive the push constants
@@ -60,14 +63,17 @@ def main():
     ap.add_argument("--deferred", action="store_true", help="clustered deferred shading of a traced G-buffer")
     ap.add_argument("--ibl", action="store_true", help="with --deferred: add image-based lighting from the sky")
     ap.add_argument("--sky", action="store_true", help="with --deferred: fill the sky where the G-buffer's ray missed")
+    ap.add_argument("--bloom", action="store_true", help="with --deferred: bloom (multi-resolution blur) over the shaded image")
+    ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
+    ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
     ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
     args = ap.parse_args()
-    if (args.sky or args.dof) and not args.deferred:
-        ap.error("--sky and --dof belong to --deferred")
+    if (args.sky or args.dof or args.bloom) and not args.deferred:
+        ap.error("--sky, --bloom and --dof belong to --deferred")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
-    from prosper_amd.rt_reference import Camera, DepthOfField
+    from prosper_amd.rt_reference import Bloom, Camera, DepthOfField
     w, h = (int(v) for v in args.size.lower().split("x"))
     world = gltf.load_gltf(args.gltf, bc7_on_gpu=True)  # prosper_cache BC7 files are decoded by the library at upload
     if world.missing_images:
@@ -96,6 +102,13 @@ def main():
         ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
         if args.sky:
             ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
+        if args.bloom:
+            bloom = Bloom(ctx)
+            bloom.draw_ui(threshold=args.bloom_threshold, resolution_scale=S.BLOOM_QUARTER if args.bloom_quarter else S.BLOOM_HALF)
+            bloom.record(w, h)  # in place
+            info = ctx.bloom_info()
+            print("bloom: threshold %.3f, working extent %dx%d, streak half-width %d" % (
+                args.bloom_threshold, info.workingWidth, info.workingHeight, info.streakHalfWidth), file=sys.stderr)
         if args.dof:
             dpc = DepthOfField(ctx).record(hcam, w, h)  # in place over the traced G-buffer's depth
             print("depth of field: focus %.3f, maxBackgroundCoC %.2f half-resolution texels, gatherRadius %d tiles" % (
