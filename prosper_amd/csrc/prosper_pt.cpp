@@ -470,16 +470,6 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
 namespace ppt
 {
 
-void wait_for_slot(RenderSlot &slot, hipStream_t stream)
-{
-    if (slot.freeRecorded) (void)hipStreamWaitEvent(stream, slot.free, 0);
-}
-void release_slot(RenderSlot &slot, hipStream_t stream)
-{
-    (void)hipEventRecord(slot.free, stream);
-    slot.freeRecorded = true;
-}
-
 int ensure_stack_overflow(prosper_pt_ctx *ctx, RenderSlot &slot, uint32_t ldsEntries, uint32_t gridBlocks, int32_t **out)
 {
     const uint32_t bound = ctx->stats.maxDepth;
@@ -812,14 +802,11 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
     for (auto &e : ctx->events) eventsOk = eventsOk && hipEventCreate(&e) == hipSuccess;
     for (auto &ws : ctx->workStreams) eventsOk = eventsOk && hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) == hipSuccess;
     for (RenderSlot &slot : ctx->slots)
-    {
         for (uint32_t i = 0; i < kMaxChains; ++i)
         {
             eventsOk = eventsOk && hipEventCreateWithFlags(&slot.chainJoin[i], hipEventDisableTiming) == hipSuccess;
             for (auto &e : slot.chainEvents[i]) eventsOk = eventsOk && hipEventCreate(&e) == hipSuccess;
         }
-        eventsOk = eventsOk && hipEventCreateWithFlags(&slot.free, hipEventDisableTiming) == hipSuccess;
-    }
     eventsOk = eventsOk && hipEventCreateWithFlags(&ctx->chainFork, hipEventDisableTiming) == hipSuccess;
     // Every work stream is used once here, so that the device's four hardware queues go to the caller's stream and these
     // three, in this order: a stream that comes into use later (the two of prosper_pt_update_meshes, made at first need)
@@ -853,19 +840,15 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     for (auto &e : ctx->events)
         if (e) (void)hipEventDestroy(e);
     for (RenderSlot &slot : ctx->slots)
-    {
         for (uint32_t i = 0; i < kMaxChains; ++i)
         {
             for (auto &e : slot.chainEvents[i])
                 if (e) (void)hipEventDestroy(e);
             if (slot.chainJoin[i]) (void)hipEventDestroy(slot.chainJoin[i]);
         }
-        if (slot.free) (void)hipEventDestroy(slot.free);
-    }
     for (auto &ws : ctx->workStreams)
         if (ws) (void)hipStreamDestroy(ws);
     if (ctx->buildStream) (void)hipStreamDestroy(ctx->buildStream);
-    if (ctx->pinnedStaging) (void)hipHostFree(ctx->pinnedStaging);
     if (ctx->chainFork) (void)hipEventDestroy(ctx->chainFork);
     delete ctx; // (its DeviceBuffers with it)
 }
@@ -895,29 +878,25 @@ static int flush_pending_lights(prosper_pt_ctx *ctx, hipStream_t stream)
 {
     LightState *ls = ctx->lights;
     if (!ls || !ls->pending) return PROSPER_PT_OK;
-    const uint32_t v = (ls->cur + 1u) % LightState::kVersions;
+    const uint32_t v = ls->versions.next();
+    int rc;
     if (!ls->dBlocks[v])
     {
         void *d = nullptr;
-        const int rc = device_alloc(ctx, sizeof(LightBlock), &d);
-        if (rc != PROSPER_PT_OK) return rc;
+        if ((rc = device_alloc(ctx, sizeof(LightBlock), &d))) return rc;
         ls->dBlocks[v] = static_cast<LightBlock *>(d);
     }
-    if (!ls->versionFree[v]) PPT_HIP(hipEventCreateWithFlags(&ls->versionFree[v], hipEventDisableTiming));
-    if (!ls->ready) PPT_HIP(hipEventCreateWithFlags(&ls->ready, hipEventDisableTiming));
-    if (ls->versionUsed[v]) PPT_HIP(hipStreamWaitEvent(stream, ls->versionFree[v], 0));
-    const uint32_t k = ls->pendingStaging;
-    PPT_HIP(hipMemcpyAsync(ls->dBlocks[v], ls->staging[k], sizeof(LightBlock), hipMemcpyHostToDevice, stream));
-    PPT_HIP(hipEventRecord(ls->stagingDone[k], stream));
-    ls->stagingUsed[k] = true;
-    PPT_HIP(hipEventRecord(ls->ready, stream));
-    ls->readyRecorded = true;
-    ls->cur = v;
+    if ((rc = ls->versions.wait_free(v, stream))) return rc;
+    const LightBlock *staged = ls->staging.pending_buffer();
+    PPT_HIP(hipMemcpyAsync(ls->dBlocks[v], staged, sizeof(LightBlock), hipMemcpyHostToDevice, stream));
+    if ((rc = ls->staging.copy_enqueued(stream))) return rc;
+    if ((rc = ls->ready.record(stream))) return rc;
+    ls->versions.commit(v);
     ctx->scene.directionalLight = &ls->dBlocks[v]->directional;
     ctx->scene.pointLights = &ls->dBlocks[v]->points;
     ctx->scene.spotLights = &ls->dBlocks[v]->spots;
-    ctx->scene.pointLightCount = ls->staging[k]->points.count;
-    ctx->scene.spotLightCount = ls->staging[k]->spots.count;
+    ctx->scene.pointLightCount = staged->points.count;
+    ctx->scene.spotLightCount = staged->spots.count;
     ls->pending = false;
     ls->updates++;
     return PROSPER_PT_OK;
@@ -939,21 +918,13 @@ int prosper_pt_update_lights(
         std::memcmp(&ls->mirror->spots, spotLights, sizeof(*spotLights)) == 0)
         return PROSPER_PT_OK;
     PPT_HIP(hipSetDevice(ctx->device));
-    const uint32_t k = ls->pending ? ls->pendingStaging : ls->stagingNext;
-    if (!ls->pending) ls->stagingNext = (ls->stagingNext + 1u) % kStagingBuffers;
-    if (!ls->staging[k])
-    {
-        PPT_HIP(hipHostMalloc((void **)&ls->staging[k], sizeof(LightBlock), hipHostMallocDefault));
-        PPT_HIP(hipEventCreateWithFlags(&ls->stagingDone[k], hipEventDisableTiming));
-    }
-    if (ls->stagingUsed[k]) PPT_HIP(hipEventSynchronize(ls->stagingDone[k])); // the copy of four updates ago
-    ls->stagingUsed[k] = false;
-    ls->staging[k]->directional = *directionalLight;
-    ls->staging[k]->points = *pointLights;
-    ls->staging[k]->spots = *spotLights;
-    *ls->mirror = *ls->staging[k];
+    LightBlock *staged = nullptr;
+    if (const int rc = ls->staging.acquire(sizeof(LightBlock), ls->pending, &staged)) return rc;
+    staged->directional = *directionalLight;
+    staged->points = *pointLights;
+    staged->spots = *spotLights;
+    *ls->mirror = *staged;
     ls->pending = true;
-    ls->pendingStaging = k;
     return PROSPER_PT_OK;
 }
 
@@ -1035,7 +1006,7 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
 {
     AccelState *acc = ctx->accel;
     if (!acc || !acc->pending) return PROSPER_PT_OK;
-    const uint32_t v = (acc->cur + 1u) % AccelState::kVersions;
+    const uint32_t v = acc->versions.next();
     const size_t transformBytes = sizeof(prosper_ModelInstanceTransforms) * (acc->pendingCount ? acc->pendingCount : 1);
     const size_t triBytes = sizeof(WorldTriangle) * (size_t)(acc->total ? acc->total : 1);
     void *d = nullptr;
@@ -1056,23 +1027,20 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
         acc->dNodesV[v] = static_cast<BvhNode *>(d);
         acc->nodesCurrent[v] = false;
     }
-    if (!acc->versionFree[v]) PPT_HIP(hipEventCreateWithFlags(&acc->versionFree[v], hipEventDisableTiming));
     // Everything is enqueued for version v through LOCAL names; the context switches to v only after the last call has
     // succeeded.  On a failure the previous version stays current and the update stays pending (the next consumer of the
     // scene tries again); what was half-written into v is rewritten by that retry.
     // the version's last readers (three updates ago), and the previous update: it wrote the node array copied below,
     // and it shares the flat triangle array and the bounds scratch with this one
-    if (acc->versionUsed[v]) PPT_HIP(hipStreamWaitEvent(stream, acc->versionFree[v], 0));
-    if (acc->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(stream, acc->sceneEvent, 0));
+    if ((rc = acc->versions.wait_free(v, stream))) return rc;
+    if ((rc = acc->sceneDone.wait(stream))) return rc;
     if (!acc->nodesCurrent[v])
     {
         PPT_HIP(hipMemcpyAsync(acc->dNodesV[v], acc->dNodes, (size_t)acc->nodeCount * sizeof(BvhNode), hipMemcpyDeviceToDevice, stream));
         acc->nodesCurrent[v] = true;
     }
-    const uint32_t k = acc->pendingStaging;
-    PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], acc->staging[k], sizeof(prosper_ModelInstanceTransforms) * acc->pendingCount, hipMemcpyHostToDevice, stream));
-    PPT_HIP(hipEventRecord(acc->stagingDone[k], stream));
-    acc->stagingUsed[k] = true;
+    PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], acc->staging.pending_buffer(), sizeof(prosper_ModelInstanceTransforms) * acc->pendingCount, hipMemcpyHostToDevice, stream));
+    if ((rc = acc->staging.copy_enqueued(stream))) return rc;
     // world-space triangles again, in both orders (the shading and any-hit records hold object-space attributes and stay
     // as they are), then the boxes.  (Also when only transforms of instances without geometry changed: a version must be
     // whole.)
@@ -1086,10 +1054,9 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
     PPT_HIP(hipGetLastError());
     acc->flatStale = true; // (the flat array now holds the new pose whatever happens next)
     if (acc->total && (rc = enqueue_refit(acc, bvh_pad_coefficient(build_options(ctx)), acc->dNodesV[v], acc->dTrisV[v], v, stream))) return rc;
-    PPT_HIP(hipEventRecord(acc->sceneEvent, stream));
+    if ((rc = acc->sceneDone.record(stream))) return rc;
     // ---- commit: the new version becomes the scene ----
-    acc->sceneEventRecorded = true;
-    acc->cur = v;
+    acc->versions.commit(v);
     acc->dNodes = acc->dNodesV[v];
     acc->dTris = acc->dTrisV[v];
     ctx->dTransforms = acc->dTransformsV[v];
@@ -1118,48 +1085,29 @@ int check_scene(prosper_pt_ctx *ctx, const char *what)
     return PROSPER_PT_OK;
 }
 
-int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s)
+int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s, hipStream_t reader)
 {
     PPT_HIP(hipSetDevice(ctx->device));
-    int frc = flush_pending_update(ctx, s);
-    if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, s);
-    if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, s);
-    if (frc != PROSPER_PT_OK) return frc;
-    if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
-    if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
-    if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
-    return PROSPER_PT_OK;
+    int rc = flush_pending_update(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = flush_pending_lights(ctx, s);
+    if (rc == PROSPER_PT_OK) rc = flush_pending_materials(ctx, s);
+    // a flush enqueued on another stream than the reader's (a pipelined render's chain, this one's or an earlier one's, or
+    // prosper_pt_update_transforms_async) must be done before anything on the reader's stream reads the scene
+    if (rc == PROSPER_PT_OK && ctx->lights) rc = ctx->lights->ready.wait(reader);
+    if (rc == PROSPER_PT_OK && ctx->materialState) rc = ctx->materialState->ready.wait(reader);
+    if (rc == PROSPER_PT_OK && ctx->accel) rc = ctx->accel->sceneDone.wait(reader);
+    return rc;
 }
 
 // The scene and light versions a render (or a pass over a G-buffer) read are free again behind its last kernel on `s` (the
-// accumulate kernel follows the path stages on the caller's stream).  One event per version: a reader on ANOTHER stream
-// than the previous reader's first waits for that one, so the newest record always stands for every reader so far.
+// accumulate kernel follows the path stages on the caller's stream): VersionRing::mark_read.
 int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s)
 {
-    auto mark = [&](hipEvent_t &event, bool &used, hipStream_t &last) -> int {
-        if (!event) PPT_HIP(hipEventCreateWithFlags(&event, hipEventDisableTiming));
-        if (used && last != s) PPT_HIP(hipStreamWaitEvent(s, event, 0));
-        PPT_HIP(hipEventRecord(event, s));
-        used = true;
-        last = s;
-        return PROSPER_PT_OK;
-    };
-    if (AccelState *acc = ctx->accel)
-    {
-        const int rc = mark(acc->versionFree[acc->cur], acc->versionUsed[acc->cur], acc->versionStream[acc->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    if (LightState *ls = ctx->lights)
-    {
-        const int rc = mark(ls->versionFree[ls->cur], ls->versionUsed[ls->cur], ls->versionStream[ls->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    if (MaterialState *ms = ctx->materialState)
-    {
-        const int rc = mark(ms->versionFree[ms->cur], ms->versionUsed[ms->cur], ms->versionStream[ms->cur]);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    return PROSPER_PT_OK;
+    int rc = PROSPER_PT_OK;
+    if (ctx->accel) rc = ctx->accel->versions.mark_read(s);
+    if (rc == PROSPER_PT_OK && ctx->lights) rc = ctx->lights->versions.mark_read(s);
+    if (rc == PROSPER_PT_OK && ctx->materialState) rc = ctx->materialState->versions.mark_read(s);
+    return rc;
 }
 
 // rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
@@ -1239,18 +1187,10 @@ int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransf
     }
     // into pinned staging (a pageable source would make the later copy synchronous).  An update that was never consumed
     // is simply replaced: its staging buffer is reused.
-    const uint32_t k = acc->pending ? acc->pendingStaging : acc->stagingNext;
-    if (!acc->pending) acc->stagingNext = (acc->stagingNext + 1u) % kStagingBuffers;
-    if (!acc->staging[k])
-    {
-        PPT_HIP(hipHostMalloc((void **)&acc->staging[k], sizeof(prosper_ModelInstanceTransforms) * (count ? count : 1), hipHostMallocDefault));
-        PPT_HIP(hipEventCreateWithFlags(&acc->stagingDone[k], hipEventDisableTiming));
-    }
-    if (acc->stagingUsed[k]) PPT_HIP(hipEventSynchronize(acc->stagingDone[k])); // the copy of four updates ago
-    acc->stagingUsed[k] = false;
-    std::memcpy(acc->staging[k], transforms, sizeof(prosper_ModelInstanceTransforms) * count);
+    prosper_ModelInstanceTransforms *staged = nullptr;
+    if (const int rc = acc->staging.acquire(sizeof(prosper_ModelInstanceTransforms) * (count ? count : 1), acc->pending, &staged)) return rc;
+    std::memcpy(staged, transforms, sizeof(prosper_ModelInstanceTransforms) * count);
     acc->pending = true;
-    acc->pendingStaging = k;
     acc->pendingCount = count;
     acc->transforms.assign(transforms, transforms + count);
     ctx->stats.bvhBuildSeconds = 0.0;
@@ -1432,15 +1372,8 @@ int prosper_pt_render_frames(
     {
         const uint32_t nextSlot = wavefrontPipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
         hipStream_t us = wavefrontPipelined ? ctx->workStreams[nextSlot] : s;
-        int frc = flush_pending_update(ctx, us);
-        if (frc == PROSPER_PT_OK) frc = flush_pending_lights(ctx, us);
-        if (frc == PROSPER_PT_OK) frc = flush_pending_materials(ctx, us);
+        const int frc = flush_scene_updates(ctx, us, s);
         if (frc != PROSPER_PT_OK) return frc;
-        if (ctx->lights && ctx->lights->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->lights->ready, 0));
-        if (ctx->materialState && ctx->materialState->readyRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->materialState->ready, 0));
-        // a refit enqueued on another stream (another render's chain, or prosper_pt_update_transforms_async) must be
-        // done before anything on the caller's stream reads the scene
-        if (ctx->accel && ctx->accel->sceneEventRecorded) PPT_HIP(hipStreamWaitEvent(s, ctx->accel->sceneEvent, 0));
     }
     if (ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL)
     {
@@ -1512,10 +1445,10 @@ int prosper_pt_render_frames(
             if (orc != PROSPER_PT_OK) return orc;
             // the slot's previous user (a render of two calls ago, or the previous chunk of this one) must be done
             // with the workspace: detached chains wait for that on their own stream, the others on the caller's
-            chains.after = slot.freeRecorded ? slot.free : nullptr;
-            chains.scene = (ctx->accel && ctx->accel->sceneEventRecorded) ? ctx->accel->sceneEvent : nullptr;
-            chains.lights = (ctx->lights && ctx->lights->readyRecorded) ? ctx->lights->ready : nullptr;
-            chains.materials = (ctx->materialState && ctx->materialState->readyRecorded) ? ctx->materialState->ready : nullptr;
+            chains.after = slot.free.event();
+            chains.scene = ctx->accel ? ctx->accel->sceneDone.event() : nullptr;
+            chains.lights = ctx->lights ? ctx->lights->ready.event() : nullptr;
+            chains.materials = ctx->materialState ? ctx->materialState->ready.event() : nullptr;
             if (!pipelined) wait_for_slot(slot, s);
             if (tp) tp->mark(kStageChains, s);
             launch_render_wavefront(

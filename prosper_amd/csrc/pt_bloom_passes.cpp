@@ -26,12 +26,7 @@ struct BloomPassState
     uint32_t weightsHalfWidth = 0;
     BloomParams last = {}; // of the last prosper_pt_bloom
     bool valid = false;
-    hipEvent_t events[kBloomStages + 1] = {};
-    ~BloomPassState()
-    {
-        for (hipEvent_t e : events)
-            if (e) (void)hipEventDestroy(e);
-    }
+    StageEvents<kBloomStages> timing;
 };
 
 bool create_bloom_passes(prosper_pt_ctx *ctx)
@@ -52,17 +47,6 @@ namespace
 {
 
 constexpr uint32_t kMaxExtent = 32768; // compose forms (2 coord + 1) * levelSize + extent in 32 bits
-
-int grow_to(DeviceBuffer &b, size_t bytes, hipStream_t s)
-{
-    if (b.ptr && b.bytes >= bytes) return PROSPER_PT_OK;
-    return grow_buffer(b, GrowWait::Stream, s, bytes, bytes ? bytes : 16u);
-}
-
-bool hdr_has_extent(const prosper_pt_ctx *ctx, uint32_t width, uint32_t height)
-{
-    return ctx->hdr && ctx->localWidth == width && ctx->height == height && ctx->stripeCount <= 1u;
-}
 
 bool finite_non_negative(float v) { return std::isfinite(v) && v >= 0.0f; }
 
@@ -143,8 +127,7 @@ int prosper_pt_bloom(
     if (rc == PROSPER_PT_OK) rc = grow_to(st.blurred, texels * 8u, s);
     if (rc == PROSPER_PT_OK) rc = ensure_streak_weights(st, p.streakHalfWidth, s);
     if (rc != PROSPER_PT_OK) return rc;
-    for (hipEvent_t &e : st.events)
-        if (!e) PPT_HIP(hipEventCreate(&e));
+    if ((rc = st.timing.create())) return rc;
 
     BloomBuffers b = {};
     if (!inPlace)
@@ -166,7 +149,7 @@ int prosper_pt_bloom(
     b.horizontal = st.horizontal.as<uint2>();
     b.blurred = st.blurred.as<uint2>();
     b.streakWeights = st.streakWeights.as<float>();
-    launch_bloom(p, b, st.events, s);
+    launch_bloom(p, b, st.timing.events, s);
     PPT_HIP(hipGetLastError());
     st.last = p;
     st.valid = true;
@@ -208,9 +191,7 @@ int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out)
         info.firstLevel = p.firstLevel;
         info.streakHalfWidth = p.streakHalfWidth;
         PPT_HIP(hipSetDevice(ctx->device));
-        PPT_HIP(hipEventSynchronize(st.events[kBloomStages]));
-        float *ms = &info.separateMs;
-        for (uint32_t k = 0; k < kBloomStages; ++k) PPT_HIP(hipEventElapsedTime(&ms[k], st.events[k], st.events[k + 1u]));
+        if (const int rc = st.timing.elapsed(&info.separateMs)) return rc;
     }
     *out = info;
     return PROSPER_PT_OK;

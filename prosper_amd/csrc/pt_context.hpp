@@ -10,8 +10,10 @@
 
 #include "../../include/prosper_pt/prosper_pt.h"
 #include "bvh_build.hpp"
+#include "pt_error.hpp"
 #include "pt_kernels.hpp"
 #include "pt_scene.hpp"
+#include "pt_sync.hpp"
 
 namespace ppt
 {
@@ -21,9 +23,6 @@ struct DeviceAllocation
     void *ptr = nullptr;
     size_t bytes = 0;
 };
-
-// records `msg` as the calling thread's last error (prosper_pt_last_error) and returns `code`
-int fail(int code, const std::string &msg);
 
 // A device buffer of the context that only grows (grow_buffer) and is freed with its owner.  `bytes` is what the last
 // grow asked for; the allocation may be padded beyond it.
@@ -81,11 +80,7 @@ void destroy_bloom_passes(prosper_pt_ctx *ctx);
 // The three light buffers of the scene (World.cpp:531-535 rewrites them every frame), versioned like the instance
 // transforms: an update is staged by the call (an unchanged set is a no-op) and copied by the next render's own chain
 // into the next of three device copies, so the frames in flight keep theirs and nothing synchronises the device.
-// Pinned staging buffers per kind of update (transforms, lights, material tables): an update's copy is enqueued at the head
-// of the next render's chain, i.e. BEHIND the frames in flight; with two buffers the update after next may wait on the host
-// for that copy - with one buffer more than frames in flight it never does.
-constexpr uint32_t kStagingBuffers = 4;
-
+// (VersionRing, StagingRing, Fence: pt_sync.hpp)
 struct LightBlock
 {
     alignas(16) prosper_DirectionalLightParameters directional;
@@ -96,31 +91,13 @@ struct LightState
 {
     static constexpr uint32_t kVersions = 3;
     LightBlock *dBlocks[kVersions] = {}; // [0] is the upload's own allocation
-    hipEvent_t versionFree[kVersions] = {};
-    bool versionUsed[kVersions] = {};
-    hipStream_t versionStream[kVersions] = {}; // the stream versionFree was last recorded on
-    uint32_t cur = 0;
-    LightBlock *mirror = nullptr;         // host copy of what the device holds (or will hold once `pending` is flushed)
-    LightBlock *staging[kStagingBuffers] = {}; // pinned
-    hipEvent_t stagingDone[kStagingBuffers] = {};
-    bool stagingUsed[kStagingBuffers] = {};
-    uint32_t stagingNext = 0, pendingStaging = 0;
+    VersionRing<kVersions> versions;
+    LightBlock *mirror = nullptr; // host copy of what the device holds (or will hold once `pending` is flushed)
+    StagingRing<LightBlock> staging;
     bool pending = false;
-    hipEvent_t ready = nullptr; // behind the last flush: every later render's chains wait for it
-    bool readyRecorded = false;
+    Fence ready; // behind the last flush: every later render's chains wait for it
     uint32_t updates = 0;
-    ~LightState()
-    {
-        delete mirror;
-        for (uint32_t i = 0; i < kStagingBuffers; ++i)
-        {
-            if (staging[i]) (void)hipHostFree(staging[i]);
-            if (stagingDone[i]) (void)hipEventDestroy(stagingDone[i]);
-        }
-        for (hipEvent_t e : versionFree)
-            if (e) (void)hipEventDestroy(e);
-        if (ready) (void)hipEventDestroy(ready);
-    }
+    ~LightState() { delete mirror; }
 };
 
 struct AccelState
@@ -154,10 +131,10 @@ struct AccelState
     // slot of the version it produces, so a measure can be read as soon as ITS refit has finished - in a pipelined loop
     // that updates every frame the newest refit has only just been enqueued, but the one of two updates ago is done.
     float *dCost = nullptr;             // [kCostSlots] device
-    float *hCost = nullptr;             // [kCostSlots] pinned; slot i valid once costEvent[i] has passed
+    Pinned<float> hCost;                // [kCostSlots]; slot i valid once costDone[i] has passed
     static constexpr uint32_t kCostSlots = 3;
-    hipEvent_t costEvent[kCostSlots] = {};
-    bool costPending[kCostSlots] = {};
+    Fence costDone[kCostSlots];
+    bool costPending[kCostSlots] = {}; // recorded, and the measure not taken yet
     uint64_t costSequence[kCostSlots] = {}; // which refit (a running number) the slot's measure belongs to
     uint64_t refitSequence = 0, costRead = 0; // refits enqueued so far / the newest one whose measure has been taken
     float builtCost = 0.0f;             // the same measure right after the last build
@@ -165,13 +142,9 @@ struct AccelState
     std::vector<uint8_t> movedSinceBuild; // per range: its subtree is out of date in `bvh` and `flat`
     bool flatStale = false;
     // the update's transforms go through pinned staging (a pageable source would make the async copy synchronous)
-    prosper_ModelInstanceTransforms *staging[kStagingBuffers] = {};
-    hipEvent_t stagingDone[kStagingBuffers] = {};
-    bool stagingUsed[kStagingBuffers] = {};
-    uint32_t stagingNext = 0;
+    StagingRing<prosper_ModelInstanceTransforms> staging;
     // recorded on the updating stream behind the refit: every later render's path stages wait for it
-    hipEvent_t sceneEvent = nullptr;
-    bool sceneEventRecorded = false;
+    Fence sceneDone;
     uint32_t refits = 0, rebuilds = 0;
 
     // ---- scene versions: what a refit rewrites - transform table, leaf-order triangles, nodes - exists up to three
@@ -183,29 +156,11 @@ struct AccelState
     BvhNode *dNodesV[kVersions] = {};
     prosper_ModelInstanceTransforms *dTransformsV[kVersions] = {};
     bool nodesCurrent[kVersions] = {}; // the version's node array holds the tree of the last build (child references)
-    hipEvent_t versionFree[kVersions] = {}; // behind the last render that read the version
-    bool versionUsed[kVersions] = {};
-    hipStream_t versionStream[kVersions] = {}; // the stream versionFree was last recorded on
-    uint32_t cur = 0;
+    VersionRing<kVersions> versions;
     // an update waits here until the next consumer of the scene - normally the next render, which runs it at the head of
     // its own chain of launches, beside the frames in flight
     bool pending = false, pendingGeometry = false;
-    uint32_t pendingStaging = 0, pendingCount = 0;
-
-    ~AccelState()
-    {
-        for (uint32_t i = 0; i < kStagingBuffers; ++i)
-        {
-            if (staging[i]) (void)hipHostFree(staging[i]);
-            if (stagingDone[i]) (void)hipEventDestroy(stagingDone[i]);
-        }
-        if (hCost) (void)hipHostFree(hCost);
-        for (hipEvent_t e : costEvent)
-            if (e) (void)hipEventDestroy(e);
-        if (sceneEvent) (void)hipEventDestroy(sceneEvent);
-        for (hipEvent_t e : versionFree)
-            if (e) (void)hipEventDestroy(e);
-    }
+    uint32_t pendingCount = 0;
 };
 
 // The tables a streamed-in texture or material changes (prosper adopts loaded textures and materials a few per frame:
@@ -230,26 +185,17 @@ struct MaterialState
     // device side
     uint8_t *dBlocks[kVersions] = {};
     size_t blockBytes = 0, packsOffset = 0, alphaOffset = 0, texturesOffset = 0;
-    hipEvent_t versionFree[kVersions] = {};
-    bool versionUsed[kVersions] = {};
-    hipStream_t versionStream[kVersions] = {};
-    uint32_t cur = 0;
-    uint8_t *staging[kStagingBuffers] = {}; // pinned images of the block
-    hipEvent_t stagingDone[kStagingBuffers] = {};
-    bool stagingUsed[kStagingBuffers] = {};
-    uint32_t stagingNext = 0;
+    VersionRing<kVersions, 1> versions;
+    StagingRing<uint8_t> staging; // images of the block, filled by the flush itself
     bool pending = false;          // the mirrors differ from version `cur`
     uint64_t changes = 0;          // bumped whenever an update changed a mirror (a background geometry build compares)
     bool pendingAlphaPatch = false; // ... in a MASK / BLEND material: the any-hit records' copies must follow
     hipStream_t uploadStream = nullptr; // texel copies, re-tiling / BC7 decode, packs, alpha bounds of an update
-    hipEvent_t uploaded = nullptr;      // behind the last of them
-    bool uploadedRecorded = false;
-    hipEvent_t ready = nullptr;         // behind the last flush: every later render's chains wait for it
-    bool readyRecorded = false;
+    Fence uploaded;                     // behind the last of them
+    Fence ready;                        // behind the last flush: every later render's chains wait for it
     void *linearStaging = nullptr;      // device: the texels of an update as the caller holds them, before re-tiling
     size_t linearStagingBytes = 0;
-    void *pinnedStaging = nullptr;      // host, pinned: the same bytes on their way there (pt_materials.hpp create_device_texture)
-    size_t pinnedStagingBytes = 0;
+    Pinned<void> pinnedStaging;         // host: the same bytes on their way there (pt_materials.hpp create_device_texture)
     uint32_t updates = 0;
     // texel arrays, packs and alpha bounds an update replaced: a frame in flight may still read them, so they stay until
     // enough has piled up to be worth ONE device synchronisation (kRetireBytes), or the scene goes
@@ -258,18 +204,8 @@ struct MaterialState
     static constexpr uint64_t kRetireBytes = 256ull << 20;
     ~MaterialState()
     {
-        for (uint32_t i = 0; i < kStagingBuffers; ++i)
-        {
-            if (staging[i]) (void)hipHostFree(staging[i]);
-            if (stagingDone[i]) (void)hipEventDestroy(stagingDone[i]);
-        }
-        for (hipEvent_t e : versionFree)
-            if (e) (void)hipEventDestroy(e);
-        if (uploaded) (void)hipEventDestroy(uploaded);
-        if (ready) (void)hipEventDestroy(ready);
         if (uploadStream) (void)hipStreamDestroy(uploadStream);
         if (linearStaging) (void)hipFree(linearStaging);
-        if (pinnedStaging) (void)hipHostFree(pinnedStaging);
     }
 };
 
@@ -314,14 +250,6 @@ int upload(prosper_pt_ctx *ctx, const void *src, size_t bytes, void **out);
 
 } // namespace ppt
 
-#define PPT_HIP(call)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        const hipError_t e_ = (call);                                                                                  \
-        if (e_ != hipSuccess)                                                                                          \
-            return ppt::fail(PROSPER_PT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
-
 struct prosper_pt_ctx
 {
     int device = 0;
@@ -347,8 +275,7 @@ struct prosper_pt_ctx
     // Pinned staging for the large host <-> device copies of a geometry build (pt_geometry.cpp staged_copy): a copy from
     // pageable memory has the runtime pin the caller's pages for its duration, and when those pages are freed soon after - the
     // builder's vectors are - the unmapping goes through the GPU driver and stops every queue of the process for 20-30 ms
-    void *pinnedStaging = nullptr;
-    size_t pinnedStagingBytes = 0;
+    ppt::Pinned<void> pinnedStaging;
 
     float4 *hdr = nullptr; // current HDR buffer (internal or caller-owned)
     ppt::DeviceBuffer ownedHdr;
@@ -387,8 +314,7 @@ struct prosper_pt_ctx
         hipEvent_t chainEvents[ppt::kMaxChains][kMaxTimedLaunches + 1] = {};
         uint32_t chainStage[ppt::kMaxChains][kMaxTimedLaunches] = {};
         uint32_t chainLaunches[ppt::kMaxChains] = {};
-        hipEvent_t free = nullptr; // recorded after the accumulate kernel of the slot's last render
-        bool freeRecorded = false;
+        ppt::Fence free; // recorded after the accumulate kernel of the slot's last render
     };
     // prosper keeps two frames in flight; a third one fills the machine better at the batch sizes of a multi-GPU
     // rank share (1/4 share 0.71 -> 0.66 ms, C3 19.3 -> 18.9 ms; profiles/r01_pipelined.txt)

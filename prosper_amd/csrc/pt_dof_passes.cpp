@@ -26,12 +26,7 @@ struct DofPassState
     DeviceBuffer sampleOffsets; // the octaweb's unit offsets, uploaded once
     DofParams last = {};        // of the last prosper_pt_depth_of_field
     bool valid = false;
-    hipEvent_t events[kDofStages + 1] = {};
-    ~DofPassState()
-    {
-        for (hipEvent_t e : events)
-            if (e) (void)hipEventDestroy(e);
-    }
+    StageEvents<kDofStages> timing;
 };
 
 bool create_dof_passes(prosper_pt_ctx *ctx)
@@ -50,12 +45,6 @@ void destroy_dof_passes(prosper_pt_ctx *ctx)
 
 namespace
 {
-
-int grow_to(DeviceBuffer &b, size_t bytes, hipStream_t s)
-{
-    if (b.ptr && b.bytes >= bytes) return PROSPER_PT_OK;
-    return grow_buffer(b, GrowWait::Stream, s, bytes, bytes ? bytes : 16u);
-}
 
 // The depth a call reads on the device: the caller's, a copy of the caller's host array (at `hostOffset` of the
 // state's hostInputs, which the caller has grown), or with NULL the last traced G-buffer's, whose extent must match.
@@ -85,11 +74,6 @@ int device_depth(
     return PROSPER_PT_OK;
 }
 
-bool hdr_has_extent(const prosper_pt_ctx *ctx, uint32_t width, uint32_t height)
-{
-    return ctx->hdr && ctx->localWidth == width && ctx->height == height && ctx->stripeCount <= 1u;
-}
-
 } // namespace
 
 extern "C" {
@@ -109,7 +93,7 @@ int prosper_pt_skybox_fill(
     if (!hdr_has_extent(ctx, width, height))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_skybox_fill: the HDR image has another extent");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     const size_t pixels = (size_t)width * height;
     if (nonLinearDepth && !onDevice)
@@ -191,8 +175,7 @@ int prosper_pt_depth_of_field(
         if (rc == PROSPER_PT_OK) PPT_HIP(hipMemcpy(st.sampleOffsets.ptr, offsets, sizeof(offsets), hipMemcpyHostToDevice));
     }
     if (rc != PROSPER_PT_OK) return rc;
-    for (hipEvent_t &e : st.events)
-        if (!e) PPT_HIP(hipEventCreate(&e));
+    if ((rc = st.timing.create())) return rc;
 
     DofBuffers b = {};
     rc = device_depth(ctx, "prosper_pt_depth_of_field", inputs->nonLinearDepth, inputs->onDevice != 0u, width, height, pixels * 16u, s, &b.nonLinearDepth);
@@ -222,7 +205,7 @@ int prosper_pt_depth_of_field(
         b.filtered[k] = st.filtered[k].as<uint2>();
     }
     b.sampleOffsets = st.sampleOffsets.as<float>();
-    launch_depth_of_field(p, b, st.events, s);
+    launch_depth_of_field(p, b, st.timing.events, s);
     PPT_HIP(hipGetLastError());
     st.last = p;
     st.valid = true;
@@ -279,9 +262,7 @@ int prosper_pt_get_dof_info(prosper_pt_ctx *ctx, prosper_pt_dof_info *out)
         info.tileHeight = p.th;
         info.mips = p.levels;
         PPT_HIP(hipSetDevice(ctx->device));
-        PPT_HIP(hipEventSynchronize(st.events[kDofStages]));
-        float *ms = &info.setupMs;
-        for (uint32_t k = 0; k < kDofStages; ++k) PPT_HIP(hipEventElapsedTime(&ms[k], st.events[k], st.events[k + 1u]));
+        if (const int rc = st.timing.elapsed(&info.setupMs)) return rc;
     }
     *out = info;
     return PROSPER_PT_OK;

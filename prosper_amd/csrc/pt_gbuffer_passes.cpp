@@ -38,13 +38,8 @@ struct GBufferPassState
     DeviceBuffer iblIrradiance; // prosper_pt_generate_ibl: kIblIrradianceTexels RGBA16F, bordered cube
     DeviceBuffer iblRadiance;   // kIblRadianceTexels RGBA16F, 10 bordered mips
     DeviceBuffer iblLut;        // kIblLutSize^2 R16G16 UNORM
-    hipEvent_t iblEvents[4] = {}; // around the three passes of the last generation
+    StageEvents<3> iblTiming;   // around the three passes of the last generation
     bool iblGenerated = false;    // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
-    ~GBufferPassState()
-    {
-        for (hipEvent_t e : iblEvents)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 bool create_gbuffer_passes(prosper_pt_ctx *ctx)
@@ -318,7 +313,7 @@ int prosper_pt_restir_di_trace(
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_trace: empty extent");
     if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     DeviceGBuffer din;
     rc = device_gbuffer(ctx, in, (size_t)width * height, true, s, din);
@@ -347,7 +342,7 @@ int prosper_pt_restir_di_resample(
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_restir_di_resample: empty extent");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t pixels = (size_t)width * height;
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     GBufferPassState &st = *ctx->gbufferPasses;
     void *out = device_out_reservoirs;
@@ -399,7 +394,7 @@ int prosper_pt_trace_gbuffer(
     const int crc = check_scene(ctx, "prosper_pt_trace_gbuffer");
     if (crc != PROSPER_PT_OK) return crc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     prosper_pt_gbuffer_targets t = {};
     if (rc == PROSPER_PT_OK)
     {
@@ -467,7 +462,7 @@ int prosper_pt_restir_di_record(
     if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t pixels = (size_t)width * height;
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc == PROSPER_PT_OK) rc = restir_reservoir_buffers(ctx, pixels, s);
     DeviceGBuffer din;
     if (rc == PROSPER_PT_OK)
@@ -534,7 +529,7 @@ int prosper_pt_cluster_lights(
     const int crc = check_scene(ctx, "prosper_pt_cluster_lights");
     if (crc != PROSPER_PT_OK) return crc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, cluster_params(camera, width, height), s);
     if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
@@ -608,7 +603,7 @@ int prosper_pt_deferred_shading(
     const int crc = check_scene(ctx, "prosper_pt_deferred_shading");
     if (crc != PROSPER_PT_OK) return crc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     DeviceGBuffer din = {};
     if (rc == PROSPER_PT_OK)
         rc = call_gbuffer(
@@ -640,7 +635,7 @@ int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream)
     const int crc = check_scene(ctx, "prosper_pt_generate_ibl");
     if (crc != PROSPER_PT_OK) return crc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s);
+    int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     GBufferPassState &st = *ctx->gbufferPasses;
     // allocated once: the maps' sizes are fixed
@@ -651,10 +646,9 @@ int prosper_pt_generate_ibl(prosper_pt_ctx *ctx, void *stream)
     if (rc == PROSPER_PT_OK) rc = allocate_once(st.iblRadiance, kIblRadianceTexels * 8u);
     if (rc == PROSPER_PT_OK) rc = allocate_once(st.iblLut, (size_t)kIblLutSize * kIblLutSize * 4u);
     if (rc != PROSPER_PT_OK) return rc;
-    for (hipEvent_t &e : st.iblEvents)
-        if (!e) PPT_HIP(hipEventCreate(&e));
+    if ((rc = st.iblTiming.create())) return rc;
     launch_ibl_generation(
-        ctx->scene, st.iblIrradiance.as<uint16_t>(), st.iblRadiance.as<uint16_t>(), st.iblLut.as<uint32_t>(), st.iblEvents, s);
+        ctx->scene, st.iblIrradiance.as<uint16_t>(), st.iblRadiance.as<uint16_t>(), st.iblLut.as<uint32_t>(), st.iblTiming.events, s);
     PPT_HIP(hipGetLastError());
     st.iblGenerated = true;
     return mark_versions_read(ctx, s);
@@ -670,13 +664,10 @@ int prosper_pt_get_ibl_info(prosper_pt_ctx *ctx, prosper_pt_ibl_info *out)
     info.radianceSize = kIblRadianceSize;
     info.radianceMips = kIblRadianceMips;
     info.lutSize = kIblLutSize;
-    if (st.iblEvents[3])
+    if (st.iblTiming.created())
     {
         PPT_HIP(hipSetDevice(ctx->device));
-        PPT_HIP(hipEventSynchronize(st.iblEvents[3]));
-        PPT_HIP(hipEventElapsedTime(&info.irradianceMs, st.iblEvents[0], st.iblEvents[1]));
-        PPT_HIP(hipEventElapsedTime(&info.radianceMs, st.iblEvents[1], st.iblEvents[2]));
-        PPT_HIP(hipEventElapsedTime(&info.lutMs, st.iblEvents[2], st.iblEvents[3]));
+        if (const int rc = st.iblTiming.elapsed(&info.irradianceMs)) return rc; // (irradianceMs, radianceMs, lutMs)
     }
     *out = info;
     return PROSPER_PT_OK;

@@ -58,32 +58,26 @@ static int staged_copy(prosper_pt_ctx *ctx, hipStream_t stream, void *dst, const
         PPT_HIP(hipStreamSynchronize(stream));
         return PROSPER_PT_OK;
     }
-    if (bytes > ctx->pinnedStagingBytes)
-    {
-        if (ctx->pinnedStaging) PPT_HIP(hipHostFree(ctx->pinnedStaging));
-        ctx->pinnedStaging = nullptr;
-        ctx->pinnedStagingBytes = 0;
-        const size_t capacity = bytes + bytes / 4;
-        PPT_HIP(hipHostMalloc(&ctx->pinnedStaging, capacity, hipHostMallocDefault));
-        ctx->pinnedStagingBytes = capacity;
-    }
+    if (bytes > ctx->pinnedStaging.bytes)
+        if (const int rc = ctx->pinnedStaging.allocate(bytes + bytes / 4)) return rc;
+    void *pinned = ctx->pinnedStaging.ptr;
     if (kind == hipMemcpyHostToDevice)
     {
-        std::memcpy(ctx->pinnedStaging, src, bytes);
-        PPT_HIP(hipMemcpyAsync(dst, ctx->pinnedStaging, bytes, kind, stream));
+        std::memcpy(pinned, src, bytes);
+        PPT_HIP(hipMemcpyAsync(dst, pinned, bytes, kind, stream));
         PPT_HIP(hipStreamSynchronize(stream));
     }
     else
     {
-        PPT_HIP(hipMemcpyAsync(ctx->pinnedStaging, src, bytes, kind, stream));
+        PPT_HIP(hipMemcpyAsync(pinned, src, bytes, kind, stream));
         PPT_HIP(hipStreamSynchronize(stream));
-        std::memcpy(dst, ctx->pinnedStaging, bytes);
+        std::memcpy(dst, pinned, bytes);
     }
     return PROSPER_PT_OK;
 }
 
 // The refit's GPU work on `stream` for the node / triangle arrays of scene version `version`: exact bounds level by level,
-// every node re-encoded, the tree's surface-area measure into the version's cost slot (read back through hCost / costEvent).
+// every node re-encoded, the tree's surface-area measure into the version's cost slot (read back through hCost / costDone).
 int enqueue_refit(AccelState *acc, float padCoeff, BvhNode *nodes, const WorldTriangle *tris, uint32_t version, hipStream_t stream)
 {
     const uint32_t slot = version % AccelState::kCostSlots;
@@ -92,8 +86,8 @@ int enqueue_refit(AccelState *acc, float padCoeff, BvhNode *nodes, const WorldTr
         nodes, tris, acc->dNodeBounds, acc->dRefitOrder, acc->levelOffsets.data(), (uint32_t)acc->levelOffsets.size() - 1u,
         acc->nodeCount, padCoeff, acc->dCost + slot, stream);
     PPT_HIP(hipGetLastError());
-    PPT_HIP(hipMemcpyAsync(acc->hCost + slot, acc->dCost + slot, sizeof(float), hipMemcpyDeviceToHost, stream));
-    PPT_HIP(hipEventRecord(acc->costEvent[slot], stream));
+    PPT_HIP(hipMemcpyAsync(acc->hCost.ptr + slot, acc->dCost + slot, sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (const int rc = acc->costDone[slot].record(stream)) return rc;
     acc->costPending[slot] = true;
     acc->costSequence[slot] = ++acc->refitSequence;
     return PROSPER_PT_OK;
@@ -106,13 +100,14 @@ int poll_refit_cost(AccelState *acc, bool wait)
     {
         if (!acc->costPending[i]) continue;
         const bool newest = acc->costSequence[i] == acc->refitSequence;
-        if (wait && newest) PPT_HIP(hipEventSynchronize(acc->costEvent[i]));
-        if (hipEventQuery(acc->costEvent[i]) != hipSuccess) continue;
+        if (wait && newest)
+            if (const int rc = acc->costDone[i].host_wait()) return rc;
+        if (!acc->costDone[i].passed()) continue;
         acc->costPending[i] = false;
         if (acc->costSequence[i] > acc->costRead)
         {
             acc->costRead = acc->costSequence[i];
-            if (acc->builtCost > 0.0f) acc->lastCostRatio = acc->hCost[i] / acc->builtCost;
+            if (acc->builtCost > 0.0f) acc->lastCostRatio = acc->hCost.ptr[i] / acc->builtCost;
         }
     }
     return PROSPER_PT_OK;
@@ -140,10 +135,10 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
                 acc->dNodesV[ver] = nullptr;
             }
         acc->dNodes = static_cast<BvhNode *>(d);
-        acc->dNodesV[acc->cur] = acc->dNodes;
+        acc->dNodesV[acc->versions.cur] = acc->dNodes;
         acc->nodeCapacityBytes = capacity;
     }
-    for (uint32_t ver = 0; ver < AccelState::kVersions; ++ver) acc->nodesCurrent[ver] = ver == acc->cur;
+    for (uint32_t ver = 0; ver < AccelState::kVersions; ++ver) acc->nodesCurrent[ver] = ver == acc->versions.cur;
     {
         const int src = staged_copy(ctx, t.stream, acc->dNodes, bvh.nodes.data(), nodeBytes, hipMemcpyHostToDevice);
         if (src != PROSPER_PT_OK) return src;
@@ -217,9 +212,7 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
         int rc;
         if ((rc = device_alloc(ctx, sizeof(float) * AccelState::kCostSlots, &d))) return rc;
         acc->dCost = static_cast<float *>(d);
-        PPT_HIP(hipHostMalloc((void **)&acc->hCost, sizeof(float) * AccelState::kCostSlots, hipHostMallocDefault));
-        for (hipEvent_t &e : acc->costEvent) PPT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        PPT_HIP(hipEventCreateWithFlags(&acc->sceneEvent, hipEventDisableTiming));
+        if ((rc = acc->hCost.allocate(sizeof(float) * AccelState::kCostSlots))) return rc;
     }
     std::vector<uint32_t> position((size_t)acc->total);
     if (acc->total)
@@ -238,7 +231,7 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
     if (acc->total)
     {
         // (an empty scene keeps the emitter's root - child boxes at +inf - as it is: the encoder has no bounds to write)
-        int rc = enqueue_refit(acc, bvh_pad_coefficient(t.buildOpt), acc->dNodes, acc->dTris, acc->cur, t.stream);
+        int rc = enqueue_refit(acc, bvh_pad_coefficient(t.buildOpt), acc->dNodes, acc->dTris, acc->versions.cur, t.stream);
         if (rc != PROSPER_PT_OK) return rc;
         t.lap("  refit queued");
         PPT_HIP(hipStreamSynchronize(t.stream));
@@ -248,9 +241,9 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
             const int src = staged_copy(ctx, t.stream, acc->dNodes, bvh.nodes.data(), nodeBytes, hipMemcpyHostToDevice);
             if (src != PROSPER_PT_OK) return src;
         }
-        const uint32_t slot = acc->cur % AccelState::kCostSlots;
+        const uint32_t slot = acc->versions.cur % AccelState::kCostSlots;
         acc->costPending[slot] = false;
-        acc->builtCost = acc->hCost[slot];
+        acc->builtCost = acc->hCost.ptr[slot];
     }
     PPT_HIP(hipStreamSynchronize(t.stream)); // (`order` and `position` have been read)
     acc->costRead = acc->refitSequence;
@@ -411,7 +404,7 @@ int finish_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryJob &job)
     t.lap("record allocations");
     PPT_HIP(hipMemsetAsync(dTris, 0, triBytes, t.stream));
     acc->dTris = static_cast<WorldTriangle *>(dTris);
-    acc->dTrisV[acc->cur] = acc->dTris;
+    acc->dTrisV[acc->versions.cur] = acc->dTris;
     s.triangles = acc->dTris;
 
     launch_flatten_triangles(

@@ -155,8 +155,6 @@ int ensure_update_state(prosper_pt_ctx *ctx)
 {
     MaterialState *ms = ctx->materialState;
     if (!ms->uploadStream) PPT_HIP(hipStreamCreateWithFlags(&ms->uploadStream, hipStreamNonBlocking));
-    if (!ms->uploaded) PPT_HIP(hipEventCreateWithFlags(&ms->uploaded, hipEventDisableTiming));
-    if (!ms->ready) PPT_HIP(hipEventCreateWithFlags(&ms->ready, hipEventDisableTiming));
     return PROSPER_PT_OK;
 }
 
@@ -283,7 +281,7 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
 {
     MaterialState *ms = ctx->materialState;
     if (!ms || !ms->pending) return PROSPER_PT_OK;
-    const uint32_t v = ms->cur == 0u ? 1u : (ms->cur % 3u) + 1u;
+    const uint32_t v = ms->versions.next(); // 1, 2, 3, 1, ...: version 0 is the upload's own tables
     int rc;
     if (!ms->dBlocks[v])
     {
@@ -292,48 +290,37 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
         ms->dBlocks[v] = static_cast<uint8_t *>(d);
     }
     if ((rc = ensure_update_state(ctx))) return rc;
-    const uint32_t k = ms->stagingNext;
-    if (!ms->staging[k])
-    {
-        PPT_HIP(hipHostMalloc((void **)&ms->staging[k], ms->blockBytes, hipHostMallocDefault));
-        PPT_HIP(hipEventCreateWithFlags(&ms->stagingDone[k], hipEventDisableTiming));
-    }
-    if (ms->stagingUsed[k]) PPT_HIP(hipEventSynchronize(ms->stagingDone[k])); // the copy of four flushes ago
-    ms->stagingUsed[k] = false;
-    uint8_t *img = ms->staging[k];
+    uint8_t *img = nullptr;
+    if ((rc = ms->staging.acquire(ms->blockBytes, false, &img))) return rc;
     std::memcpy(img, ms->materials.data(), ms->materials.size() * sizeof(prosper_MaterialData));
     std::memcpy(img + ms->packsOffset, ms->packs.data(), ms->packs.size() * sizeof(MaterialPack));
     std::memcpy(img + ms->alphaOffset, ms->alphaMaterials.data(), ms->alphaMaterials.size() * sizeof(AlphaMaterial));
     std::memcpy(img + ms->texturesOffset, ms->textures.data(), ms->textures.size() * sizeof(DeviceTexture));
     // the block's last readers (three flushes ago), the texel arrays / packs / bounds the tables point at
-    if (ms->versionUsed[v]) PPT_HIP(hipStreamWaitEvent(stream, ms->versionFree[v], 0));
-    if (ms->uploadedRecorded) PPT_HIP(hipStreamWaitEvent(stream, ms->uploaded, 0));
+    if ((rc = ms->versions.wait_free(v, stream))) return rc;
+    if ((rc = ms->uploaded.wait(stream))) return rc;
     // ... and the previous flush, which ran on another render's stream: its rewrite of the any-hit records (they exist
     // once, for every version) must be done before this render reads them.  `ready` is recorded anew below, so this wait is
     // the only thing that orders the render behind the earlier record: without it a frame whose own flush patches nothing
     // could overtake the patch of the flush before (found when a fifth stream changed which streams share a hardware
     // queue: 927 pixels of FlightHelmet's lenses, one frame in six).
-    if (ms->readyRecorded) PPT_HIP(hipStreamWaitEvent(stream, ms->ready, 0));
+    if ((rc = ms->ready.wait(stream))) return rc;
     PPT_HIP(hipMemcpyAsync(ms->dBlocks[v], img, ms->blockBytes, hipMemcpyHostToDevice, stream));
-    PPT_HIP(hipEventRecord(ms->stagingDone[k], stream));
-    ms->stagingUsed[k] = true;
-    ms->stagingNext = (k + 1u) % kStagingBuffers;
+    if ((rc = ms->staging.copy_enqueued(stream))) return rc;
     const AlphaMaterial *dAlpha = reinterpret_cast<const AlphaMaterial *>(ms->dBlocks[v] + ms->alphaOffset);
     if (ms->pendingAlphaPatch && ctx->alphaTriangleCount)
     {
         // the any-hit records carry a copy of their material's AlphaMaterial and exist once: they are rewritten in place,
         // behind every render that may still read them (the one kind of update that waits for the frames in flight)
-        for (uint32_t i = 0; i < MaterialState::kVersions; ++i)
-            if (ms->versionUsed[i]) PPT_HIP(hipStreamWaitEvent(stream, ms->versionFree[i], 0));
+        if ((rc = ms->versions.wait_all_free(stream))) return rc;
         launch_patch_alpha_records(
             const_cast<AlphaTriangle *>(ctx->scene.alphaTriangles), (uint32_t)ctx->alphaTriangleCount, dAlpha,
             (uint32_t)ms->alphaMaterials.size(), stream);
         PPT_HIP(hipGetLastError());
     }
-    PPT_HIP(hipEventRecord(ms->ready, stream));
+    if ((rc = ms->ready.record(stream))) return rc;
     // ---- commit ----
-    ms->readyRecorded = true;
-    ms->cur = v;
+    ms->versions.commit(v);
     ctx->scene.materials = reinterpret_cast<const prosper_MaterialData *>(ms->dBlocks[v]);
     ctx->scene.materialPacks = reinterpret_cast<const MaterialPack *>(ms->dBlocks[v] + ms->packsOffset);
     ctx->scene.alphaMaterials = dAlpha;
@@ -390,7 +377,7 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
     if (rc == PROSPER_PT_OK) rc = collect_retired(ctx);
     if (rc != PROSPER_PT_OK) return rc;
     // the previous update's copies out of the pinned staging area (a frame ago, as a rule: done long since)
-    if (ms->uploadedRecorded) PPT_HIP(hipEventSynchronize(ms->uploaded));
+    if ((rc = ms->uploaded.host_wait())) return rc;
     if (stagingBytes > ms->linearStagingBytes)
     {
         // (the outgrown area joins the scene's allocations: kernels of an earlier update may still read it)
@@ -400,14 +387,10 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
         PPT_HIP(hipMalloc(&ms->linearStaging, stagingBytes));
         ms->linearStagingBytes = stagingBytes;
     }
-    if (stagingBytes > ms->pinnedStagingBytes)
+    if (stagingBytes > ms->pinnedStaging.bytes)
     {
         // (the stream was synchronised at the end of the previous call: nothing reads the old area any more)
-        if (ms->pinnedStaging) PPT_HIP(hipHostFree(ms->pinnedStaging));
-        ms->pinnedStaging = nullptr;
-        ms->pinnedStagingBytes = 0;
-        PPT_HIP(hipHostMalloc(&ms->pinnedStaging, stagingBytes, hipHostMallocDefault));
-        ms->pinnedStagingBytes = stagingBytes;
+        if ((rc = ms->pinnedStaging.allocate(stagingBytes))) return rc;
     }
     size_t offset = 0;
     std::vector<uint8_t> changed(ms->textures.size(), 0);
@@ -416,7 +399,7 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
         DeviceTexture dt;
         if ((rc = create_device_texture(
                  ctx, textures[i], static_cast<uint8_t *>(ms->linearStaging) + offset, ms->uploadStream, &dt,
-                 static_cast<uint8_t *>(ms->pinnedStaging) + offset)))
+                 static_cast<uint8_t *>(ms->pinnedStaging.ptr) + offset)))
         {
             (void)hipStreamSynchronize(ms->uploadStream);
             return rc;
@@ -440,8 +423,7 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
         if ((t3[0] && changed[t3[0]]) || (t3[1] && changed[t3[1]]) || (t3[2] && changed[t3[2]]))
             if ((rc = rebuild_material(ctx, m, nullptr))) return rc;
     }
-    PPT_HIP(hipEventRecord(ms->uploaded, ms->uploadStream));
-    ms->uploadedRecorded = true;
+    if (const int urc = ms->uploaded.record(ms->uploadStream)) return urc;
     ms->pending = true;
     ms->changes++;
     return PROSPER_PT_OK;
@@ -478,8 +460,7 @@ int prosper_pt_update_materials(prosper_pt_ctx *ctx, const prosper_MaterialData 
         if (rc != PROSPER_PT_OK) return rc;
     }
     if (!any) return PROSPER_PT_OK;
-    PPT_HIP(hipEventRecord(ms->uploaded, ms->uploadStream));
-    ms->uploadedRecorded = true;
+    if (const int urc = ms->uploaded.record(ms->uploadStream)) return urc;
     ms->pending = true;
     ms->changes++;
     return PROSPER_PT_OK;

@@ -12,9 +12,10 @@ namespace ppt
 // What every pass checks of the scene before its arguments' extents: a scene, the meshes a worker finished meanwhile,
 // no failed transform update.  `what` names the entry point in the refusal.
 int check_scene(prosper_pt_ctx *ctx, const char *what);
-// The pending transform, light and material updates take effect on `s` before the call's first kernel: every kernel
-// the call launches after this reads the same scene and light version (mark_versions_read after the last one).
-int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s);
+// The pending transform, light and material updates are enqueued on `s` and take effect on `reader` - the stream the
+// call's kernels read the scene on, `s` itself for a pass - before the call's first kernel: every kernel the call
+// launches after this reads the same scene and light version (mark_versions_read after the last one).
+int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s, hipStream_t reader);
 // The scene and light versions a call read are free again behind its last kernel on `s`.
 int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s);
 // the camera terms of the path tracer's camera ray (RenderParams eye .. cameraToWorld)
@@ -26,9 +27,20 @@ int prepare_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, const pros
 // `ldsEntries` entries; *out is nullptr when the tree never needs more.
 int ensure_stack_overflow(
     prosper_pt_ctx *ctx, prosper_pt_ctx::RenderSlot &slot, uint32_t ldsEntries, uint32_t gridBlocks, int32_t **out);
+// a DeviceBuffer of a pass holds at least `bytes`, grown behind what `s` holds
+inline int grow_to(DeviceBuffer &b, size_t bytes, hipStream_t s)
+{
+    if (b.ptr && b.bytes >= bytes) return PROSPER_PT_OK;
+    return grow_buffer(b, GrowWait::Stream, s, bytes, bytes ? bytes : 16u);
+}
+// the context's HDR image is a whole `width` x `height` image (what a pass works on in place)
+inline bool hdr_has_extent(const prosper_pt_ctx *ctx, uint32_t width, uint32_t height)
+{
+    return ctx->hdr && ctx->localWidth == width && ctx->height == height && ctx->stripeCount <= 1u;
+}
 // A slot's workspace may be reused once the kernels of its previous user are done: `free` is recorded behind them.
-void wait_for_slot(prosper_pt_ctx::RenderSlot &slot, hipStream_t stream);
-void release_slot(prosper_pt_ctx::RenderSlot &slot, hipStream_t stream);
+inline void wait_for_slot(prosper_pt_ctx::RenderSlot &slot, hipStream_t stream) { (void)slot.free.wait(stream); }
+inline void release_slot(prosper_pt_ctx::RenderSlot &slot, hipStream_t stream) { (void)slot.free.record(stream); }
 
 #pragma GCC visibility pop
 

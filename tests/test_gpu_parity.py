@@ -1279,6 +1279,66 @@ def test_lights_updated_between_frames_in_flight(gpu_ctx, oracle):
     assert same_bits(gpu_ctx.read_hdr(), want).all()
 
 
+def test_every_kind_of_update_between_frames_in_flight_wraps_the_rings(gpu_ctx, oracle):
+    """Nine states of one scene, each with another pose of one instance, another light set and another base colour (and
+    alpha: the any-hit records follow) of one material than the state before, each updated and rendered pipelined into
+    a buffer of its own with no host synchronisation in between: the three-version rings of transforms, lights and
+    material tables wrap three times and the four-buffer staging rings twice, so versions and pinned buffers are REUSED
+    behind frames in flight.  Every image equals a fresh context's in-order render of an upload of its state."""
+    import copy
+    import ctypes
+    from prosper_amd.world import rotate_y, translate
+
+    def state(k):
+        world = scenes.cornell(with_skybox=True)
+        model, m = world.model_instances[2]
+        world.model_instances[2] = (model, translate((-0.05 * k, 0.02 * k, 0.03 * k)) @ rotate_y(0.2 * k) @ m)
+        world.add_point_light((0.3 + 0.07 * k, 0.9 - 0.05 * k, 0.4), 10.0 + 4.0 * k, (0.7 - 0.15 * k, 1.3, 0.5))
+        if k % 3 == 2:
+            world.add_spot_light((0.9, 0.3, 0.2), 60.0 + k, (-0.6, 1.7, 0.9), (0.3, -0.8, -0.4), 0.3, 0.6)
+        i = [j for j, mat in enumerate(world.materials) if mat.alphaMode == S.ALPHA_MODE_BLEND][0]
+        mat = copy.copy(world.materials[i])
+        mat.baseColorFactor = S.Vec4(0.2 + 0.08 * k, 0.4, 0.9 - 0.06 * k, 0.3 + 0.05 * k)
+        world.materials[i] = mat
+        return world
+    states = [state(k) for k in range(9)]
+    w, h = 96, 64
+    cam, fl = _camera(oracle, states[0], w, h)
+    pc = default_pc(S, fl, max_bounces=3, ibl=True)
+    hip = ctypes.CDLL("libamdhip64.so")
+    nbytes = w * h * 16
+    outs = []
+    for _ in states:
+        ptr = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(ptr), ctypes.c_size_t(nbytes)) == 0
+        outs.append(ptr)
+    gpu_ctx.upload_scene(scenes.cornell(with_skybox=True))
+    for k, world in enumerate(states):
+        gpu_ctx.update_transforms(world)
+        gpu_ctx.update_lights(world)
+        gpu_ctx.update_materials(world.materials, 0)
+        gpu_ctx.set_output_buffer(outs[k].value, nbytes)
+        gpu_ctx.render(pc, cam, w, h, frames=2, flags=S.RENDER_PIPELINED)
+    assert hip.hipDeviceSynchronize() == 0
+    gpu_ctx.set_output_buffer(0, 0)
+    images = []
+    for ptr in outs:
+        img = np.zeros((h, w, 4), np.float32)
+        assert hip.hipMemcpy(ctypes.c_void_p(img.ctypes.data), ptr, ctypes.c_size_t(nbytes), 2) == 0  # hipMemcpyDeviceToHost
+        assert hip.hipFree(ptr) == 0
+        images.append(img)
+    fresh = capi.Context(device=0)
+    try:
+        for k, world in enumerate(states):
+            fresh.upload_scene(world)
+            fresh.render(pc, cam, w, h, frames=2)
+            ok = same_bits(images[k], fresh.read_hdr()).all(axis=2)
+            assert ok.all(), "state %d: %d of %d pixels differ" % (k, (~ok).sum(), ok.size)
+        assert not same_bits(images[0], images[8]).all()  # (the states do differ)
+    finally:
+        fresh.close()
+
+
 def test_pipelined_renders_survive_changing_extents(gpu_ctx, oracle, cornell_world):
     """Frames in flight while the image extent (and with it every slot's workspace size) changes from call to call,
     growing and shrinking: each image equals the in-order render of the same call."""
