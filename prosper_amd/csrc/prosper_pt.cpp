@@ -766,6 +766,32 @@ int prosper_pt_get_debug_options(prosper_pt_ctx *ctx, prosper_pt_debug_options *
     return PROSPER_PT_OK;
 }
 
+// What a context owns from its creation on: the timed events of its renders, the work streams, the work counters, the
+// passes' state.
+static int create_context_resources(prosper_pt_ctx *ctx)
+{
+    int rc;
+    if ((rc = ctx->timeline.create())) return rc;
+    for (Stream &ws : ctx->workStreams)
+        if ((rc = ws.create())) return rc;
+    for (RenderSlot &slot : ctx->slots)
+        for (LaunchTimeline &chain : slot.chains)
+            if ((rc = chain.create())) return rc;
+    // Every work stream is used once here, so that the device's four hardware queues go to the caller's stream and these
+    // three, in this order: a stream that comes into use later (the two of prosper_pt_update_meshes, made at first need)
+    // then SHARES a queue.  Streams that claim queues before the work streams do leave two of those sharing one for the
+    // life of the context: 4 % on FlightHelmet, 2 % on S-sponza-class, 60 % on a 256 x 256 frame (profiles/r04_mesh_streams.txt).
+    for (Stream &ws : ctx->workStreams)
+    {
+        if ((rc = ctx->chainFork.record(ws.get()))) return rc;
+        PPT_HIP(hipStreamSynchronize(ws.get()));
+    }
+    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
+    const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
+    return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
+}
+
 int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_ctx)
 {
     if (!desc || !out_ctx || desc->struct_size != sizeof(prosper_pt_device_desc))
@@ -798,25 +824,7 @@ int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_c
             return fail(code, err);
         }
     }
-    bool eventsOk = true;
-    for (auto &e : ctx->events) eventsOk = eventsOk && hipEventCreate(&e) == hipSuccess;
-    for (auto &ws : ctx->workStreams) eventsOk = eventsOk && hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) == hipSuccess;
-    for (RenderSlot &slot : ctx->slots)
-        for (uint32_t i = 0; i < kMaxChains; ++i)
-        {
-            eventsOk = eventsOk && hipEventCreateWithFlags(&slot.chainJoin[i], hipEventDisableTiming) == hipSuccess;
-            for (auto &e : slot.chainEvents[i]) eventsOk = eventsOk && hipEventCreate(&e) == hipSuccess;
-        }
-    eventsOk = eventsOk && hipEventCreateWithFlags(&ctx->chainFork, hipEventDisableTiming) == hipSuccess;
-    // Every work stream is used once here, so that the device's four hardware queues go to the caller's stream and these
-    // three, in this order: a stream that comes into use later (the two of prosper_pt_update_meshes, made at first need)
-    // then SHARES a queue.  Streams that claim queues before the work streams do leave two of those sharing one for the
-    // life of the context: 4 % on FlightHelmet, 2 % on S-sponza-class, 60 % on a 256 x 256 frame (profiles/r04_mesh_streams.txt).
-    for (auto &ws : ctx->workStreams)
-        eventsOk = eventsOk && ws && hipEventRecord(ctx->chainFork, ws) == hipSuccess && hipStreamSynchronize(ws) == hipSuccess;
-    if (!eventsOk || !create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) ||
-        hipMalloc((void **)&ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long)) != hipSuccess)
+    if (create_context_resources(ctx) != PROSPER_PT_OK)
     {
         prosper_pt_destroy(ctx);
         return fail(PROSPER_PT_ERR_HIP, "context allocation failed");
@@ -836,21 +844,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_gbuffer_passes(ctx);
     destroy_dof_passes(ctx);
     destroy_bloom_passes(ctx);
-    if (ctx->dCounters) (void)hipFree(ctx->dCounters);
-    for (auto &e : ctx->events)
-        if (e) (void)hipEventDestroy(e);
-    for (RenderSlot &slot : ctx->slots)
-        for (uint32_t i = 0; i < kMaxChains; ++i)
-        {
-            for (auto &e : slot.chainEvents[i])
-                if (e) (void)hipEventDestroy(e);
-            if (slot.chainJoin[i]) (void)hipEventDestroy(slot.chainJoin[i]);
-        }
-    for (auto &ws : ctx->workStreams)
-        if (ws) (void)hipStreamDestroy(ws);
-    if (ctx->buildStream) (void)hipStreamDestroy(ctx->buildStream);
-    if (ctx->chainFork) (void)hipEventDestroy(ctx->chainFork);
-    delete ctx; // (its DeviceBuffers with it)
+    delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
 int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *scene)
@@ -1319,20 +1313,80 @@ int prosper_pt_set_output_buffer(prosper_pt_ctx *ctx, void *device_rgba32f, size
     return PROSPER_PT_OK;
 }
 
+// The wavefront pipeline's render: all frames of the batch are in flight together, in chunks that keep the workspace
+// under kMaxWavefrontSlots path slots, on render slot `slotIndex`.  `tp`: the caller's-stream timeline of a timed render.
+static int render_wavefront(
+    prosper_pt_ctx *ctx, const RenderParams &p, bool countWork, bool pipelined, uint32_t slotIndex, LaunchTimeline *tp,
+    hipStream_t s)
+{
+    const uint32_t tilesX = (p.localWidth + 7u) / 8u, tilesY = (p.height + 7u) / 8u;
+    const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64u;
+    constexpr uint64_t kMaxWavefrontSlots = 64ull << 20;
+    if (pixelsPadded > kMaxWavefrontSlots) return fail(PROSPER_PT_ERR_UNSUPPORTED, "image too large for the wavefront workspace");
+    uint32_t framesPerChunk = (uint32_t)(kMaxWavefrontSlots / pixelsPadded);
+    if (framesPerChunk > p.frameCount) framesPerChunk = p.frameCount;
+    RenderSlot &slot = ctx->slots[slotIndex];
+    ctx->lastSlot = slotIndex;
+    WavefrontChains chains;
+    chains.count = (pipelined || (ctx->flags & PROSPER_PT_CREATE_SINGLE_CHAIN)) ? 1u : 2u;
+    if (!pipelined && ctx->debug.chains >= 1u && ctx->debug.chains <= kMaxChains) chains.count = ctx->debug.chains; // tuning hook (in-order mode)
+    chains.detached = pipelined;
+    chains.fork = &ctx->chainFork;
+    for (uint32_t i = 0; i < kMaxChains; ++i)
+    {
+        chains.streams[i] = ctx->workStreams[pipelined ? slotIndex : i].get();
+        chains.join[i] = &slot.chainJoin[i];
+        // (one running timeline per chain over all chunks of the render)
+        slot.chains[i].begin();
+        chains.timers[i] = tp ? &slot.chains[i] : nullptr;
+    }
+    for (uint32_t f0 = 0; f0 < p.frameCount; f0 += framesPerChunk)
+    {
+        const uint32_t frames = (p.frameCount - f0 < framesPerChunk) ? p.frameCount - f0 : framesPerChunk;
+        WavefrontBuffers w = {};
+        // Banded batches (debug option bandedBatches = 1; round 4, profiles/r04_banded_batches.txt): every XCD's segments take
+        // the camera-ray batches of one band of the image, so that the paths an XCD traces START in one part of the scene.
+        // Measured and NOT a default: on S-sponza-class wf_trace's FETCH_SIZE moves by 3 % (2.249 -> 2.184 GB per launch) -
+        // three of its four launches trace bounce rays and sun shadows that cross the whole hall wherever they start -
+        // while the bands' unequal costs bind the step to the slowest XCD: C3 13.0 -> 13.6 ms, C4 27.2 -> 30.7,
+        // FlightHelmet (a band of sky is nearly free) 1.88 -> 2.48.
+        const bool banded = ctx->debug.bandedBatches > 0;
+        const int rc = ensure_wavefront_workspace(ctx, slot, tilesX, tilesY, frames, pipelined, banded, &w);
+        if (rc != PROSPER_PT_OK) return rc;
+        RenderParams pp = p;
+        pp.frameCount = frames;
+        pp.pc.frameIndex = (p.pc.frameIndex + f0) % PROSPER_RT_FRAME_PERIOD;
+        if (f0 > 0) pp.pc.flags &= ~(uint32_t)PROSPER_PC_FLAG_SKIP_HISTORY;
+        const WavefrontPlan plan = wavefront_plan(
+            ctx->stats.maxDepth, (uint32_t)ctx->stats.nodeCount, (uint32_t)ctx->stats.triangleCount, ctx->scene, wavefront_options(ctx));
+        int32_t *ovf = nullptr;
+        const int orc = ensure_stack_overflow(ctx, slot, plan.ldsStackEntries, wavefront_grid_blocks(w), &ovf);
+        if (orc != PROSPER_PT_OK) return orc;
+        // the slot's previous user (a render of two calls ago, or the previous chunk of this one) must be done
+        // with the workspace: detached chains wait for that on their own stream, the others on the caller's
+        chains.after = slot.free.event();
+        chains.scene = ctx->accel ? ctx->accel->sceneDone.event() : nullptr;
+        chains.lights = ctx->lights ? ctx->lights->ready.event() : nullptr;
+        chains.materials = ctx->materialState ? ctx->materialState->ready.event() : nullptr;
+        if (!pipelined) wait_for_slot(slot, s);
+        if (tp) tp->mark(kStageChains, s);
+        launch_render_wavefront(
+            ctx->scene, pp, ctx->hdr, ctx->counters.as<unsigned long long>(), w, plan, ovf, (uint32_t)ctx->stats.nodeCount,
+            (uint32_t)ctx->stats.triangleCount, countWork, tp, chains, s);
+        release_slot(slot, s);
+    }
+    if (tp) ctx->timedSlot = slotIndex;
+    return PROSPER_PT_OK;
+}
+
 int prosper_pt_render_frames(
     prosper_pt_ctx *ctx, const prosper_ReferencePC *pc, const prosper_CameraUniforms *camera, uint32_t width,
     uint32_t height, const prosper_pt_tile_desc *tile, uint32_t frame_count, uint32_t render_flags, void *stream)
 {
     if (!ctx || !pc || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_render: null argument");
-    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_render called before prosper_pt_upload_scene");
-    if (ctx->meshBuild)
-    {
-        // streamed-in meshes whose geometry a worker has finished meanwhile: from this render on they are the scene
-        const int prc = poll_mesh_build(ctx, false);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    if (ctx->accel && ctx->accel->stale && !ctx->accel->pending) // (a staged update gets its chance below)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_update_transforms failed: update the transforms again (or upload the scene) before rendering");
+    // (streamed-in meshes whose geometry a worker has finished meanwhile are the scene from this render on; a staged
+    // update gets its chance below)
+    if (const int crc = check_scene(ctx, "prosper_pt_render")) return crc;
     if (width == 0 || height == 0 || frame_count == 0)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_render: empty extent or frame count");
     if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
@@ -1360,21 +1414,19 @@ int prosper_pt_render_frames(
 
     if (localWidth == 0) return PROSPER_PT_OK;
     const bool countWork = (render_flags & PROSPER_PT_RENDER_COUNT_WORK) != 0;
-    LaunchTimer timer;
-    timer.events = ctx->events;
-    timer.stage = ctx->eventStage;
-    timer.capacity = prosper_pt_ctx::kMaxTimedLaunches;
-    LaunchTimer *tp = ctx->kernelTiming ? &timer : nullptr;
+    LaunchTimeline *tp = ctx->kernelTiming ? &ctx->timeline : nullptr;
+    // Frames in flight.  Default: the chains fork from the caller's stream, i.e. after everything enqueued on
+    // it so far, and use slot 0.  PROSPER_PT_RENDER_PIPELINED: the path stages (generate / shade / trace) of
+    // this render run as ONE chain on the next slot's stream and wait only for that slot's previous render,
+    // so they overlap the previous render's remaining work - a 2 M-path batch alone fills 55 % of the GPU,
+    // two of them 80 % (profiles/r01_pipelined.txt).  The accumulate kernel stays on the caller's stream, in
+    // order: history reads, output writes and everything the caller enqueues later see finished frames.
+    const bool pipelined = !(ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL) && (render_flags & PROSPER_PT_RENDER_PIPELINED) != 0 && !countWork;
+    const uint32_t slotIndex = pipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
     // a staged prosper_pt_update_transforms runs now, on the stream this render's path stages use: a pipelined render's own
     // chain (beside the frames in flight, which keep reading their scene version), else the caller's stream
-    const bool wavefrontPipelined = !(ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL) &&
-                                    (render_flags & PROSPER_PT_RENDER_PIPELINED) != 0 && !countWork;
-    {
-        const uint32_t nextSlot = wavefrontPipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
-        hipStream_t us = wavefrontPipelined ? ctx->workStreams[nextSlot] : s;
-        const int frc = flush_scene_updates(ctx, us, s);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
+    if (const int frc = flush_scene_updates(ctx, pipelined ? ctx->workStreams[slotIndex].get() : s, s)) return frc;
+    if (tp) tp->begin();
     if (ctx->flags & PROSPER_PT_CREATE_MEGAKERNEL)
     {
         int32_t *ovf = nullptr;
@@ -1382,83 +1434,11 @@ int prosper_pt_render_frames(
         if (orc != PROSPER_PT_OK) return orc;
         wait_for_slot(ctx->slots[0], s);
         if (tp) tp->mark(kStageGenerate, s);
-        launch_render_megakernel(ctx->scene, p, ctx->hdr, ctx->dCounters, ovf, countWork, s);
+        launch_render_megakernel(ctx->scene, p, ctx->hdr, ctx->counters.as<unsigned long long>(), ovf, countWork, s);
         release_slot(ctx->slots[0], s);
     }
-    else
-    {
-        // wavefront: all frames of the batch are in flight together, in chunks that keep the
-        // workspace under kMaxWavefrontSlots path slots
-        const uint32_t tilesX = (localWidth + 7u) / 8u, tilesY = (height + 7u) / 8u;
-        const uint64_t pixelsPadded = (uint64_t)tilesX * tilesY * 64u;
-        constexpr uint64_t kMaxWavefrontSlots = 64ull << 20;
-        if (pixelsPadded > kMaxWavefrontSlots) return fail(PROSPER_PT_ERR_UNSUPPORTED, "image too large for the wavefront workspace");
-        uint32_t framesPerChunk = (uint32_t)(kMaxWavefrontSlots / pixelsPadded);
-        if (framesPerChunk > frame_count) framesPerChunk = frame_count;
-        // Frames in flight.  Default: the chains fork from the caller's stream, i.e. after everything enqueued on
-        // it so far, and use slot 0.  PROSPER_PT_RENDER_PIPELINED: the path stages (generate / shade / trace) of
-        // this render run as ONE chain on the other slot's stream and wait only for that slot's previous render,
-        // so they overlap the previous render's remaining work - a 2 M-path batch alone fills 55 % of the GPU,
-        // two of them 80 % (profiles/r01_pipelined.txt).  The accumulate kernel stays on the caller's stream, in
-        // order: history reads, output writes and everything the caller enqueues later see finished frames.
-        const bool pipelined = (render_flags & PROSPER_PT_RENDER_PIPELINED) != 0 && !countWork;
-        const uint32_t slotIndex = pipelined ? (ctx->lastSlot + 1u) % prosper_pt_ctx::kRenderSlots : 0u;
-        RenderSlot &slot = ctx->slots[slotIndex];
-        ctx->lastSlot = slotIndex;
-        WavefrontChains chains;
-        LaunchTimer chainTimers[kMaxChains];
-        chains.count = (pipelined || (ctx->flags & PROSPER_PT_CREATE_SINGLE_CHAIN)) ? 1u : 2u;
-        if (!pipelined && ctx->debug.chains >= 1u && ctx->debug.chains <= kMaxChains) chains.count = ctx->debug.chains; // tuning hook (in-order mode)
-        chains.detached = pipelined;
-        chains.fork = ctx->chainFork;
-        for (uint32_t i = 0; i < kMaxChains; ++i)
-        {
-            chains.streams[i] = pipelined ? ctx->workStreams[slotIndex] : ctx->workStreams[i];
-            chains.join[i] = slot.chainJoin[i];
-            chainTimers[i].events = slot.chainEvents[i];
-            chainTimers[i].stage = slot.chainStage[i];
-            chainTimers[i].capacity = prosper_pt_ctx::kMaxTimedLaunches;
-            chains.timers[i] = tp ? &chainTimers[i] : nullptr;
-            slot.chainLaunches[i] = 0;
-        }
-        for (uint32_t f0 = 0; f0 < frame_count; f0 += framesPerChunk)
-        {
-            const uint32_t frames = (frame_count - f0 < framesPerChunk) ? frame_count - f0 : framesPerChunk;
-            WavefrontBuffers w = {};
-            // Banded batches (debug option bandedBatches = 1; round 4, profiles/r04_banded_batches.txt): every XCD's segments take
-            // the camera-ray batches of one band of the image, so that the paths an XCD traces START in one part of the scene.
-            // Measured and NOT a default: on S-sponza-class wf_trace's FETCH_SIZE moves by 3 % (2.249 -> 2.184 GB per launch) -
-            // three of its four launches trace bounce rays and sun shadows that cross the whole hall wherever they start -
-            // while the bands' unequal costs bind the step to the slowest XCD: C3 13.0 -> 13.6 ms, C4 27.2 -> 30.7,
-            // FlightHelmet (a band of sky is nearly free) 1.88 -> 2.48.
-            const bool banded = ctx->debug.bandedBatches > 0;
-            const int rc = ensure_wavefront_workspace(ctx, slot, tilesX, tilesY, frames, pipelined, banded, &w);
-            if (rc != PROSPER_PT_OK) return rc;
-            RenderParams pp = p;
-            pp.frameCount = frames;
-            pp.pc.frameIndex = (p.pc.frameIndex + f0) % PROSPER_RT_FRAME_PERIOD;
-            if (f0 > 0) pp.pc.flags &= ~(uint32_t)PROSPER_PC_FLAG_SKIP_HISTORY;
-            const WavefrontPlan plan = wavefront_plan(
-                ctx->stats.maxDepth, (uint32_t)ctx->stats.nodeCount, (uint32_t)ctx->stats.triangleCount, ctx->scene, wavefront_options(ctx));
-            int32_t *ovf = nullptr;
-            const int orc = ensure_stack_overflow(ctx, slot, plan.ldsStackEntries, wavefront_grid_blocks(w), &ovf);
-            if (orc != PROSPER_PT_OK) return orc;
-            // the slot's previous user (a render of two calls ago, or the previous chunk of this one) must be done
-            // with the workspace: detached chains wait for that on their own stream, the others on the caller's
-            chains.after = slot.free.event();
-            chains.scene = ctx->accel ? ctx->accel->sceneDone.event() : nullptr;
-            chains.lights = ctx->lights ? ctx->lights->ready.event() : nullptr;
-            chains.materials = ctx->materialState ? ctx->materialState->ready.event() : nullptr;
-            if (!pipelined) wait_for_slot(slot, s);
-            if (tp) tp->mark(kStageChains, s);
-            launch_render_wavefront(
-                ctx->scene, pp, ctx->hdr, ctx->dCounters, w, plan, ovf, (uint32_t)ctx->stats.nodeCount,
-                (uint32_t)ctx->stats.triangleCount, countWork, tp, chains, s);
-            release_slot(slot, s);
-        }
-        for (uint32_t i = 0; i < kMaxChains; ++i) slot.chainLaunches[i] = chainTimers[i].count;
-        if (tp) ctx->timedSlot = slotIndex;
-    }
+    else if (const int wrc = render_wavefront(ctx, p, countWork, pipelined, slotIndex, tp, s))
+        return wrc;
     PPT_HIP(hipGetLastError());
     {
         const int mrc = mark_versions_read(ctx, s);
@@ -1467,7 +1447,6 @@ int prosper_pt_render_frames(
     if (tp)
     {
         tp->close(s);
-        ctx->timedLaunches = tp->count;
         ctx->timingValid = true;
     }
     return PROSPER_PT_OK;
@@ -1578,7 +1557,7 @@ static int read_stage_counters(prosper_pt_ctx *ctx, unsigned long long host[kSta
 {
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host, ctx->dCounters, kStageCount * kCounterCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipMemcpyAsync(host, ctx->counters.ptr, kStageCount * kCounterCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     PPT_HIP(hipStreamSynchronize(s));
     return PROSPER_PT_OK;
 }
@@ -1613,7 +1592,7 @@ int prosper_pt_reset_counters(prosper_pt_ctx *ctx, void *stream)
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_reset_counters: null context");
     PPT_HIP(hipSetDevice(ctx->device));
     PPT_HIP(hipMemsetAsync(
-        ctx->dCounters, 0, kStageCount * kCounterCount * sizeof(unsigned long long), static_cast<hipStream_t>(stream)));
+        ctx->counters.ptr, 0, kStageCount * kCounterCount * sizeof(unsigned long long), static_cast<hipStream_t>(stream)));
     return PROSPER_PT_OK;
 }
 
@@ -1646,36 +1625,25 @@ int prosper_pt_get_last_render_timing(
     if (!ctx->timingValid)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "no render has run with kernel timing enabled (prosper_pt_set_kernel_timing)");
     PPT_HIP(hipSetDevice(ctx->device));
-    PPT_HIP(hipEventSynchronize(ctx->events[ctx->timedLaunches]));
+    if (const int rc = ctx->timeline.wait()) return rc;
     float perStage[PROSPER_PT_MAX_KERNELS] = {};
     uint32_t launches[PROSPER_PT_MAX_KERNELS] = {};
     float total = 0.0f;
-    for (uint32_t i = 0; i < ctx->timedLaunches; ++i)
-    {
-        float ms = 0.0f;
-        PPT_HIP(hipEventElapsedTime(&ms, ctx->events[i], ctx->events[i + 1]));
-        perStage[ctx->eventStage[i]] += ms;
-        launches[ctx->eventStage[i]] += 1;
-        total += ms;
-    }
+    if (const int rc = ctx->timeline.add_to(perStage, launches, &total)) return rc;
     // The wavefront chains: their launches ran on the internal streams, between the caller's-stream
     // events counted above as the (unnamed) chains interval.  Their durations are as the device saw
     // them, i.e. a launch that shared the GPU with the other chain's is counted in full: per-stage sums
     // can exceed the wall time in `total_ms`, which stays the caller's-stream time.
     if (perStage[kStageChains] > 0.0f || launches[kStageChains] > 0)
     {
-        bool any = false;
-        const RenderSlot &slot = ctx->slots[ctx->timedSlot];
-        for (uint32_t c = 0; c < kMaxChains; ++c)
-            for (uint32_t i = 0; i < slot.chainLaunches[c]; ++i)
-            {
-                float ms = 0.0f;
-                PPT_HIP(hipEventElapsedTime(&ms, slot.chainEvents[c][i], slot.chainEvents[c][i + 1]));
-                perStage[slot.chainStage[c][i]] += ms;
-                launches[slot.chainStage[c][i]] += 1;
-                any = true;
-            }
-        if (any)
+        uint32_t chainLaunches = 0;
+        float chainMs = 0.0f; // (not part of the total)
+        for (const LaunchTimeline &chain : ctx->slots[ctx->timedSlot].chains)
+        {
+            if (const int rc = chain.add_to(perStage, launches, &chainMs)) return rc;
+            chainLaunches += chain.intervals();
+        }
+        if (chainLaunches)
         {
             perStage[kStageChains] = 0.0f;
             launches[kStageChains] = 0;

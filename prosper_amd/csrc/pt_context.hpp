@@ -190,7 +190,7 @@ struct MaterialState
     bool pending = false;          // the mirrors differ from version `cur`
     uint64_t changes = 0;          // bumped whenever an update changed a mirror (a background geometry build compares)
     bool pendingAlphaPatch = false; // ... in a MASK / BLEND material: the any-hit records' copies must follow
-    hipStream_t uploadStream = nullptr; // texel copies, re-tiling / BC7 decode, packs, alpha bounds of an update
+    Stream uploadStream;                // texel copies, re-tiling / BC7 decode, packs, alpha bounds of an update
     Fence uploaded;                     // behind the last of them
     Fence ready;                        // behind the last flush: every later render's chains wait for it
     void *linearStaging = nullptr;      // device: the texels of an update as the caller holds them, before re-tiling
@@ -204,7 +204,6 @@ struct MaterialState
     static constexpr uint64_t kRetireBytes = 256ull << 20;
     ~MaterialState()
     {
-        if (uploadStream) (void)hipStreamDestroy(uploadStream);
         if (linearStaging) (void)hipFree(linearStaging);
     }
 };
@@ -270,8 +269,8 @@ struct prosper_pt_ctx
     std::vector<ppt::AccelState *> retiredAccel;  // replaced generations: frames in flight may still use their events / staging
     std::mutex allocMutex;                        // sceneAllocations / sceneBytes (the worker thread allocates too)
     // the worker thread's stream: a plain one, made by the worker at first need - after prosper_pt_create has given the
-    // hardware queues to the work streams (ensure_build_stream)
-    hipStream_t buildStream = nullptr;
+    // hardware queues to the work streams (pt_geometry.cpp, "streamed-in meshes")
+    ppt::Stream buildStream;
     // Pinned staging for the large host <-> device copies of a geometry build (pt_geometry.cpp staged_copy): a copy from
     // pageable memory has the runtime pin the caller's pages for its duration, and when those pages are freed soon after - the
     // builder's vectors are - the unmapping goes through the GPU driver and stops every queue of the process for 20-30 ms
@@ -283,16 +282,13 @@ struct prosper_pt_ctx
     size_t externalHdrBytes = 0;
     uint32_t localWidth = 0, height = 0;
 
-    unsigned long long *dCounters = nullptr; // kStageCount x 16 u64: one block of work counters per kernel stage
+    ppt::DeviceBuffer counters; // kStageCount x kCounterCount u64: one block of work counters per kernel stage
     // wavefront workspace (one allocation, carved into the WavefrontBuffers arrays)
     // global overflow of the traversal stacks (only for trees whose stack bound exceeds the LDS stack)
     uint64_t wfSlots = 0;
 
     bool kernelTiming = false;
-    static constexpr uint32_t kMaxTimedLaunches = 96;
-    hipEvent_t events[kMaxTimedLaunches + 1] = {};
-    uint32_t eventStage[kMaxTimedLaunches] = {};
-    uint32_t timedLaunches = 0;
+    ppt::LaunchTimeline timeline; // the caller's stream of the last timed render
     bool timingValid = false;
 
     ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
@@ -303,17 +299,15 @@ struct prosper_pt_ctx
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
-    // workspace, the stack-overflow array and the two launch chains (pt_kernels.hpp WavefrontChains) with their
-    // timing events.  kRenderSlots slots = that many frames in flight (PROSPER_PT_RENDER_PIPELINED), the role `nextFrame` and
+    // workspace, the stack-overflow array and the launch chains (pt_kernels.hpp WavefrontChains) with their
+    // timelines.  kRenderSlots slots = that many frames in flight (PROSPER_PT_RENDER_PIPELINED), the role `nextFrame` and
     // the per-frame descriptor sets play in RtReference::record; everything else uses slot 0.
     struct RenderSlot
     {
         ppt::DeviceBuffer stackOverflow;
         ppt::DeviceBuffer wfBlock;
-        hipEvent_t chainJoin[ppt::kMaxChains] = {};
-        hipEvent_t chainEvents[ppt::kMaxChains][kMaxTimedLaunches + 1] = {};
-        uint32_t chainStage[ppt::kMaxChains][kMaxTimedLaunches] = {};
-        uint32_t chainLaunches[ppt::kMaxChains] = {};
+        ppt::Fence chainJoin[ppt::kMaxChains];
+        ppt::LaunchTimeline chains[ppt::kMaxChains];
         ppt::Fence free; // recorded after the accumulate kernel of the slot's last render
     };
     // prosper keeps two frames in flight; a third one fills the machine better at the batch sizes of a multi-GPU
@@ -322,11 +316,11 @@ struct prosper_pt_ctx
     // The internal streams, three in all (+ the caller's = the four hardware queues of the device; more streams
     // share queues and serialise): a pipelined render's chain runs on workStreams[slot], the two chains of an
     // in-order render on workStreams[0] and [1].  All ordering between them goes through events.
-    hipStream_t workStreams[kRenderSlots] = {};
+    ppt::Stream workStreams[kRenderSlots];
     RenderSlot slots[kRenderSlots];
     uint32_t lastSlot = 0;  // of the last render
     uint32_t timedSlot = 0; // of the last render that ran with kernel timing on (timing readout)
-    hipEvent_t chainFork = nullptr;
+    ppt::Fence chainFork;
 
     // stripe partition of the last render (prosper_pt_tile_desc) and the multi-GPU gather state
     uint32_t lastWidth = 0;

@@ -462,18 +462,13 @@ void discard_mesh_build(prosper_pt_ctx *ctx)
 }
 
 // ---- streamed-in meshes: the new geometry is made by a worker thread, beside the frame loop ----
-// The worker's stream, made by the worker thread the first time a context needs it - AFTER prosper_pt_create has given the
+// The worker's stream (ctx->buildStream), made by the worker thread the first time a context needs it - AFTER prosper_pt_create has given the
 // device's hardware queues to the work streams: a plain stream, which then shares a queue with one of those.  What the worker
 // enqueues (copies, a few dozen small kernels) waits behind the frames already queued there - three with a paced host, a
 // few milliseconds per build.  A high-priority stream gets a hardware queue of its own and never waits, but its first use costs
 // 20 ms, and more queues alive cost the frame loop 2-5 % with frames in flight and 10-17 % in order; a plain stream that claims
 // a queue BEFORE the work streams do leaves two of those sharing one (profiles/r04_mesh_streams.txt).  Its creation takes 7 ms:
 // on the worker, not in the frame loop.
-static int ensure_build_stream(prosper_pt_ctx *ctx)
-{
-    if (!ctx->buildStream) PPT_HIP(hipStreamCreateWithFlags(&ctx->buildStream, hipStreamNonBlocking));
-    return PROSPER_PT_OK;
-}
 
 // A worker for what the mirrors hold now (the caller has made sure none is running).
 static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild);
@@ -552,9 +547,9 @@ static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild)
         ppt::g_allocationLog = &b->allocations;
         auto run = [&]() -> int {
             PPT_HIP(hipSetDevice(device));
-            int r = ensure_build_stream(ctx);
+            int r = ctx->buildStream.create();
             if (r != PROSPER_PT_OK) return r;
-            t.stream = ctx->buildStream;
+            t.stream = ctx->buildStream.get();
             // the arrived meshes: new geometry buffers, bytes, metadata entries
             GeometryState *gs = ctx->geometry;
             for (const GeometryState::ArrivedMesh &a : b->arrived)
@@ -646,7 +641,7 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
             // the meshes wait for the next prosper_pt_update_meshes / _finish_mesh_updates
             const std::string why = b->error;
             // nothing of it was ever installed: once its stream is idle its arrays can go
-            if (ctx->buildStream) (void)hipStreamSynchronize(ctx->buildStream);
+            if (ctx->buildStream.get()) (void)hipStreamSynchronize(ctx->buildStream.get());
             for (GeometryState::ArrivedMesh &a : gs->arrived) b->arrived.push_back(std::move(a)); // (those that came meanwhile, behind)
             gs->arrived.swap(b->arrived);
             for (void *p : b->allocations) device_free(ctx, p);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_scene.hpp"
+#include "pt_sync.hpp"
 
 namespace ppt
 {
@@ -16,29 +17,6 @@ enum : uint32_t
     kStageTrace = 2,
     kStageAccumulate = 3,
     kStageCount = 4,
-};
-
-// Optional per-launch hipEvent timestamps (prosper_pt_set_kernel_timing): one event before every
-// launch, one after the last; interval i belongs to stage[i].
-struct LaunchTimer
-{
-    hipEvent_t *events = nullptr;
-    uint32_t *stage = nullptr;
-    uint32_t count = 0; // intervals recorded so far (events used = count + 1 once closed)
-    uint32_t capacity = 0;
-    void mark(uint32_t st, hipStream_t stream)
-    {
-        if (events && count < capacity)
-        {
-            (void)hipEventRecord(events[count], stream);
-            stage[count] = st;
-            ++count;
-        }
-    }
-    void close(hipStream_t stream)
-    {
-        if (events) (void)hipEventRecord(events[count], stream);
-    }
 };
 
 void launch_flatten_triangles(
@@ -66,7 +44,7 @@ void launch_render_megakernel(
     const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, int32_t *stackOverflow,
     bool countWork, hipStream_t stream);
 // The wavefront pipeline runs its segment groups as `count` independent chains of launches (generate,
-// shade/trace per bounce), chain i on streams[i] with its own launch timer, forked from and joined back
+// shade/trace per bounce), chain i on streams[i] with its own launch timeline, forked from and joined back
 // into the caller's stream around them; the accumulate kernel follows on the caller's stream.  With
 // count == 1 (or a batch too small to split) everything runs on the caller's stream.
 // `detached`: the (single) chain runs on streams[0] without forking from the caller's stream - it waits only
@@ -81,9 +59,9 @@ struct WavefrontChains
     hipEvent_t lights = nullptr; // the last prosper_pt_update_lights
     hipEvent_t materials = nullptr; // the last prosper_pt_update_textures / _materials
     hipStream_t streams[kMaxChains] = {};
-    hipEvent_t fork = nullptr;
-    hipEvent_t join[kMaxChains] = {};
-    LaunchTimer *timers[kMaxChains] = {};
+    Fence *fork = nullptr;
+    Fence *join[kMaxChains] = {};
+    LaunchTimeline *timers[kMaxChains] = {}; // (pt_sync.hpp; nullptr: untimed)
 };
 // Which traversal-kernel variants a render of a tree with this stack bound takes, and the global scratch they need
 struct WavefrontPlan
@@ -105,7 +83,7 @@ WavefrontPlan wavefront_plan(
 // `scratch`: plan.scratchDwordsPerBlock ints per workgroup of the launch grid (nullptr when that is 0)
 void launch_render_wavefront(
     const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, const WavefrontBuffers &w,
-    const WavefrontPlan &plan, int32_t *scratch, uint32_t nodeCount, uint32_t triCount, bool countWork, LaunchTimer *timer,
+    const WavefrontPlan &plan, int32_t *scratch, uint32_t nodeCount, uint32_t triCount, bool countWork, LaunchTimeline *timer,
     const WavefrontChains &chains, hipStream_t stream);
 // LDS stack entries (16/24/32) the wavefront traversal kernels use for a tree with this stack bound
 uint32_t wavefront_lds_stack_entries(uint32_t stackBound, uint32_t forced);

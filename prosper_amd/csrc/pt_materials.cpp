@@ -151,13 +151,6 @@ int build_alpha_material(
 namespace
 {
 
-int ensure_update_state(prosper_pt_ctx *ctx)
-{
-    MaterialState *ms = ctx->materialState;
-    if (!ms->uploadStream) PPT_HIP(hipStreamCreateWithFlags(&ms->uploadStream, hipStreamNonBlocking));
-    return PROSPER_PT_OK;
-}
-
 bool wide_packs(const prosper_pt_ctx *ctx)
 {
     // compact packs where the texels outgrow the caches; debug option widePacks = 1 / 0 forces either kind
@@ -223,7 +216,7 @@ int rebuild_material(prosper_pt_ctx *ctx, uint32_t i, const prosper_MaterialData
     if (!(previous && same_pack_inputs(*previous, m) && packKindKept))
     {
         MaterialPack pk;
-        if ((rc = build_material_pack(ctx, m, ms->textures, ctx->debug.noTexturePacks != 0, wide, ms->uploadStream, &pk))) return rc;
+        if ((rc = build_material_pack(ctx, m, ms->textures, ctx->debug.noTexturePacks != 0, wide, ms->uploadStream.get(), &pk))) return rc;
         if ((pk.texels != nullptr) != (ms->packs[i].texels != nullptr)) ms->packedMaterials += pk.texels ? 1u : ~0u;
         retire(ctx, ms->packs[i].texels);
         ms->packs[i] = pk;
@@ -241,7 +234,7 @@ int rebuild_material(prosper_pt_ctx *ctx, uint32_t i, const prosper_MaterialData
     {
         AlphaMaterial am;
         uint64_t bytes = 0;
-        if ((rc = build_alpha_material(ctx, m, ms->textures, ms->samplers, ms->uploadStream, &am, &bytes))) return rc;
+        if ((rc = build_alpha_material(ctx, m, ms->textures, ms->samplers, ms->uploadStream.get(), &am, &bytes))) return rc;
         ms->alphaBoundBytes += bytes;
         ms->alphaBoundBytes -= std::min<uint64_t>(ms->alphaBoundBytes, allocation_bytes(ctx, old.bounds));
         retire(ctx, old.bounds);
@@ -289,7 +282,7 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
         if ((rc = device_alloc(ctx, ms->blockBytes, &d))) return rc;
         ms->dBlocks[v] = static_cast<uint8_t *>(d);
     }
-    if ((rc = ensure_update_state(ctx))) return rc;
+    if ((rc = ms->uploadStream.create())) return rc;
     uint8_t *img = nullptr;
     if ((rc = ms->staging.acquire(ms->blockBytes, false, &img))) return rc;
     std::memcpy(img, ms->materials.data(), ms->materials.size() * sizeof(prosper_MaterialData));
@@ -373,7 +366,7 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
                                                     ", which kept no texels of its own at upload (only packed materials sampled it): update it in the same call");
     }
     PPT_HIP(hipSetDevice(ctx->device));
-    int rc = ensure_update_state(ctx);
+    int rc = ms->uploadStream.create();
     if (rc == PROSPER_PT_OK) rc = collect_retired(ctx);
     if (rc != PROSPER_PT_OK) return rc;
     // the previous update's copies out of the pinned staging area (a frame ago, as a rule: done long since)
@@ -398,10 +391,10 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
     {
         DeviceTexture dt;
         if ((rc = create_device_texture(
-                 ctx, textures[i], static_cast<uint8_t *>(ms->linearStaging) + offset, ms->uploadStream, &dt,
+                 ctx, textures[i], static_cast<uint8_t *>(ms->linearStaging) + offset, ms->uploadStream.get(), &dt,
                  static_cast<uint8_t *>(ms->pinnedStaging.ptr) + offset)))
         {
-            (void)hipStreamSynchronize(ms->uploadStream);
+            (void)hipStreamSynchronize(ms->uploadStream.get());
             return rc;
         }
         offset += texture_staging_bytes(textures[i]);
@@ -423,7 +416,7 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
         if ((t3[0] && changed[t3[0]]) || (t3[1] && changed[t3[1]]) || (t3[2] && changed[t3[2]]))
             if ((rc = rebuild_material(ctx, m, nullptr))) return rc;
     }
-    if (const int urc = ms->uploaded.record(ms->uploadStream)) return urc;
+    if (const int urc = ms->uploaded.record(ms->uploadStream.get())) return urc;
     ms->pending = true;
     ms->changes++;
     return PROSPER_PT_OK;
@@ -449,7 +442,7 @@ int prosper_pt_update_materials(prosper_pt_ctx *ctx, const prosper_MaterialData 
         if (!any)
         {
             PPT_HIP(hipSetDevice(ctx->device));
-            int rc = ensure_update_state(ctx);
+            int rc = ms->uploadStream.create();
             if (rc == PROSPER_PT_OK) rc = collect_retired(ctx);
             if (rc != PROSPER_PT_OK) return rc;
         }
@@ -460,7 +453,7 @@ int prosper_pt_update_materials(prosper_pt_ctx *ctx, const prosper_MaterialData 
         if (rc != PROSPER_PT_OK) return rc;
     }
     if (!any) return PROSPER_PT_OK;
-    if (const int urc = ms->uploaded.record(ms->uploadStream)) return urc;
+    if (const int urc = ms->uploaded.record(ms->uploadStream.get())) return urc;
     ms->pending = true;
     ms->changes++;
     return PROSPER_PT_OK;

@@ -1,6 +1,7 @@
 // pt_sync.hpp — the owners of the frame loop's synchronisation (private): an event that knows whether it was recorded,
-// the version ring of a resource that changes under frames in flight, the pinned staging ring of its updates, a pass's
-// timed events.  Only the HIP runtime API: tests/sync_rings_main.cpp drives them on a CPU against fakes of it.
+// a stream, the version ring of a resource that changes under frames in flight, the pinned staging ring of its updates,
+// the timed events of a pass and of a render's launches.  The only file of the library that creates or destroys an
+// event or a stream.  Only the HIP runtime API: tests/sync_rings_main.cpp drives them on a CPU against fakes of it.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -49,6 +50,22 @@ class Fence : NoCopy
   private:
     hipEvent_t ev = nullptr;
     bool recorded = false;
+};
+
+// One non-blocking stream, destroyed with its owner.  A create() that failed leaves it empty.
+class Stream : NoCopy
+{
+  public:
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    int create()
+    {
+        if (!s) PPT_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return PROSPER_PT_OK;
+    }
+    hipStream_t get() const { return s; }
+
+  private:
+    hipStream_t s = nullptr;
 };
 
 // Pinned host memory, freed with its owner.
@@ -149,11 +166,11 @@ template <class T> class StagingRing
     bool held = false; // acquired, and the copy not enqueued yet
 };
 
-// The timed events around the N stages of a pass (LaunchTimer-free passes: IBL, depth of field, bloom).
-template <uint32_t N> struct StageEvents : NoCopy
+// N events with timing, made by create() (again after a failure: only the missing ones) and destroyed with their owner.
+template <uint32_t N> struct TimedEvents : NoCopy
 {
-    hipEvent_t events[N + 1] = {};
-    ~StageEvents()
+    hipEvent_t events[N] = {};
+    ~TimedEvents()
     {
         for (hipEvent_t e : events)
             if (e) (void)hipEventDestroy(e);
@@ -164,14 +181,64 @@ template <uint32_t N> struct StageEvents : NoCopy
             if (!e) PPT_HIP(hipEventCreate(&e));
         return PROSPER_PT_OK;
     }
-    bool created() const { return events[N] != nullptr; }
+};
+
+// The timed events around the N stages of a pass (IBL, depth of field, bloom, the multi-GPU gather).
+template <uint32_t N> struct StageEvents : TimedEvents<N + 1>
+{
+    bool created() const { return this->events[N] != nullptr; }
     // waits for the last stage; ms[k] = what stage k took
     int elapsed(float *ms) const
     {
-        PPT_HIP(hipEventSynchronize(events[N]));
-        for (uint32_t k = 0; k < N; ++k) PPT_HIP(hipEventElapsedTime(&ms[k], events[k], events[k + 1u]));
+        PPT_HIP(hipEventSynchronize(this->events[N]));
+        for (uint32_t k = 0; k < N; ++k) PPT_HIP(hipEventElapsedTime(&ms[k], this->events[k], this->events[k + 1u]));
         return PROSPER_PT_OK;
     }
+};
+
+// Per-launch timestamps of a render (prosper_pt_set_kernel_timing): one event before every launch of a stream, one after
+// the last; interval i belongs to stage[i].  A launcher that is handed no timeline (nullptr) runs untimed.
+constexpr uint32_t kMaxTimedLaunches = 96;
+class LaunchTimeline : TimedEvents<kMaxTimedLaunches + 1>
+{
+  public:
+    using TimedEvents::create;
+    void begin() { count = 0; }
+    // (launches beyond the capacity go untimed)
+    void mark(uint32_t st, hipStream_t stream)
+    {
+        if (count < kMaxTimedLaunches)
+        {
+            (void)hipEventRecord(events[count], stream);
+            stage[count] = st;
+            ++count;
+        }
+    }
+    void close(hipStream_t stream) { (void)hipEventRecord(events[count], stream); }
+    uint32_t intervals() const { return count; }
+    // the host waits for the closing event
+    int wait() const
+    {
+        PPT_HIP(hipEventSynchronize(events[count]));
+        return PROSPER_PT_OK;
+    }
+    // every interval into its stage's milliseconds and launch count, and into *total
+    int add_to(float *stageMs, uint32_t *stageLaunches, float *total) const
+    {
+        for (uint32_t i = 0; i < count; ++i)
+        {
+            float ms = 0.0f;
+            PPT_HIP(hipEventElapsedTime(&ms, events[i], events[i + 1u]));
+            stageMs[stage[i]] += ms;
+            stageLaunches[stage[i]] += 1;
+            *total += ms;
+        }
+        return PROSPER_PT_OK;
+    }
+
+  private:
+    uint32_t stage[kMaxTimedLaunches] = {};
+    uint32_t count = 0; // intervals recorded so far (events used = count + 1 once closed)
 };
 
 } // namespace ppt

@@ -92,17 +92,14 @@ struct TilingState
     ncclComm_t comm = nullptr;
     bool ownsComm = false;
     uint32_t rank = 0, ranks = 1;
-    hipStream_t commStream = nullptr; // the gather + de-interleave run here, beside the next frame's path stages
-    hipEvent_t tileReady = nullptr;   // recorded on the caller's stream: the tile's accumulate kernel is done
-    hipEvent_t gatherDone = nullptr;  // recorded on the comm stream behind gather (+ de-interleave on the root)
-    bool gatherPending = false;
-    hipEvent_t gatherT0 = nullptr, gatherT1 = nullptr; // timing events around the last gather (+ de-interleave), on its stream
-    bool gatherTimed = false;
+    Stream commStream; // the gather + de-interleave run here, beside the next frame's path stages
+    Fence tileReady;   // recorded on the caller's stream: the tile's accumulate kernel is done
+    Fence gatherDone;  // recorded on the comm stream behind gather (+ de-interleave on the root), unless it ran in-stream
+    StageEvents<1> gatherTimes; // around the last gather (+ de-interleave), on its stream
+    bool gatherTimed = false;   // ... both recorded: created alone does not say so (the events are made with the state)
     uint32_t gathers = 0;
-    float4 *staging = nullptr; // root: the ranks' tiles back to back, rank order
-    size_t stagingBytes = 0;
-    float4 *ownedFull = nullptr; // root: the gathered image when the caller passes no destination
-    size_t ownedFullBytes = 0;
+    DeviceBuffer staging;   // root: the ranks' tiles back to back, rank order
+    DeviceBuffer ownedFull; // root: the gathered image when the caller passes no destination
     float4 *lastFull = nullptr; // where the last gather put the image (root)
     uint32_t lastFullWidth = 0, lastFullHeight = 0;
 };
@@ -121,15 +118,8 @@ void destroy_tiling(prosper_pt_ctx *ctx)
     TilingState *t = ctx->tiling;
     if (!t) return;
     (void)hipSetDevice(ctx->device); // one thread may drive several contexts: everything below belongs to this one's GPU
-    if (t->commStream) (void)hipStreamSynchronize(t->commStream);
+    if (t->commStream.get()) (void)hipStreamSynchronize(t->commStream.get());
     if (t->comm && t->ownsComm && rccl().commDestroy) (void)rccl().commDestroy(t->comm);
-    if (t->staging) (void)hipFree(t->staging);
-    if (t->ownedFull) (void)hipFree(t->ownedFull);
-    if (t->tileReady) (void)hipEventDestroy(t->tileReady);
-    if (t->gatherDone) (void)hipEventDestroy(t->gatherDone);
-    if (t->gatherT0) (void)hipEventDestroy(t->gatherT0);
-    if (t->gatherT1) (void)hipEventDestroy(t->gatherT1);
-    if (t->commStream) (void)hipStreamDestroy(t->commStream);
     delete t;
     ctx->tiling = nullptr;
 }
@@ -137,7 +127,7 @@ void destroy_tiling(prosper_pt_ctx *ctx)
 void wait_for_gather_before_writing_tile(prosper_pt_ctx *ctx, hipStream_t stream)
 {
     TilingState *t = ctx->tiling;
-    if (t && t->gatherPending) (void)hipStreamWaitEvent(stream, t->gatherDone, 0);
+    if (t) (void)t->gatherDone.wait(stream);
 }
 
 } // namespace ppt
@@ -151,23 +141,15 @@ int ensure_state(prosper_pt_ctx *ctx)
     PPT_HIP(hipSetDevice(ctx->device));
     TilingState *t = new (std::nothrow) TilingState();
     if (!t) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-    // published only once it is whole: a half-made state (no stream, null events) must never be seen by a later call
+    // published only once it is whole: a half-made state (no stream, no timed events) must never be seen by a later call
     // (the communication stream is a fifth stream beside the caller's and the three work streams: it shares a hardware
     // queue with one of them, so a gather can queue behind a path stage - it still overlaps the other frames' stages)
-    hipError_t e = hipStreamCreateWithFlags(&t->commStream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->tileReady, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->gatherDone, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreate(&t->gatherT0);
-    if (e == hipSuccess) e = hipEventCreate(&t->gatherT1);
-    if (e != hipSuccess)
+    int rc = t->commStream.create();
+    if (rc == PROSPER_PT_OK) rc = t->gatherTimes.create();
+    if (rc != PROSPER_PT_OK)
     {
-        if (t->tileReady) (void)hipEventDestroy(t->tileReady);
-        if (t->gatherDone) (void)hipEventDestroy(t->gatherDone);
-        if (t->gatherT0) (void)hipEventDestroy(t->gatherT0);
-        if (t->gatherT1) (void)hipEventDestroy(t->gatherT1);
-        if (t->commStream) (void)hipStreamDestroy(t->commStream);
         delete t;
-        return fail(PROSPER_PT_ERR_HIP, std::string("multi-GPU state: ") + hipGetErrorString(e));
+        return rc;
     }
     ctx->tiling = t;
     return PROSPER_PT_OK;
@@ -292,16 +274,9 @@ int prosper_pt_gather_tiles(
     {
         // no destination: the context keeps the gathered image (prosper_pt_get_gathered_device_ptr / _read_gathered)
         const size_t need = (size_t)width * height * sizeof(float4);
-        if (t->ownedFullBytes < need)
-        {
-            PPT_HIP(hipDeviceSynchronize());
-            if (t->ownedFull) PPT_HIP(hipFree(t->ownedFull));
-            t->ownedFull = nullptr;
-            t->ownedFullBytes = 0;
-            PPT_HIP(hipMalloc((void **)&t->ownedFull, need ? need : 16));
-            t->ownedFullBytes = need;
-        }
-        device_full_rgba32f = t->ownedFull;
+        if (t->ownedFull.bytes < need)
+            if ((rc = grow_buffer(t->ownedFull, GrowWait::Device, nullptr, need, need ? need : 16))) return rc;
+        device_full_rgba32f = t->ownedFull.ptr;
     }
     if (isRoot)
     {
@@ -311,21 +286,21 @@ int prosper_pt_gather_tiles(
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool inStream = (flags & PROSPER_PT_GATHER_IN_STREAM) != 0;
-    hipStream_t cs = inStream ? s : t->commStream;
+    hipStream_t cs = inStream ? s : t->commStream.get();
     if (!inStream)
     {
         // the tile is complete once everything enqueued on the caller's stream so far has run
-        PPT_HIP(hipEventRecord(t->tileReady, s));
-        PPT_HIP(hipStreamWaitEvent(cs, t->tileReady, 0));
+        if ((rc = t->tileReady.record(s))) return rc;
+        if ((rc = t->tileReady.wait(cs))) return rc;
     }
-    else if (t->gatherPending)
-        PPT_HIP(hipStreamWaitEvent(s, t->gatherDone, 0)); // staging is still in use by the previous gather
+    else if ((rc = t->gatherDone.wait(s))) // staging is still in use by the previous gather
+        return rc;
 
     TileLayout layout;
     rc = fill_layout(width, height, ctx->stripeWidth, ranks, &layout);
     if (rc != PROSPER_PT_OK) return rc;
     const size_t myCount = (size_t)ctx->localWidth * height * 4u; // floats
-    PPT_HIP(hipEventRecord(t->gatherT0, cs));
+    PPT_HIP(hipEventRecord(t->gatherTimes.events[0], cs));
     if (ranks == 1 && !t->comm)
     {
         if (device_full_rgba32f != ctx->hdr)
@@ -336,21 +311,15 @@ int prosper_pt_gather_tiles(
         if (isRoot)
         {
             const size_t need = (size_t)width * height * sizeof(float4);
-            if (t->stagingBytes < need)
-            {
-                PPT_HIP(hipStreamSynchronize(t->commStream));
-                if (t->staging) PPT_HIP(hipFree(t->staging));
-                t->staging = nullptr;
-                t->stagingBytes = 0;
-                PPT_HIP(hipMalloc((void **)&t->staging, need));
-                t->stagingBytes = need;
-            }
+            if (t->staging.bytes < need)
+                if ((rc = grow_buffer(t->staging, GrowWait::Stream, t->commStream.get(), need, need))) return rc;
         }
+        float4 *staging = t->staging.as<float4>();
         bool equal = true;
         for (uint32_t r = 1; r < ranks; ++r) equal = equal && layout.localWidth[r] == layout.localWidth[0];
         if (equal)
             // the one data-path collective: every rank's RGBA32F tile to the root (rccl.h ncclGather)
-            PPT_NCCL(rccl().gather(ctx->hdr, isRoot ? t->staging : nullptr, myCount, ncclFloat, (int)root, t->comm, cs));
+            PPT_NCCL(rccl().gather(ctx->hdr, isRoot ? staging : nullptr, myCount, ncclFloat, (int)root, t->comm, cs));
         else
         {
             // stripe counts that do not divide over the ranks: grouped send / recv with per-rank counts
@@ -359,25 +328,21 @@ int prosper_pt_gather_tiles(
             if (isRoot)
                 for (uint32_t r = 0; r < ranks && r1 == ncclSuccess; ++r)
                     r1 = rccl().recv(
-                        t->staging + layout.tileOffset[r], (size_t)layout.localWidth[r] * height * 4u, ncclFloat, (int)r, t->comm, cs);
+                        staging + layout.tileOffset[r], (size_t)layout.localWidth[r] * height * 4u, ncclFloat, (int)r, t->comm, cs);
             const ncclResult_t r2 = rccl().groupEnd();
             PPT_NCCL(r1);
             PPT_NCCL(r2);
         }
         if (isRoot)
         {
-            launch_deinterleave_tiles(t->staging, layout, static_cast<float4 *>(device_full_rgba32f), cs);
+            launch_deinterleave_tiles(staging, layout, static_cast<float4 *>(device_full_rgba32f), cs);
             PPT_HIP(hipGetLastError());
         }
     }
-    PPT_HIP(hipEventRecord(t->gatherT1, cs));
+    PPT_HIP(hipEventRecord(t->gatherTimes.events[1], cs));
     t->gatherTimed = true;
     t->gathers++;
-    if (!inStream)
-    {
-        PPT_HIP(hipEventRecord(t->gatherDone, cs));
-        t->gatherPending = true;
-    }
+    if (!inStream) return t->gatherDone.record(cs);
     return PROSPER_PT_OK;
 }
 
@@ -400,12 +365,7 @@ int prosper_pt_comm_query(prosper_pt_ctx *ctx, prosper_pt_comm_info *out)
     }
     out->gathers = t->gathers;
     if (t->gatherTimed)
-    {
-        PPT_HIP(hipEventSynchronize(t->gatherT1));
-        float ms = 0.0f;
-        PPT_HIP(hipEventElapsedTime(&ms, t->gatherT0, t->gatherT1));
-        out->lastGatherMs = ms;
-    }
+        if (const int rc = t->gatherTimes.elapsed(&out->lastGatherMs)) return rc;
     return PROSPER_PT_OK;
 }
 
@@ -429,7 +389,7 @@ int prosper_pt_read_gathered(prosper_pt_ctx *ctx, float *rgba32f, size_t byte_si
     if (byte_size < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gathered: destination too small");
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (t->gatherPending) PPT_HIP(hipStreamWaitEvent(s, t->gatherDone, 0));
+    if (const int rc = t->gatherDone.wait(s)) return rc;
     PPT_HIP(hipMemcpyAsync(rgba32f, t->lastFull, bytes, hipMemcpyDeviceToHost, s));
     PPT_HIP(hipStreamSynchronize(s));
     return PROSPER_PT_OK;
@@ -439,8 +399,7 @@ int prosper_pt_gather_wait(prosper_pt_ctx *ctx, void *stream)
 {
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_gather_wait: null context");
     TilingState *t = ctx->tiling;
-    if (t && t->gatherPending) PPT_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), t->gatherDone, 0));
-    return PROSPER_PT_OK;
+    return t ? t->gatherDone.wait(static_cast<hipStream_t>(stream)) : PROSPER_PT_OK;
 }
 
 } // extern "C"

@@ -794,7 +794,7 @@ __global__ __launch_bounds__(256) void wf_accumulate(
 template <bool COUNT, int STACK, bool LDS_SCENE>
 static void enqueue_wavefront(
     const DeviceScene &s, const RenderParams &p, unsigned long long *counters, const WavefrontBuffers &w,
-    const WavefrontPlan &plan, uint32_t nodeCount, uint32_t triCount, int32_t *stackOverflow, LaunchTimer *timer,
+    const WavefrontPlan &plan, uint32_t nodeCount, uint32_t triCount, int32_t *stackOverflow, LaunchTimeline *timer,
     hipStream_t stream)
 {
     unsigned long long *cGen = counters + kStageGenerate * kCounterCount, *cShade = counters + kStageShade * kCounterCount,
@@ -878,7 +878,7 @@ WavefrontPlan wavefront_plan(
 template <bool COUNT>
 static void enqueue_for_stack(
     const DeviceScene &s, const RenderParams &p, unsigned long long *counters, const WavefrontBuffers &w,
-    const WavefrontPlan &plan, int32_t *stackOverflow, uint32_t nodeCount, uint32_t triCount, LaunchTimer *timer,
+    const WavefrontPlan &plan, int32_t *stackOverflow, uint32_t nodeCount, uint32_t triCount, LaunchTimeline *timer,
     hipStream_t stream)
 {
     // a scene of a few KB is traversed out of LDS
@@ -895,7 +895,7 @@ static void enqueue_for_stack(
 void launch_render_wavefront(
     const DeviceScene &s, const RenderParams &p, float4 *hdr, unsigned long long *counters, const WavefrontBuffers &w,
     const WavefrontPlan &plan, int32_t *stackOverflow, uint32_t nodeCount, uint32_t triCount, bool countWork,
-    LaunchTimer *timer, const WavefrontChains &chains, hipStream_t stream)
+    LaunchTimeline *timer, const WavefrontChains &chains, hipStream_t stream)
 {
     if (w.nSeg == 0) return;
     static_assert(kTraversalStackDepth == 32, "largest LDS stack variant");
@@ -907,7 +907,7 @@ void launch_render_wavefront(
     const uint32_t per = (groups + parts - 1u) / parts;
     // (detached chains - frames in flight - do not fork from the caller's stream: they wait for their slot's previous user)
     const bool forked = parts > 1u && !chains.detached;
-    if (forked) (void)hipEventRecord(chains.fork, stream);
+    if (forked) (void)chains.fork->record(stream);
     uint32_t blocksBefore = 0;
     for (uint32_t i = 0; i < parts; ++i)
     {
@@ -915,8 +915,8 @@ void launch_render_wavefront(
         part.groupBase = i * per;
         part.groupCount = (part.groupBase + per <= groups) ? per : groups - part.groupBase;
         hipStream_t cs = ownStreams ? chains.streams[i] : stream;
-        LaunchTimer *ct = ownStreams ? chains.timers[i] : timer;
-        if (forked) (void)hipStreamWaitEvent(cs, chains.fork, 0);
+        LaunchTimeline *ct = ownStreams ? chains.timers[i] : timer;
+        if (forked) (void)chains.fork->wait(cs);
         if (chains.detached && chains.after) (void)hipStreamWaitEvent(cs, chains.after, 0);
         if (ownStreams && chains.scene) (void)hipStreamWaitEvent(cs, chains.scene, 0);
         if (ownStreams && chains.lights) (void)hipStreamWaitEvent(cs, chains.lights, 0);
@@ -932,8 +932,8 @@ void launch_render_wavefront(
         if (ownStreams)
         {
             if (ct) ct->close(cs);
-            (void)hipEventRecord(chains.join[i], cs);
-            (void)hipStreamWaitEvent(stream, chains.join[i], 0);
+            (void)chains.join[i]->record(cs);
+            (void)chains.join[i]->wait(stream);
         }
     }
     if (timer) timer->mark(kStageAccumulate, stream);

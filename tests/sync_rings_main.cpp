@@ -1,11 +1,14 @@
-// sync_rings_main.cpp — the fence, version ring and staging ring of prosper_amd/csrc/pt_sync.hpp on a CPU, against fakes
-// of the HIP entry points the header calls: every fake appends to a call log and can be told to fail once.  Built and
+// sync_rings_main.cpp — the fence, stream, version ring, staging ring and launch timeline of prosper_amd/csrc/pt_sync.hpp
+// on a CPU, against fakes of the HIP entry points the header calls: every fake appends to a call log and can be told to
+// fail once.  Built and
 // run by tests/test_sync_rings.py (host compiler, no HIP runtime linked, AddressSanitizer + UBSan).  Exit status 0: every
 // check held.
 #include "pt_sync.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <set>
 #include <string>
 #include <vector>
@@ -22,8 +25,11 @@ struct Call
 };
 std::vector<Call> g_log;
 std::string g_failOnce; // the next call of this entry point fails (once)
-std::set<void *> g_liveEvents, g_livePinned;
+uint32_t g_failAt = 0;  // ... or the g_failAt-th hipEventCreate from now on does (once)
+std::set<void *> g_liveEvents, g_livePinned, g_liveStreams;
+std::map<const void *, float> g_msFrom; // what hipEventElapsedTime reports for an interval that starts at this event
 int g_eventsCreated = 0, g_eventsDestroyed = 0, g_pinnedAllocated = 0, g_pinnedFreed = 0;
+int g_streamsCreated = 0, g_streamsDestroyed = 0;
 std::string g_lastError;
 int g_failures = 0;
 
@@ -80,6 +86,42 @@ hipError_t hipEventCreateWithFlags(hipEvent_t *event, unsigned flags)
     g_log.back().event = *event;
     ++g_eventsCreated;
     return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *event)
+{
+    if (g_failAt && --g_failAt == 0) g_failOnce = "create_timed";
+    const hipError_t e = enter("create_timed");
+    if (e != hipSuccess) return e;
+    *event = static_cast<hipEvent_t>(std::malloc(1));
+    g_liveEvents.insert(*event);
+    g_log.back().event = *event;
+    ++g_eventsCreated;
+    return hipSuccess;
+}
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t start, hipEvent_t stop)
+{
+    if (!g_liveEvents.count(start) || !g_liveEvents.count(stop)) return hipErrorInvalidHandle;
+    const hipError_t e = enter("elapsed", start, stop); // (the log's `stream` holds the closing event)
+    if (e == hipSuccess) *ms = g_msFrom.count(start) ? g_msFrom[start] : 0.0f;
+    return e;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
+{
+    if (flags != hipStreamNonBlocking) return hipErrorInvalidValue;
+    const hipError_t e = enter("stream_create");
+    if (e != hipSuccess) return e;
+    *s = static_cast<hipStream_t>(std::malloc(1));
+    g_liveStreams.insert(*s);
+    g_log.back().stream = *s;
+    ++g_streamsCreated;
+    return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s)
+{
+    if (!g_liveStreams.erase(s)) return hipErrorInvalidHandle;
+    ++g_streamsDestroyed;
+    std::free(s);
+    return enter("stream_destroy", nullptr, s);
 }
 hipError_t hipEventDestroy(hipEvent_t event)
 {
@@ -304,19 +346,133 @@ void test_commit_after_success()
     CHECK(g_liveEvents.empty() && g_livePinned.empty());
 }
 
+void test_stream()
+{
+    {
+        Stream s;
+        CHECK(s.get() == nullptr && g_log.empty());
+        CHECK(s.create() == PROSPER_PT_OK && s.get() != nullptr && count("stream_create") == 1);
+        const hipStream_t made = s.get();
+        CHECK(s.create() == PROSPER_PT_OK && s.get() == made && count("stream_create") == 1); // the one stream again
+    }
+    CHECK(count("stream_destroy") == 1 && g_log.back().stream != nullptr && g_liveStreams.empty());
+    size_t at = 0;
+    {
+        Stream s;
+        g_failOnce = "stream_create";
+        CHECK(s.create() == PROSPER_PT_ERR_HIP && s.get() == nullptr && !g_lastError.empty());
+        at = g_log.size();
+    }
+    CHECK(g_log.size() == at); // nothing was made: the destructor asked nothing of the runtime
+}
+
+void test_launch_timeline()
+{
+    const hipStream_t a = stream(1), b = stream(2);
+    constexpr uint32_t kEvents = kMaxTimedLaunches + 1u;
+    static_assert(kMaxTimedLaunches == 96, "the capacity the render's launchers were sized for");
+    {
+        LaunchTimeline t;
+        CHECK(t.create() == PROSPER_PT_OK && count("create_timed") == kEvents && g_log.size() == kEvents);
+        std::vector<const void *> events;
+        for (const Call &c : g_log) events.push_back(c.event);
+        CHECK(t.create() == PROSPER_PT_OK && g_log.size() == kEvents); // a second create makes none
+        // mark: event i on the stream of the launch; close: the event behind the last interval
+        const uint32_t stages[6] = {0, 1, 2, 1, 2, 3};
+        t.begin();
+        for (uint32_t i = 0; i < 6; ++i)
+        {
+            t.mark(stages[i], i == 5 ? b : a);
+            CHECK(g_log.back().op == "record" && g_log.back().event == events[i] && g_log.back().stream == (i == 5 ? b : a));
+            g_msFrom[events[i]] = 0.25f * (float)(1u << i); // 0.25, 0.5, 1, 2, 4, 8: sums are exact
+        }
+        t.close(b);
+        CHECK(g_log.back().op == "record" && g_log.back().event == events[6] && g_log.back().stream == b);
+        CHECK(t.intervals() == 6 && count("record") == 7);
+        CHECK(t.wait() == PROSPER_PT_OK && g_log.back().op == "host_wait" && g_log.back().event == events[6]);
+        float ms[PROSPER_PT_MAX_KERNELS] = {}, total = 0.0f;
+        uint32_t launches[PROSPER_PT_MAX_KERNELS] = {};
+        size_t at = g_log.size();
+        CHECK(t.add_to(ms, launches, &total) == PROSPER_PT_OK && count("elapsed", at) == 6 && g_log.size() == at + 6);
+        for (uint32_t i = 0; i < 6; ++i) CHECK(g_log[at + i].event == events[i] && g_log[at + i].stream == events[i + 1]);
+        CHECK(ms[0] == 0.25f && ms[1] == 2.5f && ms[2] == 5.0f && ms[3] == 8.0f && total == 15.75f);
+        CHECK(launches[0] == 1 && launches[1] == 2 && launches[2] == 2 && launches[3] == 1);
+        for (uint32_t st = 4; st < PROSPER_PT_MAX_KERNELS; ++st) CHECK(ms[st] == 0.0f && launches[st] == 0); // never marked
+        // ... INTO the caller's sums: a second timeline (a launch chain's) adds to what is there
+        CHECK(t.add_to(ms, launches, &total) == PROSPER_PT_OK && ms[1] == 5.0f && launches[1] == 4 && total == 31.5f);
+        g_failOnce = "elapsed";
+        CHECK(t.add_to(ms, launches, &total) == PROSPER_PT_ERR_HIP);
+        // begin: the next render's intervals start at the first event again
+        t.begin();
+        CHECK(t.intervals() == 0);
+        t.mark(2, a);
+        CHECK(g_log.back().event == events[0] && t.intervals() == 1);
+        // launches beyond the capacity go untimed, and close still records on the last event
+        t.begin();
+        at = g_log.size();
+        for (uint32_t i = 0; i < kMaxTimedLaunches; ++i) t.mark(1, a);
+        CHECK(count("record", at) == kMaxTimedLaunches && g_log.back().event == events[kMaxTimedLaunches - 1u]);
+        at = g_log.size();
+        t.mark(1, a); // the 97th
+        CHECK(g_log.size() == at && t.intervals() == kMaxTimedLaunches);
+        t.close(a);
+        CHECK(g_log.size() == at + 1 && g_log.back().op == "record" && g_log.back().event == events[kMaxTimedLaunches]);
+        CHECK(t.wait() == PROSPER_PT_OK && g_log.back().event == events[kMaxTimedLaunches]);
+        std::fill(ms, ms + PROSPER_PT_MAX_KERNELS, 0.0f);
+        std::fill(launches, launches + PROSPER_PT_MAX_KERNELS, 0u);
+        CHECK(t.add_to(ms, launches, &total) == PROSPER_PT_OK && launches[1] == kMaxTimedLaunches && launches[0] == 0);
+    }
+    CHECK(count("destroy") == kEvents && g_liveEvents.empty());
+    g_msFrom.clear();
+    for (const uint32_t k : {1u, 40u, kEvents})
+    {
+        // a create that fails at the k-th event: the destructor gives back the k - 1 that were made
+        g_log.clear();
+        {
+            LaunchTimeline t;
+            g_failAt = k;
+            CHECK(t.create() == PROSPER_PT_ERR_HIP && !g_lastError.empty());
+            CHECK(g_failAt == 0 && count("create_timed") == k - 1u && count("create_timed!") == 1);
+        }
+        CHECK(count("destroy") == k - 1u && g_liveEvents.empty());
+    }
+    {
+        // ... and a create after the failure makes only what is missing
+        g_log.clear();
+        LaunchTimeline t;
+        g_failAt = 40;
+        CHECK(t.create() == PROSPER_PT_ERR_HIP && t.create() == PROSPER_PT_OK && count("create_timed") == kEvents);
+    }
+    CHECK(g_liveEvents.empty());
+    {
+        // the passes' timed events share the creation: N + 1 events, one interval per stage
+        g_log.clear();
+        StageEvents<2> e;
+        CHECK(!e.created() && e.create() == PROSPER_PT_OK && e.created() && count("create_timed") == 3);
+        g_msFrom[e.events[0]] = 1.5f;
+        g_msFrom[e.events[1]] = 0.5f;
+        float ms[2] = {};
+        CHECK(e.elapsed(ms) == PROSPER_PT_OK && ms[0] == 1.5f && ms[1] == 0.5f && count("host_wait", 0, e.events[2]) == 1);
+    }
+    g_msFrom.clear();
+    CHECK(g_liveEvents.empty());
+}
+
 } // namespace
 
 int main()
 {
-    void (*const tests[])() = {test_fence, test_version_ring, test_staging_ring, test_commit_after_success};
+    void (*const tests[])() = {test_fence, test_version_ring, test_staging_ring, test_commit_after_success, test_stream,
+                               test_launch_timeline};
     for (auto test : tests)
     {
         g_log.clear();
         g_pinnedAllocated = g_pinnedFreed = 0;
         test();
     }
-    // every owner is gone: each event and each pinned buffer was given back exactly once (a second time fails in the fake)
+    // every owner is gone: each event, pinned buffer and stream was given back exactly once (a second time fails in the fake)
     CHECK(g_eventsCreated > 0 && g_eventsCreated == g_eventsDestroyed && g_liveEvents.empty() && g_livePinned.empty());
+    CHECK(g_streamsCreated > 0 && g_streamsCreated == g_streamsDestroyed && g_liveStreams.empty());
     if (g_failures) std::fprintf(stderr, "%d check(s) failed\n", g_failures);
     else std::printf("sync rings ok: %d events\n", g_eventsCreated);
     return g_failures ? 1 : 0;

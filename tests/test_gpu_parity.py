@@ -800,6 +800,43 @@ def test_all_pipelines_produce_identical_pixels(gpu_ctx, oracle, cornell_world):
     assert (z[..., :3] == 0).all() and (z[..., 3] == 1).all()
 
 
+@pytest.mark.parametrize("mode,create_flags,render_flags,want", [
+    ("in_order", 0, 0, (1, 3, 3, 1)),
+    ("single_chain", S.CREATE_SINGLE_CHAIN, 0, (1, 3, 3, 1)),
+    ("pipelined", 0, S.RENDER_PIPELINED, (1, 3, 3, 1)),
+    ("megakernel", S.CREATE_MEGAKERNEL, 0, (1, 0, 0, 0)),
+])
+def test_timing_readout_counts_the_launches_of_every_pipeline(oracle, cornell_world, mode, create_flags, render_flags, want):
+    """prosper_pt_get_last_render_timing on a 64 x 64 Cornell render of 3 bounces (too small to split into chains): one
+    generate, three shades, three traces and one accumulate launch in every wavefront mode, the one kernel of the
+    megakernel pipeline; finite times >= 0 and a total > 0; the same numbers when read again, and still after timing was
+    switched off and an untimed render ran.  A context without a timed render refuses the readout."""
+    w = h = 64
+    cam, fl = _camera(oracle, cornell_world, w, h)
+    pc = default_pc(S, fl, max_bounces=3)
+    names = ("wf_generate_extend", "wf_shade", "wf_trace", "wf_accumulate")
+    ctx = capi.Context(device=0, flags=create_flags)
+    try:
+        ctx.upload_scene(cornell_world)
+        ctx.render(pc, cam, w, h, flags=render_flags)
+        with pytest.raises(capi.ProsperPtError) as refused:
+            ctx.last_render_timing()
+        assert refused.value.code == -1  # PROSPER_PT_ERR_INVALID_ARGUMENT
+        ctx.set_kernel_timing(True)
+        ctx.render(pc, cam, w, h, flags=render_flags)
+        total, per = ctx.last_render_timing()
+        print(mode, total, per)
+        assert tuple(per[n][1] for n in names) == want
+        assert np.isfinite(total) and total > 0
+        assert all(np.isfinite(per[n][0]) and per[n][0] >= 0 for n in names)
+        assert ctx.last_render_timing() == (total, per)
+        ctx.set_kernel_timing(False)
+        ctx.render(pc, cam, w, h, flags=render_flags)
+        assert ctx.last_render_timing() == (total, per)
+    finally:
+        ctx.close()
+
+
 def test_reserved_debug_options_are_refused():
     """The debug options of the removed experiments are reserved: each one, set alone on a fresh context before any
     upload or render, fails with PROSPER_PT_ERR_UNSUPPORTED and leaves the context's options as they were."""

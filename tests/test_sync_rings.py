@@ -1,7 +1,9 @@
 """The fence, the version ring and the pinned staging ring behind the scene updates of the frame loop
 (prosper_amd/csrc/pt_sync.hpp) on a CPU: tests/sync_rings_main.cpp drives them against fakes of the HIP entry points the
 header calls - which versions a ring visits, which waits are enqueued and which are not, when the host waits for a staging
-buffer, what a failure between next() and commit() leaves behind, that every event and pinned buffer is given back once.
+buffer, what a failure between next() and commit() leaves behind; the stream owner and the launch timeline of a timed
+render (which events it records, what it drops beyond its capacity, how its intervals add up per stage, what a creation
+that failed half way gives back); that every event, pinned buffer and stream is given back once.
 A stand-alone program built with the host compiler, without the HIP runtime, under AddressSanitizer + UBSan."""
 import os
 import shutil
