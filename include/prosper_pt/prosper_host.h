@@ -41,6 +41,9 @@ void prosper_host_camera_update_resolution(prosper_host_camera *camera, uint32_t
 void prosper_host_camera_update_buffer(prosper_host_camera *camera, prosper_CameraUniforms *out, float *focalLength);
 int prosper_host_camera_changed_this_frame(const prosper_host_camera *camera);
 void prosper_host_camera_end_frame(prosper_host_camera *camera);
+/* Camera::setJitter: from the next update_buffer on the projection carries the TAA jitter of the 8-sample Halton(2, 3)
+ * cycle (prosper_pt_taa_jitter of the camera's jitter index, which end_frame advances).  Off by default. */
+void prosper_host_camera_set_jitter(prosper_host_camera *camera, int applyJitter);
 
 int prosper_host_rt_reference_create(int32_t deviceOrdinal, uint32_t createFlags, prosper_host_rt_reference **out);
 void prosper_host_rt_reference_destroy(prosper_host_rt_reference *pass);
@@ -112,6 +115,14 @@ void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *pass);
 int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
     uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer);
+/* GBufferTracer::recordVelocity = Camera::updateBuffer + prosper_pt_trace_gbuffer_velocity: the G-buffer through the
+ * pixel centres of the camera's (jittered) projection and the velocity image (*outVelocity, device, float2).
+ * `transforms` (may be NULL; `transformCount` = the scene's model instances): this frame's instance transforms, kept
+ * and handed to the next call as the previous frame's; the first call sees unmoved instances. */
+int prosper_host_gbuffer_tracer_record_velocity(
+    prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
+    uint32_t frameIndex, const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream,
+    prosper_pt_restir_inputs *outGBuffer, void **outVelocity);
 
 /* render::LightClustering (host/light_clustering.hpp; reference src/render/LightClustering.hpp:22-64) on a context the
  * scene was uploaded to (borrowed): record = Camera::updateBuffer + prosper_pt_cluster_lights into the context-owned
@@ -177,6 +188,20 @@ void prosper_host_bloom_draw_ui(
 int prosper_host_bloom_record(
     prosper_host_bloom *pass, uint32_t width, uint32_t height, const void *illumination, uint32_t onDevice, void *stream,
     prosper_pt_bloom_pc *outPushConstants);
+
+/* render::TemporalAntiAliasing (host/temporal_anti_aliasing.hpp; reference src/render/TemporalAntiAliasing.hpp) on a
+ * context (borrowed), with prosper's defaults: Catmull-Rom, Variance clipping, Closest velocity, luminance weighting.
+ * draw_ui sets what prosper's drawUi edits; record = prosper_pt_taa_resolve with those settings over `inputs` and
+ * returns the push constants it used; release_preserved = TemporalAntiAliasing::releasePreserved. */
+typedef struct prosper_host_taa prosper_host_taa;
+int prosper_host_taa_create(prosper_pt_ctx *ctx, prosper_host_taa **out);
+void prosper_host_taa_destroy(prosper_host_taa *pass);
+void prosper_host_taa_draw_ui(
+    prosper_host_taa *pass, uint32_t catmullRom, uint32_t colorClipping, uint32_t velocitySampling, uint32_t luminanceWeighting);
+int prosper_host_taa_record(
+    prosper_host_taa *pass, uint32_t width, uint32_t height, const prosper_pt_taa_inputs *inputs, void *stream,
+    prosper_pt_taa_pc *outPushConstants);
+void prosper_host_taa_release_preserved(prosper_host_taa *pass);
 
 #ifdef __cplusplus
 }

@@ -570,7 +570,8 @@ int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, s
  * and zeros where the ray misses (the targets' clear values).  With PROSPER_PT_GBUFFER_JITTER the ray goes through
  * the pixel's jittered sample (px, py) + rnd2d01() of the path tracer's rng (px, py, frameIndex): each texel is then
  * that frame's primary hit.  Without, through the pixel centre (px + 0.5, py + 0.5), as a rasteriser samples.
- * Unlike the raster G-buffer: no velocity target, no TAA jitter (currentJitter), no meshlet IDs, float storage, BLEND
+ * Unlike the raster G-buffer: no velocity target and no TAA jitter (currentJitter) in this entry -
+ * prosper_pt_trace_gbuffer_velocity has both -, no meshlet IDs, float storage, BLEND
  * surfaces follow the path tracer's stochastic transparency, and PrimitiveID is the geometry's triangle index.
  * `targets`: three caller-owned device buffers (16-byte aligned), or NULL for context-owned ones (grown as needed,
  * separate from the ReSTIR scratch).  Pending transform, light and material updates take effect first. */
@@ -587,6 +588,40 @@ typedef struct prosper_pt_gbuffer_targets
 int prosper_pt_trace_gbuffer(
     prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
     uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream);
+/* The traced G-buffer as prosper's rasteriser samples it under TAA, with a fourth target, the velocity (gbuffer.frag:74-84,
+ * forward.mesh:81-88, skybox.vert / skybox.frag).  The primary ray goes through the point whose projection
+ * by camera->cameraToClip * worldToCamera is the pixel centre: uv = (px + 0.5, py + 0.5) / extent - currentJitter * 0.5
+ * (the jittered projection moves NDC by + currentJitter on both axes).  The rng draw and the any-hit seed are
+ * prosper_pt_trace_gbuffer's; with currentJitter = (0, 0) the three targets are byte-identical to that entry's without
+ * PROSPER_PT_GBUFFER_JITTER.  `flags` must be 0.
+ *   velocity  float2: (posNDC - currentJitter) - (prevPosNDC - previousJitter), y negated, each component clamped as
+ *             fminf(fmaxf(v, -1), 1).  posNDC = xy / w of cameraToClip * worldToCamera * (positionWS, 1), prevPosNDC the
+ *             same through previousCameraToClip * previousWorldToCamera of prevPositionWS: the interpolated model-space
+ *             vertex through previousTransforms[modelInstanceIndex].modelToWorld, or positionWS itself without
+ *             previousTransforms (previousTransformValid = 0).  Where the ray misses: the same of the ray's direction d
+ *             with worldToCamera and previousWorldToCamera as mat4(mat3(.)).  Both projections go through the same code
+ *             (fma chains, the camera row first), w comes from the matrices: an unchanged camera, unchanged instances
+ *             and equal jitters give exactly (0, 0).
+ * Unlike prosper: float2 storage instead of R16G16_SNORM, and the sky's velocity is clamped too (the SNORM target clamps
+ * it on store).  The previous transforms are copied on `stream` into a grow-only device buffer of the context.  Refused:
+ * non-zero flags, a partly given target set, misaligned targets, previousTransformCount that differs from the scene's
+ * modelInstanceCount (or is given without previousTransforms). */
+typedef struct prosper_pt_velocity_gbuffer_desc
+{
+    prosper_pt_gbuffer_targets targets; /* all three given, or all three NULL for context-owned ones */
+    void *velocity;                     /* width*height float2 on the device (8-byte aligned); NULL: context-owned */
+    const prosper_ModelInstanceTransforms *previousTransforms; /* host, the scene's modelInstanceCount entries; NULL: the
+                                                                * instances did not move */
+    uint32_t previousTransformCount;
+} prosper_pt_velocity_gbuffer_desc;
+int prosper_pt_trace_gbuffer_velocity(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_velocity_gbuffer_desc *desc, void *stream);
+/* The velocity target the last prosper_pt_trace_gbuffer_velocity wrote and its extent; NO_SCENE before the first.
+ * width / height may be NULL. */
+int prosper_pt_get_velocity_device_ptr(prosper_pt_ctx *ctx, void **out, uint32_t *width, uint32_t *height);
+/* Synchronises `stream` and copies that velocity target to host memory: `pixels` = width*height of that trace. */
+int prosper_pt_read_velocity(prosper_pt_ctx *ctx, float *host_float2, size_t pixels, void *stream);
 /* The last traced G-buffer (either kind of target) as inputs of the ReSTIR-DI entries (onDevice = 1, reservoirs =
  * NULL) and its extent; NO_SCENE before the first trace.  width / height may be NULL. */
 int prosper_pt_get_gbuffer_device_ptrs(
@@ -688,7 +723,7 @@ int prosper_pt_read_ibl(
  * is the path tracer's seamless bilinear lookup of mip 0 of the scene's sky, unclamped, in the direction of the
  * G-buffer tracer's primary ray through the pixel centre (px + 0.5, py + 0.5); a cube lookup does not depend on the
  * direction's length, so this is the interpolated cube position of skybox.vert.  A scene without a sky fills
- * (0, 0, 0, 1).  No velocity output.  `nonLinearDepth`: width*height floats, on the device when `onDevice` is not 0;
+ * (0, 0, 0, 1).  No velocity output (prosper_pt_trace_gbuffer_velocity writes the sky's).  `nonLinearDepth`: width*height floats, on the device when `onDevice` is not 0;
  * NULL means the last traced G-buffer's depth (refused when its extent differs).  The HDR image must be what a render,
  * a ReSTIR trace or deferred shading produced at this extent.  Pending scene updates take effect first. */
 int prosper_pt_skybox_fill(
@@ -855,6 +890,94 @@ typedef struct prosper_pt_bloom_info
     float separateMs, reduceMs, blurHorizontalMs[3], blurVerticalMs[3], composeMs;
 } prosper_pt_bloom_info;
 int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out);
+
+/* ---- temporal anti-aliasing: the resolve (src/render/TemporalAntiAliasing.cpp, res/shader/taa_resolve.comp) ----
+ * What prosper runs between bloom and depth of field (Renderer.cpp:516-573), on by default there
+ * (m_applyTaa).  Additive: the ABI version stays 4. */
+typedef struct prosper_pt_taa_pc
+{
+    uint32_t catmullRom;         /* 0 / 1; TemporalAntiAliasing.hpp: 1 */
+    uint32_t colorClipping;      /* 0 None, 1 MinMax, 2 Variance (the default) */
+    uint32_t velocitySampling;   /* 0 Center, 1 Largest, 2 Closest (the default) */
+    uint32_t luminanceWeighting; /* 0 / 1; the default is 1 */
+    uint32_t resetHistory;       /* 1: IGNORE_HISTORY for this call */
+} prosper_pt_taa_pc;
+enum
+{
+    PROSPER_PT_TAA_CLIPPING_NONE = 0,
+    PROSPER_PT_TAA_CLIPPING_MIN_MAX = 1,
+    PROSPER_PT_TAA_CLIPPING_VARIANCE = 2,
+    PROSPER_PT_TAA_VELOCITY_CENTER = 0,
+    PROSPER_PT_TAA_VELOCITY_LARGEST = 1,
+    PROSPER_PT_TAA_VELOCITY_CLOSEST = 2,
+};
+typedef struct prosper_pt_taa_inputs
+{
+    const void *illumination;    /* width*height RGBA32F; NULL: the context's HDR image, in place */
+    const void *velocity;        /* width*height float2 (x, y), prosper's velocity target: (posNDC - currentJitter) -
+                                  * (prevPosNDC - previousJitter) with y negated; NULL: the last traced velocity target
+                                  * (prosper_pt_trace_gbuffer_velocity) */
+    const float *nonLinearDepth; /* width*height reverse-Z depth, read by Closest alone; NULL: the last traced G-buffer's */
+    uint32_t onDevice;           /* not 0: the given pointers are device pointers */
+} prosper_pt_taa_inputs;
+/* TemporalAntiAliasing::record: taa_resolve.comp over `width` x `height`, one of its 36 specialisations (catmullRom x
+ * colorClipping x velocitySampling x luminanceWeighting) or IGNORE_HISTORY, each a kernel of its own picked by
+ * prosper's specializationIndex.  The context owns two grow-only RGBA16F history images (prosper's resolved image is
+ * RGBA16F): a call reads one and writes the other, stores round to nearest even with alpha 1, and the result in the
+ * context's HDR image is the float32 expansion of the stored texel, so the HDR image and the history hold the same
+ * values as prosper's one image does.  In place (illumination NULL or the HDR image itself) the pass is two kernels,
+ * `resolve` into the new history and `expand` from it into the HDR image, because the 3 x 3 neighbourhood reaches
+ * texels other blocks write; with another input image `resolve` writes both.  Both ways give the same bytes.
+ * History is ignored (the output is the input's rgb) on the first call, when the extent differs from the last call's
+ * (TemporalAntiAliasing.cpp:199-220), with resetHistory, after prosper_pt_taa_release_history and after
+ * prosper_pt_upload_scene.
+ * The arithmetic is float32 without contraction in the GLSL's order, with px the texel and res = (width, height):
+ *   nearest lookups  at (px + offset + .5) / res: the texel px + offset clamped to the edge, formed from the integers;
+ *                    every 3 x 3 loop runs x outer, y inner
+ *   velocity         Center: the texel's; Largest: lenSqr = x x + y y, `retLenSqr < lenSqr` is strict (the first of equal
+ *                    lengths wins, all zero gives (0, 0)); Closest: `depth > closestDepth` from 0 is strict (the first of
+ *                    equal depths wins, all zero gives offset (0, 0)), then the velocity at that offset
+ *   uv               ((px + .5) / res); reprojectedUv = uv - velocity * (.5, -.5); unless every component equals its
+ *                    saturate (0 and 1 are inside, a NaN is not) the output is the illumination
+ *   history lookup   c = reprojectedUv * res - 0.5, i = floor(c), f = c - i, texels clamped to the edge.  Bilinear: the
+ *                    texels i, i + 1 of both axes with the weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy
+ *                    summed in that order.  Catmull-Rom (optimizedCatmullRom, sharpness 70): w0 .. w3 from f per axis
+ *                    as written, w12 = w1 + w2, t = w2 / w12; the five taps in texel space, without the round trip
+ *                    through tc * res: (tc12.x, tc0.y) blends the texels ix, ix + 1 of row iy - 1 with (1 - tx, tx),
+ *                    (tc0.x, tc12.y) the texels iy, iy + 1 of column ix - 1 with ty, the centre the four texels with
+ *                    (tx, ty), (tc3.x, tc12.y) column ix + 2, (tc12.x, tc3.y) row iy + 2; weighted by w12.x w0.y,
+ *                    w0.x w12.y, w12.x w12.y, w3.x w12.y, w12.x w3.y, summed in that order and divided by the weights' sum
+ *   clipping         MinMax: clamp to the neighbourhood's min and max (from 9999 and -9999); Variance: mu = m1 / 9,
+ *                    sigma = sqrt(max(m2 / 9 - mu mu, 0)) - the max is a deviation: the GLSL's argument can go negative
+ *                    on a flat neighbourhood and give NaN - clamp to mu -/+ sigma.  clamp(x, lo, hi) = min(max(x, lo), hi)
+ *   blend            currentWeight .1, historyWeight 1 - .1, each times 1 / (1 + luminance) with luminance weighting
+ *                    (luminance = (.299 r + .587 g) + .114 b); (illumination cw + previous hw) / max(cw + hw, .00001)
+ * Host inputs go through a grow-only staging buffer.  It needs no scene.  Refused, changing nothing: a NULL pc or
+ * inputs, a flag above 1 or an unknown clipping or sampling type, an empty extent or one above 32768, illumination =
+ * NULL when the HDR image has another extent, a NULL velocity when no velocity target of this extent has been traced,
+ * and with Closest a NULL depth when no G-buffer of this extent has been traced. */
+int prosper_pt_taa_resolve(
+    prosper_pt_ctx *ctx, const prosper_pt_taa_pc *pc, uint32_t width, uint32_t height, const prosper_pt_taa_inputs *inputs,
+    void *stream);
+/* TemporalAntiAliasing::releasePreserved: the next call ignores the history.  (The images stay allocated.) */
+void prosper_pt_taa_release_history(prosper_pt_ctx *ctx);
+/* Synchronises `stream` and copies the history the NEXT call will read to host memory as raw RGBA16F, row-major;
+ * `bytes` must be exactly width*height*8 of the last call.  NO_SCENE when there is no history. */
+int prosper_pt_read_taa_history(prosper_pt_ctx *ctx, uint16_t *rgba16f, size_t bytes, void *stream);
+typedef struct prosper_pt_taa_info
+{
+    uint32_t valid;          /* 1 once prosper_pt_taa_resolve ran */
+    uint32_t width, height;  /* of the last call */
+    uint32_t historyValid;   /* 1: the next call of this extent reads a history */
+    uint32_t ignoredHistory; /* 1: the last call ran IGNORE_HISTORY */
+    /* device time of the two kernels of the last call (reading them waits for it); expandMs covers nothing when
+     * `resolve` wrote the HDR image itself */
+    float resolveMs, expandMs;
+} prosper_pt_taa_info;
+int prosper_pt_get_taa_info(prosper_pt_ctx *ctx, prosper_pt_taa_info *out);
+/* Camera::perspective's jitter (Camera.cpp:119-128): (halton23[jitterIndex % 8] * 2 - 1) / (width, height) in float32,
+ * in that order of operations, for callers that build their own prosper_CameraUniforms.  Host only. */
+void prosper_pt_taa_jitter(uint32_t jitterIndex, uint32_t width, uint32_t height, float out[2]);
 
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of

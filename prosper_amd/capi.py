@@ -87,6 +87,10 @@ def lib():
     L.prosper_pt_trace_gbuffer.argtypes = [
         vp, u32, u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.GBufferTargets), vp]
     L.prosper_pt_get_gbuffer_device_ptrs.argtypes = [vp, C.POINTER(S.RestirInputs), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_trace_gbuffer_velocity.argtypes = [
+        vp, u32, u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.VelocityGBufferDesc), vp]
+    L.prosper_pt_get_velocity_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_read_velocity.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_read_gbuffer.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.prosper_pt_cluster_lights.argtypes = [vp, C.POINTER(S.CameraUniforms), u32, u32, vp]
     L.prosper_pt_get_light_cluster_dims.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
@@ -108,6 +112,13 @@ def lib():
     L.prosper_pt_bloom_streak_weights.restype = None
     L.prosper_pt_read_bloom_stage.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
     L.prosper_pt_get_bloom_info.argtypes = [vp, C.POINTER(S.BloomInfo)]
+    L.prosper_pt_taa_resolve.argtypes = [vp, C.POINTER(S.TaaPC), u32, u32, C.POINTER(S.TaaInputs), vp]
+    L.prosper_pt_taa_release_history.argtypes = [vp]
+    L.prosper_pt_taa_release_history.restype = None
+    L.prosper_pt_read_taa_history.argtypes = [vp, vp, C.c_size_t, vp]
+    L.prosper_pt_get_taa_info.argtypes = [vp, C.POINTER(S.TaaInfo)]
+    L.prosper_pt_taa_jitter.argtypes = [u32, u32, u32, C.POINTER(C.c_float * 2)]
+    L.prosper_pt_taa_jitter.restype = None
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -148,6 +159,8 @@ def lib():
     L.prosper_host_camera_changed_this_frame.argtypes = [vp]
     L.prosper_host_camera_end_frame.argtypes = [vp]
     L.prosper_host_camera_end_frame.restype = None
+    L.prosper_host_camera_set_jitter.argtypes = [vp, C.c_int]
+    L.prosper_host_camera_set_jitter.restype = None
     L.prosper_host_rt_reference_create.argtypes = [i32, u32, C.POINTER(vp)]
     L.prosper_host_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_rt_reference_destroy.restype = None
@@ -177,6 +190,8 @@ def lib():
     L.prosper_host_gbuffer_tracer_destroy.argtypes = [vp]
     L.prosper_host_gbuffer_tracer_destroy.restype = None
     L.prosper_host_gbuffer_tracer_record.argtypes = [vp, vp, u32, u32, u32, u32, C.c_int, vp, C.POINTER(S.RestirInputs)]
+    L.prosper_host_gbuffer_tracer_record_velocity.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, C.POINTER(S.RestirInputs),
+                                                              C.POINTER(vp)]
     L.prosper_host_light_clustering_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_light_clustering_destroy.argtypes = [vp]
     L.prosper_host_light_clustering_destroy.restype = None
@@ -205,6 +220,14 @@ def lib():
     L.prosper_host_bloom_draw_ui.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, u32, u32]
     L.prosper_host_bloom_draw_ui.restype = None
     L.prosper_host_bloom_record.argtypes = [vp, u32, u32, vp, u32, vp, C.POINTER(S.BloomPC)]
+    L.prosper_host_taa_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_taa_destroy.argtypes = [vp]
+    L.prosper_host_taa_destroy.restype = None
+    L.prosper_host_taa_draw_ui.argtypes = [vp, u32, u32, u32, u32]
+    L.prosper_host_taa_draw_ui.restype = None
+    L.prosper_host_taa_record.argtypes = [vp, u32, u32, C.POINTER(S.TaaInputs), vp, C.POINTER(S.TaaPC)]
+    L.prosper_host_taa_release_preserved.argtypes = [vp]
+    L.prosper_host_taa_release_preserved.restype = None
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -246,6 +269,13 @@ def dof_sample_offsets():
     out = np.empty((S.DOF_TAPS, 2), np.float32)
     lib().prosper_pt_dof_sample_offsets(out.ctypes.data)
     return out
+
+
+def taa_jitter(jitter_index, width, height):
+    """prosper_pt_taa_jitter: Camera::perspective's jitter of sample `jitter_index` of the Halton(2, 3) cycle, float32 [2]"""
+    out = (C.c_float * 2)()
+    lib().prosper_pt_taa_jitter(jitter_index, width, height, C.byref(out))
+    return np.array(out[:], np.float32)
 
 
 def bloom_streak_weights(half_width):
@@ -562,6 +592,39 @@ class Context:
             return None
         return self.read_gbuffer(stream)
 
+    def trace_gbuffer_velocity(self, camera, width, height, draw_type=0, frame_index=0, previous_transforms=None, targets=None,
+                               velocity_ptr=None, stream=None):
+        """prosper_pt_trace_gbuffer_velocity: the traced G-buffer through camera.cameraToClip's (jittered) pixel centres,
+        with the velocity target.  `previous_transforms`: a ctypes array of S.ModelInstanceTransforms, one per model
+        instance (None: the instances did not move).  `targets` (ar, nm, depth) and `velocity_ptr`: device pointers;
+        None: the context's own buffers.  Returns (albedoRoughness, normalMetallic, nonLinearDepth, velocity [h, w, 2])
+        read back, each None where the caller gave the buffer."""
+        self._sync_debug()
+        desc = S.VelocityGBufferDesc()
+        if targets is not None:
+            desc.targets = S.GBufferTargets(*targets)
+        desc.velocity = velocity_ptr
+        if previous_transforms is not None:
+            desc.previousTransforms = C.cast(previous_transforms, C.c_void_p)
+            desc.previousTransformCount = len(previous_transforms)
+        _check(lib().prosper_pt_trace_gbuffer_velocity(self._h, int(draw_type), frame_index, 0, C.byref(camera), width, height,
+                                                       C.byref(desc), C.c_void_p(stream)))
+        gbuffer = (None, None, None) if targets is not None else self.read_gbuffer(stream)
+        return gbuffer + (None if velocity_ptr is not None else self.read_velocity(stream),)
+
+    def velocity_device_ptr(self):
+        """The last traced velocity target: (device pointer, width, height)."""
+        p, w, h = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_get_velocity_device_ptr(self._h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def read_velocity(self, stream=None):
+        """The last traced velocity target as a host array [h, w, 2] float32; synchronises `stream`."""
+        _, w, h = self.velocity_device_ptr()
+        out = np.empty((h, w, 2), np.float32)
+        _check(lib().prosper_pt_read_velocity(self._h, out.ctypes.data, w * h, C.c_void_p(stream)))
+        return out
+
     def gbuffer_device_ptrs(self):
         """The last traced G-buffer: (S.RestirInputs with onDevice = 1, width, height)."""
         inp, w, h = S.RestirInputs(), C.c_uint32(), C.c_uint32()
@@ -739,6 +802,42 @@ class Context:
         i = self.bloom_info()
         out = np.empty((max(i.workingHeight >> level, 1), max(i.workingWidth >> level, 1), 4), np.float16)
         _check(lib().prosper_pt_read_bloom_stage(self._h, stage, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def taa_resolve(self, pc, width, height, velocity=None, depth=None, illumination=None, velocity_ptr=None,
+                    depth_ptr=None, illumination_ptr=None, stream=None):
+        """render::TemporalAntiAliasing::record (prosper_pt_taa_resolve) with `pc` (S.TaaPC) into the HDR image and the
+        history.  `velocity` [h, w, 2], `depth` [h, w], `illumination` [h, w, 4]: host arrays; the `_ptr` ones: device
+        pointers.  No illumination: the HDR image in place; no depth: the last traced G-buffer's (Closest reads it)."""
+        host = velocity is not None or depth is not None or illumination is not None
+        assert not (host and (velocity_ptr or depth_ptr or illumination_ptr)), "host and device inputs cannot be mixed"
+        ve = None if velocity is None else np.ascontiguousarray(velocity, np.float32)
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        assert ve is None or ve.shape == (height, width, 2)
+        assert dp is None or dp.shape == (height, width)
+        assert il is None or il.shape == (height, width, 4)
+        if host:
+            inp = S.TaaInputs(*[None if a is None else a.ctypes.data for a in (il, ve, dp)], 0)
+        else:
+            inp = S.TaaInputs(illumination_ptr, velocity_ptr, depth_ptr, 1)
+        _check(lib().prosper_pt_taa_resolve(self._h, C.byref(pc), width, height, C.byref(inp), C.c_void_p(stream)))
+
+    def taa_release_history(self):
+        """TemporalAntiAliasing::releasePreserved: the next taa_resolve ignores the history."""
+        lib().prosper_pt_taa_release_history(self._h)
+
+    def taa_info(self):
+        """S.TaaInfo: the last resolve's extent, history flags and the device times of its two kernels."""
+        info = S.TaaInfo()
+        _check(lib().prosper_pt_get_taa_info(self._h, C.byref(info)))
+        return info
+
+    def read_taa_history(self, stream=None):
+        """The history the next taa_resolve will read (what the last one wrote) as float16 [h, w, 4]."""
+        i = self.taa_info()
+        out = np.empty((i.height, i.width, 4), np.float16)
+        _check(lib().prosper_pt_read_taa_history(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
 
     def set_tone_map_lut(self, lut_r9g9b9e5):

@@ -2,6 +2,8 @@
 #include "camera.hpp"
 
 #include <cmath>
+
+#include "../../../include/prosper_pt/prosper_pt.h"
 #include <cstring>
 
 namespace scene
@@ -79,6 +81,18 @@ void Camera::lookAt(const CameraTransform &transform)
     updateWorldToCamera();
 }
 
+// src/scene/Camera.cpp:71-80
+void Camera::endFrame()
+{
+    m_changedThisFrame = false;
+    std::memcpy(m_previousCameraToClip, m_cameraToClip, 64);
+    std::memcpy(m_previousWorldToCamera, m_worldToCamera, 64);
+    m_havePrevious = true;
+    m_previousJitter[0] = m_currentJitter[0];
+    m_previousJitter[1] = m_currentJitter[1];
+    m_jitterIndex = (m_jitterIndex + 1u) % 8u;
+}
+
 void Camera::setParameters(const CameraParameters &parameters)
 {
     m_parameters = parameters;
@@ -118,9 +132,13 @@ void Camera::perspective()
     const float zN = m_parameters.zF;
     const float zF = m_parameters.zN;
     const float tf = 1.f / std::tan(m_parameters.fov * 0.5f);
+    m_currentJitter[0] = m_currentJitter[1] = 0.f;
+    if (m_applyJitter) prosper_pt_taa_jitter(m_jitterIndex, m_resolution[0], m_resolution[1], m_currentJitter);
+    // the jitter goes into column 2 ahead of the y-flip, with x negated: a shader unjitters with the value as it is
+    const float jx = m_applyJitter ? -m_currentJitter[0] : 0.f, jy = m_applyJitter ? m_currentJitter[1] : 0.f;
     const float flip[16] = {1.f, 0.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f, 0.f, 0.5f, 0.f, 0.f, 0.f, 0.5f, 1.f};
     const float proj[16] = {tf / ar, 0.f, 0.f, 0.f, 0.f, tf, 0.f, 0.f,
-                            0.f, 0.f, (zF + zN) / (zN - zF), -1.f, 0.f, 0.f, 2 * zF * zN / (zN - zF), 0.f};
+                            jx, jy, (zF + zN) / (zN - zF), -1.f, 0.f, 0.f, 2 * zF * zN / (zN - zF), 0.f};
     mul4(flip, proj, m_cameraToClip);
     float c2cw[16];
     mul4(m_cameraToClip, m_worldToCamera, c2cw);
@@ -138,11 +156,15 @@ const prosper_CameraUniforms &Camera::updateBuffer()
     std::memcpy(&u.cameraToWorld, m_cameraToWorld, 64);
     std::memcpy(&u.cameraToClip, m_cameraToClip, 64);
     std::memcpy(&u.clipToWorld, m_clipToWorld, 64);
-    std::memcpy(&u.previousWorldToCamera, m_worldToCamera, 64);
-    std::memcpy(&u.previousCameraToClip, m_cameraToClip, 64);
+    std::memcpy(&u.previousWorldToCamera, m_havePrevious ? m_previousWorldToCamera : m_worldToCamera, 64);
+    std::memcpy(&u.previousCameraToClip, m_havePrevious ? m_previousCameraToClip : m_cameraToClip, 64);
     u.eye = prosper_vec4{m_transform.eye[0], m_transform.eye[1], m_transform.eye[2], 1.f};
     u.resolution[0] = m_resolution[0];
     u.resolution[1] = m_resolution[1];
+    u.currentJitter[0] = m_currentJitter[0];
+    u.currentJitter[1] = m_currentJitter[1];
+    u.previousJitter[0] = m_previousJitter[0];
+    u.previousJitter[1] = m_previousJitter[1];
     u.near_ = m_parameters.zN;
     u.far_ = m_parameters.zF;
     u.maxViewScale = m_maxViewScale;

@@ -3,8 +3,9 @@
 // Restates the parts of prosper's camera the RT reference pass consumes
 // (reference: src/scene/Camera.hpp:22-48, src/scene/Camera.cpp:105-204,366-395): a right-handed
 // look-at worldToCamera, a reverse-Z, Y-flipped perspective cameraToClip, the CameraUniforms
-// block and CameraParameters::focalLength.  TAA jitter, frustum planes for culling and the
-// gesture offsets of the interactive app are raster/UI features and stay out of scope.
+// block and CameraParameters::focalLength, the TAA jitter (Camera.cpp:71-80,119-144) and the previous
+// frame's matrices and jitter.  Frustum planes for culling and the gesture offsets of the
+// interactive app are raster/UI features and stay out of scope.
 #pragma once
 
 #include <cstdint>
@@ -41,7 +42,10 @@ class Camera
     const prosper_CameraUniforms &updateBuffer();
     // cleared by endFrame(); feeds ReferencePC skipHistory (RtReference.cpp:282-283)
     [[nodiscard]] bool changedThisFrame() const { return m_changedThisFrame; }
-    void endFrame() { m_changedThisFrame = false; }
+    // Camera::endFrame: the current matrices and jitter become the previous ones, the jitter index advances
+    void endFrame();
+    // Camera::setJitter: the 8-sample Halton(2, 3) cycle offsets the projection from the next updateBuffer on
+    void setJitter(bool applyJitter) { m_applyJitter = applyJitter; }
     [[nodiscard]] const CameraParameters &parameters() const { return m_parameters; }
     [[nodiscard]] const prosper_CameraUniforms &uniforms() const { return m_uniforms; }
     [[nodiscard]] static float sensorWidth() { return 0.035f; }
@@ -57,6 +61,14 @@ class Camera
     float m_cameraToWorld[16] = {};
     float m_cameraToClip[16] = {};
     float m_clipToWorld[16] = {};
+    // (until the first endFrame the previous matrices are the current ones)
+    float m_previousWorldToCamera[16] = {};
+    float m_previousCameraToClip[16] = {};
+    bool m_havePrevious = false;
+    bool m_applyJitter = false;
+    uint32_t m_jitterIndex = 0;
+    float m_currentJitter[2] = {0.f, 0.f};
+    float m_previousJitter[2] = {0.f, 0.f};
     float m_maxViewScale = 1.f;
     bool m_changedThisFrame = true;
     prosper_CameraUniforms m_uniforms = {};

@@ -44,6 +44,40 @@ rtdi::GBuffer GBufferTracer::record(
     return ret;
 }
 
+GBufferTracer::VelocityGBuffer GBufferTracer::recordVelocity(
+    const scene::Camera &cam, uint32_t width, uint32_t height, scene::DrawType drawType, uint32_t frameIndex,
+    const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream)
+{
+    PROSPER_ASSERT(m_initialized);
+    prosper_pt_velocity_gbuffer_desc desc = {};
+    if (transforms && m_previousTransforms.size() == transformCount && transformCount != 0u)
+    {
+        desc.previousTransforms = m_previousTransforms.data();
+        desc.previousTransformCount = transformCount;
+    }
+    if (prosper_pt_trace_gbuffer_velocity(
+            m_ctx, static_cast<uint32_t>(drawType), frameIndex, 0u, &cam.uniforms(), width, height, &desc, stream) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("GBufferTracer::recordVelocity: ") + prosper_pt_last_error());
+    if (transforms)
+        m_previousTransforms.assign(transforms, transforms + transformCount);
+    else
+        m_previousTransforms.clear();
+    prosper_pt_restir_inputs in = {};
+    void *velocity = nullptr;
+    if (prosper_pt_get_gbuffer_device_ptrs(m_ctx, &in, nullptr, nullptr) != PROSPER_PT_OK ||
+        prosper_pt_get_velocity_device_ptr(m_ctx, &velocity, nullptr, nullptr) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("GBufferTracer::recordVelocity: ") + prosper_pt_last_error());
+    VelocityGBuffer ret;
+    ret.gbuffer.albedoRoughness = in.albedoRoughness;
+    ret.gbuffer.normalMetallic = in.normalMetallic;
+    ret.gbuffer.nonLinearDepth = in.nonLinearDepth;
+    ret.gbuffer.onDevice = true;
+    ret.gbuffer.width = width;
+    ret.gbuffer.height = height;
+    ret.velocity = velocity;
+    return ret;
+}
+
 } // namespace render
 
 // ---- plain-C shims (include/prosper_pt/prosper_host.h) ----
@@ -99,6 +133,43 @@ int prosper_host_gbuffer_tracer_record(
         outGBuffer->normalMetallic = g.normalMetallic;
         outGBuffer->nonLinearDepth = g.nonLinearDepth;
         outGBuffer->onDevice = 1;
+    }
+    catch (const std::exception &e)
+    {
+        prosper_host_set_error(e.what());
+        return PROSPER_PT_ERR_HIP;
+    }
+    return PROSPER_PT_OK;
+}
+
+int prosper_host_gbuffer_tracer_record_velocity(
+    prosper_host_gbuffer_tracer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
+    uint32_t frameIndex, const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream,
+    prosper_pt_restir_inputs *outGBuffer, void **outVelocity)
+{
+    if (!r || !camera || !outGBuffer || !outVelocity)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_record_velocity: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    if (drawType >= (uint32_t)scene::DrawType::Count)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_record_velocity: drawType out of range");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    try
+    {
+        scene::Camera &cam = *prosper_host_camera_object(camera);
+        cam.updateResolution(width, height);
+        cam.updateBuffer();
+        const render::GBufferTracer::VelocityGBuffer g = r->pass.recordVelocity(
+            cam, width, height, static_cast<scene::DrawType>(drawType), frameIndex, transforms, transformCount, stream);
+        *outGBuffer = prosper_pt_restir_inputs{};
+        outGBuffer->albedoRoughness = g.gbuffer.albedoRoughness;
+        outGBuffer->normalMetallic = g.gbuffer.normalMetallic;
+        outGBuffer->nonLinearDepth = g.gbuffer.nonLinearDepth;
+        outGBuffer->onDevice = 1;
+        *outVelocity = const_cast<void *>(g.velocity);
     }
     catch (const std::exception &e)
     {

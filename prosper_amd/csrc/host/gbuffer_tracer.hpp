@@ -2,11 +2,13 @@
 //
 // A ray-traced stand-in for the output of prosper's raster pass (reference: src/render/GBufferRenderer.hpp,
 // GBufferRenderer::record): the albedo/roughness, normal/metallic and depth images RtDirectIllumination reads, traced
-// over the context's scene by prosper_pt_trace_gbuffer into context-owned device buffers.  The raster pass itself
-// (meshlet culling, velocity, TAA jitter) stays out of scope.
+// over the context's scene by prosper_pt_trace_gbuffer into context-owned device buffers, and with `recordVelocity` the
+// velocity image TemporalAntiAliasing reads, sampled through the camera's TAA jitter (prosper_pt_trace_gbuffer_velocity;
+// DESIGN.md f10).  The raster pass itself (meshlet culling) stays out of scope.
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include "../../../include/prosper_pt/prosper_pt.h"
 #include "camera.hpp"
@@ -34,11 +36,26 @@ class GBufferTracer
         const scene::Camera &cam, uint32_t width, uint32_t height, scene::DrawType drawType, uint32_t frameIndex,
         bool jitter, void *stream);
 
+    struct VelocityGBuffer
+    {
+        rtdi::GBuffer gbuffer;
+        const void *velocity{nullptr}; // device pointer, width * height float2
+    };
+    // The same through the pixel centres of the camera's (jittered) projection, with the velocity target.  `transforms`
+    // (optional, `transformCount` = the scene's model instances): the instance transforms of this frame.  They are kept,
+    // and what the previous call kept is handed on as the previous frame's transforms (World keeps the previous
+    // frame's transform buffer the same way); the first call and a call after a changed count see unmoved instances.
+    // Without `transforms` the instances count as unmoved and nothing is kept.
+    [[nodiscard]] VelocityGBuffer recordVelocity(
+        const scene::Camera &cam, uint32_t width, uint32_t height, scene::DrawType drawType, uint32_t frameIndex,
+        const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream);
+
     [[nodiscard]] prosper_pt_ctx *context() const { return m_ctx; }
 
   private:
     bool m_initialized{false};
     prosper_pt_ctx *m_ctx{nullptr};
+    std::vector<prosper_ModelInstanceTransforms> m_previousTransforms;
 };
 
 } // namespace render

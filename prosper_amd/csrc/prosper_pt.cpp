@@ -786,7 +786,7 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         if ((rc = ctx->chainFork.record(ws.get()))) return rc;
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
-    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx))
+    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -844,6 +844,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_gbuffer_passes(ctx);
     destroy_dof_passes(ctx);
     destroy_bloom_passes(ctx);
+    destroy_taa_passes(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
@@ -853,6 +854,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     int rc = validate_scene(scene);
     if (rc != PROSPER_PT_OK) return rc;
     forget_ibl_maps(ctx);
+    forget_taa_history(ctx);
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());

@@ -71,6 +71,12 @@ void destroy_dof_passes(prosper_pt_ctx *ctx);
 struct BloomPassState;
 bool create_bloom_passes(prosper_pt_ctx *ctx);
 void destroy_bloom_passes(prosper_pt_ctx *ctx);
+// State of the temporal anti-aliasing resolve (pt_taa_passes.cpp): the two history images.  Made and freed like the others.
+struct TaaPassState;
+bool create_taa_passes(prosper_pt_ctx *ctx);
+void destroy_taa_passes(prosper_pt_ctx *ctx);
+// a new scene, or TemporalAntiAliasing::releasePreserved: the next resolve ignores the history
+void forget_taa_history(prosper_pt_ctx *ctx);
 
 #pragma GCC visibility pop
 
@@ -294,6 +300,7 @@ struct prosper_pt_ctx
     ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
     ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
     ppt::BloomPassState *bloomPasses = nullptr;
+    ppt::TaaPassState *taaPasses = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

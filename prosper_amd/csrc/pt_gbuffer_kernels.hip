@@ -7,6 +7,8 @@
 //                       maps of pt_ibl.hip in its _ibl variant
 #include "pt_gbuffer_kernels.hpp"
 
+#include <type_traits>
+
 #include "pt_device.hpp"
 #include "pt_ibl.hpp"
 #include "pt_render_common.hpp"
@@ -347,9 +349,46 @@ PPT_D f3 signed_oct_encode(f3 n)
     return o;
 }
 
+// The xy of (cameraToClip * worldToCamera * (p, 1)) / w, both matrices column-major (gbuffer.frag:74-75 over
+// forward.mesh:74-88); `direction`: worldToCamera as mat4(mat3(.)) (skybox.vert:16-24).  w comes from the matrices.
+PPT_D f2 project_ndc(const float *c, const float *m, f3 p, bool direction)
+{
+    float cam[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const float t = direction ? (k == 3 ? 1.0f : 0.0f) : m[12 + k];
+        const bool lastRow = direction && k == 3; // (0, 0, 0, 1)
+        cam[k] = lastRow ? 1.0f : __builtin_fmaf(m[8 + k], p.z, __builtin_fmaf(m[4 + k], p.y, __builtin_fmaf(m[k], p.x, t)));
+    }
+    const float x = __builtin_fmaf(c[12], cam[3], __builtin_fmaf(c[8], cam[2], __builtin_fmaf(c[4], cam[1], c[0] * cam[0])));
+    const float y = __builtin_fmaf(c[13], cam[3], __builtin_fmaf(c[9], cam[2], __builtin_fmaf(c[5], cam[1], c[1] * cam[0])));
+    const float w = __builtin_fmaf(c[15], cam[3], __builtin_fmaf(c[11], cam[2], __builtin_fmaf(c[7], cam[1], c[3] * cam[0])));
+    return f2{x / w, y / w};
+}
+
+// gbuffer.frag:76-84 / skybox.frag:22-29: the motion in NDC with both jitters taken out, y up, clamped as the SNORM
+// target clamps it
+PPT_D float2 ndc_velocity(const GBufferVelocityParams &v, f3 position, f3 previousPosition, bool direction)
+{
+    const f2 pos = project_ndc(v.cameraToClip, v.worldToCamera, position, direction);
+    const f2 prev = project_ndc(v.previousCameraToClip, v.previousWorldToCamera, previousPosition, direction);
+    const float vx = (pos.x - v.currentJitter[0]) - (prev.x - v.previousJitter[0]);
+    const float vy = -((pos.y - v.currentJitter[1]) - (prev.y - v.previousJitter[1]));
+    return make_float2(fmin_(fmax_(vx, -1.0f), 1.0f), fmin_(fmax_(vy, -1.0f), 1.0f));
+}
+
+struct GBufferNoVelocity
+{
+};
+
+// kVelocity: the primary ray goes through the point the (jittered) projection puts on the pixel centre, and a fourth
+// target takes the velocity, on hits and on the sky.  The plain instantiation reads nothing of `v`.
+template <bool kVelocity>
 __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     DeviceScene s, GBufferTraceParams g, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
-    float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow)
+    float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow,
+    std::conditional_t<kVelocity, GBufferVelocityParams, GBufferNoVelocity> v)
 {
     __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
     uint32_t px, py;
@@ -362,8 +401,10 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
 
     Rng rng{px, py, g.frameIndex};
     const f2 j = rng.rnd2d01();
-    const f2 uv = g.jitter ? f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height}
-                           : f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
+    f2 uv = g.jitter ? f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height}
+                     : f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
+    // ndc_jittered = ndc_unjittered + currentJitter: the unjittered ray half a jitter back lands on the pixel centre
+    if constexpr (kVelocity) uv = f2{uv.x - v.currentJitter[0] * 0.5f, uv.y - v.currentJitter[1] * 0.5f};
     const Ray ray = pinhole_camera_ray(g.r, uv);
     LaneCounters cnt = {};
     Hit hit;
@@ -373,9 +414,27 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
         albedoRoughness[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         nonLinearDepth[i] = 0.0f;
+        if constexpr (kVelocity) v.velocity[i] = ndc_velocity(v, ray.d, ray.d, true);
         return;
     }
     const Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
+    if constexpr (kVelocity)
+    {
+        f3 previous = sf.positionWS;
+        if (v.previousTransforms)
+        {
+            // the interpolated model-space vertex evaluate_surface transforms, through the instance's previous transform
+            const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + (s.triangleOffsets[hit.drawInstance] + hit.primitive));
+            const float4 q6 = rec[6], q7 = rec[7];
+            const f3 p0 = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
+            const f3 p1 = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
+            const f3 p2 = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
+            const float a = (1.0f - hit.bary.x) - hit.bary.y, b = hit.bary.x, c = hit.bary.y;
+            const f3 model = f3{bary1(p0.x, p1.x, p2.x, a, b, c), bary1(p0.y, p1.y, p2.y, a, b, c), bary1(p0.z, p1.z, p2.z, a, b, c)};
+            previous = mul_point_mat3x4(model, v.previousTransforms[s.drawInstances[hit.drawInstance].modelInstanceIndex].modelToWorld);
+        }
+        v.velocity[i] = ndc_velocity(v, sf.positionWS, previous, false);
+    }
     if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT && g.drawType != PROSPER_DRAW_TYPE_MESHLET_ID)
     {
         // gbuffer.frag:83-99
@@ -403,8 +462,18 @@ void launch_gbuffer_trace(
 {
     if (g.r.width == 0 || g.r.height == 0) return;
     hipLaunchKernelGGL(
-        gbuffer_trace_kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
-        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow);
+        gbuffer_trace_kernel<false>, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
+        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, GBufferNoVelocity{});
+}
+
+void launch_gbuffer_trace_velocity(
+    const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
+    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream)
+{
+    if (g.r.width == 0 || g.r.height == 0) return;
+    hipLaunchKernelGGL(
+        gbuffer_trace_kernel<true>, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
+        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, v);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -44,6 +44,19 @@ struct GBufferTraceParams
 void launch_gbuffer_trace(
     const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
     int32_t *stackOverflow, hipStream_t stream);
+// The same with a velocity target (gbuffer_trace_kernel<true>): the ray goes through the point that
+// cameraToClip * worldToCamera puts on the pixel centre (g.jitter must be 0), and `velocity` takes
+// (posNDC - currentJitter) - (prevPosNDC - previousJitter), y negated, clamped to [-1, 1], on hits and on the sky.
+struct GBufferVelocityParams
+{
+    float worldToCamera[16], cameraToClip[16], previousWorldToCamera[16], previousCameraToClip[16]; // column-major
+    float currentJitter[2], previousJitter[2];
+    const prosper_ModelInstanceTransforms *previousTransforms; // device, by model instance; nullptr: the instances did not move
+    float2 *velocity;                                          // r.width*r.height
+};
+void launch_gbuffer_trace_velocity(
+    const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
+    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream);
 // Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
 // uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
 // [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the

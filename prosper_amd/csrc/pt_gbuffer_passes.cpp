@@ -30,6 +30,10 @@ struct GBufferPassState
     DeviceBuffer gbuffer; // context-owned G-buffer targets (prosper_pt_trace_gbuffer): 16 + 16 + 4 bytes per pixel
     prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
     uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
+    DeviceBuffer velocity;           // context-owned velocity target (prosper_pt_trace_gbuffer_velocity): 8 bytes per pixel
+    DeviceBuffer previousTransforms; // the device copy of a call's previous instance transforms
+    void *velocityLast = nullptr;    // what the last prosper_pt_trace_gbuffer_velocity wrote
+    uint32_t velocityLastWidth = 0, velocityLastHeight = 0;
     DeviceBuffer clusterPointers; // prosper_pt_cluster_lights: uint2 per cluster
     DeviceBuffer clusterIndices;  // kClusterSlot uint16 entries per cluster
     DeviceBuffer clusterDropped;  // entries dropped, per cluster
@@ -172,10 +176,11 @@ int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, pro
     return PROSPER_PT_OK;
 }
 
-// The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.
+// The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.  `velocity`: the
+// velocity variant, whose matrices and jitters are filled in here from `camera`.
 int gbuffer_trace(
     prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s)
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s, GBufferVelocityParams *velocity = nullptr)
 {
     GBufferTraceParams g = {};
     set_camera_ray_params(g.r, camera);
@@ -201,13 +206,33 @@ int gbuffer_trace(
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
     if (orc != PROSPER_PT_OK) return orc;
     wait_for_slot(ctx->slots[0], s);
-    launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+    if (velocity)
+    {
+        std::memcpy(velocity->worldToCamera, &camera->worldToCamera, 64);
+        std::memcpy(velocity->cameraToClip, &camera->cameraToClip, 64);
+        std::memcpy(velocity->previousWorldToCamera, &camera->previousWorldToCamera, 64);
+        std::memcpy(velocity->previousCameraToClip, &camera->previousCameraToClip, 64);
+        for (int k = 0; k < 2; ++k)
+        {
+            velocity->currentJitter[k] = camera->currentJitter[k];
+            velocity->previousJitter[k] = camera->previousJitter[k];
+        }
+        launch_gbuffer_trace_velocity(ctx->scene, g, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+    }
+    else
+        launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
     release_slot(ctx->slots[0], s);
     PPT_HIP(hipGetLastError());
     GBufferPassState &st = *ctx->gbufferPasses;
     st.gbufferLast = t;
     st.gbufferLastWidth = width;
     st.gbufferLastHeight = height;
+    if (velocity)
+    {
+        st.velocityLast = velocity->velocity;
+        st.velocityLastWidth = width;
+        st.velocityLastHeight = height;
+    }
     return PROSPER_PT_OK;
 }
 
@@ -406,6 +431,93 @@ int prosper_pt_trace_gbuffer(
     if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s);
     if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
+}
+
+// ---- the same with a velocity target (what TemporalAntiAliasing reads) ----
+
+int prosper_pt_trace_gbuffer_velocity(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    const char *what = "prosper_pt_trace_gbuffer_velocity";
+    if (flags != 0u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
+    if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
+    if (!camera || !desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    const prosper_pt_gbuffer_targets &given = desc->targets;
+    const int targetCount = (given.albedoRoughness ? 1 : 0) + (given.normalMetallic ? 1 : 0) + (given.nonLinearDepth ? 1 : 0);
+    if (targetCount != 0 && targetCount != 3)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the three targets are given together or not at all");
+    if ((reinterpret_cast<uintptr_t>(given.albedoRoughness) | reinterpret_cast<uintptr_t>(given.normalMetallic) |
+         reinterpret_cast<uintptr_t>(given.nonLinearDepth)) & 15u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": targets must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(desc->velocity) & 7u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the velocity target must be 8-byte aligned");
+    if (!desc->previousTransforms && desc->previousTransformCount != 0u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount without previousTransforms");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    const int crc = check_scene(ctx, what);
+    if (crc != PROSPER_PT_OK) return crc;
+    if (desc->previousTransforms && desc->previousTransformCount != ctx->scene.modelInstanceCount)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t pixels = (size_t)width * height;
+    prosper_pt_gbuffer_targets t = given;
+    if (targetCount == 0) rc = gbuffer_owned_targets(ctx, pixels, s, t);
+    GBufferVelocityParams v = {};
+    v.velocity = static_cast<float2 *>(desc->velocity);
+    if (rc == PROSPER_PT_OK && !desc->velocity)
+    {
+        if (st.velocity.bytes < pixels * 8u && st.velocityLast == st.velocity.ptr)
+        {
+            st.velocityLast = nullptr;
+            st.velocityLastWidth = st.velocityLastHeight = 0;
+        }
+        rc = grow_to(st.velocity, pixels * 8u, s);
+        v.velocity = st.velocity.as<float2>();
+    }
+    if (rc == PROSPER_PT_OK && desc->previousTransforms)
+    {
+        const size_t bytes = sizeof(prosper_ModelInstanceTransforms) * (size_t)desc->previousTransformCount;
+        rc = grow_to(st.previousTransforms, bytes, s);
+        if (rc == PROSPER_PT_OK)
+        {
+            PPT_HIP(hipMemcpyAsync(st.previousTransforms.ptr, desc->previousTransforms, bytes, hipMemcpyHostToDevice, s));
+            v.previousTransforms = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
+        }
+    }
+    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, false, camera, width, height, t, s, &v);
+    if (rc != PROSPER_PT_OK) return rc;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_velocity_device_ptr(prosper_pt_ctx *ctx, void **out, uint32_t *width, uint32_t *height)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_velocity_device_ptr: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.velocityLast) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
+    *out = st.velocityLast;
+    if (width) *width = st.velocityLastWidth;
+    if (height) *height = st.velocityLastHeight;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_velocity(prosper_pt_ctx *ctx, float *host_float2, size_t pixels, void *stream)
+{
+    if (!ctx || !host_float2) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_velocity: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.velocityLast) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
+    if (pixels != (size_t)st.velocityLastWidth * st.velocityLastHeight)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_velocity: pixel count differs from the velocity target's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(host_float2, st.velocityLast, pixels * 8u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height)

@@ -53,6 +53,10 @@ class Camera:
     def end_frame(self):
         lib().prosper_host_camera_end_frame(self._h)
 
+    def set_jitter(self, apply_jitter):
+        """Camera::setJitter: the TAA jitter of the Halton(2, 3) cycle in the projection from the next update_buffer on."""
+        lib().prosper_host_camera_set_jitter(self._h, 1 if apply_jitter else 0)
+
     @classmethod
     def from_world(cls, world, width, height):
         cam = cls()
@@ -222,6 +226,19 @@ class GBufferTracer:
         if rc != 0:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
         return out
+
+    def record_velocity(self, camera, width, height, draw_type="Default", frame_index=0, transforms=None, stream=None):
+        """GBufferTracer::recordVelocity: the G-buffer through the camera's (jittered) pixel centres and the velocity
+        image; (S.RestirInputs, velocity device pointer).  `transforms`: this frame's ctypes array of
+        S.ModelInstanceTransforms (world.freeze()["transforms"]); the pass keeps it as the next call's previous frame."""
+        out, velocity = S.RestirInputs(), C.c_void_p()
+        rc = lib().prosper_host_gbuffer_tracer_record_velocity(
+            self._h, camera._h, width, height, S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
+            frame_index, None if transforms is None else C.cast(transforms, C.c_void_p), 0 if transforms is None else len(transforms),
+            C.c_void_p(stream), C.byref(out), C.byref(velocity))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out, velocity.value
 
     def close(self):
         if self._h:
@@ -413,6 +430,56 @@ class Bloom:
     def close(self):
         if self._h:
             lib().prosper_host_bloom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TemporalAntiAliasing:
+    """render::TemporalAntiAliasing (csrc/host/temporal_anti_aliasing.hpp) on a Context, with prosper's defaults: draw_ui
+    sets the four settings; record resolves into the context's HDR image (Context.read_hdr) and the preserved history
+    and returns the S.TaaPC it pushed; release_preserved drops the history."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_taa_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def draw_ui(self, catmull_rom=True, color_clipping=S.TAA_CLIPPING_VARIANCE, velocity_sampling=S.TAA_VELOCITY_CLOSEST,
+                luminance_weighting=True):
+        lib().prosper_host_taa_draw_ui(self._h, 1 if catmull_rom else 0, color_clipping, velocity_sampling,
+                                       1 if luminance_weighting else 0)
+
+    def record(self, width, height, velocity=None, depth=None, illumination=None, velocity_ptr=None, depth_ptr=None,
+               illumination_ptr=None, stream=None):
+        """Host arrays (`velocity` [h, w, 2], `depth` [h, w], `illumination` [h, w, 4]) or device pointers (`_ptr`), not
+        both; no illumination: the HDR image in place; no depth: the last traced G-buffer's."""
+        host = velocity is not None or depth is not None or illumination is not None
+        assert not (host and (velocity_ptr or depth_ptr or illumination_ptr)), "host and device inputs cannot be mixed"
+        arrays = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (illumination, velocity, depth)]
+        if host:
+            inp = S.TaaInputs(*[None if a is None else a.ctypes.data for a in arrays], 0)
+        else:
+            inp = S.TaaInputs(illumination_ptr, velocity_ptr, depth_ptr, 1)
+        pc = S.TaaPC()
+        rc = lib().prosper_host_taa_record(self._h, width, height, C.byref(inp), C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc
+
+    def release_preserved(self):
+        lib().prosper_host_taa_release_preserved(self._h)
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_taa_destroy(self._h)
             self._h = None
 
     def __del__(self):

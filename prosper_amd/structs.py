@@ -346,6 +346,13 @@ class GBufferTargets(C.Structure):
     _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetallic", C.c_void_p), ("nonLinearDepth", C.c_void_p)]
 
 
+class VelocityGBufferDesc(C.Structure):
+    """prosper_pt_velocity_gbuffer_desc: the three targets (all or none), the velocity target (None: context-owned), the
+    previous frame's instance transforms on the host (None: the instances did not move)"""
+    _fields_ = [("targets", GBufferTargets), ("velocity", C.c_void_p), ("previousTransforms", C.c_void_p),
+                ("previousTransformCount", C.c_uint32)]
+
+
 class DeferredShadingPC(C.Structure):
     """DeferredShadingPC, res/shader/shared/shader_structs/push_constants/deferred_shading.h"""
     _fields_ = [("drawType", C.c_uint32), ("ibl", C.c_uint32)]
@@ -421,6 +428,36 @@ BLOOM_STAGES = ("highlights", "horizontal", "blurred")
 BLOOM_HIGHLIGHTS, BLOOM_HORIZONTAL, BLOOM_BLURRED = range(3)
 BLOOM_LEVELS = 4
 BLOOM_HALF, BLOOM_QUARTER = 0, 1
+
+
+TAA_CLIPPING_NONE, TAA_CLIPPING_MIN_MAX, TAA_CLIPPING_VARIANCE = range(3)
+TAA_VELOCITY_CENTER, TAA_VELOCITY_LARGEST, TAA_VELOCITY_CLOSEST = range(3)
+
+
+class TaaPC(C.Structure):
+    """prosper_pt_taa_pc: the specialisation constants of taa_resolve.comp and resetHistory.  TaaPC.default() holds
+    prosper's defaults (TemporalAntiAliasing.hpp): Catmull-Rom, Variance, Closest, luminance weighting."""
+    _fields_ = [(n, C.c_uint32) for n in ("catmullRom", "colorClipping", "velocitySampling", "luminanceWeighting",
+                                          "resetHistory")]
+
+    @classmethod
+    def default(cls, catmull_rom=1, color_clipping=TAA_CLIPPING_VARIANCE, velocity_sampling=TAA_VELOCITY_CLOSEST,
+                luminance_weighting=1, reset_history=0):
+        return cls(catmull_rom, color_clipping, velocity_sampling, luminance_weighting, reset_history)
+
+
+class TaaInputs(C.Structure):
+    """prosper_pt_taa_inputs: illumination (None: the HDR image in place), velocity, depth (None: the last traced
+    G-buffer's; read by Closest alone)"""
+    _fields_ = [("illumination", C.c_void_p), ("velocity", C.c_void_p), ("nonLinearDepth", C.c_void_p),
+                ("onDevice", C.c_uint32)]
+
+
+class TaaInfo(C.Structure):
+    """prosper_pt_taa_info: the last resolve's extent, whether a history exists, whether the call ignored it, and the
+    device times of its two kernels"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid", "width", "height", "historyValid", "ignoredHistory")] + [
+        ("resolveMs", C.c_float), ("expandMs", C.c_float)]
 
 
 # ImageBasedLighting: the irradiance cube, the prefiltered radiance cube (mips 512 ... 1) and the BRDF LUT

@@ -18,6 +18,11 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred --bloom [--bloom-threshold T] [--bloom-quarter]
                                  prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
                                  defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573)
+    --deferred --taa [--frames N]
+                                 temporal anti-aliasing: N frames (8, one Halton cycle) of jittered camera -> velocity
+                                 G-buffer -> shading -> sky -> bloom -> prosper_pt_taa_resolve -> Camera::endFrame, through
+                                 the host layer's GBufferTracer and TemporalAntiAliasing; depth of field and the tone map
+                                 run after the last frame (Renderer.cpp:516-573's order)
     --deferred --sky --dof --aperture A --focus D
                                  prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
                                  aperture diameter A and focus distance D in scene units drive the push constants
@@ -66,14 +71,18 @@ def main():
     ap.add_argument("--bloom", action="store_true", help="with --deferred: bloom (multi-resolution blur) over the shaded image")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
     ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
+    ap.add_argument("--taa", action="store_true", help="with --deferred: temporal anti-aliasing over jittered frames")
+    ap.add_argument("--frames", type=int, default=8, help="with --taa: frames to resolve (8 is one Halton cycle)")
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
     ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
     args = ap.parse_args()
-    if (args.sky or args.dof or args.bloom) and not args.deferred:
-        ap.error("--sky, --bloom and --dof belong to --deferred")
+    if (args.sky or args.dof or args.bloom or args.taa) and not args.deferred:
+        ap.error("--sky, --bloom, --taa and --dof belong to --deferred")
+    if args.frames < 1:
+        ap.error("--frames must be at least 1")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
-    from prosper_amd.rt_reference import Bloom, Camera, DepthOfField
+    from prosper_amd.rt_reference import Bloom, Camera, DepthOfField, GBufferTracer, TemporalAntiAliasing
     w, h = (int(v) for v in args.size.lower().split("x"))
     world = gltf.load_gltf(args.gltf, bc7_on_gpu=True)  # prosper_cache BC7 files are decoded by the library at upload
     if world.missing_images:
@@ -99,16 +108,35 @@ def main():
         if args.ibl:
             ctx.generate_ibl()  # once per sky, before the first frame that applies IBL (Renderer.cpp:380-382)
         t0 = time.perf_counter()
-        ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
-        if args.sky:
-            ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
-        if args.bloom:
-            bloom = Bloom(ctx)
+        bloom = Bloom(ctx) if args.bloom else None
+        if bloom:
             bloom.draw_ui(threshold=args.bloom_threshold, resolution_scale=S.BLOOM_QUARTER if args.bloom_quarter else S.BLOOM_HALF)
-            bloom.record(w, h)  # in place
+        if args.taa:
+            hcam.set_jitter(True)
+            tracer, taa = GBufferTracer(ctx), TemporalAntiAliasing(ctx)
+            transforms = world.freeze()["transforms"]
+        for frame in range(args.frames if args.taa else 1):
+            if args.taa:
+                # the G-buffer through the jittered projection's pixel centres, with the velocity the resolve reads
+                cam, focal = hcam.update_buffer()
+                g, _ = tracer.record_velocity(hcam, w, h, frame_index=frame, transforms=transforms)
+                ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth, ibl=1 if args.ibl else 0)
+            else:
+                ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
+            if args.sky:
+                ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
+            if bloom:
+                bloom.record(w, h)  # in place
+            if args.taa:
+                taa.record(w, h)  # in place, over the traced velocity and depth
+                hcam.end_frame()
+        if bloom:
             info = ctx.bloom_info()
             print("bloom: threshold %.3f, working extent %dx%d, streak half-width %d" % (
                 args.bloom_threshold, info.workingWidth, info.workingHeight, info.streakHalfWidth), file=sys.stderr)
+        if args.taa:
+            info = ctx.taa_info()
+            print("taa: %d frames, last resolve %.3f ms + expand %.3f ms" % (args.frames, info.resolveMs, info.expandMs), file=sys.stderr)
         if args.dof:
             dpc = DepthOfField(ctx).record(hcam, w, h)  # in place over the traced G-buffer's depth
             print("depth of field: focus %.3f, maxBackgroundCoC %.2f half-resolution texels, gatherRadius %d tiles" % (
