@@ -178,13 +178,20 @@ int prosper_host_depth_of_field_record(
 /* render::bloom::Bloom (host/bloom.hpp; reference src/render/bloom/Bloom.hpp) on a context (borrowed), with prosper's
  * defaults: threshold 1, blend factors .9, .04, .04, biquadratic sampling, half resolution.  draw_ui sets what prosper's
  * drawUi edits (resolutionScale: 0 Half, 1 Quarter); record = prosper_pt_bloom with those settings over `illumination`
- * (RGBA32F; NULL: the context's HDR image in place) and returns the push constants it used. */
+ * (RGBA32F; NULL: the context's HDR image in place) and returns the push constants it used.  set_technique picks
+ * render::bloom::Technique (0 MultiResolutionBlur, the default; 1 Fft; any other value is ignored with the checkbox) and
+ * sets GenerateKernel's "Re-generate kernel";
+ * with Fft, record = prosper_pt_bloom_fft with what fft_push_constants returns, and `outPushConstants` still receives
+ * the blur's.  A record with the blur drops the kernel's DFT as Bloom.cpp:117 does; release_preserved drops it too. */
 typedef struct prosper_host_bloom prosper_host_bloom;
 int prosper_host_bloom_create(prosper_pt_ctx *ctx, prosper_host_bloom **out);
 void prosper_host_bloom_destroy(prosper_host_bloom *pass);
 void prosper_host_bloom_draw_ui(
     prosper_host_bloom *pass, float threshold, float blendFactor0, float blendFactor1, float blendFactor2,
     uint32_t biquadratic, uint32_t resolutionScale);
+void prosper_host_bloom_set_technique(prosper_host_bloom *pass, uint32_t technique, uint32_t regenerateKernel);
+void prosper_host_bloom_release_preserved(prosper_host_bloom *pass);
+void prosper_host_bloom_fft_push_constants(prosper_host_bloom *pass, prosper_pt_bloom_fft_pc *out);
 int prosper_host_bloom_record(
     prosper_host_bloom *pass, uint32_t width, uint32_t height, const void *illumination, uint32_t onDevice, void *stream,
     prosper_pt_bloom_pc *outPushConstants);

@@ -815,7 +815,7 @@ int prosper_pt_get_dof_info(prosper_pt_ctx *ctx, prosper_pt_dof_info *out);
 /* ---- bloom, the multi-resolution blur (src/render/bloom/{Separate,Reduce,Blur,Compose}.cpp, res/shader/bloom/) ----
  * What prosper runs first between the sky-filled illumination and the tone map (Renderer.cpp:516-573):
  * its default technique (Bloom.hpp:57-58: MultiResolutionBlur at half resolution), plain compute over the context's HDR
- * image.  The FFT technique is not part of this library.  Additive: the ABI version stays 4. */
+ * image.  The FFT technique: prosper_pt_bloom_fft below.  Additive: the ABI version stays 4. */
 typedef struct prosper_pt_bloom_pc
 {
     float threshold;          /* finite, >= 0; Separate.hpp: 1 */
@@ -890,6 +890,84 @@ typedef struct prosper_pt_bloom_info
     float separateMs, reduceMs, blurHorizontalMs[3], blurVerticalMs[3], composeMs;
 } prosper_pt_bloom_info;
 int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out);
+
+/* ---- bloom, the FFT technique (src/render/bloom/{Separate,GenerateKernel,Fft,Convolution,Compose}.cpp) ----
+ * The other entry of render::bloom::Technique (Bloom.cpp:83-114): the highlights are convolved with a
+ * generated kernel image through the DFT.  Plain compute over the context's HDR image, like prosper_pt_bloom, whose
+ * images it does not touch.  Additive: the ABI version stays 4. */
+typedef struct prosper_pt_bloom_fft_pc
+{
+    float threshold;           /* finite, >= 0; Separate.hpp: 1 */
+    uint32_t resolutionScale;  /* 0 Half, 1 Quarter */
+    uint32_t biquadratic;      /* 0 / 1; Compose.hpp: 1 */
+    uint32_t regenerateKernel; /* 0 / 1: remake the kernel's DFT (prosper's "Re-generate kernel") */
+    uint32_t reserved[4];      /* 0 */
+} prosper_pt_bloom_fft_pc;
+struct prosper_pt_bloom_fft_plan /* (no typedef: the function below has the name) */
+{
+    uint32_t dim;           /* max(bit_ceil(max(width, height)) / s, 256) with s = 2 (Half) or 4 (Quarter) */
+    uint32_t kernelDim;     /* height / s */
+    float convolutionScale; /* 2.f / float(kernelDim), times 2 at Quarter */
+};
+/* The extents prosper_pt_bloom_fft works on (Separate.cpp:98-101, GenerateKernel.cpp:81-85, Bloom.cpp:95-98).  Host
+ * only: it needs neither a context nor a GPU.  -1 on an extent or a scale prosper_pt_bloom_fft refuses. */
+int prosper_pt_bloom_fft_plan(uint32_t width, uint32_t height, uint32_t resolutionScale,
+                              struct prosper_pt_bloom_fft_plan *out);
+/* render::bloom::Bloom::record with Technique::Fft; `illumination`, `onDevice` and the result as prosper_pt_bloom.
+ *   separate     separate.comp as in prosper_pt_bloom, over dim x dim into a one-level RGBA16F image: texels whose
+ *                lookups fall outside the illumination store (0, 0, 0, 0)
+ *   kernel       generate_kernel.comp: kernelDim x kernelDim RGBA32F, the mean of filterValue(p) over 8 x 8 sub-samples
+ *                p = ((8 xy + (i, j) + .5) / (8 kernelDim)) 2 - 1, filterValue as written.  The definition is the value in
+ *                double precision rounded once to float32 (GLSL's float32 exp, atan, sin and cos have no stated
+ *                precision); it is evaluated on the device in double.  prepare_kernel.comp wraps it round the corners
+ *                of a dim x dim RGBA32F image: pIn = pOut + kernelDim / 2 below dim / 2, pOut + (kernelDim - 2 dim) / 2
+ *                from there on (formed in halves from integers, truncated), zero outside, .g = .a = 0.  Its forward
+ *                DFT is kept by the context and remade when kernelDim or dim change or regenerateKernel is 1
+ *   transform    a texel is the complex numbers r + i g and b + i a.  Forward: X[ky][kx] = (1 / dim) sum x[y][x]
+ *                e^{-2 pi i (kx x + ky y) / dim} in natural order; inverse: the unnormalised inverse DFT.  Each
+ *                dimension is one kernel that holds whole lines in LDS; twiddles from a table made in double
+ *   convolution  DFT(highlights) * DFT(kernel) * convolutionScale as a complex product per channel pair, then the inverse.
+ *                The pass runs rows forward; columns forward, the product and columns inverse in one launch; rows inverse
+ *   compose      out = (illumination.rgb + highlight, 1): one edge-clamped bilinear lookup of the convolved RGBA32F image
+ *                at the texel coordinate (2 coord + 1 - s) / (2 s); biquadratic = 1: sampleBiquadratic with res = dim
+ * Refused, changing nothing: a NULL pc, a non-finite or negative threshold, an unknown scale, flags above 1, non-zero
+ * reserved words, an empty extent, width / s or height / s of 0, max(width, height) above 8192 (dim is at most 4096),
+ * and illumination = NULL when the HDR image has another extent.  It needs no scene. */
+int prosper_pt_bloom_fft(
+    prosper_pt_ctx *ctx, const prosper_pt_bloom_fft_pc *pc, uint32_t width, uint32_t height, const void *illumination,
+    uint32_t onDevice, void *stream);
+/* One 2-D transform of a dim x dim RGBA32F image (`in` and `out` on the device when `onDevice` is not 0; they may be the
+ * same) with the kernels prosper_pt_bloom_fft uses: rows, then columns.  dim: a power of two in [256, 4096].  Waits for
+ * `stream` when the images are on the host. */
+int prosper_pt_bloom_fft_transform(
+    prosper_pt_ctx *ctx, uint32_t dim, uint32_t inverse, const void *in, void *out, uint32_t onDevice, void *stream);
+/* Drops the kernel's DFT the context keeps (GenerateKernel::releasePreserved): the next call remakes it. */
+void prosper_pt_bloom_fft_release_kernel(prosper_pt_ctx *ctx);
+enum
+{
+    PROSPER_PT_BLOOM_FFT_HIGHLIGHTS = 0, /* dim x dim RGBA16F */
+    PROSPER_PT_BLOOM_FFT_KERNEL = 1,     /* kernelDim x kernelDim RGBA32F, centred */
+    PROSPER_PT_BLOOM_FFT_KERNEL_DFT = 2, /* dim x dim RGBA32F */
+    PROSPER_PT_BLOOM_FFT_CONVOLVED = 3,  /* dim x dim RGBA32F: what compose reads */
+    PROSPER_PT_BLOOM_FFT_STAGE_COUNT = 4,
+};
+/* Synchronises `stream` and copies one image of the last prosper_pt_bloom_fft to host memory, row-major; byte_size must
+ * be exactly its size.  NO_SCENE before the first call. */
+int prosper_pt_read_bloom_fft_stage(prosper_pt_ctx *ctx, uint32_t stage, void *host, size_t byte_size, void *stream);
+typedef struct prosper_pt_bloom_fft_info
+{
+    uint32_t valid; /* 1 once prosper_pt_bloom_fft ran */
+    uint32_t width, height, dim, kernelDim;
+    uint32_t kernelRemade; /* 1: the last call made the kernel's DFT; 0: it used the kept one */
+    float convolutionScale;
+    uint32_t fused; /* bit k: stage k of the times below shares a launch.  0x70: the forward columns, the convolution
+                       and the inverse columns are one launch, timed as convolutionMs; forwardFftMs and inverseFftMs
+                       are then the row launches alone */
+    /* device time of each stage of the last call (reading them waits for it); generate, prepare and the kernel's FFT
+     * are 0 when the kernel was not remade */
+    float separateMs, generateMs, prepareMs, kernelFftMs, forwardFftMs, convolutionMs, inverseFftMs, composeMs;
+} prosper_pt_bloom_fft_info;
+int prosper_pt_get_bloom_fft_info(prosper_pt_ctx *ctx, prosper_pt_bloom_fft_info *out);
 
 /* ---- temporal anti-aliasing: the resolve (src/render/TemporalAntiAliasing.cpp, res/shader/taa_resolve.comp) ----
  * What prosper runs between bloom and depth of field (Renderer.cpp:516-573), on by default there

@@ -112,6 +112,13 @@ def lib():
     L.prosper_pt_bloom_streak_weights.restype = None
     L.prosper_pt_read_bloom_stage.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
     L.prosper_pt_get_bloom_info.argtypes = [vp, C.POINTER(S.BloomInfo)]
+    L.prosper_pt_bloom_fft_plan.argtypes = [u32, u32, u32, C.POINTER(S.BloomFftPlan)]
+    L.prosper_pt_bloom_fft.argtypes = [vp, C.POINTER(S.BloomFftPC), u32, u32, vp, u32, vp]
+    L.prosper_pt_bloom_fft_transform.argtypes = [vp, u32, u32, vp, vp, u32, vp]
+    L.prosper_pt_bloom_fft_release_kernel.argtypes = [vp]
+    L.prosper_pt_bloom_fft_release_kernel.restype = None
+    L.prosper_pt_read_bloom_fft_stage.argtypes = [vp, u32, vp, C.c_size_t, vp]
+    L.prosper_pt_get_bloom_fft_info.argtypes = [vp, C.POINTER(S.BloomFftInfo)]
     L.prosper_pt_taa_resolve.argtypes = [vp, C.POINTER(S.TaaPC), u32, u32, C.POINTER(S.TaaInputs), vp]
     L.prosper_pt_taa_release_history.argtypes = [vp]
     L.prosper_pt_taa_release_history.restype = None
@@ -219,6 +226,12 @@ def lib():
     L.prosper_host_bloom_destroy.restype = None
     L.prosper_host_bloom_draw_ui.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, u32, u32]
     L.prosper_host_bloom_draw_ui.restype = None
+    L.prosper_host_bloom_set_technique.argtypes = [vp, u32, u32]
+    L.prosper_host_bloom_set_technique.restype = None
+    L.prosper_host_bloom_release_preserved.argtypes = [vp]
+    L.prosper_host_bloom_release_preserved.restype = None
+    L.prosper_host_bloom_fft_push_constants.argtypes = [vp, C.POINTER(S.BloomFftPC)]
+    L.prosper_host_bloom_fft_push_constants.restype = None
     L.prosper_host_bloom_record.argtypes = [vp, u32, u32, vp, u32, vp, C.POINTER(S.BloomPC)]
     L.prosper_host_taa_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_taa_destroy.argtypes = [vp]
@@ -284,6 +297,13 @@ def bloom_streak_weights(half_width):
     rg, b = np.empty(2 * half_width, np.float32), np.empty(2 * half_width, np.float32)
     lib().prosper_pt_bloom_streak_weights(half_width, rg.ctypes.data, b.ctypes.data)
     return rg, b
+
+
+def bloom_fft_plan(width, height, resolution_scale=0):
+    """prosper_pt_bloom_fft_plan: S.BloomFftPlan of an extent (needs no GPU); ProsperPtError on one bloom_fft refuses."""
+    plan = S.BloomFftPlan()
+    _check(lib().prosper_pt_bloom_fft_plan(width, height, resolution_scale, C.byref(plan)))
+    return plan
 
 
 def has_experiments():
@@ -802,6 +822,44 @@ class Context:
         i = self.bloom_info()
         out = np.empty((max(i.workingHeight >> level, 1), max(i.workingWidth >> level, 1), 4), np.float16)
         _check(lib().prosper_pt_read_bloom_stage(self._h, stage, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def bloom_fft(self, pc, width, height, illumination=None, illumination_ptr=None, stream=None):
+        """render::bloom::Bloom's FFT technique (prosper_pt_bloom_fft) with `pc` (S.BloomFftPC) into the HDR image; the
+        inputs as `bloom`."""
+        assert illumination is None or illumination_ptr is None, "host and device inputs cannot be mixed"
+        il = None if illumination is None else np.ascontiguousarray(illumination, np.float32)
+        assert il is None or il.shape == (height, width, 4)
+        ptr = illumination_ptr if il is None else il.ctypes.data
+        _check(lib().prosper_pt_bloom_fft(self._h, C.byref(pc), width, height, C.c_void_p(ptr), 1 if il is None else 0,
+                                          C.c_void_p(stream)))
+
+    def bloom_fft_transform(self, image, inverse=False, stream=None):
+        """One 2-D transform (prosper_pt_bloom_fft_transform) of a host array [dim, dim, 4] float32, a texel the complex
+        numbers r + i g and b + i a: the DFT divided by dim, or the unnormalised inverse."""
+        src = np.ascontiguousarray(image, np.float32)
+        assert src.ndim == 3 and src.shape[0] == src.shape[1] and src.shape[2] == 4
+        out = np.empty_like(src)
+        _check(lib().prosper_pt_bloom_fft_transform(self._h, src.shape[0], 1 if inverse else 0, src.ctypes.data, out.ctypes.data, 0,
+                                                    C.c_void_p(stream)))
+        return out
+
+    def bloom_fft_release_kernel(self):
+        lib().prosper_pt_bloom_fft_release_kernel(self._h)
+
+    def bloom_fft_info(self):
+        """S.BloomFftInfo: the last FFT bloom's extents, whether the kernel was remade and the per-stage device times."""
+        info = S.BloomFftInfo()
+        _check(lib().prosper_pt_get_bloom_fft_info(self._h, C.byref(info)))
+        return info
+
+    def read_bloom_fft_stage(self, stage, stream=None):
+        """One image of the last FFT bloom: S.BLOOM_FFT_HIGHLIGHTS float16 [dim, dim, 4], _KERNEL float32 [kernelDim,
+        kernelDim, 4], _KERNEL_DFT and _CONVOLVED float32 [dim, dim, 4]."""
+        i = self.bloom_fft_info()
+        n = i.kernelDim if stage == S.BLOOM_FFT_KERNEL else i.dim
+        out = np.empty((n, n, 4), np.float16 if stage == S.BLOOM_FFT_HIGHLIGHTS else np.float32)
+        _check(lib().prosper_pt_read_bloom_fft_stage(self._h, stage, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
 
     def taa_resolve(self, pc, width, height, velocity=None, depth=None, illumination=None, velocity_ptr=None,

@@ -36,12 +36,38 @@ prosper_pt_bloom_pc Bloom::pushConstants() const
     return pc;
 }
 
+prosper_pt_bloom_fft_pc Bloom::fftPushConstants() const
+{
+    prosper_pt_bloom_fft_pc pc = {};
+    pc.threshold = m_threshold;
+    pc.resolutionScale = static_cast<uint32_t>(m_resolutionScale);
+    pc.biquadratic = m_biquadraticSampling ? 1u : 0u;
+    pc.regenerateKernel = m_regenerateKernel ? 1u : 0u;
+    return pc;
+}
+
+void Bloom::releasePreserved()
+{
+    PROSPER_ASSERT(m_initialized);
+    prosper_pt_bloom_fft_release_kernel(m_ctx);
+}
+
 Bloom::Output Bloom::record(const Input &input, void *stream)
 {
     PROSPER_ASSERT(m_initialized);
-    const prosper_pt_bloom_pc pc = pushConstants();
-    if (prosper_pt_bloom(m_ctx, &pc, input.width, input.height, input.illumination, input.onDevice ? 1u : 0u, stream) != PROSPER_PT_OK)
-        throw std::runtime_error(std::string("Bloom::record: ") + prosper_pt_last_error());
+    int rc;
+    if (m_technique == Technique::Fft)
+    {
+        const prosper_pt_bloom_fft_pc pc = fftPushConstants();
+        rc = prosper_pt_bloom_fft(m_ctx, &pc, input.width, input.height, input.illumination, input.onDevice ? 1u : 0u, stream);
+    }
+    else
+    {
+        releasePreserved(); // Bloom.cpp:117
+        const prosper_pt_bloom_pc pc = pushConstants();
+        rc = prosper_pt_bloom(m_ctx, &pc, input.width, input.height, input.illumination, input.onDevice ? 1u : 0u, stream);
+    }
+    if (rc != PROSPER_PT_OK) throw std::runtime_error(std::string("Bloom::record: ") + prosper_pt_last_error());
     Output ret;
     void *ptr = nullptr;
     if (prosper_pt_get_hdr_device_ptr(m_ctx, &ptr, nullptr) != PROSPER_PT_OK)
@@ -90,6 +116,23 @@ void prosper_host_bloom_draw_ui(
     r->pass.setBlendFactors(blendFactor0, blendFactor1, blendFactor2);
     r->pass.setBiquadraticSampling(biquadratic != 0u);
     r->pass.setResolutionScale(static_cast<render::bloom::ResolutionScale>(resolutionScale));
+}
+
+void prosper_host_bloom_set_technique(prosper_host_bloom *r, uint32_t technique, uint32_t regenerateKernel)
+{
+    if (!r || technique > static_cast<uint32_t>(render::bloom::Technique::Fft)) return; // an unknown technique changes nothing
+    r->pass.setTechnique(static_cast<render::bloom::Technique>(technique));
+    r->pass.setRegenerateKernel(regenerateKernel != 0u);
+}
+
+void prosper_host_bloom_release_preserved(prosper_host_bloom *r)
+{
+    if (r) r->pass.releasePreserved();
+}
+
+void prosper_host_bloom_fft_push_constants(prosper_host_bloom *r, prosper_pt_bloom_fft_pc *out)
+{
+    if (r && out) *out = r->pass.fftPushConstants();
 }
 
 int prosper_host_bloom_record(

@@ -1,9 +1,10 @@
 // host/bloom.hpp — render::bloom::Bloom of the headless host layer.
 //
-// Same surface as prosper's pass (reference: src/render/bloom/Bloom.hpp, Bloom.cpp:15-141): `record` runs separate,
-// reduce, blur and compose over the illumination through prosper_pt_bloom and returns the context's HDR image.  Only
-// the multi-resolution blur exists here.  What drawUi edits in prosper (Separate.cpp:81, Compose.cpp:85-87,
-// Bloom.cpp:61-62) are plain setters, with prosper's defaults (Separate.hpp:46, Compose.hpp:48-49, Bloom.hpp:57).
+// Same surface as prosper's pass (reference: src/render/bloom/Bloom.hpp, Bloom.cpp:15-141): `record` switches on the
+// technique as Bloom.cpp:83-124 does - separate, reduce, blur and compose through prosper_pt_bloom, or separate, the
+// kernel's DFT, the convolution and compose through prosper_pt_bloom_fft - and returns the context's HDR image.  What
+// drawUi edits in prosper (Bloom.cpp:60-62, Separate.cpp:81, GenerateKernel.cpp:65, Compose.cpp:85-87) are plain
+// setters, with prosper's defaults (Separate.hpp:46, Compose.hpp:48-49, Bloom.hpp:57-58).
 #pragma once
 
 #include <cstdint>
@@ -17,6 +18,12 @@ enum class ResolutionScale : uint32_t
 {
     Half = 0,
     Quarter = 1,
+};
+
+enum class Technique : uint32_t
+{
+    MultiResolutionBlur = 0,
+    Fft = 1,
 };
 
 class Bloom
@@ -36,6 +43,11 @@ class Bloom
     void setBlendFactors(float mip0, float mip1, float mip2);
     void setBiquadraticSampling(bool on) { m_biquadraticSampling = on; }
     void setResolutionScale(ResolutionScale scale) { m_resolutionScale = scale; }
+    void setTechnique(Technique technique) { m_technique = technique; }
+    // GenerateKernel's "Re-generate kernel" checkbox: while set, every Fft record remakes the kernel's DFT
+    void setRegenerateKernel(bool on) { m_regenerateKernel = on; }
+    // drops the kernel's DFT the context keeps; the next Fft record remakes it
+    void releasePreserved();
 
     struct Input
     {
@@ -52,6 +64,7 @@ class Bloom
     };
     // what record pushes with the current settings
     [[nodiscard]] prosper_pt_bloom_pc pushConstants() const;
+    [[nodiscard]] prosper_pt_bloom_fft_pc fftPushConstants() const; // with Technique::Fft
     // Throws std::runtime_error on failure.
     [[nodiscard]] Output record(const Input &input, void *stream);
 
@@ -61,6 +74,8 @@ class Bloom
     bool m_initialized{false};
     prosper_pt_ctx *m_ctx{nullptr};
     ResolutionScale m_resolutionScale{ResolutionScale::Half};
+    Technique m_technique{Technique::MultiResolutionBlur};
+    bool m_regenerateKernel{false};
     float m_threshold{1.f};
     bool m_biquadraticSampling{true};
     float m_blendFactors[3]{.9f, .04f, .04f};

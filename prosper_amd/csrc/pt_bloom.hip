@@ -6,6 +6,8 @@
 //   bloom_blur_kernel       blur.comp: four weighted taps along a row or a column of one level
 //   bloom_streak_kernel     blur.comp's horizontal pass of level 1: the four taps and the row-wide streak over level 0
 //   bloom_compose_kernel    compose.comp: illumination + the blend of three levels, bilinear or biquadratic
+//   bloom_compose_fft_kernel  compose.comp with MULTI_RESOLUTION = false: illumination + the convolved image of the FFT
+//                           technique (pt_bloom_fft.hip), which also runs separate over its dim x dim image
 //
 // Images have no sampler here; the lookups are written out.  A lookup's texel coordinate is formed in integers where
 // the GLSL goes through a normalised uv: (coord + 0.5) / size_a * size_b - 0.5 is a ratio of integers, whose floor and
@@ -343,6 +345,50 @@ __global__ __launch_bounds__(256) void bloom_compose_kernel(BloomParams p, Bloom
                            in.z + ((level[0].b * k0 + level[1].b * k1) + level[2].b * k2), 1.0f);
 }
 
+// ---- compose of the FFT technique ----
+
+PPT_D Rgb texel_edge(const float4 *__restrict__ img, int32_t w, int32_t h, int32_t x, int32_t y)
+{
+    const float4 c = img[(size_t)clamp_i(y, 0, h - 1) * (uint32_t)w + (uint32_t)clamp_i(x, 0, w - 1)];
+    return Rgb{c.x, c.y, c.z};
+}
+PPT_D Rgb edge_bilinear(const float4 *__restrict__ img, int32_t w, int32_t h, int32_t ix, float fx, int32_t iy, float fy)
+{
+    return blend4(texel_edge(img, w, h, ix, iy), texel_edge(img, w, h, ix + 1, iy), texel_edge(img, w, h, ix, iy + 1),
+                  texel_edge(img, w, h, ix + 1, iy + 1), fx, fy);
+}
+
+// compose.comp with MULTI_RESOLUTION = false: illumination + one lookup of the convolved dim x dim RGBA32F image at
+// highlightUV = (coord + 0.5) / (dim scale), i.e. the texel coordinate (2 coord + 1 - scale) / (2 scale): compose_axis
+// with a "full" extent of scale texels over a level of one.  Biquadratic: res = dim, so q = fract((coord + 0.5) / scale)
+// and the offsets are q (q - 1) + 0.5 texels.
+__global__ __launch_bounds__(256) void bloom_compose_fft_kernel(
+    uint32_t width, uint32_t height, uint32_t scale, uint32_t dim, uint32_t biquadraticFlag, const float4 *illumination,
+    const float4 *__restrict__ convolved, float4 *out)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= width || y >= height) return;
+    const bool biquadratic = biquadraticFlag != 0u;
+    const int32_t n = (int32_t)dim;
+    const ComposeAxis ax = compose_axis(x, scale, 1u, (float)scale, biquadratic);
+    const ComposeAxis ay = compose_axis(y, scale, 1u, (float)scale, biquadratic);
+    Rgb v;
+    if (biquadratic)
+    {
+        const Rgb s00 = edge_bilinear(convolved, n, n, ax.i[0], ax.f[0], ay.i[0], ay.f[0]);
+        const Rgb s01 = edge_bilinear(convolved, n, n, ax.i[0], ax.f[0], ay.i[1], ay.f[1]);
+        const Rgb s11 = edge_bilinear(convolved, n, n, ax.i[1], ax.f[1], ay.i[1], ay.f[1]);
+        const Rgb s10 = edge_bilinear(convolved, n, n, ax.i[1], ax.f[1], ay.i[0], ay.f[0]);
+        v = Rgb{(((s00.r + s01.r) + s11.r) + s10.r) * 0.25f, (((s00.g + s01.g) + s11.g) + s10.g) * 0.25f,
+                (((s00.b + s01.b) + s11.b) + s10.b) * 0.25f};
+    }
+    else
+        v = edge_bilinear(convolved, n, n, ax.i[0], ax.f[0], ay.i[0], ay.f[0]);
+    const size_t i = (size_t)y * width + x;
+    const float4 in = illumination[i];
+    out[i] = make_float4(in.x + v.r, in.y + v.g, in.z + v.b, 1.0f);
+}
+
 dim3 image_grid(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
 
 } // namespace bloom
@@ -381,6 +427,27 @@ void bloom_streak_weights(uint32_t halfWidth, float *rg, float *b)
         rg[k] = (float)(((c * 4.0) * wave) * fall);
         b[k] = (float)((4.0 * wave) * fall);
     }
+}
+
+void launch_bloom_fft_separate(
+    uint32_t width, uint32_t height, uint32_t scale, float threshold, uint32_t dim, const float4 *illumination, uint2 *highlights,
+    hipStream_t stream)
+{
+    BloomParams p = {};
+    p.width = width;
+    p.height = height;
+    p.scale = scale;
+    p.threshold = threshold;
+    p.levelW[0] = p.levelH[0] = dim;
+    hipLaunchKernelGGL(bloom_separate_kernel, image_grid(dim, dim), dim3(256), 0, stream, p, illumination, highlights);
+}
+
+void launch_bloom_fft_compose(
+    uint32_t width, uint32_t height, uint32_t scale, uint32_t dim, uint32_t biquadratic, const float4 *illumination,
+    const float4 *convolved, float4 *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bloom_compose_fft_kernel, image_grid(width, height), dim3(256), 0, stream, width, height, scale, dim, biquadratic,
+                       illumination, convolved, out);
 }
 
 void launch_bloom(const BloomParams &p, const BloomBuffers &b, hipEvent_t *events, hipStream_t stream)

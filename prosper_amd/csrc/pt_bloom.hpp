@@ -49,4 +49,15 @@ void bloom_streak_weights(uint32_t halfWidth, float *rg, float *b);
 // The four passes on `stream`.  `events` (optional, kBloomStages + 1): recorded before each stage and after the last.
 void launch_bloom(const BloomParams &p, const BloomBuffers &b, hipEvent_t *events, hipStream_t stream);
 
+// The two passes the FFT technique (pt_bloom_fft.hpp) shares with the blur.  Separate over dim x dim RGBA16F: a texel
+// whose lookups fall outside the illumination reads the border and stores (0, 0, 0, 0), the transform's zero padding.
+void launch_bloom_fft_separate(
+    uint32_t width, uint32_t height, uint32_t scale, float threshold, uint32_t dim, const float4 *illumination, uint2 *highlights,
+    hipStream_t stream);
+// compose.comp with MULTI_RESOLUTION = false: out = (illumination.rgb + the lookup of the convolved dim x dim RGBA32F
+// image, 1).  `illumination` may be `out`.
+void launch_bloom_fft_compose(
+    uint32_t width, uint32_t height, uint32_t scale, uint32_t dim, uint32_t biquadratic, const float4 *illumination,
+    const float4 *convolved, float4 *out, hipStream_t stream);
+
 } // namespace ppt

@@ -1,5 +1,5 @@
-// pt_bloom_passes.cpp — C-ABI of bloom (include/prosper_pt/prosper_pt.h): prosper_pt_bloom over the context's HDR image,
-// with the readbacks of what it produced.  Kernels: pt_bloom.hip.
+// pt_bloom_passes.cpp — C-ABI of bloom (include/prosper_pt/prosper_pt.h): prosper_pt_bloom and prosper_pt_bloom_fft over
+// the context's HDR image, with the readbacks of what they produced.  Kernels: pt_bloom.hip, pt_bloom_fft.hip.
 #include "../../include/prosper_pt/prosper_pt.h"
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pt_bloom.hpp"
+#include "pt_bloom_fft.hpp"
 #include "pt_context.hpp"
 #include "pt_pass_support.hpp"
 
@@ -17,6 +18,22 @@ using namespace ppt;
 
 namespace ppt
 {
+
+// The FFT technique.  It shares no image with the blur but the device copy of a host illumination.
+struct BloomFftState
+{
+    DeviceBuffer highlights;            // dim x dim RGBA16F
+    DeviceBuffer kernelImage;           // keptKernelDim x keptKernelDim RGBA32F, centred
+    DeviceBuffer kernelDft;             // keptDim x keptDim RGBA32F
+    DeviceBuffer convolved;             // dim x dim RGBA32F: the highlights' DFT, the product, its inverse
+    DeviceBuffer transformWork;         // of prosper_pt_bloom_fft_transform with host images
+    DeviceBuffer twiddles[5];           // e^{-2 pi i k / dim} of dim = 256 << n, made at first use
+    uint32_t keptKernelDim = 0, keptDim = 0; // what kernelDft was made for; 0: there is none
+    uint32_t width = 0, height = 0;     // of the last prosper_pt_bloom_fft
+    BloomFftPlan last = {};
+    bool remade = false, valid = false;
+    StageEvents<kBloomFftStages> timing;
+};
 
 struct BloomPassState
 {
@@ -27,6 +44,7 @@ struct BloomPassState
     BloomParams last = {}; // of the last prosper_pt_bloom
     bool valid = false;
     StageEvents<kBloomStages> timing;
+    BloomFftState fft;
 };
 
 bool create_bloom_passes(prosper_pt_ctx *ctx)
@@ -72,6 +90,53 @@ bool stage_has_level(const BloomParams &p, uint32_t stage, uint32_t level)
 {
     if (stage == PROSPER_PT_BLOOM_HIGHLIGHTS) return level < kBloomLevels;
     return level >= p.firstLevel && level < p.firstLevel + kBloomBlurLevels;
+}
+
+// the twiddle table of `dim` on the device
+int ensure_twiddles(BloomFftState &st, uint32_t dim, hipStream_t s, const float2 **out)
+{
+    uint32_t n = 0;
+    while ((kBloomFftMinDim << n) < dim) ++n;
+    DeviceBuffer &table = st.twiddles[n];
+    if (!table.ptr)
+    {
+        std::vector<float> w(2u * (size_t)dim);
+        bloom_fft_twiddles(dim, w.data());
+        const size_t bytes = w.size() * sizeof(float);
+        const int rc = grow_buffer(table, GrowWait::None, nullptr, bytes, bytes);
+        if (rc != PROSPER_PT_OK) return rc;
+        // `w` is gone when this returns; a table that was not filled must not be found by the next call
+        hipError_t e = hipMemcpyAsync(table.ptr, w.data(), bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess)
+        {
+            (void)hipFree(table.ptr);
+            table.ptr = nullptr;
+            table.bytes = 0;
+            PPT_HIP(e);
+        }
+    }
+    *out = table.as<float2>();
+    return PROSPER_PT_OK;
+}
+
+// what prosper_pt_bloom_fft refuses of its push constants and extent, before it looks at the context
+int check_bloom_fft_arguments(const prosper_pt_bloom_fft_pc *pc, uint32_t width, uint32_t height, BloomFftPlan &plan)
+{
+    if (!pc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: null argument");
+    if (!std::isfinite(pc->threshold)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: non-finite threshold");
+    if (pc->threshold < 0.0f) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: negative threshold");
+    if (pc->resolutionScale > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: unknown resolution scale");
+    if (pc->biquadratic > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: biquadratic is 0 or 1");
+    if (pc->regenerateKernel > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: regenerateKernel is 0 or 1");
+    for (uint32_t r : pc->reserved)
+        if (r != 0u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: reserved words must be 0");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: empty extent");
+    if (width > 2u * kBloomFftMaxDim || height > 2u * kBloomFftMaxDim)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: an extent above 8192 is not supported");
+    if (!bloom_fft_plan(width, height, pc->resolutionScale, plan))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: the extent leaves the working image empty");
+    return PROSPER_PT_OK;
 }
 
 } // namespace
@@ -192,6 +257,183 @@ int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out)
         info.streakHalfWidth = p.streakHalfWidth;
         PPT_HIP(hipSetDevice(ctx->device));
         if (const int rc = st.timing.elapsed(&info.separateMs)) return rc;
+    }
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_bloom_fft_plan(uint32_t width, uint32_t height, uint32_t resolutionScale, struct prosper_pt_bloom_fft_plan *out)
+{
+    BloomFftPlan plan = {};
+    if (!out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft_plan: null argument");
+    if (!bloom_fft_plan(width, height, resolutionScale, plan))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft_plan: an extent or a scale prosper_pt_bloom_fft refuses");
+    out->dim = plan.dim;
+    out->kernelDim = plan.kernelDim;
+    out->convolutionScale = plan.convolutionScale;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_bloom_fft(
+    prosper_pt_ctx *ctx, const prosper_pt_bloom_fft_pc *pc, uint32_t width, uint32_t height, const void *illumination, uint32_t onDevice,
+    void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    BloomFftPlan plan = {};
+    if (const int rc = check_bloom_fft_arguments(pc, width, height, plan)) return rc;
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: null argument");
+    const bool inPlace = illumination == nullptr;
+    if (inPlace && !hdr_has_extent(ctx, width, height))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: the HDR image has another extent");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BloomFftState &st = ctx->bloomPasses->fft;
+    const size_t pixels = (size_t)width * height, texels = (size_t)plan.dim * plan.dim;
+    const bool remake = pc->regenerateKernel != 0u || st.keptKernelDim != plan.kernelDim || st.keptDim != plan.dim;
+
+    st.valid = false;
+    int rc = PROSPER_PT_OK;
+    const float2 *twiddles = nullptr;
+    if (!inPlace && !onDevice) rc = grow_to(ctx->bloomPasses->hostInput, pixels * 16u, s);
+    if (rc == PROSPER_PT_OK) rc = grow_to(st.highlights, texels * 8u, s);
+    if (rc == PROSPER_PT_OK) rc = grow_to(st.convolved, texels * 16u, s);
+    if (rc == PROSPER_PT_OK && remake)
+    {
+        st.keptKernelDim = st.keptDim = 0u;
+        rc = grow_to(st.kernelImage, (size_t)plan.kernelDim * plan.kernelDim * 16u, s);
+        if (rc == PROSPER_PT_OK) rc = grow_to(st.kernelDft, texels * 16u, s);
+    }
+    if (rc == PROSPER_PT_OK) rc = ensure_twiddles(st, plan.dim, s, &twiddles);
+    if (rc != PROSPER_PT_OK) return rc;
+    if ((rc = st.timing.create())) return rc;
+
+    const float4 *input = ctx->hdr;
+    if (!inPlace)
+    {
+        input = static_cast<const float4 *>(illumination);
+        if (!onDevice)
+        {
+            PPT_HIP(hipMemcpyAsync(ctx->bloomPasses->hostInput.ptr, illumination, pixels * 16u, hipMemcpyHostToDevice, s));
+            input = ctx->bloomPasses->hostInput.as<float4>();
+        }
+        // (an explicit illumination that is the HDR image itself behaves as in place)
+        rc = prepare_hdr(ctx, width, height, nullptr, s);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+    hipEvent_t *events = st.timing.events;
+    uint32_t e = 0;
+    auto mark = [&]() { (void)hipEventRecord(events[e++], s); };
+    float4 *kernelDft = st.kernelDft.as<float4>(), *convolved = st.convolved.as<float4>();
+    mark();
+    launch_bloom_fft_separate(width, height, plan.scale, pc->threshold, plan.dim, input, st.highlights.as<uint2>(), s);
+    mark();
+    if (remake) launch_bloom_fft_generate_kernel(plan.kernelDim, st.kernelImage.as<float4>(), s);
+    mark();
+    if (remake) launch_bloom_fft_prepare_kernel(plan.kernelDim, plan.dim, st.kernelImage.as<float4>(), kernelDft, s);
+    mark();
+    if (remake)
+    {
+        launch_bloom_fft_rows(plan.dim, false, kernelDft, false, kernelDft, twiddles, s);
+        launch_bloom_fft_columns(plan.dim, false, kernelDft, kernelDft, twiddles, s);
+    }
+    mark();
+    launch_bloom_fft_rows(plan.dim, false, st.highlights.ptr, true, convolved, twiddles, s);
+    mark();
+    launch_bloom_fft_middle(plan.dim, convolved, kernelDft, twiddles, plan.convolutionScale, s);
+    mark();
+    launch_bloom_fft_rows(plan.dim, true, convolved, false, convolved, twiddles, s);
+    mark();
+    launch_bloom_fft_compose(width, height, plan.scale, plan.dim, pc->biquadratic, input, convolved, ctx->hdr, s);
+    mark();
+    PPT_HIP(hipGetLastError());
+    st.keptKernelDim = plan.kernelDim;
+    st.keptDim = plan.dim;
+    st.width = width;
+    st.height = height;
+    st.last = plan;
+    st.remade = remake;
+    st.valid = true;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_bloom_fft_transform(
+    prosper_pt_ctx *ctx, uint32_t dim, uint32_t inverse, const void *in, void *out, uint32_t onDevice, void *stream)
+{
+    if (!bloom_fft_is_dim(dim))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft_transform: dim is a power of two in [256, 4096]");
+    if (inverse > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft_transform: inverse is 0 or 1");
+    if (!ctx || !in || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft_transform: null argument");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BloomFftState &st = ctx->bloomPasses->fft;
+    const size_t bytes = (size_t)dim * dim * 16u;
+    const float2 *twiddles = nullptr;
+    int rc = ensure_twiddles(st, dim, s, &twiddles);
+    if (rc == PROSPER_PT_OK && !onDevice) rc = grow_to(st.transformWork, bytes, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    const void *source = in;
+    float4 *target = static_cast<float4 *>(out);
+    if (!onDevice)
+    {
+        PPT_HIP(hipMemcpyAsync(st.transformWork.ptr, in, bytes, hipMemcpyHostToDevice, s));
+        source = st.transformWork.ptr;
+        target = st.transformWork.as<float4>();
+    }
+    launch_bloom_fft_rows(dim, inverse != 0u, source, false, target, twiddles, s);
+    launch_bloom_fft_columns(dim, inverse != 0u, target, target, twiddles, s);
+    PPT_HIP(hipGetLastError());
+    if (!onDevice)
+    {
+        PPT_HIP(hipMemcpyAsync(out, target, bytes, hipMemcpyDeviceToHost, s));
+        PPT_HIP(hipStreamSynchronize(s));
+    }
+    return PROSPER_PT_OK;
+}
+
+void prosper_pt_bloom_fft_release_kernel(prosper_pt_ctx *ctx)
+{
+    if (ctx) ctx->bloomPasses->fft.keptKernelDim = ctx->bloomPasses->fft.keptDim = 0u;
+}
+
+int prosper_pt_read_bloom_fft_stage(prosper_pt_ctx *ctx, uint32_t stage, void *host, size_t byte_size, void *stream)
+{
+    if (stage >= PROSPER_PT_BLOOM_FFT_STAGE_COUNT)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_bloom_fft_stage: unknown stage");
+    if (!ctx || !host) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_bloom_fft_stage: null argument");
+    const BloomFftState &st = ctx->bloomPasses->fft;
+    if (!st.valid) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_bloom_fft_stage: no bloom_fft has run yet");
+    const size_t texels = (size_t)st.last.dim * st.last.dim, kernelTexels = (size_t)st.last.kernelDim * st.last.kernelDim;
+    const DeviceBuffer *image = &st.highlights;
+    size_t bytes = texels * 8u;
+    if (stage == PROSPER_PT_BLOOM_FFT_KERNEL) image = &st.kernelImage, bytes = kernelTexels * 16u;
+    if (stage == PROSPER_PT_BLOOM_FFT_KERNEL_DFT) image = &st.kernelDft, bytes = texels * 16u;
+    if (stage == PROSPER_PT_BLOOM_FFT_CONVOLVED) image = &st.convolved, bytes = texels * 16u;
+    if (byte_size != bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_bloom_fft_stage: byte_size differs from the image's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(host, image->ptr, bytes, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_bloom_fft_info(prosper_pt_ctx *ctx, prosper_pt_bloom_fft_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_bloom_fft_info: null argument");
+    const BloomFftState &st = ctx->bloomPasses->fft;
+    prosper_pt_bloom_fft_info info = {};
+    if (st.valid)
+    {
+        info.valid = 1u;
+        info.width = st.width;
+        info.height = st.height;
+        info.dim = st.last.dim;
+        info.kernelDim = st.last.kernelDim;
+        info.kernelRemade = st.remade ? 1u : 0u;
+        info.convolutionScale = st.last.convolutionScale;
+        info.fused = 0x70u; // the forward columns, the convolution and the inverse columns are one launch
+        PPT_HIP(hipSetDevice(ctx->device));
+        if (const int rc = st.timing.elapsed(&info.separateMs)) return rc;
+        if (!st.remade) info.generateMs = info.prepareMs = info.kernelFftMs = 0.0f;
     }
     *out = info;
     return PROSPER_PT_OK;

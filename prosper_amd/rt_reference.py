@@ -402,16 +402,28 @@ class DepthOfField:
 
 class Bloom:
     """render::bloom::Bloom (csrc/host/bloom.hpp) on a Context, with prosper's defaults: draw_ui sets the threshold, the
-    blend factors, the sampling and the resolution scale; record runs the four passes into the context's HDR image
-    (Context.read_hdr) and returns the S.BloomPC it pushed."""
+    blend factors, the sampling and the resolution scale; record runs the passes of the technique (S.BLOOM_MULTI_RESOLUTION_BLUR,
+    the default, or S.BLOOM_FFT) into the context's HDR image (Context.read_hdr) and returns the S.BloomPC, or with the
+    FFT technique the S.BloomFftPC, it pushed."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, technique=S.BLOOM_MULTI_RESOLUTION_BLUR):
         h = C.c_void_p()
         rc = lib().prosper_host_bloom_create(ctx._h, C.byref(h))
         if rc != 0:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
         self._h = h
         self._ctx = ctx
+        self._technique = technique
+        self.set_technique(technique)
+
+    def set_technique(self, technique, regenerate_kernel=False):
+        """render::bloom::Technique and GenerateKernel's "Re-generate kernel" checkbox"""
+        self._technique = technique
+        lib().prosper_host_bloom_set_technique(self._h, technique, 1 if regenerate_kernel else 0)
+
+    def release_preserved(self):
+        """drops the kernel's DFT the context keeps"""
+        lib().prosper_host_bloom_release_preserved(self._h)
 
     def draw_ui(self, threshold=1.0, blend_factors=(0.9, 0.04, 0.04), biquadratic=True, resolution_scale=S.BLOOM_HALF):
         lib().prosper_host_bloom_draw_ui(self._h, threshold, blend_factors[0], blend_factors[1], blend_factors[2],
@@ -425,6 +437,9 @@ class Bloom:
                                              1 if il is None else 0, C.c_void_p(stream), C.byref(pc))
         if rc != 0:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        if self._technique == S.BLOOM_FFT:
+            pc = S.BloomFftPC()
+            lib().prosper_host_bloom_fft_push_constants(self._h, C.byref(pc))
         return pc
 
     def close(self):

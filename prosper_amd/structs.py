@@ -430,6 +430,37 @@ BLOOM_LEVELS = 4
 BLOOM_HALF, BLOOM_QUARTER = 0, 1
 
 
+class BloomFftPC(C.Structure):
+    """prosper_pt_bloom_fft_pc: threshold (Separate.hpp), resolution scale (0 Half, 1 Quarter), sampling (Compose.hpp) and
+    prosper's "Re-generate kernel".  BloomFftPC.default() holds prosper's defaults."""
+    _fields_ = [("threshold", C.c_float), ("resolutionScale", C.c_uint32), ("biquadratic", C.c_uint32),
+                ("regenerateKernel", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    @classmethod
+    def default(cls, threshold=1.0, resolution_scale=0, biquadratic=1, regenerate_kernel=0):
+        return cls(threshold, resolution_scale, biquadratic, regenerate_kernel, (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+class BloomFftPlan(C.Structure):
+    """prosper_pt_bloom_fft_plan: the transform's and the kernel image's extents and the convolution's scale"""
+    _fields_ = [("dim", C.c_uint32), ("kernelDim", C.c_uint32), ("convolutionScale", C.c_float)]
+
+
+class BloomFftInfo(C.Structure):
+    """prosper_pt_bloom_fft_info: the last FFT bloom's extents, whether it remade the kernel's DFT, which stages ran
+    fused and the per-stage device times"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid", "width", "height", "dim", "kernelDim", "kernelRemade")] + [
+        ("convolutionScale", C.c_float), ("fused", C.c_uint32)] + [
+        (n, C.c_float) for n in ("separateMs", "generateMs", "prepareMs", "kernelFftMs", "forwardFftMs", "convolutionMs",
+                                 "inverseFftMs", "composeMs")]
+
+
+# prosper_pt_read_bloom_fft_stage: the images of the FFT technique
+BLOOM_FFT_STAGES = ("highlights", "kernel", "kernel_dft", "convolved")
+BLOOM_FFT_HIGHLIGHTS, BLOOM_FFT_KERNEL, BLOOM_FFT_KERNEL_DFT, BLOOM_FFT_CONVOLVED = range(4)
+BLOOM_MULTI_RESOLUTION_BLUR, BLOOM_FFT = 0, 1  # render::bloom::Technique
+
+
 TAA_CLIPPING_NONE, TAA_CLIPPING_MIN_MAX, TAA_CLIPPING_VARIANCE = range(3)
 TAA_VELOCITY_CENTER, TAA_VELOCITY_LARGEST, TAA_VELOCITY_CLOSEST = range(3)
 

@@ -15,9 +15,10 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred --ibl             with the image-based lighting term: the irradiance / radiance maps and the BRDF LUT
                                  are generated once from the sky (prosper_pt_generate_ibl), then the frame is shaded
     --deferred --sky             prosper_pt_skybox_fill after the shading: the sky wherever the G-buffer's ray missed
-    --deferred --bloom [--bloom-threshold T] [--bloom-quarter]
+    --deferred --bloom [--bloom-threshold T] [--bloom-quarter] [--bloom-fft]
                                  prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
-                                 defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573)
+                                 defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573);
+                                 --bloom-fft: the FFT technique (prosper_pt_bloom_fft) instead of the multi-resolution blur
     --deferred --taa [--frames N]
                                  temporal anti-aliasing: N frames (8, one Halton cycle) of jittered camera -> velocity
                                  G-buffer -> shading -> sky -> bloom -> prosper_pt_taa_resolve -> Camera::endFrame, through
@@ -71,12 +72,15 @@ def main():
     ap.add_argument("--bloom", action="store_true", help="with --deferred: bloom (multi-resolution blur) over the shaded image")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
     ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
+    ap.add_argument("--bloom-fft", action="store_true", help="with --bloom: the FFT technique instead of the multi-resolution blur")
     ap.add_argument("--taa", action="store_true", help="with --deferred: temporal anti-aliasing over jittered frames")
     ap.add_argument("--frames", type=int, default=8, help="with --taa: frames to resolve (8 is one Halton cycle)")
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
     ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
     args = ap.parse_args()
+    if args.bloom_fft and not args.bloom:
+        ap.error("--bloom-fft belongs to --bloom")
     if (args.sky or args.dof or args.bloom or args.taa) and not args.deferred:
         ap.error("--sky, --bloom, --taa and --dof belong to --deferred")
     if args.frames < 1:
@@ -108,7 +112,7 @@ def main():
         if args.ibl:
             ctx.generate_ibl()  # once per sky, before the first frame that applies IBL (Renderer.cpp:380-382)
         t0 = time.perf_counter()
-        bloom = Bloom(ctx) if args.bloom else None
+        bloom = Bloom(ctx, technique=S.BLOOM_FFT if args.bloom_fft else S.BLOOM_MULTI_RESOLUTION_BLUR) if args.bloom else None
         if bloom:
             bloom.draw_ui(threshold=args.bloom_threshold, resolution_scale=S.BLOOM_QUARTER if args.bloom_quarter else S.BLOOM_HALF)
         if args.taa:
@@ -130,7 +134,11 @@ def main():
             if args.taa:
                 taa.record(w, h)  # in place, over the traced velocity and depth
                 hcam.end_frame()
-        if bloom:
+        if bloom and args.bloom_fft:
+            info = ctx.bloom_fft_info()
+            print("bloom (FFT): threshold %.3f, transform %dx%d, kernel image %dx%d" % (
+                args.bloom_threshold, info.dim, info.dim, info.kernelDim, info.kernelDim), file=sys.stderr)
+        elif bloom:
             info = ctx.bloom_info()
             print("bloom: threshold %.3f, working extent %dx%d, streak half-width %d" % (
                 args.bloom_threshold, info.workingWidth, info.workingHeight, info.streakHalfWidth), file=sys.stderr)
