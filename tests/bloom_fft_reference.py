@@ -1,8 +1,9 @@
 """NumPy restatement of prosper's bloom, the FFT technique (not a test module), for tests/test_bloom_fft*.py:
 
   plan(w, h, resolution_scale)              dim, kernelDim and the convolution's scale
-  separate(illum, threshold, scale, dim)    separate.comp over the padded dim x dim image: (v, s)
-  kernel_image(kd), kernel_margins(kd)      generate_kernel.comp in float64, and how close a sub-sample comes to a branch
+  separate(illum, threshold, scale, dim)    separate.comp over the padded dim x dim image, or its lit rectangle: (v, s)
+  kernel_image(kd), kernel_margins(kd)      generate_kernel.comp in float64, and how close a sub-sample comes to a branch;
+                                            both over the whole image or, in bands, over the texel rows asked for
   prepare(kernel, dim)                      prepare_kernel.comp
   dft(x, inverse), convolve(...)            the transform (np.fft, float64) with prosper's normalisations, the convolution
   compose(illum, convolved, ...)            compose.comp with MULTI_RESOLUTION = false: (v, s)
@@ -47,19 +48,27 @@ def plan(w, h, resolution_scale):
 
 # ---- separate ----
 
-def separate(illum, threshold, resolution_scale, dim):
-    """(v, s) of the dim x dim highlights, and the first column and row whose lookups all fall outside the input."""
+def outside_from(w, h, resolution_scale):
+    """The first column and row of the highlights whose lookups all fall outside the w x h input."""
+    if resolution_scale == HALF:
+        return (w + 2) // 2, (h + 2) // 2  # the texels 2 c - 1 and 2 c: outside from 2 c - 1 >= size on
+    return (w + 5) // 4, (h + 5) // 4  # the texels 4 c - 2 .. 4 c + 1: outside from 4 c - 2 >= size on
+
+
+def separate(illum, threshold, resolution_scale, dim, crop=False):
+    """(v, s) of the dim x dim highlights, and the first column and row whose lookups all fall outside the input.  With
+    `crop`, (v, s) of the rectangle [:y_out, :x_out] alone (cut to dim): what a dim of 4096 leaves affordable."""
     h, w = illum.shape[:2]
     rgb = illum[..., :3].astype(np.float64)
-    ys, xs = np.meshgrid(np.arange(dim, dtype=np.float64), np.arange(dim, dtype=np.float64), indexing="ij")
+    outside = outside_from(w, h, resolution_scale)
+    nx, ny = (min(outside[0], dim), min(outside[1], dim)) if crop else (dim, dim)
+    ys, xs = np.meshgrid(np.arange(ny, dtype=np.float64), np.arange(nx, dtype=np.float64), indexing="ij")
     inv_w, inv_h = 1.0 / w, 1.0 / h
     if resolution_scale == HALF:
         mean = B.bilinear(rgb, (2 * xs) * inv_w, (2 * ys) * inv_h, edge=False)
-        outside = ((w + 2) // 2, (h + 2) // 2)  # the texels 2 c - 1 and 2 c: outside from 2 c - 1 >= size on
     else:
         mean = sum(B.bilinear(rgb, (4 * xs + dx) * inv_w, (4 * ys + dy) * inv_h, edge=False)
                    for dx, dy in ((-1, -1), (-1, 1), (1, -1), (1, 1))) / 4.0
-        outside = ((w + 5) // 4, (h + 5) // 4)  # the texels 4 c - 2 .. 4 c + 1: outside from 4 c - 2 >= size on
     t = float(np.float32(threshold))
     return np.maximum(mean - t, 0.0), np.abs(mean) + t, outside
 
@@ -106,25 +115,53 @@ def _filter_value(px, py):
     return rg, ba, d
 
 
-def _sub_samples(kd):
+def _sub_samples(kd, texel_rows=None):
+    """(px, py) of the 8 kd sub-sample columns over every sub-sample row, or over the eight of each texel row given."""
     c = ((np.arange(8 * kd, dtype=np.float64) + 0.5) / (8.0 * kd)) * 2.0 - 1.0
-    py, px = np.meshgrid(c, c, indexing="ij")
+    cy = c if texel_rows is None else c[(8 * np.asarray(texel_rows, np.int64)[:, None] + np.arange(8)).ravel()]
+    py, px = np.meshgrid(cy, c, indexing="ij")
     return px, py
 
 
-def kernel_image(kd):
-    """[kd, kd, 4] float64: the mean of filterValue over the 8 x 8 sub-samples of each texel (round it once to float32)."""
-    rg, ba, _ = _filter_value(*_sub_samples(kd))
-    rg = rg.reshape(kd, 8, kd, 8).sum(axis=(1, 3)) / 64.0
-    ba = ba.reshape(kd, 8, kd, 8).sum(axis=(1, 3)) / 64.0
-    return np.stack([rg, rg, ba, ba], axis=-1)
+KERNEL_BAND = 16  # texel rows evaluated at once where rows are given: 128 sub-sample rows of 8 kd values per temporary
 
 
-def kernel_margins(kd):
-    """How close a sub-sample comes to a branch of filterValue: (min |dStar|, min ||p.y| - .005|)."""
-    px, py = _sub_samples(kd)
-    d = _filter_value(px, py)[2]
-    return float(np.abs(d).min()), float(np.abs(np.abs(py) - 0.005).min())
+def _bands(kd, rows, of_band):
+    """of_band over `rows` (sorted texel rows) in bands of at most KERNEL_BAND, a few bands at a time."""
+    rows = [int(r) for r in rows]
+    assert rows == sorted(set(rows)) and (not rows or (0 <= rows[0] and rows[-1] < kd))
+    bands = [rows[i:i + KERNEL_BAND] for i in range(0, len(rows), KERNEL_BAND)]
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        return list(pool.map(of_band, bands))
+
+
+def kernel_image(kd, rows=None):
+    """[kd, kd, 4] float64: the mean of filterValue over the 8 x 8 sub-samples of each texel (round it once to float32).
+    With `rows`, a sorted list of texel rows, only their 8 len(rows) sub-sample rows are evaluated, in bands, and the
+    result is [len(rows), kd, 4]: the same arithmetic, so the same bytes as those rows of the whole image."""
+    def mean(px, py):
+        n = px.shape[0] // 8
+        rg, ba, _ = _filter_value(px, py)
+        rg = rg.reshape(n, 8, kd, 8).sum(axis=(1, 3)) / 64.0
+        ba = ba.reshape(n, 8, kd, 8).sum(axis=(1, 3)) / 64.0
+        return np.stack([rg, rg, ba, ba], axis=-1)
+
+    if rows is None:
+        return mean(*_sub_samples(kd))
+    return np.concatenate(_bands(kd, rows, lambda band: mean(*_sub_samples(kd, band))) or [np.empty((0, kd, 4))], axis=0)
+
+
+def kernel_margins(kd, rows=None):
+    """How close a sub-sample comes to a branch of filterValue: (min |dStar|, min ||p.y| - .005|); with `rows`, over the
+    sub-samples of those texel rows, in bands."""
+    def margins(px, py):
+        d = _filter_value(px, py)[2]
+        return float(np.abs(d).min()), float(np.abs(np.abs(py) - 0.005).min())
+
+    if rows is None:
+        return margins(*_sub_samples(kd))
+    found = _bands(kd, rows, lambda band: margins(*_sub_samples(kd, band)))
+    return min(f[0] for f in found), min(f[1] for f in found)
 
 
 def prepare_indices(kd, dim):

@@ -8,7 +8,12 @@ own magnitude, five to six orders above E.  Forward then inverse returns dim tim
 same rule.  No texel is left out.  The cases of dim 4096 move 268 MB images and take ten seconds or so each.
 
 The whole pass, each stage against the restatement (tests/bloom_fft_reference.py) over the GPU's own read-back of that
-stage's inputs, as tests/test_bloom.py does.  The extents (tests/test_bloom_fft_cpu.py) all have dim 256 or 512.
+stage's inputs, as tests/test_bloom.py does.  The extents (tests/test_bloom_fft_cpu.py): CASES have dim 256 or 512;
+EDGE_CASES a kernelDim of dim itself and of 1; LARGE_CASES reach dim 1024, 2048 and 4096, landscape and portrait, under the
+same rules, with the kernel image compared on KERNEL_ROWS(kernelDim) (every row up to 600) and separate restated over
+the rectangle it can light, the rest of the read-back being exactly zero.  The two cases of dim 4096 read back 134 +
+268 + 268 MB, run the schedule and the float64 DFT over them on the CPU and, like the transform's, take ten seconds or
+so each; their read-backs are not kept.
 """
 import ctypes as C
 
@@ -18,15 +23,15 @@ import pytest
 import bloom_fft_reference as F
 import bloom_reference as B
 from prosper_amd import capi, structs as S
-from test_bloom_fft_cpu import CASES
+from test_bloom_fft_cpu import CASES, EDGE_CASES, KERNEL_ROWS, LARGE_CASES, SEED
 from test_depth_of_field import DeviceCopy, check_half, share
 
 pytestmark = pytest.mark.gpu
 
-SEED = 11
 DIMS = (256, 512, 1024, 2048, 4096)
 INPUTS = ("random", "impulse", "frequency")
-IDS = ["%dx%d-%s-%s" % (w, h, "half" if s == F.HALF else "quarter", "biquadratic" if b else "bilinear") for w, h, s, b in CASES]
+ALL_CASES = CASES + EDGE_CASES + LARGE_CASES
+IDS = ["%dx%d-%s-%s" % (w, h, "half" if s == F.HALF else "quarter", "biquadratic" if b else "bilinear") for w, h, s, b in ALL_CASES]
 STAGES = ((S.BLOOM_FFT_HIGHLIGHTS, "highlights"), (S.BLOOM_FFT_KERNEL, "kernel"), (S.BLOOM_FFT_KERNEL_DFT, "kernel_dft"),
           (S.BLOOM_FFT_CONVOLVED, "convolved"))
 _runs = {}
@@ -101,15 +106,17 @@ def read_back(ctx):
 
 
 def run(ctx, w, h, scale, biquadratic):
-    """One call per case and session, with everything it left behind."""
+    """One call per case and session, with everything it left behind; a large case's images are its caller's alone."""
     key = (w, h, scale, biquadratic)
-    if key not in _runs:
-        illum, pc = B.design(w, h, SEED), S.BloomFftPC.default(B.THRESHOLD, scale, biquadratic)
-        ctx.bloom_fft(pc, w, h, illum)
-        rb = read_back(ctx)
-        rb.update(pc=pc, illum=illum)
+    if key in _runs:
+        return _runs[key]
+    illum, pc = B.design(w, h, SEED), S.BloomFftPC.default(B.THRESHOLD, scale, biquadratic)
+    ctx.bloom_fft(pc, w, h, illum)
+    rb = read_back(ctx)
+    rb.update(pc=pc, illum=illum)
+    if key not in LARGE_CASES:
         _runs[key] = rb
-    return _runs[key]
+    return rb
 
 
 def same_bytes(a, b):
@@ -120,6 +127,13 @@ def one_ulp(got32, want64):
     """got is the float32 rounding of want, or one of its two neighbours"""
     w = want64.astype(np.float32)
     return (got32 == w) | (got32 == np.nextafter(w, np.float32(np.inf))) | (got32 == np.nextafter(w, np.float32(-np.inf)))
+
+
+def worst_ulps(got32, want64):
+    """The largest distance of got from want in units of the float32 spacing at want."""
+    w = want64.astype(np.float32)
+    spacing = np.maximum(np.spacing(np.abs(w)), np.float32(np.finfo(np.float32).smallest_subnormal)).astype(np.float64)
+    return float((np.abs(got32.astype(np.float64) - want64) / spacing).max()) if w.size else 0.0
 
 
 def check_stages(rb, illum, pc, label):
@@ -134,15 +148,37 @@ def check_stages(rb, illum, pc, label):
     assert all(np.isfinite(t) and t >= 0 for t in times)
     hl, kernel, kdft, conv = rb["highlights"], rb["kernel"], rb["kernel_dft"], rb["convolved"]
     assert hl.shape == kdft.shape == conv.shape == (dim, dim, 4) and kernel.shape == (kd, kd, 4)
-    # separate, and the zero padding
-    v, s, (x_out, y_out) = F.separate(illum, pc.threshold, scale, dim)
-    check_half(label + " separate", hl[..., :3], v, F.REL * s)
-    assert not hl[..., 3].any() and not hl[:, x_out:].any() and not hl[y_out:].any()
+    # separate, and the zero padding; above dim 512 the restatement covers the rectangle separate can light and no more
+    large = dim > 512
+    v, s, (x_out, y_out) = F.separate(illum, pc.threshold, scale, dim, crop=large)
+    check_half(label + " separate", hl[:y_out, :x_out, :3] if large else hl[..., :3], v, F.REL * s)
+    assert not hl[..., 3].any()
+    # (where the input fills the image, 512 x 512 at Half for one, there is no padding on that side)
+    assert not hl[:, x_out:].any() if x_out < dim else hl[:, x_out:].size == 0
+    assert not hl[y_out:].any() if y_out < dim else hl[y_out:].size == 0
     assert hl[:y_out, :x_out, :3].any()
     # the kernel image: the float64 value rounded once, give or take the last bits of the device's exp, atan, sin and cos
-    ok = one_ulp(kernel, F.kernel_image(kd))
-    print("%s kernel: %d of %d values off the float32 rounding of the restatement by more than one ulp" % (label, (~ok).sum(), ok.size))
+    rows = KERNEL_ROWS(kd)
+    restated = F.kernel_image(kd, rows=rows)
+    ok = one_ulp(kernel[rows], restated)
+    print("%s kernel, %d of %d rows: %d of %d values off the float32 rounding of the restatement by more than one ulp, the worst %.2f ulp from it" % (
+        label, len(rows), kd, (~ok).sum(), ok.size, worst_ulps(kernel[rows], restated)))
     assert ok.all(), label + " kernel"
+    if len(rows) < kd:
+        # sampled rows: what every texel has to satisfy whatever its row
+        assert np.isfinite(kernel).all() and (kernel >= 0).all()
+        assert (kernel[..., 0] == kernel[..., 1]).all() and (kernel[..., 2] == kernel[..., 3]).all()
+        assert kd // 2 - 1 <= np.unravel_index(np.argmax(kernel[..., 0]), (kd, kd))[0] <= kd // 2 + 1
+    if kd == dim:
+        # the edge: every texel of the wrapped image comes from the kernel image, so where one of its rows or columns
+        # is empty, that row or column of the kernel image is (float32 has no value for exp(-|p| / .00605) beyond
+        # |p| = .63, so the outer rows are zero by definition), and the streak leaves no column empty
+        idx = F.prepare_indices(kd, dim)
+        wrapped = F.prepare(kernel, dim)[..., 0]
+        assert (idx >= 0).all() and sorted(idx.tolist()) == list(range(kd))
+        assert (wrapped.any(axis=1) == kernel[..., 0].any(axis=1)[idx]).all()
+        assert (wrapped.any(axis=0) == kernel[..., 0].any(axis=0)[idx]).all() and wrapped.any(axis=0).all()
+        assert (wrapped == np.roll(kernel[..., 0], (dim // 2, dim // 2), axis=(0, 1))).all()
     # the kernel's DFT, from the read-back kernel
     prepared = F.prepare(kernel, dim)
     within_twice_the_schedule(label + " kernel DFT", kdft, F.prosper_schedule(prepared), F.dft(prepared))
@@ -156,34 +192,70 @@ def check_stages(rb, illum, pc, label):
     assert (np.abs(rb["out"][..., :3].astype(np.float64) - v) <= a).all(), label + " compose"
     assert (rb["out"][..., 3] == 1).all()
     added = rb["out"][..., :3].astype(np.float64) - illum[..., :3]
-    assert added.max() > 0  # highlights and kernel are non-negative and neither is empty: some pixel gains
+    # highlights and kernel are non-negative and neither is empty: some pixel gains.  (A kernelDim of 1 is the exception:
+    # its one texel is 4e-14, so what the restatement adds nowhere exceeds the allowance and float32 cannot hold the sum.)
+    gains = (v - illum[..., :3] > a).any()
+    assert gains or kd == 1
+    assert added.max() > 0 or not gains
 
 
-@pytest.mark.parametrize("w,h,scale,biquadratic", CASES, ids=IDS)
+@pytest.mark.parametrize("w,h,scale,biquadratic", ALL_CASES, ids=IDS)
 def test_every_stage_equals_the_restatement_over_its_read_back_inputs(gpu_ctx, w, h, scale, biquadratic):
     rb = run(gpu_ctx, w, h, scale, biquadratic)
-    check_stages(rb, rb["illum"], rb["pc"], IDS[CASES.index((w, h, scale, biquadratic))])
+    check_stages(rb, rb["illum"], rb["pc"], IDS[ALL_CASES.index((w, h, scale, biquadratic))])
 
 
-def test_one_bright_texel_convolves_to_the_wrapped_shifted_kernel(gpu_ctx):
-    w, h = 75, 55
+def one_bright_texel(ctx, w, h, x, y):
+    """Input texel (2 x - 1, 2 y - 1), one of the four of highlight (x, y), a quarter of it each, is the only lit one."""
     illum = np.zeros((h, w, 4), np.float32)
     illum[..., 3] = 0.25
-    illum[31, 41, :3] = (40.0, 20.0, 10.0)  # one of the four texels of highlight (21, 16): a quarter of it each
-    gpu_ctx.bloom_fft(S.BloomFftPC.default(threshold=0.0), w, h, illum)
-    rb = read_back(gpu_ctx)
+    illum[2 * y - 1, 2 * x - 1, :3] = (40.0, 20.0, 10.0)
+    ctx.bloom_fft(S.BloomFftPC.default(threshold=0.0), w, h, illum)
+    rb = read_back(ctx)
     dim, kd, scale = F.plan(w, h, F.HALF)
     hl = rb["highlights"].astype(np.float64)
     lit = np.argwhere(hl[..., :3].any(axis=-1))
-    assert lit.tolist() == [[16, 21]] and hl[16, 21].tolist() == [10.0, 5.0, 2.5, 0.0]
+    assert lit.tolist() == [[y, x]] and hl[y, x].tolist() == [10.0, 5.0, 2.5, 0.0]
     wrapped = F.prepare(rb["kernel"], dim)
-    shifted = np.roll(wrapped.astype(np.float64), (16, 21), axis=(0, 1))
+    shifted = np.roll(wrapped.astype(np.float64), (y, x), axis=(0, 1))
     want = np.stack([shifted[..., 0] * 10.0, shifted[..., 0] * 5.0, shifted[..., 2] * 2.5, np.zeros((dim, dim))], axis=-1) * float(scale)
     # prosper's chain in float32 from the same two images
     schedule = F.schedule_convolve(rb["highlights"].astype(np.float32), F.prosper_schedule(wrapped), scale)
-    within_twice_the_schedule("one bright texel", rb["convolved"], schedule, want)
-    # the kernel is brightest at its centre (tests/test_bloom_fft_cpu.py), which lands on the lit texel
-    assert np.unravel_index(np.argmax(rb["convolved"][..., 0]), (dim, dim)) == (16, 21)
+    within_twice_the_schedule("one bright texel, dim %d" % dim, rb["convolved"], schedule, want)
+    # the kernel is brightest at its centre (tests/test_bloom_fft_cpu.py), which lands on the lit texel; an even kernelDim
+    # has four equal central texels, kd / 2 - 1 and kd / 2 a side, which the wrap puts on the lit texel and the one before
+    peak = np.unravel_index(np.argmax(rb["convolved"][..., 0]), (dim, dim))
+    if kd % 2:
+        assert peak == (y, x)
+    else:
+        centre, others = rb["kernel"][kd // 2 - 1:kd // 2 + 1, kd // 2 - 1:kd // 2 + 1, 0], rb["kernel"][..., 0].copy()
+        others[kd // 2 - 1:kd // 2 + 1, kd // 2 - 1:kd // 2 + 1] = 0
+        assert centre.min() > 2 * others.max()
+        assert peak[0] in (y - 1, y) and peak[1] in (x - 1, x)
+
+
+def test_one_bright_texel_convolves_to_the_wrapped_shifted_kernel(gpu_ctx):
+    one_bright_texel(gpu_ctx, 75, 55, 21, 16)
+
+
+def test_one_bright_texel_off_the_column_tiles_of_dim_1024(gpu_ctx):
+    """The middle kernel's tile is four columns wide at 1024: column 303 is the last of its tile, row 117 no multiple of a
+    power of two."""
+    assert F.plan(1030, 300, F.HALF)[0] == 1024 and 303 % 4 == 3
+    one_bright_texel(gpu_ctx, 1030, 300, 303, 117)
+
+
+def test_a_small_case_after_the_largest_gives_the_bytes_it_gave_before(gpu_ctx):
+    """The context's images only grow and the twiddle tables are kept per dim: 4100 x 64 leaves the largest images it
+    will own and the table of 4096 behind, and 75 x 55 after it must read neither with their strides or sizes."""
+    first = run(gpu_ctx, 75, 55, F.HALF, 1)
+    w, h = 4100, 64
+    gpu_ctx.bloom_fft(S.BloomFftPC.default(B.THRESHOLD, F.HALF, 1), w, h, B.design(w, h, SEED))
+    info = gpu_ctx.bloom_fft_info()
+    assert (info.dim, info.kernelDim, info.kernelRemade) == (4096, 32, 1)
+    gpu_ctx.bloom_fft(first["pc"], 75, 55, first["illum"])
+    assert gpu_ctx.bloom_fft_info().kernelRemade == 1  # dim changed
+    assert same_bytes(first, read_back(gpu_ctx))
 
 
 @pytest.mark.parametrize("scale", [F.HALF, F.QUARTER])

@@ -8,13 +8,16 @@ import numpy as np
 import pytest
 
 import bloom_fft_reference as F
+import bloom_reference as B
 from prosper_amd import capi, structs as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("prosper_pt_bloom_fft", "prosper_pt_bloom_fft_plan", "prosper_pt_bloom_fft_transform", "prosper_pt_bloom_fft_release_kernel",
                "prosper_pt_read_bloom_fft_stage", "prosper_pt_get_bloom_fft_info", "prosper_host_bloom_set_technique",
                "prosper_host_bloom_release_preserved", "prosper_host_bloom_fft_push_constants")
-# (w, h, resolution scale) of the whole pass on the GPU; every dim is 256 or 512.  75 x 55 is the odd one (kernelDim 27,
+SEED = 11
+# (w, h, resolution scale) of the whole pass on the GPU with a whole kernel image evaluated here; every dim is 256 or 512
+# (LARGE_CASES reach the others).  75 x 55 is the odd one (kernelDim 27,
 # compose fractions .25 / .75): at 75 x 51 the kernelDim is 25, and with 200 sub-samples a side one of them has
 # |p.y| = 1 / 200, the streak's threshold itself (test_no_sub_sample_of_the_kernel_image_lies_on_a_branch).
 HALF_EXTENTS = ((64, 48), (75, 55), (48, 100), (512, 288), (520, 8))
@@ -22,7 +25,32 @@ QUARTER_EXTENTS = ((100, 70), (1030, 40))
 EXTENTS = [(w, h, F.HALF) for w, h in HALF_EXTENTS] + [(w, h, F.QUARTER) for w, h in QUARTER_EXTENTS]
 # (w, h, resolution scale, biquadratic): biquadratic on all, bilinear on two
 CASES = [(w, h, s, 1) for w, h, s in EXTENTS] + [(75, 55, F.HALF, 0), (100, 70, F.QUARTER, 0)]
-PLAN_EXTENTS = [(1920, 1080), (64, 48), (75, 51), (48, 100), (512, 288), (520, 8), (100, 70), (1030, 40), (8192, 2)]
+# The smallest inputs that reach the instantiations of dim 1024, 2048 and 4096, each dim landscape and portrait: separate
+# lights only the rows below H / s, so the rows of a landscape image's highlights are mostly exact zeros and a middle
+# kernel that took one zero row for another would pass; a portrait one lights them all, and its kernelDim = H / s is large.
+LARGE_CASES = [(1030, 300, F.HALF, 1), (300, 1030, F.HALF, 1), (2100, 64, F.HALF, 0), (64, 2100, F.HALF, 1), (4100, 64, F.HALF, 1),
+               (64, 4100, F.HALF, 0)]
+# kernelDim == dim (the wrapped kernel image leaves no zero texel between its halves), twice, and kernelDim 1
+EDGE_CASES = [(512, 512, F.HALF, 1), (512, 1024, F.QUARTER, 1), (300, 2, F.HALF, 1)]
+NEW_CASES = EDGE_CASES + LARGE_CASES
+PLAN_EXTENTS = [(1920, 1080), (64, 48), (75, 51), (48, 100), (512, 288), (520, 8), (100, 70), (1030, 40), (8192, 2)] + sorted(
+    {(w, h) for w, h, _, _ in NEW_CASES})
+FULL_KERNEL_ROWS = 600
+
+
+def KERNEL_ROWS(kd):
+    """The sorted texel rows on which a kernel image of kernelDim kd is checked: every row up to kernelDim 600, and above
+    it the first two, the last two, the three about kd // 2 and 17 seeded ones, 24 in all.  The sampling caps the time of
+    the restatement (64 kd^2 evaluations in float64) and is no tolerance: the kernel computes a texel per wave and rows
+    do not depend on each other, a wrong texel index shifts every row, and the rows that differ in kind, those of the
+    streak |p.y| < .005, include the three about kd // 2."""
+    if kd <= FULL_KERNEL_ROWS:
+        return list(range(kd))
+    fixed = [0, 1, kd // 2 - 1, kd // 2, kd // 2 + 1, kd - 2, kd - 1]
+    rest = np.setdiff1d(np.arange(kd), fixed)
+    rows = sorted(fixed + np.random.default_rng(SEED + kd).choice(rest, 17, replace=False).tolist())
+    assert len(rows) == 24
+    return rows
 
 
 def test_new_symbols_are_exported_and_the_abi_version_is_unchanged():
@@ -69,6 +97,20 @@ def test_the_plan_equals_the_restatement(w, h, scale):
     assert (plan.dim, plan.kernelDim) == want[:2]
     assert np.float32(plan.convolutionScale).view(np.uint32) == want[2].view(np.uint32)
     assert plan.dim & (plan.dim - 1) == 0 and 256 <= plan.dim <= 4096 and plan.kernelDim <= plan.dim
+
+
+def test_every_dim_has_a_whole_pass_case_and_the_large_ones_both_orientations():
+    planned = {}
+    for w, h, scale, _ in CASES + LARGE_CASES + EDGE_CASES:
+        planned.setdefault(F.plan(w, h, scale)[0], []).append((w, h))
+    assert set(planned) == {256, 512, 1024, 2048, 4096}
+    for dim in (1024, 2048, 4096):
+        assert any(w > h for w, h in planned[dim]) and any(h > w for w, h in planned[dim]), dim
+    assert not set(CASES) & set(NEW_CASES) and len(set(NEW_CASES)) == len(NEW_CASES)
+    # the edges: kernelDim == dim at both scales, and kernelDim 1 with a convolution scale of 2
+    assert [F.plan(w, h, s)[:2] for w, h, s, _ in EDGE_CASES] == [(256, 256), (256, 256), (256, 1)]
+    assert float(F.plan(300, 2, F.HALF)[2]) == 2.0
+    assert [F.plan(w, h, s)[:2] for w, h, s, _ in LARGE_CASES] == [(1024, 150), (1024, 515), (2048, 32), (2048, 1050), (4096, 32), (4096, 2050)]
 
 
 def test_known_plans_and_the_largest_extent():
@@ -149,7 +191,7 @@ def test_prepare_at_an_odd_and_an_even_kernel_extent():
     assert not p[..., 1].any() and not p[..., 3].any() and np.count_nonzero(p[..., 0]) == 25
 
 
-@pytest.mark.parametrize("dim", [256, 512])
+@pytest.mark.parametrize("dim", [256, 512, 1024, 2048])
 def test_the_schedule_agrees_with_the_dft(dim):
     """prosper's own passes in float32 against np.fft in float64.  A transform of log2(dim^2) radix-2 levels rounds a
     value at most about four times per level (twiddle, product, sum), each within eps of the largest magnitude; a wrong
@@ -187,14 +229,63 @@ def test_an_impulse_convolves_to_the_wrapped_kernel_shifted_there():
     assert wrapped[0, 0, 0] == wrapped[..., 0].max() > 0 and (wrapped[..., 0] >= 0).all()
 
 
-@pytest.mark.parametrize("kd", sorted({F.plan(w, h, s)[1] for w, h, s in EXTENTS}))
+@pytest.mark.parametrize("kd", sorted({F.plan(w, h, s)[1] for w, h, s in EXTENTS} | {F.plan(w, h, s)[1] for w, h, s, _ in NEW_CASES}))
 def test_no_sub_sample_of_the_kernel_image_lies_on_a_branch(kd):
     """A condition on the inputs of the GPU test: float64 on the device and here may differ in the last bits, which must
-    not decide a branch of filterValue (dStar < 0, |p.y| < .005)."""
+    not decide a branch of filterValue (dStar < 0, |p.y| < .005).  Over KERNEL_ROWS(kd), the rows the GPU test compares."""
     assert F.kernel_margins(25)[1] < 1e-15  # what the condition is there to keep out
-    star, streak = F.kernel_margins(kd)
-    print("kernelDim %d: |dStar| >= %.3e, ||p.y| - .005| >= %.3e" % (kd, star, streak))
+    rows = KERNEL_ROWS(kd)
+    star, streak = F.kernel_margins(kd, rows=rows)
+    print("kernelDim %d, %d rows: |dStar| >= %.3e, ||p.y| - .005| >= %.3e" % (kd, len(rows), star, streak))
     assert star > 1e-9 and streak > 1e-9
-    k = F.kernel_image(kd)
-    assert k.shape == (kd, kd, 4) and np.isfinite(k).all() and (k >= 0).all()
+    k = F.kernel_image(kd, rows=rows)
+    assert k.shape == (len(rows), kd, 4) and np.isfinite(k).all() and (k >= 0).all()
     assert (k[..., 0] == k[..., 1]).all() and (k[..., 2] == k[..., 3]).all()
+
+
+def test_the_rows_of_a_kernel_image_are_sampled_only_above_600():
+    assert KERNEL_ROWS(1) == [0] and KERNEL_ROWS(600) == list(range(600))
+    for kd in (601, 1050, 2050):
+        rows = KERNEL_ROWS(kd)
+        assert len(rows) == 24 and rows == sorted(set(rows)) and rows == KERNEL_ROWS(kd)
+        assert {0, 1, kd // 2 - 1, kd // 2, kd // 2 + 1, kd - 2, kd - 1} <= set(rows) and 0 <= rows[0] and rows[-1] < kd
+    # a kernelDim of 25 modulo 50 puts a row of sub-samples on |p.y| = .005 itself: why the portrait extents are 2100 and 4100
+    assert F.kernel_margins(1025, rows=[515])[1] < 1e-15
+
+
+def test_a_kernel_image_in_bands_equals_the_whole_one():
+    for kd in (27, 150):
+        whole = F.kernel_image(kd)
+        assert F.kernel_image(kd, rows=list(range(kd))).tobytes() == whole.tobytes()
+        assert F.kernel_margins(kd, rows=list(range(kd))) == F.kernel_margins(kd)
+    some = [0, 74, 75, 149]
+    assert F.kernel_image(150, rows=some).tobytes() == whole[some].tobytes()
+    assert F.kernel_image(150, rows=[]).shape == (0, 150, 4)
+
+
+@pytest.mark.parametrize("w,h,scale,biquadratic", LARGE_CASES)
+def test_the_design_lights_the_rows_of_a_portrait_and_the_columns_of_a_landscape_extent(w, h, scale, biquadratic):
+    """From the restatement alone, over the rectangle separate can light (the rest of a 4096^2 image is never formed): a
+    portrait case lights every row below y_out, so the middle kernel's column tiles hold no empty row there; a landscape
+    one lights at least 400 columns."""
+    dim = F.plan(w, h, scale)[0]
+    v, _, (x_out, y_out) = F.separate(B.design(w, h, SEED), B.THRESHOLD, scale, dim, crop=True)
+    assert v.shape == (y_out, x_out, 3) and x_out <= dim and y_out <= dim
+    lit = v.any(axis=-1)
+    rows, columns = int(lit.any(axis=1).sum()), int(lit.any(axis=0).sum())
+    print("%d x %d: %d of %d rows and %d of %d columns lit" % (w, h, rows, y_out, columns, x_out))
+    if h > w:
+        assert rows == y_out
+    else:
+        assert columns >= 400
+
+
+def test_separate_over_the_rectangle_equals_the_whole_image_there():
+    for w, h, scale in ((75, 55, F.HALF), (100, 70, F.QUARTER), (512, 512, F.HALF)):
+        illum = B.design(w, h, SEED)
+        v, s, outside = F.separate(illum, B.THRESHOLD, scale, 256)
+        cv, cs, c_outside = F.separate(illum, B.THRESHOLD, scale, 256, crop=True)
+        assert outside == c_outside == F.outside_from(w, h, scale)
+        ny, nx = min(outside[1], 256), min(outside[0], 256)
+        assert cv.shape == (ny, nx, 3) and (cv == v[:ny, :nx]).all() and (cs == s[:ny, :nx]).all()
+        assert not v[ny:].any() and not v[:, nx:].any()
