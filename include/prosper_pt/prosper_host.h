@@ -112,6 +112,9 @@ int prosper_host_rt_direct_illumination_record(
 typedef struct prosper_host_gbuffer_tracer prosper_host_gbuffer_tracer;
 int prosper_host_gbuffer_tracer_create(prosper_pt_ctx *ctx, prosper_host_gbuffer_tracer **out);
 void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *pass);
+/* GBufferTracer::setOpaqueOnly: both records leave BLEND surfaces out (PROSPER_PT_GBUFFER_OPAQUE_ONLY), for
+ * prosper_host_forward_renderer_record_transparent to draw.  Off by default. */
+int prosper_host_gbuffer_tracer_set_opaque_only(prosper_host_gbuffer_tracer *pass, int opaqueOnly);
 int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
     uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer);
@@ -164,6 +167,20 @@ void prosper_host_skybox_renderer_destroy(prosper_host_skybox_renderer *pass);
 int prosper_host_skybox_renderer_record(
     prosper_host_skybox_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const float *nonLinearDepth, uint32_t onDevice, void *stream);
+
+/* render::ForwardRenderer (host/forward_renderer.hpp; reference src/render/ForwardRenderer.hpp), its transparent pass
+ * only, on a context the scene was uploaded to (borrowed): record_transparent = Camera::updateBuffer +
+ * prosper_pt_forward_transparent over the context's HDR image.  `nonLinearDepth` NULL: the last traced G-buffer's depth;
+ * `rayFlags`, `frameIndex`: the ray the G-buffer was traced with (0, PROSPER_PT_TRANSPARENT_JITTER or
+ * PROSPER_PT_TRANSPARENT_CAMERA_JITTER).  prosper itself draws transparents with ibl = 0.  *outPushConstants (may be
+ * NULL) receives the ForwardPC it pushed. */
+typedef struct prosper_host_forward_renderer prosper_host_forward_renderer;
+int prosper_host_forward_renderer_create(prosper_pt_ctx *ctx, prosper_host_forward_renderer **out);
+void prosper_host_forward_renderer_destroy(prosper_host_forward_renderer *pass);
+int prosper_host_forward_renderer_record_transparent(
+    prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    const float *nonLinearDepth, uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType,
+    void *stream, prosper_pt_forward_pc *outPushConstants);
 
 /* render::dof::DepthOfField (host/depth_of_field.hpp; reference src/render/dof/DepthOfField.hpp) on a context
  * (borrowed): record = Camera::updateBuffer + prosper_pt_depth_of_field with the push constants computed from the

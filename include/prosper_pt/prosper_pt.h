@@ -572,12 +572,17 @@ int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, s
  * that frame's primary hit.  Without, through the pixel centre (px + 0.5, py + 0.5), as a rasteriser samples.
  * Unlike the raster G-buffer: no velocity target and no TAA jitter (currentJitter) in this entry -
  * prosper_pt_trace_gbuffer_velocity has both -, no meshlet IDs, float storage, BLEND
- * surfaces follow the path tracer's stochastic transparency, and PrimitiveID is the geometry's triangle index.
+ * surfaces follow the path tracer's stochastic transparency unless PROSPER_PT_GBUFFER_OPAQUE_ONLY leaves them out, and PrimitiveID is the geometry's triangle index.
  * `targets`: three caller-owned device buffers (16-byte aligned), or NULL for context-owned ones (grown as needed,
  * separate from the ReSTIR scratch).  Pending transform, light and material updates take effect first. */
 enum
 {
     PROSPER_PT_GBUFFER_JITTER = 1u << 0,
+    /* Both G-buffer entries: a candidate whose material is BLEND is always rejected by the any-hit, as prosper keeps
+     * BLEND geometry out of its G-buffer (draw_list_generator.comp:43-54); MASK keeps its cutoff, opaque geometry and
+     * everything else about the targets is unchanged.  prosper_pt_forward_transparent draws the BLEND surfaces afterwards.
+     * (Bit 2: bit 1 stays an unknown flag of both entries.) */
+    PROSPER_PT_GBUFFER_OPAQUE_ONLY = 1u << 2,
 };
 typedef struct prosper_pt_gbuffer_targets
 {
@@ -593,7 +598,7 @@ int prosper_pt_trace_gbuffer(
  * by camera->cameraToClip * worldToCamera is the pixel centre: uv = (px + 0.5, py + 0.5) / extent - currentJitter * 0.5
  * (the jittered projection moves NDC by + currentJitter on both axes).  The rng draw and the any-hit seed are
  * prosper_pt_trace_gbuffer's; with currentJitter = (0, 0) the three targets are byte-identical to that entry's without
- * PROSPER_PT_GBUFFER_JITTER.  `flags` must be 0.
+ * PROSPER_PT_GBUFFER_JITTER.  `flags` is 0 or PROSPER_PT_GBUFFER_OPAQUE_ONLY.
  *   velocity  float2: (posNDC - currentJitter) - (prevPosNDC - previousJitter), y negated, each component clamped as
  *             fminf(fmaxf(v, -1), 1).  posNDC = xy / w of cameraToClip * worldToCamera * (positionWS, 1), prevPosNDC the
  *             same through previousCameraToClip * previousWorldToCamera of prevPositionWS: the interpolated model-space
@@ -604,7 +609,7 @@ int prosper_pt_trace_gbuffer(
  *             and equal jitters give exactly (0, 0).
  * Unlike prosper: float2 storage instead of R16G16_SNORM, and the sky's velocity is clamped too (the SNORM target clamps
  * it on store).  The previous transforms are copied on `stream` into a grow-only device buffer of the context.  Refused:
- * non-zero flags, a partly given target set, misaligned targets, previousTransformCount that differs from the scene's
+ * flags other than PROSPER_PT_GBUFFER_OPAQUE_ONLY, a partly given target set, misaligned targets, previousTransformCount that differs from the scene's
  * modelInstanceCount (or is given without previousTransforms). */
 typedef struct prosper_pt_velocity_gbuffer_desc
 {
@@ -682,6 +687,84 @@ int prosper_pt_deferred_shading(
     prosper_pt_ctx *ctx, const prosper_pt_deferred_shading_pc *pc, uint32_t flags, uint32_t frameIndex,
     const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const prosper_pt_restir_inputs *gbuffer,
     void *stream);
+
+/* ---- forward transparent pass (src/render/ForwardRenderer.cpp recordTransparent, res/shader/forward.frag) ----
+ * What prosper draws between the skybox and bloom (Renderer.cpp:493-500): the BLEND surfaces, lit forward
+ * over the light clusters and alpha-blended over the shaded, sky-filled image, in place over the context's HDR image.
+ * Use it over a G-buffer traced with PROSPER_PT_GBUFFER_OPAQUE_ONLY.  Additive: the ABI version stays 4.
+ *
+ * One lane per pixel follows the G-buffer's own ray of that pixel: through the centre (flags 0), through the path
+ * tracer's sample (px, py) + rnd2d01() of rng (px, py, frameIndex) (PROSPER_PT_TRANSPARENT_JITTER), or through the centre
+ * minus currentJitter * 0.5 as prosper_pt_trace_gbuffer_velocity traces (PROSPER_PT_TRANSPARENT_CAMERA_JITTER).  A LAYER
+ * of the pixel is an intersection of that ray with a triangle
+ *   - whose material's alphaMode is BLEND (opaque and MASK triangles are ignored: the depth is the occluder),
+ *   - met from the front of the world-space triangle, cross(p1 - p0, p2 - p0) . d < 0 (back faces are culled),
+ *   - whose sampleMaterial alpha is not 0,
+ *   - whose non-linear depth - positionWS through cameraToClip * worldToCamera, as the traced G-buffer computes it - is
+ *     strictly greater than the stored one (reverse-Z eGreater, no depth write): 0, the sky, passes everything, a layer
+ *     coplanar with the opaque surface fails.
+ * A layer's colour is forward.frag's: the surface of the hit with invViewRayWS = normalize(eye - positionWS), the sun,
+ * the point and spot lights of clusterIndex(pixel, zCam) (zCam = (worldToCamera * position).z; slice rules as deferred
+ * shading), unshadowed, then with pc->ibl = 1 evalIBL; its alpha a is the material's.  Other draw types than Default
+ * (and MeshletID, which counts as Default) give (debug colour, 1).  The layers are composited sorted per pixel, nearest
+ * last, by prosper's blend state: rgb = src.rgb * a + dst.rgb * (1 - a), alpha = a * (1 - a) of the nearest layer; equal
+ * distances order by (drawInstance, primitive), the lower one nearer.  It is evaluated front to back (C += T a src,
+ * T *= 1 - a, at the end C + T dst), and ends at T == 0 exactly: layers behind are neither shaded nor counted.  A pixel
+ * without a layer keeps its four floats bit for bit.  (prosper draws in the order an atomic counter hands out; per-pixel
+ * sorted is the defined order here, the same wherever one layer covers a pixel.)
+ *
+ * `nonLinearDepth`, `onDevice`: as prosper_pt_skybox_fill (NULL: the last traced G-buffer's depth).  The HDR image must
+ * have this extent.  The lights are clustered first on `stream`, unless the context's last clustering was made with the
+ * same camera terms and extent and no light update took effect since.  Pending scene updates are flushed once: every
+ * kernel of the call reads one scene and light version.  Refused: both jitter flags, unknown flags, drawType out of
+ * range, ibl not 0 or 1, ibl = 1 before prosper_pt_generate_ibl (PROSPER_PT_ERR_UNSUPPORTED). */
+typedef struct prosper_pt_forward_pc /* ForwardPC (shared/shader_structs/push_constants/forward.h) */
+{
+    uint32_t drawType;
+    uint32_t ibl;
+    uint32_t previousTransformValid; /* not read: the pass writes no velocity */
+} prosper_pt_forward_pc;
+enum
+{
+    PROSPER_PT_TRANSPARENT_JITTER = 1u << 0,
+    PROSPER_PT_TRANSPARENT_CAMERA_JITTER = 1u << 1,
+};
+int prosper_pt_forward_transparent(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, uint32_t flags, uint32_t frameIndex,
+    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const float *nonLinearDepth, uint32_t onDevice,
+    void *stream);
+typedef struct prosper_pt_transparent_info
+{
+    uint32_t coveredPixels; /* pixels with at least one layer */
+    uint32_t maxLayers;     /* the deepest pixel's layer count */
+    uint64_t totalLayers;
+    float ms;               /* device time of the last call, its clustering included */
+    uint32_t reclustered;   /* 1: the last call clustered the lights itself */
+} prosper_pt_transparent_info;
+/* Of the last prosper_pt_forward_transparent (waits for it); NO_SCENE before the first. */
+int prosper_pt_get_transparent_info(prosper_pt_ctx *ctx, prosper_pt_transparent_info *out);
+/* Debug mode, for tests: with layersPerPixel > 0 every later prosper_pt_forward_transparent also writes each pixel's
+ * layer count and its first layersPerPixel layers, front to back, into a context-owned grow-only buffer (the image is
+ * the same bit for bit).  0 (the default) turns it off. */
+typedef struct prosper_pt_transparent_layer
+{
+    uint32_t drawInstance, primitive;
+    float positionWS[3];
+    float nonLinearDepth;
+    float albedo[3];
+    float roughness;
+    float normal[3]; /* the shading normal */
+    float metallic;
+    float alpha;
+    uint32_t reserved;
+} prosper_pt_transparent_layer;
+int prosper_pt_set_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel);
+/* Synchronises `stream` and copies what the last call in debug mode wrote: host_counts `pixels` uint32, host_layers
+ * pixels * layersPerPixel records (pixel-major; records past a pixel's count are unspecified); either may be NULL.
+ * `pixels` and `layersPerPixel` must be that call's.  NO_SCENE if the last call did not run in debug mode. */
+int prosper_pt_read_transparent_layers(
+    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels,
+    uint32_t layersPerPixel, void *stream);
 
 /* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
  * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.

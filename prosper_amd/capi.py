@@ -97,6 +97,10 @@ def lib():
     L.prosper_pt_read_light_clusters.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.prosper_pt_deferred_shading.argtypes = [
         vp, C.POINTER(S.DeferredShadingPC), u32, u32, C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.RestirInputs), vp]
+    L.prosper_pt_forward_transparent.argtypes = [vp, C.POINTER(S.ForwardPC), u32, u32, C.POINTER(S.CameraUniforms), u32, u32, vp, u32, vp]
+    L.prosper_pt_get_transparent_info.argtypes = [vp, C.POINTER(S.TransparentInfo)]
+    L.prosper_pt_set_transparent_debug_layers.argtypes = [vp, u32]
+    L.prosper_pt_read_transparent_layers.argtypes = [vp, vp, vp, C.c_size_t, u32, vp]
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
     L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
     L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
@@ -196,6 +200,7 @@ def lib():
     L.prosper_host_gbuffer_tracer_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_gbuffer_tracer_destroy.argtypes = [vp]
     L.prosper_host_gbuffer_tracer_destroy.restype = None
+    L.prosper_host_gbuffer_tracer_set_opaque_only.argtypes = [vp, C.c_int]
     L.prosper_host_gbuffer_tracer_record.argtypes = [vp, vp, u32, u32, u32, u32, C.c_int, vp, C.POINTER(S.RestirInputs)]
     L.prosper_host_gbuffer_tracer_record_velocity.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, C.POINTER(S.RestirInputs),
                                                               C.POINTER(vp)]
@@ -217,6 +222,11 @@ def lib():
     L.prosper_host_skybox_renderer_destroy.argtypes = [vp]
     L.prosper_host_skybox_renderer_destroy.restype = None
     L.prosper_host_skybox_renderer_record.argtypes = [vp, vp, u32, u32, vp, u32, vp]
+    L.prosper_host_forward_renderer_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_forward_renderer_destroy.argtypes = [vp]
+    L.prosper_host_forward_renderer_destroy.restype = None
+    L.prosper_host_forward_renderer_record_transparent.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, C.c_int, u32, vp,
+                                                                   C.POINTER(S.ForwardPC)]
     L.prosper_host_depth_of_field_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_depth_of_field_destroy.argtypes = [vp]
     L.prosper_host_depth_of_field_destroy.restype = None
@@ -599,13 +609,15 @@ class Context:
         _check(lib().prosper_pt_read_restir_reservoirs(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
 
-    def trace_gbuffer(self, camera, width, height, draw_type=0, frame_index=0, jitter=True, targets=None, stream=None):
+    def trace_gbuffer(self, camera, width, height, draw_type=0, frame_index=0, jitter=True, targets=None, stream=None,
+                      opaque_only=False):
         """prosper_pt_trace_gbuffer: the ray-traced G-buffer of the uploaded scene.  With `targets` None it goes to the
         context's own buffers and is read back: returns (albedoRoughness [h, w, 4], normalMetallic [h, w, 4],
-        nonLinearDepth [h, w]) float32.  `targets`: three device pointers (ar, nm, depth), written; returns None."""
+        nonLinearDepth [h, w]) float32.  `targets`: three device pointers (ar, nm, depth), written; returns None.
+        `opaque_only`: PROSPER_PT_GBUFFER_OPAQUE_ONLY, BLEND surfaces left to forward_transparent."""
         self._sync_debug()
         t = None if targets is None else S.GBufferTargets(*targets)
-        flags = S.GBUFFER_JITTER if jitter else 0
+        flags = (S.GBUFFER_JITTER if jitter else 0) | (S.GBUFFER_OPAQUE_ONLY if opaque_only else 0)
         _check(lib().prosper_pt_trace_gbuffer(self._h, int(draw_type), frame_index, flags, C.byref(camera), width, height,
                                               None if t is None else C.byref(t), C.c_void_p(stream)))
         if targets is not None:
@@ -613,7 +625,7 @@ class Context:
         return self.read_gbuffer(stream)
 
     def trace_gbuffer_velocity(self, camera, width, height, draw_type=0, frame_index=0, previous_transforms=None, targets=None,
-                               velocity_ptr=None, stream=None):
+                               velocity_ptr=None, stream=None, opaque_only=False):
         """prosper_pt_trace_gbuffer_velocity: the traced G-buffer through camera.cameraToClip's (jittered) pixel centres,
         with the velocity target.  `previous_transforms`: a ctypes array of S.ModelInstanceTransforms, one per model
         instance (None: the instances did not move).  `targets` (ar, nm, depth) and `velocity_ptr`: device pointers;
@@ -627,7 +639,8 @@ class Context:
         if previous_transforms is not None:
             desc.previousTransforms = C.cast(previous_transforms, C.c_void_p)
             desc.previousTransformCount = len(previous_transforms)
-        _check(lib().prosper_pt_trace_gbuffer_velocity(self._h, int(draw_type), frame_index, 0, C.byref(camera), width, height,
+        flags = S.GBUFFER_OPAQUE_ONLY if opaque_only else 0
+        _check(lib().prosper_pt_trace_gbuffer_velocity(self._h, int(draw_type), frame_index, flags, C.byref(camera), width, height,
                                                        C.byref(desc), C.c_void_p(stream)))
         gbuffer = (None, None, None) if targets is not None else self.read_gbuffer(stream)
         return gbuffer + (None if velocity_ptr is not None else self.read_velocity(stream),)
@@ -720,6 +733,43 @@ class Context:
         pc = S.DeferredShadingPC(int(draw_type), int(ibl))
         _check(lib().prosper_pt_deferred_shading(self._h, C.byref(pc), flags, frame_index, C.byref(camera), width,
                                                  height, None, C.c_void_p(stream)))
+
+    def forward_transparent(self, camera, width, height, draw_type=0, ibl=0, flags=0, frame_index=0, depth=None,
+                            depth_ptr=None, stream=None):
+        """ForwardRenderer::recordTransparent (prosper_pt_forward_transparent): the BLEND layers of every pixel, lit over
+        the light clusters and blended in place over the HDR image.  `flags`: 0 (pixel centre), S.TRANSPARENT_JITTER or
+        S.TRANSPARENT_CAMERA_JITTER - the ray the G-buffer was traced with.  `depth`: a host array [h, w]; `depth_ptr`:
+        a device pointer; neither: the last traced G-buffer's depth."""
+        self._sync_debug()
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert dp is None or dp.shape == (height, width)
+        ptr = depth_ptr if dp is None else dp.ctypes.data
+        pc = S.ForwardPC(int(draw_type), int(ibl), 0)
+        _check(lib().prosper_pt_forward_transparent(self._h, C.byref(pc), flags, frame_index, C.byref(camera), width, height,
+                                                    C.c_void_p(ptr), 1 if dp is None else 0, C.c_void_p(stream)))
+        self._transparent_extent = (width, height)
+
+    def transparent_info(self):
+        """S.TransparentInfo of the last forward_transparent (waits for it)."""
+        info = S.TransparentInfo()
+        _check(lib().prosper_pt_get_transparent_info(self._h, C.byref(info)))
+        return info
+
+    def set_transparent_debug_layers(self, layers_per_pixel):
+        """Debug mode of forward_transparent: later calls record each pixel's first `layers_per_pixel` layers (0: off)."""
+        _check(lib().prosper_pt_set_transparent_debug_layers(self._h, layers_per_pixel))
+        self._transparent_layers = layers_per_pixel
+
+    def read_transparent_layers(self, stream=None):
+        """What the last forward_transparent in debug mode recorded: (counts uint32 [h, w], layers [h, w, N] of the
+        structured dtype of S.TransparentLayer, front to back; entries past a pixel's count are unspecified)."""
+        w, h = self._transparent_extent
+        n = self._transparent_layers
+        counts = np.empty((h, w), np.uint32)
+        layers = np.empty((h, w, n), np.dtype(S.TransparentLayer))
+        _check(lib().prosper_pt_read_transparent_layers(self._h, counts.ctypes.data, layers.ctypes.data, w * h, n,
+                                                        C.c_void_p(stream)))
+        return counts, layers
 
     def generate_ibl(self, stream=None):
         """ImageBasedLighting::recordGeneration (prosper_pt_generate_ibl): the irradiance and radiance cubes and the BRDF

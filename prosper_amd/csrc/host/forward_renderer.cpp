@@ -1,0 +1,109 @@
+// host/forward_renderer.cpp — see forward_renderer.hpp.
+#include "forward_renderer.hpp"
+
+#include <new>
+#include <stdexcept>
+#include <string>
+
+#include "../../../include/prosper_pt/prosper_host.h"
+#include "host_common.hpp"
+
+namespace render
+{
+
+void ForwardRenderer::init(prosper_pt_ctx *ctx)
+{
+    PROSPER_ASSERT(!m_initialized);
+    PROSPER_ASSERT(ctx != nullptr);
+    m_ctx = ctx;
+    m_initialized = true;
+}
+
+void ForwardRenderer::recordTransparent(
+    const scene::Camera &cam, const TransparentInOut &t, const LightClusteringOutput *lightClusters, scene::DrawType drawType,
+    bool applyIbl, void *stream)
+{
+    PROSPER_ASSERT(m_initialized);
+    if (lightClusters && (lightClusters->width != t.width || lightClusters->height != t.height))
+        throw std::runtime_error("ForwardRenderer::recordTransparent: the light clusters were built for another extent");
+
+    // ForwardRenderer.cpp:658-662
+    prosper_pt_forward_pc pc = {};
+    pc.drawType = static_cast<uint32_t>(drawType);
+    pc.ibl = applyIbl ? 1u : 0u;
+    m_lastPC = pc;
+
+    if (prosper_pt_forward_transparent(
+            m_ctx, &pc, t.rayFlags, t.frameIndex, &cam.uniforms(), t.width, t.height, t.depth, t.onDevice ? 1u : 0u, stream) !=
+        PROSPER_PT_OK)
+        throw std::runtime_error(std::string("ForwardRenderer::recordTransparent: ") + prosper_pt_last_error());
+}
+
+} // namespace render
+
+// ---- plain-C shims (include/prosper_pt/prosper_host.h) ----
+
+struct prosper_host_forward_renderer
+{
+    render::ForwardRenderer pass;
+};
+
+extern "C" {
+
+int prosper_host_forward_renderer_create(prosper_pt_ctx *ctx, prosper_host_forward_renderer **out)
+{
+    if (!out) return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!ctx)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_create: null context");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    prosper_host_forward_renderer *r = new (std::nothrow) prosper_host_forward_renderer();
+    if (!r) return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    r->pass.init(ctx);
+    *out = r;
+    return PROSPER_PT_OK;
+}
+
+void prosper_host_forward_renderer_destroy(prosper_host_forward_renderer *r) { delete r; }
+
+int prosper_host_forward_renderer_record_transparent(
+    prosper_host_forward_renderer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, const float *nonLinearDepth,
+    uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType, void *stream,
+    prosper_pt_forward_pc *outPushConstants)
+{
+    if (!r || !camera)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_record_transparent: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    if (drawType >= (uint32_t)scene::DrawType::Count)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_record_transparent: drawType out of range");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    try
+    {
+        scene::Camera &cam = *prosper_host_camera_object(camera);
+        cam.updateResolution(width, height);
+        cam.updateBuffer(); // App::drawFrame does this before Renderer::render (App.cpp:556)
+        render::ForwardRenderer::TransparentInOut t;
+        t.depth = nonLinearDepth;
+        t.onDevice = onDevice != 0u;
+        t.width = width;
+        t.height = height;
+        t.rayFlags = rayFlags;
+        t.frameIndex = frameIndex;
+        r->pass.recordTransparent(cam, t, nullptr, static_cast<scene::DrawType>(drawType), applyIbl != 0, stream);
+        if (outPushConstants) *outPushConstants = r->pass.lastPushConstants();
+    }
+    catch (const std::exception &e)
+    {
+        prosper_host_set_error(e.what());
+        return PROSPER_PT_ERR_HIP;
+    }
+    return PROSPER_PT_OK;
+}
+
+} // extern "C"

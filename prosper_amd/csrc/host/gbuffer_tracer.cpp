@@ -26,7 +26,7 @@ rtdi::GBuffer GBufferTracer::record(
     void *stream)
 {
     PROSPER_ASSERT(m_initialized);
-    const uint32_t flags = jitter ? PROSPER_PT_GBUFFER_JITTER : 0u;
+    const uint32_t flags = (jitter ? PROSPER_PT_GBUFFER_JITTER : 0u) | (m_opaqueOnly ? PROSPER_PT_GBUFFER_OPAQUE_ONLY : 0u);
     if (prosper_pt_trace_gbuffer(
             m_ctx, static_cast<uint32_t>(drawType), frameIndex, flags, &cam.uniforms(), width, height, nullptr, stream) !=
         PROSPER_PT_OK)
@@ -56,7 +56,8 @@ GBufferTracer::VelocityGBuffer GBufferTracer::recordVelocity(
         desc.previousTransformCount = transformCount;
     }
     if (prosper_pt_trace_gbuffer_velocity(
-            m_ctx, static_cast<uint32_t>(drawType), frameIndex, 0u, &cam.uniforms(), width, height, &desc, stream) != PROSPER_PT_OK)
+            m_ctx, static_cast<uint32_t>(drawType), frameIndex, m_opaqueOnly ? PROSPER_PT_GBUFFER_OPAQUE_ONLY : 0u, &cam.uniforms(),
+            width, height, &desc, stream) != PROSPER_PT_OK)
         throw std::runtime_error(std::string("GBufferTracer::recordVelocity: ") + prosper_pt_last_error());
     if (transforms)
         m_previousTransforms.assign(transforms, transforms + transformCount);
@@ -106,6 +107,17 @@ int prosper_host_gbuffer_tracer_create(prosper_pt_ctx *ctx, prosper_host_gbuffer
 }
 
 void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *r) { delete r; }
+
+int prosper_host_gbuffer_tracer_set_opaque_only(prosper_host_gbuffer_tracer *r, int opaqueOnly)
+{
+    if (!r)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_set_opaque_only: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    r->pass.setOpaqueOnly(opaqueOnly != 0);
+    return PROSPER_PT_OK;
+}
 
 int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,

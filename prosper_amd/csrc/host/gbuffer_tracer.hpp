@@ -28,6 +28,11 @@ class GBufferTracer
     // `ctx` is the context the scene was uploaded to (borrowed; it outlives the pass).
     void init(prosper_pt_ctx *ctx);
 
+    // BLEND surfaces are left out of both records (PROSPER_PT_GBUFFER_OPAQUE_ONLY), as prosper's G-buffer leaves them to
+    // ForwardRenderer::recordTransparent.  Off by default.
+    void setOpaqueOnly(bool opaqueOnly) { m_opaqueOnly = opaqueOnly; }
+    [[nodiscard]] bool opaqueOnly() const { return m_opaqueOnly; }
+
     // Traces the G-buffer for the camera's current uniforms (the caller has run Camera::updateBuffer) at the camera's
     // resolution `width` x `height`.  `jitter`: the path tracer's jittered sample of (px, py, frameIndex) instead of
     // the pixel centre.  The returned device pointers stay valid until the next record with a larger extent or the
@@ -55,6 +60,7 @@ class GBufferTracer
   private:
     bool m_initialized{false};
     prosper_pt_ctx *m_ctx{nullptr};
+    bool m_opaqueOnly{false};
     std::vector<prosper_ModelInstanceTransforms> m_previousTransforms;
 };
 

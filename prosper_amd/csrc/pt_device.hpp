@@ -1152,9 +1152,11 @@ PPT_D bool alpha_verdict(uint32_t mode, float linearAlpha, float factorA, float 
     return true;
 }
 
+// `drawn`: the ray's draw given instead of made from the seed (the transparent pass asks with 0: "is alpha exactly 0?")
 template <bool COUNT>
 PPT_D uint32_t any_hit_settle(
-    const DeviceScene &s, uint32_t alphaIndex, f2 bary, uint32_t randomSeed, LaneCounters &cnt, AlphaFootprint &fp)
+    const DeviceScene &s, uint32_t alphaIndex, f2 bary, uint32_t randomSeed, LaneCounters &cnt, AlphaFootprint &fp,
+    const float *drawn = nullptr)
 {
     const uint4 *rp = reinterpret_cast<const uint4 *>(s.alphaTriangles + alphaIndex);
     const uint4 rec = rp[0];             // uv0, uv1, uv2, drawInstance
@@ -1164,7 +1166,7 @@ PPT_D uint32_t any_hit_settle(
     fp.factorA = __builtin_bit_cast(float, m1.y);
     fp.cutoff = __builtin_bit_cast(float, m1.z);
     fp.mode = bits & 3u;
-    fp.u = (float)pcg(randomSeed) / 4294967296.0f; // the ray's one draw (scene.rahit:35); BLEND only
+    fp.u = drawn ? *drawn : (float)pcg(randomSeed) / 4294967296.0f; // the ray's one draw (scene.rahit:35); BLEND only
     if constexpr (COUNT)
     {
         cnt.anyHitCalls++;
@@ -1567,14 +1569,33 @@ PPT_D bool descend_any(const float e[4], const int32_t ref[4], const TraversalSt
     return found;
 }
 
+// What the traversal does with a candidate whose alpha material is BLEND.
+//   kBlendStochastic   the any-hit's coin flip (scene.rahit:35): every kernel of the path tracer
+//   kBlendReject       always rejected (the opaque-only G-buffer); MASK keeps its cutoff
+//   kBlendPeel         the transparent pass: ONLY front-facing BLEND candidates whose alpha is not exactly 0 count, and
+//                      of those only the ones whose key (t, drawInstance, primitive) is greater than `after`'s - the
+//                      closest of them is the next layer front to back (closest-hit rays only)
+enum BlendPolicy : uint32_t
+{
+    kBlendStochastic = 0,
+    kBlendReject = 1,
+    kBlendPeel = 2,
+};
+// lexicographic a < b
+PPT_D bool ascending(f3 a, f3 b)
+{
+    return a.x < b.x || (a.x == b.x && (a.y < b.y || (a.y == b.y && a.z < b.z)));
+}
+
 // Shared driver of traceClosest (ANY = false, main.rgen:62-81) and shadow (ANY = true,
 // main.rgen:49-60).  `stack` points at this lane's column of the workgroup's LDS stack
 // (entry e lives at stack[e * 64]).  Returns true on a hit (ANY: occluded).
-template <bool ANY, bool COUNT, class Geom>
+template <bool ANY, bool COUNT, class Geom, BlendPolicy BLEND = kBlendStochastic>
 PPT_D bool trace_in(
     const Geom &g, const DeviceScene &s, f3 o, f3 d, float tMin, float tMaxIn, uint32_t seed, const TraversalStack &stack,
-    Hit &hit, LaneCounters &cnt)
+    Hit &hit, LaneCounters &cnt, const Hit *after = nullptr)
 {
+    static_assert(BLEND != kBlendPeel || !ANY, "peeling is a closest-hit traversal");
     hit.drawInstance = kMissIndex;
     hit.primitive = kMissIndex;
     hit.bary = f2{0.0f, 0.0f};
@@ -1642,7 +1663,42 @@ PPT_D bool trace_in(
                     if (t == hit.t && !(di < hit.drawInstance || (di == hit.drawInstance && prim < hit.primitive)))
                         continue;
                 }
-                if (!(flags & kTriFlagOpaque) && !any_hit_record<COUNT>(s, flags >> kTriAlphaShift, f2{bu, bv}, seed, cnt))
+                if constexpr (BLEND == kBlendPeel)
+                {
+                    if (flags & kTriFlagOpaque) continue;
+                    if ((s.alphaTriangles[flags >> kTriAlphaShift].material.bits & 3u) != PROSPER_ALPHA_MODE_BLEND) continue;
+                    // the rasteriser's back-face cull on the world-space triangle: counter-clockwise seen from the ray's origin
+                    const f3 p0 = f3{a.x, a.y, a.z}, p1 = f3{b.x, b.y, b.z}, p2 = f3{c.x, c.y, c.z};
+                    if (!(dot(cross(p1 - p0, p2 - p0), d) < 0.0f)) continue;
+                    // A ray through an edge that two triangles share meets both: the edge's function is 0 in both, exactly
+                    // (the same two vertices, the products negated).  The rasteriser's fill rule draws such a pixel once; here
+                    // the triangle whose winding runs along the edge in ascending (x, y, z) order keeps it - the neighbour
+                    // runs along it the other way.
+                    const EdgeFunctions ef = edge_functions(o, d, p0, p1, p2);
+                    if ((ef.W == 0.0f && !ascending(p0, p1)) || (ef.U == 0.0f && !ascending(p1, p2)) || (ef.V == 0.0f && !ascending(p2, p0)))
+                        continue;
+                    if (t < after->t) continue;
+                    if (t == after->t && !(di > after->drawInstance || (di == after->drawInstance && prim > after->primitive)))
+                        continue;
+                    // forward.frag:57 discards alpha 0.  With a draw of 0 the any-hit's own code rejects exactly that (alpha ==
+                    // 0; 0 > alpha never), mostly from the alpha bounds alone: the empty texels of a leaf cost no traversal of
+                    // their own.  (The pass tests the shaded surface's alpha again.)
+                    {
+                        const float zero = 0.0f;
+                        AlphaFootprint fp;
+                        const uint32_t v = any_hit_settle<COUNT>(s, flags >> kTriAlphaShift, f2{bu, bv}, 0u, cnt, fp, &zero);
+                        if (!(v == kAlphaUndecided ? any_hit_exact<COUNT>(fp, cnt) : v == kAlphaAccept)) continue;
+                    }
+                }
+                else if constexpr (BLEND == kBlendReject)
+                {
+                    if (!(flags & kTriFlagOpaque))
+                    {
+                        if ((s.alphaTriangles[flags >> kTriAlphaShift].material.bits & 3u) == PROSPER_ALPHA_MODE_BLEND) continue;
+                        if (!any_hit_record<COUNT>(s, flags >> kTriAlphaShift, f2{bu, bv}, seed, cnt)) continue;
+                    }
+                }
+                else if (!(flags & kTriFlagOpaque) && !any_hit_record<COUNT>(s, flags >> kTriAlphaShift, f2{bu, bv}, seed, cnt))
                     continue;
                 hit.drawInstance = di;
                 hit.primitive = prim;
@@ -1657,12 +1713,12 @@ PPT_D bool trace_in(
     return hit.drawInstance != kMissIndex;
 }
 
-template <bool ANY, bool COUNT>
+template <bool ANY, bool COUNT, BlendPolicy BLEND = kBlendStochastic>
 PPT_D bool trace(
     const DeviceScene &s, f3 o, f3 d, float tMin, float tMaxIn, uint32_t seed, const TraversalStack &stack, Hit &hit,
-    LaneCounters &cnt)
+    LaneCounters &cnt, const Hit *after = nullptr)
 {
-    return trace_in<ANY, COUNT>(GlobalGeom{s.nodes, s.triangles}, s, o, d, tMin, tMaxIn, seed, stack, hit, cnt);
+    return trace_in<ANY, COUNT, GlobalGeom, BLEND>(GlobalGeom{s.nodes, s.triangles}, s, o, d, tMin, tMaxIn, seed, stack, hit, cnt, after);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -384,7 +384,9 @@ struct GBufferNoVelocity
 
 // kVelocity: the primary ray goes through the point the (jittered) projection puts on the pixel centre, and a fourth
 // target takes the velocity, on hits and on the sky.  The plain instantiation reads nothing of `v`.
-template <bool kVelocity>
+// kOpaqueOnly (PROSPER_PT_GBUFFER_OPAQUE_ONLY): BLEND candidates are always rejected, as prosper keeps BLEND geometry out of its G-buffer
+// (draw_list_generator.comp:43-54); forward_transparent_kernel draws them afterwards.
+template <bool kVelocity, bool kOpaqueOnly = false>
 __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     DeviceScene s, GBufferTraceParams g, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
     float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow,
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     const Ray ray = pinhole_camera_ray(g.r, uv);
     LaneCounters cnt = {};
     Hit hit;
-    if (!trace<false, false>(s, ray.o, ray.d, ray.tMin, ray.tMax, pcg(rng.x ^ rng.z), stack, hit, cnt))
+    if (!trace<false, false, kOpaqueOnly ? kBlendReject : kBlendStochastic>(s, ray.o, ray.d, ray.tMin, ray.tMax, pcg(rng.x ^ rng.z), stack, hit, cnt))
     {
         // the clear values of GBufferRenderer.cpp:487-516
         albedoRoughness[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -461,8 +463,9 @@ void launch_gbuffer_trace(
     int32_t *stackOverflow, hipStream_t stream)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
+    const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<false, true> : gbuffer_trace_kernel<false, false>;
     hipLaunchKernelGGL(
-        gbuffer_trace_kernel<false>, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
+        kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
         static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, GBufferNoVelocity{});
 }
 
@@ -471,8 +474,9 @@ void launch_gbuffer_trace_velocity(
     float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
+    const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<true, true> : gbuffer_trace_kernel<true, false>;
     hipLaunchKernelGGL(
-        gbuffer_trace_kernel<true>, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
+        kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
         static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, v);
 }
 
@@ -645,26 +649,19 @@ PPT_D f3 eval_ibl(const IblMaps &m, const Surface &sf)
     return kD * diffuse + specular;
 }
 
-// The body of both shading kernels; IBL adds evalIBL after the spot lights (deferred_shading.comp:59-60).
-template <bool IBL>
-PPT_D void deferred_shade(
-    const DeviceScene &s, const DeferredParams &d, const float4 *__restrict__ albedoRoughness,
-    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
-    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, const IblMaps *ibl)
+// What deferred_shading.comp:40-60 and forward.frag:69-81 both sum over a surface, in their order: the sun, then the
+// point and the spot lights of clusterIndex(px, zCam) (scene/light_clusters.glsl), each list summed from zero, then with
+// IBL evalIBL.  zCam: the surface's camera-space z (negative in front of the camera).
+struct ClusterGrid
 {
-    uint32_t px, py;
-    if (!restir_pixel(d.r, px, py) || px >= d.r.width || py >= d.r.height) return;
-    const size_t i = (size_t)py * d.r.width + px;
-    const float depth = nonLinearDepth[i];
-    const Surface sf = restir_surface(d.r, px, py, depth, albedoRoughness[i], normalMetallic[i]);
-    if (d.r.drawType != PROSPER_DRAW_TYPE_DEFAULT)
-    {
-        const f3 c = d.r.drawType == PROSPER_DRAW_TYPE_POSITION ? sf.positionWS : sf.material.albedo;
-        hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
-        return;
-    }
-    const float linearDepth = linearize_depth(d.r, depth);
-
+    float near_, far_;
+    uint32_t clustersX, clustersY;
+};
+template <bool IBL>
+PPT_D f3 shade_clustered(
+    const DeviceScene &s, const Surface &sf, uint32_t px, uint32_t py, float zCam, const ClusterGrid &d,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, const IblMaps *ibl)
+{
     // evalDirectionalLight (scene/lighting.glsl:8-12)
     const prosper_DirectionalLightParameters sun = *s.directionalLight;
     const f3 sunL = -normalize(f3{sun.direction.x, sun.direction.y, sun.direction.z});
@@ -672,7 +669,7 @@ PPT_D void deferred_shade(
 
     // clusterIndex: slice = uint(16 * log(-z / near) / log(far / near)); nearer than near (or NaN) is slice 0, past
     // the last slice (16) a cluster without lights
-    const float ratio = -linearDepth / d.near_;
+    const float ratio = -zCam / d.near_;
     float slice = ratio > 0.0f ? ((float)kClusterZSlices * log2_(ratio)) / log2_(d.far_ / d.near_) : 0.0f;
     if (!(slice >= 0.0f)) slice = 0.0f;
     uint32_t offset = 0, pointCount = 0, spotCount = 0;
@@ -703,6 +700,29 @@ PPT_D void deferred_shade(
     }
     color = color + spots;
     if constexpr (IBL) color = color + eval_ibl(*ibl, sf);
+    return color;
+}
+
+// The body of both shading kernels; IBL adds evalIBL after the spot lights (deferred_shading.comp:59-60).
+template <bool IBL>
+PPT_D void deferred_shade(
+    const DeviceScene &s, const DeferredParams &d, const float4 *__restrict__ albedoRoughness,
+    const float4 *__restrict__ normalMetallic, const float *__restrict__ nonLinearDepth,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, const IblMaps *ibl)
+{
+    uint32_t px, py;
+    if (!restir_pixel(d.r, px, py) || px >= d.r.width || py >= d.r.height) return;
+    const size_t i = (size_t)py * d.r.width + px;
+    const float depth = nonLinearDepth[i];
+    const Surface sf = restir_surface(d.r, px, py, depth, albedoRoughness[i], normalMetallic[i]);
+    if (d.r.drawType != PROSPER_DRAW_TYPE_DEFAULT)
+    {
+        const f3 c = d.r.drawType == PROSPER_DRAW_TYPE_POSITION ? sf.positionWS : sf.material.albedo;
+        hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        return;
+    }
+    const float linearDepth = linearize_depth(d.r, depth);
+    const f3 color = shade_clustered<IBL>(s, sf, px, py, linearDepth, ClusterGrid{d.near_, d.far_, d.clustersX, d.clustersY}, pointers, indices, ibl);
     hdr[i] = make_float4(color.x, color.y, color.z, 1.0f);
 }
 
@@ -758,6 +778,169 @@ void launch_deferred_shading_ibl(
         deferred_shading_ibl_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
         static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
         static_cast<const uint2 *>(pointers), indices, hdr, maps);
+}
+
+// ------------------------------------------------------------------------------------------
+// Forward transparent pass (src/render/ForwardRenderer.cpp recordTransparent, forward.frag): the BLEND
+// surfaces the opaque-only G-buffer left out, lit forward over the light clusters and blended over the HDR image in
+// place.  One lane per pixel on the G-buffer's pixel mapping, along the G-buffer's own ray of that pixel.  Layers are
+// peeled front to back: each closest-hit traversal (kBlendPeel) returns the nearest front-facing BLEND triangle behind
+// the last one by the key (t, drawInstance, primitive); C += T a src, T *= 1 - a, and the end is C + T dst - in exact
+// arithmetic prosper's blend state applied back to front.  No layer cap, no memory beyond the traversal stack.
+// ------------------------------------------------------------------------------------------
+
+// kLayers: the debug mode of prosper_pt_read_transparent_layers - the first p.debugLayers layers of a pixel are kept
+template <bool IBL, bool kLayers>
+__global__ __launch_bounds__(256) void forward_transparent_kernel(
+    DeviceScene s, TransparentParams p, const float *__restrict__ nonLinearDepth, const uint2 *__restrict__ pointers,
+    const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, int32_t *__restrict__ stackOverflow,
+    uint32_t *__restrict__ stats, uint32_t *__restrict__ layerCounts, prosper_pt_transparent_layer *__restrict__ layers,
+    IblMaps ibl)
+{
+    __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
+    const GBufferTraceParams &g = p.g;
+    uint32_t px, py;
+    if (!restir_pixel(g.r.width, g.r.height, px, py)) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const TraversalStack stack{(lds_int32 *)ldsStack + wave * (kTraversalStackDepth * 64u) + lane,
+                               stackOverflow + blockIdx.x * 256u + threadIdx.x, kTraversalStackDepth, gridDim.x * 256u, 64u};
+    uint32_t count = 0;
+    if (px < g.r.width && py < g.r.height)
+    {
+        const size_t i = (size_t)py * g.r.width + px;
+        // the G-buffer's ray of this pixel (gbuffer_trace_kernel): centre, the path tracer's sample, or the centre half a
+        // camera jitter back
+        f2 uv = f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
+        if (g.jitter)
+        {
+            Rng rng{px, py, g.frameIndex};
+            const f2 j = rng.rnd2d01();
+            uv = f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height};
+        }
+        if (p.cameraJitter) uv = f2{uv.x - p.currentJitter[0] * 0.5f, uv.y - p.currentJitter[1] * 0.5f};
+        const Ray ray = pinhole_camera_ray(g.r, uv);
+        const float stored = nonLinearDepth[i];
+        // Nothing behind the opaque surface can pass the depth test: the traversal ends a little past it (0.1 %, far more
+        // than the depth's rounding), and the exact test below decides.  A depth that gives no positive distance (the sky's
+        // 0 on an infinite far plane, a NaN) bounds nothing.
+        float tMax = ray.tMax;
+        {
+            const float zCam = -p.cameraToClip32 / (stored + p.cameraToClip22);
+            const float cosFwd = dot(ray.d, f3{g.r.fwd[0], g.r.fwd[1], g.r.fwd[2]});
+            const float bound = (-zCam / cosFwd) * 1.001f;
+            if (stored != 0.0f && bound > 0.0f && bound < tMax) tMax = bound;
+        }
+        const f3 eye = f3{g.r.eye[0], g.r.eye[1], g.r.eye[2]};
+        const bool debugView = g.drawType != PROSPER_DRAW_TYPE_DEFAULT && g.drawType != PROSPER_DRAW_TYPE_MESHLET_ID;
+        const ClusterGrid grid{p.near_, p.far_, p.clustersX, p.clustersY};
+
+        f3 C = f3{0.0f, 0.0f, 0.0f};
+        float T = 1.0f, nearestAlpha = 0.0f;
+        Hit after;
+        after.drawInstance = 0u;
+        after.primitive = 0u;
+        after.bary = f2{0.0f, 0.0f};
+        after.t = -1.0f; // every candidate's t is > tMin = 0
+        LaneCounters cnt = {};
+        while (T != 0.0f)
+        {
+            Hit hit;
+            if (!trace<false, false, kBlendPeel>(s, ray.o, ray.d, ray.tMin, tMax, 0u, stack, hit, cnt, &after)) break;
+            after = hit;
+            Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
+            if (sf.material.alpha == 0.0f) continue; // forward.frag:57
+            // posNDC.z as gbuffer_trace_kernel computes it; eGreater on reverse Z, no depth write
+            const float *m = g.worldToClip;
+            const f3 q = sf.positionWS;
+            const float cz = __builtin_fmaf(m[10], q.z, __builtin_fmaf(m[6], q.y, __builtin_fmaf(m[2], q.x, m[14])));
+            const float cw = __builtin_fmaf(m[11], q.z, __builtin_fmaf(m[7], q.y, __builtin_fmaf(m[3], q.x, m[15])));
+            const float depth = cz / cw;
+            if (!(depth > stored)) continue;
+            // forward.frag:52,67
+            sf.invViewRayWS = normalize(eye - sf.positionWS);
+            sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
+            if constexpr (kLayers)
+            {
+                if (count < p.debugLayers)
+                {
+                    prosper_pt_transparent_layer L;
+                    L.drawInstance = hit.drawInstance;
+                    L.primitive = hit.primitive;
+                    L.positionWS[0] = q.x; L.positionWS[1] = q.y; L.positionWS[2] = q.z;
+                    L.nonLinearDepth = depth;
+                    L.albedo[0] = sf.material.albedo.x; L.albedo[1] = sf.material.albedo.y; L.albedo[2] = sf.material.albedo.z;
+                    L.roughness = sf.material.roughness;
+                    L.normal[0] = sf.normalWS.x; L.normal[1] = sf.normalWS.y; L.normal[2] = sf.normalWS.z;
+                    L.metallic = sf.material.metallic;
+                    L.alpha = sf.material.alpha;
+                    L.reserved = 0u;
+                    layers[i * p.debugLayers + count] = L;
+                }
+            }
+            f3 src;
+            float a;
+            if (debugView)
+            {
+                src = debug_color(s, g.drawType, hit, sf);
+                a = 1.0f;
+            }
+            else
+            {
+                // forward.mesh:75: the third component of worldToCamera * (position, 1)
+                const float *w = p.worldToCamera;
+                const float zCam = __builtin_fmaf(w[10], q.z, __builtin_fmaf(w[6], q.y, __builtin_fmaf(w[2], q.x, w[14])));
+                src = shade_clustered<IBL>(s, sf, px, py, zCam, grid, pointers, indices, &ibl);
+                a = sf.material.alpha > 0.0f ? sf.material.alpha : 1.0f; // forward.frag:83
+            }
+            if (count == 0) nearestAlpha = a;
+            ++count;
+            C = C + src * (T * a);
+            T = T * (1.0f - a);
+        }
+        if constexpr (kLayers) layerCounts[i] = count;
+        if (count > 0)
+        {
+            const float4 dst = hdr[i];
+            // VkUtils.hpp:93-106: colour srcAlpha / oneMinusSrcAlpha; alpha oneMinusSrcAlpha / zero, i.e. the last drawn
+            // (nearest) layer's a (1 - a)
+            hdr[i] = make_float4(
+                C.x + dst.x * T, C.y + dst.y * T, C.z + dst.z * T, nearestAlpha * (1.0f - nearestAlpha));
+        }
+    }
+    // prosper_pt_get_transparent_info: one set of atomics per wave
+    const uint64_t covered = __ballot(count > 0);
+    if (covered != 0ull)
+    {
+        uint32_t sum = count, deepest = count;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            sum += __shfl_xor(sum, off, 64);
+            const uint32_t o = __shfl_xor(deepest, off, 64);
+            deepest = o > deepest ? o : deepest;
+        }
+        if (lane == 0)
+        {
+            atomicAdd(&stats[0], (uint32_t)__popcll(covered));
+            atomicMax(&stats[1], deepest);
+            atomicAdd(reinterpret_cast<unsigned long long *>(stats + 2), (unsigned long long)sum);
+        }
+    }
+}
+
+void launch_forward_transparent(
+    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
+    const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
+    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream)
+{
+    if (p.g.r.width == 0 || p.g.r.height == 0) return;
+    const bool ibl = irradiance != nullptr, debug = p.debugLayers != 0u;
+    const auto kernel = ibl ? (debug ? forward_transparent_kernel<true, true> : forward_transparent_kernel<true, false>)
+                            : (debug ? forward_transparent_kernel<false, true> : forward_transparent_kernel<false, false>);
+    const IblMaps maps = {irradiance, radiance, lut};
+    hipLaunchKernelGGL(
+        kernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
+        static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, maps);
 }
 
 } // namespace ppt

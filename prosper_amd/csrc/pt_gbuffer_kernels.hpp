@@ -38,6 +38,7 @@ struct GBufferTraceParams
     RenderParams r;
     float worldToClip[16];
     uint32_t drawType, frameIndex, jitter;
+    uint32_t opaqueOnly; // BLEND candidates are always rejected (PROSPER_PT_GBUFFER_OPAQUE_ONLY)
 };
 // albedoRoughness, normalMetallic: r.width*r.height float4; nonLinearDepth: r.width*r.height float.  Grid of
 // restir_grid_blocks(r.width, r.height) blocks (the stack overflow array is sized for it).
@@ -57,6 +58,26 @@ struct GBufferVelocityParams
 void launch_gbuffer_trace_velocity(
     const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
     float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream);
+// The forward transparent pass (forward_transparent_kernel) in place over `hdr`, r.width*r.height float4,
+// against `nonLinearDepth`.  g.jitter: the path tracer's sample; cameraJitter: the velocity entry's ray.  The lists are
+// launch_light_clustering's for the same camera and extent; irradiance / radiance / lut: the IBL maps, all nullptr
+// without IBL.  stats: four uint32 the caller zeroed - pixels with a layer, the deepest pixel's layers, total layers
+// (64 bits).  debugLayers != 0: layerCounts[pixel] and the first debugLayers layers of each pixel are written.
+struct TransparentParams
+{
+    GBufferTraceParams g;
+    float worldToCamera[16]; // column-major
+    float cameraToClip22, cameraToClip32;
+    float currentJitter[2];
+    uint32_t cameraJitter;
+    float near_, far_;
+    uint32_t clustersX, clustersY;
+    uint32_t debugLayers;
+};
+void launch_forward_transparent(
+    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
+    const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
+    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream);
 // Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
 // uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
 // [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the

@@ -44,6 +44,19 @@ struct GBufferPassState
     DeviceBuffer iblLut;        // kIblLutSize^2 R16G16 UNORM
     StageEvents<3> iblTiming;   // around the three passes of the last generation
     bool iblGenerated = false;    // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
+    // what the last clustering was made from: prosper_pt_forward_transparent reuses it for the same camera and lights
+    ClusterParams clusterParams = {};
+    uint32_t clusterLightUpdates = 0;
+    bool clusterValid = false; // (cleared by prosper_pt_upload_scene)
+    // prosper_pt_forward_transparent
+    DeviceBuffer transparentDepth; // device copy of a call's host depth
+    DeviceBuffer transparentStats; // four uint32: covered pixels, deepest pixel, total layers (64 bits)
+    DeviceBuffer transparentLayers; // debug mode: width*height counts, then width*height*N layer records
+    StageEvents<1> transparentTiming;
+    uint32_t transparentDebugLayers = 0; // prosper_pt_set_transparent_debug_layers
+    bool transparentRan = false, transparentReclustered = false;
+    size_t transparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
+    uint32_t transparentLayerCount = 0;
 };
 
 bool create_gbuffer_passes(prosper_pt_ctx *ctx)
@@ -61,6 +74,7 @@ void destroy_gbuffer_passes(prosper_pt_ctx *ctx)
 void forget_ibl_maps(prosper_pt_ctx *ctx)
 {
     ctx->gbufferPasses->iblGenerated = false;
+    ctx->gbufferPasses->clusterValid = false; // the clustering describes the old scene's lights too
 }
 
 } // namespace ppt
@@ -176,11 +190,10 @@ int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, pro
     return PROSPER_PT_OK;
 }
 
-// The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.  `velocity`: the
-// velocity variant, whose matrices and jitters are filled in here from `camera`.
-int gbuffer_trace(
-    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s, GBufferVelocityParams *velocity = nullptr)
+// The camera ray, the depth's worldToClip and the switches of a G-buffer trace (the transparent pass follows the same ray)
+GBufferTraceParams gbuffer_trace_params(
+    uint32_t drawType, uint32_t frameIndex, bool jitter, bool opaqueOnly, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height)
 {
     GBufferTraceParams g = {};
     set_camera_ray_params(g.r, camera);
@@ -201,6 +214,18 @@ int gbuffer_trace(
     g.drawType = drawType;
     g.frameIndex = frameIndex;
     g.jitter = jitter ? 1u : 0u;
+    g.opaqueOnly = opaqueOnly ? 1u : 0u;
+    return g;
+}
+
+// The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.  `velocity`: the
+// velocity variant, whose matrices and jitters are filled in here from `camera`.
+int gbuffer_trace(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s, GBufferVelocityParams *velocity = nullptr,
+    bool opaqueOnly = false)
+{
+    const GBufferTraceParams g = gbuffer_trace_params(drawType, frameIndex, jitter, opaqueOnly, camera, width, height);
 
     int32_t *ovf = nullptr;
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
@@ -295,6 +320,9 @@ int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
     st.clusterDims[0] = c.dimX;
     st.clusterDims[1] = c.dimY;
     st.clusterDims[2] = kClusterZSlices + 1u;
+    st.clusterParams = c;
+    st.clusterLightUpdates = ctx->lights ? ctx->lights->updates : 0u;
+    st.clusterValid = true;
     return PROSPER_PT_OK;
 }
 
@@ -403,7 +431,7 @@ int prosper_pt_trace_gbuffer(
     uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets *targets, void *stream)
 {
     // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_JITTER)
+    if (flags & ~(uint32_t)(PROSPER_PT_GBUFFER_JITTER | PROSPER_PT_GBUFFER_OPAQUE_ONLY))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: unknown flags");
     if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_trace_gbuffer: empty extent");
@@ -428,7 +456,10 @@ int prosper_pt_trace_gbuffer(
         else
             rc = gbuffer_owned_targets(ctx, (size_t)width * height, s, t);
     }
-    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s);
+    if (rc == PROSPER_PT_OK)
+        rc = gbuffer_trace(
+            ctx, drawType, frameIndex, (flags & PROSPER_PT_GBUFFER_JITTER) != 0, camera, width, height, t, s, nullptr,
+            (flags & PROSPER_PT_GBUFFER_OPAQUE_ONLY) != 0);
     if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
 }
@@ -441,7 +472,7 @@ int prosper_pt_trace_gbuffer_velocity(
 {
     // the arguments are checked before the context, so that every refusal happens without a GPU
     const char *what = "prosper_pt_trace_gbuffer_velocity";
-    if (flags != 0u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
+    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_OPAQUE_ONLY) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
     if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
     if (!camera || !desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
@@ -490,7 +521,8 @@ int prosper_pt_trace_gbuffer_velocity(
             v.previousTransforms = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
         }
     }
-    if (rc == PROSPER_PT_OK) rc = gbuffer_trace(ctx, drawType, frameIndex, false, camera, width, height, t, s, &v);
+    if (rc == PROSPER_PT_OK)
+        rc = gbuffer_trace(ctx, drawType, frameIndex, false, camera, width, height, t, s, &v, (flags & PROSPER_PT_GBUFFER_OPAQUE_ONLY) != 0);
     if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
 }
@@ -737,6 +769,155 @@ int prosper_pt_deferred_shading(
             st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ctx->hdr, s);
     PPT_HIP(hipGetLastError());
     return mark_versions_read(ctx, s);
+}
+
+// ---- forward transparent pass (src/render/ForwardRenderer.cpp recordTransparent) ----
+
+int prosper_pt_forward_transparent(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, uint32_t flags, uint32_t frameIndex,
+    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const float *nonLinearDepth, uint32_t onDevice,
+    void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    const char *what = "prosper_pt_forward_transparent";
+    if (flags & ~(uint32_t)(PROSPER_PT_TRANSPARENT_JITTER | PROSPER_PT_TRANSPARENT_CAMERA_JITTER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
+    if ((flags & PROSPER_PT_TRANSPARENT_JITTER) && (flags & PROSPER_PT_TRANSPARENT_CAMERA_JITTER))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": JITTER and CAMERA_JITTER exclude each other");
+    if (!pc || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
+    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    const int crc = check_scene(ctx, what);
+    if (crc != PROSPER_PT_OK) return crc;
+    if (!hdr_has_extent(ctx, width, height))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the HDR image has another extent");
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t pixels = (size_t)width * height;
+    const float *depth = nonLinearDepth;
+    if (!depth)
+    {
+        if (!st.gbufferLast.nonLinearDepth) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+        if (st.gbufferLastWidth != width || st.gbufferLastHeight != height)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the last traced G-buffer has another extent");
+        depth = st.gbufferLast.nonLinearDepth;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    if (nonLinearDepth && !onDevice)
+    {
+        rc = grow_to(st.transparentDepth, pixels * 4u, s);
+        if (rc != PROSPER_PT_OK) return rc;
+        PPT_HIP(hipMemcpyAsync(st.transparentDepth.ptr, nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
+        depth = st.transparentDepth.as<float>();
+    }
+    rc = grow_to(st.transparentStats, 16u, s);
+    const uint32_t debugLayers = st.transparentDebugLayers;
+    if (rc == PROSPER_PT_OK && debugLayers) rc = grow_to(st.transparentLayers, pixels * (4u + (size_t)debugLayers * sizeof(prosper_pt_transparent_layer)), s);
+    if (rc == PROSPER_PT_OK) rc = st.transparentTiming.create();
+    if (rc != PROSPER_PT_OK) return rc;
+    st.transparentRan = false;
+    st.transparentLayerPixels = 0;
+    PPT_HIP(hipEventRecord(st.transparentTiming.events[0], s));
+
+    // the lists of the last clustering serve when they were made from the same camera terms, extent and lights
+    const ClusterParams c = cluster_params(camera, width, height);
+    const uint32_t lightUpdates = ctx->lights ? ctx->lights->updates : 0u;
+    const bool reuse = st.clusterValid && std::memcmp(&st.clusterParams, &c, sizeof(c)) == 0 && st.clusterLightUpdates == lightUpdates;
+    if (!reuse)
+    {
+        rc = cluster_lights(ctx, c, s);
+        if (rc != PROSPER_PT_OK) return rc;
+    }
+
+    TransparentParams p = {};
+    p.g = gbuffer_trace_params(pc->drawType, frameIndex, (flags & PROSPER_PT_TRANSPARENT_JITTER) != 0, false, camera, width, height);
+    std::memcpy(p.worldToCamera, &camera->worldToCamera, 64);
+    const RestirCamera rc2 = gbuffer_camera(camera);
+    p.cameraToClip22 = rc2.cameraToClip22;
+    p.cameraToClip32 = rc2.cameraToClip32;
+    p.cameraJitter = (flags & PROSPER_PT_TRANSPARENT_CAMERA_JITTER) ? 1u : 0u;
+    p.currentJitter[0] = camera->currentJitter[0];
+    p.currentJitter[1] = camera->currentJitter[1];
+    p.near_ = c.near_;
+    p.far_ = c.far_;
+    p.clustersX = c.dimX;
+    p.clustersY = c.dimY;
+    p.debugLayers = debugLayers;
+
+    int32_t *ovf = nullptr;
+    rc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
+    if (rc != PROSPER_PT_OK) return rc;
+    PPT_HIP(hipMemsetAsync(st.transparentStats.ptr, 0, 16u, s));
+    wait_for_slot(ctx->slots[0], s);
+    const bool ibl = pc->ibl == 1u;
+    uint32_t *counts = debugLayers ? st.transparentLayers.as<uint32_t>() : nullptr;
+    launch_forward_transparent(
+        ctx->scene, p, depth, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
+        ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, ovf,
+        st.transparentStats.as<uint32_t>(), counts,
+        debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s);
+    release_slot(ctx->slots[0], s);
+    PPT_HIP(hipGetLastError());
+    PPT_HIP(hipEventRecord(st.transparentTiming.events[1], s));
+    st.transparentRan = true;
+    st.transparentReclustered = !reuse;
+    st.transparentLayerPixels = debugLayers ? pixels : 0u;
+    st.transparentLayerCount = debugLayers;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_get_transparent_info(prosper_pt_ctx *ctx, prosper_pt_transparent_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_transparent_info: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.transparentRan) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_forward_transparent has not run yet");
+    PPT_HIP(hipSetDevice(ctx->device));
+    prosper_pt_transparent_info info = {};
+    if (const int rc = st.transparentTiming.elapsed(&info.ms)) return rc; // (waits for the call's last kernel)
+    uint32_t stats[4] = {};
+    PPT_HIP(hipMemcpy(stats, st.transparentStats.ptr, 16u, hipMemcpyDeviceToHost));
+    info.coveredPixels = stats[0];
+    info.maxLayers = stats[1];
+    info.totalLayers = ((uint64_t)stats[3] << 32) | stats[2];
+    info.reclustered = st.transparentReclustered ? 1u : 0u;
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_set_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_transparent_debug_layers: null argument");
+    if (layersPerPixel > 64u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_transparent_debug_layers: at most 64 layers per pixel");
+    ctx->gbufferPasses->transparentDebugLayers = layersPerPixel;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_transparent_layers(
+    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels,
+    uint32_t layersPerPixel, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_transparent_layers: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.transparentRan || !st.transparentLayerPixels)
+        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_forward_transparent did not run in debug mode (prosper_pt_set_transparent_debug_layers)");
+    if (pixels != st.transparentLayerPixels || layersPerPixel != st.transparentLayerCount)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_transparent_layers: pixels or layersPerPixel differ from the call's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t *counts = st.transparentLayers.as<uint32_t>();
+    if (host_counts) PPT_HIP(hipMemcpyAsync(host_counts, counts, pixels * 4u, hipMemcpyDeviceToHost, s));
+    if (host_layers)
+        PPT_HIP(hipMemcpyAsync(host_layers, counts + pixels, pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
 }
 
 // ---- image-based lighting (src/render/ImageBasedLighting.cpp) ----

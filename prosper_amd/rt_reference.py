@@ -218,7 +218,15 @@ class GBufferTracer:
         self._h = h
         self._ctx = ctx
 
-    def record(self, camera, width, height, draw_type="Default", frame_index=0, jitter=True, stream=None):
+    def set_opaque_only(self, opaque_only):
+        """GBufferTracer::setOpaqueOnly: later records leave BLEND surfaces to ForwardRenderer.record_transparent."""
+        rc = lib().prosper_host_gbuffer_tracer_set_opaque_only(self._h, int(opaque_only))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def record(self, camera, width, height, draw_type="Default", frame_index=0, jitter=True, stream=None, opaque_only=None):
+        if opaque_only is not None:
+            self.set_opaque_only(opaque_only)
         out = S.RestirInputs()
         rc = lib().prosper_host_gbuffer_tracer_record(
             self._h, camera._h, width, height, S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
@@ -227,10 +235,13 @@ class GBufferTracer:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
         return out
 
-    def record_velocity(self, camera, width, height, draw_type="Default", frame_index=0, transforms=None, stream=None):
+    def record_velocity(self, camera, width, height, draw_type="Default", frame_index=0, transforms=None, stream=None,
+                        opaque_only=None):
         """GBufferTracer::recordVelocity: the G-buffer through the camera's (jittered) pixel centres and the velocity
         image; (S.RestirInputs, velocity device pointer).  `transforms`: this frame's ctypes array of
         S.ModelInstanceTransforms (world.freeze()["transforms"]); the pass keeps it as the next call's previous frame."""
+        if opaque_only is not None:
+            self.set_opaque_only(opaque_only)
         out, velocity = S.RestirInputs(), C.c_void_p()
         rc = lib().prosper_host_gbuffer_tracer_record_velocity(
             self._h, camera._h, width, height, S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
@@ -349,6 +360,45 @@ class SkyboxRenderer:
     def close(self):
         if self._h:
             lib().prosper_host_skybox_renderer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ForwardRenderer:
+    """render::ForwardRenderer (csrc/host/forward_renderer.hpp), its transparent pass, on a Context the scene was uploaded
+    to: record_transparent blends the BLEND layers over the context's HDR image (Context.forward_transparent) and returns
+    the S.ForwardPC it pushed."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_forward_renderer_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record_transparent(self, camera, width, height, depth=None, depth_ptr=None, ray_flags=0, frame_index=0,
+                           apply_ibl=False, draw_type="Default", stream=None):
+        """`depth`: a host array [h, w]; `depth_ptr`: a device pointer; neither: the last traced G-buffer's depth.
+        `ray_flags`: 0, S.TRANSPARENT_JITTER (with `frame_index`) or S.TRANSPARENT_CAMERA_JITTER."""
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        pc = S.ForwardPC()
+        rc = lib().prosper_host_forward_renderer_record_transparent(
+            self._h, camera._h, width, height, C.c_void_p(depth_ptr if dp is None else dp.ctypes.data),
+            1 if dp is None else 0, ray_flags, frame_index, int(apply_ibl),
+            S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type), C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_forward_renderer_destroy(self._h)
             self._h = None
 
     def __del__(self):

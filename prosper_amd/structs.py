@@ -340,6 +340,7 @@ RESTIR_TRACE_GBUFFER = 1 << 1
 RESTIR_JITTER_GBUFFER = 1 << 2
 # prosper_pt_trace_gbuffer flags
 GBUFFER_JITTER = 1 << 0
+GBUFFER_OPAQUE_ONLY = 1 << 2  # BLEND candidates always rejected (both G-buffer entries); bit 1 stays an unknown flag
 
 
 class GBufferTargets(C.Structure):
@@ -366,6 +367,29 @@ CLUSTER_DIM = 32
 CLUSTER_Z_SLICES = 16
 CLUSTER_MAX_POINTS = 128
 CLUSTER_MAX_SPOTS = 128
+
+
+class ForwardPC(C.Structure):
+    """ForwardPC, res/shader/shared/shader_structs/push_constants/forward.h (previousTransformValid is not read)"""
+    _fields_ = [("drawType", C.c_uint32), ("ibl", C.c_uint32), ("previousTransformValid", C.c_uint32)]
+
+
+# prosper_pt_forward_transparent flags: which of the G-buffer's rays the pass follows (neither: the pixel centre)
+TRANSPARENT_JITTER = 1 << 0
+TRANSPARENT_CAMERA_JITTER = 1 << 1
+
+
+class TransparentInfo(C.Structure):
+    """prosper_pt_transparent_info of the last prosper_pt_forward_transparent"""
+    _fields_ = [("coveredPixels", C.c_uint32), ("maxLayers", C.c_uint32), ("totalLayers", C.c_uint64),
+                ("ms", C.c_float), ("reclustered", C.c_uint32)]
+
+
+class TransparentLayer(C.Structure):
+    """prosper_pt_transparent_layer: one layer of a pixel as the pass's debug mode records it (64 bytes)"""
+    _fields_ = [("drawInstance", C.c_uint32), ("primitive", C.c_uint32), ("positionWS", C.c_float * 3),
+                ("nonLinearDepth", C.c_float), ("albedo", C.c_float * 3), ("roughness", C.c_float),
+                ("normal", C.c_float * 3), ("metallic", C.c_float), ("alpha", C.c_float), ("reserved", C.c_uint32)]
 
 
 class IblInfo(C.Structure):

@@ -15,6 +15,11 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred --ibl             with the image-based lighting term: the irradiance / radiance maps and the BRDF LUT
                                  are generated once from the sky (prosper_pt_generate_ibl), then the frame is shaded
     --deferred --sky             prosper_pt_skybox_fill after the shading: the sky wherever the G-buffer's ray missed
+    --deferred --transparents    prosper's transparent pass: the G-buffer leaves BLEND surfaces out
+                                 (PROSPER_PT_GBUFFER_OPAQUE_ONLY) and prosper_pt_forward_transparent blends them, lit
+                                 forward over the light clusters, over the shaded image after --sky and before --bloom
+                                 (Renderer.cpp:493-500), through the host layer's ForwardRenderer; under --taa along the
+                                 camera-jittered ray
     --deferred --bloom [--bloom-threshold T] [--bloom-quarter] [--bloom-fft]
                                  prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
                                  defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573);
@@ -69,6 +74,7 @@ def main():
     ap.add_argument("--deferred", action="store_true", help="clustered deferred shading of a traced G-buffer")
     ap.add_argument("--ibl", action="store_true", help="with --deferred: add image-based lighting from the sky")
     ap.add_argument("--sky", action="store_true", help="with --deferred: fill the sky where the G-buffer's ray missed")
+    ap.add_argument("--transparents", action="store_true", help="with --deferred: BLEND surfaces through the forward transparent pass")
     ap.add_argument("--bloom", action="store_true", help="with --deferred: bloom (multi-resolution blur) over the shaded image")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
     ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
@@ -81,12 +87,12 @@ def main():
     args = ap.parse_args()
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
-    if (args.sky or args.dof or args.bloom or args.taa) and not args.deferred:
-        ap.error("--sky, --bloom, --taa and --dof belong to --deferred")
+    if (args.sky or args.dof or args.bloom or args.taa or args.transparents) and not args.deferred:
+        ap.error("--sky, --transparents, --bloom, --taa and --dof belong to --deferred")
     if args.frames < 1:
         ap.error("--frames must be at least 1")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
-    from prosper_amd.rt_reference import Bloom, Camera, DepthOfField, GBufferTracer, TemporalAntiAliasing
+    from prosper_amd.rt_reference import Bloom, Camera, DepthOfField, ForwardRenderer, GBufferTracer, TemporalAntiAliasing
     w, h = (int(v) for v in args.size.lower().split("x"))
     world = gltf.load_gltf(args.gltf, bc7_on_gpu=True)  # prosper_cache BC7 files are decoded by the library at upload
     if world.missing_images:
@@ -115,9 +121,12 @@ def main():
         bloom = Bloom(ctx, technique=S.BLOOM_FFT if args.bloom_fft else S.BLOOM_MULTI_RESOLUTION_BLUR) if args.bloom else None
         if bloom:
             bloom.draw_ui(threshold=args.bloom_threshold, resolution_scale=S.BLOOM_QUARTER if args.bloom_quarter else S.BLOOM_HALF)
+        forward = ForwardRenderer(ctx) if args.transparents else None
+        tracer = GBufferTracer(ctx)
+        tracer.set_opaque_only(args.transparents)  # the BLEND surfaces are the transparent pass's
         if args.taa:
             hcam.set_jitter(True)
-            tracer, taa = GBufferTracer(ctx), TemporalAntiAliasing(ctx)
+            taa = TemporalAntiAliasing(ctx)
             transforms = world.freeze()["transforms"]
         for frame in range(args.frames if args.taa else 1):
             if args.taa:
@@ -125,10 +134,16 @@ def main():
                 cam, focal = hcam.update_buffer()
                 g, _ = tracer.record_velocity(hcam, w, h, frame_index=frame, transforms=transforms)
                 ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth, ibl=1 if args.ibl else 0)
+            elif args.transparents:
+                g = tracer.record(hcam, w, h, jitter=False)
+                ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth, ibl=1 if args.ibl else 0)
             else:
                 ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
             if args.sky:
                 ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
+            if forward:
+                # over the sky-filled image, along the ray the G-buffer was traced with; ibl = 0, as prosper draws them
+                forward.record_transparent(hcam, w, h, ray_flags=S.TRANSPARENT_CAMERA_JITTER if args.taa else 0, frame_index=frame)
             if bloom:
                 bloom.record(w, h)  # in place
             if args.taa:
@@ -142,6 +157,10 @@ def main():
             info = ctx.bloom_info()
             print("bloom: threshold %.3f, working extent %dx%d, streak half-width %d" % (
                 args.bloom_threshold, info.workingWidth, info.workingHeight, info.streakHalfWidth), file=sys.stderr)
+        if forward:
+            info = ctx.transparent_info()
+            print("transparents: %d pixels with layers, %d layers, deepest %d, last pass %.3f ms" % (
+                info.coveredPixels, info.totalLayers, info.maxLayers, info.ms), file=sys.stderr)
         if args.taa:
             info = ctx.taa_info()
             print("taa: %d frames, last resolve %.3f ms + expand %.3f ms" % (args.frames, info.resolveMs, info.expandMs), file=sys.stderr)
