@@ -182,6 +182,21 @@ int prosper_host_forward_renderer_record_transparent(
     const float *nonLinearDepth, uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType,
     void *stream, prosper_pt_forward_pc *outPushConstants);
 
+/* render::particles::Particles (host/particles.hpp; reference src/render/particles/Particles.hpp) on a context
+ * (borrowed): record = Camera::updateBuffer + prosper_pt_particles with every stage, over the context's HDR image and
+ * `nonLinearDepth` (device, or NULL: the last traced G-buffer's).  It keeps m_resetParticles (true at first, cleared only
+ * when init was recorded) and the two frame indices; *outPushConstants (may be NULL) receives what it pushed,
+ * *outInitRecorded (may be NULL) whether init was recorded.  set_source / set_max_particle_count: the draw instance the
+ * emitters come from (default 0) and the pool's size (0: 500 000). */
+typedef struct prosper_host_particles prosper_host_particles;
+int prosper_host_particles_create(prosper_pt_ctx *ctx, prosper_host_particles **out);
+void prosper_host_particles_destroy(prosper_host_particles *pass);
+void prosper_host_particles_set_source(prosper_host_particles *pass, uint32_t sourceDrawInstanceIndex);
+void prosper_host_particles_set_max_particle_count(prosper_host_particles *pass, uint32_t maxParticleCount);
+int prosper_host_particles_record(
+    prosper_host_particles *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, float *nonLinearDepth,
+    float deltaTimeS, void *stream, prosper_pt_particles_pc *outPushConstants, uint32_t *outInitRecorded);
+
 /* render::dof::DepthOfField (host/depth_of_field.hpp; reference src/render/dof/DepthOfField.hpp) on a context
  * (borrowed): record = Camera::updateBuffer + prosper_pt_depth_of_field with the push constants computed from the
  * camera's aperture, focus distance and focal length as dof/Setup.cpp and dof/Dilate.cpp compute them; returns them. */

@@ -766,6 +766,88 @@ int prosper_pt_read_transparent_layers(
     prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels,
     uint32_t layersPerPixel, void *stream);
 
+/* ---- particles (src/render/particles/, res/shader/particles/) ----
+ * What prosper runs between bloom and TAA (Renderer.cpp:530-538): a pool of maxParticleCount
+ * prosper_pt_particle records and a freelist of its dead slots (int32 count, int32 indices[max]), both owned by the
+ * context and resident on the device across frames and scenes.  Additive: the ABI version stays 4.
+ *
+ * prosper_pt_particles runs, on `stream`, the stages `stages` names, in Particles::record's order:
+ *   1. decay    decay.comp: a slot with the Decay bit and lifetime <= 0 - with pc->reset every slot that is not dead -
+ *               becomes (-9999) x 4 and its index is pushed on the freelist;
+ *   2. init     only with pc->reset: init.comp, one emitter per vertex of the mesh of draw instance
+ *               pc->sourceDrawInstanceIndex (position and normal through the instance's transform, lifetime 0, spawn
+ *               rate 0.1 s, mask Emit), each in a slot popped from the freelist.  A source mesh that is not loaded yet
+ *               (bufferIndex == PROSPER_PT_ABSENT or indexCount == 0) skips the stage, as Init::record returns false:
+ *               the call succeeds and prosper_pt_particles_info.initRecorded is 0;
+ *   3. simulate simulate.comp per slot with rng (slot, slot % 256, pc->simulateFrameIndex): move, gravity, decay of
+ *               the lifetime, and for an emitter the random push, the 0.05 speed clamp and, every spawn rate, a child
+ *               (lifetime 4, Gravity | Decay) in a popped slot.  A child is never simulated in the step that spawned
+ *               it.  With deltaTimeS == 0 an emitter's velocity can become 0 / 0, as in the reference;
+ *   4. render   render.vert / render.frag as a compute rasteriser, in place over the context's HDR image AND the depth:
+ *               one camera-facing quad of +-0.001 per live slot (lifetime >= 0), yellow (1, 1, 0, 1) for an emitter,
+ *               otherwise magenta (1, 0, 1, 1) with the dithered fade saturate(lifetime * 4) against sBayerMatrix
+ *               shifted by pc->renderFrameIndex (% 8 the column, / 8 the row), depth-tested strictly greater (reverse
+ *               Z) against the stored depth and written to it.  Coverage: corners snapped to 1/256 pixel, the strip's
+ *               triangles (0, 1, 2) and (2, 1, 3), pixel centres, top-left rule, back faces culled; the quad's depth is
+ *               z / w of its centre.  Among equal depths the lowest slot wins.  Untouched pixels keep colour and depth
+ *               bit for bit.
+ * A pop that finds the freelist dry is refused lane by lane: a launch with k requesters and c free slots grants exactly
+ * min(k, c), and the count is never negative when a call returns (DESIGN.md f13 says how this differs from the
+ * reference's dry case).
+ *
+ * pc->maxParticleCount: the pool's size, 0 = prosper's 500 000; a call with another size than the pool's reallocates it
+ * fresh (every slot dead, count = max, indices[i] = i), as does the first call.  `camera`, `width`, `height`,
+ * `nonLinearDepth` are read by render only.  `nonLinearDepth` NULL: the last traced G-buffer's depth, whose extent must
+ * be width x height; otherwise DEVICE memory, width * height floats - the pass writes it, so host memory is refused.
+ * Refused before anything is launched: unknown stage bits; reset not 0 or 1; with init requested (the INIT bit and
+ * pc->reset) no scene, or sourceDrawInstanceIndex out of range; with render requested no camera, an empty extent or one
+ * that differs from the HDR image's. */
+typedef struct prosper_pt_particles_pc
+{
+    uint32_t maxParticleCount;        /* 0: 500 000 */
+    uint32_t sourceDrawInstanceIndex; /* InitPC.drawInstanceIndex */
+    uint32_t reset;                   /* DecayPC.decayAll, and init runs */
+    float deltaTimeS;                 /* SimulatePC.deltaTimeS */
+    uint32_t simulateFrameIndex;      /* SimulatePC.frameIndex */
+    uint32_t renderFrameIndex;        /* RenderPC.frameIndex */
+} prosper_pt_particles_pc;
+enum
+{
+    PROSPER_PT_PARTICLES_DECAY = 1u << 0,
+    PROSPER_PT_PARTICLES_INIT = 1u << 1,
+    PROSPER_PT_PARTICLES_SIMULATE = 1u << 2,
+    PROSPER_PT_PARTICLES_RENDER = 1u << 3,
+    PROSPER_PT_PARTICLES_ALL = 15u,
+};
+int prosper_pt_particles(
+    prosper_pt_ctx *ctx, const prosper_pt_particles_pc *pc, uint32_t stages, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, float *nonLinearDepth, void *stream);
+typedef struct prosper_pt_particles_info
+{
+    uint32_t valid;            /* 1 once prosper_pt_particles ran on the current pool; the rest is of its last call */
+    uint32_t initRecorded;     /* 1: init ran (0: not requested, or the source mesh is not loaded yet) */
+    uint32_t maxParticleCount; /* of the pool */
+    uint32_t liveCount;        /* maxParticleCount - freelistCount */
+    uint32_t freelistCount;    /* the freelist's count behind the call */
+    uint32_t grantedSpawns;    /* children simulate placed */
+    uint32_t refusedSpawns;    /* ... and spawns it refused because the freelist was dry */
+    uint32_t fragmentsWritten; /* pixels render wrote */
+    float decayMs, initMs, simulateMs, renderMs; /* device time per stage (0 for a stage that did not run) */
+} prosper_pt_particles_info;
+/* Of the last prosper_pt_particles (waits for it). */
+int prosper_pt_get_particles_info(prosper_pt_ctx *ctx, prosper_pt_particles_info *out);
+/* Synchronises `stream` and copies the pool to host memory: `particles` maxParticleCount records, `freelist`
+ * 1 + maxParticleCount int32 (the count, then the indices); either may be NULL.  maxParticleCount must be the pool's (0:
+ * 500 000).  NO_SCENE before there is a pool. */
+int prosper_pt_read_particles(
+    prosper_pt_ctx *ctx, prosper_pt_particle *particles, int32_t *freelist, uint32_t maxParticleCount, void *stream);
+/* Uploads a caller's pool of maxParticleCount slots (reallocating one of another size) and returns when the arrays have
+ * been read: for tests that place designed states.  The count must lie in [0, maxParticleCount] and every one of the
+ * maxParticleCount indices in [0, maxParticleCount): the kernels index the pool with them. */
+int prosper_pt_set_particles(
+    prosper_pt_ctx *ctx, const prosper_pt_particle *particles, const int32_t *freelist, uint32_t maxParticleCount,
+    void *stream);
+
 /* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
  * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.
  *

@@ -15,6 +15,7 @@
  *   Directional/Point/SpotLight res/shader/shared/shader_structs/scene/lights.h:16-33
  *   PointLights/SpotLights SSBO res/shader/scene/lights.glsl:11-23, src/scene/Light.hpp:27-59
  *   DrawType                    src/scene/DrawType.hpp:8-10
+ *   Particle                    res/shader/shared/shader_structs/particles/particle.h:26-35
  */
 #ifndef PROSPER_PT_SHADER_STRUCTS_H
 #define PROSPER_PT_SHADER_STRUCTS_H
@@ -197,6 +198,25 @@ typedef struct prosper_SpotLightsBuffer
  * trailing count to the struct's 4-byte alignment, which is the same number. */
 PROSPER_PT_STATIC_ASSERT(sizeof(prosper_PointLightsBuffer) == 32772, "PointLights SSBO is 32772 B");
 PROSPER_PT_STATIC_ASSERT(sizeof(prosper_SpotLightsBuffer) == 49156, "SpotLights SSBO is 49156 B");
+
+/* particles/particle.h:11-35.  A dead slot's position_lifetime is (-9999) x 4 (the struct's default). */
+enum
+{
+    PROSPER_PARTICLE_MASK_GRAVITY = 1u << 0,
+    PROSPER_PARTICLE_MASK_DECAY = 1u << 1,
+    PROSPER_PARTICLE_MASK_EMIT = 1u << 2,
+};
+typedef struct prosper_pt_particle
+{
+    prosper_vec4 position_lifetime;
+    prosper_vec4 normal_spawnRateS;
+    prosper_vec4 velocity_spawnTimerS;
+    uint32_t mask; /* PROSPER_PARTICLE_MASK_* */
+    uint32_t _pad0;
+    uint32_t _pad1;
+    uint32_t _pad2;
+} prosper_pt_particle;
+PROSPER_PT_STATIC_ASSERT(sizeof(prosper_pt_particle) == 64, "Particle is 64 B");
 
 /* RtReference::sMaxBounces (src/render/RtReference.hpp:22) = MAX_BOUNCES in main.rgen:241. */
 #define PROSPER_RT_MAX_BOUNCES 6

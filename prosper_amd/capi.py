@@ -101,6 +101,10 @@ def lib():
     L.prosper_pt_get_transparent_info.argtypes = [vp, C.POINTER(S.TransparentInfo)]
     L.prosper_pt_set_transparent_debug_layers.argtypes = [vp, u32]
     L.prosper_pt_read_transparent_layers.argtypes = [vp, vp, vp, C.c_size_t, u32, vp]
+    L.prosper_pt_particles.argtypes = [vp, C.POINTER(S.ParticlesPC), u32, C.POINTER(S.CameraUniforms), u32, u32, vp, vp]
+    L.prosper_pt_get_particles_info.argtypes = [vp, C.POINTER(S.ParticlesInfo)]
+    L.prosper_pt_read_particles.argtypes = [vp, vp, vp, u32, vp]
+    L.prosper_pt_set_particles.argtypes = [vp, vp, vp, u32, vp]
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
     L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
     L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
@@ -227,6 +231,15 @@ def lib():
     L.prosper_host_forward_renderer_destroy.restype = None
     L.prosper_host_forward_renderer_record_transparent.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, C.c_int, u32, vp,
                                                                    C.POINTER(S.ForwardPC)]
+    L.prosper_host_particles_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_particles_destroy.argtypes = [vp]
+    L.prosper_host_particles_destroy.restype = None
+    L.prosper_host_particles_set_source.argtypes = [vp, u32]
+    L.prosper_host_particles_set_source.restype = None
+    L.prosper_host_particles_set_max_particle_count.argtypes = [vp, u32]
+    L.prosper_host_particles_set_max_particle_count.restype = None
+    L.prosper_host_particles_record.argtypes = [vp, vp, u32, u32, vp, C.c_float, vp, C.POINTER(S.ParticlesPC),
+                                                C.POINTER(u32)]
     L.prosper_host_depth_of_field_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_depth_of_field_destroy.argtypes = [vp]
     L.prosper_host_depth_of_field_destroy.restype = None
@@ -770,6 +783,44 @@ class Context:
         _check(lib().prosper_pt_read_transparent_layers(self._h, counts.ctypes.data, layers.ctypes.data, w * h, n,
                                                         C.c_void_p(stream)))
         return counts, layers
+
+    # ---- particles (prosper_pt_particles) ----
+
+    def particles(self, pc, stages=S.PARTICLES_ALL, camera=None, width=0, height=0, depth_ptr=None, stream=None):
+        """particles::Particles::record (prosper_pt_particles): the stages `stages` names (S.PARTICLES_DECAY | _INIT |
+        _SIMULATE | _RENDER) of the push constants `pc` (S.ParticlesPC) over the context's pool and freelist; render
+        works in place over the HDR image and the depth.  `depth_ptr`: a device pointer the pass reads AND writes;
+        None: the last traced G-buffer's depth.  `camera`, `width`, `height`: read by render only."""
+        self._sync_debug()
+        cam = None if camera is None else C.byref(camera)
+        _check(lib().prosper_pt_particles(self._h, C.byref(pc), stages, cam, width, height, C.c_void_p(depth_ptr),
+                                          C.c_void_p(stream)))
+        self._particles_max = pc.maxParticleCount
+
+    def particles_info(self):
+        """S.ParticlesInfo of the last particles() (waits for it)."""
+        info = S.ParticlesInfo()
+        _check(lib().prosper_pt_get_particles_info(self._h, C.byref(info)))
+        return info
+
+    def read_particles(self, stream=None):
+        """The pool as the device holds it: (records [max] of S.PARTICLE_DTYPE, count, indices int32 [max])."""
+        asked = getattr(self, "_particles_max", 0)
+        n = asked or S.MAX_PARTICLE_COUNT
+        records = np.empty(n, S.PARTICLE_DTYPE)
+        freelist = np.empty(n + 1, np.int32)
+        _check(lib().prosper_pt_read_particles(self._h, records.ctypes.data, freelist.ctypes.data, asked, C.c_void_p(stream)))
+        return records, int(freelist[0]), freelist[1:]
+
+    def set_particles(self, records, count, indices, stream=None):
+        """prosper_pt_set_particles: a designed pool.  `records` [max] of S.PARTICLE_DTYPE, `count` free slots, `indices`
+        int32 [max] (all of them inside the pool; the first `count` are the free ones)."""
+        rec = np.ascontiguousarray(records, S.PARTICLE_DTYPE)
+        idx = np.ascontiguousarray(indices, np.int32)
+        assert rec.ndim == 1 and idx.shape == rec.shape
+        freelist = np.concatenate([np.array([count], np.int32), idx])
+        _check(lib().prosper_pt_set_particles(self._h, rec.ctypes.data, freelist.ctypes.data, rec.size, C.c_void_p(stream)))
+        self._particles_max = rec.size
 
     def generate_ibl(self, stream=None):
         """ImageBasedLighting::recordGeneration (prosper_pt_generate_ibl): the irradiance and radiance cubes and the BRDF

@@ -786,7 +786,8 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         if ((rc = ctx->chainFork.record(ws.get()))) return rc;
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
-    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx))
+    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
+        !create_particles_passes(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -845,6 +846,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_dof_passes(ctx);
     destroy_bloom_passes(ctx);
     destroy_taa_passes(ctx);
+    destroy_particles_passes(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 

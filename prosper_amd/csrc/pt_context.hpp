@@ -77,6 +77,11 @@ bool create_taa_passes(prosper_pt_ctx *ctx);
 void destroy_taa_passes(prosper_pt_ctx *ctx);
 // a new scene, or TemporalAntiAliasing::releasePreserved: the next resolve ignores the history
 void forget_taa_history(prosper_pt_ctx *ctx);
+// State of the particle system (pt_particles_passes.cpp): the pool, its freelist and the render's per-pixel keys, which
+// live across frames and scenes.  Made and freed like the others.
+struct ParticlesPassState;
+bool create_particles_passes(prosper_pt_ctx *ctx);
+void destroy_particles_passes(prosper_pt_ctx *ctx);
 
 #pragma GCC visibility pop
 
@@ -301,6 +306,7 @@ struct prosper_pt_ctx
     ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
     ppt::BloomPassState *bloomPasses = nullptr;
     ppt::TaaPassState *taaPasses = nullptr;
+    ppt::ParticlesPassState *particlesPasses = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

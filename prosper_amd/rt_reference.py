@@ -408,6 +408,43 @@ class ForwardRenderer:
             pass
 
 
+class Particles:
+    """render::particles::Particles (csrc/host/particles.hpp) on a Context: record runs decay, init while a reset is
+    pending, simulate and render over the context's HDR image and the depth; returns (S.ParticlesPC pushed, init recorded)."""
+
+    def __init__(self, ctx, source_draw_instance=0, max_particle_count=0):
+        h = C.c_void_p()
+        rc = lib().prosper_host_particles_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+        lib().prosper_host_particles_set_source(h, source_draw_instance)
+        lib().prosper_host_particles_set_max_particle_count(h, max_particle_count)
+        ctx._particles_max = max_particle_count
+
+    def record(self, camera, width, height, delta_time_s, depth_ptr=None, stream=None):
+        """`depth_ptr`: a device pointer the pass reads and writes; None: the last traced G-buffer's depth."""
+        pc = S.ParticlesPC()
+        recorded = C.c_uint32()
+        rc = lib().prosper_host_particles_record(self._h, camera._h, width, height, C.c_void_p(depth_ptr), delta_time_s,
+                                                 C.c_void_p(stream), C.byref(pc), C.byref(recorded))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return pc, bool(recorded.value)
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_particles_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DepthOfField:
     """render::dof::DepthOfField (csrc/host/depth_of_field.hpp) on a Context: record computes the push constants from the
     camera's aperture, focus distance and focal length and runs the seven passes into the context's HDR image

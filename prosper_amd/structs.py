@@ -392,6 +392,41 @@ class TransparentLayer(C.Structure):
                 ("normal", C.c_float * 3), ("metallic", C.c_float), ("alpha", C.c_float), ("reserved", C.c_uint32)]
 
 
+class Particle(C.Structure):
+    """prosper_pt_particle == Particle, res/shader/shared/shader_structs/particles/particle.h (64 bytes)"""
+    _fields_ = [("position_lifetime", Vec4), ("normal_spawnRateS", Vec4), ("velocity_spawnTimerS", Vec4),
+                ("mask", C.c_uint32), ("_pad0", C.c_uint32), ("_pad1", C.c_uint32), ("_pad2", C.c_uint32)]
+
+
+# the same record as a NumPy structured dtype (what Context.read_particles returns)
+PARTICLE_DTYPE = np.dtype([("position_lifetime", np.float32, 4), ("normal_spawnRateS", np.float32, 4),
+                           ("velocity_spawnTimerS", np.float32, 4), ("mask", np.uint32), ("_pad", np.uint32, 3)])
+PARTICLE_MASK_GRAVITY = 1 << 0
+PARTICLE_MASK_DECAY = 1 << 1
+PARTICLE_MASK_EMIT = 1 << 2
+PARTICLE_DEAD = -9999.0            # a dead slot's position_lifetime, all four
+MAX_PARTICLE_COUNT = 500000        # Particles.hpp sMaxParticleCount: what maxParticleCount 0 means
+PARTICLES_DECAY = 1 << 0           # prosper_pt_particles stages
+PARTICLES_INIT = 1 << 1
+PARTICLES_SIMULATE = 1 << 2
+PARTICLES_RENDER = 1 << 3
+PARTICLES_ALL = 15
+
+
+class ParticlesPC(C.Structure):
+    """prosper_pt_particles_pc: DecayPC, InitPC, SimulatePC and RenderPC of push_constants/particles/ in one"""
+    _fields_ = [("maxParticleCount", C.c_uint32), ("sourceDrawInstanceIndex", C.c_uint32), ("reset", C.c_uint32),
+                ("deltaTimeS", C.c_float), ("simulateFrameIndex", C.c_uint32), ("renderFrameIndex", C.c_uint32)]
+
+
+class ParticlesInfo(C.Structure):
+    """prosper_pt_particles_info of the last prosper_pt_particles"""
+    _fields_ = [("valid", C.c_uint32), ("initRecorded", C.c_uint32), ("maxParticleCount", C.c_uint32),
+                ("liveCount", C.c_uint32), ("freelistCount", C.c_uint32), ("grantedSpawns", C.c_uint32),
+                ("refusedSpawns", C.c_uint32), ("fragmentsWritten", C.c_uint32), ("decayMs", C.c_float),
+                ("initMs", C.c_float), ("simulateMs", C.c_float), ("renderMs", C.c_float)]
+
+
 class IblInfo(C.Structure):
     """prosper_pt_ibl_info: whether the maps exist for the current scene, their sizes, the last generation's pass times"""
     _fields_ = [("generated", C.c_uint32), ("irradianceSize", C.c_uint32), ("radianceSize", C.c_uint32),

@@ -24,6 +24,12 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
                                  defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573);
                                  --bloom-fft: the FFT technique (prosper_pt_bloom_fft) instead of the multi-resolution blur
+    --deferred --particles [--particle-source N] [--particle-steps K]
+                                 prosper's particle system (prosper_pt_particles) between bloom and TAA
+                                 (Renderer.cpp:530-538): one emitter per vertex of draw instance N's mesh (default 0), K
+                                 steps (default 120) at 1/60 s of decay / simulate before the first frame, then every
+                                 frame one more step and the quads drawn into the image and the depth, which TAA and
+                                 depth of field then read
     --deferred --taa [--frames N]
                                  temporal anti-aliasing: N frames (8, one Halton cycle) of jittered camera -> velocity
                                  G-buffer -> shading -> sky -> bloom -> prosper_pt_taa_resolve -> Camera::endFrame, through
@@ -79,6 +85,9 @@ def main():
     ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
     ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
     ap.add_argument("--bloom-fft", action="store_true", help="with --bloom: the FFT technique instead of the multi-resolution blur")
+    ap.add_argument("--particles", action="store_true", help="with --deferred: the particle system, between bloom and TAA")
+    ap.add_argument("--particle-source", type=int, default=0, help="with --particles: the draw instance whose vertices emit")
+    ap.add_argument("--particle-steps", type=int, default=120, help="with --particles: steps of 1/60 s before the first frame")
     ap.add_argument("--taa", action="store_true", help="with --deferred: temporal anti-aliasing over jittered frames")
     ap.add_argument("--frames", type=int, default=8, help="with --taa: frames to resolve (8 is one Halton cycle)")
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
@@ -87,8 +96,8 @@ def main():
     args = ap.parse_args()
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
-    if (args.sky or args.dof or args.bloom or args.taa or args.transparents) and not args.deferred:
-        ap.error("--sky, --transparents, --bloom, --taa and --dof belong to --deferred")
+    if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles) and not args.deferred:
+        ap.error("--sky, --transparents, --bloom, --particles, --taa and --dof belong to --deferred")
     if args.frames < 1:
         ap.error("--frames must be at least 1")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
@@ -128,6 +137,12 @@ def main():
             hcam.set_jitter(True)
             taa = TemporalAntiAliasing(ctx)
             transforms = world.freeze()["transforms"]
+        particle_step = 0
+        if args.particles:
+            # Particles::record without its render, K times: the reset step makes the emitters, the rest ages them
+            for particle_step in range(1, args.particle_steps + 1):
+                ppc = S.ParticlesPC(0, args.particle_source, 1 if particle_step == 1 else 0, 1.0 / 60.0, particle_step, 0)
+                ctx.particles(ppc, S.PARTICLES_DECAY | S.PARTICLES_INIT | S.PARTICLES_SIMULATE)
         for frame in range(args.frames if args.taa else 1):
             if args.taa:
                 # the G-buffer through the jittered projection's pixel centres, with the velocity the resolve reads
@@ -146,6 +161,11 @@ def main():
                 forward.record_transparent(hcam, w, h, ray_flags=S.TRANSPARENT_CAMERA_JITTER if args.taa else 0, frame_index=frame)
             if bloom:
                 bloom.record(w, h)  # in place
+            if args.particles:
+                # in place over the illumination and the traced G-buffer's depth (Renderer.cpp:530-538)
+                particle_step += 1
+                ppc = S.ParticlesPC(0, args.particle_source, 1 if particle_step == 1 else 0, 1.0 / 60.0, particle_step, particle_step % 64)
+                ctx.particles(ppc, S.PARTICLES_ALL, cam, w, h)
             if args.taa:
                 taa.record(w, h)  # in place, over the traced velocity and depth
                 hcam.end_frame()
@@ -161,6 +181,10 @@ def main():
             info = ctx.transparent_info()
             print("transparents: %d pixels with layers, %d layers, deepest %d, last pass %.3f ms" % (
                 info.coveredPixels, info.totalLayers, info.maxLayers, info.ms), file=sys.stderr)
+        if args.particles:
+            info = ctx.particles_info()
+            print("particles: %d live of %d, %d fragments written, last step decay %.3f + simulate %.3f + render %.3f ms" % (
+                info.liveCount, info.maxParticleCount, info.fragmentsWritten, info.decayMs, info.simulateMs, info.renderMs), file=sys.stderr)
         if args.taa:
             info = ctx.taa_info()
             print("taa: %d frames, last resolve %.3f ms + expand %.3f ms" % (args.frames, info.resolveMs, info.expandMs), file=sys.stderr)
