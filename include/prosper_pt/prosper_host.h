@@ -115,6 +115,11 @@ void prosper_host_gbuffer_tracer_destroy(prosper_host_gbuffer_tracer *pass);
 /* GBufferTracer::setOpaqueOnly: both records leave BLEND surfaces out (PROSPER_PT_GBUFFER_OPAQUE_ONLY), for
  * prosper_host_forward_renderer_record_transparent to draw.  Off by default. */
 int prosper_host_gbuffer_tracer_set_opaque_only(prosper_host_gbuffer_tracer *pass, int opaqueOnly);
+/* GBufferTracer::setTextureLod / setLodBias: later records sample material textures through their mip chains
+ * (prosper_pt_set_texture_lod) with `lodBias`; prosper_host_renderer_lod_bias is Renderer::lodBias(): -1 while TAA is
+ * applied, otherwise 0. */
+int prosper_host_gbuffer_tracer_set_texture_lod(prosper_host_gbuffer_tracer *pass, int enabled, float lodBias);
+float prosper_host_renderer_lod_bias(int applyTaa);
 int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
     uint32_t frameIndex, int jitter, void *stream, prosper_pt_restir_inputs *outGBuffer);
@@ -177,6 +182,8 @@ int prosper_host_skybox_renderer_record(
 typedef struct prosper_host_forward_renderer prosper_host_forward_renderer;
 int prosper_host_forward_renderer_create(prosper_pt_ctx *ctx, prosper_host_forward_renderer **out);
 void prosper_host_forward_renderer_destroy(prosper_host_forward_renderer *pass);
+/* ForwardRenderer::setTextureLod / setLodBias: later records sample every layer's material through the mip chains. */
+int prosper_host_forward_renderer_set_texture_lod(prosper_host_forward_renderer *pass, int enabled, float lodBias);
 int prosper_host_forward_renderer_record_transparent(
     prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const float *nonLinearDepth, uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType,

@@ -80,6 +80,11 @@ enum
     /* run the wavefront pipeline as ONE chain of launches on the caller's stream instead of two
      * half-batches on two internal streams (A/B switch; the two-chain default hides launch tails) */
     PROSPER_PT_CREATE_SINGLE_CHAIN = 1u << 2,
+    /* every material texture gets a mip chain at prosper_pt_upload_scene / prosper_pt_update_textures (generated on the
+     * GPU, or taken from the caller: prosper_pt_texture_desc.mipLevelCount), kept beside its level 0 for
+     * sample_texture_lod ("texture mip chains" below).  Without the flag nothing about textures changes and
+     * mipLevelCount is not read. */
+    PROSPER_PT_CREATE_TEXTURE_MIPS = 1u << 3,
 };
 
 /* Texel formats of material textures (reference: src/scene/Texture.cpp:217-296 stores UNORM,
@@ -105,15 +110,20 @@ enum
     PROSPER_PT_WRAP_CLAMP_TO_EDGE = 2,
 };
 
-/* One entry of the bindless materialTextures[] table (materials.glsl:23-24); mip 0 only, because
- * RT stages have no derivatives and sample LOD 0. Index 0 is the "no texture" slot. */
+/* One entry of the bindless materialTextures[] table (materials.glsl:23-24).  RT stages have no derivatives and sample
+ * LOD 0: level 0 is all they read.  Index 0 is the "no texture" slot.
+ * mipLevelCount (the former `reserved`) is read only by a context created with PROSPER_PT_CREATE_TEXTURE_MIPS:
+ *   0 or 1   `texels` is level 0; the library generates the other levels of prosper's chain
+ *            (max(floor(log2(max(w, h))) + 1 - 2, 1) levels of extent max(extent >> l, 1), src/scene/Texture.cpp:217-225)
+ *   n > 1    `texels` holds n levels back to back as prosper's texture cache lays them out (src/utils/Dds.cpp:100-135;
+ *            BC7 levels in whole 4x4 blocks); they are taken as they are.  n above prosper's count is refused. */
 typedef struct prosper_pt_texture_desc
 {
     const void *texels; /* RGBA8: width*height texels, row-major, tightly packed; BC7: the level's blocks */
     uint32_t width;
     uint32_t height;
     uint32_t format; /* PROSPER_PT_FORMAT_* */
-    uint32_t reserved;
+    uint32_t mipLevelCount;
 } prosper_pt_texture_desc;
 
 /* One entry of materialSamplers[] (src/scene/WorldData.cpp:681-720); index 0 = repeat/linear. */
@@ -383,6 +393,58 @@ int prosper_pt_update_transforms_async(
  * changed MASK / BLEND material rewrites the any-hit records in place, behind the frames in flight.)  Every frame shows the
  * scene a fresh prosper_pt_upload_scene of that state would show, bit for bit. */
 int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_desc *textures, uint32_t first, uint32_t count);
+
+/* ---- texture mip chains (PROSPER_PT_CREATE_TEXTURE_MIPS) ----
+ * prosper's raster passes sample material textures through full mip chains (materials.glsl:40-45).  A context created
+ * with the flag keeps levels >= 1 of every texture beside its level 0, in the same tiling, also where level 0 itself
+ * lives only in a material pack.  A generated level is the 2 x 2 box of its parent - child (i, j) = mean of parent
+ * (2i, min(2i + 1, pw - 1)) x (2j, min(2j + 1, ph - 1)) - as (a + b + c + d + 2) >> 2 per channel; a texture that some
+ * material uses as base colour (at the time its texels arrive) has RGB averaged in linear light instead: the device's
+ * srgb_to_linear of the four codes, ((l00 + l10) + (l01 + l11)) * 0.25 in float32, and back to the code whose
+ * srgb_to_linear(c / 255) is nearest (ties to the lower code).
+ * The ray-traced passes go on sampling LOD 0. */
+typedef struct prosper_pt_texture_mips_info
+{
+    uint32_t width, height;  /* level 0 of `texture` */
+    uint32_t levelCount;     /* levels of its chain, level 0 included (1: no further level) */
+    uint32_t srgbAveraged;   /* its generated levels were averaged in linear light */
+    uint64_t mipTexelBytes;  /* the whole scene: texel bytes of all levels >= 1 (4 B per texel, without tile padding) */
+} prosper_pt_texture_mips_info;
+/* prosper's level count for an extent: max(floor(log2(max(w, h))) + 1 - 2, 1); 0 for an empty extent. */
+uint32_t prosper_pt_texture_mip_level_count(uint32_t width, uint32_t height);
+/* What prosper_pt_upload_scene / prosper_pt_update_textures of a context created with `create_flags` say about one
+ * descriptor (PROSPER_PT_OK, or the refusal with its message in prosper_pt_last_error).  Touches no device. */
+int prosper_pt_check_texture_desc(const prosper_pt_texture_desc *desc, uint32_t create_flags);
+/* PROSPER_PT_ERR_UNSUPPORTED on a context created without PROSPER_PT_CREATE_TEXTURE_MIPS. */
+int prosper_pt_get_texture_mips_info(prosper_pt_ctx *ctx, uint32_t texture, prosper_pt_texture_mips_info *out);
+/* Test hook: level `level` of `texture` un-tiled into `rgba8` (max(w >> level, 1) * max(h >> level, 1) * 4 = `bytes`
+ * bytes, row-major).  Level 0 of a texture that lives only in a material pack is PROSPER_PT_ERR_UNSUPPORTED.
+ * Enqueued on `stream` and waited for. */
+int prosper_pt_read_texture_level(prosper_pt_ctx *ctx, uint32_t texture, uint32_t level, void *rgba8, uint64_t bytes, void *stream);
+/* Test hook: sample_texture_lod over n records.  in6: (u, v, du/dx, dv/dx, du/dy, dv/dy) per record, the uv forward
+ * differences towards the pixel's right and lower neighbour; out5: (R, G, B, A, lambda).
+ *   rho_x = |(du/dx * w, dv/dx * h)|, rho_y likewise, lambda = log2(max(rho_x, rho_y)) + bias   (Vulkan 1.3 §16.5.7, no
+ *   anisotropy, lambda kept in float); an inf / NaN derivative gives +inf (the last level), rho = 0 gives -inf.
+ *   lambda <= 0: the LOD-0 sample as every other pass takes it (magFilter), bit for bit.
+ *   lambda > 0: levels floor(lambda) and min(floor(lambda) + 1, last), each through minFilter and the wrap modes,
+ *   blended by the fraction. */
+int prosper_pt_debug_sample_texture_lod(
+    prosper_pt_ctx *ctx, uint32_t texture, uint32_t sampler, const float *in6, uint32_t n, float bias, float *out5);
+/* The traced G-buffer (prosper_pt_trace_gbuffer, prosper_pt_trace_gbuffer_velocity, and the records that trace one) samples
+ * material textures through their mip chains: context state, the counterpart of the lodBias prosper writes with its
+ * material buffer each frame (Renderer::lodBias(): -1 while TAA is on, otherwise 0).  The uv derivatives are the forward
+ * differences a rasteriser's quad would see: the pinhole rays through (px + 1, py) and (px, py + 1), with the pixel's
+ * own jitter offset, met with the hit triangle's plane (a ray parallel to it or meeting it behind the eye: inf, the last
+ * level).  The hit, depth, velocity and every debug draw type that does not show the material are unchanged.  Default:
+ * off.  Refused: a lodBias that is not finite; enabling on a context created without PROSPER_PT_CREATE_TEXTURE_MIPS
+ * (PROSPER_PT_ERR_UNSUPPORTED).  prosper_pt_forward_transparent follows the same state: every peeled layer is sampled
+ * with the same two neighbour rays, met with the layer's own triangle plane.  The path tracer samples LOD 0. */
+int prosper_pt_set_texture_lod(prosper_pt_ctx *ctx, int enabled, float lodBias);
+/* Test hook: with it (and texture LOD on) the next traced G-buffer also writes, per pixel, the float4
+ * (du/dx, dv/dx, du/dy, dv/dy) it sampled with, zeros on a miss; prosper_pt_read_texture_lod_derivatives copies it out
+ * (width * height * 16 bytes). */
+int prosper_pt_set_texture_lod_debug(prosper_pt_ctx *ctx, int enabled);
+int prosper_pt_read_texture_lod_derivatives(prosper_pt_ctx *ctx, float *out, size_t bytes, void *stream);
 int prosper_pt_update_materials(prosper_pt_ctx *ctx, const prosper_MaterialData *materials, uint32_t first, uint32_t count);
 
 /* ---- incremental adoption: streamed-in meshes ----

@@ -60,6 +60,15 @@ def lib():
     L.prosper_pt_get_scene_stats.argtypes = [vp, C.POINTER(S.SceneStats)]
     L.prosper_pt_update_textures.argtypes = [vp, vp, u32, u32]
     L.prosper_pt_update_materials.argtypes = [vp, vp, u32, u32]
+    L.prosper_pt_texture_mip_level_count.argtypes = [u32, u32]
+    L.prosper_pt_texture_mip_level_count.restype = u32
+    L.prosper_pt_check_texture_desc.argtypes = [C.POINTER(S.TextureDesc), u32]
+    L.prosper_pt_get_texture_mips_info.argtypes = [vp, u32, C.POINTER(S.TextureMipsInfo)]
+    L.prosper_pt_read_texture_level.argtypes = [vp, u32, u32, vp, C.c_uint64, vp]
+    L.prosper_pt_debug_sample_texture_lod.argtypes = [vp, u32, u32, vp, u32, C.c_float, vp]
+    L.prosper_pt_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
+    L.prosper_pt_set_texture_lod_debug.argtypes = [vp, C.c_int]
+    L.prosper_pt_read_texture_lod_derivatives.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_update_meshes.argtypes = [vp, vp, u32]
     L.prosper_pt_finish_mesh_updates.argtypes = [vp]
     L.prosper_pt_update_transforms.argtypes = [vp, vp, u32]
@@ -205,6 +214,9 @@ def lib():
     L.prosper_host_gbuffer_tracer_destroy.argtypes = [vp]
     L.prosper_host_gbuffer_tracer_destroy.restype = None
     L.prosper_host_gbuffer_tracer_set_opaque_only.argtypes = [vp, C.c_int]
+    L.prosper_host_gbuffer_tracer_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
+    L.prosper_host_renderer_lod_bias.argtypes = [C.c_int]
+    L.prosper_host_renderer_lod_bias.restype = C.c_float
     L.prosper_host_gbuffer_tracer_record.argtypes = [vp, vp, u32, u32, u32, u32, C.c_int, vp, C.POINTER(S.RestirInputs)]
     L.prosper_host_gbuffer_tracer_record_velocity.argtypes = [vp, vp, u32, u32, u32, u32, vp, u32, vp, C.POINTER(S.RestirInputs),
                                                               C.POINTER(vp)]
@@ -228,6 +240,7 @@ def lib():
     L.prosper_host_skybox_renderer_record.argtypes = [vp, vp, u32, u32, vp, u32, vp]
     L.prosper_host_forward_renderer_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_forward_renderer_destroy.argtypes = [vp]
+    L.prosper_host_forward_renderer_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
     L.prosper_host_forward_renderer_destroy.restype = None
     L.prosper_host_forward_renderer_record_transparent.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, C.c_int, u32, vp,
                                                                    C.POINTER(S.ForwardPC)]
@@ -446,18 +459,50 @@ class Context:
         self._world = world
 
     def update_textures(self, textures, first):
-        """Replaces materialTextures[first .. first + len(textures)): numpy [h, w, 4] uint8 arrays or world.Bc7Texture."""
+        """Replaces materialTextures[first .. first + len(textures)): numpy [h, w, 4] uint8 arrays, world.Bc7Texture or
+        world.TextureChain."""
+        from .world import fill_texture_desc
         self._sync_debug()
         descs = (S.TextureDesc * len(textures))()
-        keep = []
-        for i, t in enumerate(textures):
-            if hasattr(t, "blocks"):
-                descs[i].texels, descs[i].width, descs[i].height, descs[i].format = t.blocks.ctypes.data, t.width, t.height, S.FORMAT_BC7_UNORM
-                continue
-            a = np.ascontiguousarray(t, np.uint8)
-            keep.append(a)
-            descs[i].texels, descs[i].width, descs[i].height, descs[i].format = a.ctypes.data, a.shape[1], a.shape[0], S.FORMAT_RGBA8_UNORM
+        keep = [fill_texture_desc(descs[i], t) for i, t in enumerate(textures)]
         _check(lib().prosper_pt_update_textures(self._h, C.cast(descs, C.c_void_p), first, len(textures)))
+        del keep
+
+    def texture_mips_info(self, texture):
+        """structs.TextureMipsInfo of materialTextures[texture] (a CREATE_TEXTURE_MIPS context)."""
+        info = S.TextureMipsInfo()
+        _check(lib().prosper_pt_get_texture_mips_info(self._h, texture, C.byref(info)))
+        return info
+
+    def read_texture_level(self, texture, level, width, height, stream=None):
+        """Level `level` of materialTextures[texture] as the device holds it: uint8 [h, w, 4] of the LEVEL's extent,
+        derived from the level-0 extent given."""
+        w, h = max(width >> level, 1), max(height >> level, 1)
+        out = np.zeros((h, w, 4), np.uint8)
+        _check(lib().prosper_pt_read_texture_level(self._h, texture, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def set_texture_lod(self, enabled, lod_bias=0.0):
+        """The traced G-buffer samples materials through the mip chains (a CREATE_TEXTURE_MIPS context), with `lod_bias`."""
+        _check(lib().prosper_pt_set_texture_lod(self._h, int(bool(enabled)), lod_bias))
+
+    def set_texture_lod_debug(self, enabled):
+        _check(lib().prosper_pt_set_texture_lod_debug(self._h, int(bool(enabled))))
+
+    def read_texture_lod_derivatives(self, width, height, stream=None):
+        """float32 [h, w, 4] = (du/dx, dv/dx, du/dy, dv/dy) the last traced G-buffer sampled with (zeros on a miss)."""
+        out = np.zeros((height, width, 4), np.float32)
+        _check(lib().prosper_pt_read_texture_lod_derivatives(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def debug_sample_texture_lod(self, texture, sampler, records, bias=0.0):
+        """sample_texture_lod over float32 [n, 6] records (u, v, du/dx, dv/dx, du/dy, dv/dy) -> float32 [n, 5]
+        (R, G, B, A, lambda)."""
+        self._sync_debug()
+        rec = np.ascontiguousarray(records, np.float32).reshape(-1, 6)
+        out = np.zeros((rec.shape[0], 5), np.float32)
+        _check(lib().prosper_pt_debug_sample_texture_lod(self._h, texture, sampler, rec.ctypes.data, rec.shape[0], bias, out.ctypes.data))
+        return out
 
     def update_materials(self, materials, first):
         """Replaces MaterialData[first .. first + len(materials)) (structs.MaterialData)."""

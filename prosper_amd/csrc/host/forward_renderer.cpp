@@ -33,6 +33,8 @@ void ForwardRenderer::recordTransparent(
     pc.ibl = applyIbl ? 1u : 0u;
     m_lastPC = pc;
 
+    if (prosper_pt_set_texture_lod(m_ctx, m_textureLod ? 1 : 0, m_lodBias) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("ForwardRenderer::recordTransparent: ") + prosper_pt_last_error());
     if (prosper_pt_forward_transparent(
             m_ctx, &pc, t.rayFlags, t.frameIndex, &cam.uniforms(), t.width, t.height, t.depth, t.onDevice ? 1u : 0u, stream) !=
         PROSPER_PT_OK)
@@ -67,6 +69,18 @@ int prosper_host_forward_renderer_create(prosper_pt_ctx *ctx, prosper_host_forwa
 }
 
 void prosper_host_forward_renderer_destroy(prosper_host_forward_renderer *r) { delete r; }
+
+int prosper_host_forward_renderer_set_texture_lod(prosper_host_forward_renderer *r, int enabled, float lodBias)
+{
+    if (!r)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_set_texture_lod: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    r->pass.setTextureLod(enabled != 0);
+    r->pass.setLodBias(lodBias);
+    return PROSPER_PT_OK;
+}
 
 int prosper_host_forward_renderer_record_transparent(
     prosper_host_forward_renderer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, const float *nonLinearDepth,

@@ -49,10 +49,20 @@ class ForwardRenderer
     [[nodiscard]] prosper_pt_ctx *context() const { return m_ctx; }
     [[nodiscard]] const prosper_pt_forward_pc &lastPushConstants() const { return m_lastPC; }
 
+    // Every layer's material sampled through the textures' mip chains (prosper_pt_set_texture_lod, which the pass sets
+    // before each record; the context must have been created with PROSPER_PT_CREATE_TEXTURE_MIPS), with the bias
+    // prosper's forward pass is given each frame: GBufferTracer::lodBias(applyTaa).  Off, bias 0 by default.
+    void setTextureLod(bool enabled) { m_textureLod = enabled; }
+    void setLodBias(float lodBias) { m_lodBias = lodBias; }
+    [[nodiscard]] bool textureLod() const { return m_textureLod; }
+    [[nodiscard]] float lodBias() const { return m_lodBias; }
+
   private:
     bool m_initialized{false};
     prosper_pt_ctx *m_ctx{nullptr};
     prosper_pt_forward_pc m_lastPC{};
+    bool m_textureLod{false};
+    float m_lodBias{0.0f};
 };
 
 } // namespace render

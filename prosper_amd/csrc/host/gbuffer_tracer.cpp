@@ -21,11 +21,19 @@ void GBufferTracer::init(prosper_pt_ctx *ctx)
     m_initialized = true;
 }
 
+// the context's texture-LOD state is this pass's before each of its records (another user of the context may have set it)
+void GBufferTracer::applyTextureLod(const char *what) const
+{
+    if (prosper_pt_set_texture_lod(m_ctx, m_textureLod ? 1 : 0, m_lodBias) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string(what) + ": " + prosper_pt_last_error());
+}
+
 rtdi::GBuffer GBufferTracer::record(
     const scene::Camera &cam, uint32_t width, uint32_t height, scene::DrawType drawType, uint32_t frameIndex, bool jitter,
     void *stream)
 {
     PROSPER_ASSERT(m_initialized);
+    applyTextureLod("GBufferTracer::record");
     const uint32_t flags = (jitter ? PROSPER_PT_GBUFFER_JITTER : 0u) | (m_opaqueOnly ? PROSPER_PT_GBUFFER_OPAQUE_ONLY : 0u);
     if (prosper_pt_trace_gbuffer(
             m_ctx, static_cast<uint32_t>(drawType), frameIndex, flags, &cam.uniforms(), width, height, nullptr, stream) !=
@@ -49,6 +57,7 @@ GBufferTracer::VelocityGBuffer GBufferTracer::recordVelocity(
     const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream)
 {
     PROSPER_ASSERT(m_initialized);
+    applyTextureLod("GBufferTracer::recordVelocity");
     prosper_pt_velocity_gbuffer_desc desc = {};
     if (transforms && m_previousTransforms.size() == transformCount && transformCount != 0u)
     {
@@ -118,6 +127,20 @@ int prosper_host_gbuffer_tracer_set_opaque_only(prosper_host_gbuffer_tracer *r, 
     r->pass.setOpaqueOnly(opaqueOnly != 0);
     return PROSPER_PT_OK;
 }
+
+int prosper_host_gbuffer_tracer_set_texture_lod(prosper_host_gbuffer_tracer *r, int enabled, float lodBias)
+{
+    if (!r)
+    {
+        prosper_host_set_error("prosper_host_gbuffer_tracer_set_texture_lod: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    r->pass.setTextureLod(enabled != 0);
+    r->pass.setLodBias(lodBias);
+    return PROSPER_PT_OK;
+}
+
+float prosper_host_renderer_lod_bias(int applyTaa) { return render::GBufferTracer::lodBias(applyTaa != 0); }
 
 int prosper_host_gbuffer_tracer_record(
     prosper_host_gbuffer_tracer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,

@@ -33,6 +33,15 @@ class GBufferTracer
     void setOpaqueOnly(bool opaqueOnly) { m_opaqueOnly = opaqueOnly; }
     [[nodiscard]] bool opaqueOnly() const { return m_opaqueOnly; }
 
+    // Material textures sampled through their mip chains by both records (prosper_pt_set_texture_lod; the context must
+    // have been created with PROSPER_PT_CREATE_TEXTURE_MIPS), with the bias prosper writes beside its material buffer
+    // each frame: lodBias(applyTaa), Renderer::lodBias() (Renderer.cpp:709-715).  Off, bias 0 by default.
+    void setTextureLod(bool enabled) { m_textureLod = enabled; }
+    void setLodBias(float lodBias) { m_lodBias = lodBias; }
+    [[nodiscard]] bool textureLod() const { return m_textureLod; }
+    [[nodiscard]] float lodBias() const { return m_lodBias; }
+    [[nodiscard]] static float lodBias(bool applyTaa) { return applyTaa ? -1.0f : 0.0f; }
+
     // Traces the G-buffer for the camera's current uniforms (the caller has run Camera::updateBuffer) at the camera's
     // resolution `width` x `height`.  `jitter`: the path tracer's jittered sample of (px, py, frameIndex) instead of
     // the pixel centre.  The returned device pointers stay valid until the next record with a larger extent or the
@@ -61,6 +70,9 @@ class GBufferTracer
     bool m_initialized{false};
     prosper_pt_ctx *m_ctx{nullptr};
     bool m_opaqueOnly{false};
+    bool m_textureLod{false};
+    float m_lodBias{0.0f};
+    void applyTextureLod(const char *what) const;
     std::vector<prosper_ModelInstanceTransforms> m_previousTransforms;
 };
 

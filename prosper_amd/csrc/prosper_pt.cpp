@@ -148,11 +148,12 @@ void free_scene(prosper_pt_ctx *ctx)
     ctx->sceneBytes = 0;
     ctx->haveScene = false;
     ctx->scene = DeviceScene{};
+    ctx->textureMips = nullptr;
 }
 
 // Everything the kernels index with is range-checked here, so a malformed view can only fail the
 // upload, never fault the GPU.
-int validate_scene(const prosper_pt_scene_view *v)
+int validate_scene(const prosper_pt_scene_view *v, bool mips)
 {
     if (v->struct_size != sizeof(prosper_pt_scene_view))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "scene view struct_size mismatch");
@@ -173,11 +174,8 @@ int validate_scene(const prosper_pt_scene_view *v)
 
     for (uint32_t i = 0; i < v->textureCount; ++i)
     {
-        const prosper_pt_texture_desc &t = v->textures[i];
-        if (!t.texels || t.width == 0 || t.height == 0 || t.format > PROSPER_PT_FORMAT_BC7_UNORM)
-            return fail(PROSPER_PT_ERR_SCENE, "texture " + std::to_string(i) + " is invalid");
-        if (t.format == PROSPER_PT_FORMAT_BC7_UNORM && (t.width % 4u != 0u || t.height % 4u != 0u))
-            return fail(PROSPER_PT_ERR_SCENE, "BC7 texture " + std::to_string(i) + " is not a whole number of 4x4 blocks");
+        const int rc = validate_texture(v->textures[i], i, mips);
+        if (rc != PROSPER_PT_OK) return rc;
     }
     for (uint32_t i = 0; i < v->samplerCount; ++i)
     {
@@ -313,16 +311,22 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     std::vector<DeviceTexture> &textures = ms->textures;
     textures.assign(v->textureCount ? v->textureCount : 1, DeviceTexture{nullptr, 0u, 0u, 0u, 0u});
     uint64_t texelBytes = 0;
+    // mip chains (PROSPER_PT_CREATE_TEXTURE_MIPS): built right behind each level 0, before a packed material's may be freed
+    const bool withMips = (ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0;
+    const std::vector<uint8_t> baseColour = base_colour_textures(v->materials, v->materialCount, textures.size());
+    if (withMips) ms->mips.assign(textures.size(), DeviceTextureMips{nullptr, 1u, 0u, {}});
     {
         size_t stagingBytes = 0;
-        for (uint32_t i = 0; i < v->textureCount; ++i) stagingBytes = std::max(stagingBytes, texture_staging_bytes(v->textures[i]));
+        for (uint32_t i = 0; i < v->textureCount; ++i) stagingBytes = std::max(stagingBytes, texture_staging_bytes(v->textures[i], withMips));
         void *staging = nullptr;
         if (stagingBytes) PPT_HIP(hipMalloc(&staging, stagingBytes));
         for (uint32_t i = 0; i < v->textureCount && rc == PROSPER_PT_OK; ++i)
         {
             texelBytes += (uint64_t)v->textures[i].width * v->textures[i].height * 4u;
             // (one staging area, one stream: the copy of texture i + 1 queues behind the kernel that reads texture i)
-            rc = create_device_texture(ctx, v->textures[i], staging, nullptr, &textures[i]);
+            rc = create_device_texture(
+                ctx, v->textures[i], staging, nullptr, &textures[i], nullptr, withMips ? &ms->mips[i] : nullptr, baseColour[i] != 0);
+            if (withMips && rc == PROSPER_PT_OK) ms->mipTexelBytes += mip_texel_bytes(textures[i].width, textures[i].height, ms->mips[i].levelCount);
         }
         const hipError_t e = hipDeviceSynchronize();
         if (staging) (void)hipFree(staging);
@@ -387,6 +391,11 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     }
     if ((rc = upload(ctx, textures.data(), textures.size() * sizeof(DeviceTexture), &d))) return rc;
     s.textures = static_cast<const DeviceTexture *>(d);
+    if (withMips)
+    {
+        if ((rc = upload(ctx, ms->mips.data(), ms->mips.size() * sizeof(DeviceTextureMips), &d))) return rc;
+        ctx->textureMips = static_cast<const DeviceTextureMips *>(d);
+    }
     const double textureSeconds = seconds_since(tTextures);
 
     // lights: one block (directional, point list, spot list), the first of up to three versions
@@ -454,7 +463,8 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
         ms->packsOffset = align16(ms->materials.size() * sizeof(prosper_MaterialData));
         ms->alphaOffset = ms->packsOffset + align16(ms->packs.size() * sizeof(MaterialPack));
         ms->texturesOffset = ms->alphaOffset + align16(ms->alphaMaterials.size() * sizeof(AlphaMaterial));
-        ms->blockBytes = ms->texturesOffset + align16(ms->textures.size() * sizeof(DeviceTexture));
+        ms->mipsOffset = ms->texturesOffset + align16(ms->textures.size() * sizeof(DeviceTexture));
+        ms->blockBytes = ms->mipsOffset + align16(ms->mips.size() * sizeof(DeviceTextureMips));
     }
 
     if ((rc = finish_geometry(ctx, target, job))) return rc;
@@ -853,7 +863,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
 int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *scene)
 {
     if (!ctx || !scene) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_upload_scene: null argument");
-    int rc = validate_scene(scene);
+    int rc = validate_scene(scene, (ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0);
     if (rc != PROSPER_PT_OK) return rc;
     forget_ibl_maps(ctx);
     forget_taa_history(ctx);

@@ -190,6 +190,11 @@ struct MaterialState
     std::vector<AlphaMaterial> alphaMaterials;
     std::vector<DeviceTexture> textures;
     std::vector<prosper_pt_sampler_desc> samplers;
+    // levels >= 1 of every texture's chain, [textures.size()] on a context created with PROSPER_PT_CREATE_TEXTURE_MIPS
+    // (empty otherwise); the device table is the block's fifth part and ctx->textureMips its current version
+    std::vector<DeviceTextureMips> mips;
+    uint64_t mipTexelBytes = 0;
+    size_t mipsOffset = 0;
     uint64_t texelBytes = 0;       // level-0 texel footprint of the textures as the caller gave them (4 B per texel)
     uint64_t alphaBoundBytes = 0;
     uint32_t packedMaterials = 0;
@@ -269,6 +274,7 @@ struct prosper_pt_ctx
     std::atomic<uint64_t> sceneBytes{0}; // (the worker thread of a mesh build allocates too)
     bool haveScene = false;
     ppt::DeviceScene scene = {};
+    const ppt::DeviceTextureMips *textureMips = nullptr; // beside scene.textures (nullptr: the context keeps no mip chains)
     prosper_pt_scene_stats stats = {};
     uint32_t packedMaterials = 0; // materials whose three textures are interleaved (MaterialPack)
     uint64_t alphaTriangleCount = 0, alphaBoundBytes = 0; // any-hit records and bytes of alpha bounds (AlphaMaterial)

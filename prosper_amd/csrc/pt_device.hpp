@@ -407,6 +407,114 @@ PPT_D f4 sample_texture(const DeviceScene &s, uint32_t tex, uint32_t smp, f2 uv)
     return filter_taps(k, fetch_taps(k));
 }
 
+// ------------------------------------------------------------------------------------------
+// Texture sampling through a mip chain (Vulkan 1.3 §16.5.7 without anisotropy, lambda kept in float)
+// ------------------------------------------------------------------------------------------
+
+// The uv forward differences of a pixel towards its right (x) and lower (y) neighbour.
+struct UvDerivatives
+{
+    float dudx, dvdx, dudy, dvdy;
+};
+
+PPT_D bool is_finite(float x) { return (f2u(x) & 0x7F800000u) != 0x7F800000u; }
+
+// lambda of one texture: rho_x = |(du/dx * w, dv/dx * h)|, rho_y likewise, lambda = log2_(max(rho_x, rho_y)) + bias.
+// A derivative that is inf or NaN (or a rho that overflows) gives +inf: the last level.  rho == 0 gives -inf: level 0.
+PPT_D float texture_lambda(uint32_t width, uint32_t height, const UvDerivatives &d, float bias)
+{
+    if (!(is_finite(d.dudx) && is_finite(d.dvdx) && is_finite(d.dudy) && is_finite(d.dvdy))) return __builtin_inff();
+    const float w = (float)width, h = (float)height;
+    const float ax = d.dudx * w, ay = d.dvdx * h;
+    const float bx = d.dudy * w, by = d.dvdy * h;
+    const float rhoX = sqrt_(__builtin_fmaf(ay, ay, ax * ax));
+    const float rhoY = sqrt_(__builtin_fmaf(by, by, bx * bx));
+    const float rho = fmax_(rhoX, rhoY);
+    if (!is_finite(rho)) return __builtin_inff();
+    if (rho == 0.0f) return -__builtin_inff();
+    return log2_(rho) + bias;
+}
+
+// Level `level` >= 1 of texture `t` (level 0) in its chain.  (The entry is read where it lies: a copy of the 80-byte
+// record indexed by a run-time level would become a per-lane array.)
+PPT_D DeviceTexture mip_level(const DeviceTexture &t, const DeviceTextureMips *m, uint32_t level)
+{
+    const uint32_t w = t.width >> level, h = t.height >> level;
+    DeviceTexture r;
+    r.texels = m->texels + (size_t)m->wordOffset[level] * 4u;
+    r.width = w ? w : 1u;
+    r.height = h ? h : 1u;
+    r.tilesPerRow = (r.width + kTexTileW - 1u) / kTexTileW;
+    r.pad = 0u;
+    return r;
+}
+
+// The two levels a lambda > 0 blends and the fraction between them: floor(lambda) and the next one, both clamped to the
+// chain's last level (where the fraction is 0).
+struct LodLevels
+{
+    uint32_t lo, hi;
+    float fraction;
+};
+PPT_D LodLevels lod_levels(float lambda, uint32_t levelCount)
+{
+    const float last = (float)(levelCount - 1u);
+    LodLevels r;
+    if (lambda >= last)
+    {
+        r.lo = r.hi = levelCount - 1u;
+        r.fraction = 0.0f;
+        return r;
+    }
+    const float fl = __builtin_floorf(lambda);
+    r.lo = (uint32_t)f2i(fl);
+    r.hi = r.lo + 1u; // <= last: floor(lambda) < last
+    r.fraction = lambda - fl;
+    return r;
+}
+
+// A lambda > 0 sample in the same three steps as an LOD-0 one: both levels' footprints (the sampler's minFilter and wrap
+// modes at each), all eight loads in flight, two filters, then fraction * hi + (1 - fraction) * lo as one fmaf per channel.
+struct LodTaps
+{
+    TexelTaps lo, hi;
+    float fraction;
+};
+PPT_D LodTaps lod_taps(const DeviceTexture &t, const DeviceTextureMips *m, const prosper_pt_sampler_desc &sd, f2 uv, float lambda)
+{
+    prosper_pt_sampler_desc sm = sd;
+    sm.magFilter = sd.minFilter; // (texel_taps goes by magFilter: the LOD-0 path's filter)
+    const LodLevels l = lod_levels(lambda, m->levelCount);
+    LodTaps k;
+    k.lo = texel_taps(l.lo == 0u ? t : mip_level(t, m, l.lo), sm, uv);
+    k.hi = texel_taps(l.hi == 0u ? t : mip_level(t, m, l.hi), sm, uv);
+    k.fraction = l.fraction;
+    return k;
+}
+PPT_D f4 filter_lod_taps(const LodTaps &k, const RawTaps &lo, const RawTaps &hi)
+{
+    const f4 a = filter_taps(k.lo, lo);
+    const f4 b = filter_taps(k.hi, hi);
+    const float f = k.fraction, g = 1.0f - f;
+    return f4{__builtin_fmaf(f, b.x, g * a.x), __builtin_fmaf(f, b.y, g * a.y), __builtin_fmaf(f, b.z, g * a.z),
+              __builtin_fmaf(f, b.w, g * a.w)};
+}
+
+// texture(sampler2D, uv) with explicit derivatives: lambda <= 0 IS sample_texture (the same code, the same bits).
+PPT_D f4 sample_texture_lod(
+    const DeviceScene &s, const DeviceTextureMips *mips, uint32_t tex, uint32_t smp, f2 uv, const UvDerivatives &d, float bias,
+    float *lambdaOut = nullptr)
+{
+    const DeviceTexture t = s.textures[tex];
+    const float lambda = texture_lambda(t.width, t.height, d, bias);
+    if (lambdaOut) *lambdaOut = lambda;
+    if (!(lambda > 0.0f)) return sample_texture(s, tex, smp, uv);
+    const LodTaps k = lod_taps(t, mips + tex, s.samplers[smp], uv, lambda);
+    const RawTaps lo = fetch_taps(k.lo);
+    const RawTaps hi = fetch_taps(k.hi);
+    return filter_lod_taps(k, lo, hi);
+}
+
 // Cube face selection per Vulkan 1.3 §16.5.4 (faces +X,-X,+Y,-Y,+Z,-Z)
 PPT_D void cube_face_coords(f3 d, uint32_t &face, float &sc, float &tc, float &ma)
 {
@@ -537,7 +645,105 @@ PPT_D float srgb_to_linear(float x)
     return x <= 0.04045f ? x * (1.0f / 12.92f) : pow_((x + 0.055f) * (1.0f / 1.055f), 2.4f);
 }
 
+// The three level-0 samples of a packed material (pt_scene.hpp MaterialPack) through sampler `sd`, and the part of
+// sample_material behind its three samples: what sample_material_lod shares with it, restated.  sample_material itself
+// stays as it was written, so that the kernels built from it keep their code and their register figures.
+PPT_D void sample_pack(const MaterialPack &pack, const prosper_pt_sampler_desc &sd, f2 uv, f4 &sBaseT, f4 &sMrT, f4 &sNT)
+{
+    // the three textures interleaved per texel (pt_scene.hpp MaterialPack): one footprint, four 12-byte loads - or
+    // four 8-byte ones from the compact pack of an opaque material, which keeps the eight bytes this function reads
+    typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) u32x3 *global_u32x3_ptr;
+    typedef const __attribute__((address_space(1))) u32x2 *global_u32x2_ptr;
+    const PackTaps k = pack_taps(pack, sd, uv);
+    const global_u32_ptr base = (global_u32_ptr)pack.texels;
+    TexelTaps w;
+    w.a = k.a;
+    w.b = k.b;
+    if (pack.sampler & kPackCompactBit)
+    {
+        // (the compact pack is the one of texture sets that outgrow the caches: PPT_TEXEL_NT reads it past them)
+#if defined(PPT_TEXEL_NT) && PPT_TEXEL_NT
+        const u32x2 p00 = __builtin_nontemporal_load((global_u32x2_ptr)(base + k.o00 * 2u));
+        const u32x2 p10 = __builtin_nontemporal_load((global_u32x2_ptr)(base + k.o10 * 2u));
+        const u32x2 p01 = __builtin_nontemporal_load((global_u32x2_ptr)(base + k.o01 * 2u));
+        const u32x2 p11 = __builtin_nontemporal_load((global_u32x2_ptr)(base + k.o11 * 2u));
+#else
+        const u32x2 p00 = *(global_u32x2_ptr)(base + k.o00 * 2u);
+        const u32x2 p10 = *(global_u32x2_ptr)(base + k.o10 * 2u);
+        const u32x2 p01 = *(global_u32x2_ptr)(base + k.o01 * 2u);
+        const u32x2 p11 = *(global_u32x2_ptr)(base + k.o11 * 2u);
+#endif
+        const f4 lo = filter_taps(w, RawTaps{p00.x, p10.x, p01.x, p11.x}); // R G B roughness
+        const f4 hi = filter_taps(w, RawTaps{p00.y, p10.y, p01.y, p11.y}); // metallic Nx Ny Nz
+        sBaseT = f4{lo.x, lo.y, lo.z, 1.0f};
+        sMrT = f4{0.0f, lo.w, hi.x, 0.0f};
+        sNT = f4{hi.y, hi.z, hi.w, 0.0f};
+    }
+    else
+    {
+        const u32x3 p00 = *(global_u32x3_ptr)(base + k.o00 * 4u);
+        const u32x3 p10 = *(global_u32x3_ptr)(base + k.o10 * 4u);
+        const u32x3 p01 = *(global_u32x3_ptr)(base + k.o01 * 4u);
+        const u32x3 p11 = *(global_u32x3_ptr)(base + k.o11 * 4u);
+        sBaseT = filter_taps(w, RawTaps{p00.x, p10.x, p01.x, p11.x});
+        sMrT = filter_taps(w, RawTaps{p00.y, p10.y, p01.y, p11.y});
+        sNT = filter_taps(w, RawTaps{p00.z, p10.z, p01.z, p11.z});
+    }
+}
+
+// materials.glsl:47-119 behind the three texture samples
+PPT_D Material finish_material(
+    const prosper_MaterialData &data, uint32_t baseTex, uint32_t mrTex, uint32_t nTex, f4 sBaseT, f4 sMrT, f4 sNT)
+{
+    Material ret;
+    ret.albedo = f3{0.0f, 0.0f, 0.0f};
+    ret.normal = f3{0.0f, 0.0f, 0.0f};
+    ret.roughness = 0.0f;
+    ret.metallic = 0.0f;
+    f4 base = f4{1.0f, 1.0f, 1.0f, 1.0f};
+    if (baseTex > 0) base = f4{srgb_to_linear(sBaseT.x), srgb_to_linear(sBaseT.y), srgb_to_linear(sBaseT.z), sBaseT.w};
+    base.x *= data.baseColorFactor.x;
+    base.y *= data.baseColorFactor.y;
+    base.z *= data.baseColorFactor.z;
+    base.w *= data.baseColorFactor.w;
+
+    if (data.alphaMode == PROSPER_ALPHA_MODE_BLEND)
+        ret.alpha = base.w;
+    else
+    {
+        if (data.alphaMode == PROSPER_ALPHA_MODE_MASK && base.w < data.alphaCutoff)
+        {
+            ret.alpha = 0.0f;
+            return ret;
+        }
+        ret.alpha = -1.0f;
+    }
+    ret.albedo = f3{base.x, base.y, base.z};
+
+    if (mrTex > 0)
+    {
+        ret.roughness = sMrT.y * data.roughnessFactor;
+        ret.metallic = sMrT.z * data.metallicFactor;
+    }
+    else
+    {
+        ret.roughness = data.roughnessFactor;
+        ret.metallic = data.metallicFactor;
+    }
+    ret.roughness = fmax_(ret.roughness, 0.05f);
+
+    if (nTex > 0)
+        ret.normal = f3{__builtin_fmaf(sNT.x, 2.0f, -1.0f), __builtin_fmaf(sNT.y, 2.0f, -1.0f), __builtin_fmaf(sNT.z, 2.0f, -1.0f)};
+    else
+        ret.normal = f3{-2.0f, -2.0f, -2.0f};
+    return ret;
+}
+
 // materials.glsl:47-119
+// (sample_pack and finish_material above restate this function's pack branch and tail for sample_material_lod: a change
+//  here is a change there.)
 // BATCHED: all texel loads of the three textures in flight together (costs ~13 more VGPRs: the shade kernel then
 // sits at its 128-register limit with a 16-byte spill, which a scene without big textures does not get back)
 template <bool BATCHED>
@@ -679,6 +885,103 @@ PPT_D Material sample_material(const DeviceScene &s, uint32_t index, f2 uv)
     else
         ret.normal = f3{-2.0f, -2.0f, -2.0f};
     return ret;
+}
+
+// sample_material through the textures' mip chains.  lambda is computed per texture from the same uv
+// derivatives and that texture's own extent.  When no texture is minified this IS sample_material - the same call, pack
+// included.  Otherwise a texture with lambda <= 0 is sampled as sample_material samples it, and one with lambda > 0
+// blends its two levels (lod_levels) through the sampler's minFilter: a level >= 1 comes from the chain, level 0 from
+// where it lives today - the material's pack (all three textures at once) or the texture itself.  All footprints first,
+// then every load of both levels and all three textures, then the filters.
+template <bool BATCHED>
+PPT_D Material sample_material_lod(
+    const DeviceScene &s, const DeviceTextureMips *mips, uint32_t index, f2 uv, const UvDerivatives &d, float bias)
+{
+    const prosper_MaterialData data = s.materials[index];
+    const uint32_t tex[3] = {data.baseColorTextureSampler & 0xFFFFFFu, data.metallicRoughnessTextureSampler & 0xFFFFFFu,
+                             data.normalTextureSampler & 0xFFFFFFu};
+    const uint32_t smp[3] = {data.baseColorTextureSampler >> 24, data.metallicRoughnessTextureSampler >> 24,
+                             data.normalTextureSampler >> 24};
+    float lambda[3];
+    bool minified = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+    {
+        lambda[k] = -__builtin_inff();
+        if (tex[k] > 0)
+        {
+            const DeviceTexture t = s.textures[tex[k]];
+            lambda[k] = texture_lambda(t.width, t.height, d, bias);
+        }
+        minified = minified || lambda[k] > 0.0f;
+    }
+    if (!minified) return sample_material<BATCHED>(s, index, uv);
+
+    const MaterialPack pack = s.materialPacks[index];
+    const bool packed = pack.texels != nullptr;
+    f4 out[3] = {f4{1.0f, 1.0f, 1.0f, 1.0f}, f4{0.0f, 0.0f, 0.0f, 0.0f}, f4{0.0f, 0.0f, 0.0f, 0.0f}};
+    // footprints
+    LodTaps taps[3];
+    bool lod[3], loInPack[3], hiInPack[3], oneLevel[3]; // oneLevel: lambda at or beyond the last level - fetched once
+    bool needPack = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+    {
+        lod[k] = lambda[k] > 0.0f;
+        loInPack[k] = hiInPack[k] = oneLevel[k] = false;
+        if (!lod[k]) continue;
+        const DeviceTexture t = s.textures[tex[k]];
+        const DeviceTextureMips *m = mips + tex[k];
+        prosper_pt_sampler_desc sm = s.samplers[smp[k]];
+        sm.magFilter = sm.minFilter;
+        const LodLevels l = lod_levels(lambda[k], m->levelCount);
+        taps[k].fraction = l.fraction;
+        loInPack[k] = packed && l.lo == 0u;
+        oneLevel[k] = l.lo == l.hi; // (the fraction is 0 then: fmaf(0, b, 1 * a) is a, bit for bit)
+        hiInPack[k] = packed && l.hi == 0u;
+        needPack = needPack || loInPack[k] || hiInPack[k];
+        if (!loInPack[k]) taps[k].lo = texel_taps(l.lo == 0u ? t : mip_level(t, m, l.lo), sm, uv);
+        if (!hiInPack[k] && !oneLevel[k]) taps[k].hi = texel_taps(mip_level(t, m, l.hi), sm, uv);
+    }
+    // loads
+    RawTaps lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+    {
+        if (lod[k] && !loInPack[k]) lo[k] = fetch_taps(taps[k].lo);
+        if (lod[k] && !hiInPack[k] && !oneLevel[k]) hi[k] = fetch_taps(taps[k].hi);
+    }
+    f4 pack0[3] = {out[0], out[1], out[2]};
+    if (needPack)
+    {
+        // (a packed material's textures share extent and sampler: one lambda, one level-0 footprint for the three)
+        prosper_pt_sampler_desc sm = s.samplers[pack.sampler & ~kPackCompactBit];
+        sm.magFilter = sm.minFilter;
+        sample_pack(pack, sm, uv, pack0[0], pack0[1], pack0[2]);
+    }
+    // filters
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+    {
+        if (tex[k] == 0u) continue;
+        if (!lod[k])
+        {
+            // (an unpacked material: in a pack the three lambdas are one, and it is > 0 here)
+            out[k] = sample_texture(s, tex[k], smp[k], uv);
+            continue;
+        }
+        const f4 a = loInPack[k] ? pack0[k] : filter_taps(taps[k].lo, lo[k]);
+        if (oneLevel[k])
+        {
+            out[k] = a;
+            continue;
+        }
+        const f4 b = hiInPack[k] ? pack0[k] : filter_taps(taps[k].hi, hi[k]);
+        const float f = taps[k].fraction, g = 1.0f - f;
+        out[k] = f4{__builtin_fmaf(f, b.x, g * a.x), __builtin_fmaf(f, b.y, g * a.y), __builtin_fmaf(f, b.z, g * a.z),
+                    __builtin_fmaf(f, b.w, g * a.w)};
+    }
+    return finish_material(data, tex[0], tex[1], tex[2], out[0], out[1], out[2]);
 }
 
 // (sampleAlpha, materials.glsl:121-147, lives with the any-hit shader below: any_hit_settle / any_hit_exact / alpha_verdict)
@@ -1731,8 +2034,38 @@ PPT_D f3 mapped_normal(f3 tsn, f3 normal, f3 tangent, float sgn)
     return normalize(((tangent * tsn.x) + (vB * tsn.y)) + (normal * tsn.z));
 }
 
-template <bool COUNT, bool BATCHED_TEXTURES = false>
-PPT_D Surface evaluate_surface(const DeviceScene &s, f3 rayDir, const Hit &hit, LaneCounters &cnt)
+// What a surface needs to sample its material through the mip chains: the chain table, the bias and the rays of the
+// pixel's right and lower neighbour (the same eye).  nullptr: LOD 0.
+struct SurfaceLod
+{
+    const DeviceTextureMips *mips;
+    float bias;
+    f3 eye, dirX, dirY;
+    UvDerivatives *derivativesOut; // what the surface sampled with (debug output); may be nullptr
+};
+
+// The uv a ray from `o` along `dir` finds on the plane of the world-space triangle (p0, p1, p2) with corner uvs
+// (t0, t1, t2), minus `uv`: one forward difference of the rasteriser's quad.  A ray parallel to the plane or meeting it
+// behind the eye gives (inf, inf).  The float32 sequence is DESIGN.md (f14)'s.
+PPT_D f2 ray_uv_difference(f3 o, f3 dir, f3 p0, f3 p1, f3 p2, f2 t0, f2 t1, f2 t2, f2 uv)
+{
+    const f3 e1 = p1 - p0, e2 = p2 - p0;
+    const f3 n = cross(e1, e2);
+    const float denom = dot(n, dir);
+    const float t = dot(n, p0 - o) / denom;
+    if (!(t > 0.0f) || !is_finite(t)) return f2{__builtin_inff(), __builtin_inff()};
+    const f3 q = f3{__builtin_fmaf(dir.x, t, o.x), __builtin_fmaf(dir.y, t, o.y), __builtin_fmaf(dir.z, t, o.z)} - p0;
+    const float d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2), d20 = dot(q, e1), d21 = dot(q, e2);
+    const float den = __builtin_fmaf(d00, d11, -(d01 * d01));
+    const float b1 = __builtin_fmaf(d11, d20, -(d01 * d21)) / den;
+    const float b2 = __builtin_fmaf(d00, d21, -(d01 * d20)) / den;
+    const float u = __builtin_fmaf(b2, t2.x - t0.x, __builtin_fmaf(b1, t1.x - t0.x, t0.x));
+    const float v = __builtin_fmaf(b2, t2.y - t0.y, __builtin_fmaf(b1, t1.y - t0.y, t0.y));
+    return f2{u - uv.x, v - uv.y};
+}
+
+template <bool COUNT, bool BATCHED_TEXTURES = false, bool LOD = false>
+PPT_D Surface evaluate_surface(const DeviceScene &s, f3 rayDir, const Hit &hit, LaneCounters &cnt, const SurfaceLod *lodIn = nullptr)
 {
     // loadVertexThroughIndexBuffer x 3 (geometry.glsl:220-244) from the triangle's record, decoded at upload (128 B)
     const prosper_DrawInstance inst = s.drawInstances[hit.drawInstance];
@@ -1764,7 +2097,18 @@ PPT_D Surface evaluate_surface(const DeviceScene &s, f3 rayDir, const Hit &hit, 
     sf.positionWS = v.position;
     sf.invViewRayWS = -rayDir;
     sf.uv = v.uv;
-    sf.material = sample_material<BATCHED_TEXTURES>(s, inst.materialIndex, v.uv);
+    if constexpr (LOD)
+    {
+        const prosper_mat3x4 &m = s.modelInstanceTransforms[inst.modelInstanceIndex].modelToWorld;
+        const f3 p0 = mul_point_mat3x4(v0.position, m), p1 = mul_point_mat3x4(v1.position, m), p2 = mul_point_mat3x4(v2.position, m);
+        const f2 dx = ray_uv_difference(lodIn->eye, lodIn->dirX, p0, p1, p2, v0.uv, v1.uv, v2.uv, v.uv);
+        const f2 dy = ray_uv_difference(lodIn->eye, lodIn->dirY, p0, p1, p2, v0.uv, v1.uv, v2.uv, v.uv);
+        const UvDerivatives d{dx.x, dx.y, dy.x, dy.y};
+        if (lodIn->derivativesOut) *lodIn->derivativesOut = d;
+        sf.material = sample_material_lod<BATCHED_TEXTURES>(s, lodIn->mips, inst.materialIndex, v.uv, d, lodIn->bias);
+    }
+    else
+        sf.material = sample_material<BATCHED_TEXTURES>(s, inst.materialIndex, v.uv);
     if (sf.material.normal.x != -2.0f && v.tangent.w != 0.0f)
         sf.normalWS = mapped_normal(sf.material.normal, v.normal, f3{v.tangent.x, v.tangent.y, v.tangent.z}, v.tangent.w);
     else

@@ -381,16 +381,23 @@ PPT_D float2 ndc_velocity(const GBufferVelocityParams &v, f3 position, f3 previo
 struct GBufferNoVelocity
 {
 };
+struct GBufferNoLod
+{
+};
 
 // kVelocity: the primary ray goes through the point the (jittered) projection puts on the pixel centre, and a fourth
 // target takes the velocity, on hits and on the sky.  The plain instantiation reads nothing of `v`.
 // kOpaqueOnly (PROSPER_PT_GBUFFER_OPAQUE_ONLY): BLEND candidates are always rejected, as prosper keeps BLEND geometry out of its G-buffer
 // (draw_list_generator.comp:43-54); forward_transparent_kernel draws them afterwards.
-template <bool kVelocity, bool kOpaqueOnly = false>
+// kLod (prosper_pt_set_texture_lod): the material is sampled through the textures' mip chains, with the uv
+// forward differences towards the pixels (px + 1, py) and (px, py + 1) - the pinhole rays through them, with this
+// pixel's own jitter offset, met with the hit triangle's plane.  The ray, the hit and everything but the sampled
+// material are the plain instantiation's.
+template <bool kVelocity, bool kOpaqueOnly = false, bool kLod = false>
 __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     DeviceScene s, GBufferTraceParams g, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
     float *__restrict__ nonLinearDepth, int32_t *__restrict__ stackOverflow,
-    std::conditional_t<kVelocity, GBufferVelocityParams, GBufferNoVelocity> v)
+    std::conditional_t<kVelocity, GBufferVelocityParams, GBufferNoVelocity> v, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
 {
     __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
     uint32_t px, py;
@@ -417,9 +424,30 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
         normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         nonLinearDepth[i] = 0.0f;
         if constexpr (kVelocity) v.velocity[i] = ndc_velocity(v, ray.d, ray.d, true);
+        if constexpr (kLod)
+            if (lodp.derivatives) lodp.derivatives[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-    const Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
+    Surface sf;
+    if constexpr (kLod)
+    {
+        // the neighbours' uv by the expressions above with px + 1 / py + 1
+        const float w = (float)g.r.width, h = (float)g.r.height;
+        const float ox = g.jitter ? j.x : 0.5f, oy = g.jitter ? j.y : 0.5f;
+        f2 uvX = f2{((float)(px + 1u) + ox) / w, ((float)py + oy) / h};
+        f2 uvY = f2{((float)px + ox) / w, ((float)(py + 1u) + oy) / h};
+        if constexpr (kVelocity)
+        {
+            uvX = f2{uvX.x - v.currentJitter[0] * 0.5f, uvX.y - v.currentJitter[1] * 0.5f};
+            uvY = f2{uvY.x - v.currentJitter[0] * 0.5f, uvY.y - v.currentJitter[1] * 0.5f};
+        }
+        UvDerivatives used;
+        const SurfaceLod lod{lodp.mips, lodp.bias, ray.o, pinhole_camera_ray(g.r, uvX).d, pinhole_camera_ray(g.r, uvY).d, &used};
+        sf = evaluate_surface<false, false, true>(s, ray.d, hit, cnt, &lod);
+        if (lodp.derivatives) lodp.derivatives[i] = make_float4(used.dudx, used.dvdx, used.dudy, used.dvdy);
+    }
+    else
+        sf = evaluate_surface<false>(s, ray.d, hit, cnt);
     if constexpr (kVelocity)
     {
         f3 previous = sf.positionWS;
@@ -460,24 +488,42 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
 
 void launch_gbuffer_trace(
     const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
-    int32_t *stackOverflow, hipStream_t stream)
+    int32_t *stackOverflow, hipStream_t stream, const GBufferLodParams *lod)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
+    const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
+    if (lod)
+    {
+        const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<false, true, true> : gbuffer_trace_kernel<false, false, true>;
+        hipLaunchKernelGGL(
+            kernel, grid, dim3(256), 0, stream, s, g, static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic),
+            nonLinearDepth, stackOverflow, GBufferNoVelocity{}, *lod);
+        return;
+    }
     const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<false, true> : gbuffer_trace_kernel<false, false>;
     hipLaunchKernelGGL(
-        kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
-        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, GBufferNoVelocity{});
+        kernel, grid, dim3(256), 0, stream, s, g, static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic),
+        nonLinearDepth, stackOverflow, GBufferNoVelocity{}, GBufferNoLod{});
 }
 
 void launch_gbuffer_trace_velocity(
     const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
-    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream)
+    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream, const GBufferLodParams *lod)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
+    const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
+    if (lod)
+    {
+        const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<true, true, true> : gbuffer_trace_kernel<true, false, true>;
+        hipLaunchKernelGGL(
+            kernel, grid, dim3(256), 0, stream, s, g, static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic),
+            nonLinearDepth, stackOverflow, v, *lod);
+        return;
+    }
     const auto kernel = g.opaqueOnly ? gbuffer_trace_kernel<true, true> : gbuffer_trace_kernel<true, false>;
     hipLaunchKernelGGL(
-        kernel, dim3(restir_grid_blocks(g.r.width, g.r.height)), dim3(256), 0, stream, s, g,
-        static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic), nonLinearDepth, stackOverflow, v);
+        kernel, grid, dim3(256), 0, stream, s, g, static_cast<float4 *>(albedoRoughness), static_cast<float4 *>(normalMetallic),
+        nonLinearDepth, stackOverflow, v, GBufferNoLod{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -790,12 +836,15 @@ void launch_deferred_shading_ibl(
 // ------------------------------------------------------------------------------------------
 
 // kLayers: the debug mode of prosper_pt_read_transparent_layers - the first p.debugLayers layers of a pixel are kept
-template <bool IBL, bool kLayers>
+// kLod (prosper_pt_set_texture_lod): every peeled layer samples its material through the mip chains, with
+// the uv forward differences of gbuffer_trace_kernel<.., .., true> - the same two neighbour rays for all layers of the
+// pixel, met with each layer's own triangle plane.
+template <bool IBL, bool kLayers, bool kLod = false>
 __global__ __launch_bounds__(256) void forward_transparent_kernel(
     DeviceScene s, TransparentParams p, const float *__restrict__ nonLinearDepth, const uint2 *__restrict__ pointers,
     const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, int32_t *__restrict__ stackOverflow,
     uint32_t *__restrict__ stats, uint32_t *__restrict__ layerCounts, prosper_pt_transparent_layer *__restrict__ layers,
-    IblMaps ibl)
+    IblMaps ibl, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
 {
     __shared__ int32_t ldsStack[kTraversalStackDepth * 256];
     const GBufferTraceParams &g = p.g;
@@ -811,14 +860,29 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
         // the G-buffer's ray of this pixel (gbuffer_trace_kernel): centre, the path tracer's sample, or the centre half a
         // camera jitter back
         f2 uv = f2{((float)px + 0.5f) / (float)g.r.width, ((float)py + 0.5f) / (float)g.r.height};
+        [[maybe_unused]] float ox = 0.5f, oy = 0.5f; // the pixel's own offset, for the neighbours' rays (kLod)
         if (g.jitter)
         {
             Rng rng{px, py, g.frameIndex};
             const f2 j = rng.rnd2d01();
             uv = f2{((float)px + j.x) / (float)g.r.width, ((float)py + j.y) / (float)g.r.height};
+            ox = j.x;
+            oy = j.y;
         }
         if (p.cameraJitter) uv = f2{uv.x - p.currentJitter[0] * 0.5f, uv.y - p.currentJitter[1] * 0.5f};
         const Ray ray = pinhole_camera_ray(g.r, uv);
+        [[maybe_unused]] SurfaceLod lod = {};
+        if constexpr (kLod)
+        {
+            f2 uvX = f2{((float)(px + 1u) + ox) / (float)g.r.width, ((float)py + oy) / (float)g.r.height};
+            f2 uvY = f2{((float)px + ox) / (float)g.r.width, ((float)(py + 1u) + oy) / (float)g.r.height};
+            if (p.cameraJitter)
+            {
+                uvX = f2{uvX.x - p.currentJitter[0] * 0.5f, uvX.y - p.currentJitter[1] * 0.5f};
+                uvY = f2{uvY.x - p.currentJitter[0] * 0.5f, uvY.y - p.currentJitter[1] * 0.5f};
+            }
+            lod = SurfaceLod{lodp.mips, lodp.bias, ray.o, pinhole_camera_ray(g.r, uvX).d, pinhole_camera_ray(g.r, uvY).d, nullptr};
+        }
         const float stored = nonLinearDepth[i];
         // Nothing behind the opaque surface can pass the depth test: the traversal ends a little past it (0.1 %, far more
         // than the depth's rounding), and the exact test below decides.  A depth that gives no positive distance (the sky's
@@ -847,7 +911,11 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
             Hit hit;
             if (!trace<false, false, kBlendPeel>(s, ray.o, ray.d, ray.tMin, tMax, 0u, stack, hit, cnt, &after)) break;
             after = hit;
-            Surface sf = evaluate_surface<false>(s, ray.d, hit, cnt);
+            Surface sf;
+            if constexpr (kLod)
+                sf = evaluate_surface<false, false, true>(s, ray.d, hit, cnt, &lod);
+            else
+                sf = evaluate_surface<false>(s, ray.d, hit, cnt);
             if (sf.material.alpha == 0.0f) continue; // forward.frag:57
             // posNDC.z as gbuffer_trace_kernel computes it; eGreater on reverse Z, no depth write
             const float *m = g.worldToClip;
@@ -931,16 +999,26 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
 void launch_forward_transparent(
     const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
     const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
-    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream)
+    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream, const GBufferLodParams *lod)
 {
     if (p.g.r.width == 0 || p.g.r.height == 0) return;
     const bool ibl = irradiance != nullptr, debug = p.debugLayers != 0u;
+    if (lod)
+    {
+        const auto lodKernel = ibl ? (debug ? forward_transparent_kernel<true, true, true> : forward_transparent_kernel<true, false, true>)
+                                   : (debug ? forward_transparent_kernel<false, true, true> : forward_transparent_kernel<false, false, true>);
+        const IblMaps lodMaps = {irradiance, radiance, lut};
+        hipLaunchKernelGGL(
+            lodKernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
+            static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, lodMaps, *lod);
+        return;
+    }
     const auto kernel = ibl ? (debug ? forward_transparent_kernel<true, true> : forward_transparent_kernel<true, false>)
                             : (debug ? forward_transparent_kernel<false, true> : forward_transparent_kernel<false, false>);
     const IblMaps maps = {irradiance, radiance, lut};
     hipLaunchKernelGGL(
         kernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, maps);
+        static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, maps, GBufferNoLod{});
 }
 
 } // namespace ppt

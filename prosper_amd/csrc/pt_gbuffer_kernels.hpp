@@ -42,9 +42,18 @@ struct GBufferTraceParams
 };
 // albedoRoughness, normalMetallic: r.width*r.height float4; nonLinearDepth: r.width*r.height float.  Grid of
 // restir_grid_blocks(r.width, r.height) blocks (the stack overflow array is sized for it).
+// `lod` (nullptr: LOD 0, the instantiations of before): the material is sampled through the textures' mip chains
+// (gbuffer_trace_kernel<.., .., true>); `derivatives` != nullptr also takes the uv forward differences the
+// pixel sampled with, (du/dx, dv/dx, du/dy, dv/dy), zeros on a miss.
+struct GBufferLodParams
+{
+    const DeviceTextureMips *mips; // beside s.textures
+    float bias;
+    float4 *derivatives; // r.width*r.height, or nullptr
+};
 void launch_gbuffer_trace(
     const DeviceScene &s, const GBufferTraceParams &g, void *albedoRoughness, void *normalMetallic, float *nonLinearDepth,
-    int32_t *stackOverflow, hipStream_t stream);
+    int32_t *stackOverflow, hipStream_t stream, const GBufferLodParams *lod = nullptr);
 // The same with a velocity target (gbuffer_trace_kernel<true>): the ray goes through the point that
 // cameraToClip * worldToCamera puts on the pixel centre (g.jitter must be 0), and `velocity` takes
 // (posNDC - currentJitter) - (prevPosNDC - previousJitter), y negated, clamped to [-1, 1], on hits and on the sky.
@@ -57,7 +66,7 @@ struct GBufferVelocityParams
 };
 void launch_gbuffer_trace_velocity(
     const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
-    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream);
+    float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream, const GBufferLodParams *lod = nullptr);
 // The forward transparent pass (forward_transparent_kernel) in place over `hdr`, r.width*r.height float4,
 // against `nonLinearDepth`.  g.jitter: the path tracer's sample; cameraJitter: the velocity entry's ray.  The lists are
 // launch_light_clustering's for the same camera and extent; irradiance / radiance / lut: the IBL maps, all nullptr
@@ -77,7 +86,8 @@ struct TransparentParams
 void launch_forward_transparent(
     const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
     const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
-    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream);
+    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
+    const GBufferLodParams *lod = nullptr); // lod: every layer's material through the mip chains (its `derivatives` is not read)
 // Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
 // uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
 // [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the

@@ -33,6 +33,11 @@ struct GBufferPassState
     DeviceBuffer velocity;           // context-owned velocity target (prosper_pt_trace_gbuffer_velocity): 8 bytes per pixel
     DeviceBuffer previousTransforms; // the device copy of a call's previous instance transforms
     void *velocityLast = nullptr;    // what the last prosper_pt_trace_gbuffer_velocity wrote
+    // prosper_pt_set_texture_lod / _debug: the traced G-buffer samples materials through the mip chains
+    bool lodEnabled = false, lodDebug = false;
+    float lodBias = 0.0f;
+    DeviceBuffer lodDerivatives; // debug: float4 per pixel of the last traced G-buffer
+    uint32_t lodDerivativesWidth = 0, lodDerivativesHeight = 0; // 0: the last traced G-buffer wrote none
     uint32_t velocityLastWidth = 0, velocityLastHeight = 0;
     DeviceBuffer clusterPointers; // prosper_pt_cluster_lights: uint2 per cluster
     DeviceBuffer clusterIndices;  // kClusterSlot uint16 entries per cluster
@@ -231,6 +236,18 @@ int gbuffer_trace(
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
     if (orc != PROSPER_PT_OK) return orc;
     wait_for_slot(ctx->slots[0], s);
+    GBufferPassState &lst = *ctx->gbufferPasses;
+    GBufferLodParams lodParams{ctx->textureMips, lst.lodBias, nullptr};
+    const GBufferLodParams *lod = lst.lodEnabled && ctx->textureMips ? &lodParams : nullptr;
+    lst.lodDerivativesWidth = lst.lodDerivativesHeight = 0;
+    if (lod && lst.lodDebug)
+    {
+        const int grc = grow_to(lst.lodDerivatives, (size_t)width * height * sizeof(float4), s);
+        if (grc != PROSPER_PT_OK) return grc;
+        lodParams.derivatives = lst.lodDerivatives.as<float4>();
+        lst.lodDerivativesWidth = width;
+        lst.lodDerivativesHeight = height;
+    }
     if (velocity)
     {
         std::memcpy(velocity->worldToCamera, &camera->worldToCamera, 64);
@@ -242,10 +259,10 @@ int gbuffer_trace(
             velocity->currentJitter[k] = camera->currentJitter[k];
             velocity->previousJitter[k] = camera->previousJitter[k];
         }
-        launch_gbuffer_trace_velocity(ctx->scene, g, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+        launch_gbuffer_trace_velocity(ctx->scene, g, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
     }
     else
-        launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s);
+        launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
     release_slot(ctx->slots[0], s);
     PPT_HIP(hipGetLastError());
     GBufferPassState &st = *ctx->gbufferPasses;
@@ -859,11 +876,13 @@ int prosper_pt_forward_transparent(
     wait_for_slot(ctx->slots[0], s);
     const bool ibl = pc->ibl == 1u;
     uint32_t *counts = debugLayers ? st.transparentLayers.as<uint32_t>() : nullptr;
+    const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
     launch_forward_transparent(
         ctx->scene, p, depth, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
         ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, ovf,
         st.transparentStats.as<uint32_t>(), counts,
-        debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s);
+        debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s,
+        st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
     release_slot(ctx->slots[0], s);
     PPT_HIP(hipGetLastError());
     PPT_HIP(hipEventRecord(st.transparentTiming.events[1], s));
@@ -992,6 +1011,39 @@ int prosper_pt_read_ibl(
     PPT_HIP(hipStreamSynchronize(s));
     if (irradiance_rgba16f) strip_cube_borders(irr, kIblIrradianceSize, 1u, irradiance_rgba16f);
     if (radiance_rgba16f) strip_cube_borders(rad, kIblRadianceSize, kIblRadianceMips, radiance_rgba16f);
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_set_texture_lod(prosper_pt_ctx *ctx, int enabled, float lodBias)
+{
+    if (!std::isfinite(lodBias)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_texture_lod: lodBias is not finite");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_texture_lod: null context");
+    if (enabled && !(ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_set_texture_lod: the context was created without PROSPER_PT_CREATE_TEXTURE_MIPS");
+    ctx->gbufferPasses->lodEnabled = enabled != 0;
+    ctx->gbufferPasses->lodBias = lodBias;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_set_texture_lod_debug(prosper_pt_ctx *ctx, int enabled)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_texture_lod_debug: null context");
+    ctx->gbufferPasses->lodDebug = enabled != 0;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_texture_lod_derivatives(prosper_pt_ctx *ctx, float *out, size_t bytes, void *stream)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (st.lodDerivativesWidth == 0)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: the last traced G-buffer wrote no derivatives (prosper_pt_set_texture_lod, prosper_pt_set_texture_lod_debug)");
+    if (bytes != (size_t)st.lodDerivativesWidth * st.lodDerivativesHeight * sizeof(float4))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: size mismatch");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(out, st.lodDerivatives.ptr, bytes, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
     return PROSPER_PT_OK;
 }
 

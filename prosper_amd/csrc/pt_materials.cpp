@@ -10,65 +10,192 @@
 // alpha bounds, and the next render switches to a new version of the four small tables at the head of its own chain.
 #include "pt_materials.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 
 #include "pt_kernels.hpp"
+#include "pt_pass_support.hpp"
+#include "pt_texture_mips.hpp"
 
 namespace ppt
 {
 
-size_t texture_staging_bytes(const prosper_pt_texture_desc &t)
+namespace
 {
-    const size_t bytes = t.format == PROSPER_PT_FORMAT_BC7_UNORM ? (size_t)(t.width / 4u) * (t.height / 4u) * 16u : (size_t)t.width * t.height * 4u;
-    return (bytes + 255u) & ~(size_t)255u;
+
+bool is_bc7(const prosper_pt_texture_desc &t) { return t.format == PROSPER_PT_FORMAT_BC7_UNORM; }
+
+// bytes of level `l` as the caller holds it (src/utils/Dds.cpp:100-135: BC7 in whole 16-byte blocks)
+size_t level_source_bytes(const prosper_pt_texture_desc &t, uint32_t l)
+{
+    const size_t w = std::max(t.width >> l, 1u), h = std::max(t.height >> l, 1u);
+    return is_bc7(t) ? (w / 4u) * (h / 4u) * 16u : w * h * 4u;
 }
 
-int validate_texture(const prosper_pt_texture_desc &t, uint32_t index)
+// levels the caller supplies in `texels`
+uint32_t supplied_levels(const prosper_pt_texture_desc &t, bool mips) { return mips && t.mipLevelCount > 1u ? t.mipLevelCount : 1u; }
+
+size_t source_bytes(const prosper_pt_texture_desc &t, bool mips)
+{
+    size_t bytes = 0;
+    for (uint32_t l = 0; l < supplied_levels(t, mips); ++l) bytes += level_source_bytes(t, l);
+    return bytes;
+}
+
+size_t tiled_level_words(uint32_t w, uint32_t h)
+{
+    return (size_t)((w + kTexTileW - 1u) / kTexTileW) * ((h + kTexTileH - 1u) / kTexTileH) * (kTexTileW * kTexTileH);
+}
+
+} // namespace
+
+size_t texture_staging_bytes(const prosper_pt_texture_desc &t, bool mips)
+{
+    return (source_bytes(t, mips) + 255u) & ~(size_t)255u;
+}
+
+int validate_texture(const prosper_pt_texture_desc &t, uint32_t index, bool mips)
 {
     if (!t.texels || t.width == 0 || t.height == 0 || t.format > PROSPER_PT_FORMAT_BC7_UNORM)
         return fail(PROSPER_PT_ERR_SCENE, "texture " + std::to_string(index) + " is invalid");
     if (t.format == PROSPER_PT_FORMAT_BC7_UNORM && (t.width % 4u != 0u || t.height % 4u != 0u))
         return fail(PROSPER_PT_ERR_SCENE, "BC7 texture " + std::to_string(index) + " is not a whole number of 4x4 blocks");
+    if (!mips) return PROSPER_PT_OK;
+    const uint32_t count = mip_level_count(t.width, t.height);
+    if (count > kMaxMipLevels)
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "texture " + std::to_string(index) + ": a mip chain of more than 16 levels");
+    if (t.mipLevelCount > count)
+        return fail(
+            PROSPER_PT_ERR_SCENE, "texture " + std::to_string(index) + ": mipLevelCount " + std::to_string(t.mipLevelCount) +
+                                      " exceeds the " + std::to_string(count) + " levels of prosper's chain for its extent");
+    if (is_bc7(t))
+        for (uint32_t l = 1; l < supplied_levels(t, true); ++l)
+            if ((std::max(t.width >> l, 1u) % 4u) != 0u || (std::max(t.height >> l, 1u) % 4u) != 0u)
+                return fail(
+                    PROSPER_PT_ERR_SCENE,
+                    "BC7 texture " + std::to_string(index) + ": mip level " + std::to_string(l) + " is not a whole number of 4x4 blocks");
     return PROSPER_PT_OK;
 }
 
-int create_device_texture(prosper_pt_ctx *ctx, const prosper_pt_texture_desc &t, void *staging, hipStream_t stream, DeviceTexture *out, void *pinned)
+uint64_t mip_texel_bytes(uint32_t width, uint32_t height, uint32_t levelCount)
+{
+    uint64_t bytes = 0;
+    for (uint32_t l = 1; l < levelCount; ++l) bytes += (uint64_t)std::max(width >> l, 1u) * std::max(height >> l, 1u) * 4u;
+    return bytes;
+}
+
+std::vector<uint8_t> base_colour_textures(const prosper_MaterialData *materials, size_t materialCount, size_t textureCount)
+{
+    std::vector<uint8_t> srgb(textureCount, 0);
+    for (size_t i = 0; i < materialCount; ++i)
+    {
+        const uint32_t t = materials[i].baseColorTextureSampler & 0xFFFFFFu;
+        if (t > 0 && t < textureCount) srgb[t] = 1;
+    }
+    return srgb;
+}
+
+namespace
+{
+
+// Levels >= 1 of `t`'s chain behind its level 0 `dt` (already enqueued on `stream`, its source levels in `staging`).
+int build_texture_mips(
+    prosper_pt_ctx *ctx, const prosper_pt_texture_desc &t, const DeviceTexture &dt, const void *staging, hipStream_t stream, bool srgb,
+    DeviceTextureMips *out)
+{
+    DeviceTextureMips m{};
+    const uint32_t supplied = supplied_levels(t, true);
+    m.levelCount = supplied > 1u ? supplied : mip_level_count(t.width, t.height);
+    m.srgb = supplied > 1u ? 0u : (srgb ? 1u : 0u);
+    if (m.levelCount == 1u)
+    {
+        *out = m;
+        return PROSPER_PT_OK;
+    }
+    size_t words = 0;
+    for (uint32_t l = 1; l < m.levelCount; ++l)
+    {
+        m.wordOffset[l] = (uint32_t)words;
+        words += tiled_level_words(std::max(t.width >> l, 1u), std::max(t.height >> l, 1u));
+    }
+    if (words >= (1ull << 32)) return fail(PROSPER_PT_ERR_UNSUPPORTED, "a texture's mip chain exceeds 2^32 texels");
+    void *d = nullptr;
+    const int rc = device_alloc(ctx, words * 4u, &d);
+    if (rc != PROSPER_PT_OK) return rc;
+    m.texels = static_cast<const uint8_t *>(d);
+    PPT_HIP(hipMemsetAsync(d, 0, words * 4u, stream)); // (tile padding)
+    size_t source = level_source_bytes(t, 0);
+    for (uint32_t l = 1; l < m.levelCount; ++l)
+    {
+        const uint32_t w = std::max(t.width >> l, 1u), h = std::max(t.height >> l, 1u);
+        uint32_t *level = static_cast<uint32_t *>(d) + m.wordOffset[l];
+        if (supplied > 1u)
+        {
+            const uint8_t *src = static_cast<const uint8_t *>(staging) + source;
+            if (is_bc7(t))
+                launch_decode_bc7(src, w, h, (w + kTexTileW - 1u) / kTexTileW, level, stream);
+            else
+                launch_retile_rgba8(src, w, h, (w + kTexTileW - 1u) / kTexTileW, level, stream);
+            source += level_source_bytes(t, l);
+        }
+        else
+        {
+            const uint32_t pw = std::max(t.width >> (l - 1u), 1u), ph = std::max(t.height >> (l - 1u), 1u);
+            const void *parent = l == 1u ? static_cast<const void *>(dt.texels) : static_cast<uint32_t *>(d) + m.wordOffset[l - 1u];
+            launch_generate_mip(parent, pw, ph, level, w, h, srgb, stream);
+        }
+    }
+    PPT_HIP(hipGetLastError());
+    *out = m;
+    return PROSPER_PT_OK;
+}
+
+} // namespace
+
+int create_device_texture(
+    prosper_pt_ctx *ctx, const prosper_pt_texture_desc &t, void *staging, hipStream_t stream, DeviceTexture *out, void *pinned,
+    DeviceTextureMips *mipsOut, bool srgb)
 {
     const uint32_t tilesX = (t.width + kTexTileW - 1u) / kTexTileW, tilesY = (t.height + kTexTileH - 1u) / kTexTileH;
     const size_t tiledBytes = (size_t)tilesX * tilesY * (kTexTileW * kTexTileH) * 4u;
     void *d = nullptr;
     const int rc = device_alloc(ctx, tiledBytes, &d);
     if (rc != PROSPER_PT_OK) return rc;
+    // the caller's bytes - level 0, and with it the levels it supplies - go up as they are
+    const size_t srcBytes = source_bytes(t, mipsOut != nullptr);
+    const void *src = t.texels;
+    if (pinned)
+    {
+        std::memcpy(pinned, t.texels, srcBytes);
+        src = pinned;
+    }
+    PPT_HIP(hipMemcpyAsync(staging, src, srcBytes, hipMemcpyHostToDevice, stream));
     if (t.format == PROSPER_PT_FORMAT_BC7_UNORM)
     {
-        // the blocks go up as they are and a kernel decodes them into the tiles (pt_bc7.hpp)
-        const size_t blockBytes = (size_t)(t.width / 4u) * (t.height / 4u) * 16u;
-        const void *src = t.texels;
-        if (pinned)
-        {
-            std::memcpy(pinned, t.texels, blockBytes);
-            src = pinned;
-        }
-        PPT_HIP(hipMemcpyAsync(staging, src, blockBytes, hipMemcpyHostToDevice, stream));
+        // a kernel decodes the blocks into the tiles (pt_bc7.hpp)
         PPT_HIP(hipMemsetAsync(d, 0, tiledBytes, stream));
         launch_decode_bc7(staging, t.width, t.height, tilesX, d, stream);
     }
     else
     {
         // 8 x 4-texel tiles of one cache line each (pt_scene.hpp DeviceTexture), laid out by a kernel
-        const void *src = t.texels;
-        if (pinned)
-        {
-            std::memcpy(pinned, t.texels, (size_t)t.width * t.height * 4u);
-            src = pinned;
-        }
-        PPT_HIP(hipMemcpyAsync(staging, src, (size_t)t.width * t.height * 4u, hipMemcpyHostToDevice, stream));
         launch_retile_rgba8(staging, t.width, t.height, tilesX, d, stream);
     }
     PPT_HIP(hipGetLastError());
     *out = DeviceTexture{static_cast<const uint8_t *>(d), t.width, t.height, tilesX, 0u};
+    if (mipsOut)
+    {
+        const int mrc = build_texture_mips(ctx, t, *out, staging, stream, srgb, mipsOut);
+        if (mrc != PROSPER_PT_OK)
+        {
+            // the texture failed as a whole: its level 0 does not stay in the scene
+            device_free(ctx, d);
+            *out = DeviceTexture{nullptr, 0u, 0u, 0u, 0u};
+        }
+        return mrc;
+    }
     return PROSPER_PT_OK;
 }
 
@@ -289,6 +416,7 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
     std::memcpy(img + ms->packsOffset, ms->packs.data(), ms->packs.size() * sizeof(MaterialPack));
     std::memcpy(img + ms->alphaOffset, ms->alphaMaterials.data(), ms->alphaMaterials.size() * sizeof(AlphaMaterial));
     std::memcpy(img + ms->texturesOffset, ms->textures.data(), ms->textures.size() * sizeof(DeviceTexture));
+    if (!ms->mips.empty()) std::memcpy(img + ms->mipsOffset, ms->mips.data(), ms->mips.size() * sizeof(DeviceTextureMips));
     // the block's last readers (three flushes ago), the texel arrays / packs / bounds the tables point at
     if ((rc = ms->versions.wait_free(v, stream))) return rc;
     if ((rc = ms->uploaded.wait(stream))) return rc;
@@ -318,6 +446,7 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
     ctx->scene.materialPacks = reinterpret_cast<const MaterialPack *>(ms->dBlocks[v] + ms->packsOffset);
     ctx->scene.alphaMaterials = dAlpha;
     ctx->scene.textures = reinterpret_cast<const DeviceTexture *>(ms->dBlocks[v] + ms->texturesOffset);
+    if (!ms->mips.empty()) ctx->textureMips = reinterpret_cast<const DeviceTextureMips *>(ms->dBlocks[v] + ms->mipsOffset);
     ctx->scene.batchedTextures = ctx->debug.batchedTextures >= 0 ? (ctx->debug.batchedTextures ? 1u : 0u) : (texel_set_is_big(ms->texelBytes) ? 1u : 0u);
     ctx->packedMaterials = ms->packedMaterials;
     ctx->alphaBoundBytes = ms->alphaBoundBytes;
@@ -344,11 +473,12 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_textures: range exceeds the scene's textureCount");
     if (count == 0) return PROSPER_PT_OK;
     size_t stagingBytes = 0;
+    const bool withMips = !ms->mips.empty();
     for (uint32_t i = 0; i < count; ++i)
     {
-        const int rc = validate_texture(textures[i], first + i);
+        const int rc = validate_texture(textures[i], first + i, withMips);
         if (rc != PROSPER_PT_OK) return rc;
-        stagingBytes += texture_staging_bytes(textures[i]);
+        stagingBytes += texture_staging_bytes(textures[i], withMips);
     }
     // A material that samples a replaced texture gets its pack rebuilt from its three textures' own texels: a texture whose
     // own copy was released at upload (only packed materials sampled it) must arrive in the same call.
@@ -387,17 +517,29 @@ int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_des
     }
     size_t offset = 0;
     std::vector<uint8_t> changed(ms->textures.size(), 0);
+    const std::vector<uint8_t> baseColour = base_colour_textures(ms->materials.data(), ms->materials.size(), ms->textures.size());
     for (uint32_t i = 0; i < count; ++i)
     {
         DeviceTexture dt;
+        DeviceTextureMips dm{nullptr, 1u, 0u, {}};
         if ((rc = create_device_texture(
                  ctx, textures[i], static_cast<uint8_t *>(ms->linearStaging) + offset, ms->uploadStream.get(), &dt,
-                 static_cast<uint8_t *>(ms->pinnedStaging.ptr) + offset)))
+                 static_cast<uint8_t *>(ms->pinnedStaging.ptr) + offset, withMips ? &dm : nullptr, baseColour[first + i] != 0)))
         {
             (void)hipStreamSynchronize(ms->uploadStream.get());
             return rc;
         }
-        offset += texture_staging_bytes(textures[i]);
+        offset += texture_staging_bytes(textures[i], withMips);
+        if (withMips)
+        {
+            // (the old chain like the old level 0: a frame in flight may still read it)
+            DeviceTextureMips &oldMips = ms->mips[first + i];
+            const DeviceTexture &was = ms->textures[first + i];
+            ms->mipTexelBytes += mip_texel_bytes(dt.width, dt.height, dm.levelCount);
+            ms->mipTexelBytes -= std::min<uint64_t>(ms->mipTexelBytes, mip_texel_bytes(was.width, was.height, oldMips.levelCount));
+            retire(ctx, oldMips.texels);
+            oldMips = dm;
+        }
         const DeviceTexture &old = ms->textures[first + i];
         ms->texelBytes += (uint64_t)dt.width * dt.height * 4u;
         ms->texelBytes -= std::min<uint64_t>(ms->texelBytes, (uint64_t)old.width * old.height * 4u);
@@ -457,6 +599,98 @@ int prosper_pt_update_materials(prosper_pt_ctx *ctx, const prosper_MaterialData 
     ms->pending = true;
     ms->changes++;
     return PROSPER_PT_OK;
+}
+
+uint32_t prosper_pt_texture_mip_level_count(uint32_t width, uint32_t height)
+{
+    return width && height ? mip_level_count(width, height) : 0u;
+}
+
+int prosper_pt_check_texture_desc(const prosper_pt_texture_desc *desc, uint32_t create_flags)
+{
+    if (!desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_check_texture_desc: null argument");
+    return validate_texture(*desc, 0, (create_flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0);
+}
+
+int prosper_pt_get_texture_mips_info(prosper_pt_ctx *ctx, uint32_t texture, prosper_pt_texture_mips_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_texture_mips_info: null argument");
+    if (!(ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_get_texture_mips_info: the context was created without PROSPER_PT_CREATE_TEXTURE_MIPS");
+    if (!ctx->haveScene || !ctx->materialState) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    const MaterialState *ms = ctx->materialState;
+    if (texture >= ms->textures.size()) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_texture_mips_info: texture out of range");
+    out->width = ms->textures[texture].width;
+    out->height = ms->textures[texture].height;
+    out->levelCount = ms->mips[texture].levelCount;
+    out->srgbAveraged = ms->mips[texture].srgb;
+    out->mipTexelBytes = ms->mipTexelBytes;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_texture_level(prosper_pt_ctx *ctx, uint32_t texture, uint32_t level, void *rgba8, uint64_t bytes, void *stream)
+{
+    if (!ctx || !rgba8) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_level: null argument");
+    if (!ctx->haveScene || !ctx->materialState) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    MaterialState *ms = ctx->materialState;
+    if (texture >= ms->textures.size()) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_level: texture out of range");
+    const DeviceTexture &t = ms->textures[texture];
+    const uint32_t levels = ms->mips.empty() ? 1u : ms->mips[texture].levelCount;
+    if (level >= levels || t.width == 0)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_level: the texture has no level " + std::to_string(level));
+    const uint32_t w = std::max(t.width >> level, 1u), h = std::max(t.height >> level, 1u);
+    if (bytes != (uint64_t)w * h * 4u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_level: the level holds " + std::to_string((uint64_t)w * h * 4u) + " bytes");
+    const uint8_t *tiled = level == 0 ? t.texels : ms->mips[texture].texels + (size_t)ms->mips[texture].wordOffset[level] * 4u;
+    if (!tiled)
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_read_texture_level: level 0 of this texture lives only in a material pack");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = ms->uploaded.wait(s); // (an update's kernels run on its own stream)
+    if (rc != PROSPER_PT_OK) return rc;
+    void *linear = nullptr;
+    PPT_HIP(hipMalloc(&linear, (size_t)bytes));
+    launch_untile_level(tiled, w, h, linear, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(rgba8, linear, (size_t)bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t f = hipStreamSynchronize(s);
+    (void)hipFree(linear);
+    PPT_HIP(e);
+    PPT_HIP(f);
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_debug_sample_texture_lod(
+    prosper_pt_ctx *ctx, uint32_t texture, uint32_t sampler, const float *in6, uint32_t n, float bias, float *out5)
+{
+    if (!std::isfinite(bias)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_sample_texture_lod: the bias is not finite");
+    if (!ctx || (n && (!in6 || !out5))) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_sample_texture_lod: null argument");
+    if (!(ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_debug_sample_texture_lod: the context was created without PROSPER_PT_CREATE_TEXTURE_MIPS");
+    int rc = check_scene(ctx, "prosper_pt_debug_sample_texture_lod");
+    if (rc != PROSPER_PT_OK) return rc;
+    const MaterialState *ms = ctx->materialState;
+    if (texture == 0 || texture >= ms->textures.size() || sampler >= ms->samplers.size())
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_sample_texture_lod: texture / sampler out of range");
+    if (!ms->textures[texture].texels)
+        return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_debug_sample_texture_lod: level 0 of this texture lives only in a material pack");
+    if (n == 0) return PROSPER_PT_OK;
+    if ((rc = flush_scene_updates(ctx, nullptr, nullptr))) return rc;
+    float *dIn = nullptr, *dOut = nullptr;
+    const size_t inBytes = (size_t)n * 6u * sizeof(float), outBytes = (size_t)n * 5u * sizeof(float);
+    PPT_HIP(hipMalloc((void **)&dIn, inBytes));
+    hipError_t e = hipMalloc((void **)&dOut, outBytes);
+    if (e == hipSuccess) e = hipMemcpy(dIn, in6, inBytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+    {
+        launch_sample_texture_lod(ctx->scene, ctx->textureMips, texture, sampler, dIn, n, bias, dOut, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out5, dOut, outBytes, hipMemcpyDeviceToHost);
+    (void)hipFree(dIn);
+    (void)hipFree(dOut);
+    if (e != hipSuccess) return fail(PROSPER_PT_ERR_HIP, std::string("prosper_pt_debug_sample_texture_lod: ") + hipGetErrorString(e));
+    return mark_versions_read(ctx, nullptr);
 }
 
 } // extern "C"

@@ -13,10 +13,19 @@ namespace ppt
 // go once `stream` has been synchronised).  `pinned` (host, texture_staging_bytes(desc) bytes): the texels go through it - the
 // caller's memory has been read when the call returns, and the runtime never pins the caller's pages (which, freed soon
 // after, would stop every queue of the process for 20-30 ms while the driver unmaps them: prosper_pt_update_textures).
-size_t texture_staging_bytes(const prosper_pt_texture_desc &t);
-int validate_texture(const prosper_pt_texture_desc &t, uint32_t index);
+// `mips` (a context created with PROSPER_PT_CREATE_TEXTURE_MIPS): desc.mipLevelCount is read - validate_texture refuses a
+// count above prosper's and a BC7 level that is no whole number of blocks, the staging areas hold every supplied level -
+// and create_device_texture also builds the chain's levels >= 1 into `mipsOut` (taken from the caller where supplied,
+// generated level by level otherwise; `srgb`: averaged in linear light), on the same stream.
+size_t texture_staging_bytes(const prosper_pt_texture_desc &t, bool mips = false);
+int validate_texture(const prosper_pt_texture_desc &t, uint32_t index, bool mips = false);
 int create_device_texture(
-    prosper_pt_ctx *ctx, const prosper_pt_texture_desc &t, void *staging, hipStream_t stream, DeviceTexture *out, void *pinned = nullptr);
+    prosper_pt_ctx *ctx, const prosper_pt_texture_desc &t, void *staging, hipStream_t stream, DeviceTexture *out, void *pinned = nullptr,
+    DeviceTextureMips *mipsOut = nullptr, bool srgb = false);
+// texel bytes of the levels >= 1 of a chain (4 B per texel, without tile padding)
+uint64_t mip_texel_bytes(uint32_t width, uint32_t height, uint32_t levelCount);
+// per texture: some material samples it as base colour (index 0, "no texture", never)
+std::vector<uint8_t> base_colour_textures(const prosper_MaterialData *materials, size_t materialCount, size_t textureCount);
 
 // The interleaved copy of a material's three textures (pt_scene.hpp MaterialPack) where they share extent and sampler;
 // texels == nullptr where the material is not packable.  `wide`: 16-byte texels also for opaque materials.

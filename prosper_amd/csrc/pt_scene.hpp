@@ -124,6 +124,31 @@ struct DeviceTexture
 };
 constexpr uint32_t kTexTileW = 8, kTexTileH = 4;
 
+// Levels >= 1 of one texture's mip chain (PROSPER_PT_CREATE_TEXTURE_MIPS): one allocation, every level in
+// the DeviceTexture tiling, padded to whole tiles, back to back.  Level l has the extent max(extent >> l, 1) of level 0
+// (DeviceTexture holds it) and starts wordOffset[l] 32-bit words into `texels`.  levelCount counts level 0:
+// 1 (texels == nullptr) is a texture without further levels.  The table lives beside DeviceScene::textures, not in it:
+// the kernels that sample LOD 0 take the same arguments as ever.
+constexpr uint32_t kMaxMipLevels = 16;
+struct DeviceTextureMips
+{
+    const uint8_t *texels;
+    uint32_t levelCount;
+    uint32_t srgb; // levels were averaged in linear light (the texture is some material's base colour)
+    uint32_t wordOffset[kMaxMipLevels]; // [0] unused
+};
+// prosper's level count (src/scene/Texture.cpp:217-225): the chain stops at the level whose larger side is 4..7
+inline uint32_t mip_level_count(uint32_t width, uint32_t height)
+{
+    uint32_t m = width > height ? width : height, log2m = 0;
+    while (m > 1u)
+    {
+        m >>= 1;
+        ++log2m;
+    }
+    return log2m + 1u > 3u ? log2m + 1u - 2u : 1u;
+}
+
 // The three textures of a material - base colour, metallic-roughness, normal - are sampled at the SAME uv of every hit
 // (materials.glsl:47-119).  When they have the same extent and sampler (the usual glTF export) their texels are also
 // kept interleaved: one uint4 per texel = {base RGBA8, MR RGBA8, normal RGBA8, 0}, in 4 x 2-texel tiles of one 128-byte

@@ -104,15 +104,24 @@ def _texture_header(blob):
     return fmt, width, height, _level_sizes(width, height, fmt, max(mips, 1))
 
 
-def read_texture_raw(path):
-    """-> (DXGI format, width, height, level-0 payload bytes) of a texture-cache DDS, undecoded: BC7 blocks can go
-    to the library as they are (PROSPER_PT_FORMAT_BC7_UNORM, decoded on the GPU at upload)."""
+def read_texture_raw(path, levels=1):
+    """-> (DXGI format, width, height, payload bytes) of a texture-cache DDS, undecoded: BC7 blocks can go to the
+    library as they are (PROSPER_PT_FORMAT_BC7_UNORM, decoded on the GPU at upload).  The payload is level 0, or the
+    first `levels` levels back to back (None = all the file holds; `level_count` tells how many that is)."""
     with open(path, "rb") as f:
         blob = f.read()
     fmt, width, height, sizes = _texture_header(blob)
-    if len(blob) < 148 + sizes[0][2]:
+    nbytes = sum(s[2] for s in (sizes if levels is None else sizes[:levels]))
+    if len(blob) < 148 + nbytes:
         raise DdsError("truncated DDS payload")
-    return fmt, width, height, blob[148: 148 + sizes[0][2]]
+    return fmt, width, height, blob[148: 148 + nbytes]
+
+
+def level_count(path):
+    """Mip levels a texture-cache DDS holds."""
+    with open(path, "rb") as f:
+        blob = f.read(148)
+    return len(_texture_header(blob)[3])
 
 
 def read_texture(path, levels=1):

@@ -37,7 +37,7 @@ import zlib
 import numpy as np
 
 from . import dds, structs as S
-from .world import World
+from .world import World, mip_level_count
 
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
 _WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT2": 4, "MAT3": 9, "MAT4": 16}
@@ -314,7 +314,7 @@ _FILTERS = {9728: S.FILTER_NEAREST, 9984: S.FILTER_NEAREST, 9986: S.FILTER_NEARE
 _WRAPS = {33071: S.WRAP_CLAMP_TO_EDGE, 33648: S.WRAP_MIRRORED_REPEAT, 10497: S.WRAP_REPEAT}
 
 
-def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on_gpu=False):
+def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on_gpu=False, mip_chains=False):
     """Reads `path` (.gltf or .glb) into a World laid out the way prosper lays the same file out.
 
     With `use_texture_cache`, an image file whose `prosper_cache/<name>.dds` exists (prosper's BC7 / RGBA8 cache,
@@ -324,6 +324,9 @@ def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on
     encoder's input.  A stale or untagged cache is ignored (prosper would re-encode it from the source).
     With `bc7_on_gpu` a BC7 cache file is handed to the library undecoded (`World.add_texture_bc7`: decoded by the
     HIP kernel at upload); otherwise `prosper_amd.bc7` decodes it here - same texels either way (tested).
+    With `mip_chains` a cache file's further levels go along (`World.add_texture_bc7(levels=)` / `add_texture_chain`):
+    a context created with CREATE_TEXTURE_MIPS samples prosper's own chain instead of generating one.  An image without
+    a cache stays level 0 alone.
 
     `world.missing_images` lists the image URIs that could not be read; they become 1x1 white textures
     (what prosper's texture slot 0, `empty.png`, is)."""
@@ -357,8 +360,13 @@ def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on
                 if cached is not None and os.path.exists(cached):
                     w.cached_images.append(cached)
                     fmt, tw, th, payload = dds.read_texture_raw(cached)
+                    # (prosper writes exactly its own count; a longer chain from elsewhere is cut there)
+                    levels = min(dds.level_count(cached), mip_level_count(tw, th)) if mip_chains else 1
                     if bc7_on_gpu and fmt == dds.DXGI_FORMAT_BC7_UNORM:
-                        w.add_texture_bc7(payload, tw, th)
+                        w.add_texture_bc7(dds.read_texture_raw(cached, levels)[3] if levels > 1 else payload, tw, th, levels)
+                        continue
+                    if levels > 1:
+                        w.add_texture_chain(dds.read_texture(cached, levels=levels))
                         continue
                     rgba = dds.read_texture(cached, levels=1)[0]
                 elif "uri" in img:

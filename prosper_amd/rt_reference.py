@@ -206,6 +206,11 @@ class RtDirectIllumination:
             pass
 
 
+def renderer_lod_bias(apply_taa):
+    """Renderer::lodBias() (Renderer.cpp:709-715): -1 while TAA is applied, otherwise 0."""
+    return float(lib().prosper_host_renderer_lod_bias(int(bool(apply_taa))))
+
+
 class GBufferTracer:
     """render::GBufferTracer (csrc/host/gbuffer_tracer.hpp) on a Context the scene was uploaded to: record traces the
     G-buffer into the context's buffers and returns them as device inputs (S.RestirInputs, onDevice = 1)."""
@@ -221,6 +226,13 @@ class GBufferTracer:
     def set_opaque_only(self, opaque_only):
         """GBufferTracer::setOpaqueOnly: later records leave BLEND surfaces to ForwardRenderer.record_transparent."""
         rc = lib().prosper_host_gbuffer_tracer_set_opaque_only(self._h, int(opaque_only))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def set_texture_lod(self, enabled, lod_bias=0.0):
+        """GBufferTracer::setTextureLod / setLodBias: later records sample materials through the mip chains (a
+        CREATE_TEXTURE_MIPS context) with `lod_bias` - renderer_lod_bias(taa) is what prosper passes."""
+        rc = lib().prosper_host_gbuffer_tracer_set_texture_lod(self._h, int(bool(enabled)), lod_bias)
         if rc != 0:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
 
@@ -381,6 +393,12 @@ class ForwardRenderer:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
         self._h = h
         self._ctx = ctx
+
+    def set_texture_lod(self, enabled, lod_bias=0.0):
+        """ForwardRenderer::setTextureLod / setLodBias: later records sample the layers' materials through the mip chains."""
+        rc = lib().prosper_host_forward_renderer_set_texture_lod(self._h, int(bool(enabled)), lod_bias)
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
 
     def record_transparent(self, camera, width, height, depth=None, depth_ptr=None, ray_flags=0, frame_index=0,
                            apply_ibl=False, draw_type="Default", stream=None):

@@ -155,6 +155,7 @@ WRAP_REPEAT, WRAP_MIRRORED_REPEAT, WRAP_CLAMP_TO_EDGE = 0, 1, 2
 CREATE_MEGAKERNEL = 1 << 0
 CREATE_PERSISTENT = 1 << 1  # reserved: prosper_pt_create refuses it
 CREATE_SINGLE_CHAIN = 1 << 2
+CREATE_TEXTURE_MIPS = 1 << 3  # every material texture keeps a mip chain (generated, or supplied: TextureDesc.mipLevelCount)
 RENDER_COUNT_WORK = 1 << 0
 RENDER_PIPELINED = 1 << 1
 MAX_KERNELS = 8
@@ -175,7 +176,17 @@ class TextureDesc(C.Structure):
         ("width", C.c_uint32),
         ("height", C.c_uint32),
         ("format", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("mipLevelCount", C.c_uint32),  # read by a CREATE_TEXTURE_MIPS context only: levels held by `texels` (0 / 1: level 0)
+    ]
+
+
+class TextureMipsInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("levelCount", C.c_uint32),
+        ("srgbAveraged", C.c_uint32),
+        ("mipTexelBytes", C.c_uint64),
     ]
 
 

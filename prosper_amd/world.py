@@ -77,10 +77,48 @@ def rotate_z(angle):
 
 
 class Bc7Texture:
-    """BC7 blocks of one texture level, [N, 16] uint8, row-major."""
+    """BC7 blocks of a texture, [N, 16] uint8, row-major: level 0, or `levels` levels back to back as prosper's texture
+    cache holds them (a context created with CREATE_TEXTURE_MIPS takes the further levels as they are)."""
 
-    def __init__(self, blocks, width, height):
-        self.blocks, self.width, self.height = blocks, width, height
+    def __init__(self, blocks, width, height, levels=1):
+        self.blocks, self.width, self.height, self.levels = blocks, width, height, levels
+
+
+class TextureChain:
+    """An RGBA8 texture with a caller-supplied mip chain: `levels` = [h, w, 4] uint8 arrays, level l of extent
+    max(extent >> l, 1), kept back to back (the DDS cache's layout).  A context created without CREATE_TEXTURE_MIPS
+    reads level 0 only."""
+
+    def __init__(self, levels):
+        levels = [np.ascontiguousarray(a, np.uint8) for a in levels]
+        h, w = levels[0].shape[:2]
+        for i, a in enumerate(levels):
+            assert a.shape == (max(h >> i, 1), max(w >> i, 1), 4), "level %d has the wrong extent" % i
+        self.levels = levels
+        self.width, self.height = w, h
+        self.texels = np.concatenate([a.reshape(-1) for a in levels])
+
+
+def mip_level_count(width, height):
+    """prosper's level count (src/scene/Texture.cpp:217-225): full chain minus the two smallest levels."""
+    return max(int(max(width, height)).bit_length() - 2, 1)
+
+
+def fill_texture_desc(desc, t):
+    """One prosper_pt_texture_desc from a numpy [h, w, 4] uint8 array, a Bc7Texture or a TextureChain.  -> what must
+    stay alive while the descriptor is in use."""
+    desc.mipLevelCount = 0
+    if isinstance(t, Bc7Texture):
+        desc.texels, desc.width, desc.height, desc.format = t.blocks.ctypes.data, t.width, t.height, S.FORMAT_BC7_UNORM
+        desc.mipLevelCount = t.levels if t.levels > 1 else 0
+        return t.blocks
+    if isinstance(t, TextureChain):
+        desc.texels, desc.width, desc.height, desc.format = t.texels.ctypes.data, t.width, t.height, S.FORMAT_RGBA8_UNORM
+        desc.mipLevelCount = len(t.levels) if len(t.levels) > 1 else 0
+        return t.texels
+    a = np.ascontiguousarray(t, np.uint8)
+    desc.texels, desc.width, desc.height, desc.format = a.ctypes.data, a.shape[1], a.shape[0], S.FORMAT_RGBA8_UNORM
+    return a
 
 
 class World:
@@ -117,13 +155,19 @@ class World:
         self.textures.append(rgba8)
         return len(self.textures) - 1
 
-    def add_texture_bc7(self, blocks, width, height):
-        """Level 0 of a BC7 texture as prosper's cache stores it (`dds.read_texture_level0_raw`): the library
-        decodes it on the GPU at upload (PROSPER_PT_FORMAT_BC7_UNORM)."""
+    def add_texture_bc7(self, blocks, width, height, levels=1):
+        """A BC7 texture as prosper's cache stores it (`dds.read_texture_raw`): level 0, or the first `levels` levels
+        back to back.  The library decodes it on the GPU at upload (PROSPER_PT_FORMAT_BC7_UNORM)."""
         blocks = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if not isinstance(blocks, np.ndarray) else blocks,
                                       dtype=np.uint8).reshape(-1, 16)
-        assert width % 4 == 0 and height % 4 == 0 and blocks.shape[0] == (width // 4) * (height // 4)
-        self.textures.append(Bc7Texture(blocks, width, height))
+        count = sum((max(width >> l, 1) // 4) * (max(height >> l, 1) // 4) for l in range(levels))
+        assert width % 4 == 0 and height % 4 == 0 and blocks.shape[0] == count
+        self.textures.append(Bc7Texture(blocks, width, height, levels))
+        return len(self.textures) - 1
+
+    def add_texture_chain(self, levels):
+        """An RGBA8 texture with its mip chain supplied ([h, w, 4] uint8 per level; TextureChain)."""
+        self.textures.append(TextureChain(levels))
         return len(self.textures) - 1
 
     def add_sampler(self, mag=S.FILTER_LINEAR, min_=S.FILTER_LINEAR, wrap_s=S.WRAP_REPEAT, wrap_t=S.WRAP_REPEAT):
@@ -315,15 +359,7 @@ class World:
         f["draw_instance_count"] = len(draw_instances)
         f["materials"] = (S.MaterialData * len(self.materials))(*self.materials)
         tex = (S.TextureDesc * len(self.textures))()
-        for i, t in enumerate(self.textures):
-            if isinstance(t, Bc7Texture):
-                tex[i].texels = t.blocks.ctypes.data
-                tex[i].height, tex[i].width = t.height, t.width
-                tex[i].format = S.FORMAT_BC7_UNORM
-                continue
-            tex[i].texels = t.ctypes.data
-            tex[i].height, tex[i].width = t.shape[0], t.shape[1]
-            tex[i].format = S.FORMAT_RGBA8_UNORM
+        f["_texels"] = [fill_texture_desc(tex[i], t) for i, t in enumerate(self.textures)]
         f["textures"] = tex
         smp = (S.SamplerDesc * len(self.samplers))()
         for i, s in enumerate(self.samplers):

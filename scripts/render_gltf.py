@@ -89,6 +89,8 @@ def main():
     ap.add_argument("--particle-source", type=int, default=0, help="with --particles: the draw instance whose vertices emit")
     ap.add_argument("--particle-steps", type=int, default=120, help="with --particles: steps of 1/60 s before the first frame")
     ap.add_argument("--taa", action="store_true", help="with --deferred: temporal anti-aliasing over jittered frames")
+    ap.add_argument("--texture-lod", action="store_true",
+                    help="with --deferred: the G-buffer samples material textures through mip chains (bias -1 under --taa)")
     ap.add_argument("--frames", type=int, default=8, help="with --taa: frames to resolve (8 is one Halton cycle)")
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
@@ -103,7 +105,8 @@ def main():
     from prosper_amd import capi, dds, gltf, ktx, structs as S
     from prosper_amd.rt_reference import Bloom, Camera, DepthOfField, ForwardRenderer, GBufferTracer, TemporalAntiAliasing
     w, h = (int(v) for v in args.size.lower().split("x"))
-    world = gltf.load_gltf(args.gltf, bc7_on_gpu=True)  # prosper_cache BC7 files are decoded by the library at upload
+    # prosper_cache BC7 files are decoded by the library at upload; with --texture-lod their mip levels go along
+    world = gltf.load_gltf(args.gltf, bc7_on_gpu=True, mip_chains=args.texture_lod)
     if world.missing_images:
         print("missing images replaced by white: %s" % ", ".join(world.missing_images), file=sys.stderr)
     if args.env:
@@ -118,7 +121,7 @@ def main():
         focus = args.focus or math.dist(c["eye"], c["target"])
         hcam.set_parameters(c["fov"], c["zN"], c["zF"], args.aperture, focus)
     cam, focal = hcam.update_buffer()
-    ctx = capi.Context(0)
+    ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
     ctx.upload_scene(world)
     st = ctx.scene_stats()
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_SKIP_HISTORY | (S.PC_FLAG_IBL if args.env else 0)
@@ -133,6 +136,11 @@ def main():
         forward = ForwardRenderer(ctx) if args.transparents else None
         tracer = GBufferTracer(ctx)
         tracer.set_opaque_only(args.transparents)  # the BLEND surfaces are the transparent pass's
+        if args.texture_lod:
+            from prosper_amd.rt_reference import renderer_lod_bias
+            tracer.set_texture_lod(True, renderer_lod_bias(args.taa))  # Renderer::lodBias(): -1 while TAA is on
+            if forward:
+                forward.set_texture_lod(True, renderer_lod_bias(args.taa))
         if args.taa:
             hcam.set_jitter(True)
             taa = TemporalAntiAliasing(ctx)
