@@ -249,6 +249,15 @@ int prosper_host_taa_record(
     prosper_pt_taa_pc *outPushConstants);
 void prosper_host_taa_release_preserved(prosper_host_taa *pass);
 
+/* scene::Animations (host/animations.hpp; reference src/scene/World.hpp updateAnimations / updateScene) on a context
+ * (borrowed) whose scene is uploaded: create = prosper_pt_set_animations of `desc` (borrowed for the call); update =
+ * World::updateAnimations(timeS), staged for the next render (prosper_pt_animate); end_time = Scene::endTimeS. */
+typedef struct prosper_host_animations prosper_host_animations;
+int prosper_host_animations_create(prosper_pt_ctx *ctx, const prosper_pt_animation_desc *desc, prosper_host_animations **out);
+void prosper_host_animations_destroy(prosper_host_animations *animations);
+int prosper_host_animations_update(prosper_host_animations *animations, float timeS);
+float prosper_host_animations_end_time(const prosper_host_animations *animations);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,6 +375,114 @@ enum
 };
 int prosper_pt_update_transforms_async(
     prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, uint32_t flags, void *stream);
+/* ---- glTF keyframe animation, evaluated on the GPU ahead of the refit ----
+ * World::updateAnimations + World::updateScene (src/scene/Animations.hpp, Accessors.cpp:25-75, World.cpp:349-466) as two
+ * kernels at the head of the refit's chain of launches: one thread per animated (node, path) samples its keyframes into the
+ * node's translation / rotation / scale, one thread per node multiplies the chain of its ancestors down and writes the
+ * ModelInstanceTransforms entry, the light fields and the camera record of what the node carries.  A frame's update is one
+ * float.
+ *   prosper_pt_set_animations   the scene's node tree and its channels (flat tables, borrowed for the call); the scene must
+ *                               be uploaded, and a new prosper_pt_upload_scene forgets them.  Nodes come in prosper's scene-node
+ *                               order (WorldData.cpp:1364-1456): a parent has a lower index than its child.  The HAS_* flags say
+ *                               which components the node keeps (a static one within 1e-3 of the identity is dropped,
+ *                               WorldData.cpp:1197-1211; one a channel targets is kept whatever the flag says, :1237-1272).
+ *                               Where several channels target one (node, path) the last one wins.
+ *   prosper_pt_animate          stages `timeS` like prosper_pt_update_transforms stages a table: the kernels run at the head of
+ *                               the next render's chain, into the next scene version (and the next light version when a light's
+ *                               node is bound); PROSPER_PT_UPDATE_NOW enqueues them on `stream` inside the call.  A
+ *                               prosper_pt_update_transforms that is still pending is the base table, otherwise the current
+ *                               table is; only entries a node binds are overwritten.
+ * Refused by prosper_pt_set_animations: no scene (PROSPER_PT_ERR_NO_SCENE); a wrong struct_size, an index out of range, a parent
+ * that does not precede its child, a model instance or light bound by two nodes, more than one CAMERA node, keyCount = 0,
+ * key times that decrease, offsets past the arrays, a path / interpolation that does not exist, a valueWidth other than 3
+ * for translation and scale or 4 for rotation.  By prosper_pt_animate: no animations set, unknown flags, a time that is not
+ * finite. */
+#define PROSPER_PT_ANIMATION_NONE 0xFFFFFFFFu
+enum
+{
+    PROSPER_PT_NODE_HAS_TRANSLATION = 1u << 0,
+    PROSPER_PT_NODE_HAS_ROTATION = 1u << 1,
+    PROSPER_PT_NODE_HAS_SCALE = 1u << 2,
+    PROSPER_PT_NODE_DIRECTIONAL_LIGHT = 1u << 3, /* the node carries the scene's directional light */
+    PROSPER_PT_NODE_CAMERA = 1u << 4,            /* the node carries the current camera */
+};
+enum
+{
+    PROSPER_PT_ANIMATION_PATH_TRANSLATION = 0,
+    PROSPER_PT_ANIMATION_PATH_ROTATION = 1,
+    PROSPER_PT_ANIMATION_PATH_SCALE = 2,
+};
+enum
+{
+    PROSPER_PT_ANIMATION_STEP = 0,
+    PROSPER_PT_ANIMATION_LINEAR = 1,
+    PROSPER_PT_ANIMATION_CUBICSPLINE = 2,
+};
+typedef struct prosper_pt_animation_node
+{
+    uint32_t parent;        /* PROSPER_PT_ANIMATION_NONE: a root */
+    uint32_t modelInstance; /* index into the scene's ModelInstanceTransforms, or PROSPER_PT_ANIMATION_NONE */
+    uint32_t pointLight;    /* index into PointLightsBuffer.lights, or PROSPER_PT_ANIMATION_NONE */
+    uint32_t spotLight;     /* index into SpotLightsBuffer.lights, or PROSPER_PT_ANIMATION_NONE */
+    uint32_t flags;         /* PROSPER_PT_NODE_* */
+    float translation[3];   /* the static pose */
+    float rotation[4];      /* x, y, z, w as glTF stores it */
+    float scale[3];
+} prosper_pt_animation_node;
+typedef struct prosper_pt_animation_channel
+{
+    uint32_t node;
+    uint32_t path;          /* PROSPER_PT_ANIMATION_PATH_* */
+    uint32_t interpolation; /* PROSPER_PT_ANIMATION_STEP / _LINEAR / _CUBICSPLINE */
+    uint32_t timeOffset;    /* first of keyCount key times in times[] */
+    uint32_t keyCount;
+    uint32_t valueOffset;   /* first float in values[]: valueWidth per key, three times that for CUBICSPLINE
+                             * (in-tangent, value, out-tangent) */
+    uint32_t valueWidth;    /* 3 for translation and scale, 4 for rotation */
+    float startTimeS;       /* min and max of the input accessor */
+    float endTimeS;
+} prosper_pt_animation_channel;
+typedef struct prosper_pt_animation_desc
+{
+    uint32_t struct_size;
+    uint32_t nodeCount;
+    const prosper_pt_animation_node *nodes;
+    uint32_t channelCount;
+    uint32_t timeCount;
+    const prosper_pt_animation_channel *channels;
+    const float *times;
+    const float *values;
+    uint32_t valueCount; /* floats */
+    uint32_t reserved;
+} prosper_pt_animation_desc;
+int prosper_pt_set_animations(prosper_pt_ctx *ctx, const prosper_pt_animation_desc *desc);
+/* `flags`: 0 or PROSPER_PT_UPDATE_NOW. */
+int prosper_pt_animate(prosper_pt_ctx *ctx, float timeS, uint32_t flags, void *stream);
+typedef struct prosper_pt_animation_state
+{
+    float endTimeS;             /* the largest channel end (Scene::endTimeS) */
+    uint32_t nodeCount;
+    uint32_t animatedNodeCount; /* nodes a channel targets, and their descendants (WorldData.cpp:1279-1320) */
+    uint32_t updates;           /* prosper_pt_animate calls whose kernels have been enqueued */
+    uint32_t cameraValid;       /* 1: a CAMERA node exists and an update has run */
+    uint32_t lightUpdates;      /* light versions made since the upload, by prosper_pt_update_lights or by an update here */
+    float eye[3], target[3], up[3]; /* CameraTransform of the last enqueued update (World.cpp:416-426) */
+    float sampleMs, hierarchyMs;    /* the two kernels of the last enqueued update, between events on its stream */
+} prosper_pt_animation_state;
+/* Enqueues a staged update first and waits for the last one's camera record.  Before prosper_pt_set_animations: all zero. */
+int prosper_pt_get_animation_state(prosper_pt_ctx *ctx, prosper_pt_animation_state *out);
+/* The scene's ModelInstanceTransforms table as the device holds it (`which` = 0; a staged update is enqueued first), or as
+ * it held it before the last animated update (`which` = 1; the current one while none has run): what
+ * prosper_pt_trace_gbuffer_velocity takes as previousTransforms.  `count` = the scene's modelInstanceCount.  Synchronises. */
+int prosper_pt_read_animated_transforms(prosper_pt_ctx *ctx, uint32_t which, prosper_ModelInstanceTransforms *out, uint32_t count);
+/* The three light buffers as the device holds them (a staged update is enqueued first).  Synchronises. */
+int prosper_pt_read_lights(
+    prosper_pt_ctx *ctx, prosper_DirectionalLightParameters *directionalLight, prosper_PointLightsBuffer *pointLights,
+    prosper_SpotLightsBuffer *spotLights);
+/* Test hook: per node the translation, rotation (x, y, z, w) and scale of the last update (`trs`, 10 floats a node) and its
+ * world matrix (`world`, 16 floats a node, column by column); either may be NULL.  `nodeCount` = the animations' own. */
+int prosper_pt_debug_read_animation_nodes(prosper_pt_ctx *ctx, float *trs, float *world, uint32_t nodeCount);
+
 /* ---- incremental adoption: streamed-in textures and materials ----
  * prosper loads a scene in the background and adopts what has arrived a few items per frame: new images get their slot in
  * materialTextures[] (src/scene/WorldData.cpp:2182-2206), a material switches from its placeholder - the default material

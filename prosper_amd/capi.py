@@ -73,6 +73,13 @@ def lib():
     L.prosper_pt_finish_mesh_updates.argtypes = [vp]
     L.prosper_pt_update_transforms.argtypes = [vp, vp, u32]
     L.prosper_pt_update_transforms_async.argtypes = [vp, vp, u32, u32, vp]
+    L.prosper_pt_set_animations.argtypes = [vp, C.POINTER(S.AnimationDesc)]
+    L.prosper_pt_animate.argtypes = [vp, C.c_float, u32, vp]
+    L.prosper_pt_get_animation_state.argtypes = [vp, C.POINTER(S.AnimationStateInfo)]
+    L.prosper_pt_read_animated_transforms.argtypes = [vp, u32, vp, u32]
+    L.prosper_pt_read_lights.argtypes = [
+        vp, C.POINTER(S.DirectionalLightParameters), C.POINTER(S.PointLightsBuffer), C.POINTER(S.SpotLightsBuffer)]
+    L.prosper_pt_debug_read_animation_nodes.argtypes = [vp, vp, vp, u32]
     L.prosper_pt_rebuild_hierarchy.argtypes = [vp]
     L.prosper_pt_get_hierarchy_state.argtypes = [vp, C.POINTER(S.HierarchyState)]
     L.prosper_pt_debug_read_nodes.argtypes = [vp, vp, C.c_size_t]
@@ -277,6 +284,12 @@ def lib():
     L.prosper_host_taa_record.argtypes = [vp, u32, u32, C.POINTER(S.TaaInputs), vp, C.POINTER(S.TaaPC)]
     L.prosper_host_taa_release_preserved.argtypes = [vp]
     L.prosper_host_taa_release_preserved.restype = None
+    L.prosper_host_animations_create.argtypes = [vp, C.POINTER(S.AnimationDesc), C.POINTER(vp)]
+    L.prosper_host_animations_destroy.argtypes = [vp]
+    L.prosper_host_animations_destroy.restype = None
+    L.prosper_host_animations_update.argtypes = [vp, C.c_float]
+    L.prosper_host_animations_end_time.argtypes = [vp]
+    L.prosper_host_animations_end_time.restype = C.c_float
     L.prosper_host_tiled_rt_reference_create.argtypes = [i32, u32, u32, vp, u32, u32, C.POINTER(vp)]
     L.prosper_host_tiled_rt_reference_destroy.argtypes = [vp]
     L.prosper_host_tiled_rt_reference_destroy.restype = None
@@ -380,6 +393,7 @@ class Context:
         self._base_debug = None
         self._debug_seen = -1
         self._world = None
+        self._animation_nodes = 0
         self._restir_extent = None
         if _borrowed is not None:
             self._h = C.c_void_p(_borrowed)
@@ -457,6 +471,46 @@ class Context:
         _check(lib().prosper_pt_update_transforms_async(self._h, C.cast(t, C.c_void_p), len(world.model_instances),
                                                          S.UPDATE_NOW if now else 0, C.c_void_p(stream)))
         self._world = world
+
+    # ---- keyframe animation (prosper_amd/animation.py makes the tables of a glTF) ----
+    def set_animations(self, tables):
+        """The node tree and channels of the uploaded scene: an `animation.AnimationTables`."""
+        desc = tables.desc()
+        _check(lib().prosper_pt_set_animations(self._h, C.byref(desc)))
+        self._animation_nodes = len(tables.nodes)
+
+    def animate(self, time_s, stream=None, now=None):
+        """World::updateAnimations(timeS) + updateScene: staged; the kernels run ahead of the refit at the head of the next
+        render's chain, or on `stream` inside the call with `now` (default: whenever a stream is given)."""
+        if now is None:
+            now = stream is not None
+        _check(lib().prosper_pt_animate(self._h, float(time_s), S.UPDATE_NOW if now else 0, C.c_void_p(stream)))
+
+    def animation_state(self):
+        st = S.AnimationStateInfo()
+        _check(lib().prosper_pt_get_animation_state(self._h, C.byref(st)))
+        return st
+
+    def read_animated_transforms(self, previous=False):
+        """The ModelInstanceTransforms table the device holds (or held before the last animated update): a ctypes array
+        that prosper_pt_update_transforms / a velocity trace's previousTransforms take as it is."""
+        n = len(self._world.model_instances)
+        out = (S.ModelInstanceTransforms * max(1, n))()
+        _check(lib().prosper_pt_read_animated_transforms(self._h, 1 if previous else 0, C.cast(out, C.c_void_p), n))
+        return out
+
+    def read_lights(self):
+        """(DirectionalLightParameters, PointLightsBuffer, SpotLightsBuffer) as the device holds them."""
+        d, p, s = S.DirectionalLightParameters(), S.PointLightsBuffer(), S.SpotLightsBuffer()
+        _check(lib().prosper_pt_read_lights(self._h, C.byref(d), C.byref(p), C.byref(s)))
+        return d, p, s
+
+    def read_animation_nodes(self):
+        """Test hook: (trs [nodes, 10], world [nodes, 4, 4] with world[n, column, row]) of the last update."""
+        n = self._animation_nodes
+        trs, world = np.zeros((n, 10), np.float32), np.zeros((n, 4, 4), np.float32)
+        _check(lib().prosper_pt_debug_read_animation_nodes(self._h, trs.ctypes.data, world.ctypes.data, n))
+        return trs, world
 
     def update_textures(self, textures, first):
         """Replaces materialTextures[first .. first + len(textures)): numpy [h, w, 4] uint8 arrays, world.Bc7Texture or

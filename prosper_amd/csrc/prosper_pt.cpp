@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bvh_build.hpp"
+#include "pt_animation.hpp"
 #include "pt_context.hpp"
 #include "pt_geometry.hpp"
 #include "pt_kernels.hpp"
@@ -797,7 +798,7 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
     if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
-        !create_particles_passes(ctx))
+        !create_particles_passes(ctx) || !create_animation_state(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -857,6 +858,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_bloom_passes(ctx);
     destroy_taa_passes(ctx);
     destroy_particles_passes(ctx);
+    destroy_animation_state(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
@@ -870,6 +872,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());
+    forget_animations(ctx); // (its read-back with it: the new scene's mirrors are the new scene's)
     free_scene(ctx);
     rc = upload_scene_impl(ctx, scene);
     if (rc != PROSPER_PT_OK)
@@ -920,6 +923,7 @@ int prosper_pt_update_lights(
     if (pointLights->count > PROSPER_MAX_POINT_LIGHT_COUNT || spotLights->count > PROSPER_MAX_SPOT_LIGHT_COUNT)
         return fail(PROSPER_PT_ERR_SCENE, "light count exceeds 1024");
     LightState *ls = ctx->lights;
+    if (const int rc = sync_animation_mirrors(ctx)) return rc; // (an animated update may have moved the lights)
     // prosper rewrites the buffers every frame (World.cpp:531-535) and mostly with what they held: that costs a memcmp
     if (std::memcmp(&ls->mirror->directional, directionalLight, sizeof(*directionalLight)) == 0 &&
         std::memcmp(&ls->mirror->points, pointLights, sizeof(*pointLights)) == 0 &&
@@ -950,7 +954,8 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
     AccelState *acc = ctx->accel;
     const auto t0 = std::chrono::steady_clock::now();
     {
-        const int frc = flush_pending_update(ctx, nullptr); // the moved triangles must be in the flat array
+        int frc = flush_pending_update(ctx, nullptr); // the moved triangles must be in the flat array
+        if (frc == PROSPER_PT_OK) frc = sync_animation_mirrors(ctx);
         if (frc != PROSPER_PT_OK) return frc;
     }
     PPT_HIP(hipDeviceSynchronize()); // renders in flight read the old hierarchy
@@ -1013,9 +1018,14 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx);
 static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
 {
     AccelState *acc = ctx->accel;
-    if (!acc || !acc->pending) return PROSPER_PT_OK;
+    if (!acc) return PROSPER_PT_OK;
+    // a staged prosper_pt_animate: the table of the new version is the staged one (or the current one) with the entries
+    // the scene's nodes bind evaluated over it, ahead of the refit
+    const bool animate = animation_pending(ctx);
+    if (!acc->pending && !animate) return PROSPER_PT_OK;
+    const uint32_t tableCount = acc->pending ? acc->pendingCount : (uint32_t)acc->transforms.size();
     const uint32_t v = acc->versions.next();
-    const size_t transformBytes = sizeof(prosper_ModelInstanceTransforms) * (acc->pendingCount ? acc->pendingCount : 1);
+    const size_t transformBytes = sizeof(prosper_ModelInstanceTransforms) * (tableCount ? tableCount : 1);
     const size_t triBytes = sizeof(WorldTriangle) * (size_t)(acc->total ? acc->total : 1);
     void *d = nullptr;
     int rc;
@@ -1047,8 +1057,34 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
         PPT_HIP(hipMemcpyAsync(acc->dNodesV[v], acc->dNodes, (size_t)acc->nodeCount * sizeof(BvhNode), hipMemcpyDeviceToDevice, stream));
         acc->nodesCurrent[v] = true;
     }
-    PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], acc->staging.pending_buffer(), sizeof(prosper_ModelInstanceTransforms) * acc->pendingCount, hipMemcpyHostToDevice, stream));
-    if ((rc = acc->staging.copy_enqueued(stream))) return rc;
+    if (acc->pending)
+    {
+        PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], acc->staging.pending_buffer(), sizeof(prosper_ModelInstanceTransforms) * acc->pendingCount, hipMemcpyHostToDevice, stream));
+        if ((rc = acc->staging.copy_enqueued(stream))) return rc;
+    }
+    else if (tableCount)
+        PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], ctx->dTransforms, sizeof(prosper_ModelInstanceTransforms) * tableCount, hipMemcpyDeviceToDevice, stream));
+    // The lights its nodes carry go into the next light version, a copy of the current one, ordered like a flushed
+    // prosper_pt_update_lights (a staged one is flushed first: it is what the copy starts from).
+    LightState *ls = ctx->lights;
+    const bool animateLights = animate && ls && animation_moves_lights(ctx);
+    uint32_t lv = 0;
+    if (animateLights)
+    {
+        if ((rc = flush_pending_lights(ctx, stream))) return rc;
+        lv = ls->versions.next();
+        if (!ls->dBlocks[lv])
+        {
+            if ((rc = device_alloc(ctx, sizeof(LightBlock), &d))) return rc;
+            ls->dBlocks[lv] = static_cast<LightBlock *>(d);
+        }
+        if ((rc = ls->versions.wait_free(lv, stream))) return rc;
+        if ((rc = ls->ready.wait(stream))) return rc;
+        PPT_HIP(hipMemcpyAsync(ls->dBlocks[lv], ls->dBlocks[ls->versions.cur], sizeof(LightBlock), hipMemcpyDeviceToDevice, stream));
+        if ((rc = ls->versions.mark_read(stream))) return rc; // (the copy read the current version)
+    }
+    if (animate && (rc = enqueue_animation(ctx, acc->dTransformsV[v], tableCount, animateLights ? ls->dBlocks[lv] : nullptr, stream))) return rc;
+    if (animateLights && (rc = ls->ready.record(stream))) return rc;
     // world-space triangles again, in both orders (the shading and any-hit records hold object-space attributes and stay
     // as they are), then the boxes.  (Also when only transforms of instances without geometry changed: a version must be
     // whole.)
@@ -1072,6 +1108,15 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
     acc->refits++;
     acc->pending = false;
     acc->stale = false;
+    if (animateLights)
+    {
+        ls->versions.commit(lv);
+        ctx->scene.directionalLight = &ls->dBlocks[lv]->directional;
+        ctx->scene.pointLights = &ls->dBlocks[lv]->points;
+        ctx->scene.spotLights = &ls->dBlocks[lv]->spots;
+        ls->updates++;
+    }
+    if (animate) animation_committed(ctx);
     return PROSPER_PT_OK;
 }
 
@@ -1174,6 +1219,7 @@ int prepare_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, const pros
 int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count)
 {
     AccelState *acc = ctx->accel;
+    if (const int src = sync_animation_mirrors(ctx)) return src; // (the table an animated update left on the device)
     const auto t0 = std::chrono::steady_clock::now();
     // which instances moved (World::updateScene rewrites every transform each frame, World.cpp:359-466; most are unchanged)
     bool any = acc->stale;
@@ -1245,6 +1291,25 @@ int prosper_pt_update_transforms_async(
     if (flags & ~(uint32_t)PROSPER_PT_UPDATE_NOW) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_transforms_async: unknown flag");
     const int rc = check_update_arguments(ctx, transforms, count);
     return rc != PROSPER_PT_OK ? rc : update_transforms_impl(ctx, transforms, count, static_cast<hipStream_t>(stream), (flags & PROSPER_PT_UPDATE_NOW) != 0);
+}
+
+int prosper_pt_animate(prosper_pt_ctx *ctx, float timeS, uint32_t flags, void *stream)
+{
+    if (flags & ~(uint32_t)PROSPER_PT_UPDATE_NOW) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: unknown flag");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: null argument");
+    if (!std::isfinite(timeS)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: timeS is not finite");
+    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    int rc = stage_animation(ctx, timeS);
+    if (rc != PROSPER_PT_OK) return rc;
+    // like a staged table (stage_transforms): refits leave the tree's measure behind, and once it has grown too far the
+    // instances that moved are split again in the background
+    AccelState *acc = ctx->accel;
+    PPT_HIP(hipSetDevice(ctx->device));
+    if ((rc = poll_refit_cost(acc, false))) return rc;
+    if (ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
+    if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild && (rc = start_mesh_build(ctx, true))) return rc;
+    if (!(flags & PROSPER_PT_UPDATE_NOW)) return PROSPER_PT_OK;
+    return flush_pending_update(ctx, static_cast<hipStream_t>(stream));
 }
 
 int prosper_pt_rebuild_hierarchy(prosper_pt_ctx *ctx)

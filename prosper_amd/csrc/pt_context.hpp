@@ -82,6 +82,9 @@ void forget_taa_history(prosper_pt_ctx *ctx);
 struct ParticlesPassState;
 bool create_particles_passes(prosper_pt_ctx *ctx);
 void destroy_particles_passes(prosper_pt_ctx *ctx);
+// State of the keyframe animation (pt_animation.hip, pt_animation.hpp): the node and channel tables of the scene, the
+// staged time and the read-back that feeds the host mirrors below.  Made and freed like the others.
+struct AnimationState;
 
 #pragma GCC visibility pop
 
@@ -313,6 +316,7 @@ struct prosper_pt_ctx
     ppt::BloomPassState *bloomPasses = nullptr;
     ppt::TaaPassState *taaPasses = nullptr;
     ppt::ParticlesPassState *particlesPasses = nullptr;
+    ppt::AnimationState *animation = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

@@ -1,4 +1,5 @@
 // pt_geometry.cpp — see pt_geometry.hpp.
+#include "pt_animation.hpp"
 #include "pt_geometry.hpp"
 
 #include <algorithm>
@@ -490,6 +491,7 @@ static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild)
     AccelState *old = ctx->accel;
     auto layout = std::make_shared<GeometryLayout>();
     int rc;
+    if ((rc = sync_animation_mirrors(ctx))) return rc; // (old->transforms below: what an animated update left on the device)
     if ((rc = layout_geometry(*gs, ms->materials.data(), *layout))) return rc;
     // the subtrees that are split again: model instances that became complete, and those that moved since the last build
     auto changed = std::make_shared<std::vector<uint8_t>>(layout->ranges.size(), 0);
@@ -631,6 +633,9 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
     while (MeshBuild *b = ctx->meshBuild)
     {
         if (!wait && b->done.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return PROSPER_PT_OK;
+        // (old->transforms below: animated updates that ran while the build did; before the build is taken, so that a
+        // failure here leaves it to the next poll)
+        if (const int src = sync_animation_mirrors(ctx)) return src;
         const int built = b->done.get();
         GeometryState *gs = ctx->geometry;
         MaterialState *ms = ctx->materialState;
@@ -665,6 +670,7 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
             retire(ctx, old->dTransformsV[v]);
         }
         ctx->retiredAccel.push_back(old);
+        acc->refits = std::max(acc->refits, old->refits); // (refits of the old generation while the build ran count too)
         ctx->accel = acc;
         DeviceScene &s = ctx->scene;
         s.nodes = b->scene.nodes;

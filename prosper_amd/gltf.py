@@ -281,8 +281,9 @@ def _decompose(m):
 _SRT_THRESHOLD = 0.001  # WorldData.cpp:1197
 
 
-def _node_local_matrix(node):
-    """The node's T * R * S with components within 1e-3 of identity dropped, as the reference keeps them."""
+def node_trs(node):
+    """The node's (translation, rotation (x, y, z, w), scale) in float32 and which of them the reference keeps: a
+    component within 1e-3 of identity is dropped (WorldData.cpp:1179-1211)."""
     translation, rotation, scale = np.zeros(3), (0.0, 0.0, 0.0, 1.0), np.ones(3)
     if "matrix" in node:
         translation, rotation, scale = _decompose(node["matrix"])
@@ -292,15 +293,24 @@ def _node_local_matrix(node):
         rotation = tuple(node["rotation"])
     if "scale" in node:
         scale = np.asarray(node["scale"], np.float64)
+    t, r, sc = np.asarray(translation, np.float32), np.asarray(rotation, np.float32), np.asarray(scale, np.float32)
+    has_t = bool(np.any(np.abs(t) > _SRT_THRESHOLD))
+    has_r = any(abs(a) > _SRT_THRESHOLD for a in _euler_angles(r))
+    has_s = bool(np.any(sc < 1.0 - _SRT_THRESHOLD) or np.any(sc > 1.0 + _SRT_THRESHOLD))
+    return (t, r, sc), (has_t, has_r, has_s)
+
+
+def _node_local_matrix(node):
+    """The node's T * R * S with components within 1e-3 of identity dropped, as the reference keeps them."""
+    (translation, rotation, sc), (has_t, has_r, has_s) = node_trs(node)
     m = np.eye(4)
-    if np.any(np.abs(np.asarray(translation, np.float32)) > _SRT_THRESHOLD):
+    if has_t:
         t = np.eye(4)
-        t[:3, 3] = np.asarray(translation, np.float32)
+        t[:3, 3] = translation
         m = m @ t
-    if any(abs(a) > _SRT_THRESHOLD for a in _euler_angles(np.asarray(rotation, np.float32))):
-        m = m @ _quat_to_mat4(np.asarray(rotation, np.float32))
-    sc = np.asarray(scale, np.float32)
-    if np.any(sc < 1.0 - _SRT_THRESHOLD) or np.any(sc > 1.0 + _SRT_THRESHOLD):
+    if has_r:
+        m = m @ _quat_to_mat4(rotation)
+    if has_s:
         m = m @ np.diag([float(sc[0]), float(sc[1]), float(sc[2]), 1.0])
     return m
 

@@ -288,6 +288,38 @@ class HierarchyState(C.Structure):
                 ("geometryBuildRunning", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# ---- keyframe animation (prosper_pt_set_animations / prosper_pt_animate) ----
+ANIMATION_NONE = 0xFFFFFFFF
+NODE_HAS_TRANSLATION, NODE_HAS_ROTATION, NODE_HAS_SCALE, NODE_DIRECTIONAL_LIGHT, NODE_CAMERA = 1, 2, 4, 8, 16
+ANIMATION_PATH_TRANSLATION, ANIMATION_PATH_ROTATION, ANIMATION_PATH_SCALE = 0, 1, 2
+ANIMATION_STEP, ANIMATION_LINEAR, ANIMATION_CUBICSPLINE = 0, 1, 2
+
+
+class AnimationNode(C.Structure):
+    _fields_ = [("parent", C.c_uint32), ("modelInstance", C.c_uint32), ("pointLight", C.c_uint32), ("spotLight", C.c_uint32),
+                ("flags", C.c_uint32), ("translation", C.c_float * 3), ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
+
+
+class AnimationChannel(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("timeOffset", C.c_uint32),
+                ("keyCount", C.c_uint32), ("valueOffset", C.c_uint32), ("valueWidth", C.c_uint32),
+                ("startTimeS", C.c_float), ("endTimeS", C.c_float)]
+
+
+class AnimationDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nodeCount", C.c_uint32), ("nodes", C.c_void_p),
+                ("channelCount", C.c_uint32), ("timeCount", C.c_uint32), ("channels", C.c_void_p),
+                ("times", C.c_void_p), ("values", C.c_void_p), ("valueCount", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AnimationStateInfo(C.Structure):
+    """prosper_pt_animation_state"""
+
+    _fields_ = [("endTimeS", C.c_float), ("nodeCount", C.c_uint32), ("animatedNodeCount", C.c_uint32), ("updates", C.c_uint32),
+                ("cameraValid", C.c_uint32), ("lightUpdates", C.c_uint32), ("eye", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3),
+                ("sampleMs", C.c_float), ("hierarchyMs", C.c_float)]
+
+
 class DebugOptions(C.Structure):
     """prosper_pt_debug_options (include/prosper_pt/prosper_pt.h): tuning / test options of a context."""
 

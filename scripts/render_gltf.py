@@ -35,6 +35,11 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  G-buffer -> shading -> sky -> bloom -> prosper_pt_taa_resolve -> Camera::endFrame, through
                                  the host layer's GBufferTracer and TemporalAntiAliasing; depth of field and the tone map
                                  run after the last frame (Renderer.cpp:516-573's order)
+    --time T [--time-step DT]    an animated glTF at T seconds: its nodes and channels go to the library
+                                 (prosper_amd/animation.py -> prosper_pt_set_animations) and prosper_pt_animate(T) runs on
+                                 the GPU ahead of the refit, before anything is rendered; the camera node's animated pose is
+                                 the camera unless --eye / --target are given.  Under --taa every jittered frame advances
+                                 the time by DT (default 1/60 s) and hands its table to the velocity target
     --deferred --sky --dof --aperture A --focus D
                                  prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
                                  aperture diameter A and focus distance D in scene units drive the push constants
@@ -95,6 +100,8 @@ def main():
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
     ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
+    ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
+    ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     args = ap.parse_args()
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
@@ -115,15 +122,24 @@ def main():
         world.camera["eye"] = tuple(float(v) for v in args.eye.split(","))
     if args.target:
         world.camera["target"] = tuple(float(v) for v in args.target.split(","))
+    ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
+    ctx.upload_scene(world)
+    st = ctx.scene_stats()
+    if args.time is not None:
+        from prosper_amd import animation
+        ctx.set_animations(animation.load_animations(args.gltf))
+        ctx.animate(args.time)
+        pose = ctx.animation_state()
+        print("animation: %d of %d nodes animated, end time %.3f s, evaluated at %.3f s" % (
+            pose.animatedNodeCount, pose.nodeCount, pose.endTimeS, args.time), file=sys.stderr)
+        if pose.cameraValid and not args.eye and not args.target:
+            world.camera.update(eye=tuple(pose.eye), target=tuple(pose.target), up=tuple(pose.up))
     hcam = Camera.from_world(world, w, h)
     if args.dof:
         c = world.camera
         focus = args.focus or math.dist(c["eye"], c["target"])
         hcam.set_parameters(c["fov"], c["zN"], c["zF"], args.aperture, focus)
     cam, focal = hcam.update_buffer()
-    ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
-    ctx.upload_scene(world)
-    st = ctx.scene_stats()
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_SKIP_HISTORY | (S.PC_FLAG_IBL if args.env else 0)
     if args.deferred:
         import time
@@ -153,6 +169,14 @@ def main():
                 ctx.particles(ppc, S.PARTICLES_DECAY | S.PARTICLES_INIT | S.PARTICLES_SIMULATE)
         for frame in range(args.frames if args.taa else 1):
             if args.taa:
+                if args.time is not None and frame:
+                    # the scene moves on; this frame's table is the next frame's previous one (the tracer keeps it)
+                    ctx.animate(args.time + frame * args.time_step)
+                    pose = ctx.animation_state()
+                    if pose.cameraValid and not args.eye and not args.target:
+                        hcam.look_at(tuple(pose.eye), tuple(pose.target), tuple(pose.up))
+                if args.time is not None:
+                    transforms = ctx.read_animated_transforms()
                 # the G-buffer through the jittered projection's pixel centres, with the velocity the resolve reads
                 cam, focal = hcam.update_buffer()
                 g, _ = tracer.record_velocity(hcam, w, h, frame_index=frame, transforms=transforms)
