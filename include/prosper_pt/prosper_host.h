@@ -204,6 +204,58 @@ int prosper_host_particles_record(
     prosper_host_particles *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, float *nonLinearDepth,
     float deltaTimeS, void *stream, prosper_pt_particles_pc *outPushConstants, uint32_t *outInitRecorded);
 
+/* scene::DebugLines and render::DebugRenderer (host/debug_renderer.hpp; reference src/scene/DebugGeometry.hpp,
+ * src/render/DebugRenderer.cpp): a host-side list of at most 100 000 lines (reset / add_line; an add to a full list is
+ * refused where the reference would write past its buffer), and record = Camera::updateBuffer + prosper_pt_debug_lines
+ * over the context's HDR image and the last traced G-buffer's depth. */
+typedef struct prosper_host_debug_lines prosper_host_debug_lines;
+int prosper_host_debug_lines_create(prosper_host_debug_lines **out);
+void prosper_host_debug_lines_destroy(prosper_host_debug_lines *lines);
+void prosper_host_debug_lines_reset(prosper_host_debug_lines *lines);
+int prosper_host_debug_lines_add_line(prosper_host_debug_lines *lines, const float *p0, const float *p1, const float *color);
+uint32_t prosper_host_debug_lines_count(const prosper_host_debug_lines *lines);
+const float *prosper_host_debug_lines_data(const prosper_host_debug_lines *lines);
+typedef struct prosper_host_debug_renderer prosper_host_debug_renderer;
+int prosper_host_debug_renderer_create(prosper_pt_ctx *ctx, prosper_host_debug_renderer **out);
+void prosper_host_debug_renderer_destroy(prosper_host_debug_renderer *pass);
+int prosper_host_debug_renderer_record(
+    prosper_host_debug_renderer *pass, prosper_host_camera *camera, const prosper_host_debug_lines *lines, uint32_t width,
+    uint32_t height, void *stream);
+
+/* render::TextureReadback (host/texture_readback.hpp; reference src/render/TextureReadback.cpp) on a context
+ * (borrowed): record queues prosper_pt_texture_readback of registry entry `resource` and sets the reference's
+ * m_framesUntilReady to MAX_FRAMES_IN_FLIGHT = 2; start_frame counts it down; readback gives nothing (*outReady 0) while
+ * it is above 0 or the copy has not finished, then the value once.  Where the reference asserts - a second record while
+ * one is unread, readback with none in flight, a frame started at 0 that nobody polled - the call is refused with
+ * PROSPER_PT_ERR_INVALID_ARGUMENT and the assertion's text in prosper_host_last_error. */
+typedef struct prosper_host_texture_readback prosper_host_texture_readback;
+int prosper_host_texture_readback_create(prosper_pt_ctx *ctx, prosper_host_texture_readback **out);
+void prosper_host_texture_readback_destroy(prosper_host_texture_readback *pass);
+int prosper_host_texture_readback_start_frame(prosper_host_texture_readback *pass);
+int prosper_host_texture_readback_record(prosper_host_texture_readback *pass, uint32_t resource, float pxX, float pxY, void *stream);
+int prosper_host_texture_readback_readback(prosper_host_texture_readback *pass, float out[4], uint32_t *outReady);
+int32_t prosper_host_texture_readback_frames_until_ready(const prosper_host_texture_readback *pass);
+
+/* render::TextureDebug (host/texture_debug.hpp; reference src/render/TextureDebug.cpp) on a context (borrowed): set_target
+ * names a registry image ("" or NULL deselects; texture_selected says whether one is named), set_settings keeps the
+ * reference's per-name TargetSettings (range, lod, channel 0-3 or 4 = RGB, abs, bilinear sampler), set_zoom its zoom
+ * toggle; record = prosper_pt_texture_debug of the selected image into outWidth x outHeight RGBA8, with the magnifier
+ * when cursorUv (two floats, may be NULL) is given, the LOD clamped to the image's last level; *outPushConstants (may be
+ * NULL) receives what it pushed.  peeked_value: prosper_pt_get_texture_debug_peek. */
+typedef struct prosper_host_texture_debug prosper_host_texture_debug;
+int prosper_host_texture_debug_create(prosper_pt_ctx *ctx, prosper_host_texture_debug **out);
+void prosper_host_texture_debug_destroy(prosper_host_texture_debug *pass);
+void prosper_host_texture_debug_set_target(prosper_host_texture_debug *pass, const char *name);
+int prosper_host_texture_debug_texture_selected(const prosper_host_texture_debug *pass);
+void prosper_host_texture_debug_set_settings(
+    prosper_host_texture_debug *pass, const char *name, float rangeLo, float rangeHi, int32_t lod, uint32_t channelType,
+    int absBeforeRange, int useBilinearSampler);
+void prosper_host_texture_debug_set_zoom(prosper_host_texture_debug *pass, int zoom);
+int prosper_host_texture_debug_record(
+    prosper_host_texture_debug *pass, uint32_t outWidth, uint32_t outHeight, const float *cursorUv, void *deviceRgba8,
+    uint8_t *hostRgba8, size_t byteSize, void *stream, prosper_pt_texture_debug_pc *outPushConstants);
+int prosper_host_texture_debug_peeked_value(prosper_host_texture_debug *pass, float out[4]);
+
 /* render::dof::DepthOfField (host/depth_of_field.hpp; reference src/render/dof/DepthOfField.hpp) on a context
  * (borrowed): record = Camera::updateBuffer + prosper_pt_depth_of_field with the push constants computed from the
  * camera's aperture, focus distance and focal length as dof/Setup.cpp and dof/Dilate.cpp compute them; returns them. */

@@ -56,6 +56,7 @@ enum
     PROSPER_PT_ERR_NO_SCENE = -4,   /* render before upload_scene */
     PROSPER_PT_ERR_SCENE = -5,      /* scene view failed validation (out-of-range index/offset) */
     PROSPER_PT_ERR_UNSUPPORTED = -6,
+    PROSPER_PT_NOT_READY = -7,      /* prosper_pt_try_texture_readback: nothing queued, or not finished yet (sets no error message) */
 };
 
 typedef struct prosper_pt_ctx prosper_pt_ctx;
@@ -1017,6 +1018,135 @@ int prosper_pt_read_particles(
 int prosper_pt_set_particles(
     prosper_pt_ctx *ctx, const prosper_pt_particle *particles, const int32_t *freelist, uint32_t maxParticleCount,
     void *stream);
+
+/* ---- debug lines (src/render/DebugRenderer.cpp, src/scene/DebugGeometry.hpp, res/shader/debug_lines.vert) ----
+ * What prosper runs between the transparents and bloom (Renderer.cpp:502): the line-list pipeline of
+ * DebugRenderer as a compute rasteriser, in place over the context's HDR image AND the depth of the last traced G-buffer,
+ * where prosper_pt_particles draws.  Additive: the ABI version stays 4.
+ *
+ * `lines`: count * 9 floats (p0, p1, colour: DebugLines::addLine), host or device memory; the call copies them, so the
+ * array may go once it returns.  At most 100 000 lines (DebugLines::sMaxLineCount); 0 lines launch nothing.
+ *   projection  clip = cameraToClip * (worldToCamera * (p, 1)) in float32, each row one chain of fused multiply-adds;
+ *   clipping    in homogeneous space against -w <= x, y <= w, 0 <= z <= w by a Liang-Barsky parameter interval; a line
+ *               with a non-finite clip coordinate or an empty interval draws nothing and counts in linesClippedAway;
+ *   fragments   Vulkan leaves non-strict lines to the implementation, so the rule is this library's own (DESIGN.md f16
+ *               states it, tests/debug_view_reference.py restates it): along the major axis of the clipped segment in
+ *               framebuffer coordinates, one fragment per pixel centre in [start, end) - half-open, so a polyline that
+ *               keeps its direction writes no pixel twice and leaves no gap at a joint; the minor coordinate and z / w
+ *               are interpolated linearly in screen space; a segment of zero length on screen writes nothing;
+ *   depth       strictly greater (reverse Z) against the stored depth - equal loses - and written; colour (rgb, 1).
+ * Among the fragments of one pixel the nearest wins, among equal depths the higher line index: the image does not depend
+ * on the order the lines are walked in.  Untouched pixels keep colour and depth bit for bit.
+ * Refused before anything is launched: more than 100 000 lines, a null camera (or null lines with count > 0), an empty
+ * extent or one above 32768; NO_SCENE without a traced G-buffer of that extent; an HDR image of another extent. */
+int prosper_pt_debug_lines(
+    prosper_pt_ctx *ctx, const float *lines, uint32_t count, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height, void *stream);
+typedef struct prosper_pt_debug_lines_info
+{
+    uint32_t valid;            /* 1 once prosper_pt_debug_lines ran; the rest is of its last call */
+    uint32_t lineCount;        /* lines it was given */
+    uint32_t fragmentsWritten; /* pixels it wrote */
+    uint32_t linesClippedAway; /* lines with a non-finite endpoint or an empty clip interval */
+    float ms;                  /* device time of the two kernels */
+} prosper_pt_debug_lines_info;
+/* Of the last prosper_pt_debug_lines (waits for it). */
+int prosper_pt_get_debug_lines_info(prosper_pt_ctx *ctx, prosper_pt_debug_lines_info *out);
+
+/* ---- the registry of the context's 2-D images, and the one-texel readback (src/render/TextureReadback.cpp,
+ * res/shader/texture_readback.comp; Renderer.cpp:510-514, App.cpp:583-631) ----
+ * Every pass module lists the images it owns, in a fixed order: an index names the same image for the life of the
+ * context.  The entries: the HDR "illumination"; the traced G-buffer's "albedoRoughness", "normalMetalness", "depth";
+ * "velocity"; the IBL "SpecularBrdfLut"; depth of field's eight stages ("HalfResIllumination" with its mips as levels);
+ * bloom's three working images (the two blur images hold levels firstLevel .. firstLevel + 2, numbered from 0 here) and
+ * the FFT technique's four; TAA's "previousResolvedIllumination"; "toneMapped", the tone map's RGBA8 while the context keeps
+ * it (prosper_pt_tone_map asked for a host copy alone).  Cube maps are not 2-D and are not listed.  Names are prosper's debug names where the reference creates
+ * the corresponding image.
+ * `valid` is 0 until the owning pass has run, and 0 again when what the entry described is gone: a G-buffer or velocity
+ * target traced into a caller's buffers (the context cannot vouch for them), the TAA history after
+ * prosper_pt_taa_release_history or a new scene, the LUT after a new scene, the tone-mapped
+ * image after a tone map into the caller's buffer.  A valid entry means "what the last call of
+ * its pass left": prosper's pool preserves an image that is marked for debug, this library does not - a later call of
+ * the pass overwrites it.  No two entries share storage. */
+enum
+{
+    PROSPER_PT_DEBUG_FORMAT_RGBA32F = 0,
+    PROSPER_PT_DEBUG_FORMAT_RG32F = 1,
+    PROSPER_PT_DEBUG_FORMAT_R32F = 2,
+    PROSPER_PT_DEBUG_FORMAT_RGBA16F = 3,
+    PROSPER_PT_DEBUG_FORMAT_RG16F = 4,
+    PROSPER_PT_DEBUG_FORMAT_R16F = 5,
+    PROSPER_PT_DEBUG_FORMAT_RG16_UNORM = 6,
+    PROSPER_PT_DEBUG_FORMAT_RGBA8_UNORM = 7,
+};
+typedef struct prosper_pt_debug_resource
+{
+    char name[64];
+    uint32_t format;     /* PROSPER_PT_DEBUG_FORMAT_* */
+    uint32_t width;      /* of level 0; 0 while the entry is not valid */
+    uint32_t height;
+    uint32_t levelCount; /* level l is max(width >> l, 1) x max(height >> l, 1) */
+    uint32_t valid;
+} prosper_pt_debug_resource;
+uint32_t prosper_pt_debug_resource_count(prosper_pt_ctx *ctx); /* 0 for a null context */
+int prosper_pt_get_debug_resource(prosper_pt_ctx *ctx, uint32_t index, prosper_pt_debug_resource *out);
+/* texture_readback.comp over level 0 of registry entry `resource`, on `stream`: uv = (pxX, pxY) / extent in float32, one
+ * nearest clamp-to-edge sample - texel clamp(floor(u * width), 0, width - 1) - as a float4 into pinned memory behind a
+ * fence.  Missing components read as Vulkan defines them, (r, 0, 0, 1) and (r, g, 0, 1); fp16 decodes exactly, UNORM
+ * codes are divided by 65535 or 255.  Refused: a bad index or an entry that is not valid (NO_SCENE), non-finite pixel
+ * coordinates, and a second record while one is queued and unread (the reference asserts on it). */
+int prosper_pt_texture_readback(prosper_pt_ctx *ctx, uint32_t resource, float pxX, float pxY, void *stream);
+/* Never blocks.  PROSPER_PT_NOT_READY while nothing is queued or the queued readback has not finished; otherwise the
+ * value, once: the slot is free again. */
+int prosper_pt_try_texture_readback(prosper_pt_ctx *ctx, float out[4]);
+/* Streams: the readback and the viewer below read the image on `stream` as the owning pass left it; a caller that ran
+ * that pass on another stream orders the two itself (an event, or a synchronise), as for every pass that reads what
+ * another wrote. */
+
+/* ---- the texture viewer (src/render/TextureDebug.cpp, res/shader/texture_debug.comp; Renderer.cpp:621) ----
+ * prosper_pt_texture_debug views level pc->lod of registry entry `resource` as outRes.x x outRes.y RGBA8, one lane per
+ * output texel, restating the shader as it is compiled (the magnifier's warp is commented out in its main() and is not
+ * here; the magnifier's peek and marker are), in this order: uv = (texel + 0.5) / outRes; aspect correction, only when
+ * inRes() != outRes, either branch; zoom 4x (uv * 0.25 + 0.375); black unless 0 <= uv <= 1, both ends inclusive;
+ * textureLod(uv, lod) with clamp-to-edge - useBilinearSampler 0: texel clamp(floor(u * W), 0, W - 1); 1: u * W - 0.5, its
+ * floor and the unquantised float32 fraction, the four texels blended as prosper_pt's BRDF LUT lookup blends; channel
+ * select (0-3 one component in all three, above 3 xyz); abs; (c - range.x) / (range.y - range.x); with the magnifier flag
+ * the marker squares of 3 and 2 pixels around the cursor snapped to its input texel; alpha 1; float -> UNORM8 as
+ * prosper_pt_tone_map converts (NaN stores 0).  inRes() = max(inRes / (1 << lod), 1).  Missing components read
+ * (0, 0, 1), fp16 decodes exactly, UNORM codes are divided by 65535 or 255.
+ * flags: bits 0-2 the channel, bit 3 abs before range, bit 4 zoom, bit 5 magnifier (the shader's bitfieldExtract calls).
+ * With the magnifier flag the lane of output texel (0, 0) writes the peek - the nearest sample at the snapped cursor
+ * texel, or +inf four times when the snapped uv lies outside [0, 1) - into a slot of the context, copied to pinned
+ * memory behind a fence; prosper_pt_get_texture_debug_peek waits for that fence (NO_SCENE before any magnifier call).
+ * The output goes to device_rgba8 and / or host_rgba8 (then `stream` is synchronised), byte_size >= 4 * outRes.x *
+ * outRes.y, as prosper_pt_tone_map takes them.
+ * Refused (prosper clears to black there): a bad index or an entry that is not valid (NO_SCENE); pc->inRes other than
+ * the entry's extent; lod above levelCount - 1; an empty outRes or one above 32768; non-finite range or cursorUv is NOT
+ * refused (the arithmetic is the shader's); flag bits above 5; useBilinearSampler above 1. */
+typedef struct prosper_pt_texture_debug_pc
+{
+    int32_t inRes[2];
+    int32_t outRes[2];
+    float range[2];
+    uint32_t lod;
+    uint32_t flags;
+    float cursorUv[2];
+} prosper_pt_texture_debug_pc;
+enum
+{
+    PROSPER_PT_TEXTURE_DEBUG_CHANNEL_R = 0,
+    PROSPER_PT_TEXTURE_DEBUG_CHANNEL_G = 1,
+    PROSPER_PT_TEXTURE_DEBUG_CHANNEL_B = 2,
+    PROSPER_PT_TEXTURE_DEBUG_CHANNEL_A = 3,
+    PROSPER_PT_TEXTURE_DEBUG_CHANNEL_RGB = 4,
+    PROSPER_PT_TEXTURE_DEBUG_ABS_BEFORE_RANGE = 1u << 3,
+    PROSPER_PT_TEXTURE_DEBUG_ZOOM = 1u << 4,
+    PROSPER_PT_TEXTURE_DEBUG_MAGNIFIER = 1u << 5,
+};
+int prosper_pt_texture_debug(
+    prosper_pt_ctx *ctx, uint32_t resource, const prosper_pt_texture_debug_pc *pc, uint32_t useBilinearSampler,
+    void *device_rgba8, uint8_t *host_rgba8, size_t byte_size, void *stream);
+int prosper_pt_get_texture_debug_peek(prosper_pt_ctx *ctx, float out[4]);
 
 /* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
  * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.

@@ -121,6 +121,15 @@ def lib():
     L.prosper_pt_get_particles_info.argtypes = [vp, C.POINTER(S.ParticlesInfo)]
     L.prosper_pt_read_particles.argtypes = [vp, vp, vp, u32, vp]
     L.prosper_pt_set_particles.argtypes = [vp, vp, vp, u32, vp]
+    L.prosper_pt_debug_lines.argtypes = [vp, vp, u32, C.POINTER(S.CameraUniforms), u32, u32, vp]
+    L.prosper_pt_get_debug_lines_info.argtypes = [vp, C.POINTER(S.DebugLinesInfo)]
+    L.prosper_pt_debug_resource_count.argtypes = [vp]
+    L.prosper_pt_debug_resource_count.restype = u32
+    L.prosper_pt_get_debug_resource.argtypes = [vp, u32, C.POINTER(S.DebugResource)]
+    L.prosper_pt_texture_readback.argtypes = [vp, u32, C.c_float, C.c_float, vp]
+    L.prosper_pt_try_texture_readback.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    L.prosper_pt_texture_debug.argtypes = [vp, u32, C.POINTER(S.TextureDebugPC), u32, vp, vp, C.c_size_t, vp]
+    L.prosper_pt_get_texture_debug_peek.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
     L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
     L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
@@ -260,6 +269,40 @@ def lib():
     L.prosper_host_particles_set_max_particle_count.restype = None
     L.prosper_host_particles_record.argtypes = [vp, vp, u32, u32, vp, C.c_float, vp, C.POINTER(S.ParticlesPC),
                                                 C.POINTER(u32)]
+    L.prosper_host_debug_lines_create.argtypes = [C.POINTER(vp)]
+    L.prosper_host_debug_lines_destroy.argtypes = [vp]
+    L.prosper_host_debug_lines_destroy.restype = None
+    L.prosper_host_debug_lines_reset.argtypes = [vp]
+    L.prosper_host_debug_lines_reset.restype = None
+    L.prosper_host_debug_lines_add_line.argtypes = [vp, vp, vp, vp]
+    L.prosper_host_debug_lines_count.argtypes = [vp]
+    L.prosper_host_debug_lines_count.restype = u32
+    L.prosper_host_debug_lines_data.argtypes = [vp]
+    L.prosper_host_debug_lines_data.restype = vp
+    L.prosper_host_debug_renderer_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_debug_renderer_destroy.argtypes = [vp]
+    L.prosper_host_debug_renderer_destroy.restype = None
+    L.prosper_host_debug_renderer_record.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.prosper_host_texture_readback_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_texture_readback_destroy.argtypes = [vp]
+    L.prosper_host_texture_readback_destroy.restype = None
+    L.prosper_host_texture_readback_start_frame.argtypes = [vp]
+    L.prosper_host_texture_readback_frames_until_ready.argtypes = [vp]
+    L.prosper_host_texture_readback_frames_until_ready.restype = i32
+    L.prosper_host_texture_readback_record.argtypes = [vp, u32, C.c_float, C.c_float, vp]
+    L.prosper_host_texture_readback_readback.argtypes = [vp, C.POINTER(C.c_float * 4), C.POINTER(u32)]
+    L.prosper_host_texture_debug_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_texture_debug_destroy.argtypes = [vp]
+    L.prosper_host_texture_debug_destroy.restype = None
+    L.prosper_host_texture_debug_set_target.argtypes = [vp, C.c_char_p]
+    L.prosper_host_texture_debug_set_target.restype = None
+    L.prosper_host_texture_debug_texture_selected.argtypes = [vp]
+    L.prosper_host_texture_debug_set_settings.argtypes = [vp, C.c_char_p, C.c_float, C.c_float, i32, u32, C.c_int, C.c_int]
+    L.prosper_host_texture_debug_set_settings.restype = None
+    L.prosper_host_texture_debug_set_zoom.argtypes = [vp, C.c_int]
+    L.prosper_host_texture_debug_set_zoom.restype = None
+    L.prosper_host_texture_debug_record.argtypes = [vp, u32, u32, vp, vp, vp, C.c_size_t, vp, C.POINTER(S.TextureDebugPC)]
+    L.prosper_host_texture_debug_peeked_value.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.prosper_host_depth_of_field_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_depth_of_field_destroy.argtypes = [vp]
     L.prosper_host_depth_of_field_destroy.restype = None
@@ -920,6 +963,79 @@ class Context:
         freelist = np.concatenate([np.array([count], np.int32), idx])
         _check(lib().prosper_pt_set_particles(self._h, rec.ctypes.data, freelist.ctypes.data, rec.size, C.c_void_p(stream)))
         self._particles_max = rec.size
+
+    # ---- debug lines (prosper_pt_debug_lines) ----
+
+    def debug_lines(self, lines, camera, width, height, stream=None):
+        """DebugRenderer::record (prosper_pt_debug_lines): `lines` [n, 9] float32 (p0, p1, colour; a
+        debug_geometry.DebugLines' .array()) drawn depth-tested, in place, over the HDR image and the last traced
+        G-buffer's depth."""
+        self._sync_debug()
+        arr = np.ascontiguousarray(lines, np.float32).reshape(-1, 9)
+        ptr = C.c_void_p(arr.ctypes.data) if arr.shape[0] else None
+        _check(lib().prosper_pt_debug_lines(self._h, ptr, arr.shape[0], C.byref(camera), width, height, C.c_void_p(stream)))
+
+    def debug_lines_info(self):
+        """S.DebugLinesInfo of the last debug_lines() (waits for it)."""
+        info = S.DebugLinesInfo()
+        _check(lib().prosper_pt_get_debug_lines_info(self._h, C.byref(info)))
+        return info
+
+    # ---- the registry of the context's images and the one-texel readback (DESIGN.md f16) ----
+
+    def debug_resources(self):
+        """The registry: a list of S.DebugResource, index = the resource's number."""
+        out = []
+        for i in range(lib().prosper_pt_debug_resource_count(self._h)):
+            r = S.DebugResource()
+            _check(lib().prosper_pt_get_debug_resource(self._h, i, C.byref(r)))
+            out.append(r)
+        return out
+
+    def debug_resource_index(self, name):
+        for i, r in enumerate(self.debug_resources()):
+            if r.name.decode() == name:
+                return i
+        raise KeyError(name)
+
+    def texture_readback(self, resource, px_x, px_y, stream=None):
+        """TextureReadback::record (prosper_pt_texture_readback): one nearest clamp-to-edge texel of level 0 of registry
+        entry `resource` (index or name) at uv = px / extent, queued; try_texture_readback hands it out."""
+        if isinstance(resource, str):
+            resource = self.debug_resource_index(resource)
+        _check(lib().prosper_pt_texture_readback(self._h, resource, px_x, px_y, C.c_void_p(stream)))
+
+    def try_texture_readback(self):
+        """The queued texel as float32 [4], once; None while nothing is queued or it has not finished (never blocks)."""
+        out = (C.c_float * 4)()
+        rc = lib().prosper_pt_try_texture_readback(self._h, C.byref(out))
+        if rc == S.NOT_READY:
+            return None
+        _check(rc)
+        return np.array(out[:], np.float32)
+
+    def texture_debug(self, resource, out_res, value_range=(0.0, 1.0), lod=0, flags=S.TEXTURE_DEBUG_CHANNEL_RGB,
+                      cursor_uv=(0.0, 0.0), bilinear=False, device_ptr=None, to_host=True, stream=None):
+        """TextureDebug::record (prosper_pt_texture_debug): level `lod` of registry entry `resource` (index or name) viewed
+        as out_res = (width, height) RGBA8 -> uint8 [h, w, 4] (None with to_host=False).  `flags`: a channel (0-3, or
+        S.TEXTURE_DEBUG_CHANNEL_RGB) | S.TEXTURE_DEBUG_ABS_BEFORE_RANGE | _ZOOM | _MAGNIFIER."""
+        if isinstance(resource, str):
+            resource = self.debug_resource_index(resource)
+        r = S.DebugResource()
+        _check(lib().prosper_pt_get_debug_resource(self._h, resource, C.byref(r)))
+        w, h = int(out_res[0]), int(out_res[1])
+        pc = S.TextureDebugPC((C.c_int32 * 2)(r.width, r.height), (C.c_int32 * 2)(w, h), (C.c_float * 2)(*value_range), lod, flags,
+                              (C.c_float * 2)(*cursor_uv))
+        out = np.empty((max(h, 0), max(w, 0), 4), np.uint8) if to_host else None
+        _check(lib().prosper_pt_texture_debug(self._h, resource, C.byref(pc), 1 if bilinear else 0, C.c_void_p(device_ptr),
+                                              out.ctypes.data if to_host else None, max(w, 0) * max(h, 0) * 4, C.c_void_p(stream)))
+        return out
+
+    def texture_debug_peek(self):
+        """The magnifier's peeked texel of the last texture_debug with S.TEXTURE_DEBUG_MAGNIFIER: float32 [4] (waits)."""
+        out = (C.c_float * 4)()
+        _check(lib().prosper_pt_get_texture_debug_peek(self._h, C.byref(out)))
+        return np.array(out[:], np.float32)
 
     def generate_ibl(self, stream=None):
         """ImageBasedLighting::recordGeneration (prosper_pt_generate_ibl): the irradiance and radiance cubes and the BRDF

@@ -798,7 +798,7 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
     if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
-        !create_particles_passes(ctx) || !create_animation_state(ctx))
+        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_animation_state(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -858,6 +858,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_bloom_passes(ctx);
     destroy_taa_passes(ctx);
     destroy_particles_passes(ctx);
+    destroy_debug_passes(ctx);
     destroy_animation_state(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
@@ -1622,6 +1623,9 @@ int prosper_pt_tone_map(
         }
         out = ctx->toneScratch.ptr;
     }
+    // (the registry of the inspection passes lists the kept image)
+    ctx->toneKeptWidth = device_rgba8 ? 0u : ctx->localWidth;
+    ctx->toneKeptHeight = device_rgba8 ? 0u : ctx->height;
     launch_tone_map(ctx->hdr, ctx->toneLut.as<uint32_t>(), ctx->toneLutDim, exposure, contrast, out, count, s);
     PPT_HIP(hipGetLastError());
     if (host_rgba8)

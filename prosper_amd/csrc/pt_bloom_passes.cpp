@@ -59,6 +59,61 @@ void destroy_bloom_passes(prosper_pt_ctx *ctx)
     ctx->bloomPasses = nullptr;
 }
 
+void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+{
+    const BloomPassState &st = *ctx->bloomPasses;
+    const BloomParams &p = st.last;
+    // the multi-resolution blur: the highlights hold levels 0-3; the two blur images only levels firstLevel .. + 2,
+    // which the registry numbers from 0
+    const struct
+    {
+        const char *name;
+        const DeviceBuffer *buffer;
+        bool blur;
+    } images[3] = {{"BloomWorkingImage", &st.highlights, false}, {"BloomBlurPong", &st.horizontal, true}, {"BloomBlurred", &st.blurred, true}};
+    for (const auto &i : images)
+    {
+        DebugImage im;
+        im.name = i.name;
+        im.format = PROSPER_PT_DEBUG_FORMAT_RGBA16F;
+        im.valid = st.valid && i.buffer->ptr;
+        if (im.valid)
+        {
+            const uint32_t first = i.blur ? p.firstLevel : 0u;
+            im.levelCount = i.blur ? kBloomBlurLevels : kBloomLevels;
+            for (uint32_t l = 0; l < im.levelCount; ++l)
+            {
+                im.level[l] = i.buffer->as<uint8_t>() + (size_t)p.levelOffset[first + l] * 8u;
+                im.levelW[l] = p.levelW[first + l];
+                im.levelH[l] = p.levelH[first + l];
+            }
+            im.width = im.levelW[0], im.height = im.levelH[0];
+        }
+        out.push_back(im);
+    }
+    // the FFT technique
+    const BloomFftState &f = st.fft;
+    const struct
+    {
+        const char *name;
+        uint32_t format;
+        const DeviceBuffer *buffer;
+        uint32_t dim;
+    } fft[4] = {{"BloomFftHighlights", PROSPER_PT_DEBUG_FORMAT_RGBA16F, &f.highlights, f.last.dim},
+                {"BloomKernelImageCentered", PROSPER_PT_DEBUG_FORMAT_RGBA32F, &f.kernelImage, f.last.kernelDim},
+                {"BloomKernelDft", PROSPER_PT_DEBUG_FORMAT_RGBA32F, &f.kernelDft, f.last.dim},
+                {"BloomFftConvolved", PROSPER_PT_DEBUG_FORMAT_RGBA32F, &f.convolved, f.last.dim}};
+    for (const auto &i : fft)
+    {
+        DebugImage im;
+        im.name = i.name;
+        im.format = i.format;
+        im.valid = f.valid && i.buffer->ptr && i.dim != 0u;
+        if (im.valid) im.one_level(i.buffer->ptr, i.dim, i.dim);
+        out.push_back(im);
+    }
+}
+
 } // namespace ppt
 
 namespace

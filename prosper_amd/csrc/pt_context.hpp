@@ -82,6 +82,33 @@ void forget_taa_history(prosper_pt_ctx *ctx);
 struct ParticlesPassState;
 bool create_particles_passes(prosper_pt_ctx *ctx);
 void destroy_particles_passes(prosper_pt_ctx *ctx);
+// State of the inspection passes (pt_debug_passes.cpp): the debug lines' copy, their per-pixel keys and statistics.  Made
+// and freed like the others.
+struct DebugPassState;
+bool create_debug_passes(prosper_pt_ctx *ctx);
+void destroy_debug_passes(prosper_pt_ctx *ctx);
+// One 2-D image a pass module owns, as the registry of the inspection passes describes it (prosper_pt_get_debug_resource).
+// Every module lists its images in a fixed order whether they are valid or not, so an index means the same image for
+// the life of the context.  `valid`: the owning pass has run and the storage still holds what its last call left.
+constexpr uint32_t kDebugImageMaxLevels = 16;
+struct DebugImage
+{
+    const char *name = "";
+    uint32_t format = 0; // PROSPER_PT_DEBUG_FORMAT_*
+    uint32_t width = 0, height = 0, levelCount = 0; // extent of level 0
+    bool valid = false;
+    const void *level[kDebugImageMaxLevels] = {};
+    uint32_t levelW[kDebugImageMaxLevels] = {}, levelH[kDebugImageMaxLevels] = {};
+    void one_level(const void *p, uint32_t w, uint32_t h)
+    {
+        width = w, height = h, levelCount = 1;
+        level[0] = p, levelW[0] = w, levelH[0] = h;
+    }
+};
+void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out); // G-buffer, velocity, IBL LUT
+void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);
+void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);   // both techniques
+void list_taa_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);
 // State of the keyframe animation (pt_animation.hip, pt_animation.hpp): the node and channel tables of the scene, the
 // staged time and the read-back that feeds the host mirrors below.  Made and freed like the others.
 struct AnimationState;
@@ -316,10 +343,12 @@ struct prosper_pt_ctx
     ppt::BloomPassState *bloomPasses = nullptr;
     ppt::TaaPassState *taaPasses = nullptr;
     ppt::ParticlesPassState *particlesPasses = nullptr;
+    ppt::DebugPassState *debugPasses = nullptr;
     ppt::AnimationState *animation = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy
+    uint32_t toneKeptWidth = 0, toneKeptHeight = 0; // of the image the last tone map left in toneScratch (0: it went to the caller's buffer)
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
     // workspace, the stack-overflow array and the launch chains (pt_kernels.hpp WavefrontChains) with their

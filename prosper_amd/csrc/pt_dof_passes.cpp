@@ -41,6 +41,52 @@ void destroy_dof_passes(prosper_pt_ctx *ctx)
     ctx->dofPasses = nullptr;
 }
 
+void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+{
+    const DofPassState &st = *ctx->dofPasses;
+    const DofParams &p = st.last;
+    {
+        DebugImage im;
+        im.name = "HalfResIllumination";
+        im.format = PROSPER_PT_DEBUG_FORMAT_RGBA16F;
+        im.valid = st.valid;
+        if (st.valid)
+        {
+            im.width = p.hw, im.height = p.hh;
+            im.levelCount = p.levels < kDebugImageMaxLevels ? p.levels : kDebugImageMaxLevels;
+            for (uint32_t l = 0; l < im.levelCount; ++l)
+            {
+                im.level[l] = st.halfIllumination.as<uint8_t>() + (size_t)p.levelOffset[l] * 8u;
+                im.levelW[l] = (p.hw >> l) ? (p.hw >> l) : 1u;
+                im.levelH[l] = (p.hh >> l) ? (p.hh >> l) : 1u;
+            }
+        }
+        out.push_back(im);
+    }
+    const struct
+    {
+        const char *name;
+        uint32_t format;
+        const DeviceBuffer *buffer;
+        bool tiles;
+    } images[7] = {{"HalfResCircleOfConfusion", PROSPER_PT_DEBUG_FORMAT_R16F, &st.halfCoC, false},
+                   {"tileMinMaxCircleOfConfusion", PROSPER_PT_DEBUG_FORMAT_RG16F, &st.tileMinMax, true},
+                   {"dilatedTileMinMaxCoC", PROSPER_PT_DEBUG_FORMAT_RG16F, &st.dilatedMinMax, true},
+                   {"halfResFgBokehColorWeight", PROSPER_PT_DEBUG_FORMAT_RGBA16F, &st.gather[0], false},
+                   {"halfResBgBokehColorWeight", PROSPER_PT_DEBUG_FORMAT_RGBA16F, &st.gather[1], false},
+                   {"halfResFgBokehColorWeightFiltered", PROSPER_PT_DEBUG_FORMAT_RGBA16F, &st.filtered[0], false},
+                   {"halfResBgBokehColorWeightFiltered", PROSPER_PT_DEBUG_FORMAT_RGBA16F, &st.filtered[1], false}};
+    for (const auto &i : images)
+    {
+        DebugImage im;
+        im.name = i.name;
+        im.format = i.format;
+        im.valid = st.valid && i.buffer->ptr;
+        if (im.valid) im.one_level(i.buffer->ptr, i.tiles ? p.tw : p.hw, i.tiles ? p.th : p.hh);
+        out.push_back(im);
+    }
+}
+
 } // namespace ppt
 
 namespace

@@ -76,6 +76,46 @@ void destroy_gbuffer_passes(prosper_pt_ctx *ctx)
     ctx->gbufferPasses = nullptr;
 }
 
+void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+{
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    // only targets the context owns: a caller's buffers may be gone by the time someone looks
+    const auto owned = [](const DeviceBuffer &b, const void *p) {
+        return p && b.ptr && (const uint8_t *)p >= b.as<uint8_t>() && (const uint8_t *)p < b.as<uint8_t>() + b.bytes;
+    };
+    const bool g = owned(st.gbuffer, st.gbufferLast.albedoRoughness) && owned(st.gbuffer, st.gbufferLast.normalMetallic) &&
+                   owned(st.gbuffer, st.gbufferLast.nonLinearDepth);
+    const struct
+    {
+        const char *name;
+        uint32_t format;
+        const void *ptr;
+    } targets[3] = {{"albedoRoughness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.albedoRoughness},
+                    {"normalMetalness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.normalMetallic},
+                    {"depth", PROSPER_PT_DEBUG_FORMAT_R32F, st.gbufferLast.nonLinearDepth}};
+    for (const auto &t : targets)
+    {
+        DebugImage im;
+        im.name = t.name;
+        im.format = t.format;
+        im.valid = g;
+        if (g) im.one_level(t.ptr, st.gbufferLastWidth, st.gbufferLastHeight);
+        out.push_back(im);
+    }
+    DebugImage v;
+    v.name = "velocity";
+    v.format = PROSPER_PT_DEBUG_FORMAT_RG32F;
+    v.valid = owned(st.velocity, st.velocityLast);
+    if (v.valid) v.one_level(st.velocityLast, st.velocityLastWidth, st.velocityLastHeight);
+    out.push_back(v);
+    DebugImage lut;
+    lut.name = "SpecularBrdfLut";
+    lut.format = PROSPER_PT_DEBUG_FORMAT_RG16_UNORM;
+    lut.valid = st.iblGenerated && st.iblLut.ptr;
+    if (lut.valid) lut.one_level(st.iblLut.ptr, kIblLutSize, kIblLutSize);
+    out.push_back(lut);
+}
+
 void forget_ibl_maps(prosper_pt_ctx *ctx)
 {
     ctx->gbufferPasses->iblGenerated = false;

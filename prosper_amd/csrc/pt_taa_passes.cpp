@@ -39,6 +39,17 @@ void destroy_taa_passes(prosper_pt_ctx *ctx)
     ctx->taaPasses = nullptr;
 }
 
+void list_taa_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+{
+    const TaaPassState &st = *ctx->taaPasses;
+    DebugImage im;
+    im.name = "previousResolvedIllumination";
+    im.format = PROSPER_PT_DEBUG_FORMAT_RGBA16F;
+    im.valid = st.historyValid && st.history[st.newest].ptr;
+    if (im.valid) im.one_level(st.history[st.newest].ptr, st.width, st.height);
+    out.push_back(im);
+}
+
 void forget_taa_history(prosper_pt_ctx *ctx)
 {
     ctx->taaPasses->historyValid = false;

@@ -463,6 +463,70 @@ class Particles:
             pass
 
 
+class HostDebugLines:
+    """scene::DebugLines (csrc/host/debug_renderer.hpp): the C++ line list, for DebugRenderer.record."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        rc = lib().prosper_host_debug_lines_create(C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, "prosper_host_debug_lines_create failed")
+        self._h = h
+
+    @property
+    def count(self):
+        return lib().prosper_host_debug_lines_count(self._h)
+
+    def reset(self):
+        lib().prosper_host_debug_lines_reset(self._h)
+
+    def add_line(self, p0, p1, color):
+        v = np.concatenate([np.asarray(a, np.float32).reshape(3) for a in (p0, p1, color)])
+        rc = lib().prosper_host_debug_lines_add_line(self._h, v.ctypes.data, v[3:].ctypes.data, v[6:].ctypes.data)
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_debug_lines_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DebugRenderer:
+    """render::DebugRenderer (csrc/host/debug_renderer.hpp) on a Context: record draws a HostDebugLines list, depth-tested,
+    in place over the context's HDR image and the last traced G-buffer's depth."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_debug_renderer_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, lines, width, height, stream=None):
+        rc = lib().prosper_host_debug_renderer_record(self._h, camera._h, lines._h, width, height, C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_debug_renderer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DepthOfField:
     """render::dof::DepthOfField (csrc/host/depth_of_field.hpp) on a Context: record computes the push constants from the
     camera's aperture, focus distance and focal length and runs the seven passes into the context's HDR image

@@ -470,6 +470,36 @@ class ParticlesInfo(C.Structure):
                 ("initMs", C.c_float), ("simulateMs", C.c_float), ("renderMs", C.c_float)]
 
 
+MAX_DEBUG_LINE_COUNT = 100000  # DebugGeometry.hpp DebugLines::sMaxLineCount
+
+
+class DebugLinesInfo(C.Structure):
+    """prosper_pt_debug_lines_info of the last prosper_pt_debug_lines"""
+    _fields_ = [("valid", C.c_uint32), ("lineCount", C.c_uint32), ("fragmentsWritten", C.c_uint32),
+                ("linesClippedAway", C.c_uint32), ("ms", C.c_float)]
+
+
+NOT_READY = -7  # PROSPER_PT_NOT_READY
+(DEBUG_FORMAT_RGBA32F, DEBUG_FORMAT_RG32F, DEBUG_FORMAT_R32F, DEBUG_FORMAT_RGBA16F, DEBUG_FORMAT_RG16F, DEBUG_FORMAT_R16F,
+ DEBUG_FORMAT_RG16_UNORM, DEBUG_FORMAT_RGBA8_UNORM) = range(8)
+
+
+TEXTURE_DEBUG_CHANNEL_RGB = 4  # channels 0-3: one component in all three
+TEXTURE_DEBUG_ABS_BEFORE_RANGE, TEXTURE_DEBUG_ZOOM, TEXTURE_DEBUG_MAGNIFIER = 1 << 3, 1 << 4, 1 << 5
+
+
+class TextureDebugPC(C.Structure):
+    """prosper_pt_texture_debug_pc: TextureDebugPC of push_constants/texture_debug.h"""
+    _fields_ = [("inRes", C.c_int32 * 2), ("outRes", C.c_int32 * 2), ("range", C.c_float * 2), ("lod", C.c_uint32),
+                ("flags", C.c_uint32), ("cursorUv", C.c_float * 2)]
+
+
+class DebugResource(C.Structure):
+    """prosper_pt_debug_resource: one 2-D image of the context's registry"""
+    _fields_ = [("name", C.c_char * 64), ("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("levelCount", C.c_uint32), ("valid", C.c_uint32)]
+
+
 class IblInfo(C.Structure):
     """prosper_pt_ibl_info: whether the maps exist for the current scene, their sizes, the last generation's pass times"""
     _fields_ = [("generated", C.c_uint32), ("irradianceSize", C.c_uint32), ("radianceSize", C.c_uint32),

@@ -20,6 +20,12 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  forward over the light clusters, over the shaded image after --sky and before --bloom
                                  (Renderer.cpp:493-500), through the host layer's ForwardRenderer; under --taa along the
                                  camera-jittered ray
+    --deferred --debug-lines [--debug-frustum]
+                                 prosper's DebugRenderer (prosper_pt_debug_lines) between the transparents and bloom
+                                 (Renderer.cpp:502): the axes of the point and spot lights as the device holds them
+                                 (prosper_pt_read_lights, so lights moved by --time show where they are), 0.2 long in
+                                 red / green / blue, depth-tested against the traced G-buffer; --debug-frustum adds the
+                                 glTF camera's own frustum in white, to look at from an --eye / --target elsewhere
     --deferred --bloom [--bloom-threshold T] [--bloom-quarter] [--bloom-fft]
                                  prosper_pt_bloom over the (filled) image, through the host layer's Bloom with prosper's
                                  defaults: after --sky and before --dof, which is prosper's order (Renderer.cpp:516-573);
@@ -43,6 +49,18 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
     --deferred --sky --dof --aperture A --focus D
                                  prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
                                  aperture diameter A and focus distance D in scene units drive the push constants
+    --deferred --sky --dof --focus-at X,Y
+                                 prosper's click-to-focus (App.cpp:583-631): the focus distance is that of the surface
+                                 under pixel (X, Y), from the depth texel prosper_pt_texture_readback hands back
+                                 (prosper_amd/debug_geometry.py focus_distance_from_depth)
+    --deferred ... --debug-view NAME[:LOD] [--debug-channel r|g|b|a|rgb] [--debug-range LO,HI] [--debug-abs]
+                   [--debug-bilinear] [--debug-zoom]
+                                 prosper's texture viewer (prosper_pt_texture_debug): the PNG is level LOD of the registry
+                                 image NAME through these settings instead of the tone map's output, as Renderer.cpp:621-640
+                                 replaces the final composite
+    --deferred ... --list-debug-views
+                                 after the frame, the registry of the context's 2-D images (prosper_pt_get_debug_resource):
+                                 index, name, format, extent and levels of what each pass left
 """
 import argparse
 import math
@@ -86,6 +104,8 @@ def main():
     ap.add_argument("--ibl", action="store_true", help="with --deferred: add image-based lighting from the sky")
     ap.add_argument("--sky", action="store_true", help="with --deferred: fill the sky where the G-buffer's ray missed")
     ap.add_argument("--transparents", action="store_true", help="with --deferred: BLEND surfaces through the forward transparent pass")
+    ap.add_argument("--debug-lines", action="store_true", help="with --deferred: the lights' axes as depth-tested debug lines")
+    ap.add_argument("--debug-frustum", action="store_true", help="with --deferred: the glTF camera's frustum as debug lines")
     ap.add_argument("--bloom", action="store_true", help="with --deferred: bloom (multi-resolution blur) over the shaded image")
     ap.add_argument("--bloom-threshold", type=float, default=1.0, help="with --bloom: what is subtracted from the highlights")
     ap.add_argument("--bloom-quarter", action="store_true", help="with --bloom: quarter resolution instead of half")
@@ -100,13 +120,27 @@ def main():
     ap.add_argument("--dof", action="store_true", help="with --deferred: depth of field over the shaded image")
     ap.add_argument("--aperture", type=float, default=0.02, help="with --dof: aperture diameter in scene units")
     ap.add_argument("--focus", type=float, default=None, help="with --dof: focus distance (default: eye to target)")
+    ap.add_argument("--focus-at", default=None, metavar="X,Y",
+                    help="with --dof: focus on the surface under this pixel instead of --focus (prosper's click-to-focus)")
+    ap.add_argument("--list-debug-views", action="store_true",
+                    help="with --deferred: print the registry of the context's images after the frame")
+    ap.add_argument("--debug-view", default=None, metavar="NAME[:LOD]",
+                    help="with --deferred: the PNG is the texture viewer's output over this registry image instead of the tone map's")
+    ap.add_argument("--debug-channel", default="rgb", choices=("r", "g", "b", "a", "rgb"), help="with --debug-view: the channel shown")
+    ap.add_argument("--debug-range", default="0,1", metavar="LO,HI", help="with --debug-view: the values mapped to black and white")
+    ap.add_argument("--debug-abs", action="store_true", help="with --debug-view: the absolute value before the range")
+    ap.add_argument("--debug-bilinear", action="store_true", help="with --debug-view: the bilinear sampler instead of nearest")
+    ap.add_argument("--debug-zoom", action="store_true", help="with --debug-view: the middle of the image four times larger")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     args = ap.parse_args()
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
-    if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles) and not args.deferred:
-        ap.error("--sky, --transparents, --bloom, --particles, --taa and --dof belong to --deferred")
+    if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles or args.debug_lines
+            or args.debug_frustum or args.debug_view or args.list_debug_views) and not args.deferred:
+        ap.error("--sky, --transparents, --debug-lines, --debug-frustum, --bloom, --particles, --taa and --dof belong to --deferred")
+    if args.focus_at and not args.dof:
+        ap.error("--focus-at belongs to --dof")
     if args.frames < 1:
         ap.error("--frames must be at least 1")
     from prosper_amd import capi, dds, gltf, ktx, structs as S
@@ -118,6 +152,7 @@ def main():
         print("missing images replaced by white: %s" % ", ".join(world.missing_images), file=sys.stderr)
     if args.env:
         world.skybox = ktx.read_cube(args.env)
+    gltf_camera = dict(world.camera)  # before --eye / --target: what --debug-frustum draws
     if args.eye:
         world.camera["eye"] = tuple(float(v) for v in args.eye.split(","))
     if args.target:
@@ -161,6 +196,14 @@ def main():
             hcam.set_jitter(True)
             taa = TemporalAntiAliasing(ctx)
             transforms = world.freeze()["transforms"]
+        frustum = None
+        if args.debug_frustum:
+            from prosper_amd import debug_geometry
+            own = Camera()
+            own.set_parameters(gltf_camera["fov"], gltf_camera["zN"], gltf_camera["zF"])
+            own.look_at(gltf_camera["eye"], gltf_camera["target"], gltf_camera["up"])
+            own.update_resolution(w, h)
+            frustum = debug_geometry.frustum_lines(debug_geometry.frustum_corners(own.update_buffer()[0]), (1.0, 1.0, 1.0))
         particle_step = 0
         if args.particles:
             # Particles::record without its render, K times: the reset step makes the emitters, the rest ages them
@@ -191,6 +234,16 @@ def main():
             if forward:
                 # over the sky-filled image, along the ray the G-buffer was traced with; ibl = 0, as prosper draws them
                 forward.record_transparent(hcam, w, h, ray_flags=S.TRANSPARENT_CAMERA_JITTER if args.taa else 0, frame_index=frame)
+            if args.debug_lines or frustum is not None:
+                # App::updateDebugLines, then DebugRenderer::record in place over the illumination and the depth
+                from prosper_amd import debug_geometry
+                debug = debug_geometry.DebugLines()
+                if args.debug_lines:
+                    _, points, spots = ctx.read_lights()
+                    debug.extend(debug_geometry.light_axes_from_buffers(points, spots))
+                if frustum is not None:
+                    debug.extend(frustum)
+                ctx.debug_lines(debug.array(), cam, w, h)
             if bloom:
                 bloom.record(w, h)  # in place
             if args.particles:
@@ -213,6 +266,10 @@ def main():
             info = ctx.transparent_info()
             print("transparents: %d pixels with layers, %d layers, deepest %d, last pass %.3f ms" % (
                 info.coveredPixels, info.totalLayers, info.maxLayers, info.ms), file=sys.stderr)
+        if args.debug_lines or frustum is not None:
+            info = ctx.debug_lines_info()
+            print("debug lines: %d lines, %d clipped away, %d fragments written, %.3f ms" % (
+                info.lineCount, info.linesClippedAway, info.fragmentsWritten, info.ms), file=sys.stderr)
         if args.particles:
             info = ctx.particles_info()
             print("particles: %d live of %d, %d fragments written, last step decay %.3f + simulate %.3f + render %.3f ms" % (
@@ -220,6 +277,20 @@ def main():
         if args.taa:
             info = ctx.taa_info()
             print("taa: %d frames, last resolve %.3f ms + expand %.3f ms" % (args.frames, info.resolveMs, info.expandMs), file=sys.stderr)
+        if args.focus_at:
+            # prosper's click-to-focus (App.cpp:583-631): TextureReadback of the depth as it stands here, debug lines and
+            # particles included, as Renderer.cpp:510 records it; prosper polls the value over the next frames, this waits
+            from prosper_amd import debug_geometry
+            px, py = (float(v) for v in args.focus_at.split(","))
+            ctx.texture_readback("depth", px, py)
+            ctx.read_hdr()  # (synchronises)
+            texel = ctx.try_texture_readback()
+            if texel is None or not texel[0] > 0.0:
+                sys.exit("--focus-at %s: nothing but sky under that pixel" % args.focus_at)
+            focus = float(debug_geometry.focus_distance_from_depth(cam, (px, py), (w, h), texel[0]))
+            c = world.camera
+            hcam.set_parameters(c["fov"], c["zN"], c["zF"], args.aperture, focus)
+            print("focus at (%g, %g): depth %.6f, focus distance %.4f" % (px, py, texel[0], focus), file=sys.stderr)
         if args.dof:
             dpc = DepthOfField(ctx).record(hcam, w, h)  # in place over the traced G-buffer's depth
             print("depth of field: focus %.3f, maxBackgroundCoC %.2f half-resolution texels, gatherRadius %d tiles" % (
@@ -227,6 +298,11 @@ def main():
         ctx.read_hdr()  # (synchronises)
         ms = (time.perf_counter() - t0) * 1e3
         args.spp = 1
+        if args.list_debug_views:
+            formats = ("RGBA32F", "RG32F", "R32F", "RGBA16F", "RG16F", "R16F", "RG16_UNORM", "RGBA8_UNORM")
+            for i, r in enumerate(ctx.debug_resources()):
+                print("%2d %-36s %-11s %s" % (i, r.name.decode(), formats[r.format], "%dx%d, %d level%s" % (
+                    r.width, r.height, r.levelCount, "" if r.levelCount == 1 else "s") if r.valid else "(not valid: its pass has not run)"))
     elif args.restir_di:
         import time
         t0 = time.perf_counter()
@@ -247,7 +323,16 @@ def main():
         b, gg, r = np.meshgrid(g, g, g, indexing="ij")
         lut = dds.encode_r9g9b9e5(np.stack([r, gg, b], axis=-1))
     ctx.set_tone_map_lut(lut)
-    write_png(args.out, ctx.tone_map(args.exposure, 1.0))
+    image = ctx.tone_map(args.exposure, 1.0)
+    if args.debug_view:
+        # TextureDebug::record, whose output replaces the final composite (Renderer.cpp:621-640)
+        name, _, lod = args.debug_view.partition(":")
+        lo, hi = (float(v) for v in args.debug_range.split(","))
+        flags = ("r", "g", "b", "a", "rgb").index(args.debug_channel) | (S.TEXTURE_DEBUG_ABS_BEFORE_RANGE if args.debug_abs else 0) | (
+            S.TEXTURE_DEBUG_ZOOM if args.debug_zoom else 0)
+        image = ctx.texture_debug(name, (w, h), (lo, hi), int(lod or 0), flags, bilinear=args.debug_bilinear)
+        print("debug view: %s, level %d, range %g..%g, channel %s" % (name, int(lod or 0), lo, hi, args.debug_channel), file=sys.stderr)
+    write_png(args.out, image)
     print("%s: %d triangles, %dx%d x %d spp in %.1f ms (%.0f Mpaths/s) -> %s" % (
         os.path.basename(args.gltf), st.triangleCount, w, h, args.spp, ms, w * h * args.spp / ms / 1e3, args.out))
     ctx.close()
