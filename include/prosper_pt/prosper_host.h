@@ -173,6 +173,44 @@ int prosper_host_skybox_renderer_record(
     prosper_host_skybox_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const float *nonLinearDepth, uint32_t onDevice, void *stream);
 
+/* render::HierarchicalDepthDownsampler (host/hierarchical_depth_downsampler.hpp; reference
+ * src/render/HierarchicalDepthDownsampler.hpp) on a context (borrowed): record = prosper_pt_hiz_downsample into the slot
+ * `nextFrame` & 1 picks, as the reference picks one of its two storage sets.  It needs no scene with a caller's depth;
+ * `nonLinearDepth` NULL: the last traced G-buffer's depth.  *mipCount and mips[0 .. *mipCount) (room for 12, either may
+ * be NULL) receive the levels' device pointers, which stand in for the reference's image handle. */
+typedef struct prosper_host_hiz_downsampler prosper_host_hiz_downsampler;
+int prosper_host_hiz_downsampler_create(prosper_pt_ctx *ctx, prosper_host_hiz_downsampler **out);
+void prosper_host_hiz_downsampler_destroy(prosper_host_hiz_downsampler *pass);
+int prosper_host_hiz_downsampler_record(
+    prosper_host_hiz_downsampler *pass, const float *nonLinearDepth, uint32_t onDevice, uint32_t width, uint32_t height,
+    uint32_t nextFrame, uint32_t *mipCount, const float **mips, void *stream);
+
+/* render::MeshletCuller and render::DrawStats (host/meshlet_culler.hpp; reference src/render/MeshletCuller.hpp,
+ * DrawStats.hpp) on a context the scene was uploaded to (borrowed): record_first_phase = Camera::updateBuffer +
+ * prosper_pt_cull_meshlets_first_phase (mode 0 Opaque, 1 Transparent; `inHierarchicalDepth` a pyramid slot or
+ * PROSPER_PT_NO_HIZ), record_second_phase = Camera::updateBuffer + prosper_pt_cull_meshlets_second_phase.  The output's
+ * device pointers stand in for the reference's buffer handles (secondPhaseInput NULL: none) and are valid until the next
+ * culling call.  read_draw_stats: prosper_pt_get_draw_stats (PROSPER_PT_NOT_READY with `wait` 0 while the device counts
+ * have not landed; the totals are there all the same). */
+typedef struct prosper_host_meshlet_culler prosper_host_meshlet_culler;
+typedef struct prosper_host_meshlet_culler_output
+{
+    const uint32_t *dataBuffer;       /* uint count; { drawInstanceIndex, meshletIndex }[] */
+    const uint32_t *argumentBuffer;   /* groupsX, groupsY, groupsZ */
+    const uint32_t *secondPhaseInput; /* first phase with a hierarchical depth only */
+    uint32_t capacity;                /* pairs each list has room for */
+    uint32_t reserved;
+} prosper_host_meshlet_culler_output;
+int prosper_host_meshlet_culler_create(prosper_pt_ctx *ctx, prosper_host_meshlet_culler **out);
+void prosper_host_meshlet_culler_destroy(prosper_host_meshlet_culler *pass);
+int prosper_host_meshlet_culler_record_first_phase(
+    prosper_host_meshlet_culler *pass, uint32_t mode, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    uint32_t inHierarchicalDepth, prosper_host_meshlet_culler_output *out, void *stream);
+int prosper_host_meshlet_culler_record_second_phase(
+    prosper_host_meshlet_culler *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
+    uint32_t inHierarchicalDepth, prosper_host_meshlet_culler_output *out, void *stream);
+int prosper_host_meshlet_culler_read_draw_stats(prosper_host_meshlet_culler *pass, prosper_pt_draw_stats *out, uint32_t wait);
+
 /* render::ForwardRenderer (host/forward_renderer.hpp; reference src/render/ForwardRenderer.hpp), its transparent pass
  * only, on a context the scene was uploaded to (borrowed): record_transparent = Camera::updateBuffer +
  * prosper_pt_forward_transparent over the context's HDR image.  `nonLinearDepth` NULL: the last traced G-buffer's depth;

@@ -1148,6 +1148,129 @@ int prosper_pt_texture_debug(
     void *device_rgba8, uint8_t *host_rgba8, size_t byte_size, void *stream);
 int prosper_pt_get_texture_debug_peek(prosper_pt_ctx *ctx, float out[4]);
 
+/* ---- hierarchical depth (src/render/HierarchicalDepthDownsampler.cpp, res/shader/hiz_downsampler.comp) ----
+ * HierarchicalDepthDownsampler::record: the depth pyramid prosper's meshlet culling tests bounding spheres against
+ * (DESIGN.md f17).  Additive: the ABI version stays 4.
+ *
+ * Input: `width` x `height` floats of reverse-Z depth (sky = 0), both sides above 1 (the reference asserts it) and at
+ * most 4096 (its twelve levels).  `nonLinearDepth` NULL: the last traced G-buffer's depth, whose extent must be
+ * width x height; otherwise the caller's array, on the device when `onDevice` is not 0, else host memory the call copies.
+ * Output: the context-owned pyramid of `slot` (0 or 1: prosper keeps the previous frame's beside this frame's), R32F,
+ *   level 0            bit_ceil(width) / 2 x bit_ceil(height) / 2
+ *   level l            max(level 0 >> l, 1) per side
+ *   levels             floor(log2(larger side of level 0)) + 1
+ * Texel (x, y) of level l is the MINIMUM of depth[min(Y, height - 1)][min(X, width - 1)] over the square
+ * x * 2^(l+1) <= X < (x + 1) * 2^(l+1), likewise Y: the farthest depth of the footprint, source coordinates clamped to the
+ * edge.  The minimum is exact and order-free, so every level is defined bit for bit.  Finite depths are assumed: a NaN
+ * loses against a number, and a footprint of NaNs alone gives a NaN.
+ * It needs no scene with a caller's depth.  A call on another stream than the slot's previous one waits for that one on
+ * the device; the caller keeps the slot's READERS on other streams ahead of the next call into it.  prosper_pt_upload_scene invalidates both slots.
+ * Refused: slot > 1, a side of 0, 1 or above 4096, NULL depth with no traced G-buffer or one of another extent. */
+int prosper_pt_hiz_downsample(
+    prosper_pt_ctx *ctx, uint32_t slot, const float *nonLinearDepth, uint32_t onDevice, uint32_t width, uint32_t height,
+    void *stream);
+typedef struct prosper_pt_hiz_info
+{
+    uint32_t valid;       /* 1: the slot holds the pyramid of the last prosper_pt_hiz_downsample into it; else the rest is 0 */
+    uint32_t width;       /* extent of level 0 */
+    uint32_t height;
+    uint32_t levelCount;
+    uint32_t sourceWidth; /* extent of the depth it was made from */
+    uint32_t sourceHeight;
+    uint32_t launches;    /* kernel launches of that call: 1, or 2 with more than six levels */
+    uint32_t reserved;
+} prosper_pt_hiz_info;
+int prosper_pt_get_hiz_info(prosper_pt_ctx *ctx, uint32_t slot, prosper_pt_hiz_info *out);
+/* Level `level` of the slot's pyramid on the device (row-major floats, its extent in *width / *height, which may be
+ * NULL); valid until the next call into that slot or the next scene.  A reader on the producing call's stream is ordered
+ * behind it already; a reader on another stream calls prosper_pt_hiz_wait first. */
+int prosper_pt_get_hiz_device_ptr(
+    prosper_pt_ctx *ctx, uint32_t slot, uint32_t level, const float **out, uint32_t *width, uint32_t *height);
+/* Makes `stream` wait, on the device, for the last prosper_pt_hiz_downsample into `slot` (nothing to wait for before the
+ * first): what a binder's own kernels that read prosper_pt_get_hiz_device_ptr's levels on another stream enqueue first. */
+int prosper_pt_hiz_wait(prosper_pt_ctx *ctx, uint32_t slot, void *stream);
+/* Synchronises `stream` (behind the producing call, whatever its stream) and copies the level to host memory;
+ * `bytes` is at least the level's width * height * 4. */
+int prosper_pt_read_hiz_level(prosper_pt_ctx *ctx, uint32_t slot, uint32_t level, float *host, size_t bytes, void *stream);
+
+/* ---- meshlet culling (src/render/MeshletCuller.cpp, res/shader/draw_list_generator.comp, draw_list_culler.comp) ----
+ * Prosper's two-phase visibility over the scene's meshlets: which meshlets of which draw instances the
+ * camera can see, given a depth pyramid.  The scene carries meshlets in prosper's layout (GeometryMetadata's four meshlet
+ * offsets, prosper_pt_mesh_info.meshletCount); a mesh without any contributes nothing.
+ *
+ * A draw list is prosper's: uint count; { drawInstanceIndex, meshletIndex }[count].  Beside each culled list lies its
+ * argument triple: (count, 1, 1) - groupsX mirrors the count - or (0, 0, 0) when the culler had nothing to cull (the
+ * argument writer's empty case).  The library cannot dispatch indirectly: it launches the culler over the host's upper
+ * bound, MeshletCuller::recordGenerateList's meshletCountUpperBound, and lanes past the list's count leave.  The order of
+ * a list's entries is whatever the atomics gave; the SET is the contract.
+ *
+ * first phase   generates the list of `mode` (OPAQUE: every material that is not BLEND; TRANSPARENT: BLEND only), then
+ *               culls it: an instance whose uniform scale is 0 (non-uniform) is always visible; otherwise the six frustum
+ *               planes of `camera`, the normal cone, and - with a pyramid slot - the occlusion test against that pyramid,
+ *               draw_list_culler.comp restated operation for operation in float32.  With `hizSlot` = PROSPER_PT_NO_HIZ
+ *               there is no occlusion test and no second-phase input.  Otherwise the meshlets that failed ONLY the
+ *               occlusion test form the second-phase input list.
+ * second phase  culls that list against another slot; never a third list.
+ * prosper_pt_cull_gbuffer  GBufferRenderer::record's sequence: first phase (OPAQUE) against the pyramid the previous call
+ *               kept, if any and if its source extent is camera->resolution; the pyramid of the last traced G-buffer's
+ *               depth into the other slot; the second phase against it (when the first had a pyramid); that pyramid is kept
+ *               as the next call's previous.  A new scene forgets it.
+ * Pending transform, animation and material updates take effect first.  The context holds ONE set of lists: a call
+ * replaces what the call before left.  Calls on different streams are ordered on the device like prosper_pt_debug_lines.
+ * Refused: no scene; an unknown mode or list; a slot that is not valid; camera->resolution differing from the pyramid's
+ * source extent; the second phase without a first phase that produced its input; meshlet ranges of a loaded mesh that
+ * leave its geometry buffer (PROSPER_PT_ERR_SCENE; checked once per geometry generation). */
+enum
+{
+    PROSPER_PT_CULL_MODE_OPAQUE = 0,
+    PROSPER_PT_CULL_MODE_TRANSPARENT = 1,
+};
+enum
+{
+    PROSPER_PT_DRAW_LIST_GENERATED = 0,
+    PROSPER_PT_DRAW_LIST_FIRST_PHASE = 1,
+    PROSPER_PT_DRAW_LIST_SECOND_PHASE_INPUT = 2,
+    PROSPER_PT_DRAW_LIST_SECOND_PHASE = 3,
+    PROSPER_PT_DRAW_LIST_COUNT = 4,
+};
+#define PROSPER_PT_NO_HIZ 0xFFFFFFFFu
+int prosper_pt_cull_meshlets_first_phase(
+    prosper_pt_ctx *ctx, uint32_t mode, const prosper_CameraUniforms *camera, uint32_t hizSlot, void *stream);
+int prosper_pt_cull_meshlets_second_phase(prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t hizSlot, void *stream);
+int prosper_pt_cull_gbuffer(prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, void *stream);
+/* Synchronises `stream` and copies list `which` to host memory: *count, its first min(count, capacity) pairs (`pairs`
+ * may be NULL with capacity 0) and, for the two culled lists, the argument triple (zeros for the other two; `args3` may be
+ * NULL).  PROSPER_PT_ERR_NO_SCENE for a list the last calls did not produce. */
+int prosper_pt_read_draw_list(
+    prosper_pt_ctx *ctx, uint32_t which, uint32_t *count, uint32_t *pairs, uint32_t capacity, uint32_t args3[3], void *stream);
+/* The list on the device (count first, then the pairs; room for *capacity pairs) and, for the culled lists, its argument
+ * triple (NULL otherwise): what a binder hands to its own indirect dispatch.  Valid until the next culling call. */
+int prosper_pt_get_draw_list_device_ptr(
+    prosper_pt_ctx *ctx, uint32_t which, const uint32_t **list, const uint32_t **args3, uint32_t *capacity);
+/* render::DrawStats.  The totals are counted on the host as recordGenerateList counts them, for the first phase's mode;
+ * drawnMeshletCount is the sum of both phases' visible counts; rasterizedTriangleCount the sum of the drawn meshlets'
+ * triangleCount, counted by the culler (prosper counts it in its mesh shader).  The two device counts travel through pinned
+ * memory behind the phases: with `wait` = 0 the call never blocks and returns PROSPER_PT_NOT_READY until they have landed,
+ * with the host's four totals in *out and the two device counts zero. */
+typedef struct prosper_pt_draw_stats
+{
+    uint32_t drawnMeshletCount;
+    uint32_t rasterizedTriangleCount;
+    uint32_t totalTriangleCount;
+    uint32_t totalMeshletCount;
+    uint32_t totalMeshCount;
+    uint32_t totalModelCount;
+} prosper_pt_draw_stats;
+int prosper_pt_get_draw_stats(prosper_pt_ctx *ctx, prosper_pt_draw_stats *out, uint32_t wait);
+/* Device time (ms) of the kernels of the last phases, between events on their stream (waits for them): the generator,
+ * the first-phase culler, the second-phase culler (0 where the last first phase was not followed by one). */
+int prosper_pt_get_cull_stage_ms(prosper_pt_ctx *ctx, float ms[3]);
+/* The per-model-instance uniform scales of the current scene version (World.cpp:485-498: the common length of the three
+ * rows of modelToWorld, 0 where they differ by more than 1e-4 relative), which the library computes on the GPU wherever a
+ * version's ModelInstanceTransforms table is made: the upload, prosper_pt_update_transforms, prosper_pt_animate.  Pending
+ * updates take effect first; synchronises `stream`.  `count` = the scene's model instances. */
+int prosper_pt_read_instance_scales(prosper_pt_ctx *ctx, float *host, uint32_t count, void *stream);
+
 /* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
  * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.
  *

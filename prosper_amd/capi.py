@@ -130,6 +130,19 @@ def lib():
     L.prosper_pt_try_texture_readback.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.prosper_pt_texture_debug.argtypes = [vp, u32, C.POINTER(S.TextureDebugPC), u32, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_texture_debug_peek.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    L.prosper_pt_hiz_downsample.argtypes = [vp, u32, vp, u32, u32, u32, vp]
+    L.prosper_pt_get_hiz_info.argtypes = [vp, u32, C.POINTER(S.HizInfo)]
+    L.prosper_pt_get_hiz_device_ptr.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_hiz_wait.argtypes = [vp, u32, vp]
+    L.prosper_pt_cull_meshlets_first_phase.argtypes = [vp, u32, C.POINTER(S.CameraUniforms), u32, vp]
+    L.prosper_pt_cull_meshlets_second_phase.argtypes = [vp, C.POINTER(S.CameraUniforms), u32, vp]
+    L.prosper_pt_cull_gbuffer.argtypes = [vp, C.POINTER(S.CameraUniforms), vp]
+    L.prosper_pt_read_draw_list.argtypes = [vp, u32, C.POINTER(u32), vp, u32, C.POINTER(u32 * 3), vp]
+    L.prosper_pt_get_draw_list_device_ptr.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
+    L.prosper_pt_get_draw_stats.argtypes = [vp, C.POINTER(S.DrawStats), u32]
+    L.prosper_pt_get_cull_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 3)]
+    L.prosper_pt_read_instance_scales.argtypes = [vp, vp, u32, vp]
+    L.prosper_pt_read_hiz_level.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
     L.prosper_pt_get_ibl_info.argtypes = [vp, C.POINTER(S.IblInfo)]
     L.prosper_pt_read_ibl.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
@@ -254,6 +267,16 @@ def lib():
     L.prosper_host_skybox_renderer_destroy.argtypes = [vp]
     L.prosper_host_skybox_renderer_destroy.restype = None
     L.prosper_host_skybox_renderer_record.argtypes = [vp, vp, u32, u32, vp, u32, vp]
+    L.prosper_host_meshlet_culler_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_meshlet_culler_destroy.argtypes = [vp]
+    L.prosper_host_meshlet_culler_destroy.restype = None
+    L.prosper_host_meshlet_culler_record_first_phase.argtypes = [vp, u32, vp, u32, u32, u32, C.POINTER(S.MeshletCullerOutput), vp]
+    L.prosper_host_meshlet_culler_record_second_phase.argtypes = [vp, vp, u32, u32, u32, C.POINTER(S.MeshletCullerOutput), vp]
+    L.prosper_host_meshlet_culler_read_draw_stats.argtypes = [vp, C.POINTER(S.DrawStats), u32]
+    L.prosper_host_hiz_downsampler_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_hiz_downsampler_destroy.argtypes = [vp]
+    L.prosper_host_hiz_downsampler_destroy.restype = None
+    L.prosper_host_hiz_downsampler_record.argtypes = [vp, vp, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(vp), vp]
     L.prosper_host_forward_renderer_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_forward_renderer_destroy.argtypes = [vp]
     L.prosper_host_forward_renderer_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
@@ -980,6 +1003,98 @@ class Context:
         info = S.DebugLinesInfo()
         _check(lib().prosper_pt_get_debug_lines_info(self._h, C.byref(info)))
         return info
+
+    # ---- hierarchical depth (prosper_pt_hiz_downsample) ----
+
+    def hiz_downsample(self, width, height, slot=0, depth=None, depth_ptr=None, stream=None):
+        """HierarchicalDepthDownsampler::record (prosper_pt_hiz_downsample): the minimum pyramid of a reverse-Z depth into
+        `slot` (0 or 1).  `depth`: a host array [h, w]; `depth_ptr`: a device pointer; neither: the last traced
+        G-buffer's depth."""
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert dp is None or dp.shape == (height, width)
+        ptr = depth_ptr if dp is None else dp.ctypes.data
+        _check(lib().prosper_pt_hiz_downsample(self._h, slot, C.c_void_p(ptr), 1 if dp is None else 0, width, height,
+                                               C.c_void_p(stream)))
+
+    def hiz_info(self, slot=0):
+        """S.HizInfo of `slot` (never waits)."""
+        info = S.HizInfo()
+        _check(lib().prosper_pt_get_hiz_info(self._h, slot, C.byref(info)))
+        return info
+
+    def hiz_device_ptr(self, slot, level):
+        """(device pointer, width, height) of one level of the slot's pyramid."""
+        ptr, w, h = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_get_hiz_device_ptr(self._h, slot, level, C.byref(ptr), C.byref(w), C.byref(h)))
+        return ptr.value, w.value, h.value
+
+    def hiz_wait(self, slot, stream):
+        """prosper_pt_hiz_wait: `stream` waits on the device for the last hiz_downsample into `slot`."""
+        _check(lib().prosper_pt_hiz_wait(self._h, slot, C.c_void_p(stream)))
+
+    def read_hiz_level(self, slot, level, stream=None):
+        """One level of the slot's pyramid as float32 [h, w] (waits for it)."""
+        _, w, h = self.hiz_device_ptr(slot, level)
+        out = np.empty((h, w), np.float32)
+        _check(lib().prosper_pt_read_hiz_level(self._h, slot, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def read_hiz(self, slot=0, stream=None):
+        """Every level of the slot's pyramid, finest first."""
+        return [self.read_hiz_level(slot, l, stream) for l in range(self.hiz_info(slot).levelCount)]
+
+    # ---- meshlet culling (prosper_pt_cull_meshlets_*; DESIGN.md f17) ----
+
+    def cull_first_phase(self, camera, mode=S.CULL_MODE_OPAQUE, hiz_slot=None, stream=None):
+        """MeshletCuller::recordFirstPhase: generate the list of `mode`, cull it against `camera` and, with `hiz_slot`
+        (0 or 1), against that pyramid."""
+        slot = S.NO_HIZ if hiz_slot is None else hiz_slot
+        _check(lib().prosper_pt_cull_meshlets_first_phase(self._h, mode, C.byref(camera), slot, C.c_void_p(stream)))
+
+    def cull_second_phase(self, camera, hiz_slot, stream=None):
+        """MeshletCuller::recordSecondPhase: the first phase's occluded list against the pyramid of `hiz_slot`."""
+        _check(lib().prosper_pt_cull_meshlets_second_phase(self._h, C.byref(camera), hiz_slot, C.c_void_p(stream)))
+
+    def cull_gbuffer(self, camera, stream=None):
+        """prosper_pt_cull_gbuffer: first phase against the kept pyramid, the traced depth's pyramid, second phase."""
+        _check(lib().prosper_pt_cull_gbuffer(self._h, C.byref(camera), C.c_void_p(stream)))
+
+    def read_draw_list(self, which, stream=None):
+        """-> (pairs uint32 [count, 2] of (drawInstanceIndex, meshletIndex), args uint32 [3])"""
+        n, args = C.c_uint32(), (C.c_uint32 * 3)()
+        _check(lib().prosper_pt_read_draw_list(self._h, which, C.byref(n), None, 0, C.byref(args), C.c_void_p(stream)))
+        pairs = np.empty((n.value, 2), np.uint32)
+        if n.value:
+            _check(lib().prosper_pt_read_draw_list(self._h, which, C.byref(n), pairs.ctypes.data, pairs.shape[0], C.byref(args),
+                                                   C.c_void_p(stream)))
+        return pairs, np.array(args[:], np.uint32)
+
+    def draw_list_device_ptr(self, which):
+        """(list pointer, argument triple pointer or None, capacity in pairs)"""
+        lp, ap, cap = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _check(lib().prosper_pt_get_draw_list_device_ptr(self._h, which, C.byref(lp), C.byref(ap), C.byref(cap)))
+        return lp.value, ap.value, cap.value
+
+    def draw_stats(self, wait=True):
+        """S.DrawStats of the last culling calls; None with wait=False while the counts have not landed."""
+        out = S.DrawStats()
+        rc = lib().prosper_pt_get_draw_stats(self._h, C.byref(out), 1 if wait else 0)
+        if rc == S.NOT_READY:
+            return None
+        _check(rc)
+        return out
+
+    def cull_stage_ms(self):
+        """(generator, first-phase culler, second-phase culler) device milliseconds of the last phases (waits for them)."""
+        ms = (C.c_float * 3)()
+        _check(lib().prosper_pt_get_cull_stage_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def read_instance_scales(self, count, stream=None):
+        """The current scene version's per-model-instance uniform scales, float32 [count] (0: non-uniform)."""
+        out = np.empty(count, np.float32)
+        _check(lib().prosper_pt_read_instance_scales(self._h, out.ctypes.data, count, C.c_void_p(stream)))
+        return out
 
     # ---- the registry of the context's images and the one-texel readback (DESIGN.md f16) ----
 

@@ -25,6 +25,16 @@ V3 norm3(V3 a)
     return {a.x * inv, a.y * inv, a.z * inv};
 }
 
+V3 add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+V3 mul(float f, V3 a) { return {f * a.x, f * a.y, f * a.z}; }
+
+// src/scene/Camera.cpp:39-45 getPlane: the plane through three points, (normal, -dot(normal, p0))
+prosper_vec4 plane_through(V3 p0, V3 p1, V3 p2)
+{
+    const V3 normal = norm3(cross3(sub(p1, p0), sub(p2, p0)));
+    return prosper_vec4{normal.x, normal.y, normal.z, -dot3(normal, p0)};
+}
+
 // Gauss-Jordan inverse of a column-major 4x4 (well conditioned for rigid/projective camera matrices)
 void invert4(const float in[16], float out[16])
 {
@@ -147,11 +157,40 @@ void Camera::perspective()
     m_parameters.focalLength = sensorHeight * tf * 0.5f;
 }
 
+// src/scene/Camera.cpp:274-315 getFrustumCorners, then :397-415 updateFrustumPlanes: the six planes through the
+// frustum's world-space corners, normals pointing into the frustum
+void Camera::updateFrustumPlanes(prosper_CameraUniforms &u) const
+{
+    const float *m = m_worldToCamera; // rows 0, 1, 2 of the matrix: right, up, -forward
+    const V3 right{m[0], m[4], m[8]}, up{m[1], m[5], m[9]}, fwd{-m[2], -m[6], -m[10]};
+    const V3 eye{m_transform.eye[0], m_transform.eye[1], m_transform.eye[2]};
+    const float ar = (float)m_resolution[0] / (float)m_resolution[1];
+    const float halfYFar = m_parameters.zF * std::tan(m_parameters.fov * 0.5f);
+    const float halfXFar = halfYFar * ar;
+    const float halfYNear = m_parameters.zN * std::tan(m_parameters.fov * 0.5f);
+    const float halfXNear = halfYNear * ar;
+    // eye + z * fwd -+ halfX * right -+ halfY * up, summed in that order
+    const auto corner = [&](float z, float sx, float halfX, float sy, float halfY)
+    { return add(add(add(eye, mul(z, fwd)), mul(sx * halfX, right)), mul(sy * halfY, up)); };
+    const float zN = m_parameters.zN, zF = m_parameters.zF;
+    const V3 bottomLeftNear = corner(zN, -1.f, halfXNear, -1.f, halfYNear), bottomRightNear = corner(zN, 1.f, halfXNear, -1.f, halfYNear);
+    const V3 topLeftNear = corner(zN, -1.f, halfXNear, 1.f, halfYNear), topRightNear = corner(zN, 1.f, halfXNear, 1.f, halfYNear);
+    const V3 bottomLeftFar = corner(zF, -1.f, halfXFar, -1.f, halfYFar), bottomRightFar = corner(zF, 1.f, halfXFar, -1.f, halfYFar);
+    const V3 topLeftFar = corner(zF, -1.f, halfXFar, 1.f, halfYFar), topRightFar = corner(zF, 1.f, halfXFar, 1.f, halfYFar);
+    u.nearPlane = plane_through(bottomRightNear, bottomLeftNear, topRightNear);
+    u.farPlane = plane_through(bottomRightFar, topRightFar, bottomLeftFar);
+    u.leftPlane = plane_through(bottomLeftNear, bottomLeftFar, topLeftNear);
+    u.rightPlane = plane_through(bottomRightNear, topRightNear, bottomRightFar);
+    u.topPlane = plane_through(topLeftNear, topLeftFar, topRightNear);
+    u.bottomPlane = plane_through(bottomLeftNear, bottomRightNear, bottomLeftFar);
+}
+
 // src/scene/Camera.cpp:162-204
 const prosper_CameraUniforms &Camera::updateBuffer()
 {
     perspective();
     prosper_CameraUniforms u = {};
+    updateFrustumPlanes(u);
     std::memcpy(&u.worldToCamera, m_worldToCamera, 64);
     std::memcpy(&u.cameraToWorld, m_cameraToWorld, 64);
     std::memcpy(&u.cameraToClip, m_cameraToClip, 64);

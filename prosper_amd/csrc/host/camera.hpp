@@ -1,11 +1,11 @@
 // host/camera.hpp — scene::Camera of the headless host layer.
 //
 // Restates the parts of prosper's camera the RT reference pass consumes
-// (reference: src/scene/Camera.hpp:22-48, src/scene/Camera.cpp:105-204,366-395): a right-handed
+// (reference: src/scene/Camera.hpp:22-48, src/scene/Camera.cpp:39-45,105-204,274-315,366-415): a right-handed
 // look-at worldToCamera, a reverse-Z, Y-flipped perspective cameraToClip, the CameraUniforms
 // block and CameraParameters::focalLength, the TAA jitter (Camera.cpp:71-80,119-144) and the previous
-// frame's matrices and jitter.  Frustum planes for culling and the gesture offsets of the
-// interactive app are raster/UI features and stay out of scope.
+// frame's matrices and jitter, and the six frustum planes prosper's culling tests against (normals pointing
+// inwards).  The gesture offsets of the interactive app are UI features and stay out of scope.
 #pragma once
 
 #include <cstdint>
@@ -53,6 +53,7 @@ class Camera
   private:
     void updateWorldToCamera();
     void perspective();
+    void updateFrustumPlanes(prosper_CameraUniforms &u) const;
 
     CameraTransform m_transform;
     CameraParameters m_parameters;

@@ -4,8 +4,9 @@
 // ForwardRenderer.cpp:222-256; Renderer.cpp:493-500 runs it between the skybox and bloom): the BLEND surfaces drawn over
 // the illumination against the depth, through prosper_pt_forward_transparent over the context's HDR image (DESIGN.md
 // f12).  prosper draws them with Options{transparents, drawType}, i.e. ibl = 0; `applyIbl` is there for the push constant's
-// other value.  The opaque passes of ForwardRenderer (recordOpaque: the forward path's meshlet-culled raster) stay out
-// of scope like the raster G-buffer.
+// other value.  The culling recordTransparent runs first is render::MeshletCuller in Mode::Transparent (meshlet_culler.hpp,
+// DESIGN.md f17).  The opaque passes of ForwardRenderer (recordOpaque: the forward path's mesh-shader raster) stay out of
+// scope like the raster G-buffer.
 #pragma once
 
 #include <cstdint>

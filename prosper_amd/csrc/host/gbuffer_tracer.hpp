@@ -4,7 +4,9 @@
 // GBufferRenderer::record): the albedo/roughness, normal/metallic and depth images RtDirectIllumination reads, traced
 // over the context's scene by prosper_pt_trace_gbuffer into context-owned device buffers, and with `recordVelocity` the
 // velocity image TemporalAntiAliasing reads, sampled through the camera's TAA jitter (prosper_pt_trace_gbuffer_velocity;
-// DESIGN.md f10).  The raster pass itself (meshlet culling) stays out of scope.
+// DESIGN.md f10).  The meshlet culling GBufferRenderer::record runs around its draws is render::MeshletCuller
+// (meshlet_culler.hpp; prosper_pt_cull_gbuffer is the whole sequence); the mesh-shader draws themselves stay
+// out of scope.
 #pragma once
 
 #include <cstdint>

@@ -291,6 +291,8 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     acc->transforms.assign(v->modelInstanceTransforms, v->modelInstanceTransforms + v->modelInstanceCount);
     ctx->dTransforms = const_cast<prosper_ModelInstanceTransforms *>(s.modelInstanceTransforms);
     acc->dTransformsV[0] = ctx->dTransforms;
+    if ((rc = enqueue_instance_scales(ctx, acc, 0, ctx->dTransforms, v->modelInstanceCount, nullptr))) return rc;
+    PPT_HIP(hipStreamSynchronize(nullptr));
     GeometryJob job;
     GeometryTarget target = context_target(ctx);
     {
@@ -798,7 +800,7 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
     if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
-        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_animation_state(ctx))
+        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_culling_passes(ctx) || !create_animation_state(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -859,6 +861,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_taa_passes(ctx);
     destroy_particles_passes(ctx);
     destroy_debug_passes(ctx);
+    destroy_culling_passes(ctx);
     destroy_animation_state(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
@@ -870,6 +873,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     if (rc != PROSPER_PT_OK) return rc;
     forget_ibl_maps(ctx);
     forget_taa_history(ctx);
+    forget_hiz(ctx);
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());
@@ -1086,6 +1090,7 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
     }
     if (animate && (rc = enqueue_animation(ctx, acc->dTransformsV[v], tableCount, animateLights ? ls->dBlocks[lv] : nullptr, stream))) return rc;
     if (animateLights && (rc = ls->ready.record(stream))) return rc;
+    if ((rc = enqueue_instance_scales(ctx, acc, v, acc->dTransformsV[v], tableCount, stream))) return rc;
     // world-space triangles again, in both orders (the shading and any-hit records hold object-space attributes and stay
     // as they are), then the boxes.  (Also when only transforms of instances without geometry changed: a version must be
     // whole.)

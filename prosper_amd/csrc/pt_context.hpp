@@ -87,6 +87,16 @@ void destroy_particles_passes(prosper_pt_ctx *ctx);
 struct DebugPassState;
 bool create_debug_passes(prosper_pt_ctx *ctx);
 void destroy_debug_passes(prosper_pt_ctx *ctx);
+// State of the visibility system (pt_culling_passes.cpp): the two depth pyramids, the draw lists of the last culling
+// calls with their argument triples and statistics.  Made and freed like the others.
+struct CullingPassState;
+bool create_culling_passes(prosper_pt_ctx *ctx);
+void destroy_culling_passes(prosper_pt_ctx *ctx);
+// a new scene: both pyramids and the draw lists describe the old one
+void forget_hiz(prosper_pt_ctx *ctx);
+struct AccelState;
+// the scales of the table `transforms` into acc->dScalesV[v] (allocated at first need), enqueued on `stream`
+int enqueue_instance_scales(prosper_pt_ctx *ctx, AccelState *acc, uint32_t v, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t stream);
 // One 2-D image a pass module owns, as the registry of the inspection passes describes it (prosper_pt_get_debug_resource).
 // Every module lists its images in a fixed order whether they are valid or not, so an index means the same image for
 // the life of the context.  `valid`: the owning pass has run and the storage still holds what its last call left.
@@ -196,6 +206,9 @@ struct AccelState
     WorldTriangle *dTrisV[kVersions] = {};
     BvhNode *dNodesV[kVersions] = {};
     prosper_ModelInstanceTransforms *dTransformsV[kVersions] = {};
+    // one uniform scale per model instance beside every version's table (World.cpp:485-498; 0: non-uniform), made on the
+    // GPU wherever that table is made: the upload, a flushed transform update or animation, a geometry build
+    float *dScalesV[kVersions] = {};
     bool nodesCurrent[kVersions] = {}; // the version's node array holds the tree of the last build (child references)
     VersionRing<kVersions> versions;
     // an update waits here until the next consumer of the scene - normally the next render, which runs it at the head of
@@ -344,6 +357,7 @@ struct prosper_pt_ctx
     ppt::TaaPassState *taaPasses = nullptr;
     ppt::ParticlesPassState *particlesPasses = nullptr;
     ppt::DebugPassState *debugPasses = nullptr;
+    ppt::CullingPassState *cullingPasses = nullptr; // the depth pyramids, the draw lists, DrawStats
     ppt::AnimationState *animation = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;

@@ -590,6 +590,7 @@ static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild)
                 PPT_HIP(hipMemcpyAsync(dT, acc->transforms.data(), sizeof(prosper_ModelInstanceTransforms) * acc->transforms.size(), hipMemcpyHostToDevice, t.stream));
             acc->dTransformsV[0] = static_cast<prosper_ModelInstanceTransforms *>(dT);
             b->scene.modelInstanceTransforms = acc->dTransformsV[0];
+            if ((r = enqueue_instance_scales(ctx, acc, 0, acc->dTransformsV[0], (uint32_t)acc->transforms.size(), t.stream))) return r;
             GeometryJob job;
             if ((r = begin_geometry(ctx, t, *layout, keep ? changed.get() : nullptr, job))) return r;
             if (failHalfWay) return fail(PROSPER_PT_ERR_UNSUPPORTED, "debug option failNextUpdate is set");
@@ -668,6 +669,7 @@ int poll_mesh_build(prosper_pt_ctx *ctx, bool wait)
             retire(ctx, old->dTrisV[v]);
             retire(ctx, old->dNodesV[v]);
             retire(ctx, old->dTransformsV[v]);
+            retire(ctx, old->dScalesV[v]);
         }
         ctx->retiredAccel.push_back(old);
         acc->refits = std::max(acc->refits, old->refits); // (refits of the old generation while the build ran count too)

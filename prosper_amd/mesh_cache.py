@@ -7,7 +7,7 @@ eight offsets, usesShortIndices, blobByteCount) and the blob: indices (u16 padde
 meshletTriangles.  Attribute offsets count u32 words from the start of the blob; 0xFFFFFFFF = absent.
 
 The path tracer needs indices, positions, normals, tangents and uvs; meshlet sections are carried along
-untouched (the RT pass never reads them)."""
+untouched (the RT pass never reads them).  pack_cache writes them on request (meshlets.py)."""
 import struct
 
 import numpy as np
@@ -55,8 +55,9 @@ def write_mesh_cache(path, header, blob_words, source_write_time=0):
         f.write(blob.tobytes())
 
 
-def pack_cache(positions, indices, normals, tangents=None, uvs=None):
-    """What writeCache lays out for a primitive without meshlets: (header, blob words)."""
+def pack_cache(positions, indices, normals, tangents=None, uvs=None, with_meshlets=False):
+    """What writeCache lays out for a primitive: (header, blob words).  Without meshlets by default; `with_meshlets`
+    appends the four sections of meshlets.build_meshlets in writeCache's order."""
     from .world import pack_mesh_data
     positions = np.asarray(positions, np.float32).reshape(-1, 3)
     indices = np.asarray(indices, np.uint32).reshape(-1)
@@ -84,6 +85,18 @@ def pack_cache(positions, indices, normals, tangents=None, uvs=None):
     header["meshletsOffset"] = header["meshletBoundsOffset"] = words
     header["meshletVerticesOffset"] = words * (2 if short else 1)
     header["meshletTrianglesByteOffset"] = words * 4
+    if with_meshlets and indices.size:
+        from . import meshlets as M
+        # (over the positions as the blob holds them: fp16)
+        built = M.build_meshlets(positions.astype(np.float16).astype(np.float32), indices)
+        header["meshletCount"] = len(built["meshlets"])
+        keys = {"meshlets": ("meshletsOffset", 1), "bounds": ("meshletBoundsOffset", 1),
+                "vertices": ("meshletVerticesOffset", 2 if short else 1), "triangles": ("meshletTrianglesByteOffset", 4)}
+        for name, section in M.pack_sections(built, short):
+            key, unit = keys[name]
+            header[key] = words * unit
+            parts.append(section)
+            words += section.size
     return header, np.concatenate(parts).astype(np.uint32)
 
 
@@ -111,6 +124,11 @@ def add_cached_mesh(world, header, blob_words, material_index):
     md.normalsOffset = off("normalsOffset")
     md.tangentsOffset = off("tangentsOffset")
     md.texCoord0sOffset = off("texCoord0sOffset")
+    if header["meshletCount"]:
+        md.meshletsOffset = base + header["meshletsOffset"]
+        md.meshletBoundsOffset = base + header["meshletBoundsOffset"]
+        md.meshletVerticesOffset = base * (2 if short else 1) + header["meshletVerticesOffset"]
+        md.meshletTrianglesByteOffset = base * 4 + header["meshletTrianglesByteOffset"]
     world.metadatas.append(md)
     world.mesh_infos.append(S.MeshInfo(header["vertexCount"], header["indexCount"], header["meshletCount"], material_index))
     world._frozen = None

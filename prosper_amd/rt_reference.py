@@ -348,6 +348,82 @@ class DeferredShading:
             pass
 
 
+class HierarchicalDepthDownsampler:
+    """render::HierarchicalDepthDownsampler (csrc/host/hierarchical_depth_downsampler.hpp) on a Context: record makes the
+    depth pyramid (Context.hiz_downsample) in the slot `next_frame` & 1 picks and returns its levels' device pointers."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_hiz_downsampler_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, width, height, next_frame=0, depth=None, depth_ptr=None, stream=None):
+        """`depth`: a host array [h, w]; `depth_ptr`: a device pointer; neither: the last traced G-buffer's depth."""
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        count, mips = C.c_uint32(), (C.c_void_p * 12)()
+        rc = lib().prosper_host_hiz_downsampler_record(
+            self._h, C.c_void_p(depth_ptr if dp is None else dp.ctypes.data), 1 if dp is None else 0, width, height,
+            next_frame, C.byref(count), mips, C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return [mips[l] for l in range(count.value)]
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_hiz_downsampler_destroy(self._h)
+            self._h = None
+
+
+class MeshletCuller:
+    """render::MeshletCuller (csrc/host/meshlet_culler.hpp) on a Context the scene was uploaded to: record_first_phase /
+    record_second_phase return S.MeshletCullerOutput (device pointers of the lists and argument triples);
+    read_draw_stats is render::DrawStats."""
+
+    MODE_OPAQUE, MODE_TRANSPARENT = 0, 1
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_meshlet_culler_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record_first_phase(self, camera, width, height, mode=0, hierarchical_depth=None, stream=None):
+        """`camera`: a Camera; `hierarchical_depth`: a pyramid slot (0 or 1) or None"""
+        out = S.MeshletCullerOutput()
+        slot = S.NO_HIZ if hierarchical_depth is None else hierarchical_depth
+        rc = lib().prosper_host_meshlet_culler_record_first_phase(self._h, mode, camera._h, width, height, slot, C.byref(out),
+                                                                   C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out
+
+    def record_second_phase(self, camera, width, height, hierarchical_depth, stream=None):
+        out = S.MeshletCullerOutput()
+        rc = lib().prosper_host_meshlet_culler_record_second_phase(self._h, camera._h, width, height, hierarchical_depth,
+                                                                    C.byref(out), C.c_void_p(stream))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out
+
+    def read_draw_stats(self, wait=True):
+        """(S.DrawStats, landed): with wait=False the totals come at once, the two device counts once `landed`"""
+        out = S.DrawStats()
+        rc = lib().prosper_host_meshlet_culler_read_draw_stats(self._h, C.byref(out), 1 if wait else 0)
+        if rc not in (0, S.NOT_READY):
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out, rc == 0
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_meshlet_culler_destroy(self._h)
+            self._h = None
+
+
 class SkyboxRenderer:
     """render::SkyboxRenderer (csrc/host/skybox_renderer.hpp) on a Context the scene was uploaded to: record fills the sky
     into the context's HDR image wherever the depth is the far plane's (Context.skybox_fill)."""

@@ -479,6 +479,29 @@ class DebugLinesInfo(C.Structure):
                 ("linesClippedAway", C.c_uint32), ("ms", C.c_float)]
 
 
+class HizInfo(C.Structure):
+    """prosper_pt_hiz_info: one slot's depth pyramid (level 0's extent, the depth's extent it was made from)"""
+    _fields_ = [("valid", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("levelCount", C.c_uint32),
+                ("sourceWidth", C.c_uint32), ("sourceHeight", C.c_uint32), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CULL_MODE_OPAQUE, CULL_MODE_TRANSPARENT = 0, 1
+DRAW_LIST_GENERATED, DRAW_LIST_FIRST_PHASE, DRAW_LIST_SECOND_PHASE_INPUT, DRAW_LIST_SECOND_PHASE = range(4)
+NO_HIZ = 0xFFFFFFFF  # PROSPER_PT_NO_HIZ
+
+
+class DrawStats(C.Structure):
+    """prosper_pt_draw_stats: render::DrawStats"""
+    _fields_ = [("drawnMeshletCount", C.c_uint32), ("rasterizedTriangleCount", C.c_uint32), ("totalTriangleCount", C.c_uint32),
+                ("totalMeshletCount", C.c_uint32), ("totalMeshCount", C.c_uint32), ("totalModelCount", C.c_uint32)]
+
+
+class MeshletCullerOutput(C.Structure):
+    """prosper_host_meshlet_culler_output: device pointers in place of the reference's buffer handles"""
+    _fields_ = [("dataBuffer", C.c_void_p), ("argumentBuffer", C.c_void_p), ("secondPhaseInput", C.c_void_p),
+                ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 NOT_READY = -7  # PROSPER_PT_NOT_READY
 (DEBUG_FORMAT_RGBA32F, DEBUG_FORMAT_RG32F, DEBUG_FORMAT_R32F, DEBUG_FORMAT_RGBA16F, DEBUG_FORMAT_RG16F, DEBUG_FORMAT_R16F,
  DEBUG_FORMAT_RG16_UNORM, DEBUG_FORMAT_RGBA8_UNORM) = range(8)

@@ -244,6 +244,56 @@ class World:
         self.mesh_infos.append(S.MeshInfo(vertex_count, int(indices.size), 0, material_index))
         return len(self.metadatas) - 1
 
+    def _buffer_words_of(self, buffer_index):
+        """the geometry buffer as one array (its parts are joined once and kept as one part)"""
+        parts = self._buffers[buffer_index]
+        if len(parts) != 1:
+            self._buffers[buffer_index] = parts = [np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)]
+        return parts[0]
+
+    def mesh_geometry(self, mesh_index):
+        """(positions float32 [n, 3] as the buffer holds them - fp16 -, indices uint32 [m]) of a loaded mesh"""
+        md, info = self.metadatas[mesh_index], self.mesh_infos[mesh_index]
+        words = self._buffer_words_of(md.bufferIndex)
+        n = info.vertexCount
+        positions = words[md.positionsOffset:md.positionsOffset + 2 * n].view(np.float16).reshape(n, 4)[:, :3].astype(np.float32)
+        if md.usesShortIndices == 1:
+            indices = words.view(np.uint16)[md.indicesOffset:md.indicesOffset + info.indexCount].astype(np.uint32)
+        else:
+            indices = words[md.indicesOffset:md.indicesOffset + info.indexCount].copy()
+        return positions, indices
+
+    def attach_meshlets(self, mesh_index, built):
+        """Appends the four sections of `built` (what meshlets.build_meshlets returns) to the mesh's geometry buffer in
+        writeCache's order - meshlets, meshletBounds, meshletVertices (u16 when the mesh usesShortIndices),
+        meshletTriangles - and fills the four metadata offsets and MeshInfo.meshletCount.  Nothing that was there moves."""
+        from . import meshlets as M
+        md, info = self.metadatas[mesh_index], self.mesh_infos[mesh_index]
+        assert md.bufferIndex != S.ABSENT and info.meshletCount == 0
+        b, short = md.bufferIndex, md.usesShortIndices == 1
+        offsets = {}
+        for name, words in M.pack_sections(built, short):
+            offsets[name] = self._buffer_words[b]
+            self._buffers[b].append(np.ascontiguousarray(words, np.uint32))
+            self._buffer_words[b] += int(words.size)
+        md.meshletsOffset = offsets["meshlets"]
+        md.meshletBoundsOffset = offsets["bounds"]
+        md.meshletVerticesOffset = offsets["vertices"] * (2 if short else 1)
+        md.meshletTrianglesByteOffset = offsets["triangles"] * 4
+        info.meshletCount = len(built["meshlets"])
+        self._frozen = None
+        return info.meshletCount
+
+    def add_meshlets(self):
+        """Opt-in: partitions every loaded mesh that has no meshlets yet (meshlets.build_meshlets, over the positions as the
+        buffer holds them) and attaches the result (attach_meshlets).  -> meshlets added"""
+        from . import meshlets as M
+        todo = [i for i, (md, info) in enumerate(zip(self.metadatas, self.mesh_infos))
+                if md.bufferIndex != S.ABSENT and info.indexCount != 0 and info.meshletCount == 0]
+        # (every mesh is read before anything is appended: a buffer is joined once, not once per mesh)
+        built = [M.build_meshlets(*self.mesh_geometry(i)) for i in todo]
+        return sum(self.attach_meshlets(i, b) for i, b in zip(todo, built))
+
     @property
     def mesh_ranges(self):
         """Per mesh: (buffer index, first word, words) of the bytes the path reads of it in its geometry buffer - indices,

@@ -58,6 +58,10 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  prosper's texture viewer (prosper_pt_texture_debug): the PNG is level LOD of the registry
                                  image NAME through these settings instead of the tone map's output, as Renderer.cpp:621-640
                                  replaces the final composite
+    --deferred --cull-stats      prosper's visibility system: meshlets are built for the loaded scene
+                                 (World.add_meshlets), prosper_pt_cull_gbuffer runs after the G-buffer of each frame - first
+                                 phase against the previous frame's depth pyramid, the pyramid of this frame's depth, second
+                                 phase - and the frame's DrawStats are printed
     --deferred ... --list-debug-views
                                  after the frame, the registry of the context's 2-D images (prosper_pt_get_debug_resource):
                                  index, name, format, extent and levels of what each pass left
@@ -131,14 +135,15 @@ def main():
     ap.add_argument("--debug-abs", action="store_true", help="with --debug-view: the absolute value before the range")
     ap.add_argument("--debug-bilinear", action="store_true", help="with --debug-view: the bilinear sampler instead of nearest")
     ap.add_argument("--debug-zoom", action="store_true", help="with --debug-view: the middle of the image four times larger")
+    ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     args = ap.parse_args()
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
     if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles or args.debug_lines
-            or args.debug_frustum or args.debug_view or args.list_debug_views) and not args.deferred:
-        ap.error("--sky, --transparents, --debug-lines, --debug-frustum, --bloom, --particles, --taa and --dof belong to --deferred")
+            or args.debug_frustum or args.debug_view or args.list_debug_views or args.cull_stats) and not args.deferred:
+        ap.error("--sky, --transparents, --debug-lines, --debug-frustum, --bloom, --particles, --taa, --cull-stats and --dof belong to --deferred")
     if args.focus_at and not args.dof:
         ap.error("--focus-at belongs to --dof")
     if args.frames < 1:
@@ -157,6 +162,8 @@ def main():
         world.camera["eye"] = tuple(float(v) for v in args.eye.split(","))
     if args.target:
         world.camera["target"] = tuple(float(v) for v in args.target.split(","))
+    if args.cull_stats:
+        print("meshlets: %d over %d meshes" % (world.add_meshlets(), len(world.metadatas)))
     ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
     ctx.upload_scene(world)
     st = ctx.scene_stats()
@@ -229,6 +236,13 @@ def main():
                 ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth, ibl=1 if args.ibl else 0)
             else:
                 ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
+            if args.cull_stats:
+                # GBufferRenderer::record's culling around this frame's depth (the previous frame's pyramid is kept)
+                ctx.cull_gbuffer(cam)
+                ds = ctx.draw_stats()
+                print("frame %d DrawStats: drawn meshlets %d of %d, rasterized triangles %d of %d, meshes %d, models %d" % (
+                    frame, ds.drawnMeshletCount, ds.totalMeshletCount, ds.rasterizedTriangleCount, ds.totalTriangleCount,
+                    ds.totalMeshCount, ds.totalModelCount))
             if args.sky:
                 ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
             if forward:
