@@ -185,6 +185,26 @@ int prosper_host_hiz_downsampler_record(
     prosper_host_hiz_downsampler *pass, const float *nonLinearDepth, uint32_t onDevice, uint32_t width, uint32_t height,
     uint32_t nextFrame, uint32_t *mipCount, const float **mips, void *stream);
 
+/* render::GBufferRenderer (host/gbuffer_renderer.hpp; reference src/render/GBufferRenderer.hpp): record is
+ * prosper_pt_raster_gbuffer - both culling phases around the rasteriser's own depth, the draws and the resolve - into the
+ * context's own targets, returned as device pointers; `transforms` (optional) are this frame's instance transforms, kept
+ * as the next record's previous ones.  release_preserved forgets the kept pyramid and transforms. */
+typedef struct prosper_host_gbuffer_renderer prosper_host_gbuffer_renderer;
+typedef struct prosper_host_gbuffer_renderer_output
+{
+    const void *albedoRoughness;
+    const void *normalMetalness;
+    const void *velocity;
+    const float *depth;
+} prosper_host_gbuffer_renderer_output;
+int prosper_host_gbuffer_renderer_create(prosper_pt_ctx *ctx, prosper_host_gbuffer_renderer **out);
+void prosper_host_gbuffer_renderer_destroy(prosper_host_gbuffer_renderer *pass);
+int prosper_host_gbuffer_renderer_record(
+    prosper_host_gbuffer_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, uint32_t drawType,
+    const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream, prosper_host_gbuffer_renderer_output *out);
+int prosper_host_gbuffer_renderer_read_draw_stats(prosper_host_gbuffer_renderer *pass, prosper_pt_draw_stats *out, uint32_t wait);
+int prosper_host_gbuffer_renderer_release_preserved(prosper_host_gbuffer_renderer *pass);
+
 /* render::MeshletCuller and render::DrawStats (host/meshlet_culler.hpp; reference src/render/MeshletCuller.hpp,
  * DrawStats.hpp) on a context the scene was uploaded to (borrowed): record_first_phase = Camera::updateBuffer +
  * prosper_pt_cull_meshlets_first_phase (mode 0 Opaque, 1 Transparent; `inHierarchicalDepth` a pyramid slot or

@@ -1271,6 +1271,97 @@ int prosper_pt_get_cull_stage_ms(prosper_pt_ctx *ctx, float ms[3]);
  * updates take effect first; synchronises `stream`.  `count` = the scene's model instances. */
 int prosper_pt_read_instance_scales(prosper_pt_ctx *ctx, float *host, uint32_t count, void *stream);
 
+/* ---- the rasteriser over the draw lists (src/render/GBufferRenderer.cpp recordDraw) ----
+ * A compute rasteriser that consumes the culled lists: it draws the meshlets of a list into the context's VISIBILITY
+ * IMAGE, one 64-bit key per pixel: the reverse-Z depth's bits above ~(ordinal * 128 + meshlet triangle), 0 where nothing
+ * is drawn.  ordinal = (prefix sum of the meshlet counts of the draw instances before this one) + meshletIndex.  The
+ * greatest depth wins (eGreater against the clear value 0); among equal depths the lowest (drawInstanceIndex,
+ * meshletIndex, triangle), whatever order the GPU ran in.  Vulkan's rasteriser cannot run here: the fragment rule
+ * (vertices, snapping to 1/256 pixel, 64-bit edge functions with the top-left rule, back-face culling, the clipper and
+ * its guard band, the depth) is this library's own, written out in DESIGN.md (f18) and restated in
+ * tests/raster_reference.py.  Additive: the ABI version stays 4.
+ *
+ * prosper_pt_raster_meshlets    draws list `which` (GENERATED - the unculled list -, FIRST_PHASE or SECOND_PHASE) of the last
+ *                               culling calls with `camera` (its worldToCamera, cameraToClip and resolution).  With
+ *                               PROSPER_PT_RASTER_CLEAR every key is set to 0 first and the image takes camera->resolution;
+ *                               without it the draw loads what is there (GBufferRenderer.cpp:475 loadOp).
+ * prosper_pt_raster_visibility  GBufferRenderer::record's sequence over the rasteriser's OWN depth: first phase (OPAQUE)
+ *                               against the pyramid the previous call kept, if any and if its source extent is
+ *                               camera->resolution; clear and draw; when the first phase had a pyramid: the image's depth ->
+ *                               pyramid in the other slot -> second phase -> draw without clear; the depth -> pyramid, kept
+ *                               as the next call's previous.  The kept slot is the one prosper_pt_cull_gbuffer keeps; a new
+ *                               scene forgets it.  The image then equals the one drawn from the GENERATED list.
+ * Pending transform, animation and material updates take effect first.  Calls on different streams are ordered on the
+ * device like prosper_pt_debug_lines.  MASK materials: gbuffer.frag:61-63 discards a fragment whose sampleMaterial alpha is 0
+ * (the raw alpha * factor < cutoff, not the any-hit's sampleAlpha) before the depth write; the rasteriser makes that test
+ * before its atomic with the resolve's own surface code - same pixel ray, same uv, same texture LOD state
+ * (prosper_pt_set_texture_lod, camera->currentJitter) - so a draw and its resolve take the same camera and LOD state.
+ * Refused before anything is launched: no scene or no meshlets in it (PROSPER_PT_ERR_NO_SCENE); a list the last culling
+ * calls did not produce (PROSPER_PT_ERR_NO_SCENE); unknown flags or lists; camera->resolution empty, a side above 16384
+ * (prosper_pt_raster_visibility: not above 1, or above 4096), or differing from the image's extent on a draw without
+ * CLEAR; 2^25 meshlets or more (PROSPER_PT_ERR_SCENE).  A refused call leaves everything as it was.  A call that FAILS
+ * later (a HIP or memory error) leaves the lists and the image as its steps so far made them, as a failed culling call
+ * does; prosper_pt_raster_visibility then still keeps the pyramid it had kept before. */
+#define PROSPER_PT_RASTER_CLEAR 1u
+int prosper_pt_raster_meshlets(prosper_pt_ctx *ctx, uint32_t which, uint32_t flags, const prosper_CameraUniforms *camera, void *stream);
+int prosper_pt_raster_visibility(prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, void *stream);
+/* The resolve of the visibility image into the G-buffer targets, and GBufferRenderer::record:146-231 as one chain.
+ *   prosper_pt_raster_resolve  albedoRoughness, normalMetalness, velocity and depth of camera->resolution from the image.
+ *       Nothing is interpolated in screen space: for the pixel's winning triangle the pixel's own ray is formed as
+ *       prosper_pt_trace_gbuffer_velocity forms it (centre minus currentJitter * 0.5), its barycentrics on the world-space
+ *       triangle are taken unclamped, and from that hit the traced kernel's own code runs (material, texture LOD of
+ *       prosper_pt_set_texture_lod, normal encoding, velocity with previous transforms, the debug draw types): where the
+ *       traced G-buffer hits the same triangle the three attribute targets are bit-identical.  The depth is the
+ *       rasteriser's.  MeshletID writes (uintToColor(meshletIndex), 1) and zeros (gbuffer.frag:88-93), PrimitiveID the
+ *       meshlet-local triangle (forward.mesh:144).  Uncovered pixels get the clear values and the sky's velocity.
+ *       `desc` and its refusals are prosper_pt_trace_gbuffer_velocity's: targets caller-owned or context-owned.  With
+ *       context-owned targets the result IS the context's last G-buffer and velocity target for every call that takes
+ *       "NULL: the last traced G-buffer".  Refused also: nothing drawn on this scene or on its geometry as it is now (meshes arrived since), an extent other than
+ *       the image's.
+ *   prosper_pt_raster_gbuffer  prosper_pt_raster_visibility, then the resolve.
+ * A meshlet triangle is mapped to the mesh's index-buffer triangle with the same three vertices (any rotation, the
+ * lowest on duplicates), on the host, by the first draw after a mesh arrived (per mesh: the others' maps are kept); a meshlet triangle without one, or
+ * meshlet sections that leave the buffer, are PROSPER_PT_ERR_SCENE. */
+int prosper_pt_raster_resolve(
+    prosper_pt_ctx *ctx, uint32_t drawType, const prosper_CameraUniforms *camera, const prosper_pt_velocity_gbuffer_desc *desc, void *stream);
+int prosper_pt_raster_gbuffer(
+    prosper_pt_ctx *ctx, uint32_t drawType, const prosper_CameraUniforms *camera, const prosper_pt_velocity_gbuffer_desc *desc, void *stream);
+/* GBufferRenderer::releasePreserved: forgets the pyramid the last sequence kept (prosper_pt_raster_visibility /
+ * prosper_pt_raster_gbuffer / prosper_pt_cull_gbuffer): the next one runs a single phase, as the first after an upload. */
+int prosper_pt_raster_release_preserved(prosper_pt_ctx *ctx);
+/* Synchronises `stream` (behind the last draw, whatever its stream) and decodes the image on the host: per pixel
+ * (drawInstanceIndex, meshletIndex, triangle) as three uint32 - 0xFFFFFFFF each where nothing is drawn - into `ids`, the
+ * key's depth into `depth`; either may be NULL.  `pixels`: room in pixels, at least width * height of the image. */
+int prosper_pt_read_raster_visibility(prosper_pt_ctx *ctx, uint32_t *ids, float *depth, size_t pixels, void *stream);
+/* What the last draws counted.  draw[0]: the draw that cleared; draw[1]: the draw on top of it (valid = 0 without one).
+ * Every count is a property of the list and the view: `fragments` passed coverage and the depth range, counted BEFORE the
+ * depth test.  culledOutside: no pixel centre in the box, all three vertices beyond one clip plane, or clipped to nothing.
+ * queued: triangles handed to the tile pass (large boxes, and every triangle the clipper sees).  queueOverflow stays 0
+ * unless a mesh's meshlets hold more triangles than its index buffer.  The counts travel through pinned memory behind the
+ * draws: the call never blocks and returns PROSPER_PT_NOT_READY (extent set, counts zero) until they have landed. */
+typedef struct prosper_pt_raster_draw_info
+{
+    uint32_t valid;
+    uint32_t triangles;
+    uint32_t culledBackface;
+    uint32_t culledZeroArea;
+    uint32_t culledOutside;
+    uint32_t clipped;
+    uint32_t queued;
+    uint32_t fragments;
+    uint32_t queueOverflow;
+    float meshletsMs; /* device time of the meshlet kernel ... */
+    float largeMs;    /* ... and of the tile pass, between events on the draw's stream */
+    uint32_t reserved;
+} prosper_pt_raster_draw_info;
+typedef struct prosper_pt_raster_info
+{
+    uint32_t width;
+    uint32_t height;
+    prosper_pt_raster_draw_info draw[2];
+} prosper_pt_raster_info;
+int prosper_pt_get_raster_info(prosper_pt_ctx *ctx, prosper_pt_raster_info *out);
+
 /* ---- image-based lighting (src/render/ImageBasedLighting.cpp, res/shader/ibl/) ----
  * ImageBasedLighting::recordGeneration: the three products evalIBL reads, from the scene's sky.
  *

@@ -141,6 +141,12 @@ def lib():
     L.prosper_pt_get_draw_list_device_ptr.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
     L.prosper_pt_get_draw_stats.argtypes = [vp, C.POINTER(S.DrawStats), u32]
     L.prosper_pt_get_cull_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 3)]
+    L.prosper_pt_raster_meshlets.argtypes = [vp, u32, u32, C.POINTER(S.CameraUniforms), vp]
+    L.prosper_pt_raster_visibility.argtypes = [vp, C.POINTER(S.CameraUniforms), vp]
+    L.prosper_pt_raster_resolve.argtypes = [vp, u32, C.POINTER(S.CameraUniforms), C.POINTER(S.VelocityGBufferDesc), vp]
+    L.prosper_pt_raster_gbuffer.argtypes = [vp, u32, C.POINTER(S.CameraUniforms), C.POINTER(S.VelocityGBufferDesc), vp]
+    L.prosper_pt_read_raster_visibility.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.prosper_pt_get_raster_info.argtypes = [vp, C.POINTER(S.RasterInfo)]
     L.prosper_pt_read_instance_scales.argtypes = [vp, vp, u32, vp]
     L.prosper_pt_read_hiz_level.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
     L.prosper_pt_generate_ibl.argtypes = [vp, vp]
@@ -267,6 +273,13 @@ def lib():
     L.prosper_host_skybox_renderer_destroy.argtypes = [vp]
     L.prosper_host_skybox_renderer_destroy.restype = None
     L.prosper_host_skybox_renderer_record.argtypes = [vp, vp, u32, u32, vp, u32, vp]
+    L.prosper_pt_raster_release_preserved.argtypes = [vp]
+    L.prosper_host_gbuffer_renderer_create.argtypes = [vp, C.POINTER(vp)]
+    L.prosper_host_gbuffer_renderer_destroy.argtypes = [vp]
+    L.prosper_host_gbuffer_renderer_destroy.restype = None
+    L.prosper_host_gbuffer_renderer_record.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, C.POINTER(S.GBufferRendererOutput)]
+    L.prosper_host_gbuffer_renderer_read_draw_stats.argtypes = [vp, C.POINTER(S.DrawStats), u32]
+    L.prosper_host_gbuffer_renderer_release_preserved.argtypes = [vp]
     L.prosper_host_meshlet_culler_create.argtypes = [vp, C.POINTER(vp)]
     L.prosper_host_meshlet_culler_destroy.argtypes = [vp]
     L.prosper_host_meshlet_culler_destroy.restype = None
@@ -1089,6 +1102,59 @@ class Context:
         ms = (C.c_float * 3)()
         _check(lib().prosper_pt_get_cull_stage_ms(self._h, C.byref(ms)))
         return tuple(ms)
+
+    # ---- the rasteriser over the draw lists (prosper_pt_raster_*) ----
+
+    def raster_meshlets(self, camera, which=S.DRAW_LIST_GENERATED, clear=True, stream=None):
+        """GBufferRenderer::recordDraw: list `which` of the last culling calls into the visibility image; `clear` sets
+        every key to 0 first and gives the image camera.resolution."""
+        _check(lib().prosper_pt_raster_meshlets(self._h, which, S.RASTER_CLEAR if clear else 0, C.byref(camera), C.c_void_p(stream)))
+
+    def raster_visibility(self, camera, stream=None):
+        """prosper_pt_raster_visibility: both culling phases and their draws over the rasteriser's own depth."""
+        _check(lib().prosper_pt_raster_visibility(self._h, C.byref(camera), C.c_void_p(stream)))
+
+    def _raster_targets(self, entry, camera, draw_type, previous_transforms, targets, velocity_ptr, stream):
+        self._sync_debug()
+        desc = S.VelocityGBufferDesc()
+        if targets is not None:
+            desc.targets = S.GBufferTargets(*targets)
+        desc.velocity = velocity_ptr
+        if previous_transforms is not None:
+            desc.previousTransforms = C.cast(previous_transforms, C.c_void_p)
+            desc.previousTransformCount = len(previous_transforms)
+        _check(entry(self._h, int(draw_type), C.byref(camera), C.byref(desc), C.c_void_p(stream)))
+        gbuffer = (None, None, None) if targets is not None else self.read_gbuffer(stream)
+        return gbuffer + (None if velocity_ptr is not None else self.read_velocity(stream),)
+
+    def raster_resolve(self, camera, draw_type=0, previous_transforms=None, targets=None, velocity_ptr=None, stream=None):
+        """prosper_pt_raster_resolve: the visibility image into the G-buffer targets; arguments and result as
+        trace_gbuffer_velocity's.  With the context's own targets the result is the context's last G-buffer."""
+        return self._raster_targets(lib().prosper_pt_raster_resolve, camera, draw_type, previous_transforms, targets, velocity_ptr, stream)
+
+    def raster_gbuffer(self, camera, draw_type=0, previous_transforms=None, targets=None, velocity_ptr=None, stream=None):
+        """prosper_pt_raster_gbuffer (GBufferRenderer::record): raster_visibility, then raster_resolve."""
+        return self._raster_targets(lib().prosper_pt_raster_gbuffer, camera, draw_type, previous_transforms, targets, velocity_ptr, stream)
+
+    def raster_release_preserved(self):
+        """GBufferRenderer::releasePreserved: the next raster_visibility / raster_gbuffer has no previous pyramid."""
+        _check(lib().prosper_pt_raster_release_preserved(self._h))
+
+    def read_raster_visibility(self, width, height, stream=None):
+        """-> (ids uint32 [h, w, 3] of (drawInstanceIndex, meshletIndex, triangle), 0xFFFFFFFF where nothing is drawn;
+        depth float32 [h, w]) of the visibility image, whose extent is width x height (waits for it)"""
+        ids, depth = np.empty((height, width, 3), np.uint32), np.empty((height, width), np.float32)
+        _check(lib().prosper_pt_read_raster_visibility(self._h, ids.ctypes.data, depth.ctypes.data, width * height, C.c_void_p(stream)))
+        return ids, depth
+
+    def raster_info(self):
+        """S.RasterInfo of the last draws; None while the counts have not landed (never waits)."""
+        out = S.RasterInfo()
+        rc = lib().prosper_pt_get_raster_info(self._h, C.byref(out))
+        if rc == S.NOT_READY:
+            return None
+        _check(rc)
+        return out
 
     def read_instance_scales(self, count, stream=None):
         """The current scene version's per-model-instance uniform scales, float32 [count] (0: non-uniform)."""

@@ -800,7 +800,8 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
     if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
-        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_culling_passes(ctx) || !create_animation_state(ctx))
+        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_culling_passes(ctx) || !create_raster_passes(ctx) ||
+        !create_animation_state(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
@@ -862,6 +863,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_particles_passes(ctx);
     destroy_debug_passes(ctx);
     destroy_culling_passes(ctx);
+    destroy_raster_passes(ctx);
     destroy_animation_state(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
@@ -874,6 +876,7 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     forget_ibl_maps(ctx);
     forget_taa_history(ctx);
     forget_hiz(ctx);
+    forget_raster(ctx);
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());

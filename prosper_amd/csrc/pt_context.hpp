@@ -94,6 +94,13 @@ bool create_culling_passes(prosper_pt_ctx *ctx);
 void destroy_culling_passes(prosper_pt_ctx *ctx);
 // a new scene: both pyramids and the draw lists describe the old one
 void forget_hiz(prosper_pt_ctx *ctx);
+// State of the rasteriser over the draw lists (pt_raster_passes.cpp): the visibility image, the large pass's queue, the
+// counts of the last draws.  Made and freed like the others.
+struct RasterPassState;
+bool create_raster_passes(prosper_pt_ctx *ctx);
+void destroy_raster_passes(prosper_pt_ctx *ctx);
+// a new scene: the visibility image and the ordinal tables describe the old one
+void forget_raster(prosper_pt_ctx *ctx);
 struct AccelState;
 // the scales of the table `transforms` into acc->dScalesV[v] (allocated at first need), enqueued on `stream`
 int enqueue_instance_scales(prosper_pt_ctx *ctx, AccelState *acc, uint32_t v, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t stream);
@@ -358,6 +365,7 @@ struct prosper_pt_ctx
     ppt::ParticlesPassState *particlesPasses = nullptr;
     ppt::DebugPassState *debugPasses = nullptr;
     ppt::CullingPassState *cullingPasses = nullptr; // the depth pyramids, the draw lists, DrawStats
+    ppt::RasterPassState *rasterPasses = nullptr;   // the visibility image drawn from the lists
     ppt::AnimationState *animation = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;

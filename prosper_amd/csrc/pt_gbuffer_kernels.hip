@@ -11,6 +11,7 @@
 
 #include "pt_device.hpp"
 #include "pt_ibl.hpp"
+#include "pt_raster_surface.hpp"
 #include "pt_render_common.hpp"
 
 namespace ppt
@@ -484,6 +485,127 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     const float cz = __builtin_fmaf(m[10], p.z, __builtin_fmaf(m[6], p.y, __builtin_fmaf(m[2], p.x, m[14])));
     const float cw = __builtin_fmaf(m[11], p.z, __builtin_fmaf(m[7], p.y, __builtin_fmaf(m[3], p.x, m[15])));
     nonLinearDepth[i] = cz / cw;
+}
+
+// The resolve of the rasteriser's visibility image (pt_raster.hip) into the G-buffer targets: one lane per
+// pixel.  Nothing is interpolated in screen space: for the winning triangle the lane forms the pixel's own ray exactly as
+// gbuffer_trace_kernel<true, true, kLod> does, takes bu = V / det, bv = W / det from edge_functions on the world-space
+// triangle the traversal tests (flatten_triangles_kernel's: the index buffer's vertices through modelToWorld) - unclamped,
+// no pass / range / box-guard rejection, the traversal's own `* (1 / det)` - and from that Hit runs the traced kernel's
+// code.  The depth is the rasteriser's, from the key.  MeshletID and PrimitiveID are the mesh shader's (gbuffer.frag:88-93,
+// forward.mesh:144): the meshlet's index and the meshlet-local triangle.
+template <bool kLod>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(
+    DeviceScene s, GBufferTraceParams g, RasterResolveTables r, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
+    float *__restrict__ nonLinearDepth, GBufferVelocityParams v, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)g.r.width * g.r.height) return;
+    const uint32_t px = (uint32_t)(i % g.r.width), py = (uint32_t)(i / g.r.width);
+    const Ray ray = raster_pixel_ray(g.r, v.currentJitter, px, py);
+    const unsigned long long key = r.keys[i];
+    bool covered = key != 0ull;
+    uint32_t di = 0, mi = 0, local = 0, prim = 0;
+    if (covered)
+    {
+        const uint32_t low = ~(uint32_t)key, ordinal = low >> 7;
+        local = low & 127u;
+        // the last draw instance whose base is not above the ordinal
+        uint32_t lo = 0, hi = r.drawInstanceCount;
+        while (hi - lo > 1u)
+        {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (r.meshletBase[mid] <= ordinal)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        di = lo;
+        covered = r.drawInstanceCount != 0u && r.meshletBase[di] <= ordinal;
+        if (covered)
+        {
+            mi = ordinal - r.meshletBase[di];
+            const uint32_t mesh = s.drawInstances[di].meshIndex;
+            covered = mesh < r.meshCount && mi < r.meshMeshletBase[mesh + 1u] - r.meshMeshletBase[mesh];
+            if (covered)
+            {
+                const uint32_t gm = r.meshMeshletBase[mesh] + mi;
+                covered = local < r.meshletTriStart[gm + 1u] - r.meshletTriStart[gm];
+                if (covered) prim = r.triMap[r.meshletTriStart[gm] + local];
+            }
+        }
+    }
+    if (!covered)
+    {
+        // the clear values of GBufferRenderer.cpp:487-516; the sky's velocity as the traced entry computes it
+        albedoRoughness[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        nonLinearDepth[i] = 0.0f;
+        v.velocity[i] = ndc_velocity(v, ray.d, ray.d, true);
+        if constexpr (kLod)
+            if (lodp.derivatives) lodp.derivatives[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const prosper_DrawInstance inst = s.drawInstances[di];
+    const Hit hit = raster_hit(s, ray, di, prim);
+    Surface sf;
+    if constexpr (kLod)
+    {
+        UvDerivatives used;
+        sf = raster_pixel_surface<true>(s, g.r, v.currentJitter, lodp.mips, lodp.bias, px, py, ray, hit, &used);
+        if (lodp.derivatives) lodp.derivatives[i] = make_float4(used.dudx, used.dvdx, used.dudy, used.dvdy);
+    }
+    else
+        sf = raster_pixel_surface<false>(s, g.r, v.currentJitter, nullptr, 0.0f, px, py, ray, hit, nullptr);
+    {
+        f3 previous = sf.positionWS;
+        if (v.previousTransforms)
+        {
+            const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + (s.triangleOffsets[hit.drawInstance] + hit.primitive));
+            const float4 q6 = rec[6], q7 = rec[7];
+            const f3 p0 = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
+            const f3 p1 = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
+            const f3 p2 = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
+            const float a = (1.0f - hit.bary.x) - hit.bary.y, b = hit.bary.x, c = hit.bary.y;
+            const f3 model = f3{bary1(p0.x, p1.x, p2.x, a, b, c), bary1(p0.y, p1.y, p2.y, a, b, c), bary1(p0.z, p1.z, p2.z, a, b, c)};
+            previous = mul_point_mat3x4(model, v.previousTransforms[inst.modelInstanceIndex].modelToWorld);
+        }
+        v.velocity[i] = ndc_velocity(v, sf.positionWS, previous, false);
+    }
+    if (g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID || g.drawType == PROSPER_DRAW_TYPE_PRIMITIVE_ID)
+    {
+        const f3 c = uint_to_color(g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID ? mi : local);
+        albedoRoughness[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    else if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT)
+    {
+        const f3 c = debug_color(s, g.drawType, hit, sf);
+        albedoRoughness[i] = make_float4(c.x, c.y, c.z, 1.0f);
+        normalMetallic[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    else
+    {
+        const f3 enc = signed_oct_encode(sf.normalWS);
+        albedoRoughness[i] = make_float4(sf.material.albedo.x, sf.material.albedo.y, sf.material.albedo.z, sf.material.roughness);
+        normalMetallic[i] = make_float4(enc.x, enc.y, sf.material.metallic, enc.z);
+    }
+    nonLinearDepth[i] = u2f((uint32_t)(key >> 32));
+}
+
+void launch_raster_resolve(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, void *albedoRoughness,
+    void *normalMetallic, float *nonLinearDepth, hipStream_t stream, const GBufferLodParams *lod)
+{
+    const size_t pixels = (size_t)g.r.width * g.r.height;
+    if (pixels == 0) return;
+    const dim3 grid((uint32_t)((pixels + 255u) / 256u));
+    if (lod)
+        hipLaunchKernelGGL(raster_resolve_kernel<true>, grid, dim3(256), 0, stream, s, g, r, static_cast<float4 *>(albedoRoughness),
+                           static_cast<float4 *>(normalMetallic), nonLinearDepth, v, *lod);
+    else
+        hipLaunchKernelGGL(raster_resolve_kernel<false>, grid, dim3(256), 0, stream, s, g, r, static_cast<float4 *>(albedoRoughness),
+                           static_cast<float4 *>(normalMetallic), nonLinearDepth, v, GBufferNoLod{});
 }
 
 void launch_gbuffer_trace(

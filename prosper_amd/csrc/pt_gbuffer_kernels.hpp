@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "pt_raster.hpp"
 #include "pt_scene.hpp"
 
 namespace ppt
@@ -67,6 +68,11 @@ struct GBufferVelocityParams
 void launch_gbuffer_trace_velocity(
     const DeviceScene &s, const GBufferTraceParams &g, const GBufferVelocityParams &v, void *albedoRoughness, void *normalMetallic,
     float *nonLinearDepth, int32_t *stackOverflow, hipStream_t stream, const GBufferLodParams *lod = nullptr);
+// The resolve of the rasteriser's visibility image into the same four targets (raster_resolve_kernel):
+// g as for the velocity variant (g.jitter 0; g.opaqueOnly and g.frameIndex are not read), the depth from the keys.
+void launch_raster_resolve(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, void *albedoRoughness,
+    void *normalMetallic, float *nonLinearDepth, hipStream_t stream, const GBufferLodParams *lod = nullptr);
 // The forward transparent pass (forward_transparent_kernel) in place over `hdr`, r.width*r.height float4,
 // against `nonLinearDepth`.  g.jitter: the path tracer's sample; cameraJitter: the velocity entry's ray.  The lists are
 // launch_light_clustering's for the same camera and extent; irradiance / radiance / lut: the IBL maps, all nullptr

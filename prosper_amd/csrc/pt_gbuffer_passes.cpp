@@ -15,6 +15,7 @@
 #include "pt_gbuffer_kernels.hpp"
 #include "pt_kernels.hpp"
 #include "pt_pass_support.hpp"
+#include "pt_raster.hpp"
 
 using namespace ppt;
 
@@ -63,6 +64,12 @@ struct GBufferPassState
     size_t transparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
     uint32_t transparentLayerCount = 0;
 };
+
+void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias)
+{
+    *enabled = ctx->gbufferPasses->lodEnabled;
+    *bias = ctx->gbufferPasses->lodBias;
+}
 
 bool create_gbuffer_passes(prosper_pt_ctx *ctx)
 {
@@ -268,7 +275,7 @@ GBufferTraceParams gbuffer_trace_params(
 int gbuffer_trace(
     prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, bool jitter, const prosper_CameraUniforms *camera,
     uint32_t width, uint32_t height, const prosper_pt_gbuffer_targets &t, hipStream_t s, GBufferVelocityParams *velocity = nullptr,
-    bool opaqueOnly = false)
+    bool opaqueOnly = false, const RasterResolveTables *raster = nullptr)
 {
     const GBufferTraceParams g = gbuffer_trace_params(drawType, frameIndex, jitter, opaqueOnly, camera, width, height);
 
@@ -299,7 +306,11 @@ int gbuffer_trace(
             velocity->currentJitter[k] = camera->currentJitter[k];
             velocity->previousJitter[k] = camera->previousJitter[k];
         }
-        launch_gbuffer_trace_velocity(ctx->scene, g, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
+        // `raster`: the resolve of the rasteriser's visibility image writes the targets instead of a trace
+        if (raster)
+            launch_raster_resolve(ctx->scene, g, *raster, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, s, lod);
+        else
+            launch_gbuffer_trace_velocity(ctx->scene, g, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
     }
     else
         launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
@@ -523,15 +534,13 @@ int prosper_pt_trace_gbuffer(
 
 // ---- the same with a velocity target (what TemporalAntiAliasing reads) ----
 
-int prosper_pt_trace_gbuffer_velocity(
-    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
-    uint32_t width, uint32_t height, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+// What the velocity entry, the rasteriser's resolve and prosper_pt_raster_gbuffer refuse of a descriptor, before anything
+// is enqueued (and, for the last, before the culling phases replace the lists): one copy for the three
+static int check_velocity_desc(
+    const char *what, prosper_pt_ctx *ctx, uint32_t drawType, const prosper_CameraUniforms *camera, const prosper_pt_velocity_gbuffer_desc *desc)
 {
     // the arguments are checked before the context, so that every refusal happens without a GPU
-    const char *what = "prosper_pt_trace_gbuffer_velocity";
-    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_OPAQUE_ONLY) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
     if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
     if (!camera || !desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
     const prosper_pt_gbuffer_targets &given = desc->targets;
     const int targetCount = (given.albedoRoughness ? 1 : 0) + (given.normalMetallic ? 1 : 0) + (given.nonLinearDepth ? 1 : 0);
@@ -549,6 +558,20 @@ int prosper_pt_trace_gbuffer_velocity(
     if (crc != PROSPER_PT_OK) return crc;
     if (desc->previousTransforms && desc->previousTransformCount != ctx->scene.modelInstanceCount)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
+    return PROSPER_PT_OK;
+}
+
+// The velocity entry, and the rasteriser's resolve (`raster`), which takes the same targets under the same rules
+static int velocity_gbuffer(
+    const char *what, bool raster, prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (flags & ~(uint32_t)PROSPER_PT_GBUFFER_OPAQUE_ONLY) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
+    if (const int rc = check_velocity_desc(what, ctx, drawType, camera, desc)) return rc;
+    const prosper_pt_gbuffer_targets &given = desc->targets;
+    const int targetCount = given.albedoRoughness ? 3 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
@@ -578,10 +601,41 @@ int prosper_pt_trace_gbuffer_velocity(
             v.previousTransforms = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
         }
     }
+    RasterResolveTables tables = {};
+    if (rc == PROSPER_PT_OK && raster) rc = raster_resolve_tables(ctx, what, width, height, s, &tables);
     if (rc == PROSPER_PT_OK)
-        rc = gbuffer_trace(ctx, drawType, frameIndex, false, camera, width, height, t, s, &v, (flags & PROSPER_PT_GBUFFER_OPAQUE_ONLY) != 0);
+        rc = gbuffer_trace(ctx, drawType, frameIndex, false, camera, width, height, t, s, &v, (flags & PROSPER_PT_GBUFFER_OPAQUE_ONLY) != 0,
+                           raster ? &tables : nullptr);
+    if (rc == PROSPER_PT_OK && raster) rc = raster_resolve_enqueued(ctx, s);
     if (rc != PROSPER_PT_OK) return rc;
     return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_trace_gbuffer_velocity(
+    prosper_pt_ctx *ctx, uint32_t drawType, uint32_t frameIndex, uint32_t flags, const prosper_CameraUniforms *camera,
+    uint32_t width, uint32_t height, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+{
+    return velocity_gbuffer("prosper_pt_trace_gbuffer_velocity", false, ctx, drawType, frameIndex, flags, camera, width, height, desc, stream);
+}
+
+// ---- the rasteriser's resolve (GBufferRenderer::record's attribute outputs) ----
+
+int prosper_pt_raster_resolve(
+    prosper_pt_ctx *ctx, uint32_t drawType, const prosper_CameraUniforms *camera, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+{
+    if (!camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_raster_resolve: null argument");
+    return velocity_gbuffer("prosper_pt_raster_resolve", true, ctx, drawType, 0u, 0u, camera, camera->resolution[0], camera->resolution[1], desc, stream);
+}
+
+int prosper_pt_raster_gbuffer(
+    prosper_pt_ctx *ctx, uint32_t drawType, const prosper_CameraUniforms *camera, const prosper_pt_velocity_gbuffer_desc *desc, void *stream)
+{
+    const char *what = "prosper_pt_raster_gbuffer";
+    // what the resolve would refuse of its arguments is refused before the culling phases replace the lists
+    if (const int rc = check_velocity_desc(what, ctx, drawType, camera, desc)) return rc;
+    const int rc = prosper_pt_raster_visibility(ctx, camera, stream);
+    if (rc != PROSPER_PT_OK) return rc;
+    return velocity_gbuffer(what, true, ctx, drawType, 0u, 0u, camera, camera->resolution[0], camera->resolution[1], desc, stream);
 }
 
 int prosper_pt_get_velocity_device_ptr(prosper_pt_ctx *ctx, void **out, uint32_t *width, uint32_t *height)

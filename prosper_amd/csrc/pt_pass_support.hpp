@@ -18,6 +18,8 @@ int check_scene(prosper_pt_ctx *ctx, const char *what);
 int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s, hipStream_t reader);
 // The scene and light versions a call read are free again behind its last kernel on `s`.
 int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s);
+// (pt_gbuffer_passes.cpp) prosper_pt_set_texture_lod's state: what the traced G-buffer and the rasteriser's passes sample with
+void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias);
 // the camera terms of the path tracer's camera ray (RenderParams eye .. cameraToWorld)
 void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera);
 // The context's HDR image for a `width` x `height` image, or for the stripes of it `tile` gives this rank (nullptr:

@@ -377,6 +377,54 @@ class HierarchicalDepthDownsampler:
             self._h = None
 
 
+class GBufferRenderer:
+    """render::GBufferRenderer (csrc/host/gbuffer_renderer.hpp) on a Context the scene was uploaded to: record is
+    prosper_pt_raster_gbuffer into the context's own targets and returns S.GBufferRendererOutput (device pointers);
+    read_draw_stats is render::DrawStats; release_preserved forgets the kept pyramid and transforms."""
+
+    def __init__(self, ctx):
+        h = C.c_void_p()
+        rc = lib().prosper_host_gbuffer_renderer_create(ctx._h, C.byref(h))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._h = h
+        self._ctx = ctx
+
+    def record(self, camera, width, height, draw_type="Default", transforms=None, stream=None):
+        """`camera`: a Camera; `transforms`: this frame's ctypes array of S.ModelInstanceTransforms, kept as the next
+        record's previous frame"""
+        out = S.GBufferRendererOutput()
+        rc = lib().prosper_host_gbuffer_renderer_record(
+            self._h, camera._h, width, height, S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
+            None if transforms is None else C.cast(transforms, C.c_void_p), 0 if transforms is None else len(transforms),
+            C.c_void_p(stream), C.byref(out))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out
+
+    def read_draw_stats(self, wait=True):
+        """(S.DrawStats, landed)"""
+        out = S.DrawStats()
+        rc = lib().prosper_host_gbuffer_renderer_read_draw_stats(self._h, C.byref(out), 1 if wait else 0)
+        if rc not in (0, S.NOT_READY):
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        return out, rc == 0
+
+    def release_preserved(self):
+        lib().prosper_host_gbuffer_renderer_release_preserved(self._h)
+
+    def close(self):
+        if self._h:
+            lib().prosper_host_gbuffer_renderer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MeshletCuller:
     """render::MeshletCuller (csrc/host/meshlet_culler.hpp) on a Context the scene was uploaded to: record_first_phase /
     record_second_phase return S.MeshletCullerOutput (device pointers of the lists and argument triples);

@@ -496,6 +496,26 @@ class DrawStats(C.Structure):
                 ("totalMeshletCount", C.c_uint32), ("totalMeshCount", C.c_uint32), ("totalModelCount", C.c_uint32)]
 
 
+RASTER_CLEAR = 1  # PROSPER_PT_RASTER_CLEAR
+
+
+class GBufferRendererOutput(C.Structure):
+    """prosper_host_gbuffer_renderer_output: device pointers in place of the reference's image handles"""
+    _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetalness", C.c_void_p), ("velocity", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class RasterDrawInfo(C.Structure):
+    """prosper_pt_raster_draw_info: what one draw of the rasteriser counted, and the device time of its two kernels"""
+    _fields_ = [("valid", C.c_uint32), ("triangles", C.c_uint32), ("culledBackface", C.c_uint32), ("culledZeroArea", C.c_uint32),
+                ("culledOutside", C.c_uint32), ("clipped", C.c_uint32), ("queued", C.c_uint32), ("fragments", C.c_uint32),
+                ("queueOverflow", C.c_uint32), ("meshletsMs", C.c_float), ("largeMs", C.c_float), ("reserved", C.c_uint32)]
+
+
+class RasterInfo(C.Structure):
+    """prosper_pt_raster_info: the visibility image's extent; draw[0] cleared it, draw[1] drew on top"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("draw", RasterDrawInfo * 2)]
+
+
 class MeshletCullerOutput(C.Structure):
     """prosper_host_meshlet_culler_output: device pointers in place of the reference's buffer handles"""
     _fields_ = [("dataBuffer", C.c_void_p), ("argumentBuffer", C.c_void_p), ("secondPhaseInput", C.c_void_p),

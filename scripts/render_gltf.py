@@ -58,6 +58,10 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  prosper's texture viewer (prosper_pt_texture_debug): the PNG is level LOD of the registry
                                  image NAME through these settings instead of the tone map's output, as Renderer.cpp:621-640
                                  replaces the final composite
+    --deferred --raster          the G-buffer by prosper_pt_raster_gbuffer in place of the traced one: meshlets
+                                 are built for the loaded scene, both culling phases run on the rasteriser's own depth, the
+                                 resolve fills the context's targets; composes with --sky --ibl --bloom --taa --dof
+                                 --texture-lod --cull-stats; --draw-type MeshletID / PrimitiveID show the mesh shader's ids.
     --deferred --cull-stats      prosper's visibility system: meshlets are built for the loaded scene
                                  (World.add_meshlets), prosper_pt_cull_gbuffer runs after the G-buffer of each frame - first
                                  phase against the previous frame's depth pyramid, the pyramid of this frame's depth, second
@@ -135,6 +139,11 @@ def main():
     ap.add_argument("--debug-abs", action="store_true", help="with --debug-view: the absolute value before the range")
     ap.add_argument("--debug-bilinear", action="store_true", help="with --debug-view: the bilinear sampler instead of nearest")
     ap.add_argument("--debug-zoom", action="store_true", help="with --debug-view: the middle of the image four times larger")
+    ap.add_argument("--raster", action="store_true", help="with --deferred: the G-buffer by prosper_pt_raster_gbuffer (meshlets, both culling phases, "
+                    "the compute rasteriser and its resolve) in place of the traced one")
+    ap.add_argument("--draw-type", default="Default", choices=["Default", "PrimitiveID", "MeshletID", "MeshID", "MaterialID", "Position", "ShadingNormal", "TexCoord0", "Albedo",
+                             "Roughness", "Metallic"],
+                    help="with --raster: the G-buffer's draw type (MeshletID and PrimitiveID are the mesh shader's), shaded as that debug view")
     ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
@@ -142,7 +151,7 @@ def main():
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
     if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles or args.debug_lines
-            or args.debug_frustum or args.debug_view or args.list_debug_views or args.cull_stats) and not args.deferred:
+            or args.debug_frustum or args.debug_view or args.list_debug_views or args.cull_stats or args.raster) and not args.deferred:
         ap.error("--sky, --transparents, --debug-lines, --debug-frustum, --bloom, --particles, --taa, --cull-stats and --dof belong to --deferred")
     if args.focus_at and not args.dof:
         ap.error("--focus-at belongs to --dof")
@@ -162,7 +171,11 @@ def main():
         world.camera["eye"] = tuple(float(v) for v in args.eye.split(","))
     if args.target:
         world.camera["target"] = tuple(float(v) for v in args.target.split(","))
-    if args.cull_stats:
+    if args.raster and args.time is not None:
+        ap.error("--raster does not take --time yet (the animated tables' previous frame is the tracer's to keep)")
+    if args.draw_type != "Default" and not args.raster:
+        ap.error("--draw-type belongs to --raster")
+    if args.cull_stats or args.raster:
         print("meshlets: %d over %d meshes" % (world.add_meshlets(), len(world.metadatas)))
     ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
     ctx.upload_scene(world)
@@ -218,7 +231,22 @@ def main():
                 ppc = S.ParticlesPC(0, args.particle_source, 1 if particle_step == 1 else 0, 1.0 / 60.0, particle_step, 0)
                 ctx.particles(ppc, S.PARTICLES_DECAY | S.PARTICLES_INIT | S.PARTICLES_SIMULATE)
         for frame in range(args.frames if args.taa else 1):
-            if args.taa:
+            if args.raster:
+                # GBufferRenderer::record: the culled lists drawn by the compute rasteriser, resolved into the context's
+                # own targets, which every pass below then reads as the last G-buffer (and TAA its velocity)
+                if args.taa:
+                    cam, focal = hcam.update_buffer()
+                # (this frame's table is the next frame's previous one; the first frame sees unmoved instances)
+                ctx.raster_gbuffer(cam, draw_type=S.DrawType[args.draw_type], previous_transforms=transforms if args.taa and frame else None)
+                g, _, _ = ctx.gbuffer_device_ptrs()
+                ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth,
+                                            draw_type=S.DrawType[args.draw_type], ibl=1 if args.ibl else 0)
+                if args.cull_stats:
+                    ds = ctx.draw_stats()
+                    print("frame %d DrawStats: drawn meshlets %d of %d, rasterized triangles %d of %d, meshes %d, models %d" % (
+                        frame, ds.drawnMeshletCount, ds.totalMeshletCount, ds.rasterizedTriangleCount, ds.totalTriangleCount,
+                        ds.totalMeshCount, ds.totalModelCount))
+            elif args.taa:
                 if args.time is not None and frame:
                     # the scene moves on; this frame's table is the next frame's previous one (the tracer keeps it)
                     ctx.animate(args.time + frame * args.time_step)
@@ -236,7 +264,7 @@ def main():
                 ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth, ibl=1 if args.ibl else 0)
             else:
                 ctx.deferred_shading_traced(cam, w, h, ibl=1 if args.ibl else 0)
-            if args.cull_stats:
+            if args.cull_stats and not args.raster:
                 # GBufferRenderer::record's culling around this frame's depth (the previous frame's pyramid is kept)
                 ctx.cull_gbuffer(cam)
                 ds = ctx.draw_stats()
