@@ -231,21 +231,34 @@ int prosper_host_meshlet_culler_record_second_phase(
     uint32_t inHierarchicalDepth, prosper_host_meshlet_culler_output *out, void *stream);
 int prosper_host_meshlet_culler_read_draw_stats(prosper_host_meshlet_culler *pass, prosper_pt_draw_stats *out, uint32_t wait);
 
-/* render::ForwardRenderer (host/forward_renderer.hpp; reference src/render/ForwardRenderer.hpp), its transparent pass
- * only, on a context the scene was uploaded to (borrowed): record_transparent = Camera::updateBuffer +
- * prosper_pt_forward_transparent over the context's HDR image.  `nonLinearDepth` NULL: the last traced G-buffer's depth;
+/* render::ForwardRenderer (host/forward_renderer.hpp; reference src/render/ForwardRenderer.hpp) on a context the scene was
+ * uploaded to (borrowed).  record_opaque = Camera::updateBuffer + prosper_pt_raster_forward - both culling phases around
+ * the rasteriser's own depth, the draws and the forward shade - into the context's HDR image and its own
+ * depth and velocity, returned as device pointers; `transforms` (optional) are this frame's instance transforms, kept as
+ * the next record's previous ones.  release_preserved forgets the kept pyramid and transforms.  record_transparent =
+ * Camera::updateBuffer + prosper_pt_forward_transparent over the context's HDR image.  `nonLinearDepth` NULL: the last traced G-buffer's depth;
  * `rayFlags`, `frameIndex`: the ray the G-buffer was traced with (0, PROSPER_PT_TRANSPARENT_JITTER or
  * PROSPER_PT_TRANSPARENT_CAMERA_JITTER).  prosper itself draws transparents with ibl = 0.  *outPushConstants (may be
  * NULL) receives the ForwardPC it pushed. */
 typedef struct prosper_host_forward_renderer prosper_host_forward_renderer;
 int prosper_host_forward_renderer_create(prosper_pt_ctx *ctx, prosper_host_forward_renderer **out);
 void prosper_host_forward_renderer_destroy(prosper_host_forward_renderer *pass);
-/* ForwardRenderer::setTextureLod / setLodBias: later records sample every layer's material through the mip chains. */
+/* ForwardRenderer::setTextureLod / setLodBias: later records of both passes sample every material through the mip chains. */
 int prosper_host_forward_renderer_set_texture_lod(prosper_host_forward_renderer *pass, int enabled, float lodBias);
 int prosper_host_forward_renderer_record_transparent(
     prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const float *nonLinearDepth, uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType,
     void *stream, prosper_pt_forward_pc *outPushConstants);
+typedef struct prosper_host_forward_renderer_output
+{
+    const void *illumination; /* the context's HDR image */
+    const void *velocity;
+    const float *depth;
+} prosper_host_forward_renderer_output;
+int prosper_host_forward_renderer_record_opaque(
+    prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, int applyIbl, uint32_t drawType,
+    const prosper_ModelInstanceTransforms *transforms, uint32_t transformCount, void *stream, prosper_host_forward_renderer_output *out);
+int prosper_host_forward_renderer_release_preserved(prosper_host_forward_renderer *pass);
 
 /* render::particles::Particles (host/particles.hpp; reference src/render/particles/Particles.hpp) on a context
  * (borrowed): record = Camera::updateBuffer + prosper_pt_particles with every stage, over the context's HDR image and

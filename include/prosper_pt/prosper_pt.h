@@ -1329,6 +1329,71 @@ int prosper_pt_raster_gbuffer(
 /* GBufferRenderer::releasePreserved: forgets the pyramid the last sequence kept (prosper_pt_raster_visibility /
  * prosper_pt_raster_gbuffer / prosper_pt_cull_gbuffer): the next one runs a single phase, as the first after an upload. */
 int prosper_pt_raster_release_preserved(prosper_pt_ctx *ctx);
+/* ---- forward opaque pass (src/render/ForwardRenderer.cpp recordOpaque, forward.frag) ----
+ * The third way to the opaque image (Renderer.cpp:404-483, m_renderDeferred == false): every pixel's winning triangle of
+ * the visibility image is shaded directly over the light clusters, without a G-buffer in between.  Additive: the ABI
+ * version stays 4.
+ *   prosper_pt_raster_forward_shade  over the image as drawn.  A covered pixel's surface is the resolve's (the pixel's own
+ *       ray, unclamped barycentrics on the world-space triangle, the traced kernel's material code, the texture LOD of
+ *       prosper_pt_set_texture_lod) with forward.frag's view vector normalize(eye - positionWS); its colour is the sun, then
+ *       the point and spot lights of clusterIndex(pixel, zCam) with zCam = (worldToCamera * position).z, unshadowed, then
+ *       with pc->ibl = 1 evalIBL - what prosper_pt_forward_transparent sums for a layer; its alpha is the material's where
+ *       that is above 0, else 1.  Other draw types than Default write (colour, 1) with the colour the resolve writes to
+ *       albedoRoughness: MeshletID uintToColor(meshletIndex), PrimitiveID the meshlet-local triangle, the rest the debug
+ *       colour.  Velocity (whatever the draw type) and depth are the resolve's, bit for bit.  An uncovered pixel gets
+ *       (0, 0, 0, 0), depth 0 and the sky's velocity.  pc->previousTransformValid is not read: desc->previousTransforms
+ *       decides.
+ *   prosper_pt_raster_forward  prosper_pt_raster_visibility, then the shade: ForwardRenderer::recordOpaque:134-217.  The
+ *       kept pyramid is the one prosper_pt_raster_gbuffer and prosper_pt_cull_gbuffer keep, and
+ *       prosper_pt_raster_release_preserved is ForwardRenderer::releasePreserved as well.
+ * The illumination is the context's HDR image at camera->resolution, overwritten and sized as prosper_pt_deferred_shading
+ * does.  The lights are clustered first on `stream`, unless the context's last clustering serves (same camera terms and
+ * extent, no light update since).  Pending scene updates are flushed once; calls on different streams are ordered on the
+ * device as prosper_pt_raster_gbuffer orders them.
+ * The depth and the velocity become the context's last depth and last velocity target for every call that takes "NULL:
+ * the last traced G-buffer's" of either (prosper_pt_skybox_fill, prosper_pt_forward_transparent, prosper_pt_debug_lines,
+ * prosper_pt_hiz_downsample, prosper_pt_taa_resolve, prosper_pt_depth_of_field, prosper_pt_particles,
+ * prosper_pt_get_velocity_device_ptr).  A forward frame has no albedo or normal target: until the next G-buffer,
+ * prosper_pt_get_gbuffer_device_ptrs and prosper_pt_read_gbuffer answer "no G-buffer has been traced yet", and the
+ * registry lists albedoRoughness and normalMetalness as not yet run, depth as valid.
+ * Refused before anything is launched, the HDR image, the depth and the velocity left as they were: what
+ * prosper_pt_raster_resolve refuses (nothing drawn, geometry changed since, another extent, an unmatched triangle); drawType
+ * out of range, ibl not 0 or 1, ibl = 1 before prosper_pt_generate_ibl (PROSPER_PT_ERR_UNSUPPORTED), a camera without
+ * 0 < near_ < far_; a depth target that is not 4-byte or a velocity target that is not 8-byte aligned; a
+ * previousTransformCount that is not the scene's modelInstanceCount, or one without previousTransforms. */
+typedef struct prosper_pt_forward_opaque_desc
+{
+    float *nonLinearDepth; /* width*height float on the device; NULL: context-owned */
+    void *velocity;        /* width*height float2 on the device (8-byte aligned); NULL: context-owned */
+    const prosper_ModelInstanceTransforms *previousTransforms; /* as prosper_pt_velocity_gbuffer_desc */
+    uint32_t previousTransformCount;
+} prosper_pt_forward_opaque_desc;
+int prosper_pt_raster_forward_shade(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream);
+int prosper_pt_raster_forward(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream);
+/* Debug mode, for tests: every later forward shade also writes one prosper_pt_transparent_layer per pixel into a
+ * context-owned buffer - drawInstance, the geometry primitive, positionWS, the key's nonLinearDepth, albedo, roughness, the
+ * shading normal, metallic, alpha; drawInstance 0xFFFFFFFF (and zeros) where nothing is drawn.  The images are the same
+ * bit for bit.  prosper_pt_read_forward_surfaces synchronises `stream` and copies the `pixels` records of the last call
+ * out; NO_SCENE if that call did not run in debug mode. */
+int prosper_pt_set_forward_debug_surfaces(prosper_pt_ctx *ctx, int enabled);
+int prosper_pt_read_forward_surfaces(prosper_pt_ctx *ctx, prosper_pt_transparent_layer *out, size_t pixels, void *stream);
+typedef struct prosper_pt_forward_opaque_info
+{
+    uint32_t shadedPixels; /* covered pixels */
+    uint32_t reclustered;  /* 1: the last call clustered the lights itself */
+    float ms;              /* device time of the last shade, its clustering included */
+    float shadeMs;         /* of the shade kernel alone */
+} prosper_pt_forward_opaque_info;
+/* Of the last forward shade; never blocks: PROSPER_PT_NOT_READY (only `reclustered` filled in) while it is still running,
+ * NO_SCENE before the first. */
+int prosper_pt_get_forward_opaque_info(prosper_pt_ctx *ctx, prosper_pt_forward_opaque_info *out);
+/* The depth target of the last forward frame, while it is the context's last depth (NO_SCENE before a forward frame and
+ * after the next G-buffer): its device pointer and extent, and a copy to the host that synchronises `stream`; `pixels`
+ * must be its width * height.  The velocity is prosper_pt_get_velocity_device_ptr's and prosper_pt_read_velocity's. */
+int prosper_pt_get_forward_depth_device_ptr(prosper_pt_ctx *ctx, float **out, uint32_t *width, uint32_t *height);
+int prosper_pt_read_forward_depth(prosper_pt_ctx *ctx, float *host_depth, size_t pixels, void *stream);
 /* Synchronises `stream` (behind the last draw, whatever its stream) and decodes the image on the host: per pixel
  * (drawInstanceIndex, meshletIndex, triangle) as three uint32 - 0xFFFFFFFF each where nothing is drawn - into `ids`, the
  * key's depth into `depth`; either may be NULL.  `pixels`: room in pixels, at least width * height of the image. */

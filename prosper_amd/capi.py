@@ -146,6 +146,13 @@ def lib():
     L.prosper_pt_raster_resolve.argtypes = [vp, u32, C.POINTER(S.CameraUniforms), C.POINTER(S.VelocityGBufferDesc), vp]
     L.prosper_pt_raster_gbuffer.argtypes = [vp, u32, C.POINTER(S.CameraUniforms), C.POINTER(S.VelocityGBufferDesc), vp]
     L.prosper_pt_read_raster_visibility.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.prosper_pt_raster_forward_shade.argtypes = [vp, C.POINTER(S.ForwardPC), C.POINTER(S.CameraUniforms), C.POINTER(S.ForwardOpaqueDesc), vp]
+    L.prosper_pt_raster_forward.argtypes = [vp, C.POINTER(S.ForwardPC), C.POINTER(S.CameraUniforms), C.POINTER(S.ForwardOpaqueDesc), vp]
+    L.prosper_pt_set_forward_debug_surfaces.argtypes = [vp, C.c_int]
+    L.prosper_pt_read_forward_surfaces.argtypes = [vp, vp, C.c_size_t, vp]
+    L.prosper_pt_get_forward_opaque_info.argtypes = [vp, C.POINTER(S.ForwardOpaqueInfo)]
+    L.prosper_pt_get_forward_depth_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_read_forward_depth.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_raster_info.argtypes = [vp, C.POINTER(S.RasterInfo)]
     L.prosper_pt_read_instance_scales.argtypes = [vp, vp, u32, vp]
     L.prosper_pt_read_hiz_level.argtypes = [vp, u32, u32, vp, C.c_size_t, vp]
@@ -294,6 +301,8 @@ def lib():
     L.prosper_host_forward_renderer_destroy.argtypes = [vp]
     L.prosper_host_forward_renderer_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
     L.prosper_host_forward_renderer_destroy.restype = None
+    L.prosper_host_forward_renderer_record_opaque.argtypes = [vp, vp, u32, u32, C.c_int, u32, vp, u32, vp, C.POINTER(S.ForwardRendererOutput)]
+    L.prosper_host_forward_renderer_release_preserved.argtypes = [vp]
     L.prosper_host_forward_renderer_record_transparent.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, C.c_int, u32, vp,
                                                                    C.POINTER(S.ForwardPC)]
     L.prosper_host_particles_create.argtypes = [vp, C.POINTER(vp)]
@@ -1139,6 +1148,65 @@ class Context:
     def raster_release_preserved(self):
         """GBufferRenderer::releasePreserved: the next raster_visibility / raster_gbuffer has no previous pyramid."""
         _check(lib().prosper_pt_raster_release_preserved(self._h))
+
+    # ---- the forward opaque pass over the visibility image (prosper_pt_raster_forward*; DESIGN.md f19) ----
+
+    def _forward_opaque(self, entry, camera, draw_type, ibl, previous_transforms, depth_ptr, velocity_ptr, stream):
+        self._sync_debug()
+        pc = S.ForwardPC(int(draw_type), int(ibl), 0)
+        desc = S.ForwardOpaqueDesc()
+        desc.nonLinearDepth = depth_ptr
+        desc.velocity = velocity_ptr
+        if previous_transforms is not None:
+            desc.previousTransforms = C.cast(previous_transforms, C.c_void_p)
+            desc.previousTransformCount = len(previous_transforms)
+        _check(entry(self._h, C.byref(pc), C.byref(camera), C.byref(desc), C.c_void_p(stream)))
+        self._forward_extent = (int(camera.resolution[0]), int(camera.resolution[1]))
+
+    def raster_forward_shade(self, camera, draw_type=0, ibl=0, previous_transforms=None, depth_ptr=None, velocity_ptr=None, stream=None):
+        """prosper_pt_raster_forward_shade: the visibility image as drawn, shaded forward over the light clusters into the
+        HDR image (read_hdr), with the depth (read_forward_depth) and the velocity (read_velocity) of the resolve.
+        `previous_transforms`: a ctypes array of S.ModelInstanceTransforms, one per model instance; `depth_ptr`,
+        `velocity_ptr`: device targets of the caller's (None: context-owned, the context's last depth and velocity)."""
+        self._forward_opaque(lib().prosper_pt_raster_forward_shade, camera, draw_type, ibl, previous_transforms, depth_ptr, velocity_ptr, stream)
+
+    def raster_forward(self, camera, draw_type=0, ibl=0, previous_transforms=None, depth_ptr=None, velocity_ptr=None, stream=None):
+        """prosper_pt_raster_forward (ForwardRenderer::recordOpaque): raster_visibility, then raster_forward_shade."""
+        self._forward_opaque(lib().prosper_pt_raster_forward, camera, draw_type, ibl, previous_transforms, depth_ptr, velocity_ptr, stream)
+
+    def read_forward_depth(self, stream=None):
+        """The context-owned depth of the last forward frame as a host array [h, w] float32; synchronises `stream`."""
+        _, w, h = self.forward_depth_device_ptr()
+        out = np.empty((h, w), np.float32)
+        _check(lib().prosper_pt_read_forward_depth(self._h, out.ctypes.data, w * h, C.c_void_p(stream)))
+        return out
+
+    def forward_depth_device_ptr(self):
+        """The depth of the last forward frame: (device pointer, width, height)."""
+        p, w, h = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().prosper_pt_get_forward_depth_device_ptr(self._h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def set_forward_debug_surfaces(self, enabled):
+        """Debug mode of the forward opaque pass: later shades also record every pixel's surface."""
+        _check(lib().prosper_pt_set_forward_debug_surfaces(self._h, 1 if enabled else 0))
+
+    def read_forward_surfaces(self, stream=None):
+        """What the last forward shade in debug mode recorded: [h, w] of the structured dtype of S.TransparentLayer
+        (drawInstance 0xFFFFFFFF where nothing is drawn)."""
+        w, h = getattr(self, "_forward_extent", (0, 0))  # (before the first shade the library refuses)
+        out = np.empty((h, w), np.dtype(S.TransparentLayer))
+        _check(lib().prosper_pt_read_forward_surfaces(self._h, out.ctypes.data, w * h, C.c_void_p(stream)))
+        return out
+
+    def forward_opaque_info(self):
+        """S.ForwardOpaqueInfo of the last forward shade; None while it is still running (never waits)."""
+        out = S.ForwardOpaqueInfo()
+        rc = lib().prosper_pt_get_forward_opaque_info(self._h, C.byref(out))
+        if rc == S.NOT_READY:
+            return None
+        _check(rc)
+        return out
 
     def read_raster_visibility(self, width, height, stream=None):
         """-> (ids uint32 [h, w, 3] of (drawInstanceIndex, meshletIndex, triangle), 0xFFFFFFFF where nothing is drawn;

@@ -320,13 +320,13 @@ int prosper_pt_hiz_downsample(
     const float *depth = nonLinearDepth;
     if (!depth)
     {
-        prosper_pt_restir_inputs g = {};
+        const float *last = nullptr;
         uint32_t gw = 0, gh = 0;
-        const int grc = prosper_pt_get_gbuffer_device_ptrs(ctx, &g, &gw, &gh);
+        const int grc = gbuffer_last_depth(ctx, &last, &gw, &gh);
         if (grc != PROSPER_PT_OK) return grc;
         if (gw != width || gh != height)
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_hiz_downsample: the last traced G-buffer has another extent");
-        depth = g.nonLinearDepth;
+        depth = last;
     }
     CullingPassState::HizSlot &st = ctx->cullingPasses->hiz[slot];
     st.valid = false;

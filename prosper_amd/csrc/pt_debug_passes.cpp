@@ -250,9 +250,9 @@ int prosper_pt_debug_lines(
     if (width > kMaxExtent || height > kMaxExtent)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_lines: an extent above 32768 is not supported");
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_lines: null argument");
-    prosper_pt_restir_inputs g = {};
+    const float *lastDepth = nullptr;
     uint32_t gw = 0, gh = 0;
-    int rc = prosper_pt_get_gbuffer_device_ptrs(ctx, &g, &gw, &gh);
+    int rc = gbuffer_last_depth(ctx, &lastDepth, &gw, &gh);
     if (rc != PROSPER_PT_OK) return rc;
     if (gw != width || gh != height)
         return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_debug_lines: the last traced G-buffer has another extent");
@@ -305,7 +305,7 @@ int prosper_pt_debug_lines(
     p.width = width;
     p.height = height;
     p.hdr = ctx->hdr;
-    p.nonLinearDepth = const_cast<float *>(g.nonLinearDepth);
+    p.nonLinearDepth = const_cast<float *>(lastDepth);
     p.keys = st.keys.as<unsigned long long>();
     p.stats = st.stats.as<DebugLineStats>();
     PPT_HIP(hipEventRecord(st.timing.events[0], s));

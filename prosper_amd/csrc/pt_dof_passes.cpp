@@ -100,13 +100,13 @@ int device_depth(
 {
     if (!depth)
     {
-        prosper_pt_restir_inputs g = {};
+        const float *last = nullptr;
         uint32_t gw = 0, gh = 0;
-        const int rc = prosper_pt_get_gbuffer_device_ptrs(ctx, &g, &gw, &gh);
+        const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
         if (rc != PROSPER_PT_OK) return rc;
         if (gw != width || gh != height)
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the last traced G-buffer has another extent");
-        *out = g.nonLinearDepth;
+        *out = last;
         return PROSPER_PT_OK;
     }
     if (onDevice)

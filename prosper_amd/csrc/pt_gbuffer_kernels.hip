@@ -487,25 +487,13 @@ __global__ __launch_bounds__(256) void gbuffer_trace_kernel(
     nonLinearDepth[i] = cz / cw;
 }
 
-// The resolve of the rasteriser's visibility image (pt_raster.hip; DESIGN.md f18) into the G-buffer targets: one lane per
-// pixel.  Nothing is interpolated in screen space: for the winning triangle the lane forms the pixel's own ray exactly as
-// gbuffer_trace_kernel<true, true, kLod> does, takes bu = V / det, bv = W / det from edge_functions on the world-space
-// triangle the traversal tests (flatten_triangles_kernel's: the index buffer's vertices through modelToWorld) - unclamped,
-// no pass / range / box-guard rejection, the traversal's own `* (1 / det)` - and from that Hit runs the traced kernel's
-// code.  The depth is the rasteriser's, from the key.  MeshletID and PrimitiveID are the mesh shader's (gbuffer.frag:88-93,
-// forward.mesh:144): the meshlet's index and the meshlet-local triangle.
-template <bool kLod>
-__global__ __launch_bounds__(256) void raster_resolve_kernel(
-    DeviceScene s, GBufferTraceParams g, RasterResolveTables r, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
-    float *__restrict__ nonLinearDepth, GBufferVelocityParams v, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
+// The winning triangle of a visibility key (pt_raster.hpp RasterParams::keys): the draw instance whose meshlet range holds
+// the ordinal, the meshlet in it, the meshlet-local triangle, and the geometry triangle through the triangle map.  False
+// for the clear value and for a key that names nothing the tables hold.  One copy for the resolve and the forward pass.
+PPT_D bool raster_decode_key(
+    const DeviceScene &s, const RasterResolveTables &r, unsigned long long key, uint32_t &di, uint32_t &mi, uint32_t &local, uint32_t &prim)
 {
-    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= (size_t)g.r.width * g.r.height) return;
-    const uint32_t px = (uint32_t)(i % g.r.width), py = (uint32_t)(i / g.r.width);
-    const Ray ray = raster_pixel_ray(g.r, v.currentJitter, px, py);
-    const unsigned long long key = r.keys[i];
     bool covered = key != 0ull;
-    uint32_t di = 0, mi = 0, local = 0, prim = 0;
     if (covered)
     {
         const uint32_t low = ~(uint32_t)key, ordinal = low >> 7;
@@ -535,6 +523,47 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(
             }
         }
     }
+    return covered;
+}
+
+// The velocity of a covered pixel of the visibility image, as gbuffer_trace_kernel<true> takes it: the interpolated
+// model-space vertex evaluate_surface transforms, through the instance's previous transform where there is one
+PPT_D float2 raster_surface_velocity(const DeviceScene &s, const GBufferVelocityParams &v, uint32_t modelInstanceIndex, const Hit &hit, const Surface &sf)
+{
+    f3 previous = sf.positionWS;
+    if (v.previousTransforms)
+    {
+        const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + (s.triangleOffsets[hit.drawInstance] + hit.primitive));
+        const float4 q6 = rec[6], q7 = rec[7];
+        const f3 p0 = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
+        const f3 p1 = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
+        const f3 p2 = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
+        const float a = (1.0f - hit.bary.x) - hit.bary.y, b = hit.bary.x, c = hit.bary.y;
+        const f3 model = f3{bary1(p0.x, p1.x, p2.x, a, b, c), bary1(p0.y, p1.y, p2.y, a, b, c), bary1(p0.z, p1.z, p2.z, a, b, c)};
+        previous = mul_point_mat3x4(model, v.previousTransforms[modelInstanceIndex].modelToWorld);
+    }
+    return ndc_velocity(v, sf.positionWS, previous, false);
+}
+
+// The resolve of the rasteriser's visibility image (pt_raster.hip; DESIGN.md f18) into the G-buffer targets: one lane per
+// pixel.  Nothing is interpolated in screen space: for the winning triangle the lane forms the pixel's own ray exactly as
+// gbuffer_trace_kernel<true, true, kLod> does, takes bu = V / det, bv = W / det from edge_functions on the world-space
+// triangle the traversal tests (flatten_triangles_kernel's: the index buffer's vertices through modelToWorld) - unclamped,
+// no pass / range / box-guard rejection, the traversal's own `* (1 / det)` - and from that Hit runs the traced kernel's
+// code.  The depth is the rasteriser's, from the key.  MeshletID and PrimitiveID are the mesh shader's (gbuffer.frag:88-93,
+// forward.mesh:144): the meshlet's index and the meshlet-local triangle.
+template <bool kLod>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(
+    DeviceScene s, GBufferTraceParams g, RasterResolveTables r, float4 *__restrict__ albedoRoughness, float4 *__restrict__ normalMetallic,
+    float *__restrict__ nonLinearDepth, GBufferVelocityParams v, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)g.r.width * g.r.height) return;
+    const uint32_t px = (uint32_t)(i % g.r.width), py = (uint32_t)(i / g.r.width);
+    const Ray ray = raster_pixel_ray(g.r, v.currentJitter, px, py);
+    const unsigned long long key = r.keys[i];
+    uint32_t di = 0, mi = 0, local = 0, prim = 0;
+    const bool covered = raster_decode_key(s, r, key, di, mi, local, prim);
     if (!covered)
     {
         // the clear values of GBufferRenderer.cpp:487-516; the sky's velocity as the traced entry computes it
@@ -557,21 +586,7 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(
     }
     else
         sf = raster_pixel_surface<false>(s, g.r, v.currentJitter, nullptr, 0.0f, px, py, ray, hit, nullptr);
-    {
-        f3 previous = sf.positionWS;
-        if (v.previousTransforms)
-        {
-            const float4 *rec = reinterpret_cast<const float4 *>(s.shadeTriangles + (s.triangleOffsets[hit.drawInstance] + hit.primitive));
-            const float4 q6 = rec[6], q7 = rec[7];
-            const f3 p0 = unpack_half3(__builtin_bit_cast(uint32_t, q6.x), __builtin_bit_cast(uint32_t, q6.y));
-            const f3 p1 = unpack_half3(__builtin_bit_cast(uint32_t, q6.z), __builtin_bit_cast(uint32_t, q6.w));
-            const f3 p2 = unpack_half3(__builtin_bit_cast(uint32_t, q7.x), __builtin_bit_cast(uint32_t, q7.y));
-            const float a = (1.0f - hit.bary.x) - hit.bary.y, b = hit.bary.x, c = hit.bary.y;
-            const f3 model = f3{bary1(p0.x, p1.x, p2.x, a, b, c), bary1(p0.y, p1.y, p2.y, a, b, c), bary1(p0.z, p1.z, p2.z, a, b, c)};
-            previous = mul_point_mat3x4(model, v.previousTransforms[inst.modelInstanceIndex].modelToWorld);
-        }
-        v.velocity[i] = ndc_velocity(v, sf.positionWS, previous, false);
-    }
+    v.velocity[i] = raster_surface_velocity(s, v, inst.modelInstanceIndex, hit, sf);
     if (g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID || g.drawType == PROSPER_DRAW_TYPE_PRIMITIVE_ID)
     {
         const f3 c = uint_to_color(g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID ? mi : local);
@@ -1141,6 +1156,130 @@ void launch_forward_transparent(
     hipLaunchKernelGGL(
         kernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
         static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, maps, GBufferNoLod{});
+}
+
+// ------------------------------------------------------------------------------------------
+// Forward opaque pass (src/render/ForwardRenderer.cpp recordOpaque, forward.frag): the pixel's winning
+// triangle of the visibility image shaded directly over the light clusters - raster_resolve_kernel's surface, which is
+// never stored, then forward_transparent_kernel's shading of it.  One lane per pixel on the G-buffer passes' mapping
+// (restir_pixel: a wave is an aligned 8 x 8 block, which never straddles an edge of the 32 x 32 clusters: its lanes' lists
+// differ only where the block spans two depth slices).  It stands here, not beside the resolve, because it needs
+// shade_clustered.
+//   covered    illumination (colour, material alpha or 1), velocity and depth as the resolve writes them; the debug draw
+//              types write what the resolve writes to albedoRoughness (forward.frag:99-116)
+//   uncovered  the clear values (0, 0, 0, 0) and 0 (ForwardRenderer.cpp:574-604), the sky's velocity
+// kSurfaces (prosper_pt_set_forward_debug_surfaces): the pixel's surface is also stored, one record per pixel.
+// ------------------------------------------------------------------------------------------
+template <bool IBL, bool kLod, bool kSurfaces>
+__global__ __launch_bounds__(256) void forward_opaque_kernel(
+    DeviceScene s, GBufferTraceParams g, RasterResolveTables r, GBufferVelocityParams v, ClusterGrid grid, const uint2 *__restrict__ pointers,
+    const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, float *__restrict__ nonLinearDepth, uint32_t *__restrict__ shadedPixels,
+    prosper_pt_transparent_layer *__restrict__ surfaces, IblMaps ibl, std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
+{
+    uint32_t px, py;
+    if (!restir_pixel(g.r.width, g.r.height, px, py)) return;
+    bool covered = false;
+    if (px < g.r.width && py < g.r.height)
+    {
+        const size_t i = (size_t)py * g.r.width + px;
+        const Ray ray = raster_pixel_ray(g.r, v.currentJitter, px, py);
+        const unsigned long long key = r.keys[i];
+        uint32_t di = 0, mi = 0, local = 0, prim = 0;
+        covered = raster_decode_key(s, r, key, di, mi, local, prim);
+        if (!covered)
+        {
+            hdr[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            nonLinearDepth[i] = 0.0f;
+            v.velocity[i] = ndc_velocity(v, ray.d, ray.d, true);
+            if constexpr (kSurfaces)
+            {
+                prosper_pt_transparent_layer L = {};
+                L.drawInstance = 0xFFFFFFFFu;
+                surfaces[i] = L;
+            }
+        }
+        else
+        {
+            const prosper_DrawInstance inst = s.drawInstances[di];
+            const Hit hit = raster_hit(s, ray, di, prim);
+            Surface sf;
+            if constexpr (kLod)
+                sf = raster_pixel_surface<true>(s, g.r, v.currentJitter, lodp.mips, lodp.bias, px, py, ray, hit, nullptr);
+            else
+                sf = raster_pixel_surface<false>(s, g.r, v.currentJitter, nullptr, 0.0f, px, py, ray, hit, nullptr);
+            // forward.frag:94-97: the velocity is written whatever the draw type
+            v.velocity[i] = raster_surface_velocity(s, v, inst.modelInstanceIndex, hit, sf);
+            const float depth = u2f((uint32_t)(key >> 32));
+            nonLinearDepth[i] = depth;
+            const f3 q = sf.positionWS;
+            if constexpr (kSurfaces)
+            {
+                prosper_pt_transparent_layer L;
+                L.drawInstance = hit.drawInstance;
+                L.primitive = hit.primitive;
+                L.positionWS[0] = q.x; L.positionWS[1] = q.y; L.positionWS[2] = q.z;
+                L.nonLinearDepth = depth;
+                L.albedo[0] = sf.material.albedo.x; L.albedo[1] = sf.material.albedo.y; L.albedo[2] = sf.material.albedo.z;
+                L.roughness = sf.material.roughness;
+                L.normal[0] = sf.normalWS.x; L.normal[1] = sf.normalWS.y; L.normal[2] = sf.normalWS.z;
+                L.metallic = sf.material.metallic;
+                L.alpha = sf.material.alpha;
+                L.reserved = 0u;
+                surfaces[i] = L;
+            }
+            if (g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID || g.drawType == PROSPER_DRAW_TYPE_PRIMITIVE_ID)
+            {
+                // forward.frag:99-107 over forward.mesh:144
+                const f3 c = uint_to_color(g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID ? mi : local);
+                hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
+            }
+            else if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT)
+            {
+                const f3 c = debug_color(s, g.drawType, hit, sf);
+                hdr[i] = make_float4(c.x, c.y, c.z, 1.0f);
+            }
+            else
+            {
+                // forward.frag:52,67
+                sf.invViewRayWS = normalize(f3{g.r.eye[0], g.r.eye[1], g.r.eye[2]} - q);
+                sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
+                // forward.mesh:75: the third component of worldToCamera * (position, 1)
+                const float *w = v.worldToCamera;
+                const float zCam = __builtin_fmaf(w[10], q.z, __builtin_fmaf(w[6], q.y, __builtin_fmaf(w[2], q.x, w[14])));
+                const f3 color = shade_clustered<IBL>(s, sf, px, py, zCam, grid, pointers, indices, &ibl);
+                const float a = sf.material.alpha > 0.0f ? sf.material.alpha : 1.0f; // forward.frag:83,118
+                hdr[i] = make_float4(color.x, color.y, color.z, a);
+            }
+        }
+    }
+    // prosper_pt_get_forward_opaque_info: one atomic per wave, dealt over kForwardCountSlots counters a cache line apart (32 400
+    // waves at 1920x1080 on one address serialise: measured)
+    const uint64_t mask = __ballot(covered);
+    if (mask != 0ull && (threadIdx.x & 63u) == 0u)
+        atomicAdd(shadedPixels + (blockIdx.x % kForwardCountSlots) * kForwardCountStride, (uint32_t)__popcll(mask));
+}
+
+void launch_forward_opaque(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusterParams &c,
+    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr,
+    float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream, const GBufferLodParams *lod)
+{
+    if (g.r.width == 0 || g.r.height == 0) return;
+    const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
+    const ClusterGrid cg{c.near_, c.far_, c.dimX, c.dimY};
+    const IblMaps maps = {irradiance, radiance, lut};
+    const uint2 *ptrs = static_cast<const uint2 *>(pointers);
+    const bool ibl = irradiance != nullptr, debug = surfaces != nullptr;
+    if (lod)
+    {
+        const auto kernel = ibl ? (debug ? forward_opaque_kernel<true, true, true> : forward_opaque_kernel<true, true, false>)
+                                : (debug ? forward_opaque_kernel<false, true, true> : forward_opaque_kernel<false, true, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, *lod);
+        return;
+    }
+    const auto kernel = ibl ? (debug ? forward_opaque_kernel<true, false, true> : forward_opaque_kernel<true, false, false>)
+                            : (debug ? forward_opaque_kernel<false, false, true> : forward_opaque_kernel<false, false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, GBufferNoLod{});
 }
 
 } // namespace ppt

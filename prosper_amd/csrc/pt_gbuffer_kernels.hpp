@@ -118,6 +118,17 @@ void launch_deferred_shading(
     const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
     const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
     const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream);
+// The forward opaque pass (forward_opaque_kernel): the visibility image `r` shaded into `hdr` (overwritten,
+// g.r.width*g.r.height float4), with `nonLinearDepth` from the keys and v.velocity as launch_raster_resolve writes them; g, r,
+// v and lod as for the resolve.  The lists are launch_light_clustering's with `c`; irradiance / radiance / lut: the IBL
+// maps, all nullptr without IBL.  shadedPixels: kForwardCountSlots counters, kForwardCountStride uint32 apart, which the
+// caller zeroed: their sum is the covered pixels.  surfaces != nullptr: every pixel's surface record too (drawInstance
+// 0xFFFFFFFF where nothing is drawn).
+constexpr uint32_t kForwardCountSlots = 64, kForwardCountStride = 32;
+void launch_forward_opaque(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusterParams &c,
+    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr,
+    float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream, const GBufferLodParams *lod = nullptr);
 // Image-based lighting (ImageBasedLighting / evalIBL).  Every cube is stored with a one-texel seamless border, as the
 // sky is: 6 faces of (n + 2)^2 RGBA16F texels.  Radiance mip m (size kIblRadianceSize >> m) starts
 // ibl_radiance_offset(m) RGBA texels into its buffer; the LUT is kIblLutSize^2 R16G16 UNORM, row = roughness.

@@ -63,12 +63,32 @@ struct GBufferPassState
     bool transparentRan = false, transparentReclustered = false;
     size_t transparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
     uint32_t transparentLayerCount = 0;
+    // prosper_pt_raster_forward / _shade
+    DeviceBuffer forwardDepth;    // context-owned depth target: 4 bytes per pixel
+    DeviceBuffer forwardCount;    // kForwardCountSlots counters a cache line apart: the covered pixels of the last call
+    DeviceBuffer forwardSurfaces; // debug mode: one prosper_pt_transparent_layer per pixel
+    Pinned<uint32_t> forwardCountHost;
+    StageEvents<2> forwardTiming; // the clustering | the shade kernel
+    Fence forwardDone;            // behind the last call's copy of the count
+    bool forwardDebugSurfaces = false; // prosper_pt_set_forward_debug_surfaces
+    bool forwardRan = false, forwardReclustered = false;
+    size_t forwardSurfacePixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
 };
 
 void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias)
 {
     *enabled = ctx->gbufferPasses->lodEnabled;
     *bias = ctx->gbufferPasses->lodBias;
+}
+
+int gbuffer_last_depth(prosper_pt_ctx *ctx, const float **depth, uint32_t *width, uint32_t *height)
+{
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.gbufferLast.nonLinearDepth) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    *depth = st.gbufferLast.nonLinearDepth;
+    *width = st.gbufferLastWidth;
+    *height = st.gbufferLastHeight;
+    return PROSPER_PT_OK;
 }
 
 bool create_gbuffer_passes(prosper_pt_ctx *ctx)
@@ -92,21 +112,24 @@ void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage
     };
     const bool g = owned(st.gbuffer, st.gbufferLast.albedoRoughness) && owned(st.gbuffer, st.gbufferLast.normalMetallic) &&
                    owned(st.gbuffer, st.gbufferLast.nonLinearDepth);
+    // a forward frame leaves a depth and no attribute targets (prosper_pt_raster_forward)
+    const bool forwardDepth = !st.gbufferLast.albedoRoughness && owned(st.forwardDepth, st.gbufferLast.nonLinearDepth);
     const struct
     {
         const char *name;
         uint32_t format;
         const void *ptr;
-    } targets[3] = {{"albedoRoughness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.albedoRoughness},
-                    {"normalMetalness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.normalMetallic},
-                    {"depth", PROSPER_PT_DEBUG_FORMAT_R32F, st.gbufferLast.nonLinearDepth}};
+        bool valid;
+    } targets[3] = {{"albedoRoughness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.albedoRoughness, g},
+                    {"normalMetalness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.normalMetallic, g},
+                    {"depth", PROSPER_PT_DEBUG_FORMAT_R32F, st.gbufferLast.nonLinearDepth, g || forwardDepth}};
     for (const auto &t : targets)
     {
         DebugImage im;
         im.name = t.name;
         im.format = t.format;
-        im.valid = g;
-        if (g) im.one_level(t.ptr, st.gbufferLastWidth, st.gbufferLastHeight);
+        im.valid = t.valid;
+        if (t.valid) im.one_level(t.ptr, st.gbufferLastWidth, st.gbufferLastHeight);
         out.push_back(im);
     }
     DebugImage v;
@@ -270,6 +293,47 @@ GBufferTraceParams gbuffer_trace_params(
     return g;
 }
 
+// the matrices and jitters a velocity target is computed from
+void velocity_camera_terms(GBufferVelocityParams &v, const prosper_CameraUniforms *camera)
+{
+    std::memcpy(v.worldToCamera, &camera->worldToCamera, 64);
+    std::memcpy(v.cameraToClip, &camera->cameraToClip, 64);
+    std::memcpy(v.previousWorldToCamera, &camera->previousWorldToCamera, 64);
+    std::memcpy(v.previousCameraToClip, &camera->previousCameraToClip, 64);
+    for (int k = 0; k < 2; ++k)
+    {
+        v.currentJitter[k] = camera->currentJitter[k];
+        v.previousJitter[k] = camera->previousJitter[k];
+    }
+}
+
+// the context-owned velocity target, 8 bytes per pixel, grown like hostInputs
+int velocity_owned_target(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, float2 **out)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    if (st.velocity.bytes < pixels * 8u && st.velocityLast == st.velocity.ptr)
+    {
+        st.velocityLast = nullptr;
+        st.velocityLastWidth = st.velocityLastHeight = 0;
+    }
+    const int rc = grow_to(st.velocity, pixels * 8u, s);
+    *out = st.velocity.as<float2>();
+    return rc;
+}
+
+// the device copy of a call's previous instance transforms, enqueued on `s`
+int upload_previous_transforms(
+    prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t s, const prosper_ModelInstanceTransforms **out)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t bytes = sizeof(prosper_ModelInstanceTransforms) * (size_t)count;
+    const int rc = grow_to(st.previousTransforms, bytes, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    PPT_HIP(hipMemcpyAsync(st.previousTransforms.ptr, transforms, bytes, hipMemcpyHostToDevice, s));
+    *out = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
+    return PROSPER_PT_OK;
+}
+
 // The G-buffer pass on `s` after flush_scene_updates: camera terms, the traversal stacks, the launch.  `velocity`: the
 // velocity variant, whose matrices and jitters are filled in here from `camera`.
 int gbuffer_trace(
@@ -297,15 +361,7 @@ int gbuffer_trace(
     }
     if (velocity)
     {
-        std::memcpy(velocity->worldToCamera, &camera->worldToCamera, 64);
-        std::memcpy(velocity->cameraToClip, &camera->cameraToClip, 64);
-        std::memcpy(velocity->previousWorldToCamera, &camera->previousWorldToCamera, 64);
-        std::memcpy(velocity->previousCameraToClip, &camera->previousCameraToClip, 64);
-        for (int k = 0; k < 2; ++k)
-        {
-            velocity->currentJitter[k] = camera->currentJitter[k];
-            velocity->previousJitter[k] = camera->previousJitter[k];
-        }
+        velocity_camera_terms(*velocity, camera);
         // `raster`: the resolve of the rasteriser's visibility image writes the targets instead of a trace
         if (raster)
             launch_raster_resolve(ctx->scene, g, *raster, *velocity, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, s, lod);
@@ -392,6 +448,16 @@ int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
     st.clusterLightUpdates = ctx->lights ? ctx->lights->updates : 0u;
     st.clusterValid = true;
     return PROSPER_PT_OK;
+}
+
+// The forward passes' clustering: the lists of the last clustering serve when they were made from the same camera terms,
+// extent and lights (*reused); otherwise the lights are clustered on `s`
+int cluster_lights_unless_current(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s, bool *reused)
+{
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    const uint32_t lightUpdates = ctx->lights ? ctx->lights->updates : 0u;
+    *reused = st.clusterValid && std::memcmp(&st.clusterParams, &c, sizeof(c)) == 0 && st.clusterLightUpdates == lightUpdates;
+    return *reused ? PROSPER_PT_OK : cluster_lights(ctx, c, s);
 }
 
 // near_ and far_ feed log(far / near) and pow(far / near, s): both positive and ordered
@@ -575,32 +641,14 @@ static int velocity_gbuffer(
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
-    GBufferPassState &st = *ctx->gbufferPasses;
     const size_t pixels = (size_t)width * height;
     prosper_pt_gbuffer_targets t = given;
     if (targetCount == 0) rc = gbuffer_owned_targets(ctx, pixels, s, t);
     GBufferVelocityParams v = {};
     v.velocity = static_cast<float2 *>(desc->velocity);
-    if (rc == PROSPER_PT_OK && !desc->velocity)
-    {
-        if (st.velocity.bytes < pixels * 8u && st.velocityLast == st.velocity.ptr)
-        {
-            st.velocityLast = nullptr;
-            st.velocityLastWidth = st.velocityLastHeight = 0;
-        }
-        rc = grow_to(st.velocity, pixels * 8u, s);
-        v.velocity = st.velocity.as<float2>();
-    }
+    if (rc == PROSPER_PT_OK && !desc->velocity) rc = velocity_owned_target(ctx, pixels, s, &v.velocity);
     if (rc == PROSPER_PT_OK && desc->previousTransforms)
-    {
-        const size_t bytes = sizeof(prosper_ModelInstanceTransforms) * (size_t)desc->previousTransformCount;
-        rc = grow_to(st.previousTransforms, bytes, s);
-        if (rc == PROSPER_PT_OK)
-        {
-            PPT_HIP(hipMemcpyAsync(st.previousTransforms.ptr, desc->previousTransforms, bytes, hipMemcpyHostToDevice, s));
-            v.previousTransforms = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
-        }
-    }
+        rc = upload_previous_transforms(ctx, desc->previousTransforms, desc->previousTransformCount, s, &v.previousTransforms);
     RasterResolveTables tables = {};
     if (rc == PROSPER_PT_OK && raster) rc = raster_resolve_tables(ctx, what, width, height, s, &tables);
     if (rc == PROSPER_PT_OK)
@@ -636,6 +684,201 @@ int prosper_pt_raster_gbuffer(
     const int rc = prosper_pt_raster_visibility(ctx, camera, stream);
     if (rc != PROSPER_PT_OK) return rc;
     return velocity_gbuffer(what, true, ctx, drawType, 0u, 0u, camera, camera->resolution[0], camera->resolution[1], desc, stream);
+}
+
+// ---- forward opaque pass (src/render/ForwardRenderer.cpp recordOpaque) ----
+
+constexpr size_t kForwardCountBytes = (size_t)kForwardCountSlots * kForwardCountStride * sizeof(uint32_t);
+
+// What both forward entries refuse of their arguments, before anything is enqueued (and, for prosper_pt_raster_forward,
+// before the culling phases replace the lists)
+static int check_forward_opaque(
+    const char *what, prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (!pc || !camera || !desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
+    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
+    if (reinterpret_cast<uintptr_t>(desc->nonLinearDepth) & 3u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the depth target must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(desc->velocity) & 7u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the velocity target must be 8-byte aligned");
+    if (!desc->previousTransforms && desc->previousTransformCount != 0u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount without previousTransforms");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    const int crc = check_scene(ctx, what);
+    if (crc != PROSPER_PT_OK) return crc;
+    if (desc->previousTransforms && desc->previousTransformCount != ctx->scene.modelInstanceCount)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
+    return PROSPER_PT_OK;
+}
+
+// The shade over the visibility image as it stands: what the resolve refuses is refused before the HDR image, the depth or
+// the velocity are touched; then the targets, the clustering (unless the last one serves) and the kernel, all on `s`.
+static int forward_shade(
+    const char *what, prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc,
+    void *stream)
+{
+    if (const int rc = check_forward_opaque(what, ctx, pc, camera, desc)) return rc;
+    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = flush_scene_updates(ctx, s, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    RasterResolveTables tables = {};
+    if ((rc = raster_resolve_tables(ctx, what, width, height, s, &tables)) != PROSPER_PT_OK) return rc;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t pixels = (size_t)width * height;
+    float *depth = desc->nonLinearDepth;
+    if (!depth)
+    {
+        if (st.forwardDepth.bytes < pixels * 4u && st.gbufferLast.nonLinearDepth == st.forwardDepth.ptr)
+        {
+            st.gbufferLast = prosper_pt_gbuffer_targets{};
+            st.gbufferLastWidth = st.gbufferLastHeight = 0;
+        }
+        if ((rc = grow_to(st.forwardDepth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
+        depth = st.forwardDepth.as<float>();
+    }
+    GBufferVelocityParams v = {};
+    v.velocity = static_cast<float2 *>(desc->velocity);
+    if (!desc->velocity && (rc = velocity_owned_target(ctx, pixels, s, &v.velocity)) != PROSPER_PT_OK) return rc;
+    if (desc->previousTransforms &&
+        (rc = upload_previous_transforms(ctx, desc->previousTransforms, desc->previousTransformCount, s, &v.previousTransforms)) != PROSPER_PT_OK)
+        return rc;
+    velocity_camera_terms(v, camera);
+    if ((rc = prepare_hdr(ctx, width, height, nullptr, s)) != PROSPER_PT_OK) return rc;
+    if ((rc = grow_to(st.forwardCount, kForwardCountBytes, s)) != PROSPER_PT_OK) return rc;
+    if (!st.forwardCountHost.ptr && (rc = st.forwardCountHost.allocate(kForwardCountBytes)) != PROSPER_PT_OK) return rc;
+    const bool debug = st.forwardDebugSurfaces;
+    if (debug && (rc = grow_to(st.forwardSurfaces, pixels * sizeof(prosper_pt_transparent_layer), s)) != PROSPER_PT_OK) return rc;
+    if ((rc = st.forwardTiming.create()) != PROSPER_PT_OK) return rc;
+    st.forwardRan = false;
+    st.forwardSurfacePixels = 0;
+
+    PPT_HIP(hipEventRecord(st.forwardTiming.events[0], s));
+    const ClusterParams c = cluster_params(camera, width, height);
+    bool reuse = false;
+    if ((rc = cluster_lights_unless_current(ctx, c, s, &reuse)) != PROSPER_PT_OK) return rc;
+    PPT_HIP(hipMemsetAsync(st.forwardCount.ptr, 0, kForwardCountBytes, s));
+    PPT_HIP(hipEventRecord(st.forwardTiming.events[1], s));
+
+    // previousTransformValid is not read: desc->previousTransforms decides
+    const GBufferTraceParams g = gbuffer_trace_params(pc->drawType, 0u, false, false, camera, width, height);
+    const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
+    const bool ibl = pc->ibl == 1u;
+    launch_forward_opaque(
+        ctx->scene, g, tables, v, c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
+        ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, depth, st.forwardCount.as<uint32_t>(),
+        debug ? st.forwardSurfaces.as<prosper_pt_transparent_layer>() : nullptr, s, st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
+    PPT_HIP(hipGetLastError());
+    PPT_HIP(hipEventRecord(st.forwardTiming.events[2], s));
+    PPT_HIP(hipMemcpyAsync(st.forwardCountHost.ptr, st.forwardCount.ptr, kForwardCountBytes, hipMemcpyDeviceToHost, s));
+    if ((rc = st.forwardDone.record(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = raster_resolve_enqueued(ctx, s)) != PROSPER_PT_OK) return rc;
+    st.forwardRan = true;
+    st.forwardReclustered = !reuse;
+    st.forwardSurfacePixels = debug ? pixels : 0u;
+    // a forward frame has a depth and a velocity, and no attribute targets
+    st.gbufferLast = prosper_pt_gbuffer_targets{};
+    st.gbufferLast.nonLinearDepth = depth;
+    st.gbufferLastWidth = width;
+    st.gbufferLastHeight = height;
+    st.lodDerivativesWidth = st.lodDerivativesHeight = 0;
+    st.velocityLast = v.velocity;
+    st.velocityLastWidth = width;
+    st.velocityLastHeight = height;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_raster_forward_shade(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream)
+{
+    return forward_shade("prosper_pt_raster_forward_shade", ctx, pc, camera, desc, stream);
+}
+
+int prosper_pt_raster_forward(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream)
+{
+    const char *what = "prosper_pt_raster_forward";
+    // what the shade would refuse of its arguments is refused before the culling phases replace the lists
+    if (const int rc = check_forward_opaque(what, ctx, pc, camera, desc)) return rc;
+    const int rc = prosper_pt_raster_visibility(ctx, camera, stream);
+    if (rc != PROSPER_PT_OK) return rc;
+    return forward_shade(what, ctx, pc, camera, desc, stream);
+}
+
+int prosper_pt_set_forward_debug_surfaces(prosper_pt_ctx *ctx, int enabled)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_forward_debug_surfaces: null argument");
+    ctx->gbufferPasses->forwardDebugSurfaces = enabled != 0;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_forward_surfaces(prosper_pt_ctx *ctx, prosper_pt_transparent_layer *out, size_t pixels, void *stream)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_surfaces: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.forwardRan || !st.forwardSurfacePixels)
+        return fail(PROSPER_PT_ERR_NO_SCENE, "the last forward opaque pass did not run in debug mode (prosper_pt_set_forward_debug_surfaces)");
+    if (pixels != st.forwardSurfacePixels)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_surfaces: pixel count differs from the call's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = st.forwardDone.wait(s)) return rc;
+    PPT_HIP(hipMemcpyAsync(out, st.forwardSurfaces.ptr, pixels * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_forward_opaque_info(prosper_pt_ctx *ctx, prosper_pt_forward_opaque_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_forward_opaque_info: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.forwardRan) return fail(PROSPER_PT_ERR_NO_SCENE, "the forward opaque pass has not run yet");
+    PPT_HIP(hipSetDevice(ctx->device));
+    prosper_pt_forward_opaque_info info = {};
+    info.reclustered = st.forwardReclustered ? 1u : 0u;
+    *out = info;
+    if (!st.forwardDone.passed()) return PROSPER_PT_NOT_READY;
+    float ms[2] = {};
+    if (const int rc = st.forwardTiming.elapsed(ms)) return rc; // (behind the fence that has passed: no wait)
+    for (uint32_t k = 0; k < kForwardCountSlots; ++k) info.shadedPixels += st.forwardCountHost.ptr[k * kForwardCountStride];
+    info.ms = ms[0] + ms[1];
+    info.shadeMs = ms[1];
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_forward_depth_device_ptr(prosper_pt_ctx *ctx, float **out, uint32_t *width, uint32_t *height)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_forward_depth_device_ptr: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.forwardRan || st.gbufferLast.albedoRoughness || !st.gbufferLast.nonLinearDepth)
+        return fail(PROSPER_PT_ERR_NO_SCENE, "the context's last depth is not a forward frame's");
+    *out = st.gbufferLast.nonLinearDepth;
+    if (width) *width = st.gbufferLastWidth;
+    if (height) *height = st.gbufferLastHeight;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_forward_depth(prosper_pt_ctx *ctx, float *host_depth, size_t pixels, void *stream)
+{
+    if (!ctx || !host_depth) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_depth: null argument");
+    float *depth = nullptr;
+    uint32_t w = 0, h = 0;
+    if (const int rc = prosper_pt_get_forward_depth_device_ptr(ctx, &depth, &w, &h)) return rc;
+    if (pixels != (size_t)w * h) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_depth: pixel count differs from the depth's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = ctx->gbufferPasses->forwardDone.wait(s)) return rc;
+    PPT_HIP(hipMemcpyAsync(host_depth, depth, pixels * 4u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_get_velocity_device_ptr(prosper_pt_ctx *ctx, void **out, uint32_t *width, uint32_t *height)
@@ -938,15 +1181,10 @@ int prosper_pt_forward_transparent(
     st.transparentLayerPixels = 0;
     PPT_HIP(hipEventRecord(st.transparentTiming.events[0], s));
 
-    // the lists of the last clustering serve when they were made from the same camera terms, extent and lights
     const ClusterParams c = cluster_params(camera, width, height);
-    const uint32_t lightUpdates = ctx->lights ? ctx->lights->updates : 0u;
-    const bool reuse = st.clusterValid && std::memcmp(&st.clusterParams, &c, sizeof(c)) == 0 && st.clusterLightUpdates == lightUpdates;
-    if (!reuse)
-    {
-        rc = cluster_lights(ctx, c, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
+    bool reuse = false;
+    rc = cluster_lights_unless_current(ctx, c, s, &reuse);
+    if (rc != PROSPER_PT_OK) return rc;
 
     TransparentParams p = {};
     p.g = gbuffer_trace_params(pc->drawType, frameIndex, (flags & PROSPER_PT_TRANSPARENT_JITTER) != 0, false, camera, width, height);

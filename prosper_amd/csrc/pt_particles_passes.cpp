@@ -139,13 +139,13 @@ int prosper_pt_particles(
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_particles: the HDR image has another extent");
         if (!depth)
         {
-            prosper_pt_restir_inputs g = {};
+            const float *last = nullptr;
             uint32_t gw = 0, gh = 0;
-            const int rc = prosper_pt_get_gbuffer_device_ptrs(ctx, &g, &gw, &gh);
+            const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
             if (rc != PROSPER_PT_OK) return rc;
             if (gw != width || gh != height)
                 return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_particles: the last traced G-buffer has another extent");
-            depth = const_cast<float *>(g.nonLinearDepth);
+            depth = const_cast<float *>(last);
         }
     }
     PPT_HIP(hipSetDevice(ctx->device));

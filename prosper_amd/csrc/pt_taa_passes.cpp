@@ -109,13 +109,13 @@ int prosper_pt_taa_resolve(
     }
     if (closest && !inputs->nonLinearDepth)
     {
-        prosper_pt_restir_inputs g = {};
+        const float *last = nullptr;
         uint32_t gw = 0, gh = 0;
-        const int rc = prosper_pt_get_gbuffer_device_ptrs(ctx, &g, &gw, &gh);
+        const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
         if (rc != PROSPER_PT_OK) return rc;
         if (gw != width || gh != height)
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_taa_resolve: the last traced G-buffer has another extent");
-        b.nonLinearDepth = g.nonLinearDepth;
+        b.nonLinearDepth = last;
     }
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);

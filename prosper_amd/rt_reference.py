@@ -506,9 +506,10 @@ class SkyboxRenderer:
 
 
 class ForwardRenderer:
-    """render::ForwardRenderer (csrc/host/forward_renderer.hpp), its transparent pass, on a Context the scene was uploaded
-    to: record_transparent blends the BLEND layers over the context's HDR image (Context.forward_transparent) and returns
-    the S.ForwardPC it pushed."""
+    """render::ForwardRenderer (csrc/host/forward_renderer.hpp) on a Context the scene was uploaded to: record_opaque is
+    prosper_pt_raster_forward into the context's HDR image, depth and velocity and returns S.ForwardRendererOutput (device
+    pointers); release_preserved forgets the kept pyramid and transforms; record_transparent blends the BLEND layers over
+    the context's HDR image (Context.forward_transparent) and returns the S.ForwardPC it pushed."""
 
     def __init__(self, ctx):
         h = C.c_void_p()
@@ -523,6 +524,22 @@ class ForwardRenderer:
         rc = lib().prosper_host_forward_renderer_set_texture_lod(self._h, int(bool(enabled)), lod_bias)
         if rc != 0:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+
+    def record_opaque(self, camera, width, height, apply_ibl=False, draw_type="Default", transforms=None, stream=None):
+        """`camera`: a Camera; `transforms`: this frame's ctypes array of S.ModelInstanceTransforms, kept as the next
+        record's previous frame"""
+        out = S.ForwardRendererOutput()
+        rc = lib().prosper_host_forward_renderer_record_opaque(
+            self._h, camera._h, width, height, int(apply_ibl), S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type),
+            None if transforms is None else C.cast(transforms, C.c_void_p), 0 if transforms is None else len(transforms),
+            C.c_void_p(stream), C.byref(out))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._ctx._forward_extent = (width, height)
+        return out
+
+    def release_preserved(self):
+        lib().prosper_host_forward_renderer_release_preserved(self._h)
 
     def record_transparent(self, camera, width, height, depth=None, depth_ptr=None, ray_flags=0, frame_index=0,
                            apply_ibl=False, draw_type="Default", stream=None):

@@ -417,6 +417,18 @@ class ForwardPC(C.Structure):
     _fields_ = [("drawType", C.c_uint32), ("ibl", C.c_uint32), ("previousTransformValid", C.c_uint32)]
 
 
+class ForwardOpaqueDesc(C.Structure):
+    """prosper_pt_forward_opaque_desc: the depth and velocity targets on the device (None: context-owned), the previous
+    frame's instance transforms on the host (None: the instances did not move)"""
+    _fields_ = [("nonLinearDepth", C.c_void_p), ("velocity", C.c_void_p), ("previousTransforms", C.c_void_p),
+                ("previousTransformCount", C.c_uint32)]
+
+
+class ForwardOpaqueInfo(C.Structure):
+    """prosper_pt_forward_opaque_info of the last forward shade"""
+    _fields_ = [("shadedPixels", C.c_uint32), ("reclustered", C.c_uint32), ("ms", C.c_float), ("shadeMs", C.c_float)]
+
+
 # prosper_pt_forward_transparent flags: which of the G-buffer's rays the pass follows (neither: the pixel centre)
 TRANSPARENT_JITTER = 1 << 0
 TRANSPARENT_CAMERA_JITTER = 1 << 1
@@ -502,6 +514,11 @@ RASTER_CLEAR = 1  # PROSPER_PT_RASTER_CLEAR
 class GBufferRendererOutput(C.Structure):
     """prosper_host_gbuffer_renderer_output: device pointers in place of the reference's image handles"""
     _fields_ = [("albedoRoughness", C.c_void_p), ("normalMetalness", C.c_void_p), ("velocity", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class ForwardRendererOutput(C.Structure):
+    """prosper_host_forward_renderer_output: device pointers in place of the reference's image handles"""
+    _fields_ = [("illumination", C.c_void_p), ("velocity", C.c_void_p), ("depth", C.c_void_p)]
 
 
 class RasterDrawInfo(C.Structure):

@@ -62,6 +62,13 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  are built for the loaded scene, both culling phases run on the rasteriser's own depth, the
                                  resolve fills the context's targets; composes with --sky --ibl --bloom --taa --dof
                                  --texture-lod --cull-stats; --draw-type MeshletID / PrimitiveID show the mesh shader's ids.
+    --forward                    prosper's forward path in place of --deferred's G-buffer and shading:
+                                 prosper_pt_raster_forward - meshlets are built for the loaded scene, both culling phases run
+                                 on the rasteriser's own depth, and every pixel's winning triangle is shaded directly over
+                                 the light clusters into the image, with the depth and the velocity the later passes read;
+                                 composes with --ibl --sky --bloom --particles --taa --dof --texture-lod --draw-type
+                                 --cull-stats --debug-lines exactly as --deferred --raster does; not with --deferred or
+                                 --restir-di
     --deferred --cull-stats      prosper's visibility system: meshlets are built for the loaded scene
                                  (World.add_meshlets), prosper_pt_cull_gbuffer runs after the G-buffer of each frame - first
                                  phase against the previous frame's depth pyramid, the pyramid of this frame's depth, second
@@ -141,6 +148,8 @@ def main():
     ap.add_argument("--debug-zoom", action="store_true", help="with --debug-view: the middle of the image four times larger")
     ap.add_argument("--raster", action="store_true", help="with --deferred: the G-buffer by prosper_pt_raster_gbuffer (meshlets, both culling phases, "
                     "the compute rasteriser and its resolve) in place of the traced one")
+    ap.add_argument("--forward", action="store_true", help="the forward path (prosper_pt_raster_forward) in place of --deferred's G-buffer and shading; "
+                    "implies the rasteriser and meshlets")
     ap.add_argument("--draw-type", default="Default", choices=["Default", "PrimitiveID", "MeshletID", "MeshID", "MaterialID", "Position", "ShadingNormal", "TexCoord0", "Albedo",
                              "Roughness", "Metallic"],
                     help="with --raster: the G-buffer's draw type (MeshletID and PrimitiveID are the mesh shader's), shaded as that debug view")
@@ -148,6 +157,11 @@ def main():
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     args = ap.parse_args()
+    if args.forward and (args.deferred or args.restir_di):
+        ap.error("--forward is the forward path: it does not go with --deferred or --restir-di")
+    if args.forward:
+        # what follows the opaque image is --deferred --raster's: the same passes over the same "last" depth and velocity
+        args.deferred = args.raster = True
     if args.bloom_fft and not args.bloom:
         ap.error("--bloom-fft belongs to --bloom")
     if (args.sky or args.dof or args.bloom or args.taa or args.transparents or args.particles or args.debug_lines
@@ -212,6 +226,8 @@ def main():
             tracer.set_texture_lod(True, renderer_lod_bias(args.taa))  # Renderer::lodBias(): -1 while TAA is on
             if forward:
                 forward.set_texture_lod(True, renderer_lod_bias(args.taa))
+            if args.forward:
+                ctx.set_texture_lod(True, renderer_lod_bias(args.taa))  # the rasteriser's discard and the shade read the context's state
         if args.taa:
             hcam.set_jitter(True)
             taa = TemporalAntiAliasing(ctx)
@@ -237,10 +253,15 @@ def main():
                 if args.taa:
                     cam, focal = hcam.update_buffer()
                 # (this frame's table is the next frame's previous one; the first frame sees unmoved instances)
-                ctx.raster_gbuffer(cam, draw_type=S.DrawType[args.draw_type], previous_transforms=transforms if args.taa and frame else None)
-                g, _, _ = ctx.gbuffer_device_ptrs()
-                ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth,
-                                            draw_type=S.DrawType[args.draw_type], ibl=1 if args.ibl else 0)
+                if args.forward:
+                    # ForwardRenderer::recordOpaque: the same lists and draws, shaded without a G-buffer in between
+                    ctx.raster_forward(cam, draw_type=S.DrawType[args.draw_type], ibl=1 if args.ibl else 0,
+                                       previous_transforms=transforms if args.taa and frame else None)
+                else:
+                    ctx.raster_gbuffer(cam, draw_type=S.DrawType[args.draw_type], previous_transforms=transforms if args.taa and frame else None)
+                    g, _, _ = ctx.gbuffer_device_ptrs()
+                    ctx.deferred_shading_device(cam, w, h, g.albedoRoughness, g.normalMetallic, g.nonLinearDepth,
+                                                draw_type=S.DrawType[args.draw_type], ibl=1 if args.ibl else 0)
                 if args.cull_stats:
                     ds = ctx.draw_stats()
                     print("frame %d DrawStats: drawn meshlets %d of %d, rasterized triangles %d of %d, meshes %d, models %d" % (
@@ -304,6 +325,10 @@ def main():
             info = ctx.bloom_info()
             print("bloom: threshold %.3f, working extent %dx%d, streak half-width %d" % (
                 args.bloom_threshold, info.workingWidth, info.workingHeight, info.streakHalfWidth), file=sys.stderr)
+        if args.forward:
+            ctx.read_hdr()  # (synchronises: the info never waits)
+            info = ctx.forward_opaque_info() or S.ForwardOpaqueInfo()
+            print("forward opaque: %d pixels shaded, last shade %.3f ms (kernel %.3f ms)" % (info.shadedPixels, info.ms, info.shadeMs), file=sys.stderr)
         if forward:
             info = ctx.transparent_info()
             print("transparents: %d pixels with layers, %d layers, deepest %d, last pass %.3f ms" % (
