@@ -249,6 +249,13 @@ int prosper_host_forward_renderer_record_transparent(
     prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height,
     const float *nonLinearDepth, uint32_t onDevice, uint32_t rayFlags, uint32_t frameIndex, int applyIbl, uint32_t drawType,
     void *stream, prosper_pt_forward_pc *outPushConstants);
+/* ForwardRenderer::recordTransparentRaster: Camera::updateBuffer + prosper_pt_raster_forward_transparent -
+ * the TRANSPARENT list culled once, its per-pixel fragment lists, their resolve over the context's HDR image, against
+ * `nonLinearDepth` (NULL: the context's last depth, a forward frame's included).  The raster frame's transparents; the call
+ * waits on the host once.  The context's draw lists are the transparent ones afterwards. */
+int prosper_host_forward_renderer_record_transparent_raster(
+    prosper_host_forward_renderer *pass, prosper_host_camera *camera, uint32_t width, uint32_t height, const float *nonLinearDepth,
+    uint32_t onDevice, int applyIbl, uint32_t drawType, void *stream, prosper_pt_forward_pc *outPushConstants);
 typedef struct prosper_host_forward_renderer_output
 {
     const void *illumination; /* the context's HDR image */

@@ -1394,6 +1394,82 @@ int prosper_pt_get_forward_opaque_info(prosper_pt_ctx *ctx, prosper_pt_forward_o
  * must be its width * height.  The velocity is prosper_pt_get_velocity_device_ptr's and prosper_pt_read_velocity's. */
 int prosper_pt_get_forward_depth_device_ptr(prosper_pt_ctx *ctx, float **out, uint32_t *width, uint32_t *height);
 int prosper_pt_read_forward_depth(prosper_pt_ctx *ctx, float *host_depth, size_t pixels, void *stream);
+/* ---- rasterised transparent pass (src/render/ForwardRenderer.cpp recordTransparent:222-260) ----
+ * The BLEND layers of the raster frame, from the meshlet draw lists instead of a ray per pixel: the rasteriser's own
+ * coverage (the top-left rule the opaque image was drawn with), meshlet culling, draw statistics, and no hierarchy in the
+ * loop.  In place over the context's HDR image, which must have camera->resolution.  Additive: the ABI version stays 4,
+ * prosper_pt_forward_transparent stays.
+ *
+ * A LAYER CANDIDATE of a pixel is a fragment of the rasteriser's rule above (same vertices, snapping, edge functions,
+ * culling, clipper and depth) of a triangle of the list's meshlets
+ *   - whose depth is strictly greater than the stored depth of the pixel (reverse-Z eGreater, no depth write): a stored 0
+ *     passes everything, a coplanar fragment fails;
+ *   - whose sampleMaterial alpha is not 0 (forward.frag:57), decided by the MASK discard's own code: the pixel's ray, the
+ *     uv and the texture LOD state of prosper_pt_set_texture_lod.
+ * Every candidate contributes the visibility image's key, depth bits above ~(ordinal * 128 + triangle).  The keys of one
+ * pixel are unique and totally ordered: the greatest is the nearest, on equal depths the lowest (drawInstanceIndex,
+ * meshletIndex, triangle).  The lists are built in three steps - a raster pass that counts, an exclusive scan of the
+ * per-pixel counts, the same raster pass again that fills - and resolved with one lane per pixel: front to back, each layer
+ * with the surface prosper_pt_raster_forward_shade gives a winner, forward.frag's colour and alpha as there, composited
+ * as prosper_pt_forward_transparent composites (C += T a src, T *= 1 - a, the end C + T dst at T == 0 or after the last
+ * layer; alpha = a (1 - a) of the nearest layer).  A pixel without a layer keeps its four floats bit for bit.  Other draw
+ * types than Default show the nearest layer with alpha 1: MeshletID uintToColor(meshletIndex), PrimitiveID the
+ * meshlet-local triangle, the rest the debug colour.
+ *
+ *   prosper_pt_raster_transparent_draw     count, scan, fill and resolve over list `which` (GENERATED, FIRST_PHASE or
+ *       SECOND_PHASE) of the last culling call.
+ *   prosper_pt_raster_forward_transparent  recordTransparent: the first phase in TRANSPARENT mode with PROSPER_PT_NO_HIZ,
+ *       then the draw of FIRST_PHASE.  The context holds ONE set of draw lists: after the call they are the transparent
+ *       ones, and prosper_pt_get_draw_stats reports this cull.  The pyramid prosper_pt_raster_visibility kept is untouched.
+ * THE CALL BLOCKS THE HOST ONCE, between scan and fill: it reads the 4-byte total of the scan from pinned memory behind an
+ * event and grows the context-owned, grow-only fragment buffer to it.  A total of 0 launches nothing further.
+ * `nonLinearDepth`, `onDevice`: as prosper_pt_skybox_fill (NULL: the context's last depth, a forward frame's included).
+ * The lights are clustered first on `stream` unless the context's last clustering serves; pending scene updates are flushed
+ * once; calls on different streams are ordered on the device as prosper_pt_raster_gbuffer orders them.
+ * Refused before anything is launched, the image left as it was: what prosper_pt_raster_meshlets refuses (no scene, no
+ * meshlets, a list the last culling calls did not produce, an unknown list, camera->resolution empty or above 16384);
+ * drawType out of range, ibl not 0 or 1, ibl = 1 before prosper_pt_generate_ibl (PROSPER_PT_ERR_UNSUPPORTED), a camera
+ * without 0 < near_ < far_, a depth that is not 4-byte aligned, NULL before any depth exists; an HDR image or a last depth
+ * whose extent is not camera->resolution. */
+int prosper_pt_raster_transparent_draw(
+    prosper_pt_ctx *ctx, uint32_t which, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth,
+    uint32_t onDevice, void *stream);
+int prosper_pt_raster_forward_transparent(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth, uint32_t onDevice,
+    void *stream);
+typedef struct prosper_pt_raster_transparent_info
+{
+    uint32_t fragments;     /* layer candidates in all lists (the scan's total) */
+    uint32_t coveredPixels; /* pixels with at least one */
+    uint32_t shadedLayers;  /* layers the resolve shaded: those behind a pixel's T == 0 are not */
+    uint32_t maxLayers;     /* the longest list */
+    uint32_t reclustered;   /* 1: the call clustered the lights itself */
+    float countMs;          /* device time of the counting raster pass ... */
+    float scanMs;           /* ... the scan ... */
+    float fillMs;           /* ... the filling raster pass ... */
+    float resolveMs;        /* ... and the resolve, its clustering included */
+    uint32_t reserved;
+} prosper_pt_raster_transparent_info;
+/* Of the last pass; never blocks: PROSPER_PT_NOT_READY (`fragments` and `reclustered` filled in) until the counts have
+ * landed, NO_SCENE before the first. */
+int prosper_pt_get_raster_transparent_info(prosper_pt_ctx *ctx, prosper_pt_raster_transparent_info *out);
+/* Synchronises `stream` and decodes the lists of the last pass on the host: `counts` pixels uint32, and the fragments
+ * pixel after pixel - a pixel's run starts at the sum of the counts before it - each run sorted front to back.  *total: the
+ * fragments in all lists (with counts and fragments NULL the call only reports it, without synchronising).  `pixels` must
+ * be the pass's width * height, `capacity` at least *total. */
+typedef struct prosper_pt_raster_fragment
+{
+    uint32_t drawInstance, meshlet, triangle;
+    float depth;
+} prosper_pt_raster_fragment;
+int prosper_pt_read_raster_fragments(
+    prosper_pt_ctx *ctx, uint32_t *counts, size_t pixels, prosper_pt_raster_fragment *fragments, size_t capacity, uint64_t *total, void *stream);
+/* Debug mode, for tests, as prosper_pt_set_transparent_debug_layers: with layersPerPixel > 0 (at most 128) every later pass
+ * also writes each pixel's count of SHADED layers and the first layersPerPixel of them, front to back (`primitive` is the
+ * geometry triangle, nonLinearDepth the key's depth); the image is the same bit for bit. */
+int prosper_pt_set_raster_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel);
+int prosper_pt_read_raster_transparent_layers(
+    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels, uint32_t layersPerPixel, void *stream);
 /* Synchronises `stream` (behind the last draw, whatever its stream) and decodes the image on the host: per pixel
  * (drawInstanceIndex, meshletIndex, triangle) as three uint32 - 0xFFFFFFFF each where nothing is drawn - into `ids`, the
  * key's depth into `depth`; either may be NULL.  `pixels`: room in pixels, at least width * height of the image. */

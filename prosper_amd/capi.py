@@ -151,6 +151,12 @@ def lib():
     L.prosper_pt_set_forward_debug_surfaces.argtypes = [vp, C.c_int]
     L.prosper_pt_read_forward_surfaces.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_forward_opaque_info.argtypes = [vp, C.POINTER(S.ForwardOpaqueInfo)]
+    L.prosper_pt_raster_transparent_draw.argtypes = [vp, u32, C.POINTER(S.ForwardPC), C.POINTER(S.CameraUniforms), vp, u32, vp]
+    L.prosper_pt_raster_forward_transparent.argtypes = [vp, C.POINTER(S.ForwardPC), C.POINTER(S.CameraUniforms), vp, u32, vp]
+    L.prosper_pt_get_raster_transparent_info.argtypes = [vp, C.POINTER(S.RasterTransparentInfo)]
+    L.prosper_pt_read_raster_fragments.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_uint64), vp]
+    L.prosper_pt_set_raster_transparent_debug_layers.argtypes = [vp, u32]
+    L.prosper_pt_read_raster_transparent_layers.argtypes = [vp, vp, vp, C.c_size_t, u32, vp]
     L.prosper_pt_get_forward_depth_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.prosper_pt_read_forward_depth.argtypes = [vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_raster_info.argtypes = [vp, C.POINTER(S.RasterInfo)]
@@ -303,6 +309,7 @@ def lib():
     L.prosper_host_forward_renderer_destroy.restype = None
     L.prosper_host_forward_renderer_record_opaque.argtypes = [vp, vp, u32, u32, C.c_int, u32, vp, u32, vp, C.POINTER(S.ForwardRendererOutput)]
     L.prosper_host_forward_renderer_release_preserved.argtypes = [vp]
+    L.prosper_host_forward_renderer_record_transparent_raster.argtypes = [vp, vp, u32, u32, vp, u32, C.c_int, u32, vp, C.POINTER(S.ForwardPC)]
     L.prosper_host_forward_renderer_record_transparent.argtypes = [vp, vp, u32, u32, vp, u32, u32, u32, C.c_int, u32, vp,
                                                                    C.POINTER(S.ForwardPC)]
     L.prosper_host_particles_create.argtypes = [vp, C.POINTER(vp)]
@@ -1207,6 +1214,66 @@ class Context:
             return None
         _check(rc)
         return out
+
+    # ---- the rasterised transparent pass over the draw lists (prosper_pt_raster_*transparent*) ----
+
+    def _raster_transparent(self, entry, head, camera, draw_type, ibl, depth, depth_ptr, stream):
+        self._sync_debug()
+        w, h = int(camera.resolution[0]), int(camera.resolution[1])
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        assert dp is None or dp.shape == (h, w)
+        ptr = depth_ptr if dp is None else dp.ctypes.data
+        pc = S.ForwardPC(int(draw_type), int(ibl), 0)
+        _check(entry(self._h, *head, C.byref(pc), C.byref(camera), C.c_void_p(ptr), 1 if dp is None else 0, C.c_void_p(stream)))
+        self._raster_transparent_extent = (w, h)
+
+    def raster_transparent_draw(self, camera, which=S.DRAW_LIST_FIRST_PHASE, draw_type=0, ibl=0, depth=None, depth_ptr=None, stream=None):
+        """prosper_pt_raster_transparent_draw: the per-pixel fragment lists of draw list `which` (count, scan, fill) against
+        the depth, resolved front to back in place over the HDR image.  `depth`: a host array [h, w]; `depth_ptr`: a device
+        pointer; neither: the context's last depth.  Blocks the host once, for the scan's total."""
+        self._raster_transparent(lib().prosper_pt_raster_transparent_draw, (which,), camera, draw_type, ibl, depth, depth_ptr, stream)
+
+    def raster_forward_transparent(self, camera, draw_type=0, ibl=0, depth=None, depth_ptr=None, stream=None):
+        """prosper_pt_raster_forward_transparent (ForwardRenderer::recordTransparent): the first phase in TRANSPARENT mode
+        without a pyramid, then raster_transparent_draw of its list.  The context's draw lists are then the transparent ones."""
+        self._raster_transparent(lib().prosper_pt_raster_forward_transparent, (), camera, draw_type, ibl, depth, depth_ptr, stream)
+
+    def raster_transparent_info(self):
+        """S.RasterTransparentInfo of the last rasterised transparent pass; None while its counts have not landed (never waits)."""
+        out = S.RasterTransparentInfo()
+        rc = lib().prosper_pt_get_raster_transparent_info(self._h, C.byref(out))
+        if rc == S.NOT_READY:
+            return None
+        _check(rc)
+        return out
+
+    def read_raster_fragments(self, stream=None):
+        """The lists of the last rasterised transparent pass: (counts uint32 [h, w], fragments [total] of the structured dtype
+        of S.RasterFragment, pixel after pixel in row-major order, each pixel's run sorted front to back)."""
+        w, h = getattr(self, "_raster_transparent_extent", (0, 0))  # (before the first pass the library refuses)
+        total = C.c_uint64()
+        _check(lib().prosper_pt_read_raster_fragments(self._h, None, 0, None, 0, C.byref(total), C.c_void_p(stream)))
+        counts = np.empty((h, w), np.uint32)
+        fragments = np.empty(total.value, np.dtype(S.RasterFragment))
+        _check(lib().prosper_pt_read_raster_fragments(self._h, counts.ctypes.data, w * h, fragments.ctypes.data, len(fragments),
+                                                      C.byref(total), C.c_void_p(stream)))
+        return counts, fragments
+
+    def set_raster_transparent_debug_layers(self, layers_per_pixel):
+        """Debug mode of the rasterised transparent pass: later calls record each pixel's first `layers_per_pixel` shaded
+        layers (0: off)."""
+        _check(lib().prosper_pt_set_raster_transparent_debug_layers(self._h, layers_per_pixel))
+        self._raster_transparent_layers = layers_per_pixel
+
+    def read_raster_transparent_layers(self, stream=None):
+        """What the last rasterised transparent pass in debug mode recorded: (counts uint32 [h, w] of the layers shaded,
+        layers [h, w, N] of the structured dtype of S.TransparentLayer, front to back)."""
+        w, h = getattr(self, "_raster_transparent_extent", (0, 0))
+        n = getattr(self, "_raster_transparent_layers", 0)
+        counts = np.empty((h, w), np.uint32)
+        layers = np.empty((h, w, n), np.dtype(S.TransparentLayer))
+        _check(lib().prosper_pt_read_raster_transparent_layers(self._h, counts.ctypes.data, layers.ctypes.data, w * h, n, C.c_void_p(stream)))
+        return counts, layers
 
     def read_raster_visibility(self, width, height, stream=None):
         """-> (ids uint32 [h, w, 3] of (drawInstanceIndex, meshletIndex, triangle), 0xFFFFFFFF where nothing is drawn;

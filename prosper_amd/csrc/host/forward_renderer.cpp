@@ -106,6 +106,29 @@ void ForwardRenderer::recordTransparent(
         throw std::runtime_error(std::string("ForwardRenderer::recordTransparent: ") + prosper_pt_last_error());
 }
 
+void ForwardRenderer::recordTransparentRaster(
+    const scene::Camera &cam, const TransparentInOut &t, const LightClusteringOutput *lightClusters, bool applyIbl, scene::DrawType drawType,
+    void *stream)
+{
+    PROSPER_ASSERT(m_initialized);
+    const prosper_CameraUniforms &u = cam.uniforms();
+    if (t.width != u.resolution[0] || t.height != u.resolution[1])
+        throw std::runtime_error("ForwardRenderer::recordTransparentRaster: the targets' extent is not the camera's resolution");
+    if (lightClusters && (lightClusters->width != t.width || lightClusters->height != t.height))
+        throw std::runtime_error("ForwardRenderer::recordTransparentRaster: the light clusters were built for another extent");
+
+    // ForwardRenderer.cpp:658-662
+    prosper_pt_forward_pc pc = {};
+    pc.drawType = static_cast<uint32_t>(drawType);
+    pc.ibl = applyIbl ? 1u : 0u;
+    m_lastPC = pc;
+
+    if (prosper_pt_set_texture_lod(m_ctx, m_textureLod ? 1 : 0, m_lodBias) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("ForwardRenderer::recordTransparentRaster: ") + prosper_pt_last_error());
+    if (prosper_pt_raster_forward_transparent(m_ctx, &pc, &u, t.depth, t.onDevice ? 1u : 0u, stream) != PROSPER_PT_OK)
+        throw std::runtime_error(std::string("ForwardRenderer::recordTransparentRaster: ") + prosper_pt_last_error());
+}
+
 } // namespace render
 
 // ---- plain-C shims (include/prosper_pt/prosper_host.h) ----
@@ -175,6 +198,41 @@ int prosper_host_forward_renderer_record_transparent(
         t.rayFlags = rayFlags;
         t.frameIndex = frameIndex;
         r->pass.recordTransparent(cam, t, nullptr, static_cast<scene::DrawType>(drawType), applyIbl != 0, stream);
+        if (outPushConstants) *outPushConstants = r->pass.lastPushConstants();
+    }
+    catch (const std::exception &e)
+    {
+        prosper_host_set_error(e.what());
+        return PROSPER_PT_ERR_HIP;
+    }
+    return PROSPER_PT_OK;
+}
+
+int prosper_host_forward_renderer_record_transparent_raster(
+    prosper_host_forward_renderer *r, prosper_host_camera *camera, uint32_t width, uint32_t height, const float *nonLinearDepth,
+    uint32_t onDevice, int applyIbl, uint32_t drawType, void *stream, prosper_pt_forward_pc *outPushConstants)
+{
+    if (!r || !camera)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_record_transparent_raster: null argument");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    if (drawType >= (uint32_t)scene::DrawType::Count)
+    {
+        prosper_host_set_error("prosper_host_forward_renderer_record_transparent_raster: drawType out of range");
+        return PROSPER_PT_ERR_INVALID_ARGUMENT;
+    }
+    try
+    {
+        scene::Camera &cam = *prosper_host_camera_object(camera);
+        cam.updateResolution(width, height);
+        cam.updateBuffer(); // App::drawFrame does this before Renderer::render (App.cpp:556)
+        render::ForwardRenderer::TransparentInOut t;
+        t.depth = nonLinearDepth;
+        t.onDevice = onDevice != 0u;
+        t.width = width;
+        t.height = height;
+        r->pass.recordTransparentRaster(cam, t, nullptr, applyIbl != 0, static_cast<scene::DrawType>(drawType), stream);
         if (outPushConstants) *outPushConstants = r->pass.lastPushConstants();
     }
     catch (const std::exception &e)

@@ -12,6 +12,8 @@
 //                      the context's HDR image.  prosper draws them with Options{transparents, drawType},
 //                      i.e. ibl = 0; `applyIbl` is there for the push constant's other value.  The culling it runs first is
 //                      render::MeshletCuller in Mode::Transparent (meshlet_culler.hpp).
+//   recordTransparentRaster  the same step of the raster frame: that culling and the draw of its list as one chain
+//                      (prosper_pt_raster_forward_transparent).
 #pragma once
 
 #include <cstdint>
@@ -74,6 +76,16 @@ class ForwardRenderer
     void recordTransparent(
         const scene::Camera &cam, const TransparentInOut &inOutTargets, const LightClusteringOutput *lightClusters,
         scene::DrawType drawType, bool applyIbl, void *stream);
+
+    // recordTransparent over the meshlet draw lists (ForwardRenderer.cpp:222-260): the TRANSPARENT list culled
+    // once without a pyramid, its fragments listed per pixel and resolved front to back over the illumination, through
+    // prosper_pt_raster_forward_transparent - the raster frame's transparents, where recordTransparent above is the traced
+    // frame's.  inOut.rayFlags and frameIndex are not read (the rasteriser's pixel is the camera's, jitter included); the
+    // extent must be the camera's resolution.  The call waits on the host once (for the lists' size).  Arguments and
+    // failures otherwise as recordTransparent.
+    void recordTransparentRaster(
+        const scene::Camera &cam, const TransparentInOut &inOutTargets, const LightClusteringOutput *lightClusters, bool applyIbl,
+        scene::DrawType drawType, void *stream);
 
     [[nodiscard]] prosper_pt_ctx *context() const { return m_ctx; }
     [[nodiscard]] const prosper_pt_forward_pc &lastPushConstants() const { return m_lastPC; }

@@ -972,6 +972,46 @@ void launch_deferred_shading_ibl(
 // arithmetic prosper's blend state applied back to front.  No layer cap, no memory beyond the traversal stack.
 // ------------------------------------------------------------------------------------------
 
+// What the forward passes keep of a layer (prosper_pt_read_transparent_layers, prosper_pt_read_forward_surfaces,
+// prosper_pt_read_raster_transparent_layers): one copy for the three kernels
+PPT_D void store_layer_record(prosper_pt_transparent_layer *out, const Hit &hit, const Surface &sf, float depth)
+{
+    const f3 q = sf.positionWS;
+    prosper_pt_transparent_layer L;
+    L.drawInstance = hit.drawInstance;
+    L.primitive = hit.primitive;
+    L.positionWS[0] = q.x; L.positionWS[1] = q.y; L.positionWS[2] = q.z;
+    L.nonLinearDepth = depth;
+    L.albedo[0] = sf.material.albedo.x; L.albedo[1] = sf.material.albedo.y; L.albedo[2] = sf.material.albedo.z;
+    L.roughness = sf.material.roughness;
+    L.normal[0] = sf.normalWS.x; L.normal[1] = sf.normalWS.y; L.normal[2] = sf.normalWS.z;
+    L.metallic = sf.material.metallic;
+    L.alpha = sf.material.alpha;
+    L.reserved = 0u;
+    *out = L;
+}
+
+// forward.frag:69-83 for a layer whose view vector is set: the clustered lights (and evalIBL) at its own camera-space z
+// (forward.mesh:75: the third component of worldToCamera * (position, 1)), and the source alpha in *a
+template <bool IBL>
+PPT_D f3 shade_forward_layer(
+    const DeviceScene &s, const Surface &sf, uint32_t px, uint32_t py, const float *w, const ClusterGrid &grid, const uint2 *__restrict__ pointers,
+    const uint16_t *__restrict__ indices, const IblMaps *ibl, float *a)
+{
+    const f3 q = sf.positionWS;
+    const float zCam = __builtin_fmaf(w[10], q.z, __builtin_fmaf(w[6], q.y, __builtin_fmaf(w[2], q.x, w[14])));
+    const f3 src = shade_clustered<IBL>(s, sf, px, py, zCam, grid, pointers, indices, ibl);
+    *a = sf.material.alpha > 0.0f ? sf.material.alpha : 1.0f; // forward.frag:83
+    return src;
+}
+
+// One step of the front-to-back blend: C += T a src, T *= 1 - a
+PPT_D void blend_layer_under(f3 &C, float &T, f3 src, float a)
+{
+    C = C + src * (T * a);
+    T = T * (1.0f - a);
+}
+
 // kLayers: the debug mode of prosper_pt_read_transparent_layers - the first p.debugLayers layers of a pixel are kept
 // kLod (prosper_pt_set_texture_lod): every peeled layer samples its material through the mip chains, with
 // the uv forward differences of gbuffer_trace_kernel<.., .., true> - the same two neighbour rays for all layers of the
@@ -1066,21 +1106,7 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
             sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
             if constexpr (kLayers)
             {
-                if (count < p.debugLayers)
-                {
-                    prosper_pt_transparent_layer L;
-                    L.drawInstance = hit.drawInstance;
-                    L.primitive = hit.primitive;
-                    L.positionWS[0] = q.x; L.positionWS[1] = q.y; L.positionWS[2] = q.z;
-                    L.nonLinearDepth = depth;
-                    L.albedo[0] = sf.material.albedo.x; L.albedo[1] = sf.material.albedo.y; L.albedo[2] = sf.material.albedo.z;
-                    L.roughness = sf.material.roughness;
-                    L.normal[0] = sf.normalWS.x; L.normal[1] = sf.normalWS.y; L.normal[2] = sf.normalWS.z;
-                    L.metallic = sf.material.metallic;
-                    L.alpha = sf.material.alpha;
-                    L.reserved = 0u;
-                    layers[i * p.debugLayers + count] = L;
-                }
+                if (count < p.debugLayers) store_layer_record(layers + (i * p.debugLayers + count), hit, sf, depth);
             }
             f3 src;
             float a;
@@ -1090,17 +1116,10 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
                 a = 1.0f;
             }
             else
-            {
-                // forward.mesh:75: the third component of worldToCamera * (position, 1)
-                const float *w = p.worldToCamera;
-                const float zCam = __builtin_fmaf(w[10], q.z, __builtin_fmaf(w[6], q.y, __builtin_fmaf(w[2], q.x, w[14])));
-                src = shade_clustered<IBL>(s, sf, px, py, zCam, grid, pointers, indices, &ibl);
-                a = sf.material.alpha > 0.0f ? sf.material.alpha : 1.0f; // forward.frag:83
-            }
+                src = shade_forward_layer<IBL>(s, sf, px, py, p.worldToCamera, grid, pointers, indices, &ibl, &a);
             if (count == 0) nearestAlpha = a;
             ++count;
-            C = C + src * (T * a);
-            T = T * (1.0f - a);
+            blend_layer_under(C, T, src, a);
         }
         if constexpr (kLayers) layerCounts[i] = count;
         if (count > 0)
@@ -1212,21 +1231,7 @@ __global__ __launch_bounds__(256) void forward_opaque_kernel(
             const float depth = u2f((uint32_t)(key >> 32));
             nonLinearDepth[i] = depth;
             const f3 q = sf.positionWS;
-            if constexpr (kSurfaces)
-            {
-                prosper_pt_transparent_layer L;
-                L.drawInstance = hit.drawInstance;
-                L.primitive = hit.primitive;
-                L.positionWS[0] = q.x; L.positionWS[1] = q.y; L.positionWS[2] = q.z;
-                L.nonLinearDepth = depth;
-                L.albedo[0] = sf.material.albedo.x; L.albedo[1] = sf.material.albedo.y; L.albedo[2] = sf.material.albedo.z;
-                L.roughness = sf.material.roughness;
-                L.normal[0] = sf.normalWS.x; L.normal[1] = sf.normalWS.y; L.normal[2] = sf.normalWS.z;
-                L.metallic = sf.material.metallic;
-                L.alpha = sf.material.alpha;
-                L.reserved = 0u;
-                surfaces[i] = L;
-            }
+            if constexpr (kSurfaces) store_layer_record(surfaces + i, hit, sf, depth);
             if (g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID || g.drawType == PROSPER_DRAW_TYPE_PRIMITIVE_ID)
             {
                 // forward.frag:99-107 over forward.mesh:144
@@ -1243,11 +1248,8 @@ __global__ __launch_bounds__(256) void forward_opaque_kernel(
                 // forward.frag:52,67
                 sf.invViewRayWS = normalize(f3{g.r.eye[0], g.r.eye[1], g.r.eye[2]} - q);
                 sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
-                // forward.mesh:75: the third component of worldToCamera * (position, 1)
-                const float *w = v.worldToCamera;
-                const float zCam = __builtin_fmaf(w[10], q.z, __builtin_fmaf(w[6], q.y, __builtin_fmaf(w[2], q.x, w[14])));
-                const f3 color = shade_clustered<IBL>(s, sf, px, py, zCam, grid, pointers, indices, &ibl);
-                const float a = sf.material.alpha > 0.0f ? sf.material.alpha : 1.0f; // forward.frag:83,118
+                float a; // forward.frag:83,118
+                const f3 color = shade_forward_layer<IBL>(s, sf, px, py, v.worldToCamera, grid, pointers, indices, &ibl, &a);
                 hdr[i] = make_float4(color.x, color.y, color.z, a);
             }
         }
@@ -1281,5 +1283,130 @@ void launch_forward_opaque(
                             : (debug ? forward_opaque_kernel<false, false, true> : forward_opaque_kernel<false, false, false>);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, GBufferNoLod{});
 }
+
+// ------------------------------------------------------------------------------------------
+// Rasterised transparent pass (ForwardRenderer::recordTransparent over the meshlet draw lists): the resolve
+// of the per-pixel fragment lists the raster kernels filled (pt_raster.hip).  One lane per pixel on forward_opaque_kernel's
+// mapping, for its reason.  Front to back the lane SELECTS the greatest key of its list below the previous one - over
+// global memory, no per-lane array, O(n^2) in the layers of one pixel - rebuilds the layer's surface as forward_opaque_kernel
+// rebuilds the winner's, shades it and blends it under what is nearer with forward_transparent_kernel's own arithmetic.
+// A pixel without a list keeps its four floats.  kLayers: the first t.debugLayers shaded layers of a pixel are kept.
+// stats: kForwardCountSlots sets a cache line apart of { pixels with a list, layers shaded, the longest list }.
+// ------------------------------------------------------------------------------------------
+template <bool IBL, bool kLod, bool kLayers>
+__global__ __launch_bounds__(256) void raster_transparent_kernel(
+    DeviceScene s, GBufferTraceParams g, RasterResolveTables r, RasterLayerLists t, GBufferVelocityParams v, ClusterGrid grid,
+    const uint2 *__restrict__ pointers, const uint16_t *__restrict__ indices, float4 *__restrict__ hdr, uint32_t *__restrict__ stats,
+    uint32_t debugLayers, uint32_t *__restrict__ layerCounts, prosper_pt_transparent_layer *__restrict__ layers, IblMaps ibl,
+    std::conditional_t<kLod, GBufferLodParams, GBufferNoLod> lodp)
+{
+    uint32_t px, py;
+    if (!restir_pixel(g.r.width, g.r.height, px, py)) return;
+    uint32_t n = 0, shaded = 0;
+    if (px < g.r.width && py < g.r.height)
+    {
+        const size_t i = (size_t)py * g.r.width + px;
+        n = t.counts[i];
+        const uint32_t first = t.offsets[i];
+        // (a list never leaves the buffer: the scan's total bounds offset + count)
+        if (first > t.total || n > t.total - first) n = 0u;
+        if (n != 0u)
+        {
+            const unsigned long long *list = t.fragments + first;
+            const Ray ray = raster_pixel_ray(g.r, v.currentJitter, px, py);
+            const f3 eye = f3{g.r.eye[0], g.r.eye[1], g.r.eye[2]};
+            f3 C = f3{0.0f, 0.0f, 0.0f};
+            float T = 1.0f, nearestAlpha = 0.0f;
+            unsigned long long previous = ~0ull; // (above every key: a depth is at most 1)
+            for (uint32_t k = 0; k < n && T != 0.0f; ++k)
+            {
+                unsigned long long key = 0ull;
+                for (uint32_t j = 0; j < n; ++j)
+                {
+                    const unsigned long long c = list[j];
+                    if (c < previous && c > key) key = c;
+                }
+                if (key == 0ull) break; // (keys of one pixel are unique: never taken before k == n)
+                previous = key;
+                uint32_t di = 0, mi = 0, local = 0, prim = 0;
+                if (!raster_decode_key(s, r, key, di, mi, local, prim)) continue;
+                const Hit hit = raster_hit(s, ray, di, prim);
+                Surface sf;
+                if constexpr (kLod)
+                    sf = raster_pixel_surface<true>(s, g.r, v.currentJitter, lodp.mips, lodp.bias, px, py, ray, hit, nullptr);
+                else
+                    sf = raster_pixel_surface<false>(s, g.r, v.currentJitter, nullptr, 0.0f, px, py, ray, hit, nullptr);
+                // forward.frag:52,67
+                sf.invViewRayWS = normalize(eye - sf.positionWS);
+                sf.NoV = saturate(dot(sf.normalWS, sf.invViewRayWS));
+                if constexpr (kLayers)
+                    if (shaded < debugLayers) store_layer_record(layers + (i * debugLayers + shaded), hit, sf, u2f((uint32_t)(key >> 32)));
+                f3 src;
+                float a = 1.0f;
+                if (g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID || g.drawType == PROSPER_DRAW_TYPE_PRIMITIVE_ID)
+                    src = uint_to_color(g.drawType == PROSPER_DRAW_TYPE_MESHLET_ID ? mi : local); // forward.frag:99-107 over forward.mesh:144
+                else if (g.drawType != PROSPER_DRAW_TYPE_DEFAULT)
+                    src = debug_color(s, g.drawType, hit, sf);
+                else
+                    src = shade_forward_layer<IBL>(s, sf, px, py, v.worldToCamera, grid, pointers, indices, &ibl, &a);
+                if (shaded == 0u) nearestAlpha = a;
+                ++shaded;
+                blend_layer_under(C, T, src, a);
+            }
+            if (shaded > 0u)
+            {
+                const float4 dst = hdr[i];
+                // VkUtils.hpp:93-106, as forward_transparent_kernel ends
+                hdr[i] = make_float4(C.x + dst.x * T, C.y + dst.y * T, C.z + dst.z * T, nearestAlpha * (1.0f - nearestAlpha));
+            }
+        }
+        if constexpr (kLayers) layerCounts[i] = shaded;
+    }
+    // prosper_pt_get_raster_transparent_info: one set of atomics per wave, dealt over kForwardCountSlots sets a cache line apart
+    const uint64_t listed = __ballot(n != 0u);
+    if (listed != 0ull)
+    {
+        uint32_t sum = shaded, deepest = n;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            sum += __shfl_xor(sum, off, 64);
+            const uint32_t o = __shfl_xor(deepest, off, 64);
+            deepest = o > deepest ? o : deepest;
+        }
+        if ((threadIdx.x & 63u) == 0u)
+        {
+            uint32_t *slot = stats + (blockIdx.x % kForwardCountSlots) * kForwardCountStride;
+            atomicAdd(slot + 0, (uint32_t)__popcll(listed));
+            atomicAdd(slot + 1, sum);
+            atomicMax(slot + 2, deepest);
+        }
+    }
+}
+
+void launch_raster_transparent(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const RasterLayerLists &t, const GBufferVelocityParams &v,
+    const ClusterParams &c, const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut,
+    float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
+    const GBufferLodParams *lod)
+{
+    if (g.r.width == 0 || g.r.height == 0) return;
+    const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
+    const ClusterGrid cg{c.near_, c.far_, c.dimX, c.dimY};
+    const IblMaps maps = {irradiance, radiance, lut};
+    const uint2 *ptrs = static_cast<const uint2 *>(pointers);
+    const bool ibl = irradiance != nullptr, debug = debugLayers != 0u;
+    if (lod)
+    {
+        const auto kernel = ibl ? (debug ? raster_transparent_kernel<true, true, true> : raster_transparent_kernel<true, true, false>)
+                                : (debug ? raster_transparent_kernel<false, true, true> : raster_transparent_kernel<false, true, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, indices, hdr, stats, debugLayers, layerCounts, layers, maps, *lod);
+        return;
+    }
+    const auto kernel = ibl ? (debug ? raster_transparent_kernel<true, false, true> : raster_transparent_kernel<true, false, false>)
+                            : (debug ? raster_transparent_kernel<false, false, true> : raster_transparent_kernel<false, false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, indices, hdr, stats, debugLayers, layerCounts, layers, maps, GBufferNoLod{});
+}
+
 
 } // namespace ppt

@@ -129,6 +129,17 @@ void launch_forward_opaque(
     const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusterParams &c,
     const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr,
     float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream, const GBufferLodParams *lod = nullptr);
+// The rasterised transparent pass's resolve (raster_transparent_kernel) in place over `hdr`: the per-pixel
+// fragment lists `t` (pt_raster.hpp) selected front to back, every layer shaded as launch_forward_opaque shades a winner and
+// blended as launch_forward_transparent blends.  g, r, v (its velocity is not used), c, the lists and the maps as for
+// launch_forward_opaque.  stats: kForwardCountSlots sets, kForwardCountStride uint32 apart, of { pixels with a list, layers
+// shaded, the longest list }, which the caller zeroed.  debugLayers != 0: layerCounts[pixel] = the layers shaded, and the
+// first debugLayers of them are written to layers[pixel * debugLayers ..].
+void launch_raster_transparent(
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const RasterLayerLists &t, const GBufferVelocityParams &v,
+    const ClusterParams &c, const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut,
+    float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
+    const GBufferLodParams *lod = nullptr);
 // Image-based lighting (ImageBasedLighting / evalIBL).  Every cube is stored with a one-texel seamless border, as the
 // sky is: 6 faces of (n + 2)^2 RGBA16F texels.  Radiance mip m (size kIblRadianceSize >> m) starts
 // ibl_radiance_offset(m) RGBA texels into its buffer; the LUT is kIblLutSize^2 R16G16 UNORM, row = roughness.

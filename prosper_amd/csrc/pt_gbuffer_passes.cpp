@@ -1,6 +1,7 @@
 // pt_gbuffer_passes.cpp — C-ABI of the passes over a G-buffer (include/prosper_pt/prosper_pt.h): ReSTIR-DI
 // (prosper_pt_restir_di_*), the ray-traced G-buffer (prosper_pt_trace_gbuffer), clustered lighting and deferred shading
-// (prosper_pt_cluster_lights, prosper_pt_deferred_shading) and image-based lighting (prosper_pt_generate_ibl), with the
+// (prosper_pt_cluster_lights, prosper_pt_deferred_shading), image-based lighting (prosper_pt_generate_ibl) and the forward
+// passes (prosper_pt_forward_transparent, prosper_pt_raster_forward, prosper_pt_raster_forward_transparent), with the
 // readbacks of what each produced.  Kernels: pt_gbuffer_kernels.hip, pt_ibl.hip.
 #include "../../include/prosper_pt/prosper_pt.h"
 
@@ -73,6 +74,18 @@ struct GBufferPassState
     bool forwardDebugSurfaces = false; // prosper_pt_set_forward_debug_surfaces
     bool forwardRan = false, forwardReclustered = false;
     size_t forwardSurfacePixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
+    // prosper_pt_raster_transparent_draw / prosper_pt_raster_forward_transparent
+    DeviceBuffer rasterTransparentDepth;  // device copy of a call's host depth
+    DeviceBuffer rasterTransparentStats;  // kForwardCountSlots sets a cache line apart: pixels with a list, layers shaded, longest list
+    DeviceBuffer rasterTransparentLayers; // debug mode: width*height counts, then width*height*N layer records
+    Pinned<uint32_t> rasterTransparentStatsHost;
+    StageEvents<4> rasterTransparentTiming; // count | scan | fill | resolve (its clustering included)
+    Fence rasterTransparentDone;            // behind the last call's copy of the stats
+    uint32_t rasterTransparentDebugLayers = 0; // prosper_pt_set_raster_transparent_debug_layers
+    uint32_t rasterTransparentFragments = 0;
+    bool rasterTransparentRan = false, rasterTransparentReclustered = false;
+    size_t rasterTransparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
+    uint32_t rasterTransparentLayerCount = 0;
 };
 
 void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias)
@@ -810,6 +823,188 @@ int prosper_pt_raster_forward(
     const int rc = prosper_pt_raster_visibility(ctx, camera, stream);
     if (rc != PROSPER_PT_OK) return rc;
     return forward_shade(what, ctx, pc, camera, desc, stream);
+}
+
+// ---- rasterised transparent pass (ForwardRenderer::recordTransparent over the draw lists) ----
+
+// What both entries refuse, before anything is enqueued (and, for prosper_pt_raster_forward_transparent, before the culling
+// phase replaces the lists): the draw's refusals, prosper_pt_forward_transparent's for pc, ibl, the camera and the depth
+// argument, and an HDR image or a depth of another extent than camera->resolution.  *depth: the device depth to test
+// against, nullptr where a host depth has to be copied first.
+static int check_raster_transparent(
+    const char *what, prosper_pt_ctx *ctx, uint32_t which, bool listNeeded, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera,
+    const float *nonLinearDepth, uint32_t onDevice, const float **depth)
+{
+    // the arguments are checked before the context, so that every refusal happens without a GPU
+    if (which != PROSPER_PT_DRAW_LIST_GENERATED && which != PROSPER_PT_DRAW_LIST_FIRST_PHASE && which != PROSPER_PT_DRAW_LIST_SECOND_PHASE)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the list is GENERATED, FIRST_PHASE or SECOND_PHASE");
+    if (!pc || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
+    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
+    if (reinterpret_cast<uintptr_t>(nonLinearDepth) & 3u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the depth must be 4-byte aligned");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (const int rc = raster_layers_check(ctx, what, which, listNeeded, camera)) return rc;
+    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
+    if (!hdr_has_extent(ctx, width, height))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the HDR image's extent is not camera->resolution");
+    *depth = onDevice ? nonLinearDepth : nullptr;
+    if (!nonLinearDepth)
+    {
+        uint32_t w = 0, h = 0;
+        if (const int rc = gbuffer_last_depth(ctx, depth, &w, &h)) return rc;
+        if (w != width || h != height)
+            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the context's last depth has another extent than camera->resolution");
+    }
+    return PROSPER_PT_OK;
+}
+
+static int raster_transparent(
+    const char *what, prosper_pt_ctx *ctx, uint32_t which, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera,
+    const float *nonLinearDepth, uint32_t onDevice, void *stream)
+{
+    const float *depth = nullptr;
+    if (const int rc = check_raster_transparent(what, ctx, which, true, pc, camera, nonLinearDepth, onDevice, &depth)) return rc;
+    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
+    const size_t pixels = (size_t)width * height;
+    GBufferPassState &st = *ctx->gbufferPasses;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipSetDevice(ctx->device));
+    int rc = flush_scene_updates(ctx, s, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    if ((rc = st.rasterTransparentDone.wait(s)) != PROSPER_PT_OK) return rc; // (a call on another stream may still copy the stats)
+    if (!depth)
+    {
+        if ((rc = grow_to(st.rasterTransparentDepth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
+        PPT_HIP(hipMemcpyAsync(st.rasterTransparentDepth.ptr, nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
+        depth = st.rasterTransparentDepth.as<float>();
+    }
+    if ((rc = grow_to(st.rasterTransparentStats, kForwardCountBytes, s)) != PROSPER_PT_OK) return rc;
+    if (!st.rasterTransparentStatsHost.ptr && (rc = st.rasterTransparentStatsHost.allocate(kForwardCountBytes)) != PROSPER_PT_OK) return rc;
+    const uint32_t debugLayers = st.rasterTransparentDebugLayers;
+    if (debugLayers &&
+        (rc = grow_to(st.rasterTransparentLayers, pixels * (4u + (size_t)debugLayers * sizeof(prosper_pt_transparent_layer)), s)) != PROSPER_PT_OK)
+        return rc;
+    if ((rc = st.rasterTransparentTiming.create()) != PROSPER_PT_OK) return rc;
+    st.rasterTransparentRan = false;
+    st.rasterTransparentLayerPixels = 0;
+
+    RasterLayerLists lists = {};
+    RasterResolveTables tables = {};
+    if ((rc = raster_layers_build(ctx, what, which, camera, depth, s, st.rasterTransparentTiming.events, &lists, &tables)) != PROSPER_PT_OK) return rc;
+    bool reuse = true;
+    PPT_HIP(hipMemsetAsync(st.rasterTransparentStats.ptr, 0, kForwardCountBytes, s));
+    uint32_t *counts = debugLayers ? st.rasterTransparentLayers.as<uint32_t>() : nullptr;
+    if (lists.total != 0u)
+    {
+        const ClusterParams c = cluster_params(camera, width, height);
+        if ((rc = cluster_lights_unless_current(ctx, c, s, &reuse)) != PROSPER_PT_OK) return rc;
+        GBufferVelocityParams v = {};
+        velocity_camera_terms(v, camera);
+        const GBufferTraceParams g = gbuffer_trace_params(pc->drawType, 0u, false, false, camera, width, height);
+        const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
+        const bool ibl = pc->ibl == 1u;
+        launch_raster_transparent(
+            ctx->scene, g, tables, lists, v, c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
+            ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, st.rasterTransparentStats.as<uint32_t>(),
+            debugLayers, counts, debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s,
+            st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
+        PPT_HIP(hipGetLastError());
+    }
+    else if (debugLayers)
+        PPT_HIP(hipMemsetAsync(counts, 0, pixels * 4u, s)); // (no list anywhere: every pixel has 0 layers)
+    PPT_HIP(hipEventRecord(st.rasterTransparentTiming.events[4], s));
+    PPT_HIP(hipMemcpyAsync(st.rasterTransparentStatsHost.ptr, st.rasterTransparentStats.ptr, kForwardCountBytes, hipMemcpyDeviceToHost, s));
+    if ((rc = st.rasterTransparentDone.record(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = raster_resolve_enqueued(ctx, s)) != PROSPER_PT_OK) return rc;
+    st.rasterTransparentRan = true;
+    st.rasterTransparentReclustered = !reuse;
+    st.rasterTransparentFragments = lists.total;
+    st.rasterTransparentLayerPixels = debugLayers ? pixels : 0u;
+    st.rasterTransparentLayerCount = debugLayers;
+    return mark_versions_read(ctx, s);
+}
+
+int prosper_pt_raster_transparent_draw(
+    prosper_pt_ctx *ctx, uint32_t which, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth,
+    uint32_t onDevice, void *stream)
+{
+    return raster_transparent("prosper_pt_raster_transparent_draw", ctx, which, pc, camera, nonLinearDepth, onDevice, stream);
+}
+
+int prosper_pt_raster_forward_transparent(
+    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth, uint32_t onDevice,
+    void *stream)
+{
+    const char *what = "prosper_pt_raster_forward_transparent";
+    // what the draw would refuse of its arguments is refused before the culling phase replaces the lists
+    const float *depth = nullptr;
+    if (const int rc = check_raster_transparent(what, ctx, PROSPER_PT_DRAW_LIST_FIRST_PHASE, false, pc, camera, nonLinearDepth, onDevice, &depth)) return rc;
+    // ForwardRenderer.cpp:222-260: the TRANSPARENT list culled once, without a pyramid and without a second phase
+    const int rc = prosper_pt_cull_meshlets_first_phase(ctx, PROSPER_PT_CULL_MODE_TRANSPARENT, camera, PROSPER_PT_NO_HIZ, stream);
+    if (rc != PROSPER_PT_OK) return rc;
+    return raster_transparent(what, ctx, PROSPER_PT_DRAW_LIST_FIRST_PHASE, pc, camera, nonLinearDepth, onDevice, stream);
+}
+
+int prosper_pt_get_raster_transparent_info(prosper_pt_ctx *ctx, prosper_pt_raster_transparent_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_raster_transparent_info: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.rasterTransparentRan) return fail(PROSPER_PT_ERR_NO_SCENE, "the rasterised transparent pass has not run yet");
+    PPT_HIP(hipSetDevice(ctx->device));
+    prosper_pt_raster_transparent_info info = {};
+    info.fragments = st.rasterTransparentFragments; // (the host read it between scan and fill)
+    info.reclustered = st.rasterTransparentReclustered ? 1u : 0u;
+    *out = info;
+    if (!st.rasterTransparentDone.passed()) return PROSPER_PT_NOT_READY;
+    for (uint32_t k = 0; k < kForwardCountSlots; ++k)
+    {
+        const uint32_t *slot = st.rasterTransparentStatsHost.ptr + k * kForwardCountStride;
+        info.coveredPixels += slot[0];
+        info.shadedLayers += slot[1];
+        info.maxLayers = slot[2] > info.maxLayers ? slot[2] : info.maxLayers;
+    }
+    float ms[4] = {};
+    if (const int rc = st.rasterTransparentTiming.elapsed(ms)) return rc; // (behind the fence that has passed: no wait)
+    info.countMs = ms[0];
+    info.scanMs = ms[1];
+    info.fillMs = ms[2];
+    info.resolveMs = ms[3];
+    *out = info;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_set_raster_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_raster_transparent_debug_layers: null argument");
+    if (layersPerPixel > 128u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_raster_transparent_debug_layers: at most 128 layers per pixel");
+    ctx->gbufferPasses->rasterTransparentDebugLayers = layersPerPixel;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_raster_transparent_layers(
+    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels, uint32_t layersPerPixel, void *stream)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_transparent_layers: null argument");
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    if (!st.rasterTransparentRan || !st.rasterTransparentLayerPixels)
+        return fail(PROSPER_PT_ERR_NO_SCENE, "the last rasterised transparent pass did not run in debug mode (prosper_pt_set_raster_transparent_debug_layers)");
+    if (pixels != st.rasterTransparentLayerPixels || layersPerPixel != st.rasterTransparentLayerCount)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_transparent_layers: pixels or layersPerPixel differ from the call's");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = st.rasterTransparentDone.wait(s)) return rc;
+    const uint32_t *counts = st.rasterTransparentLayers.as<uint32_t>();
+    if (host_counts) PPT_HIP(hipMemcpyAsync(host_counts, counts, pixels * 4u, hipMemcpyDeviceToHost, s));
+    if (host_layers)
+        PPT_HIP(hipMemcpyAsync(host_layers, counts + pixels, pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_set_forward_debug_surfaces(prosper_pt_ctx *ctx, int enabled)

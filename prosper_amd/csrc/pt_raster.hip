@@ -13,10 +13,16 @@
 //                           in float32 over a polygon in the lane's slice of LDS -, the box against the tile) and walks the
 //                           part of each record that reaches its tile; the fan's triangles take the common rule.
 //   raster_depth_kernel     key -> depth, for the pyramid between the culling phases
+//   raster_layers_*_kernel  the two kernels above instantiated for the transparent pass's per-pixel lists:
+//                           a fragment that is a layer candidate is counted (kFill false) or its key stored (kFill true)
+//   raster_scan_*_kernel    the exclusive scan of the per-pixel counts between the two: a wave per 1024 counters, the wave's
+//                           scan by DPP row shifts and row broadcasts
 //
 // A fragment is one 64-bit atomicMax on (depth bits, ~(ordinal * 128 + triangle)): the greatest depth wins (reverse Z),
 // among equal depths the lowest ordinal, whatever order the waves ran in.
 #include "pt_raster.hpp"
+
+#include <type_traits>
 
 #include "pt_math.hpp"
 #include "pt_raster_surface.hpp"
@@ -204,7 +210,29 @@ template <bool kLod> PPT_RS bool alpha_discards(const RasterParams &p, int32_t p
     return sf.material.alpha == 0.0f;
 }
 
-PPT_RS bool load_meshlet(const RasterParams &p, uint32_t entry, Meshlet *out)
+// What a raster pass does with its fragments: the visibility image's atomicMax, or the transparent lists' two passes
+// (plain ints, not an unnamed enum: the mode is part of the kernels' mangled names, which host and device must agree on)
+constexpr int kModeVisibility = 0, kModeLayerCount = 1, kModeLayerFill = 2;
+
+// A fragment of the transparent lists: eGreater against the stored depth (a coplanar fragment fails, a stored 0 passes
+// everything, a NaN nothing), then forward.frag:57's discard, then the count or the key.  One function for both passes.
+template <int kMode, bool kLod>
+PPT_RS void layer_fragment(const RasterParams &p, const RasterLayerTargets &L, int32_t px, int32_t py, float depth, uint32_t low, uint32_t di, uint32_t prim)
+{
+    const size_t pixel = (size_t)py * p.view.width + (size_t)px;
+    if (!(depth > L.depth[pixel])) return;
+    if (alpha_discards<kLod>(p, px, py, di, prim)) return;
+    if constexpr (kMode == kModeLayerCount)
+        atomicAdd(L.counts + pixel, 1u);
+    else
+    {
+        const uint32_t at = L.offsets[pixel] + atomicAdd(L.cursor + pixel, 1u);
+        if (at < L.capacity) L.fragments[at] = ((unsigned long long)f2u(depth) << 32) | (unsigned long long)low;
+    }
+}
+
+// kAll: every meshlet's fragments are tested against the material (the transparent lists), not only a MASK meshlet's
+template <bool kAll = false> PPT_RS bool load_meshlet(const RasterParams &p, uint32_t entry, Meshlet *out)
 {
     const uint32_t di = p.list[1u + 2u * entry], mi = p.list[2u + 2u * entry];
     if (di >= p.drawInstanceCount) return false;
@@ -225,7 +253,10 @@ PPT_RS bool load_meshlet(const RasterParams &p, uint32_t entry, Meshlet *out)
     m.ordinal = p.meshletBase[di] + mi;
     m.drawInstance = di;
     m.mask = 0u, m.mapStart = 0u, m.mapCount = 0u;
-    if (p.anyMask && inst.materialIndex < p.scene.materialCount && p.scene.materials[inst.materialIndex].alphaMode == PROSPER_ALPHA_MODE_MASK)
+    bool tested = true;
+    if constexpr (!kAll)
+        tested = p.anyMask && inst.materialIndex < p.scene.materialCount && p.scene.materials[inst.materialIndex].alphaMode == PROSPER_ALPHA_MODE_MASK;
+    if (tested)
     {
         const uint32_t gm = p.meshMeshletBase[inst.meshIndex] + mi; // (mi is below the mesh's meshlet count: the map has it)
         m.mask = 1u;
@@ -278,14 +309,24 @@ enum : uint32_t
     kClassQueue = 3,
 };
 
-template <bool kMask, bool kLod> __global__ __launch_bounds__(256) void raster_meshlets_kernel(const RasterParams p)
+// kMode: what becomes of a fragment.  The layer modes test every meshlet's fragments against the material (kMask), in the
+// wave's walk, and count nothing.
+struct RasterNoLayers
 {
+};
+template <int kMode> using LayerTargetsOf = std::conditional_t<kMode != kModeVisibility, RasterLayerTargets, RasterNoLayers>;
+
+template <bool kMask, bool kLod, int kMode = kModeVisibility>
+__global__ __launch_bounds__(256) void raster_meshlets_kernel(const RasterParams p, const LayerTargetsOf<kMode> L)
+{
+    constexpr bool kLayers = kMode != kModeVisibility;
+    static_assert(kMask || !kLayers, "the layer modes test every fragment");
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t entry = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t count = p.list[0] < p.capacity ? p.list[0] : p.capacity;
     if (entry >= count) return; // (the whole wave)
     Meshlet m;
-    if (!load_meshlet(p, entry, &m)) return; // (the whole wave: every lane reads the same entry)
+    if (!load_meshlet<kLayers>(p, entry, &m)) return; // (the whole wave: every lane reads the same entry)
 
     // ---- a lane per vertex ----
     int32_t vX = 0, vY = 0;
@@ -354,23 +395,27 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(256) void raster_m
         }
         if constexpr (kMask)
             if (m.mask && cls == kClassSmall) cls = kClassMedium; // (one place tests the material: the wave's walk)
-        count_ballot(&p.counters->triangles, live, lane);
-        count_ballot(&p.counters->culledBackface, back, lane);
-        count_ballot(&p.counters->culledZeroArea, zero, lane);
-        count_ballot(&p.counters->culledOutside, outside, lane);
-
-        if (cls == kClassSmall)
+        if constexpr (!kLayers)
         {
-            const uint32_t low = ~(lowBase + t);
-            for (int32_t py = tri.py0; py <= tri.py1; ++py)
-                for (int32_t px = tri.px0; px <= tri.px1; ++px)
-                {
-                    float depth;
-                    if (!covers(tri, area2, px, py, &depth)) continue;
-                    ++fragments;
-                    emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, low);
-                }
+            count_ballot(&p.counters->triangles, live, lane);
+            count_ballot(&p.counters->culledBackface, back, lane);
+            count_ballot(&p.counters->culledZeroArea, zero, lane);
+            count_ballot(&p.counters->culledOutside, outside, lane);
         }
+
+        if constexpr (!kLayers) // (a layer mode has no small class: m.mask)
+            if (cls == kClassSmall)
+            {
+                const uint32_t low = ~(lowBase + t);
+                for (int32_t py = tri.py0; py <= tri.py1; ++py)
+                    for (int32_t px = tri.px0; px <= tri.px1; ++px)
+                    {
+                        float depth;
+                        if (!covers(tri, area2, px, py, &depth)) continue;
+                        ++fragments;
+                        emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, low);
+                    }
+            }
         // medium: one triangle at a time, the wave over its box in blocks of 8 x 8 pixels
         unsigned long long medium = __ballot(cls == kClassMedium);
         while (medium != 0ull) // (the same in every lane)
@@ -392,10 +437,15 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(256) void raster_m
                     const int32_t px = bx + (int32_t)(lane & 7u), py = by + (int32_t)(lane >> 3);
                     float depth;
                     if (px > w.px1 || py > w.py1 || !covers(w, a2, px, py, &depth)) continue;
-                    if constexpr (kMask)
-                        if (m.mask && alpha_discards<kLod>(p, px, py, m.drawInstance, wprim)) continue;
-                    ++fragments;
-                    emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, low);
+                    if constexpr (kLayers)
+                        layer_fragment<kMode, kLod>(p, L, px, py, depth, low, m.drawInstance, wprim);
+                    else
+                    {
+                        if constexpr (kMask)
+                            if (m.mask && alpha_discards<kLod>(p, px, py, m.drawInstance, wprim)) continue;
+                        ++fragments;
+                        emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, low);
+                    }
                 }
         }
         // large, and what has to be clipped: the queue
@@ -415,14 +465,21 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(256) void raster_m
                     p.queue[2u + 2u * at] = entry;
                     p.queue[3u + 2u * at] = t;
                 }
-                count_ballot(&p.counters->queued, queued && room, lane);
-                count_ballot(&p.counters->queueOverflow, queued && !room, lane);
+                if constexpr (!kLayers)
+                {
+                    count_ballot(&p.counters->queued, queued && room, lane);
+                    count_ballot(&p.counters->queueOverflow, queued && !room, lane);
+                }
             }
         }
     }
-    fragments = wave_sum(fragments);
-    if (lane == 0u && fragments != 0u) atomicAdd(&p.counters->fragments, fragments);
+    if constexpr (!kLayers)
+    {
+        fragments = wave_sum(fragments);
+        if (lane == 0u && fragments != 0u) atomicAdd(&p.counters->fragments, fragments);
+    }
 }
+
 
 // Sutherland-Hodgman over the six planes, in float32, by the record's lane: the polygon ping-pongs between poly[0] and poly[1]
 // (LDS, so that the running index costs no private memory).  A crossing is cut from the inside vertex towards the outside
@@ -463,8 +520,10 @@ PPT_RS uint32_t clip_polygon(ClipV (*poly)[kPolyMax], float G)
 // vertices again, the clipper where it is needed, the snapped polygon into the lane's slice of LDS - and tests the
 // polygon's box against the tile; the records that reach the tile are then walked one after the other by the whole wave.
 // (A workgroup is one wave: the barriers order the wave's own LDS traffic and cost nothing.)
-template <bool kMask, bool kLod> __global__ __launch_bounds__(64) void raster_large_kernel(const RasterParams p)
+template <bool kMask, bool kLod, int kMode = kModeVisibility>
+__global__ __launch_bounds__(64) void raster_large_kernel(const RasterParams p, const LayerTargetsOf<kMode> L)
 {
+    constexpr bool kLayers = kMode != kModeVisibility;
     __shared__ ClipV poly[64][2][kPolyMax];
     __shared__ int32_t sX[64][kPolyMax], sY[64][kPolyMax];
     __shared__ float sD[64][kPolyMax];
@@ -488,7 +547,7 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(64) void raster_la
             Meshlet m;
             uint32_t i0, i1, i2;
             ClipV c0, c1, c2;
-            if (entry < p.capacity && load_meshlet(p, entry, &m) && t < m.triangleCount && load_triangle(m, t, &i0, &i1, &i2) &&
+            if (entry < p.capacity && load_meshlet<kLayers>(p, entry, &m) && t < m.triangleCount && load_triangle(m, t, &i0, &i1, &i2) &&
                 load_clip_vertex(p, m, i0, &c0) && load_clip_vertex(p, m, i1, &c1) && load_clip_vertex(p, m, i2, &c2))
             {
                 const SnapV s0 = snap_vertex(p.view, c0), s1 = snap_vertex(p.view, c1), s2 = snap_vertex(p.view, c2);
@@ -540,11 +599,12 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(64) void raster_la
                 }
             }
         }
-        if (first)
-        {
-            count_ballot(&p.counters->clipped, clipped, lane);
-            count_ballot(&p.counters->culledOutside, nothingLeft, lane);
-        }
+        if constexpr (!kLayers)
+            if (first)
+            {
+                count_ballot(&p.counters->clipped, clipped, lane);
+                count_ballot(&p.counters->culledOutside, nothingLeft, lane);
+            }
         __syncthreads(); // the lanes' polygons are in LDS
         unsigned long long todo = __ballot(hit);
         while (todo != 0ull) // (the same in every lane)
@@ -570,17 +630,97 @@ template <bool kMask, bool kLod> __global__ __launch_bounds__(64) void raster_la
                     const int32_t px = x0 + (int32_t)(i % bw), py = y0 + (int32_t)(i / bw);
                     float depth;
                     if (!covers(tri, area2, px, py, &depth)) continue;
-                    if constexpr (kMask)
-                        if (smask && alpha_discards<kLod>(p, px, py, sdi, sprim)) continue;
-                    ++fragments;
-                    emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, key);
+                    if constexpr (kLayers)
+                        layer_fragment<kMode, kLod>(p, L, px, py, depth, key, sdi, sprim);
+                    else
+                    {
+                        if constexpr (kMask)
+                            if (smask && alpha_discards<kLod>(p, px, py, sdi, sprim)) continue;
+                        ++fragments;
+                        emit(p.keys, (size_t)py * p.view.width + (size_t)px, depth, key);
+                    }
                 }
             }
         }
         __syncthreads(); // ... and have been read before the next 64 records replace them
     }
-    fragments = wave_sum(fragments);
-    if (lane == 0u && fragments != 0u) atomicAdd(&p.counters->fragments, fragments);
+    if constexpr (!kLayers)
+    {
+        fragments = wave_sum(fragments);
+        if (lane == 0u && fragments != 0u) atomicAdd(&p.counters->fragments, fragments);
+    }
+}
+
+
+// ---- the exclusive scan of the per-pixel counts ----
+
+// The inclusive scan of a wave's 64 values: Hillis-Steele inside each row of 16 lanes by DPP row_shr 1, 2, 4, 8 (a lane
+// whose source lies outside its row adds 0), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3.
+// Every lane of the wave is active where it is called.
+template <int Ctrl, int RowMask> PPT_RS uint32_t dpp_or_zero(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, Ctrl, RowMask, 0xF, false);
+}
+PPT_RS uint32_t wave_inclusive_scan(uint32_t v)
+{
+    v += dpp_or_zero<0x111, 0xF>(v);
+    v += dpp_or_zero<0x112, 0xF>(v);
+    v += dpp_or_zero<0x114, 0xF>(v);
+    v += dpp_or_zero<0x118, 0xF>(v);
+    v += dpp_or_zero<0x142, 0xA>(v);
+    v += dpp_or_zero<0x143, 0xC>(v);
+    return v;
+}
+
+constexpr uint32_t kScanPerLane = kRasterScanBlock / 64u; // consecutive counters of one lane
+
+// blockSums[b] = the sum of the block's counters
+__global__ __launch_bounds__(64) void raster_scan_sums_kernel(const uint32_t *__restrict__ counts, uint32_t *__restrict__ blockSums, size_t pixels)
+{
+    const size_t base = (size_t)blockIdx.x * kRasterScanBlock + (size_t)threadIdx.x * kScanPerLane;
+    uint32_t sum = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPerLane; ++k)
+        if (base + k < pixels) sum += counts[base + k];
+    sum = wave_inclusive_scan(sum);
+    if (threadIdx.x == 63u) blockSums[blockIdx.x] = sum;
+}
+
+// One wave: blockSums -> their exclusive scan in place, 64 at a time with a carry; *total = the sum of all
+__global__ __launch_bounds__(64) void raster_scan_blocks_kernel(uint32_t *__restrict__ blockSums, uint32_t blocks, uint32_t *__restrict__ total)
+{
+    uint32_t carry = 0u;
+    for (uint32_t b = 0; b < blocks; b += 64u) // (the same in every lane)
+    {
+        const uint32_t i = b + threadIdx.x;
+        const uint32_t v = i < blocks ? blockSums[i] : 0u;
+        const uint32_t inclusive = wave_inclusive_scan(v);
+        if (i < blocks) blockSums[i] = carry + (inclusive - v);
+        carry += (uint32_t)__builtin_amdgcn_readlane((int)inclusive, 63);
+    }
+    if (threadIdx.x == 0u) *total = carry;
+}
+
+// offsets[i] = the block's offset + the counters before i in the block
+__global__ __launch_bounds__(64) void raster_scan_offsets_kernel(
+    const uint32_t *__restrict__ counts, const uint32_t *__restrict__ blockOffsets, uint32_t *__restrict__ offsets, size_t pixels)
+{
+    const size_t base = (size_t)blockIdx.x * kRasterScanBlock + (size_t)threadIdx.x * kScanPerLane;
+    uint32_t c[kScanPerLane];
+    uint32_t sum = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPerLane; ++k)
+    {
+        c[k] = base + k < pixels ? counts[base + k] : 0u;
+        sum += c[k];
+    }
+    uint32_t run = blockOffsets[blockIdx.x] + (wave_inclusive_scan(sum) - sum);
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPerLane; ++k)
+    {
+        if (base + k < pixels) offsets[base + k] = run;
+        run += c[k];
+    }
 }
 
 __global__ __launch_bounds__(256) void raster_depth_kernel(const unsigned long long *keys, float *depth, size_t pixels)
@@ -602,14 +742,35 @@ void launch_raster_meshlets(const RasterParams &p, hipStream_t stream)
     if (p.capacity == 0u) return;
     // the instantiations that test MASK fragments run only where the scene has such a material on meshlets
     const auto kernel = !p.anyMask ? raster_meshlets_kernel<false, false> : p.lod ? raster_meshlets_kernel<true, true> : raster_meshlets_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3((p.capacity + 3u) / 4u), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(kernel, dim3((p.capacity + 3u) / 4u), dim3(256), 0, stream, p, RasterNoLayers{});
 }
 
 void launch_raster_large(const RasterParams &p, hipStream_t stream)
 {
     const dim3 grid((p.view.width + kRasterTile - 1u) / kRasterTile, (p.view.height + kRasterTile - 1u) / kRasterTile);
     const auto kernel = !p.anyMask ? raster_large_kernel<false, false> : p.lod ? raster_large_kernel<true, true> : raster_large_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, p);
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, p, RasterNoLayers{});
+}
+
+void launch_raster_layers(const RasterParams &p, const RasterLayerTargets &t, bool fill, hipStream_t stream)
+{
+    if (p.capacity == 0u) return;
+    const auto meshlets = p.lod ? (fill ? raster_meshlets_kernel<true, true, kModeLayerFill> : raster_meshlets_kernel<true, true, kModeLayerCount>)
+                                : (fill ? raster_meshlets_kernel<true, false, kModeLayerFill> : raster_meshlets_kernel<true, false, kModeLayerCount>);
+    hipLaunchKernelGGL(meshlets, dim3((p.capacity + 3u) / 4u), dim3(256), 0, stream, p, t);
+    const dim3 grid((p.view.width + kRasterTile - 1u) / kRasterTile, (p.view.height + kRasterTile - 1u) / kRasterTile);
+    const auto large = p.lod ? (fill ? raster_large_kernel<true, true, kModeLayerFill> : raster_large_kernel<true, true, kModeLayerCount>)
+                             : (fill ? raster_large_kernel<true, false, kModeLayerFill> : raster_large_kernel<true, false, kModeLayerCount>);
+    hipLaunchKernelGGL(large, grid, dim3(64), 0, stream, p, t);
+}
+
+void launch_raster_layer_scan(const uint32_t *counts, uint32_t *offsets, uint32_t *blockSums, uint32_t *total, size_t pixels, hipStream_t stream)
+{
+    const uint32_t blocks = raster_scan_blocks(pixels);
+    if (blocks == 0u) return;
+    hipLaunchKernelGGL(raster_scan_sums_kernel, dim3(blocks), dim3(64), 0, stream, counts, blockSums, pixels);
+    hipLaunchKernelGGL(raster_scan_blocks_kernel, dim3(1), dim3(64), 0, stream, blockSums, blocks, total);
+    hipLaunchKernelGGL(raster_scan_offsets_kernel, dim3(blocks), dim3(64), 0, stream, counts, blockSums, offsets, pixels);
 }
 
 void launch_raster_depth(const unsigned long long *keys, float *depth, uint32_t width, uint32_t height, hipStream_t stream)

@@ -89,8 +89,34 @@ struct RasterResolveTables
     const uint32_t *triMap;          // [their triangles]
 };
 
+// The per-pixel fragment lists of the rasterised transparent pass.  A LAYER CANDIDATE is a fragment of the
+// rule above whose depth is strictly greater than depth[pixel] (reverse-Z eGreater, no depth write) and whose
+// sampleMaterial alpha is not 0 (the MASK discard's own code, for every meshlet of the list).  The raster kernels run twice
+// from one template: the count pass adds 1 to counts[pixel]; the fill pass writes the fragment's key - the visibility
+// image's - at offsets[pixel] + atomicAdd(cursor[pixel], 1), never at or past `capacity`.
+struct RasterLayerTargets
+{
+    const float *depth;            // [height * width], the stored depth the candidates are tested against
+    uint32_t *counts;              // [height * width], 0 before the count pass
+    const uint32_t *offsets;       // [height * width], the exclusive scan of counts (fill pass)
+    uint32_t *cursor;              // [height * width], 0 before the fill pass
+    unsigned long long *fragments; // [capacity] (fill pass)
+    uint32_t capacity;             // the scan's total
+};
+
+// What the resolve of those lists reads (raster_transparent_kernel, pt_gbuffer_kernels.hip)
+struct RasterLayerLists
+{
+    const uint32_t *counts, *offsets;
+    const unsigned long long *fragments;
+    uint32_t total; // fragments in all lists
+};
+
 // G for an extent: 65536 / max(width, height) - 2, so that a clipped vertex snaps to at most 2^23 - 256 * extent
 float raster_guard_band(uint32_t width, uint32_t height);
+// The elements one wave of the scan's kernels takes, and the block sums a scan over `pixels` counters needs
+constexpr uint32_t kRasterScanBlock = 1024;
+inline uint32_t raster_scan_blocks(size_t pixels) { return (uint32_t)((pixels + kRasterScanBlock - 1u) / kRasterScanBlock); }
 
 // raster_meshlets_kernel over the list's capacity, then raster_large_kernel over the screen's tiles.  The queue's count
 // and the counters are 0 before the first (the host clears them, and the keys, with memsets).
@@ -98,6 +124,11 @@ void launch_raster_meshlets(const RasterParams &p, hipStream_t stream);
 void launch_raster_large(const RasterParams &p, hipStream_t stream);
 // depth[i] = the key's high word as a float (0 where the key is 0)
 void launch_raster_depth(const unsigned long long *keys, float *depth, uint32_t width, uint32_t height, hipStream_t stream);
+// One raster pass of the transparent lists: both kernels above instantiated for layer candidates, `fill` false: the count
+// pass, true: the fill pass.  p.keys and p.counters are not used; the queue's count is 0 before each pass.
+void launch_raster_layers(const RasterParams &p, const RasterLayerTargets &t, bool fill, hipStream_t stream);
+// offsets = the exclusive scan of counts, *total = their sum (32 bits); blockSums: raster_scan_blocks(pixels) words of scratch
+void launch_raster_layer_scan(const uint32_t *counts, uint32_t *offsets, uint32_t *blockSums, uint32_t *total, size_t pixels, hipStream_t stream);
 
 } // namespace ppt
 
@@ -110,5 +141,15 @@ namespace ppt
 int raster_resolve_tables(prosper_pt_ctx *ctx, const char *what, uint32_t width, uint32_t height, hipStream_t s, RasterResolveTables *out);
 // the resolve's kernel has been enqueued on `s`: the next draw waits for it before it clears the image
 int raster_resolve_enqueued(prosper_pt_ctx *ctx, hipStream_t s);
+// (pt_raster_passes.cpp) The rasterised transparent pass's lists.  raster_layers_check: what a draw of list
+// `which` refuses (`listNeeded` false: a culling call that produces the list comes first), without a GPU call.
+// raster_layers_build: count, scan and fill of list `which` against `depth` (camera->resolution floats on the device) on
+// `s`, after flush_scene_updates; events[0 .. 3] are recorded before the count pass and behind the count pass, the scan and
+// the fill pass.  BLOCKS THE HOST once, between scan and fill, for the 4-byte total that sizes the fragment buffer.  A total
+// of 0 launches no fill pass.  *tables: what the resolve decodes the keys with.
+int raster_layers_check(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool listNeeded, const prosper_CameraUniforms *camera);
+int raster_layers_build(
+    prosper_pt_ctx *ctx, const char *what, uint32_t which, const prosper_CameraUniforms *camera, const float *depth, hipStream_t s,
+    hipEvent_t *events, RasterLayerLists *lists, RasterResolveTables *tables);
 #pragma GCC visibility pop
 } // namespace ppt

@@ -1,7 +1,8 @@
 // pt_raster_passes.cpp — C-ABI of the compute rasteriser over the meshlet draw lists (include/prosper_pt/prosper_pt.h;
 // DESIGN.md f18): GBufferRenderer::recordDraw into the context's visibility image, the two-phase sequence of
 // GBufferRenderer::record over the rasteriser's OWN depth, the tables of the resolve (its entry points live with the
-// traced G-buffer's in pt_gbuffer_passes.cpp), and the read-backs.  Kernels: pt_raster.hip.
+// traced G-buffer's in pt_gbuffer_passes.cpp), the per-pixel fragment lists of the rasterised transparent pass (DESIGN.md
+// f20; its entry points live beside the forward opaque pass's), and the read-backs.  Kernels: pt_raster.hip.
 #include "../../include/prosper_pt/prosper_pt.h"
 
 #include <hip/hip_runtime.h>
@@ -58,6 +59,14 @@ struct RasterPassState
     Fence countersDone;
     StageEvents<2> timing[2]; // the meshlet kernel | the large pass
     Fence done;               // behind the last call's kernels
+    // the rasterised transparent pass's per-pixel lists: grow-only
+    DeviceBuffer layerCounts;    // three words per pixel: the count, the scan's offset, the fill pass's cursor
+    DeviceBuffer layerBlockSums; // the scan's block sums, then the total
+    DeviceBuffer layerFragments; // the keys, list after list
+    Pinned<uint32_t> layerTotalHost;
+    Fence layerTotalCopied;
+    uint32_t layerWidth = 0, layerHeight = 0, layerTotal = 0;
+    bool layersValid = false;
 };
 
 bool create_raster_passes(prosper_pt_ctx *ctx)
@@ -80,6 +89,7 @@ void forget_raster(prosper_pt_ctx *ctx)
     rs.meshMaps.clear(); // (a new scene's buffers are other buffers)
     rs.imageValid = false;
     rs.drawn[0] = rs.drawn[1] = false;
+    rs.layersValid = false;
 }
 
 } // namespace ppt
@@ -286,34 +296,19 @@ int check_draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear
     return PROSPER_PT_OK;
 }
 
-int draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear, const prosper_CameraUniforms *camera, hipStream_t s)
+// What a raster pass over list `which` reads, on `s` behind the calls that still use the lists: the queue grown for the list,
+// the tables of this geometry generation on the device, and the kernels' parameters but for the keys and the counters.
+// The queue's count is NOT cleared here.
+int prepare_raster_params(prosper_pt_ctx *ctx, uint32_t which, const prosper_CameraUniforms *camera, hipStream_t s, RasterParams *out)
 {
-    int rc = check_draw(ctx, what, which, clear, camera);
-    if (rc != PROSPER_PT_OK) return rc;
     RasterPassState &rs = *ctx->rasterPasses;
     CullingPassState &st = *ctx->cullingPasses;
-    PPT_HIP(hipSetDevice(ctx->device));
-    if ((rc = flush_scene_updates(ctx, s, s)) != PROSPER_PT_OK) return rc;
-    // calls on other streams may still use the lists or the image: `s` takes up behind them before anything grows
-    if ((rc = st.done.wait(s)) != PROSPER_PT_OK) return rc;
-    if ((rc = rs.done.wait(s)) != PROSPER_PT_OK) return rc;
+    int rc = PROSPER_PT_OK;
     const uint32_t w = camera->resolution[0], h = camera->resolution[1];
-    const size_t pixels = (size_t)w * h;
-    const uint32_t slot = clear ? 0u : 1u;
-    if (clear)
-    {
-        rs.imageValid = false;
-        rs.drawn[0] = rs.drawn[1] = false;
-        if ((rc = grow_to(rs.keys, pixels * 8u, s)) != PROSPER_PT_OK) return rc;
-        if ((rc = grow_to(rs.depth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
-    }
-    else
-        rs.drawn[1] = false;
     // the queue holds every triangle of the list at most: 124 per entry, and no more than the meshes' index buffers hold
     const uint64_t triangleBound = std::min<uint64_t>((uint64_t)st.upperBound * kRasterMaxTriangles, st.totals.totalTriangleCount);
     const uint32_t queueCapacity = (uint32_t)std::max<uint64_t>(triangleBound, 1u);
     if ((rc = grow_to(rs.queue, 8u + 8u * (size_t)queueCapacity, s)) != PROSPER_PT_OK) return rc;
-    if ((rc = grow_to(rs.counters, 2u * sizeof(RasterCounters), s)) != PROSPER_PT_OK) return rc;
     const size_t guardBytes = rs.hostGuards.size() * sizeof(RasterMeshGuard), baseBytes = rs.hostBase.size() * sizeof(uint32_t);
     if (rs.guards.bytes < guardBytes || !rs.guards.ptr || rs.meshletBase.bytes < baseBytes || !rs.meshletBase.ptr) rs.tablesDirty = true;
     if ((rc = grow_to(rs.guards, guardBytes, s)) != PROSPER_PT_OK) return rc;
@@ -339,17 +334,6 @@ int draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear, cons
         PPT_HIP(hipMemcpy(rs.triMap.ptr, rs.hostTriMap.data(), rs.hostTriMap.size() * 4u, hipMemcpyHostToDevice));
         rs.tablesDirty = false;
     }
-    if (!rs.countersHost.ptr)
-    {
-        if ((rc = rs.countersHost.allocate(2u * sizeof(RasterCounters))) != PROSPER_PT_OK) return rc;
-        std::memset(rs.countersHost.ptr, 0, 2u * sizeof(RasterCounters));
-    }
-    if ((rc = rs.timing[slot].create()) != PROSPER_PT_OK) return rc;
-
-    if (clear) PPT_HIP(hipMemsetAsync(rs.keys.ptr, 0, pixels * 8u, s));
-    PPT_HIP(hipMemsetAsync(rs.queue.ptr, 0, 8u, s));
-    PPT_HIP(hipMemsetAsync(rs.counters.as<RasterCounters>() + slot, 0, sizeof(RasterCounters), s));
-
     RasterParams p = {};
     p.geometryBuffers = ctx->scene.geometryBuffers;
     p.metadatas = ctx->scene.geometryMetadatas;
@@ -362,10 +346,8 @@ int draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear, cons
     p.modelInstanceCount = ctx->scene.modelInstanceCount;
     p.list = st.lists[which].as<uint32_t>();
     p.capacity = st.capacity;
-    p.keys = rs.keys.as<unsigned long long>();
     p.queue = rs.queue.as<uint32_t>();
     p.queueCapacity = queueCapacity;
-    p.counters = rs.counters.as<RasterCounters>() + slot;
     // the MASK discard reads what the resolve's surface code reads: the scene, the pixel ray's camera terms, the LOD state
     // (from the materials as they are NOW: prosper_pt_update_materials may have made one MASK since the tables were made)
     p.anyMask = 0u;
@@ -401,6 +383,49 @@ int draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear, cons
     p.view.width = w;
     p.view.height = h;
     p.view.guardBand = raster_guard_band(w, h);
+
+    *out = p;
+    return PROSPER_PT_OK;
+}
+
+int draw(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool clear, const prosper_CameraUniforms *camera, hipStream_t s)
+{
+    int rc = check_draw(ctx, what, which, clear, camera);
+    if (rc != PROSPER_PT_OK) return rc;
+    RasterPassState &rs = *ctx->rasterPasses;
+    CullingPassState &st = *ctx->cullingPasses;
+    PPT_HIP(hipSetDevice(ctx->device));
+    if ((rc = flush_scene_updates(ctx, s, s)) != PROSPER_PT_OK) return rc;
+    // calls on other streams may still use the lists or the image: `s` takes up behind them before anything grows
+    if ((rc = st.done.wait(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = rs.done.wait(s)) != PROSPER_PT_OK) return rc;
+    const uint32_t w = camera->resolution[0], h = camera->resolution[1];
+    const size_t pixels = (size_t)w * h;
+    const uint32_t slot = clear ? 0u : 1u;
+    if (clear)
+    {
+        rs.imageValid = false;
+        rs.drawn[0] = rs.drawn[1] = false;
+        if ((rc = grow_to(rs.keys, pixels * 8u, s)) != PROSPER_PT_OK) return rc;
+        if ((rc = grow_to(rs.depth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
+    }
+    else
+        rs.drawn[1] = false;
+    if ((rc = grow_to(rs.counters, 2u * sizeof(RasterCounters), s)) != PROSPER_PT_OK) return rc;
+    RasterParams p = {};
+    if ((rc = prepare_raster_params(ctx, which, camera, s, &p)) != PROSPER_PT_OK) return rc;
+    p.keys = rs.keys.as<unsigned long long>();
+    p.counters = rs.counters.as<RasterCounters>() + slot;
+    if (!rs.countersHost.ptr)
+    {
+        if ((rc = rs.countersHost.allocate(2u * sizeof(RasterCounters))) != PROSPER_PT_OK) return rc;
+        std::memset(rs.countersHost.ptr, 0, 2u * sizeof(RasterCounters));
+    }
+    if ((rc = rs.timing[slot].create()) != PROSPER_PT_OK) return rc;
+
+    if (clear) PPT_HIP(hipMemsetAsync(rs.keys.ptr, 0, pixels * 8u, s));
+    PPT_HIP(hipMemsetAsync(rs.queue.ptr, 0, 8u, s));
+    PPT_HIP(hipMemsetAsync(rs.counters.as<RasterCounters>() + slot, 0, sizeof(RasterCounters), s));
 
     PPT_HIP(hipEventRecord(rs.timing[slot].events[0], s));
     launch_raster_meshlets(p, s);
@@ -456,6 +481,99 @@ int raster_resolve_tables(prosper_pt_ctx *ctx, const char *what, uint32_t width,
 }
 
 int raster_resolve_enqueued(prosper_pt_ctx *ctx, hipStream_t s) { return ctx->rasterPasses->done.record(s); }
+
+int raster_layers_check(prosper_pt_ctx *ctx, const char *what, uint32_t which, bool listNeeded, const prosper_CameraUniforms *camera)
+{
+    if (which != PROSPER_PT_DRAW_LIST_GENERATED && which != PROSPER_PT_DRAW_LIST_FIRST_PHASE && which != PROSPER_PT_DRAW_LIST_SECOND_PHASE)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the list is GENERATED, FIRST_PHASE or SECOND_PHASE");
+    if (!ctx || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (listNeeded) return check_draw(ctx, what, which, true, camera);
+    // check_draw but for the list, which the culling call ahead produces
+    int rc = check_scene(ctx, what);
+    if (rc != PROSPER_PT_OK) return rc;
+    if (!ctx->accel || !ctx->geometry || !ctx->materialState) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + ": no scene");
+    if ((rc = make_tables(ctx, what)) != PROSPER_PT_OK) return rc;
+    if (!ctx->rasterPasses->anyMeshlets) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + ": the scene has no meshlets");
+    const uint32_t w = camera->resolution[0], h = camera->resolution[1];
+    if (w == 0u || h == 0u || w > kMaxSide || h > kMaxSide)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera->resolution is empty or a side is above 16384");
+    return PROSPER_PT_OK;
+}
+
+int raster_layers_build(
+    prosper_pt_ctx *ctx, const char *what, uint32_t which, const prosper_CameraUniforms *camera, const float *depth, hipStream_t s,
+    hipEvent_t *events, RasterLayerLists *lists, RasterResolveTables *tables)
+{
+    int rc = raster_layers_check(ctx, what, which, true, camera);
+    if (rc != PROSPER_PT_OK) return rc;
+    RasterPassState &rs = *ctx->rasterPasses;
+    CullingPassState &st = *ctx->cullingPasses;
+    PPT_HIP(hipSetDevice(ctx->device));
+    // calls on other streams may still use the lists, the queue or the fragment lists: `s` takes up behind them
+    if ((rc = st.done.wait(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = rs.done.wait(s)) != PROSPER_PT_OK) return rc;
+    const uint32_t w = camera->resolution[0], h = camera->resolution[1];
+    const size_t pixels = (size_t)w * h;
+    const uint32_t blocks = raster_scan_blocks(pixels);
+    rs.layersValid = false;
+    if ((rc = grow_to(rs.layerCounts, pixels * 12u, s)) != PROSPER_PT_OK) return rc;
+    if ((rc = grow_to(rs.layerBlockSums, ((size_t)blocks + 1u) * 4u, s)) != PROSPER_PT_OK) return rc;
+    if (!rs.layerTotalHost.ptr && (rc = rs.layerTotalHost.allocate(sizeof(uint32_t))) != PROSPER_PT_OK) return rc;
+    RasterParams p = {};
+    if ((rc = prepare_raster_params(ctx, which, camera, s, &p)) != PROSPER_PT_OK) return rc;
+    RasterLayerTargets t = {};
+    t.depth = depth;
+    t.counts = rs.layerCounts.as<uint32_t>();
+    uint32_t *offsets = t.counts + pixels;
+    t.offsets = offsets;
+    t.cursor = t.counts + 2u * pixels;
+    uint32_t *total = rs.layerBlockSums.as<uint32_t>() + blocks;
+
+    // counts and cursors (the offsets between them are all written by the scan)
+    PPT_HIP(hipMemsetAsync(t.counts, 0, pixels * 4u, s));
+    PPT_HIP(hipMemsetAsync(t.cursor, 0, pixels * 4u, s));
+    PPT_HIP(hipMemsetAsync(rs.queue.ptr, 0, 8u, s));
+    PPT_HIP(hipEventRecord(events[0], s));
+    launch_raster_layers(p, t, false, s);
+    PPT_HIP(hipGetLastError());
+    PPT_HIP(hipEventRecord(events[1], s));
+    launch_raster_layer_scan(t.counts, offsets, rs.layerBlockSums.as<uint32_t>(), total, pixels, s);
+    PPT_HIP(hipGetLastError());
+    PPT_HIP(hipEventRecord(events[2], s));
+    // the one host wait of the pass: the total sizes the fragment buffer
+    PPT_HIP(hipMemcpyAsync(rs.layerTotalHost.ptr, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if ((rc = rs.layerTotalCopied.record(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = rs.layerTotalCopied.host_wait()) != PROSPER_PT_OK) return rc;
+    const uint32_t fragments = *rs.layerTotalHost.ptr;
+    if (fragments != 0u)
+    {
+        if ((rc = grow_to(rs.layerFragments, (size_t)fragments * 8u, s)) != PROSPER_PT_OK) return rc;
+        t.fragments = rs.layerFragments.as<unsigned long long>();
+        t.capacity = fragments;
+        PPT_HIP(hipMemsetAsync(rs.queue.ptr, 0, 8u, s));
+        launch_raster_layers(p, t, true, s);
+        PPT_HIP(hipGetLastError());
+    }
+    PPT_HIP(hipEventRecord(events[3], s));
+    if ((rc = rs.done.record(s)) != PROSPER_PT_OK) return rc;
+    if ((rc = st.done.record(s)) != PROSPER_PT_OK) return rc; // (the next culling call clears the list these passes read)
+    rs.layerWidth = w;
+    rs.layerHeight = h;
+    rs.layerTotal = fragments;
+    rs.layersValid = true;
+    lists->counts = t.counts;
+    lists->offsets = offsets;
+    lists->fragments = rs.layerFragments.as<unsigned long long>();
+    lists->total = fragments;
+    tables->keys = nullptr; // (the lists hold the keys)
+    tables->meshletBase = rs.meshletBase.as<uint32_t>();
+    tables->drawInstanceCount = std::min<uint32_t>(ctx->scene.drawInstanceCount, (uint32_t)(rs.hostBase.size() - 1u));
+    tables->meshMeshletBase = rs.meshMeshletBase.as<uint32_t>();
+    tables->meshCount = (uint32_t)(rs.hostMeshMeshletBase.size() - 1u);
+    tables->meshletTriStart = rs.meshletTriStart.as<uint32_t>();
+    tables->triMap = rs.triMap.as<uint32_t>();
+    return PROSPER_PT_OK;
+}
 
 } // namespace ppt
 
@@ -548,6 +666,52 @@ int prosper_pt_read_raster_visibility(prosper_pt_ctx *ctx, uint32_t *ids, float 
         o[0] = (uint32_t)d;
         o[1] = ordinal - base[d];
         o[2] = low & 127u;
+    }
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_read_raster_fragments(
+    prosper_pt_ctx *ctx, uint32_t *counts, size_t pixels, prosper_pt_raster_fragment *fragments, size_t capacity, uint64_t *total, void *stream)
+{
+    const char *what = "prosper_pt_read_raster_fragments";
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    RasterPassState &rs = *ctx->rasterPasses;
+    if (!rs.layersValid) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + ": the rasterised transparent pass has not run on this scene");
+    const size_t need = (size_t)rs.layerWidth * rs.layerHeight;
+    if (total) *total = rs.layerTotal;
+    if ((counts || fragments) && pixels != need) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": pixel count differs from the pass's");
+    if (fragments && capacity < rs.layerTotal) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": room for fewer fragments than the lists hold");
+    if (!counts && !fragments) return PROSPER_PT_OK;
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = rs.done.wait(s)) return rc;
+    std::vector<uint32_t> hostCounts(need);
+    std::vector<unsigned long long> keys(rs.layerTotal);
+    PPT_HIP(hipMemcpyAsync(hostCounts.data(), rs.layerCounts.ptr, need * 4u, hipMemcpyDeviceToHost, s));
+    if (fragments && rs.layerTotal)
+        PPT_HIP(hipMemcpyAsync(keys.data(), rs.layerFragments.ptr, (size_t)rs.layerTotal * 8u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    if (counts) std::memcpy(counts, hostCounts.data(), need * 4u);
+    if (!fragments) return PROSPER_PT_OK;
+    const std::vector<uint32_t> &base = rs.hostBase;
+    size_t at = 0;
+    for (size_t i = 0; i < need; ++i)
+    {
+        const size_t n = hostCounts[i];
+        if (at + n > keys.size()) return fail(PROSPER_PT_ERR_SCENE, std::string(what) + ": the counts exceed the scan's total");
+        std::sort(keys.begin() + at, keys.begin() + at + n, [](unsigned long long a, unsigned long long b) { return a > b; }); // nearest first
+        for (size_t k = at; k < at + n; ++k)
+        {
+            const unsigned long long key = keys[k];
+            const uint32_t low = ~(uint32_t)key, ordinal = low >> 7;
+            const size_t d = (size_t)(std::upper_bound(base.begin(), base.end() - 1, ordinal) - base.begin()) - 1u;
+            prosper_pt_raster_fragment &f = fragments[k];
+            f.drawInstance = (uint32_t)d;
+            f.meshlet = ordinal - base[d];
+            f.triangle = low & 127u;
+            std::memcpy(&f.depth, reinterpret_cast<const char *>(&key) + 4, 4); // the high word (little endian)
+        }
+        at += n;
     }
     return PROSPER_PT_OK;
 }

@@ -555,6 +555,21 @@ class ForwardRenderer:
             raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
         return pc
 
+    def record_transparent_raster(self, camera, width, height, depth=None, depth_ptr=None, apply_ibl=False, draw_type="Default",
+                                  stream=None):
+        """ForwardRenderer::recordTransparentRaster: the raster frame's transparents (Context.raster_forward_transparent) -
+        the TRANSPARENT draw list culled once, listed per pixel and resolved over the context's HDR image.  `depth`,
+        `depth_ptr`: as record_transparent (neither: the context's last depth, a forward frame's included)."""
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        pc = S.ForwardPC()
+        rc = lib().prosper_host_forward_renderer_record_transparent_raster(
+            self._h, camera._h, width, height, C.c_void_p(depth_ptr if dp is None else dp.ctypes.data), 1 if dp is None else 0,
+            int(apply_ibl), S.DrawType[draw_type] if isinstance(draw_type, str) else int(draw_type), C.c_void_p(stream), C.byref(pc))
+        if rc != 0:
+            raise ProsperPtError(rc, lib().prosper_host_last_error().decode())
+        self._ctx._raster_transparent_extent = (width, height)
+        return pc
+
     def close(self):
         if self._h:
             lib().prosper_host_forward_renderer_destroy(self._h)

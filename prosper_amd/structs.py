@@ -429,6 +429,18 @@ class ForwardOpaqueInfo(C.Structure):
     _fields_ = [("shadedPixels", C.c_uint32), ("reclustered", C.c_uint32), ("ms", C.c_float), ("shadeMs", C.c_float)]
 
 
+class RasterTransparentInfo(C.Structure):
+    """prosper_pt_raster_transparent_info of the last rasterised transparent pass"""
+    _fields_ = [("fragments", C.c_uint32), ("coveredPixels", C.c_uint32), ("shadedLayers", C.c_uint32), ("maxLayers", C.c_uint32),
+                ("reclustered", C.c_uint32), ("countMs", C.c_float), ("scanMs", C.c_float), ("fillMs", C.c_float),
+                ("resolveMs", C.c_float), ("reserved", C.c_uint32)]
+
+
+class RasterFragment(C.Structure):
+    """prosper_pt_raster_fragment: one entry of a pixel's list as prosper_pt_read_raster_fragments decodes it (16 bytes)"""
+    _fields_ = [("drawInstance", C.c_uint32), ("meshlet", C.c_uint32), ("triangle", C.c_uint32), ("depth", C.c_float)]
+
+
 # prosper_pt_forward_transparent flags: which of the G-buffer's rays the pass follows (neither: the pixel centre)
 TRANSPARENT_JITTER = 1 << 0
 TRANSPARENT_CAMERA_JITTER = 1 << 1

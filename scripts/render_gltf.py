@@ -19,7 +19,9 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  (PROSPER_PT_GBUFFER_OPAQUE_ONLY) and prosper_pt_forward_transparent blends them, lit
                                  forward over the light clusters, over the shaded image after --sky and before --bloom
                                  (Renderer.cpp:493-500), through the host layer's ForwardRenderer; under --taa along the
-                                 camera-jittered ray
+                                 camera-jittered ray.  With --forward or --deferred --raster the transparents are
+                                 rasterised too (prosper_pt_raster_forward_transparent): the TRANSPARENT
+                                 draw list, per-pixel fragment lists, sorted and blended against the rasteriser's depth
     --deferred --debug-lines [--debug-frustum]
                                  prosper's DebugRenderer (prosper_pt_debug_lines) between the transparents and bloom
                                  (Renderer.cpp:502): the axes of the point and spot lights as the device holds them
@@ -294,7 +296,11 @@ def main():
                     ds.totalMeshCount, ds.totalModelCount))
             if args.sky:
                 ctx.skybox_fill(cam, w, h)  # before the lens: a silhouette against an empty background blurs towards black
-            if forward:
+            if forward and args.raster:
+                # the raster frame's transparents: the TRANSPARENT draw list culled once, listed per pixel and
+                # resolved over the sky-filled image against the rasteriser's own depth; ibl = 0, as prosper draws them
+                forward.record_transparent_raster(hcam, w, h)
+            elif forward:
                 # over the sky-filled image, along the ray the G-buffer was traced with; ibl = 0, as prosper draws them
                 forward.record_transparent(hcam, w, h, ray_flags=S.TRANSPARENT_CAMERA_JITTER if args.taa else 0, frame_index=frame)
             if args.debug_lines or frustum is not None:
@@ -329,7 +335,12 @@ def main():
             ctx.read_hdr()  # (synchronises: the info never waits)
             info = ctx.forward_opaque_info() or S.ForwardOpaqueInfo()
             print("forward opaque: %d pixels shaded, last shade %.3f ms (kernel %.3f ms)" % (info.shadedPixels, info.ms, info.shadeMs), file=sys.stderr)
-        if forward:
+        if forward and args.raster:
+            ctx.read_hdr()  # (synchronises: the info never waits)
+            info = ctx.raster_transparent_info() or S.RasterTransparentInfo()
+            print("transparents (rasterised): %d fragments in %d pixels, %d layers shaded, deepest %d; count %.3f + scan %.3f + fill %.3f + resolve %.3f ms" % (
+                info.fragments, info.coveredPixels, info.shadedLayers, info.maxLayers, info.countMs, info.scanMs, info.fillMs, info.resolveMs), file=sys.stderr)
+        elif forward:
             info = ctx.transparent_info()
             print("transparents: %d pixels with layers, %d layers, deepest %d, last pass %.3f ms" % (
                 info.coveredPixels, info.totalLayers, info.maxLayers, info.ms), file=sys.stderr)
