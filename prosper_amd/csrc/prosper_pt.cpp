@@ -799,7 +799,7 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         if ((rc = ctx->chainFork.record(ws.get()))) return rc;
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
-    if (!create_gbuffer_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
+    if (!create_gbuffer_passes(ctx) || !create_forward_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
         !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_culling_passes(ctx) || !create_raster_passes(ctx) ||
         !create_animation_state(ctx))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
@@ -857,6 +857,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     destroy_tiling(ctx);
     free_scene(ctx);
     destroy_gbuffer_passes(ctx);
+    destroy_forward_passes(ctx);
     destroy_dof_passes(ctx);
     destroy_bloom_passes(ctx);
     destroy_taa_passes(ctx);

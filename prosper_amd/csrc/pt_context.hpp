@@ -62,6 +62,11 @@ bool create_gbuffer_passes(prosper_pt_ctx *ctx);
 void destroy_gbuffer_passes(prosper_pt_ctx *ctx);
 // a new scene: the image-based lighting maps describe the old sky
 void forget_ibl_maps(prosper_pt_ctx *ctx);
+// State of ForwardRenderer's passes (pt_forward_passes.cpp): their buffers and what the last call of each produced.  Made
+// and freed like the G-buffer passes' state.
+struct ForwardPassState;
+bool create_forward_passes(prosper_pt_ctx *ctx);
+void destroy_forward_passes(prosper_pt_ctx *ctx);
 // State of the skybox fill and of depth of field (pt_dof_passes.cpp): the intermediates of the last call.  Made and
 // freed like the G-buffer passes' state.
 struct DofPassState;
@@ -359,6 +364,7 @@ struct prosper_pt_ctx
     bool timingValid = false;
 
     ppt::GBufferPassState *gbufferPasses = nullptr; // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL
+    ppt::ForwardPassState *forwardPasses = nullptr; // the traced and the rasterised transparent pass, the forward opaque pass
     ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
     ppt::BloomPassState *bloomPasses = nullptr;
     ppt::TaaPassState *taaPasses = nullptr;

@@ -13,6 +13,7 @@
 
 #include "pt_context.hpp"
 #include "pt_debug_view.hpp"
+#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 
 using namespace ppt;

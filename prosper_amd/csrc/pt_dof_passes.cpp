@@ -11,6 +11,7 @@
 
 #include "pt_context.hpp"
 #include "pt_dof.hpp"
+#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 
 using namespace ppt;

@@ -1,4 +1,5 @@
-// pt_gbuffer_kernels.hip — gfx950 kernels of the passes over a G-buffer (host side: pt_gbuffer_passes.cpp).
+// pt_gbuffer_kernels.hip — gfx950 kernels of the passes over a G-buffer (host side: pt_gbuffer_passes.cpp,
+// pt_forward_passes.cpp).
 //
 //   restir_di_*         ReSTIR-DI initial reservoirs, spatial reuse and trace over a G-buffer
 //   gbuffer_trace       the ray-traced G-buffer those passes read
@@ -926,41 +927,24 @@ __global__ __launch_bounds__(256) void deferred_shading_ibl_kernel(
 }
 
 void launch_deferred_shading(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream)
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam, const ClusteredLights &l,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, float4 *hdr, hipStream_t stream)
 {
     if (width == 0 || height == 0) return;
     DeferredParams d;
     d.r = restir_params(drawType, 0, 0, width, height, cam);
-    d.near_ = c.near_;
-    d.far_ = c.far_;
-    d.clustersX = c.dimX;
-    d.clustersY = c.dimY;
-    hipLaunchKernelGGL(
-        deferred_shading_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
-        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr);
-}
-
-void launch_deferred_shading_ibl(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
-    const uint32_t *lut, float4 *hdr, hipStream_t stream)
-{
-    if (width == 0 || height == 0) return;
-    DeferredParams d;
-    d.r = restir_params(drawType, 0, 0, width, height, cam);
-    d.near_ = c.near_;
-    d.far_ = c.far_;
-    d.clustersX = c.dimX;
-    d.clustersY = c.dimY;
-    const IblMaps maps = {irradiance, radiance, lut};
-    hipLaunchKernelGGL(
-        deferred_shading_ibl_kernel, dim3(restir_grid_blocks(width, height)), dim3(256), 0, stream, s, d,
-        static_cast<const float4 *>(albedoRoughness), static_cast<const float4 *>(normalMetallic), nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr, maps);
+    d.near_ = l.params.near_;
+    d.far_ = l.params.far_;
+    d.clustersX = l.params.dimX;
+    d.clustersY = l.params.dimY;
+    const dim3 grid(restir_grid_blocks(width, height));
+    const float4 *ar = static_cast<const float4 *>(albedoRoughness), *nm = static_cast<const float4 *>(normalMetallic);
+    const uint2 *ptrs = static_cast<const uint2 *>(l.pointers);
+    const IblMaps maps = {l.irradiance, l.radiance, l.lut};
+    if (l.irradiance)
+        hipLaunchKernelGGL(deferred_shading_ibl_kernel, grid, dim3(256), 0, stream, s, d, ar, nm, nonLinearDepth, ptrs, l.indices, hdr, maps);
+    else
+        hipLaunchKernelGGL(deferred_shading_kernel, grid, dim3(256), 0, stream, s, d, ar, nm, nonLinearDepth, ptrs, l.indices, hdr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1153,28 +1137,25 @@ __global__ __launch_bounds__(256) void forward_transparent_kernel(
 }
 
 void launch_forward_transparent(
-    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
-    const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
-    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream, const GBufferLodParams *lod)
+    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const ClusteredLights &l, float4 *hdr,
+    int32_t *stackOverflow, uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
+    const GBufferLodParams *lod)
 {
     if (p.g.r.width == 0 || p.g.r.height == 0) return;
-    const bool ibl = irradiance != nullptr, debug = p.debugLayers != 0u;
+    const dim3 grid(restir_grid_blocks(p.g.r.width, p.g.r.height));
+    const IblMaps maps = {l.irradiance, l.radiance, l.lut};
+    const uint2 *ptrs = static_cast<const uint2 *>(l.pointers);
+    const bool ibl = l.irradiance != nullptr, debug = p.debugLayers != 0u;
     if (lod)
     {
-        const auto lodKernel = ibl ? (debug ? forward_transparent_kernel<true, true, true> : forward_transparent_kernel<true, false, true>)
-                                   : (debug ? forward_transparent_kernel<false, true, true> : forward_transparent_kernel<false, false, true>);
-        const IblMaps lodMaps = {irradiance, radiance, lut};
-        hipLaunchKernelGGL(
-            lodKernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
-            static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, lodMaps, *lod);
+        const auto kernel = ibl ? (debug ? forward_transparent_kernel<true, true, true> : forward_transparent_kernel<true, false, true>)
+                                : (debug ? forward_transparent_kernel<false, true, true> : forward_transparent_kernel<false, false, true>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, p, nonLinearDepth, ptrs, l.indices, hdr, stackOverflow, stats, layerCounts, layers, maps, *lod);
         return;
     }
     const auto kernel = ibl ? (debug ? forward_transparent_kernel<true, true> : forward_transparent_kernel<true, false>)
                             : (debug ? forward_transparent_kernel<false, true> : forward_transparent_kernel<false, false>);
-    const IblMaps maps = {irradiance, radiance, lut};
-    hipLaunchKernelGGL(
-        kernel, dim3(restir_grid_blocks(p.g.r.width, p.g.r.height)), dim3(256), 0, stream, s, p, nonLinearDepth,
-        static_cast<const uint2 *>(pointers), indices, hdr, stackOverflow, stats, layerCounts, layers, maps, GBufferNoLod{});
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, p, nonLinearDepth, ptrs, l.indices, hdr, stackOverflow, stats, layerCounts, layers, maps, GBufferNoLod{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1262,26 +1243,26 @@ __global__ __launch_bounds__(256) void forward_opaque_kernel(
 }
 
 void launch_forward_opaque(
-    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusterParams &c,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr,
-    float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream, const GBufferLodParams *lod)
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusteredLights &l,
+    float4 *hdr, float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream,
+    const GBufferLodParams *lod)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
     const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
-    const ClusterGrid cg{c.near_, c.far_, c.dimX, c.dimY};
-    const IblMaps maps = {irradiance, radiance, lut};
-    const uint2 *ptrs = static_cast<const uint2 *>(pointers);
-    const bool ibl = irradiance != nullptr, debug = surfaces != nullptr;
+    const ClusterGrid cg{l.params.near_, l.params.far_, l.params.dimX, l.params.dimY};
+    const IblMaps maps = {l.irradiance, l.radiance, l.lut};
+    const uint2 *ptrs = static_cast<const uint2 *>(l.pointers);
+    const bool ibl = l.irradiance != nullptr, debug = surfaces != nullptr;
     if (lod)
     {
         const auto kernel = ibl ? (debug ? forward_opaque_kernel<true, true, true> : forward_opaque_kernel<true, true, false>)
                                 : (debug ? forward_opaque_kernel<false, true, true> : forward_opaque_kernel<false, true, false>);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, *lod);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, l.indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, *lod);
         return;
     }
     const auto kernel = ibl ? (debug ? forward_opaque_kernel<true, false, true> : forward_opaque_kernel<true, false, false>)
                             : (debug ? forward_opaque_kernel<false, false, true> : forward_opaque_kernel<false, false, false>);
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, GBufferNoLod{});
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, v, cg, ptrs, l.indices, hdr, nonLinearDepth, shadedPixels, surfaces, maps, GBufferNoLod{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1386,27 +1367,25 @@ __global__ __launch_bounds__(256) void raster_transparent_kernel(
 
 void launch_raster_transparent(
     const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const RasterLayerLists &t, const GBufferVelocityParams &v,
-    const ClusterParams &c, const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut,
-    float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
-    const GBufferLodParams *lod)
+    const ClusteredLights &l, float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers,
+    hipStream_t stream, const GBufferLodParams *lod)
 {
     if (g.r.width == 0 || g.r.height == 0) return;
     const dim3 grid(restir_grid_blocks(g.r.width, g.r.height));
-    const ClusterGrid cg{c.near_, c.far_, c.dimX, c.dimY};
-    const IblMaps maps = {irradiance, radiance, lut};
-    const uint2 *ptrs = static_cast<const uint2 *>(pointers);
-    const bool ibl = irradiance != nullptr, debug = debugLayers != 0u;
+    const ClusterGrid cg{l.params.near_, l.params.far_, l.params.dimX, l.params.dimY};
+    const IblMaps maps = {l.irradiance, l.radiance, l.lut};
+    const uint2 *ptrs = static_cast<const uint2 *>(l.pointers);
+    const bool ibl = l.irradiance != nullptr, debug = debugLayers != 0u;
     if (lod)
     {
         const auto kernel = ibl ? (debug ? raster_transparent_kernel<true, true, true> : raster_transparent_kernel<true, true, false>)
                                 : (debug ? raster_transparent_kernel<false, true, true> : raster_transparent_kernel<false, true, false>);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, indices, hdr, stats, debugLayers, layerCounts, layers, maps, *lod);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, l.indices, hdr, stats, debugLayers, layerCounts, layers, maps, *lod);
         return;
     }
     const auto kernel = ibl ? (debug ? raster_transparent_kernel<true, false, true> : raster_transparent_kernel<true, false, false>)
                             : (debug ? raster_transparent_kernel<false, false, true> : raster_transparent_kernel<false, false, false>);
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, indices, hdr, stats, debugLayers, layerCounts, layers, maps, GBufferNoLod{});
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s, g, r, t, v, cg, ptrs, l.indices, hdr, stats, debugLayers, layerCounts, layers, maps, GBufferNoLod{});
 }
-
 
 } // namespace ppt

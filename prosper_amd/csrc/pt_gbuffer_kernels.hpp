@@ -1,5 +1,6 @@
 // pt_gbuffer_kernels.hpp — host-callable launchers of the gfx950 kernels of the passes over a G-buffer
-// (pt_gbuffer_kernels.hip; ImageBasedLighting's generation in pt_ibl.hip).  Their C entry points: pt_gbuffer_passes.cpp.
+// (pt_gbuffer_kernels.hip; ImageBasedLighting's generation in pt_ibl.hip).  Their C entry points: pt_gbuffer_passes.cpp,
+// pt_forward_passes.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,27 +74,6 @@ void launch_gbuffer_trace_velocity(
 void launch_raster_resolve(
     const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, void *albedoRoughness,
     void *normalMetallic, float *nonLinearDepth, hipStream_t stream, const GBufferLodParams *lod = nullptr);
-// The forward transparent pass (forward_transparent_kernel; DESIGN.md f12) in place over `hdr`, r.width*r.height float4,
-// against `nonLinearDepth`.  g.jitter: the path tracer's sample; cameraJitter: the velocity entry's ray.  The lists are
-// launch_light_clustering's for the same camera and extent; irradiance / radiance / lut: the IBL maps, all nullptr
-// without IBL.  stats: four uint32 the caller zeroed - pixels with a layer, the deepest pixel's layers, total layers
-// (64 bits).  debugLayers != 0: layerCounts[pixel] and the first debugLayers layers of each pixel are written.
-struct TransparentParams
-{
-    GBufferTraceParams g;
-    float worldToCamera[16]; // column-major
-    float cameraToClip22, cameraToClip32;
-    float currentJitter[2];
-    uint32_t cameraJitter;
-    float near_, far_;
-    uint32_t clustersX, clustersY;
-    uint32_t debugLayers;
-};
-void launch_forward_transparent(
-    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const void *pointers, const uint16_t *indices,
-    const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr, int32_t *stackOverflow,
-    uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
-    const GBufferLodParams *lod = nullptr); // lod: every layer's material through the mip chains (its `derivatives` is not read)
 // Clustered lighting (LightClustering / DeferredShading).  The pointer grid is dimX x dimY x (kClusterZSlices + 1)
 // uint2 (indexOffset, pointCount << 16 | spotCount), x fastest; cluster k owns the uint16 index entries
 // [k * kClusterSlot, k * kClusterSlot + kClusterSlot), points first.  dropped: per cluster, the entries past the
@@ -113,33 +93,60 @@ struct ClusterParams
 };
 void launch_light_clustering(
     const DeviceScene &s, const ClusterParams &c, void *pointers, uint16_t *indices, uint32_t *dropped, hipStream_t stream);
-// One lane per pixel over restir_grid_blocks(width, height); reads the lists launch_light_clustering wrote with `c`.
+// What a lit pass reads of the lights: the lists launch_light_clustering wrote with `params`, and the IBL maps
+// launch_ibl_generation wrote, all three nullptr without IBL.
+struct ClusteredLights
+{
+    ClusterParams params;
+    const void *pointers;
+    const uint16_t *indices;
+    const uint16_t *irradiance, *radiance;
+    const uint32_t *lut;
+};
+// The forward transparent pass (forward_transparent_kernel; DESIGN.md f12) in place over `hdr`, r.width*r.height float4,
+// against `nonLinearDepth`.  g.jitter: the path tracer's sample; cameraJitter: the velocity entry's ray.  `l`: the lists for
+// the same camera and extent.  stats: four uint32 the caller zeroed - pixels with a layer, the deepest pixel's layers, total
+// layers (64 bits).  debugLayers != 0: layerCounts[pixel] and the first debugLayers layers of each pixel are written.
+struct TransparentParams
+{
+    GBufferTraceParams g;
+    float worldToCamera[16]; // column-major
+    float cameraToClip22, cameraToClip32;
+    float currentJitter[2];
+    uint32_t cameraJitter;
+    float near_, far_;
+    uint32_t clustersX, clustersY;
+    uint32_t debugLayers;
+};
+void launch_forward_transparent(
+    const DeviceScene &s, const TransparentParams &p, const float *nonLinearDepth, const ClusteredLights &l, float4 *hdr,
+    int32_t *stackOverflow, uint32_t *stats, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
+    const GBufferLodParams *lod = nullptr); // lod: every layer's material through the mip chains (its `derivatives` is not read)
+// One lane per pixel over restir_grid_blocks(width, height); reads the lists of `l`, and with its maps set adds evalIBL after
+// the spot lights (deferred_shading_ibl_kernel; ibl = 1).
 void launch_deferred_shading(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, float4 *hdr, hipStream_t stream);
+    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam, const ClusteredLights &l,
+    const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth, float4 *hdr, hipStream_t stream);
 // The forward opaque pass (forward_opaque_kernel): the visibility image `r` shaded into `hdr` (overwritten,
 // g.r.width*g.r.height float4), with `nonLinearDepth` from the keys and v.velocity as launch_raster_resolve writes them; g, r,
-// v and lod as for the resolve.  The lists are launch_light_clustering's with `c`; irradiance / radiance / lut: the IBL
-// maps, all nullptr without IBL.  shadedPixels: kForwardCountSlots counters, kForwardCountStride uint32 apart, which the
-// caller zeroed: their sum is the covered pixels.  surfaces != nullptr: every pixel's surface record too (drawInstance
-// 0xFFFFFFFF where nothing is drawn).
+// v and lod as for the resolve, `l` as for the transparent pass.  shadedPixels: kForwardCountSlots counters,
+// kForwardCountStride uint32 apart, which the caller zeroed: their sum is the covered pixels.  surfaces != nullptr: every
+// pixel's surface record too (drawInstance 0xFFFFFFFF where nothing is drawn).
 constexpr uint32_t kForwardCountSlots = 64, kForwardCountStride = 32;
 void launch_forward_opaque(
-    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusterParams &c,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut, float4 *hdr,
-    float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream, const GBufferLodParams *lod = nullptr);
+    const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const GBufferVelocityParams &v, const ClusteredLights &l,
+    float4 *hdr, float *nonLinearDepth, uint32_t *shadedPixels, prosper_pt_transparent_layer *surfaces, hipStream_t stream,
+    const GBufferLodParams *lod = nullptr);
 // The rasterised transparent pass's resolve (raster_transparent_kernel) in place over `hdr`: the per-pixel
 // fragment lists `t` (pt_raster.hpp) selected front to back, every layer shaded as launch_forward_opaque shades a winner and
-// blended as launch_forward_transparent blends.  g, r, v (its velocity is not used), c, the lists and the maps as for
-// launch_forward_opaque.  stats: kForwardCountSlots sets, kForwardCountStride uint32 apart, of { pixels with a list, layers
-// shaded, the longest list }, which the caller zeroed.  debugLayers != 0: layerCounts[pixel] = the layers shaded, and the
-// first debugLayers of them are written to layers[pixel * debugLayers ..].
+// blended as launch_forward_transparent blends.  g, r, v (its velocity is not used) and l as for launch_forward_opaque.
+// stats: kForwardCountSlots sets, kForwardCountStride uint32 apart, of { pixels with a list, layers shaded, the longest
+// list }, which the caller zeroed.  debugLayers != 0: layerCounts[pixel] = the layers shaded, and the first debugLayers of
+// them are written to layers[pixel * debugLayers ..].
 void launch_raster_transparent(
     const DeviceScene &s, const GBufferTraceParams &g, const RasterResolveTables &r, const RasterLayerLists &t, const GBufferVelocityParams &v,
-    const ClusterParams &c, const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance, const uint32_t *lut,
-    float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers, hipStream_t stream,
-    const GBufferLodParams *lod = nullptr);
+    const ClusteredLights &l, float4 *hdr, uint32_t *stats, uint32_t debugLayers, uint32_t *layerCounts, prosper_pt_transparent_layer *layers,
+    hipStream_t stream, const GBufferLodParams *lod = nullptr);
 // Image-based lighting (ImageBasedLighting / evalIBL).  Every cube is stored with a one-texel seamless border, as the
 // sky is: 6 faces of (n + 2)^2 RGBA16F texels.  Radiance mip m (size kIblRadianceSize >> m) starts
 // ibl_radiance_offset(m) RGBA texels into its buffer; the LUT is kIblLutSize^2 R16G16 UNORM, row = roughness.
@@ -161,11 +168,5 @@ constexpr size_t kIblRadianceTexels = ibl_radiance_offset(kIblRadianceMips);
 // (optional, 4): recorded before the irradiance pass, the radiance pass, the LUT pass and after it.
 void launch_ibl_generation(
     const DeviceScene &s, uint16_t *irradiance, uint16_t *radiance, uint32_t *lut, hipEvent_t *events, hipStream_t stream);
-// deferred shading with evalIBL after the spot lights (ibl = 1), over the maps launch_ibl_generation wrote
-void launch_deferred_shading_ibl(
-    const DeviceScene &s, uint32_t drawType, uint32_t width, uint32_t height, const RestirCamera &cam,
-    const ClusterParams &c, const void *albedoRoughness, const void *normalMetallic, const float *nonLinearDepth,
-    const void *pointers, const uint16_t *indices, const uint16_t *irradiance, const uint16_t *radiance,
-    const uint32_t *lut, float4 *hdr, hipStream_t stream);
 
 } // namespace ppt

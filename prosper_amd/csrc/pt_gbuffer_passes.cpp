@@ -1,8 +1,10 @@
 // pt_gbuffer_passes.cpp — C-ABI of the passes over a G-buffer (include/prosper_pt/prosper_pt.h): ReSTIR-DI
 // (prosper_pt_restir_di_*), the ray-traced G-buffer (prosper_pt_trace_gbuffer), clustered lighting and deferred shading
-// (prosper_pt_cluster_lights, prosper_pt_deferred_shading), image-based lighting (prosper_pt_generate_ibl) and the forward
-// passes (prosper_pt_forward_transparent, prosper_pt_raster_forward, prosper_pt_raster_forward_transparent), with the
-// readbacks of what each produced.  Kernels: pt_gbuffer_kernels.hip, pt_ibl.hip.
+// (prosper_pt_cluster_lights, prosper_pt_deferred_shading), the rasteriser's resolve into the same targets
+// (prosper_pt_raster_resolve), image-based lighting (prosper_pt_generate_ibl) and the texture LOD switches, with the
+// readbacks of what each produced.  The module owns the context's last frame and the lighting inputs, which the other pass
+// modules reach through pt_gbuffer_passes.hpp; the forward passes over them are in pt_forward_passes.cpp.
+// Kernels: pt_gbuffer_kernels.hip, pt_ibl.hip.
 #include "../../include/prosper_pt/prosper_pt.h"
 
 #include <hip/hip_runtime.h>
@@ -14,6 +16,7 @@
 
 #include "pt_context.hpp"
 #include "pt_gbuffer_kernels.hpp"
+#include "pt_gbuffer_passes.hpp"
 #include "pt_kernels.hpp"
 #include "pt_pass_support.hpp"
 #include "pt_raster.hpp"
@@ -30,17 +33,13 @@ struct GBufferPassState
     const void *lastReservoirs = nullptr; // prosper_pt_get_restir_reservoirs_device_ptr
     size_t lastReservoirBytes = 0;
     DeviceBuffer gbuffer; // context-owned G-buffer targets (prosper_pt_trace_gbuffer): 16 + 16 + 4 bytes per pixel
-    prosper_pt_gbuffer_targets gbufferLast = {}; // what the last prosper_pt_trace_gbuffer wrote
-    uint32_t gbufferLastWidth = 0, gbufferLastHeight = 0;
     DeviceBuffer velocity;           // context-owned velocity target (prosper_pt_trace_gbuffer_velocity): 8 bytes per pixel
     DeviceBuffer previousTransforms; // the device copy of a call's previous instance transforms
-    void *velocityLast = nullptr;    // what the last prosper_pt_trace_gbuffer_velocity wrote
+    LastFrame last; // what the last G-buffer or forward frame wrote, here or into the caller's targets
     // prosper_pt_set_texture_lod / _debug: the traced G-buffer samples materials through the mip chains
     bool lodEnabled = false, lodDebug = false;
     float lodBias = 0.0f;
-    DeviceBuffer lodDerivatives; // debug: float4 per pixel of the last traced G-buffer
-    uint32_t lodDerivativesWidth = 0, lodDerivativesHeight = 0; // 0: the last traced G-buffer wrote none
-    uint32_t velocityLastWidth = 0, velocityLastHeight = 0;
+    DeviceBuffer lodDerivatives; // debug: float4 per pixel of the last traced G-buffer (last.derivativesWidth)
     DeviceBuffer clusterPointers; // prosper_pt_cluster_lights: uint2 per cluster
     DeviceBuffer clusterIndices;  // kClusterSlot uint16 entries per cluster
     DeviceBuffer clusterDropped;  // entries dropped, per cluster
@@ -51,41 +50,10 @@ struct GBufferPassState
     DeviceBuffer iblLut;        // kIblLutSize^2 R16G16 UNORM
     StageEvents<3> iblTiming;   // around the three passes of the last generation
     bool iblGenerated = false;    // the maps describe the current scene's sky (cleared by prosper_pt_upload_scene)
-    // what the last clustering was made from: prosper_pt_forward_transparent reuses it for the same camera and lights
+    // what the last clustering was made from: the forward passes reuse it for the same camera and lights
     ClusterParams clusterParams = {};
     uint32_t clusterLightUpdates = 0;
     bool clusterValid = false; // (cleared by prosper_pt_upload_scene)
-    // prosper_pt_forward_transparent
-    DeviceBuffer transparentDepth; // device copy of a call's host depth
-    DeviceBuffer transparentStats; // four uint32: covered pixels, deepest pixel, total layers (64 bits)
-    DeviceBuffer transparentLayers; // debug mode: width*height counts, then width*height*N layer records
-    StageEvents<1> transparentTiming;
-    uint32_t transparentDebugLayers = 0; // prosper_pt_set_transparent_debug_layers
-    bool transparentRan = false, transparentReclustered = false;
-    size_t transparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
-    uint32_t transparentLayerCount = 0;
-    // prosper_pt_raster_forward / _shade
-    DeviceBuffer forwardDepth;    // context-owned depth target: 4 bytes per pixel
-    DeviceBuffer forwardCount;    // kForwardCountSlots counters a cache line apart: the covered pixels of the last call
-    DeviceBuffer forwardSurfaces; // debug mode: one prosper_pt_transparent_layer per pixel
-    Pinned<uint32_t> forwardCountHost;
-    StageEvents<2> forwardTiming; // the clustering | the shade kernel
-    Fence forwardDone;            // behind the last call's copy of the count
-    bool forwardDebugSurfaces = false; // prosper_pt_set_forward_debug_surfaces
-    bool forwardRan = false, forwardReclustered = false;
-    size_t forwardSurfacePixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
-    // prosper_pt_raster_transparent_draw / prosper_pt_raster_forward_transparent
-    DeviceBuffer rasterTransparentDepth;  // device copy of a call's host depth
-    DeviceBuffer rasterTransparentStats;  // kForwardCountSlots sets a cache line apart: pixels with a list, layers shaded, longest list
-    DeviceBuffer rasterTransparentLayers; // debug mode: width*height counts, then width*height*N layer records
-    Pinned<uint32_t> rasterTransparentStatsHost;
-    StageEvents<4> rasterTransparentTiming; // count | scan | fill | resolve (its clustering included)
-    Fence rasterTransparentDone;            // behind the last call's copy of the stats
-    uint32_t rasterTransparentDebugLayers = 0; // prosper_pt_set_raster_transparent_debug_layers
-    uint32_t rasterTransparentFragments = 0;
-    bool rasterTransparentRan = false, rasterTransparentReclustered = false;
-    size_t rasterTransparentLayerPixels = 0; // of the last call in debug mode (0: it did not run in debug mode)
-    uint32_t rasterTransparentLayerCount = 0;
 };
 
 void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias)
@@ -94,14 +62,62 @@ void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias)
     *bias = ctx->gbufferPasses->lodBias;
 }
 
+const GBufferLodParams *gbuffer_lod_params(const prosper_pt_ctx *ctx, GBufferLodParams &storage)
+{
+    storage = GBufferLodParams{ctx->textureMips, ctx->gbufferPasses->lodBias, nullptr};
+    return ctx->gbufferPasses->lodEnabled && ctx->textureMips ? &storage : nullptr;
+}
+
+void LastFrame::set_gbuffer(const prosper_pt_gbuffer_targets &t, void *v, uint32_t w, uint32_t h)
+{
+    targets = t;
+    width = w;
+    height = h;
+    forwardDepthOwned = false;
+    if (!v) return;
+    velocity = v;
+    velocityWidth = w;
+    velocityHeight = h;
+}
+
+void LastFrame::set_forward(float *depth, bool depthOwned, void *v, uint32_t w, uint32_t h)
+{
+    prosper_pt_gbuffer_targets t = {};
+    t.nonLinearDepth = depth;
+    set_gbuffer(t, v, w, h);
+    forwardDepthOwned = depthOwned;
+    derivativesWidth = derivativesHeight = 0;
+}
+
+void LastFrame::forget_if_in(const DeviceBuffer &b)
+{
+    if (lies_in(b, targets.albedoRoughness) || lies_in(b, targets.normalMetallic) || lies_in(b, targets.nonLinearDepth))
+    {
+        targets = prosper_pt_gbuffer_targets{};
+        width = height = 0;
+        forwardDepthOwned = false;
+    }
+    if (lies_in(b, velocity))
+    {
+        velocity = nullptr;
+        velocityWidth = velocityHeight = 0;
+    }
+}
+
+int LastFrame::depth(const float **out, uint32_t *w, uint32_t *h) const
+{
+    if (!targets.nonLinearDepth) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    *out = targets.nonLinearDepth;
+    *w = width;
+    *h = height;
+    return PROSPER_PT_OK;
+}
+
+LastFrame &gbuffer_last_frame(prosper_pt_ctx *ctx) { return ctx->gbufferPasses->last; }
+
 int gbuffer_last_depth(prosper_pt_ctx *ctx, const float **depth, uint32_t *width, uint32_t *height)
 {
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.gbufferLast.nonLinearDepth) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
-    *depth = st.gbufferLast.nonLinearDepth;
-    *width = st.gbufferLastWidth;
-    *height = st.gbufferLastHeight;
-    return PROSPER_PT_OK;
+    return ctx->gbufferPasses->last.depth(depth, width, height);
 }
 
 bool create_gbuffer_passes(prosper_pt_ctx *ctx)
@@ -119,37 +135,34 @@ void destroy_gbuffer_passes(prosper_pt_ctx *ctx)
 void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
 {
     const GBufferPassState &st = *ctx->gbufferPasses;
-    // only targets the context owns: a caller's buffers may be gone by the time someone looks
-    const auto owned = [](const DeviceBuffer &b, const void *p) {
-        return p && b.ptr && (const uint8_t *)p >= b.as<uint8_t>() && (const uint8_t *)p < b.as<uint8_t>() + b.bytes;
-    };
-    const bool g = owned(st.gbuffer, st.gbufferLast.albedoRoughness) && owned(st.gbuffer, st.gbufferLast.normalMetallic) &&
-                   owned(st.gbuffer, st.gbufferLast.nonLinearDepth);
-    // a forward frame leaves a depth and no attribute targets (prosper_pt_raster_forward)
-    const bool forwardDepth = !st.gbufferLast.albedoRoughness && owned(st.forwardDepth, st.gbufferLast.nonLinearDepth);
+    const LastFrame &last = st.last;
+    // only targets the context owns: a caller's buffers may be gone by the time someone looks.  A forward frame leaves a
+    // depth and no attribute targets (prosper_pt_raster_forward)
+    const bool g = LastFrame::lies_in(st.gbuffer, last.targets.albedoRoughness) && LastFrame::lies_in(st.gbuffer, last.targets.normalMetallic) &&
+                   LastFrame::lies_in(st.gbuffer, last.targets.nonLinearDepth);
     const struct
     {
         const char *name;
         uint32_t format;
         const void *ptr;
         bool valid;
-    } targets[3] = {{"albedoRoughness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.albedoRoughness, g},
-                    {"normalMetalness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, st.gbufferLast.normalMetallic, g},
-                    {"depth", PROSPER_PT_DEBUG_FORMAT_R32F, st.gbufferLast.nonLinearDepth, g || forwardDepth}};
+    } targets[3] = {{"albedoRoughness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, last.targets.albedoRoughness, g},
+                    {"normalMetalness", PROSPER_PT_DEBUG_FORMAT_RGBA32F, last.targets.normalMetallic, g},
+                    {"depth", PROSPER_PT_DEBUG_FORMAT_R32F, last.targets.nonLinearDepth, g || last.forwardDepthOwned}};
     for (const auto &t : targets)
     {
         DebugImage im;
         im.name = t.name;
         im.format = t.format;
         im.valid = t.valid;
-        if (t.valid) im.one_level(t.ptr, st.gbufferLastWidth, st.gbufferLastHeight);
+        if (t.valid) im.one_level(t.ptr, last.width, last.height);
         out.push_back(im);
     }
     DebugImage v;
     v.name = "velocity";
     v.format = PROSPER_PT_DEBUG_FORMAT_RG32F;
-    v.valid = owned(st.velocity, st.velocityLast);
-    if (v.valid) v.one_level(st.velocityLast, st.velocityLastWidth, st.velocityLastHeight);
+    v.valid = LastFrame::lies_in(st.velocity, last.velocity);
+    if (v.valid) v.one_level(last.velocity, last.velocityWidth, last.velocityHeight);
     out.push_back(v);
     DebugImage lut;
     lut.name = "SpecularBrdfLut";
@@ -165,12 +178,6 @@ void forget_ibl_maps(prosper_pt_ctx *ctx)
     ctx->gbufferPasses->clusterValid = false; // the clustering describes the old scene's lights too
 }
 
-} // namespace ppt
-
-namespace
-{
-
-// The camera terms a pass needs to rebuild a G-buffer texel's surface (RestirCamera)
 RestirCamera gbuffer_camera(const prosper_CameraUniforms *camera)
 {
     RestirCamera c;
@@ -184,6 +191,71 @@ RestirCamera gbuffer_camera(const prosper_CameraUniforms *camera)
     c.cameraToClip32 = c2c[3 * 4 + 2]; // column 3, row 2
     return c;
 }
+
+GBufferTraceParams gbuffer_trace_params(
+    uint32_t drawType, uint32_t frameIndex, bool jitter, bool opaqueOnly, const prosper_CameraUniforms *camera, uint32_t width,
+    uint32_t height)
+{
+    GBufferTraceParams g = {};
+    set_camera_ray_params(g.r, camera);
+    g.r.width = width;
+    g.r.height = height;
+    g.r.localWidth = width;
+    g.r.stripeCount = 1;
+    g.r.frameCount = 1;
+    // worldToClip = cameraToClip * worldToCamera (column-major), in double, rounded once
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r)
+        {
+            double v = 0.0;
+            for (int k = 0; k < 4; ++k)
+                v += (double)(&camera->cameraToClip.col[k].x)[r] * (double)(&camera->worldToCamera.col[c].x)[k];
+            g.worldToClip[c * 4 + r] = (float)v;
+        }
+    g.drawType = drawType;
+    g.frameIndex = frameIndex;
+    g.jitter = jitter ? 1u : 0u;
+    g.opaqueOnly = opaqueOnly ? 1u : 0u;
+    return g;
+}
+
+void velocity_camera_terms(GBufferVelocityParams &v, const prosper_CameraUniforms *camera)
+{
+    std::memcpy(v.worldToCamera, &camera->worldToCamera, 64);
+    std::memcpy(v.cameraToClip, &camera->cameraToClip, 64);
+    std::memcpy(v.previousWorldToCamera, &camera->previousWorldToCamera, 64);
+    std::memcpy(v.previousCameraToClip, &camera->previousCameraToClip, 64);
+    for (int k = 0; k < 2; ++k)
+    {
+        v.currentJitter[k] = camera->currentJitter[k];
+        v.previousJitter[k] = camera->previousJitter[k];
+    }
+}
+
+int velocity_owned_target(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, float2 **out)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const int rc = st.last.grow(st.velocity, pixels * 8u, s);
+    *out = st.velocity.as<float2>();
+    return rc;
+}
+
+int upload_previous_transforms(
+    prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t s, const prosper_ModelInstanceTransforms **out)
+{
+    GBufferPassState &st = *ctx->gbufferPasses;
+    const size_t bytes = sizeof(prosper_ModelInstanceTransforms) * (size_t)count;
+    const int rc = grow_to(st.previousTransforms, bytes, s);
+    if (rc != PROSPER_PT_OK) return rc;
+    PPT_HIP(hipMemcpyAsync(st.previousTransforms.ptr, transforms, bytes, hipMemcpyHostToDevice, s));
+    *out = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
+    return PROSPER_PT_OK;
+}
+
+} // namespace ppt
+
+namespace
+{
 
 // The G-buffer (and, with `withReservoirs`, the reservoirs) on the device: host inputs are copied into hostInputs,
 // 16 + 16 + 8 + 4 bytes per pixel.
@@ -260,90 +332,12 @@ int restir_trace(
 int gbuffer_owned_targets(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, prosper_pt_gbuffer_targets &out)
 {
     GBufferPassState &st = *ctx->gbufferPasses;
-    const size_t need = pixels * 36u + 64u;
-    if (st.gbuffer.bytes < need || !st.gbuffer.ptr)
-    {
-        if (st.gbufferLast.albedoRoughness == st.gbuffer.ptr)
-        {
-            st.gbufferLast = prosper_pt_gbuffer_targets{};
-            st.gbufferLastWidth = st.gbufferLastHeight = 0;
-        }
-        const int rc = grow_buffer(st.gbuffer, GrowWait::Stream, s, need, need);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
+    const int rc = st.last.grow(st.gbuffer, pixels * 36u + 64u, s);
+    if (rc != PROSPER_PT_OK) return rc;
     uint8_t *base = st.gbuffer.as<uint8_t>();
     out.albedoRoughness = base;
     out.normalMetallic = base + pixels * 16u;
     out.nonLinearDepth = reinterpret_cast<float *>(base + pixels * 32u);
-    return PROSPER_PT_OK;
-}
-
-// The camera ray, the depth's worldToClip and the switches of a G-buffer trace (the transparent pass follows the same ray)
-GBufferTraceParams gbuffer_trace_params(
-    uint32_t drawType, uint32_t frameIndex, bool jitter, bool opaqueOnly, const prosper_CameraUniforms *camera, uint32_t width,
-    uint32_t height)
-{
-    GBufferTraceParams g = {};
-    set_camera_ray_params(g.r, camera);
-    g.r.width = width;
-    g.r.height = height;
-    g.r.localWidth = width;
-    g.r.stripeCount = 1;
-    g.r.frameCount = 1;
-    // worldToClip = cameraToClip * worldToCamera (column-major), in double, rounded once
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 4; ++r)
-        {
-            double v = 0.0;
-            for (int k = 0; k < 4; ++k)
-                v += (double)(&camera->cameraToClip.col[k].x)[r] * (double)(&camera->worldToCamera.col[c].x)[k];
-            g.worldToClip[c * 4 + r] = (float)v;
-        }
-    g.drawType = drawType;
-    g.frameIndex = frameIndex;
-    g.jitter = jitter ? 1u : 0u;
-    g.opaqueOnly = opaqueOnly ? 1u : 0u;
-    return g;
-}
-
-// the matrices and jitters a velocity target is computed from
-void velocity_camera_terms(GBufferVelocityParams &v, const prosper_CameraUniforms *camera)
-{
-    std::memcpy(v.worldToCamera, &camera->worldToCamera, 64);
-    std::memcpy(v.cameraToClip, &camera->cameraToClip, 64);
-    std::memcpy(v.previousWorldToCamera, &camera->previousWorldToCamera, 64);
-    std::memcpy(v.previousCameraToClip, &camera->previousCameraToClip, 64);
-    for (int k = 0; k < 2; ++k)
-    {
-        v.currentJitter[k] = camera->currentJitter[k];
-        v.previousJitter[k] = camera->previousJitter[k];
-    }
-}
-
-// the context-owned velocity target, 8 bytes per pixel, grown like hostInputs
-int velocity_owned_target(prosper_pt_ctx *ctx, size_t pixels, hipStream_t s, float2 **out)
-{
-    GBufferPassState &st = *ctx->gbufferPasses;
-    if (st.velocity.bytes < pixels * 8u && st.velocityLast == st.velocity.ptr)
-    {
-        st.velocityLast = nullptr;
-        st.velocityLastWidth = st.velocityLastHeight = 0;
-    }
-    const int rc = grow_to(st.velocity, pixels * 8u, s);
-    *out = st.velocity.as<float2>();
-    return rc;
-}
-
-// the device copy of a call's previous instance transforms, enqueued on `s`
-int upload_previous_transforms(
-    prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t s, const prosper_ModelInstanceTransforms **out)
-{
-    GBufferPassState &st = *ctx->gbufferPasses;
-    const size_t bytes = sizeof(prosper_ModelInstanceTransforms) * (size_t)count;
-    const int rc = grow_to(st.previousTransforms, bytes, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    PPT_HIP(hipMemcpyAsync(st.previousTransforms.ptr, transforms, bytes, hipMemcpyHostToDevice, s));
-    *out = st.previousTransforms.as<prosper_ModelInstanceTransforms>();
     return PROSPER_PT_OK;
 }
 
@@ -360,17 +354,17 @@ int gbuffer_trace(
     const int orc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
     if (orc != PROSPER_PT_OK) return orc;
     wait_for_slot(ctx->slots[0], s);
-    GBufferPassState &lst = *ctx->gbufferPasses;
-    GBufferLodParams lodParams{ctx->textureMips, lst.lodBias, nullptr};
-    const GBufferLodParams *lod = lst.lodEnabled && ctx->textureMips ? &lodParams : nullptr;
-    lst.lodDerivativesWidth = lst.lodDerivativesHeight = 0;
-    if (lod && lst.lodDebug)
+    GBufferPassState &st = *ctx->gbufferPasses;
+    GBufferLodParams lodParams;
+    const GBufferLodParams *lod = gbuffer_lod_params(ctx, lodParams);
+    st.last.derivativesWidth = st.last.derivativesHeight = 0;
+    if (lod && st.lodDebug)
     {
-        const int grc = grow_to(lst.lodDerivatives, (size_t)width * height * sizeof(float4), s);
+        const int grc = grow_to(st.lodDerivatives, (size_t)width * height * sizeof(float4), s);
         if (grc != PROSPER_PT_OK) return grc;
-        lodParams.derivatives = lst.lodDerivatives.as<float4>();
-        lst.lodDerivativesWidth = width;
-        lst.lodDerivativesHeight = height;
+        lodParams.derivatives = st.lodDerivatives.as<float4>();
+        st.last.derivativesWidth = width;
+        st.last.derivativesHeight = height;
     }
     if (velocity)
     {
@@ -385,16 +379,7 @@ int gbuffer_trace(
         launch_gbuffer_trace(ctx->scene, g, t.albedoRoughness, t.normalMetallic, t.nonLinearDepth, ovf, s, lod);
     release_slot(ctx->slots[0], s);
     PPT_HIP(hipGetLastError());
-    GBufferPassState &st = *ctx->gbufferPasses;
-    st.gbufferLast = t;
-    st.gbufferLastWidth = width;
-    st.gbufferLastHeight = height;
-    if (velocity)
-    {
-        st.velocityLast = velocity->velocity;
-        st.velocityLastWidth = width;
-        st.velocityLastHeight = height;
-    }
+    st.last.set_gbuffer(t, velocity ? velocity->velocity : nullptr, width, height);
     return PROSPER_PT_OK;
 }
 
@@ -463,16 +448,6 @@ int cluster_lights(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s)
     return PROSPER_PT_OK;
 }
 
-// The forward passes' clustering: the lists of the last clustering serve when they were made from the same camera terms,
-// extent and lights (*reused); otherwise the lights are clustered on `s`
-int cluster_lights_unless_current(prosper_pt_ctx *ctx, const ClusterParams &c, hipStream_t s, bool *reused)
-{
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    const uint32_t lightUpdates = ctx->lights ? ctx->lights->updates : 0u;
-    *reused = st.clusterValid && std::memcmp(&st.clusterParams, &c, sizeof(c)) == 0 && st.clusterLightUpdates == lightUpdates;
-    return *reused ? PROSPER_PT_OK : cluster_lights(ctx, c, s);
-}
-
 // near_ and far_ feed log(far / near) and pow(far / near, s): both positive and ordered
 bool cluster_camera_ok(const prosper_CameraUniforms *camera)
 {
@@ -497,6 +472,54 @@ void strip_cube_borders(const std::vector<uint16_t> &bordered, uint32_t n, uint3
 }
 
 } // namespace
+
+int ppt::check_lit_pass(const char *what, const prosper_pt_ctx *ctx, uint32_t drawType, uint32_t ibl, const prosper_CameraUniforms *camera)
+{
+    if (drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
+    if (ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
+    if (ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
+        return fail(PROSPER_PT_ERR_UNSUPPORTED,
+                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
+    if (!cluster_camera_ok(camera))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
+    return PROSPER_PT_OK;
+}
+
+int ppt::check_velocity_inputs(
+    const char *what, prosper_pt_ctx *ctx, const void *velocity, const prosper_ModelInstanceTransforms *previousTransforms, uint32_t previousTransformCount)
+{
+    if (reinterpret_cast<uintptr_t>(velocity) & 7u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the velocity target must be 8-byte aligned");
+    if (!previousTransforms && previousTransformCount != 0u)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount without previousTransforms");
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    const int crc = check_scene(ctx, what);
+    if (crc != PROSPER_PT_OK) return crc;
+    if (previousTransforms && previousTransformCount != ctx->scene.modelInstanceCount)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
+    return PROSPER_PT_OK;
+}
+
+int ppt::clustered_lights(
+    prosper_pt_ctx *ctx, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, bool ibl, hipStream_t s, ClusteredLights *out,
+    bool *reused)
+{
+    const GBufferPassState &st = *ctx->gbufferPasses;
+    const ClusterParams c = cluster_params(camera, width, height);
+    const uint32_t lightUpdates = ctx->lights ? ctx->lights->updates : 0u;
+    const bool current = reused && st.clusterValid && std::memcmp(&st.clusterParams, &c, sizeof(c)) == 0 && st.clusterLightUpdates == lightUpdates;
+    if (reused) *reused = current;
+    if (!current)
+        if (const int rc = cluster_lights(ctx, c, s)) return rc;
+    *out = ClusteredLights{c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), nullptr, nullptr, nullptr};
+    if (ibl)
+    {
+        out->irradiance = st.iblIrradiance.as<uint16_t>();
+        out->radiance = st.iblRadiance.as<uint16_t>();
+        out->lut = st.iblLut.as<uint32_t>();
+    }
+    return PROSPER_PT_OK;
+}
 
 extern "C" {
 
@@ -628,16 +651,7 @@ static int check_velocity_desc(
     if ((reinterpret_cast<uintptr_t>(given.albedoRoughness) | reinterpret_cast<uintptr_t>(given.normalMetallic) |
          reinterpret_cast<uintptr_t>(given.nonLinearDepth)) & 15u)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": targets must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(desc->velocity) & 7u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the velocity target must be 8-byte aligned");
-    if (!desc->previousTransforms && desc->previousTransformCount != 0u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount without previousTransforms");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    const int crc = check_scene(ctx, what);
-    if (crc != PROSPER_PT_OK) return crc;
-    if (desc->previousTransforms && desc->previousTransformCount != ctx->scene.modelInstanceCount)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
-    return PROSPER_PT_OK;
+    return check_velocity_inputs(what, ctx, desc->velocity, desc->previousTransforms, desc->previousTransformCount);
 }
 
 // The velocity entry, and the rasteriser's resolve (`raster`), which takes the same targets under the same rules
@@ -699,391 +713,14 @@ int prosper_pt_raster_gbuffer(
     return velocity_gbuffer(what, true, ctx, drawType, 0u, 0u, camera, camera->resolution[0], camera->resolution[1], desc, stream);
 }
 
-// ---- forward opaque pass (src/render/ForwardRenderer.cpp recordOpaque) ----
-
-constexpr size_t kForwardCountBytes = (size_t)kForwardCountSlots * kForwardCountStride * sizeof(uint32_t);
-
-// What both forward entries refuse of their arguments, before anything is enqueued (and, for prosper_pt_raster_forward,
-// before the culling phases replace the lists)
-static int check_forward_opaque(
-    const char *what, prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (!pc || !camera || !desc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
-    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
-        return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
-    if (reinterpret_cast<uintptr_t>(desc->nonLinearDepth) & 3u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the depth target must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(desc->velocity) & 7u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the velocity target must be 8-byte aligned");
-    if (!desc->previousTransforms && desc->previousTransformCount != 0u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount without previousTransforms");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    const int crc = check_scene(ctx, what);
-    if (crc != PROSPER_PT_OK) return crc;
-    if (desc->previousTransforms && desc->previousTransformCount != ctx->scene.modelInstanceCount)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": previousTransformCount differs from the scene's modelInstanceCount");
-    return PROSPER_PT_OK;
-}
-
-// The shade over the visibility image as it stands: what the resolve refuses is refused before the HDR image, the depth or
-// the velocity are touched; then the targets, the clustering (unless the last one serves) and the kernel, all on `s`.
-static int forward_shade(
-    const char *what, prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc,
-    void *stream)
-{
-    if (const int rc = check_forward_opaque(what, ctx, pc, camera, desc)) return rc;
-    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    RasterResolveTables tables = {};
-    if ((rc = raster_resolve_tables(ctx, what, width, height, s, &tables)) != PROSPER_PT_OK) return rc;
-    GBufferPassState &st = *ctx->gbufferPasses;
-    const size_t pixels = (size_t)width * height;
-    float *depth = desc->nonLinearDepth;
-    if (!depth)
-    {
-        if (st.forwardDepth.bytes < pixels * 4u && st.gbufferLast.nonLinearDepth == st.forwardDepth.ptr)
-        {
-            st.gbufferLast = prosper_pt_gbuffer_targets{};
-            st.gbufferLastWidth = st.gbufferLastHeight = 0;
-        }
-        if ((rc = grow_to(st.forwardDepth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
-        depth = st.forwardDepth.as<float>();
-    }
-    GBufferVelocityParams v = {};
-    v.velocity = static_cast<float2 *>(desc->velocity);
-    if (!desc->velocity && (rc = velocity_owned_target(ctx, pixels, s, &v.velocity)) != PROSPER_PT_OK) return rc;
-    if (desc->previousTransforms &&
-        (rc = upload_previous_transforms(ctx, desc->previousTransforms, desc->previousTransformCount, s, &v.previousTransforms)) != PROSPER_PT_OK)
-        return rc;
-    velocity_camera_terms(v, camera);
-    if ((rc = prepare_hdr(ctx, width, height, nullptr, s)) != PROSPER_PT_OK) return rc;
-    if ((rc = grow_to(st.forwardCount, kForwardCountBytes, s)) != PROSPER_PT_OK) return rc;
-    if (!st.forwardCountHost.ptr && (rc = st.forwardCountHost.allocate(kForwardCountBytes)) != PROSPER_PT_OK) return rc;
-    const bool debug = st.forwardDebugSurfaces;
-    if (debug && (rc = grow_to(st.forwardSurfaces, pixels * sizeof(prosper_pt_transparent_layer), s)) != PROSPER_PT_OK) return rc;
-    if ((rc = st.forwardTiming.create()) != PROSPER_PT_OK) return rc;
-    st.forwardRan = false;
-    st.forwardSurfacePixels = 0;
-
-    PPT_HIP(hipEventRecord(st.forwardTiming.events[0], s));
-    const ClusterParams c = cluster_params(camera, width, height);
-    bool reuse = false;
-    if ((rc = cluster_lights_unless_current(ctx, c, s, &reuse)) != PROSPER_PT_OK) return rc;
-    PPT_HIP(hipMemsetAsync(st.forwardCount.ptr, 0, kForwardCountBytes, s));
-    PPT_HIP(hipEventRecord(st.forwardTiming.events[1], s));
-
-    // previousTransformValid is not read: desc->previousTransforms decides
-    const GBufferTraceParams g = gbuffer_trace_params(pc->drawType, 0u, false, false, camera, width, height);
-    const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
-    const bool ibl = pc->ibl == 1u;
-    launch_forward_opaque(
-        ctx->scene, g, tables, v, c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
-        ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, depth, st.forwardCount.as<uint32_t>(),
-        debug ? st.forwardSurfaces.as<prosper_pt_transparent_layer>() : nullptr, s, st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
-    PPT_HIP(hipGetLastError());
-    PPT_HIP(hipEventRecord(st.forwardTiming.events[2], s));
-    PPT_HIP(hipMemcpyAsync(st.forwardCountHost.ptr, st.forwardCount.ptr, kForwardCountBytes, hipMemcpyDeviceToHost, s));
-    if ((rc = st.forwardDone.record(s)) != PROSPER_PT_OK) return rc;
-    if ((rc = raster_resolve_enqueued(ctx, s)) != PROSPER_PT_OK) return rc;
-    st.forwardRan = true;
-    st.forwardReclustered = !reuse;
-    st.forwardSurfacePixels = debug ? pixels : 0u;
-    // a forward frame has a depth and a velocity, and no attribute targets
-    st.gbufferLast = prosper_pt_gbuffer_targets{};
-    st.gbufferLast.nonLinearDepth = depth;
-    st.gbufferLastWidth = width;
-    st.gbufferLastHeight = height;
-    st.lodDerivativesWidth = st.lodDerivativesHeight = 0;
-    st.velocityLast = v.velocity;
-    st.velocityLastWidth = width;
-    st.velocityLastHeight = height;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_raster_forward_shade(
-    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream)
-{
-    return forward_shade("prosper_pt_raster_forward_shade", ctx, pc, camera, desc, stream);
-}
-
-int prosper_pt_raster_forward(
-    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const prosper_pt_forward_opaque_desc *desc, void *stream)
-{
-    const char *what = "prosper_pt_raster_forward";
-    // what the shade would refuse of its arguments is refused before the culling phases replace the lists
-    if (const int rc = check_forward_opaque(what, ctx, pc, camera, desc)) return rc;
-    const int rc = prosper_pt_raster_visibility(ctx, camera, stream);
-    if (rc != PROSPER_PT_OK) return rc;
-    return forward_shade(what, ctx, pc, camera, desc, stream);
-}
-
-// ---- rasterised transparent pass (ForwardRenderer::recordTransparent over the draw lists) ----
-
-// What both entries refuse, before anything is enqueued (and, for prosper_pt_raster_forward_transparent, before the culling
-// phase replaces the lists): the draw's refusals, prosper_pt_forward_transparent's for pc, ibl, the camera and the depth
-// argument, and an HDR image or a depth of another extent than camera->resolution.  *depth: the device depth to test
-// against, nullptr where a host depth has to be copied first.
-static int check_raster_transparent(
-    const char *what, prosper_pt_ctx *ctx, uint32_t which, bool listNeeded, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera,
-    const float *nonLinearDepth, uint32_t onDevice, const float **depth)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    if (which != PROSPER_PT_DRAW_LIST_GENERATED && which != PROSPER_PT_DRAW_LIST_FIRST_PHASE && which != PROSPER_PT_DRAW_LIST_SECOND_PHASE)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the list is GENERATED, FIRST_PHASE or SECOND_PHASE");
-    if (!pc || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
-    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
-        return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
-    if (reinterpret_cast<uintptr_t>(nonLinearDepth) & 3u)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the depth must be 4-byte aligned");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    if (const int rc = raster_layers_check(ctx, what, which, listNeeded, camera)) return rc;
-    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
-    if (!hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the HDR image's extent is not camera->resolution");
-    *depth = onDevice ? nonLinearDepth : nullptr;
-    if (!nonLinearDepth)
-    {
-        uint32_t w = 0, h = 0;
-        if (const int rc = gbuffer_last_depth(ctx, depth, &w, &h)) return rc;
-        if (w != width || h != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the context's last depth has another extent than camera->resolution");
-    }
-    return PROSPER_PT_OK;
-}
-
-static int raster_transparent(
-    const char *what, prosper_pt_ctx *ctx, uint32_t which, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera,
-    const float *nonLinearDepth, uint32_t onDevice, void *stream)
-{
-    const float *depth = nullptr;
-    if (const int rc = check_raster_transparent(what, ctx, which, true, pc, camera, nonLinearDepth, onDevice, &depth)) return rc;
-    const uint32_t width = camera->resolution[0], height = camera->resolution[1];
-    const size_t pixels = (size_t)width * height;
-    GBufferPassState &st = *ctx->gbufferPasses;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipSetDevice(ctx->device));
-    int rc = flush_scene_updates(ctx, s, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    if ((rc = st.rasterTransparentDone.wait(s)) != PROSPER_PT_OK) return rc; // (a call on another stream may still copy the stats)
-    if (!depth)
-    {
-        if ((rc = grow_to(st.rasterTransparentDepth, pixels * 4u, s)) != PROSPER_PT_OK) return rc;
-        PPT_HIP(hipMemcpyAsync(st.rasterTransparentDepth.ptr, nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
-        depth = st.rasterTransparentDepth.as<float>();
-    }
-    if ((rc = grow_to(st.rasterTransparentStats, kForwardCountBytes, s)) != PROSPER_PT_OK) return rc;
-    if (!st.rasterTransparentStatsHost.ptr && (rc = st.rasterTransparentStatsHost.allocate(kForwardCountBytes)) != PROSPER_PT_OK) return rc;
-    const uint32_t debugLayers = st.rasterTransparentDebugLayers;
-    if (debugLayers &&
-        (rc = grow_to(st.rasterTransparentLayers, pixels * (4u + (size_t)debugLayers * sizeof(prosper_pt_transparent_layer)), s)) != PROSPER_PT_OK)
-        return rc;
-    if ((rc = st.rasterTransparentTiming.create()) != PROSPER_PT_OK) return rc;
-    st.rasterTransparentRan = false;
-    st.rasterTransparentLayerPixels = 0;
-
-    RasterLayerLists lists = {};
-    RasterResolveTables tables = {};
-    if ((rc = raster_layers_build(ctx, what, which, camera, depth, s, st.rasterTransparentTiming.events, &lists, &tables)) != PROSPER_PT_OK) return rc;
-    bool reuse = true;
-    PPT_HIP(hipMemsetAsync(st.rasterTransparentStats.ptr, 0, kForwardCountBytes, s));
-    uint32_t *counts = debugLayers ? st.rasterTransparentLayers.as<uint32_t>() : nullptr;
-    if (lists.total != 0u)
-    {
-        const ClusterParams c = cluster_params(camera, width, height);
-        if ((rc = cluster_lights_unless_current(ctx, c, s, &reuse)) != PROSPER_PT_OK) return rc;
-        GBufferVelocityParams v = {};
-        velocity_camera_terms(v, camera);
-        const GBufferTraceParams g = gbuffer_trace_params(pc->drawType, 0u, false, false, camera, width, height);
-        const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
-        const bool ibl = pc->ibl == 1u;
-        launch_raster_transparent(
-            ctx->scene, g, tables, lists, v, c, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
-            ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, st.rasterTransparentStats.as<uint32_t>(),
-            debugLayers, counts, debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s,
-            st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
-        PPT_HIP(hipGetLastError());
-    }
-    else if (debugLayers)
-        PPT_HIP(hipMemsetAsync(counts, 0, pixels * 4u, s)); // (no list anywhere: every pixel has 0 layers)
-    PPT_HIP(hipEventRecord(st.rasterTransparentTiming.events[4], s));
-    PPT_HIP(hipMemcpyAsync(st.rasterTransparentStatsHost.ptr, st.rasterTransparentStats.ptr, kForwardCountBytes, hipMemcpyDeviceToHost, s));
-    if ((rc = st.rasterTransparentDone.record(s)) != PROSPER_PT_OK) return rc;
-    if ((rc = raster_resolve_enqueued(ctx, s)) != PROSPER_PT_OK) return rc;
-    st.rasterTransparentRan = true;
-    st.rasterTransparentReclustered = !reuse;
-    st.rasterTransparentFragments = lists.total;
-    st.rasterTransparentLayerPixels = debugLayers ? pixels : 0u;
-    st.rasterTransparentLayerCount = debugLayers;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_raster_transparent_draw(
-    prosper_pt_ctx *ctx, uint32_t which, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth,
-    uint32_t onDevice, void *stream)
-{
-    return raster_transparent("prosper_pt_raster_transparent_draw", ctx, which, pc, camera, nonLinearDepth, onDevice, stream);
-}
-
-int prosper_pt_raster_forward_transparent(
-    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, const prosper_CameraUniforms *camera, const float *nonLinearDepth, uint32_t onDevice,
-    void *stream)
-{
-    const char *what = "prosper_pt_raster_forward_transparent";
-    // what the draw would refuse of its arguments is refused before the culling phase replaces the lists
-    const float *depth = nullptr;
-    if (const int rc = check_raster_transparent(what, ctx, PROSPER_PT_DRAW_LIST_FIRST_PHASE, false, pc, camera, nonLinearDepth, onDevice, &depth)) return rc;
-    // ForwardRenderer.cpp:222-260: the TRANSPARENT list culled once, without a pyramid and without a second phase
-    const int rc = prosper_pt_cull_meshlets_first_phase(ctx, PROSPER_PT_CULL_MODE_TRANSPARENT, camera, PROSPER_PT_NO_HIZ, stream);
-    if (rc != PROSPER_PT_OK) return rc;
-    return raster_transparent(what, ctx, PROSPER_PT_DRAW_LIST_FIRST_PHASE, pc, camera, nonLinearDepth, onDevice, stream);
-}
-
-int prosper_pt_get_raster_transparent_info(prosper_pt_ctx *ctx, prosper_pt_raster_transparent_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_raster_transparent_info: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.rasterTransparentRan) return fail(PROSPER_PT_ERR_NO_SCENE, "the rasterised transparent pass has not run yet");
-    PPT_HIP(hipSetDevice(ctx->device));
-    prosper_pt_raster_transparent_info info = {};
-    info.fragments = st.rasterTransparentFragments; // (the host read it between scan and fill)
-    info.reclustered = st.rasterTransparentReclustered ? 1u : 0u;
-    *out = info;
-    if (!st.rasterTransparentDone.passed()) return PROSPER_PT_NOT_READY;
-    for (uint32_t k = 0; k < kForwardCountSlots; ++k)
-    {
-        const uint32_t *slot = st.rasterTransparentStatsHost.ptr + k * kForwardCountStride;
-        info.coveredPixels += slot[0];
-        info.shadedLayers += slot[1];
-        info.maxLayers = slot[2] > info.maxLayers ? slot[2] : info.maxLayers;
-    }
-    float ms[4] = {};
-    if (const int rc = st.rasterTransparentTiming.elapsed(ms)) return rc; // (behind the fence that has passed: no wait)
-    info.countMs = ms[0];
-    info.scanMs = ms[1];
-    info.fillMs = ms[2];
-    info.resolveMs = ms[3];
-    *out = info;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_set_raster_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_raster_transparent_debug_layers: null argument");
-    if (layersPerPixel > 128u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_raster_transparent_debug_layers: at most 128 layers per pixel");
-    ctx->gbufferPasses->rasterTransparentDebugLayers = layersPerPixel;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_raster_transparent_layers(
-    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels, uint32_t layersPerPixel, void *stream)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_transparent_layers: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.rasterTransparentRan || !st.rasterTransparentLayerPixels)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last rasterised transparent pass did not run in debug mode (prosper_pt_set_raster_transparent_debug_layers)");
-    if (pixels != st.rasterTransparentLayerPixels || layersPerPixel != st.rasterTransparentLayerCount)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_transparent_layers: pixels or layersPerPixel differ from the call's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = st.rasterTransparentDone.wait(s)) return rc;
-    const uint32_t *counts = st.rasterTransparentLayers.as<uint32_t>();
-    if (host_counts) PPT_HIP(hipMemcpyAsync(host_counts, counts, pixels * 4u, hipMemcpyDeviceToHost, s));
-    if (host_layers)
-        PPT_HIP(hipMemcpyAsync(host_layers, counts + pixels, pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_set_forward_debug_surfaces(prosper_pt_ctx *ctx, int enabled)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_forward_debug_surfaces: null argument");
-    ctx->gbufferPasses->forwardDebugSurfaces = enabled != 0;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_forward_surfaces(prosper_pt_ctx *ctx, prosper_pt_transparent_layer *out, size_t pixels, void *stream)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_surfaces: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.forwardRan || !st.forwardSurfacePixels)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last forward opaque pass did not run in debug mode (prosper_pt_set_forward_debug_surfaces)");
-    if (pixels != st.forwardSurfacePixels)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_surfaces: pixel count differs from the call's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = st.forwardDone.wait(s)) return rc;
-    PPT_HIP(hipMemcpyAsync(out, st.forwardSurfaces.ptr, pixels * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_forward_opaque_info(prosper_pt_ctx *ctx, prosper_pt_forward_opaque_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_forward_opaque_info: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.forwardRan) return fail(PROSPER_PT_ERR_NO_SCENE, "the forward opaque pass has not run yet");
-    PPT_HIP(hipSetDevice(ctx->device));
-    prosper_pt_forward_opaque_info info = {};
-    info.reclustered = st.forwardReclustered ? 1u : 0u;
-    *out = info;
-    if (!st.forwardDone.passed()) return PROSPER_PT_NOT_READY;
-    float ms[2] = {};
-    if (const int rc = st.forwardTiming.elapsed(ms)) return rc; // (behind the fence that has passed: no wait)
-    for (uint32_t k = 0; k < kForwardCountSlots; ++k) info.shadedPixels += st.forwardCountHost.ptr[k * kForwardCountStride];
-    info.ms = ms[0] + ms[1];
-    info.shadeMs = ms[1];
-    *out = info;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_forward_depth_device_ptr(prosper_pt_ctx *ctx, float **out, uint32_t *width, uint32_t *height)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_forward_depth_device_ptr: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.forwardRan || st.gbufferLast.albedoRoughness || !st.gbufferLast.nonLinearDepth)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the context's last depth is not a forward frame's");
-    *out = st.gbufferLast.nonLinearDepth;
-    if (width) *width = st.gbufferLastWidth;
-    if (height) *height = st.gbufferLastHeight;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_forward_depth(prosper_pt_ctx *ctx, float *host_depth, size_t pixels, void *stream)
-{
-    if (!ctx || !host_depth) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_depth: null argument");
-    float *depth = nullptr;
-    uint32_t w = 0, h = 0;
-    if (const int rc = prosper_pt_get_forward_depth_device_ptr(ctx, &depth, &w, &h)) return rc;
-    if (pixels != (size_t)w * h) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_depth: pixel count differs from the depth's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = ctx->gbufferPasses->forwardDone.wait(s)) return rc;
-    PPT_HIP(hipMemcpyAsync(host_depth, depth, pixels * 4u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
-}
-
 int prosper_pt_get_velocity_device_ptr(prosper_pt_ctx *ctx, void **out, uint32_t *width, uint32_t *height)
 {
     if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_velocity_device_ptr: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.velocityLast) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
-    *out = st.velocityLast;
-    if (width) *width = st.velocityLastWidth;
-    if (height) *height = st.velocityLastHeight;
+    if (!st.last.velocity) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
+    *out = st.last.velocity;
+    if (width) *width = st.last.velocityWidth;
+    if (height) *height = st.last.velocityHeight;
     return PROSPER_PT_OK;
 }
 
@@ -1091,12 +728,12 @@ int prosper_pt_read_velocity(prosper_pt_ctx *ctx, float *host_float2, size_t pix
 {
     if (!ctx || !host_float2) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_velocity: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.velocityLast) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
-    if (pixels != (size_t)st.velocityLastWidth * st.velocityLastHeight)
+    if (!st.last.velocity) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
+    if (pixels != (size_t)st.last.velocityWidth * st.last.velocityHeight)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_velocity: pixel count differs from the velocity target's");
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host_float2, st.velocityLast, pixels * 8u, hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipMemcpyAsync(host_float2, st.last.velocity, pixels * 8u, hipMemcpyDeviceToHost, s));
     PPT_HIP(hipStreamSynchronize(s));
     return PROSPER_PT_OK;
 }
@@ -1105,14 +742,14 @@ int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_in
 {
     if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gbuffer_device_ptrs: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    if (!st.last.targets.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
     *out = prosper_pt_restir_inputs{};
-    out->albedoRoughness = st.gbufferLast.albedoRoughness;
-    out->normalMetallic = st.gbufferLast.normalMetallic;
-    out->nonLinearDepth = st.gbufferLast.nonLinearDepth;
+    out->albedoRoughness = st.last.targets.albedoRoughness;
+    out->normalMetallic = st.last.targets.normalMetallic;
+    out->nonLinearDepth = st.last.targets.nonLinearDepth;
     out->onDevice = 1;
-    if (width) *width = st.gbufferLastWidth;
-    if (height) *height = st.gbufferLastHeight;
+    if (width) *width = st.last.width;
+    if (height) *height = st.last.height;
     return PROSPER_PT_OK;
 }
 
@@ -1122,12 +759,12 @@ int prosper_pt_read_gbuffer(
 {
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.gbufferLast.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
-    if (pixels != (size_t)st.gbufferLastWidth * st.gbufferLastHeight)
+    if (!st.last.targets.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
+    if (pixels != (size_t)st.last.width * st.last.height)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: pixel count differs from the G-buffer's");
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const prosper_pt_gbuffer_targets &t = st.gbufferLast;
+    const prosper_pt_gbuffer_targets &t = st.last.targets;
     if (host_albedo_roughness)
         PPT_HIP(hipMemcpyAsync(host_albedo_roughness, t.albedoRoughness, pixels * 16u, hipMemcpyDeviceToHost, s));
     if (host_normal_metallic)
@@ -1285,13 +922,7 @@ int prosper_pt_deferred_shading(
         (!traced && (!gbuffer || !gbuffer->albedoRoughness || !gbuffer->normalMetallic || !gbuffer->nonLinearDepth)))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
     if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: ibl is 0 or 1");
-    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
-        return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    "prosper_pt_deferred_shading: ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: camera needs 0 < near_ < far_ and a resolution");
+    if (const int rc = check_lit_pass("prosper_pt_deferred_shading", ctx, pc->drawType, pc->ibl, camera)) return rc;
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_deferred_shading: null argument");
     const int crc = check_scene(ctx, "prosper_pt_deferred_shading");
     if (crc != PROSPER_PT_OK) return crc;
@@ -1302,168 +933,13 @@ int prosper_pt_deferred_shading(
         rc = call_gbuffer(
             ctx, traced, pc->drawType, frameIndex, (flags & PROSPER_PT_DEFERRED_JITTER_GBUFFER) != 0, camera, width, height,
             gbuffer, s, din);
-    const ClusterParams c = cluster_params(camera, width, height);
-    if (rc == PROSPER_PT_OK) rc = cluster_lights(ctx, c, s);
+    ClusteredLights lights = {};
+    if (rc == PROSPER_PT_OK) rc = clustered_lights(ctx, camera, width, height, pc->ibl == 1u, s, &lights, nullptr); // (clusters every frame)
     if (rc == PROSPER_PT_OK) rc = prepare_hdr(ctx, width, height, nullptr, s);
     if (rc != PROSPER_PT_OK) return rc;
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (pc->ibl == 1u)
-        launch_deferred_shading_ibl(
-            ctx->scene, pc->drawType, width, height, gbuffer_camera(camera), c, din.ar, din.nm, din.depth,
-            st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), st.iblIrradiance.as<uint16_t>(),
-            st.iblRadiance.as<uint16_t>(), st.iblLut.as<uint32_t>(), ctx->hdr, s);
-    else
-        launch_deferred_shading(
-            ctx->scene, pc->drawType, width, height, gbuffer_camera(camera), c, din.ar, din.nm, din.depth,
-            st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ctx->hdr, s);
+    launch_deferred_shading(ctx->scene, pc->drawType, width, height, gbuffer_camera(camera), lights, din.ar, din.nm, din.depth, ctx->hdr, s);
     PPT_HIP(hipGetLastError());
     return mark_versions_read(ctx, s);
-}
-
-// ---- forward transparent pass (src/render/ForwardRenderer.cpp recordTransparent) ----
-
-int prosper_pt_forward_transparent(
-    prosper_pt_ctx *ctx, const prosper_pt_forward_pc *pc, uint32_t flags, uint32_t frameIndex,
-    const prosper_CameraUniforms *camera, uint32_t width, uint32_t height, const float *nonLinearDepth, uint32_t onDevice,
-    void *stream)
-{
-    // the arguments are checked before the context, so that every refusal happens without a GPU
-    const char *what = "prosper_pt_forward_transparent";
-    if (flags & ~(uint32_t)(PROSPER_PT_TRANSPARENT_JITTER | PROSPER_PT_TRANSPARENT_CAMERA_JITTER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown flags");
-    if ((flags & PROSPER_PT_TRANSPARENT_JITTER) && (flags & PROSPER_PT_TRANSPARENT_CAMERA_JITTER))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": JITTER and CAMERA_JITTER exclude each other");
-    if (!pc || !camera) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": empty extent");
-    if (pc->drawType >= PROSPER_DRAW_TYPE_COUNT) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "drawType out of range");
-    if (pc->ibl > 1u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": ibl is 0 or 1");
-    if (pc->ibl == 1u && (!ctx || !ctx->gbufferPasses->iblGenerated))
-        return fail(PROSPER_PT_ERR_UNSUPPORTED,
-                    std::string(what) + ": ibl = 1 needs ImageBasedLighting's maps and BRDF LUT: call prosper_pt_generate_ibl after the scene upload");
-    if (!cluster_camera_ok(camera))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": camera needs 0 < near_ < far_ and a resolution");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
-    const int crc = check_scene(ctx, what);
-    if (crc != PROSPER_PT_OK) return crc;
-    if (!hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the HDR image has another extent");
-    GBufferPassState &st = *ctx->gbufferPasses;
-    const size_t pixels = (size_t)width * height;
-    const float *depth = nonLinearDepth;
-    if (!depth)
-    {
-        if (!st.gbufferLast.nonLinearDepth) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
-        if (st.gbufferLastWidth != width || st.gbufferLastHeight != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the last traced G-buffer has another extent");
-        depth = st.gbufferLast.nonLinearDepth;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = flush_scene_updates(ctx, s, s);
-    if (rc != PROSPER_PT_OK) return rc;
-    if (nonLinearDepth && !onDevice)
-    {
-        rc = grow_to(st.transparentDepth, pixels * 4u, s);
-        if (rc != PROSPER_PT_OK) return rc;
-        PPT_HIP(hipMemcpyAsync(st.transparentDepth.ptr, nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
-        depth = st.transparentDepth.as<float>();
-    }
-    rc = grow_to(st.transparentStats, 16u, s);
-    const uint32_t debugLayers = st.transparentDebugLayers;
-    if (rc == PROSPER_PT_OK && debugLayers) rc = grow_to(st.transparentLayers, pixels * (4u + (size_t)debugLayers * sizeof(prosper_pt_transparent_layer)), s);
-    if (rc == PROSPER_PT_OK) rc = st.transparentTiming.create();
-    if (rc != PROSPER_PT_OK) return rc;
-    st.transparentRan = false;
-    st.transparentLayerPixels = 0;
-    PPT_HIP(hipEventRecord(st.transparentTiming.events[0], s));
-
-    const ClusterParams c = cluster_params(camera, width, height);
-    bool reuse = false;
-    rc = cluster_lights_unless_current(ctx, c, s, &reuse);
-    if (rc != PROSPER_PT_OK) return rc;
-
-    TransparentParams p = {};
-    p.g = gbuffer_trace_params(pc->drawType, frameIndex, (flags & PROSPER_PT_TRANSPARENT_JITTER) != 0, false, camera, width, height);
-    std::memcpy(p.worldToCamera, &camera->worldToCamera, 64);
-    const RestirCamera rc2 = gbuffer_camera(camera);
-    p.cameraToClip22 = rc2.cameraToClip22;
-    p.cameraToClip32 = rc2.cameraToClip32;
-    p.cameraJitter = (flags & PROSPER_PT_TRANSPARENT_CAMERA_JITTER) ? 1u : 0u;
-    p.currentJitter[0] = camera->currentJitter[0];
-    p.currentJitter[1] = camera->currentJitter[1];
-    p.near_ = c.near_;
-    p.far_ = c.far_;
-    p.clustersX = c.dimX;
-    p.clustersY = c.dimY;
-    p.debugLayers = debugLayers;
-
-    int32_t *ovf = nullptr;
-    rc = ensure_stack_overflow(ctx, ctx->slots[0], kTraversalStackDepth, restir_grid_blocks(width, height), &ovf);
-    if (rc != PROSPER_PT_OK) return rc;
-    PPT_HIP(hipMemsetAsync(st.transparentStats.ptr, 0, 16u, s));
-    wait_for_slot(ctx->slots[0], s);
-    const bool ibl = pc->ibl == 1u;
-    uint32_t *counts = debugLayers ? st.transparentLayers.as<uint32_t>() : nullptr;
-    const GBufferLodParams lodParams{ctx->textureMips, st.lodBias, nullptr};
-    launch_forward_transparent(
-        ctx->scene, p, depth, st.clusterPointers.ptr, st.clusterIndices.as<uint16_t>(), ibl ? st.iblIrradiance.as<uint16_t>() : nullptr,
-        ibl ? st.iblRadiance.as<uint16_t>() : nullptr, ibl ? st.iblLut.as<uint32_t>() : nullptr, ctx->hdr, ovf,
-        st.transparentStats.as<uint32_t>(), counts,
-        debugLayers ? reinterpret_cast<prosper_pt_transparent_layer *>(counts + pixels) : nullptr, s,
-        st.lodEnabled && ctx->textureMips ? &lodParams : nullptr);
-    release_slot(ctx->slots[0], s);
-    PPT_HIP(hipGetLastError());
-    PPT_HIP(hipEventRecord(st.transparentTiming.events[1], s));
-    st.transparentRan = true;
-    st.transparentReclustered = !reuse;
-    st.transparentLayerPixels = debugLayers ? pixels : 0u;
-    st.transparentLayerCount = debugLayers;
-    return mark_versions_read(ctx, s);
-}
-
-int prosper_pt_get_transparent_info(prosper_pt_ctx *ctx, prosper_pt_transparent_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_transparent_info: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.transparentRan) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_forward_transparent has not run yet");
-    PPT_HIP(hipSetDevice(ctx->device));
-    prosper_pt_transparent_info info = {};
-    if (const int rc = st.transparentTiming.elapsed(&info.ms)) return rc; // (waits for the call's last kernel)
-    uint32_t stats[4] = {};
-    PPT_HIP(hipMemcpy(stats, st.transparentStats.ptr, 16u, hipMemcpyDeviceToHost));
-    info.coveredPixels = stats[0];
-    info.maxLayers = stats[1];
-    info.totalLayers = ((uint64_t)stats[3] << 32) | stats[2];
-    info.reclustered = st.transparentReclustered ? 1u : 0u;
-    *out = info;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_set_transparent_debug_layers(prosper_pt_ctx *ctx, uint32_t layersPerPixel)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_transparent_debug_layers: null argument");
-    if (layersPerPixel > 64u) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_transparent_debug_layers: at most 64 layers per pixel");
-    ctx->gbufferPasses->transparentDebugLayers = layersPerPixel;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_read_transparent_layers(
-    prosper_pt_ctx *ctx, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers, size_t pixels,
-    uint32_t layersPerPixel, void *stream)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_transparent_layers: null argument");
-    const GBufferPassState &st = *ctx->gbufferPasses;
-    if (!st.transparentRan || !st.transparentLayerPixels)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_forward_transparent did not run in debug mode (prosper_pt_set_transparent_debug_layers)");
-    if (pixels != st.transparentLayerPixels || layersPerPixel != st.transparentLayerCount)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_transparent_layers: pixels or layersPerPixel differ from the call's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t *counts = st.transparentLayers.as<uint32_t>();
-    if (host_counts) PPT_HIP(hipMemcpyAsync(host_counts, counts, pixels * 4u, hipMemcpyDeviceToHost, s));
-    if (host_layers)
-        PPT_HIP(hipMemcpyAsync(host_layers, counts + pixels, pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
 }
 
 // ---- image-based lighting (src/render/ImageBasedLighting.cpp) ----
@@ -1563,9 +1039,9 @@ int prosper_pt_read_texture_lod_derivatives(prosper_pt_ctx *ctx, float *out, siz
 {
     if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
-    if (st.lodDerivativesWidth == 0)
+    if (st.last.derivativesWidth == 0)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: the last traced G-buffer wrote no derivatives (prosper_pt_set_texture_lod, prosper_pt_set_texture_lod_debug)");
-    if (bytes != (size_t)st.lodDerivativesWidth * st.lodDerivativesHeight * sizeof(float4))
+    if (bytes != (size_t)st.last.derivativesWidth * st.last.derivativesHeight * sizeof(float4))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: size mismatch");
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);

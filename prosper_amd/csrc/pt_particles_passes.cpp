@@ -7,6 +7,7 @@
 #include <new>
 
 #include "pt_context.hpp"
+#include "pt_gbuffer_passes.hpp"
 #include "pt_math.hpp"
 #include "pt_particles.hpp"
 #include "pt_pass_support.hpp"

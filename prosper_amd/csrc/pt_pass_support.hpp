@@ -1,4 +1,4 @@
-// pt_pass_support.hpp — what the passes over a G-buffer (pt_gbuffer_passes.cpp) use of the render path in
+// pt_pass_support.hpp — what the pass modules (pt_gbuffer_passes.cpp and the others) use of the render path in
 // prosper_pt.cpp.  Private to the library's translation units.
 #pragma once
 
@@ -18,11 +18,6 @@ int check_scene(prosper_pt_ctx *ctx, const char *what);
 int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s, hipStream_t reader);
 // The scene and light versions a call read are free again behind its last kernel on `s`.
 int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s);
-// (pt_gbuffer_passes.cpp) prosper_pt_set_texture_lod's state: what the traced G-buffer and the rasteriser's passes sample with
-void gbuffer_texture_lod(const prosper_pt_ctx *ctx, bool *enabled, float *bias);
-// (pt_gbuffer_passes.cpp) The depth a pass reads with "NULL: the last traced G-buffer's": that of the last G-buffer or of the
-// last forward frame, which leaves a depth and no attribute targets (prosper_pt_raster_forward).  NO_SCENE before either.
-int gbuffer_last_depth(prosper_pt_ctx *ctx, const float **depth, uint32_t *width, uint32_t *height);
 // the camera terms of the path tracer's camera ray (RenderParams eye .. cameraToWorld)
 void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera);
 // The context's HDR image for a `width` x `height` image, or for the stripes of it `tile` gives this rank (nullptr:

@@ -15,6 +15,7 @@
 
 #include "pt_context.hpp"
 #include "pt_culling_state.hpp"
+#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 #include "pt_raster.hpp"
 
