@@ -539,6 +539,45 @@ int prosper_pt_read_texture_level(prosper_pt_ctx *ctx, uint32_t texture, uint32_
  *   blended by the fraction. */
 int prosper_pt_debug_sample_texture_lod(
     prosper_pt_ctx *ctx, uint32_t texture, uint32_t sampler, const float *in6, uint32_t n, float bias, float *out5);
+
+/* ---- texture compression: what prosper's compress() does before it writes a cache file ----
+ * src/scene/Texture.cpp:213-296 builds a mip chain truncated at 4x4, compresses it to BC7 when every level divides by 4 in
+ * both directions (otherwise the chain stays RGBA8), and writes the levels back to back (src/utils/Dds.cpp:100-135).  The
+ * BC7 encoder is a HIP kernel, one lane per 4x4 block, with a rule of the library's own (prosper's third-party encoder is
+ * not part of its tree): single-subset modes 6, 5 and 4, rotation 0, integer arithmetic throughout; prosper_amd/bc7.py
+ * (encode_blocks) states it and the kernel reproduces it bit for bit.  Generated levels are the 2 x 2 box of "texture mip
+ * chains" above, not stb's resize: the result is a valid payload of prosper's cache whose texels are this library's. */
+enum
+{
+    PROSPER_PT_COMPRESS_SRGB = 1u << 0,          /* generated levels average RGB in linear light (a base-colour texture) */
+    PROSPER_PT_COMPRESS_GENERATE_MIPS = 1u << 1, /* Texture2DOptions::generateMipMaps */
+};
+/* What compress() decides for an extent, host only: the level count (prosper_pt_texture_mip_level_count, or 1 without
+ * generateMips), the format (PROSPER_PT_FORMAT_BC7_UNORM if every level divides by 4 in both directions, else
+ * PROSPER_PT_FORMAT_RGBA8_UNORM) and the payload size of the levels back to back.  Refused: null pointers, an empty extent. */
+int prosper_pt_compressed_texture_layout(
+    uint32_t width, uint32_t height, uint32_t generateMips, uint32_t *format, uint32_t *levelCount, uint64_t *bytes);
+/* Compresses `src` (RGBA8) into `dst`.  src->mipLevelCount <= 1: the layout is that of
+ * prosper_pt_compressed_texture_layout(width, height, flags & GENERATE_MIPS) and the levels are generated on the GPU;
+ * src->mipLevelCount = n > 1: the caller's n levels are taken as they are (the layout's rule over those n levels; SRGB and
+ * GENERATE_MIPS are not read).  `dstBytes` must be the payload size.  With the RGBA8 format `dst` receives the raw chain.
+ * Needs no scene and no PROSPER_PT_CREATE_TEXTURE_MIPS; uses staging of the context that only grows; tiling, mip
+ * generation and encoding run on `stream`, the payload is copied to `dst` and the call waits for it.  One call at a time
+ * per context.
+ * Refused with nothing launched: null pointers, an empty extent, a BC7 `src`, unknown flags, a chain of more than 16
+ * levels, a supplied chain longer than prosper's count for the extent, a `dstBytes` that is not the payload size. */
+int prosper_pt_compress_texture(
+    prosper_pt_ctx *ctx, const prosper_pt_texture_desc *src, uint32_t flags, void *dst, uint64_t dstBytes, void *stream);
+/* Device time of the stages of the last completed prosper_pt_compress_texture, between events on its stream: the source's
+ * way up with tiling and mip generation, the encode kernels of all levels (the un-tiling on the RGBA8 fallback), the
+ * payload's way back.  Refused before any call has completed. */
+int prosper_pt_get_compress_texture_timing(prosper_pt_ctx *ctx, float *prepareMs, float *encodeMs, float *readbackMs);
+/* Test hook: the encoder's device function over n loose blocks.  texels: n x 16 RGBA8 words (R in the low byte), row-major
+ * inside the block; blocks: n x 4 words; sse: n squared errors of the decoded block against the source over all four
+ * channels.  modeMask: bits 4, 5 and 6 enable that mode, 0 enables all; other bits are refused.  n = 0 succeeds and
+ * does nothing.  Enqueued on `stream` and waited for. */
+int prosper_pt_debug_bc7_encode_blocks(
+    prosper_pt_ctx *ctx, const uint32_t *texels, uint32_t n, uint32_t modeMask, uint32_t *blocks, uint32_t *sse, void *stream);
 /* The traced G-buffer (prosper_pt_trace_gbuffer, prosper_pt_trace_gbuffer_velocity, and the records that trace one) samples
  * material textures through their mip chains: context state, the counterpart of the lodBias prosper writes with its
  * material buffer each frame (Renderer::lodBias(): -1 while TAA is on, otherwise 0).  The uv derivatives are the forward

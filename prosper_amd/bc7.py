@@ -1,11 +1,12 @@
-"""BC7 (BPTC UNORM) block decoder, numpy, bit-exact per the format definition (Khronos Data Format Specification,
+"""BC7 (BPTC UNORM) block decoder and encoder, numpy; the decoder bit-exact per the format definition (Khronos Data Format Specification,
 "BPTC compressed texture image formats"; the same rules D3D11's BC7_UNORM and VK_FORMAT_BC7_UNORM_BLOCK decode by).
 
 Why it is here: prosper does not sample the PNG texels of a glTF - it compresses every texture whose
 mip chain divides by 4 to BC7 with a third-party encoder and caches the result as `prosper_cache/<name>.dds`
 (src/scene/Texture.cpp:213-296, 377-415); the GPU then decodes those blocks in hardware.  Texel parity with prosper
 on real assets therefore means reading that cache and decoding it exactly; the encoder itself (lossy heuristics of
-the ISPC texture compressor) is not part of the path.
+the ISPC texture compressor) is not part of the path.  Where no cache exists yet the library writes one with an encoder
+of its own rule: `encode_blocks` below states that rule, the HIP kernel reproduces it.
 
 Pinned against an independent implementation: tests/test_bc7.py decodes random blocks of all eight modes (and the
 reserved one) with Pillow's "bcn" decoder and compares every byte; the partition / anchor tables below were
@@ -225,3 +226,225 @@ def decode_image(data, width, height):
     blocks = np.frombuffer(data, np.uint8, count=bx * by * 16).reshape(-1, 16)
     texels = decode_blocks(blocks).reshape(by, bx, 4, 4, 4)
     return np.ascontiguousarray(texels.transpose(0, 2, 1, 3, 4).reshape(height, width, 4))
+
+
+# ---- the encoder ----
+# prosper compresses with a third-party encoder whose source is not part of its tree, so no byte-for-byte pin against
+# it exists.  The rule below is this library's own: integer arithmetic only, stated here in numpy, and the HIP kernel
+# (csrc/pt_bc7_encode.hip) has to reproduce it bit for bit (tests/test_bc7_encode.py).  Candidates are the three
+# single-subset modes with alpha - 6, 5 and 4, the latter with both values of its index-selection bit - with rotation 0.
+ENCODE_CANDIDATES = ((6, 0), (5, 0), (4, 0), (4, 1))   # (mode, index selection), in tie order
+_COLOUR, _ALPHA, _ALL = (0, 1, 2), (3,), (0, 1, 2, 3)
+_CHUNK = 1 << 14
+
+
+def _index_sets(mode, selection):
+    """(channels, index bits) of every index set of a candidate, the colour set first."""
+    if mode == 6:
+        return ((_ALL, 4),)
+    if mode == 5:
+        return ((_COLOUR, 2), (_ALPHA, 2))
+    return ((_COLOUR, 3), (_ALPHA, 2)) if selection else ((_COLOUR, 2), (_ALPHA, 3))
+
+
+def _expand(code, bits):
+    """The decoder's bit replication of a `bits`-bit endpoint code to 8 bits."""
+    v = code << (8 - bits)
+    return v | (v >> bits)
+
+
+def _nearest(values):
+    """[256] table: of the ascending 8-bit `values`, the one nearest to v; a tie goes to the lower one."""
+    values = np.asarray(values, np.int64)
+    return values[np.argmin(np.abs(values[None, :] - np.arange(256, dtype=np.int64)[:, None]), axis=1)]
+
+
+_NEAREST = {bits: _nearest(_expand(np.arange(1 << bits, dtype=np.int64), bits)) for bits in (5, 6, 7, 8)}
+_NEAREST_PARITY = (_nearest(np.arange(0, 256, 2)), _nearest(np.arange(1, 256, 2)))
+
+
+def _endpoint_line(x):
+    """x [N, 16, C] -> (e0, e1) [N, C]: the corners of the channels' bounding box that the block's line runs between.
+    The reference channel is the first with the largest range; a channel whose covariance with it is negative runs
+    from its maximum to its minimum."""
+    lo, hi = x.min(axis=1), x.max(axis=1)
+    ref = np.argmax(hi - lo, axis=1)
+    xr = np.take_along_axis(x, ref[:, None, None], axis=2)                       # [N, 16, 1]
+    cov = 16 * (xr * x).sum(axis=1) - xr.sum(axis=1) * x.sum(axis=1)             # [N, C]
+    return np.where(cov < 0, hi, lo), np.where(cov < 0, lo, hi)
+
+
+def _quantise(mode, e, opaque):
+    """8-bit endpoint e [N, 4] -> the value the decoder dequantises the nearest code of the mode's precision to."""
+    if mode == 6:
+        # 7 bits and a p-bit: both p tried, the channels take the nearest value of that parity; the smaller squared
+        # error wins, p = 0 on a tie; an opaque block takes p = 1, so that alpha stays 255
+        q = [table[e] for table in _NEAREST_PARITY]
+        err = [((v - e) ** 2).sum(axis=1) for v in q]
+        p = (err[1] < err[0]) | opaque
+        return np.where(p[:, None], q[1], q[0])
+    colour, alpha = (7, 8) if mode == 5 else (5, 6)
+    return np.concatenate([_NEAREST[colour][e[:, :3]], _NEAREST[alpha][e[:, 3:]]], axis=1)
+
+
+def _assign(x, e0, e1, bits):
+    """Per texel the index (lowest on a tie) whose decoded value is nearest over the set's channels.
+    x [N, 16, C], e0 / e1 [N, C] -> (indices [N, 16], squared error [N, 16])"""
+    best = idx = None
+    for k, w in enumerate(WEIGHTS[bits]):
+        value = ((64 - w) * e0 + w * e1 + 32) >> 6
+        d = ((x - value[:, None, :]) ** 2).sum(axis=2)
+        if best is None:
+            best, idx = d, np.zeros(d.shape, np.int64)
+        else:
+            better = d < best
+            best = np.where(better, d, best)
+            idx = np.where(better, k, idx)
+    return idx, best
+
+
+def _refine(x, idx, bits, e0, e1):
+    """Least-squares endpoints for the given indices: with a = 64 - w, b = w the model is (a e0 + b e1) / 64, whose
+    normal equations are solved per channel in integers; the quotient is rounded as floor((2 n + d) / (2 d)) and
+    clamped to 0..255.  A zero determinant (every texel on one index) keeps the endpoints."""
+    w = np.array(WEIGHTS[bits], np.int64)[idx]
+    a, b = 64 - w, w
+    saa, sab, sbb = (a * a).sum(axis=1), (a * b).sum(axis=1), (b * b).sum(axis=1)
+    det = saa * sbb - sab * sab
+    sax, sbx = (a[:, :, None] * x).sum(axis=1), (b[:, :, None] * x).sum(axis=1)
+    n0 = 64 * (sbb[:, None] * sax - sab[:, None] * sbx)
+    n1 = 64 * (saa[:, None] * sbx - sab[:, None] * sax)
+    d = np.maximum(det, 1)[:, None]
+    keep = (det == 0)[:, None]
+    r0 = np.where(keep, e0, np.clip((2 * n0 + d) // (2 * d), 0, 255))
+    r1 = np.where(keep, e1, np.clip((2 * n1 + d) // (2 * d), 0, 255))
+    return r0, r1
+
+
+def _candidate(x, opaque, mode, selection):
+    """One candidate over x [N, 16, 4] -> (e0, e1 [N, 4] dequantised, [indices [N, 16] per set], sse [N])."""
+    sets = _index_sets(mode, selection)
+
+    def fit(e0, e1):
+        e0, e1 = _quantise(mode, e0, opaque), _quantise(mode, e1, opaque)
+        indices, sse = [], 0
+        for channels, bits in sets:
+            c = list(channels)
+            idx, err = _assign(x[:, :, c], e0[:, c], e1[:, c], bits)
+            indices.append(idx)
+            sse = sse + err.sum(axis=1)
+        return e0, e1, indices, sse
+
+    e0, e1 = np.empty((x.shape[0], 4), np.int64), np.empty((x.shape[0], 4), np.int64)
+    for channels, _ in sets:
+        c = list(channels)
+        e0[:, c], e1[:, c] = _endpoint_line(x[:, :, c])
+    e0, e1, indices, sse = fit(e0, e1)
+    r0, r1 = e0.copy(), e1.copy()
+    for (channels, bits), idx in zip(sets, indices):
+        c = list(channels)
+        r0[:, c], r1[:, c] = _refine(x[:, :, c], idx, bits, e0[:, c], e1[:, c])
+    r0, r1, refined, refined_sse = fit(r0, r1)
+    use = refined_sse < sse                                    # the refinement stays only where strictly better
+    e0, e1 = np.where(use[:, None], r0, e0), np.where(use[:, None], r1, e1)
+    indices = [np.where(use[:, None], r, i) for r, i in zip(refined, indices)]
+    return e0, e1, indices, np.where(use, refined_sse, sse)
+
+
+class _Bits:
+    """128 bits per block, written least significant first at fixed positions."""
+
+    def __init__(self, n):
+        self.lo, self.hi, self.pos = np.zeros(n, np.uint64), np.zeros(n, np.uint64), 0
+
+    def put(self, value, n):
+        v = np.asarray(value).astype(np.uint64) & np.uint64((1 << n) - 1)
+        if self.pos < 64:
+            self.lo |= v << np.uint64(self.pos)
+            if self.pos + n > 64:
+                self.hi |= v >> np.uint64(64 - self.pos)
+        else:
+            self.hi |= v << np.uint64(self.pos - 64)
+        self.pos += n
+
+    def indices(self, idx, bits):
+        self.put(idx[:, 0], bits - 1)                         # the anchor's top bit is implied 0
+        for i in range(1, 16):
+            self.put(idx[:, i], bits)
+
+
+def _pack(mode, selection, e0, e1, indices):
+    sets = _index_sets(mode, selection)
+    e0, e1, indices = e0.copy(), e1.copy(), list(indices)
+    for s, (channels, bits) in enumerate(sets):
+        # an anchor index with its top bit set: the set's endpoints (p-bits with them) swap, its indices complement
+        swap = (indices[s][:, 0] >> (bits - 1)) == 1
+        c = list(channels)
+        e0[:, c], e1[:, c] = np.where(swap[:, None], e1[:, c], e0[:, c]), np.where(swap[:, None], e0[:, c], e1[:, c])
+        indices[s] = np.where(swap[:, None], (1 << bits) - 1 - indices[s], indices[s])
+    out = _Bits(e0.shape[0])
+    out.put(1 << mode, mode + 1)
+    if mode == 6:
+        for c in range(4):
+            out.put(e0[:, c] >> 1, 7)
+            out.put(e1[:, c] >> 1, 7)
+        out.put(e0[:, 0] & 1, 1)
+        out.put(e1[:, 0] & 1, 1)
+        out.indices(indices[0], 4)
+    else:
+        colour, alpha = (7, 8) if mode == 5 else (5, 6)
+        out.put(0, 2)                                          # rotation
+        if mode == 4:
+            out.put(selection, 1)
+        for c in range(3):
+            out.put(e0[:, c] >> (8 - colour), colour)
+            out.put(e1[:, c] >> (8 - colour), colour)
+        out.put(e0[:, 3] >> (8 - alpha), alpha)
+        out.put(e1[:, 3] >> (8 - alpha), alpha)
+        # the primary (2-bit) set first; with the selection bit it is alpha's
+        first, second = (1, 0) if selection else (0, 1)
+        out.indices(indices[first], sets[first][1])
+        out.indices(indices[second], sets[second][1])
+    assert out.pos == 128
+    return np.stack([out.lo, out.hi], axis=1).astype("<u8").view(np.uint8).reshape(-1, 16)
+
+
+def encode_blocks(texels, mode_mask=0):
+    """uint8 [N, 16, 4] RGBA texels (row-major inside the 4x4 block) -> (blocks uint8 [N, 16], sse int64 [N] of the
+    decoded block against the source over all four channels, mode int64 [N]).  mode_mask: bits 4, 5 and 6 enable
+    that mode; 0 enables all three.  The block takes the candidate with the least SSE, ties in the order 6, 5, 4
+    (index selection 0 before 1)."""
+    texels = np.ascontiguousarray(texels, np.uint8).reshape(-1, 16, 4)
+    n = texels.shape[0]
+    mode_mask = int(mode_mask) & 0x70 or 0x70
+    blocks, sse, mode = np.zeros((n, 16), np.uint8), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for c0 in range(0, n, _CHUNK):
+        x = texels[c0:c0 + _CHUNK].astype(np.int64)
+        opaque = (x[:, :, 3] == 255).all(axis=1)
+        best = None
+        for m, selection in ENCODE_CANDIDATES:
+            if not mode_mask >> m & 1:
+                continue
+            e0, e1, indices, err = _candidate(x, opaque, m, selection)
+            packed = _pack(m, selection, e0, e1, indices)
+            if best is None:
+                best = [packed, err, np.full(len(x), m, np.int64)]
+            else:
+                better = err < best[1]
+                best = [np.where(better[:, None], packed, best[0]), np.where(better, err, best[1]), np.where(better, m, best[2])]
+        blocks[c0:c0 + _CHUNK], sse[c0:c0 + _CHUNK], mode[c0:c0 + _CHUNK] = best
+    return blocks, sse, mode
+
+
+def image_blocks(rgba):
+    """uint8 [height, width, 4] -> uint8 [(height / 4) * (width / 4), 16, 4]: the image's 4x4 blocks, row-major."""
+    rgba = np.ascontiguousarray(rgba, np.uint8)
+    height, width = rgba.shape[:2]
+    if width % 4 or height % 4 or rgba.shape[2] != 4:
+        raise ValueError("BC7 levels are whole 4x4 blocks of RGBA8 texels")
+    return np.ascontiguousarray(rgba.reshape(height // 4, 4, width // 4, 4, 4).transpose(0, 2, 1, 3, 4)).reshape(-1, 16, 4)
+
+
+def encode_image(rgba, mode_mask=0):
+    """uint8 [height, width, 4] -> the BC7 payload of the level (bytes; blocks row-major, 16 B each)."""
+    return encode_blocks(image_blocks(rgba), mode_mask)[0].tobytes()

@@ -66,6 +66,10 @@ def lib():
     L.prosper_pt_get_texture_mips_info.argtypes = [vp, u32, C.POINTER(S.TextureMipsInfo)]
     L.prosper_pt_read_texture_level.argtypes = [vp, u32, u32, vp, C.c_uint64, vp]
     L.prosper_pt_debug_sample_texture_lod.argtypes = [vp, u32, u32, vp, u32, C.c_float, vp]
+    L.prosper_pt_compressed_texture_layout.argtypes = [u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64)]
+    L.prosper_pt_compress_texture.argtypes = [vp, C.POINTER(S.TextureDesc), u32, vp, C.c_uint64, vp]
+    L.prosper_pt_debug_bc7_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.prosper_pt_get_compress_texture_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.prosper_pt_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
     L.prosper_pt_set_texture_lod_debug.argtypes = [vp, C.c_int]
     L.prosper_pt_read_texture_lod_derivatives.argtypes = [vp, vp, C.c_size_t, vp]
@@ -412,6 +416,13 @@ class RecordOptions(C.Structure):
                 ("drawType", C.c_uint32)]
 
 
+def compressed_texture_layout(width, height, mips=True):
+    """What prosper's compress() decides for an extent -> (PROSPER_PT_FORMAT_*, level count, payload bytes)."""
+    fmt, levels, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    _check(lib().prosper_pt_compressed_texture_layout(width, height, int(bool(mips)), C.byref(fmt), C.byref(levels), C.byref(nbytes)))
+    return fmt.value, levels.value, nbytes.value
+
+
 def _check(rc):
     if rc != 0:
         raise ProsperPtError(rc, lib().prosper_pt_last_error().decode())
@@ -630,6 +641,43 @@ class Context:
         out = np.zeros((h, w, 4), np.uint8)
         _check(lib().prosper_pt_read_texture_level(self._h, texture, level, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
+
+    def compress_texture(self, texture, srgb=False, mips=True, stream=None):
+        """prosper's compress() on the GPU: a numpy [h, w, 4] uint8 array (its chain is generated when `mips`; `srgb`:
+        in linear light) or a world.TextureChain / list of levels (taken as it is) -> (PROSPER_PT_FORMAT_*, [payload
+        bytes of every level]): BC7 blocks when every level divides by 4, otherwise the raw RGBA8 chain."""
+        from .world import TextureChain, fill_texture_desc
+        if isinstance(texture, (list, tuple)):
+            texture = TextureChain(texture)
+        desc = S.TextureDesc()
+        keep = fill_texture_desc(desc, texture)
+        supplied = desc.mipLevelCount if desc.mipLevelCount > 1 else 0
+        levels = supplied or (lib().prosper_pt_texture_mip_level_count(desc.width, desc.height) if mips else 1)
+        extents = [(max(desc.width >> l, 1), max(desc.height >> l, 1)) for l in range(levels)]
+        bc7 = desc.format == S.FORMAT_RGBA8_UNORM and all(w % 4 == 0 and h % 4 == 0 for w, h in extents)
+        sizes = [(w // 4) * (h // 4) * 16 if bc7 else w * h * 4 for w, h in extents]
+        out = np.zeros(max(sum(sizes), 1), np.uint8)
+        flags = (S.COMPRESS_SRGB if srgb else 0) | (S.COMPRESS_GENERATE_MIPS if mips else 0)
+        _check(lib().prosper_pt_compress_texture(self._h, C.byref(desc), flags, out.ctypes.data, sum(sizes), C.c_void_p(stream)))
+        del keep
+        offsets = np.concatenate([[0], np.cumsum(sizes)])
+        return (S.FORMAT_BC7_UNORM if bc7 else S.FORMAT_RGBA8_UNORM), [out[offsets[l]:offsets[l + 1]].tobytes() for l in range(levels)]
+
+    def compress_texture_timing(self):
+        """(prepare, encode, read back) device milliseconds of the last compress_texture."""
+        ms = [C.c_float(), C.c_float(), C.c_float()]
+        _check(lib().prosper_pt_get_compress_texture_timing(self._h, *[C.byref(m) for m in ms]))
+        return tuple(m.value for m in ms)
+
+    def debug_bc7_encode_blocks(self, texels, mode_mask=0, stream=None):
+        """Test hook: the encoder's device function over uint8 [n, 16, 4] loose blocks -> (blocks uint8 [n, 16],
+        sse uint32 [n]); mode_mask as bc7.encode_blocks."""
+        texels = np.ascontiguousarray(texels, np.uint8).reshape(-1, 16, 4)
+        n = texels.shape[0]
+        blocks, sse = np.zeros((n, 16), np.uint8), np.zeros(n, np.uint32)
+        _check(lib().prosper_pt_debug_bc7_encode_blocks(
+            self._h, texels.ctypes.data, n, mode_mask, blocks.ctypes.data, sse.ctypes.data, C.c_void_p(stream)))
+        return blocks, sse
 
     def set_texture_lod(self, enabled, lod_bias=0.0):
         """The traced G-buffer samples materials through the mip chains (a CREATE_TEXTURE_MIPS context), with `lod_bias`."""

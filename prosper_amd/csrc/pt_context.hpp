@@ -377,6 +377,11 @@ struct prosper_pt_ctx
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy
     uint32_t toneKeptWidth = 0, toneKeptHeight = 0; // of the image the last tone map left in toneScratch (0: it went to the caller's buffer)
+    // prosper_pt_compress_texture / prosper_pt_debug_bc7_encode_blocks (pt_materials.cpp): the source as the caller holds it,
+    // its levels in the DeviceTexture tiling, the payload on its way back
+    ppt::DeviceBuffer compressSource, compressTiled, compressPayload;
+    ppt::StageEvents<3> compressEvents; // around the last compression's stages: prepare, encode, read back
+    bool compressTimed = false;
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
     // workspace, the stack-overflow array and the launch chains (pt_kernels.hpp WavefrontChains) with their

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <string>
 
+#include "pt_bc7_encode.hpp"
 #include "pt_kernels.hpp"
 #include "pt_pass_support.hpp"
 #include "pt_texture_mips.hpp"
@@ -462,6 +463,32 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
 
 using namespace ppt;
 
+namespace
+{
+
+// What compress() decides for `levels` levels of an extent (src/scene/Texture.cpp:227-237, src/utils/Dds.cpp:100-135)
+struct CompressedLayout
+{
+    uint32_t format = PROSPER_PT_FORMAT_BC7_UNORM;
+    uint32_t levels = 1;
+    uint64_t bytes = 0;
+};
+CompressedLayout compressed_layout(uint32_t width, uint32_t height, uint32_t levels)
+{
+    CompressedLayout out;
+    out.levels = levels;
+    for (uint32_t l = 0; l < levels; ++l)
+        if (std::max(width >> l, 1u) % 4u != 0u || std::max(height >> l, 1u) % 4u != 0u) out.format = PROSPER_PT_FORMAT_RGBA8_UNORM;
+    for (uint32_t l = 0; l < levels; ++l)
+    {
+        const uint64_t w = std::max(width >> l, 1u), h = std::max(height >> l, 1u);
+        out.bytes += out.format == PROSPER_PT_FORMAT_BC7_UNORM ? (w / 4u) * (h / 4u) * 16u : w * h * 4u;
+    }
+    return out;
+}
+
+} // namespace
+
 extern "C" {
 
 int prosper_pt_update_textures(prosper_pt_ctx *ctx, const prosper_pt_texture_desc *textures, uint32_t first, uint32_t count)
@@ -691,6 +718,149 @@ int prosper_pt_debug_sample_texture_lod(
     (void)hipFree(dOut);
     if (e != hipSuccess) return fail(PROSPER_PT_ERR_HIP, std::string("prosper_pt_debug_sample_texture_lod: ") + hipGetErrorString(e));
     return mark_versions_read(ctx, nullptr);
+}
+
+int prosper_pt_compressed_texture_layout(
+    uint32_t width, uint32_t height, uint32_t generateMips, uint32_t *format, uint32_t *levelCount, uint64_t *bytes)
+{
+    if (!format || !levelCount || !bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compressed_texture_layout: null argument");
+    if (width == 0 || height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compressed_texture_layout: empty extent");
+    const CompressedLayout layout = compressed_layout(width, height, generateMips ? mip_level_count(width, height) : 1u);
+    *format = layout.format;
+    *levelCount = layout.levels;
+    *bytes = layout.bytes;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_compress_texture(
+    prosper_pt_ctx *ctx, const prosper_pt_texture_desc *src, uint32_t flags, void *dst, uint64_t dstBytes, void *stream)
+{
+    if (!ctx || !src || !dst || !src->texels) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: null argument");
+    if (src->width == 0 || src->height == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: empty extent");
+    if (src->format != PROSPER_PT_FORMAT_RGBA8_UNORM)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: the source must be PROSPER_PT_FORMAT_RGBA8_UNORM");
+    if (flags & ~(uint32_t)(PROSPER_PT_COMPRESS_SRGB | PROSPER_PT_COMPRESS_GENERATE_MIPS))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: unknown flags");
+    const uint32_t w0 = src->width, h0 = src->height, count = mip_level_count(w0, h0);
+    const uint32_t supplied = src->mipLevelCount > 1u ? src->mipLevelCount : 1u;
+    if (supplied > count)
+        return fail(
+            PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: mipLevelCount " + std::to_string(supplied) + " exceeds the " +
+                                                 std::to_string(count) + " levels of prosper's chain for the extent");
+    const uint32_t levels = supplied > 1u ? supplied : ((flags & PROSPER_PT_COMPRESS_GENERATE_MIPS) ? count : 1u);
+    if (levels > kMaxMipLevels) return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_compress_texture: a mip chain of more than 16 levels");
+    const CompressedLayout layout = compressed_layout(w0, h0, levels);
+    if (dstBytes != layout.bytes)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_compress_texture: the payload holds " + std::to_string(layout.bytes) + " bytes");
+    size_t sourceBytes = 0, tiledWords = 0, tiledOffset[kMaxMipLevels] = {};
+    for (uint32_t l = 0; l < levels; ++l)
+    {
+        const uint32_t w = std::max(w0 >> l, 1u), h = std::max(h0 >> l, 1u);
+        if (l < supplied) sourceBytes += (size_t)w * h * 4u;
+        tiledOffset[l] = tiledWords;
+        tiledWords += tiled_level_words(w, h);
+    }
+    if (tiledWords >= (1ull << 32)) return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_compress_texture: the chain exceeds 2^32 texels");
+
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    if ((rc = grow_to(ctx->compressSource, sourceBytes, s))) return rc;
+    if ((rc = grow_to(ctx->compressTiled, tiledWords * 4u, s))) return rc;
+    if ((rc = grow_to(ctx->compressPayload, (size_t)layout.bytes, s))) return rc;
+    if ((rc = ctx->compressEvents.create())) return rc;
+    ctx->compressTimed = false;
+    // stages between the events: source up + tiling + mip generation, encoding, payload back
+    const bool srgb = (flags & PROSPER_PT_COMPRESS_SRGB) != 0;
+    const auto enqueue = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = hipEventRecord(ctx->compressEvents.events[0], s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(ctx->compressSource.ptr, src->texels, sourceBytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctx->compressTiled.ptr, 0, tiledWords * 4u, s)) != hipSuccess) return e; // (tile padding)
+        size_t sourceOffset = 0, payloadOffset = 0;
+        for (uint32_t l = 0; l < levels; ++l)
+        {
+            const uint32_t w = std::max(w0 >> l, 1u), h = std::max(h0 >> l, 1u);
+            uint32_t *level = ctx->compressTiled.as<uint32_t>() + tiledOffset[l];
+            if (l < supplied)
+            {
+                launch_retile_rgba8(ctx->compressSource.as<uint8_t>() + sourceOffset, w, h, (w + kTexTileW - 1u) / kTexTileW, level, s);
+                sourceOffset += (size_t)w * h * 4u;
+            }
+            else
+                launch_generate_mip(
+                    ctx->compressTiled.as<uint32_t>() + tiledOffset[l - 1u], std::max(w0 >> (l - 1u), 1u), std::max(h0 >> (l - 1u), 1u), level, w, h, srgb, s);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ctx->compressEvents.events[1], s)) != hipSuccess) return e;
+        for (uint32_t l = 0; l < levels; ++l)
+        {
+            const uint32_t w = std::max(w0 >> l, 1u), h = std::max(h0 >> l, 1u);
+            const uint32_t *level = ctx->compressTiled.as<uint32_t>() + tiledOffset[l];
+            uint8_t *out = ctx->compressPayload.as<uint8_t>() + payloadOffset;
+            if (layout.format == PROSPER_PT_FORMAT_BC7_UNORM)
+            {
+                launch_bc7_encode_level(level, w, h, 0u, out, s);
+                payloadOffset += (size_t)(w / 4u) * (h / 4u) * 16u;
+            }
+            else
+            {
+                // compress()'s memcpy branch: the raw chain
+                launch_untile_level(level, w, h, out, s);
+                payloadOffset += (size_t)w * h * 4u;
+            }
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ctx->compressEvents.events[2], s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dst, ctx->compressPayload.ptr, (size_t)layout.bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        return hipEventRecord(ctx->compressEvents.events[3], s);
+    };
+    // (whatever was enqueued is waited for, also after a failure: `src` and `dst` are borrowed for the call only)
+    const hipError_t e = enqueue();
+    const hipError_t f = hipStreamSynchronize(s);
+    PPT_HIP(e);
+    PPT_HIP(f);
+    ctx->compressTimed = true;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_compress_texture_timing(prosper_pt_ctx *ctx, float *prepareMs, float *encodeMs, float *readbackMs)
+{
+    if (!ctx || !prepareMs || !encodeMs || !readbackMs) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_compress_texture_timing: null argument");
+    if (!ctx->compressTimed) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_compress_texture_timing: no prosper_pt_compress_texture has completed");
+    PPT_HIP(hipSetDevice(ctx->device));
+    float ms[3];
+    const int rc = ctx->compressEvents.elapsed(ms);
+    if (rc != PROSPER_PT_OK) return rc;
+    *prepareMs = ms[0];
+    *encodeMs = ms[1];
+    *readbackMs = ms[2];
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_debug_bc7_encode_blocks(
+    prosper_pt_ctx *ctx, const uint32_t *texels, uint32_t n, uint32_t modeMask, uint32_t *blocks, uint32_t *sse, void *stream)
+{
+    if (!ctx || (n && (!texels || !blocks || !sse))) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_bc7_encode_blocks: null argument");
+    if (modeMask & ~kBc7EncodeModes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_bc7_encode_blocks: modeMask has bits 4, 5 and 6");
+    if (n == 0) return PROSPER_PT_OK;
+    if (n > (1u << 26)) return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_debug_bc7_encode_blocks: more than 2^26 blocks");
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc;
+    // blocks and errors side by side: 16 + 4 bytes per block
+    if ((rc = grow_to(ctx->compressSource, (size_t)n * 64u, s))) return rc;
+    if ((rc = grow_to(ctx->compressPayload, (size_t)n * 20u, s))) return rc;
+    uint32_t *dBlocks = ctx->compressPayload.as<uint32_t>(), *dSse = dBlocks + (size_t)n * 4u;
+    PPT_HIP(hipMemcpyAsync(ctx->compressSource.ptr, texels, (size_t)n * 64u, hipMemcpyHostToDevice, s));
+    launch_bc7_encode_blocks(ctx->compressSource.as<uint32_t>(), n, modeMask, dBlocks, dSse, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(blocks, dBlocks, (size_t)n * 16u, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sse, dSse, (size_t)n * 4u, hipMemcpyDeviceToHost, s);
+    const hipError_t f = hipStreamSynchronize(s);
+    PPT_HIP(e);
+    PPT_HIP(f);
+    return PROSPER_PT_OK;
 }
 
 } // extern "C"

@@ -149,6 +149,8 @@ class SpotLightsBuffer(C.Structure):
 
 FORMAT_RGBA8_UNORM = 0
 FORMAT_BC7_UNORM = 1
+COMPRESS_SRGB = 1 << 0           # prosper_pt_compress_texture: generated levels average RGB in linear light
+COMPRESS_GENERATE_MIPS = 1 << 1  # ... Texture2DOptions::generateMipMaps
 FILTER_NEAREST, FILTER_LINEAR = 0, 1
 WRAP_REPEAT, WRAP_MIRRORED_REPEAT, WRAP_CLAMP_TO_EDGE = 0, 1, 2
 

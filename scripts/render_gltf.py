@@ -158,6 +158,8 @@ def main():
     ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
+    ap.add_argument("--build-texture-cache", action="store_true",
+                    help="compress every image whose prosper_cache file is missing or stale (GPU BC7 encoder) before loading")
     args = ap.parse_args()
     if args.forward and (args.deferred or args.restir_di):
         ap.error("--forward is the forward path: it does not go with --deferred or --restir-di")
@@ -176,6 +178,12 @@ def main():
     from prosper_amd import capi, dds, gltf, ktx, structs as S
     from prosper_amd.rt_reference import Bloom, Camera, DepthOfField, ForwardRenderer, GBufferTracer, TemporalAntiAliasing
     w, h = (int(v) for v in args.size.lower().split("x"))
+    if args.build_texture_cache:
+        from prosper_amd import texture_cache
+        builder = capi.Context(0)
+        for cached in texture_cache.build_for_gltf(args.gltf, builder):
+            print("texture cache: wrote %s" % cached)
+        builder.close()
     # prosper_cache BC7 files are decoded by the library at upload; with --texture-lod their mip levels go along
     world = gltf.load_gltf(args.gltf, bc7_on_gpu=True, mip_chains=args.texture_lod)
     if world.missing_images:
