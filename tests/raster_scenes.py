@@ -155,6 +155,338 @@ def list_world(count):
     return w
 
 
+# ---- the sweep's scenes (tests/test_raster_sweep_cpu.py states what each has to reach) ----
+
+SWEEP_EXTENT = (96, 80)  # 3 x 3 tiles of 32 x 32, the last row of tiles half as high
+
+
+def _half(points):
+    """the positions as a mesh's buffer holds them (fp16), finite"""
+    p = np.asarray(points, np.float64).astype(np.float16).astype(F)
+    assert np.isfinite(p).all()
+    return p
+
+
+def _facing(p):
+    """the triangle's front looks at the eye at the origin: counter-clockwise seen from there"""
+    p = np.asarray(p, np.float64)
+    return float(np.dot(np.cross(p[1] - p[0], p[2] - p[0]), -p[0])) > 0.0
+
+
+def _materials(world, n):
+    return [world.add_material(base_color=(0.8 - 0.1 * k, 0.5 + 0.1 * k, 0.4, 1.0), metallic=0.0, roughness=0.6 + 0.1 * k) for k in range(n)]
+
+
+def _light(world):
+    world.add_point_light((1.0, 1.0, 1.0), 100.0, (0.0, 3.0, 0.0))
+
+
+def _queue_kind(view, points):
+    """what the rasteriser does with a front-facing triangle at SWEEP_EXTENT: 0 queued unclipped, 1 clipped by the near plane
+    alone, 2 by the guard band alone, 3 by both; None: anything else"""
+    import raster_reference as R
+    clip = R.to_clip(view, np.eye(4, dtype=F)[:3], points)
+    X, Y, _, ok = R.snap(view, clip)
+    if R.is_fast(clip, ok).all():
+        bx = R.box(X, Y, view.width, view.height)
+        side = max(bx[2] - bx[0], bx[3] - bx[1]) + 1
+        return 0 if R.area2(X, Y) < 0 and min(bx[2] - bx[0], bx[3] - bx[1]) >= 0 and side > R.MEDIUM_SIDE else None
+    out = ~(R.plane_distances(view, clip) >= 0)
+    if out.all(axis=0).any() or out[:, 1].any() or len(R.clip_polygon(view, clip)) < 3:
+        return None
+    # (a vertex behind the eye is outside everything: the guard band's kinds are told by the vertices in front of it)
+    return (1 if out[:, 0].any() else 0) + (2 if out[clip[:, 3] > 0, 2:].any() else 0)
+
+
+def _queue_group(rng, count):
+    """Up to 124 queue-class triangles over a pool of 64 vertices: 22 points near the image's left edge and 22 near its right
+    one at depths of 0.4 to 30, 10 behind the near plane and far above the view, 10 far beyond the guard band.  A
+    triangle's kind is its index modulo 4 (_queue_kind): a wedge across the whole image; two neighbours of one side and a
+    point behind the near plane; two and a point beyond the guard band; one of each, starting far away because it is wide.
+    What such a triangle shows of itself is a thin band near the depth of its side points: many triangles win pixels.
+    -> (points fp16 [64, 3], triangles)"""
+    import raster_reference as R
+    assert count <= M.MAX_TRIANGLES
+    view = R.View(CS.camera_at(width=SWEEP_EXTENT[0], height=SWEEP_EXTENT[1]))
+    aspect = SWEEP_EXTENT[0] / SWEEP_EXTENT[1]
+    side = []
+    for sign in (-1.0, 1.0):
+        d = 10.0 ** rng.uniform(-0.4, 1.45, 22)
+        side.append(np.stack([sign * rng.uniform(0.8, 1.1, 22) * aspect * d, rng.uniform(-0.95, 0.95, 22) * d, -d], axis=1))
+    behind = np.stack([rng.uniform(-1.0, 1.0, 10), rng.uniform(20.0, 60.0, 10), rng.uniform(0.0, 0.5, 10)], axis=1)
+    d = 10.0 ** rng.uniform(-0.4, 1.45, 10)
+    far = rng.uniform(40000.0, 60000.0, 10) * rng.choice([-1.0, 1.0], 10)
+    along_x = rng.random(10) < 0.5
+    far = np.where(along_x, far, np.abs(far))  # (above, like the points behind: a triangle of both never passes the eye's front)
+    guard = np.stack([np.where(along_x, far, rng.uniform(-1.0, 1.0, 10) * d), np.where(along_x, rng.uniform(-1.0, 1.0, 10) * d, far), -d], axis=1)
+    points = _half(np.concatenate(side + [behind, guard]))
+    height = points[:44, 1] / -points[:44, 2]  # where a side's point lies along its edge of the image
+    far_half = [int(i) for i in np.argsort(points[:44, 2])[:22]]
+
+    def neighbour(i):
+        """another point of i's side, among the two nearest to it along the edge"""
+        same = [j for j in range(22 * (i // 22), 22 * (i // 22) + 22) if j != i]
+        same.sort(key=lambda j: abs(height[j] - height[i]))
+        return same[int(rng.integers(0, 2))]
+
+    tris = []
+    while len(tris) < count:
+        kind = len(tris) % 4
+        i = int(rng.integers(0, 44))
+        if kind == 0:
+            t = [i, neighbour(i), int(rng.integers(0, 22)) + (22 if i < 22 else 0)]
+        elif kind == 1:
+            t = [i, neighbour(i), 44 + int(rng.integers(0, 10))]
+        elif kind == 2:
+            t = [i, neighbour(i), 54 + int(rng.integers(0, 10))]
+        else:
+            i = far_half[int(rng.integers(0, len(far_half)))]
+            t = [i, 44 + int(rng.integers(0, 10)), 54 + int(rng.integers(0, 10))]
+        if not _facing(points[t]):
+            t = [t[0], t[2], t[1]]
+        if tuple(t) not in tris and _queue_kind(view, points[t]) == kind:
+            tris.append(tuple(t))
+    return points, tris
+
+
+def queue_world(n, grouped):
+    """`n` triangles that all go to the queue at SWEEP_EXTENT, a quarter each of: unclipped with a box side above 64 pixel
+    centres; crossing the near plane; reaching beyond the guard band; both.  Steeply tilted wedges at depths of 0.4 to 30, so
+    that many of them win pixels.  grouped False: a meshlet per triangle; True: meshlets of up to 124 triangles over 64
+    vertices, so that a wave appends up to 64 records in one ballot, in both rounds.  The first 124 triangles are one mesh
+    under one material, the rest another under another."""
+    rng = np.random.default_rng(1000 + n)
+    w = scenes.World()
+    mats = _materials(w, 2)
+    for k, at in enumerate(range(0, n, M.MAX_TRIANGLES)):
+        points, tris = _queue_group(rng, min(M.MAX_TRIANGLES, n - at))
+        material = mats[min(k, 1)]
+        mesh = _mesh(w, material, points, tris, groups=[(list(range(64)), tris)] if grouped else None)
+        w.add_instance(w.add_model([(mesh, material)]))
+    _light(w)
+    return w
+
+
+_ZOO = []
+
+
+def _zoo_triangles():
+    """The seeded search of clip_zoo_world, made once: -> [(points fp16 [3, 3], polygon size, fan triangles skipped)]"""
+    import raster_reference as R
+    if _ZOO:
+        return _ZOO
+    rng = np.random.default_rng(77)
+    view = R.View(CS.camera_at(width=SWEEP_EXTENT[0], height=SWEEP_EXTENT[1]))
+    identity = np.eye(4, dtype=F)[:3]
+    by_size, skipping = {}, []
+    wanted = {4: 3, 5: 3, 6: 3, 7: 3, 8: 1, 9: 1}
+    for attempt in range(4000):  # the fixed budget; 8 and 9 vertices are looked for over its first 800 attempts only
+        full = len(skipping) >= 4 and all(len(by_size.get(s, [])) >= wanted[s] for s in (4, 5, 6, 7))
+        if full and (attempt >= 800 or any(s >= 8 for s in by_size)):
+            break
+        if attempt % 4 == 3 and len(skipping) < 4:
+            # a vertex a few fp16 steps behind the near plane: two cuts that snap onto each other
+            d = rng.uniform(0.5, 4.0)
+            p = np.array([(rng.uniform(-1, 1) * d, rng.uniform(-1, 1) * d, -d), (rng.uniform(-1, 1) * d, rng.uniform(-1, 1) * d, -d),
+                          (rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), -CS.NEAR + rng.uniform(0.0, 3e-4))])
+        else:
+            scale = 10.0 ** rng.uniform(2.5, 4.5)
+            p = rng.normal(size=(3, 3)) * [scale, scale, 1.0] + [0.0, 0.0, -0.3]
+        p = np.clip(p, -60000.0, 60000.0).astype(np.float16).astype(F)
+        if not _facing(p):
+            p = p[::-1].copy()
+        clip = R.to_clip(view, identity, p)
+        X, Y, _, ok = R.snap(view, clip)
+        out = ~(R.plane_distances(view, clip) >= 0)
+        if R.is_fast(clip, ok).all() or out.all(axis=0).any():
+            continue
+        # a plane adds a vertex at the most, and only where it separates the triangle's vertices
+        most = 3 + int((out.any(axis=0) & ~out.all(axis=0)).sum())
+        if len(skipping) >= 4 and not any(len(by_size.get(s, [])) < n for s, n in wanted.items() if s <= most):
+            continue
+        poly = R.clip_polygon(view, clip)
+        if len(poly) < 4:
+            continue
+        PX, PY, _, pok = R.snap(view, poly)
+        if not pok.all():
+            continue
+        areas = [R.area2(PX[[0, k, k + 1]], PY[[0, k, k + 1]]) for k in range(1, len(poly) - 1)]
+        drawn, skipped = sum(a < 0 for a in areas), sum(a >= 0 for a in areas)
+        if drawn == 0:
+            continue
+        if skipped and len(skipping) < 4:
+            skipping.append((p, len(poly), skipped))
+        elif not skipped and len(by_size.setdefault(len(poly), [])) < wanted[len(poly)]:
+            by_size[len(poly)].append((p, len(poly), 0))
+    _ZOO.extend([t for s in sorted(by_size) for t in by_size[s]] + skipping)
+    return _ZOO
+
+
+def clip_zoo_world():
+    """Triangles whose clipped polygons at SWEEP_EXTENT have 4, 5, 6 and 7 vertices (three each; 8 or 9 where the search's
+    budget finds one), and four whose fan holds a triangle that snaps to zero or positive area next to ones that are drawn.
+    A meshlet per triangle."""
+    w = scenes.World()
+    (m,) = _materials(w, 1)
+    found = _zoo_triangles()
+    points = np.concatenate([p for p, _, _ in found])
+    mesh = _mesh(w, m, points, [(3 * k, 3 * k + 1, 3 * k + 2) for k in range(len(found))])
+    w.add_instance(w.add_model([(mesh, m)]))
+    _light(w)
+    return w
+
+
+def _pack(rng, tris):
+    """consecutive triangles into meshlets of random size from 1 to 124, of at most 64 vertices -> groups for _attach"""
+    groups, at = [], 0
+    while at < len(tris):
+        want = int(rng.integers(1, M.MAX_TRIANGLES + 1))
+        verts, local = [], []
+        while at < len(tris) and len(local) < want:
+            new = [v for v in dict.fromkeys(tris[at]) if v not in verts]
+            if len(verts) + len(new) > M.MAX_VERTICES:
+                break
+            verts += new
+            local.append(tuple(verts.index(v) for v in tris[at]))
+            at += 1
+        groups.append((verts, local))
+    return groups
+
+
+def _soup_mesh(rng, world, material, count, **kw):
+    """`count` triangles in strips of 1 to 6 that share their vertices, in a frustum-shaped volume down -z:
+    screen size log-uniform from a tenth of a pixel to several tiles, any orientation, either winding; of twelve strips one is
+    pulled through the near plane, one beyond the guard band, one lies wholly outside, one has coincident vertices"""
+    points, tris = [], []
+    while len(tris) < count:
+        d = 10.0 ** rng.uniform(-0.3, 1.2)
+        size = d * 10.0 ** rng.uniform(-2.2, 0.7)
+        c = np.array([rng.uniform(-1.3, 1.3) * d, rng.uniform(-1.0, 1.0) * d, -d])
+        kind = int(rng.integers(0, 12))
+        if kind == 2:
+            c[int(rng.integers(0, 2))] = rng.choice([-1.0, 1.0]) * (3.0 * d + 4.0 * size)
+        a = rng.uniform(0.0, 2.0 * np.pi)
+        tilt = min(1.0, 0.2 * d / size)  # (a strip of several tiles keeps clear of the near plane unless it is pulled there)
+        u = np.array([np.cos(a), np.sin(a), rng.uniform(-0.5, 0.5) * tilt]) * size
+        v = np.array([-np.sin(a), np.cos(a), rng.uniform(-0.5, 0.5) * tilt]) * size
+        k = int(rng.integers(1, 7))
+        strip = [c + u * (j // 2) + v * (j % 2) + rng.uniform(-0.15, 0.15, 3) * size * [1.0, 1.0, tilt] for j in range(k + 2)]
+        if kind == 0:
+            strip[int(rng.integers(0, k + 2))][2] = rng.uniform(0.0, 1.0)
+        if kind == 1:
+            strip[int(rng.integers(0, k + 2))][:2] *= 1e4
+        if kind == 3:
+            strip[-1] = strip[-3].copy()  # the last triangle has no area, under any transform
+        base = len(points)
+        flip = rng.random() < 0.35
+        points += [np.clip(p, -60000.0, 60000.0) for p in strip]
+        for j in range(k):
+            t = (base + j, base + j + 1, base + j + 2)
+            tris.append((t[1], t[0], t[2]) if (j % 2 == 1) != flip else t)
+    tris = tris[:count]
+    return _mesh(world, material, _half(points), tris, groups=_pack(rng, tris), **kw)
+
+
+def soup_world(seed):
+    """Two meshes of triangle strips of every size class (_soup_mesh), one with u16 and one with u32 meshlet vertices, in
+    meshlets of random size; five draw instances: the first mesh as it is, mirrored, and as it is once more (equal depths
+    across draw instances at every pixel); the second under a non-uniform scale and under a rotation.  -> (world, names)"""
+    rng = np.random.default_rng(seed)
+    w = scenes.World()
+    mats = _materials(w, 3)
+    first = _soup_mesh(rng, w, mats[0], 125)
+    second = _soup_mesh(rng, w, mats[1], 105, force_u32_indices=True)
+    names = {}
+    for name, mesh, material, transform in (
+            ("plain", first, mats[0], W.translate((0.1, -0.05, -0.2))),
+            ("mirrored", first, mats[1], W.translate((-0.2, 0.1, 0.1)) @ W.scale((-1.0, 1.0, 1.0))),
+            ("stretched", second, mats[1], W.scale((1.3, 0.7, 1.1))),
+            ("duplicate", first, mats[0], W.translate((0.1, -0.05, -0.2))),
+            ("turned", second, mats[2], W.rotate_z(0.8) @ W.rotate_y(0.15))):
+        w.add_instance(w.add_model([(mesh, material)]), transform)
+        names[name] = len(w.model_instances) - 1
+    _light(w)
+    return w, names
+
+
+def graded_floor_world(columns=(8, 1, 1, 1, 1) * 3, nz=28, below=0.06, nearest=0.06, ratio=1.2, half=(2.4, 1.0), roll=0.3):
+    """One indexed planar grid of nx x nz quads `below` the eye: its rows are graded geometrically in distance, from `nearest`
+    (behind the near plane, 0.1) on - queue class where the floor enters the image, a thirtieth of a pixel deep at the far end -
+    and the floor is turned about the vertical, so that an image row crosses rows of the grid of several classes.  No jitter:
+    no triangle folds under the fp16 rounding.  Meshlets by the builder."""
+    w = scenes.World()
+    (m,) = _materials(w, 1)
+    nx = len(columns)
+    edges = np.concatenate([[0.0], np.cumsum(columns)]) / float(sum(columns))
+    points = []
+    for z in -nearest * ratio ** np.arange(nz + 1):
+        reach = half[0] + half[1] * abs(z)
+        points += [(reach * (2.0 * x - 1.0), -below, z) for x in edges]
+    tris = []
+    for j in range(nz):
+        for i in range(nx):
+            v = j * (nx + 1) + i
+            a, b, c, d = v, v + 1, v + nx + 2, v + nx + 1  # a, b on the nearer row
+            tris += [(a, b, c), (a, c, d)] if (i + j) % 2 else [(a, b, d), (b, c, d)]
+    points = np.array(points, F)
+    mesh = w.add_mesh(points, np.array(tris, np.uint32).reshape(-1), m, normals=np.tile(np.array([[0, 1, 0]], F), (len(points), 1)))
+    w.add_instance(w.add_model([(mesh, m)]), W.rotate_z(roll))
+    _light(w)
+    w.add_meshlets()
+    return w
+
+
+def scan_world():
+    """Four large BLEND triangles, tilted in depth along both image axes and overlapping only partly, in front of an opaque
+    backdrop: a pixel holds 0 to 4 layers, and no two neighbouring pixels the same keys.  They reach past the image's last
+    rows, where the scan's last blocks lie.  Made for a camera at the origin looking down -z (any extent)."""
+    from prosper_amd import structs as S
+    w = scenes.World()
+    tris = [[(-2.6, -2.4, -1.6), (3.4, -2.9, -2.9), (-1.9, 2.2, -2.3)],
+            [(3.0, 2.6, -1.4), (-3.1, 2.9, -2.6), (2.4, -3.3, -3.2)],
+            [(-0.3, 3.1, -1.9), (-2.2, -3.4, -3.4), (2.3, -3.0, -1.5)],
+            [(-3.6, 0.4, -2.7), (1.9, -1.4, -1.7), (1.2, 2.7, -3.6)]]
+    for k, p in enumerate(tris):
+        mat = w.add_material(base_color=(0.3 + 0.2 * k, 0.8 - 0.15 * k, 0.4, 0.3 + 0.15 * k), metallic=0.0, roughness=0.5, alpha_mode=S.ALPHA_MODE_BLEND)
+        p = _half(p)
+        mesh = _mesh(w, mat, p if _facing(p) else p[::-1], [(0, 1, 2)])
+        w.add_instance(w.add_model([(mesh, mat)]))
+    _backdrop(w)
+    _light(w)
+    return w
+
+
+def _backdrop(world):
+    """one far opaque quad over the whole view, so that the scene has an opaque list too"""
+    m = world.add_material(base_color=(0.5, 0.5, 0.5, 1.0), metallic=0.0, roughness=0.8)
+    mesh = _mesh(world, m, [(-400.0, -400.0, -90.0), (400.0, -400.0, -90.0), (400.0, 400.0, -90.0), (-400.0, 400.0, -90.0)], [(0, 1, 2), (0, 2, 3)])
+    world.add_instance(world.add_model([(mesh, m)]))
+
+
+def blend_variant(world):
+    """the same geometry under BLEND materials without a texture (alpha 0.3, 0.5, 0.7, ...), in front of one far opaque
+    backdrop: for the layer modes.  Changes `world` and returns it."""
+    from prosper_amd import structs as S
+    for k, m in enumerate(world.materials[1:]):
+        m.alphaMode = S.ALPHA_MODE_BLEND
+        m.baseColorFactor.w = 0.3 + 0.2 * (k % 3)
+    _backdrop(world)
+    world._frozen = None
+    return world
+
+
+def mask_variant(world):
+    """the same geometry under MASK materials without a texture, cutoff 0.5: the first, third, ... with an alpha factor of
+    0.75 (every fragment kept), the others of 0.25 (every fragment discarded).  Changes `world` and returns it."""
+    from prosper_amd import structs as S
+    for k, m in enumerate(world.materials[1:]):
+        m.alphaMode = S.ALPHA_MODE_MASK
+        m.alphaCutoff = 0.5
+        m.baseColorFactor.w = 0.25 if k % 2 else 0.75
+    world._frozen = None
+    return world
+
+
 def closed_world(n=5):
     """A closed, outward-facing object in front of the camera: a cube of n x n quads per face pushed out onto a sphere of
     radius 1.5 at z = -3.6 (every vertex is shared by index, so the fp16 rounding opens no crack), and a smaller plain cube
