@@ -70,6 +70,10 @@ def lib():
     L.prosper_pt_compress_texture.argtypes = [vp, C.POINTER(S.TextureDesc), u32, vp, C.c_uint64, vp]
     L.prosper_pt_debug_bc7_encode_blocks.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.prosper_pt_get_compress_texture_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.prosper_pt_prepare_mesh.argtypes = [vp, C.POINTER(S.MeshSource), u32, C.POINTER(S.PreparedMesh), vp]
+    L.prosper_pt_read_prepared_mesh.argtypes = [vp, vp, C.c_uint64]
+    L.prosper_pt_read_prepared_tangents.argtypes = [vp, vp, C.c_uint64]
+    L.prosper_pt_get_prepare_mesh_timing.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
     L.prosper_pt_set_texture_lod.argtypes = [vp, C.c_int, C.c_float]
     L.prosper_pt_set_texture_lod_debug.argtypes = [vp, C.c_int]
     L.prosper_pt_read_texture_lod_derivatives.argtypes = [vp, vp, C.c_size_t, vp]
@@ -678,6 +682,37 @@ class Context:
         _check(lib().prosper_pt_debug_bc7_encode_blocks(
             self._h, texels.ctypes.data, n, mode_mask, blocks.ctypes.data, sse.ctypes.data, C.c_void_p(stream)))
         return blocks, sse
+
+    def prepare_mesh(self, positions, indices, normals=None, tangents=None, uvs=None, generate_tangents=True, meshlets=True, stream=None):
+        """prosper's loadNextMesh on the GPU: a primitive's accessors -> (header dict, blob words, tangents), what
+        mesh_cache.pack_cache(..., with_meshlets=meshlets, ordered=True) gives.  `generate_tangents` acts when `tangents`
+        is None and `uvs` is not (tangents.generate_tangents, on the GPU); the third result is then the float32 [n, 4]
+        tangents, otherwise None."""
+        arrays = {"positions": np.ascontiguousarray(positions, np.float32).reshape(-1, 3), "indices": np.ascontiguousarray(indices, np.uint32).reshape(-1)}
+        n = arrays["positions"].shape[0]
+        for name, value, width in (("normals", normals, 3), ("tangents", tangents, 4), ("texCoord0s", uvs, 2)):
+            if value is not None:
+                arrays[name] = np.ascontiguousarray(value, np.float32).reshape(n, width)
+        src = S.MeshSource(vertexCount=n, indexCount=arrays["indices"].size)
+        for name, a in arrays.items():
+            setattr(src, name, a.ctypes.data if a.size else None)
+        flags = (S.PREPARE_GENERATE_TANGENTS if generate_tangents else 0) | (S.PREPARE_MESHLETS if meshlets else 0)
+        out = S.PreparedMesh()
+        _check(lib().prosper_pt_prepare_mesh(self._h, C.byref(src), flags, C.byref(out), C.c_void_p(stream)))
+        header = {name: getattr(out, name) for name, _ in S.PreparedMesh._fields_}
+        blob = np.zeros(out.blobByteCount // 4, np.uint32)
+        _check(lib().prosper_pt_read_prepared_mesh(self._h, blob.ctypes.data, blob.nbytes))
+        generated = None
+        if generate_tangents and tangents is None and uvs is not None:
+            generated = np.zeros((n, 4), np.float32)
+            _check(lib().prosper_pt_read_prepared_tangents(self._h, generated.ctypes.data, generated.nbytes))
+        return header, blob, generated
+
+    def prepare_mesh_timing(self):
+        """(tangents, pack, meshlet partition on the host, bounds, read back) milliseconds of the last prepare_mesh."""
+        ms = [C.c_float() for _ in range(5)]
+        _check(lib().prosper_pt_get_prepare_mesh_timing(self._h, *[C.byref(m) for m in ms]))
+        return tuple(m.value for m in ms)
 
     def set_texture_lod(self, enabled, lod_bias=0.0):
         """The traced G-buffer samples materials through the mip chains (a CREATE_TEXTURE_MIPS context), with `lod_bias`."""

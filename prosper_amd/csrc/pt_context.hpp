@@ -382,6 +382,15 @@ struct prosper_pt_ctx
     ppt::DeviceBuffer compressSource, compressTiled, compressPayload;
     ppt::StageEvents<3> compressEvents; // around the last compression's stages: prepare, encode, read back
     bool compressTimed = false;
+    // prosper_pt_prepare_mesh (pt_mesh_passes.cpp): the source streams as the caller holds them, the six fixed-point
+    // tangent sums of every vertex, the float32 tangents and the blob on the device; on the host the sections the
+    // partition fills, and what the last call left for the read-backs
+    ppt::DeviceBuffer prepareSource, prepareSums, prepareTangents, prepareBlob;
+    ppt::StageEvents<4> prepareEvents; // around the last call's stages: tangents, pack, bounds, read back
+    std::vector<uint32_t> prepareImage, preparedBlob;
+    std::vector<float> preparedTangents;
+    float prepareMeshletHostMs = 0.0f;
+    bool prepared = false, preparedTangentsValid = false, prepareTimed = false;
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
     // workspace, the stack-overflow array and the launch chains (pt_kernels.hpp WavefrontChains) with their

@@ -24,7 +24,8 @@ T3-T9 tables prosper would upload for the file -
 
 Not restated (third-party arithmetic the survey lists as result-invariant or unpinned, §8c): meshoptimizer's
 vertex/index reordering (changes PrimitiveID colours only), mikktspace (a primitive without TANGENT keeps no
-tangents here, i.e. its normal map is ignored), BC7 compression of the textures (texels are the decoded
+tangents when it is packed here, i.e. its normal map is ignored; `mesh_cache.build_for_gltf` generates them on the GPU by
+the rule of `prosper_amd/tangents.py` and `load_gltf(use_mesh_cache=True)` loads them), BC7 compression of the textures (texels are the decoded
 PNG/JPEG bytes), glm's fp32 `inverse`/`decompose` (float64 here, rounded once).
 """
 import base64
@@ -324,7 +325,23 @@ _FILTERS = {9728: S.FILTER_NEAREST, 9984: S.FILTER_NEAREST, 9986: S.FILTER_NEARE
 _WRAPS = {33071: S.WRAP_CLAMP_TO_EDGE, 33648: S.WRAP_MIRRORED_REPEAT, 10497: S.WRAP_REPEAT}
 
 
-def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on_gpu=False, mip_chains=False):
+def primitive_source(d, prim):
+    """The accessors prosper reads of a primitive (WorldData.cpp:830-915) -> dict(positions, indices, normals, tangents,
+    uvs), the last two None where the primitive has none."""
+    if prim.get("mode", 4) != 4:
+        raise GltfError("only triangle lists are supported")
+    if "indices" not in prim:
+        raise GltfError("non-indexed primitives are not supported (the reference asserts on them)")
+    attrs = prim["attributes"]
+    if "POSITION" not in attrs or "NORMAL" not in attrs:
+        raise GltfError("POSITION and NORMAL are required (the reference asserts on them)")
+    return dict(positions=d.floats(attrs["POSITION"])[:, :3], indices=d.indices(prim["indices"]),
+                normals=d.floats(attrs["NORMAL"])[:, :3],
+                tangents=d.floats(attrs["TANGENT"])[:, :4] if "TANGENT" in attrs else None,
+                uvs=d.floats(attrs["TEXCOORD_0"])[:, :2] if "TEXCOORD_0" in attrs else None)
+
+
+def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on_gpu=False, mip_chains=False, use_mesh_cache=False):
     """Reads `path` (.gltf or .glb) into a World laid out the way prosper lays the same file out.
 
     With `use_texture_cache`, an image file whose `prosper_cache/<name>.dds` exists (prosper's BC7 / RGBA8 cache,
@@ -338,6 +355,12 @@ def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on
     a context created with CREATE_TEXTURE_MIPS samples prosper's own chain instead of generating one.  An image without
     a cache stays level 0 alone.
 
+    With `use_mesh_cache` (opt-in) a primitive whose `prosper_cache/cache<meshIndex>.prosper_mesh` is valid - version 4
+    and the .gltf file's write time, prosper's cacheValid - is added from that blob as it is
+    (`mesh_cache.add_cached_mesh`: with whatever tangents and meshlets it carries, e.g. those of
+    `mesh_cache.build_for_gltf`) instead of being packed here; `world.cached_meshes` lists the files read.  The default
+    does not look at the files.
+
     `world.missing_images` lists the image URIs that could not be read; they become 1x1 white textures
     (what prosper's texture slot 0, `empty.png`, is)."""
     d = _Document(path)
@@ -346,6 +369,7 @@ def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on
     w.missing_images = []
     w.cached_images = []
     w.stale_cached_images = []
+    w.cached_meshes = []
 
     # samplers: index + 1 (WorldData.cpp:699-719)
     for smp in doc.get("samplers", []):
@@ -417,22 +441,23 @@ def load_gltf(path, load_images=True, scene=None, use_texture_cache=True, bc7_on
                        normal_tex=pair(m.get("normalTexture")))
 
     # meshes: one Model per glTF mesh, one mesh per primitive (WorldData.cpp:830-915)
+    mesh_index = 0
     for mesh in doc.get("meshes", []):
         subs = []
         for prim in mesh["primitives"]:
-            if prim.get("mode", 4) != 4:
-                raise GltfError("only triangle lists are supported")
-            if "indices" not in prim:
-                raise GltfError("non-indexed primitives are not supported (the reference asserts on them)")
-            attrs = prim["attributes"]
-            if "POSITION" not in attrs or "NORMAL" not in attrs:
-                raise GltfError("POSITION and NORMAL are required (the reference asserts on them)")
+            source = primitive_source(d, prim)
             material = prim["material"] + 1 if "material" in prim else 0
-            mi = w.add_mesh(
-                d.floats(attrs["POSITION"])[:, :3], d.indices(prim["indices"]), material,
-                normals=d.floats(attrs["NORMAL"])[:, :3],
-                tangents=d.floats(attrs["TANGENT"])[:, :4] if "TANGENT" in attrs else None,
-                uvs=d.floats(attrs["TEXCOORD_0"])[:, :2] if "TEXCOORD_0" in attrs else None)
+            mi = None
+            if use_mesh_cache:
+                from . import mesh_cache
+                cached = mesh_cache.cache_path(path, mesh_index)
+                if mesh_cache.cache_valid(cached, path):
+                    mi = mesh_cache.add_cached_mesh(w, *mesh_cache.read_mesh_cache(cached), material)
+                    w.cached_meshes.append(cached)
+            if mi is None:
+                mi = w.add_mesh(source["positions"], source["indices"], material, normals=source["normals"],
+                                tangents=source["tangents"], uvs=source["uvs"])
+            mesh_index += 1
             subs.append((mi, material))
         w.add_model(subs)
 

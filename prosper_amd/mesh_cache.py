@@ -8,6 +8,7 @@ meshletTriangles.  Attribute offsets count u32 words from the start of the blob;
 
 The path tracer needs indices, positions, normals, tangents and uvs; meshlet sections are carried along
 untouched (the RT pass never reads them).  pack_cache writes them on request (meshlets.py)."""
+import os
 import struct
 
 import numpy as np
@@ -55,9 +56,58 @@ def write_mesh_cache(path, header, blob_words, source_write_time=0):
         f.write(blob.tobytes())
 
 
-def pack_cache(positions, indices, normals, tangents=None, uvs=None, with_meshlets=False):
+def cache_path(gltf_path, mesh_index):
+    """getCachePath (DeferredLoadingContext.cpp:492-499): `prosper_cache/cache<meshIndex>.prosper_mesh` beside the scene"""
+    return os.path.join(os.path.dirname(os.path.abspath(gltf_path)), "prosper_cache", "cache%d.prosper_mesh" % mesh_index)
+
+
+def cache_valid(cache_file, gltf_path):
+    """cacheValid (DeferredLoadingContext.cpp:561-577): the file reads as a cache of the current version and carries the
+    scene file's write time; any error reading it means invalid."""
+    from . import dds
+    try:
+        if not os.path.exists(cache_file):
+            return False
+        with open(cache_file, "rb") as f:
+            head = f.read(_HEADER.size)
+        if len(head) < _HEADER.size:
+            return False
+        magic, version, write_time = _HEADER.unpack(head)[:3]
+        return magic == MAGIC and version == VERSION and write_time == dds.source_write_time(gltf_path)
+    except (OSError, struct.error):
+        return False
+
+
+def build_for_gltf(ctx, path):
+    """What loadNextMesh does for every primitive of the glTF at `path` whose cache is missing, of another version or
+    carries another write time than the file's (`cache_valid`): tangents where the primitive has uvs and none of its own,
+    meshlets, packing - on the GPU, `ctx.prepare_mesh` of a capi.Context - and the cache file, written through a temporary
+    one.  meshIndex is load_gltf's own primitive order.  -> the files written"""
+    from . import dds, gltf
+    d = gltf._Document(path)
+    write_time = dds.source_write_time(path)
+    written, mesh_index = [], 0
+    for mesh in d.doc.get("meshes", []):
+        for prim in mesh["primitives"]:
+            cached = cache_path(path, mesh_index)
+            mesh_index += 1
+            if cache_valid(cached, path):
+                continue
+            src = gltf.primitive_source(d, prim)
+            header, blob, _ = ctx.prepare_mesh(src["positions"], src["indices"], normals=src["normals"], tangents=src["tangents"],
+                                               uvs=src["uvs"], generate_tangents=True, meshlets=True)
+            os.makedirs(os.path.dirname(cached), exist_ok=True)
+            tmp = os.path.splitext(cached)[0] + ".prosper_mesh_TMP"
+            write_mesh_cache(tmp, header, blob, source_write_time=write_time)
+            os.replace(tmp, cached)
+            written.append(cached)
+    return written
+
+
+def pack_cache(positions, indices, normals, tangents=None, uvs=None, with_meshlets=False, ordered=False):
     """What writeCache lays out for a primitive: (header, blob words).  Without meshlets by default; `with_meshlets`
-    appends the four sections of meshlets.build_meshlets in writeCache's order."""
+    appends the four sections of meshlets.build_meshlets in writeCache's order, `ordered` passed through to it (True:
+    the bytes prosper_pt_prepare_mesh gives)."""
     from .world import pack_mesh_data
     positions = np.asarray(positions, np.float32).reshape(-1, 3)
     indices = np.asarray(indices, np.uint32).reshape(-1)
@@ -88,7 +138,7 @@ def pack_cache(positions, indices, normals, tangents=None, uvs=None, with_meshle
     if with_meshlets and indices.size:
         from . import meshlets as M
         # (over the positions as the blob holds them: fp16)
-        built = M.build_meshlets(positions.astype(np.float16).astype(np.float32), indices)
+        built = M.build_meshlets(positions.astype(np.float16).astype(np.float32), indices, ordered=ordered)
         header["meshletCount"] = len(built["meshlets"])
         keys = {"meshlets": ("meshletsOffset", 1), "bounds": ("meshletBoundsOffset", 1),
                 "vertices": ("meshletVerticesOffset", 2 if short else 1), "triangles": ("meshletTrianglesByteOffset", 4)}

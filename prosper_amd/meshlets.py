@@ -44,8 +44,10 @@ def decode_cone(word):
     return b[:3].astype(np.float64) / 127.0, float(b[3]) / 127.0
 
 
-def meshlet_bounds(points, triangles):
-    """`points` [n, 3] of the meshlet's vertices, `triangles` [m, 3] into them -> the five bounds words"""
+def meshlet_bounds(points, triangles, ordered=False):
+    """`points` [n, 3] of the meshlet's vertices, `triangles` [m, 3] into them -> the five bounds words.  `ordered`: the
+    cone's dot products are elementwise float64 products added as (x*sx + y*sy) + z*sz, an order a kernel can follow
+    (csrc/pt_mesh_prepare.hip does); the default leaves them to the matrix product."""
     p = np.asarray(points, np.float64)
     centre = ((p.min(axis=0) + p.max(axis=0)) * 0.5).astype(np.float32)
     radius = _round_up_f32(float(np.sqrt(((p - centre.astype(np.float64)) ** 2).sum(axis=1)).max()))
@@ -61,7 +63,10 @@ def meshlet_bounds(points, triangles):
             seen = q.astype(np.float64)
             if (seen * seen).sum() > 0:
                 seen /= np.sqrt((seen * seen).sum())
-                mindp = float((n @ seen).min())
+                if ordered:
+                    mindp = float(((n[:, 0] * seen[0] + n[:, 1] * seen[1]) + n[:, 2] * seen[2]).min())
+                else:
+                    mindp = float((n @ seen).min())
                 if mindp > 0.1:
                     c = int(np.ceil(np.sqrt(max(0.0, 1.0 - mindp * mindp)) * 127.0)) + 1
                     if c < 127:
@@ -74,8 +79,9 @@ def meshlet_bounds(points, triangles):
     return words
 
 
-def build_meshlets(positions, indices):
-    """-> dict(meshlets uint32 [n, 4], bounds uint32 [n, 5], vertices uint32 [k], triangles uint8 [padded])"""
+def build_meshlets(positions, indices, ordered=False):
+    """-> dict(meshlets uint32 [n, 4], bounds uint32 [n, 5], vertices uint32 [k], triangles uint8 [padded]);
+    `ordered` as in meshlet_bounds"""
     positions = np.asarray(positions, np.float32).reshape(-1, 3)
     indices = np.asarray(indices, np.int64).reshape(-1, 3)
     meshlets, vertices, triangles = [], [], bytearray()
@@ -111,7 +117,7 @@ def build_meshlets(positions, indices):
     assert t.size % 4 == 0
     bounds = np.empty((len(m), 5), np.uint32)
     for i, (vo, to, vc, tc) in enumerate(m.tolist()):
-        bounds[i] = meshlet_bounds(positions[v[vo:vo + vc]], t[to:to + 3 * tc].reshape(-1, 3))
+        bounds[i] = meshlet_bounds(positions[v[vo:vo + vc]], t[to:to + 3 * tc].reshape(-1, 3), ordered=ordered)
     return dict(meshlets=m, bounds=bounds, vertices=v, triangles=t)
 
 

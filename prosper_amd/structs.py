@@ -151,6 +151,8 @@ FORMAT_RGBA8_UNORM = 0
 FORMAT_BC7_UNORM = 1
 COMPRESS_SRGB = 1 << 0           # prosper_pt_compress_texture: generated levels average RGB in linear light
 COMPRESS_GENERATE_MIPS = 1 << 1  # ... Texture2DOptions::generateMipMaps
+PREPARE_GENERATE_TANGENTS = 1 << 0  # prosper_pt_prepare_mesh: tangents for a primitive with uvs and none of its own
+PREPARE_MESHLETS = 1 << 1           # ... the four meshlet sections
 FILTER_NEAREST, FILTER_LINEAR = 0, 1
 WRAP_REPEAT, WRAP_MIRRORED_REPEAT, WRAP_CLAMP_TO_EDGE = 0, 1, 2
 
@@ -180,6 +182,27 @@ class TextureDesc(C.Structure):
         ("format", C.c_uint32),
         ("mipLevelCount", C.c_uint32),  # read by a CREATE_TEXTURE_MIPS context only: levels held by `texels` (0 / 1: level 0)
     ]
+
+
+class MeshSource(C.Structure):
+    """prosper_pt_mesh_source"""
+    _fields_ = [
+        ("positions", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("tangents", C.c_void_p),
+        ("texCoord0s", C.c_void_p),
+        ("indices", C.c_void_p),
+        ("vertexCount", C.c_uint32),
+        ("indexCount", C.c_uint32),
+    ]
+
+
+class PreparedMesh(C.Structure):
+    """prosper_pt_prepared_mesh: the cache header's thirteen fields, as mesh_cache._FIELDS"""
+    _fields_ = [(name, C.c_uint32) for name in (
+        "indexCount", "vertexCount", "meshletCount", "positionsOffset", "normalsOffset", "tangentsOffset", "texCoord0sOffset",
+        "meshletsOffset", "meshletBoundsOffset", "meshletVerticesOffset", "meshletTrianglesByteOffset", "usesShortIndices",
+        "blobByteCount")]
 
 
 class TextureMipsInfo(C.Structure):

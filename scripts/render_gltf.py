@@ -160,6 +160,9 @@ def main():
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     ap.add_argument("--build-texture-cache", action="store_true",
                     help="compress every image whose prosper_cache file is missing or stale (GPU BC7 encoder) before loading")
+    ap.add_argument("--build-mesh-cache", action="store_true",
+                    help="prepare every primitive whose prosper_cache mesh file is missing or stale (tangents, meshlets and packing "
+                         "on the GPU), then load the meshes from those files")
     args = ap.parse_args()
     if args.forward and (args.deferred or args.restir_di):
         ap.error("--forward is the forward path: it does not go with --deferred or --restir-di")
@@ -184,8 +187,14 @@ def main():
         for cached in texture_cache.build_for_gltf(args.gltf, builder):
             print("texture cache: wrote %s" % cached)
         builder.close()
+    if args.build_mesh_cache:
+        from prosper_amd import mesh_cache
+        builder = capi.Context(0)
+        for cached in mesh_cache.build_for_gltf(builder, args.gltf):
+            print("mesh cache: wrote %s" % cached)
+        builder.close()
     # prosper_cache BC7 files are decoded by the library at upload; with --texture-lod their mip levels go along
-    world = gltf.load_gltf(args.gltf, bc7_on_gpu=True, mip_chains=args.texture_lod)
+    world = gltf.load_gltf(args.gltf, bc7_on_gpu=True, mip_chains=args.texture_lod, use_mesh_cache=args.build_mesh_cache)
     if world.missing_images:
         print("missing images replaced by white: %s" % ", ".join(world.missing_images), file=sys.stderr)
     if args.env:
