@@ -799,10 +799,9 @@ static int create_context_resources(prosper_pt_ctx *ctx)
         if ((rc = ctx->chainFork.record(ws.get()))) return rc;
         PPT_HIP(hipStreamSynchronize(ws.get()));
     }
-    if (!create_gbuffer_passes(ctx) || !create_forward_passes(ctx) || !create_dof_passes(ctx) || !create_bloom_passes(ctx) || !create_taa_passes(ctx) ||
-        !create_particles_passes(ctx) || !create_debug_passes(ctx) || !create_culling_passes(ctx) || !create_raster_passes(ctx) ||
-        !create_animation_state(ctx))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
+    bool made = true;
+    for (const PassModule *m : kPassModules) made = made && m->create(ctx);
+    if (!made || !create_animation_state(ctx)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
 }
@@ -856,15 +855,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     (void)hipDeviceSynchronize();
     destroy_tiling(ctx);
     free_scene(ctx);
-    destroy_gbuffer_passes(ctx);
-    destroy_forward_passes(ctx);
-    destroy_dof_passes(ctx);
-    destroy_bloom_passes(ctx);
-    destroy_taa_passes(ctx);
-    destroy_particles_passes(ctx);
-    destroy_debug_passes(ctx);
-    destroy_culling_passes(ctx);
-    destroy_raster_passes(ctx);
+    for (const PassModule *m : kPassModules) m->destroy(ctx);
     destroy_animation_state(ctx);
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
@@ -874,10 +865,8 @@ int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *sc
     if (!ctx || !scene) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_upload_scene: null argument");
     int rc = validate_scene(scene, (ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0);
     if (rc != PROSPER_PT_OK) return rc;
-    forget_ibl_maps(ctx);
-    forget_taa_history(ctx);
-    forget_hiz(ctx);
-    forget_raster(ctx);
+    for (const PassModule *m : kPassModules)
+        if (m->forget_scene) m->forget_scene(ctx);
     PPT_HIP(hipSetDevice(ctx->device));
     discard_mesh_build(ctx); // (a worker may still be launching)
     PPT_HIP(hipDeviceSynchronize());

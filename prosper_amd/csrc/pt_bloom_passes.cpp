@@ -5,8 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "pt_bloom.hpp"
@@ -47,19 +45,7 @@ struct BloomPassState
     BloomFftState fft;
 };
 
-bool create_bloom_passes(prosper_pt_ctx *ctx)
-{
-    ctx->bloomPasses = new (std::nothrow) BloomPassState();
-    return ctx->bloomPasses != nullptr;
-}
-
-void destroy_bloom_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->bloomPasses;
-    ctx->bloomPasses = nullptr;
-}
-
-void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+static void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
 {
     const BloomPassState &st = *ctx->bloomPasses;
     const BloomParams &p = st.last;
@@ -114,12 +100,12 @@ void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> 
     }
 }
 
+extern const PassModule kBloomPasses = pass_module<BloomPassState, &prosper_pt_ctx::bloomPasses>(nullptr, list_bloom_debug_images);
+
 } // namespace ppt
 
 namespace
 {
-
-constexpr uint32_t kMaxExtent = 32768; // compose forms (2 coord + 1) * levelSize + extent in 32 bits
 
 bool finite_non_negative(float v) { return std::isfinite(v) && v >= 0.0f; }
 
@@ -229,20 +215,16 @@ int prosper_pt_bloom(
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom: the extent leaves a blurred level empty");
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom: null argument");
     const bool inPlace = illumination == nullptr;
-    if (inPlace && !hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom: the HDR image has another extent");
+    if (const int rc = check_in_place_hdr(ctx, "prosper_pt_bloom", inPlace, width, height)) return rc;
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     BloomPassState &st = *ctx->bloomPasses;
-    const size_t pixels = (size_t)width * height;
     p.threshold = pc->threshold;
     for (uint32_t k = 0; k < 3u; ++k) p.blendFactors[k] = pc->blendFactors[k];
     p.biquadratic = pc->biquadratic;
 
     st.valid = false;
-    int rc = PROSPER_PT_OK;
-    if (!inPlace && !onDevice) rc = grow_to(st.hostInput, pixels * 16u, s);
-    if (rc == PROSPER_PT_OK) rc = grow_to(st.highlights, texels * 8u, s);
+    int rc = grow_to(st.highlights, texels * 8u, s);
     if (rc == PROSPER_PT_OK) rc = grow_to(st.horizontal, texels * 8u, s);
     if (rc == PROSPER_PT_OK) rc = grow_to(st.blurred, texels * 8u, s);
     if (rc == PROSPER_PT_OK) rc = ensure_streak_weights(st, p.streakHalfWidth, s);
@@ -250,20 +232,9 @@ int prosper_pt_bloom(
     if ((rc = st.timing.create())) return rc;
 
     BloomBuffers b = {};
-    if (!inPlace)
-    {
-        b.illumination = static_cast<const float4 *>(illumination);
-        if (!onDevice)
-        {
-            PPT_HIP(hipMemcpyAsync(st.hostInput.ptr, illumination, pixels * 16u, hipMemcpyHostToDevice, s));
-            b.illumination = st.hostInput.as<float4>();
-        }
-        // (an explicit illumination that is the HDR image itself behaves as in place)
-        rc = prepare_hdr(ctx, width, height, nullptr, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    else
-        b.illumination = ctx->hdr;
+    // (an explicit illumination that is the HDR image itself behaves as in place)
+    rc = resolve_illumination(ctx, illumination, inPlace, onDevice != 0u, st.hostInput, width, height, s, &b.illumination);
+    if (rc != PROSPER_PT_OK) return rc;
     b.out = ctx->hdr;
     b.highlights = st.highlights.as<uint2>();
     b.horizontal = st.horizontal.as<uint2>();
@@ -288,11 +259,7 @@ int prosper_pt_read_bloom_stage(prosper_pt_ctx *ctx, uint32_t stage, uint32_t le
     const DeviceBuffer &image = stage == PROSPER_PT_BLOOM_HIGHLIGHTS ? st.highlights : (stage == PROSPER_PT_BLOOM_HORIZONTAL ? st.horizontal : st.blurred);
     const size_t bytes = (size_t)p.levelW[level] * p.levelH[level] * 8u;
     if (byte_size != bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_bloom_stage: byte_size differs from the level's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host, image.as<uint8_t>() + (size_t)p.levelOffset[level] * 8u, bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host, image.as<uint8_t>() + (size_t)p.levelOffset[level] * 8u, bytes}});
 }
 
 int prosper_pt_get_bloom_info(prosper_pt_ctx *ctx, prosper_pt_bloom_info *out)
@@ -338,19 +305,16 @@ int prosper_pt_bloom_fft(
     if (const int rc = check_bloom_fft_arguments(pc, width, height, plan)) return rc;
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: null argument");
     const bool inPlace = illumination == nullptr;
-    if (inPlace && !hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_bloom_fft: the HDR image has another extent");
+    if (const int rc = check_in_place_hdr(ctx, "prosper_pt_bloom_fft", inPlace, width, height)) return rc;
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     BloomFftState &st = ctx->bloomPasses->fft;
-    const size_t pixels = (size_t)width * height, texels = (size_t)plan.dim * plan.dim;
+    const size_t texels = (size_t)plan.dim * plan.dim;
     const bool remake = pc->regenerateKernel != 0u || st.keptKernelDim != plan.kernelDim || st.keptDim != plan.dim;
 
     st.valid = false;
-    int rc = PROSPER_PT_OK;
     const float2 *twiddles = nullptr;
-    if (!inPlace && !onDevice) rc = grow_to(ctx->bloomPasses->hostInput, pixels * 16u, s);
-    if (rc == PROSPER_PT_OK) rc = grow_to(st.highlights, texels * 8u, s);
+    int rc = grow_to(st.highlights, texels * 8u, s);
     if (rc == PROSPER_PT_OK) rc = grow_to(st.convolved, texels * 16u, s);
     if (rc == PROSPER_PT_OK && remake)
     {
@@ -362,19 +326,10 @@ int prosper_pt_bloom_fft(
     if (rc != PROSPER_PT_OK) return rc;
     if ((rc = st.timing.create())) return rc;
 
-    const float4 *input = ctx->hdr;
-    if (!inPlace)
-    {
-        input = static_cast<const float4 *>(illumination);
-        if (!onDevice)
-        {
-            PPT_HIP(hipMemcpyAsync(ctx->bloomPasses->hostInput.ptr, illumination, pixels * 16u, hipMemcpyHostToDevice, s));
-            input = ctx->bloomPasses->hostInput.as<float4>();
-        }
-        // (an explicit illumination that is the HDR image itself behaves as in place)
-        rc = prepare_hdr(ctx, width, height, nullptr, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
+    const float4 *input = nullptr;
+    // (an explicit illumination that is the HDR image itself behaves as in place)
+    rc = resolve_illumination(ctx, illumination, inPlace, onDevice != 0u, ctx->bloomPasses->hostInput, width, height, s, &input);
+    if (rc != PROSPER_PT_OK) return rc;
     hipEvent_t *events = st.timing.events;
     uint32_t e = 0;
     auto mark = [&]() { (void)hipEventRecord(events[e++], s); };
@@ -464,11 +419,7 @@ int prosper_pt_read_bloom_fft_stage(prosper_pt_ctx *ctx, uint32_t stage, void *h
     if (stage == PROSPER_PT_BLOOM_FFT_KERNEL_DFT) image = &st.kernelDft, bytes = texels * 16u;
     if (stage == PROSPER_PT_BLOOM_FFT_CONVOLVED) image = &st.convolved, bytes = texels * 16u;
     if (byte_size != bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_bloom_fft_stage: byte_size differs from the image's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host, image->ptr, bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host, image->ptr, bytes}});
 }
 
 int prosper_pt_get_bloom_fft_info(prosper_pt_ctx *ctx, prosper_pt_bloom_fft_info *out)

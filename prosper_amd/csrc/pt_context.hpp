@@ -55,57 +55,22 @@ enum class GrowWait
 // left empty (nullptr, 0).
 int grow_buffer(DeviceBuffer &buf, GrowWait wait, hipStream_t s, size_t bytes, size_t allocBytes, int fill = -1);
 
-// State of the passes over a G-buffer (pt_gbuffer_passes.cpp): their buffers and what the last call of each produced.
-// Made by prosper_pt_create (false: out of host memory), freed by prosper_pt_destroy.
-struct GBufferPassState;
-bool create_gbuffer_passes(prosper_pt_ctx *ctx);
-void destroy_gbuffer_passes(prosper_pt_ctx *ctx);
-// a new scene: the image-based lighting maps describe the old sky
-void forget_ibl_maps(prosper_pt_ctx *ctx);
-// State of ForwardRenderer's passes (pt_forward_passes.cpp): their buffers and what the last call of each produced.  Made
-// and freed like the G-buffer passes' state.
-struct ForwardPassState;
-bool create_forward_passes(prosper_pt_ctx *ctx);
-void destroy_forward_passes(prosper_pt_ctx *ctx);
-// State of the skybox fill and of depth of field (pt_dof_passes.cpp): the intermediates of the last call.  Made and
-// freed like the G-buffer passes' state.
-struct DofPassState;
-bool create_dof_passes(prosper_pt_ctx *ctx);
-void destroy_dof_passes(prosper_pt_ctx *ctx);
-// State of bloom (pt_bloom_passes.cpp): the working images of the last call.  Made and freed like the others.
-struct BloomPassState;
-bool create_bloom_passes(prosper_pt_ctx *ctx);
-void destroy_bloom_passes(prosper_pt_ctx *ctx);
-// State of the temporal anti-aliasing resolve (pt_taa_passes.cpp): the two history images.  Made and freed like the others.
-struct TaaPassState;
-bool create_taa_passes(prosper_pt_ctx *ctx);
-void destroy_taa_passes(prosper_pt_ctx *ctx);
+// The state of a pass module (pt_*_passes.cpp, pt_materials.cpp's texture compression): its buffers and what the last
+// call of each of its passes produced, defined in the module's own file.  Made by prosper_pt_create, freed by
+// prosper_pt_destroy.
+struct GBufferPassState;     // ReSTIR-DI, traced G-buffer, clustering, deferred shading, IBL; the context's last frame
+struct ForwardPassState;     // ForwardRenderer's passes
+struct DofPassState;         // the skybox fill and depth of field: the intermediates of the last call
+struct BloomPassState;       // the working images of the last call, of both techniques
+struct TaaPassState;         // the two history images
+struct ParticlesPassState;   // the pool, its freelist and the render's per-pixel keys, which live across frames and scenes
+struct DebugPassState;       // the debug lines' copy, their per-pixel keys and statistics
+struct CullingPassState;     // the two depth pyramids, the draw lists with their argument triples and statistics
+struct RasterPassState;      // the visibility image, the large pass's queue, the counts of the last draws
+struct CompressPassState;    // prosper_pt_compress_texture (pt_materials.cpp)
+struct MeshPreparePassState; // prosper_pt_prepare_mesh (pt_mesh_passes.cpp)
 // a new scene, or TemporalAntiAliasing::releasePreserved: the next resolve ignores the history
 void forget_taa_history(prosper_pt_ctx *ctx);
-// State of the particle system (pt_particles_passes.cpp): the pool, its freelist and the render's per-pixel keys, which
-// live across frames and scenes.  Made and freed like the others.
-struct ParticlesPassState;
-bool create_particles_passes(prosper_pt_ctx *ctx);
-void destroy_particles_passes(prosper_pt_ctx *ctx);
-// State of the inspection passes (pt_debug_passes.cpp): the debug lines' copy, their per-pixel keys and statistics.  Made
-// and freed like the others.
-struct DebugPassState;
-bool create_debug_passes(prosper_pt_ctx *ctx);
-void destroy_debug_passes(prosper_pt_ctx *ctx);
-// State of the visibility system (pt_culling_passes.cpp): the two depth pyramids, the draw lists of the last culling
-// calls with their argument triples and statistics.  Made and freed like the others.
-struct CullingPassState;
-bool create_culling_passes(prosper_pt_ctx *ctx);
-void destroy_culling_passes(prosper_pt_ctx *ctx);
-// a new scene: both pyramids and the draw lists describe the old one
-void forget_hiz(prosper_pt_ctx *ctx);
-// State of the rasteriser over the draw lists (pt_raster_passes.cpp): the visibility image, the large pass's queue, the
-// counts of the last draws.  Made and freed like the others.
-struct RasterPassState;
-bool create_raster_passes(prosper_pt_ctx *ctx);
-void destroy_raster_passes(prosper_pt_ctx *ctx);
-// a new scene: the visibility image and the ordinal tables describe the old one
-void forget_raster(prosper_pt_ctx *ctx);
 struct AccelState;
 // the scales of the table `transforms` into acc->dScalesV[v] (allocated at first need), enqueued on `stream`
 int enqueue_instance_scales(prosper_pt_ctx *ctx, AccelState *acc, uint32_t v, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t stream);
@@ -127,10 +92,21 @@ struct DebugImage
         level[0] = p, levelW[0] = w, levelH[0] = h;
     }
 };
-void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out); // G-buffer, velocity, IBL LUT
-void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);
-void list_bloom_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);   // both techniques
-void list_taa_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out);
+// What the context asks of a pass module.  Each module defines one (pass_module, pt_pass_support.hpp).
+struct PassModule
+{
+    bool (*create)(prosper_pt_ctx *);       // false: out of host memory
+    void (*destroy)(prosper_pt_ctx *);
+    void (*forget_scene)(prosper_pt_ctx *); // prosper_pt_upload_scene; nullptr: nothing of it describes a scene
+    void (*list_debug_images)(const prosper_pt_ctx *, std::vector<DebugImage> &); // nullptr: it owns no listed image
+};
+extern const PassModule kGBufferPasses, kForwardPasses, kDofPasses, kBloomPasses, kTaaPasses, kParticlesPasses, kDebugPasses,
+    kCullingPasses, kRasterPasses, kCompressPasses, kMeshPreparePasses;
+// Every module, in the order they are made.  The registry of debug images lists theirs in this order too, which is part
+// of the interface: the G-buffer module's, dof's, bloom's, taa's.
+inline const PassModule *const kPassModules[] = {&kGBufferPasses, &kForwardPasses,   &kDofPasses,         &kBloomPasses,
+                                                 &kTaaPasses,     &kParticlesPasses, &kDebugPasses,       &kCullingPasses,
+                                                 &kRasterPasses,  &kCompressPasses,  &kMeshPreparePasses};
 // State of the keyframe animation (pt_animation.hip, pt_animation.hpp): the node and channel tables of the scene, the
 // staged time and the read-back that feeds the host mirrors below.  Made and freed like the others.
 struct AnimationState;
@@ -372,25 +348,13 @@ struct prosper_pt_ctx
     ppt::DebugPassState *debugPasses = nullptr;
     ppt::CullingPassState *cullingPasses = nullptr; // the depth pyramids, the draw lists, DrawStats
     ppt::RasterPassState *rasterPasses = nullptr;   // the visibility image drawn from the lists
+    ppt::CompressPassState *compressPasses = nullptr;       // prosper_pt_compress_texture, prosper_pt_debug_bc7_encode_blocks
+    ppt::MeshPreparePassState *meshPreparePasses = nullptr; // prosper_pt_prepare_mesh
     ppt::AnimationState *animation = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy
     uint32_t toneKeptWidth = 0, toneKeptHeight = 0; // of the image the last tone map left in toneScratch (0: it went to the caller's buffer)
-    // prosper_pt_compress_texture / prosper_pt_debug_bc7_encode_blocks (pt_materials.cpp): the source as the caller holds it,
-    // its levels in the DeviceTexture tiling, the payload on its way back
-    ppt::DeviceBuffer compressSource, compressTiled, compressPayload;
-    ppt::StageEvents<3> compressEvents; // around the last compression's stages: prepare, encode, read back
-    bool compressTimed = false;
-    // prosper_pt_prepare_mesh (pt_mesh_passes.cpp): the source streams as the caller holds them, the six fixed-point
-    // tangent sums of every vertex, the float32 tangents and the blob on the device; on the host the sections the
-    // partition fills, and what the last call left for the read-backs
-    ppt::DeviceBuffer prepareSource, prepareSums, prepareTangents, prepareBlob;
-    ppt::StageEvents<4> prepareEvents; // around the last call's stages: tangents, pack, bounds, read back
-    std::vector<uint32_t> prepareImage, preparedBlob;
-    std::vector<float> preparedTangents;
-    float prepareMeshletHostMs = 0.0f;
-    bool prepared = false, preparedTangentsValid = false, prepareTimed = false;
 
     // Everything a render has in flight between its first launch and its accumulate kernel: the wavefront
     // workspace, the stack-overflow array and the launch chains (pt_kernels.hpp WavefrontChains) with their

@@ -6,14 +6,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "pt_context.hpp"
 #include "pt_culling.hpp"
 #include "pt_culling_state.hpp"
-#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 
 using namespace ppt;
@@ -21,19 +19,8 @@ using namespace ppt;
 namespace ppt
 {
 
-bool create_culling_passes(prosper_pt_ctx *ctx)
-{
-    ctx->cullingPasses = new (std::nothrow) CullingPassState();
-    return ctx->cullingPasses != nullptr;
-}
-
-void destroy_culling_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->cullingPasses;
-    ctx->cullingPasses = nullptr;
-}
-
-void forget_hiz(prosper_pt_ctx *ctx)
+// a new scene: both pyramids and the draw lists describe the old one
+static void forget_hiz(prosper_pt_ctx *ctx)
 {
     if (!ctx->cullingPasses) return;
     CullingPassState &st = *ctx->cullingPasses;
@@ -44,6 +31,8 @@ void forget_hiz(prosper_pt_ctx *ctx)
     st.checked = false;
     st.firstTimed = st.secondTimed = false;
 }
+
+extern const PassModule kCullingPasses = pass_module<CullingPassState, &prosper_pt_ctx::cullingPasses>(forget_hiz);
 
 int enqueue_instance_scales(
     prosper_pt_ctx *ctx, AccelState *acc, uint32_t v, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t stream)
@@ -318,17 +307,8 @@ int prosper_pt_hiz_downsample(
     if (!hiz_layout(width, height, &layout))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_hiz_downsample: width and height are above 1 and at most 4096");
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_hiz_downsample: null argument");
-    const float *depth = nonLinearDepth;
-    if (!depth)
-    {
-        const float *last = nullptr;
-        uint32_t gw = 0, gh = 0;
-        const int grc = gbuffer_last_depth(ctx, &last, &gw, &gh);
-        if (grc != PROSPER_PT_OK) return grc;
-        if (gw != width || gh != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_hiz_downsample: the last traced G-buffer has another extent");
-        depth = last;
-    }
+    const float *depth = nullptr;
+    if (const int drc = resolve_depth(ctx, "prosper_pt_hiz_downsample", nonLinearDepth, onDevice != 0u, width, height, &depth)) return drc;
     CullingPassState::HizSlot &st = ctx->cullingPasses->hiz[slot];
     st.valid = false;
     PPT_HIP(hipSetDevice(ctx->device));
@@ -338,13 +318,7 @@ int prosper_pt_hiz_downsample(
     int rc = st.done.wait(s);
     if (rc != PROSPER_PT_OK) return rc;
     if ((rc = grow_to(st.pyramid, layout.floats * sizeof(float), s)) != PROSPER_PT_OK) return rc;
-    if (nonLinearDepth && !onDevice)
-    {
-        const size_t bytes = (size_t)width * height * sizeof(float);
-        if ((rc = grow_to(st.hostDepth, bytes, s)) != PROSPER_PT_OK) return rc;
-        PPT_HIP(hipMemcpyAsync(st.hostDepth.ptr, nonLinearDepth, bytes, hipMemcpyHostToDevice, s));
-        depth = st.hostDepth.as<float>();
-    }
+    if ((rc = stage_depth(st.hostDepth, 0, nonLinearDepth, (size_t)width * height, s, &depth)) != PROSPER_PT_OK) return rc;
     launch_hiz_downsample(depth, width, height, st.pyramid.as<float>(), layout, s);
     PPT_HIP(hipGetLastError());
     if ((rc = st.done.record(s)) != PROSPER_PT_OK) return rc;
@@ -403,12 +377,7 @@ int prosper_pt_read_hiz_level(prosper_pt_ctx *ctx, uint32_t slot, uint32_t level
     if (const int rc = hiz_level(ctx, "prosper_pt_read_hiz_level", slot, level, &st)) return rc;
     const size_t need = (size_t)st->layout.levelW[level] * st->layout.levelH[level] * sizeof(float);
     if (bytes < need) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_hiz_level: destination too small");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = st->done.wait(s)) return rc;
-    PPT_HIP(hipMemcpyAsync(host, st->pyramid.as<float>() + st->layout.levelOffset[level], need, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host, st->pyramid.as<float>() + st->layout.levelOffset[level], need}}, &st->done);
 }
 
 int prosper_pt_cull_meshlets_first_phase(

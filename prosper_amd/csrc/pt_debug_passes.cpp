@@ -1,6 +1,6 @@
 // pt_debug_passes.cpp — C-ABI of prosper's inspection passes (include/prosper_pt/prosper_pt.h): prosper_pt_debug_lines
 // over the context's HDR image and the last traced G-buffer's depth, the registry of the context's 2-D images (every pass
-// module lists its own: list_*_debug_images) the one-texel readback and the texture viewer over an entry.  Kernels:
+// module lists its own: PassModule::list_debug_images), the one-texel readback and the texture viewer over an entry.  Kernels:
 // pt_debug_view.hip.
 #include "../../include/prosper_pt/prosper_pt.h"
 
@@ -8,7 +8,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "pt_context.hpp"
@@ -44,37 +43,14 @@ struct DebugPassState
     bool peekRecorded = false;
 };
 
-bool create_debug_passes(prosper_pt_ctx *ctx)
-{
-    ctx->debugPasses = new (std::nothrow) DebugPassState();
-    return ctx->debugPasses != nullptr;
-}
-
-void destroy_debug_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->debugPasses;
-    ctx->debugPasses = nullptr;
-}
+extern const PassModule kDebugPasses = pass_module<DebugPassState, &prosper_pt_ctx::debugPasses>();
 
 } // namespace ppt
 
 namespace
 {
 
-constexpr uint32_t kMaxExtent = 32768; // a texel index fits 32 bits
-
-bool is_device_pointer(const void *p)
-{
-    hipPointerAttribute_t a = {};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
-// The registry: the illumination, then every module's images, each in its fixed order
+// The registry: the illumination, then every module's images in the modules' order (kPassModules), each in its fixed order
 std::vector<DebugImage> debug_images(const prosper_pt_ctx *ctx)
 {
     std::vector<DebugImage> images;
@@ -84,10 +60,8 @@ std::vector<DebugImage> debug_images(const prosper_pt_ctx *ctx)
     hdr.valid = ctx->hdr && ctx->localWidth != 0u && ctx->height != 0u;
     if (hdr.valid) hdr.one_level(ctx->hdr, ctx->localWidth, ctx->height);
     images.push_back(hdr);
-    list_gbuffer_debug_images(ctx, images);
-    list_dof_debug_images(ctx, images);
-    list_bloom_debug_images(ctx, images);
-    list_taa_debug_images(ctx, images);
+    for (const PassModule *m : kPassModules)
+        if (m->list_debug_images) m->list_debug_images(ctx, images);
     DebugImage tone; // the last tone-mapped image, kept only when the caller asked for a host copy alone
     tone.name = "toneMapped";
     tone.format = PROSPER_PT_DEBUG_FORMAT_RGBA8_UNORM;

@@ -6,12 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <new>
-#include <string>
 
 #include "pt_context.hpp"
 #include "pt_dof.hpp"
-#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 
 using namespace ppt;
@@ -30,19 +27,7 @@ struct DofPassState
     StageEvents<kDofStages> timing;
 };
 
-bool create_dof_passes(prosper_pt_ctx *ctx)
-{
-    ctx->dofPasses = new (std::nothrow) DofPassState();
-    return ctx->dofPasses != nullptr;
-}
-
-void destroy_dof_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->dofPasses;
-    ctx->dofPasses = nullptr;
-}
-
-void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+static void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
 {
     const DofPassState &st = *ctx->dofPasses;
     const DofParams &p = st.last;
@@ -88,40 +73,9 @@ void list_dof_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &o
     }
 }
 
+extern const PassModule kDofPasses = pass_module<DofPassState, &prosper_pt_ctx::dofPasses>(nullptr, list_dof_debug_images);
+
 } // namespace ppt
-
-namespace
-{
-
-// The depth a call reads on the device: the caller's, a copy of the caller's host array (at `hostOffset` of the
-// state's hostInputs, which the caller has grown), or with NULL the last traced G-buffer's, whose extent must match.
-int device_depth(
-    prosper_pt_ctx *ctx, const char *what, const float *depth, bool onDevice, uint32_t width, uint32_t height,
-    size_t hostOffset, hipStream_t s, const float **out)
-{
-    if (!depth)
-    {
-        const float *last = nullptr;
-        uint32_t gw = 0, gh = 0;
-        const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
-        if (rc != PROSPER_PT_OK) return rc;
-        if (gw != width || gh != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the last traced G-buffer has another extent");
-        *out = last;
-        return PROSPER_PT_OK;
-    }
-    if (onDevice)
-    {
-        *out = depth;
-        return PROSPER_PT_OK;
-    }
-    float *dst = reinterpret_cast<float *>(ctx->dofPasses->hostInputs.as<uint8_t>() + hostOffset);
-    PPT_HIP(hipMemcpyAsync(dst, depth, (size_t)width * height * 4u, hipMemcpyHostToDevice, s));
-    *out = dst;
-    return PROSPER_PT_OK;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -143,13 +97,10 @@ int prosper_pt_skybox_fill(
     int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     const size_t pixels = (size_t)width * height;
-    if (nonLinearDepth && !onDevice)
-    {
-        rc = grow_to(ctx->dofPasses->hostInputs, pixels * 20u, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
     const float *depth = nullptr;
-    rc = device_depth(ctx, "prosper_pt_skybox_fill", nonLinearDepth, onDevice != 0u, width, height, pixels * 16u, s, &depth);
+    rc = resolve_depth(ctx, "prosper_pt_skybox_fill", nonLinearDepth, onDevice != 0u, width, height, &depth);
+    // (behind the 16 bytes per pixel of a depth of field's illumination: hostInputs holds both)
+    if (rc == PROSPER_PT_OK) rc = stage_depth(ctx->dofPasses->hostInputs, pixels * 16u, nonLinearDepth, pixels, s, &depth);
     if (rc != PROSPER_PT_OK) return rc;
     RenderParams r = {};
     set_camera_ray_params(r, camera);
@@ -185,8 +136,7 @@ int prosper_pt_depth_of_field(
     if (pc->gatherRadius < 1) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_depth_of_field: gatherRadius must be at least 1");
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_depth_of_field: null argument");
     const bool inPlace = inputs->illumination == nullptr;
-    if (inPlace && !hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_depth_of_field: the HDR image has another extent");
+    if (const int rc = check_in_place_hdr(ctx, "prosper_pt_depth_of_field", inPlace, width, height)) return rc;
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     DofPassState &st = *ctx->dofPasses;
@@ -225,22 +175,12 @@ int prosper_pt_depth_of_field(
     if ((rc = st.timing.create())) return rc;
 
     DofBuffers b = {};
-    rc = device_depth(ctx, "prosper_pt_depth_of_field", inputs->nonLinearDepth, inputs->onDevice != 0u, width, height, pixels * 16u, s, &b.nonLinearDepth);
+    const bool onDevice = inputs->onDevice != 0u;
+    rc = resolve_depth(ctx, "prosper_pt_depth_of_field", inputs->nonLinearDepth, onDevice, width, height, &b.nonLinearDepth);
+    if (rc == PROSPER_PT_OK) rc = stage_depth(st.hostInputs, pixels * 16u, inputs->nonLinearDepth, pixels, s, &b.nonLinearDepth);
+    // (an explicit illumination that is the HDR image itself behaves as in place)
+    if (rc == PROSPER_PT_OK) rc = resolve_illumination(ctx, inputs->illumination, inPlace, onDevice, st.hostInputs, width, height, s, &b.illumination);
     if (rc != PROSPER_PT_OK) return rc;
-    if (!inPlace)
-    {
-        b.illumination = static_cast<const float4 *>(inputs->illumination);
-        if (!inputs->onDevice)
-        {
-            PPT_HIP(hipMemcpyAsync(st.hostInputs.ptr, inputs->illumination, pixels * 16u, hipMemcpyHostToDevice, s));
-            b.illumination = st.hostInputs.as<float4>();
-        }
-        // (an explicit illumination that is the HDR image itself behaves as in place)
-        rc = prepare_hdr(ctx, width, height, nullptr, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    else
-        b.illumination = ctx->hdr;
     b.out = ctx->hdr;
     b.halfIllumination = st.halfIllumination.as<uint2>();
     b.halfCoC = st.halfCoC.as<uint16_t>();
@@ -285,11 +225,7 @@ int prosper_pt_read_dof_stage(prosper_pt_ctx *ctx, uint32_t stage, uint32_t leve
     default: src = st.filtered[1].as<uint8_t>(); bytes = halfTexels * 8u; break;
     }
     if (byte_size != bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_dof_stage: byte_size differs from the stage's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host, src, bytes}});
 }
 
 int prosper_pt_get_dof_info(prosper_pt_ctx *ctx, prosper_pt_dof_info *out)

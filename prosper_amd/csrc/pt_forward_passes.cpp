@@ -59,20 +59,15 @@ struct LayerStore
     void written() { filled = pixels != 0; }
     // `notDebug`: the refusal when the last call left no layers; `done`: what the copies wait for on `s`, if anything
     int read(
-        int device, const char *what, const char *notDebug, const Fence *done, uint32_t *host_counts, prosper_pt_transparent_layer *host_layers,
-        size_t readPixels, uint32_t readLayers, hipStream_t s) const
+        const prosper_pt_ctx *ctx, const char *what, const char *notDebug, const Fence *done, uint32_t *host_counts,
+        prosper_pt_transparent_layer *host_layers, size_t readPixels, uint32_t readLayers, hipStream_t s) const
     {
         if (!filled) return fail(PROSPER_PT_ERR_NO_SCENE, notDebug);
         if (readPixels != pixels || readLayers != layersPerPixel)
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": pixels or layersPerPixel differ from the call's");
-        PPT_HIP(hipSetDevice(device));
-        if (done)
-            if (const int rc = done->wait(s)) return rc;
-        if (host_counts) PPT_HIP(hipMemcpyAsync(host_counts, counts(), pixels * 4u, hipMemcpyDeviceToHost, s));
-        if (host_layers)
-            PPT_HIP(hipMemcpyAsync(host_layers, layers(), pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
-        PPT_HIP(hipStreamSynchronize(s));
-        return PROSPER_PT_OK;
+        return read_back(
+            ctx, s, {{host_counts, counts(), pixels * 4u}, {host_layers, layers(), pixels * layersPerPixel * sizeof(prosper_pt_transparent_layer)}},
+            done);
     }
 };
 
@@ -138,31 +133,11 @@ struct ForwardPassState
     } raster;
 };
 
-bool create_forward_passes(prosper_pt_ctx *ctx)
-{
-    ctx->forwardPasses = new (std::nothrow) ForwardPassState();
-    return ctx->forwardPasses != nullptr;
-}
-
-void destroy_forward_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->forwardPasses;
-    ctx->forwardPasses = nullptr;
-}
+extern const PassModule kForwardPasses = pass_module<ForwardPassState, &prosper_pt_ctx::forwardPasses>();
 
 #pragma GCC visibility pop
 
 } // namespace ppt
-
-// the device depth a transparent pass tests against: `depth` as it is, or the copy of a host depth in `copy`, enqueued on `s`
-static int device_depth(DeviceBuffer &copy, const float *host, size_t pixels, hipStream_t s, const float **depth)
-{
-    if (*depth) return PROSPER_PT_OK;
-    if (const int rc = grow_to(copy, pixels * 4u, s)) return rc;
-    PPT_HIP(hipMemcpyAsync(copy.ptr, host, pixels * 4u, hipMemcpyHostToDevice, s));
-    *depth = copy.as<float>();
-    return PROSPER_PT_OK;
-}
 
 extern "C" {
 
@@ -189,19 +164,13 @@ int prosper_pt_forward_transparent(
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the HDR image has another extent");
     ForwardPassState::Traced &st = ctx->forwardPasses->traced;
     const size_t pixels = (size_t)width * height;
-    const float *depth = onDevice ? nonLinearDepth : nullptr;
-    if (!nonLinearDepth)
-    {
-        uint32_t w = 0, h = 0;
-        if (const int rc = gbuffer_last_depth(ctx, &depth, &w, &h)) return rc;
-        if (w != width || h != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": the last traced G-buffer has another extent");
-    }
+    const float *depth = nullptr;
+    if (const int rc = resolve_depth(ctx, what, nonLinearDepth, onDevice != 0u, width, height, &depth)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = flush_scene_updates(ctx, s, s);
     if (rc != PROSPER_PT_OK) return rc;
     st.ran = false;
-    rc = device_depth(st.depth, nonLinearDepth, pixels, s, &depth);
+    rc = stage_depth(st.depth, 0, nonLinearDepth, pixels, s, &depth);
     if (rc == PROSPER_PT_OK) rc = grow_to(st.stats, 16u, s);
     if (rc == PROSPER_PT_OK) rc = st.layers.prepare(pixels, s);
     if (rc == PROSPER_PT_OK) rc = st.timing.create();
@@ -275,7 +244,7 @@ int prosper_pt_read_transparent_layers(
 {
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_transparent_layers: null argument");
     return ctx->forwardPasses->traced.layers.read(
-        ctx->device, "prosper_pt_read_transparent_layers",
+        ctx, "prosper_pt_read_transparent_layers",
         "the last prosper_pt_forward_transparent did not run in debug mode (prosper_pt_set_transparent_debug_layers)", nullptr, host_counts,
         host_layers, pixels, layersPerPixel, static_cast<hipStream_t>(stream));
 }
@@ -387,12 +356,8 @@ int prosper_pt_read_forward_surfaces(prosper_pt_ctx *ctx, prosper_pt_transparent
         return fail(PROSPER_PT_ERR_NO_SCENE, "the last forward opaque pass did not run in debug mode (prosper_pt_set_forward_debug_surfaces)");
     if (pixels != st.surfacePixels)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_surfaces: pixel count differs from the call's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = st.count.done.wait(s)) return rc;
-    PPT_HIP(hipMemcpyAsync(out, st.surfaces.ptr, pixels * sizeof(prosper_pt_transparent_layer), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(
+        ctx, static_cast<hipStream_t>(stream), {{out, st.surfaces.ptr, pixels * sizeof(prosper_pt_transparent_layer)}}, &st.count.done);
 }
 
 int prosper_pt_get_forward_opaque_info(prosper_pt_ctx *ctx, prosper_pt_forward_opaque_info *out)
@@ -433,12 +398,7 @@ int prosper_pt_read_forward_depth(prosper_pt_ctx *ctx, float *host_depth, size_t
     uint32_t w = 0, h = 0;
     if (const int rc = prosper_pt_get_forward_depth_device_ptr(ctx, &depth, &w, &h)) return rc;
     if (pixels != (size_t)w * h) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_forward_depth: pixel count differs from the depth's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = ctx->forwardPasses->opaque.count.done.wait(s)) return rc;
-    PPT_HIP(hipMemcpyAsync(host_depth, depth, pixels * 4u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host_depth, depth, pixels * 4u}}, &ctx->forwardPasses->opaque.count.done);
 }
 
 // ---- rasterised transparent pass (ForwardRenderer::recordTransparent over the draw lists) ----
@@ -489,7 +449,7 @@ static int raster_transparent(
     if (rc != PROSPER_PT_OK) return rc;
     st.ran = false;
     rc = st.stats.prepare(s); // (first: the last call's resolve may still read the depth copy on another stream)
-    if (rc == PROSPER_PT_OK) rc = device_depth(st.depth, nonLinearDepth, pixels, s, &depth);
+    if (rc == PROSPER_PT_OK) rc = stage_depth(st.depth, 0, nonLinearDepth, pixels, s, &depth);
     if (rc == PROSPER_PT_OK) rc = st.layers.prepare(pixels, s);
     if (rc == PROSPER_PT_OK) rc = st.timing.create();
     if (rc != PROSPER_PT_OK) return rc;
@@ -585,7 +545,7 @@ int prosper_pt_read_raster_transparent_layers(
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_transparent_layers: null argument");
     const ForwardPassState::Raster &st = ctx->forwardPasses->raster;
     return st.layers.read(
-        ctx->device, "prosper_pt_read_raster_transparent_layers",
+        ctx, "prosper_pt_read_raster_transparent_layers",
         "the last rasterised transparent pass did not run in debug mode (prosper_pt_set_raster_transparent_debug_layers)", &st.stats.done,
         host_counts, host_layers, pixels, layersPerPixel, static_cast<hipStream_t>(stream));
 }

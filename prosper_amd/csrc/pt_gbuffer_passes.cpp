@@ -120,19 +120,8 @@ int gbuffer_last_depth(prosper_pt_ctx *ctx, const float **depth, uint32_t *width
     return ctx->gbufferPasses->last.depth(depth, width, height);
 }
 
-bool create_gbuffer_passes(prosper_pt_ctx *ctx)
-{
-    ctx->gbufferPasses = new (std::nothrow) GBufferPassState();
-    return ctx->gbufferPasses != nullptr;
-}
-
-void destroy_gbuffer_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->gbufferPasses;
-    ctx->gbufferPasses = nullptr;
-}
-
-void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+// the G-buffer, the velocity, the IBL LUT
+static void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
 {
     const GBufferPassState &st = *ctx->gbufferPasses;
     const LastFrame &last = st.last;
@@ -172,11 +161,14 @@ void list_gbuffer_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage
     out.push_back(lut);
 }
 
-void forget_ibl_maps(prosper_pt_ctx *ctx)
+// a new scene: the image-based lighting maps describe the old sky
+static void forget_ibl_maps(prosper_pt_ctx *ctx)
 {
     ctx->gbufferPasses->iblGenerated = false;
     ctx->gbufferPasses->clusterValid = false; // the clustering describes the old scene's lights too
 }
+
+extern const PassModule kGBufferPasses = pass_module<GBufferPassState, &prosper_pt_ctx::gbufferPasses>(forget_ibl_maps, list_gbuffer_debug_images);
 
 RestirCamera gbuffer_camera(const prosper_CameraUniforms *camera)
 {
@@ -731,11 +723,7 @@ int prosper_pt_read_velocity(prosper_pt_ctx *ctx, float *host_float2, size_t pix
     if (!st.last.velocity) return fail(PROSPER_PT_ERR_NO_SCENE, "no velocity target has been traced yet");
     if (pixels != (size_t)st.last.velocityWidth * st.last.velocityHeight)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_velocity: pixel count differs from the velocity target's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host_float2, st.last.velocity, pixels * 8u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host_float2, st.last.velocity, pixels * 8u}});
 }
 
 int prosper_pt_get_gbuffer_device_ptrs(prosper_pt_ctx *ctx, prosper_pt_restir_inputs *out, uint32_t *width, uint32_t *height)
@@ -762,16 +750,10 @@ int prosper_pt_read_gbuffer(
     if (!st.last.targets.albedoRoughness) return fail(PROSPER_PT_ERR_NO_SCENE, "no G-buffer has been traced yet");
     if (pixels != (size_t)st.last.width * st.last.height)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_gbuffer: pixel count differs from the G-buffer's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const prosper_pt_gbuffer_targets &t = st.last.targets;
-    if (host_albedo_roughness)
-        PPT_HIP(hipMemcpyAsync(host_albedo_roughness, t.albedoRoughness, pixels * 16u, hipMemcpyDeviceToHost, s));
-    if (host_normal_metallic)
-        PPT_HIP(hipMemcpyAsync(host_normal_metallic, t.normalMetallic, pixels * 16u, hipMemcpyDeviceToHost, s));
-    if (host_depth) PPT_HIP(hipMemcpyAsync(host_depth, t.nonLinearDepth, pixels * 4u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(
+        ctx, static_cast<hipStream_t>(stream),
+        {{host_albedo_roughness, t.albedoRoughness, pixels * 16u}, {host_normal_metallic, t.normalMetallic, pixels * 16u}, {host_depth, t.nonLinearDepth, pixels * 4u}});
 }
 
 int prosper_pt_restir_di_record(
@@ -838,11 +820,7 @@ int prosper_pt_read_restir_reservoirs(prosper_pt_ctx *ctx, float *host_float2, s
     if (!st.lastReservoirs) return fail(PROSPER_PT_ERR_NO_SCENE, "no ReSTIR reservoirs have been produced yet");
     if (byte_size != st.lastReservoirBytes)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_restir_reservoirs: size differs from the reservoirs'");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host_float2, st.lastReservoirs, byte_size, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{host_float2, st.lastReservoirs, byte_size}});
 }
 
 // ---- clustered lighting and deferred shading (src/render/LightClustering.cpp, src/render/DeferredShading.cpp) ----
@@ -885,14 +863,11 @@ int prosper_pt_read_light_clusters(
     if (!st.clusterDims[0]) return fail(PROSPER_PT_ERR_NO_SCENE, "no lights have been clustered yet");
     if (clusters != (size_t)st.clusterDims[0] * st.clusterDims[1] * st.clusterDims[2])
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_light_clusters: cluster count differs from the last clustering's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<uint32_t> ptrs(clusters * 2u), dropped(clusters);
-    PPT_HIP(hipMemcpyAsync(ptrs.data(), st.clusterPointers.ptr, clusters * 8u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipMemcpyAsync(dropped.data(), st.clusterDropped.ptr, clusters * 4u, hipMemcpyDeviceToHost, s));
-    if (host_indices)
-        PPT_HIP(hipMemcpyAsync(host_indices, st.clusterIndices.ptr, clusters * kClusterSlot * 2u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
+    const int rc = read_back(
+        ctx, static_cast<hipStream_t>(stream),
+        {{ptrs.data(), st.clusterPointers.ptr, clusters * 8u}, {dropped.data(), st.clusterDropped.ptr, clusters * 4u}, {host_indices, st.clusterIndices.ptr, clusters * kClusterSlot * 2u}});
+    if (rc != PROSPER_PT_OK) return rc;
     if (host_pointers) std::memcpy(host_pointers, ptrs.data(), clusters * 8u);
     uint32_t count = 0, droppedSum = 0, overflowing = 0;
     for (size_t k = 0; k < clusters; ++k)
@@ -1004,14 +979,13 @@ int prosper_pt_read_ibl(
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_ibl: null argument");
     const GBufferPassState &st = *ctx->gbufferPasses;
     if (!st.iblGenerated) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_ibl: no maps were generated for the current scene (prosper_pt_generate_ibl)");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (a map the caller does not want is an empty vector: zero bytes, no copy)
     std::vector<uint16_t> irr(irradiance_rgba16f ? 4u * kIblIrradianceTexels : 0u);
     std::vector<uint16_t> rad(radiance_rgba16f ? 4u * kIblRadianceTexels : 0u);
-    if (irradiance_rgba16f) PPT_HIP(hipMemcpyAsync(irr.data(), st.iblIrradiance.ptr, irr.size() * 2u, hipMemcpyDeviceToHost, s));
-    if (radiance_rgba16f) PPT_HIP(hipMemcpyAsync(rad.data(), st.iblRadiance.ptr, rad.size() * 2u, hipMemcpyDeviceToHost, s));
-    if (lut_rg16) PPT_HIP(hipMemcpyAsync(lut_rg16, st.iblLut.ptr, lut_bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
+    const int rc = read_back(
+        ctx, static_cast<hipStream_t>(stream),
+        {{irr.data(), st.iblIrradiance.ptr, irr.size() * 2u}, {rad.data(), st.iblRadiance.ptr, rad.size() * 2u}, {lut_rg16, st.iblLut.ptr, lut_bytes}});
+    if (rc != PROSPER_PT_OK) return rc;
     if (irradiance_rgba16f) strip_cube_borders(irr, kIblIrradianceSize, 1u, irradiance_rgba16f);
     if (radiance_rgba16f) strip_cube_borders(rad, kIblRadianceSize, kIblRadianceMips, radiance_rgba16f);
     return PROSPER_PT_OK;
@@ -1043,11 +1017,7 @@ int prosper_pt_read_texture_lod_derivatives(prosper_pt_ctx *ctx, float *out, siz
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: the last traced G-buffer wrote no derivatives (prosper_pt_set_texture_lod, prosper_pt_set_texture_lod_debug)");
     if (bytes != (size_t)st.last.derivativesWidth * st.last.derivativesHeight * sizeof(float4))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_texture_lod_derivatives: size mismatch");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(out, st.lodDerivatives.ptr, bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{out, st.lodDerivatives.ptr, bytes}});
 }
 
 } // extern "C"

@@ -459,6 +459,17 @@ int flush_pending_materials(prosper_pt_ctx *ctx, hipStream_t stream)
     return PROSPER_PT_OK;
 }
 
+// prosper_pt_compress_texture / prosper_pt_debug_bc7_encode_blocks: the source as the caller holds it, its levels in the
+// DeviceTexture tiling, the payload on its way back
+struct CompressPassState
+{
+    DeviceBuffer source, tiled, payload;
+    StageEvents<3> events; // around the last compression's stages: prepare, encode, read back
+    bool timed = false;
+};
+
+extern const PassModule kCompressPasses = pass_module<CompressPassState, &prosper_pt_ctx::compressPasses>();
+
 } // namespace ppt
 
 using namespace ppt;
@@ -764,40 +775,41 @@ int prosper_pt_compress_texture(
 
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    CompressPassState &st = *ctx->compressPasses;
     int rc;
-    if ((rc = grow_to(ctx->compressSource, sourceBytes, s))) return rc;
-    if ((rc = grow_to(ctx->compressTiled, tiledWords * 4u, s))) return rc;
-    if ((rc = grow_to(ctx->compressPayload, (size_t)layout.bytes, s))) return rc;
-    if ((rc = ctx->compressEvents.create())) return rc;
-    ctx->compressTimed = false;
+    if ((rc = grow_to(st.source, sourceBytes, s))) return rc;
+    if ((rc = grow_to(st.tiled, tiledWords * 4u, s))) return rc;
+    if ((rc = grow_to(st.payload, (size_t)layout.bytes, s))) return rc;
+    if ((rc = st.events.create())) return rc;
+    st.timed = false;
     // stages between the events: source up + tiling + mip generation, encoding, payload back
     const bool srgb = (flags & PROSPER_PT_COMPRESS_SRGB) != 0;
     const auto enqueue = [&]() -> hipError_t {
         hipError_t e;
-        if ((e = hipEventRecord(ctx->compressEvents.events[0], s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(ctx->compressSource.ptr, src->texels, sourceBytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(ctx->compressTiled.ptr, 0, tiledWords * 4u, s)) != hipSuccess) return e; // (tile padding)
+        if ((e = hipEventRecord(st.events.events[0], s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(st.source.ptr, src->texels, sourceBytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(st.tiled.ptr, 0, tiledWords * 4u, s)) != hipSuccess) return e; // (tile padding)
         size_t sourceOffset = 0, payloadOffset = 0;
         for (uint32_t l = 0; l < levels; ++l)
         {
             const uint32_t w = std::max(w0 >> l, 1u), h = std::max(h0 >> l, 1u);
-            uint32_t *level = ctx->compressTiled.as<uint32_t>() + tiledOffset[l];
+            uint32_t *level = st.tiled.as<uint32_t>() + tiledOffset[l];
             if (l < supplied)
             {
-                launch_retile_rgba8(ctx->compressSource.as<uint8_t>() + sourceOffset, w, h, (w + kTexTileW - 1u) / kTexTileW, level, s);
+                launch_retile_rgba8(st.source.as<uint8_t>() + sourceOffset, w, h, (w + kTexTileW - 1u) / kTexTileW, level, s);
                 sourceOffset += (size_t)w * h * 4u;
             }
             else
                 launch_generate_mip(
-                    ctx->compressTiled.as<uint32_t>() + tiledOffset[l - 1u], std::max(w0 >> (l - 1u), 1u), std::max(h0 >> (l - 1u), 1u), level, w, h, srgb, s);
+                    st.tiled.as<uint32_t>() + tiledOffset[l - 1u], std::max(w0 >> (l - 1u), 1u), std::max(h0 >> (l - 1u), 1u), level, w, h, srgb, s);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ctx->compressEvents.events[1], s)) != hipSuccess) return e;
+        if ((e = hipEventRecord(st.events.events[1], s)) != hipSuccess) return e;
         for (uint32_t l = 0; l < levels; ++l)
         {
             const uint32_t w = std::max(w0 >> l, 1u), h = std::max(h0 >> l, 1u);
-            const uint32_t *level = ctx->compressTiled.as<uint32_t>() + tiledOffset[l];
-            uint8_t *out = ctx->compressPayload.as<uint8_t>() + payloadOffset;
+            const uint32_t *level = st.tiled.as<uint32_t>() + tiledOffset[l];
+            uint8_t *out = st.payload.as<uint8_t>() + payloadOffset;
             if (layout.format == PROSPER_PT_FORMAT_BC7_UNORM)
             {
                 launch_bc7_encode_level(level, w, h, 0u, out, s);
@@ -811,26 +823,27 @@ int prosper_pt_compress_texture(
             }
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ctx->compressEvents.events[2], s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(dst, ctx->compressPayload.ptr, (size_t)layout.bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        return hipEventRecord(ctx->compressEvents.events[3], s);
+        if ((e = hipEventRecord(st.events.events[2], s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dst, st.payload.ptr, (size_t)layout.bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        return hipEventRecord(st.events.events[3], s);
     };
     // (whatever was enqueued is waited for, also after a failure: `src` and `dst` are borrowed for the call only)
     const hipError_t e = enqueue();
     const hipError_t f = hipStreamSynchronize(s);
     PPT_HIP(e);
     PPT_HIP(f);
-    ctx->compressTimed = true;
+    st.timed = true;
     return PROSPER_PT_OK;
 }
 
 int prosper_pt_get_compress_texture_timing(prosper_pt_ctx *ctx, float *prepareMs, float *encodeMs, float *readbackMs)
 {
     if (!ctx || !prepareMs || !encodeMs || !readbackMs) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_compress_texture_timing: null argument");
-    if (!ctx->compressTimed) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_compress_texture_timing: no prosper_pt_compress_texture has completed");
+    const CompressPassState &st = *ctx->compressPasses;
+    if (!st.timed) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_compress_texture_timing: no prosper_pt_compress_texture has completed");
     PPT_HIP(hipSetDevice(ctx->device));
     float ms[3];
-    const int rc = ctx->compressEvents.elapsed(ms);
+    const int rc = st.events.elapsed(ms);
     if (rc != PROSPER_PT_OK) return rc;
     *prepareMs = ms[0];
     *encodeMs = ms[1];
@@ -847,13 +860,14 @@ int prosper_pt_debug_bc7_encode_blocks(
     if (n > (1u << 26)) return fail(PROSPER_PT_ERR_UNSUPPORTED, "prosper_pt_debug_bc7_encode_blocks: more than 2^26 blocks");
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    CompressPassState &st = *ctx->compressPasses;
     int rc;
     // blocks and errors side by side: 16 + 4 bytes per block
-    if ((rc = grow_to(ctx->compressSource, (size_t)n * 64u, s))) return rc;
-    if ((rc = grow_to(ctx->compressPayload, (size_t)n * 20u, s))) return rc;
-    uint32_t *dBlocks = ctx->compressPayload.as<uint32_t>(), *dSse = dBlocks + (size_t)n * 4u;
-    PPT_HIP(hipMemcpyAsync(ctx->compressSource.ptr, texels, (size_t)n * 64u, hipMemcpyHostToDevice, s));
-    launch_bc7_encode_blocks(ctx->compressSource.as<uint32_t>(), n, modeMask, dBlocks, dSse, s);
+    if ((rc = grow_to(st.source, (size_t)n * 64u, s))) return rc;
+    if ((rc = grow_to(st.payload, (size_t)n * 20u, s))) return rc;
+    uint32_t *dBlocks = st.payload.as<uint32_t>(), *dSse = dBlocks + (size_t)n * 4u;
+    PPT_HIP(hipMemcpyAsync(st.source.ptr, texels, (size_t)n * 64u, hipMemcpyHostToDevice, s));
+    launch_bc7_encode_blocks(st.source.as<uint32_t>(), n, modeMask, dBlocks, dSse, s);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(blocks, dBlocks, (size_t)n * 16u, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(sse, dSse, (size_t)n * 4u, hipMemcpyDeviceToHost, s);

@@ -13,6 +13,26 @@
 
 using namespace ppt;
 
+namespace ppt
+{
+
+// prosper_pt_prepare_mesh: on the device the source streams as the caller holds them, the six fixed-point tangent sums of
+// every vertex, the float32 tangents and the blob; on the host the sections the partition fills, and what the last call
+// left for the read-backs
+struct MeshPreparePassState
+{
+    DeviceBuffer source, sums, tangents, blob;
+    StageEvents<4> events; // around the last call's stages: tangents, pack, bounds, read back
+    std::vector<uint32_t> image, hostBlob;
+    std::vector<float> hostTangents;
+    float meshletHostMs = 0.0f;
+    bool prepared = false, tangentsValid = false, timed = false;
+};
+
+extern const PassModule kMeshPreparePasses = pass_module<MeshPreparePassState, &prosper_pt_ctx::meshPreparePasses>();
+
+} // namespace ppt
+
 namespace
 {
 
@@ -113,19 +133,20 @@ int prosper_pt_prepare_mesh(
 
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    MeshPreparePassState &st = *ctx->meshPreparePasses;
     int rc;
-    if ((rc = grow_to(ctx->prepareSource, sourceBytes, s))) return rc;
-    if ((rc = grow_to(ctx->prepareBlob, (size_t)words * 4u, s))) return rc;
+    if ((rc = grow_to(st.source, sourceBytes, s))) return rc;
+    if ((rc = grow_to(st.blob, (size_t)words * 4u, s))) return rc;
     if (generate)
     {
-        if ((rc = grow_to(ctx->prepareSums, 48ull * n, s))) return rc;
-        if ((rc = grow_to(ctx->prepareTangents, 16ull * n, s))) return rc;
+        if ((rc = grow_to(st.sums, 48ull * n, s))) return rc;
+        if ((rc = grow_to(st.tangents, 16ull * n, s))) return rc;
     }
-    if ((rc = ctx->prepareEvents.create())) return rc;
+    if ((rc = st.events.create())) return rc;
 
     // what the host writes of the blob: the indices in front, the partition behind the vertex streams (the bounds' words
     // are the kernel's)
-    std::vector<uint32_t> &image = ctx->prepareImage;
+    std::vector<uint32_t> &image = st.image;
     image.assign((size_t)(indexWords + (words - meshletWords)), 0u);
     write_indices(image.data(), src->indices, indexCount, isShort);
     uint32_t *tail = image.data() + indexWords;
@@ -136,16 +157,16 @@ int prosper_pt_prepare_mesh(
         std::memcpy(tail + (trianglesByteOffset / 4u - meshletWords), part.triangles.data(), part.triangles.size());
     }
 
-    ctx->prepared = false;
-    ctx->prepareTimed = false;
-    if (generate) ctx->preparedTangentsValid = false;
-    ctx->preparedBlob.resize((size_t)words);
-    if (generate) ctx->preparedTangents.resize(4ull * n);
-    uint8_t *dSource = ctx->prepareSource.as<uint8_t>();
-    uint32_t *dBlob = ctx->prepareBlob.as<uint32_t>();
+    st.prepared = false;
+    st.timed = false;
+    if (generate) st.tangentsValid = false;
+    st.hostBlob.resize((size_t)words);
+    if (generate) st.hostTangents.resize(4ull * n);
+    uint8_t *dSource = st.source.as<uint8_t>();
+    uint32_t *dBlob = st.blob.as<uint32_t>();
     const auto enqueue = [&]() -> hipError_t {
         hipError_t e;
-        if ((e = hipEventRecord(ctx->prepareEvents.events[0], s)) != hipSuccess) return e;
+        if ((e = hipEventRecord(st.events.events[0], s)) != hipSuccess) return e;
         if ((e = hipMemcpyAsync(dSource + positionsAt, src->positions, 12ull * n, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
         if (src->normals && (e = hipMemcpyAsync(dSource + normalsAt, src->normals, 12ull * n, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
         if (src->tangents && (e = hipMemcpyAsync(dSource + tangentsAt, src->tangents, 16ull * n, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
@@ -153,20 +174,20 @@ int prosper_pt_prepare_mesh(
         if (generate)
         {
             if (indexCount && (e = hipMemcpyAsync(dSource + indicesAt, src->indices, 4ull * indexCount, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctx->prepareSums.ptr, 0, 48ull * n, s)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(st.sums.ptr, 0, 48ull * n, s)) != hipSuccess) return e;
             launch_tangent_sums(
                 reinterpret_cast<const float *>(dSource + positionsAt), reinterpret_cast<const float *>(dSource + uvsAt),
-                reinterpret_cast<const uint32_t *>(dSource + indicesAt), indexCount / 3u, ctx->prepareSums.as<long long>(), s);
+                reinterpret_cast<const uint32_t *>(dSource + indicesAt), indexCount / 3u, st.sums.as<long long>(), s);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        if ((e = hipEventRecord(ctx->prepareEvents.events[1], s)) != hipSuccess) return e;
+        if ((e = hipEventRecord(st.events.events[1], s)) != hipSuccess) return e;
         PackMeshArgs pack = {};
         pack.positions = reinterpret_cast<const float *>(dSource + positionsAt);
         pack.normals = src->normals ? reinterpret_cast<const float *>(dSource + normalsAt) : nullptr;
         pack.tangents = src->tangents ? reinterpret_cast<const float *>(dSource + tangentsAt) : nullptr;
         pack.uvs = src->texCoord0s ? reinterpret_cast<const float *>(dSource + uvsAt) : nullptr;
-        pack.sums = generate ? ctx->prepareSums.as<long long>() : nullptr;
-        pack.tangentsOut = generate ? ctx->prepareTangents.as<float>() : nullptr;
+        pack.sums = generate ? st.sums.as<long long>() : nullptr;
+        pack.tangentsOut = generate ? st.tangents.as<float>() : nullptr;
         pack.blob = dBlob;
         pack.vertexCount = n;
         pack.positionsOffset = h.positionsOffset;
@@ -176,7 +197,7 @@ int prosper_pt_prepare_mesh(
         pack.mode = mode;
         launch_pack_mesh(pack, s);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ctx->prepareEvents.events[2], s)) != hipSuccess) return e;
+        if ((e = hipEventRecord(st.events.events[2], s)) != hipSuccess) return e;
         if (indexWords && (e = hipMemcpyAsync(dBlob, image.data(), indexWords * 4u, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
         if (h.meshletCount)
         {
@@ -193,20 +214,20 @@ int prosper_pt_prepare_mesh(
             launch_meshlet_bounds(bounds, s);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        if ((e = hipEventRecord(ctx->prepareEvents.events[3], s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(ctx->preparedBlob.data(), dBlob, (size_t)words * 4u, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        if (generate && (e = hipMemcpyAsync(ctx->preparedTangents.data(), ctx->prepareTangents.ptr, 16ull * n, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        return hipEventRecord(ctx->prepareEvents.events[4], s);
+        if ((e = hipEventRecord(st.events.events[3], s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(st.hostBlob.data(), dBlob, (size_t)words * 4u, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if (generate && (e = hipMemcpyAsync(st.hostTangents.data(), st.tangents.ptr, 16ull * n, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        return hipEventRecord(st.events.events[4], s);
     };
     // (whatever was enqueued is waited for, also after a failure: `src` is borrowed for the call only)
     const hipError_t e = enqueue();
     const hipError_t f = hipStreamSynchronize(s);
     PPT_HIP(e);
     PPT_HIP(f);
-    ctx->prepared = true;
-    ctx->prepareTimed = true;
-    if (generate) ctx->preparedTangentsValid = true;
-    ctx->prepareMeshletHostMs = hostMs;
+    st.prepared = true;
+    st.timed = true;
+    if (generate) st.tangentsValid = true;
+    st.meshletHostMs = hostMs;
     *out = h;
     return PROSPER_PT_OK;
 }
@@ -214,21 +235,23 @@ int prosper_pt_prepare_mesh(
 int prosper_pt_read_prepared_mesh(prosper_pt_ctx *ctx, void *dst, uint64_t bytes)
 {
     if (!ctx || !dst) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_mesh: null argument");
-    if (!ctx->prepared) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_mesh: no prosper_pt_prepare_mesh has completed");
-    const uint64_t have = (uint64_t)ctx->preparedBlob.size() * 4u;
+    const MeshPreparePassState &st = *ctx->meshPreparePasses;
+    if (!st.prepared) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_mesh: no prosper_pt_prepare_mesh has completed");
+    const uint64_t have = (uint64_t)st.hostBlob.size() * 4u;
     if (bytes != have) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_mesh: the blob holds " + std::to_string(have) + " bytes");
-    std::memcpy(dst, ctx->preparedBlob.data(), (size_t)have);
+    std::memcpy(dst, st.hostBlob.data(), (size_t)have);
     return PROSPER_PT_OK;
 }
 
 int prosper_pt_read_prepared_tangents(prosper_pt_ctx *ctx, float *dst, uint64_t bytes)
 {
     if (!ctx || !dst) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_tangents: null argument");
-    if (!ctx->preparedTangentsValid)
+    const MeshPreparePassState &st = *ctx->meshPreparePasses;
+    if (!st.tangentsValid)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_tangents: no prosper_pt_prepare_mesh has generated tangents");
-    const uint64_t have = (uint64_t)ctx->preparedTangents.size() * 4u;
+    const uint64_t have = (uint64_t)st.hostTangents.size() * 4u;
     if (bytes != have) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_prepared_tangents: the tangents hold " + std::to_string(have) + " bytes");
-    std::memcpy(dst, ctx->preparedTangents.data(), (size_t)have);
+    std::memcpy(dst, st.hostTangents.data(), (size_t)have);
     return PROSPER_PT_OK;
 }
 
@@ -237,14 +260,15 @@ int prosper_pt_get_prepare_mesh_timing(
 {
     if (!ctx || !tangentsMs || !packMs || !meshletHostMs || !boundsMs || !readbackMs)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_prepare_mesh_timing: null argument");
-    if (!ctx->prepareTimed) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_prepare_mesh_timing: no prosper_pt_prepare_mesh has completed");
+    const MeshPreparePassState &st = *ctx->meshPreparePasses;
+    if (!st.timed) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_prepare_mesh_timing: no prosper_pt_prepare_mesh has completed");
     PPT_HIP(hipSetDevice(ctx->device));
     float ms[4];
-    const int rc = ctx->prepareEvents.elapsed(ms);
+    const int rc = st.events.elapsed(ms);
     if (rc != PROSPER_PT_OK) return rc;
     *tangentsMs = ms[0];
     *packMs = ms[1];
-    *meshletHostMs = ctx->prepareMeshletHostMs;
+    *meshletHostMs = st.meshletHostMs;
     *boundsMs = ms[2];
     *readbackMs = ms[3];
     return PROSPER_PT_OK;

@@ -4,10 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "pt_context.hpp"
-#include "pt_gbuffer_passes.hpp"
 #include "pt_math.hpp"
 #include "pt_particles.hpp"
 #include "pt_pass_support.hpp"
@@ -27,17 +24,7 @@ struct ParticlesPassState
     StageEvents<kParticleStages> timing;
 };
 
-bool create_particles_passes(prosper_pt_ctx *ctx)
-{
-    ctx->particlesPasses = new (std::nothrow) ParticlesPassState();
-    return ctx->particlesPasses != nullptr;
-}
-
-void destroy_particles_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->particlesPasses;
-    ctx->particlesPasses = nullptr;
-}
+extern const PassModule kParticlesPasses = pass_module<ParticlesPassState, &prosper_pt_ctx::particlesPasses>();
 
 } // namespace ppt
 
@@ -47,7 +34,6 @@ namespace
 constexpr uint32_t kAllStages =
     PROSPER_PT_PARTICLES_DECAY | PROSPER_PT_PARTICLES_INIT | PROSPER_PT_PARTICLES_SIMULATE | PROSPER_PT_PARTICLES_RENDER;
 constexpr uint32_t kMaxPool = 1u << 26; // 4 GiB of records
-constexpr uint32_t kMaxExtent = 32768;  // a texel index fits 32 bits
 
 uint32_t pool_size(uint32_t maxParticleCount) { return maxParticleCount ? maxParticleCount : kDefaultMaxParticleCount; }
 
@@ -80,18 +66,6 @@ int ensure_pool(ParticlesPassState &st, uint32_t max, bool fresh, hipStream_t s)
         PPT_HIP(hipGetLastError());
     }
     return PROSPER_PT_OK;
-}
-
-// the pass writes the depth: only device memory will do
-bool is_device_pointer(const void *p)
-{
-    hipPointerAttribute_t a = {};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
 }
 
 } // namespace
@@ -133,23 +107,15 @@ int prosper_pt_particles(
         initRecorded = geo.metadatas[mesh].bufferIndex != PROSPER_PT_ABSENT && geo.infos[mesh].indexCount != 0u;
         vertexCount = geo.infos[mesh].vertexCount;
     }
-    float *depth = nonLinearDepth;
+    const float *depth = nullptr; // (written through: the caller's device memory, or the last traced G-buffer's own)
     if (render)
     {
         if (!hdr_has_extent(ctx, width, height))
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_particles: the HDR image has another extent");
-        if (!depth)
-        {
-            const float *last = nullptr;
-            uint32_t gw = 0, gh = 0;
-            const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
-            if (rc != PROSPER_PT_OK) return rc;
-            if (gw != width || gh != height)
-                return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_particles: the last traced G-buffer has another extent");
-            depth = const_cast<float *>(last);
-        }
+        if (const int rc = resolve_depth(ctx, "prosper_pt_particles", nonLinearDepth, true, width, height, &depth)) return rc;
     }
     PPT_HIP(hipSetDevice(ctx->device));
+    // the pass writes the depth: only device memory will do
     if (render && nonLinearDepth && !is_device_pointer(nonLinearDepth))
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_particles: nonLinearDepth must be device memory (the pass writes it)");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -200,7 +166,7 @@ int prosper_pt_particles(
         r.height = height;
         r.frameIndex = pc->renderFrameIndex;
         r.hdr = ctx->hdr;
-        r.nonLinearDepth = depth;
+        r.nonLinearDepth = const_cast<float *>(depth);
         r.keys = st.keys.as<unsigned long long>();
         launch_particles_render(b, r, s);
     }
@@ -250,13 +216,10 @@ int prosper_pt_read_particles(
     if (st.maxParticleCount == 0u) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_particles: there is no particle pool yet");
     if (pool_size(maxParticleCount) != st.maxParticleCount)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_particles: maxParticleCount differs from the pool's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n = st.maxParticleCount;
-    if (particles) PPT_HIP(hipMemcpyAsync(particles, st.particles.ptr, n * sizeof(prosper_pt_particle), hipMemcpyDeviceToHost, s));
-    if (freelist) PPT_HIP(hipMemcpyAsync(freelist, st.freelist.ptr, (n + 1u) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(
+        ctx, static_cast<hipStream_t>(stream),
+        {{particles, st.particles.ptr, n * sizeof(prosper_pt_particle)}, {freelist, st.freelist.ptr, (n + 1u) * sizeof(int32_t)}});
 }
 
 int prosper_pt_set_particles(

@@ -70,19 +70,8 @@ struct RasterPassState
     bool layersValid = false;
 };
 
-bool create_raster_passes(prosper_pt_ctx *ctx)
-{
-    ctx->rasterPasses = new (std::nothrow) RasterPassState();
-    return ctx->rasterPasses != nullptr;
-}
-
-void destroy_raster_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->rasterPasses;
-    ctx->rasterPasses = nullptr;
-}
-
-void forget_raster(prosper_pt_ctx *ctx)
+// a new scene: the visibility image and the ordinal tables describe the old one
+static void forget_raster(prosper_pt_ctx *ctx)
 {
     if (!ctx->rasterPasses) return;
     RasterPassState &rs = *ctx->rasterPasses;
@@ -92,6 +81,8 @@ void forget_raster(prosper_pt_ctx *ctx)
     rs.drawn[0] = rs.drawn[1] = false;
     rs.layersValid = false;
 }
+
+extern const PassModule kRasterPasses = pass_module<RasterPassState, &prosper_pt_ctx::rasterPasses>(forget_raster);
 
 } // namespace ppt
 
@@ -643,12 +634,8 @@ int prosper_pt_read_raster_visibility(prosper_pt_ctx *ctx, uint32_t *ids, float 
     if (!rs.imageValid) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_raster_visibility: nothing has been drawn on this scene");
     const size_t need = (size_t)rs.width * rs.height;
     if (pixels < need) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_raster_visibility: destination too small");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = rs.done.wait(s)) return rc;
     std::vector<unsigned long long> keys(need);
-    PPT_HIP(hipMemcpyAsync(keys.data(), rs.keys.ptr, need * 8u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
+    if (const int rc = read_back(ctx, static_cast<hipStream_t>(stream), {{keys.data(), rs.keys.ptr, need * 8u}}, &rs.done)) return rc;
     const std::vector<uint32_t> &base = rs.hostBase;
     for (size_t i = 0; i < need; ++i)
     {
@@ -683,15 +670,12 @@ int prosper_pt_read_raster_fragments(
     if ((counts || fragments) && pixels != need) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": pixel count differs from the pass's");
     if (fragments && capacity < rs.layerTotal) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, std::string(what) + ": room for fewer fragments than the lists hold");
     if (!counts && !fragments) return PROSPER_PT_OK;
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = rs.done.wait(s)) return rc;
     std::vector<uint32_t> hostCounts(need);
     std::vector<unsigned long long> keys(rs.layerTotal);
-    PPT_HIP(hipMemcpyAsync(hostCounts.data(), rs.layerCounts.ptr, need * 4u, hipMemcpyDeviceToHost, s));
-    if (fragments && rs.layerTotal)
-        PPT_HIP(hipMemcpyAsync(keys.data(), rs.layerFragments.ptr, (size_t)rs.layerTotal * 8u, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
+    const int rc = read_back(
+        ctx, static_cast<hipStream_t>(stream),
+        {{hostCounts.data(), rs.layerCounts.ptr, need * 4u}, {fragments ? keys.data() : nullptr, rs.layerFragments.ptr, (size_t)rs.layerTotal * 8u}}, &rs.done);
+    if (rc != PROSPER_PT_OK) return rc;
     if (counts) std::memcpy(counts, hostCounts.data(), need * 4u);
     if (!fragments) return PROSPER_PT_OK;
     const std::vector<uint32_t> &base = rs.hostBase;

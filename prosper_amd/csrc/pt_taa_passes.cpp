@@ -4,10 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "pt_context.hpp"
-#include "pt_gbuffer_passes.hpp"
 #include "pt_pass_support.hpp"
 #include "pt_taa.hpp"
 
@@ -28,19 +25,7 @@ struct TaaPassState
     StageEvents<kTaaStages> timing;
 };
 
-bool create_taa_passes(prosper_pt_ctx *ctx)
-{
-    ctx->taaPasses = new (std::nothrow) TaaPassState();
-    return ctx->taaPasses != nullptr;
-}
-
-void destroy_taa_passes(prosper_pt_ctx *ctx)
-{
-    delete ctx->taaPasses;
-    ctx->taaPasses = nullptr;
-}
-
-void list_taa_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
+static void list_taa_debug_images(const prosper_pt_ctx *ctx, std::vector<DebugImage> &out)
 {
     const TaaPassState &st = *ctx->taaPasses;
     DebugImage im;
@@ -56,14 +41,9 @@ void forget_taa_history(prosper_pt_ctx *ctx)
     ctx->taaPasses->historyValid = false;
 }
 
+extern const PassModule kTaaPasses = pass_module<TaaPassState, &prosper_pt_ctx::taaPasses>(forget_taa_history, list_taa_debug_images);
+
 } // namespace ppt
-
-namespace
-{
-
-constexpr uint32_t kMaxExtent = 32768; // a texel index fits 32 bits
-
-} // namespace
 
 extern "C" {
 
@@ -94,8 +74,7 @@ int prosper_pt_taa_resolve(
     const bool onDevice = inputs->onDevice != 0u;
     // (an explicit illumination that is the HDR image itself behaves as in place)
     const bool inPlace = inputs->illumination == nullptr || (onDevice && ctx->hdr && inputs->illumination == ctx->hdr);
-    if (inPlace && !hdr_has_extent(ctx, width, height))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_taa_resolve: the HDR image has another extent");
+    if (const int rc = check_in_place_hdr(ctx, "prosper_pt_taa_resolve", inPlace, width, height)) return rc;
     const bool closest = pc->velocitySampling == PROSPER_PT_TAA_VELOCITY_CLOSEST;
     TaaBuffers b = {};
     if (!inputs->velocity)
@@ -108,16 +87,8 @@ int prosper_pt_taa_resolve(
             return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_taa_resolve: the last traced velocity target has another extent");
         b.velocity = static_cast<const float2 *>(traced);
     }
-    if (closest && !inputs->nonLinearDepth)
-    {
-        const float *last = nullptr;
-        uint32_t gw = 0, gh = 0;
-        const int rc = gbuffer_last_depth(ctx, &last, &gw, &gh);
-        if (rc != PROSPER_PT_OK) return rc;
-        if (gw != width || gh != height)
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_taa_resolve: the last traced G-buffer has another extent");
-        b.nonLinearDepth = last;
-    }
+    if (closest)
+        if (const int rc = resolve_depth(ctx, "prosper_pt_taa_resolve", inputs->nonLinearDepth, onDevice, width, height, &b.nonLinearDepth)) return rc;
     PPT_HIP(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TaaPassState &st = *ctx->taaPasses;
@@ -135,34 +106,15 @@ int prosper_pt_taa_resolve(
     if ((rc = st.timing.create())) return rc;
 
     if (inputs->velocity) b.velocity = static_cast<const float2 *>(inputs->velocity);
-    if (closest && inputs->nonLinearDepth) b.nonLinearDepth = inputs->nonLinearDepth;
-    if (!onDevice)
+    if (!onDevice && inputs->velocity)
     {
-        uint8_t *staged = st.hostInputs.as<uint8_t>();
-        if (inputs->velocity)
-        {
-            PPT_HIP(hipMemcpyAsync(staged + pixels * 16u, inputs->velocity, pixels * 8u, hipMemcpyHostToDevice, s));
-            b.velocity = reinterpret_cast<const float2 *>(staged + pixels * 16u);
-        }
-        if (closest && inputs->nonLinearDepth)
-        {
-            PPT_HIP(hipMemcpyAsync(staged + pixels * 24u, inputs->nonLinearDepth, pixels * 4u, hipMemcpyHostToDevice, s));
-            b.nonLinearDepth = reinterpret_cast<const float *>(staged + pixels * 24u);
-        }
+        uint8_t *staged = st.hostInputs.as<uint8_t>() + pixels * 16u;
+        PPT_HIP(hipMemcpyAsync(staged, inputs->velocity, pixels * 8u, hipMemcpyHostToDevice, s));
+        b.velocity = reinterpret_cast<const float2 *>(staged);
     }
-    if (!inPlace)
-    {
-        b.illumination = static_cast<const float4 *>(inputs->illumination);
-        if (!onDevice)
-        {
-            PPT_HIP(hipMemcpyAsync(st.hostInputs.ptr, inputs->illumination, pixels * 16u, hipMemcpyHostToDevice, s));
-            b.illumination = st.hostInputs.as<float4>();
-        }
-        rc = prepare_hdr(ctx, width, height, nullptr, s);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    else
-        b.illumination = ctx->hdr;
+    if (closest && (rc = stage_depth(st.hostInputs, pixels * 24u, inputs->nonLinearDepth, pixels, s, &b.nonLinearDepth)) != PROSPER_PT_OK) return rc;
+    rc = resolve_illumination(ctx, inputs->illumination, inPlace, onDevice, st.hostInputs, width, height, s, &b.illumination);
+    if (rc != PROSPER_PT_OK) return rc;
     b.hdr = ctx->hdr;
     const uint32_t oldest = st.newest ^ 1u;
     b.history = st.history[st.newest].as<uint2>();
@@ -193,11 +145,7 @@ int prosper_pt_read_taa_history(prosper_pt_ctx *ctx, uint16_t *rgba16f, size_t b
     if (!st.historyValid) return fail(PROSPER_PT_ERR_NO_SCENE, "prosper_pt_read_taa_history: there is no history");
     if (bytes != (size_t)st.width * st.height * 8u)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_read_taa_history: bytes differ from the history's");
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(rgba16f, st.history[st.newest].ptr, bytes, hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
-    return PROSPER_PT_OK;
+    return read_back(ctx, static_cast<hipStream_t>(stream), {{rgba16f, st.history[st.newest].ptr, bytes}});
 }
 
 int prosper_pt_get_taa_info(prosper_pt_ctx *ctx, prosper_pt_taa_info *out)

@@ -300,6 +300,31 @@ def test_skybox_fill(oracle, sky):
         ctx.close()
 
 
+def test_skybox_fill_takes_a_device_depth_like_a_host_one(oracle):
+    """The caller's depth as a device pointer gives, bit for bit, the image the same depth gives as a host array."""
+    w, h = 50, 35
+    world = scenes.cornell(with_skybox=True)
+    ctx = capi.Context(device=0)
+    try:
+        ctx.upload_scene(world)
+        c = world.camera
+        cam, _ = oracle.camera_uniforms(c["eye"], c["target"], c["up"], c["fov"], c["zN"], c["zF"], w, h)
+        depth = checker_depth(w, h)
+        ctx.deferred_shading_traced(cam, w, h)
+        before = ctx.read_hdr()
+        ctx.skybox_fill(cam, w, h, depth=depth)
+        host = ctx.read_hdr()
+        ctx.deferred_shading_traced(cam, w, h)  # the same image again under the second fill
+        assert ctx.read_hdr().tobytes() == before.tobytes()
+        with DeviceCopy(depth) as dp:
+            ctx.skybox_fill(cam, w, h, depth_ptr=dp)
+            device = ctx.read_hdr()
+        assert host.tobytes() != before.tobytes()  # (the fill wrote the misses)
+        assert device.tobytes() == host.tobytes()
+    finally:
+        ctx.close()
+
+
 # ---- end to end ----
 
 def hand_pc(hcam, w):

@@ -492,3 +492,46 @@ def test_render_refuses_what_it_cannot_write(gpu_ctx, render_setup):
         run(gpu_ctx, N_RENDER, S.PARTICLES_RENDER, camera=cam, w=W - 1, h=H, depth_ptr=depth.ptr.value)
     with pytest.raises(Exception, match="unknown stage bits"):
         run(gpu_ctx, N_RENDER, 32)
+
+
+def test_render_over_the_last_traced_depth_equals_the_same_depth_as_the_callers(gpu_ctx, render_setup, oracle):
+    """No depth - the last traced G-buffer's, read and written where it lies - gives, bit for bit, the image and the depth
+    that a device copy of that G-buffer's depth gives as the caller's."""
+    w, h = 50, 35
+    world = scenes.cornell()  # (what render_setup uploaded)
+    c = world.camera
+    cam, _ = oracle.camera_uniforms(c["eye"], c["target"], c["up"], c["fov"], c["zN"], c["zF"], w, h)
+    # A quad is 2 mm across, far less than a pixel of this image: it draws only where it covers a pixel's centre.  So the
+    # particles lie on the rays through the centres of random pixels, some in front of the room's surfaces, some behind.
+    eye, target, up = (np.array(c[k], np.float64) for k in ("eye", "target", "up"))
+    forward = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(forward, up) / np.linalg.norm(np.cross(forward, up))
+    focal = (h / 2) / math.tan(c["fov"] / 2)  # pixels per unit of x / distance
+    rng = np.random.default_rng(5)
+    n = 600
+    px, py, d = rng.integers(0, w, n), rng.integers(0, h, n), rng.uniform(0.5, 6.0, n)
+    rays = forward * focal + right * (px + 0.5 - w / 2)[:, None] - np.cross(right, forward) * (py + 0.5 - h / 2)[:, None]
+    rec, _, _ = P.fresh_pool(N_RENDER)
+    rec["position_lifetime"][300:300 + n, :3] = eye + rays / focal * d[:, None]
+    rec["position_lifetime"][300:300 + n, 3] = 4.0
+    rec["mask"][300:300 + n] = S.PARTICLE_MASK_GRAVITY | S.PARTICLE_MASK_DECAY
+    gpu_ctx.set_particles(rec, 0, np.arange(N_RENDER, dtype=np.int32))
+
+    gpu_ctx.deferred_shading_traced(cam, w, h)
+    hdr_in, depth_in = gpu_ctx.read_hdr(), gpu_ctx.read_gbuffer()[2]
+    run(gpu_ctx, N_RENDER, S.PARTICLES_RENDER, camera=cam, w=w, h=h)
+    written = gpu_ctx.particles_info().fragmentsWritten
+    last_hdr, last_depth = gpu_ctx.read_hdr(), gpu_ctx.read_gbuffer()[2]
+    assert written > 0 and not same_bits(last_depth, depth_in).all()  # (the pass drew, and into the G-buffer's own depth)
+
+    gpu_ctx.deferred_shading_traced(cam, w, h)  # the same image and depth again
+    assert gpu_ctx.read_hdr().tobytes() == hdr_in.tobytes() and gpu_ctx.read_gbuffer()[2].tobytes() == depth_in.tobytes()
+    own = DeviceArray(w * h * 4)
+    try:
+        own.upload(depth_in)
+        run(gpu_ctx, N_RENDER, S.PARTICLES_RENDER, camera=cam, w=w, h=h, depth_ptr=own.ptr.value)
+        assert gpu_ctx.particles_info().fragmentsWritten == written
+        assert gpu_ctx.read_hdr().tobytes() == last_hdr.tobytes()
+        assert own.download((h, w)).tobytes() == last_depth.tobytes()
+    finally:
+        own.free()
