@@ -711,6 +711,47 @@ typedef struct prosper_pt_hierarchy_state
 int prosper_pt_get_hierarchy_state(prosper_pt_ctx *ctx, prosper_pt_hierarchy_state *out);
 /* Test hook: the node array as the device holds it (prosper_pt_scene_stats.nodeCount x nodeBytes). */
 int prosper_pt_debug_read_nodes(prosper_pt_ctx *ctx, void *out, size_t byte_size);
+
+/* ---- the hierarchy built on the GPU (opt-in) ----
+ * prosper builds its acceleration structures on the GPU and its TLAS again every frame (src/scene/World.cpp:585-802, 878-928).
+ * prosper_pt_build_hierarchy_gpu makes the whole 4-wide tree on the device from the device's own world triangles: a linear
+ * BVH (Morton order, a binary radix tree, a collapse to the same 80-byte nodes; the rule is prosper_amd/lbvh.py), then the
+ * refit that writes every box.  Same contract as prosper_pt_rebuild_hierarchy: a pending background geometry is installed
+ * first, a staged update flushed, the device synchronised; it counts in `rebuilds`, resets costRatio to 1 and fills nodeCount,
+ * maxDepth and bvhBuildSeconds.  Hits do not depend on the hierarchy, so the image is the one the host's tree gives, bit for
+ * bit; a linear BVH traces slower than the host's SAH tree and builds much faster, which is why it is a choice.  A tree whose
+ * stack bound exceeds what the traversal can hold is refused with PROSPER_PT_ERR_UNSUPPORTED and the scene stays exactly as it
+ * was.  Leaves hold at most prosper_pt_debug_options.leafSize triangles (1 .. 4; 0: the default).
+ * prosper_pt_set_hierarchy_builder: PROSPER_PT_BUILDER_HOST (the default) changes nothing.  With PROSPER_PT_BUILDER_GPU,
+ * prosper_pt_rebuild_hierarchy runs the GPU build, and so does an update whose refits have degraded the tree past
+ * rebuildCostRatio - inside that call, in place of the worker thread.  prosper_pt_upload_scene and prosper_pt_update_meshes
+ * build on the host in either mode.  After a GPU build the next host build splits every instance again. */
+#define PROSPER_PT_BUILDER_HOST 0u
+#define PROSPER_PT_BUILDER_GPU 1u
+int prosper_pt_build_hierarchy_gpu(prosper_pt_ctx *ctx);
+int prosper_pt_set_hierarchy_builder(prosper_pt_ctx *ctx, uint32_t builder);
+#define PROSPER_PT_HIERARCHY_BUILD_STAGES 8u
+typedef struct prosper_pt_hierarchy_build_info
+{
+    uint32_t builder;         /* PROSPER_PT_BUILDER_* of the build that made the tree in use */
+    uint32_t selectedBuilder; /* prosper_pt_set_hierarchy_builder */
+    uint32_t leafSize;        /* most triangles per leaf of that build */
+    uint32_t nodeCount;
+    uint32_t levels;          /* node heights: kernel launches of a refit = levels + 1 */
+    uint32_t depths;          /* 4-wide depths the GPU build numbered (0 after a host build) */
+    uint32_t stackBound;      /* prosper_pt_scene_stats.maxDepth */
+    uint32_t reserved;
+    /* device milliseconds of a GPU build (0 after a host build): centroid bounds, codes, sort, radix tree, collapse and
+     * numbering, heights, refit tables, and the switch (copies, permuted triangles, the first refit) */
+    float stageMs[PROSPER_PT_HIERARCHY_BUILD_STAGES];
+    float totalMs;
+    uint32_t reserved2;
+} prosper_pt_hierarchy_build_info;
+int prosper_pt_get_hierarchy_build_info(prosper_pt_ctx *ctx, prosper_pt_hierarchy_build_info *out);
+/* Test hook: the flat world triangles ((drawInstance, primitive) order, 48 bytes each) and the leaf-order permutation
+ * (uint32 per triangle) as the device holds them; a staged update is flushed first. */
+int prosper_pt_debug_read_hierarchy_arrays(
+    prosper_pt_ctx *ctx, void *triangles, size_t triangle_bytes, void *permutation, size_t permutation_bytes);
 int prosper_pt_get_scene_stats(prosper_pt_ctx *ctx, prosper_pt_scene_stats *out);
 
 /* Optional: render into caller-owned device memory (localWidth*height RGBA32F texels, 16-byte

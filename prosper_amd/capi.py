@@ -91,6 +91,10 @@ def lib():
     L.prosper_pt_rebuild_hierarchy.argtypes = [vp]
     L.prosper_pt_get_hierarchy_state.argtypes = [vp, C.POINTER(S.HierarchyState)]
     L.prosper_pt_debug_read_nodes.argtypes = [vp, vp, C.c_size_t]
+    L.prosper_pt_build_hierarchy_gpu.argtypes = [vp]
+    L.prosper_pt_set_hierarchy_builder.argtypes = [vp, u32]
+    L.prosper_pt_get_hierarchy_build_info.argtypes = [vp, C.POINTER(S.HierarchyBuildInfo)]
+    L.prosper_pt_debug_read_hierarchy_arrays.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     L.prosper_pt_set_output_buffer.argtypes = [vp, vp, C.c_size_t]
     L.prosper_pt_render.argtypes = [
         vp, C.POINTER(S.ReferencePC), C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.TileDesc), u32, vp]
@@ -780,6 +784,27 @@ class Context:
         out = np.zeros((n, 20), np.uint32)
         _check(lib().prosper_pt_debug_read_nodes(self._h, out.ctypes.data, out.nbytes))
         return out
+
+    def build_hierarchy_gpu(self):
+        """prosper_pt_build_hierarchy_gpu: the whole tree again, made on the device (prosper_amd/lbvh.py states the rule)."""
+        self._sync_debug()
+        _check(lib().prosper_pt_build_hierarchy_gpu(self._h))
+
+    def set_hierarchy_builder(self, builder):
+        """structs.BUILDER_HOST (the default) or BUILDER_GPU: who rebuilds - prosper_pt_rebuild_hierarchy and the drift trigger."""
+        _check(lib().prosper_pt_set_hierarchy_builder(self._h, builder))
+
+    def hierarchy_build_info(self):
+        info = S.HierarchyBuildInfo()
+        _check(lib().prosper_pt_get_hierarchy_build_info(self._h, C.byref(info)))
+        return info
+
+    def read_hierarchy_arrays(self):
+        """The flat world triangles, (n, 12) uint32 words, and the leaf-order permutation, (n,) uint32, as the device holds them."""
+        n = int(self.scene_stats().triangleCount)
+        tris, perm = np.zeros((n, 12), np.uint32), np.zeros(n, np.uint32)
+        _check(lib().prosper_pt_debug_read_hierarchy_arrays(self._h, tris.ctypes.data, tris.nbytes, perm.ctypes.data, perm.nbytes))
+        return tris, perm
 
     def scene_stats(self):
         self._sync_debug()

@@ -23,6 +23,7 @@
 
 #include "bvh_build.hpp"
 #include "pt_animation.hpp"
+#include "pt_bvh_build.hpp"
 #include "pt_context.hpp"
 #include "pt_geometry.hpp"
 #include "pt_kernels.hpp"
@@ -857,6 +858,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     free_scene(ctx);
     for (const PassModule *m : kPassModules) m->destroy(ctx);
     destroy_animation_state(ctx);
+    delete ctx->lbvh;
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
@@ -941,7 +943,7 @@ int prosper_pt_update_lights(
 // The synchronous path: re-split the instances that moved since the last build, re-assemble, upload (what
 // prosper_pt_update_transforms did before the refit existed; prosper's own TLAS build is of this kind, on the GPU).
 static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream);
-static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
+static int rebuild_hierarchy_on_host(prosper_pt_ctx *ctx)
 {
     PPT_HIP(hipSetDevice(ctx->device));
     {
@@ -968,6 +970,7 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
             sizeof(WorldTriangle) * (size_t)acc->ranges[r].count, hipMemcpyDeviceToHost));
     }
     BvhBuildResult bvh;
+    bool instancedNow = acc->instanced;
     const auto tBuild = std::chrono::steady_clock::now();
     try
     {
@@ -976,8 +979,24 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
             ctx->debug.failNextUpdate = 0;
             throw std::runtime_error("debug option failNextUpdate is set");
         }
-        bvh = acc->instanced ? acc->bvh.rebuild(acc->flat.data(), acc->movedSinceBuild, build_options(ctx))
-                             : build_bvh(acc->flat.data(), acc->total, build_options(ctx));
+        if (acc->instanced)
+            bvh = acc->bvh.rebuild(acc->flat.data(), acc->movedSinceBuild, build_options(ctx));
+        else if (acc->foreignTree && ctx->debug.flatBvh == 0)
+        {
+            // the last build ran on the GPU: no subtree is kept, every instance is split as the scene's first build
+            // splits it (begin_geometry), with the same way out for a spliced tree that is too deep
+            try
+            {
+                bvh = acc->bvh.build(acc->flat.data(), acc->total, acc->ranges, build_options(ctx));
+                instancedNow = true;
+            }
+            catch (const std::exception &)
+            {
+                bvh = build_bvh(acc->flat.data(), acc->total, build_options(ctx));
+            }
+        }
+        else
+            bvh = build_bvh(acc->flat.data(), acc->total, build_options(ctx));
     }
     catch (const std::exception &ex)
     {
@@ -988,6 +1007,9 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
     const int rc = upload_hierarchy(ctx, target, bvh);
     if (rc != PROSPER_PT_OK) return rc;
     acc->stale = false;
+    acc->instanced = instancedNow;
+    acc->foreignTree = false;
+    acc->gpuStagesValid = false;
     acc->rebuilds++;
     ctx->stats.nodeCount = bvh.nodes.size();
     ctx->stats.maxDepth = bvh.maxDepth;
@@ -995,6 +1017,42 @@ static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
     ctx->stats.bvhBuildSeconds = buildSeconds;
     ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return PROSPER_PT_OK;
+}
+
+// The same contract with the tree made on the GPU (pt_bvh_build.hpp): a pending background geometry is
+// installed first, a staged update flushed, the device synchronised; then the linear BVH over the device's own flat world
+// triangles.  A tree the traversal cannot hold is refused and the scene stays exactly as it was.  An empty scene has
+// nothing to build on the device and takes the host's path.
+static int rebuild_hierarchy_on_gpu(prosper_pt_ctx *ctx)
+{
+    PPT_HIP(hipSetDevice(ctx->device));
+    {
+        const int prc = poll_mesh_build(ctx, true);
+        if (prc != PROSPER_PT_OK) return prc;
+    }
+    AccelState *acc = ctx->accel;
+    if (acc->total == 0) return rebuild_hierarchy_on_host(ctx);
+    const auto t0 = std::chrono::steady_clock::now();
+    {
+        int frc = flush_pending_update(ctx, nullptr); // the moved triangles must be in the flat array
+        if (frc == PROSPER_PT_OK) frc = sync_animation_mirrors(ctx);
+        if (frc != PROSPER_PT_OK) return frc;
+    }
+    PPT_HIP(hipDeviceSynchronize()); // renders in flight read the old hierarchy
+    const auto tBuild = std::chrono::steady_clock::now();
+    GeometryTarget target = context_target(ctx);
+    const int rc = build_hierarchy_on_device(ctx, target);
+    if (rc != PROSPER_PT_OK) return rc;
+    acc->rebuilds++;
+    ctx->stats.deviceBytes = ctx->sceneBytes;
+    ctx->stats.bvhBuildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild).count();
+    ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return PROSPER_PT_OK;
+}
+
+static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
+{
+    return ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU ? rebuild_hierarchy_on_gpu(ctx) : rebuild_hierarchy_on_host(ctx);
 }
 
 static float rebuild_cost_ratio(const prosper_pt_ctx *ctx)
@@ -1097,6 +1155,7 @@ static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
     PPT_HIP(hipGetLastError());
     acc->flatStale = true; // (the flat array now holds the new pose whatever happens next)
     if (acc->total && (rc = enqueue_refit(acc, bvh_pad_coefficient(build_options(ctx)), acc->dNodesV[v], acc->dTrisV[v], v, stream))) return rc;
+    if (acc->total && acc->foreignTree && (rc = enqueue_nest_boxes(acc, acc->dNodesV[v], stream))) return rc;
     if ((rc = acc->sceneDone.record(stream))) return rc;
     // ---- commit: the new version becomes the scene ----
     acc->versions.commit(v);
@@ -1249,6 +1308,8 @@ int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransf
     ctx->stats.bvhBuildSeconds = 0.0;
     ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (any && ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
+    // (the GPU builder is quick enough for the synchronous route; the worker thread is the host builder's)
+    if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
     if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild)
     {
         // The refits have degraded the tree: the instances that moved since the last build are split again - by the worker
@@ -1306,6 +1367,7 @@ int prosper_pt_animate(prosper_pt_ctx *ctx, float timeS, uint32_t flags, void *s
     PPT_HIP(hipSetDevice(ctx->device));
     if ((rc = poll_refit_cost(acc, false))) return rc;
     if (ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
+    if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
     if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild && (rc = start_mesh_build(ctx, true))) return rc;
     if (!(flags & PROSPER_PT_UPDATE_NOW)) return PROSPER_PT_OK;
     return flush_pending_update(ctx, static_cast<hipStream_t>(stream));
@@ -1316,6 +1378,73 @@ int prosper_pt_rebuild_hierarchy(prosper_pt_ctx *ctx)
     if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_rebuild_hierarchy: null argument");
     if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
     return rebuild_hierarchy_impl(ctx);
+}
+
+int prosper_pt_build_hierarchy_gpu(prosper_pt_ctx *ctx)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_build_hierarchy_gpu: null argument");
+    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    return rebuild_hierarchy_on_gpu(ctx);
+}
+
+int prosper_pt_set_hierarchy_builder(prosper_pt_ctx *ctx, uint32_t builder)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_hierarchy_builder: null argument");
+    if (builder != PROSPER_PT_BUILDER_HOST && builder != PROSPER_PT_BUILDER_GPU)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_hierarchy_builder: unknown builder");
+    ctx->hierarchyBuilder = builder;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_hierarchy_build_info(prosper_pt_ctx *ctx, prosper_pt_hierarchy_build_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_hierarchy_build_info: null argument");
+    *out = prosper_pt_hierarchy_build_info{};
+    out->selectedBuilder = ctx->hierarchyBuilder;
+    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    {
+        const int prc = ctx->meshBuild ? poll_mesh_build(ctx, false) : PROSPER_PT_OK;
+        if (prc != PROSPER_PT_OK) return prc;
+    }
+    const AccelState *acc = ctx->accel;
+    out->builder = acc->foreignTree ? PROSPER_PT_BUILDER_GPU : PROSPER_PT_BUILDER_HOST;
+    const uint32_t hostLeaf = ctx->debug.leafSize ? std::min(std::max(ctx->debug.leafSize, 1u), 8u) : kMaxLeafTriangles;
+    out->leafSize = acc->foreignTree ? acc->gpuLeafSize : hostLeaf;
+    out->nodeCount = acc->nodeCount;
+    out->levels = (uint32_t)acc->levelOffsets.size() - 1u;
+    out->depths = acc->foreignTree ? acc->gpuDepths : 0u;
+    out->stackBound = ctx->stats.maxDepth;
+    if (acc->foreignTree && acc->gpuStagesValid)
+        for (uint32_t k = 0; k < PROSPER_PT_HIERARCHY_BUILD_STAGES; ++k)
+        {
+            out->stageMs[k] = acc->gpuStageMs[k];
+            out->totalMs += acc->gpuStageMs[k];
+        }
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_debug_read_hierarchy_arrays(
+    prosper_pt_ctx *ctx, void *triangles, size_t triangle_bytes, void *permutation, size_t permutation_bytes)
+{
+    if (!ctx || !triangles || !permutation) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_hierarchy_arrays: null argument");
+    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
+    PPT_HIP(hipSetDevice(ctx->device));
+    {
+        int frc = ctx->meshBuild ? poll_mesh_build(ctx, false) : PROSPER_PT_OK;
+        if (frc == PROSPER_PT_OK) frc = flush_pending_update(ctx, nullptr);
+        if (frc != PROSPER_PT_OK) return frc;
+    }
+    const AccelState *acc = ctx->accel;
+    const size_t total = (size_t)acc->total;
+    if (triangle_bytes < total * sizeof(WorldTriangle) || permutation_bytes < total * sizeof(uint32_t))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_hierarchy_arrays: destination too small");
+    PPT_HIP(hipDeviceSynchronize());
+    if (total)
+    {
+        PPT_HIP(hipMemcpy(triangles, acc->dFlat, total * sizeof(WorldTriangle), hipMemcpyDeviceToHost));
+        PPT_HIP(hipMemcpy(permutation, acc->dPerm, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return PROSPER_PT_OK;
 }
 
 int prosper_pt_get_hierarchy_state(prosper_pt_ctx *ctx, prosper_pt_hierarchy_state *out)

@@ -110,6 +110,8 @@ inline const PassModule *const kPassModules[] = {&kGBufferPasses, &kForwardPasse
 // State of the keyframe animation (pt_animation.hip, pt_animation.hpp): the node and channel tables of the scene, the
 // staged time and the read-back that feeds the host mirrors below.  Made and freed like the others.
 struct AnimationState;
+// Scratch arrays and timed events of the GPU hierarchy build (pt_bvh_build.hpp), made by the first such build.
+struct LbvhState;
 
 #pragma GCC visibility pop
 
@@ -153,6 +155,11 @@ struct AccelState
     std::vector<prosper_ModelInstanceTransforms> transforms;
     InstancedBvh bvh;
     bool instanced = false;
+    // The tree on the device was built there (pt_bvh_build.hpp): `bvh` and `flat` describe an older one, so the next host
+    // build of any kind splits every instance again.  What that build reported, for prosper_pt_get_hierarchy_build_info.
+    bool foreignTree = false, gpuStagesValid = false;
+    uint32_t gpuLeafSize = 0, gpuDepths = 0;
+    float gpuStageMs[8] = {};
     // a prosper_pt_update_transforms that failed half way leaves transforms, world triangles and nodes out of step: renders
     // are refused and the next update redoes every instance, whatever the transforms it is given
     bool stale = false;
@@ -351,6 +358,8 @@ struct prosper_pt_ctx
     ppt::CompressPassState *compressPasses = nullptr;       // prosper_pt_compress_texture, prosper_pt_debug_bc7_encode_blocks
     ppt::MeshPreparePassState *meshPreparePasses = nullptr; // prosper_pt_prepare_mesh
     ppt::AnimationState *animation = nullptr;
+    uint32_t hierarchyBuilder = PROSPER_PT_BUILDER_HOST; // prosper_pt_set_hierarchy_builder
+    ppt::LbvhState *lbvh = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

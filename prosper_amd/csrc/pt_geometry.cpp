@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "pt_bvh_build.hpp"
 #include "pt_kernels.hpp"
 #include "pt_materials.hpp"
 #include "pt_scene.hpp"
@@ -94,6 +95,15 @@ int enqueue_refit(AccelState *acc, float padCoeff, BvhNode *nodes, const WorldTr
     return PROSPER_PT_OK;
 }
 
+// Behind the refit of a tree that was built on the GPU: its stored child boxes made to nest (pt_bvh_build.hpp).  The host
+// builder's trees are left as the encoder writes them.
+int enqueue_nest_boxes(AccelState *acc, BvhNode *nodes, hipStream_t stream)
+{
+    launch_lbvh_nest_boxes(nodes, acc->dRefitOrder, acc->levelOffsets.data(), (uint32_t)acc->levelOffsets.size() - 1u, stream);
+    PPT_HIP(hipGetLastError());
+    return PROSPER_PT_OK;
+}
+
 // Takes the newest measure that has arrived (wait: also waits for the newest refit's) into lastCostRatio.
 int poll_refit_cost(AccelState *acc, bool wait)
 {
@@ -114,13 +124,10 @@ int poll_refit_cost(AccelState *acc, bool wait)
     return PROSPER_PT_OK;
 }
 
-// Nodes + leaf-order triangles of a freshly built hierarchy to the device (the node array grows when it has to), and
-// what a later refit needs: the nodes ordered by height, every triangle's place in the leaf order, the bounds array.
-// Everything runs on the target's stream, which has been waited for when this returns.
-int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResult &bvh)
+// The version-`cur` node array holds `nodeBytes` (it grows when it has to; the other versions' arrays go, a later update
+// makes them again), and no other version's array counts as holding the tree.
+static int reserve_node_array(prosper_pt_ctx *ctx, AccelState *acc, size_t nodeBytes)
 {
-    AccelState *acc = t.acc;
-    const size_t nodeBytes = bvh.nodes.size() * sizeof(BvhNode);
     if (nodeBytes > acc->nodeCapacityBytes)
     {
         void *d = nullptr;
@@ -140,6 +147,55 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
         acc->nodeCapacityBytes = capacity;
     }
     for (uint32_t ver = 0; ver < AccelState::kVersions; ++ver) acc->nodesCurrent[ver] = ver == acc->versions.cur;
+    return PROSPER_PT_OK;
+}
+
+// The refit's tables for a tree of n nodes: bounds, node order, leaf positions, the cost slots.
+static int reserve_refit_tables(prosper_pt_ctx *ctx, AccelState *acc, size_t n)
+{
+    if (n > acc->refitCapacityNodes)
+    {
+        const size_t capacity = n + n / 4 + 64;
+        void *d = nullptr;
+        int rc;
+        // (as above: no refit is reading the old tables)
+        if (acc->dNodeBounds) device_free(ctx, acc->dNodeBounds);
+        if (acc->dRefitOrder) device_free(ctx, acc->dRefitOrder);
+        acc->dNodeBounds = nullptr;
+        acc->dRefitOrder = nullptr;
+        acc->refitCapacityNodes = 0;
+        if ((rc = device_alloc(ctx, capacity * 2 * sizeof(float4), &d))) return rc;
+        acc->dNodeBounds = static_cast<float4 *>(d);
+        if ((rc = device_alloc(ctx, capacity * sizeof(uint32_t), &d))) return rc;
+        acc->dRefitOrder = static_cast<uint32_t *>(d);
+        acc->refitCapacityNodes = capacity;
+    }
+    if (!acc->dLeafPosition)
+    {
+        void *d = nullptr;
+        int rc;
+        if ((rc = device_alloc(ctx, (size_t)(acc->total ? acc->total : 1) * sizeof(uint32_t), &d))) return rc;
+        acc->dLeafPosition = static_cast<uint32_t *>(d);
+    }
+    if (!acc->dCost)
+    {
+        void *d = nullptr;
+        int rc;
+        if ((rc = device_alloc(ctx, sizeof(float) * AccelState::kCostSlots, &d))) return rc;
+        acc->dCost = static_cast<float *>(d);
+        if ((rc = acc->hCost.allocate(sizeof(float) * AccelState::kCostSlots))) return rc;
+    }
+    return PROSPER_PT_OK;
+}
+
+// Nodes + leaf-order triangles of a freshly built hierarchy to the device (the node array grows when it has to), and
+// what a later refit needs: the nodes ordered by height, every triangle's place in the leaf order, the bounds array.
+// Everything runs on the target's stream, which has been waited for when this returns.
+int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResult &bvh)
+{
+    AccelState *acc = t.acc;
+    const size_t nodeBytes = bvh.nodes.size() * sizeof(BvhNode);
+    if (const int rc = reserve_node_array(ctx, acc, nodeBytes)) return rc;
     {
         const int src = staged_copy(ctx, t.stream, acc->dNodes, bvh.nodes.data(), nodeBytes, hipMemcpyHostToDevice);
         if (src != PROSPER_PT_OK) return src;
@@ -178,42 +234,11 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
     for (uint32_t l = 0; l < levels; ++l) acc->levelOffsets[l + 1u] += acc->levelOffsets[l];
     std::vector<uint32_t> order(n ? n : 1), cursor(acc->levelOffsets.begin(), acc->levelOffsets.end() - 1);
     for (size_t i = 0; i < n; ++i) order[cursor[height[i]]++] = (uint32_t)i;
-    if (n > acc->refitCapacityNodes)
-    {
-        const size_t capacity = n + n / 4 + 64;
-        void *d = nullptr;
-        int rc;
-        // (as above: no refit is reading the old tables)
-        if (acc->dNodeBounds) device_free(ctx, acc->dNodeBounds);
-        if (acc->dRefitOrder) device_free(ctx, acc->dRefitOrder);
-        acc->dNodeBounds = nullptr;
-        acc->dRefitOrder = nullptr;
-        acc->refitCapacityNodes = 0;
-        if ((rc = device_alloc(ctx, capacity * 2 * sizeof(float4), &d))) return rc;
-        acc->dNodeBounds = static_cast<float4 *>(d);
-        if ((rc = device_alloc(ctx, capacity * sizeof(uint32_t), &d))) return rc;
-        acc->dRefitOrder = static_cast<uint32_t *>(d);
-        acc->refitCapacityNodes = capacity;
-    }
+    if (const int rc = reserve_refit_tables(ctx, acc, n)) return rc;
     t.lap("  refit tables (host)");
     {
         const int src = staged_copy(ctx, t.stream, acc->dRefitOrder, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (src != PROSPER_PT_OK) return src;
-    }
-    if (!acc->dLeafPosition)
-    {
-        void *d = nullptr;
-        int rc;
-        if ((rc = device_alloc(ctx, (size_t)(acc->total ? acc->total : 1) * sizeof(uint32_t), &d))) return rc;
-        acc->dLeafPosition = static_cast<uint32_t *>(d);
-    }
-    if (!acc->dCost)
-    {
-        void *d = nullptr;
-        int rc;
-        if ((rc = device_alloc(ctx, sizeof(float) * AccelState::kCostSlots, &d))) return rc;
-        acc->dCost = static_cast<float *>(d);
-        if ((rc = acc->hCost.allocate(sizeof(float) * AccelState::kCostSlots))) return rc;
     }
     std::vector<uint32_t> position((size_t)acc->total);
     if (acc->total)
@@ -251,6 +276,66 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
     acc->lastCostRatio = 1.0f;
     acc->movedSinceBuild.assign(acc->ranges.size(), 0);
     acc->flatStale = false;
+    return PROSPER_PT_OK;
+}
+
+// The GPU builder's counterpart of build + upload_hierarchy (pt_bvh_build.hpp): the tree is made from the
+// device's own flat world triangles into the build's scratch arrays; only when its stack bound has been accepted are the
+// scene's arrays written - device-to-device copies, the leaf positions, the permuted triangles, the first refit, which
+// writes every origin and child box.  A refused build leaves the scene exactly as it was.  The caller has synchronised
+// the device; the target's stream has been waited for when this returns.
+int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t)
+{
+    AccelState *acc = t.acc;
+    if (!acc->total) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: the scene has no triangles");
+    if (!ctx->lbvh) ctx->lbvh = new (std::nothrow) LbvhState();
+    if (!ctx->lbvh) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
+    LbvhState &st = *ctx->lbvh;
+    static_assert(sizeof(acc->gpuStageMs) / sizeof(float) == kLbvhStageCount, "one slot per stage");
+    const uint32_t leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles) : kLbvhDefaultLeafSize;
+    LbvhResult built;
+    int rc;
+    acc->gpuStagesValid = false;
+    if ((rc = lbvh_build(st, acc->dFlat, (uint32_t)acc->total, leafSize, t.stream, built))) return rc;
+
+    // ---- accepted: from here on the scene's arrays change ----
+    acc->stale = true;
+    const size_t n = built.nodeCount;
+    if ((rc = reserve_node_array(ctx, acc, n * sizeof(BvhNode)))) return rc;
+    if ((rc = reserve_refit_tables(ctx, acc, n))) return rc;
+    PPT_HIP(hipMemcpyAsync(acc->dNodes, st.nodes, n * sizeof(BvhNode), hipMemcpyDeviceToDevice, t.stream));
+    t.s->nodes = acc->dNodes;
+    PPT_HIP(hipMemcpyAsync(acc->dPerm, st.perm, (size_t)acc->total * sizeof(uint32_t), hipMemcpyDeviceToDevice, t.stream));
+    PPT_HIP(hipMemcpyAsync(acc->dRefitOrder, st.order, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, t.stream));
+    launch_lbvh_leaf_positions(acc->dPerm, acc->dLeafPosition, (uint32_t)acc->total, t.stream);
+    launch_permute_triangles(acc->dFlat, acc->dPerm, acc->dTris, (uint32_t)acc->total, t.stream);
+    PPT_HIP(hipGetLastError());
+    acc->nodeCount = built.nodeCount;
+    acc->levelOffsets = built.levelOffsets;
+    for (bool &pending : acc->costPending) pending = false;
+    acc->builtCost = 0.0f;
+    if ((rc = enqueue_refit(acc, bvh_pad_coefficient(t.buildOpt), acc->dNodes, acc->dTris, acc->versions.cur, t.stream))) return rc;
+    if ((rc = enqueue_nest_boxes(acc, acc->dNodes, t.stream))) return rc;
+    PPT_HIP(hipEventRecord(st.events.events[kLbvhStageCount], t.stream));
+    PPT_HIP(hipStreamSynchronize(t.stream));
+    const uint32_t slot = acc->versions.cur % AccelState::kCostSlots;
+    acc->costPending[slot] = false;
+    acc->builtCost = acc->hCost.ptr[slot];
+    acc->costRead = acc->refitSequence;
+    acc->lastCostRatio = 1.0f;
+    acc->movedSinceBuild.assign(acc->ranges.size(), 0);
+    // the host builder's subtrees and its copy of the triangles no longer describe the tree: its next build of any
+    // kind splits every instance again (prosper_pt.cpp rebuild_hierarchy_on_host, start_mesh_build)
+    acc->instanced = false;
+    acc->foreignTree = true;
+    acc->flatStale = true;
+    acc->stale = false;
+    if ((rc = st.events.elapsed(acc->gpuStageMs))) return rc;
+    acc->gpuStagesValid = true;
+    acc->gpuLeafSize = leafSize;
+    acc->gpuDepths = built.depths;
+    t.stats->nodeCount = built.nodeCount;
+    t.stats->maxDepth = built.stackBound;
     return PROSPER_PT_OK;
 }
 

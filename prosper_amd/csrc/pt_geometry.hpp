@@ -50,8 +50,12 @@ GeometryTarget context_target(prosper_pt_ctx *ctx);
 // the refit's GPU work for the node / triangle arrays of scene version `version`, and the readback of its measure
 int enqueue_refit(AccelState *acc, float padCoeff, BvhNode *nodes, const WorldTriangle *tris, uint32_t version, hipStream_t stream);
 int poll_refit_cost(AccelState *acc, bool wait);
+// behind the refit of a GPU-built tree (AccelState::foreignTree): the stored child boxes made to nest
+int enqueue_nest_boxes(AccelState *acc, BvhNode *nodes, hipStream_t stream);
 // nodes + leaf-order triangles of a freshly built hierarchy to the device, and what a later refit needs
 int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResult &bvh);
+// the same from the GPU builder: the tree made on the device from acc->dFlat, installed once its stack bound is accepted
+int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t);
 
 
 // ---- the geometry of the scene: where every draw instance's triangles live, the hierarchy over them, the per-triangle

@@ -313,6 +313,18 @@ class HierarchyState(C.Structure):
                 ("geometryBuildRunning", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# ---- the hierarchy built on the GPU (prosper_pt_build_hierarchy_gpu / prosper_pt_set_hierarchy_builder) ----
+BUILDER_HOST, BUILDER_GPU = 0, 1
+HIERARCHY_BUILD_STAGES = 8
+HIERARCHY_BUILD_STAGE_NAMES = ("bounds", "codes", "sort", "radixTree", "collapse", "heights", "tables", "install")
+
+
+class HierarchyBuildInfo(C.Structure):
+    _fields_ = [("builder", C.c_uint32), ("selectedBuilder", C.c_uint32), ("leafSize", C.c_uint32), ("nodeCount", C.c_uint32),
+                ("levels", C.c_uint32), ("depths", C.c_uint32), ("stackBound", C.c_uint32), ("reserved", C.c_uint32),
+                ("stageMs", C.c_float * HIERARCHY_BUILD_STAGES), ("totalMs", C.c_float), ("reserved2", C.c_uint32)]
+
+
 # ---- keyframe animation (prosper_pt_set_animations / prosper_pt_animate) ----
 ANIMATION_NONE = 0xFFFFFFFF
 NODE_HAS_TRANSLATION, NODE_HAS_ROTATION, NODE_HAS_SCALE, NODE_DIRECTIONAL_LIGHT, NODE_CAMERA = 1, 2, 4, 8, 16

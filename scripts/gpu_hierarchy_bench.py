@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""The GPU hierarchy build (prosper_pt_build_hierarchy_gpu) beside the host builder, on S-sponza-class (C3),
+C4 and the FlightHelmet fixture: device milliseconds per stage (events) and the wall time of the call; the host's
+prosper_pt_rebuild_hierarchy on the same state with every instance moved, interleaved with it; the frame time at
+1920x1080 x 8 spp on one chain under the host tree and under the GPU tree at leaf sizes 1, 2 and 4, interleaved; and the
+drift scenario of scripts/drift_rebuild_bench.py with either builder selected.  One JSON object on stdout
+(profiles/f24_gpu_hierarchy_bench.json); run on the GPU box.
+
+    python scripts/gpu_hierarchy_bench.py [--scenes c3,c4,helmet] [--repeats 5] [--no-drift]"""
+import argparse
+import copy
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from prosper_amd import capi, flight_helmet, scenes, structs as S  # noqa: E402
+from prosper_amd.rt_reference import Camera  # noqa: E402
+from prosper_amd.world import translate  # noqa: E402
+
+hip = ctypes.CDLL("libamdhip64.so")
+W, H, SPP = 1920, 1080, 8
+FLAGS = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_IBL | S.PC_FLAG_SKIP_HISTORY
+
+
+def moved(base, offset, which=None):
+    world = copy.copy(base)
+    world._frozen = None
+    world.model_instances = list(base.model_instances)
+    for i in (range(len(world.model_instances)) if which is None else which):
+        model, m = world.model_instances[i]
+        world.model_instances[i] = (model, translate(offset) @ m)
+    world.freeze()
+    return world
+
+
+def wall_ms(call):
+    hip.hipDeviceSynchronize()
+    t0 = time.perf_counter()
+    call()
+    hip.hipDeviceSynchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def frame_ms(ctx, cam, focal, ibl, repeats):
+    """(device ms from events, wall ms) of one 8-spp frame: the median of `repeats` after one warm-up."""
+    start, stop = ctypes.c_void_p(), ctypes.c_void_p()
+    hip.hipEventCreate(ctypes.byref(start))
+    hip.hipEventCreate(ctypes.byref(stop))
+    pc = S.ReferencePC(0, FLAGS if ibl else FLAGS & ~S.PC_FLAG_IBL, 1, 1e-5, 1.0, focal, 3, 4)
+    device, wall = [], []
+    for k in range(repeats + 1):
+        hip.hipDeviceSynchronize()
+        t0 = time.perf_counter()
+        hip.hipEventRecord(start, None)
+        ctx.render(pc, cam, W, H, frames=SPP)
+        hip.hipEventRecord(stop, None)
+        hip.hipEventSynchronize(stop)
+        ms = ctypes.c_float()
+        hip.hipEventElapsedTime(ctypes.byref(ms), start, stop)
+        if k:
+            device.append(ms.value)
+            wall.append((time.perf_counter() - t0) * 1e3)
+    hip.hipEventDestroy(start)
+    hip.hipEventDestroy(stop)
+    return statistics.median(device), statistics.median(wall)
+
+
+def bench_scene(name, base, repeats):
+    out = {"triangles": base.triangle_count(), "instances": len(base.model_instances)}
+    ibl = base.skybox is not None
+    cam, focal = Camera.from_world(base, W, H).update_buffer()
+    ctx = capi.Context(0, flags=S.CREATE_SINGLE_CHAIN)
+    ctx.upload_scene(base)
+    out["host_upload_bvh_ms"] = ctx.scene_stats().bvhBuildSeconds * 1e3
+    # ---- builds: every instance moved before each one, host and GPU interleaved ----
+    poses = [moved(base, (0.01 * (k + 1), 0.0, 0.0)) for k in range(2)]
+    host_wall, gpu_wall, gpu_total, stages = [], [], [], []
+    for k in range(repeats + 1):
+        ctx.update_transforms(poses[k % 2])
+        ms = wall_ms(ctx.rebuild_hierarchy)
+        ctx.update_transforms(poses[(k + 1) % 2])
+        g = wall_ms(ctx.build_hierarchy_gpu)
+        info = ctx.hierarchy_build_info()
+        if k:  # (the first round allocates)
+            host_wall.append(ms)
+            gpu_wall.append(g)
+            gpu_total.append(info.totalMs)
+            stages.append(list(info.stageMs))
+    out["host_rebuild_all_moved_wall_ms"] = {"median": statistics.median(host_wall), "runs": host_wall}
+    out["gpu_build_wall_ms"] = {"median": statistics.median(gpu_wall), "runs": gpu_wall}
+    out["gpu_build_device_ms"] = {"median": statistics.median(gpu_total), "runs": gpu_total}
+    out["gpu_build_stage_ms"] = {n: statistics.median(s[i] for s in stages) for i, n in enumerate(S.HIERARCHY_BUILD_STAGE_NAMES)}
+    # ---- frame time under each tree, interleaved ----
+    ctx.update_transforms(base)
+    frames = {"host": [], "gpu_leaf1": [], "gpu_leaf2": [], "gpu_leaf4": []}
+    trees = {}
+    for rnd in range(3):
+        for tree in frames:
+            if tree == "host":
+                capi.debug(leafSize=None)
+                ctx.rebuild_hierarchy()
+            else:
+                capi.debug(leafSize=int(tree[-1]))
+                ctx.build_hierarchy_gpu()
+            info = ctx.hierarchy_build_info()
+            trees[tree] = {"nodes": info.nodeCount, "levels": info.levels, "stackBound": info.stackBound}
+            frames[tree].append(frame_ms(ctx, cam, focal, ibl, repeats))
+    capi.debug(leafSize=None)
+    out["frame_1920x1080x8spp_one_chain"] = {
+        tree: dict(trees[tree], device_ms=statistics.median(d for d, _ in runs), wall_ms=statistics.median(w for _, w in runs),
+                   device_ms_runs=[d for d, _ in runs]) for tree, runs in frames.items()}
+    host = out["frame_1920x1080x8spp_one_chain"]["host"]["device_ms"]
+    for tree in frames:
+        out["frame_1920x1080x8spp_one_chain"][tree]["ratio_to_host"] = out["frame_1920x1080x8spp_one_chain"][tree]["device_ms"] / host
+    ctx.close()
+    return out
+
+
+def drift(builder, steps=240, threshold=1.3):
+    """scripts/drift_rebuild_bench.py's loop with `builder` selected: 1-spp frames, three in flight, three instances moved
+    every frame.  The measure is read when the host has waited for the device anyway (every third frame)."""
+    base = scenes.sponza_class()
+    cam, focal = Camera.from_world(base, W, H).update_buffer()
+    ctx = capi.Context(0)
+    ctx.upload_scene(base)
+    ctx.set_hierarchy_builder(builder)
+    poses = [moved(base, (0.12 * k, 0.016 * k, 0.032 * k), which=(3, 5, 7)) for k in range(steps)]
+    times, update_ms, above = [], [], 0
+    t0 = time.perf_counter()
+    for k, world in enumerate(poses):
+        t1 = time.perf_counter()
+        ctx.update_transforms(world)
+        update_ms.append((time.perf_counter() - t1) * 1e3)
+        ctx.render(S.ReferencePC(0, FLAGS, 1 + k, 1e-5, 1.0, focal, 3, 4), cam, W, H, frames=1, flags=S.RENDER_PIPELINED)
+        if k % 3 == 2:
+            hip.hipDeviceSynchronize()
+            times.append((time.perf_counter() - t0) * 1e3 / 3)
+            if ctx.hierarchy_state().costRatio > threshold:
+                above += 3
+            t0 = time.perf_counter()
+    hip.hipDeviceSynchronize()
+    ctx.finish_mesh_updates()
+    hs = ctx.hierarchy_state()
+    out = {"frames": steps, "median_frame_ms": statistics.median(times), "worst_frame_ms": max(times),
+           "worst_update_call_ms": max(update_ms), "median_update_call_ms": statistics.median(update_ms),
+           "frames_above_cost_threshold": above, "rebuilds": hs.rebuilds, "refits": hs.refits,
+           "geometryInstalls": hs.geometryInstalls, "cost_ratio_at_end": hs.costRatio}
+    ctx.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="c3,c4,helmet")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--no-drift", action="store_true")
+    args = ap.parse_args()
+    make = {"c3": scenes.sponza_class, "c4": lambda: scenes.sponza_class(lights=True, foliage=True),
+            "helmet": lambda: flight_helmet.load_fixture()}
+    result = {"what": "GPU hierarchy build (linear BVH) beside the host builder; frames 1920x1080 x 8 spp, one chain, all bounces",
+              "scenes": {}}
+    for name in args.scenes.split(","):
+        result["scenes"][name] = bench_scene(name, make[name](), args.repeats)
+        print("%s done" % name, file=sys.stderr)
+    if not args.no_drift:
+        result["drift_scenario"] = {"host_builder": drift(S.BUILDER_HOST), "gpu_builder": drift(S.BUILDER_GPU)}
+    print(json.dumps(result, indent=1))
+
+
+if __name__ == "__main__":
+    main()

@@ -157,6 +157,8 @@ def main():
                     help="with --raster: the G-buffer's draw type (MeshletID and PrimitiveID are the mesh shader's), shaded as that debug view")
     ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
+    ap.add_argument("--gpu-hierarchy", action="store_true",
+                    help="build the hierarchy once more on the GPU after the upload (and after --time's pose): a linear BVH, the same image")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     ap.add_argument("--build-texture-cache", action="store_true",
                     help="compress every image whose prosper_cache file is missing or stale (GPU BC7 encoder) before loading")
@@ -222,6 +224,12 @@ def main():
             pose.animatedNodeCount, pose.nodeCount, pose.endTimeS, args.time), file=sys.stderr)
         if pose.cameraValid and not args.eye and not args.target:
             world.camera.update(eye=tuple(pose.eye), target=tuple(pose.target), up=tuple(pose.up))
+    if args.gpu_hierarchy:
+        ctx.build_hierarchy_gpu()  # (flushes the pose --time staged first)
+        info = ctx.hierarchy_build_info()
+        print("GPU hierarchy: %d nodes, %d levels, stack bound %d, leaves of at most %d, %.3f ms on the device (%s)" % (
+            info.nodeCount, info.levels, info.stackBound, info.leafSize, info.totalMs,
+            ", ".join("%s %.3f" % (n, ms) for n, ms in zip(S.HIERARCHY_BUILD_STAGE_NAMES, info.stageMs))), file=sys.stderr)
     hcam = Camera.from_world(world, w, h)
     if args.dof:
         c = world.camera
