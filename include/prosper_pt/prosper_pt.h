@@ -336,6 +336,10 @@ const char *prosper_pt_last_error(void);
 uint32_t prosper_pt_abi_version(void);
 /* Always 0: the measured-slower kernel variants this reported on were removed from the library. */
 uint32_t prosper_pt_has_experiments(void);
+/* Test hook (needs no device): the terms the wavefront kernels divide by `divisor` with - a tile count fixed for a launch.
+ * With t = the high 32 bits of *mul x n:  n / divisor = (t + ((n - t) >> (*shifts & 255))) >> (*shifts >> 8)  for every
+ * 32-bit n.  A divisor of 0 gets the terms of 1. */
+void prosper_pt_debug_magic_divisor(uint32_t divisor, uint32_t *mul, uint32_t *shifts);
 void prosper_pt_debug_options_default(prosper_pt_debug_options *out);
 int prosper_pt_set_debug_options(prosper_pt_ctx *ctx, const prosper_pt_debug_options *options);
 int prosper_pt_get_debug_options(prosper_pt_ctx *ctx, prosper_pt_debug_options *out);

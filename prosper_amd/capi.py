@@ -47,6 +47,8 @@ def lib():
     L.prosper_pt_last_error.restype = C.c_char_p
     L.prosper_pt_abi_version.restype = u32
     L.prosper_pt_has_experiments.restype = u32
+    L.prosper_pt_debug_magic_divisor.argtypes = [u32, C.POINTER(u32), C.POINTER(u32)]
+    L.prosper_pt_debug_magic_divisor.restype = None
     L.prosper_pt_debug_options_default.argtypes = [C.POINTER(S.DebugOptions)]
     L.prosper_pt_debug_options_default.restype = None
     L.prosper_pt_set_debug_options.argtypes = [vp, C.POINTER(S.DebugOptions)]
@@ -467,6 +469,14 @@ def bloom_fft_plan(width, height, resolution_scale=0):
     plan = S.BloomFftPlan()
     _check(lib().prosper_pt_bloom_fft_plan(width, height, resolution_scale, C.byref(plan)))
     return plan
+
+
+def magic_divisor(divisor):
+    """prosper_pt_debug_magic_divisor: (mul, sh1, sh2) with n // divisor == (t + ((n - t) >> sh1)) >> sh2, t = (mul * n) >> 32,
+    for every 32-bit n - the terms the wavefront kernels divide by a launch's tile counts with.  Needs no device."""
+    mul, shifts = C.c_uint32(), C.c_uint32()
+    lib().prosper_pt_debug_magic_divisor(divisor, C.byref(mul), C.byref(shifts))
+    return mul.value, shifts.value & 0xFF, shifts.value >> 8
 
 
 def has_experiments():

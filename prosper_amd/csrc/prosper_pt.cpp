@@ -578,6 +578,8 @@ int ensure_wavefront_workspace(
         if (bandSegments == 0) return fail(PROSPER_PT_ERR_UNSUPPORTED, "banded batches: no segment layout covers the image");
     }
     const uint64_t padded = nSeg * segLen;
+    // (the kernels address a record as a 32-bit byte offset from its array: 16 B x 2^28 slots)
+    if (padded >= (1ull << 28)) return fail(PROSPER_PT_ERR_UNSUPPORTED, "wavefront workspace beyond 2^28 path slots");
     // The arrays, each rounded up to 256 B: laid out from 0 to size the block, then over the block.
     // per slot: 2 x (3 x 16 + 8) B ping-pong state, camera slot 4, hit 16 + idx 4, shadow 48, colour 16; + 3 counters per segment
     WavefrontBuffers w = {};
@@ -622,6 +624,9 @@ int ensure_wavefront_workspace(
     w.tilesY = tilesY;
     w.bandSegments = bandSegments;
     for (uint32_t x = 0; x < 9u; ++x) w.bandTile[x] = bandTile[x];
+    w.divTilesX = make_magic_div(tilesX);
+    w.divTiles = make_magic_div(tilesX * tilesY);
+    for (uint32_t x = 0; x < 8u; ++x) w.divBandTiles[x] = make_magic_div(bandTile[x + 1u] - bandTile[x]);
     *out = w;
     return PROSPER_PT_OK;
 }
@@ -748,6 +753,13 @@ const char *prosper_pt_last_error(void) { return ppt::g_lastErrorStorage.c_str()
 uint32_t prosper_pt_abi_version(void) { return PROSPER_PT_ABI_VERSION; }
 
 uint32_t prosper_pt_has_experiments(void) { return 0u; }
+
+void prosper_pt_debug_magic_divisor(uint32_t divisor, uint32_t *mul, uint32_t *shifts)
+{
+    const ppt::MagicDiv m = ppt::make_magic_div(divisor);
+    if (mul) *mul = m.mul;
+    if (shifts) *shifts = m.shifts;
+}
 
 void prosper_pt_debug_options_default(prosper_pt_debug_options *out)
 {

@@ -1023,14 +1023,18 @@ PPT_D float schlick_trowbridge_reitz(float NoL, float NoV, float alpha)
     return gl * gv;
 }
 // brdf.glsl:46-58
-PPT_D f3 cook_torrance_brdf(float NoL, float NoV, float NoH, float VoH, f3 f0, float roughness)
+// (`alpha` = roughness * roughness)
+PPT_D f3 cook_torrance_brdf_alpha(float NoL, float NoV, float NoH, float VoH, f3 f0, float alpha)
 {
-    const float alpha = roughness * roughness;
     const float D = trowbridge_reitz(NoH, alpha);
     const f3 F = schlick_fresnel(VoH, f0);
     const float G = schlick_trowbridge_reitz(NoL, NoV, alpha);
     const float denom = __builtin_fmaf(4.0f * NoL, NoV, 0.0001f);
     return ((F * D) * G) / denom;
+}
+PPT_D f3 cook_torrance_brdf(float NoL, float NoV, float NoH, float VoH, f3 f0, float roughness)
+{
+    return cook_torrance_brdf_alpha(NoL, NoV, NoH, VoH, f0, roughness * roughness);
 }
 // brdf.glsl:60-64
 PPT_D f3 fresnel_zero(const Surface &sf)
@@ -1042,19 +1046,32 @@ PPT_D f3 fresnel_zero(const Surface &sf)
 // brdf.glsl:9
 PPT_D f3 lambert_brdf(f3 c) { return c * kInvPi; }
 
+// What evalBRDFTimesNoL and importanceSampleBounce both derive from the material of a hit: a kernel that runs both for
+// a hit (wf_shade) works them out once and passes them to the two.
+struct BrdfTerms
+{
+    f3 f0;       // fresnel_zero(sf)
+    float alpha; // roughness * roughness
+};
+PPT_D BrdfTerms brdf_terms(const Surface &sf)
+{
+    return BrdfTerms{fresnel_zero(sf), sf.material.roughness * sf.material.roughness};
+}
+
 // brdf.glsl:67-87
-PPT_D f3 eval_brdf_times_nol(f3 l, const Surface &sf)
+PPT_D f3 eval_brdf_times_nol(f3 l, const Surface &sf, const BrdfTerms &bt)
 {
     const f3 h = normalize(sf.invViewRayWS + l);
     const float NoL = saturate(dot(sf.normalWS, l));
     const float NoH = saturate(dot(sf.normalWS, h));
     const float VoH = saturate(dot(sf.invViewRayWS, h));
-    const f3 f0 = fresnel_zero(sf);
+    const f3 f0 = bt.f0;
     const float m = sf.material.metallic;
     const f3 cdiff = f3{mix(sf.material.albedo.x * 0.96f, 0.0f, m), mix(sf.material.albedo.y * 0.96f, 0.0f, m),
                         mix(sf.material.albedo.z * 0.96f, 0.0f, m)};
-    return (lambert_brdf(cdiff) + cook_torrance_brdf(NoL, sf.NoV, NoH, VoH, f0, sf.material.roughness)) * NoL;
+    return (lambert_brdf(cdiff) + cook_torrance_brdf_alpha(NoL, sf.NoV, NoH, VoH, f0, bt.alpha)) * NoL;
 }
+PPT_D f3 eval_brdf_times_nol(f3 l, const Surface &sf) { return eval_brdf_times_nol(l, sf, brdf_terms(sf)); }
 
 // ------------------------------------------------------------------------------------------
 // F17 sampling — common/sampling.glsl
@@ -1185,13 +1202,32 @@ PPT_D void eval_spot_light(const prosper_SpotLight &light, f3 surfacePos, f3 &l,
     irradiance = (rad * att) / d2;
 }
 
+// The direction towards the sun, lighting.glsl:64: -normalize(direction).  It is the same for every hit of a launch, so a
+// kernel that shades many hits per lane works it out once per workgroup (sun_direction below, by one lane, into LDS) and
+// hands sample_light a SunInLds; SunPerHit is the expression where it stood.  Same operations on the same operands,
+// on the same device: same bits.
+PPT_D f3 sun_direction(const prosper_DirectionalLightParameters &sun)
+{
+    return -normalize(f3{sun.direction.x, sun.direction.y, sun.direction.z});
+}
+struct SunPerHit
+{
+    PPT_D f3 operator()(const prosper_DirectionalLightParameters &sun) const { return sun_direction(sun); }
+};
+struct SunInLds
+{
+    __attribute__((address_space(3))) const float *l; // sun_direction(): x, y, z
+    PPT_D f3 operator()(const prosper_DirectionalLightParameters &) const { return f3{l[0], l[1], l[2]}; }
+};
+
 // lighting.glsl:58-89; returns true when a spot light was picked
-PPT_D bool sample_light(const DeviceScene &s, f3 surfacePos, uint32_t lightIndex, f3 &l, float &d, f3 &irradiance)
+template <class Sun = SunPerHit>
+PPT_D bool sample_light(const DeviceScene &s, f3 surfacePos, uint32_t lightIndex, f3 &l, float &d, f3 &irradiance, Sun sunL = {})
 {
     if (lightIndex == 0)
     {
         const prosper_DirectionalLightParameters sun = *s.directionalLight;
-        l = -normalize(f3{sun.direction.x, sun.direction.y, sun.direction.z});
+        l = sunL(sun);
         d = 100.0f;
         irradiance = f3{sun.irradiance.x, sun.irradiance.y, sun.irradiance.z};
         return false;
@@ -1346,7 +1382,14 @@ PPT_D float safe_rcp_dir(float d)
 // with a larger tolerance (slab_entry) can never cull a valid candidate.
 constexpr float kGuardPad = 1.52587890625e-05f;    // 2^-16
 constexpr float kGuardTol = 1.000003814697265625f; // 1 + 2^-18
-PPT_D bool box_guard(f3 o, f3 invd, f3 v0, f3 v1, f3 v2, float tt)
+// The padded box is a function of the three vertices alone: a kernel that keeps its triangles in LDS stores it beside
+// each triangle when it stages them (guard_box, once per triangle and workgroup) instead of rebuilding it for every
+// candidate; box_guard on the vertices is the two in a row - the same operations on the same operands, the same bits.
+struct GuardBox
+{
+    f3 lo, hi; // (min - pad, max + pad)
+};
+PPT_D GuardBox guard_box(f3 v0, f3 v1, f3 v2)
 {
     const float lox = fminf(fminf(v0.x, v1.x), v2.x), hix = fmaxf(fmaxf(v0.x, v1.x), v2.x);
     const float loy = fminf(fminf(v0.y, v1.y), v2.y), hiy = fmaxf(fmaxf(v0.y, v1.y), v2.y);
@@ -1355,13 +1398,18 @@ PPT_D bool box_guard(f3 o, f3 invd, f3 v0, f3 v1, f3 v2, float tt)
     const float my = fmaxf(fabs_(loy), fabs_(hiy));
     const float mz = fmaxf(fabs_(loz), fabs_(hiz));
     const float pad = fmaxf(fmaxf(mx, my), mz) * kGuardPad;
-    const float ax = ((lox - pad) - o.x) * invd.x, bx = ((hix + pad) - o.x) * invd.x;
-    const float ay = ((loy - pad) - o.y) * invd.y, by = ((hiy + pad) - o.y) * invd.y;
-    const float az = ((loz - pad) - o.z) * invd.z, bz = ((hiz + pad) - o.z) * invd.z;
+    return GuardBox{f3{lox - pad, loy - pad, loz - pad}, f3{hix + pad, hiy + pad, hiz + pad}};
+}
+PPT_D bool box_guard(f3 o, f3 invd, const GuardBox &g, float tt)
+{
+    const float ax = (g.lo.x - o.x) * invd.x, bx = (g.hi.x - o.x) * invd.x;
+    const float ay = (g.lo.y - o.y) * invd.y, by = (g.hi.y - o.y) * invd.y;
+    const float az = (g.lo.z - o.z) * invd.z, bz = (g.hi.z - o.z) * invd.z;
     const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
     const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     return tn <= tt * kGuardTol && tt <= tf * kGuardTol;
 }
+PPT_D bool box_guard(f3 o, f3 invd, f3 v0, f3 v1, f3 v2, float tt) { return box_guard(o, invd, guard_box(v0, v1, v2), tt); }
 
 // The triangle test in two halves, so that a leaf of two triangles can share the second one between
 // them (pt_trace_stream.hpp): first the edge functions of hit contract (1), then distance, range and
@@ -1385,9 +1433,12 @@ PPT_D EdgeFunctions edge_functions(f3 o, f3 d, f3 v0, f3 v1, f3 v2)
     e.pass = !mixed && e.det != 0.0f;
     return e;
 }
-// `invd` = safe_rcp_dir of each component of d (the traversal keeps it per ray)
-PPT_D bool finish_triangle(
-    const EdgeFunctions &e, f3 o, f3 d, f3 invd, f3 v0, f3 v1, f3 v2, float tMin, float tMax, float &t, float &bu, float &bv)
+// `invd` = safe_rcp_dir of each component of d (the traversal keeps it per ray); `guard()` gives the triangle's guard box
+// - worked out from the vertices, or the stored one of an LDS-resident scene - and is asked only once the range test passed
+template <class Guard>
+PPT_D bool finish_triangle_guarded(
+    const EdgeFunctions &e, f3 o, f3 d, f3 invd, f3 v0, f3 v1, f3 v2, float tMin, float tMax, float &t, float &bu, float &bv,
+    Guard &&guard)
 {
     // t = projection of the barycentric point on the (unit) direction: (U*(A.d) + V*(B.d) + W*(C.d)) / det.
     // Well conditioned for grazing rays (the plane equation is not).
@@ -1395,11 +1446,16 @@ PPT_D bool finish_triangle(
     const float tt =
         __builtin_fmaf(e.W, dot(v2 - o, d), __builtin_fmaf(e.V, dot(v1 - o, d), e.U * dot(v0 - o, d))) * inv;
     if (!(tt > tMin && tt < tMax)) return false;
-    if (!box_guard(o, invd, v0, v1, v2, tt)) return false;
+    if (!box_guard(o, invd, guard(), tt)) return false;
     t = tt;
     bu = e.V * inv;
     bv = e.W * inv;
     return true;
+}
+PPT_D bool finish_triangle(
+    const EdgeFunctions &e, f3 o, f3 d, f3 invd, f3 v0, f3 v1, f3 v2, float tMin, float tMax, float &t, float &bu, float &bv)
+{
+    return finish_triangle_guarded(e, o, d, invd, v0, v1, v2, tMin, tMax, t, bu, bv, [&]() { return guard_box(v0, v1, v2); });
 }
 PPT_D bool intersect_triangle(
     f3 o, f3 d, f3 invd, f3 v0, f3 v1, f3 v2, float tMin, float tMax, float &t, float &bu, float &bv)
@@ -1575,8 +1631,9 @@ PPT_D bool any_hit(
 // Where the traversal reads BVH nodes and world triangles from.  GlobalGeom: the HBM arrays (through
 // L1/L2).  LdsGeom: a copy a workgroup staged in LDS — for scenes of a few KB (a Cornell box) every
 // node fetch then costs an LDS access (~64 cycles) instead of a vector-memory round trip (~200+),
-// which is what the latency-bound traversal of tiny scenes is made of.  Node stride 80 B and
-// triangle stride 48 B keep 16-byte reads of different records spread over 16 bank groups.
+// which is what the latency-bound traversal of tiny scenes is made of.  Node stride 80 B (144 B for the
+// fp32 image) and triangle stride 80 B - the triangle and its guard box, kLdsTriStride - keep 16-byte
+// reads of different records spread over the bank groups.
 struct TriangleData
 {
     float4 a, b, c;
@@ -1743,6 +1800,7 @@ PPT_D void intersect_node4(const NodeData &n, f3 o, const RaySlabs &rs, float tM
 
 struct GlobalGeom
 {
+    static constexpr bool kStoredGuard = false; // the guard box is rebuilt from the vertices per candidate
     const BvhNode *nodes;
     const WorldTriangle *triangles;
     PPT_D NodeData node(int32_t i) const
@@ -1770,10 +1828,19 @@ struct GlobalGeom
 // (256 B/clk per CU) instead of 5 x 16 B, ~15 % fewer issue cycles per node visit.  The 144-byte stride spreads the same
 // float4 of neighbouring nodes over different banks.
 constexpr uint32_t kLdsNodeStride = 9; // float4s per node in LDS (144 B)
+// A triangle in LDS: the three float4s of its WorldTriangle, then its guard box (guard_box: lo - pad, hi + pad; .w unused)
+constexpr uint32_t kLdsTriStride = 5; // float4s per triangle in LDS (80 B)
+PPT_D GuardBox lds_guard_box(const float4 *triangles, uint32_t i)
+{
+    const float4 *tp = triangles + i * kLdsTriStride;
+    const float4 lo = tp[3], hi = tp[4];
+    return GuardBox{f3{lo.x, lo.y, lo.z}, f3{hi.x, hi.y, hi.z}};
+}
 struct LdsGeom
 {
+    static constexpr bool kStoredGuard = true;
     const float4 *nodes;     // LDS: kLdsNodeStride float4s per node (see above)
-    const float4 *triangles; // LDS
+    const float4 *triangles; // LDS: kLdsTriStride float4s per triangle
     template <bool SORTED>
     PPT_D void test_node(int32_t i, f3 o, const RaySlabs &rs, float tMin, float tMax, float e[4], int32_t ref[4]) const
     {
@@ -1804,17 +1871,19 @@ struct LdsGeom
     }
     PPT_D TriangleData tri(uint32_t i) const
     {
-        const float4 *tp = triangles + i * 3u;
+        const float4 *tp = triangles + i * kLdsTriStride;
         return TriangleData{tp[0], tp[1], tp[2]};
     }
+    PPT_D GuardBox guard(uint32_t i) const { return lds_guard_box(triangles, i); }
 };
 // The nodes as they are in HBM (80 B) in LDS: what the camera-ray kernel uses - its lockstep loop holds a whole node of
 // the fp32 image in registers at once and spills at its 96-VGPR budget with it (9 dwords), the stream scheduler's does not.
 constexpr uint32_t kLdsNodeStrideHalf = 5; // float4s per node (80 B)
 struct LdsGeomHalf
 {
+    static constexpr bool kStoredGuard = true;
     const float4 *nodes;     // LDS
-    const float4 *triangles; // LDS
+    const float4 *triangles; // LDS: kLdsTriStride float4s per triangle
     PPT_D NodeData node(int32_t i) const
     {
         const uint4 *np = reinterpret_cast<const uint4 *>(nodes + (uint32_t)i * kLdsNodeStrideHalf);
@@ -1827,11 +1896,12 @@ struct LdsGeomHalf
     }
     PPT_D TriangleData tri(uint32_t i) const
     {
-        const float4 *tp = triangles + i * 3u;
+        const float4 *tp = triangles + i * kLdsTriStride;
         return TriangleData{tp[0], tp[1], tp[2]};
     }
+    PPT_D GuardBox guard(uint32_t i) const { return lds_guard_box(triangles, i); }
 };
-// LDS budget of a staged scene (float4s): nodes * kLdsNodeStride + triangles * 3 must fit
+// LDS budget of a staged scene (float4s): nodes * kLdsNodeStride + triangles * kLdsTriStride must fit
 constexpr uint32_t kLdsSceneFloat4s = 768; // 12 KB
 
 // Any-hit rays (shadow(): terminate on the first accepted hit) take the children a node test reports in storage
@@ -1954,8 +2024,17 @@ PPT_D bool trace_in(
                     cnt.shortIndexTriangleTests += (__builtin_bit_cast(uint32_t, c.w) & kTriFlagShortIndices) ? 1u : 0u;
                 }
                 float t, bu, bv;
-                if (!intersect_triangle(
-                        o, d, invd, f3{a.x, a.y, a.z}, f3{b.x, b.y, b.z}, f3{c.x, c.y, c.z}, tMin, tMaxIn, t, bu, bv))
+                if constexpr (Geom::kStoredGuard)
+                {
+                    // intersect_triangle with the stored guard box, read only for a candidate inside the ray's range
+                    const f3 v0 = f3{a.x, a.y, a.z}, v1 = f3{b.x, b.y, b.z}, v2 = f3{c.x, c.y, c.z};
+                    const EdgeFunctions e = edge_functions(o, d, v0, v1, v2);
+                    if (!e.pass) continue;
+                    if (!finish_triangle_guarded(e, o, d, invd, v0, v1, v2, tMin, tMaxIn, t, bu, bv, [&]() { return g.guard(first + i); }))
+                        continue;
+                }
+                else if (!intersect_triangle(
+                             o, d, invd, f3{a.x, a.y, a.z}, f3{b.x, b.y, b.z}, f3{c.x, c.y, c.z}, tMin, tMaxIn, t, bu, bv))
                     continue;
                 const uint32_t di = __builtin_bit_cast(uint32_t, a.w);
                 const uint32_t prim = __builtin_bit_cast(uint32_t, b.w);
@@ -2146,14 +2225,14 @@ PPT_D void add_bounce(uint32_t flags, f3 &acc, f3 color, uint32_t bounce)
 }
 
 // main.rgen:90-144
-PPT_D void importance_sample_bounce(const Surface &sf, Rng &rng, f3 &throughput, f3 &rd)
+PPT_D void importance_sample_bounce(const Surface &sf, const BrdfTerms &bt, Rng &rng, f3 &throughput, f3 &rd)
 {
     const bool specularOnly = sf.material.metallic > 0.999f;
     const float specularWeight = specularOnly ? 1.0f : 0.5f;
     const float diffuseWeight = 1.0f - specularWeight;
     const Onb basis = orthonormal_basis(sf.normalWS);
     const f3 vInBasis = basis.to_local(sf.invViewRayWS);
-    const float alpha = sf.material.roughness * sf.material.roughness;
+    const float alpha = bt.alpha;
     const bool pickDiffuse = rng.rnd01() < diffuseWeight;
     const f2 u = rng.rnd2d01();
     float sinPhi, cosPhi; // phi = 2 pi u.y in cosineSampleHemisphere and in sampleVisibleTrowbridgeReitz alike
@@ -2177,12 +2256,17 @@ PPT_D void importance_sample_bounce(const Surface &sf, Rng &rng, f3 &throughput,
         const f3 h = normalize(sf.invViewRayWS + rd);
         const float NoH = saturate(dot(sf.normalWS, h));
         const float VoH = saturate(dot(sf.invViewRayWS, h));
-        brdf = cook_torrance_brdf(NoL, sf.NoV, NoH, VoH, fresnel_zero(sf), sf.material.roughness);
+        brdf = cook_torrance_brdf_alpha(NoL, sf.NoV, NoH, VoH, bt.f0, alpha);
         pdf = visible_trowbridge_reitz_pdf(vInBasis, basis.to_local(rd), alpha);
         pdf *= specularWeight;
     }
     const f3 w = (brdf * NoL) / pdf;
     throughput = f3{throughput.x * fmax_(w.x, 0.0f), throughput.y * fmax_(w.y, 0.0f), throughput.z * fmax_(w.z, 0.0f)};
+}
+
+PPT_D void importance_sample_bounce(const Surface &sf, Rng &rng, f3 &throughput, f3 &rd)
+{
+    importance_sample_bounce(sf, brdf_terms(sf), rng, throughput, rd);
 }
 
 // A path whose throughput is exactly (0, 0, 0) after importanceSampleBounce ends there (arithmetic contract,
@@ -2194,16 +2278,16 @@ PPT_D bool throughput_is_zero(f3 t) { return t.x == 0.0f && t.y == 0.0f && t.z =
 // First half of evaluateDirectLighting (main.rgen:195-214): pick a light, evaluate it.  Returns
 // true when a shadow ray towards `l` of length `d` must be traced; `contribution` is then
 // throughput * irradiance * lightCount * BRDF (everything but the visibility term).
-template <bool COUNT>
+template <bool COUNT, class Sun = SunPerHit>
 PPT_D bool prepare_direct_lighting(
     const DeviceScene &s, const Surface &sf, f3 throughput, Rng &rng, f3 &l, float &d, f3 &irradiance,
-    LaneCounters &cnt)
+    LaneCounters &cnt, Sun sunL = {})
 {
     if (sf.material.alpha == 0.0f) return false;
     const uint32_t lightCount = 1u + s.pointLightCount + s.spotLightCount;
     uint32_t lightIndex = f2uint(rng.rnd01() * (float)lightCount);
     if (lightIndex > lightCount - 1u) lightIndex = lightCount - 1u;
-    const bool spot = sample_light(s, sf.positionWS, lightIndex, l, d, irradiance);
+    const bool spot = sample_light(s, sf.positionWS, lightIndex, l, d, irradiance, sunL);
     if constexpr (COUNT)
     {
         if (spot)

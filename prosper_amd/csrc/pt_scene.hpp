@@ -234,6 +234,26 @@ struct RenderParams
     uint32_t traceDeadPaths;
 };
 
+// Division of a 32-bit dividend by a divisor fixed for a launch, as a multiplication (Granlund & Montgomery's round-up
+// method): with l = ceil(log2 d) and mul = floor(2^32 (2^l - d) / d) + 1 - the 33-bit multiplier less its top bit -
+//     t = mul_hi(mul, n);   n / d = (t + ((n - t) >> sh1)) >> sh2        sh1 = min(l, 1), sh2 = max(l, 1) - 1
+// for EVERY n below 2^32: five integer instructions instead of the ~28 of a 32-bit division.  The host makes the terms
+// (make_magic_div), the kernels apply them (pt_wavefront.hip magic_div).  A divisor of 0 gets the terms of 1.
+struct MagicDiv
+{
+    uint32_t mul;
+    uint32_t shifts; // sh1 | sh2 << 8
+};
+inline MagicDiv make_magic_div(uint32_t d)
+{
+    if (d == 0u) d = 1u;
+    uint32_t l = 0;
+    while (l < 32u && (1ull << l) < d) ++l;
+    const uint64_t mul = (((1ull << l) - d) << 32) / d + 1u;
+    const uint32_t sh1 = l < 1u ? l : 1u, sh2 = l > 1u ? l - 1u : 0u;
+    return MagicDiv{(uint32_t)mul, sh1 | (sh2 << 8)};
+}
+
 // Workspace of the wavefront pipeline (pt_wavefront.hip).  Paths live in fixed-length SEGMENTS of
 // `segLen` slots, one segment per wave; every stage compacts its survivors to the front of the
 // wave's own segment with ballot/popcount, so there is no global queue counter and no atomic.
@@ -267,6 +287,11 @@ struct WavefrontBuffers
     // bandSegments == 0: batches strided over the whole image.
     uint32_t bandSegments;
     uint32_t bandTile[9];
+    // what the kernels divide by per lane (decode_slot, batch_lane), as multiplications: tilesX, tilesX * tilesY and the
+    // tile count of each band
+    MagicDiv divTilesX;
+    MagicDiv divTiles;
+    MagicDiv divBandTiles[8];
     uint32_t groupBase;  // this launch covers segment groups [groupBase, groupBase + groupCount)
     uint32_t groupCount; // (a group = the 4 segments of one workgroup)
 };

@@ -49,6 +49,13 @@ namespace ppt
 
 PPT_D f3 xyz3(float4 v) { return f3{v.x, v.y, v.z}; }
 
+// How many lanes below this one are set in a wave mask: popcount(mask & ((1 << lane) - 1)) as the two v_mbcnt, with no
+// per-lane 64-bit mask to build or keep.
+PPT_D uint32_t lanes_below(unsigned long long mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 enum : uint32_t
 {
     kLaneIdle = 0,
@@ -65,23 +72,25 @@ struct StreamRay
     uint32_t seed;
 };
 
-// fetch(i) -> StreamRay for stream position i (called by the lanes that take a new ray);
+// `tMin`: where every ray of the stream starts (one value for the stream: a scalar, not a register per lane).
+// fetch(i) -> StreamRay for stream position i (called by the lanes that take a new ray; its tMin is not read);
 // commit(pred, i, found, hit, dir) is called by ALL lanes in converged code; lanes with pred set
 // hand over the result of ray i with direction dir (so commit may compact with ballots).
-template <bool ANY, bool COUNT, class Geom, class Fetch, class Commit>
+// UNBOUNDED: every ray of the stream ends at infinity (closest-hit rays): the end is a constant, not a register per lane,
+// and fetch's tMax is not read.
+template <bool ANY, bool COUNT, bool UNBOUNDED, class Geom, class Fetch, class Commit>
 PPT_D void trace_stream(
-    const Geom &g, const DeviceScene &s, uint32_t n, const TraversalStack &stack, LaneCounters &cnt, Fetch &&fetch,
-    Commit &&commit)
+    const Geom &g, const DeviceScene &s, uint32_t n, float tMin, const TraversalStack &stack, LaneCounters &cnt,
+    Fetch &&fetch, Commit &&commit)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long below = (1ull << lane) - 1ull;
 
     uint32_t next = 0; // wave-uniform: next stream position to hand out
     uint32_t state = kLaneIdle;
     uint32_t ray = 0;
     f3 o = {}, d = {}, invd = {};
     RaySlabs rs = {};
-    float tMin = 0.0f, tMaxIn = 0.0f;
+    float tMaxLane = 0.0f;
     uint32_t seed = 0;
     int32_t node = 0, sp = 0;
     uint32_t triFirst = 0, triCount = 0;
@@ -205,11 +214,18 @@ PPT_D void trace_stream(
                 if (inTri)
                 {
                     TriangleData td = g.tri(triFirst);
+                    // (an LDS-resident scene keeps each triangle's guard box beside it: read with the triangle, and
+                    // carried along by the same select, so that the step's dependent chain has no second LDS read)
+                    GuardBox box = {};
+                    if constexpr (Geom::kStoredGuard) box = g.guard(triFirst);
                     EdgeFunctions e = edge_functions(o, d, xyz3(td.a), xyz3(td.b), xyz3(td.c));
                     uint32_t consumed = 1u;
                     if (anyTwo)
                     {
-                        const TriangleData td2 = g.tri(two ? triFirst + 1u : triFirst);
+                        const uint32_t second = two ? triFirst + 1u : triFirst;
+                        const TriangleData td2 = g.tri(second);
+                        GuardBox box2 = {};
+                        if constexpr (Geom::kStoredGuard) box2 = g.guard(second);
                         EdgeFunctions e2 = edge_functions(o, d, xyz3(td2.a), xyz3(td2.b), xyz3(td2.c));
                         e2.pass = e2.pass && two;
                         if (two && !(e.pass && e2.pass)) consumed = 2u;
@@ -217,6 +233,7 @@ PPT_D void trace_stream(
                         {
                             td = td2;
                             e = e2;
+                            box = box2;
                         }
                     }
                     const float4 a = td.a, b = td.b, c4 = td.c;
@@ -229,8 +246,13 @@ PPT_D void trace_stream(
                             (__builtin_bit_cast(uint32_t, c4.w) & kTriFlagShortIndices) ? consumed : 0u;
                     }
                     float t, bu, bv;
-                    bool candidate =
-                        e.pass && finish_triangle(e, o, d, invd, xyz3(a), xyz3(b), xyz3(c4), tMin, tMaxIn, t, bu, bv);
+                    const float tMaxIn = UNBOUNDED ? kInf : tMaxLane;
+                    bool candidate = false;
+                    if constexpr (Geom::kStoredGuard)
+                        candidate = e.pass && finish_triangle_guarded(e, o, d, invd, xyz3(a), xyz3(b), xyz3(c4), tMin, tMaxIn, t,
+                                                                      bu, bv, [&]() { return box; });
+                    else
+                        candidate = e.pass && finish_triangle(e, o, d, invd, xyz3(a), xyz3(b), xyz3(c4), tMin, tMaxIn, t, bu, bv);
                     const uint32_t di = __builtin_bit_cast(uint32_t, a.w);
                     const uint32_t prim = __builtin_bit_cast(uint32_t, b.w);
                     const uint32_t flags = __builtin_bit_cast(uint32_t, c4.w);
@@ -278,7 +300,7 @@ PPT_D void trace_stream(
             commit(state == kLaneFinished, ray, hit.drawInstance != kMissIndex, hit, d);
             if (state == kLaneFinished) state = kLaneIdle;
             const unsigned long long mIdle = __ballot(state == kLaneIdle);
-            const uint32_t rank = (uint32_t)__builtin_popcountll(mIdle & below);
+            const uint32_t rank = lanes_below(mIdle);
             const uint32_t idx = next + rank;
             if (state == kLaneIdle && idx < n)
             {
@@ -286,8 +308,8 @@ PPT_D void trace_stream(
                 const StreamRay r = fetch(idx);
                 o = r.o;
                 d = r.d;
-                tMin = r.tMin;
-                tMaxIn = r.tMax;
+                tMaxLane = r.tMax;
+                const float tMaxIn = UNBOUNDED ? kInf : tMaxLane;
                 seed = r.seed;
                 invd = f3{safe_rcp_dir(d.x), safe_rcp_dir(d.y), safe_rcp_dir(d.z)};
                 rs = make_ray_slabs(invd);

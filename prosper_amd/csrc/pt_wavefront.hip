@@ -54,12 +54,20 @@ struct SegmentId
 // Workgroup -> 4 consecutive segments of this launch's group range; block ids are remapped so that each
 // XCD (blocks b, b+8, ...) works on one contiguous range of segments, i.e. one band of the image
 // (speed only).
+// SCALAR: the wave's index in its workgroup - the same in all its lanes - is read from the first lane, so that the
+// segment's number and base are scalars, and with them the part of every record address that they make up
+// (wf_generate_extend 1562 -> 1481 VALU instructions and 94 -> 90 VGPRs, wf_shade 3847 -> 3837 and 128 -> 126).  Not in
+// wf_trace: with scalar stream lengths the compiler duplicates the scheduler's loops there (2274 -> 2574 instructions)
+// and spills.
+template <bool SCALAR>
 __device__ __forceinline__ SegmentId my_segment(const WavefrontBuffers &w)
 {
     const uint32_t groups = w.groupCount;
     const uint32_t perXcd = (groups + 7u) / 8u;
     const uint32_t local = (blockIdx.x % 8u) * perXcd + (blockIdx.x / 8u);
-    const uint32_t seg = (w.groupBase + local) * 4u + (threadIdx.x >> 6);
+    uint32_t wave = threadIdx.x >> 6;
+    if constexpr (SCALAR) wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
+    const uint32_t seg = (w.groupBase + local) * 4u + wave;
     SegmentId id;
     id.seg = seg;
     id.base = seg * w.segLen;
@@ -74,7 +82,7 @@ __device__ __forceinline__ uint32_t wave_rank(bool pred, uint32_t &total)
 {
     const unsigned long long m = __ballot(pred);
     total = (uint32_t)__builtin_popcountll(m);
-    return (uint32_t)__builtin_popcountll(m & ((1ull << lane_id()) - 1ull));
+    return lanes_below(m);
 }
 
 __device__ __forceinline__ f3 xyz(float4 v) { return f3{v.x, v.y, v.z}; }
@@ -159,6 +167,24 @@ __device__ __forceinline__ void sst(uint32_t *p, uint32_t v)
 #endif
 }
 
+// Record `i` of a workspace array.  Every index is below nSeg * segLen < 2^28 (ensure_wavefront_workspace refuses more) and
+// a record has at most 16 bytes, so the byte offset fits 32 bits: written as one, the access is the array's (uniform)
+// address in SGPRs plus a 32-bit VGPR offset - one shift per access instead of a 64-bit shift-and-add (and the zero or
+// sign extension of the index that feeds it).
+template <class T>
+__device__ __forceinline__ T *rec(T *base, uint32_t i)
+{
+    using Byte = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return reinterpret_cast<T *>(reinterpret_cast<Byte *>(base) + (uint32_t)(i * (uint32_t)sizeof(T)));
+}
+
+// n / d by the terms make_magic_div(d) made (pt_scene.hpp): exact for every n
+__device__ __forceinline__ uint32_t magic_div(uint32_t n, MagicDiv m)
+{
+    const uint32_t t = __umulhi(m.mul, n);
+    return (t + ((n - t) >> (m.shifts & 0xFFu))) >> (m.shifts >> 8);
+}
+
 struct SlotPixel
 {
     uint32_t lx, py, frame;
@@ -167,10 +193,10 @@ struct SlotPixel
 __device__ __forceinline__ SlotPixel decode_slot(const WavefrontBuffers &w, const RenderParams &p, uint32_t slot)
 {
     SlotPixel r;
-    r.frame = slot / w.pixelsPadded;
+    r.frame = magic_div(slot >> 6, w.divTiles); // slot / pixelsPadded: pixelsPadded = 64 x tiles
     const uint32_t rem = slot - r.frame * w.pixelsPadded;
     const uint32_t tile = rem >> 6, inTile = rem & 63u;
-    const uint32_t ty = tile / w.tilesX;
+    const uint32_t ty = magic_div(tile, w.divTilesX);
     r.lx = (tile - ty * w.tilesX) * 8u + (inTile & 7u);
     r.py = ty * 8u + (inTile >> 3);
     r.valid = r.frame < p.frameCount && r.lx < p.localWidth && r.py < p.height;
@@ -193,9 +219,11 @@ struct BatchLane
 #ifndef PPT_BATCH_MAX_FRAMES
 #define PPT_BATCH_MAX_FRAMES 64u
 #endif
-// `q` counts the batches of the tiles [tileBase, tileBase + tiles) only (the whole image: 0, pixelsPadded >> 6).
+// `q` counts the batches of the tiles [tileBase, tileBase + tiles) only (the whole image: 0, pixelsPadded >> 6); `divTiles`
+// are the division terms of `tiles`.
 __device__ __forceinline__ BatchLane batch_lane(
-    const WavefrontBuffers &w, const RenderParams &p, uint32_t q, uint32_t lane, uint32_t tileBase, uint32_t tiles)
+    const WavefrontBuffers &w, const RenderParams &p, uint32_t q, uint32_t lane, uint32_t tileBase, uint32_t tiles,
+    MagicDiv divTiles)
 {
     constexpr uint32_t kMax = PPT_BATCH_MAX_FRAMES, kMaxShift = kMax == 64u ? 6u : (kMax == 32u ? 5u : (kMax == 16u ? 4u : (kMax == 8u ? 3u : 0u)));
     static_assert(kMaxShift != 0u || kMax == 1u, "PPT_BATCH_MAX_FRAMES is 1, 8, 16, 32 or 64");
@@ -206,7 +234,7 @@ __device__ __forceinline__ BatchLane batch_lane(
     bool inRange = true;
     if (rem < fullBatches)
     {
-        const uint32_t group = rem / (tiles << kMaxShift);
+        const uint32_t group = magic_div(rem >> kMaxShift, divTiles); // rem / (tiles << kMaxShift)
         firstFrame = group << kMaxShift;
         rem -= group * (tiles << kMaxShift);
     }
@@ -237,7 +265,7 @@ __device__ __forceinline__ BatchLane batch_lane(
     const uint32_t ix = (bx << wShift) + (pixel & ((1u << wShift) - 1u)), iy = (by << hShift) + (pixel >> wShift);
     BatchLane r;
     r.frame = firstFrame + (lane >> (6u - shift));
-    const uint32_t ty = tile / w.tilesX;
+    const uint32_t ty = magic_div(tile, w.divTilesX);
     r.lx = (tile - ty * w.tilesX) * 8u + ix;
     r.py = ty * 8u + iy;
     r.slot = r.frame * w.pixelsPadded + tile * 64u + iy * 8u + ix;
@@ -249,28 +277,45 @@ __device__ __forceinline__ BatchLane batch_lane(
 __device__ __forceinline__ void add_to_slot(float4 *color, uint32_t slot, uint32_t flags, f3 value, uint32_t bounce)
 {
 #if PPT_STREAM_NT & 4
-    const ppt_f4v cv = __builtin_nontemporal_load(reinterpret_cast<const ppt_f4v *>(color + slot));
+    const ppt_f4v cv = __builtin_nontemporal_load(reinterpret_cast<const ppt_f4v *>(rec(color, slot)));
     float4 c = make_float4(cv.x, cv.y, cv.z, cv.w);
 #else
-    float4 c = color[slot];
+    float4 c = *rec(color, slot);
 #endif
     f3 acc = f3{c.x, c.y, c.z};
     add_bounce(flags, acc, value, bounce);
 #if PPT_STREAM_NT & 4
-    __builtin_nontemporal_store(ppt_f4v{acc.x, acc.y, acc.z, 0.0f}, reinterpret_cast<ppt_f4v *>(color + slot));
+    __builtin_nontemporal_store(ppt_f4v{acc.x, acc.y, acc.z, 0.0f}, reinterpret_cast<ppt_f4v *>(rec(color, slot)));
 #else
-    color[slot] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    *rec(color, slot) = make_float4(acc.x, acc.y, acc.z, 0.0f);
 #endif
 }
 
-// Copies the BVH nodes and world triangles into this workgroup's LDS as they are (LdsGeomHalf).
+// The world triangles into LDS, each followed by its guard box (kLdsTriStride float4s per triangle; pt_device.hpp
+// guard_box): what box_guard would rebuild for every candidate, worked out once per triangle and workgroup.
+__device__ __forceinline__ void stage_triangles_in_lds(const DeviceScene &s, float4 *lt, uint32_t triCount)
+{
+    const float4 *gt = reinterpret_cast<const float4 *>(s.triangles);
+    for (uint32_t i = threadIdx.x; i < triCount; i += blockDim.x)
+    {
+        const float4 a = gt[i * 3u], b = gt[i * 3u + 1u], c = gt[i * 3u + 2u];
+        const GuardBox box = guard_box(xyz(a), xyz(b), xyz(c));
+        float4 *to = lt + i * kLdsTriStride;
+        to[0] = a;
+        to[1] = b;
+        to[2] = c;
+        to[3] = make_float4(box.lo.x, box.lo.y, box.lo.z, 0.0f);
+        to[4] = make_float4(box.hi.x, box.hi.y, box.hi.z, 0.0f);
+    }
+}
+
+// Copies the BVH nodes into this workgroup's LDS as they are (LdsGeomHalf), and the world triangles.
 __device__ __forceinline__ LdsGeomHalf stage_scene_in_lds_half(const DeviceScene &s, float4 *lds, uint32_t nodeCount, uint32_t triCount)
 {
     const float4 *gn = reinterpret_cast<const float4 *>(s.nodes);
     for (uint32_t i = threadIdx.x; i < nodeCount * kLdsNodeStrideHalf; i += blockDim.x) lds[i] = gn[i];
     float4 *lt = lds + nodeCount * kLdsNodeStrideHalf;
-    const float4 *gt = reinterpret_cast<const float4 *>(s.triangles);
-    for (uint32_t i = threadIdx.x; i < triCount * 3u; i += blockDim.x) lt[i] = gt[i];
+    stage_triangles_in_lds(s, lt, triCount);
     __syncthreads();
     return LdsGeomHalf{lds, lt};
 }
@@ -297,8 +342,7 @@ __device__ __forceinline__ LdsGeom stage_scene_in_lds(const DeviceScene &s, floa
         lf[i] = v;
     }
     float4 *lt = lds + nodeCount * kLdsNodeStride;
-    const float4 *gt = reinterpret_cast<const float4 *>(s.triangles);
-    for (uint32_t i = threadIdx.x; i < triCount * 3u; i += blockDim.x) lt[i] = gt[i];
+    stage_triangles_in_lds(s, lt, triCount);
     __syncthreads();
     return LdsGeom{lds, lt};
 }
@@ -319,7 +363,7 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
     LdsGeomHalf lg = {};
     if constexpr (LDS_SCENE) lg = stage_scene_in_lds_half(s, ldsScene, nodeCount, triCount);
     const GlobalGeom gg{s.nodes, s.triangles};
-    const SegmentId id = my_segment(w);
+    const SegmentId id = my_segment<true>(w);
     if (!id.valid) return;
     const uint32_t lane = lane_id();
     const TraversalStack stack{(lds_int32 *)ldsStack + (threadIdx.x >> 6) * (STACK * 64u) + lane,
@@ -337,7 +381,7 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
             if (sp.valid)
             {
                 if constexpr (COUNT) cnt.paths++;
-                w.color[id.base + k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                *rec(w.color, id.base + k) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
         }
     }
@@ -366,9 +410,9 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
             if constexpr (COUNT) cnt.closestRays++;
             // a path's state between stages: direction + one word of the generator, the other two words, and for
             // bounce 0 - no throughput record, it is (1, 1, 1) - the radiance slot as one dword (28 B per camera path)
-            sst(&w.rayB[0][at], make_float4(st.d.x, st.d.y, st.d.z, asf(st.rng.x)));
-            sst(&w.pathR[0][at], make_uint2(st.rng.y, st.rng.z));
-            sst(&w.cameraSlot[at], bl.slot);
+            sst(rec(w.rayB[0], at), make_float4(st.d.x, st.d.y, st.d.z, asf(st.rng.x)));
+            sst(rec(w.pathR[0], at), make_uint2(st.rng.y, st.rng.z));
+            sst(rec(w.cameraSlot, at), bl.slot);
             r.o = st.o;
             r.d = st.d;
             r.tMin = 0.0f;
@@ -387,9 +431,9 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
                     add_bounce(p.pc.flags, color, sample_skybox(s, dir), 0u); // throughput is (1,1,1)
                 }
 #if PPT_STREAM_NT & 4
-                __builtin_nontemporal_store(ppt_f4v{color.x, color.y, color.z, 0.0f}, reinterpret_cast<ppt_f4v *>(w.color + bl.slot));
+                __builtin_nontemporal_store(ppt_f4v{color.x, color.y, color.z, 0.0f}, reinterpret_cast<ppt_f4v *>(rec(w.color, bl.slot)));
 #else
-                w.color[bl.slot] = make_float4(color.x, color.y, color.z, 0.0f);
+                *rec(w.color, bl.slot) = make_float4(color.x, color.y, color.z, 0.0f);
 #endif
             }
             const bool isHit = valid && found;
@@ -397,8 +441,8 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
             const uint32_t pos = nHit + wave_rank(isHit, total);
             if (isHit)
             {
-                sst(&w.hit[id.base + pos], make_uint4(hit.drawInstance, hit.primitive, asu(hit.bary.x), asu(hit.bary.y)));
-                sst(&w.hitIdx[id.base + pos], k);
+                sst(rec(w.hit, id.base + pos),make_uint4(hit.drawInstance, hit.primitive, asu(hit.bary.x), asu(hit.bary.y)));
+                sst(rec(w.hitIdx, id.base + pos), k);
             }
             nHit += total;
         };
@@ -409,6 +453,7 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
         // ... or, banded (WavefrontBuffers::bandSegments): batch number b * S + j of the batches of ONE band of tiles, S the
         // segments that share the band and j this segment's place among them - the same striding inside the band.
         uint32_t dealStride = w.nSeg, dealFirst = id.seg, tileBase = 0u, tileCount = w.pixelsPadded >> 6;
+        MagicDiv divTileCount = w.divTiles;
         if (w.bandSegments != 0u)
         {
             const uint32_t band = id.seg / w.bandSegments;
@@ -417,11 +462,12 @@ __global__ __launch_bounds__(256, PPT_GEN_WPE) void wf_generate_extend(
             dealFirst = id.seg - firstSeg;
             tileBase = w.bandTile[band];
             tileCount = w.bandTile[band + 1u] - tileBase;
+            divTileCount = w.divBandTiles[band];
         }
         for (uint32_t k0 = 0; k0 < w.segLen; k0 += 64u)
         {
             const uint32_t k = k0 + lane;
-            bl = batch_lane(w, p, (k0 >> 6) * dealStride + dealFirst, lane, tileBase, tileCount);
+            bl = batch_lane(w, p, (k0 >> 6) * dealStride + dealFirst, lane, tileBase, tileCount, divTileCount);
             const StreamRay r = fetch(k);
             Hit hit;
             bool found;
@@ -451,8 +497,8 @@ __device__ __forceinline__ uint32_t extend_segment(
     const float4 *__restrict__ rayB = w.rayB[cur];
     uint32_t nHit = 0;
     auto fetch = [&](uint32_t k) {
-        const float4 a = sld(&rayA[id.base + k]);
-        const float4 b = sld(&rayB[id.base + k]);
+        const float4 a = sld(rec(rayA, id.base + k));
+        const float4 b = sld(rec(rayB, id.base + k));
         if constexpr (COUNT) cnt.closestRays++;
         StreamRay r;
         r.o = xyz(a);
@@ -466,7 +512,7 @@ __device__ __forceinline__ uint32_t extend_segment(
         if (pred && !found && (p.pc.flags & PROSPER_PC_FLAG_IBL))
         {
             if constexpr (COUNT) cnt.skyLookups++;
-            const float4 t = sld(&w.pathT[cur][id.base + k]);
+            const float4 t = sld(rec(w.pathT[cur], id.base + k));
             add_to_slot(w.color, asu(t.w) & kSlotMask, p.pc.flags, xyz(t) * sample_skybox(s, dir), bounce);
         }
         const bool isHit = pred && found;
@@ -474,12 +520,12 @@ __device__ __forceinline__ uint32_t extend_segment(
         const uint32_t pos = nHit + wave_rank(isHit, total);
         if (isHit)
         {
-            sst(&w.hit[id.base + pos], make_uint4(hit.drawInstance, hit.primitive, asu(hit.bary.x), asu(hit.bary.y)));
-            sst(&w.hitIdx[id.base + pos], k);
+            sst(rec(w.hit, id.base + pos),make_uint4(hit.drawInstance, hit.primitive, asu(hit.bary.x), asu(hit.bary.y)));
+            sst(rec(w.hitIdx, id.base + pos), k);
         }
         nHit += total;
     };
-    trace_stream<false, COUNT>(g, s, n, stack, cnt, fetch, commit);
+    trace_stream<false, COUNT, true>(g, s, n, 0.0f, stack, cnt, fetch, commit);
     return nHit;
 }
 
@@ -521,6 +567,17 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
     unsigned long long *__restrict__ counters)
 {
     __shared__ uint32_t ldsTables[LDS_TABLES != 0 ? kLdsTableBytes / 4u : 4u];
+    // the direction towards the sun, once per workgroup instead of once per hit that draws light 0 (pt_device.hpp SunInLds)
+    __shared__ float ldsSun[4];
+    if (threadIdx.x == 0)
+    {
+        const f3 l = sun_direction(*s.directionalLight);
+        ldsSun[0] = l.x;
+        ldsSun[1] = l.y;
+        ldsSun[2] = l.z;
+    }
+    const SunInLds sunL{(__attribute__((address_space(3))) const float *)ldsSun};
+    if constexpr (LDS_TABLES == 0) __syncthreads();
     if constexpr (LDS_TABLES != 0)
     {
         uint32_t off = 0;
@@ -545,7 +602,7 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
         }
         __syncthreads();
     }
-    const SegmentId id = my_segment(w);
+    const SegmentId id = my_segment<true>(w);
     if (!id.valid) return;
     const uint32_t lane = lane_id();
     const uint32_t nxt = cur ^ 1u;
@@ -569,12 +626,12 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
         uint32_t slot = 0;
         if (j < n)
         {
-            const uint32_t i = sld(&w.hitIdx[id.base + j]);
-            const uint4 h = sld(&w.hit[id.base + j]);
-            const float4 b = sld(&w.rayB[cur][id.base + i]);
+            const uint32_t i = sld(rec(w.hitIdx, id.base + j));
+            const uint4 h = sld(rec(w.hit, id.base + j));
+            const float4 b = sld(rec(w.rayB[cur], id.base + i));
             // bounce 0: no throughput record - it is (1, 1, 1) - and the slot comes from the camera paths' own array
-            const float4 t = bounce == 0u ? make_float4(1.0f, 1.0f, 1.0f, asf(sld(&w.cameraSlot[id.base + i]))) : sld(&w.pathT[cur][id.base + i]);
-            const uint2 r = sld(&w.pathR[cur][id.base + i]);
+            const float4 t = bounce == 0u ? make_float4(1.0f, 1.0f, 1.0f, asf(sld(rec(w.cameraSlot, id.base + i)))) : sld(rec(w.pathT[cur], id.base + i));
+            const uint2 r = sld(rec(w.pathR[cur], id.base + i));
             slot = asu(t.w) & kSlotMask;
             rng = Rng{asu(b.w), r.x, r.y};
             const f3 throughput = xyz(t);
@@ -587,20 +644,21 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
             if (debugDraw)
             {
                 const f3 c = debug_color(s, p.pc.drawType, hit, sf);
-                w.color[slot] = make_float4(c.x, c.y, c.z, 0.0f); // `color =`, not `+=` (main.rgen:262)
+                *rec(w.color, slot) = make_float4(c.x, c.y, c.z, 0.0f); // `color =`, not `+=` (main.rgen:262)
             }
             else
             {
                 f3 l, irradiance;
                 float d;
-                if (prepare_direct_lighting<COUNT>(s, sf, throughput, rng, l, d, irradiance, cnt))
+                const BrdfTerms bt = brdf_terms(sf); // for the light sample and the bounce sample alike
+                if (prepare_direct_lighting<COUNT>(s, sf, throughput, rng, l, d, irradiance, cnt, sunL))
                 {
                     if constexpr (COUNT) cnt.shadowRays++;
                     shSeed = pcg(rng.x ^ rng.y);
                     shP = sf.positionWS;
                     shL = l;
                     shDist = d;
-                    const f3 brdf = eval_brdf_times_nol(l, sf);
+                    const f3 brdf = eval_brdf_times_nol(l, sf, bt);
                     shC1 = direct_lighting_value(s, throughput, irradiance, brdf, 1.0f);
                     // what the reference adds when the light is occluded is (t * (irr*0*n)) * brdf:
                     // +-0 unless a factor is non-finite; remember which channels come out NaN
@@ -614,7 +672,7 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
                 {
                     f3 rd;
                     f3 tp = throughput;
-                    importance_sample_bounce(sf, rng, tp, rd);
+                    importance_sample_bounce(sf, bt, rng, tp, rd);
                     bool alive = p.traceDeadPaths || !throughput_is_zero(tp);
                     if (alive && bounce > p.pc.rouletteStartBounce)
                         alive = !(rng.rnd01() < fmax_(0.05f, 1.0f - max3(tp)));
@@ -632,18 +690,18 @@ __global__ __launch_bounds__(256, PPT_SHADE_WPE) void wf_shade(
         uint32_t pos = nShadow + wave_rank(wantShadow, total);
         if (wantShadow)
         {
-            sst(&w.shA[id.base + pos], make_float4(shP.x, shP.y, shP.z, asf(shSeed)));
-            sst(&w.shB[id.base + pos], make_float4(shL.x, shL.y, shL.z, shDist));
-            sst(&w.shC[id.base + pos], make_float4(shC1.x, shC1.y, shC1.z, asf(slot | (nanMask << 28))));
+            sst(rec(w.shA, id.base + pos), make_float4(shP.x, shP.y, shP.z, asf(shSeed)));
+            sst(rec(w.shB, id.base + pos), make_float4(shL.x, shL.y, shL.z, shDist));
+            sst(rec(w.shC, id.base + pos), make_float4(shC1.x, shC1.y, shC1.z, asf(slot | (nanMask << 28))));
         }
         nShadow += total;
         pos = nNext + wave_rank(wantNext, total);
         if (wantNext)
         {
-            sst(&w.rayA[nxt][id.base + pos], make_float4(nO.x, nO.y, nO.z, asf(pcg(rng.x ^ rng.z))));
-            sst(&w.rayB[nxt][id.base + pos], make_float4(nD.x, nD.y, nD.z, asf(rng.x)));
-            sst(&w.pathT[nxt][id.base + pos], make_float4(nT.x, nT.y, nT.z, asf(slot)));
-            sst(&w.pathR[nxt][id.base + pos], make_uint2(rng.y, rng.z));
+            sst(rec(w.rayA[nxt], id.base + pos), make_float4(nO.x, nO.y, nO.z, asf(pcg(rng.x ^ rng.z))));
+            sst(rec(w.rayB[nxt], id.base + pos), make_float4(nD.x, nD.y, nD.z, asf(rng.x)));
+            sst(rec(w.pathT[nxt], id.base + pos), make_float4(nT.x, nT.y, nT.z, asf(slot)));
+            sst(rec(w.pathR[nxt], id.base + pos), make_uint2(rng.y, rng.z));
         }
         nNext += total;
     }
@@ -667,8 +725,8 @@ __device__ __forceinline__ void shadow_segment(
     uint32_t bounce, const TraversalStack &stack, LaneCounters &cnt)
 {
     auto fetch = [&](uint32_t k) {
-        const float4 a = sld(&w.shA[id.base + k]);
-        const float4 b = sld(&w.shB[id.base + k]);
+        const float4 a = sld(rec(w.shA, id.base + k));
+        const float4 b = sld(rec(w.shB, id.base + k));
         StreamRay r;
         r.o = xyz(a);
         r.d = xyz(b);
@@ -680,7 +738,7 @@ __device__ __forceinline__ void shadow_segment(
     auto commit = [&](bool pred, uint32_t k, bool occluded, const Hit &, const f3 &) {
         if (pred)
         {
-            const float4 c = sld(&w.shC[id.base + k]);
+            const float4 c = sld(rec(w.shC, id.base + k));
             const uint32_t packed = asu(c.w);
             const uint32_t nanMask = packed >> 28;
             if (!occluded || nanMask)
@@ -695,7 +753,7 @@ __device__ __forceinline__ void shadow_segment(
             }
         }
     };
-    trace_stream<true, COUNT>(g, s, n, stack, cnt, fetch, commit);
+    trace_stream<true, COUNT, false>(g, s, n, 0.1f, stack, cnt, fetch, commit); // main.rgen:217
 }
 
 // Shadow rays of bounce `bounce` and (unless it was the last bounce) the closest-hit rays of bounce
@@ -714,13 +772,17 @@ __global__ __launch_bounds__(256, PPT_TRACE_WPE(STACK)) void wf_trace(
     LdsGeom lg = {};
     if constexpr (LDS_SCENE) lg = stage_scene_in_lds(s, ldsScene, nodeCount, triCount);
     const GlobalGeom gg{s.nodes, s.triangles};
-    const SegmentId id = my_segment(w);
-    if (!id.valid) return;
+    const SegmentId vid = my_segment<false>(w);
+    if (!vid.valid) return;
     const TraversalStack stack{(lds_int32 *)ldsStack + (threadIdx.x >> 6) * (STACK * 64u) + lane_id(),
                                stackOverflow + blockIdx.x * 256u + threadIdx.x, (uint32_t)STACK, gridDim.x * 256u, 64u, LDS_SCENE};
     LaneCounters cnt = {};
-    const uint32_t nShadow = w.segShadow[id.seg];
-    const uint32_t nRays = doExtend ? w.segRays[id.seg] : 0u;
+    // the stream lengths stay per-lane values (my_segment), the segment's number and base in the record addresses are
+    // scalars: the thread index they come from is not kept - or spilled - through the two streams
+    const uint32_t nShadow = w.segShadow[vid.seg];
+    const uint32_t nRays = doExtend ? w.segRays[vid.seg] : 0u;
+    const uint32_t segScalar = (uint32_t)__builtin_amdgcn_readfirstlane((int)vid.seg);
+    const SegmentId id{segScalar, (uint32_t)__builtin_amdgcn_readfirstlane((int)vid.base), true};
     if constexpr (LDS_SCENE)
         shadow_segment<COUNT>(lg, s, p, w, id, nShadow, bounce, stack, cnt);
     else
@@ -735,7 +797,7 @@ __global__ __launch_bounds__(256, PPT_TRACE_WPE(STACK)) void wf_trace(
             nHit = extend_segment<COUNT>(lg, s, p, w, id, nRays, bounce + 1u, nextCur, stack, cnt);
         else
             nHit = extend_segment<COUNT>(gg, s, p, w, id, nRays, bounce + 1u, nextCur, stack, cnt);
-        if (lane_id() == 0u) w.segHits[id.seg] = nHit;
+        if (lanes_below(~0ull) == 0u) w.segHits[segScalar] = nHit; // (the wave's first lane)
     }
     flush_counters<COUNT>(cnt, counters);
 }
@@ -760,10 +822,10 @@ __global__ __launch_bounds__(256) void wf_accumulate(
             for (uint32_t f = 0; f < p.frameCount; ++f)
             {
 #if PPT_STREAM_NT & 4
-                const ppt_f4v cv = __builtin_nontemporal_load(reinterpret_cast<const ppt_f4v *>(w.color + (size_t)f * w.pixelsPadded + rem)); // (its last use)
+                const ppt_f4v cv = __builtin_nontemporal_load(reinterpret_cast<const ppt_f4v *>(rec(w.color, f * w.pixelsPadded + rem))); // (its last use)
                 const float4 c = make_float4(cv.x, cv.y, cv.z, cv.w);
 #else
-                const float4 c = w.color[(size_t)f * w.pixelsPadded + rem];
+                const float4 c = *rec(w.color, f * w.pixelsPadded + rem);
 #endif
                 const bool skip = (f == 0 && (p.pc.flags & PROSPER_PC_FLAG_SKIP_HISTORY)) ||
                                   !(p.pc.flags & PROSPER_PC_FLAG_ACCUMULATE);
@@ -859,7 +921,7 @@ bool wavefront_shade_tables_in_lds(const DeviceScene &s, bool disabled)
 bool wavefront_scene_in_lds(uint32_t ldsStackEntries, uint32_t stackBound, uint32_t nodeCount, uint32_t triCount, bool disabled)
 {
     // (stackBound <= 16: the LDS-scene kernels have no global stack path at all - TraversalStack::ldsOnly)
-    return ldsStackEntries == 16u && stackBound <= 16u && nodeCount * kLdsNodeStride + triCount * 3u <= kLdsSceneFloat4s && !disabled;
+    return ldsStackEntries == 16u && stackBound <= 16u && nodeCount * kLdsNodeStride + triCount * kLdsTriStride <= kLdsSceneFloat4s && !disabled;
 }
 
 // The traversal kernels of a render and the global scratch they index: `overflowEntries` stack entries per lane.
