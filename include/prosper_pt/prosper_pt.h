@@ -752,6 +752,30 @@ typedef struct prosper_pt_hierarchy_build_info
     uint32_t reserved2;
 } prosper_pt_hierarchy_build_info;
 int prosper_pt_get_hierarchy_build_info(prosper_pt_ctx *ctx, prosper_pt_hierarchy_build_info *out);
+/* ---- the GPU builder's method (opt-in) ----
+ * How prosper_pt_build_hierarchy_gpu, and every path that PROSPER_PT_BUILDER_GPU routes to it, makes the binary tree over the
+ * Morton order.  PROSPER_PT_GPU_HIERARCHY_LINEAR (the default) is the radix tree above.  PROSPER_PT_GPU_HIERARCHY_PLOC merges
+ * clusters round by round with their nearest neighbour within `radius` positions of that order (parallel locally-ordered
+ * clustering; the rule is prosper_amd/ploc.py) and collapses by box cost: a tree of lower cost, a longer build.  Everything
+ * else - the 4-wide nodes, the stack bound and its refusal, the refit, the hit contract - is the same.  radius: 1 .. 32, 0 for
+ * the default; anything else, or an unknown method, is refused with PROSPER_PT_ERR_INVALID_ARGUMENT and the selection stays as
+ * it was.  The call needs no scene and builds nothing.  Without a leaf size in prosper_pt_debug_options the PLOC method uses its
+ * own default.  In prosper_pt_hierarchy_build_info the stage slot of the radix tree holds the clustering and the ranges. */
+#define PROSPER_PT_GPU_HIERARCHY_LINEAR 0u
+#define PROSPER_PT_GPU_HIERARCHY_PLOC 1u
+int prosper_pt_set_gpu_hierarchy_method(prosper_pt_ctx *ctx, uint32_t method, uint32_t radius);
+typedef struct prosper_pt_gpu_hierarchy_method_info
+{
+    uint32_t selectedMethod; /* prosper_pt_set_gpu_hierarchy_method */
+    uint32_t selectedRadius; /* (the default's value where 0 was given) */
+    uint32_t method;         /* of the build that made the tree in use; LINEAR, and 0 below, after a host build */
+    uint32_t radius;         /* 0 for the linear method */
+    uint32_t rounds;         /* clustering rounds of that build */
+    uint32_t finishRounds;   /* those of them that ran in the single-workgroup launch */
+    uint32_t reserved[2];
+} prosper_pt_gpu_hierarchy_method_info;
+/* Needs no scene: without one only the selection is filled. */
+int prosper_pt_get_gpu_hierarchy_method_info(prosper_pt_ctx *ctx, prosper_pt_gpu_hierarchy_method_info *out);
 /* Test hook: the flat world triangles ((drawInstance, primitive) order, 48 bytes each) and the leaf-order permutation
  * (uint32 per triangle) as the device holds them; a staged update is flushed first. */
 int prosper_pt_debug_read_hierarchy_arrays(

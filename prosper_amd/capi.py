@@ -96,6 +96,8 @@ def lib():
     L.prosper_pt_build_hierarchy_gpu.argtypes = [vp]
     L.prosper_pt_set_hierarchy_builder.argtypes = [vp, u32]
     L.prosper_pt_get_hierarchy_build_info.argtypes = [vp, C.POINTER(S.HierarchyBuildInfo)]
+    L.prosper_pt_set_gpu_hierarchy_method.argtypes = [vp, u32, u32]
+    L.prosper_pt_get_gpu_hierarchy_method_info.argtypes = [vp, C.POINTER(S.GpuHierarchyMethodInfo)]
     L.prosper_pt_debug_read_hierarchy_arrays.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     L.prosper_pt_set_output_buffer.argtypes = [vp, vp, C.c_size_t]
     L.prosper_pt_render.argtypes = [
@@ -803,6 +805,17 @@ class Context:
     def set_hierarchy_builder(self, builder):
         """structs.BUILDER_HOST (the default) or BUILDER_GPU: who rebuilds - prosper_pt_rebuild_hierarchy and the drift trigger."""
         _check(lib().prosper_pt_set_hierarchy_builder(self._h, builder))
+
+    def set_gpu_hierarchy_method(self, method, radius=0):
+        """structs.GPU_HIERARCHY_LINEAR (the default) or GPU_HIERARCHY_PLOC with a search radius of 1 .. 32 (0: the default):
+        how every later GPU build makes its binary tree (prosper_amd/ploc.py states the PLOC rule)."""
+        _check(lib().prosper_pt_set_gpu_hierarchy_method(self._h, method, radius))
+
+    def gpu_hierarchy_method_info(self):
+        """The selected method and radius, and method, radius and rounds of the build that made the tree in use."""
+        info = S.GpuHierarchyMethodInfo()
+        _check(lib().prosper_pt_get_gpu_hierarchy_method_info(self._h, C.byref(info)))
+        return info
 
     def hierarchy_build_info(self):
         info = S.HierarchyBuildInfo()

@@ -1408,6 +1408,34 @@ int prosper_pt_set_hierarchy_builder(prosper_pt_ctx *ctx, uint32_t builder)
     return PROSPER_PT_OK;
 }
 
+int prosper_pt_set_gpu_hierarchy_method(prosper_pt_ctx *ctx, uint32_t method, uint32_t radius)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: null argument");
+    if (method != PROSPER_PT_GPU_HIERARCHY_LINEAR && method != PROSPER_PT_GPU_HIERARCHY_PLOC)
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: unknown method");
+    if (radius > kPlocMaxRadius) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: the radius is 1 .. 32 (0: the default)");
+    ctx->gpuHierarchyMethod = method;
+    ctx->gpuHierarchyRadius = radius;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_gpu_hierarchy_method_info(prosper_pt_ctx *ctx, prosper_pt_gpu_hierarchy_method_info *out)
+{
+    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gpu_hierarchy_method_info: null argument");
+    *out = prosper_pt_gpu_hierarchy_method_info{};
+    out->selectedMethod = ctx->gpuHierarchyMethod;
+    out->selectedRadius = ctx->gpuHierarchyRadius ? ctx->gpuHierarchyRadius : kPlocDefaultRadius;
+    const AccelState *acc = ctx->haveScene ? ctx->accel : nullptr;
+    if (acc && acc->foreignTree)
+    {
+        out->method = acc->gpuMethod;
+        out->radius = acc->gpuRadius;
+        out->rounds = acc->gpuRounds;
+        out->finishRounds = acc->gpuFinishRounds;
+    }
+    return PROSPER_PT_OK;
+}
+
 int prosper_pt_get_hierarchy_build_info(prosper_pt_ctx *ctx, prosper_pt_hierarchy_build_info *out)
 {
     if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_hierarchy_build_info: null argument");

@@ -4,7 +4,9 @@
 //   lbvh_codes          21 bits per axis, interleaved to 63-bit codes
 //   (hipCUB radix sort) ascending (code, triangle index): the sort is stable and starts from index order
 //   lbvh_radix_tree     Karras 2012: every inner node finds its own range and split, no atomics
-//   lbvh_count / _emit  per 4-wide depth: collapse by largest range, children numbered by a prefix sum over the depth
+//                       (the PLOC method makes the binary tree in its place: pt_bvh_ploc.hip, prosper_amd/ploc.py)
+//   lbvh_count / _emit  per 4-wide depth: collapse by largest range (PLOC: by largest box cost), children numbered by a
+//                       prefix sum over the depth
 //   lbvh_heights        per depth, deepest first: node heights, their histogram
 //   (hipCUB radix sort) nodes by (height, index)
 //   lbvh_nest_boxes     behind every refit of such a tree: inner children's stored boxes grown to contain their own children's
@@ -345,8 +347,10 @@ dim3 grid_for(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 } // namespace
 
-int lbvh_build(LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, hipStream_t stream, LbvhResult &out)
+int lbvh_build(
+    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out)
 {
+    const bool ploc = method.method == PROSPER_PT_GPU_HIERARCHY_PLOC;
     if (count == 0 || leafSize == 0 || leafSize > kMaxLeafTriangles)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: nothing to build, or a leaf size outside 1 .. 4");
     if (const int rc = reserve(st, count)) return rc;
@@ -378,10 +382,20 @@ int lbvh_build(LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_
     }
     else
     {
-        hipLaunchKernelGGL(lbvh_radix_tree_kernel, grid_for(count - 1u), block, 0, stream, st.codesSorted, count, st.first, st.last, st.split);
+        if (ploc)
+        {
+            // the rounds read the Morton order and leave the leaf order in st.index (free since the sort), which then
+            // becomes st.perm: everything behind this point reads the same arrays under either method
+            if (const int rc = ploc_binary_tree(
+                    st.ploc, flat, st.perm, count, method.radius, st.first, st.last, st.split, st.index, st.readback.ptr, stream, out.ploc))
+                return rc;
+            PPT_HIP(hipMemcpyAsync(st.perm, st.index, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        }
+        else
+            hipLaunchKernelGGL(lbvh_radix_tree_kernel, grid_for(count - 1u), block, 0, stream, st.codesSorted, count, st.first, st.last, st.split);
         PPT_HIP(hipGetLastError());
         PPT_HIP(hipEventRecord(ev[kLbvhStageCollapse], stream));
-        const LbvhRadixTree tree{st.first, st.last, st.split};
+        const LbvhRadixTree tree{st.first, st.last, st.split, ploc ? st.ploc.cost : nullptr};
         // the root: radix node 0, nothing above it on its path
         PPT_HIP(hipMemsetAsync(st.radixOf, 0, sizeof(uint32_t), stream));
         PPT_HIP(hipMemsetAsync(st.pathSum, 0, sizeof(uint32_t), stream));

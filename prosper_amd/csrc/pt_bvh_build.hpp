@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "pt_bvh_ploc.hpp"
 #include "pt_context.hpp"
 #include "pt_scene.hpp"
 #include "pt_sync.hpp"
@@ -18,6 +19,7 @@ namespace ppt
 {
 
 constexpr uint32_t kLbvhDefaultLeafSize = 2; // (the lowest C3 frame time of 1, 2 and 4: DESIGN.md f24)
+constexpr uint32_t kPlocDefaultLeafSize = 2; // (with the default radius, the lowest C3 frame time of the sweep: DESIGN.md f26)
 constexpr uint32_t kLbvhMaxLevels = 128;     // 4-wide depths a build can number (63 code bits + 28 index bits at most)
 
 // the device stages of a build, as prosper_pt_hierarchy_build_info reports them
@@ -26,7 +28,7 @@ enum LbvhStage : uint32_t
     kLbvhStageBounds = 0, // primitive boxes, centroids, centroid bounds
     kLbvhStageCodes,
     kLbvhStageSort,
-    kLbvhStageRadixTree,
+    kLbvhStageRadixTree,  // the binary tree: Karras' radix tree, or the PLOC method's rounds and ranges
     kLbvhStageCollapse,   // 4-wide collapse and breadth-first numbering, stack bound
     kLbvhStageHeights,
     kLbvhStageTables,     // nodes by height, level histogram
@@ -50,6 +52,14 @@ struct LbvhState
     size_t sortTempBytes = 0;
     Pinned<uint32_t> readback;
     StageEvents<kLbvhStageCount> events;
+    PlocState ploc; // the PLOC method's own scratch, made by its first build
+};
+
+// How the binary tree is made (prosper_pt_set_gpu_hierarchy_method)
+struct LbvhMethod
+{
+    uint32_t method = 0; // PROSPER_PT_GPU_HIERARCHY_LINEAR / _PLOC
+    uint32_t radius = 0; // PLOC: 1 .. kPlocMaxRadius
 };
 
 struct LbvhResult
@@ -58,12 +68,14 @@ struct LbvhResult
     uint32_t depths = 0;     // 4-wide depths (breadth-first levels)
     uint32_t stackBound = 0; // what BvhBuildResult::maxDepth is for the host builder
     std::vector<uint32_t> levelOffsets; // [levels + 1] into LbvhState::order (nodes by height)
+    PlocRounds ploc;                    // (zero for the linear method)
 };
 
 // The build of `count` >= 1 triangles on `stream`, which has been waited for when this returns.  Results stay in the
 // state's arrays (nodes: child references and `reserved` only, the boxes are the refit's; perm; order).
 // PROSPER_PT_ERR_UNSUPPORTED: the stack bound exceeds kMaxStackBound.
-int lbvh_build(LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, hipStream_t stream, LbvhResult &out);
+int lbvh_build(
+    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out);
 // After a refit of a GPU-built tree (nodes by height in `order`, `levelOffsets` on the host): every inner child's stored box
 // grown to contain the stored boxes of that child's own children; boxes only grow, nodes that nest already keep their bytes.
 void launch_lbvh_nest_boxes(BvhNode *nodes, const uint32_t *order, const uint32_t *levelOffsets, uint32_t levels, hipStream_t stream);

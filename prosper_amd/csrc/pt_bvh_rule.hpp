@@ -101,6 +101,7 @@ struct LbvhKid
 struct LbvhRadixTree
 {
     const uint32_t *first, *last, *split;
+    const float *cost; // null: the linear method.  Else the cost of every inner node's own box (pt_bvh_ploc_rule.hpp)
 };
 PPT_RULE uint32_t lbvh_kid_triangles(const LbvhKid &k) { return k.b - k.a + 1u; }
 PPT_RULE void lbvh_children(const LbvhRadixTree &r, uint32_t t, LbvhKid &left, LbvhKid &right)
@@ -110,7 +111,8 @@ PPT_RULE void lbvh_children(const LbvhRadixTree &r, uint32_t t, LbvhKid &left, L
     right = LbvhKid{s + 1u, r.last[t], s + 1u};
 }
 // the slots of the 4-wide node made of radix node t: open the largest range (the first one on a tie) until four slots are
-// in use or none holds more than leafSize triangles; returns the slots in use
+// in use or none holds more than leafSize triangles; returns the slots in use.  A tree that carries box costs opens the
+// slot of more than leafSize triangles with the largest cost instead (on equal cost the larger range, then the first).
 PPT_RULE uint32_t lbvh_collapse(const LbvhRadixTree &r, uint32_t t, uint32_t leafSize, LbvhKid kids[4])
 {
     lbvh_children(r, t, kids[0], kids[1]);
@@ -119,12 +121,19 @@ PPT_RULE uint32_t lbvh_collapse(const LbvhRadixTree &r, uint32_t t, uint32_t lea
     {
         int best = -1;
         uint32_t bestCount = leafSize;
+        float bestCost = 0.0f;
         for (uint32_t c = 0; c < k; ++c)
-            if (lbvh_kid_triangles(kids[c]) > bestCount)
+        {
+            const uint32_t triangles = lbvh_kid_triangles(kids[c]);
+            if (triangles <= leafSize) continue;
+            const float cost = r.cost ? r.cost[kids[c].radix] : 0.0f;
+            if (r.cost ? (best < 0 || cost > bestCost || (cost == bestCost && triangles > bestCount)) : triangles > bestCount)
             {
                 best = (int)c;
-                bestCount = lbvh_kid_triangles(kids[c]);
+                bestCount = triangles;
+                bestCost = cost;
             }
+        }
         if (best < 0) break;
         LbvhKid left, right;
         lbvh_children(r, kids[best].radix, left, right);

@@ -159,6 +159,7 @@ struct AccelState
     // build of any kind splits every instance again.  What that build reported, for prosper_pt_get_hierarchy_build_info.
     bool foreignTree = false, gpuStagesValid = false;
     uint32_t gpuLeafSize = 0, gpuDepths = 0;
+    uint32_t gpuMethod = 0, gpuRadius = 0, gpuRounds = 0, gpuFinishRounds = 0; // prosper_pt_get_gpu_hierarchy_method_info
     float gpuStageMs[8] = {};
     // a prosper_pt_update_transforms that failed half way leaves transforms, world triangles and nodes out of step: renders
     // are refused and the next update redoes every instance, whatever the transforms it is given
@@ -359,6 +360,7 @@ struct prosper_pt_ctx
     ppt::MeshPreparePassState *meshPreparePasses = nullptr; // prosper_pt_prepare_mesh
     ppt::AnimationState *animation = nullptr;
     uint32_t hierarchyBuilder = PROSPER_PT_BUILDER_HOST; // prosper_pt_set_hierarchy_builder
+    uint32_t gpuHierarchyMethod = PROSPER_PT_GPU_HIERARCHY_LINEAR, gpuHierarchyRadius = 0; // prosper_pt_set_gpu_hierarchy_method (0: the default radius)
     ppt::LbvhState *lbvh = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;

@@ -292,11 +292,16 @@ int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t)
     if (!ctx->lbvh) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     LbvhState &st = *ctx->lbvh;
     static_assert(sizeof(acc->gpuStageMs) / sizeof(float) == kLbvhStageCount, "one slot per stage");
-    const uint32_t leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles) : kLbvhDefaultLeafSize;
+    LbvhMethod method;
+    method.method = ctx->gpuHierarchyMethod;
+    const bool ploc = method.method == PROSPER_PT_GPU_HIERARCHY_PLOC;
+    if (ploc) method.radius = ctx->gpuHierarchyRadius ? ctx->gpuHierarchyRadius : kPlocDefaultRadius;
+    const uint32_t leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles)
+                                                  : (ploc ? kPlocDefaultLeafSize : kLbvhDefaultLeafSize);
     LbvhResult built;
     int rc;
     acc->gpuStagesValid = false;
-    if ((rc = lbvh_build(st, acc->dFlat, (uint32_t)acc->total, leafSize, t.stream, built))) return rc;
+    if ((rc = lbvh_build(st, acc->dFlat, (uint32_t)acc->total, leafSize, method, t.stream, built))) return rc;
 
     // ---- accepted: from here on the scene's arrays change ----
     acc->stale = true;
@@ -334,6 +339,10 @@ int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t)
     acc->gpuStagesValid = true;
     acc->gpuLeafSize = leafSize;
     acc->gpuDepths = built.depths;
+    acc->gpuMethod = method.method;
+    acc->gpuRadius = method.radius;
+    acc->gpuRounds = built.ploc.rounds;
+    acc->gpuFinishRounds = built.ploc.finishRounds;
     t.stats->nodeCount = built.nodeCount;
     t.stats->maxDepth = built.stackBound;
     return PROSPER_PT_OK;

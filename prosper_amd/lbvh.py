@@ -141,8 +141,13 @@ def radix_tree(codes):
     return np.minimum(i, j).astype(np.uint32), np.maximum(i, j).astype(np.uint32), split.astype(np.uint32)
 
 
-def build(flat, leaf_size=DEFAULT_LEAF_SIZE, max_stack_bound=MAX_STACK_BOUND):
-    """The whole statement over flat world triangles ((n, 12) uint32 words or (n, 3, 3) float32 vertices)."""
+def build(flat, leaf_size=DEFAULT_LEAF_SIZE, max_stack_bound=MAX_STACK_BOUND, binary=None):
+    """The whole statement over flat world triangles ((n, 12) uint32 words or (n, 3, 3) float32 vertices).
+
+    `binary` is the hook of another method of the same builder (prosper_amd/ploc.py): called with the vertices and the
+    order by (code, index) of a scene of more than leaf_size triangles, it returns the leaf order and a binary tree over
+    it in the radix tree's own form (first, last, split), plus a key per inner node; the collapse then opens the slot
+    with the largest (key, range) instead of the largest range.  Without it nothing here changes."""
     if not 1 <= leaf_size <= MAX_LEAF_TRIANGLES:
         raise ValueError("leaf_size is 1 .. %d" % MAX_LEAF_TRIANGLES)
     v = vertices(flat)
@@ -158,7 +163,11 @@ def build(flat, leaf_size=DEFAULT_LEAF_SIZE, max_stack_bound=MAX_STACK_BOUND):
         path.append(0)
         level_starts = [0, 1]
     else:
-        first, last, split = radix_tree(ordered)
+        key = None
+        if binary is None:
+            first, last, split = radix_tree(ordered)
+        else:
+            permutation, first, last, split, key = binary(v, permutation)
 
         def kids_of(t):
             return [(int(first[t]), int(split[t]), int(split[t])), (int(split[t]) + 1, int(last[t]), int(split[t]) + 1)]
@@ -170,10 +179,13 @@ def build(flat, leaf_size=DEFAULT_LEAF_SIZE, max_stack_bound=MAX_STACK_BOUND):
             for t in level:
                 kids = kids_of(t)
                 while len(kids) < 4:
-                    best, best_count = -1, leaf_size
-                    for c, (a, b, _) in enumerate(kids):
-                        if b - a + 1 > best_count:
-                            best, best_count = c, b - a + 1
+                    best, best_key = -1, None
+                    for c, (a, b, radix) in enumerate(kids):
+                        if b - a + 1 <= leaf_size:
+                            continue
+                        kid_key = b - a + 1 if key is None else (key[radix], b - a + 1)
+                        if best < 0 or kid_key > best_key:
+                            best, best_key = c, kid_key
                     if best < 0:
                         break
                     opened = kids_of(kids[best][2])

@@ -325,6 +325,15 @@ class HierarchyBuildInfo(C.Structure):
                 ("stageMs", C.c_float * HIERARCHY_BUILD_STAGES), ("totalMs", C.c_float), ("reserved2", C.c_uint32)]
 
 
+# the GPU builder's method (prosper_pt_set_gpu_hierarchy_method; prosper_amd/ploc.py states the PLOC rule)
+GPU_HIERARCHY_LINEAR, GPU_HIERARCHY_PLOC = 0, 1
+
+
+class GpuHierarchyMethodInfo(C.Structure):
+    _fields_ = [("selectedMethod", C.c_uint32), ("selectedRadius", C.c_uint32), ("method", C.c_uint32), ("radius", C.c_uint32),
+                ("rounds", C.c_uint32), ("finishRounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 # ---- keyframe animation (prosper_pt_set_animations / prosper_pt_animate) ----
 ANIMATION_NONE = 0xFFFFFFFF
 NODE_HAS_TRANSLATION, NODE_HAS_ROTATION, NODE_HAS_SCALE, NODE_DIRECTIONAL_LIGHT, NODE_CAMERA = 1, 2, 4, 8, 16

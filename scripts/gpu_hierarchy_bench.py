@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""The GPU hierarchy build (prosper_pt_build_hierarchy_gpu) beside the host builder, on S-sponza-class (C3),
-C4 and the FlightHelmet fixture: device milliseconds per stage (events) and the wall time of the call; the host's
-prosper_pt_rebuild_hierarchy on the same state with every instance moved, interleaved with it; the frame time at
-1920x1080 x 8 spp on one chain under the host tree and under the GPU tree at leaf sizes 1, 2 and 4, interleaved; and the
-drift scenario of scripts/drift_rebuild_bench.py with either builder selected.  One JSON object on stdout
-(profiles/f24_gpu_hierarchy_bench.json); run on the GPU box.
+"""The GPU hierarchy build (prosper_pt_build_hierarchy_gpu) beside the host builder, on
+S-sponza-class (C3), C4 and the FlightHelmet fixture: device milliseconds per stage (events) and the wall time of the call,
+for the linear method and the PLOC method (with its round counts); the host's prosper_pt_rebuild_hierarchy on the same
+state with every instance moved, interleaved with them; the frame time at 1920x1080 x 8 spp on one chain under the host
+tree, under the linear tree at leaf sizes 1, 2 and 4 and under the PLOC tree at radii 8, 16 and 32 and the same leaf sizes,
+interleaved, with the run-to-run spread of every one of them; and the drift scenario of scripts/drift_rebuild_bench.py with
+the host builder, the GPU builder and the GPU builder's PLOC method.  One JSON object on stdout
+(profiles/f26_ploc_bench.json; profiles/f24_gpu_hierarchy_bench.json is the run before the method axis); run on the GPU box.
 
-    python scripts/gpu_hierarchy_bench.py [--scenes c3,c4,helmet] [--repeats 5] [--no-drift]"""
+    python scripts/gpu_hierarchy_bench.py [--scenes c3,c4,helmet] [--repeats 5] [--rounds 5] [--no-drift]"""
 import argparse
 import copy
 import ctypes
@@ -71,7 +73,25 @@ def frame_ms(ctx, cam, focal, ibl, repeats):
     return statistics.median(device), statistics.median(wall)
 
 
-def bench_scene(name, base, repeats):
+PLOC_RADII, LEAF_SIZES = (8, 16, 32), (1, 2, 4)
+
+
+def select(ctx, tree):
+    """`tree` is host, gpu_leafL (the linear method) or ploc_rR_leafL: selects method and leaf size, builds."""
+    if tree == "host":
+        capi.debug(leafSize=None)
+        ctx.rebuild_hierarchy()
+        return
+    parts = tree.split("_")
+    capi.debug(leafSize=int(parts[-1][4:]))
+    if parts[0] == "ploc":
+        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_PLOC, int(parts[1][1:]))
+    else:
+        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_LINEAR)
+    ctx.build_hierarchy_gpu()
+
+
+def bench_scene(name, base, repeats, rounds):
     out = {"triangles": base.triangle_count(), "instances": len(base.model_instances)}
     ibl = base.skybox is not None
     cam, focal = Camera.from_world(base, W, H).update_buffer()
@@ -80,49 +100,67 @@ def bench_scene(name, base, repeats):
     out["host_upload_bvh_ms"] = ctx.scene_stats().bvhBuildSeconds * 1e3
     # ---- builds: every instance moved before each one, host and GPU interleaved ----
     poses = [moved(base, (0.01 * (k + 1), 0.0, 0.0)) for k in range(2)]
-    host_wall, gpu_wall, gpu_total, stages = [], [], [], []
+    methods = {"gpu": (S.GPU_HIERARCHY_LINEAR, 0), "ploc": (S.GPU_HIERARCHY_PLOC, 0)}  # (each with its default leaf size)
+    host_wall = []
+    gpu = {m: {"wall": [], "total": [], "stages": [], "how": None} for m in methods}
     for k in range(repeats + 1):
         ctx.update_transforms(poses[k % 2])
         ms = wall_ms(ctx.rebuild_hierarchy)
-        ctx.update_transforms(poses[(k + 1) % 2])
-        g = wall_ms(ctx.build_hierarchy_gpu)
-        info = ctx.hierarchy_build_info()
         if k:  # (the first round allocates)
             host_wall.append(ms)
-            gpu_wall.append(g)
-            gpu_total.append(info.totalMs)
-            stages.append(list(info.stageMs))
+        for i, (m, (method, radius)) in enumerate(methods.items()):
+            ctx.update_transforms(poses[(k + 1 + i) % 2])
+            ctx.set_gpu_hierarchy_method(method, radius)
+            g = wall_ms(ctx.build_hierarchy_gpu)
+            info, how = ctx.hierarchy_build_info(), ctx.gpu_hierarchy_method_info()
+            if k:
+                gpu[m]["wall"].append(g)
+                gpu[m]["total"].append(info.totalMs)
+                gpu[m]["stages"].append(list(info.stageMs))
+                gpu[m]["how"] = {"leafSize": info.leafSize, "radius": how.radius, "rounds": how.rounds,
+                                 "rounds_in_one_workgroup": how.finishRounds}
     out["host_rebuild_all_moved_wall_ms"] = {"median": statistics.median(host_wall), "runs": host_wall}
-    out["gpu_build_wall_ms"] = {"median": statistics.median(gpu_wall), "runs": gpu_wall}
-    out["gpu_build_device_ms"] = {"median": statistics.median(gpu_total), "runs": gpu_total}
-    out["gpu_build_stage_ms"] = {n: statistics.median(s[i] for s in stages) for i, n in enumerate(S.HIERARCHY_BUILD_STAGE_NAMES)}
-    # ---- frame time under each tree, interleaved ----
+    for m, runs in gpu.items():
+        out["%s_build_wall_ms" % m] = {"median": statistics.median(runs["wall"]), "runs": runs["wall"]}
+        out["%s_build_device_ms" % m] = {"median": statistics.median(runs["total"]), "runs": runs["total"]}
+        out["%s_build_stage_ms" % m] = {n: statistics.median(s[i] for s in runs["stages"]) for i, n in enumerate(S.HIERARCHY_BUILD_STAGE_NAMES)}
+        out["%s_build" % m] = runs["how"]
+    # ---- frame time under each tree, interleaved; one figure per round (the median of its repeats), the spread between
+    #      the rounds is the run-to-run spread of that measurement ----
     ctx.update_transforms(base)
-    frames = {"host": [], "gpu_leaf1": [], "gpu_leaf2": [], "gpu_leaf4": []}
+    names = ["host"] + ["gpu_leaf%d" % leaf for leaf in LEAF_SIZES] + \
+            ["ploc_r%d_leaf%d" % (radius, leaf) for radius in PLOC_RADII for leaf in LEAF_SIZES]
+    frames = {tree: [] for tree in names}
     trees = {}
-    for rnd in range(3):
+    for rnd in range(rounds):
         for tree in frames:
-            if tree == "host":
-                capi.debug(leafSize=None)
-                ctx.rebuild_hierarchy()
-            else:
-                capi.debug(leafSize=int(tree[-1]))
-                ctx.build_hierarchy_gpu()
-            info = ctx.hierarchy_build_info()
-            trees[tree] = {"nodes": info.nodeCount, "levels": info.levels, "stackBound": info.stackBound}
+            select(ctx, tree)
+            info, how = ctx.hierarchy_build_info(), ctx.gpu_hierarchy_method_info()
+            trees[tree] = {"nodes": info.nodeCount, "levels": info.levels, "stackBound": info.stackBound, "rounds": how.rounds,
+                           "rounds_in_one_workgroup": how.finishRounds}
             frames[tree].append(frame_ms(ctx, cam, focal, ibl, repeats))
     capi.debug(leafSize=None)
-    out["frame_1920x1080x8spp_one_chain"] = {
+    ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_LINEAR)
+    table = out["frame_1920x1080x8spp_one_chain"] = {
         tree: dict(trees[tree], device_ms=statistics.median(d for d, _ in runs), wall_ms=statistics.median(w for _, w in runs),
-                   device_ms_runs=[d for d, _ in runs]) for tree, runs in frames.items()}
-    host = out["frame_1920x1080x8spp_one_chain"]["host"]["device_ms"]
+                   device_ms_runs=[d for d, _ in runs], spread_ms=max(d for d, _ in runs) - min(d for d, _ in runs))
+        for tree, runs in frames.items()}
+    host = table["host"]["device_ms"]
     for tree in frames:
-        out["frame_1920x1080x8spp_one_chain"][tree]["ratio_to_host"] = out["frame_1920x1080x8spp_one_chain"][tree]["device_ms"] / host
+        table[tree]["ratio_to_host"] = table[tree]["device_ms"] / host
+    # PLOC counts as faster to trace than the linear tree only where its frame is lower by more than the spread of either
+    linear = min((t for t in names if t.startswith("gpu_")), key=lambda t: table[t]["device_ms"])
+    best = min((t for t in names if t.startswith("ploc_")), key=lambda t: table[t]["device_ms"])
+    spread = max(table[linear]["spread_ms"], table[best]["spread_ms"])
+    out["ploc_against_linear"] = {
+        "best_linear": linear, "best_ploc": best, "linear_ms": table[linear]["device_ms"], "ploc_ms": table[best]["device_ms"],
+        "spread_ms": spread, "ratio": table[best]["device_ms"] / table[linear]["device_ms"],
+        "ploc_is_faster": table[linear]["device_ms"] - table[best]["device_ms"] > spread}
     ctx.close()
     return out
 
 
-def drift(builder, steps=240, threshold=1.3):
+def drift(builder, steps=240, threshold=1.3, method=S.GPU_HIERARCHY_LINEAR):
     """scripts/drift_rebuild_bench.py's loop with `builder` selected: 1-spp frames, three in flight, three instances moved
     every frame.  The measure is read when the host has waited for the device anyway (every third frame)."""
     base = scenes.sponza_class()
@@ -130,6 +168,7 @@ def drift(builder, steps=240, threshold=1.3):
     ctx = capi.Context(0)
     ctx.upload_scene(base)
     ctx.set_hierarchy_builder(builder)
+    ctx.set_gpu_hierarchy_method(method)
     poses = [moved(base, (0.12 * k, 0.016 * k, 0.032 * k), which=(3, 5, 7)) for k in range(steps)]
     times, update_ms, above = [], [], 0
     t0 = time.perf_counter()
@@ -159,17 +198,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c3,c4,helmet")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds over the trees of the frame-time table")
     ap.add_argument("--no-drift", action="store_true")
     args = ap.parse_args()
     make = {"c3": scenes.sponza_class, "c4": lambda: scenes.sponza_class(lights=True, foliage=True),
             "helmet": lambda: flight_helmet.load_fixture()}
-    result = {"what": "GPU hierarchy build (linear BVH) beside the host builder; frames 1920x1080 x 8 spp, one chain, all bounces",
+    result = {"what": "GPU hierarchy build (linear method, PLOC method) beside the host builder; frames 1920x1080 x 8 spp, one chain, all bounces",
               "scenes": {}}
     for name in args.scenes.split(","):
-        result["scenes"][name] = bench_scene(name, make[name](), args.repeats)
+        result["scenes"][name] = bench_scene(name, make[name](), args.repeats, args.rounds)
         print("%s done" % name, file=sys.stderr)
     if not args.no_drift:
-        result["drift_scenario"] = {"host_builder": drift(S.BUILDER_HOST), "gpu_builder": drift(S.BUILDER_GPU)}
+        result["drift_scenario"] = {"host_builder": drift(S.BUILDER_HOST), "gpu_builder": drift(S.BUILDER_GPU),
+                                    "gpu_builder_ploc": drift(S.BUILDER_GPU, method=S.GPU_HIERARCHY_PLOC)}
     print(json.dumps(result, indent=1))
 
 

@@ -157,8 +157,9 @@ def main():
                     help="with --raster: the G-buffer's draw type (MeshletID and PrimitiveID are the mesh shader's), shaded as that debug view")
     ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
-    ap.add_argument("--gpu-hierarchy", action="store_true",
-                    help="build the hierarchy once more on the GPU after the upload (and after --time's pose): a linear BVH, the same image")
+    ap.add_argument("--gpu-hierarchy", nargs="?", const="linear", default=None, metavar="linear|ploc[:radius]",
+                    help="build the hierarchy once more on the GPU after the upload (and after --time's pose), the same image: "
+                         "a linear BVH (the default), or ploc[:radius] for the PLOC method with a search radius of 1 .. 32")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     ap.add_argument("--build-texture-cache", action="store_true",
                     help="compress every image whose prosper_cache file is missing or stale (GPU BC7 encoder) before loading")
@@ -225,8 +226,15 @@ def main():
         if pose.cameraValid and not args.eye and not args.target:
             world.camera.update(eye=tuple(pose.eye), target=tuple(pose.target), up=tuple(pose.up))
     if args.gpu_hierarchy:
+        method, _, radius = args.gpu_hierarchy.partition(":")
+        if method not in ("linear", "ploc") or (radius and (method != "ploc" or not radius.isdigit())):
+            ap.error("--gpu-hierarchy takes linear or ploc[:radius]")
+        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_PLOC if method == "ploc" else S.GPU_HIERARCHY_LINEAR, int(radius or 0))
         ctx.build_hierarchy_gpu()  # (flushes the pose --time staged first)
-        info = ctx.hierarchy_build_info()
+        info, how = ctx.hierarchy_build_info(), ctx.gpu_hierarchy_method_info()
+        if how.method == S.GPU_HIERARCHY_PLOC:
+            print("GPU hierarchy: PLOC, radius %d, %d rounds (%d of them in one workgroup)" % (how.radius, how.rounds, how.finishRounds),
+                  file=sys.stderr)
         print("GPU hierarchy: %d nodes, %d levels, stack bound %d, leaves of at most %d, %.3f ms on the device (%s)" % (
             info.nodeCount, info.levels, info.stackBound, info.leafSize, info.totalMs,
             ", ".join("%s %.3f" % (n, ms) for n, ms in zip(S.HIERARCHY_BUILD_STAGE_NAMES, info.stageMs))), file=sys.stderr)
