@@ -729,7 +729,8 @@ int prosper_pt_debug_read_nodes(prosper_pt_ctx *ctx, void *out, size_t byte_size
  * prosper_pt_set_hierarchy_builder: PROSPER_PT_BUILDER_HOST (the default) changes nothing.  With PROSPER_PT_BUILDER_GPU,
  * prosper_pt_rebuild_hierarchy runs the GPU build, and so does an update whose refits have degraded the tree past
  * rebuildCostRatio - inside that call, in place of the worker thread.  prosper_pt_upload_scene and prosper_pt_update_meshes
- * build on the host in either mode.  After a GPU build the next host build splits every instance again. */
+ * build on the host in either mode, unless prosper_pt_set_gpu_hierarchy_sites (below) gives them to the GPU builder.  After a
+ * GPU build the next host build splits every instance again. */
 #define PROSPER_PT_BUILDER_HOST 0u
 #define PROSPER_PT_BUILDER_GPU 1u
 int prosper_pt_build_hierarchy_gpu(prosper_pt_ctx *ctx);
@@ -776,6 +777,32 @@ typedef struct prosper_pt_gpu_hierarchy_method_info
 } prosper_pt_gpu_hierarchy_method_info;
 /* Needs no scene: without one only the selection is filled. */
 int prosper_pt_get_gpu_hierarchy_method_info(prosper_pt_ctx *ctx, prosper_pt_gpu_hierarchy_method_info *out);
+/* ---- the GPU builder's build sites (opt-in) ----
+ * Which of the builds that are not a rebuild the GPU builder makes: a mask of the sites below, 0 (none) by default and
+ * independent of prosper_pt_set_hierarchy_builder.  A mask with an unknown bit is refused with
+ * PROSPER_PT_ERR_INVALID_ARGUMENT and the selection stays as it was.  The call needs no scene and builds nothing; method,
+ * radius and leaf size are those of every other GPU build.
+ *   UPLOAD        prosper_pt_upload_scene makes the scene's first tree on the device: the flat world triangles never cross
+ *                 to the host and no host build runs.  Afterwards prosper_pt_hierarchy_build_info reports
+ *                 PROSPER_PT_BUILDER_GPU with the build's stages (slot 0 is the launch that writes the world triangles, the
+ *                 shading and any-hit records and the centroid bounds in one pass), `rebuilds` is 0, costRatio 1, and
+ *                 bvhBuildSeconds is the wall time of the build section.  A tree that is refused (the stack bound,
+ *                 PROSPER_PT_ERR_UNSUPPORTED) fails the upload like any failed upload; there is no fall-back to the host:
+ *                 clear the bit and upload again.
+ *   MESH_UPDATES  the generations the worker thread builds for prosper_pt_update_meshes get their tree from the GPU builder,
+ *                 on the worker's own stream and in scratch arrays of the worker's own (grow-only, 152 bytes a triangle,
+ *                 plus 112 with the PLOC method, beside those of the synchronous GPU build); no subtree is kept.
+ *   DRIFT         an update whose refits have degraded the tree past rebuildCostRatio starts such a background generation
+ *                 with the GPU builder, under either selected builder, in place of the synchronous GPU rebuild and of the
+ *                 host's re-split; the call does not wait for the device.
+ * A refused or failed background build follows prosper_pt_update_meshes' contract: the call that would have switched to it
+ * reports it, the scene stays, the meshes wait.  A layout without triangles takes the host's path under every site.  The
+ * host builder's debug options flatBvh and noUploadRefit have no effect on a generation the GPU builder makes. */
+#define PROSPER_PT_GPU_BUILD_SITE_UPLOAD 1u       /* prosper_pt_upload_scene */
+#define PROSPER_PT_GPU_BUILD_SITE_MESH_UPDATES 2u /* the generations the worker thread builds for prosper_pt_update_meshes */
+#define PROSPER_PT_GPU_BUILD_SITE_DRIFT 4u        /* the re-split that drifting instances trigger: a background generation */
+int prosper_pt_set_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t sites);
+int prosper_pt_get_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t *sites);
 /* Test hook: the flat world triangles ((drawInstance, primitive) order, 48 bytes each) and the leaf-order permutation
  * (uint32 per triangle) as the device holds them; a staged update is flushed first. */
 int prosper_pt_debug_read_hierarchy_arrays(

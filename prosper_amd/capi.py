@@ -98,6 +98,8 @@ def lib():
     L.prosper_pt_get_hierarchy_build_info.argtypes = [vp, C.POINTER(S.HierarchyBuildInfo)]
     L.prosper_pt_set_gpu_hierarchy_method.argtypes = [vp, u32, u32]
     L.prosper_pt_get_gpu_hierarchy_method_info.argtypes = [vp, C.POINTER(S.GpuHierarchyMethodInfo)]
+    L.prosper_pt_set_gpu_hierarchy_sites.argtypes = [vp, u32]
+    L.prosper_pt_get_gpu_hierarchy_sites.argtypes = [vp, C.POINTER(u32)]
     L.prosper_pt_debug_read_hierarchy_arrays.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     L.prosper_pt_set_output_buffer.argtypes = [vp, vp, C.c_size_t]
     L.prosper_pt_render.argtypes = [
@@ -816,6 +818,16 @@ class Context:
         info = S.GpuHierarchyMethodInfo()
         _check(lib().prosper_pt_get_gpu_hierarchy_method_info(self._h, C.byref(info)))
         return info
+
+    def set_gpu_hierarchy_sites(self, sites):
+        """A mask of structs.GPU_BUILD_SITE_UPLOAD, _MESH_UPDATES and _DRIFT (0, the default: none): the builds besides
+        rebuilds that the GPU builder makes - the scene's first tree, the worker thread's generations, the drift re-split."""
+        _check(lib().prosper_pt_set_gpu_hierarchy_sites(self._h, sites))
+
+    def gpu_hierarchy_sites(self):
+        sites = C.c_uint32(0)
+        _check(lib().prosper_pt_get_gpu_hierarchy_sites(self._h, C.byref(sites)))
+        return int(sites.value)
 
     def hierarchy_build_info(self):
         info = S.HierarchyBuildInfo()

@@ -285,7 +285,9 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
 
     // ---- world triangles first: the host-side hierarchy build - the longest step of an upload - runs on the host's threads
     //      while this thread goes on with textures, packs, sky, lights and the alpha tables (begin_geometry); the flatten
-    //      kernel runs again in finish_geometry for the shading and any-hit records (the same world triangles a second time) ----
+    //      kernel runs again in finish_geometry for the shading and any-hit records (the same world triangles a second time).
+    //      With site UPLOAD of prosper_pt_set_gpu_hierarchy_sites there is no host build: finish_geometry touches the
+    //      triangles once and builds on the device ----
     AccelState *acc = new (std::nothrow) AccelState();
     if (!acc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
     ctx->accel = acc;
@@ -296,6 +298,9 @@ int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
     PPT_HIP(hipStreamSynchronize(nullptr));
     GeometryJob job;
     GeometryTarget target = context_target(ctx);
+    // (site UPLOAD: the first tree from the GPU builder - begin_geometry then only lays the triangles out, and everything
+    //  else happens in finish_geometry, in one pass over the geometry)
+    target.gpuTree = (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_UPLOAD) != 0;
     {
         GeometryLayout layout;
         if ((rc = layout_geometry(*gs, v->materials, layout))) return rc;
@@ -871,6 +876,7 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     for (const PassModule *m : kPassModules) m->destroy(ctx);
     destroy_animation_state(ctx);
     delete ctx->lbvh;
+    delete ctx->lbvhWorker;
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
@@ -973,6 +979,7 @@ static int rebuild_hierarchy_on_host(prosper_pt_ctx *ctx)
     PPT_HIP(hipDeviceSynchronize()); // renders in flight read the old hierarchy
     acc->stale = true;               // until the new hierarchy is up
     bool any = false;
+    if (acc->flat.size() != (size_t)acc->total) acc->flat.resize((size_t)acc->total); // (a first tree built on the GPU kept no host copy)
     for (size_t r = 0; r < acc->ranges.size(); ++r)
     {
         if (!(acc->movedSinceBuild[r] || !acc->instanced) || !acc->ranges[r].count) continue;
@@ -1320,6 +1327,9 @@ int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransf
     ctx->stats.bvhBuildSeconds = 0.0;
     ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (any && ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
+    // (site DRIFT: a background generation from the GPU builder under either selected builder; nothing waits for the device)
+    if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_DRIFT))
+        return ctx->meshBuild ? PROSPER_PT_OK : start_mesh_build(ctx, true);
     // (the GPU builder is quick enough for the synchronous route; the worker thread is the host builder's)
     if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
     if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild)
@@ -1379,7 +1389,8 @@ int prosper_pt_animate(prosper_pt_ctx *ctx, float timeS, uint32_t flags, void *s
     PPT_HIP(hipSetDevice(ctx->device));
     if ((rc = poll_refit_cost(acc, false))) return rc;
     if (ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
-    if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
+    const bool driftSite = (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_DRIFT) != 0; // (stage_transforms)
+    if (!driftSite && acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
     if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild && (rc = start_mesh_build(ctx, true))) return rc;
     if (!(flags & PROSPER_PT_UPDATE_NOW)) return PROSPER_PT_OK;
     return flush_pending_update(ctx, static_cast<hipStream_t>(stream));
@@ -1416,6 +1427,22 @@ int prosper_pt_set_gpu_hierarchy_method(prosper_pt_ctx *ctx, uint32_t method, ui
     if (radius > kPlocMaxRadius) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: the radius is 1 .. 32 (0: the default)");
     ctx->gpuHierarchyMethod = method;
     ctx->gpuHierarchyRadius = radius;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_set_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t sites)
+{
+    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_sites: null argument");
+    constexpr uint32_t known = PROSPER_PT_GPU_BUILD_SITE_UPLOAD | PROSPER_PT_GPU_BUILD_SITE_MESH_UPDATES | PROSPER_PT_GPU_BUILD_SITE_DRIFT;
+    if (sites & ~known) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_sites: unknown build site");
+    ctx->gpuHierarchySites = sites;
+    return PROSPER_PT_OK;
+}
+
+int prosper_pt_get_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t *sites)
+{
+    if (!ctx || !sites) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gpu_hierarchy_sites: null argument");
+    *sites = ctx->gpuHierarchySites;
     return PROSPER_PT_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cstddef>
 
 namespace ppt
 {
@@ -37,11 +38,7 @@ struct LbvhScalars
     uint32_t histogram[kLbvhMaxLevels];    // nodes per height
 };
 
-__device__ __forceinline__ uint32_t float_key(float f)
-{
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// (float_key, the other direction: pt_bvh_rule.hpp)
 __device__ __forceinline__ float key_float(uint32_t k)
 {
     return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
@@ -347,21 +344,39 @@ dim3 grid_for(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 } // namespace
 
+int lbvh_begin(LbvhState &st, uint32_t count, hipStream_t stream, uint32_t **bounds)
+{
+    static_assert(offsetof(LbvhScalars, centroidLo) == 0 && offsetof(LbvhScalars, centroidHi) == 3 * sizeof(uint32_t), "lo[3], hi[3] lead the scalars");
+    if (count == 0) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: nothing to build");
+    if (const int rc = reserve(st, count)) return rc;
+    PPT_HIP(hipEventRecord(st.events.events[kLbvhStageBounds], stream));
+    hipLaunchKernelGGL(lbvh_reset_kernel, dim3(1), dim3(kLbvhMaxLevels), 0, stream, reinterpret_cast<LbvhScalars *>(st.scalars));
+    PPT_HIP(hipGetLastError());
+    *bounds = st.scalars;
+    return PROSPER_PT_OK;
+}
+
 int lbvh_build(
-    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out)
+    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out,
+    bool boundsReady)
 {
     const bool ploc = method.method == PROSPER_PT_GPU_HIERARCHY_PLOC;
     if (count == 0 || leafSize == 0 || leafSize > kMaxLeafTriangles)
         return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: nothing to build, or a leaf size outside 1 .. 4");
-    if (const int rc = reserve(st, count)) return rc;
+    if (boundsReady && (!st.block.ptr || count > st.capacity))
+        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: the centroid bounds were not made for this build");
+    if (const int rc = reserve(st, count)) return rc; // (boundsReady: lbvh_begin has sized the arrays, nothing moves)
     LbvhScalars *s = reinterpret_cast<LbvhScalars *>(st.scalars);
     const uint32_t capacity = (uint32_t)st.capacity;
     hipEvent_t *ev = st.events.events;
     const dim3 block(256);
 
-    PPT_HIP(hipEventRecord(ev[kLbvhStageBounds], stream));
-    hipLaunchKernelGGL(lbvh_reset_kernel, dim3(1), dim3(kLbvhMaxLevels), 0, stream, s);
-    hipLaunchKernelGGL(lbvh_bounds_kernel, grid_for(count), block, 0, stream, flat, count, s);
+    if (!boundsReady)
+    {
+        PPT_HIP(hipEventRecord(ev[kLbvhStageBounds], stream));
+        hipLaunchKernelGGL(lbvh_reset_kernel, dim3(1), dim3(kLbvhMaxLevels), 0, stream, s);
+        hipLaunchKernelGGL(lbvh_bounds_kernel, grid_for(count), block, 0, stream, flat, count, s);
+    }
     PPT_HIP(hipEventRecord(ev[kLbvhStageCodes], stream));
     hipLaunchKernelGGL(lbvh_codes_kernel, grid_for(count), block, 0, stream, flat, count, s, st.codes, st.index);
     PPT_HIP(hipGetLastError());

@@ -74,8 +74,14 @@ struct LbvhResult
 // The build of `count` >= 1 triangles on `stream`, which has been waited for when this returns.  Results stay in the
 // state's arrays (nodes: child references and `reserved` only, the boxes are the refit's; perm; order).
 // PROSPER_PT_ERR_UNSUPPORTED: the stack bound exceeds kMaxStackBound.
+// boundsReady: the scalars already hold the centroid bounds of `flat` (lbvh_begin, then the caller's own launch on `stream`,
+// pt_kernels.hpp launch_flatten_triangles_bounds); the bounds kernel is skipped and stage slot 0 times the caller's launch.
 int lbvh_build(
-    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out);
+    LbvhState &st, const WorldTriangle *flat, uint32_t count, uint32_t leafSize, const LbvhMethod &method, hipStream_t stream, LbvhResult &out,
+    bool boundsReady = false);
+// Ahead of such a build: the arrays sized for `count` triangles, the start of stage 0 recorded, the scalars reset on `stream`.
+// *bounds: the six words the caller's launch reduces into (least keys per axis, then the greatest).
+int lbvh_begin(LbvhState &st, uint32_t count, hipStream_t stream, uint32_t **bounds);
 // After a refit of a GPU-built tree (nodes by height in `order`, `levelOffsets` on the host): every inner child's stored box
 // grown to contain the stored boxes of that child's own children; boxes only grow, nodes that nest already keep their bytes.
 void launch_lbvh_nest_boxes(BvhNode *nodes, const uint32_t *order, const uint32_t *levelOffsets, uint32_t levels, hipStream_t stream);

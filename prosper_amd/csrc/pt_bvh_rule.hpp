@@ -29,6 +29,14 @@ PPT_RULE void lbvh_centroid(const float *tri, float c[3])
     }
 }
 
+// an unsigned key whose order is the floats' own: the centroid bounds are integer minima and maxima of these
+PPT_RULE uint32_t float_key(float f)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &f, sizeof u);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // the cell of c on an axis whose centroid bounds are [lo, hi]: 21 bits, 0 on an axis without extent, the top clamped
 PPT_RULE uint32_t lbvh_quantise(float c, float lo, float hi)
 {

@@ -362,6 +362,10 @@ struct prosper_pt_ctx
     uint32_t hierarchyBuilder = PROSPER_PT_BUILDER_HOST; // prosper_pt_set_hierarchy_builder
     uint32_t gpuHierarchyMethod = PROSPER_PT_GPU_HIERARCHY_LINEAR, gpuHierarchyRadius = 0; // prosper_pt_set_gpu_hierarchy_method (0: the default radius)
     ppt::LbvhState *lbvh = nullptr;
+    // prosper_pt_set_gpu_hierarchy_sites: the builds the GPU builder makes besides rebuilds (PROSPER_PT_GPU_BUILD_SITE_*), and
+    // the scratch of those the worker thread runs (pt_geometry.hpp GeometryTarget::lbvh); grow-only like `lbvh`
+    uint32_t gpuHierarchySites = 0;
+    ppt::LbvhState *lbvhWorker = nullptr;
     ppt::DeviceBuffer toneLut; // dim^3 R9G9B9E5 texels
     uint32_t toneLutDim = 0;
     ppt::DeviceBuffer toneScratch; // RGBA8 output when the caller only wants a host copy

@@ -44,6 +44,9 @@ GeometryTarget context_target(prosper_pt_ctx *ctx)
     t.buildOpt = build_options(ctx);
     t.flatBvh = ctx->debug.flatBvh != 0;
     t.noUploadRefit = ctx->debug.noUploadRefit != 0;
+    t.lbvh = &ctx->lbvh;
+    t.gpuMethod = ctx->gpuHierarchyMethod;
+    t.gpuRadius = ctx->gpuHierarchyRadius;
     return t;
 }
 
@@ -279,31 +282,54 @@ int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResul
     return PROSPER_PT_OK;
 }
 
-// The GPU builder's counterpart of build + upload_hierarchy (pt_bvh_build.hpp): the tree is made from the
-// device's own flat world triangles into the build's scratch arrays; only when its stack bound has been accepted are the
-// scene's arrays written - device-to-device copies, the leaf positions, the permuted triangles, the first refit, which
-// writes every origin and child box.  A refused build leaves the scene exactly as it was.  The caller has synchronised
-// the device; the target's stream has been waited for when this returns.
-int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t)
+// The GPU builder's counterpart of build + upload_hierarchy (pt_bvh_build.hpp), in two halves that the
+// synchronous rebuild and the build sites (finish_geometry) share.
+namespace
+{
+struct DeviceBuild
+{
+    LbvhState *st = nullptr;
+    LbvhMethod method;
+    uint32_t leafSize = 0;
+    LbvhResult built;
+};
+
+// The target's scratch state, made at first need.
+int device_build_state(GeometryTarget &t, LbvhState **out)
+{
+    if (!t.lbvh) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: the target has no scratch state");
+    if (!*t.lbvh) *t.lbvh = new (std::nothrow) LbvhState();
+    if (!*t.lbvh) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
+    *out = *t.lbvh;
+    return PROSPER_PT_OK;
+}
+
+// First half: the tree from the device's own flat world triangles into the build's scratch arrays.  Nothing of the scene
+// changes; a refused build (the stack bound) leaves it exactly as it was.
+int build_into_scratch(GeometryTarget &t, bool boundsReady, DeviceBuild &b)
 {
     AccelState *acc = t.acc;
     if (!acc->total) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "GPU hierarchy build: the scene has no triangles");
-    if (!ctx->lbvh) ctx->lbvh = new (std::nothrow) LbvhState();
-    if (!ctx->lbvh) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-    LbvhState &st = *ctx->lbvh;
+    if (const int rc = device_build_state(t, &b.st)) return rc;
     static_assert(sizeof(acc->gpuStageMs) / sizeof(float) == kLbvhStageCount, "one slot per stage");
-    LbvhMethod method;
-    method.method = ctx->gpuHierarchyMethod;
-    const bool ploc = method.method == PROSPER_PT_GPU_HIERARCHY_PLOC;
-    if (ploc) method.radius = ctx->gpuHierarchyRadius ? ctx->gpuHierarchyRadius : kPlocDefaultRadius;
-    const uint32_t leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles)
-                                                  : (ploc ? kPlocDefaultLeafSize : kLbvhDefaultLeafSize);
-    LbvhResult built;
-    int rc;
+    b.method.method = t.gpuMethod;
+    const bool ploc = b.method.method == PROSPER_PT_GPU_HIERARCHY_PLOC;
+    if (ploc) b.method.radius = t.gpuRadius ? t.gpuRadius : kPlocDefaultRadius;
+    b.leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles)
+                                     : (ploc ? kPlocDefaultLeafSize : kLbvhDefaultLeafSize);
     acc->gpuStagesValid = false;
-    if ((rc = lbvh_build(st, acc->dFlat, (uint32_t)acc->total, leafSize, method, t.stream, built))) return rc;
+    return lbvh_build(*b.st, acc->dFlat, (uint32_t)acc->total, b.leafSize, b.method, t.stream, b.built, boundsReady);
+}
 
-    // ---- accepted: from here on the scene's arrays change ----
+// Second half, once the stack bound has been accepted: the scene's arrays are written - device-to-device copies, the leaf
+// positions, the permuted triangles, the first refit, which writes every origin and child box.  The target's stream has
+// been waited for when this returns.
+int install_device_build(prosper_pt_ctx *ctx, GeometryTarget &t, DeviceBuild &b)
+{
+    AccelState *acc = t.acc;
+    LbvhState &st = *b.st;
+    const LbvhResult &built = b.built;
+    int rc;
     acc->stale = true;
     const size_t n = built.nodeCount;
     if ((rc = reserve_node_array(ctx, acc, n * sizeof(BvhNode)))) return rc;
@@ -337,15 +363,25 @@ int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t)
     acc->stale = false;
     if ((rc = st.events.elapsed(acc->gpuStageMs))) return rc;
     acc->gpuStagesValid = true;
-    acc->gpuLeafSize = leafSize;
+    acc->gpuLeafSize = b.leafSize;
     acc->gpuDepths = built.depths;
-    acc->gpuMethod = method.method;
-    acc->gpuRadius = method.radius;
+    acc->gpuMethod = b.method.method;
+    acc->gpuRadius = b.method.radius;
     acc->gpuRounds = built.ploc.rounds;
     acc->gpuFinishRounds = built.ploc.finishRounds;
     t.stats->nodeCount = built.nodeCount;
     t.stats->maxDepth = built.stackBound;
     return PROSPER_PT_OK;
+}
+} // namespace
+
+// Both halves: a refused build leaves the scene exactly as it was.  The synchronous rebuild's caller has synchronised the
+// device; the target's stream has been waited for when this returns.
+int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t, bool boundsReady)
+{
+    DeviceBuild b;
+    if (const int rc = build_into_scratch(t, boundsReady, b)) return rc;
+    return install_device_build(ctx, t, b);
 }
 
 int layout_geometry(const GeometryState &gs, const prosper_MaterialData *materials, GeometryLayout &out)
@@ -425,6 +461,21 @@ int begin_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryLayout &layou
     if ((rc = device_alloc(ctx, triBytes, &d))) return rc;
     acc->dFlat = static_cast<WorldTriangle *>(d);
     t.lap("tables, allocations");
+    // a tree from the GPU builder: the triangles are written once, by finish_geometry's launch, when the tables of the
+    // any-hit records are there too; none crosses to the host, no host build starts, acc->flat stays empty.  What refits
+    // and later host rebuilds need of the layout is kept all the same.
+    job.gpuTree = t.gpuTree && total > 0;
+    if (job.gpuTree)
+    {
+        PPT_HIP(hipStreamSynchronize(t.stream)); // (the layout's host arrays have been read)
+        acc->flat.clear();
+        acc->triOffsets.swap(layout.triOffsets);
+        acc->ranges.swap(layout.ranges);
+        acc->rangeModelInstance.swap(layout.rangeModelInstance);
+        acc->total = total;
+        acc->drawInstanceCount = drawInstanceCount;
+        return PROSPER_PT_OK;
+    }
     launch_flatten_triangles(s, acc->dOffsets, drawInstanceCount, acc->dFlags, acc->dFlat, nullptr, nullptr, (uint32_t)total, t.stream);
     PPT_HIP(hipGetLastError());
     acc->flat.resize((size_t)total);
@@ -501,6 +552,33 @@ int finish_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryJob &job)
     acc->dTris = static_cast<WorldTriangle *>(dTris);
     acc->dTrisV[acc->versions.cur] = acc->dTris;
     s.triangles = acc->dTris;
+
+    if (job.gpuTree)
+    {
+        // One pass over the geometry: the world triangles, the records and the centroid bounds the build starts from
+        // (pt_kernels.hip flatten_triangles_bounds_kernel); then the GPU builder's two halves, which make the allocations
+        // upload_hierarchy makes and leave the AccelState as a synchronous GPU build leaves it.  A refused tree fails
+        // the generation: there is no fall-back to the host's builder.
+        const auto tBuild = std::chrono::steady_clock::now();
+        LbvhState *lbvh = nullptr;
+        uint32_t *bounds = nullptr;
+        if ((rc = device_build_state(t, &lbvh))) return rc;
+        if ((rc = lbvh_begin(*lbvh, (uint32_t)total, t.stream, &bounds))) return rc;
+        launch_flatten_triangles_bounds(
+            s, acc->dOffsets, acc->drawInstanceCount, acc->dFlags, acc->dFlat, static_cast<ShadeTriangle *>(dShade),
+            const_cast<AlphaTriangle *>(s.alphaTriangles), (uint32_t)total, bounds, t.stream);
+        PPT_HIP(hipGetLastError());
+        if ((rc = build_hierarchy_on_device(ctx, t, true))) return rc;
+        t.lap("records + GPU build");
+        prosper_pt_scene_stats &st = *t.stats; // (nodeCount and maxDepth are the build's)
+        st.triangleCount = total;
+        st.nodeBytes = sizeof(BvhNode);
+        st.triangleBytes = sizeof(WorldTriangle);
+        st.bvhBuildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild).count();
+        st.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - job.t0).count();
+        st.alphaTriangleCount = job.alphaTotal;
+        return PROSPER_PT_OK;
+    }
 
     launch_flatten_triangles(
         s, acc->dOffsets, acc->drawInstanceCount, acc->dFlags, acc->dFlat, static_cast<ShadeTriangle *>(dShade),
@@ -611,7 +689,10 @@ static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild)
     b->acc->rebuilds = old->rebuilds + (rebuild ? 1u : 0u);
     // The subtrees of the last build move to the new generation.  (The old one keeps rendering with its node array; should it
     // have to be rebuilt before the switch, prosper_pt_rebuild_hierarchy waits for this build instead.)
-    const bool keep = old->instanced && ctx->debug.flatBvh == 0;
+    // (a generation the GPU builder makes - prosper_pt_set_gpu_hierarchy_sites: a build started for meshes goes by
+    // MESH_UPDATES, one started by the drift trigger by DRIFT - keeps no subtree; the old generation keeps its own)
+    const bool gpuTree = (ctx->gpuHierarchySites & (rebuild ? PROSPER_PT_GPU_BUILD_SITE_DRIFT : PROSPER_PT_GPU_BUILD_SITE_MESH_UPDATES)) != 0;
+    const bool keep = old->instanced && ctx->debug.flatBvh == 0 && !gpuTree;
     if (keep)
     {
         b->acc->bvh.swap(old->bvh);
@@ -634,6 +715,8 @@ static int start_mesh_build_impl(prosper_pt_ctx *ctx, bool rebuild)
     t.acc = b->acc;
     t.stats = &b->stats;
     t.alphaTriangleCount = &b->alphaTriangleCount;
+    t.gpuTree = gpuTree;
+    t.lbvh = &ctx->lbvhWorker; // (the worker's own scratch: never the arrays of a synchronous GPU rebuild)
     b->arrived.swap(gs->arrived);
     const int device = ctx->device;
     // debug option failNextUpdate: the worker gives up half way (the test of what a failed build leaves behind)

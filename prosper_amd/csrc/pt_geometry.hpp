@@ -36,6 +36,15 @@ struct GeometryTarget
     hipStream_t stream = nullptr;
     BvhBuildOptions buildOpt;
     bool flatBvh = false, noUploadRefit = false;
+    // The generation's tree comes from the GPU builder (prosper_pt_set_gpu_hierarchy_sites): begin_geometry
+    // reads no triangle back and starts no host build, finish_geometry builds and installs on the target's stream.  Set by
+    // the build site; a layout without triangles takes the host's path all the same.
+    bool gpuTree = false;
+    // The GPU builder's scratch (made at first need) and method: the context's own state for the context's target, a second
+    // one for the worker thread, so that a background build and a synchronous GPU rebuild on the calling thread can never
+    // share arrays.  Both only grow: 152 bytes a triangle each, plus 112 once the PLOC method has run in them.
+    LbvhState **lbvh = nullptr;
+    uint32_t gpuMethod = 0, gpuRadius = 0;
     // debug option buildTiming: where a build spends its time (stderr)
     std::chrono::steady_clock::time_point tick = std::chrono::steady_clock::now();
     void lap(const char *what)
@@ -54,8 +63,9 @@ int poll_refit_cost(AccelState *acc, bool wait);
 int enqueue_nest_boxes(AccelState *acc, BvhNode *nodes, hipStream_t stream);
 // nodes + leaf-order triangles of a freshly built hierarchy to the device, and what a later refit needs
 int upload_hierarchy(prosper_pt_ctx *ctx, GeometryTarget &t, const BvhBuildResult &bvh);
-// the same from the GPU builder: the tree made on the device from acc->dFlat, installed once its stack bound is accepted
-int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t);
+// the same from the GPU builder: the tree made on the device from acc->dFlat, installed once its stack bound is accepted.
+// boundsReady: the caller has reduced the centroid bounds into the scratch itself (finish_geometry's fused flatten launch).
+int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t, bool boundsReady = false);
 
 
 // ---- the geometry of the scene: where every draw instance's triangles live, the hierarchy over them, the per-triangle
@@ -87,6 +97,7 @@ struct GeometryJob
     std::future<BuildOutcome> build;
     std::chrono::steady_clock::time_point t0;
     uint64_t alphaTotal = 0;
+    bool gpuTree = false; // no host build was started: finish_geometry makes the tree on the device
 };
 
 int begin_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryLayout &layout, const std::vector<uint8_t> *changed, GeometryJob &job);
@@ -95,7 +106,8 @@ int finish_geometry(prosper_pt_ctx *ctx, GeometryTarget &t, GeometryJob &job);
 // ---- geometry generations built in the background (prosper_pt_update_meshes, drifted instances) ----
 // upload / destroy: the worker is waited for, its result dropped
 void discard_mesh_build(prosper_pt_ctx *ctx);
-// a worker for what the mirrors hold now (the caller has made sure none is running); rebuild: counts as a re-split
+// a worker for what the mirrors hold now (the caller has made sure none is running); rebuild: counts as a re-split.  The
+// GPU builder makes its tree where prosper_pt_set_gpu_hierarchy_sites says so: DRIFT for a re-split, MESH_UPDATES otherwise.
 int start_mesh_build(prosper_pt_ctx *ctx, bool rebuild = false);
 // the finished build becomes the scene; wait: block until nothing handed over so far is outstanding
 int poll_mesh_build(prosper_pt_ctx *ctx, bool wait);

@@ -1,6 +1,7 @@
 // pt_kernels.hip — gfx950 kernels of the path-tracing reference pass.
 //
 //   flatten_triangles   upload: bindless fp16 geometry x instance transforms -> world triangles
+//   flatten_triangles_bounds   the same with the records, and the centroid bounds of the GPU hierarchy build, in one pass
 //   permute_triangles   upload: reorder world triangles into BVH leaf order
 //   render_megakernel   one lane per pixel runs whole paths (rt/reference/main.rgen:225-299)
 //   blit_rgba16f        RGBA32F -> RGBA16F (src/render/RtReference.cpp:339-377)
@@ -12,6 +13,7 @@
 
 #include "bvh_encode.hpp"
 #include "pt_bc7.hpp"
+#include "pt_bvh_rule.hpp"
 #include "pt_device.hpp"
 #include "pt_render_common.hpp"
 
@@ -22,14 +24,14 @@ namespace ppt
 // upload kernels
 // ------------------------------------------------------------------------------------------
 
-__global__ void flatten_triangles_kernel(
-    DeviceScene s, const uint32_t *__restrict__ triOffsets, uint32_t drawInstanceCount,
+// World triangle g of the layout and, with shadeOut, its shading and any-hit records: the body of both flatten kernels.
+// `t`: the triangle as it was written.
+__device__ __forceinline__ void flatten_triangle(
+    const DeviceScene &s, const uint32_t *__restrict__ triOffsets, uint32_t drawInstanceCount,
     const uint32_t *__restrict__ drawInstanceFlags, WorldTriangle *__restrict__ out,
-    ShadeTriangle *__restrict__ shadeOut, AlphaTriangle *__restrict__ alphaOut, uint32_t total,
-    const uint32_t *__restrict__ leafPosition, WorldTriangle *__restrict__ leafOrder)
+    ShadeTriangle *__restrict__ shadeOut, AlphaTriangle *__restrict__ alphaOut, uint32_t g,
+    const uint32_t *__restrict__ leafPosition, WorldTriangle *__restrict__ leafOrder, WorldTriangle &t)
 {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= total) return;
     // find the draw instance whose triangle range holds g
     uint32_t lo = 0, hi = drawInstanceCount;
     while (hi - lo > 1)
@@ -51,7 +53,6 @@ __global__ void flatten_triangles_kernel(
     const f3 v0 = mul_point_mat3x4(load_r16g16b16a16(s, m.bufferIndex, m.positionsOffset, i0), modelToWorld);
     const f3 v1 = mul_point_mat3x4(load_r16g16b16a16(s, m.bufferIndex, m.positionsOffset, i1), modelToWorld);
     const f3 v2 = mul_point_mat3x4(load_r16g16b16a16(s, m.bufferIndex, m.positionsOffset, i2), modelToWorld);
-    WorldTriangle t;
     t.v0[0] = v0.x; t.v0[1] = v0.y; t.v0[2] = v0.z;
     t.v1[0] = v1.x; t.v1[1] = v1.y; t.v1[2] = v1.z;
     t.v2[0] = v2.x; t.v2[1] = v2.y; t.v2[2] = v2.z;
@@ -108,6 +109,62 @@ __global__ void flatten_triangles_kernel(
     }
 }
 
+__global__ void flatten_triangles_kernel(
+    DeviceScene s, const uint32_t *__restrict__ triOffsets, uint32_t drawInstanceCount,
+    const uint32_t *__restrict__ drawInstanceFlags, WorldTriangle *__restrict__ out,
+    ShadeTriangle *__restrict__ shadeOut, AlphaTriangle *__restrict__ alphaOut, uint32_t total,
+    const uint32_t *__restrict__ leafPosition, WorldTriangle *__restrict__ leafOrder)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    WorldTriangle t;
+    flatten_triangle(s, triOffsets, drawInstanceCount, drawInstanceFlags, out, shadeOut, alphaOut, g, leafPosition, leafOrder, t);
+}
+
+// The first tree of a scene built on the GPU (pt_geometry.cpp finish_geometry): one pass over the bindless
+// geometry writes the world triangles and their shading and any-hit records - flatten_triangles_kernel's own code - and
+// reduces the centroid bounds the hierarchy build starts from (pt_bvh_build.hip lbvh_bounds_kernel: integer min / max of
+// order-preserving keys, so the result does not depend on the order of arrival) - per wave across lanes, per workgroup
+// through LDS, then one atomic per bound and workgroup.  bounds: lo[3], hi[3], reset by the build (lbvh_begin).
+constexpr uint32_t kFlattenBoundsBlock = 256, kFlattenBoundsWaves = kFlattenBoundsBlock / 64;
+__global__ __launch_bounds__(kFlattenBoundsBlock) void flatten_triangles_bounds_kernel(
+    DeviceScene s, const uint32_t *__restrict__ triOffsets, uint32_t drawInstanceCount,
+    const uint32_t *__restrict__ drawInstanceFlags, WorldTriangle *__restrict__ out,
+    ShadeTriangle *__restrict__ shadeOut, AlphaTriangle *__restrict__ alphaOut, uint32_t total, uint32_t *bounds)
+{
+    __shared__ uint32_t part[kFlattenBoundsWaves][6];
+    const uint32_t g = blockIdx.x * kFlattenBoundsBlock + threadIdx.x;
+    uint32_t key[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u}; // lo[3], hi[3]
+    if (g < total)
+    {
+        WorldTriangle t;
+        flatten_triangle(s, triOffsets, drawInstanceCount, drawInstanceFlags, out, shadeOut, alphaOut, g, nullptr, nullptr, t);
+        const float tri[12] = {t.v0[0], t.v0[1], t.v0[2], 0.0f, t.v1[0], t.v1[1], t.v1[2], 0.0f, t.v2[0], t.v2[1], t.v2[2], 0.0f};
+        float c[3];
+        lbvh_centroid(tri, c);
+        for (int k = 0; k < 3; ++k) key[k] = key[3 + k] = float_key(c[k]);
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            key[k] = min(key[k], (uint32_t)__shfl_xor((int)key[k], off, 64));
+            key[3 + k] = max(key[3 + k], (uint32_t)__shfl_xor((int)key[3 + k], off, 64));
+        }
+    if ((threadIdx.x & 63u) == 0u)
+        for (int k = 0; k < 6; ++k) part[threadIdx.x >> 6][k] = key[k];
+    __syncthreads();
+    if (threadIdx.x < 6u)
+    {
+        const uint32_t k = threadIdx.x;
+        uint32_t v = part[0][k];
+        for (uint32_t w = 1; w < kFlattenBoundsWaves; ++w) v = k < 3u ? min(v, part[w][k]) : max(v, part[w][k]);
+        if (k < 3u)
+            atomicMin(&bounds[k], v);
+        else
+            atomicMax(&bounds[k], v);
+    }
+}
+
 __global__ void permute_triangles_kernel(
     const WorldTriangle *__restrict__ in, const uint32_t *__restrict__ permutation, WorldTriangle *__restrict__ out,
     uint32_t total)
@@ -130,6 +187,16 @@ void launch_flatten_triangles(
     hipLaunchKernelGGL(
         flatten_triangles_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, s, triOffsets, drawInstanceCount,
         drawInstanceFlags, out, shadeOut, alphaOut, total, leafPosition, leafOrder);
+}
+
+void launch_flatten_triangles_bounds(
+    const DeviceScene &s, const uint32_t *triOffsets, uint32_t drawInstanceCount, const uint32_t *drawInstanceFlags,
+    WorldTriangle *out, ShadeTriangle *shadeOut, AlphaTriangle *alphaOut, uint32_t total, uint32_t *bounds, hipStream_t stream)
+{
+    if (total == 0) return;
+    hipLaunchKernelGGL(
+        flatten_triangles_bounds_kernel, dim3((total + kFlattenBoundsBlock - 1) / kFlattenBoundsBlock), dim3(kFlattenBoundsBlock), 0,
+        stream, s, triOffsets, drawInstanceCount, drawInstanceFlags, out, shadeOut, alphaOut, total, bounds);
 }
 
 void launch_permute_triangles(

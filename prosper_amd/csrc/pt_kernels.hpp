@@ -23,6 +23,11 @@ void launch_flatten_triangles(
     const DeviceScene &s, const uint32_t *triOffsets, uint32_t drawInstanceCount, const uint32_t *drawInstanceFlags,
     WorldTriangle *out, ShadeTriangle *shadeOut, AlphaTriangle *alphaOut, uint32_t total, hipStream_t stream,
     const uint32_t *leafPosition = nullptr, WorldTriangle *leafOrder = nullptr);
+// flatten with the records and, in the same pass, the centroid bounds a GPU hierarchy build starts from: bounds[0..2] the
+// least, [3..5] the greatest order-preserving key per axis (pt_bvh_rule.hpp float_key), reset by the caller (lbvh_begin)
+void launch_flatten_triangles_bounds(
+    const DeviceScene &s, const uint32_t *triOffsets, uint32_t drawInstanceCount, const uint32_t *drawInstanceFlags,
+    WorldTriangle *out, ShadeTriangle *shadeOut, AlphaTriangle *alphaOut, uint32_t total, uint32_t *bounds, hipStream_t stream);
 // refit of an unchanged tree after moved instances: exact bounds level by level (`order` = nodes by height,
 // levelOffsets[levels + 1] on the HOST), then every node's boxes re-encoded; *cost += the tree's surface-area measure
 void launch_refit(

@@ -334,6 +334,10 @@ class GpuHierarchyMethodInfo(C.Structure):
                 ("rounds", C.c_uint32), ("finishRounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+# the builds the GPU builder makes besides rebuilds (prosper_pt_set_gpu_hierarchy_sites): a mask, 0 by default
+GPU_BUILD_SITE_UPLOAD, GPU_BUILD_SITE_MESH_UPDATES, GPU_BUILD_SITE_DRIFT = 1, 2, 4
+
+
 # ---- keyframe animation (prosper_pt_set_animations / prosper_pt_animate) ----
 ANIMATION_NONE = 0xFFFFFFFF
 NODE_HAS_TRANSLATION, NODE_HAS_ROTATION, NODE_HAS_SCALE, NODE_DIRECTIONAL_LIGHT, NODE_CAMERA = 1, 2, 4, 8, 16

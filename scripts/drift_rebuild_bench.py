@@ -4,7 +4,9 @@ out of the hall, moved EVERY frame; 1-spp frames, three in flight, host paced li
 re-split, which runs on the context's worker thread since round 4 (it was a synchronous 60-75 ms rebuild inside
 prosper_pt_update_transforms).  Tooling (profiles/r04_drift_rebuild.txt); run on the GPU box.
 
-    python scripts/drift_rebuild_bench.py [sync]        sync: debug option alwaysRebuild on the frame that would trigger"""
+    python scripts/drift_rebuild_bench.py [sync]        sync: debug option alwaysRebuild on the frame that would trigger
+    python scripts/drift_rebuild_bench.py gpu-background[:ploc]
+                                    the re-split as a background generation from the GPU builder (site DRIFT)"""
 import copy
 import ctypes
 import os
@@ -27,6 +29,10 @@ def main():
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_IBL | S.PC_FLAG_SKIP_HISTORY
     ctx = capi.Context(0)
     ctx.upload_scene(base)
+    mode = sys.argv[1] if len(sys.argv) > 1 else ""
+    if mode.startswith("gpu-background"):
+        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_PLOC if mode.endswith(":ploc") else S.GPU_HIERARCHY_LINEAR)
+        ctx.set_gpu_hierarchy_sites(S.GPU_BUILD_SITE_DRIFT)
     steps = 240
     poses = []
     for k in range(steps):
@@ -59,6 +65,8 @@ def main():
     print("%d frames, every one with three instances moved: %.3f ms per frame (median of groups of three), worst group %.3f ms per frame (group %d);"
           " prosper_pt_update_transforms %.3f ms median, worst %.3f ms; %d refits, %d re-splits on the worker thread, measure x%.2f at the end" % (
               steps, med, times[worst], worst, sorted(update_ms)[len(update_ms) // 2], max(update_ms), hs.refits, hs.rebuilds, hs.costRatio))
+    print("tree in use: %s builder, %d background generations installed" % (
+        "the GPU" if ctx.hierarchy_build_info().builder == S.BUILDER_GPU else "the host", hs.geometryInstalls))
     print("groups over 1.5 x the median: %s" % ", ".join("%d: %.2f ms" % (i, t) for i, t in enumerate(times) if t > 1.5 * med))
 
 

@@ -7,8 +7,11 @@ tree, under the linear tree at leaf sizes 1, 2 and 4 and under the PLOC tree at 
 interleaved, with the run-to-run spread of every one of them; and the drift scenario of scripts/drift_rebuild_bench.py with
 the host builder, the GPU builder and the GPU builder's PLOC method.  One JSON object on stdout
 (profiles/f26_ploc_bench.json; profiles/f24_gpu_hierarchy_bench.json is the run before the method axis); run on the GPU box.
+With --sites the build sites of DESIGN.md f27 instead (profiles/f27_gpu_build_sites_bench.json): uploads with the first tree
+from the host and from the GPU builder, alternating; stage slot 0 of those uploads (the fused launch) beside slot 0 of
+synchronous GPU rebuilds of the same scene; and the drift scenario with the re-split as a background GPU generation.
 
-    python scripts/gpu_hierarchy_bench.py [--scenes c3,c4,helmet] [--repeats 5] [--rounds 5] [--no-drift]"""
+    python scripts/gpu_hierarchy_bench.py [--scenes c3,c4,helmet] [--repeats 5] [--rounds 5] [--no-drift] [--sites]"""
 import argparse
 import copy
 import ctypes
@@ -160,17 +163,72 @@ def bench_scene(name, base, repeats, rounds):
     return out
 
 
-def drift(builder, steps=240, threshold=1.3, method=S.GPU_HIERARCHY_LINEAR):
+def spread(runs):
+    return max(runs) - min(runs)
+
+
+def bench_uploads(base, repeats):
+    """prosper_pt_upload_scene with the first tree from the host (sites 0: the path as it was) and from the GPU builder
+    (site UPLOAD) under both methods, alternating on one context after one warm-up upload each; then, on the same context,
+    synchronous GPU rebuilds of the same scene, whose stage slot 0 is lbvh_bounds_kernel's where a sited upload's is the
+    fused launch's."""
+    variants = {"host": (0, S.GPU_HIERARCHY_LINEAR), "gpu_linear": (S.GPU_BUILD_SITE_UPLOAD, S.GPU_HIERARCHY_LINEAR),
+                "gpu_ploc": (S.GPU_BUILD_SITE_UPLOAD, S.GPU_HIERARCHY_PLOC)}
+    view = base.view()
+    lib = capi.lib()
+    ctx = capi.Context(0, flags=S.CREATE_SINGLE_CHAIN)
+    runs = {v: {"wall": [], "build": [], "bvh": [], "stages": []} for v in variants}
+    for k in range(repeats + 1):
+        for v, (sites, method) in variants.items():
+            ctx.set_gpu_hierarchy_sites(sites)
+            ctx.set_gpu_hierarchy_method(method)
+            ms = wall_ms(lambda: capi._check(lib.prosper_pt_upload_scene(ctx._h, ctypes.byref(view))))
+            stats, info = ctx.scene_stats(), ctx.hierarchy_build_info()
+            assert info.builder == (S.BUILDER_GPU if sites else S.BUILDER_HOST)
+            if k:  # (the first upload of each variant allocates; the first of the process is slower still)
+                runs[v]["wall"].append(ms)
+                runs[v]["build"].append(stats.buildSeconds * 1e3)
+                runs[v]["bvh"].append(stats.bvhBuildSeconds * 1e3)
+                runs[v]["stages"].append(list(info.stageMs))
+    out = {}
+    for v, r in runs.items():
+        out[v] = {"upload_wall_ms": {"median": statistics.median(r["wall"]), "spread": spread(r["wall"]), "runs": r["wall"]},
+                  "buildSeconds_ms": {"median": statistics.median(r["build"]), "spread": spread(r["build"])},
+                  "bvhBuildSeconds_ms": {"median": statistics.median(r["bvh"]), "spread": spread(r["bvh"])}}
+        if v != "host":
+            out[v]["stage_ms"] = {n: statistics.median(st[i] for st in r["stages"]) for i, n in enumerate(S.HIERARCHY_BUILD_STAGE_NAMES)}
+            out[v]["fused_launch_ms"] = {"median": statistics.median(st[0] for st in r["stages"]), "spread": spread([st[0] for st in r["stages"]])}
+            gap = out["host"]["upload_wall_ms"]["median"] - out[v]["upload_wall_ms"]["median"]
+            out[v]["faster_than_host_upload"] = gap > max(out["host"]["upload_wall_ms"]["spread"], out[v]["upload_wall_ms"]["spread"])
+            out[v]["upload_wall_ms_saved"] = gap
+    # slot 0 of synchronous rebuilds of the same scene in the same run: reset + lbvh_bounds_kernel
+    ctx.set_gpu_hierarchy_sites(0)
+    ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_LINEAR)
+    ctx.upload_scene(base)
+    slot0 = []
+    for k in range(repeats + 1):
+        ctx.build_hierarchy_gpu()
+        if k:
+            slot0.append(ctx.hierarchy_build_info().stageMs[0])
+    out["synchronous_rebuild_bounds_stage_ms"] = {"median": statistics.median(slot0), "spread": spread(slot0)}
+    ctx.close()
+    return out
+
+
+def drift(builder, steps=240, threshold=1.3, method=S.GPU_HIERARCHY_LINEAR, sites=0):
     """scripts/drift_rebuild_bench.py's loop with `builder` selected: 1-spp frames, three in flight, three instances moved
-    every frame.  The measure is read when the host has waited for the device anyway (every third frame)."""
+    every frame.  The measure is read when the host has waited for the device anyway (every third frame).  sites: the GPU
+    builder's build sites (DRIFT: the re-split as a background generation from the GPU builder)."""
     base = scenes.sponza_class()
     cam, focal = Camera.from_world(base, W, H).update_buffer()
     ctx = capi.Context(0)
     ctx.upload_scene(base)
     ctx.set_hierarchy_builder(builder)
     ctx.set_gpu_hierarchy_method(method)
+    ctx.set_gpu_hierarchy_sites(sites)
     poses = [moved(base, (0.12 * k, 0.016 * k, 0.032 * k), which=(3, 5, 7)) for k in range(steps)]
     times, update_ms, above = [], [], 0
+    seen = []  # (frame, geometryInstalls, geometryBuildRunning) wherever the state is read
     t0 = time.perf_counter()
     for k, world in enumerate(poses):
         t1 = time.perf_counter()
@@ -180,8 +238,10 @@ def drift(builder, steps=240, threshold=1.3, method=S.GPU_HIERARCHY_LINEAR):
         if k % 3 == 2:
             hip.hipDeviceSynchronize()
             times.append((time.perf_counter() - t0) * 1e3 / 3)
-            if ctx.hierarchy_state().costRatio > threshold:
+            hs = ctx.hierarchy_state()
+            if hs.costRatio > threshold:
                 above += 3
+            seen.append((k, hs.geometryInstalls, hs.geometryBuildRunning))
             t0 = time.perf_counter()
     hip.hipDeviceSynchronize()
     ctx.finish_mesh_updates()
@@ -190,6 +250,16 @@ def drift(builder, steps=240, threshold=1.3, method=S.GPU_HIERARCHY_LINEAR):
            "worst_update_call_ms": max(update_ms), "median_update_call_ms": statistics.median(update_ms),
            "frames_above_cost_threshold": above, "rebuilds": hs.rebuilds, "refits": hs.refits,
            "geometryInstalls": hs.geometryInstalls, "cost_ratio_at_end": hs.costRatio}
+    # a background generation: the frames from the first reading that saw it running to the first that saw it installed
+    # (the state is read every third frame: each figure is exact to three frames; None: it was installed at the end)
+    waits, started = [], None
+    for (k, installs, running), (_, before, _) in zip(seen[1:], seen):
+        if running and started is None:
+            started = k
+        if installs > before:
+            waits.append(k - started if started is not None else 0)
+            started = k if running else None
+    out["frames_from_trigger_to_install"] = waits
     ctx.close()
     return out
 
@@ -200,11 +270,25 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5, help="interleaved rounds over the trees of the frame-time table")
     ap.add_argument("--no-drift", action="store_true")
+    ap.add_argument("--sites", action="store_true", help="the build sites (DESIGN.md f27) in place of the builds and frame times")
     args = ap.parse_args()
     make = {"c3": scenes.sponza_class, "c4": lambda: scenes.sponza_class(lights=True, foliage=True),
             "helmet": lambda: flight_helmet.load_fixture()}
     result = {"what": "GPU hierarchy build (linear method, PLOC method) beside the host builder; frames 1920x1080 x 8 spp, one chain, all bounces",
               "scenes": {}}
+    if args.sites:
+        result["what"] = "GPU builder's build sites: uploads with the first tree from the host / the GPU builder, the fused launch, the drift scenario"
+        for name in args.scenes.split(","):
+            result["scenes"][name] = dict(bench_uploads(make[name](), args.repeats), triangles=make[name]().triangle_count())
+            print("%s done" % name, file=sys.stderr)
+        if not args.no_drift:
+            rows = {"host_builder": dict(builder=S.BUILDER_HOST), "gpu_builder": dict(builder=S.BUILDER_GPU),
+                    "gpu_builder_ploc": dict(builder=S.BUILDER_GPU, method=S.GPU_HIERARCHY_PLOC),
+                    "gpu_background_linear": dict(builder=S.BUILDER_HOST, sites=S.GPU_BUILD_SITE_DRIFT),
+                    "gpu_background_ploc": dict(builder=S.BUILDER_HOST, sites=S.GPU_BUILD_SITE_DRIFT, method=S.GPU_HIERARCHY_PLOC)}
+            result["drift_scenario"] = {row: drift(**how) for row, how in rows.items()}
+        print(json.dumps(result, indent=1))
+        return
     for name in args.scenes.split(","):
         result["scenes"][name] = bench_scene(name, make[name](), args.repeats, args.rounds)
         print("%s done" % name, file=sys.stderr)

@@ -160,6 +160,9 @@ def main():
     ap.add_argument("--gpu-hierarchy", nargs="?", const="linear", default=None, metavar="linear|ploc[:radius]",
                     help="build the hierarchy once more on the GPU after the upload (and after --time's pose), the same image: "
                          "a linear BVH (the default), or ploc[:radius] for the PLOC method with a search radius of 1 .. 32")
+    ap.add_argument("--gpu-first-tree", nargs="?", const="linear", default=None, metavar="linear|ploc[:radius]",
+                    help="build the scene's first tree on the GPU, inside the upload (site UPLOAD of "
+                         "prosper_pt_set_gpu_hierarchy_sites): no host build, the same image")
     ap.add_argument("--time-step", type=float, default=1.0 / 60.0, help="with --time and --taa: seconds per jittered frame")
     ap.add_argument("--build-texture-cache", action="store_true",
                     help="compress every image whose prosper_cache file is missing or stale (GPU BC7 encoder) before loading")
@@ -214,8 +217,29 @@ def main():
     if args.cull_stats or args.raster:
         print("meshlets: %d over %d meshes" % (world.add_meshlets(), len(world.metadatas)))
     ctx = capi.Context(0, flags=S.CREATE_TEXTURE_MIPS if args.texture_lod else 0)
+
+    def gpu_method(option, text):
+        method, _, radius = text.partition(":")
+        if method not in ("linear", "ploc") or (radius and (method != "ploc" or not radius.isdigit())):
+            ap.error("%s takes linear or ploc[:radius]" % option)
+        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_PLOC if method == "ploc" else S.GPU_HIERARCHY_LINEAR, int(radius or 0))
+
+    def print_gpu_build(what):
+        info, how = ctx.hierarchy_build_info(), ctx.gpu_hierarchy_method_info()
+        if how.method == S.GPU_HIERARCHY_PLOC:
+            print("%s: PLOC, radius %d, %d rounds (%d of them in one workgroup)" % (what, how.radius, how.rounds, how.finishRounds),
+                  file=sys.stderr)
+        print("%s: %d nodes, %d levels, stack bound %d, leaves of at most %d, %.3f ms on the device (%s)" % (
+            what, info.nodeCount, info.levels, info.stackBound, info.leafSize, info.totalMs,
+            ", ".join("%s %.3f" % (n, ms) for n, ms in zip(S.HIERARCHY_BUILD_STAGE_NAMES, info.stageMs))), file=sys.stderr)
+
+    if args.gpu_first_tree:
+        gpu_method("--gpu-first-tree", args.gpu_first_tree)
+        ctx.set_gpu_hierarchy_sites(S.GPU_BUILD_SITE_UPLOAD)
     ctx.upload_scene(world)
     st = ctx.scene_stats()
+    if args.gpu_first_tree and ctx.hierarchy_build_info().builder == S.BUILDER_GPU:  # (a scene without triangles: the host's root)
+        print_gpu_build("GPU first tree (stage 'bounds' is the one pass over the geometry)")
     if args.time is not None:
         from prosper_amd import animation
         ctx.set_animations(animation.load_animations(args.gltf))
@@ -226,18 +250,9 @@ def main():
         if pose.cameraValid and not args.eye and not args.target:
             world.camera.update(eye=tuple(pose.eye), target=tuple(pose.target), up=tuple(pose.up))
     if args.gpu_hierarchy:
-        method, _, radius = args.gpu_hierarchy.partition(":")
-        if method not in ("linear", "ploc") or (radius and (method != "ploc" or not radius.isdigit())):
-            ap.error("--gpu-hierarchy takes linear or ploc[:radius]")
-        ctx.set_gpu_hierarchy_method(S.GPU_HIERARCHY_PLOC if method == "ploc" else S.GPU_HIERARCHY_LINEAR, int(radius or 0))
+        gpu_method("--gpu-hierarchy", args.gpu_hierarchy)
         ctx.build_hierarchy_gpu()  # (flushes the pose --time staged first)
-        info, how = ctx.hierarchy_build_info(), ctx.gpu_hierarchy_method_info()
-        if how.method == S.GPU_HIERARCHY_PLOC:
-            print("GPU hierarchy: PLOC, radius %d, %d rounds (%d of them in one workgroup)" % (how.radius, how.rounds, how.finishRounds),
-                  file=sys.stderr)
-        print("GPU hierarchy: %d nodes, %d levels, stack bound %d, leaves of at most %d, %.3f ms on the device (%s)" % (
-            info.nodeCount, info.levels, info.stackBound, info.leafSize, info.totalMs,
-            ", ".join("%s %.3f" % (n, ms) for n, ms in zip(S.HIERARCHY_BUILD_STAGE_NAMES, info.stageMs))), file=sys.stderr)
+        print_gpu_build("GPU hierarchy")
     hcam = Camera.from_world(world, w, h)
     if args.dof:
         c = world.camera
