@@ -305,7 +305,8 @@ int device_build_state(GeometryTarget &t, LbvhState **out)
 }
 
 // First half: the tree from the device's own flat world triangles into the build's scratch arrays.  Nothing of the scene
-// changes; a refused build (the stack bound) leaves it exactly as it was.
+// changes, neither its arrays nor what prosper_pt_get_hierarchy_build_info reports of the standing tree (the stage times
+// are given up where the install begins, not here); a refused build (the stack bound) leaves it exactly as it was.
 int build_into_scratch(GeometryTarget &t, bool boundsReady, DeviceBuild &b)
 {
     AccelState *acc = t.acc;
@@ -317,7 +318,6 @@ int build_into_scratch(GeometryTarget &t, bool boundsReady, DeviceBuild &b)
     if (ploc) b.method.radius = t.gpuRadius ? t.gpuRadius : kPlocDefaultRadius;
     b.leafSize = t.buildOpt.leafSize ? std::min(std::max(t.buildOpt.leafSize, 1u), kMaxLeafTriangles)
                                      : (ploc ? kPlocDefaultLeafSize : kLbvhDefaultLeafSize);
-    acc->gpuStagesValid = false;
     return lbvh_build(*b.st, acc->dFlat, (uint32_t)acc->total, b.leafSize, b.method, t.stream, b.built, boundsReady);
 }
 
@@ -331,6 +331,7 @@ int install_device_build(prosper_pt_ctx *ctx, GeometryTarget &t, DeviceBuild &b)
     const LbvhResult &built = b.built;
     int rc;
     acc->stale = true;
+    acc->gpuStagesValid = false; // (from here on the standing tree's stage times describe no tree in use)
     const size_t n = built.nodeCount;
     if ((rc = reserve_node_array(ctx, acc, n * sizeof(BvhNode)))) return rc;
     if ((rc = reserve_refit_tables(ctx, acc, n))) return rc;
@@ -375,8 +376,9 @@ int install_device_build(prosper_pt_ctx *ctx, GeometryTarget &t, DeviceBuild &b)
 }
 } // namespace
 
-// Both halves: a refused build leaves the scene exactly as it was.  The synchronous rebuild's caller has synchronised the
-// device; the target's stream has been waited for when this returns.
+// Both halves: a refused build leaves the scene exactly as it was, the standing tree's build info and stage times
+// included (tests/test_gpu_hierarchy_refusal.py reaches the refusal with a nested comb).  The synchronous rebuild's
+// caller has synchronised the device; the target's stream has been waited for when this returns.
 int build_hierarchy_on_device(prosper_pt_ctx *ctx, GeometryTarget &t, bool boundsReady)
 {
     DeviceBuild b;

@@ -1,7 +1,8 @@
 """prosper_amd/ploc.py alone: the NumPy statement of the PLOC method of the GPU hierarchy build, held to
 what a valid tree is, to rounds computed by hand, to its tie rule and to the tree cost it is there for; and
 tests/ploc_rule_main.cpp, the kernels' own rule functions run on a CPU under sanitizers, held to the statement.
-tests/test_gpu_hierarchy_ploc.py holds the kernels to it."""
+tests/test_gpu_hierarchy_ploc.py holds the kernels to it.  The nested comb (tests/ploc_sets.py) puts the statement's stack
+bound on the limit and one beyond it: the facts tests/test_gpu_hierarchy_refusal.py leans on are derived here."""
 import os
 import shutil
 import subprocess
@@ -243,10 +244,7 @@ def rule_program(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("leaf,radius", [(1, 16), (4, 16), (1, 1), (4, 32)])
-@pytest.mark.parametrize("name", ["soup", "identical70", "spread", "n257", "t_plus_1", "n2", "n0"])
-def test_the_kernels_arithmetic_meets_the_statement_on_a_cpu(rule_program, built, tmp_path, name, leaf, radius):
-    v, want = SETS[name], built[(name, leaf, radius)]
+def _check_rule_program(rule_program, tmp_path, v, want, leaf, radius):
     flat = np.zeros((len(v), 12), np.uint32)
     flat.reshape(-1, 3, 4)[:, :, :3] = v.view(np.uint32)
     flat[:, 3] = 7  # (the words between the vertices are not coordinates)
@@ -266,3 +264,79 @@ def test_the_kernels_arithmetic_meets_the_statement_on_a_cpu(rule_program, built
     at += n
     nodes = words[at:].reshape(count, 5)
     assert np.array_equal(nodes[:, :4].view(np.int32), want.child) and np.array_equal(nodes[:, 4], want.reserved)
+
+
+@pytest.mark.parametrize("leaf,radius", [(1, 16), (4, 16), (1, 1), (4, 32)])
+@pytest.mark.parametrize("name", ["soup", "identical70", "spread", "n257", "t_plus_1", "n2", "n0"])
+def test_the_kernels_arithmetic_meets_the_statement_on_a_cpu(rule_program, built, tmp_path, name, leaf, radius):
+    _check_rule_program(rule_program, tmp_path, SETS[name], built[(name, leaf, radius)], leaf, radius)
+
+
+# ---- the nested comb (ploc_sets.nested_comb): trees on the traversal's stack limit and beyond it ----
+HUGE = 1 << 20
+COMB_RADII = (1, 8, 32)
+
+
+@pytest.fixture(scope="module")
+def combs():
+    """The statement over every comb with no limit on the stack bound: what the device computes before it decides."""
+    return {(n, leaf, radius): ploc.build(ploc_sets.nested_comb(n), leaf_size=leaf, radius=radius, max_stack_bound=HUGE)
+            for n in ploc_sets.COMB_SIZES for leaf in LEAF_SIZES for radius in COMB_RADII}
+
+
+def test_the_nested_comb_is_exact_and_nested():
+    for n in ploc_sets.COMB_SIZES:
+        v = ploc_sets.nested_comb(n)
+        s = np.exp2(np.arange(n, dtype=np.float64) - n // 2)
+        want = np.zeros((n, 3, 3))
+        want[:, 0], want[:, 1], want[:, 2] = (np.stack([-s, 0 * s, s / 16], 1), np.stack([s, 0 * s + 0.0625, s / 16], 1),
+                                              np.stack([0 * s, 0 * s + 0.0625, s / 16], 1))
+        assert v.dtype == np.float32 and np.array_equal(v.astype(np.float64), want)  # every value is exact in fp32
+        lo, hi = ploc.boxes(v)
+        assert (lo[1:, :2] <= lo[:-1, :2]).all() and (hi[1:, :2] >= hi[:-1, :2]).all()  # boxes nest in x and y
+        assert (lo[:, 2] == hi[:, 2]).all() and (np.diff(lo[:, 2]) > 0).all()  # one plane each, all different
+
+
+@pytest.mark.parametrize("leaf", LEAF_SIZES)
+@pytest.mark.parametrize("n", ploc_sets.COMB_SIZES)
+def test_the_nested_comb_reaches_the_stack_limit_one_triangle_apart(combs, n, leaf):
+    v = ploc_sets.nested_comb(n)
+    bounds = set()
+    for radius in COMB_RADII:
+        tree = combs[(n, leaf, radius)]
+        assert tree.stack_bound == lbvh.recursive_stack_bound(tree.child, tree.reserved)
+        assert tree.rounds == n - 1  # a comb: one merge a round
+        bounds.add(tree.stack_bound)
+        # under the default limit the statement refuses exactly the trees beyond it
+        if tree.stack_bound > lbvh.MAX_STACK_BOUND:
+            with pytest.raises(lbvh.Refused):
+                ploc.build(v, leaf_size=leaf, radius=radius)
+        else:
+            for x, y in zip(ploc.build(v, leaf_size=leaf, radius=radius), tree):
+                assert np.array_equal(x, y)
+    assert len(bounds) == 1  # (the search radius does not matter: the nearest neighbour is the next position)
+    bound = bounds.pop()
+    print("nested_comb(%d), leaf %d: PLOC stack bound %d (%s), linear %d" % (
+        n, leaf, bound, "refused" if bound > lbvh.MAX_STACK_BOUND else "accepted", lbvh.build(v, leaf_size=leaf).stack_bound))
+    if leaf == 1:
+        assert bound == n
+    # the linear method's tree over the same set is nowhere near the limit (lbvh.build raises Refused beyond it)
+    assert lbvh.build(v, leaf_size=leaf).stack_bound <= lbvh.MAX_STACK_BOUND
+
+
+def test_the_nested_comb_sits_on_the_limit_or_is_refused(combs):
+    """The facts tests/test_gpu_hierarchy_refusal.py leans on, with the default radius: 96 triangles at leaf 1 and 97 at
+    leaf 2 sit exactly on the limit; 97 at leaf 1 and 101 at every leaf size are beyond it."""
+    bound = lambda n, leaf: combs[(n, leaf, ploc.DEFAULT_RADIUS)].stack_bound
+    assert lbvh.MAX_STACK_BOUND == 96 and ploc.DEFAULT_RADIUS in COMB_RADII
+    assert bound(96, 1) == 96 and bound(97, 2) == 96
+    assert bound(97, 1) == 97
+    assert all(bound(101, leaf) > 96 for leaf in LEAF_SIZES)
+
+
+@pytest.mark.parametrize("leaf", [1, ploc.DEFAULT_LEAF_SIZE])
+@pytest.mark.parametrize("n", ploc_sets.COMB_SIZES)
+def test_the_kernels_arithmetic_meets_the_statement_on_the_nested_comb(rule_program, combs, tmp_path, n, leaf):
+    """The program computes the stack bound and does not decide on it: compared with the statement without a limit."""
+    radius = ploc.DEFAULT_RADIUS
+    _check_rule_program(rule_program, tmp_path, ploc_sets.nested_comb(n), combs[(n, leaf, radius)], leaf, radius)
