@@ -2066,6 +2066,122 @@ int prosper_pt_get_taa_info(prosper_pt_ctx *ctx, prosper_pt_taa_info *out);
  * in that order of operations, for callers that build their own prosper_CameraUniforms.  Host only. */
 void prosper_pt_taa_jitter(uint32_t jitterIndex, uint32_t width, uint32_t height, float out[2]);
 
+/* ---- spatiotemporal denoiser of the path-traced image ----
+ * prosper has no denoiser: the rule below is this library's own, stated operation for operation in
+ * prosper_amd/denoise.py (NumPy, float32) and met by the kernels bit for bit.  An SVGF-style pass over the HDR image:
+ * temporal accumulation of colour and luminance moments reprojected through the velocity target, a variance estimate,
+ * and an edge-avoiding a-trous wavelet filter guided by depth, normal and variance.  Opt-in: nothing else calls it.
+ * Additive: the ABI version stays 4. */
+typedef struct prosper_pt_denoise_pc
+{
+    uint32_t iterations;        /* a-trous passes, 0 .. 5; the step of pass i is 1 << i; default 5 */
+    uint32_t demodulate;        /* 0 / 1: filter illumination / max(albedo, 1/64), multiply back at the end; default 1 */
+    uint32_t maxHistoryLength;  /* 1 .. 255; default 32 */
+    uint32_t feedbackIteration; /* which a-trous output becomes the next frame's colour history; >= iterations: the
+                                 * temporal result; default 1 */
+    uint32_t normalPowerLog2;   /* 0 .. 8: the normal weight is max(0, n.n') squared this many times; default 7 */
+    uint32_t resetHistory;      /* 0 / 1; default 0 */
+    float minAlpha;             /* lower bound of the temporal blend weight, (0, 1]; default 0.05 */
+    float depthTolerance;       /* reprojection: |zPrev - z| <= depthTolerance * max(z, zPrev); default 0.1 */
+    float normalThreshold;      /* reprojection: dot(nPrev, n) >= normalThreshold; default 0.9 */
+    float sigmaDepth;           /* default 1 */
+    float sigmaLuminance;       /* default 4 */
+} prosper_pt_denoise_pc;
+/* The defaults named above.  Host only. */
+void prosper_pt_denoise_pc_default(prosper_pt_denoise_pc *out);
+typedef struct prosper_pt_denoise_inputs
+{
+    const void *illumination;    /* width*height RGBA32F; NULL: the context's HDR image, in place */
+    const void *albedoRoughness; /* width*height float4 each and the reverse-Z depth, given together; all three NULL: */
+    const void *normalMetallic;  /* the last traced or rastered G-buffer */
+    const float *nonLinearDepth;
+    const void *velocity;        /* width*height float2 as for prosper_pt_taa_resolve; NULL: the last traced velocity target */
+    uint32_t onDevice;           /* not 0: the given pointers are device pointers */
+} prosper_pt_denoise_inputs;
+/* One denoise of `width` x `height` into the context's HDR image, so that tone map, bloom, TAA and depth of field consume
+ * the result unchanged.  `camera` supplies linearize_depth's two terms (cameraToClip[2][2] and [3][2]), as for depth of
+ * field.  It needs no scene.  History is ignored on the first call, when the extent differs from the last call's, with
+ * resetHistory, after prosper_pt_denoise_release_history and after prosper_pt_upload_scene.
+ *
+ * Everything is stored as float32: the rule has no quantisation.  Arithmetic is float32 without contraction, only
+ * + - * / sqrt min max floor abs and comparisons, in this order (min/max: a NaN operand loses); px the texel, res =
+ * (width, height):
+ *   per pixel    geometry: nonLinearDepth != 0.  z = cameraToClip32 / (depth + cameraToClip22), -viewZ.  n = signedOctDecode of
+ *                normalMetallic's (x, y, w) with dot(a, b) = (ax bx + ay by) + az bz and n = o * (1 / sqrt(dot(o, o))).
+ *                x = illumination.rgb, with demodulate each channel / max(albedo, 1/64).  l = (.299 r + .587 g) + .114 b.
+ *                A sky texel leaves the pass byte for byte as it came in, has length 0 and is nobody's tap.  A texel
+ *                whose x has a non-finite component is an invalid sample: it keeps its reprojected history, the length
+ *                not incremented; without a history its colour, moments and length are 0.
+ *   guide        z, n, the flag and a depth gradient per axis: the forward (z[+1] - z) and backward (z - z[-1])
+ *                differences to geometry neighbours inside the image, the one of smaller magnitude (ties: forward); 0
+ *                without one
+ *   reprojection uv = (px + .5) / res; reprojectedUv = uv - velocity * (.5, -.5); c = reprojectedUv * res - .5; unless
+ *                -1 <= c <= res on both axes there is no history; i = floor(c), f = c - i.  The taps (0,0) (1,0) (0,1)
+ *                (1,1) with the weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy.  A tap counts if it lies inside the
+ *                image (no clamping), the previous guide there is geometry, |zPrev - z| <= depthTolerance max(z, zPrev)
+ *                and dot(nPrev, n) >= normalThreshold.  The counted weights are summed in that order (so are w * colour
+ *                and w * moments); a sum that is not > 0 means no history; else prev = sum / weight sum
+ *   length       with history min(maxHistoryLength, max(lengths of the counted taps) + 1), without 1
+ *   blend        alpha = max(1 / N', minAlpha), keep = 1 - alpha; x' = keep * prev + alpha * x for the colour, for
+ *                m1 (x = l) and m2 (x = l * l); without history x' = x.  Temporal variance max(m2' - m1' m1', 0)
+ *   variance     where N' < 4: over the 7 x 7 window, dy outer, dx inner, the taps inside the image that are geometry,
+ *                the centre with weight 1, the others with w_n F(x_z) below at step 1; m = sum(w m) / sum(w) for both
+ *                moments, variance = max(m2 - m1 m1, 0) * (4 / max(N', 1)).  Elsewhere the temporal variance stands
+ *   a-trous i    s = 1 << i; h = (1/16, 1/4, 3/8, 1/4, 1/16); taps p + s (dx, dy), dy outer, dx inner, inside the image
+ *                and geometry; the centre counts with w = h(0) h(0).  vbar: the 3 x 3 Gaussian (centre 1/4, edge 1/8,
+ *                corner 1/16) of the variance at p + (dx, dy) over the geometry taps inside, sum(k v) / sum(k).
+ *                x_l = |l_q - l_p| / (sigmaLuminance sqrt(vbar) + 1e-4), l of the pass's input colours
+ *                t_x = g_x * float(s dx), t_y = g_y * float(s dy)
+ *                x_z = |z_q - ((z_p + t_x) + t_y)| / (sigmaDepth (|t_x| + |t_y|) + 1e-3 z_p)
+ *                w_n = max(0, dot(n_p, n_q)) squared normalPowerLog2 times
+ *                F(x) = t^8, t = max(0, 1 - x * .125), by three squarings; w = (h(dx) h(dy)) * (w_n * F(x_z + x_l))
+ *                colour = sum(w c_q) / sum(w), variance = sum((w w) v_q) / (sum(w) sum(w))
+ *   output       passes ping-pong between two images.  The output of pass feedbackIteration (rgb and variance) is the
+ *                next call's colour history; moments, length and guide come from the temporal stage.  After the last
+ *                pass: times max(albedo, 1/64) with demodulate, the input's alpha, stored to the HDR image
+ * Host inputs go through a grow-only staging buffer; the working and history images (176 bytes per pixel) are
+ * grow-only too.  Refused, before the device is touched and changing nothing: a NULL pc, camera or inputs; iterations
+ * above 5, demodulate or resetHistory above 1, maxHistoryLength outside 1 .. 255, normalPowerLog2 above 8; a float
+ * parameter that is not finite or not positive, minAlpha above 1; an empty extent or one above 32768; a partly given
+ * G-buffer; with onDevice an illumination, albedo or normal pointer that is not 16-byte, a velocity that is not 8-byte
+ * or a depth that is not 4-byte aligned; illumination = NULL when the HDR image has another extent; a NULL velocity or
+ * G-buffer when none of this extent has been traced. */
+int prosper_pt_denoise(
+    prosper_pt_ctx *ctx, const prosper_pt_denoise_pc *pc, const prosper_CameraUniforms *camera, uint32_t width, uint32_t height,
+    const prosper_pt_denoise_inputs *inputs, void *stream);
+/* The next call ignores the history.  (The images stay allocated.) */
+void prosper_pt_denoise_release_history(prosper_pt_ctx *ctx);
+/* The images of the last call, each width*height records of 16 bytes.  The guide and the moments are what the temporal
+ * stage made AND what the next call reads as its previous frame; HISTORY_COLOUR is the colour history the next call
+ * reads.  An a-trous image is held while no later pass has written over it: the last two passes' are. */
+enum
+{
+    PROSPER_PT_DENOISE_GUIDE_A = 0,        /* float z, dz/dx, dz/dy; uint32 geometry flag */
+    PROSPER_PT_DENOISE_GUIDE_B = 1,        /* float n.x, n.y, n.z, 0 */
+    PROSPER_PT_DENOISE_MOMENTS = 2,        /* float m1, m2; uint32 history length; 0 */
+    PROSPER_PT_DENOISE_TEMPORAL = 3,       /* float r, g, b of the temporal stage, the variance after the estimate */
+    PROSPER_PT_DENOISE_ATROUS_0 = 4,       /* .. ATROUS_0 + 4: float r, g, b, variance after that pass */
+    PROSPER_PT_DENOISE_HISTORY_COLOUR = 9, /* float r, g, b, variance of the fed-back image */
+    PROSPER_PT_DENOISE_STAGE_COUNT = 10,
+};
+/* Synchronises `stream` and copies one of them to host memory; `bytes` must be exactly width*height*16 of the last
+ * call.  NO_SCENE before the first call, and for the history images when there is no history. */
+int prosper_pt_read_denoise_stage(prosper_pt_ctx *ctx, uint32_t stage, void *host, size_t bytes, void *stream);
+typedef struct prosper_pt_denoise_info
+{
+    uint32_t valid;           /* 1 once prosper_pt_denoise ran */
+    uint32_t width, height;   /* of the last call */
+    uint32_t historyValid;    /* 1: the next call of this extent reads a history */
+    uint32_t ignoredHistory;  /* 1: the last call ignored the history */
+    uint32_t iterations;      /* of the last call */
+    uint32_t historyPixels;   /* geometry pixels of the last call with a usable history ... */
+    uint32_t noHistoryPixels; /* ... and without; counted by the temporal kernel, one atomic per wave and counter */
+    /* device time of each stage of the last call (reading them waits for it); an a-trous pass that did not run takes
+     * none; finishMs covers the store to the HDR image when no a-trous pass ran (otherwise the last pass stores) */
+    float temporalMs, varianceMs, atrousMs[5], finishMs, totalMs;
+} prosper_pt_denoise_info;
+int prosper_pt_get_denoise_info(prosper_pt_ctx *ctx, prosper_pt_denoise_info *out);
+
 /* ---- multi-GPU: image stripes per rank + ONE gather of the per-rank HDR tiles over RCCL + de-interleave ----
  * (north star: "the image is tiled across the 8 GPUs of one node with an RCCL gather over xGMI of
  * per-tile HDR buffers".)  The reference renders the whole image on one GPU and asserts renderArea.offset == 0

@@ -209,6 +209,13 @@ def lib():
     L.prosper_pt_get_taa_info.argtypes = [vp, C.POINTER(S.TaaInfo)]
     L.prosper_pt_taa_jitter.argtypes = [u32, u32, u32, C.POINTER(C.c_float * 2)]
     L.prosper_pt_taa_jitter.restype = None
+    L.prosper_pt_denoise_pc_default.argtypes = [C.POINTER(S.DenoisePC)]
+    L.prosper_pt_denoise_pc_default.restype = None
+    L.prosper_pt_denoise.argtypes = [vp, C.POINTER(S.DenoisePC), C.POINTER(S.CameraUniforms), u32, u32, C.POINTER(S.DenoiseInputs), vp]
+    L.prosper_pt_denoise_release_history.argtypes = [vp]
+    L.prosper_pt_denoise_release_history.restype = None
+    L.prosper_pt_read_denoise_stage.argtypes = [vp, u32, vp, C.c_size_t, vp]
+    L.prosper_pt_get_denoise_info.argtypes = [vp, C.POINTER(S.DenoiseInfo)]
     L.prosper_pt_set_tone_map_lut.argtypes = [vp, vp, u32]
     L.prosper_pt_tone_map.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_size_t, vp]
     L.prosper_pt_get_counters.argtypes = [vp, C.POINTER(S.Counters), vp]
@@ -1671,6 +1678,44 @@ class Context:
         i = self.taa_info()
         out = np.empty((i.height, i.width, 4), np.float16)
         _check(lib().prosper_pt_read_taa_history(self._h, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
+        return out
+
+    def denoise(self, pc, camera, width, height, illumination=None, albedo_roughness=None, normal_metallic=None, depth=None,
+                velocity=None, illumination_ptr=None, albedo_roughness_ptr=None, normal_metallic_ptr=None, depth_ptr=None,
+                velocity_ptr=None, stream=None):
+        """prosper_pt_denoise with `pc` (S.DenoisePC) into the HDR image and the history.  `illumination`,
+        `albedo_roughness`, `normal_metallic` [h, w, 4], `depth` [h, w], `velocity` [h, w, 2]: host arrays; the `_ptr`
+        ones: device pointers.  No illumination: the HDR image in place; no G-buffer (all three): the last traced one;
+        no velocity: the last traced velocity target."""
+        arrays = (illumination, albedo_roughness, normal_metallic, depth, velocity)
+        pointers = (illumination_ptr, albedo_roughness_ptr, normal_metallic_ptr, depth_ptr, velocity_ptr)
+        host = any(a is not None for a in arrays)
+        assert not (host and any(pointers)), "host and device inputs cannot be mixed"
+        held = [None if a is None else np.ascontiguousarray(a, np.float32) for a in arrays]
+        for a, shape in zip(held, ((height, width, 4),) * 3 + ((height, width), (height, width, 2))):
+            assert a is None or a.shape == shape
+        if host:
+            inp = S.DenoiseInputs(*[None if a is None else a.ctypes.data for a in held], 0)
+        else:
+            inp = S.DenoiseInputs(*pointers, 1)
+        _check(lib().prosper_pt_denoise(self._h, C.byref(pc), C.byref(camera), width, height, C.byref(inp), C.c_void_p(stream)))
+
+    def denoise_release_history(self):
+        """The next denoise ignores the history."""
+        lib().prosper_pt_denoise_release_history(self._h)
+
+    def denoise_info(self):
+        """S.DenoiseInfo: the last denoise's extent, history flags, history counts and per-stage device times."""
+        info = S.DenoiseInfo()
+        _check(lib().prosper_pt_get_denoise_info(self._h, C.byref(info)))
+        return info
+
+    def read_denoise_stage(self, stage, stream=None):
+        """One image of the last denoise (S.DENOISE_*) as float32 [h, w, 4]; the geometry flag and the history length are
+        uint32 bits (prosper_amd.denoise.bits)."""
+        i = self.denoise_info()
+        out = np.empty((i.height, i.width, 4), np.float32)
+        _check(lib().prosper_pt_read_denoise_stage(self._h, stage, out.ctypes.data, out.nbytes, C.c_void_p(stream)))
         return out
 
     def set_tone_map_lut(self, lut_r9g9b9e5):

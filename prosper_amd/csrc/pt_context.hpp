@@ -69,6 +69,7 @@ struct CullingPassState;     // the two depth pyramids, the draw lists with thei
 struct RasterPassState;      // the visibility image, the large pass's queue, the counts of the last draws
 struct CompressPassState;    // prosper_pt_compress_texture (pt_materials.cpp)
 struct MeshPreparePassState; // prosper_pt_prepare_mesh (pt_mesh_passes.cpp)
+struct DenoisePassState;     // the denoiser's history (colour, moments, guide) and working images
 // a new scene, or TemporalAntiAliasing::releasePreserved: the next resolve ignores the history
 void forget_taa_history(prosper_pt_ctx *ctx);
 struct AccelState;
@@ -101,12 +102,12 @@ struct PassModule
     void (*list_debug_images)(const prosper_pt_ctx *, std::vector<DebugImage> &); // nullptr: it owns no listed image
 };
 extern const PassModule kGBufferPasses, kForwardPasses, kDofPasses, kBloomPasses, kTaaPasses, kParticlesPasses, kDebugPasses,
-    kCullingPasses, kRasterPasses, kCompressPasses, kMeshPreparePasses;
+    kCullingPasses, kRasterPasses, kCompressPasses, kMeshPreparePasses, kDenoisePasses;
 // Every module, in the order they are made.  The registry of debug images lists theirs in this order too, which is part
 // of the interface: the G-buffer module's, dof's, bloom's, taa's.
 inline const PassModule *const kPassModules[] = {&kGBufferPasses, &kForwardPasses,   &kDofPasses,         &kBloomPasses,
                                                  &kTaaPasses,     &kParticlesPasses, &kDebugPasses,       &kCullingPasses,
-                                                 &kRasterPasses,  &kCompressPasses,  &kMeshPreparePasses};
+                                                 &kRasterPasses,  &kCompressPasses,  &kMeshPreparePasses, &kDenoisePasses};
 // State of the keyframe animation (pt_animation.hip, pt_animation.hpp): the node and channel tables of the scene, the
 // staged time and the read-back that feeds the host mirrors below.  Made and freed like the others.
 struct AnimationState;
@@ -352,6 +353,7 @@ struct prosper_pt_ctx
     ppt::DofPassState *dofPasses = nullptr; // skybox fill, depth of field
     ppt::BloomPassState *bloomPasses = nullptr;
     ppt::TaaPassState *taaPasses = nullptr;
+    ppt::DenoisePassState *denoisePasses = nullptr;
     ppt::ParticlesPassState *particlesPasses = nullptr;
     ppt::DebugPassState *debugPasses = nullptr;
     ppt::CullingPassState *cullingPasses = nullptr; // the depth pyramids, the draw lists, DrawStats

@@ -745,6 +745,43 @@ class TaaInfo(C.Structure):
         ("resolveMs", C.c_float), ("expandMs", C.c_float)]
 
 
+class DenoisePC(C.Structure):
+    """prosper_pt_denoise_pc: the parameters of the spatiotemporal denoiser.  DenoisePC.default() holds
+    prosper_pt_denoise_pc_default's values."""
+    _fields_ = [(n, C.c_uint32) for n in ("iterations", "demodulate", "maxHistoryLength", "feedbackIteration",
+                                          "normalPowerLog2", "resetHistory")] + [
+        (n, C.c_float) for n in ("minAlpha", "depthTolerance", "normalThreshold", "sigmaDepth", "sigmaLuminance")]
+
+    @classmethod
+    def default(cls, iterations=5, demodulate=1, max_history_length=32, feedback_iteration=1, normal_power_log2=7,
+                reset_history=0, min_alpha=0.05, depth_tolerance=0.1, normal_threshold=0.9, sigma_depth=1.0,
+                sigma_luminance=4.0):
+        return cls(iterations, demodulate, max_history_length, feedback_iteration, normal_power_log2, reset_history,
+                   min_alpha, depth_tolerance, normal_threshold, sigma_depth, sigma_luminance)
+
+
+class DenoiseInputs(C.Structure):
+    """prosper_pt_denoise_inputs: illumination (None: the HDR image in place), the G-buffer (all None: the last traced
+    one), velocity (None: the last traced velocity target)"""
+    _fields_ = [("illumination", C.c_void_p), ("albedoRoughness", C.c_void_p), ("normalMetallic", C.c_void_p),
+                ("nonLinearDepth", C.c_void_p), ("velocity", C.c_void_p), ("onDevice", C.c_uint32)]
+
+
+class DenoiseInfo(C.Structure):
+    """prosper_pt_denoise_info: the last call's extent, history flags, the pixels with and without a usable history and
+    the device time per stage"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid", "width", "height", "historyValid", "ignoredHistory", "iterations",
+                                          "historyPixels", "noHistoryPixels")] + [
+        ("temporalMs", C.c_float), ("varianceMs", C.c_float), ("atrousMs", C.c_float * 5), ("finishMs", C.c_float),
+        ("totalMs", C.c_float)]
+
+
+# prosper_pt_read_denoise_stage: the images of the last denoise, 16 bytes per pixel each
+DENOISE_GUIDE_A, DENOISE_GUIDE_B, DENOISE_MOMENTS, DENOISE_TEMPORAL, DENOISE_ATROUS_0 = range(5)
+DENOISE_HISTORY_COLOUR = 9
+DENOISE_STAGE_COUNT = 10
+
+
 # ImageBasedLighting: the irradiance cube, the prefiltered radiance cube (mips 512 ... 1) and the BRDF LUT
 IBL_IRRADIANCE_SIZE = 64
 IBL_RADIANCE_SIZE = 512

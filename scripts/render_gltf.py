@@ -48,6 +48,12 @@ glTF ingest (prosper_amd/gltf.py) -> prosper_pt_upload_scene -> prosper_pt_rende
                                  the GPU ahead of the refit, before anything is rendered; the camera node's animated pose is
                                  the camera unless --eye / --target are given.  Under --taa every jittered frame advances
                                  the time by DT (default 1/60 s) and hands its table to the velocity target
+    --denoise [--denoise-frames N] [--spp 1] [--time T [--time-step DT]]
+                                 the path-traced mode for a moving scene: N frames (8) of --spp samples, each rendered afresh
+                                 (PROSPER_PC_FLAG_SKIP_HISTORY), preceded by prosper_pt_trace_gbuffer_velocity with the previous
+                                 frame's transforms (prosper_pt_read_animated_transforms, which = 1) and followed by
+                                 prosper_pt_denoise; with --time every frame advances the animation by DT.  The PNG is the
+                                 last frame through the tone map
     --deferred --sky --dof --aperture A --focus D
                                  prosper_pt_depth_of_field over the filled image, through the host layer's DepthOfField:
                                  aperture diameter A and focus distance D in scene units drive the push constants
@@ -156,6 +162,9 @@ def main():
                              "Roughness", "Metallic"],
                     help="with --raster: the G-buffer's draw type (MeshletID and PrimitiveID are the mesh shader's), shaded as that debug view")
     ap.add_argument("--cull-stats", action="store_true", help="with --deferred: meshlet culling after each frame's G-buffer, DrawStats printed")
+    ap.add_argument("--denoise", action="store_true", help="the path-traced mode: --spp samples per frame (think 1), each frame through "
+                    "prosper_pt_denoise over a traced velocity G-buffer; with --time every frame advances the animation by --time-step")
+    ap.add_argument("--denoise-frames", type=int, default=8, help="with --denoise: frames to render; the PNG is the last one")
     ap.add_argument("--time", type=float, default=None, help="evaluate the glTF's animations at this time (seconds) before rendering")
     ap.add_argument("--gpu-hierarchy", nargs="?", const="linear", default=None, metavar="linear|ploc[:radius]",
                     help="build the hierarchy once more on the GPU after the upload (and after --time's pose), the same image: "
@@ -260,6 +269,7 @@ def main():
         hcam.set_parameters(c["fov"], c["zN"], c["zF"], args.aperture, focus)
     cam, focal = hcam.update_buffer()
     flags = S.PC_FLAG_ACCUMULATE | S.PC_FLAG_CLAMP_INDIRECT | S.PC_FLAG_SKIP_HISTORY | (S.PC_FLAG_IBL if args.env else 0)
+    samples = None  # (--denoise renders more than --spp)
     if args.deferred:
         import time
         if args.ibl:
@@ -437,6 +447,32 @@ def main():
             ctx.restir_di_record_traced(rpc, cam, w, h, spatial_reuse=not args.no_spatial)
         ctx.read_hdr()  # (synchronises)
         ms = (time.perf_counter() - t0) * 1e3
+    elif args.denoise:
+        # every frame: the scene moves on, the velocity G-buffer is traced against the previous frame's transforms, the frame is
+        # rendered afresh (SKIP_HISTORY: no running mean over a moving scene) and denoised into the HDR image
+        import time
+        t0 = time.perf_counter()
+        dpc = S.DenoisePC.default()
+        for frame in range(args.denoise_frames):
+            transforms = None
+            if args.time is not None:
+                if frame:
+                    ctx.animate(args.time + frame * args.time_step)
+                    pose = ctx.animation_state()
+                    if pose.cameraValid and not args.eye and not args.target:
+                        hcam.look_at(tuple(pose.eye), tuple(pose.target), tuple(pose.up))
+                transforms = ctx.read_animated_transforms(previous=True)
+            cam, focal = hcam.update_buffer()
+            ctx.trace_gbuffer_velocity(cam, w, h, frame_index=frame, previous_transforms=transforms)
+            pc = S.ReferencePC(0, flags, 1 + frame * args.spp, 1e-5, 1.0, focal, 3, min(args.bounces, 6))
+            ctx.render(pc, cam, w, h, frames=args.spp)
+            ctx.denoise(dpc, cam, w, h)
+            hcam.end_frame()
+        info = ctx.denoise_info()  # (synchronises)
+        ms = (time.perf_counter() - t0) * 1e3
+        samples = args.spp * args.denoise_frames  # per pixel, over every frame: what the closing line reports
+        print("denoise: %d frames of %d spp; the last: %d pixels with a history, %d without, %.3f ms on the device" % (
+            args.denoise_frames, args.spp, info.historyPixels, info.noHistoryPixels, info.totalMs), file=sys.stderr)
     else:
         pc = S.ReferencePC(0, flags, 1, 1e-5, 1.0, focal, 3, min(args.bounces, 6))
         ctx.set_kernel_timing(True)
@@ -460,7 +496,7 @@ def main():
         print("debug view: %s, level %d, range %g..%g, channel %s" % (name, int(lod or 0), lo, hi, args.debug_channel), file=sys.stderr)
     write_png(args.out, image)
     print("%s: %d triangles, %dx%d x %d spp in %.1f ms (%.0f Mpaths/s) -> %s" % (
-        os.path.basename(args.gltf), st.triangleCount, w, h, args.spp, ms, w * h * args.spp / ms / 1e3, args.out))
+        os.path.basename(args.gltf), st.triangleCount, w, h, samples or args.spp, ms, w * h * (samples or args.spp) / ms / 1e3, args.out))
     ctx.close()
 
 
