@@ -1,35 +1,28 @@
 // prosper_pt.cpp — C-ABI of the MI355X path-tracing reference pass (include/prosper_pt/prosper_pt.h).
 //
-// Host side of what prosper does around `cb.traceRaysKHR` (src/render/RtReference.cpp:161-383)
-// and of the scene/acceleration-structure upload the pass depends on
-// (src/scene/World.cpp:468-536,585-802).  There is no CPU fallback: without a usable HIP device
-// every entry point fails with PROSPER_PT_ERR_NO_DEVICE.
+// The context - error string, scene-lifetime device memory, debug options, create / destroy - and the host side of what
+// prosper does around `cb.traceRaysKHR` (src/render/RtReference.cpp:161-383): the render, its read-backs, counters and
+// timing.  The scene itself is pt_scene_upload.cpp's, its updates pt_scene_updates.cpp's, its hierarchy pt_hierarchy.cpp's.
+// There is no CPU fallback: without a usable HIP device every entry point fails with PROSPER_PT_ERR_NO_DEVICE.
 #include "../../include/prosper_pt/prosper_pt.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <future>
-#include <memory>
-#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <exception>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "bvh_build.hpp"
 #include "pt_animation.hpp"
 #include "pt_bvh_build.hpp"
 #include "pt_context.hpp"
 #include "pt_geometry.hpp"
 #include "pt_kernels.hpp"
-#include "pt_materials.hpp"
 #include "pt_pass_support.hpp"
 #include "pt_scene.hpp"
+#include "pt_scene_updates.hpp"
 #include "pt_tiling.hpp"
 
 using namespace ppt;
@@ -124,364 +117,6 @@ WavefrontOptions wavefront_options(const prosper_pt_ctx *ctx)
     o.noLdsScene = d.noLdsScene != 0;
     o.noLdsTables = d.noLdsTables != 0;
     return o;
-}
-
-} // namespace
-
-namespace
-{
-
-void free_scene(prosper_pt_ctx *ctx)
-{
-    discard_mesh_build(ctx);
-    for (ppt::AccelState *old : ctx->retiredAccel) delete old;
-    ctx->retiredAccel.clear();
-    for (auto &a : ctx->sceneAllocations) (void)hipFree(a.ptr);
-    ctx->sceneAllocations.clear();
-    delete ctx->accel; // its device arrays are in the list above
-    ctx->accel = nullptr;
-    delete ctx->lights;
-    ctx->lights = nullptr;
-    delete ctx->materialState;
-    ctx->materialState = nullptr;
-    delete ctx->geometry;
-    ctx->geometry = nullptr;
-    ctx->dTransforms = nullptr;
-    ctx->sceneBytes = 0;
-    ctx->haveScene = false;
-    ctx->scene = DeviceScene{};
-    ctx->textureMips = nullptr;
-}
-
-// Everything the kernels index with is range-checked here, so a malformed view can only fail the
-// upload, never fault the GPU.
-int validate_scene(const prosper_pt_scene_view *v, bool mips)
-{
-    if (v->struct_size != sizeof(prosper_pt_scene_view))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "scene view struct_size mismatch");
-    if (v->geometryBufferCount && (!v->geometryBuffers || !v->geometryBufferByteSizes))
-        return fail(PROSPER_PT_ERR_SCENE, "geometry buffers missing");
-    if (v->geometryBufferCount > PROSPER_PT_MAX_GEOMETRY_BUFFERS)
-        return fail(PROSPER_PT_ERR_SCENE, "more than PROSPER_PT_MAX_GEOMETRY_BUFFERS geometry buffers");
-    if (v->meshCount && (!v->geometryMetadatas || !v->meshInfos)) return fail(PROSPER_PT_ERR_SCENE, "mesh tables missing");
-    if (v->drawInstanceCount && !v->drawInstances) return fail(PROSPER_PT_ERR_SCENE, "draw instances missing");
-    if (v->modelInstanceCount && !v->modelInstanceTransforms) return fail(PROSPER_PT_ERR_SCENE, "transforms missing");
-    if (v->materialCount == 0 || !v->materials) return fail(PROSPER_PT_ERR_SCENE, "materials missing (index 0 is required)");
-    if (v->samplerCount == 0 || !v->samplers) return fail(PROSPER_PT_ERR_SCENE, "samplers missing (index 0 is required)");
-    if (v->textureCount && !v->textures) return fail(PROSPER_PT_ERR_SCENE, "textures missing");
-    if (!v->directionalLight || !v->pointLights || !v->spotLights) return fail(PROSPER_PT_ERR_SCENE, "light buffers missing");
-    if (v->pointLights->count > PROSPER_MAX_POINT_LIGHT_COUNT || v->spotLights->count > PROSPER_MAX_SPOT_LIGHT_COUNT)
-        return fail(PROSPER_PT_ERR_SCENE, "light count exceeds 1024");
-    if (v->skybox.texels && v->skybox.faceSize == 0) return fail(PROSPER_PT_ERR_SCENE, "skybox face size is zero");
-
-    for (uint32_t i = 0; i < v->textureCount; ++i)
-    {
-        const int rc = validate_texture(v->textures[i], i, mips);
-        if (rc != PROSPER_PT_OK) return rc;
-    }
-    for (uint32_t i = 0; i < v->samplerCount; ++i)
-    {
-        const prosper_pt_sampler_desc &s = v->samplers[i];
-        if (s.magFilter > PROSPER_PT_FILTER_LINEAR || s.wrapS > PROSPER_PT_WRAP_CLAMP_TO_EDGE ||
-            s.wrapT > PROSPER_PT_WRAP_CLAMP_TO_EDGE)
-            return fail(PROSPER_PT_ERR_SCENE, "sampler " + std::to_string(i) + " is invalid");
-    }
-    for (uint32_t i = 0; i < v->materialCount; ++i)
-    {
-        const prosper_MaterialData &m = v->materials[i];
-        const uint32_t ts[3] = {m.baseColorTextureSampler, m.metallicRoughnessTextureSampler, m.normalTextureSampler};
-        for (uint32_t k = 0; k < 3; ++k)
-        {
-            const uint32_t tex = ts[k] & 0xFFFFFFu, smp = ts[k] >> 24;
-            if (tex > 0 && (tex >= v->textureCount || smp >= v->samplerCount))
-                return fail(PROSPER_PT_ERR_SCENE, "material " + std::to_string(i) + " references a missing texture/sampler");
-        }
-        if (m.alphaMode > PROSPER_ALPHA_MODE_BLEND) return fail(PROSPER_PT_ERR_SCENE, "material alpha mode invalid");
-    }
-    for (uint32_t i = 0; i < v->meshCount; ++i)
-    {
-        const prosper_GeometryMetadata &m = v->geometryMetadatas[i];
-        const prosper_pt_mesh_info &info = v->meshInfos[i];
-        const std::string name = "mesh " + std::to_string(i);
-        if (m.bufferIndex == PROSPER_PT_ABSENT) continue; // not loaded yet (prosper_pt_update_meshes): nothing else of it is read
-        if (m.bufferIndex >= v->geometryBufferCount) return fail(PROSPER_PT_ERR_SCENE, name + ": bufferIndex out of range");
-        if (info.materialIndex >= v->materialCount) return fail(PROSPER_PT_ERR_SCENE, name + ": materialIndex out of range");
-        if (info.indexCount % 3 != 0) return fail(PROSPER_PT_ERR_SCENE, name + ": indexCount is not a multiple of 3");
-        const uint64_t words = v->geometryBufferByteSizes[m.bufferIndex] / 4;
-        if (m.indicesOffset == PROSPER_PT_ABSENT || m.positionsOffset == PROSPER_PT_ABSENT)
-            return fail(PROSPER_PT_ERR_SCENE, name + ": indices/positions are required");
-        const uint64_t indexEndWords = m.usesShortIndices == 1 ? ((uint64_t)m.indicesOffset + info.indexCount + 1) / 2
-                                                               : (uint64_t)m.indicesOffset + info.indexCount;
-        if (indexEndWords > words) return fail(PROSPER_PT_ERR_SCENE, name + ": indices run past the geometry buffer");
-        if ((uint64_t)m.positionsOffset + 2ull * info.vertexCount > words)
-            return fail(PROSPER_PT_ERR_SCENE, name + ": positions run past the geometry buffer");
-        const uint32_t attrs[3] = {m.normalsOffset, m.tangentsOffset, m.texCoord0sOffset};
-        for (uint32_t k = 0; k < 3; ++k)
-            if (attrs[k] != PROSPER_PT_ABSENT && (uint64_t)attrs[k] + info.vertexCount > words)
-                return fail(PROSPER_PT_ERR_SCENE, name + ": attribute stream runs past the geometry buffer");
-        const void *buffer = v->geometryBuffers[m.bufferIndex];
-        for (uint32_t k = 0; k < info.indexCount; ++k)
-        {
-            const uint32_t idx = m.usesShortIndices == 1 ? (uint32_t) static_cast<const uint16_t *>(buffer)[m.indicesOffset + k]
-                                                          : static_cast<const uint32_t *>(buffer)[m.indicesOffset + k];
-            if (idx >= info.vertexCount) return fail(PROSPER_PT_ERR_SCENE, name + ": vertex index out of range");
-        }
-    }
-    for (uint32_t i = 0; i < v->drawInstanceCount; ++i)
-    {
-        const prosper_DrawInstance &d = v->drawInstances[i];
-        if (d.meshIndex >= v->meshCount || d.materialIndex >= v->materialCount || d.modelInstanceIndex >= v->modelInstanceCount)
-            return fail(PROSPER_PT_ERR_SCENE, "draw instance " + std::to_string(i) + " references a missing mesh/material/transform");
-    }
-    return PROSPER_PT_OK;
-}
-
-int upload_scene_impl(prosper_pt_ctx *ctx, const prosper_pt_scene_view *v)
-{
-    DeviceScene &s = ctx->scene;
-    int rc = PROSPER_PT_OK;
-    ctx->stats = prosper_pt_scene_stats{};
-    const auto tUpload = std::chrono::steady_clock::now();
-    auto seconds_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    };
-
-    // bindless geometry buffers + pointer table, with the mirrors a later prosper_pt_update_meshes works from
-    GeometryState *gs = new (std::nothrow) GeometryState();
-    if (!gs) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-    ctx->geometry = gs;
-    gs->metadatas.assign(v->geometryMetadatas, v->geometryMetadatas + v->meshCount);
-    gs->infos.assign(v->meshInfos, v->meshInfos + v->meshCount);
-    gs->drawInstances.assign(v->drawInstances, v->drawInstances + v->drawInstanceCount);
-    std::vector<const void *> bufferPtrs(std::max<size_t>(v->geometryBufferCount, PROSPER_PT_MAX_GEOMETRY_BUFFERS), nullptr);
-    void *d = nullptr;
-    // (fixed sizes: while a mesh build runs the calling thread and the worker both index these, neither may move them)
-    gs->buffers.assign(bufferPtrs.size(), nullptr);
-    gs->bufferBytes.assign(bufferPtrs.size(), 0);
-    for (uint32_t i = 0; i < v->geometryBufferCount; ++i)
-    {
-        if ((rc = upload(ctx, v->geometryBuffers[i], (size_t)v->geometryBufferByteSizes[i], &d))) return rc;
-        bufferPtrs[i] = d;
-        gs->buffers[i] = d;
-        gs->bufferBytes[i] = v->geometryBufferByteSizes[i];
-    }
-    if ((rc = upload(ctx, bufferPtrs.data(), bufferPtrs.size() * sizeof(void *), &d))) return rc;
-    gs->dBufferTable = static_cast<const void **>(d);
-    s.geometryBuffers = gs->dBufferTable;
-    if ((rc = upload(ctx, v->geometryMetadatas, sizeof(prosper_GeometryMetadata) * v->meshCount, &d))) return rc;
-    gs->dMetadatas = static_cast<prosper_GeometryMetadata *>(d);
-    s.geometryMetadatas = gs->dMetadatas;
-    if ((rc = upload(ctx, v->drawInstances, sizeof(prosper_DrawInstance) * v->drawInstanceCount, &d))) return rc;
-    s.drawInstances = static_cast<const prosper_DrawInstance *>(d);
-    if ((rc = upload(ctx, v->modelInstanceTransforms, sizeof(prosper_ModelInstanceTransforms) * v->modelInstanceCount, &d)))
-        return rc;
-    s.modelInstanceTransforms = static_cast<const prosper_ModelInstanceTransforms *>(d);
-    if ((rc = upload(ctx, v->materials, sizeof(prosper_MaterialData) * v->materialCount, &d))) return rc;
-    s.materials = static_cast<const prosper_MaterialData *>(d);
-    if ((rc = upload(ctx, v->samplers, sizeof(prosper_pt_sampler_desc) * v->samplerCount, &d))) return rc;
-    s.samplers = static_cast<const prosper_pt_sampler_desc *>(d);
-    s.drawInstanceCount = v->drawInstanceCount;
-    s.modelInstanceCount = v->modelInstanceCount;
-
-    // ---- world triangles first: the host-side hierarchy build - the longest step of an upload - runs on the host's threads
-    //      while this thread goes on with textures, packs, sky, lights and the alpha tables (begin_geometry); the flatten
-    //      kernel runs again in finish_geometry for the shading and any-hit records (the same world triangles a second time).
-    //      With site UPLOAD of prosper_pt_set_gpu_hierarchy_sites there is no host build: finish_geometry touches the
-    //      triangles once and builds on the device ----
-    AccelState *acc = new (std::nothrow) AccelState();
-    if (!acc) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-    ctx->accel = acc;
-    acc->transforms.assign(v->modelInstanceTransforms, v->modelInstanceTransforms + v->modelInstanceCount);
-    ctx->dTransforms = const_cast<prosper_ModelInstanceTransforms *>(s.modelInstanceTransforms);
-    acc->dTransformsV[0] = ctx->dTransforms;
-    if ((rc = enqueue_instance_scales(ctx, acc, 0, ctx->dTransforms, v->modelInstanceCount, nullptr))) return rc;
-    PPT_HIP(hipStreamSynchronize(nullptr));
-    GeometryJob job;
-    GeometryTarget target = context_target(ctx);
-    // (site UPLOAD: the first tree from the GPU builder - begin_geometry then only lays the triangles out, and everything
-    //  else happens in finish_geometry, in one pass over the geometry)
-    target.gpuTree = (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_UPLOAD) != 0;
-    {
-        GeometryLayout layout;
-        if ((rc = layout_geometry(*gs, v->materials, layout))) return rc;
-        if ((rc = begin_geometry(ctx, target, layout, nullptr, job))) return rc;
-    }
-
-    // textures: one allocation each (256-B aligned by hipMalloc), re-laid out in 8x4-texel tiles of one cache line each
-    // (pt_scene.hpp DeviceTexture) by a kernel - until round 4 the host did that a texel at a time, 40 ms for
-    // S-sponza-class - + descriptor table.  The tables a later prosper_pt_update_textures / _materials changes are mirrored
-    // in ctx->materialState (pt_materials.cpp).
-    const auto tTextures = std::chrono::steady_clock::now();
-    MaterialState *ms = new (std::nothrow) MaterialState();
-    if (!ms) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-    ctx->materialState = ms;
-    ms->materials.assign(v->materials, v->materials + v->materialCount);
-    ms->samplers.assign(v->samplers, v->samplers + v->samplerCount);
-    std::vector<DeviceTexture> &textures = ms->textures;
-    textures.assign(v->textureCount ? v->textureCount : 1, DeviceTexture{nullptr, 0u, 0u, 0u, 0u});
-    uint64_t texelBytes = 0;
-    // mip chains (PROSPER_PT_CREATE_TEXTURE_MIPS): built right behind each level 0, before a packed material's may be freed
-    const bool withMips = (ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0;
-    const std::vector<uint8_t> baseColour = base_colour_textures(v->materials, v->materialCount, textures.size());
-    if (withMips) ms->mips.assign(textures.size(), DeviceTextureMips{nullptr, 1u, 0u, {}});
-    {
-        size_t stagingBytes = 0;
-        for (uint32_t i = 0; i < v->textureCount; ++i) stagingBytes = std::max(stagingBytes, texture_staging_bytes(v->textures[i], withMips));
-        void *staging = nullptr;
-        if (stagingBytes) PPT_HIP(hipMalloc(&staging, stagingBytes));
-        for (uint32_t i = 0; i < v->textureCount && rc == PROSPER_PT_OK; ++i)
-        {
-            texelBytes += (uint64_t)v->textures[i].width * v->textures[i].height * 4u;
-            // (one staging area, one stream: the copy of texture i + 1 queues behind the kernel that reads texture i)
-            rc = create_device_texture(
-                ctx, v->textures[i], staging, nullptr, &textures[i], nullptr, withMips ? &ms->mips[i] : nullptr, baseColour[i] != 0);
-            if (withMips && rc == PROSPER_PT_OK) ms->mipTexelBytes += mip_texel_bytes(textures[i].width, textures[i].height, ms->mips[i].levelCount);
-        }
-        const hipError_t e = hipDeviceSynchronize();
-        if (staging) (void)hipFree(staging);
-        if (rc != PROSPER_PT_OK) return rc;
-        PPT_HIP(e);
-    }
-    ms->texelBytes = texelBytes;
-    // beyond the 8 x 4 MB of L2 the texels of a hit come from the Infinity Cache or HBM: overlap their fetches
-    // (debug option batchedTextures = 0 / 1 forces either path: same pixels, tested)
-    s.batchedTextures = texel_set_is_big(texelBytes) ? 1u : 0u;
-    if (ctx->debug.batchedTextures >= 0) s.batchedTextures = ctx->debug.batchedTextures ? 1u : 0u;
-    // material texture packs (pt_scene.hpp MaterialPack): base / MR / normal interleaved per texel where a material's
-    // three textures share extent and sampler.  Debug option noTexturePacks keeps every material unpacked.
-    // Compact packs where the texels outgrow the caches (the threshold of the batched loads above): on a small texture set
-    // the bytes are not what the shade kernel waits for, and two kinds of pack in one wave cost a divergent branch
-    // (FlightHelmet fixture: +1 % on the step).  Debug option widePacks = 1 / 0 forces the 16-byte / the compact pack.
-    std::vector<MaterialPack> &packs = ms->packs;
-    packs.assign(v->materialCount, MaterialPack{nullptr, 0u, 0u, 0u, 0u});
-    uint32_t packedMaterials = 0;
-    bool widePacks = !texel_set_is_big(texelBytes);
-    if (ctx->debug.widePacks >= 0) widePacks = ctx->debug.widePacks != 0;
-    for (uint32_t i = 0; i < v->materialCount; ++i)
-    {
-        if ((rc = build_material_pack(ctx, v->materials[i], textures, ctx->debug.noTexturePacks != 0, widePacks, nullptr, &packs[i]))) return rc;
-        packedMaterials += packs[i].texels ? 1u : 0u;
-    }
-    PPT_HIP(hipGetLastError());
-    PPT_HIP(hipDeviceSynchronize());
-    if ((rc = upload(ctx, packs.data(), packs.size() * sizeof(MaterialPack), &d))) return rc;
-    s.materialPacks = static_cast<const MaterialPack *>(d);
-    ctx->packedMaterials = packedMaterials;
-    ms->packedMaterials = packedMaterials;
-    // A texture that only packed materials use is never sampled by itself again (sample_material takes the pack): its
-    // own copy goes - half of a packed scene's texel memory.  What keeps a texture: an unpacked material, or the any-hit
-    // of a MASK / BLEND material, which reads the base colour's alpha out of the texture itself.
-    {
-        std::vector<uint8_t> needed(textures.size(), 0);
-        needed[0] = 1;
-        for (uint32_t i = 0; i < v->materialCount; ++i)
-        {
-            const prosper_MaterialData &m = v->materials[i];
-            const uint32_t t3[3] = {m.baseColorTextureSampler & 0xFFFFFFu, m.metallicRoughnessTextureSampler & 0xFFFFFFu,
-                                    m.normalTextureSampler & 0xFFFFFFu};
-            if (packs[i].texels == nullptr)
-                for (uint32_t t : t3) needed[t] = 1;
-            if (m.alphaMode != PROSPER_ALPHA_MODE_OPAQUE) needed[t3[0]] = 1;
-        }
-        // (a texture no material samples yet stays: it is what a streamed-in material will point at)
-        std::vector<uint8_t> sampled(textures.size(), 0);
-        for (uint32_t i = 0; i < v->materialCount; ++i)
-        {
-            const prosper_MaterialData &m = v->materials[i];
-            sampled[m.baseColorTextureSampler & 0xFFFFFFu] = sampled[m.metallicRoughnessTextureSampler & 0xFFFFFFu] =
-                sampled[m.normalTextureSampler & 0xFFFFFFu] = 1;
-        }
-        for (uint32_t i = 1; i < v->textureCount; ++i)
-            if (!needed[i] && sampled[i] && textures[i].texels)
-            {
-                device_free(ctx, textures[i].texels);
-                textures[i].texels = nullptr;
-            }
-    }
-    if ((rc = upload(ctx, textures.data(), textures.size() * sizeof(DeviceTexture), &d))) return rc;
-    s.textures = static_cast<const DeviceTexture *>(d);
-    if (withMips)
-    {
-        if ((rc = upload(ctx, ms->mips.data(), ms->mips.size() * sizeof(DeviceTextureMips), &d))) return rc;
-        ctx->textureMips = static_cast<const DeviceTextureMips *>(d);
-    }
-    const double textureSeconds = seconds_since(tTextures);
-
-    // lights: one block (directional, point list, spot list), the first of up to three versions
-    {
-        LightState *ls = new (std::nothrow) LightState();
-        if (ls) ls->mirror = new (std::nothrow) LightBlock();
-        if (!ls || !ls->mirror)
-        {
-            delete ls;
-            return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "out of host memory");
-        }
-        ctx->lights = ls;
-        ls->mirror->directional = *v->directionalLight;
-        ls->mirror->points = *v->pointLights;
-        ls->mirror->spots = *v->spotLights;
-        if ((rc = upload(ctx, ls->mirror, sizeof(LightBlock), &d))) return rc;
-        ls->dBlocks[0] = static_cast<LightBlock *>(d);
-        s.directionalLight = &ls->dBlocks[0]->directional;
-        s.pointLights = &ls->dBlocks[0]->points;
-        s.spotLights = &ls->dBlocks[0]->spots;
-    }
-    s.pointLightCount = v->pointLights->count;
-    s.spotLightCount = v->spotLights->count;
-    s.materialCount = v->materialCount;
-
-    // skybox
-    s.skybox = nullptr;
-    s.skyboxFaceSize = 0;
-    if (v->skybox.texels)
-    {
-        // kept with a one-texel seamless border per face (pt_device.hpp fetch_cube_rgb); the plain copy is only the source
-        const size_t bytes = 6ull * v->skybox.faceSize * v->skybox.faceSize * 4u * sizeof(uint16_t);
-        const size_t n2 = (size_t)v->skybox.faceSize + 2u;
-        void *plain = nullptr;
-        if ((rc = upload(ctx, v->skybox.texels, bytes, &plain))) return rc;
-        if ((rc = device_alloc(ctx, 6ull * n2 * n2 * 4u * sizeof(uint16_t), &d))) return rc;
-        launch_border_skybox(static_cast<const uint16_t *>(plain), v->skybox.faceSize, d, nullptr);
-        PPT_HIP(hipGetLastError());
-        PPT_HIP(hipDeviceSynchronize());
-        device_free(ctx, plain);
-        s.skybox = static_cast<const uint16_t *>(d);
-        s.skyboxFaceSize = v->skybox.faceSize;
-    }
-
-    // ---- acceleration structure (replaces buildNextBlas/buildCurrentTlas, World.cpp:585-802) ----
-    // ---- what the any-hit shader reads: one 32-byte record per non-opaque triangle, one per material, and the
-    //      materials' alpha bounds (pt_scene.hpp AlphaTriangle / AlphaMaterial) ----
-    {
-        std::vector<AlphaMaterial> &alphaMaterials = ms->alphaMaterials;
-        alphaMaterials.assign(v->materialCount ? v->materialCount : 1, AlphaMaterial{});
-        uint64_t boundBytes = 0;
-        for (uint32_t i = 0; i < v->materialCount; ++i)
-        {
-            uint64_t bytes = 0;
-            if ((rc = build_alpha_material(ctx, v->materials[i], textures, ms->samplers, nullptr, &alphaMaterials[i], &bytes))) return rc;
-            boundBytes += bytes;
-        }
-        PPT_HIP(hipGetLastError());
-        if ((rc = upload(ctx, alphaMaterials.data(), alphaMaterials.size() * sizeof(AlphaMaterial), &d))) return rc;
-        s.alphaMaterials = static_cast<const AlphaMaterial *>(d);
-        ctx->alphaBoundBytes = boundBytes;
-        ms->alphaBoundBytes = boundBytes;
-        // layout of the table block of a later version (pt_materials.cpp flush_pending_materials)
-        auto align16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
-        ms->packsOffset = align16(ms->materials.size() * sizeof(prosper_MaterialData));
-        ms->alphaOffset = ms->packsOffset + align16(ms->packs.size() * sizeof(MaterialPack));
-        ms->texturesOffset = ms->alphaOffset + align16(ms->alphaMaterials.size() * sizeof(AlphaMaterial));
-        ms->mipsOffset = ms->texturesOffset + align16(ms->textures.size() * sizeof(DeviceTexture));
-        ms->blockBytes = ms->mipsOffset + align16(ms->mips.size() * sizeof(DeviceTextureMips));
-    }
-
-    if ((rc = finish_geometry(ctx, target, job))) return rc;
-    ctx->stats.deviceBytes = ctx->sceneBytes;
-    ctx->stats.alphaBoundBytes = ctx->alphaBoundBytes;
-    ctx->stats.textureSeconds = textureSeconds;
-    ctx->stats.uploadSeconds = seconds_since(tUpload);
-    return PROSPER_PT_OK;
 }
 
 } // namespace
@@ -797,9 +432,14 @@ int prosper_pt_get_debug_options(prosper_pt_ctx *ctx, prosper_pt_debug_options *
     return PROSPER_PT_OK;
 }
 
+} // extern "C"
+
+namespace
+{
+
 // What a context owns from its creation on: the timed events of its renders, the work streams, the work counters, the
 // passes' state.
-static int create_context_resources(prosper_pt_ctx *ctx)
+int create_context_resources(prosper_pt_ctx *ctx)
 {
     int rc;
     if ((rc = ctx->timeline.create())) return rc;
@@ -823,6 +463,10 @@ static int create_context_resources(prosper_pt_ctx *ctx)
     const size_t counterBytes = kStageCount * kCounterCount * sizeof(unsigned long long);
     return grow_buffer(ctx->counters, GrowWait::None, nullptr, counterBytes, counterBytes, 0);
 }
+
+} // namespace
+
+extern "C" {
 
 int prosper_pt_create(const prosper_pt_device_desc *desc, prosper_pt_ctx **out_ctx)
 {
@@ -880,365 +524,10 @@ void prosper_pt_destroy(prosper_pt_ctx *ctx)
     delete ctx; // (its events, streams and DeviceBuffers with it: the device is set and idle)
 }
 
-int prosper_pt_upload_scene(prosper_pt_ctx *ctx, const prosper_pt_scene_view *scene)
-{
-    if (!ctx || !scene) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_upload_scene: null argument");
-    int rc = validate_scene(scene, (ctx->flags & PROSPER_PT_CREATE_TEXTURE_MIPS) != 0);
-    if (rc != PROSPER_PT_OK) return rc;
-    for (const PassModule *m : kPassModules)
-        if (m->forget_scene) m->forget_scene(ctx);
-    PPT_HIP(hipSetDevice(ctx->device));
-    discard_mesh_build(ctx); // (a worker may still be launching)
-    PPT_HIP(hipDeviceSynchronize());
-    forget_animations(ctx); // (its read-back with it: the new scene's mirrors are the new scene's)
-    free_scene(ctx);
-    rc = upload_scene_impl(ctx, scene);
-    if (rc != PROSPER_PT_OK)
-    {
-        free_scene(ctx);
-        return rc;
-    }
-    ctx->haveScene = true;
-    return PROSPER_PT_OK;
-}
-
-// the staged light set into the next device version, on the stream of the render that is about to read it
-static int flush_pending_lights(prosper_pt_ctx *ctx, hipStream_t stream)
-{
-    LightState *ls = ctx->lights;
-    if (!ls || !ls->pending) return PROSPER_PT_OK;
-    const uint32_t v = ls->versions.next();
-    int rc;
-    if (!ls->dBlocks[v])
-    {
-        void *d = nullptr;
-        if ((rc = device_alloc(ctx, sizeof(LightBlock), &d))) return rc;
-        ls->dBlocks[v] = static_cast<LightBlock *>(d);
-    }
-    if ((rc = ls->versions.wait_free(v, stream))) return rc;
-    const LightBlock *staged = ls->staging.pending_buffer();
-    PPT_HIP(hipMemcpyAsync(ls->dBlocks[v], staged, sizeof(LightBlock), hipMemcpyHostToDevice, stream));
-    if ((rc = ls->staging.copy_enqueued(stream))) return rc;
-    if ((rc = ls->ready.record(stream))) return rc;
-    ls->versions.commit(v);
-    ctx->scene.directionalLight = &ls->dBlocks[v]->directional;
-    ctx->scene.pointLights = &ls->dBlocks[v]->points;
-    ctx->scene.spotLights = &ls->dBlocks[v]->spots;
-    ctx->scene.pointLightCount = staged->points.count;
-    ctx->scene.spotLightCount = staged->spots.count;
-    ls->pending = false;
-    ls->updates++;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_update_lights(
-    prosper_pt_ctx *ctx, const prosper_DirectionalLightParameters *directionalLight,
-    const prosper_PointLightsBuffer *pointLights, const prosper_SpotLightsBuffer *spotLights)
-{
-    if (!ctx || !directionalLight || !pointLights || !spotLights)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_lights: null argument");
-    if (!ctx->haveScene || !ctx->lights) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    if (pointLights->count > PROSPER_MAX_POINT_LIGHT_COUNT || spotLights->count > PROSPER_MAX_SPOT_LIGHT_COUNT)
-        return fail(PROSPER_PT_ERR_SCENE, "light count exceeds 1024");
-    LightState *ls = ctx->lights;
-    if (const int rc = sync_animation_mirrors(ctx)) return rc; // (an animated update may have moved the lights)
-    // prosper rewrites the buffers every frame (World.cpp:531-535) and mostly with what they held: that costs a memcmp
-    if (std::memcmp(&ls->mirror->directional, directionalLight, sizeof(*directionalLight)) == 0 &&
-        std::memcmp(&ls->mirror->points, pointLights, sizeof(*pointLights)) == 0 &&
-        std::memcmp(&ls->mirror->spots, spotLights, sizeof(*spotLights)) == 0)
-        return PROSPER_PT_OK;
-    PPT_HIP(hipSetDevice(ctx->device));
-    LightBlock *staged = nullptr;
-    if (const int rc = ls->staging.acquire(sizeof(LightBlock), ls->pending, &staged)) return rc;
-    staged->directional = *directionalLight;
-    staged->points = *pointLights;
-    staged->spots = *spotLights;
-    *ls->mirror = *staged;
-    ls->pending = true;
-    return PROSPER_PT_OK;
-}
-
-// The synchronous path: re-split the instances that moved since the last build, re-assemble, upload (what
-// prosper_pt_update_transforms did before the refit existed; prosper's own TLAS build is of this kind, on the GPU).
-static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream);
-static int rebuild_hierarchy_on_host(prosper_pt_ctx *ctx)
-{
-    PPT_HIP(hipSetDevice(ctx->device));
-    {
-        // a background build of streamed-in meshes holds the subtrees: its result is installed first
-        const int prc = poll_mesh_build(ctx, true);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    AccelState *acc = ctx->accel;
-    const auto t0 = std::chrono::steady_clock::now();
-    {
-        int frc = flush_pending_update(ctx, nullptr); // the moved triangles must be in the flat array
-        if (frc == PROSPER_PT_OK) frc = sync_animation_mirrors(ctx);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
-    PPT_HIP(hipDeviceSynchronize()); // renders in flight read the old hierarchy
-    acc->stale = true;               // until the new hierarchy is up
-    bool any = false;
-    if (acc->flat.size() != (size_t)acc->total) acc->flat.resize((size_t)acc->total); // (a first tree built on the GPU kept no host copy)
-    for (size_t r = 0; r < acc->ranges.size(); ++r)
-    {
-        if (!(acc->movedSinceBuild[r] || !acc->instanced) || !acc->ranges[r].count) continue;
-        any = any || acc->movedSinceBuild[r];
-        PPT_HIP(hipMemcpy(
-            acc->flat.data() + acc->ranges[r].first, acc->dFlat + acc->ranges[r].first,
-            sizeof(WorldTriangle) * (size_t)acc->ranges[r].count, hipMemcpyDeviceToHost));
-    }
-    BvhBuildResult bvh;
-    bool instancedNow = acc->instanced;
-    const auto tBuild = std::chrono::steady_clock::now();
-    try
-    {
-        if (ctx->debug.failNextUpdate)
-        {
-            ctx->debug.failNextUpdate = 0;
-            throw std::runtime_error("debug option failNextUpdate is set");
-        }
-        if (acc->instanced)
-            bvh = acc->bvh.rebuild(acc->flat.data(), acc->movedSinceBuild, build_options(ctx));
-        else if (acc->foreignTree && ctx->debug.flatBvh == 0)
-        {
-            // the last build ran on the GPU: no subtree is kept, every instance is split as the scene's first build
-            // splits it (begin_geometry), with the same way out for a spliced tree that is too deep
-            try
-            {
-                bvh = acc->bvh.build(acc->flat.data(), acc->total, acc->ranges, build_options(ctx));
-                instancedNow = true;
-            }
-            catch (const std::exception &)
-            {
-                bvh = build_bvh(acc->flat.data(), acc->total, build_options(ctx));
-            }
-        }
-        else
-            bvh = build_bvh(acc->flat.data(), acc->total, build_options(ctx));
-    }
-    catch (const std::exception &ex)
-    {
-        return fail(PROSPER_PT_ERR_UNSUPPORTED, std::string("BVH rebuild failed: ") + ex.what());
-    }
-    const double buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild).count();
-    GeometryTarget target = context_target(ctx);
-    const int rc = upload_hierarchy(ctx, target, bvh);
-    if (rc != PROSPER_PT_OK) return rc;
-    acc->stale = false;
-    acc->instanced = instancedNow;
-    acc->foreignTree = false;
-    acc->gpuStagesValid = false;
-    acc->rebuilds++;
-    ctx->stats.nodeCount = bvh.nodes.size();
-    ctx->stats.maxDepth = bvh.maxDepth;
-    ctx->stats.deviceBytes = ctx->sceneBytes;
-    ctx->stats.bvhBuildSeconds = buildSeconds;
-    ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return PROSPER_PT_OK;
-}
-
-// The same contract with the tree made on the GPU (pt_bvh_build.hpp): a pending background geometry is
-// installed first, a staged update flushed, the device synchronised; then the linear BVH over the device's own flat world
-// triangles.  A tree the traversal cannot hold is refused and the scene stays exactly as it was.  An empty scene has
-// nothing to build on the device and takes the host's path.
-static int rebuild_hierarchy_on_gpu(prosper_pt_ctx *ctx)
-{
-    PPT_HIP(hipSetDevice(ctx->device));
-    {
-        const int prc = poll_mesh_build(ctx, true);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    AccelState *acc = ctx->accel;
-    if (acc->total == 0) return rebuild_hierarchy_on_host(ctx);
-    const auto t0 = std::chrono::steady_clock::now();
-    {
-        int frc = flush_pending_update(ctx, nullptr); // the moved triangles must be in the flat array
-        if (frc == PROSPER_PT_OK) frc = sync_animation_mirrors(ctx);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
-    PPT_HIP(hipDeviceSynchronize()); // renders in flight read the old hierarchy
-    const auto tBuild = std::chrono::steady_clock::now();
-    GeometryTarget target = context_target(ctx);
-    const int rc = build_hierarchy_on_device(ctx, target);
-    if (rc != PROSPER_PT_OK) return rc;
-    acc->rebuilds++;
-    ctx->stats.deviceBytes = ctx->sceneBytes;
-    ctx->stats.bvhBuildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tBuild).count();
-    ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return PROSPER_PT_OK;
-}
-
-static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx)
-{
-    return ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU ? rebuild_hierarchy_on_gpu(ctx) : rebuild_hierarchy_on_host(ctx);
-}
-
-static float rebuild_cost_ratio(const prosper_pt_ctx *ctx)
-{
-    return ctx->debug.rebuildCostRatio > 0.0f ? std::max(1.0f, ctx->debug.rebuildCostRatio) : 1.3f;
-}
-
-// World::updateScene + the per-frame TLAS rebuild (World.cpp:359-466,749-802,878-928) as a REFIT: the new transforms, the
-// world triangles and new boxes for the unchanged tree - no host build, no device-wide synchronisation.  Hits do not
-// depend on the hierarchy (hit contract), so the image is the one a fresh upload gives.  Two steps:
-//   stage_transforms      the call itself: which instances moved, the table into pinned staging; nothing on the GPU
-//   flush_pending_update  run by the next consumer of the scene on ITS stream - a pipelined render's own chain - into the
-//                         NEXT scene version: the frames in flight go on reading theirs, nothing waits for them
-// What a refit cannot do is keep the tree GOOD when instances travel far: every refit leaves the tree's surface-area
-// measure behind, and once that has grown by 30 % over its value at the last build the next update rebuilds
-// (synchronously: prosper_pt_rebuild_hierarchy).
-static int rebuild_hierarchy_impl(prosper_pt_ctx *ctx);
-
-static int flush_pending_update(prosper_pt_ctx *ctx, hipStream_t stream)
-{
-    AccelState *acc = ctx->accel;
-    if (!acc) return PROSPER_PT_OK;
-    // a staged prosper_pt_animate: the table of the new version is the staged one (or the current one) with the entries
-    // the scene's nodes bind evaluated over it, ahead of the refit
-    const bool animate = animation_pending(ctx);
-    if (!acc->pending && !animate) return PROSPER_PT_OK;
-    const uint32_t tableCount = acc->pending ? acc->pendingCount : (uint32_t)acc->transforms.size();
-    const uint32_t v = acc->versions.next();
-    const size_t transformBytes = sizeof(prosper_ModelInstanceTransforms) * (tableCount ? tableCount : 1);
-    const size_t triBytes = sizeof(WorldTriangle) * (size_t)(acc->total ? acc->total : 1);
-    void *d = nullptr;
-    int rc;
-    if (!acc->dTransformsV[v])
-    {
-        if ((rc = device_alloc(ctx, transformBytes, &d))) return rc;
-        acc->dTransformsV[v] = static_cast<prosper_ModelInstanceTransforms *>(d);
-    }
-    if (!acc->dTrisV[v])
-    {
-        if ((rc = device_alloc(ctx, triBytes, &d))) return rc;
-        acc->dTrisV[v] = static_cast<WorldTriangle *>(d);
-    }
-    if (!acc->dNodesV[v])
-    {
-        if ((rc = device_alloc(ctx, acc->nodeCapacityBytes, &d))) return rc;
-        acc->dNodesV[v] = static_cast<BvhNode *>(d);
-        acc->nodesCurrent[v] = false;
-    }
-    // Everything is enqueued for version v through LOCAL names; the context switches to v only after the last call has
-    // succeeded.  On a failure the previous version stays current and the update stays pending (the next consumer of the
-    // scene tries again); what was half-written into v is rewritten by that retry.
-    // the version's last readers (three updates ago), and the previous update: it wrote the node array copied below,
-    // and it shares the flat triangle array and the bounds scratch with this one
-    if ((rc = acc->versions.wait_free(v, stream))) return rc;
-    if ((rc = acc->sceneDone.wait(stream))) return rc;
-    if (!acc->nodesCurrent[v])
-    {
-        PPT_HIP(hipMemcpyAsync(acc->dNodesV[v], acc->dNodes, (size_t)acc->nodeCount * sizeof(BvhNode), hipMemcpyDeviceToDevice, stream));
-        acc->nodesCurrent[v] = true;
-    }
-    if (acc->pending)
-    {
-        PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], acc->staging.pending_buffer(), sizeof(prosper_ModelInstanceTransforms) * acc->pendingCount, hipMemcpyHostToDevice, stream));
-        if ((rc = acc->staging.copy_enqueued(stream))) return rc;
-    }
-    else if (tableCount)
-        PPT_HIP(hipMemcpyAsync(acc->dTransformsV[v], ctx->dTransforms, sizeof(prosper_ModelInstanceTransforms) * tableCount, hipMemcpyDeviceToDevice, stream));
-    // The lights its nodes carry go into the next light version, a copy of the current one, ordered like a flushed
-    // prosper_pt_update_lights (a staged one is flushed first: it is what the copy starts from).
-    LightState *ls = ctx->lights;
-    const bool animateLights = animate && ls && animation_moves_lights(ctx);
-    uint32_t lv = 0;
-    if (animateLights)
-    {
-        if ((rc = flush_pending_lights(ctx, stream))) return rc;
-        lv = ls->versions.next();
-        if (!ls->dBlocks[lv])
-        {
-            if ((rc = device_alloc(ctx, sizeof(LightBlock), &d))) return rc;
-            ls->dBlocks[lv] = static_cast<LightBlock *>(d);
-        }
-        if ((rc = ls->versions.wait_free(lv, stream))) return rc;
-        if ((rc = ls->ready.wait(stream))) return rc;
-        PPT_HIP(hipMemcpyAsync(ls->dBlocks[lv], ls->dBlocks[ls->versions.cur], sizeof(LightBlock), hipMemcpyDeviceToDevice, stream));
-        if ((rc = ls->versions.mark_read(stream))) return rc; // (the copy read the current version)
-    }
-    if (animate && (rc = enqueue_animation(ctx, acc->dTransformsV[v], tableCount, animateLights ? ls->dBlocks[lv] : nullptr, stream))) return rc;
-    if (animateLights && (rc = ls->ready.record(stream))) return rc;
-    if ((rc = enqueue_instance_scales(ctx, acc, v, acc->dTransformsV[v], tableCount, stream))) return rc;
-    // world-space triangles again, in both orders (the shading and any-hit records hold object-space attributes and stay
-    // as they are), then the boxes.  (Also when only transforms of instances without geometry changed: a version must be
-    // whole.)
-    DeviceScene next = ctx->scene;
-    next.nodes = acc->dNodesV[v];
-    next.triangles = acc->dTrisV[v];
-    next.modelInstanceTransforms = acc->dTransformsV[v];
-    launch_flatten_triangles(
-        next, acc->dOffsets, acc->drawInstanceCount, acc->dFlags, acc->dFlat, nullptr, nullptr, (uint32_t)acc->total, stream,
-        acc->dLeafPosition, acc->dTrisV[v]);
-    PPT_HIP(hipGetLastError());
-    acc->flatStale = true; // (the flat array now holds the new pose whatever happens next)
-    if (acc->total && (rc = enqueue_refit(acc, bvh_pad_coefficient(build_options(ctx)), acc->dNodesV[v], acc->dTrisV[v], v, stream))) return rc;
-    if (acc->total && acc->foreignTree && (rc = enqueue_nest_boxes(acc, acc->dNodesV[v], stream))) return rc;
-    if ((rc = acc->sceneDone.record(stream))) return rc;
-    // ---- commit: the new version becomes the scene ----
-    acc->versions.commit(v);
-    acc->dNodes = acc->dNodesV[v];
-    acc->dTris = acc->dTrisV[v];
-    ctx->dTransforms = acc->dTransformsV[v];
-    ctx->scene = next;
-    acc->refits++;
-    acc->pending = false;
-    acc->stale = false;
-    if (animateLights)
-    {
-        ls->versions.commit(lv);
-        ctx->scene.directionalLight = &ls->dBlocks[lv]->directional;
-        ctx->scene.pointLights = &ls->dBlocks[lv]->points;
-        ctx->scene.spotLights = &ls->dBlocks[lv]->spots;
-        ls->updates++;
-    }
-    if (animate) animation_committed(ctx);
-    return PROSPER_PT_OK;
-}
-
 } // extern "C"
 
 namespace ppt
 {
-
-int check_scene(prosper_pt_ctx *ctx, const char *what)
-{
-    if (!ctx->haveScene) return fail(PROSPER_PT_ERR_NO_SCENE, std::string(what) + " called before prosper_pt_upload_scene");
-    if (ctx->meshBuild)
-    {
-        const int prc = poll_mesh_build(ctx, false);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    if (ctx->accel && ctx->accel->stale && !ctx->accel->pending)
-        return fail(PROSPER_PT_ERR_NO_SCENE, "the last prosper_pt_update_transforms failed: update the transforms again (or upload the scene) before tracing");
-    return PROSPER_PT_OK;
-}
-
-int flush_scene_updates(prosper_pt_ctx *ctx, hipStream_t s, hipStream_t reader)
-{
-    PPT_HIP(hipSetDevice(ctx->device));
-    int rc = flush_pending_update(ctx, s);
-    if (rc == PROSPER_PT_OK) rc = flush_pending_lights(ctx, s);
-    if (rc == PROSPER_PT_OK) rc = flush_pending_materials(ctx, s);
-    // a flush enqueued on another stream than the reader's (a pipelined render's chain, this one's or an earlier one's, or
-    // prosper_pt_update_transforms_async) must be done before anything on the reader's stream reads the scene
-    if (rc == PROSPER_PT_OK && ctx->lights) rc = ctx->lights->ready.wait(reader);
-    if (rc == PROSPER_PT_OK && ctx->materialState) rc = ctx->materialState->ready.wait(reader);
-    if (rc == PROSPER_PT_OK && ctx->accel) rc = ctx->accel->sceneDone.wait(reader);
-    return rc;
-}
-
-// The scene and light versions a render (or a pass over a G-buffer) read are free again behind its last kernel on `s` (the
-// accumulate kernel follows the path stages on the caller's stream): VersionRing::mark_read.
-int mark_versions_read(prosper_pt_ctx *ctx, hipStream_t s)
-{
-    int rc = PROSPER_PT_OK;
-    if (ctx->accel) rc = ctx->accel->versions.mark_read(s);
-    if (rc == PROSPER_PT_OK && ctx->lights) rc = ctx->lights->versions.mark_read(s);
-    if (rc == PROSPER_PT_OK && ctx->materialState) rc = ctx->materialState->versions.mark_read(s);
-    return rc;
-}
 
 // rt/ray.glsl:21-35 and scene/camera.glsl:46-51 read these parts of CameraUniforms
 void set_camera_ray_params(RenderParams &p, const prosper_CameraUniforms *camera)
@@ -1293,272 +582,7 @@ int prepare_hdr(prosper_pt_ctx *ctx, uint32_t width, uint32_t height, const pros
 
 } // namespace ppt
 
-int ppt::stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count)
-{
-    AccelState *acc = ctx->accel;
-    if (const int src = sync_animation_mirrors(ctx)) return src; // (the table an animated update left on the device)
-    const auto t0 = std::chrono::steady_clock::now();
-    // which instances moved (World::updateScene rewrites every transform each frame, World.cpp:359-466; most are unchanged)
-    bool any = acc->stale;
-    for (size_t r = 0; r < acc->ranges.size(); ++r)
-    {
-        const uint32_t mi = acc->rangeModelInstance[r];
-        if (acc->stale || std::memcmp(&transforms[mi], &acc->transforms[mi], sizeof(prosper_ModelInstanceTransforms)) != 0)
-        {
-            acc->movedSinceBuild[r] = 1;
-            any = true;
-        }
-    }
-    if (!any && std::memcmp(transforms, acc->transforms.data(), sizeof(prosper_ModelInstanceTransforms) * count) == 0) return PROSPER_PT_OK;
-    PPT_HIP(hipSetDevice(ctx->device));
-    // the measure of the newest refit that has finished (the newest may still be queued behind frames in flight)
-    {
-        const int prc = poll_refit_cost(acc, false);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    // into pinned staging (a pageable source would make the later copy synchronous).  An update that was never consumed
-    // is simply replaced: its staging buffer is reused.
-    prosper_ModelInstanceTransforms *staged = nullptr;
-    if (const int rc = acc->staging.acquire(sizeof(prosper_ModelInstanceTransforms) * (count ? count : 1), acc->pending, &staged)) return rc;
-    std::memcpy(staged, transforms, sizeof(prosper_ModelInstanceTransforms) * count);
-    acc->pending = true;
-    acc->pendingCount = count;
-    acc->transforms.assign(transforms, transforms + count);
-    ctx->stats.bvhBuildSeconds = 0.0;
-    ctx->stats.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (any && ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
-    // (site DRIFT: a background generation from the GPU builder under either selected builder; nothing waits for the device)
-    if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_DRIFT))
-        return ctx->meshBuild ? PROSPER_PT_OK : start_mesh_build(ctx, true);
-    // (the GPU builder is quick enough for the synchronous route; the worker thread is the host builder's)
-    if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
-    if (any && acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild)
-    {
-        // The refits have degraded the tree: the instances that moved since the last build are split again - by the worker
-        // thread that also takes up streamed-in meshes, into a new geometry generation, while the frame loop goes on
-        // refitting and rendering this one (until round 4 this was a 60-75 ms synchronous rebuild in the middle of the
-        // frame loop).  The generation is switched in by the first render after it is done.
-        return start_mesh_build(ctx, true);
-    }
-    return PROSPER_PT_OK;
-}
-
 extern "C" {
-
-static int update_transforms_impl(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, hipStream_t stream, bool flushNow)
-{
-    const int rc = stage_transforms(ctx, transforms, count);
-    if (rc != PROSPER_PT_OK || !flushNow) return rc;
-    return flush_pending_update(ctx, stream);
-}
-
-static int check_update_arguments(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count)
-{
-    if (!ctx || !transforms) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_transforms: null argument");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    if (count != ctx->accel->transforms.size())
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_transforms: count differs from the scene's modelInstanceCount");
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_update_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count)
-{
-    const int rc = check_update_arguments(ctx, transforms, count);
-    return rc != PROSPER_PT_OK ? rc : update_transforms_impl(ctx, transforms, count, nullptr, false);
-}
-
-int prosper_pt_update_transforms_async(
-    prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count, uint32_t flags, void *stream)
-{
-    if (flags & ~(uint32_t)PROSPER_PT_UPDATE_NOW) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_update_transforms_async: unknown flag");
-    const int rc = check_update_arguments(ctx, transforms, count);
-    return rc != PROSPER_PT_OK ? rc : update_transforms_impl(ctx, transforms, count, static_cast<hipStream_t>(stream), (flags & PROSPER_PT_UPDATE_NOW) != 0);
-}
-
-int prosper_pt_animate(prosper_pt_ctx *ctx, float timeS, uint32_t flags, void *stream)
-{
-    if (flags & ~(uint32_t)PROSPER_PT_UPDATE_NOW) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: unknown flag");
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: null argument");
-    if (!std::isfinite(timeS)) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_animate: timeS is not finite");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    int rc = stage_animation(ctx, timeS);
-    if (rc != PROSPER_PT_OK) return rc;
-    // like a staged table (stage_transforms): refits leave the tree's measure behind, and once it has grown too far the
-    // instances that moved are split again in the background
-    AccelState *acc = ctx->accel;
-    PPT_HIP(hipSetDevice(ctx->device));
-    if ((rc = poll_refit_cost(acc, false))) return rc;
-    if (ctx->debug.alwaysRebuild) return rebuild_hierarchy_impl(ctx); // (debug option: the synchronous path, every time)
-    const bool driftSite = (ctx->gpuHierarchySites & PROSPER_PT_GPU_BUILD_SITE_DRIFT) != 0; // (stage_transforms)
-    if (!driftSite && acc->lastCostRatio > rebuild_cost_ratio(ctx) && ctx->hierarchyBuilder == PROSPER_PT_BUILDER_GPU) return rebuild_hierarchy_impl(ctx);
-    if (acc->lastCostRatio > rebuild_cost_ratio(ctx) && !ctx->meshBuild && (rc = start_mesh_build(ctx, true))) return rc;
-    if (!(flags & PROSPER_PT_UPDATE_NOW)) return PROSPER_PT_OK;
-    return flush_pending_update(ctx, static_cast<hipStream_t>(stream));
-}
-
-int prosper_pt_rebuild_hierarchy(prosper_pt_ctx *ctx)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_rebuild_hierarchy: null argument");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    return rebuild_hierarchy_impl(ctx);
-}
-
-int prosper_pt_build_hierarchy_gpu(prosper_pt_ctx *ctx)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_build_hierarchy_gpu: null argument");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    return rebuild_hierarchy_on_gpu(ctx);
-}
-
-int prosper_pt_set_hierarchy_builder(prosper_pt_ctx *ctx, uint32_t builder)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_hierarchy_builder: null argument");
-    if (builder != PROSPER_PT_BUILDER_HOST && builder != PROSPER_PT_BUILDER_GPU)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_hierarchy_builder: unknown builder");
-    ctx->hierarchyBuilder = builder;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_set_gpu_hierarchy_method(prosper_pt_ctx *ctx, uint32_t method, uint32_t radius)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: null argument");
-    if (method != PROSPER_PT_GPU_HIERARCHY_LINEAR && method != PROSPER_PT_GPU_HIERARCHY_PLOC)
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: unknown method");
-    if (radius > kPlocMaxRadius) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_method: the radius is 1 .. 32 (0: the default)");
-    ctx->gpuHierarchyMethod = method;
-    ctx->gpuHierarchyRadius = radius;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_set_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t sites)
-{
-    if (!ctx) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_sites: null argument");
-    constexpr uint32_t known = PROSPER_PT_GPU_BUILD_SITE_UPLOAD | PROSPER_PT_GPU_BUILD_SITE_MESH_UPDATES | PROSPER_PT_GPU_BUILD_SITE_DRIFT;
-    if (sites & ~known) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_set_gpu_hierarchy_sites: unknown build site");
-    ctx->gpuHierarchySites = sites;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_gpu_hierarchy_sites(prosper_pt_ctx *ctx, uint32_t *sites)
-{
-    if (!ctx || !sites) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gpu_hierarchy_sites: null argument");
-    *sites = ctx->gpuHierarchySites;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_gpu_hierarchy_method_info(prosper_pt_ctx *ctx, prosper_pt_gpu_hierarchy_method_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_gpu_hierarchy_method_info: null argument");
-    *out = prosper_pt_gpu_hierarchy_method_info{};
-    out->selectedMethod = ctx->gpuHierarchyMethod;
-    out->selectedRadius = ctx->gpuHierarchyRadius ? ctx->gpuHierarchyRadius : kPlocDefaultRadius;
-    const AccelState *acc = ctx->haveScene ? ctx->accel : nullptr;
-    if (acc && acc->foreignTree)
-    {
-        out->method = acc->gpuMethod;
-        out->radius = acc->gpuRadius;
-        out->rounds = acc->gpuRounds;
-        out->finishRounds = acc->gpuFinishRounds;
-    }
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_hierarchy_build_info(prosper_pt_ctx *ctx, prosper_pt_hierarchy_build_info *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_hierarchy_build_info: null argument");
-    *out = prosper_pt_hierarchy_build_info{};
-    out->selectedBuilder = ctx->hierarchyBuilder;
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    {
-        const int prc = ctx->meshBuild ? poll_mesh_build(ctx, false) : PROSPER_PT_OK;
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    const AccelState *acc = ctx->accel;
-    out->builder = acc->foreignTree ? PROSPER_PT_BUILDER_GPU : PROSPER_PT_BUILDER_HOST;
-    const uint32_t hostLeaf = ctx->debug.leafSize ? std::min(std::max(ctx->debug.leafSize, 1u), 8u) : kMaxLeafTriangles;
-    out->leafSize = acc->foreignTree ? acc->gpuLeafSize : hostLeaf;
-    out->nodeCount = acc->nodeCount;
-    out->levels = (uint32_t)acc->levelOffsets.size() - 1u;
-    out->depths = acc->foreignTree ? acc->gpuDepths : 0u;
-    out->stackBound = ctx->stats.maxDepth;
-    if (acc->foreignTree && acc->gpuStagesValid)
-        for (uint32_t k = 0; k < PROSPER_PT_HIERARCHY_BUILD_STAGES; ++k)
-        {
-            out->stageMs[k] = acc->gpuStageMs[k];
-            out->totalMs += acc->gpuStageMs[k];
-        }
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_debug_read_hierarchy_arrays(
-    prosper_pt_ctx *ctx, void *triangles, size_t triangle_bytes, void *permutation, size_t permutation_bytes)
-{
-    if (!ctx || !triangles || !permutation) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_hierarchy_arrays: null argument");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    PPT_HIP(hipSetDevice(ctx->device));
-    {
-        int frc = ctx->meshBuild ? poll_mesh_build(ctx, false) : PROSPER_PT_OK;
-        if (frc == PROSPER_PT_OK) frc = flush_pending_update(ctx, nullptr);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
-    const AccelState *acc = ctx->accel;
-    const size_t total = (size_t)acc->total;
-    if (triangle_bytes < total * sizeof(WorldTriangle) || permutation_bytes < total * sizeof(uint32_t))
-        return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_hierarchy_arrays: destination too small");
-    PPT_HIP(hipDeviceSynchronize());
-    if (total)
-    {
-        PPT_HIP(hipMemcpy(triangles, acc->dFlat, total * sizeof(WorldTriangle), hipMemcpyDeviceToHost));
-        PPT_HIP(hipMemcpy(permutation, acc->dPerm, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_get_hierarchy_state(prosper_pt_ctx *ctx, prosper_pt_hierarchy_state *out)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_get_hierarchy_state: null argument");
-    *out = prosper_pt_hierarchy_state{};
-    if (ctx->geometry)
-    {
-        out->meshUpdates = ctx->geometry->meshUpdates;
-        out->geometryInstalls = ctx->geometry->installs;
-        out->geometryBuildRunning = (ctx->meshBuild || ctx->geometry->dirty) ? 1u : 0u;
-    }
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    AccelState *acc = ctx->accel;
-    PPT_HIP(hipSetDevice(ctx->device));
-    {
-        const int frc = flush_pending_update(ctx, nullptr);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
-    {
-        const int prc = poll_refit_cost(acc, true);
-        if (prc != PROSPER_PT_OK) return prc;
-    }
-    out->refits = acc->refits;
-    out->rebuilds = acc->rebuilds;
-    out->costRatio = acc->lastCostRatio;
-    out->builtCost = acc->builtCost;
-    out->nodeCount = acc->nodeCount;
-    out->levels = (uint32_t)acc->levelOffsets.size() - 1u;
-    return PROSPER_PT_OK;
-}
-
-int prosper_pt_debug_read_nodes(prosper_pt_ctx *ctx, void *out, size_t byte_size)
-{
-    if (!ctx || !out) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_nodes: null argument");
-    if (!ctx->haveScene || !ctx->accel) return fail(PROSPER_PT_ERR_NO_SCENE, "no scene uploaded");
-    const size_t bytes = (size_t)ctx->accel->nodeCount * sizeof(BvhNode);
-    if (byte_size < bytes) return fail(PROSPER_PT_ERR_INVALID_ARGUMENT, "prosper_pt_debug_read_nodes: destination too small");
-    PPT_HIP(hipSetDevice(ctx->device));
-    {
-        const int frc = flush_pending_update(ctx, nullptr);
-        if (frc != PROSPER_PT_OK) return frc;
-    }
-    PPT_HIP(hipDeviceSynchronize());
-    PPT_HIP(hipMemcpy(out, ctx->accel->dNodes, bytes, hipMemcpyDeviceToHost));
-    return PROSPER_PT_OK;
-}
 
 int prosper_pt_get_scene_stats(prosper_pt_ctx *ctx, prosper_pt_scene_stats *out)
 {
@@ -1587,9 +611,14 @@ int prosper_pt_set_output_buffer(prosper_pt_ctx *ctx, void *device_rgba32f, size
     return PROSPER_PT_OK;
 }
 
+} // extern "C"
+
+namespace
+{
+
 // The wavefront pipeline's render: all frames of the batch are in flight together, in chunks that keep the workspace
 // under kMaxWavefrontSlots path slots, on render slot `slotIndex`.  `tp`: the caller's-stream timeline of a timed render.
-static int render_wavefront(
+int render_wavefront(
     prosper_pt_ctx *ctx, const RenderParams &p, bool countWork, bool pipelined, uint32_t slotIndex, LaunchTimeline *tp,
     hipStream_t s)
 {
@@ -1652,6 +681,19 @@ static int render_wavefront(
     if (tp) ctx->timedSlot = slotIndex;
     return PROSPER_PT_OK;
 }
+
+int read_stage_counters(prosper_pt_ctx *ctx, unsigned long long host[kStageCount * kCounterCount], void *stream)
+{
+    PPT_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PPT_HIP(hipMemcpyAsync(host, ctx->counters.ptr, kStageCount * kCounterCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    PPT_HIP(hipStreamSynchronize(s));
+    return PROSPER_PT_OK;
+}
+
+} // namespace
+
+extern "C" {
 
 int prosper_pt_render_frames(
     prosper_pt_ctx *ctx, const prosper_ReferencePC *pc, const prosper_CameraUniforms *camera, uint32_t width,
@@ -1827,15 +869,6 @@ int prosper_pt_tone_map(
         PPT_HIP(hipMemcpyAsync(host_rgba8, out, bytes, hipMemcpyDeviceToHost, s));
         PPT_HIP(hipStreamSynchronize(s));
     }
-    return PROSPER_PT_OK;
-}
-
-static int read_stage_counters(prosper_pt_ctx *ctx, unsigned long long host[kStageCount * kCounterCount], void *stream)
-{
-    PPT_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PPT_HIP(hipMemcpyAsync(host, ctx->counters.ptr, kStageCount * kCounterCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    PPT_HIP(hipStreamSynchronize(s));
     return PROSPER_PT_OK;
 }
 

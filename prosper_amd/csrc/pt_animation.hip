@@ -1,6 +1,6 @@
 // pt_animation.hip — glTF keyframe animation on the GPU (include/prosper_pt/prosper_pt.h "glTF keyframe animation";
 // DESIGN.md (f15)): World::updateAnimations + World::updateScene of the reference (src/scene/Animations.hpp:71-125,
-// Accessors.cpp:25-75, World.cpp:349-466) as two kernels that the scene update (prosper_pt.cpp flush_pending_update) runs
+// Accessors.cpp:25-75, World.cpp:349-466) as two kernels that the scene update (pt_scene_updates.cpp flush_pending_update) runs
 // ahead of the refit, the tables prosper_pt_set_animations makes for them, and the read-back that keeps the host mirrors of
 // the transform table and the light buffers in step.  The arithmetic is glm's, one operation per rounding
 // (-ffp-contract=off); DESIGN.md (f15) carries the formulas.
@@ -522,7 +522,7 @@ int sync_animation_mirrors(prosper_pt_ctx *ctx)
     return PROSPER_PT_OK;
 }
 
-// prosper_pt_animate up to the flush (prosper_pt.cpp): the time is staged and the instances it moves count as moved
+// prosper_pt_animate up to the flush (pt_scene_updates.cpp): the time is staged and the instances it moves count as moved
 int stage_animation(prosper_pt_ctx *ctx, float timeS)
 {
     AnimationState *an = ctx->animation;

@@ -1,4 +1,4 @@
-// pt_animation.hpp — what the scene update (prosper_pt.cpp flush_pending_update) and the readers of the host mirrors use
+// pt_animation.hpp — what the scene update (pt_scene_updates.cpp flush_pending_update) and the readers of the host mirrors use
 // of the keyframe animation (pt_animation.hip).  Private to the library's translation units.
 #pragma once
 

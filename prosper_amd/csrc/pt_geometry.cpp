@@ -14,6 +14,7 @@
 #include "pt_kernels.hpp"
 #include "pt_materials.hpp"
 #include "pt_scene.hpp"
+#include "pt_scene_updates.hpp"
 
 namespace ppt
 {
@@ -357,7 +358,7 @@ int install_device_build(prosper_pt_ctx *ctx, GeometryTarget &t, DeviceBuild &b)
     acc->lastCostRatio = 1.0f;
     acc->movedSinceBuild.assign(acc->ranges.size(), 0);
     // the host builder's subtrees and its copy of the triangles no longer describe the tree: its next build of any
-    // kind splits every instance again (prosper_pt.cpp rebuild_hierarchy_on_host, start_mesh_build)
+    // kind splits every instance again (pt_hierarchy.cpp build_on_host, start_mesh_build)
     acc->instanced = false;
     acc->foreignTree = true;
     acc->flatStale = true;

@@ -112,7 +112,4 @@ int start_mesh_build(prosper_pt_ctx *ctx, bool rebuild = false);
 // the finished build becomes the scene; wait: block until nothing handed over so far is outstanding
 int poll_mesh_build(prosper_pt_ctx *ctx, bool wait);
 
-// (prosper_pt.cpp) which instances moved, the table into pinned staging; nothing on the GPU
-int stage_transforms(prosper_pt_ctx *ctx, const prosper_ModelInstanceTransforms *transforms, uint32_t count);
-
 } // namespace ppt

@@ -18,6 +18,7 @@
 #include "pt_bc7_encode.hpp"
 #include "pt_kernels.hpp"
 #include "pt_pass_support.hpp"
+#include "pt_scene_updates.hpp"
 #include "pt_texture_mips.hpp"
 
 namespace ppt
@@ -316,8 +317,7 @@ int collect_retired(prosper_pt_ctx *ctx)
     ms->retired.clear();
     ms->retiredBytes = 0;
     // (the device is idle: the generations a geometry build replaced can go with their events and pinned staging)
-    for (AccelState *old : ctx->retiredAccel) delete old;
-    ctx->retiredAccel.clear();
+    delete_retired_accel(ctx);
     return PROSPER_PT_OK;
 }
 

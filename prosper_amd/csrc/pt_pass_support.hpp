@@ -1,5 +1,6 @@
-// pt_pass_support.hpp — what the pass modules (pt_gbuffer_passes.cpp and the others) share: what they use of the render
-// path in prosper_pt.cpp, and the one way in for a call's image inputs and out for its read-backs (pt_pass_support.cpp).
+// pt_pass_support.hpp — what the pass modules (pt_gbuffer_passes.cpp and the others) share: what they use of the scene's
+// updates (pt_scene_updates.cpp) and of the render path in prosper_pt.cpp, and the one way in for a call's image inputs and
+// out for its read-backs (pt_pass_support.cpp).
 // Private to the library's translation units.
 #pragma once
 

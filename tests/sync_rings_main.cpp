@@ -291,7 +291,7 @@ void test_staging_ring()
     CHECK(g_liveEvents.empty() && g_livePinned.empty());
 }
 
-// what flush_pending_lights does with its rings (prosper_amd/csrc/prosper_pt.cpp): commit after the last enqueue
+// what flush_pending_lights does with its rings (prosper_amd/csrc/pt_scene_updates.cpp): commit after the last enqueue
 struct Resource
 {
     VersionRing<3> versions;
